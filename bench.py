@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — similarity-pairs/sec of the fused similarity + per-row top-k (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the hot path over the whole synthetic workload: N = 262144 rows, d = 512,
@@ -10,16 +10,24 @@ With P ranks the N rows are sharded P ways (strong scaling: total work is fixed)
 exchange of the shards (multimodal-fusion_amd/distributed.py) and every rank scans all N columns for its rows.
 value = N*N pairs / max-over-ranks step time.  Inputs are resident in HBM before the timed region.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs is given and
+prints the line.  Extra objects on the JSON line:
   roofline       the scan kernel against the MFMA peak of the pipe it ran on (duration from HIP events recorded
-                 inside the library on the launch stream)
-  roofline_bf16  N = 1 only: the same workload once more with bf16 scan operands (MMF_PREC_FAST_BF16), untimed
-                 in `value` — north_star words its target on the bf16 pipe
-  cpu_baseline   the CPU oracle on a bounded sample of the same workload, rank 0, N = 1 only
+                 inside the library on the launch stream during the timed steps)
   per_rank       N > 1: [min, max] over ranks of the step and of its parts (exposed_comm_ms = what the scan stream
                  spent waiting for operand chunks to arrive)
-and in `config`: `driver` (which multi-GPU driver ran) and `self_check` (after the timed loop every rank re-computes
-256 of its rows through the single-call path on the gathered matrix and compares bit for bit; a mismatch exits 1).
+and in `config`: `driver` (which multi-GPU driver ran).
+--full adds what takes runs of its own:
+  roofline_bf16  N = 1 only: the same workload once more with bf16 scan operands (MMF_PREC_FAST_BF16), untimed
+                 in `value` — north_star words its target on the bf16 pipe (skip with --no-bf16-leg)
+  cpu_baseline   the CPU oracle on a bounded sample of the same workload, rank 0, N = 1 only (skip with --no-cpu-baseline)
+  config.self_check  N > 1: after the timed loop every rank re-computes 256 of its rows through the single-call path
+                 on the gathered matrix and compares bit for bit; a mismatch exits 1.
+
+--dump-outputs DIR: after the timed steps, the top-k the last timed step returned, gathered over ranks into the
+full [N, k] result: DIR/indices.npy (global column ids as float64, exact) and DIR/scores.npy (float32).  Above
+DUMP_LIMIT bytes a fixed, seeded sample of rows is written instead, and DIR/sample_rows.npy (float64) holds their ids.
+The inputs depend on the arguments only, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -37,6 +45,7 @@ SCAN_NAME = {1: "scan_f32 (v_mfma_f32_32x32x2_f32)", 2: "scan_b16x<f16> (v_mfma_
              3: "scan_b16x<bf16> (v_mfma_f32_16x16x32_bf16)"}
 DTYPE_NAME = {1: "f32", 2: "f16 MFMA scan + f32 exact re-rank", 3: "bf16 MFMA scan + f32 exact re-rank"}
 CLUSTERS, SIGMA = 2048, 0.03    # --data clustered: near-duplicate patches (what slide embeddings look like)
+DUMP_LIMIT = 60_000_000         # bytes of --dump-outputs arrays (headers aside); the default workload needs 15.7 MB
 
 
 def make_rows(lo: int, hi: int, d: int, device, block: int = 4096, data: str = "gaussian"):
@@ -88,6 +97,29 @@ def cpu_baseline(n: int, d: int, k: int, metric: str, device, data: str):
                       f"oracle/mmf_oracle.c with {threads} OpenMP threads, {dt:.1f} s"}
 
 
+def dump_outputs(dirname: str, idx, val, n: int, world: int, rank: int) -> None:
+    """--dump-outputs: write what the timed path returned (module docstring).  Every rank calls this (all-gather)."""
+    import numpy as np
+    import torch
+    if world > 1:
+        from importlib import import_module
+        dmod = import_module("multimodal_fusion_amd.distributed")
+        idx, val = dmod.all_gather_rows(idx, n), dmod.all_gather_rows(val, n)
+    if rank != 0:
+        return
+    rows = None
+    per_row = idx.shape[1] * (8 + 4) + 8
+    if idx.shape[0] * per_row > DUMP_LIMIT:
+        rows = np.sort(np.random.default_rng(0).choice(idx.shape[0], size=DUMP_LIMIT // per_row, replace=False))
+        sel = torch.from_numpy(rows).to(idx.device)
+        idx, val = idx.index_select(0, sel), val.index_select(0, sel)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "indices.npy"), idx.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirname, "scores.npy"), val.float().cpu().numpy().astype(np.float32))
+    if rows is not None:
+        np.save(os.path.join(dirname, "sample_rows.npy"), rows.astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -101,12 +133,18 @@ def main() -> None:
     ap.add_argument("--data", default="gaussian", choices=["gaussian", "clustered"])
     ap.add_argument("--query-order", default="auto", choices=["auto", "off", "on"],
                     help="order in which the scan takes the query rows (csrc/mmf_order.hip); auto = the library's own decision")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-bf16-leg", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the extras that take runs of their own: bf16 leg, CPU baseline, multi-rank self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's top-k to DIR/indices.npy and DIR/scores.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-bf16-leg", action="store_true", help="--full without the bf16 leg")
     ap.add_argument("--simple-driver", action="store_true", help="N > 1: one all-gather of the f32 shard, then one scan")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal of the multi-rank path on a box with fewer GPUs than ranks")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -164,6 +202,8 @@ def main() -> None:
         return time.perf_counter() - t0, per_step, out
 
     elapsed, per_step, (out_i, out_v) = timed(args.precision)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out_i, out_v, n, world, rank)
     stats = per_step[-1]
     mean = lambda key: sum(float(s.get(key, 0.0)) for s in per_step) / len(per_step)   # noqa: E731
     local_ms = [1e3 * elapsed / args.steps, mean("prep_ms"), mean("scan_ms"), mean("scan_wait_ms"), mean("rerank_ms"),
@@ -177,6 +217,10 @@ def main() -> None:
             dist.all_reduce(t, op=op)
             return [float(x) for x in t.tolist()]
         elapsed = reduce([elapsed], dist.ReduceOp.MAX)[0]
+        mn, mx = reduce(local_ms, dist.ReduceOp.MIN), reduce(local_ms, dist.ReduceOp.MAX)
+        names = ("step_ms", "prep_ms", "scan_ms", "exposed_comm_ms", "rerank_ms", "fallback_ms")
+        per_rank = {nm: [mn[j], mx[j]] for j, nm in enumerate(names)}
+    if world > 1 and args.full:
         # ---- self-check (untimed): 256 of this rank's rows through the single-call path on the gathered matrix ----
         full = dmod.all_gather_rows(x_local, n, None)
         nchk = min(256, hi - lo)
@@ -185,9 +229,6 @@ def main() -> None:
         good = bool(torch.equal(ci, out_i[:nchk])) and bool(torch.equal(cv, out_v[:nchk]))
         del full
         all_good = reduce([1.0 if good else 0.0], dist.ReduceOp.MIN)[0] == 1.0
-        mn, mx = reduce(local_ms, dist.ReduceOp.MIN), reduce(local_ms, dist.ReduceOp.MAX)
-        names = ("step_ms", "prep_ms", "scan_ms", "exposed_comm_ms", "rerank_ms", "fallback_ms")
-        per_rank = {nm: [mn[j], mx[j]] for j, nm in enumerate(names)}
         check = {"rows_per_rank": nchk, "ok": all_good,
                  "against": "mmf_simtopk(full[lo:lo+256], full, row_offset=lo), indices and scores bit for bit"}
         if not good:
@@ -240,11 +281,12 @@ def main() -> None:
                        "query_order": bool(stats.get("query_order", 0)), "near_duplicate_rows_estimate": stats.get("near_rows", -1)},
             "roofline": roof,
         }
+        if per_rank is not None:
+            line["per_rank"] = per_rank
         if check is not None:
             line["config"]["self_check"] = check
-            line["per_rank"] = per_rank
         print_line = line
-    if world == 1 and not args.no_bf16_leg and args.precision in ("auto", "fast"):
+    if world == 1 and args.full and not args.no_bf16_leg and args.precision in ("auto", "fast"):
         _, per_step_b, _ = timed("fast_bf16")
         stb = per_step_b[-1]
         if stb["precision_used"] == 3:
@@ -253,7 +295,7 @@ def main() -> None:
                        "note": "same workload with bf16 scan operands, separate untimed-in-value leg"})
             print_line["roofline_bf16"] = rb
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             print_line["cpu_baseline"] = cpu_baseline(n, d, k, args.metric, device, args.data)
         print(json.dumps(print_line), flush=True)
     bad = check is not None and not check["ok"]

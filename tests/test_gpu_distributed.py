@@ -56,11 +56,11 @@ def test_rccl_code_path_with_one_rank():
     assert "chunks=4 rep=1: panels=4" in out.stdout, tail
 
 
-def test_bench_two_ranks_is_self_checking():
-    """bench.py --gpus 2 through gloo: one JSON line that names the driver, carries per-rank timing spread and
+def test_bench_two_ranks_is_self_checking(tmp_path):
+    """bench.py --gpus 2 --full through gloo: one JSON line that names the driver, carries per-rank timing spread and
     the result of its own bit-for-bit re-check of 256 rows per rank against the single-call path."""
     out = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--rows", "32768",
-                        "--steps", "2", "--warmup", "1"])
+                        "--steps", "2", "--warmup", "1", "--full", "--dump-outputs", str(tmp_path)])
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -72,3 +72,9 @@ def test_bench_two_ranks_is_self_checking():
     for key in ("step_ms", "prep_ms", "scan_ms", "exposed_comm_ms", "rerank_ms", "fallback_ms"):
         assert len(pr[key]) == 2 and pr[key][0] <= pr[key][1], key
     assert abs(d["value"] - 32768.0 * 32768.0 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    # --dump-outputs gathers both ranks' shards into the full result
+    import numpy as np
+    idx, val = np.load(tmp_path / "indices.npy"), np.load(tmp_path / "scores.npy")
+    assert idx.dtype == np.float64 and val.dtype == np.float32 and idx.shape == val.shape == (32768, 5)
+    assert idx.min() >= 0 and idx.max() < 32768 and not (idx == np.arange(32768)[:, None]).any()
+    assert np.isfinite(val).all() and (np.diff(val, axis=1) <= 0).all()
