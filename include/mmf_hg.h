@@ -148,6 +148,28 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
                    int device_id, void* hip_stream);
 
 /*
+ * Per-segment fused similarity + top-k (block-diagonal k-NN over a ragged batch, e.g. one patch graph per slide).
+ * Query rows [x_ptr[s], x_ptr[s+1]) of X are ranked only against candidate rows [y_ptr[s], y_ptr[s+1]) of Y
+ * (Y == NULL: Y = X, y_ptr = x_ptr, exclude_self as in mmf_simtopk).  No reference counterpart (the reference loops over
+ * slides: process_dataset, batch_rebuild_hypergraph).
+ * x_ptr_host / y_ptr_host: HOST int64 arrays of n_segments + 1 offsets, x_ptr[0] = 0, x_ptr[S] = n, non-decreasing
+ * (same for y_ptr with m).  Empty segments are allowed.
+ * out_idx [n,k]: GLOBAL row ids of Y, sorted (key desc, id asc) exactly as mmf_simtopk.
+ * A row whose segment has fewer than k admissible columns gets them first, then id -1 / value -inf.
+ * k + self > 44 -> MMF_E_UNSUPPORTED (multi-pass large k is out of scope here).
+ * Results are bit-identical to calling mmf_simtopk_ex on each segment with row_offset = x_ptr[s],
+ * col_offset = y_ptr[s] (whenever that segment has >= k admissible columns).
+ * opts->precision as in mmf_simtopk_ex; opts->query_order is ignored; col_splits / select_wait_event must be 0 / NULL
+ * (MMF_E_UNSUPPORTED otherwise).  Host-synchronous: once, plus once more when some rows need the exact pass.
+ */
+int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, int64_t d,
+                          int in_dtype, int metric, float lambda, int k, int exclude_self,
+                          const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_segments,
+                          int64_t* out_idx, float* out_val,
+                          const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats,
+                          int device_id, void* hip_stream);
+
+/*
  * Phase API of the fast path, for the row-sharded multi-GPU driver: every rank prepares
  * the 16-bit operands of ITS rows once, ranks exchange them (half the bytes of the f32 rows), and the
  * scan runs on prepared operands while the f32 rows — needed only by the exact re-rank — are still

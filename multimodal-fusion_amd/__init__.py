@@ -4,12 +4,13 @@ The directory name carries a hyphen (it mirrors the reference repo's name), so i
 shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
 
     mmf.ops.simtopk(...)                          fused similarity + top-k on gfx950
+    mmf.ops.simtopk_segmented(..., ptr=/batch=)   the same per segment of a ragged batch (one graph per slide)
     mmf.build_hypergraph.*                        the reference's function names and signatures
     mmf.distributed.sharded_simtopk(...)          row-sharded multi-GPU driver (RCCL all-gather)
 """
 from . import _lib, ops  # noqa: F401
 from .ops import (edge_cosine, offdiag_lower_median, sim_dense, sim_dense_combined, simtopk,  # noqa: F401
-                  threshold_edges, topk_merge)
+                  simtopk_segmented, threshold_edges, topk_merge)
 
-__all__ = ["ops", "simtopk", "sim_dense", "sim_dense_combined", "edge_cosine", "topk_merge",
+__all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combined", "edge_cosine", "topk_merge",
            "offdiag_lower_median", "threshold_edges"]

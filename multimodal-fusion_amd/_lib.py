@@ -47,7 +47,7 @@ class SimtopkStats(ctypes.Structure):
 _lib = None
 
 EXPORTS = ["mmf_version", "mmf_last_error", "mmf_simtopk", "mmf_simtopk_ex", "mmf_row_scalars", "mmf_prep_rows",
-           "mmf_simtopk_prepared", "mmf_simtopk_panels", "mmf_padded_dim", "mmf_fast_scan_supported", "mmf_topk_merge", "mmf_edge_cosine",
+           "mmf_simtopk_prepared", "mmf_simtopk_panels", "mmf_simtopk_segmented", "mmf_padded_dim", "mmf_fast_scan_supported", "mmf_topk_merge", "mmf_edge_cosine",
            "mmf_sim_dense", "mmf_sim_dense_stats", "mmf_sim_dense_combined", "mmf_offdiag_lower_median", "mmf_threshold_edges", "mmf_threshold_edges_count", "mmf_threshold_edges_fill", "mmf_lower_median", "mmf_array_stats",
            "mmf_segment_sort", "mmf_segment_mean", "mmf_segment_offdiag_mean", "mmf_clique_pairs", "mmf_knn_pairs", "mmf_kmeans_fit", "mmf_combined_offdiag_median", "mmf_combined_threshold_edges",
            "mmf_release_workspaces", "mmf_debug_query_order"]
@@ -78,6 +78,8 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_panels.argtypes = [vp, i64, vp, i64, i64, ci, ci, f32, ci, ci, i64, i64,
                                      ctypes.POINTER(PreparedSide), vp, ctypes.POINTER(Panel), ci, vp, ci, vp, vp,
                                      ctypes.POINTER(SimtopkOpts), ctypes.POINTER(SimtopkStats), ci, vp]
+    L.mmf_simtopk_segmented.argtypes = [vp, i64, vp, i64, i64, ci, ci, f32, ci, ci, vp, vp, i64, vp, vp,
+                                        ctypes.POINTER(SimtopkOpts), ctypes.POINTER(SimtopkStats), ci, vp]
     L.mmf_topk_merge.argtypes = [vp, vp, vp, vp, i64, ci, vp, vp, ci, vp]
     L.mmf_edge_cosine.argtypes = [vp, i64, i64, ci, vp, i64, vp, ci, vp]
     L.mmf_sim_dense.argtypes = [vp, i64, vp, i64, i64, ci, ci, f32, vp, ci, vp]

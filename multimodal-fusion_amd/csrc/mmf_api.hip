@@ -3,6 +3,7 @@
 #include <stdarg.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -73,6 +74,14 @@ int launch_scan_b16_audit(const ScanB16Panel& pn, uint32_t* overflow, int64_t n_
 size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap);
 int scan_bf16_slot_ulp(int cap);
 int scan_b16_queries_per_block(int dp);
+int launch_prep_half_gather(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
+                            const uint32_t* max_n, const int32_t* gather, void* Z, int64_t n_pos, int64_t n_pad, int dp,
+                            int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima, hipStream_t s);
+size_t scan_b16_seg_scratch_bytes(int64_t grid, int dp, int cap);
+int launch_scan_b16_seg(const void* ZQ, const void* ZC, const float* cb, const float* q_zn, const float* q_rn,
+                        const float* q_un, const uint32_t* maxima, const int32_t* sched, int64_t grid, int64_t n_rows,
+                        int64_t m, int dp, int64_t d, bool f16, int metric, int kk, const CandLists& L, void* scratch,
+                        const ScanB16Panel& pn, hipStream_t s);
 
 static int check_common(const void* X, int64_t n, int64_t m, int64_t d, int in_dtype, int device_id) {
   if (device_id < 0) {
@@ -1210,5 +1219,350 @@ int mmf_combined_threshold_edges(const float* F, const float* P, int64_t n, int6
   }
   return MMF_OK;
 }
+
+// ---- segmented simtopk (block-diagonal k-NN over a ragged batch) ------------------------------------------------
+// DESIGN.md §4.7.  One call: row scalars, a segment-padded 16-bit image of each side (gathered prep), ONE scan launch
+// driven by a host-built work table (a workgroup = one row block of one segment against that segment's tiles), the
+// audit and the exact re-rank over all rows, then one host synchronisation.  Rows the 16-bit path cannot certify, and
+// every row of a segment with fewer than k admissible columns (or of every segment under MMF_PREC_EXACT), go through the
+// exact f32 scan segment by segment: two launches per segment, not a work table ("Exact rows").
+int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
+                          float lambda, int k, int exclude_self, const int64_t* x_ptr_host, const int64_t* y_ptr_host,
+                          int64_t n_segments, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
+                          mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  const bool self = (Y == nullptr);
+  if (self) { Y = X; m = n; y_ptr_host = x_ptr_host; }
+  MMF_TRY(check_common(X, n, m, d, in_dtype, device_id));
+  if (metric < MMF_DOT || metric > MMF_RBF) { set_error("simtopk_segmented: bad metric %d", metric); return MMF_E_INVALID; }
+  if (metric == MMF_RBF && !(lambda > 0.0f)) { set_error("simtopk_segmented: MMF_RBF needs lambda > 0 (got %g)", lambda); return MMF_E_INVALID; }
+  if (k < 1) { set_error("simtopk_segmented: k must be >= 1 (got %d)", k); return MMF_E_INVALID; }
+  if (n_segments < 0 || !x_ptr_host || !y_ptr_host) { set_error("simtopk_segmented: bad segment offsets"); return MMF_E_INVALID; }
+  if (x_ptr_host[0] != 0 || x_ptr_host[n_segments] != n || y_ptr_host[0] != 0 || y_ptr_host[n_segments] != m) {
+    set_error("simtopk_segmented: offsets must start at 0 and end at n = %lld / m = %lld", (long long)n, (long long)m);
+    return MMF_E_INVALID;
+  }
+  for (int64_t g = 0; g < n_segments; ++g)
+    if (x_ptr_host[g + 1] < x_ptr_host[g] || y_ptr_host[g + 1] < y_ptr_host[g]) {
+      set_error("simtopk_segmented: offsets must be non-decreasing (segment %lld)", (long long)g);
+      return MMF_E_INVALID;
+    }
+  if (m > 0 && !Y) { set_error("simtopk_segmented: Y is NULL"); return MMF_E_INVALID; }
+  const int self1 = exclude_self ? 1 : 0;
+  const int kk = k + self1;
+  if (kk > 44) { set_error("simtopk_segmented: k + self = %d > 44 is not supported", kk); return MMF_E_UNSUPPORTED; }
+  if (opts && (opts->col_splits != 0 || opts->select_wait_event)) {
+    set_error("simtopk_segmented: col_splits and select_wait_event are not supported");
+    return MMF_E_UNSUPPORTED;
+  }
+  if (stats) { memset(stats, 0, sizeof(*stats)); stats->near_rows = -1; }
+  if (n == 0) return MMF_OK;
+  if (!out_idx || !out_val) { set_error("simtopk_segmented: NULL output"); return MMF_E_INVALID; }
+  int precision = opts ? opts->precision : MMF_PREC_AUTO;
+  const bool profile = opts && opts->profile;
+  if (precision == MMF_PREC_AUTO) precision = scan_bf16_supported(d, kk, in_dtype) ? MMF_PREC_FAST : MMF_PREC_EXACT;
+  if (precision != MMF_PREC_EXACT && precision != MMF_PREC_FAST && precision != MMF_PREC_FAST_BF16) {
+    set_error("simtopk_segmented: bad precision %d", precision);
+    return MMF_E_INVALID;
+  }
+  if (precision != MMF_PREC_EXACT && !scan_bf16_supported(d, kk, in_dtype)) {
+    set_error("simtopk_segmented: MMF_PREC_FAST does not support d = %lld, k = %d (use AUTO or EXACT)", (long long)d, k);
+    return MMF_E_UNSUPPORTED;
+  }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  const int64_t S = n_segments;
+  const int64_t* xp = x_ptr_host;
+  const int64_t* yp = y_ptr_host;
+  // admissible columns of segment g: its m_g columns, minus one when a row's own id may lie among them
+  std::vector<int64_t> adm(S);
+  for (int64_t g = 0; g < S; ++g) {
+    const bool overlap = exclude_self && xp[g] < yp[g + 1] && xp[g + 1] > yp[g];
+    adm[g] = (yp[g + 1] - yp[g]) - (overlap ? 1 : 0);
+  }
+  const size_t esz = dtype_size(in_dtype);
+  const bool fast = precision != MMF_PREC_EXACT;
+  const int dp = fast ? scan_bf16_dp(d) : 0;
+  const int qt = fast ? scan_b16_queries_per_block(dp) : 1;
+  constexpr int kTile = 32;                       // candidate rows per tile of the 16-bit scan (B_CT)
+  constexpr int kSpillCap = FastTail::kSpillCap;
+  // segments the 16-bit scan serves: rows present and at least k admissible columns (the others are done exactly)
+  std::vector<char> on_fast(S, 0);
+  int64_t nq_pos = 0, mc_pos = 0;
+  std::vector<int32_t> sched;
+  if (fast) {
+    for (int64_t g = 0; g < S; ++g) {
+      const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g];
+      if (ng == 0 || adm[g] < k) continue;
+      const int64_t tiles = (mg + kTile - 1) / kTile;
+      if (tiles * kTile * (int64_t)dp * 2 >= (int64_t(1) << 32)) {   // 32-bit offsets of the tile DMA
+        set_error("simtopk_segmented: segment %lld has %lld candidate rows, over 4 GiB of 16-bit operands", (long long)g, (long long)mg);
+        return MMF_E_UNSUPPORTED;
+      }
+      on_fast[g] = 1;
+      const int64_t t0 = mc_pos / kTile;
+      for (int64_t b = 0; b < ng; b += qt) {
+        const int32_t e[8] = {(int32_t)(nq_pos + b), (int32_t)(xp[g] + b), (int32_t)(ng - b < qt ? ng - b : qt), (int32_t)t0,
+                              (int32_t)(t0 + tiles), (int32_t)(uint32_t)(yp[g] - t0 * kTile), 0, 0};
+        sched.insert(sched.end(), e, e + 8);
+      }
+      nq_pos += (ng + qt - 1) / qt * qt;
+      mc_pos += tiles * kTile;
+    }
+    if (nq_pos >= (int64_t(1) << 31) || mc_pos >= (int64_t(1) << 31)) { set_error("simtopk_segmented: padded images too large"); return MMF_E_UNSUPPORTED; }
+  }
+  const int64_t grid = (int64_t)sched.size() / 8;
+  std::vector<int32_t> qgather(nq_pos, -1), cgather(mc_pos, -1);
+  {
+    int64_t qpos = 0, cpos = 0;
+    for (int64_t g = 0; g < S && grid > 0; ++g) {
+      if (!on_fast[g]) continue;
+      const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g];
+      for (int64_t i = 0; i < ng; ++i) qgather[qpos + i] = (int32_t)(xp[g] + i);
+      for (int64_t j = 0; j < mg; ++j) cgather[cpos + j] = (int32_t)(yp[g] + j);
+      qpos += (ng + qt - 1) / qt * qt;
+      cpos += (mg + kTile - 1) / kTile * kTile;
+    }
+  }
+
+  // ---- workspace (slot 0): row scalars, the 16-bit images, tables, lists -------------------------------------------
+  const int64_t nq_pad = (nq_pos + 255) / 256 * 256, mc_pad = (mc_pos + 255) / 256 * 256;
+  const int bcap = fast ? scan_bf16_cap(kk, dp) : 0;
+  const int64_t n_seed = n;
+  size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + ws_bytes(n, 4) + ws_bytes(4, 4) + ws_bytes(256, 4);
+  if (grid > 0)
+    need += ws_bytes((size_t)nq_pad * dp, 2) + 4 * ws_bytes(nq_pad, 4) + ws_bytes((size_t)mc_pad * dp, 2) + 4 * ws_bytes(mc_pad, 4) +
+            3 * ws_bytes(4, 4) + ws_bytes(sched.size(), 4) + ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + ws_bytes((size_t)n * 2, 4) +
+            ws_bytes((size_t)n * 2 * bcap, 4) + 2 * ws_bytes(n, 4) + ws_bytes((size_t)n * kSpillCap, 4) +
+            ws_bytes(scan_b16_seg_scratch_bytes(grid, dp, bcap), 1) + ws_bytes(2 * (size_t)n_seed, 4) + ws_bytes(select_order_bytes(n), 1);
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, need, &ws));
+  float* rx = ws.take<float>(n);
+  float* cy = self ? rx : ws.take<float>(m);
+  int32_t* fail_rows = ws.take<int32_t>(n);
+  uint32_t* fail_count = ws.take<uint32_t>(4);
+  uint32_t* cand_total = ws.take<uint32_t>(256);
+  MMF_HIP(hipMemsetAsync(fail_count, 0, 16, s));
+  MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
+
+  EventTimer t_prep, t_scan, t_sel, t_fb;
+  MMF_TRY(t_prep.start(profile, s));
+  uint32_t* max_n = nullptr;
+  if (grid > 0) { max_n = ws.take<uint32_t>(4); MMF_HIP(hipMemsetAsync(max_n, 0, 16, s)); }
+  MMF_TRY(launch_row_scalars(X, n, d, in_dtype, metric, rx, max_n, s));
+  if (!self && m > 0) MMF_TRY(launch_row_scalars(Y, m, d, in_dtype, metric, cy, max_n, s));
+
+  uint32_t h_fail4[4] = {0, 0, 0, 0};
+  std::vector<int32_t> h_fail_rows;
+  std::vector<uint32_t> h_tot(stats ? 256 : 0);
+  if (grid > 0) {
+    const bool f16 = (precision == MMF_PREC_FAST);
+    uint16_t* ZQ = ws.take<uint16_t>((size_t)nq_pad * dp);
+    float *q_zn = ws.take<float>(nq_pad), *q_rn = ws.take<float>(nq_pad), *q_un = ws.take<float>(nq_pad), *q_cb = ws.take<float>(nq_pad);
+    uint16_t* ZC = ws.take<uint16_t>((size_t)mc_pad * dp);
+    float *c_zn = ws.take<float>(mc_pad), *c_rn = ws.take<float>(mc_pad), *c_un = ws.take<float>(mc_pad), *c_cb = ws.take<float>(mc_pad);
+    uint32_t *max_q = ws.take<uint32_t>(4), *max_c = ws.take<uint32_t>(4);
+    int32_t* d_sched = ws.take<int32_t>(sched.size());
+    int32_t* d_qg = ws.take<int32_t>(nq_pos);
+    int32_t* d_cg = ws.take<int32_t>(mc_pos);
+    CandLists L;
+    L.cnt = ws.take<uint32_t>((size_t)n * 2);
+    L.ids = ws.take<uint32_t>((size_t)n * 2 * bcap);
+    L.keys = nullptr; L.margin = nullptr;   // one list pair per row: nothing to prune against
+    L.overflow = ws.take<uint32_t>(n);
+    L.lists = 2; L.cap = bcap; L.slot_ulp = scan_bf16_slot_ulp(bcap);
+    L.spill_cnt = ws.take<uint32_t>(n);
+    L.spill_ids = ws.take<uint32_t>((size_t)n * kSpillCap);
+    L.spill_cap = kSpillCap;
+    L.spill_stacks = getenv("MMF_SPILL_COUNTER") ? 0 : 1;
+    char* scan_scratch = ws.take<char>(scan_b16_seg_scratch_bytes(grid, dp, bcap));
+    int32_t* seed = ws.take<int32_t>(2 * (size_t)n_seed);
+    char* order_scratch = ws.take<char>(select_order_bytes(n));
+    MMF_HIP(hipMemcpyAsync(d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice, s));
+    MMF_HIP(hipMemcpyAsync(d_qg, qgather.data(), (size_t)nq_pos * 4, hipMemcpyHostToDevice, s));
+    MMF_HIP(hipMemcpyAsync(d_cg, cgather.data(), (size_t)mc_pos * 4, hipMemcpyHostToDevice, s));
+    MMF_HIP(hipMemsetAsync(max_q, 0, 16, s));
+    MMF_HIP(hipMemsetAsync(max_c, 0, 16, s));
+    MMF_TRY(launch_prep_half_gather(Y, m, d, in_dtype, metric, cy, max_n, d_cg, ZC, mc_pos, mc_pad, dp, f16 ? 1 : 0, c_zn, c_rn,
+                                    c_un, c_cb, max_c, s));
+    MMF_TRY(launch_prep_half_gather(X, n, d, in_dtype, metric, rx, max_n, d_qg, ZQ, nq_pos, nq_pad, dp, f16 ? 1 : 0, q_zn, q_rn,
+                                    q_un, q_cb, max_q, s));
+    MMF_TRY(t_prep.stop(s));
+
+    // rows of segments the scan does not serve keep empty lists: the re-rank reports them, the exact pass below redoes them
+    MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * 2 * 4, s));
+    MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
+    MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
+    MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n_seed * 8, s));
+    ScanB16Panel pn;
+    pn.seed = seed; pn.seed_stride = n_seed; pn.share = 0;
+    MMF_TRY(t_scan.start(profile, s));
+    MMF_TRY(launch_scan_b16_seg(ZQ, ZC, c_cb, q_zn, q_rn, q_un, max_c, d_sched, grid, n, m, dp, d, f16, metric, kk, L,
+                                scan_scratch, pn, s));
+    MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
+    MMF_TRY(t_scan.stop(s));
+
+    SelectProblem q{};
+    q.X = X; q.n = n; q.Y = Y; q.m = m; q.d = d; q.dtype = in_dtype; q.metric = metric; q.lambda = lambda;
+    q.k = k; q.exclude_self = exclude_self; q.row_offset = 0; q.col_offset = 0;
+    q.rx = rx; q.cy = cy; q.row_ids = nullptr; q.n_rows = n; q.out_idx = out_idx; q.out_val = out_val;
+    q.fail_rows = fail_rows; q.fail_count = fail_count; q.cand_total = stats ? cand_total : nullptr;
+    q.two_pass = true;
+    q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
+    MMF_TRY(t_sel.start(profile, s));
+    MMF_TRY(launch_select(q, L, s));
+    MMF_TRY(t_sel.stop(s));
+    MMF_HIP(hipMemcpyAsync(h_fail4, fail_count, 16, hipMemcpyDeviceToHost, s));
+    if (stats) MMF_HIP(hipMemcpyAsync(h_tot.data(), cand_total, 1024, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    h_fail_rows.resize(h_fail4[0]);
+    if (h_fail4[0] > 0) MMF_HIP(hipMemcpy(h_fail_rows.data(), fail_rows, (size_t)h_fail4[0] * 4, hipMemcpyDeviceToHost));
+  } else {
+    MMF_TRY(t_prep.stop(s));
+  }
+
+  // ---- exact f32 pass: per segment, the rows the scan did not certify or did not serve ------------------------------
+  // Two launches (scan, re-rank) per group, one group per segment: whole segments (short of admissible columns, or every
+  // segment under MMF_PREC_EXACT) as slices of X, Y and their f32 images; rows the 16-bit path flagged gathered, in pieces
+  // and batches of at most kFB rows (the f32 image of a batch is all that is prepared at once).
+  struct Group { int64_t seg, off, cnt; int ks; bool whole; };
+  constexpr int64_t kFB = 4096;
+  std::vector<int32_t> ex_rows;         // flagged rows, grouped by segment, ascending
+  std::vector<Group> groups;
+  int64_t fallback_rows = 0;
+  bool any_whole = false;
+  {
+    std::vector<std::vector<int32_t>> flagged(fast ? S : 0);
+    for (int32_t r : h_fail_rows) {
+      const int64_t g = (int64_t)(std::upper_bound(xp, xp + S + 1, (int64_t)r) - xp) - 1;
+      if (g >= 0 && g < S && on_fast[g]) { flagged[g].push_back(r); ++fallback_rows; }
+    }
+    for (int64_t g = 0; g < S; ++g) {
+      const int64_t ng = xp[g + 1] - xp[g];
+      if (ng == 0) continue;
+      if (!on_fast[g]) {
+        int ks = k;
+        if (adm[g] < k) {   // a segment short of admissible columns: its top-(m_g - self) first, then -1 / -inf
+          MMF_HIP(hipMemsetAsync(out_idx + xp[g] * k, 0xff, (size_t)ng * k * 8, s));
+          MMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out_val + xp[g] * k), (int)0xff800000u, (size_t)ng * k, s));
+          ks = (int)(adm[g] > 0 ? adm[g] : 0);
+        }
+        if (ks == 0) continue;
+        groups.push_back(Group{g, xp[g], ng, ks, true});
+        any_whole = true;
+      } else if (!flagged[g].empty()) {
+        std::sort(flagged[g].begin(), flagged[g].end());
+        for (size_t i = 0; i < flagged[g].size(); i += kFB) {
+          const int64_t off = (int64_t)ex_rows.size();
+          const size_t e = std::min(flagged[g].size(), i + (size_t)kFB);
+          ex_rows.insert(ex_rows.end(), flagged[g].begin() + i, flagged[g].begin() + e);
+          groups.push_back(Group{g, off, (int64_t)(e - i), k, false});
+        }
+      }
+    }
+  }
+  MMF_TRY(t_fb.start(profile && !groups.empty(), s));
+  int ex_grid = 0;
+  if (!groups.empty()) {
+    const int64_t E = (int64_t)ex_rows.size();
+    const int64_t XB = E < kFB ? E : kFB;       // rows of the gathered image
+    const int cap_max = scan_f32_cap(kk);
+    if (cap_max == 0) { set_error("simtopk_segmented: no list capacity for k = %d (internal)", k); return MMF_E_INTERNAL; }
+    size_t list_words = 0;
+    std::vector<int> g_splits(groups.size());
+    int64_t rows_total = 0;
+    for (size_t i = 0; i < groups.size(); ++i) {
+      const Group& G = groups[i];
+      const int64_t mg = yp[G.seg + 1] - yp[G.seg];
+      g_splits[i] = pick_splits((G.cnt + 127) / 128, (mg + 127) / 128, 0, cap_max, 0);
+      list_words = std::max(list_words, (size_t)G.cnt * 2 * g_splits[i]);
+      rows_total += G.cnt;
+    }
+    // f32 images: all of Y; all of X for whole segments (self: the same image); the gathered batch of flagged rows
+    const bool own_x = any_whole && !self;
+    int dev_now = 0;
+    MMF_HIP(hipGetDevice(&dev_now));
+    Workspace aux;
+    MMF_TRY(get_workspace_slot(dev_now, s, 1,
+                               ws_bytes(prep_f32_bytes(m, d), 1) + (own_x ? ws_bytes(prep_f32_bytes(n, d), 1) : 0) +
+                                   (XB > 0 ? ws_bytes(prep_f32_bytes(XB, d), 1) : 0) + ws_bytes(E, 4) + ws_bytes(list_words, 4) +
+                                   ws_bytes(list_words * cap_max, 4) + ws_bytes(rows_total, 4) + ws_bytes(4, 4) + ws_bytes(rows_total, 4),
+                               &aux));
+    float* Yp = reinterpret_cast<float*>(aux.take<char>(prep_f32_bytes(m, d)));
+    float* Xp = self ? Yp : (own_x ? reinterpret_cast<float*>(aux.take<char>(prep_f32_bytes(n, d))) : nullptr);
+    float* Xe = XB > 0 ? reinterpret_cast<float*>(aux.take<char>(prep_f32_bytes(XB, d))) : nullptr;
+    int32_t* d_rows = aux.take<int32_t>(E);
+    CandLists FL;
+    FL.cnt = aux.take<uint32_t>(list_words);
+    FL.ids = aux.take<uint32_t>(list_words * cap_max);
+    uint32_t* overflow = aux.take<uint32_t>(rows_total);   // one slice per group: a single memset
+    uint32_t* ex_fail_count = aux.take<uint32_t>(4);
+    int32_t* ex_fail_rows = aux.take<int32_t>(rows_total);
+    if (E > 0) MMF_HIP(hipMemcpyAsync(d_rows, ex_rows.data(), (size_t)E * 4, hipMemcpyHostToDevice, s));
+    MMF_HIP(hipMemsetAsync(ex_fail_count, 0, 16, s));
+    MMF_HIP(hipMemsetAsync(overflow, 0, (size_t)rows_total * 4, s));
+    MMF_TRY(launch_prep_f32(Y, m, d, in_dtype, nullptr, Yp, s));
+    if (own_x) MMF_TRY(launch_prep_f32(X, n, d, in_dtype, nullptr, Xp, s));
+    const int64_t dpad = prep_f32_dim(d);
+    int64_t batch0 = -1, ov = 0;                  // first flagged position of the batch in Xe
+    for (size_t i = 0; i < groups.size(); ++i) {
+      const Group& G = groups[i];
+      const int64_t y0 = yp[G.seg], mg = yp[G.seg + 1] - y0;
+      if (!G.whole && (batch0 < 0 || G.off + G.cnt > batch0 + kFB)) {   // next batch of flagged rows
+        batch0 = G.off;
+        MMF_TRY(launch_prep_f32(X, std::min(kFB, E - batch0), d, in_dtype, d_rows + batch0, Xe, s));
+      }
+      FL.lists = 2 * g_splits[i];
+      FL.cap = scan_f32_cap(G.ks + self1);
+      FL.overflow = overflow + ov;
+      ov += G.cnt;
+      const char* Xs = static_cast<const char*>(X) + (G.whole ? (size_t)G.off * d * esz : 0);
+      const int64_t r0 = G.whole ? G.off : 0;    // whole segments: X, its scalars and the outputs as slices
+      ScanProblem sp{};
+      sp.X = Xs; sp.n = G.whole ? G.cnt : n; sp.Y = static_cast<const char*>(Y) + (size_t)y0 * d * esz; sp.m = mg; sp.d = d;
+      sp.dtype = in_dtype; sp.metric = metric; sp.lambda = lambda;
+      sp.Xp = G.whole ? Xp + G.off * dpad : Xe + (G.off - batch0) * dpad; sp.Yp = Yp + y0 * dpad;
+      sp.kk = G.ks + self1; sp.rx = rx + r0; sp.cy = cy + y0;
+      sp.row_ids = G.whole ? nullptr : d_rows + G.off; sp.n_rows = G.cnt;
+      sp.col_splits = g_splits[i];
+      int gg = 0;
+      MMF_TRY(launch_scan_f32(sp, FL, s, &gg));
+      ex_grid += gg;
+      SelectProblem fq{};
+      fq.X = Xs; fq.n = sp.n; fq.Y = sp.Y; fq.m = mg; fq.d = d; fq.dtype = in_dtype; fq.metric = metric; fq.lambda = lambda;
+      fq.k = G.ks; fq.exclude_self = exclude_self; fq.row_offset = r0; fq.col_offset = y0;
+      fq.rx = sp.rx; fq.cy = sp.cy; fq.row_ids = sp.row_ids; fq.n_rows = G.cnt;
+      fq.out_idx = out_idx + r0 * k; fq.out_val = out_val + r0 * k; fq.out_stride = k; fq.out_off = 0;
+      fq.fail_rows = ex_fail_rows; fq.fail_count = ex_fail_count; fq.cand_total = nullptr;
+      MMF_TRY(launch_select(fq, FL, s));
+    }
+    uint32_t h_ex = 0;
+    MMF_HIP(hipMemcpyAsync(&h_ex, ex_fail_count, 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    if (h_ex != 0) {
+      set_error("simtopk_segmented: %u rows failed in the exact scan (internal invariant)", h_ex);
+      return MMF_E_INTERNAL;
+    }
+  }
+  MMF_TRY(t_fb.stop(s));
+  MMF_HIP(hipStreamSynchronize(s));
+  if (stats) {
+    stats->precision_used = grid > 0 ? precision : MMF_PREC_EXACT;
+    stats->col_splits = 1;
+    stats->scan_grid = grid > 0 ? (int)grid : ex_grid;
+    stats->prep_ms = t_prep.ms();
+    stats->scan_ms = grid > 0 ? t_scan.ms() : t_fb.ms();
+    stats->rerank_ms = t_sel.ms();
+    stats->fallback_ms = grid > 0 ? t_fb.ms() : 0.f;
+    stats->fallback_rows = fallback_rows;
+    stats->overflow_rows = h_fail4[1] < (uint32_t)fallback_rows ? h_fail4[1] : fallback_rows;
+    stats->short_rows = fallback_rows - stats->overflow_rows;
+    int64_t tot = 0;
+    for (uint32_t v : h_tot) tot += v;
+    stats->candidates = tot;
+  }
+  return MMF_OK;
+}
+
 
 }  // extern "C"

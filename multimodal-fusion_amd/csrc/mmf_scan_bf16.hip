@@ -64,6 +64,7 @@ struct PrepArgs {
   void* Z; int64_t n_pad; int dp; int z_f16;
   float* zn; float* rn; float* un; float* cb;
   uint32_t* maxima;         // [4] float bits: max zn, max rn, max un, max |cb|
+  const int32_t* gather;    // optional: position -> row of X (-1 = padding row); n counts positions, scal is indexed by row
 };
 
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
@@ -95,12 +96,13 @@ __global__ __launch_bounds__(256) void prep_half_kernel(PrepArgs a) {
   const int64_t nwaves = (int64_t)gridDim.x * 4;
   for (int64_t row = wave0; row < a.n_pad; row += nwaves) {
     uint16_t* zrow = reinterpret_cast<uint16_t*>(a.Z) + row * a.dp;
-    if (row >= a.n) {  // padding rows: zeros, bias -inf so they can never be candidates
+    const int64_t src = (row < a.n && a.gather) ? (int64_t)a.gather[row] : row;
+    if (row >= a.n || src < 0) {  // padding rows: zeros, bias -inf so they can never be candidates
       for (int k = lane; k < a.dp; k += 64) zrow[k] = 0;
       if (lane == 0) { a.zn[row] = 0.f; a.rn[row] = 0.f; a.un[row] = 0.f; a.cb[row] = kNegInf; }
       continue;
     }
-    const float sc = a.scal[row];
+    const float sc = a.scal[src];
     float s_z = 0.f, s_r = 0.f, s_u = 0.f;
     const bool vec = (a.dtype == MMF_F32) && ((a.d & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.X) & 15) == 0);
     const bool vec16 = (a.dtype != MMF_F32) && ((a.d & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.X) & 7) == 0);
@@ -108,12 +110,12 @@ __global__ __launch_bounds__(256) void prep_half_kernel(PrepArgs a) {
       float u4[4] = {0.f, 0.f, 0.f, 0.f};
       if (vec) {
         if (k4 < a.d) {
-          const f32x4 x4 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(a.X) + row * a.d + k4);
+          const f32x4 x4 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(a.X) + src * a.d + k4);
           u4[0] = x4[0]; u4[1] = x4[1]; u4[2] = x4[2]; u4[3] = x4[3];
         }
       } else if (vec16) {                                   // bf16 / f16 rows: 8 bytes per lane, exact upcasts
         if (k4 < a.d) {
-          const uint2 h = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(a.X) + row * a.d + k4);
+          const uint2 h = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(a.X) + src * a.d + k4);
           if (a.dtype == MMF_BF16) {
             u4[0] = __uint_as_float(h.x << 16); u4[1] = __uint_as_float(h.x & 0xffff0000u);
             u4[2] = __uint_as_float(h.y << 16); u4[3] = __uint_as_float(h.y & 0xffff0000u);
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(256) void prep_half_kernel(PrepArgs a) {
       } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          if (k4 + i < a.d) u4[i] = ld_elem(a.X, row * a.d + k4 + i, a.dtype);
+          if (k4 + i < a.d) u4[i] = ld_elem(a.X, src * a.d + k4 + i, a.dtype);
       }
       uint16_t b4[4];
 #pragma unroll
@@ -215,7 +217,13 @@ struct ScanB16Args {
   float* margin_out;         // [n_rows] the queries' error margins, written with cand_keys
   uint32_t* spill_cnt; uint32_t* spill_ids; int spill_cap;   // per-row overflow lists (SpillSink), or nullptr / 0
   int spill_stacks;          // one list pair per row: the two lanes fill the row's slots from both ends, no counter (SpillSink)
+  const int32_t* sched;      // SEG kernels only: [grid][SEG_ENTRY] work table (segmented calls, see launch_scan_b16_seg)
 };
+
+// Work table entry of a segmented scan (one per workgroup): the row block's first position in the segment-padded query
+// image, the list row (= row of X) of its first query, how many of its QT queries are real, its candidate tile range
+// in the segment-padded candidate image, and the id offset that turns an image column into a global row id of Y.
+enum { SEG_QPOS = 0, SEG_ROW0 = 1, SEG_NQ = 2, SEG_T0 = 3, SEG_T1 = 4, SEG_IDOFF = 5, SEG_ENTRY = 8 };
 
 // Order-preserving float <-> int32 map (an involution) so that thresholds can be merged with atomicMax.
 __device__ __forceinline__ int32_t seed_enc(float f) {
@@ -246,7 +254,11 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 //              each other's DMA issue, as at d <= 512.
 //              (k + self in 12..20 at d <= 1024: NW = 4, one wave per SIMD with all of k — its 16-entry lists leave no
 //              room for the exchange block.)
-template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false>
+//
+// SEG (segmented calls): the workgroup's row block, column range and id offset come from the work table a.sched instead
+// of blockIdx / col_splits; one workgroup per row block (split 0), queries past the block's count are idle.  List rows
+// (lists, thresholds, margins, overflow lists) are rows of X, operand rows are positions of the padded query image.
+template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(ScanB16Args a) {
   static_assert(!SPLITK || (TPB == 1 && NW == 8 && (KS % 8) == 0), "split-k pairs");
   constexpr int NQW = SPLITK ? NW / 2 : NW;     // waves that own queries and lists
@@ -286,7 +298,15 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   // dispatch order: their workgroups start from the thresholds the earlier ones published (a.seed).
   int64_t rb;
   int split;
-  {
+  int64_t t_begin, t_end, row0 = 0;
+  int nq = 0;
+  uint32_t id_off = a.id_off;
+  if constexpr (SEG) {
+    const int32_t* e = a.sched + (size_t)blockIdx.x * SEG_ENTRY;
+    rb = e[SEG_QPOS] / QT; row0 = e[SEG_ROW0]; nq = e[SEG_NQ];
+    t_begin = e[SEG_T0]; t_end = e[SEG_T1]; id_off = (uint32_t)e[SEG_IDOFF];
+    split = 0;
+  } else {
     const int CS = a.conc_splits;
     const int64_t round = blockIdx.x / a.blocks_per_round;
     const int64_t j = blockIdx.x - round * a.blocks_per_round;
@@ -294,24 +314,25 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
     const int x = (int)(j & 7);
     split = (int)round * CS + x % CS;
     rb = q * (8 / CS) + x / CS;
+    if (rb >= a.row_blocks) return;
+    t_begin = (int64_t)split * a.tiles_per_split;
+    t_end = t_begin + a.tiles_per_split;
+    if (t_end > a.tiles_total) t_end = a.tiles_total;
+    if (t_begin > t_end) t_begin = t_end;
   }
-  if (rb >= a.row_blocks) return;
   const int64_t q0 = rb * QT;
-  int64_t t_begin = (int64_t)split * a.tiles_per_split;
-  int64_t t_end = t_begin + a.tiles_per_split;
-  if (t_end > a.tiles_total) t_end = a.tiles_total;
-  if (t_begin > t_end) t_begin = t_end;
   const int64_t T = t_end - t_begin;
 
-  const int64_t qpos = q0 + 32 * qw + c;
-  const bool qvalid = (qpos < a.n_rows) && owner;
+  const int64_t qop = q0 + 32 * qw + c;                    // operand position of this lane's query
+  const int64_t qpos = SEG ? row0 + 32 * qw + c : qop;     // its list row
+  const bool qvalid = (SEG ? (32 * qw + c < nq) : (qpos < a.n_rows)) && owner;
 
   // margin of this lane's query (see the header): 2 (E1 + E2)
   float margin;
   {
     const float ZB = __uint_as_float(a.maxima[0]), RB = __uint_as_float(a.maxima[1]);
     const float UB = __uint_as_float(a.maxima[2]), CB = __uint_as_float(a.maxima[3]);
-    const float zn = a.q_zn[qpos], rn = a.q_rn[qpos], un = a.q_un[qpos];   // arrays are padded
+    const float zn = a.q_zn[qop], rn = a.q_rn[qop], un = a.q_un[qop];   // arrays are padded
     const float g_acc = (float)(KS * 16 + 8) * 5.9604645e-8f;
     const float g_chain = (float)(a.d + 2) * 5.9604645e-8f;
     // + 2^-19 |G| (2^-18 with 5 slot bits): the slot number a stored key carries in its low mantissa bits (SlotList)
@@ -329,7 +350,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   if (!qvalid) list.thr = __builtin_huge_valf();
   else if (a.spill_cnt) {
     list.sink.cnt = a.spill_cnt; list.sink.ids = a.spill_ids; list.sink.cap = (uint32_t)a.spill_cap; list.sink.row = qpos;
-    list.sink.seg_len = a.seg_len; list.sink.seg_stride = a.seg_stride; list.sink.id_off = a.id_off;
+    list.sink.seg_len = a.seg_len; list.sink.seg_stride = a.seg_stride; list.sink.id_off = id_off;
     if (DBG) list.sink.ablate = (a.debug & 128) ? 1 : 0;
     if (a.spill_stacks) list.sink.stacks = 1 + half;
   }
@@ -670,7 +691,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
     for (int e = 0; e < list.cnt; ++e) {
       uint32_t id = list.id_of(e);
       if (a.seg_len) id = (id / a.seg_len) * a.seg_stride + id % a.seg_len;
-      a.cand_ids[lbase * CAP + e] = id + a.id_off;
+      a.cand_ids[lbase * CAP + e] = id + id_off;
       if (a.cand_keys) a.cand_keys[lbase * CAP + e] = list.keys[e * NTL];
     }
     // Audited loss, settled after the last launch: a dropped candidate matters only if its key reaches the
@@ -718,10 +739,22 @@ int scan_bf16_cap(int kk, int dp) {
 int scan_bf16_slot_ulp(int cap) { return cap <= 16 ? 16 : 32; }
 int scan_bf16_dp(int64_t d) { return pad_dp(d); }
 
+int launch_prep_half_gather(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
+                            const uint32_t* max_n, const int32_t* gather, void* Z, int64_t n_pos, int64_t n_pad, int dp,
+                            int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima, hipStream_t s);
+
 int launch_prep_half(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
                      const uint32_t* max_n, void* Z, int64_t n_pad, int dp, int z_f16, float* zn, float* rn,
                      float* un, float* cb, uint32_t* maxima, hipStream_t s) {
-  PrepArgs a{X, n, d, dtype, metric, scal, max_n, Z, n_pad, dp, z_f16, zn, rn, un, cb, maxima};
+  return launch_prep_half_gather(X, n, d, dtype, metric, scal, max_n, nullptr, Z, n, n_pad, dp, z_f16, zn, rn, un, cb, maxima, s);
+}
+
+// positions [0, n_pos) of Z are rows gather[pos] of X (-1: padding), positions [n_pos, n_pad) padding
+int launch_prep_half_gather(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
+                            const uint32_t* max_n, const int32_t* gather, void* Z, int64_t n_pos, int64_t n_pad, int dp,
+                            int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima, hipStream_t s) {
+  (void)n;
+  PrepArgs a{X, n_pos, d, dtype, metric, scal, max_n, Z, n_pad, dp, z_f16, zn, rn, un, cb, maxima, gather};
   int64_t grid = (n_pad + 3) / 4;
   if (grid > 1024) grid = 1024;          // 16 waves per CU; fewer, longer workgroups keep the final atomics few
   hipLaunchKernelGGL(prep_half_kernel, dim3((unsigned)grid), dim3(256), 0, s, a);
@@ -759,7 +792,7 @@ size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap) {
   return (size_t)scan_b16_grid(n_rows, col_splits, dp) * (cap <= 16 ? 16 : 32) * (64 * waves_for_dp(dp)) * 4 + 256;
 }
 
-template <int KS, int NW, int TPB, int CAP, bool SPLITK = false>
+template <int KS, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false>
 static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_t s) {
   const size_t lds = scan_b16_lds(KS, NW, TPB, CAP, SPLITK);
   auto go = [&](auto kern) -> int {
@@ -768,6 +801,10 @@ static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_
     MMF_LAUNCH_CHECK();
     return MMF_OK;
   };
+  if constexpr (SEG) {
+    if (f16) return go(scan_b16x_kernel<KS, true, false, NW, TPB, CAP, SPLITK, true>);
+    return go(scan_b16x_kernel<KS, false, false, NW, TPB, CAP, SPLITK, true>);
+  }
   if (a.debug != 0) {   // instrumented build of the same kernel (MMF_SCAN_DEBUG)
     if (f16) return go(scan_b16x_kernel<KS, true, true, NW, TPB, CAP, SPLITK>);
     return go(scan_b16x_kernel<KS, false, true, NW, TPB, CAP, SPLITK>);
@@ -858,6 +895,55 @@ int launch_scan_b16(const void* ZQ, const void* ZC, const float* cb, const float
     MMF_HIP(hipStreamSynchronize(s));
     fprintf(stderr, "[mmf scan dbg] wave-tiles=%llu slow-entries=%llu (cold %llu) hits=%llu warm-compactions=%llu lanes-with-hit=%llu\n",
             h[5], h[0], h[1], h[2], h[3], h[4]);
+  }
+  return rc;
+}
+
+// Segmented scan (mmf_simtopk_segmented): one workgroup per entry of the work table `sched` ([grid][SEG_ENTRY] int32,
+// device), one list pair per row (L.lists == 2), no threshold sharing.  The tables' tile ranges index the segment-padded
+// candidate image ZC / cb; ZQ / q_zn / q_rn / q_un are the segment-padded query image.  Same kernel as launch_scan_b16
+// with its schedule read from the table (template flag SEG: the production instantiations are untouched).
+size_t scan_b16_seg_scratch_bytes(int64_t grid, int dp, int cap) {
+  return (size_t)grid * (cap <= 16 ? 16 : 32) * (64 * waves_for_dp(dp)) * 4 + 256;
+}
+
+int launch_scan_b16_seg(const void* ZQ, const void* ZC, const float* cb, const float* q_zn, const float* q_rn,
+                        const float* q_un, const uint32_t* maxima, const int32_t* sched, int64_t grid, int64_t n_rows,
+                        int64_t m, int dp, int64_t d, bool f16, int metric, int kk, const CandLists& L, void* scratch,
+                        const ScanB16Panel& pn, hipStream_t s) {
+  if (grid <= 0) return MMF_OK;
+  if (L.lists != 2) { set_error("scan_b16_seg: one list pair per row expected"); return MMF_E_INTERNAL; }
+  if (!pn.seed) { set_error("scan_b16_seg: threshold buffers missing"); return MMF_E_INTERNAL; }
+  ScanB16Args a{};
+  a.ZQ = ZQ; a.ZC = ZC; a.cb = cb; a.q_zn = q_zn; a.q_rn = q_rn; a.q_un = q_un; a.maxima = maxima;
+  a.n_rows = n_rows; a.m = m; a.tiles_total = 0; a.tiles_per_split = 0;
+  a.row_blocks = 0; a.col_splits = 1; a.conc_splits = 1; a.blocks_per_round = 0;
+  a.kk = kk; a.metric = metric; a.d = (int)d;
+  a.lists_total = L.lists; a.list_base = 0;
+  a.seg_len = 0; a.seg_stride = 0; a.id_off = 0;
+  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride; a.share = 0;
+  a.debug = 0; a.dbg = nullptr;
+  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow; a.cand_keys = L.keys; a.margin_out = L.margin;
+  a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap;
+  a.spill_stacks = L.spill_stacks;
+  a.lids = reinterpret_cast<uint32_t*>(scratch);
+  a.sched = sched;
+  int rc = MMF_E_INTERNAL;
+  const bool big = (L.cap == B_CAP_BIG);
+  if (L.cap == B_CAP_WIDE) {
+    switch (dp) {
+      case 128: rc = launch_b16_t<8, 8, 1, B_CAP_WIDE, false, true>(a, f16, grid, s); break;
+      case 256: rc = launch_b16_t<16, 8, 1, B_CAP_WIDE, false, true>(a, f16, grid, s); break;
+      case 512: rc = launch_b16_t<32, 8, 1, B_CAP_WIDE, false, true>(a, f16, grid, s); break;
+      default: set_error("scan_b16_seg: 32-entry lists need a padded dim <= 512 (got %d)", dp);
+    }
+  } else
+  switch (dp) {
+    case 128: rc = big ? launch_b16_t<8, 8, 2, B_CAP_BIG, false, true>(a, f16, grid, s) : launch_b16_t<8, 8, 4, B_CAP, false, true>(a, f16, grid, s); break;
+    case 256: rc = big ? launch_b16_t<16, 8, 2, B_CAP_BIG, false, true>(a, f16, grid, s) : launch_b16_t<16, 8, 4, B_CAP, false, true>(a, f16, grid, s); break;
+    case 512: rc = big ? launch_b16_t<32, 8, 1, B_CAP_BIG, false, true>(a, f16, grid, s) : launch_b16_t<32, 8, 2, B_CAP, false, true>(a, f16, grid, s); break;
+    case 1024: rc = launch_b16_t<64, 8, 1, B_CAP, true, true>(a, f16, grid, s); break;
+    default: set_error("scan_b16_seg: unsupported padded dim %d", dp);
   }
   return rc;
 }

@@ -74,6 +74,78 @@ def simtopk(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, metric="cosine
     return idx, val
 
 
+def _segment_ptr(ptr, batch, rows: int, side: str) -> torch.Tensor:
+    """Host int64 offsets [S + 1] from exactly one of ptr (offsets) / batch (sorted segment id per row, PyG convention)."""
+    if (ptr is None) == (batch is None):
+        raise ValueError(f"simtopk_segmented: give exactly one of {side}ptr / {side}batch")
+    if ptr is not None:
+        p = torch.as_tensor(ptr).detach().to("cpu", torch.int64).reshape(-1)
+        if p.numel() < 1 or int(p[0]) != 0 or int(p[-1]) != rows:
+            raise ValueError(f"simtopk_segmented: {side}ptr must start at 0 and end at {rows}")
+        if p.numel() > 1 and bool((p[1:] < p[:-1]).any()):
+            raise ValueError(f"simtopk_segmented: {side}ptr must be non-decreasing")
+        return p.contiguous()
+    b = torch.as_tensor(batch)
+    if b.dim() != 1 or b.numel() != rows:
+        raise ValueError(f"simtopk_segmented: {side}batch must hold one segment id per row ({rows})")
+    b = b.detach().to("cpu", torch.int64)           # the one device -> host copy of a batch vector
+    if rows == 0:
+        return torch.zeros(1, dtype=torch.int64)
+    if bool((b < 0).any()) or bool((b[1:] < b[:-1]).any()):
+        raise ValueError(f"simtopk_segmented: {side}batch must be sorted and non-negative")
+    counts = torch.bincount(b)
+    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(counts, 0)])
+
+
+def simtopk_segmented(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, ptr=None, batch=None, y_ptr=None, y_batch=None,
+                      metric="cosine", lam: float = 1.0, k: int = 5, exclude_self: Optional[bool] = None,
+                      precision: str = "auto", return_stats: bool = False, profile: bool = False):
+    """Per-segment fused similarity + top-k (mmf_simtopk_segmented): rows of segment s of X are ranked only against
+    rows of segment s of Y (Y None: of X).  Returns (idx int64 [n,k] GLOBAL row ids of Y, val f32 [n,k]); a row whose
+    segment has fewer than k admissible columns gets them first, then -1 / -inf.  The bits equal one simtopk call per
+    segment (row_offset / col_offset = the segment's offsets).
+
+    Segments per side: exactly one of ptr ([S + 1] offsets) / batch ([n] sorted segment ids, as PyG's knn_graph);
+    y_ptr / y_batch likewise for Y (both sides need the same number of segments).  Offsets are read on the host:
+    a batch (or ptr) on the device costs one device -> host copy, i.e. a synchronisation."""
+    X = _feat(X, "simtopk_segmented X")
+    if Y is not None:
+        Y = _feat(Y, "simtopk_segmented Y")
+        if Y.device != X.device or Y.dtype != X.dtype or Y.shape[1] != X.shape[1]:
+            raise ValueError("simtopk_segmented: X and Y must share device, dtype and feature dim")
+    if int(k) < 1:
+        raise ValueError(f"simtopk_segmented: k must be >= 1 (got {k})")
+    if precision not in _lib.PRECISIONS:
+        raise ValueError(f"simtopk_segmented: unknown precision {precision!r}")
+    n, d = X.shape
+    xp = _segment_ptr(ptr, batch, n, "")
+    if Y is None:
+        if y_ptr is not None or y_batch is not None:
+            raise ValueError("simtopk_segmented: y_ptr / y_batch need Y")
+        m, yp = n, xp
+    else:
+        m = Y.shape[0]
+        yp = _segment_ptr(y_ptr, y_batch, m, "y_")
+        if xp.numel() != yp.numel():
+            raise ValueError(f"simtopk_segmented: X has {xp.numel() - 1} segments, Y has {yp.numel() - 1}")
+    if exclude_self is None:
+        exclude_self = Y is None
+    _need_gpu(X, "simtopk_segmented")
+    S = xp.numel() - 1
+    idx = torch.empty((n, k), dtype=torch.int64, device=X.device)
+    val = torch.empty((n, k), dtype=torch.float32, device=X.device)
+    opts = _lib.SimtopkOpts(_lib.PRECISIONS[precision], int(profile), 0, _lib.QUERY_ORDERS["off"], None)
+    stats = _lib.SimtopkStats()
+    rc = _lib.lib().mmf_simtopk_segmented(_p(X), n, _p(Y), m, d, _DT[X.dtype], _metric(metric), float(lam), int(k),
+                                          int(bool(exclude_self)), ctypes.c_void_p(xp.data_ptr()), ctypes.c_void_p(yp.data_ptr()),
+                                          S, _p(idx), _p(val), ctypes.byref(opts), ctypes.byref(stats),
+                                          X.device.index or 0, _stream(X.device))
+    _lib.check(rc, "mmf_simtopk_segmented")
+    if return_stats:
+        return idx, val, stats.as_dict()
+    return idx, val
+
+
 def last_query_order(n: int) -> torch.Tensor:
     """Diagnostics: scan position -> row of the most recent simtopk call that reordered its n queries (mmf_debug_query_order)."""
     out = torch.empty((n,), dtype=torch.int32)
