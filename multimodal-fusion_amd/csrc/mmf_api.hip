@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <utility>
 #include <vector>
 
@@ -148,19 +149,240 @@ struct EventTimer {
   }
 };
 
-static int pick_splits(int64_t row_blocks, int64_t col_tiles, int lists_cap, int cap, int forced) {
+static int pick_splits(int64_t row_blocks, int64_t col_tiles, int cap, int forced) {
   int64_t s = forced > 0 ? forced : (768 + row_blocks - 1) / row_blocks;
   if (s > col_tiles) s = col_tiles;
   const int64_t max_lists = 1024 / cap;  // select kernel capacity per row
   if (2 * s > max_lists) s = max_lists / 2;
   if (s < 1) s = 1;
-  (void)lists_cap;
   return (int)s;
 }
 
+// Columns a row of rows [r0, r0 + n) may take from columns [c0, c0 + m): all m, minus one when self is excluded and a row's
+// own id may lie among them (any overlap of the two ranges).
+static int64_t admissible_columns(int64_t r0, int64_t n, int64_t c0, int64_t m, int exclude_self, bool* overlap = nullptr) {
+  const bool o = exclude_self && r0 < c0 + m && r0 + n > c0;
+  if (overlap) *overlap = o;
+  return m - (o ? 1 : 0);
+}
+
+// One simtopk call (`who`: the entry, for error messages): its arguments, and what check() derives from them.
+struct Request {
+  const char* who;
+  const void* X; int64_t n; const void* Y; int64_t m; int64_t d; int dtype, metric; float lambda;
+  int k, exclude_self; int64_t row_offset, col_offset;   // ids reported: row_offset + row of X, col_offset + row of Y
+  int64_t* out_idx; float* out_val; mmf_simtopk_stats* stats; bool profile; hipStream_t s;
+  int kk = 0;                       // entries a row's lists keep: k, + 1 when self is excluded
+  int precision = MMF_PREC_AUTO;    // resolved: MMF_PREC_EXACT, _FAST or _FAST_BF16
+  std::optional<DeviceGuard> guard;
+
+  // The checks every simtopk entry makes, in this order: shapes / dtype / device, metric, lambda, k, the entry's own
+  // (`entry_checks`); stats zeroed; then, when there are rows: outputs, admissible columns (of the whole block unless
+  // `per_segment`), device, precision (`prec`: requested, or fixed by the operands; AUTO: the 16-bit scan if it applies).
+  template <class F>
+  int check(int prec, bool per_segment, int device_id, F&& entry_checks) {
+    MMF_TRY(check_common(X, n, m, d, dtype, device_id));
+    if (metric < MMF_DOT || metric > MMF_RBF) { set_error("%s: bad metric %d", who, metric); return MMF_E_INVALID; }
+    if (metric == MMF_RBF && !(lambda > 0.0f)) { set_error("%s: MMF_RBF needs lambda > 0 (got %g)", who, lambda); return MMF_E_INVALID; }
+    if (k < 1) { set_error("%s: k must be >= 1 (got %d)", who, k); return MMF_E_INVALID; }
+    kk = k + (exclude_self ? 1 : 0);
+    MMF_TRY(entry_checks());
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n == 0) return MMF_OK;
+    if (!out_idx || !out_val) { set_error("%s: NULL output", who); return MMF_E_INVALID; }
+    bool overlap = false;
+    const int64_t adm = admissible_columns(row_offset, n, col_offset, m, exclude_self, &overlap);
+    if (!per_segment && k > adm) {
+      set_error("%s: k = %d exceeds the %lld admissible columns (m = %lld%s)", who, k, (long long)adm, (long long)m, overlap ? ", self excluded" : "");
+      return MMF_E_INVALID;
+    }
+    guard.emplace(device_id);
+    if (!guard->ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+    const bool b16 = scan_bf16_supported(d, kk, dtype);
+    precision = prec == MMF_PREC_AUTO ? (b16 ? MMF_PREC_FAST : MMF_PREC_EXACT) : prec;
+    if (precision != MMF_PREC_EXACT && precision != MMF_PREC_FAST && precision != MMF_PREC_FAST_BF16) { set_error("%s: bad precision %d", who, precision); return MMF_E_INVALID; }
+    if (precision != MMF_PREC_EXACT && !b16) {
+      set_error("%s: MMF_PREC_FAST does not support d = %lld, k = %d (AUTO takes the exact scan there)", who, (long long)d, k);
+      return MMF_E_UNSUPPORTED;
+    }
+    return MMF_OK;
+  }
+};
+
+// What a simtopk call reports (check() zeroed the rest).  h_tot: the re-rank's candidate counters.
+static void fill_stats(mmf_simtopk_stats* st, int precision, int splits, int grid, float prep_ms, float scan_ms, float rerank_ms,
+                       float fallback_ms, int64_t fallback_rows, int64_t overflow_rows, int64_t short_rows,
+                       const std::vector<uint32_t>& h_tot, int64_t near_rows = -1) {
+  if (!st) return;
+  st->precision_used = precision; st->col_splits = splits; st->scan_grid = grid;
+  st->prep_ms = prep_ms; st->scan_ms = scan_ms; st->rerank_ms = rerank_ms; st->fallback_ms = fallback_ms;
+  st->fallback_rows = fallback_rows; st->overflow_rows = overflow_rows; st->short_rows = short_rows;
+  for (uint32_t v : h_tot) st->candidates += v;
+  st->near_rows = near_rows;
+}
+
+// overflow slots per row of the 16-bit scan for the columns a row's lane lists cannot hold (near-duplicate data); a row
+// that fills them as well is redone exactly
+static constexpr int kSpillCap = 192;
+
+// The 16-bit scan's candidate lists of n rows: `lists` lists of bcap entries per row, and the overflow lists.
+static size_t b16_lists_bytes(int64_t n, int lists, int bcap) {
+  const size_t e = (size_t)n * lists;
+  return ws_bytes(e, 4) + ws_bytes(e * bcap, 4) + (lists > 2 ? ws_bytes(e * bcap, 4) + ws_bytes(n, 4) : 0) + 2 * ws_bytes(n, 4) +
+         ws_bytes((size_t)n * kSpillCap, 4);
+}
+static CandLists carve_b16_lists(Workspace& ws, int64_t n, int lists, int bcap) {
+  CandLists L{};
+  L.lists = lists; L.cap = bcap; L.slot_ulp = scan_bf16_slot_ulp(bcap); L.spill_cap = kSpillCap;
+  L.cnt = ws.take<uint32_t>((size_t)n * lists); L.ids = ws.take<uint32_t>((size_t)n * lists * bcap);
+  if (lists > 2) { L.keys = ws.take<float>((size_t)n * lists * bcap); L.margin = ws.take<float>(n); }   // one pair: nothing to prune against
+  L.overflow = ws.take<uint32_t>(n); L.spill_cnt = ws.take<uint32_t>(n); L.spill_ids = ws.take<uint32_t>((size_t)n * kSpillCap);
+  L.spill_stacks = (lists == 2 && !getenv("MMF_SPILL_COUNTER")) ? 1 : 0;   // one pair: its two lanes fill the slots from both ends
+  return L;
+}
+
+// ---- the exact f32 pass -----------------------------------------------------------------------------------------------
+// The exact scan (mmf_scan_f32.hip) and the re-rank over groups of rows: all of X in the plain exact call, the rows the
+// 16-bit path flagged (gathered), and in the segmented call the whole segments it sends there (slices) and the flagged
+// rows of each segment.  Each group is one scan and one re-rank on the stream (one of each per pass of at most 44 entries
+// when k + self is larger); one fail-count readback ends the pass.
+
+// Candidate lists, overflow words and fail list of an exact pass, for `rows` rows at a time.
+struct ExactLists {
+  CandLists L{};                 // cnt / ids: list_words (x cap) words; overflow: one word per row
+  int32_t* fail_rows = nullptr; uint32_t* fail_count = nullptr;
+  float* floor_key = nullptr; uint32_t* floor_id = nullptr;   // k + self > 44: where each row's previous pass ended
+  int64_t rows = 0;
+  static size_t bytes(int64_t rows, size_t list_words, int cap, bool floors) {
+    return ws_bytes(list_words, 4) + ws_bytes(list_words * cap, 4) + (floors ? 4 : 2) * ws_bytes(rows, 4) + ws_bytes(4, 4);
+  }
+  void carve(Workspace& ws, int64_t rows_, size_t list_words, int cap, bool floors) {
+    rows = rows_;
+    L.cnt = ws.take<uint32_t>(list_words); L.ids = ws.take<uint32_t>(list_words * cap); L.overflow = ws.take<uint32_t>(rows);
+    fail_rows = ws.take<int32_t>(rows); fail_count = ws.take<uint32_t>(4);
+    if (floors) { floor_key = ws.take<float>(rows); floor_id = ws.take<uint32_t>(rows); }
+  }
+  int zero(hipStream_t s) const {   // fail count and overflow words
+    MMF_HIP(hipMemsetAsync(fail_count, 0, 16, s)); MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)rows * 4, s));
+    return MMF_OK;
+  }
+};
+
+struct ExactGroup {
+  int64_t row0, rows;   // rows [row0, row0 + rows) of X, or (gathered) entries [row0, row0 + rows) of ExactPass::row_ids
+  bool gathered;
+  int64_t col0, cols;   // ranked against rows [col0, col0 + cols) of Y
+  int k;                // entries per row (the output rows stay r.k wide)
+};
+
+struct ExactPass {
+  static constexpr int64_t kBatch = 4096;   // gathered rows that have an f32 image at a time
+  const Request& r;
+  const float *rx, *cy;                     // row scalars of X and Y
+  bool same = false;                        // X is Y: one f32 image serves both
+  int forced_splits = 0;                    // (set before add())
+  const int32_t* row_ids = nullptr;         // device: the rows of X that gathered groups name
+  int64_t n_ids = 0;
+  uint32_t* cand_total = nullptr;           // optional: the re-rank counts its candidates here
+  std::vector<ExactGroup> pieces;           // the groups, gathered ones in pieces of at most kBatch rows
+  int64_t rows_total = 0; size_t list_words = 0; bool slices = false;
+  int grid = 0;                             // out: scan workgroups (of each piece's last pass)
+
+  ExactPass(const Request& r_, const float* rx_, const float* cy_) : r(r_), rx(rx_), cy(cy_) {}
+  int cap() const { return scan_f32_cap(std::min(r.kk, 44)); }
+  bool floors() const { return r.kk > 44; }
+  int splits(const ExactGroup& G) const { return pick_splits((G.rows + 127) / 128, (G.cols + 127) / 128, cap(), forced_splits); }
+  void add(ExactGroup G) {
+    const int64_t end = G.row0 + G.rows;
+    for (; G.row0 < end; G.row0 += G.rows) {
+      G.rows = G.gathered ? std::min(kBatch, end - G.row0) : end - G.row0;
+      pieces.push_back(G);
+      rows_total += G.rows; slices |= !G.gathered;
+      list_words = std::max(list_words, (size_t)G.rows * 2 * splits(G));
+    }
+  }
+  // f32 images: all of Y, all of X when a piece is a slice of it (and X is not Y), one batch of gathered rows
+  size_t image_bytes() const {
+    return ws_bytes(prep_f32_bytes(r.m, r.d), 1) + (slices && !same ? ws_bytes(prep_f32_bytes(r.n, r.d), 1) : 0) +
+           (n_ids > 0 ? ws_bytes(prep_f32_bytes(std::min(n_ids, kBatch), r.d), 1) : 0);
+  }
+  size_t list_bytes() const { return ExactLists::bytes(rows_total, list_words, cap(), floors()); }
+
+  int read_fails(const ExactLists& B, std::vector<uint32_t>* h_tot) const {
+    uint32_t h_fail = 0;
+    MMF_HIP(hipMemcpyAsync(&h_fail, B.fail_count, 4, hipMemcpyDeviceToHost, r.s));
+    if (h_tot) MMF_HIP(hipMemcpyAsync(h_tot->data(), cand_total, 1024, hipMemcpyDeviceToHost, r.s));
+    MMF_HIP(hipStreamSynchronize(r.s));
+    if (h_fail != 0) { set_error("%s: %u rows failed in the exact scan (internal invariant)", r.who, h_fail); return MMF_E_INTERNAL; }
+    return MMF_OK;
+  }
+
+  // Images from ws; lists from B (zeroed by the caller), which holds B.rows rows: when the next piece does not fit, the
+  // fail count is read back and B starts over.  t: the plain exact call's timers (prep, started by the caller; scan; re-rank), else null.
+  // h_tot: the candidate counters (cand_total), read back with the fail count.
+  int run(Workspace& ws, const ExactLists& B, EventTimer* t = nullptr, std::vector<uint32_t>* h_tot = nullptr) {
+    const hipStream_t s = r.s;
+    const int64_t dpad = prep_f32_dim(r.d);
+    const size_t row_bytes = (size_t)r.d * dtype_size(r.dtype);
+    auto image = [&](int64_t rows) { return reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(rows, r.d))); };
+    float* Yp = image(r.m);
+    float* Xp = same ? Yp : (slices ? image(r.n) : nullptr);
+    float* Xe = n_ids > 0 ? image(std::min(n_ids, kBatch)) : nullptr;
+    MMF_TRY(launch_prep_f32(r.Y, r.m, r.d, r.dtype, nullptr, Yp, s));
+    if (Xp && Xp != Yp) MMF_TRY(launch_prep_f32(r.X, r.n, r.d, r.dtype, nullptr, Xp, s));
+    const int self1 = r.exclude_self ? 1 : 0, k_pass_max = 44 - self1;   // entries one pass can emit
+    const bool one_pass = r.k <= k_pass_max;   // timers: scan and re-rank apart for one pass, the whole loop as "scan" otherwise
+    if (t) { MMF_TRY(t[0].stop(s)); MMF_TRY(t[1].start(r.profile, s)); }
+    int64_t batch0 = -1, used = 0;   // first entry of row_ids in Xe; rows of B in use
+    for (const ExactGroup& G : pieces) {
+      if (used + G.rows > B.rows) { MMF_TRY(read_fails(B, nullptr)); MMF_TRY(B.zero(s)); used = 0; }
+      if (G.gathered && (batch0 < 0 || G.row0 + G.rows > batch0 + kBatch)) {   // next batch of gathered rows
+        batch0 = G.row0;
+        MMF_TRY(launch_prep_f32(r.X, std::min(kBatch, n_ids - batch0), r.d, r.dtype, row_ids + batch0, Xe, s));
+      }
+      const int64_t r0 = G.gathered ? 0 : G.row0;   // a slice: X, its scalars, its image and the outputs from row r0 on
+      CandLists L = B.L;
+      L.lists = 2 * splits(G); L.cap = scan_f32_cap(std::min(G.k + self1, 44)); L.overflow = B.L.overflow + used;
+      ScanProblem sp{};
+      sp.X = static_cast<const char*>(r.X) + r0 * row_bytes; sp.n = G.gathered ? r.n : G.rows;
+      sp.Y = static_cast<const char*>(r.Y) + G.col0 * row_bytes; sp.m = G.cols;
+      sp.d = r.d; sp.dtype = r.dtype; sp.metric = r.metric; sp.lambda = r.lambda;
+      sp.Xp = G.gathered ? Xe + (G.row0 - batch0) * dpad : Xp + r0 * dpad; sp.Yp = Yp + G.col0 * dpad;
+      sp.rx = rx + r0; sp.cy = cy + G.col0; sp.row_ids = G.gathered ? row_ids + G.row0 : nullptr; sp.n_rows = G.rows;
+      sp.col_splits = L.lists / 2;
+      SelectProblem q{};   // (exact lists have no overflow lists: nothing for a second select launch)
+      q.X = sp.X; q.n = sp.n; q.Y = sp.Y; q.m = sp.m; q.d = r.d; q.dtype = r.dtype; q.metric = r.metric; q.lambda = r.lambda;
+      q.exclude_self = r.exclude_self; q.row_offset = r.row_offset + r0; q.col_offset = r.col_offset + G.col0;
+      q.rx = sp.rx; q.cy = sp.cy; q.row_ids = sp.row_ids; q.n_rows = G.rows;
+      q.out_idx = r.out_idx + r0 * r.k; q.out_val = r.out_val + r0 * r.k; q.out_stride = r.k;
+      q.fail_rows = B.fail_rows; q.fail_count = B.fail_count; q.cand_total = cand_total;
+      q.two_pass = false; q.order_scratch = nullptr; q.perm = nullptr;
+      // k + self beyond 44: several passes, each offering only what ranks after the previous pass's last entry
+      // (scikit-learn's n_neighbors is uncapped, preprocess_hypergraph.py:379)
+      int g = 0;
+      for (int done = 0; done < G.k; done += k_pass_max) {
+        const int kp = std::min(G.k - done, k_pass_max);
+        const bool more = done + kp < G.k;
+        sp.kk = kp + self1;
+        if (done > 0) { sp.floor_key = B.floor_key; sp.floor_id = B.floor_id; }
+        MMF_TRY(launch_scan_f32(sp, L, s, &g));
+        if (t && one_pass) { MMF_TRY(t[1].stop(s)); MMF_TRY(t[2].start(r.profile, s)); }
+        q.k = kp; q.out_off = done;
+        q.floor_key_out = more ? B.floor_key : nullptr; q.floor_id_out = more ? B.floor_id : nullptr;
+        MMF_TRY(launch_select(q, L, s));
+      }
+      grid += g;
+      used += G.rows;
+    }
+    if (t && one_pass) MMF_TRY(t[2].stop(s));
+    if (t && !one_pass) { MMF_TRY(t[1].stop(s)); MMF_TRY(t[2].start(r.profile, s)); MMF_TRY(t[2].stop(s)); }
+    return read_fails(B, h_tot);
+  }
+};
+
 // Everything of the fast path after the 16-bit operands exist: candidate lists, scan, (optional event
-// wait), exact re-rank, exact rescan of flagged rows, stats.  Shared by mmf_simtopk_ex and
-// mmf_simtopk_prepared.
+// wait), exact re-rank, exact rescan of flagged rows, stats.  Shared by mmf_simtopk_ex,
+// mmf_simtopk_prepared and mmf_simtopk_panels.
 struct FastOperands {
   const uint16_t* ZQ; const uint16_t* ZC;
   const float* rx; const float* cy;
@@ -176,10 +398,11 @@ struct FastOperands {
 };
 
 struct FastTail {
-  int64_t n, m; int kk, cap, bcap, splits, lists, fb_splits, fb_lists; int64_t FB;
-  CandLists L, FL;
-  int32_t *fail_rows = nullptr, *fb_fail_rows = nullptr;
-  uint32_t *fail_count = nullptr, *cand_total = nullptr, *fb_fail_count = nullptr;
+  int64_t n, m; int kk, cap, bcap, splits, lists, fb_splits; int64_t FB;
+  CandLists L;
+  ExactLists XL;   // the exact rescan of flagged rows, FB rows at a time
+  int32_t* fail_rows = nullptr;
+  uint32_t *fail_count = nullptr, *cand_total = nullptr;
   char* scan_scratch = nullptr;
   char* order_scratch = nullptr;
   // query order of the scan (mmf_order.hip): near-duplicate rows next to each other.  Tried when forced, or (auto) at sizes where
@@ -200,15 +423,12 @@ struct FastTail {
   int32_t* seed = nullptr;
   // a handful of flagged rows skips the matrix-core rescan: all their keys, then a block-wide top-k
   static constexpr int64_t kRowsExactMax = 48;
-  // overflow slots per row for the columns a row's lane lists cannot hold (near-duplicate data); a row that fills
-  // them as well is redone exactly
-  static constexpr int kSpillCap = 192;
   int64_t rows_exact_cap = 0;
   float* row_keys = nullptr;
   // m_panel_min: columns of the smallest panel (== m_ when the scan is one launch); `splits` is per launch
-  FastTail(int64_t n_, int64_t m_, int kk_, int cap_, int forced_splits, int dp_, int panels_ = 1, int64_t m_panel_min = -1,
+  FastTail(int64_t n_, int64_t m_, int kk_, int forced_splits, int dp_, int panels_ = 1, int64_t m_panel_min = -1,
            int64_t m_panel_max = -1)
-      : n(n_), m(m_), kk(kk_), cap(cap_), dp(dp_), panels(panels_) {
+      : n(n_), m(m_), kk(kk_), cap(scan_f32_cap(kk_)), dp(dp_), panels(panels_) {
     bcap = scan_bf16_cap(kk, dp);
     const int qt = scan_b16_queries_per_block(dp);
     if (m_panel_min < 0) m_panel_min = m;
@@ -248,41 +468,24 @@ struct FastTail {
     rows_exact_cap = (int64_t(64) << 20) / (4 * (m > 0 ? m : 1));
     if (rows_exact_cap > kRowsExactMax) rows_exact_cap = kRowsExactMax;
     if (rows_exact_cap < 1) rows_exact_cap = 1;
-    FB = n < 4096 ? n : 4096;   // exact rescans are done in batches of at most FB rows
-    fb_splits = pick_splits((FB + 127) / 128, (m + 127) / 128, 0, cap, 0);
-    fb_lists = 2 * fb_splits;
+    FB = n < ExactPass::kBatch ? n : ExactPass::kBatch;   // exact rescans are done in batches of at most FB rows
+    fb_splits = pick_splits((FB + 127) / 128, (m + 127) / 128, cap, 0);
   }
   size_t bytes() const {
-    return ws_bytes((size_t)n * lists, 4) + 2 * ws_bytes((size_t)n * lists * bcap, 4) + 3 * ws_bytes(n, 4) + ws_bytes(4, 4) +
-           ws_bytes(256, 4) + ws_bytes((size_t)FB * fb_lists, 4) + ws_bytes((size_t)FB * fb_lists * cap, 4) +
-           2 * ws_bytes(FB, 4) + ws_bytes(4, 4) + ws_bytes(scan_b16_scratch_bytes(n, max_splits, dp, bcap), 1) + ws_bytes(2 * n_seed, 4) +
-           ws_bytes((size_t)rows_exact_cap * m, 4) + ws_bytes(n, 4) + ws_bytes((size_t)n * kSpillCap, 4) + ws_bytes(select_order_bytes(n), 1) +
+    return b16_lists_bytes(n, lists, bcap) + ws_bytes(n, 4) + ws_bytes(4, 4) + ws_bytes(256, 4) +
+           ExactLists::bytes(FB, (size_t)FB * 2 * fb_splits, cap, false) + ws_bytes(scan_b16_scratch_bytes(n, max_splits, dp, bcap), 1) +
+           ws_bytes(2 * n_seed, 4) + ws_bytes((size_t)rows_exact_cap * m, 4) + ws_bytes(select_order_bytes(n), 1) +
            (order_try ? ws_bytes(query_order_bytes(n), 1) + ws_bytes((size_t)n_pad_q() * dp, 2) + 3 * ws_bytes(n_pad_q(), 4) : 0);
   }
   void carve(Workspace& ws) {
-    L.cnt = ws.take<uint32_t>((size_t)n * lists);
-    L.ids = ws.take<uint32_t>((size_t)n * lists * bcap);
-    L.keys = ws.take<float>((size_t)n * lists * bcap);
-    L.margin = ws.take<float>(n);
-    L.overflow = ws.take<uint32_t>(n);
-    L.lists = lists; L.cap = bcap; L.slot_ulp = scan_bf16_slot_ulp(bcap);
+    L = carve_b16_lists(ws, n, lists, bcap);
     fail_rows = ws.take<int32_t>(n);
     fail_count = ws.take<uint32_t>(4);
     cand_total = ws.take<uint32_t>(256);
-    FL.cnt = ws.take<uint32_t>((size_t)FB * fb_lists);
-    FL.ids = ws.take<uint32_t>((size_t)FB * fb_lists * cap);
-    FL.overflow = ws.take<uint32_t>(FB);
-    FL.lists = fb_lists; FL.cap = cap;
-    fb_fail_rows = ws.take<int32_t>(FB);
-    fb_fail_count = ws.take<uint32_t>(4);
+    XL.carve(ws, FB, (size_t)FB * 2 * fb_splits, cap, false);
     scan_scratch = ws.take<char>(scan_b16_scratch_bytes(n, max_splits, dp, bcap));
     seed = ws.take<int32_t>(2 * n_seed);
-    if (lists <= 2) { L.keys = nullptr; L.margin = nullptr; }    // one list pair per row: nothing to prune against
     row_keys = ws.take<float>((size_t)rows_exact_cap * m);
-    L.spill_cnt = ws.take<uint32_t>(n);
-    L.spill_ids = ws.take<uint32_t>((size_t)n * kSpillCap);
-    L.spill_cap = kSpillCap;
-    L.spill_stacks = (lists == 2 && kSpillCap < 65536 && !getenv("MMF_SPILL_COUNTER")) ? 1 : 0;
     order_scratch = ws.take<char>(select_order_bytes(n));
     if (order_try) {
       qo_scratch = ws.take<char>(query_order_bytes(n));
@@ -290,9 +493,9 @@ struct FastTail {
       qo_zn = ws.take<float>(n_pad_q()); qo_rn = ws.take<float>(n_pad_q()); qo_un = ws.take<float>(n_pad_q());
     }
   }
-  int run(const void* X, int64_t n_, const void* Y, int64_t m_, int64_t d, int in_dtype, int metric, float lambda, int k,
-          int exclude_self, int64_t row_offset, int64_t col_offset, const FastOperands& fo_in, int64_t* out_idx,
-          float* out_val, bool profile, void* select_wait_event, mmf_simtopk_stats* stats, int precision, hipStream_t s) {
+  int run(const Request& r, const FastOperands& fo_in, void* select_wait_event) {
+    const hipStream_t s = r.s;
+    const bool profile = r.profile;
     FastOperands fo = fo_in;
     query_order_forget();
     EventTimer t_order;
@@ -319,8 +522,8 @@ struct FastTail {
     pn.seed = seed; pn.seed_stride = n_seed;
     pn.share = (splits > 1 || fo.n_panels > 1) ? 1 : 0;
     if (fo.n_panels == 0) {
-      MMF_TRY(launch_scan_b16(fo.ZQ, fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, m, fo.m_pad_tiles, fo.dp, d, fo.f16,
-                              metric, kk, splits, L, scan_scratch, pn, s, &grid));
+      MMF_TRY(launch_scan_b16(fo.ZQ, fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, m, fo.m_pad_tiles, fo.dp, r.d, fo.f16,
+                              r.metric, kk, splits, L, scan_scratch, pn, s, &grid));
     } else {
       // one launch per panel, each behind its own arrival event; the launches share the lists (disjoint
       // slots), the id scratch (they run one after the other) and the per-query thresholds
@@ -332,8 +535,8 @@ struct FastTail {
         pn.list_base = list_base;
         list_base += 2 * panel_splits[p];
         pn.seg_len = (uint32_t)P.seg_len; pn.seg_stride = (uint32_t)P.seg_stride; pn.id_off = (uint32_t)P.id_base;
-        MMF_TRY(launch_scan_b16(fo.ZQ, P.Z, P.cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, P.m, P.m_pad, fo.dp, d, fo.f16,
-                                metric, kk, panel_splits[p], L, scan_scratch, pn, s, &grid));
+        MMF_TRY(launch_scan_b16(fo.ZQ, P.Z, P.cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, P.m, P.m_pad, fo.dp, r.d, fo.f16,
+                                r.metric, kk, panel_splits[p], L, scan_scratch, pn, s, &grid));
         MMF_TRY(t_panel[p].stop(s));
       }
     }
@@ -348,10 +551,10 @@ struct FastTail {
     if (select_wait_event) MMF_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(select_wait_event), 0));
 
     SelectProblem q{};
-    q.X = X; q.n = n; q.Y = Y; q.m = m; q.d = d; q.dtype = in_dtype; q.metric = metric; q.lambda = lambda;
-    q.k = k; q.exclude_self = exclude_self; q.row_offset = row_offset; q.col_offset = col_offset;
-    q.rx = fo.rx; q.cy = fo.cy; q.row_ids = nullptr; q.perm = fo.perm; q.n_rows = n; q.out_idx = out_idx; q.out_val = out_val;
-    q.fail_rows = fail_rows; q.fail_count = fail_count; q.cand_total = stats ? cand_total : nullptr;
+    q.X = r.X; q.n = n; q.Y = r.Y; q.m = m; q.d = r.d; q.dtype = r.dtype; q.metric = r.metric; q.lambda = r.lambda;
+    q.k = r.k; q.exclude_self = r.exclude_self; q.row_offset = r.row_offset; q.col_offset = r.col_offset;
+    q.rx = fo.rx; q.cy = fo.cy; q.row_ids = nullptr; q.perm = fo.perm; q.n_rows = n; q.out_idx = r.out_idx; q.out_val = r.out_val;
+    q.fail_rows = fail_rows; q.fail_count = fail_count; q.cand_total = r.stats ? cand_total : nullptr;
     q.two_pass = true;
     q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
     MMF_TRY(t_sel.start(profile, s));
@@ -360,8 +563,8 @@ struct FastTail {
 
     uint32_t h_fail4[4] = {0, 0, 0, 0};
     MMF_HIP(hipMemcpyAsync(h_fail4, fail_count, 16, hipMemcpyDeviceToHost, s));
-    std::vector<uint32_t> h_tot(stats ? 256 : 0);
-    if (stats) MMF_HIP(hipMemcpyAsync(h_tot.data(), cand_total, 1024, hipMemcpyDeviceToHost, s));
+    std::vector<uint32_t> h_tot(r.stats ? 256 : 0);
+    if (r.stats) MMF_HIP(hipMemcpyAsync(h_tot.data(), cand_total, 1024, hipMemcpyDeviceToHost, s));
     MMF_HIP(hipStreamSynchronize(s));
     const uint32_t h_fail = h_fail4[0];
     if (h_fail > 0 && getenv("MMF_DEBUG_PRINT_FLAGGED")) {   // diagnosis: which rows, and the threshold / dropped key that flagged them
@@ -387,66 +590,30 @@ struct FastTail {
         fq.n_rows = ((int64_t)h_fail - off < rows_exact_cap) ? ((int64_t)h_fail - off) : rows_exact_cap;
         MMF_TRY(launch_rows_exact(fq, row_keys, s));
       }
-    } else {
-    float *fb_Xp = nullptr, *fb_Yp = nullptr;
-    int dev_now = 0;
-    MMF_HIP(hipGetDevice(&dev_now));
-    for (int64_t off = 0; off < (int64_t)h_fail; off += FB) {
-      const int64_t nb = ((int64_t)h_fail - off < FB) ? ((int64_t)h_fail - off) : FB;
-      if (off == 0) {   // f32 operand images for the exact scan: all candidate rows once, the flagged rows per batch
-        Workspace aux;
-        MMF_TRY(get_workspace_slot(dev_now, s, 1, ws_bytes(prep_f32_bytes(m, d), 1) + ws_bytes(prep_f32_bytes(FB, d), 1), &aux));
-        fb_Yp = reinterpret_cast<float*>(aux.take<char>(prep_f32_bytes(m, d)));
-        fb_Xp = reinterpret_cast<float*>(aux.take<char>(prep_f32_bytes(FB, d)));
-        MMF_TRY(launch_prep_f32(Y, m, d, in_dtype, nullptr, fb_Yp, s));
-      }
-      MMF_TRY(launch_prep_f32(X, nb, d, in_dtype, fail_rows + off, fb_Xp, s));
-      MMF_HIP(hipMemsetAsync(FL.overflow, 0, (size_t)nb * 4, s));
-      MMF_HIP(hipMemsetAsync(fb_fail_count, 0, 16, s));
-      ScanProblem sp{};
-      sp.X = X; sp.n = n; sp.Y = Y; sp.m = m; sp.d = d; sp.dtype = in_dtype; sp.metric = metric; sp.lambda = lambda;
-      sp.Xp = fb_Xp; sp.Yp = fb_Yp;
-      sp.kk = kk; sp.rx = fo.rx; sp.cy = fo.cy; sp.row_ids = fail_rows + off; sp.n_rows = nb; sp.col_splits = fb_splits;
-      MMF_TRY(launch_scan_f32(sp, FL, s, nullptr));
-      SelectProblem fq = q;
-      fq.perm = nullptr;
-      fq.row_ids = fail_rows + off; fq.n_rows = nb; fq.fail_rows = fb_fail_rows; fq.fail_count = fb_fail_count;
-      fq.cand_total = nullptr;
-      MMF_TRY(launch_select(fq, FL, s));
-      uint32_t h_fb = 0;
-      MMF_HIP(hipMemcpyAsync(&h_fb, fb_fail_count, 4, hipMemcpyDeviceToHost, s));
-      MMF_HIP(hipStreamSynchronize(s));
-      if (h_fb != 0) {
-        set_error("simtopk: %u rows failed in the exact rescan (internal invariant)", h_fb);
-        return MMF_E_INTERNAL;
-      }
-    }
+    } else if (h_fail > 0) {   // the exact pass over the flagged rows; its f32 images in the second workspace slot
+      ExactPass ex(r, fo.rx, fo.cy);
+      ex.row_ids = fail_rows; ex.n_ids = h_fail; ex.forced_splits = fb_splits;
+      ex.add(ExactGroup{0, (int64_t)h_fail, true, 0, m, r.k});
+      int dev_now = 0;
+      MMF_HIP(hipGetDevice(&dev_now));
+      Workspace aux;
+      MMF_TRY(get_workspace_slot(dev_now, s, 1, ex.image_bytes(), &aux));
+      MMF_TRY(XL.zero(s));
+      MMF_TRY(ex.run(aux, XL));
     }
     MMF_TRY(t_fb.stop(s));
-    if (stats) {
-      stats->precision_used = precision;
-      stats->col_splits = splits;
-      stats->scan_grid = grid;
-      stats->scan_ms = t_scan.ms();
-      stats->rerank_ms = t_sel.ms();
-      stats->fallback_ms = t_fb.ms();
+    fill_stats(r.stats, r.precision, splits, grid, 0.f, t_scan.ms(), t_sel.ms(), t_fb.ms(), h_fail, h_fail4[1], h_fail4[2], h_tot,
+               near_rows);
+    if (r.stats) {
       if (profile && fo.n_panels > 0) {     // what the scan stream spent waiting for panels to arrive
         float launches = 0.f;
         for (int p = 0; p < fo.n_panels; ++p) launches += t_panel[p].ms();
-        const float w = stats->scan_ms - launches;
-        stats->scan_wait_ms = w > 0.f ? w : 0.f;
+        const float w = r.stats->scan_ms - launches;
+        r.stats->scan_wait_ms = w > 0.f ? w : 0.f;
       }
-      stats->fallback_rows = h_fail;
-      stats->overflow_rows = h_fail4[1];
-      stats->short_rows = h_fail4[2];
-      int64_t tot = 0;
-      for (uint32_t v : h_tot) tot += v;
-      stats->candidates = tot;
-      stats->near_rows = near_rows;
-      stats->order_ms = t_order.ms();
-      stats->query_order = fo.perm ? 1 : 0;
+      r.stats->order_ms = t_order.ms();
+      r.stats->query_order = fo.perm ? 1 : 0;
     }
-    (void)n_; (void)m_;
     return MMF_OK;
   }
 };
@@ -485,53 +652,18 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
                    float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id,
                    void* hip_stream) {
   if (!Y) { Y = X; m = n; }
-  MMF_TRY(check_common(X, n, m, d, in_dtype, device_id));
-  if (metric < MMF_DOT || metric > MMF_RBF) { set_error("simtopk: bad metric %d", metric); return MMF_E_INVALID; }
-  if (metric == MMF_RBF && !(lambda > 0.0f)) { set_error("simtopk: MMF_RBF needs lambda > 0 (got %g)", lambda); return MMF_E_INVALID; }
-  if (k < 1) { set_error("simtopk: k must be >= 1 (got %d)", k); return MMF_E_INVALID; }
-  if (stats) memset(stats, 0, sizeof(*stats));
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  Request r{"simtopk", X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset, out_idx, out_val, stats,
+            opts && opts->profile, s};
+  MMF_TRY(r.check(opts ? opts->precision : MMF_PREC_AUTO, false, device_id, [] { return MMF_OK; }));
   if (n == 0) return MMF_OK;
-  if (!out_idx || !out_val) { set_error("simtopk: NULL output"); return MMF_E_INVALID; }
-  // admissible columns: m, minus one for rows whose own id lies in the column range
-  {
-    const int64_t lo = col_offset, hi = col_offset + m;
-    const int64_t r0 = row_offset, r1 = row_offset + n;  // any overlap -> some row loses one column
-    const bool overlap = exclude_self && (r0 < hi) && (r1 > lo);
-    const int64_t adm = m - (overlap ? 1 : 0);
-    if (k > adm) {
-      set_error("simtopk: k = %d exceeds the %lld admissible columns (m = %lld%s)", k, (long long)adm, (long long)m,
-                overlap ? ", self excluded" : "");
-      return MMF_E_INVALID;
-    }
-  }
-  const int kk = k + (exclude_self ? 1 : 0);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-
-  int precision = opts ? opts->precision : MMF_PREC_AUTO;
-  const bool profile = opts && opts->profile;
   const int forced_splits = opts ? opts->col_splits : 0;
-  if (precision == MMF_PREC_AUTO) precision = scan_bf16_supported(d, kk, in_dtype) ? MMF_PREC_FAST : MMF_PREC_EXACT;
-  if (precision != MMF_PREC_EXACT && precision != MMF_PREC_FAST && precision != MMF_PREC_FAST_BF16) {
-    set_error("simtopk: bad precision %d", precision);
-    return MMF_E_INVALID;
-  }
-  if (precision != MMF_PREC_EXACT && !scan_bf16_supported(d, kk, in_dtype)) {
-    set_error("simtopk: MMF_PREC_FAST does not support d = %lld, k = %d (use AUTO or EXACT)", (long long)d, k);
-    return MMF_E_UNSUPPORTED;
-  }
-  // k + self beyond 44 (one pass of the exact scan): several passes, each offering only what ranks after the previous pass's
-  // last entry (scikit-learn's n_neighbors is uncapped, preprocess_hypergraph.py:379)
-  const int kk_pass = kk <= 44 ? kk : 44;
-  const int cap = scan_f32_cap(kk_pass);
-  if (cap == 0) { set_error("simtopk: no list capacity for k = %d (internal)", k); return MMF_E_INTERNAL; }
+  const bool same = (Y == X) && (m == n);
 
-  if (precision != MMF_PREC_EXACT) {
+  if (r.precision != MMF_PREC_EXACT) {
     // ---- fast path: f16/bf16 MFMA scan -> exact re-rank -> exact rescan of overflowed rows -------
     const int dp = scan_bf16_dp(d);
-    const bool f16 = (precision == MMF_PREC_FAST);   // operand type of the scan, not of the input
-    const bool same = (Y == X) && (m == n);
+    const bool f16 = (r.precision == MMF_PREC_FAST);   // operand type of the scan, not of the input
     // X a row-slice of Y (the row-sharded multi-GPU case passes full[lo:hi] and full): every query-side
     // buffer is then a view into the candidate-side one and only Y is prepared.
     const size_t row_bytes = (size_t)d * dtype_size(in_dtype);
@@ -544,7 +676,7 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
     }
     const bool shared = same || slice0 >= 0;
     const int64_t n_pad = (n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256 + (slice0 >= 0 ? 256 : 0);
-    FastTail ft(n, m, kk, cap, forced_splits, dp);
+    FastTail ft(n, m, r.kk, forced_splits, dp);
     MMF_TRY(ft.set_query_order(opts ? opts->query_order : MMF_QUERY_ORDER_AUTO));
     size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + ws_bytes((size_t)n_pad * dp, 2) + ws_bytes((size_t)m_pad * dp, 2) +
                   4 * ws_bytes(n_pad, 4) + 4 * ws_bytes(m_pad, 4) + 3 * ws_bytes(4, 4) + ft.bytes();
@@ -574,7 +706,7 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
     if (!shared) MMF_HIP(hipMemsetAsync(max_q, 0, 16, s));
 
     EventTimer t_prep;
-    MMF_TRY(t_prep.start(profile, s));
+    MMF_TRY(t_prep.start(r.profile, s));
     MMF_TRY(launch_row_scalars(Y, m, d, in_dtype, metric, cy, max_n, s));
     if (!shared) MMF_TRY(launch_row_scalars(X, n, d, in_dtype, metric, rx, max_n, s));
     MMF_TRY(launch_prep_half(Y, m, d, in_dtype, metric, cy, max_n, ZC, m_pad, dp, f16 ? 1 : 0, c_zn, c_rn, c_un, c_cb, max_c, s));
@@ -582,98 +714,36 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
     MMF_TRY(t_prep.stop(s));
 
     FastOperands fo{ZQ, ZC, rx, cy, q_zn, q_rn, q_un, c_cb, max_c, (m + 255) / 256 * 256, dp, f16};
-    MMF_TRY(ft.run(X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset, fo, out_idx, out_val,
-                   profile, opts ? opts->select_wait_event : nullptr, stats, precision, s));
+    MMF_TRY(ft.run(r, fo, opts ? opts->select_wait_event : nullptr));
     if (stats) stats->prep_ms = t_prep.ms();
     return MMF_OK;
   }
 
-  // ---- exact path ------------------------------------------------------------------------------
-  const int64_t row_blocks = (n + 127) / 128, col_tiles = (m + 127) / 128;
-  const int splits = pick_splits(row_blocks, col_tiles, 0, cap, forced_splits);
-  const int lists = 2 * splits;
-  const bool same = (Y == X) && (m == n);
-  size_t need = ws_bytes(n, 4) + (same ? 0 : ws_bytes(m, 4)) + ws_bytes((size_t)n * lists, 4) +
-                ws_bytes((size_t)n * lists * cap, 4) + ws_bytes(n, 4) + ws_bytes(n, 4) + ws_bytes(4, 4) + ws_bytes(256, 4) +
-                ws_bytes(prep_f32_bytes(m, d), 1) + (same ? 0 : ws_bytes(prep_f32_bytes(n, d), 1)) + 2 * ws_bytes(n, 4);
+  // ---- exact path: everything in the call's workspace ---------------------------------------------------------------
+  ExactPass ex(r, nullptr, nullptr);
+  ex.same = same;
+  ex.forced_splits = forced_splits;
+  ex.add(ExactGroup{0, n, false, 0, m, k});
+  const size_t need = ws_bytes(n, 4) + (same ? 0 : ws_bytes(m, 4)) + ws_bytes(256, 4) + ex.image_bytes() + ex.list_bytes();
   Workspace ws;
   MMF_TRY(get_workspace(device_id, s, need, &ws));
   float* rx = ws.take<float>(n);
   float* cy = same ? rx : ws.take<float>(m);
-  CandLists L;
-  L.cnt = ws.take<uint32_t>((size_t)n * lists);
-  L.ids = ws.take<uint32_t>((size_t)n * lists * cap);
-  L.overflow = ws.take<uint32_t>(n);
-  L.lists = lists;
-  L.cap = cap;
-  int32_t* fail_rows = ws.take<int32_t>(n);
-  uint32_t* fail_count = ws.take<uint32_t>(4);
   uint32_t* cand_total = ws.take<uint32_t>(256);
-  MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
-  MMF_HIP(hipMemsetAsync(fail_count, 0, 16, s));
+  ExactLists B;
+  B.carve(ws, n, ex.list_words, ex.cap(), ex.floors());
+  ex.rx = rx; ex.cy = cy;
+  ex.cand_total = stats ? cand_total : nullptr;
+  MMF_TRY(B.zero(s));
   MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
 
-  EventTimer t_prep, t_scan, t_sel;
-  MMF_TRY(t_prep.start(profile, s));
+  EventTimer t[3];   // prep (row scalars and f32 images), scan, re-rank
+  MMF_TRY(t[0].start(r.profile, s));
   MMF_TRY(launch_row_scalars(X, n, d, in_dtype, metric, rx, nullptr, s));
   if (!same) MMF_TRY(launch_row_scalars(Y, m, d, in_dtype, metric, cy, nullptr, s));
-  // f32 operand images (mmf_prep.hip): what the exact scan's LDS-DMA copies
-  float* Yp = reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(m, d)));
-  float* Xp = same ? Yp : reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(n, d)));
-  MMF_TRY(launch_prep_f32(Y, m, d, in_dtype, nullptr, Yp, s));
-  if (!same) MMF_TRY(launch_prep_f32(X, n, d, in_dtype, nullptr, Xp, s));
-  MMF_TRY(t_prep.stop(s));
-
-  float* floor_key = ws.take<float>(n);
-  uint32_t* floor_id = ws.take<uint32_t>(n);
-  const int self1 = exclude_self ? 1 : 0;
-  const int k_pass_max = 44 - self1;              // entries one pass can emit
-  int grid = 0;
-  const bool one_pass = k <= k_pass_max;          // timers: scan and re-rank apart for one pass, the whole loop as "scan" otherwise
-  MMF_TRY(t_scan.start(profile, s));
-  for (int done = 0; done < k; done += k_pass_max) {
-    const int kp = (k - done < k_pass_max) ? (k - done) : k_pass_max;
-    const bool more = done + kp < k;
-    ScanProblem sp{};
-    sp.X = X; sp.n = n; sp.Y = Y; sp.m = m; sp.d = d; sp.dtype = in_dtype; sp.metric = metric; sp.lambda = lambda;
-    sp.Xp = Xp; sp.Yp = Yp;
-    sp.kk = kp + self1; sp.rx = rx; sp.cy = cy; sp.row_ids = nullptr; sp.n_rows = n; sp.col_splits = splits;
-    if (done > 0) { sp.floor_key = floor_key; sp.floor_id = floor_id; }
-    MMF_TRY(launch_scan_f32(sp, L, s, &grid));
-    if (one_pass) { MMF_TRY(t_scan.stop(s)); MMF_TRY(t_sel.start(profile, s)); }
-
-    SelectProblem q{};
-    q.X = X; q.n = n; q.Y = Y; q.m = m; q.d = d; q.dtype = in_dtype; q.metric = metric; q.lambda = lambda;
-    q.k = kp; q.exclude_self = exclude_self; q.row_offset = row_offset; q.col_offset = col_offset;
-    q.rx = rx; q.cy = cy; q.row_ids = nullptr; q.n_rows = n; q.out_idx = out_idx; q.out_val = out_val;
-    q.out_stride = k; q.out_off = done;
-    if (more) { q.floor_key_out = floor_key; q.floor_id_out = floor_id; }
-    q.fail_rows = fail_rows; q.fail_count = fail_count; q.cand_total = stats ? cand_total : nullptr;
-    MMF_TRY(launch_select(q, L, s));
-  }
-  if (one_pass) { MMF_TRY(t_sel.stop(s)); }
-  else { MMF_TRY(t_scan.stop(s)); MMF_TRY(t_sel.start(profile, s)); MMF_TRY(t_sel.stop(s)); }
-
-  uint32_t h_fail = 0;
-  MMF_HIP(hipMemcpyAsync(&h_fail, fail_count, 4, hipMemcpyDeviceToHost, s));
   std::vector<uint32_t> h_tot(stats ? 256 : 0);
-  if (stats) MMF_HIP(hipMemcpyAsync(h_tot.data(), cand_total, 1024, hipMemcpyDeviceToHost, s));
-  MMF_HIP(hipStreamSynchronize(s));
-  if (h_fail != 0) {
-    set_error("simtopk: %u rows failed in the exact scan (internal invariant)", h_fail);
-    return MMF_E_INTERNAL;
-  }
-  if (stats) {
-    stats->precision_used = MMF_PREC_EXACT;
-    stats->col_splits = splits;
-    stats->scan_grid = grid;
-    stats->prep_ms = t_prep.ms();
-    stats->scan_ms = t_scan.ms();
-    stats->rerank_ms = t_sel.ms();
-    int64_t tot = 0;
-    for (uint32_t v : h_tot) tot += v;
-    stats->candidates = tot;
-  }
+  MMF_TRY(ex.run(ws, B, t, stats ? &h_tot : nullptr));
+  fill_stats(stats, MMF_PREC_EXACT, ex.splits(ex.pieces[0]), ex.grid, t[0].ms(), t[1].ms(), t[2].ms(), 0.f, 0, 0, 0, h_tot);
   return MMF_OK;
 }
 
@@ -728,35 +798,23 @@ int mmf_simtopk_prepared(const void* X, int64_t n, const void* Y, int64_t m, int
                          const mmf_prepared_side* q, const mmf_prepared_side* c, int64_t m_pad, const float* maxima,
                          int operand, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
                          mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
-  MMF_TRY(check_common(X, n, m, d, in_dtype, device_id));
-  if (!Y || !q || !c || !maxima) { set_error("simtopk_prepared: NULL pointer"); return MMF_E_INVALID; }
-  if (metric < MMF_DOT || metric > MMF_RBF) { set_error("simtopk_prepared: bad metric %d", metric); return MMF_E_INVALID; }
-  if (metric == MMF_RBF && !(lambda > 0.0f)) { set_error("simtopk_prepared: MMF_RBF needs lambda > 0"); return MMF_E_INVALID; }
-  if (operand != MMF_F16 && operand != MMF_BF16) { set_error("simtopk_prepared: bad operand"); return MMF_E_INVALID; }
-  if (k < 1) { set_error("simtopk_prepared: k must be >= 1"); return MMF_E_INVALID; }
-  if (m_pad < m || (m_pad % 256) != 0) { set_error("simtopk_prepared: m_pad must be a multiple of 256 and >= m"); return MMF_E_INVALID; }
-  if (stats) memset(stats, 0, sizeof(*stats));
+  Request r{"simtopk_prepared", X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset, out_idx, out_val,
+            stats, opts && opts->profile, static_cast<hipStream_t>(hip_stream)};
+  MMF_TRY(r.check(operand == MMF_F16 ? MMF_PREC_FAST : MMF_PREC_FAST_BF16, false, device_id, [&] {
+    if (!Y || !q || !c || !maxima) { set_error("simtopk_prepared: NULL pointer"); return MMF_E_INVALID; }
+    if (operand != MMF_F16 && operand != MMF_BF16) { set_error("simtopk_prepared: bad operand"); return MMF_E_INVALID; }
+    if (m_pad < m || (m_pad % 256) != 0) { set_error("simtopk_prepared: m_pad must be a multiple of 256 and >= m"); return MMF_E_INVALID; }
+    return MMF_OK;
+  }));
   if (n == 0) return MMF_OK;
-  {
-    const bool overlap = exclude_self && (row_offset < col_offset + m) && (row_offset + n > col_offset);
-    if (k > m - (overlap ? 1 : 0)) { set_error("simtopk_prepared: k exceeds the admissible columns"); return MMF_E_INVALID; }
-  }
-  const int kk = k + (exclude_self ? 1 : 0);
-  if (!scan_bf16_supported(d, kk, in_dtype)) { set_error("simtopk_prepared: d = %lld / k = %d not supported by the 16-bit scan", (long long)d, k); return MMF_E_UNSUPPORTED; }
-  const int cap = scan_f32_cap(kk);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  FastTail ft(n, m, kk, cap, opts ? opts->col_splits : 0, scan_bf16_dp(d));
+  FastTail ft(n, m, r.kk, opts ? opts->col_splits : 0, scan_bf16_dp(d));
   MMF_TRY(ft.set_query_order(opts ? opts->query_order : MMF_QUERY_ORDER_AUTO));
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ft.bytes(), &ws));
+  MMF_TRY(get_workspace(device_id, r.s, ft.bytes(), &ws));
   ft.carve(ws);
   FastOperands fo{static_cast<const uint16_t*>(q->Z), static_cast<const uint16_t*>(c->Z), q->scal, c->scal, q->zn, q->rn, q->un,
                   c->cb, reinterpret_cast<const uint32_t*>(maxima), m_pad, scan_bf16_dp(d), operand == MMF_F16};
-  return ft.run(X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset, fo, out_idx, out_val,
-                opts && opts->profile, opts ? opts->select_wait_event : nullptr, stats,
-                operand == MMF_F16 ? MMF_PREC_FAST : MMF_PREC_FAST_BF16, s);
+  return ft.run(r, fo, opts ? opts->select_wait_event : nullptr);
 }
 
 int mmf_simtopk_panels(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
@@ -764,54 +822,43 @@ int mmf_simtopk_panels(const void* X, int64_t n, const void* Y, int64_t m, int64
                        const mmf_prepared_side* q, const float* c_scal, const mmf_panel* panels, int n_panels,
                        const float* maxima, int operand, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
                        mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
-  MMF_TRY(check_common(X, n, m, d, in_dtype, device_id));
-  if (!Y || !q || !c_scal || !panels || !maxima) { set_error("simtopk_panels: NULL pointer"); return MMF_E_INVALID; }
-  if (metric < MMF_DOT || metric > MMF_RBF) { set_error("simtopk_panels: bad metric %d", metric); return MMF_E_INVALID; }
-  if (metric == MMF_RBF && !(lambda > 0.0f)) { set_error("simtopk_panels: MMF_RBF needs lambda > 0"); return MMF_E_INVALID; }
-  if (operand != MMF_F16 && operand != MMF_BF16) { set_error("simtopk_panels: bad operand"); return MMF_E_INVALID; }
-  if (k < 1) { set_error("simtopk_panels: k must be >= 1"); return MMF_E_INVALID; }
-  if (n_panels < 1 || n_panels > 16) { set_error("simtopk_panels: n_panels must be in 1..16"); return MMF_E_INVALID; }
-  int64_t covered = 0, m_min = m, m_max = 0;
-  for (int p = 0; p < n_panels; ++p) {
-    const mmf_panel& P = panels[p];
-    if (!P.Z || !P.cb || P.m < 1 || P.m_pad < P.m || (P.m_pad % 256) != 0 || P.seg_len < 0 || P.id_base < 0 ||
-        (P.seg_len > 0 && (P.seg_stride < P.seg_len || (P.m % P.seg_len) != 0))) {
-      set_error("simtopk_panels: panel %d is malformed", p); return MMF_E_INVALID;
+  Request r{"simtopk_panels", X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset, out_idx, out_val,
+            stats, opts && opts->profile, static_cast<hipStream_t>(hip_stream)};
+  int64_t m_min = m, m_max = 0;
+  MMF_TRY(r.check(operand == MMF_F16 ? MMF_PREC_FAST : MMF_PREC_FAST_BF16, false, device_id, [&] {
+    if (!Y || !q || !c_scal || !panels || !maxima) { set_error("simtopk_panels: NULL pointer"); return MMF_E_INVALID; }
+    if (operand != MMF_F16 && operand != MMF_BF16) { set_error("simtopk_panels: bad operand"); return MMF_E_INVALID; }
+    if (n_panels < 1 || n_panels > 16) { set_error("simtopk_panels: n_panels must be in 1..16"); return MMF_E_INVALID; }
+    int64_t covered = 0;
+    for (int p = 0; p < n_panels; ++p) {
+      const mmf_panel& P = panels[p];
+      if (!P.Z || !P.cb || P.m < 1 || P.m_pad < P.m || (P.m_pad % 256) != 0 || P.seg_len < 0 || P.id_base < 0 ||
+          (P.seg_len > 0 && (P.seg_stride < P.seg_len || (P.m % P.seg_len) != 0))) {
+        set_error("simtopk_panels: panel %d is malformed", p); return MMF_E_INVALID;
+      }
+      const int64_t last = P.seg_len ? P.id_base + (P.m / P.seg_len - 1) * P.seg_stride + P.seg_len - 1 : P.id_base + P.m - 1;
+      if (last >= m) { set_error("simtopk_panels: panel %d maps past column %lld", p, (long long)m); return MMF_E_INVALID; }
+      covered += P.m;
+      if (P.m < m_min) m_min = P.m;
+      if (P.m_pad > m_max) m_max = P.m_pad;
     }
-    const int64_t last = P.seg_len ? P.id_base + (P.m / P.seg_len - 1) * P.seg_stride + P.seg_len - 1 : P.id_base + P.m - 1;
-    if (last >= m) { set_error("simtopk_panels: panel %d maps past column %lld", p, (long long)m); return MMF_E_INVALID; }
-    covered += P.m;
-    if (P.m < m_min) m_min = P.m;
-    if (P.m_pad > m_max) m_max = P.m_pad;
-  }
-  if (covered != m) { set_error("simtopk_panels: panels cover %lld columns, Y has %lld", (long long)covered, (long long)m); return MMF_E_INVALID; }
-  if (stats) memset(stats, 0, sizeof(*stats));
+    if (covered != m) { set_error("simtopk_panels: panels cover %lld columns, Y has %lld", (long long)covered, (long long)m); return MMF_E_INVALID; }
+    return MMF_OK;
+  }));
   if (n == 0) return MMF_OK;
-  {
-    const bool overlap = exclude_self && (row_offset < col_offset + m) && (row_offset + n > col_offset);
-    if (k > m - (overlap ? 1 : 0)) { set_error("simtopk_panels: k exceeds the admissible columns"); return MMF_E_INVALID; }
-  }
-  const int kk = k + (exclude_self ? 1 : 0);
-  if (!scan_bf16_supported(d, kk, in_dtype)) { set_error("simtopk_panels: d = %lld / k = %d not supported by the 16-bit scan", (long long)d, k); return MMF_E_UNSUPPORTED; }
-  const int cap = scan_f32_cap(kk);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  FastTail ft(n, m, kk, cap, opts ? opts->col_splits : 0, scan_bf16_dp(d), n_panels, m_min, m_max);
+  FastTail ft(n, m, r.kk, opts ? opts->col_splits : 0, scan_bf16_dp(d), n_panels, m_min, m_max);
   MMF_TRY(ft.set_query_order(opts ? opts->query_order : MMF_QUERY_ORDER_AUTO));
-  if ((int64_t)ft.lists * ft.bcap + FastTail::kSpillCap > 1024) {
+  if ((int64_t)ft.lists * ft.bcap + kSpillCap > 1024) {
     set_error("simtopk_panels: %d panels x %d-entry lists exceed the 1024 candidates a row can hand to the re-rank (k = %d): use fewer panels", n_panels, ft.bcap, k);
     return MMF_E_UNSUPPORTED;
   }
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ft.bytes(), &ws));
+  MMF_TRY(get_workspace(device_id, r.s, ft.bytes(), &ws));
   ft.carve(ws);
   FastOperands fo{static_cast<const uint16_t*>(q->Z), nullptr, q->scal, c_scal, q->zn, q->rn, q->un,
                   nullptr, reinterpret_cast<const uint32_t*>(maxima), 0, scan_bf16_dp(d), operand == MMF_F16};
   fo.panels = panels; fo.n_panels = n_panels;
-  return ft.run(X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset, fo, out_idx, out_val,
-                opts && opts->profile, opts ? opts->select_wait_event : nullptr, stats,
-                operand == MMF_F16 ? MMF_PREC_FAST : MMF_PREC_FAST_BF16, s);
+  return ft.run(r, fo, opts ? opts->select_wait_event : nullptr);
 }
 
 int mmf_topk_merge(const int64_t* ia, const float* va, const int64_t* ib, const float* vb, int64_t n, int k,
@@ -1225,67 +1272,49 @@ int mmf_combined_threshold_edges(const float* F, const float* P, int64_t n, int6
 // driven by a host-built work table (a workgroup = one row block of one segment against that segment's tiles), the
 // audit and the exact re-rank over all rows, then one host synchronisation.  Rows the 16-bit path cannot certify, and
 // every row of a segment with fewer than k admissible columns (or of every segment under MMF_PREC_EXACT), go through the
-// exact f32 scan segment by segment: two launches per segment, not a work table ("Exact rows").
+// exact pass (ExactPass) segment by segment: two launches per segment, not a work table ("Exact rows").
 int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
                           float lambda, int k, int exclude_self, const int64_t* x_ptr_host, const int64_t* y_ptr_host,
                           int64_t n_segments, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
                           mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
   const bool self = (Y == nullptr);
   if (self) { Y = X; m = n; y_ptr_host = x_ptr_host; }
-  MMF_TRY(check_common(X, n, m, d, in_dtype, device_id));
-  if (metric < MMF_DOT || metric > MMF_RBF) { set_error("simtopk_segmented: bad metric %d", metric); return MMF_E_INVALID; }
-  if (metric == MMF_RBF && !(lambda > 0.0f)) { set_error("simtopk_segmented: MMF_RBF needs lambda > 0 (got %g)", lambda); return MMF_E_INVALID; }
-  if (k < 1) { set_error("simtopk_segmented: k must be >= 1 (got %d)", k); return MMF_E_INVALID; }
-  if (n_segments < 0 || !x_ptr_host || !y_ptr_host) { set_error("simtopk_segmented: bad segment offsets"); return MMF_E_INVALID; }
-  if (x_ptr_host[0] != 0 || x_ptr_host[n_segments] != n || y_ptr_host[0] != 0 || y_ptr_host[n_segments] != m) {
-    set_error("simtopk_segmented: offsets must start at 0 and end at n = %lld / m = %lld", (long long)n, (long long)m);
-    return MMF_E_INVALID;
-  }
-  for (int64_t g = 0; g < n_segments; ++g)
-    if (x_ptr_host[g + 1] < x_ptr_host[g] || y_ptr_host[g + 1] < y_ptr_host[g]) {
-      set_error("simtopk_segmented: offsets must be non-decreasing (segment %lld)", (long long)g);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  Request r{"simtopk_segmented", X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, 0, 0, out_idx, out_val, stats,
+            opts && opts->profile, s};
+  MMF_TRY(r.check(opts ? opts->precision : MMF_PREC_AUTO, true, device_id, [&] {
+    if (n_segments < 0 || !x_ptr_host || !y_ptr_host) { set_error("simtopk_segmented: bad segment offsets"); return MMF_E_INVALID; }
+    if (x_ptr_host[0] != 0 || x_ptr_host[n_segments] != n || y_ptr_host[0] != 0 || y_ptr_host[n_segments] != m) {
+      set_error("simtopk_segmented: offsets must start at 0 and end at n = %lld / m = %lld", (long long)n, (long long)m);
       return MMF_E_INVALID;
     }
-  if (m > 0 && !Y) { set_error("simtopk_segmented: Y is NULL"); return MMF_E_INVALID; }
-  const int self1 = exclude_self ? 1 : 0;
-  const int kk = k + self1;
-  if (kk > 44) { set_error("simtopk_segmented: k + self = %d > 44 is not supported", kk); return MMF_E_UNSUPPORTED; }
-  if (opts && (opts->col_splits != 0 || opts->select_wait_event)) {
-    set_error("simtopk_segmented: col_splits and select_wait_event are not supported");
-    return MMF_E_UNSUPPORTED;
-  }
-  if (stats) { memset(stats, 0, sizeof(*stats)); stats->near_rows = -1; }
+    for (int64_t g = 0; g < n_segments; ++g)
+      if (x_ptr_host[g + 1] < x_ptr_host[g] || y_ptr_host[g + 1] < y_ptr_host[g]) {
+        set_error("simtopk_segmented: offsets must be non-decreasing (segment %lld)", (long long)g);
+        return MMF_E_INVALID;
+      }
+    if (m > 0 && !Y) { set_error("simtopk_segmented: Y is NULL"); return MMF_E_INVALID; }
+    // (lifting this is a matter of letting the exact pass take such segments: it runs the passes k + self > 44 needs)
+    if (r.kk > 44) { set_error("simtopk_segmented: k + self = %d > 44 is not supported", r.kk); return MMF_E_UNSUPPORTED; }
+    if (opts && (opts->col_splits != 0 || opts->select_wait_event)) {
+      set_error("simtopk_segmented: col_splits and select_wait_event are not supported");
+      return MMF_E_UNSUPPORTED;
+    }
+    return MMF_OK;
+  }));
+  if (stats) stats->near_rows = -1;   // the query order is never probed here
   if (n == 0) return MMF_OK;
-  if (!out_idx || !out_val) { set_error("simtopk_segmented: NULL output"); return MMF_E_INVALID; }
-  int precision = opts ? opts->precision : MMF_PREC_AUTO;
-  const bool profile = opts && opts->profile;
-  if (precision == MMF_PREC_AUTO) precision = scan_bf16_supported(d, kk, in_dtype) ? MMF_PREC_FAST : MMF_PREC_EXACT;
-  if (precision != MMF_PREC_EXACT && precision != MMF_PREC_FAST && precision != MMF_PREC_FAST_BF16) {
-    set_error("simtopk_segmented: bad precision %d", precision);
-    return MMF_E_INVALID;
-  }
-  if (precision != MMF_PREC_EXACT && !scan_bf16_supported(d, kk, in_dtype)) {
-    set_error("simtopk_segmented: MMF_PREC_FAST does not support d = %lld, k = %d (use AUTO or EXACT)", (long long)d, k);
-    return MMF_E_UNSUPPORTED;
-  }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  const int precision = r.precision;
+  const bool profile = r.profile;
   const int64_t S = n_segments;
   const int64_t* xp = x_ptr_host;
   const int64_t* yp = y_ptr_host;
-  // admissible columns of segment g: its m_g columns, minus one when a row's own id may lie among them
   std::vector<int64_t> adm(S);
-  for (int64_t g = 0; g < S; ++g) {
-    const bool overlap = exclude_self && xp[g] < yp[g + 1] && xp[g + 1] > yp[g];
-    adm[g] = (yp[g + 1] - yp[g]) - (overlap ? 1 : 0);
-  }
-  const size_t esz = dtype_size(in_dtype);
+  for (int64_t g = 0; g < S; ++g) adm[g] = admissible_columns(xp[g], xp[g + 1] - xp[g], yp[g], yp[g + 1] - yp[g], exclude_self);
   const bool fast = precision != MMF_PREC_EXACT;
   const int dp = fast ? scan_bf16_dp(d) : 0;
   const int qt = fast ? scan_b16_queries_per_block(dp) : 1;
   constexpr int kTile = 32;                       // candidate rows per tile of the 16-bit scan (B_CT)
-  constexpr int kSpillCap = FastTail::kSpillCap;
   // segments the 16-bit scan serves: rows present and at least k admissible columns (the others are done exactly)
   std::vector<char> on_fast(S, 0);
   int64_t nq_pos = 0, mc_pos = 0;
@@ -1327,13 +1356,12 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
 
   // ---- workspace (slot 0): row scalars, the 16-bit images, tables, lists -------------------------------------------
   const int64_t nq_pad = (nq_pos + 255) / 256 * 256, mc_pad = (mc_pos + 255) / 256 * 256;
-  const int bcap = fast ? scan_bf16_cap(kk, dp) : 0;
+  const int bcap = fast ? scan_bf16_cap(r.kk, dp) : 0;
   const int64_t n_seed = n;
   size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + ws_bytes(n, 4) + ws_bytes(4, 4) + ws_bytes(256, 4);
   if (grid > 0)
     need += ws_bytes((size_t)nq_pad * dp, 2) + 4 * ws_bytes(nq_pad, 4) + ws_bytes((size_t)mc_pad * dp, 2) + 4 * ws_bytes(mc_pad, 4) +
-            3 * ws_bytes(4, 4) + ws_bytes(sched.size(), 4) + ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + ws_bytes((size_t)n * 2, 4) +
-            ws_bytes((size_t)n * 2 * bcap, 4) + 2 * ws_bytes(n, 4) + ws_bytes((size_t)n * kSpillCap, 4) +
+            3 * ws_bytes(4, 4) + ws_bytes(sched.size(), 4) + ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + b16_lists_bytes(n, 2, bcap) +
             ws_bytes(scan_b16_seg_scratch_bytes(grid, dp, bcap), 1) + ws_bytes(2 * (size_t)n_seed, 4) + ws_bytes(select_order_bytes(n), 1);
   Workspace ws;
   MMF_TRY(get_workspace(device_id, s, need, &ws));
@@ -1365,16 +1393,7 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
     int32_t* d_sched = ws.take<int32_t>(sched.size());
     int32_t* d_qg = ws.take<int32_t>(nq_pos);
     int32_t* d_cg = ws.take<int32_t>(mc_pos);
-    CandLists L;
-    L.cnt = ws.take<uint32_t>((size_t)n * 2);
-    L.ids = ws.take<uint32_t>((size_t)n * 2 * bcap);
-    L.keys = nullptr; L.margin = nullptr;   // one list pair per row: nothing to prune against
-    L.overflow = ws.take<uint32_t>(n);
-    L.lists = 2; L.cap = bcap; L.slot_ulp = scan_bf16_slot_ulp(bcap);
-    L.spill_cnt = ws.take<uint32_t>(n);
-    L.spill_ids = ws.take<uint32_t>((size_t)n * kSpillCap);
-    L.spill_cap = kSpillCap;
-    L.spill_stacks = getenv("MMF_SPILL_COUNTER") ? 0 : 1;
+    const CandLists L = carve_b16_lists(ws, n, 2, bcap);
     char* scan_scratch = ws.take<char>(scan_b16_seg_scratch_bytes(grid, dp, bcap));
     int32_t* seed = ws.take<int32_t>(2 * (size_t)n_seed);
     char* order_scratch = ws.take<char>(select_order_bytes(n));
@@ -1397,7 +1416,7 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
     ScanB16Panel pn;
     pn.seed = seed; pn.seed_stride = n_seed; pn.share = 0;
     MMF_TRY(t_scan.start(profile, s));
-    MMF_TRY(launch_scan_b16_seg(ZQ, ZC, c_cb, q_zn, q_rn, q_un, max_c, d_sched, grid, n, m, dp, d, f16, metric, kk, L,
+    MMF_TRY(launch_scan_b16_seg(ZQ, ZC, c_cb, q_zn, q_rn, q_un, max_c, d_sched, grid, n, m, dp, d, f16, metric, r.kk, L,
                                 scan_scratch, pn, s));
     MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
     MMF_TRY(t_scan.stop(s));
@@ -1421,146 +1440,54 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
     MMF_TRY(t_prep.stop(s));
   }
 
-  // ---- exact f32 pass: per segment, the rows the scan did not certify or did not serve ------------------------------
-  // Two launches (scan, re-rank) per group, one group per segment: whole segments (short of admissible columns, or every
-  // segment under MMF_PREC_EXACT) as slices of X, Y and their f32 images; rows the 16-bit path flagged gathered, in pieces
-  // and batches of at most kFB rows (the f32 image of a batch is all that is prepared at once).
-  struct Group { int64_t seg, off, cnt; int ks; bool whole; };
-  constexpr int64_t kFB = 4096;
-  std::vector<int32_t> ex_rows;         // flagged rows, grouped by segment, ascending
-  std::vector<Group> groups;
-  int64_t fallback_rows = 0;
-  bool any_whole = false;
-  {
-    std::vector<std::vector<int32_t>> flagged(fast ? S : 0);
-    for (int32_t r : h_fail_rows) {
-      const int64_t g = (int64_t)(std::upper_bound(xp, xp + S + 1, (int64_t)r) - xp) - 1;
-      if (g >= 0 && g < S && on_fast[g]) { flagged[g].push_back(r); ++fallback_rows; }
-    }
-    for (int64_t g = 0; g < S; ++g) {
-      const int64_t ng = xp[g + 1] - xp[g];
-      if (ng == 0) continue;
-      if (!on_fast[g]) {
-        int ks = k;
-        if (adm[g] < k) {   // a segment short of admissible columns: its top-(m_g - self) first, then -1 / -inf
-          MMF_HIP(hipMemsetAsync(out_idx + xp[g] * k, 0xff, (size_t)ng * k * 8, s));
-          MMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out_val + xp[g] * k), (int)0xff800000u, (size_t)ng * k, s));
-          ks = (int)(adm[g] > 0 ? adm[g] : 0);
-        }
-        if (ks == 0) continue;
-        groups.push_back(Group{g, xp[g], ng, ks, true});
-        any_whole = true;
-      } else if (!flagged[g].empty()) {
-        std::sort(flagged[g].begin(), flagged[g].end());
-        for (size_t i = 0; i < flagged[g].size(); i += kFB) {
-          const int64_t off = (int64_t)ex_rows.size();
-          const size_t e = std::min(flagged[g].size(), i + (size_t)kFB);
-          ex_rows.insert(ex_rows.end(), flagged[g].begin() + i, flagged[g].begin() + e);
-          groups.push_back(Group{g, off, (int64_t)(e - i), k, false});
-        }
+  // ---- exact pass: per segment, the rows the scan did not certify or did not serve ----------------------------------
+  // whole segments (short of admissible columns, or every segment under MMF_PREC_EXACT) as slices of X and Y; the rows
+  // the 16-bit path flagged gathered per segment
+  ExactPass ex(r, rx, cy);
+  ex.same = self;
+  std::vector<int32_t> ex_rows;   // flagged rows of the segments the scan served, ascending: grouped by segment
+  for (int32_t row : h_fail_rows) {
+    const int64_t g = (int64_t)(std::upper_bound(xp, xp + S + 1, (int64_t)row) - xp) - 1;
+    if (g >= 0 && g < S && on_fast[g]) ex_rows.push_back(row);
+  }
+  std::sort(ex_rows.begin(), ex_rows.end());
+  const int64_t fallback_rows = (int64_t)ex_rows.size();
+  for (int64_t g = 0, e = 0; g < S; ++g) {
+    const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g], e0 = e;
+    if (on_fast[g]) {
+      while (e < fallback_rows && ex_rows[e] < xp[g + 1]) ++e;
+      if (e > e0) ex.add(ExactGroup{e0, e - e0, true, yp[g], mg, k});
+    } else if (ng > 0) {
+      int ks = k;
+      if (adm[g] < k) {   // a segment short of admissible columns: its top-(m_g - self) first, then -1 / -inf
+        MMF_HIP(hipMemsetAsync(out_idx + xp[g] * k, 0xff, (size_t)ng * k * 8, s));
+        MMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out_val + xp[g] * k), (int)0xff800000u, (size_t)ng * k, s));
+        ks = (int)(adm[g] > 0 ? adm[g] : 0);
       }
+      if (ks > 0) ex.add(ExactGroup{xp[g], ng, false, yp[g], mg, ks});
     }
   }
-  MMF_TRY(t_fb.start(profile && !groups.empty(), s));
-  int ex_grid = 0;
-  if (!groups.empty()) {
-    const int64_t E = (int64_t)ex_rows.size();
-    const int64_t XB = E < kFB ? E : kFB;       // rows of the gathered image
-    const int cap_max = scan_f32_cap(kk);
-    if (cap_max == 0) { set_error("simtopk_segmented: no list capacity for k = %d (internal)", k); return MMF_E_INTERNAL; }
-    size_t list_words = 0;
-    std::vector<int> g_splits(groups.size());
-    int64_t rows_total = 0;
-    for (size_t i = 0; i < groups.size(); ++i) {
-      const Group& G = groups[i];
-      const int64_t mg = yp[G.seg + 1] - yp[G.seg];
-      g_splits[i] = pick_splits((G.cnt + 127) / 128, (mg + 127) / 128, 0, cap_max, 0);
-      list_words = std::max(list_words, (size_t)G.cnt * 2 * g_splits[i]);
-      rows_total += G.cnt;
-    }
-    // f32 images: all of Y; all of X for whole segments (self: the same image); the gathered batch of flagged rows
-    const bool own_x = any_whole && !self;
+  MMF_TRY(t_fb.start(profile && !ex.pieces.empty(), s));
+  if (!ex.pieces.empty()) {   // lists and f32 images in the second workspace slot
+    ex.n_ids = fallback_rows;
     int dev_now = 0;
     MMF_HIP(hipGetDevice(&dev_now));
     Workspace aux;
-    MMF_TRY(get_workspace_slot(dev_now, s, 1,
-                               ws_bytes(prep_f32_bytes(m, d), 1) + (own_x ? ws_bytes(prep_f32_bytes(n, d), 1) : 0) +
-                                   (XB > 0 ? ws_bytes(prep_f32_bytes(XB, d), 1) : 0) + ws_bytes(E, 4) + ws_bytes(list_words, 4) +
-                                   ws_bytes(list_words * cap_max, 4) + ws_bytes(rows_total, 4) + ws_bytes(4, 4) + ws_bytes(rows_total, 4),
-                               &aux));
-    float* Yp = reinterpret_cast<float*>(aux.take<char>(prep_f32_bytes(m, d)));
-    float* Xp = self ? Yp : (own_x ? reinterpret_cast<float*>(aux.take<char>(prep_f32_bytes(n, d))) : nullptr);
-    float* Xe = XB > 0 ? reinterpret_cast<float*>(aux.take<char>(prep_f32_bytes(XB, d))) : nullptr;
-    int32_t* d_rows = aux.take<int32_t>(E);
-    CandLists FL;
-    FL.cnt = aux.take<uint32_t>(list_words);
-    FL.ids = aux.take<uint32_t>(list_words * cap_max);
-    uint32_t* overflow = aux.take<uint32_t>(rows_total);   // one slice per group: a single memset
-    uint32_t* ex_fail_count = aux.take<uint32_t>(4);
-    int32_t* ex_fail_rows = aux.take<int32_t>(rows_total);
-    if (E > 0) MMF_HIP(hipMemcpyAsync(d_rows, ex_rows.data(), (size_t)E * 4, hipMemcpyHostToDevice, s));
-    MMF_HIP(hipMemsetAsync(ex_fail_count, 0, 16, s));
-    MMF_HIP(hipMemsetAsync(overflow, 0, (size_t)rows_total * 4, s));
-    MMF_TRY(launch_prep_f32(Y, m, d, in_dtype, nullptr, Yp, s));
-    if (own_x) MMF_TRY(launch_prep_f32(X, n, d, in_dtype, nullptr, Xp, s));
-    const int64_t dpad = prep_f32_dim(d);
-    int64_t batch0 = -1, ov = 0;                  // first flagged position of the batch in Xe
-    for (size_t i = 0; i < groups.size(); ++i) {
-      const Group& G = groups[i];
-      const int64_t y0 = yp[G.seg], mg = yp[G.seg + 1] - y0;
-      if (!G.whole && (batch0 < 0 || G.off + G.cnt > batch0 + kFB)) {   // next batch of flagged rows
-        batch0 = G.off;
-        MMF_TRY(launch_prep_f32(X, std::min(kFB, E - batch0), d, in_dtype, d_rows + batch0, Xe, s));
-      }
-      FL.lists = 2 * g_splits[i];
-      FL.cap = scan_f32_cap(G.ks + self1);
-      FL.overflow = overflow + ov;
-      ov += G.cnt;
-      const char* Xs = static_cast<const char*>(X) + (G.whole ? (size_t)G.off * d * esz : 0);
-      const int64_t r0 = G.whole ? G.off : 0;    // whole segments: X, its scalars and the outputs as slices
-      ScanProblem sp{};
-      sp.X = Xs; sp.n = G.whole ? G.cnt : n; sp.Y = static_cast<const char*>(Y) + (size_t)y0 * d * esz; sp.m = mg; sp.d = d;
-      sp.dtype = in_dtype; sp.metric = metric; sp.lambda = lambda;
-      sp.Xp = G.whole ? Xp + G.off * dpad : Xe + (G.off - batch0) * dpad; sp.Yp = Yp + y0 * dpad;
-      sp.kk = G.ks + self1; sp.rx = rx + r0; sp.cy = cy + y0;
-      sp.row_ids = G.whole ? nullptr : d_rows + G.off; sp.n_rows = G.cnt;
-      sp.col_splits = g_splits[i];
-      int gg = 0;
-      MMF_TRY(launch_scan_f32(sp, FL, s, &gg));
-      ex_grid += gg;
-      SelectProblem fq{};
-      fq.X = Xs; fq.n = sp.n; fq.Y = sp.Y; fq.m = mg; fq.d = d; fq.dtype = in_dtype; fq.metric = metric; fq.lambda = lambda;
-      fq.k = G.ks; fq.exclude_self = exclude_self; fq.row_offset = r0; fq.col_offset = y0;
-      fq.rx = sp.rx; fq.cy = sp.cy; fq.row_ids = sp.row_ids; fq.n_rows = G.cnt;
-      fq.out_idx = out_idx + r0 * k; fq.out_val = out_val + r0 * k; fq.out_stride = k; fq.out_off = 0;
-      fq.fail_rows = ex_fail_rows; fq.fail_count = ex_fail_count; fq.cand_total = nullptr;
-      MMF_TRY(launch_select(fq, FL, s));
-    }
-    uint32_t h_ex = 0;
-    MMF_HIP(hipMemcpyAsync(&h_ex, ex_fail_count, 4, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipStreamSynchronize(s));
-    if (h_ex != 0) {
-      set_error("simtopk_segmented: %u rows failed in the exact scan (internal invariant)", h_ex);
-      return MMF_E_INTERNAL;
-    }
+    MMF_TRY(get_workspace_slot(dev_now, s, 1, ex.image_bytes() + ex.list_bytes() + ws_bytes(ex.n_ids, 4), &aux));
+    int32_t* d_rows = aux.take<int32_t>(ex.n_ids);
+    ExactLists B;
+    B.carve(aux, ex.rows_total, ex.list_words, ex.cap(), false);
+    ex.row_ids = d_rows;
+    if (ex.n_ids > 0) MMF_HIP(hipMemcpyAsync(d_rows, ex_rows.data(), (size_t)ex.n_ids * 4, hipMemcpyHostToDevice, s));
+    MMF_TRY(B.zero(s));
+    MMF_TRY(ex.run(aux, B));
   }
   MMF_TRY(t_fb.stop(s));
   MMF_HIP(hipStreamSynchronize(s));
-  if (stats) {
-    stats->precision_used = grid > 0 ? precision : MMF_PREC_EXACT;
-    stats->col_splits = 1;
-    stats->scan_grid = grid > 0 ? (int)grid : ex_grid;
-    stats->prep_ms = t_prep.ms();
-    stats->scan_ms = grid > 0 ? t_scan.ms() : t_fb.ms();
-    stats->rerank_ms = t_sel.ms();
-    stats->fallback_ms = grid > 0 ? t_fb.ms() : 0.f;
-    stats->fallback_rows = fallback_rows;
-    stats->overflow_rows = h_fail4[1] < (uint32_t)fallback_rows ? h_fail4[1] : fallback_rows;
-    stats->short_rows = fallback_rows - stats->overflow_rows;
-    int64_t tot = 0;
-    for (uint32_t v : h_tot) tot += v;
-    stats->candidates = tot;
-  }
+  const int64_t overflow_rows = h_fail4[1] < (uint32_t)fallback_rows ? h_fail4[1] : fallback_rows;
+  fill_stats(stats, grid > 0 ? precision : MMF_PREC_EXACT, 1, grid > 0 ? (int)grid : ex.grid, t_prep.ms(),
+             grid > 0 ? t_scan.ms() : t_fb.ms(), t_sel.ms(), grid > 0 ? t_fb.ms() : 0.f, fallback_rows, overflow_rows,
+             fallback_rows - overflow_rows, h_tot);
   return MMF_OK;
 }
 

@@ -69,13 +69,14 @@ def test_dense_equals_topk_of_dense(mmf):
     assert torch.equal(idx[~ties], i[~ties])
 
 
-@pytest.mark.parametrize("flag_rows", [1, 5, 48, 49, 300])
+@pytest.mark.parametrize("flag_rows", [1, 5, 48, 49, 300, 8200])
 @pytest.mark.parametrize("metric,dtype", [("cosine", torch.float32), ("neg_sq_l2", torch.float32), ("rbf", torch.float16)])
 def test_flagged_rows_take_the_exact_paths(mmf, monkeypatch, flag_rows, metric, dtype):
     """Rows the fast path cannot certify are redone exactly: up to 48 of them by the row-vs-all kernels,
     more by the matrix-core rescan.  MMF_DEBUG_FLAG_ROWS flags the first rows artificially."""
     X = (make(9000, 120, 7, unit=False) * (0.05 if metric == "rbf" else 1.0)).to(dtype)
-    ref = mmf.simtopk(X, metric=metric, lam=0.5, k=4, precision="exact")
+    ref = mmf.simtopk(X, metric=metric, lam=0.5, k=4, precision="exact", return_stats=True)
+    assert ref[2]["near_rows"] == -1                                   # the exact path never probes the query order
     monkeypatch.setenv("MMF_DEBUG_FLAG_ROWS", str(flag_rows))
     idx, val, st = mmf.simtopk(X, metric=metric, lam=0.5, k=4, precision="fast", return_stats=True)
     assert st["fallback_rows"] >= flag_rows
