@@ -412,6 +412,28 @@ int mmf_kmeans_fit(const float* X, int64_t n, int64_t d, int64_t n_clusters, int
                    const int64_t* first_centres, const double* uniforms, int max_iter, double tol, int64_t* labels,
                    float* centres, int64_t* seeds, double* info, int device_id, void* hip_stream);
 
+/*
+ * The same fit for every segment of a ragged batch in one call: for segment s, rows X[ptr[s]:ptr[s+1]], it returns bit for
+ * bit what mmf_kmeans_fit returns on that slice (labels, centres, seeds, inertia, iterations, best restart, ambiguity
+ * counts).  All segments share d, n_clusters, n_init, trials, max_iter, tol and the uniforms: scikit-learn's stream is data
+ * independent except for the first centre of each restart, so only first_centres is per segment.
+ *   ptr [n_seg + 1] HOST offsets (0 = ptr[0] <= ... <= ptr[n_seg] = n), every segment with at least n_clusters rows;
+ *   first_centres [n_seg][n_init] HOST, row ids local to the segment; uniforms [n_init][n_clusters - 1][trials] HOST, shared;
+ *   labels [n] int64 device, 0 .. n_clusters - 1 within each segment; centres [n_seg][n_clusters][d] f32 device or NULL;
+ *   seeds [n_seg][n_init][n_clusters] int64 device or NULL, GLOBAL row ids (ptr[s] + local);
+ *   info (host, n_seg x (7 + 2 n_init) doubles, or NULL): per segment as mmf_kmeans_fit's info; [6], the lockstep iteration
+ *   count, is that of the group the segment ran in.
+ * Segments run in groups of consecutive segments (sum of n_init * n_clusters <= 16384, sum of n_init * n_s < 2^31, bounded
+ * scratch), one after the other on the stream, each with its own lockstep and one status read per Lloyd iteration.
+ * Errors, checked on the host before any device work: MMF_E_INVALID for a bad ptr, a segment shorter than n_clusters or
+ * NULL pointers; MMF_E_UNSUPPORTED when one segment alone breaks a limit of mmf_kmeans_fit (n_init * n_clusters > 16384,
+ * n_init * n_s >= 2^31, trials > 64).
+ */
+int mmf_kmeans_fit_segmented(const float* X, int64_t n, int64_t d, const int64_t* ptr, int64_t n_seg, int64_t n_clusters,
+                             int64_t n_init, int trials, const int64_t* first_centres, const double* uniforms, int max_iter,
+                             double tol, int64_t* labels, float* centres, int64_t* seeds, double* info, int device_id,
+                             void* hip_stream);
+
 int mmf_segment_sort(const int64_t* labels, int64_t n, int64_t n_segments, int64_t* counts, int64_t* offsets,
                      int64_t* order, int device_id, void* hip_stream);
 int mmf_segment_mean(const float* X, int64_t n, int64_t d, const int64_t* order, const int64_t* offsets,

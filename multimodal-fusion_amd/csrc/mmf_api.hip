@@ -1121,6 +1121,59 @@ int mmf_kmeans_fit(const float* X, int64_t n, int64_t d, int64_t n_clusters, int
                            ws.take<char>(need), s);
 }
 
+int mmf_kmeans_fit_segmented(const float* X, int64_t n, int64_t d, const int64_t* ptr, int64_t n_seg, int64_t n_clusters, int64_t n_init,
+                             int trials, const int64_t* first_centres, const double* uniforms, int max_iter, double tol, int64_t* labels,
+                             float* centres, int64_t* seeds, double* info, int device_id, void* hip_stream) {
+  if (device_id < 0) { set_error("kmeans_fit_segmented: no CPU path"); return MMF_E_UNSUPPORTED; }
+  if (n < 1 || d < 1 || n_seg < 1 || n_clusters < 1 || n_init < 1 || trials < 1 || max_iter < 1 || !(tol >= 0.0)) {
+    set_error("kmeans_fit_segmented: need n >= 1, d >= 1, n_seg >= 1, n_clusters >= 1, n_init >= 1, trials >= 1, max_iter >= 1, tol >= 0 "
+              "(n = %lld, d = %lld, n_seg = %lld, n_clusters = %lld, n_init = %lld, trials = %d, max_iter = %d)", (long long)n, (long long)d,
+              (long long)n_seg, (long long)n_clusters, (long long)n_init, trials, max_iter);
+    return MMF_E_INVALID;
+  }
+  if (!X || !ptr || !first_centres || (n_clusters > 1 && !uniforms) || !labels) { set_error("kmeans_fit_segmented: NULL pointer"); return MMF_E_INVALID; }
+  if (ptr[0] != 0 || ptr[n_seg] != n) {
+    set_error("kmeans_fit_segmented: ptr must start at 0 and end at n = %lld (got %lld, %lld)", (long long)n, (long long)ptr[0], (long long)ptr[n_seg]);
+    return MMF_E_INVALID;
+  }
+  for (int64_t s = 0; s < n_seg; ++s) {
+    const int64_t ns = ptr[s + 1] - ptr[s];
+    if (ns < 0) { set_error("kmeans_fit_segmented: ptr decreases at segment %lld", (long long)s); return MMF_E_INVALID; }
+    if (ns < n_clusters) {
+      set_error("kmeans_fit_segmented: segment %lld: n_samples=%lld should be >= n_clusters=%lld.", (long long)s, (long long)ns, (long long)n_clusters);
+      return MMF_E_INVALID;
+    }
+  }
+  // the plain entry's limits, per segment
+  if (n_init * n_clusters > segment_max_segments()) {
+    set_error("kmeans_fit_segmented: n_init * n_clusters = %lld above the supported %d", (long long)(n_init * n_clusters), segment_max_segments());
+    return MMF_E_UNSUPPORTED;
+  }
+  if (trials > 64) { set_error("kmeans_fit_segmented: trials = %d above the supported 64", trials); return MMF_E_UNSUPPORTED; }
+  for (int64_t s = 0; s < n_seg; ++s)
+    if (n_init * (ptr[s + 1] - ptr[s]) >= ((int64_t)1 << 31)) {
+      set_error("kmeans_fit_segmented: segment %lld: n_init * n_samples must be < 2^31", (long long)s);
+      return MMF_E_UNSUPPORTED;
+    }
+  for (int64_t s = 0; s < n_seg; ++s)
+    for (int64_t i = 0; i < n_init; ++i) {
+      const int64_t f = first_centres[s * n_init + i];
+      if (f < 0 || f >= ptr[s + 1] - ptr[s]) {
+        set_error("kmeans_fit_segmented: segment %lld: first_centres[%lld] outside [0, n_samples)", (long long)s, (long long)i);
+        return MMF_E_INVALID;
+      }
+    }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  size_t need = 0;
+  const std::vector<int64_t> groups = kmeans_segment_groups(ptr, n_seg, d, n_clusters, n_init, trials, &need);
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
+  return launch_kmeans_fit_segmented(X, d, ptr, groups, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds,
+                                     info, ws.take<char>(need), s);
+}
+
 int mmf_lower_median(const float* v, int64_t count, float* out_median, int device_id, void* hip_stream) {
   if (device_id < 0) { set_error("lower_median: no CPU path"); return MMF_E_UNSUPPORTED; }
   if (count < 1) { set_error("lower_median: need count >= 1 (got %lld)", (long long)count); return MMF_E_INVALID; }

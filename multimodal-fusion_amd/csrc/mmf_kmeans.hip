@@ -45,6 +45,38 @@ struct KmState {                // one per restart, device memory
   double inertia;
 };
 
+// ---- segmented fit (mmf_kmeans_fit_segmented) ------------------------------------------------------------------------
+// A group of consecutive segments of a ragged batch runs as one fit of n_seg * n_init restarts: restart g = s n_init + r is
+// restart r of segment s and sees only the segment's rows.  Group-local layouts, for a per-restart row count T (1 or
+// `trials` candidate rows per restart during the seeding): rows of Xc / xx in batch order; segment s's candidate rows and
+// their distance rows at [T n_init row0_s, T n_init (row0_s + n_s)), its tile partials from T n_init stile0_s, its labels at
+// [n_init row0_s, n_init (row0_s + n_s)), restart by restart.  Candidate and seed ids are group-local rows.
+// The kernels below serve both fits: they take one trailing KmSegCtx in the segmented fit and an empty pack in the plain
+// one, so the plain instantiations keep their argument lists and compile to the instructions they had before.  Every
+// reduction of a segment has the structure the plain fit gives it for n = n_s (its 256-row blocks, 64-point tiles, seeding
+// tile width), which is what makes the results equal bit for bit.
+struct KmSeg {
+  int64_t row0;                 // first row, group-local
+  int64_t n;                    // rows
+  int64_t tile0;                // first 64-point tile (E step, inertia)
+  int64_t stile0;               // first seeding tile (tiles of either width, in segment order)
+  int64_t blk0;                 // first 256-row block (column sums)
+  int64_t pt;                   // seeding tile width: 32 or 64, as the plain fit chooses it for n
+};
+struct KmWork {                 // one workgroup's entry of a host-built work table
+  int seg;
+  int tile;                     // block / tile index inside the segment
+};
+struct KmSegCtx {
+  const KmSeg* segs;
+  const KmWork* work;           // the launch's work table (NULL: the segment is blockIdx.y / blockIdx.x, see each kernel)
+  int64_t n_seg;
+  int64_t n_init;
+  int64_t tprev;                // seeding: candidate rows per restart of the PREVIOUS step (layout of `prev`)
+};
+template <class... Seg>
+__device__ __forceinline__ KmSegCtx km_ctx(Seg... sx) { return KmSegCtx{sx...}; }
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -54,12 +86,23 @@ __device__ __forceinline__ double wave_sum(double v) {
 // ---- column means, centring, tolerance, row norms ---------------------------------------------------------------
 // colsum: partial[blk][col] = sum over the block's 256 rows of X[row][col] (pass 0) or of (X[row][col] - mean[col])^2
 // (pass 1), f64, rows in ascending order per thread, four threads per column combined in a fixed order.
+// Segmented: work entry blockIdx.x = block `tile` of its segment (blocks of a segment consecutive: partial row blockIdx.x).
+template <class... Seg>
 __global__ __launch_bounds__(256) void km_colsum_kernel(const float* __restrict__ X, int64_t n, int64_t d, const double* __restrict__ mean,
-                                                        double* __restrict__ partial) {
+                                                        double* __restrict__ partial, Seg... sx) {
   __shared__ double sh[4][64];
   const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
   const int64_t col = (int64_t)blockIdx.y * 64 + c;
-  const int64_t r0 = (int64_t)blockIdx.x * 256;
+  int64_t r0 = (int64_t)blockIdx.x * 256;
+  if constexpr (sizeof...(Seg) > 0) {
+    const KmSegCtx cx = km_ctx(sx...);
+    const KmWork wk = cx.work[blockIdx.x];
+    const KmSeg sg = cx.segs[wk.seg];
+    X += sg.row0 * d;
+    n = sg.n;
+    r0 = (int64_t)wk.tile * 256;
+    if (mean) mean += (int64_t)wk.seg * d;
+  }
   double acc = 0.0;
   if (col < d) {
     const double mu = mean ? mean[col] : 0.0;
@@ -78,9 +121,18 @@ __global__ __launch_bounds__(256) void km_colsum_kernel(const float* __restrict_
 
 // one thread per column: mean (f64 and the float32 scikit-learn subtracts), or the variance; thread 0 of the last launch
 // forms tol_abs = tol * mean(var).
+// Segmented: segment blockIdx.y (out64 [n_seg][d]; out32 unused).
+template <class... Seg>
 __global__ void km_colfin_kernel(const double* __restrict__ partial, int64_t nblk, int64_t n, int64_t d, double* __restrict__ out64,
-                                 float* __restrict__ out32) {
+                                 float* __restrict__ out32, Seg... sx) {
   const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (sizeof...(Seg) > 0) {
+    const KmSeg sg = km_ctx(sx...).segs[blockIdx.y];
+    partial += sg.blk0 * d;
+    nblk = (sg.n + 255) / 256;
+    n = sg.n;
+    out64 += (int64_t)blockIdx.y * d;
+  }
   if (col >= d) return;
   double s = 0.0;
   int64_t b = 0;
@@ -103,8 +155,17 @@ __global__ void km_colfin_kernel(const double* __restrict__ partial, int64_t nbl
 // latency, not bandwidth: a workgroup owns 8 columns (d / 8 workgroups keep enough loads in flight), stages chunks of 512 rows
 // through LDS — all 256 threads load, the next chunk's loads are in flight while the chain runs — and 8 lanes walk the rows.
 constexpr int CM_COLS = 8, CM_ROWS = 512;
-__global__ __launch_bounds__(256) void km_colmean_seq_kernel(const float* __restrict__ X, int64_t n, int64_t d, float* __restrict__ mean32) {
+// Segmented: segment blockIdx.y, the chain restarted at its first row (mean32 [n_seg][d]).
+template <class... Seg>
+__global__ __launch_bounds__(256) void km_colmean_seq_kernel(const float* __restrict__ X, int64_t n, int64_t d, float* __restrict__ mean32,
+                                                             Seg... sx) {
   __shared__ float tile[CM_ROWS][CM_COLS];
+  if constexpr (sizeof...(Seg) > 0) {
+    const KmSeg sg = km_ctx(sx...).segs[blockIdx.y];
+    X += sg.row0 * d;
+    n = sg.n;
+    mean32 += (int64_t)blockIdx.y * d;
+  }
   const int c = threadIdx.x & (CM_COLS - 1), q = threadIdx.x / CM_COLS;      // q in [0, 32)
   const int64_t col = (int64_t)blockIdx.x * CM_COLS + c;
   const bool live = col < d;
@@ -143,8 +204,14 @@ __global__ __launch_bounds__(256) void km_colmean_seq_kernel(const float* __rest
   if (threadIdx.x < CM_COLS && live) mean32[col] = acc / (float)n;
 }
 
-__global__ __launch_bounds__(1024) void km_tol_kernel(const double* __restrict__ var, int64_t d, double tol, double* __restrict__ tol_abs) {
+// Segmented: segment blockIdx.x (var [n_seg][d], tol_abs [n_seg]).
+template <class... Seg>
+__global__ __launch_bounds__(1024) void km_tol_kernel(const double* __restrict__ var, int64_t d, double tol, double* __restrict__ tol_abs, Seg... sx) {
   __shared__ double sh[1024];
+  if constexpr (sizeof...(Seg) > 0) {
+    var += (int64_t)blockIdx.x * d;
+    tol_abs += blockIdx.x;
+  }
   double s = 0.0;
   for (int64_t j = threadIdx.x; j < d; j += 1024) s += var[j];
   sh[threadIdx.x] = s;
@@ -158,11 +225,22 @@ __global__ __launch_bounds__(1024) void km_tol_kernel(const double* __restrict__
 
 // Xc[row][j] = X[row][j] - mean32[j] (float32 subtraction: `X -= X_mean`), zero in the padding columns; one wave per
 // row also leaves xx[row] = sum_j Xc[row][j]^2 in f64.
+// Segmented: rows of the whole group, each centred with its segment's mean (mean32 [n_seg][d]).
+template <class... Seg>
 __global__ __launch_bounds__(256) void km_centre_kernel(const float* __restrict__ X, int64_t n, int64_t d, int64_t ds,
-                                                        const float* __restrict__ mean32, float* __restrict__ Xc, double* __restrict__ xx) {
+                                                        const float* __restrict__ mean32, float* __restrict__ Xc, double* __restrict__ xx, Seg... sx) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n) return;
+  if constexpr (sizeof...(Seg) > 0) {      // the row's segment: the last one that starts at or before it
+    const KmSegCtx cx = km_ctx(sx...);
+    int64_t lo = 0, hi = cx.n_seg - 1;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) >> 1;
+      if (cx.segs[mid].row0 <= row) lo = mid; else hi = mid - 1;
+    }
+    mean32 += lo * d;
+  }
   double acc = 0.0;
   for (int64_t j = lane; j < ds; j += 64) {
     float v = 0.f;
@@ -278,17 +356,38 @@ __device__ __forceinline__ void km_tile_dots(const float* const rowp[2], const f
 // r < R, and partial[r][tile] = sum of out[r][i] over the tile's points (f64).  clamp_r = prev[sel[r / group]]: the running
 // closest-centre distances of r's restart, which are a ROW OF THE PREVIOUS STEP'S OUTPUT (the trial that won): nothing is copied.
 // prev == NULL: no clamp (the first centre).
-template <int MT>
+// Segmented: work entry blockIdx.x = tile `tile` (of this launch's width) of its segment, R = the segment's candidate rows
+// (n_init * group), blockIdx.y their 64-row block; candidates, clamp rows, outputs and partials are the segment's (layouts above).
+template <int MT, class... Seg>
 __global__ __launch_bounds__(256, 2) void km_seed_dots_kernel(const float* __restrict__ Xc, int64_t n, int64_t ds, const double* __restrict__ xx,
                                                               const int64_t* __restrict__ cand, int64_t R, int64_t group,
                                                               const float* __restrict__ prev, const int* __restrict__ sel,
-                                                              float* __restrict__ out, double* __restrict__ partial) {
+                                                              float* __restrict__ out, double* __restrict__ partial, Seg... sx) {
   constexpr int PT = (MT == 4) ? 64 : 32;
+  constexpr bool SEG = sizeof...(Seg) > 0;
   extern __shared__ double km_lds[];
   double* As = km_lds;
   double* Bs = km_lds + 2 * KM_T * KM_LD;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int64_t p0 = (int64_t)blockIdx.x * PT, r0 = (int64_t)blockIdx.y * KM_T;
+  const float* Xp = Xc;                  // the points (the candidates are rows of all of Xc)
+  const double* xxp = xx;
+  int64_t bx = blockIdx.x, ntile = 0;
+  if constexpr (SEG) {
+    const KmSegCtx cx = km_ctx(sx...);
+    const KmWork wk = cx.work[blockIdx.x];
+    const KmSeg sg = cx.segs[wk.seg];
+    bx = wk.tile;
+    n = sg.n;
+    ntile = (sg.n + PT - 1) / PT;
+    Xp = Xc + sg.row0 * ds;
+    xxp = xx + sg.row0;
+    cand += (int64_t)wk.seg * R;
+    if (prev) prev += cx.n_init * cx.tprev * sg.row0;
+    sel += (int64_t)wk.seg * cx.n_init;
+    out += R * sg.row0;
+    partial += R * sg.stile0;
+  }
+  const int64_t p0 = bx * PT, r0 = (int64_t)blockIdx.y * KM_T;
   const float* rowp[2];
   const float* ptp[2];
 #pragma unroll
@@ -298,7 +397,7 @@ __global__ __launch_bounds__(256, 2) void km_seed_dots_kernel(const float* __res
     int64_t p = p0 + (t >> 3) + 32 * u;
     if (p >= n) p = n - 1;
     rowp[u] = Xc + cand[r] * ds + (t & 7) * 4;
-    ptp[u] = Xc + p * ds + (t & 7) * 4;
+    ptp[u] = Xp + p * ds + (t & 7) * 4;
   }
   // what the epilogue needs from memory is requested before the contraction: |c_r|^2 of this lane's rows, |x_p|^2 of its point
   constexpr bool SPLIT = MT == 2;
@@ -314,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void km_seed_dots_kernel(const float* __res
       cr[m][v] = xx[cand[r]];
     }
   const int64_t pq = p0 + bpt + (lane & 15);
-  const double xp = xx[pq < n ? pq : n - 1];
+  const double xp = xxp[pq < n ? pq : n - 1];
   // ... and the clamp values of the 16 rows this wave finishes (wave w: rows 16 w .. 16 w + 15, lane = point)
   const int64_t p = p0 + lane;
   const bool live = lane < PT && p < n;
@@ -357,22 +456,36 @@ __global__ __launch_bounds__(256, 2) void km_seed_dots_kernel(const float* __res
       sm = (double)f;
     }
     sm = wave_sum(sm);
-    if (lane == 0 && r < R) partial[r * gridDim.x + blockIdx.x] = sm;
+    if (lane == 0 && r < R) partial[r * (SEG ? ntile : gridDim.x) + bx] = sm;
   }
 }
 
 // E step: label[g][i] = first arg-min over the k centres of restart g of |c|^2 - 2 x_i.c (f64); `changed[g]` when it
 // differs from the label of the previous iteration.  Labels are stored combined (g k + centre): the segment ids of the M step.
+// Segmented: work entry blockIdx.x = 64-point tile `tile` of its segment, blockIdx.y the restart inside the segment (g0 = 0).
+template <class... Seg>
 __global__ __launch_bounds__(256, 2) void km_assign_kernel(const float* __restrict__ Xc, int64_t n, int64_t ds, const float* __restrict__ C0,
                                                            const float* __restrict__ C1, const double* __restrict__ cc, int64_t k,
-                                                           KmState* __restrict__ st, int g0, int64_t* __restrict__ labels) {
+                                                           KmState* __restrict__ st, int g0, int64_t* __restrict__ labels, Seg... sx) {
   extern __shared__ double km_lds[];
   double* As = km_lds;
   double* Bs = km_lds + 2 * KM_T * KM_LD;
-  const int g = g0 + blockIdx.y;
+  constexpr bool SEG = sizeof...(Seg) > 0;
+  int g = g0 + blockIdx.y;
+  int64_t bx = blockIdx.x, labrow = 0;
+  if constexpr (SEG) {
+    const KmSegCtx cx = km_ctx(sx...);
+    const KmWork wk = cx.work[blockIdx.x];
+    const KmSeg sg = cx.segs[wk.seg];
+    g = (int)(wk.seg * cx.n_init) + (int)blockIdx.y;
+    bx = wk.tile;
+    Xc += sg.row0 * ds;
+    labrow = cx.n_init * sg.row0 + (int64_t)blockIdx.y * sg.n;
+    n = sg.n;
+  }
   if (st[g].state == KM_DONE) return;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int64_t p0 = (int64_t)blockIdx.x * KM_T;
+  const int64_t p0 = bx * KM_T;
   const float* C = (st[g].cur ? C1 : C0) + (int64_t)g * k * ds;
   const double* ccg = cc + (int64_t)g * k;
   const float* ptp[2];
@@ -425,7 +538,7 @@ __global__ __launch_bounds__(256, 2) void km_assign_kernel(const float* __restri
   const int64_t p = p0 + 16 * w + (lane & 15);
   if ((lane >> 4) == 0 && p < n) {
     const int64_t lab = (int64_t)g * k + bi;
-    int64_t* dst = labels + (int64_t)g * n + p;
+    int64_t* dst = SEG ? labels + labrow + p : labels + (int64_t)g * n + p;
     if (*dst != lab) { *dst = lab; st[g].changed = 1; }
   }
 }
@@ -450,11 +563,14 @@ __global__ void km_seed_first_kernel(const int64_t* __restrict__ first, int64_t 
 // amb[0] counts draws that land within 4 float32 ulps of the potential of a boundary of the cumulative sum, amb[1] choices whose
 // runner-up (a different point) is within 4 float32 ulps: decisions scikit-learn's own float32 BLAS sums may take either way.
 constexpr int KM_STEP_CACHE = 6144;      // tile partials (f64) of all trials of a restart kept in LDS when they fit (48 KiB)
+// Segmented: restart g = blockIdx.x is restart gl of segment s; its rows, partials, candidates and counters are the
+// segment's, the uniforms those of restart gl (shared by every segment), and its draws are offset by the segment's first row.
+template <class... Seg>
 __global__ __launch_bounds__(256) void km_seed_step_kernel(const float* __restrict__ rows, const double* __restrict__ partial, int64_t ntile, int pt,
                                                            int64_t n, int tprev, const int64_t* __restrict__ cand_prev, int64_t k, int64_t step_prev,
                                                            const double* __restrict__ U, int64_t u_stride, int trials, float* __restrict__ pot32,
                                                            int64_t* __restrict__ seeds, int* __restrict__ sel, int64_t* __restrict__ cand_next,
-                                                           unsigned int* __restrict__ amb) {
+                                                           unsigned int* __restrict__ amb, Seg... sx) {
   // What this kernel reads was written by the launch before it, mostly on other XCDs: every DEPENDENT global access is a
   // round trip of 1 - 2 us.  So: one round for everything whose address is known at entry (all trials' tile partials into LDS,
   // the uniforms, the candidates), the choice and the search out of LDS, one more round for the chosen tile's values.
@@ -463,16 +579,32 @@ __global__ __launch_bounds__(256) void km_seed_step_kernel(const float* __restri
   __shared__ double tp[KM_STEP_CACHE];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int64_t g = blockIdx.x;
+  int64_t gl = g, row0 = 0;
+  if constexpr (sizeof...(Seg) > 0) {
+    const KmSegCtx cx = km_ctx(sx...);
+    const int64_t sid = g / cx.n_init;
+    const KmSeg sg = cx.segs[sid];
+    gl = g - sid * cx.n_init;
+    row0 = sg.row0;
+    n = sg.n;
+    pt = (int)sg.pt;
+    ntile = (sg.n + sg.pt - 1) / sg.pt;
+    rows += cx.n_init * tprev * sg.row0;
+    partial += cx.n_init * tprev * sg.stile0;
+    cand_prev += sid * cx.n_init * tprev;
+    cand_next += sid * cx.n_init * trials;
+    amb += 2 * sid;
+  }
   const bool cached = (int64_t)tprev * ntile <= KM_STEP_CACHE && tprev <= 16;
   const int64_t per = (ntile + 63) / 64, b = (int64_t)lane * per;
   int64_t e = b + per;
   if (e > ntile) e = ntile;
   double u_mine = 0.0;
   int64_t cand_mine = 0;
-  if (U && w == 0 && lane < trials) u_mine = U[g * u_stride + lane];
-  if (w == 0 && lane < tprev) cand_mine = cand_prev[g * tprev + lane];
+  if (U && w == 0 && lane < trials) u_mine = U[gl * u_stride + lane];
+  if (w == 0 && lane < tprev) cand_mine = cand_prev[gl * tprev + lane];
   for (int tr = w; tr < tprev; tr += 4) {       // wave w: trials w, w + 4, ...: lane l owns the run of tiles [l per, (l + 1) per)
-    const double* p = partial + (g * tprev + tr) * ntile;
+    const double* p = partial + (gl * tprev + tr) * ntile;
     double sum = 0.0;
     for (int64_t j = b; j < e; ++j) {
       const double v = p[j];
@@ -500,12 +632,12 @@ __global__ __launch_bounds__(256) void km_seed_step_kernel(const float* __restri
       if (any) atomicAdd(amb + 1, 1u);
       seeds[g * k + step_prev] = cand_best;
       pot32[g] = pots[bsel];
-      sel[g] = (int)(g * tprev + bsel);
+      sel[g] = (int)(gl * tprev + bsel);
     }
   }
   if (!U) return;
   // the draw: candidate = searchsorted(cumsum(chosen row), u * float64(pot32), 'left') through run totals -> tile partials -> values
-  const int64_t row = g * tprev + bsel;
+  const int64_t row = gl * tprev + bsel;
   const double* bp = partial + row * ntile;
   const float* cl = rows + row * n;
   if (bsel >= 16) {                              // (never with scikit-learn's 2 + log k trials) scan the chosen row again
@@ -568,7 +700,7 @@ __global__ __launch_bounds__(256) void km_seed_step_kernel(const float* __restri
     }
     const double band = 4.0 * 1.1920928955078125e-07 * pot;
     if (target - below <= band || at - target <= band) atomicAdd(amb, 1u);
-    cand_next[g * trials + lane] = pick;
+    cand_next[gl * trials + lane] = pick + row0;
   }
 }
 
@@ -586,10 +718,12 @@ __global__ __launch_bounds__(256) void km_gather_kernel(const float* __restrict_
 // f64, the four partial sums are combined in wave order.  centre = float32(sum) * float32(1 / count) (scikit-learn's
 // _average_centers; an empty cluster keeps its zero sum).  sums32 keeps float32(sum) for the relocation of empty clusters;
 // shift_part[seg][strip] = sum over the strip of (new - old)^2.
+// Segmented: a member at label position q is row q - base of Xc, with the base of its restart's label row (g0 = 0).
+template <class... Seg>
 __global__ __launch_bounds__(256) void km_update_kernel(const float* __restrict__ Xc, int64_t n, int64_t ds, const int64_t* __restrict__ order,
                                                         const int64_t* __restrict__ offsets, int64_t k, float* __restrict__ C0,
                                                         float* __restrict__ C1, float* __restrict__ sums32, KmState* __restrict__ st, int g0,
-                                                        double* __restrict__ shift_part) {
+                                                        double* __restrict__ shift_part, Seg... sx) {
   __shared__ double part[4][64];
   const int64_t seg = (int64_t)g0 * k + blockIdx.x;
   const int g = (int)(seg / k);
@@ -598,7 +732,13 @@ __global__ __launch_bounds__(256) void km_update_kernel(const float* __restrict_
   const int64_t col = (int64_t)blockIdx.y * 64 + lane;
   const bool live = col < ds;
   const int64_t b = offsets[seg], e = offsets[seg + 1];
-  const int64_t base = (int64_t)g * n;
+  int64_t base = (int64_t)g * n;
+  if constexpr (sizeof...(Seg) > 0) {
+    const KmSegCtx cx = km_ctx(sx...);
+    const int64_t sid = g / cx.n_init;
+    const KmSeg sg = cx.segs[sid];
+    base = cx.n_init * sg.row0 + (g - sid * cx.n_init) * sg.n - sg.row0;
+  }
   double acc = 0.0;
   if (live) {
     // eight row loads in flight per wave; the member indices of the NEXT trip are read while this trip's rows arrive (index -> row
@@ -653,9 +793,13 @@ __global__ __launch_bounds__(256) void km_update_kernel(const float* __restrict_
 // One wave per restart, after the E (+ M) step of Lloyd iteration `it`: scikit-learn's convergence logic
 // (_kmeans_single_lloyd): swap the centre buffers; unchanged labels -> done, no further E step; shift <= tol or the last
 // iteration -> one more E step with the new centres.  A restart with empty clusters waits for the host (KM_RELOC).
+// Segmented: tol_abs [n_seg], restart g compares against its segment's.
+template <class... Seg>
 __global__ __launch_bounds__(64) void km_state_kernel(KmState* __restrict__ st, int n_init, int64_t k, int64_t strips, const double* __restrict__ shift_part,
-                                                      const double* __restrict__ tol_abs, int it, int max_iter, int only, int* __restrict__ status) {
+                                                      const double* __restrict__ tol_abs, int it, int max_iter, int only, int* __restrict__ status,
+                                                      Seg... sx) {
   const int g = blockIdx.x, lane = threadIdx.x;
+  if constexpr (sizeof...(Seg) > 0) tol_abs += g / n_init;
   if (only < 0 || only == g) {
     KmState s = st[g];
     if (s.state == KM_FINAL) {
@@ -688,11 +832,23 @@ __global__ __launch_bounds__(64) void km_state_kernel(KmState* __restrict__ st, 
 // the points farthest from their (old) centre, in descending order (ties: lowest index), become the centres of the empty
 // clusters in ascending cluster order; each is removed from its donor's float32 sum.  Then all k centres of the restart are
 // re-averaged and the shift recomputed.  dist: [n] f64 scratch.
+// Segmented: restart g sees its segment's rows and label row.
+template <class... Seg>
 __global__ __launch_bounds__(1024) void km_relocate_kernel(const float* __restrict__ Xc, int64_t n, int64_t ds, int64_t k, int g,
                                                            const int64_t* __restrict__ labels, const int64_t* __restrict__ offsets,
                                                            float* __restrict__ C0, float* __restrict__ C1, float* __restrict__ sums32,
                                                            const KmState* __restrict__ st, double* __restrict__ dist, float* __restrict__ cnt,
-                                                           double* __restrict__ shift_part, int64_t strips) {
+                                                           double* __restrict__ shift_part, int64_t strips, Seg... sx) {
+  constexpr bool SEG = sizeof...(Seg) > 0;
+  int64_t labrow = 0;
+  if constexpr (SEG) {
+    const KmSegCtx cx = km_ctx(sx...);
+    const int64_t sid = g / cx.n_init;
+    const KmSeg sg = cx.segs[sid];
+    Xc += sg.row0 * ds;
+    labrow = cx.n_init * sg.row0 + (g - sid * cx.n_init) * sg.n;
+    n = sg.n;
+  }
   __shared__ double rv[1024];
   __shared__ int64_t ri[1024];
   __shared__ int64_t far_s;
@@ -701,7 +857,7 @@ __global__ __launch_bounds__(1024) void km_relocate_kernel(const float* __restri
   const float* Co = (cur ? C1 : C0) + (int64_t)g * k * ds;
   float* Cn = (cur ? C0 : C1) + (int64_t)g * k * ds;
   float* S = sums32 + (int64_t)g * k * ds;
-  const int64_t* lab = labels + (int64_t)g * n;
+  const int64_t* lab = SEG ? labels + labrow : labels + (int64_t)g * n;
   for (int64_t c = t; c < k; c += 1024) cnt[c] = (float)(offsets[(int64_t)g * k + c + 1] - offsets[(int64_t)g * k + c]);
   double mx = 0.0;
   for (int64_t i = t; i < n; i += 1024) {
@@ -776,17 +932,35 @@ __global__ __launch_bounds__(1024) void km_relocate_kernel(const float* __restri
 
 // ---- inertia, best restart, outputs -------------------------------------------------------------------------------------
 // partial[g][blk] = sum over the block's points of |x_i - c_label|^2 (f64), one wave per point.
+// Segmented: work entry blockIdx.x = 64-point tile `tile` of its segment, blockIdx.y the restart inside the segment; the
+// partials of segment s start at n_init tile0_s, ntile_s per restart.
+template <class... Seg>
 __global__ __launch_bounds__(256) void km_inertia_kernel(const float* __restrict__ Xc, int64_t n, int64_t ds, const float* __restrict__ C0,
                                                          const float* __restrict__ C1, const KmState* __restrict__ st,
-                                                         const int64_t* __restrict__ labels, double* __restrict__ partial) {
+                                                         const int64_t* __restrict__ labels, double* __restrict__ partial, Seg... sx) {
   __shared__ double sh[4];
-  const int g = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  constexpr bool SEG = sizeof...(Seg) > 0;
+  int g = blockIdx.y;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int64_t bx = 0, pidx = 0;
+  if constexpr (SEG) {
+    const KmSegCtx cx = km_ctx(sx...);
+    const KmWork wk = cx.work[blockIdx.x];
+    const KmSeg sg = cx.segs[wk.seg];
+    g = (int)(wk.seg * cx.n_init) + (int)blockIdx.y;
+    bx = wk.tile;
+    Xc += sg.row0 * ds;
+    labels += cx.n_init * sg.row0 + (int64_t)blockIdx.y * sg.n;      // the restart's label row
+    n = sg.n;
+    const int64_t ntile = (sg.n + KM_T - 1) / KM_T;
+    pidx = cx.n_init * sg.tile0 + (int64_t)blockIdx.y * ntile + wk.tile;
+  }
   const float* C = st[g].cur ? C1 : C0;
   double acc = 0.0;
   for (int u = 0; u < 16; ++u) {
-    const int64_t i = (int64_t)blockIdx.x * 64 + u * 4 + w;
+    const int64_t i = (SEG ? bx : (int64_t)blockIdx.x) * 64 + u * 4 + w;
     if (i >= n) break;
-    const float* c = C + labels[(int64_t)g * n + i] * ds;
+    const float* c = C + labels[SEG ? i : (int64_t)g * n + i] * ds;
     const float* x = Xc + i * ds;
     double a = 0.0;
     for (int64_t j = lane; j < ds; j += 64) { const double v = (double)x[j] - (double)c[j]; a += v * v; }
@@ -794,17 +968,33 @@ __global__ __launch_bounds__(256) void km_inertia_kernel(const float* __restrict
   }
   if (lane == 0) sh[w] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) partial[(int64_t)g * gridDim.x + blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  if (threadIdx.x == 0) partial[SEG ? pidx : (int64_t)g * gridDim.x + blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
 // Single workgroup: inertia of every restart, then scikit-learn's choice (KMeans.fit :1525-1532): a later restart replaces the
 // best one when its inertia is strictly smaller AND its labels are not a function of the best's (_is_same_clustering).
 // map: [k] int scratch.
+// Segmented: one workgroup per segment (blockIdx.x), over its n_init restarts; map [n_seg][k], best_out [n_seg].
+template <class... Seg>
 __global__ __launch_bounds__(1024) void km_pick_kernel(KmState* __restrict__ st, int n_init, int64_t n, int64_t k, const double* __restrict__ partial,
-                                                       int64_t nblk, const int64_t* __restrict__ labels, int* __restrict__ map, int* __restrict__ best_out) {
+                                                       int64_t nblk, const int64_t* __restrict__ labels, int* __restrict__ map, int* __restrict__ best_out,
+                                                       Seg... sx) {
   __shared__ double red[1024];
   __shared__ int differs;
   const int t = threadIdx.x;
+  int64_t koff = 0;                  // the label of centre c of restart g is (g0 + g) k + c: g0 k for a segment's restarts
+  if constexpr (sizeof...(Seg) > 0) {
+    const int64_t sid = blockIdx.x;
+    const KmSeg sg = km_ctx(sx...).segs[sid];
+    st += sid * n_init;
+    n = sg.n;
+    nblk = (sg.n + KM_T - 1) / KM_T;
+    partial += n_init * sg.tile0;
+    labels += n_init * sg.row0;
+    map += sid * k;
+    best_out += sid;
+    koff = sid * n_init * k;
+  }
   for (int g = 0; g < n_init; ++g) {
     double s = 0.0;
     for (int64_t q = t; q < nblk; q += 1024) s += partial[(int64_t)g * nblk + q];
@@ -825,7 +1015,7 @@ __global__ __launch_bounds__(1024) void km_pick_kernel(KmState* __restrict__ st,
     if (t == 0) differs = 0;
     __syncthreads();
     for (int64_t i = t; i < n; i += 1024) {
-      const int a = (int)(labels[(int64_t)g * n + i] - (int64_t)g * k), b = (int)(labels[(int64_t)best * n + i] - (int64_t)best * k);
+      const int a = (int)(labels[(int64_t)g * n + i] - koff - (int64_t)g * k), b = (int)(labels[(int64_t)best * n + i] - koff - (int64_t)best * k);
       const int prev = atomicCAS(&map[a], -1, b);
       if (prev != -1 && prev != b) differs = 1;
     }
@@ -836,13 +1026,31 @@ __global__ __launch_bounds__(1024) void km_pick_kernel(KmState* __restrict__ st,
   if (t == 0) *best_out = best;
 }
 
+// Segmented: segment blockIdx.y (best_p, mean32, out_centres per segment; out_labels at its rows).
+template <class... Seg>
 __global__ __launch_bounds__(256) void km_finish_kernel(const KmState* __restrict__ st, const int* __restrict__ best_p, int64_t n, int64_t k, int64_t d,
                                                         int64_t ds, const int64_t* __restrict__ labels, const float* __restrict__ C0,
                                                         const float* __restrict__ C1, const float* __restrict__ mean32,
-                                                        int64_t* __restrict__ out_labels, float* __restrict__ out_centres) {
+                                                        int64_t* __restrict__ out_labels, float* __restrict__ out_centres, Seg... sx) {
+  int64_t koff = 0;
+  if constexpr (sizeof...(Seg) > 0) {
+    const KmSegCtx cx = km_ctx(sx...);
+    const int64_t sid = blockIdx.y;
+    const KmSeg sg = cx.segs[sid];
+    st += sid * cx.n_init;
+    best_p += sid;
+    n = sg.n;
+    labels += cx.n_init * sg.row0;
+    C0 += sid * cx.n_init * k * ds;
+    C1 += sid * cx.n_init * k * ds;
+    mean32 += sid * d;
+    out_labels += sg.row0;
+    if (out_centres) out_centres += sid * k * d;
+    koff = sid * cx.n_init * k;
+  }
   const int best = *best_p;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out_labels[i] = labels[(int64_t)best * n + i] - (int64_t)best * k;
+  if (i < n) out_labels[i] = labels[(int64_t)best * n + i] - koff - (int64_t)best * k;
   if (out_centres && i < k * d) {
     const int64_t r = i / d, j = i % d;
     const float* C = (st[best].cur ? C1 : C0) + ((int64_t)best * k + r) * ds;
@@ -941,7 +1149,7 @@ int launch_kmeans_fit(const float* X, int64_t n, int64_t d, int64_t k, int64_t n
   const size_t lds = (size_t)4 * KM_T * KM_LD * 8;
   MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(km_seed_dots_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(km_seed_dots_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 
   // the caller's stream of random numbers
   MMF_HIP(hipMemcpyAsync(first, first_h, (size_t)n_init * 8, hipMemcpyHostToDevice, s));
@@ -1057,6 +1265,293 @@ int launch_kmeans_fit(const float* X, int64_t n, int64_t d, int64_t k, int64_t n
     info_h[0] = (double)h_best; info_h[1] = hs[h_best].inertia; info_h[2] = (double)hs[h_best].n_iter; info_h[3] = h_tol;
     info_h[4] = (double)h_amb[0]; info_h[5] = (double)h_amb[1]; info_h[6] = (double)it;
     for (int64_t g = 0; g < n_init; ++g) { info_h[7 + 2 * g] = hs[g].inertia; info_h[8 + 2 * g] = (double)hs[g].n_iter; }
+  }
+  return MMF_OK;
+}
+
+// ---- segmented fit ----------------------------------------------------------------------------------------------------
+// out[i] = seeds[i] + base: group-local seed rows -> row ids of the whole batch
+__global__ void km_seeds_out_kernel(const int64_t* __restrict__ seeds, int64_t count, int64_t base, int64_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) out[i] = seeds[i] + base;
+}
+
+namespace {
+int64_t km_seed_pt(int64_t n) { return (n + KM_T - 1) / KM_T < 512 ? 32 : 64; }     // the plain fit's seeding tile width (small_tiles)
+
+struct KmCounts {                // sizes of a group of consecutive segments
+  int64_t nseg = 0, nrows = 0, max_n = 0, nblk = 0, ntile = 0, nst32 = 0, nst64 = 0;
+  void add(int64_t n) {
+    ++nseg; nrows += n; max_n = n > max_n ? n : max_n;
+    nblk += (n + 255) / 256; ntile += (n + KM_T - 1) / KM_T;
+    const int64_t pt = km_seed_pt(n);
+    (pt == 32 ? nst32 : nst64) += (n + pt - 1) / pt;
+  }
+  int64_t nstile() const { return nst32 + nst64; }
+  int64_t nwork() const { return nblk + ntile + nst32 + nst64; }
+};
+
+struct KmGroup : KmCounts {      // host plan of one group
+  int64_t s0 = 0, row0 = 0;
+  std::vector<KmSeg> segs;
+  std::vector<KmWork> work;      // column-sum blocks, then 64-point tiles, then 32- and 64-point seeding tiles
+};
+
+KmGroup km_plan(const int64_t* ptr, int64_t s0, int64_t s1) {
+  KmGroup g;
+  g.s0 = s0; g.row0 = ptr[s0];
+  std::vector<KmWork> blk, tile, st32, st64;
+  for (int64_t s = s0; s < s1; ++s) {
+    const int64_t n = ptr[s + 1] - ptr[s], pt = km_seed_pt(n);
+    const int sl = (int)(s - s0);
+    g.segs.push_back(KmSeg{ptr[s] - ptr[s0], n, g.ntile, g.nst32 + g.nst64, g.nblk, pt});
+    for (int64_t b = 0; b < (n + 255) / 256; ++b) blk.push_back(KmWork{sl, (int)b});
+    for (int64_t t = 0; t < (n + KM_T - 1) / KM_T; ++t) tile.push_back(KmWork{sl, (int)t});
+    for (int64_t t = 0; t < (n + pt - 1) / pt; ++t) (pt == 32 ? st32 : st64).push_back(KmWork{sl, (int)t});
+    g.add(n);
+  }
+  for (auto* v : {&blk, &tile, &st32, &st64}) g.work.insert(g.work.end(), v->begin(), v->end());
+  return g;
+}
+
+struct KmSegBufs {
+  float* Xc; double* xx; double* colpart; double* mean64; double* var64; float* mean32; double* tol_abs; int* best; unsigned int* amb;
+  float* rows[2]; double* rpart[2]; int64_t* cand[2]; int64_t* first; float* pot32; int* sel; double* U; int64_t* seeds;
+  float* C0; float* C1; float* sums32; double* cc; int64_t* labels; int64_t* order; int64_t* counts; int64_t* offsets; void* sort_scratch;
+  uint32_t* bad; double* shift_part; KmState* st; int* status; double* dist; float* cntf; double* ipart; int* map; KmSeg* segs; KmWork* work;
+  size_t bytes;
+};
+
+// The group's scratch, carved from `base` (NULL: only the size).
+KmSegBufs km_seg_carve(char* base, const KmCounts& g, int64_t d, int64_t k, int64_t n_init, int trials) {
+  const int64_t ds = km_ds(d), Rs = n_init * trials, G = g.nseg * n_init, S = G * k, nr = g.nrows, strips = (ds + 63) / 64;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off += al(bytes); return q; };
+  KmSegBufs b;
+  b.Xc = (float*)take((size_t)nr * ds * 4);
+  b.xx = (double*)take((size_t)nr * 8);
+  b.colpart = (double*)take((size_t)g.nblk * d * 8);
+  b.mean64 = (double*)take((size_t)g.nseg * d * 8);
+  b.var64 = (double*)take((size_t)g.nseg * d * 8);
+  b.mean32 = (float*)take((size_t)g.nseg * d * 4);
+  b.tol_abs = (double*)take((size_t)g.nseg * 8);
+  b.best = (int*)take((size_t)g.nseg * 4);
+  b.amb = (unsigned int*)take((size_t)g.nseg * 8);
+  for (int u = 0; u < 2; ++u) b.rows[u] = (float*)take((size_t)Rs * nr * 4);
+  for (int u = 0; u < 2; ++u) b.rpart[u] = (double*)take((size_t)Rs * g.nstile() * 8);
+  for (int u = 0; u < 2; ++u) b.cand[u] = (int64_t*)take((size_t)G * trials * 8);
+  b.first = (int64_t*)take((size_t)G * 8);
+  b.pot32 = (float*)take((size_t)G * 4);
+  b.sel = (int*)take((size_t)G * 4);
+  b.U = (double*)take((size_t)n_init * (k > 1 ? k - 1 : 1) * trials * 8);
+  b.seeds = (int64_t*)take((size_t)S * 8);
+  b.C0 = (float*)take((size_t)S * ds * 4);
+  b.C1 = (float*)take((size_t)S * ds * 4);
+  b.sums32 = (float*)take((size_t)S * ds * 4);
+  b.cc = (double*)take((size_t)S * 8);
+  b.labels = (int64_t*)take((size_t)n_init * nr * 8);
+  b.order = (int64_t*)take((size_t)n_init * nr * 8);
+  b.counts = (int64_t*)take((size_t)S * 8);
+  b.offsets = (int64_t*)take((size_t)(S + 1) * 8);
+  b.sort_scratch = take(segment_sort_scratch_bytes(n_init * nr, S));
+  b.bad = (uint32_t*)take(4);
+  b.shift_part = (double*)take((size_t)S * strips * 8);
+  b.st = (KmState*)take((size_t)G * sizeof(KmState));
+  b.status = (int*)take((size_t)G * 4);
+  b.dist = (double*)take((size_t)g.max_n * 8);
+  b.cntf = (float*)take((size_t)k * 4);
+  b.ipart = (double*)take((size_t)n_init * g.ntile * 8);
+  b.map = (int*)take((size_t)g.nseg * k * 4);
+  b.segs = (KmSeg*)take((size_t)g.nseg * sizeof(KmSeg));
+  b.work = (KmWork*)take((size_t)g.nwork() * sizeof(KmWork));
+  b.bytes = off + 4096;
+  return b;
+}
+
+constexpr size_t KM_GROUP_BYTES = (size_t)2 << 30;      // a group grows while its scratch stays under this (or holds one segment)
+}  // namespace
+
+std::vector<int64_t> kmeans_segment_groups(const int64_t* ptr, int64_t n_seg, int64_t d, int64_t k, int64_t n_init, int trials, size_t* max_bytes) {
+  std::vector<int64_t> bounds{0};
+  size_t mx = 0;
+  int64_t s0 = 0;
+  while (s0 < n_seg) {
+    KmCounts c;
+    c.add(ptr[s0 + 1] - ptr[s0]);
+    int64_t s1 = s0 + 1;
+    size_t bytes = km_seg_carve(nullptr, c, d, k, n_init, trials).bytes;
+    while (s1 < n_seg) {
+      KmCounts c2 = c;
+      c2.add(ptr[s1 + 1] - ptr[s1]);
+      if (c2.nseg * n_init * k > segment_max_segments() || c2.nrows * n_init >= ((int64_t)1 << 31)) break;
+      const size_t b2 = km_seg_carve(nullptr, c2, d, k, n_init, trials).bytes;
+      if (b2 > KM_GROUP_BYTES) break;
+      c = c2; bytes = b2; ++s1;
+    }
+    mx = bytes > mx ? bytes : mx;
+    bounds.push_back(s1);
+    s0 = s1;
+  }
+  if (max_bytes) *max_bytes = mx;
+  return bounds;
+}
+
+int launch_kmeans_fit_segmented(const float* X, int64_t d, const int64_t* ptr, const std::vector<int64_t>& groups, int64_t k, int64_t n_init,
+                                int trials, const int64_t* first_h, const double* u_h, int max_iter, double tol, int64_t* out_labels,
+                                float* out_centres, int64_t* out_seeds, double* info_h, void* scratch, hipStream_t s) {
+  const int64_t ds = km_ds(d), strips = (ds + 63) / 64;
+  const size_t lds = (size_t)4 * KM_T * KM_LD * 8;
+  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((km_seed_dots_kernel<2, KmSegCtx>)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((km_seed_dots_kernel<4, KmSegCtx>)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_kernel<KmSegCtx>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const size_t u_count = (size_t)n_init * (k > 1 ? k - 1 : 1) * trials;
+  for (size_t gi = 0; gi + 1 < groups.size(); ++gi) {
+    const KmGroup gp = km_plan(ptr, groups[gi], groups[gi + 1]);
+    const KmSegBufs b = km_seg_carve(static_cast<char*>(scratch), gp, d, k, n_init, trials);
+    const int64_t nseg = gp.nseg, nr = gp.nrows, G = nseg * n_init, S = G * k, R = n_init * trials;
+    KmWork* w_blk = b.work;
+    KmWork* w_tile = w_blk + gp.nblk;
+    KmWork* w_st32 = w_tile + gp.ntile;
+    KmWork* w_st64 = w_st32 + gp.nst32;
+    // (the host vectors copied below live until the first status read of the Lloyd loop has synchronised the stream)
+    const float* Xg = X + gp.row0 * d;
+    // the caller's random stream: first centres as group-local rows, the shared uniforms; the group's tables
+    std::vector<int64_t> first((size_t)G);
+    for (int64_t q = 0; q < nseg; ++q)
+      for (int64_t r = 0; r < n_init; ++r) first[q * n_init + r] = gp.segs[q].row0 + first_h[(gp.s0 + q) * n_init + r];
+    MMF_HIP(hipMemcpyAsync(b.first, first.data(), (size_t)G * 8, hipMemcpyHostToDevice, s));
+    if (k > 1) MMF_HIP(hipMemcpyAsync(b.U, u_h, u_count * 8, hipMemcpyHostToDevice, s));
+    MMF_HIP(hipMemcpyAsync(b.segs, gp.segs.data(), (size_t)nseg * sizeof(KmSeg), hipMemcpyHostToDevice, s));
+    MMF_HIP(hipMemcpyAsync(b.work, gp.work.data(), gp.work.size() * sizeof(KmWork), hipMemcpyHostToDevice, s));
+    MMF_HIP(hipMemsetAsync(b.amb, 0, (size_t)nseg * 8, s));
+    auto ctx = [&](const KmWork* w, int64_t tprev) { return KmSegCtx{b.segs, w, nseg, n_init, tprev}; };
+
+    // centring, tolerance, norms: per segment
+    const dim3 cgrid((unsigned)gp.nblk, (unsigned)((d + 63) / 64)), fgrid((unsigned)((d + 255) / 256), (unsigned)nseg);
+    hipLaunchKernelGGL(km_colsum_kernel<KmSegCtx>, cgrid, dim3(256), 0, s, Xg, nr, d, (const double*)nullptr, b.colpart, ctx(w_blk, 0));
+    MMF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_colfin_kernel<KmSegCtx>, fgrid, dim3(256), 0, s, b.colpart, gp.nblk, nr, d, b.mean64, (float*)nullptr, ctx(nullptr, 0));
+    MMF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_colmean_seq_kernel<KmSegCtx>, dim3((unsigned)((d + CM_COLS - 1) / CM_COLS), (unsigned)nseg), dim3(256), 0, s, Xg, nr, d,
+                       b.mean32, ctx(nullptr, 0));
+    MMF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_colsum_kernel<KmSegCtx>, cgrid, dim3(256), 0, s, Xg, nr, d, (const double*)b.mean64, b.colpart, ctx(w_blk, 0));
+    MMF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_colfin_kernel<KmSegCtx>, fgrid, dim3(256), 0, s, b.colpart, gp.nblk, nr, d, b.var64, (float*)nullptr, ctx(nullptr, 0));
+    MMF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_tol_kernel<KmSegCtx>, dim3((unsigned)nseg), dim3(1024), 0, s, b.var64, d, tol, b.tol_abs, ctx(nullptr, 0));
+    MMF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_centre_kernel<KmSegCtx>, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, s, Xg, nr, d, ds, b.mean32, b.Xc, b.xx,
+                       ctx(nullptr, 0));
+    MMF_LAUNCH_CHECK();
+
+    // k-means++: every restart of every segment in lockstep; per step one choice/draw launch and one distance launch per tile width
+    hipLaunchKernelGGL(km_seed_first_kernel, dim3((unsigned)((G + 63) / 64)), dim3(64), 0, s, b.first, G, k, b.seeds, b.cand[0]);
+    MMF_LAUNCH_CHECK();
+    auto dots = [&](const int64_t* cd, int64_t Rn, int64_t group, const float* prev, int64_t tprev, float* out, double* part) -> int {
+      const unsigned ry = (unsigned)((Rn + KM_T - 1) / KM_T);
+      if (gp.nst32) {
+        hipLaunchKernelGGL((km_seed_dots_kernel<2, KmSegCtx>), dim3((unsigned)gp.nst32, ry), dim3(256), lds, s, b.Xc, nr, ds, b.xx, cd, Rn, group, prev,
+                           b.sel, out, part, ctx(w_st32, tprev));
+        MMF_LAUNCH_CHECK();
+      }
+      if (gp.nst64) {
+        hipLaunchKernelGGL((km_seed_dots_kernel<4, KmSegCtx>), dim3((unsigned)gp.nst64, ry), dim3(256), lds, s, b.Xc, nr, ds, b.xx, cd, Rn, group, prev,
+                           b.sel, out, part, ctx(w_st64, tprev));
+        MMF_LAUNCH_CHECK();
+      }
+      return MMF_OK;
+    };
+    MMF_TRY(dots(b.cand[0], n_init, 1, nullptr, 1, b.rows[0], b.rpart[0]));
+    int cur = 0, tprev = 1;
+    for (int64_t step = 1; step <= k; ++step) {
+      const bool last = step == k;
+      hipLaunchKernelGGL(km_seed_step_kernel<KmSegCtx>, dim3((unsigned)G), dim3(256), 0, s, b.rows[cur], b.rpart[cur], (int64_t)0, 0, nr, tprev,
+                         b.cand[cur], k, step - 1, last ? (const double*)nullptr : b.U + (step - 1) * trials, (k - 1) * trials, trials, b.pot32,
+                         b.seeds, b.sel, b.cand[cur ^ 1], b.amb, ctx(nullptr, tprev));
+      MMF_LAUNCH_CHECK();
+      if (last) break;
+      MMF_TRY(dots(b.cand[cur ^ 1], R, trials, b.rows[cur], tprev, b.rows[cur ^ 1], b.rpart[cur ^ 1]));
+      cur ^= 1;
+      tprev = trials;
+    }
+    if (out_seeds) {
+      hipLaunchKernelGGL(km_seeds_out_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, b.seeds, S, gp.row0, out_seeds + gp.s0 * n_init * k);
+      MMF_LAUNCH_CHECK();
+    }
+
+    // Lloyd iterations: every restart of the group in lockstep, one status read per iteration
+    hipLaunchKernelGGL(km_gather_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, b.Xc, ds, b.seeds, S, b.C0);
+    MMF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_init_state_kernel, dim3((unsigned)((G + 63) / 64)), dim3(64), 0, s, b.st, (int)G);
+    MMF_LAUNCH_CHECK();
+    MMF_HIP(hipMemsetAsync(b.labels, 0xff, (size_t)n_init * nr * 8, s));
+    std::vector<int> h_status((size_t)G, KM_RUN);
+    int it = 0;
+    for (;; ++it) {
+      bool any_run = false, any_live = false;
+      for (int64_t g = 0; g < G; ++g) { any_run |= h_status[g] == KM_RUN; any_live |= h_status[g] != KM_DONE; }
+      if (!any_live) break;
+      hipLaunchKernelGGL(km_rownorm_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, b.C0, b.C1, b.st, k, S, ds, b.cc);
+      MMF_LAUNCH_CHECK();
+      hipLaunchKernelGGL(km_assign_kernel<KmSegCtx>, dim3((unsigned)gp.ntile, (unsigned)n_init), dim3(256), lds, s, b.Xc, nr, ds, b.C0, b.C1, b.cc, k,
+                         b.st, 0, b.labels, ctx(w_tile, 0));
+      MMF_LAUNCH_CHECK();
+      if (any_run) {
+        MMF_TRY(launch_segment_sort(b.labels, n_init * nr, S, b.counts, b.offsets, b.order, b.sort_scratch, b.bad, s));
+        hipLaunchKernelGGL(km_update_kernel<KmSegCtx>, dim3((unsigned)S, (unsigned)strips), dim3(256), 0, s, b.Xc, nr, ds, b.order, b.offsets, k, b.C0,
+                           b.C1, b.sums32, b.st, 0, b.shift_part, ctx(nullptr, 0));
+        MMF_LAUNCH_CHECK();
+      }
+      hipLaunchKernelGGL(km_state_kernel<KmSegCtx>, dim3((unsigned)G), dim3(64), 0, s, b.st, (int)n_init, k, strips, b.shift_part, b.tol_abs, it,
+                         max_iter, -1, b.status, ctx(nullptr, 0));
+      MMF_LAUNCH_CHECK();
+      MMF_HIP(hipMemcpyAsync(h_status.data(), b.status, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipStreamSynchronize(s));
+      for (int64_t g = 0; g < G; ++g) {
+        if (h_status[g] != KM_RELOC) continue;
+        hipLaunchKernelGGL(km_relocate_kernel<KmSegCtx>, dim3(1), dim3(1024), 0, s, b.Xc, nr, ds, k, (int)g, b.labels, b.offsets, b.C0, b.C1, b.sums32,
+                           b.st, b.dist, b.cntf, b.shift_part, strips, ctx(nullptr, 0));
+        MMF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(km_state_kernel<KmSegCtx>, dim3((unsigned)G), dim3(64), 0, s, b.st, (int)n_init, k, strips, b.shift_part, b.tol_abs, it,
+                           max_iter, (int)g, b.status, ctx(nullptr, 0));
+        MMF_LAUNCH_CHECK();
+        MMF_HIP(hipMemcpyAsync(h_status.data(), b.status, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+        MMF_HIP(hipStreamSynchronize(s));
+      }
+      if (it > max_iter + 2) { set_error("kmeans_fit_segmented: the convergence state machine did not terminate (internal invariant)"); return MMF_E_INTERNAL; }
+    }
+
+    hipLaunchKernelGGL(km_inertia_kernel<KmSegCtx>, dim3((unsigned)gp.ntile, (unsigned)n_init), dim3(256), 0, s, b.Xc, nr, ds, b.C0, b.C1, b.st,
+                       b.labels, b.ipart, ctx(w_tile, 0));
+    MMF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_pick_kernel<KmSegCtx>, dim3((unsigned)nseg), dim3(1024), 0, s, b.st, (int)n_init, nr, k, b.ipart, gp.ntile, b.labels, b.map,
+                       b.best, ctx(nullptr, 0));
+    MMF_LAUNCH_CHECK();
+    const int64_t fin = gp.max_n > k * d ? gp.max_n : k * d;
+    hipLaunchKernelGGL(km_finish_kernel<KmSegCtx>, dim3((unsigned)((fin + 255) / 256), (unsigned)nseg), dim3(256), 0, s, b.st, b.best, nr, k, d, ds,
+                       b.labels, b.C0, b.C1, b.mean32, out_labels + gp.row0, out_centres ? out_centres + gp.s0 * k * d : nullptr, ctx(nullptr, 0));
+    MMF_LAUNCH_CHECK();
+    if (info_h) {
+      // per segment as the plain fit's info; [6] is the group's lockstep iteration count
+      std::vector<KmState> hs((size_t)G);
+      std::vector<int> h_best((size_t)nseg);
+      std::vector<unsigned int> h_amb((size_t)nseg * 2);
+      std::vector<double> h_tol((size_t)nseg);
+      MMF_HIP(hipMemcpyAsync(hs.data(), b.st, (size_t)G * sizeof(KmState), hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipMemcpyAsync(h_best.data(), b.best, (size_t)nseg * 4, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipMemcpyAsync(h_amb.data(), b.amb, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipMemcpyAsync(h_tol.data(), b.tol_abs, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipStreamSynchronize(s));
+      for (int64_t q = 0; q < nseg; ++q) {
+        double* o = info_h + (gp.s0 + q) * (7 + 2 * n_init);
+        const KmState* sq = hs.data() + q * n_init;
+        const int bq = h_best[q];
+        o[0] = (double)bq; o[1] = sq[bq].inertia; o[2] = (double)sq[bq].n_iter; o[3] = h_tol[q];
+        o[4] = (double)h_amb[2 * q]; o[5] = (double)h_amb[2 * q + 1]; o[6] = (double)it;
+        for (int64_t r = 0; r < n_init; ++r) { o[7 + 2 * r] = sq[r].inertia; o[8 + 2 * r] = (double)sq[r].n_iter; }
+      }
+    }
   }
   return MMF_OK;
 }

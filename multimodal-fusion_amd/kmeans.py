@@ -73,3 +73,43 @@ def kmeans_fit_predict(X: torch.Tensor, n_clusters: int, *, n_init: int = 10, ma
     if return_info:
         return labels, centres, info["inertia"], info
     return labels, centres, info["inertia"]
+
+
+def kmeans_fit_predict_segmented(X: torch.Tensor, n_clusters: int, *, ptr=None, batch=None, n_init: int = 10, max_iter: int = 300,
+                                 tol: float = 1e-4, seed: int = 42, return_info: bool = False):
+    """kmeans_fit_predict for every segment of a ragged batch in one call: segment s is X[ptr[s]:ptr[s+1]], given by exactly
+    one of ptr ([n_seg + 1] offsets) / batch ([N] sorted segment id per row, PyG's convention).  Returns (labels int64 [N],
+    0 .. k-1 within each segment, centres f32 [n_seg, k, D], inertia f64 numpy [n_seg]), bit for bit the per-segment calls.
+    Bad segments raise ValueError on the host, before the device is touched."""
+    X = ops._feat(X, "kmeans_fit_predict_segmented X")
+    p = ops._segment_ptr(ptr, batch, X.shape[0], "", "kmeans_fit_predict_segmented")
+    sizes = (p[1:] - p[:-1]).tolist()
+    if not sizes:
+        raise ValueError("kmeans_fit_predict_segmented: no segments")
+    for s, n_s in enumerate(sizes):
+        if not (1 <= n_clusters <= n_s):
+            raise ValueError(f"kmeans_fit_predict_segmented: segment {s}: n_samples={n_s} should be >= n_clusters={n_clusters}.")
+    if not X.is_cuda:
+        raise RuntimeError("kmeans_fit_predict_segmented: X must be on a ROCm device (no CPU path)")
+    first, u = segment_streams(int(seed), int(n_init), int(n_clusters), sizes)
+    labels, centres, info = ops.kmeans_fit_segmented(X.detach().float().contiguous(), p, n_clusters, first, u, max_iter=max_iter, tol=tol)
+    inertia = np.array([i["inertia"] for i in info], dtype=np.float64)
+    if return_info:
+        return labels, centres, inertia, info
+    return labels, centres, inertia
+
+
+def segment_streams(seed: int, n_init: int, n_clusters: int, sizes) -> Tuple[np.ndarray, np.ndarray]:
+    """scikit-learn's draws for every segment: (first centres int64 [n_seg, n_init], row ids local to each segment;
+    uniforms float64 [n_init, n_clusters - 1, trials], the same for every segment).  Only the first centre depends on the
+    number of rows (through the uniform cdf), so the stream is drawn once."""
+    rs = np.random.RandomState(seed)
+    trials = 2 + int(math.log(n_clusters))
+    steps = max(n_clusters - 1, 0)
+    r = rs.random_sample(n_init * (1 + steps * trials)).reshape(n_init, 1 + steps * trials)
+    u = np.ascontiguousarray(r[:, 1:]).reshape(n_init, steps, trials)
+    first = np.empty((len(sizes), n_init), dtype=np.int64)
+    for s, n_s in enumerate(sizes):
+        f = _uniform_cdf(int(n_s)).searchsorted(r[:, 0], side="right")
+        first[s] = np.clip(f, 0, int(n_s) - 1)
+    return first, u

@@ -74,25 +74,26 @@ def simtopk(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, metric="cosine
     return idx, val
 
 
-def _segment_ptr(ptr, batch, rows: int, side: str) -> torch.Tensor:
-    """Host int64 offsets [S + 1] from exactly one of ptr (offsets) / batch (sorted segment id per row, PyG convention)."""
+def _segment_ptr(ptr, batch, rows: int, side: str, what: str = "simtopk_segmented") -> torch.Tensor:
+    """Host int64 offsets [S + 1] from exactly one of ptr (offsets) / batch (sorted segment id per row, PyG convention).
+    `what` names the caller in the messages."""
     if (ptr is None) == (batch is None):
-        raise ValueError(f"simtopk_segmented: give exactly one of {side}ptr / {side}batch")
+        raise ValueError(f"{what}: give exactly one of {side}ptr / {side}batch")
     if ptr is not None:
         p = torch.as_tensor(ptr).detach().to("cpu", torch.int64).reshape(-1)
         if p.numel() < 1 or int(p[0]) != 0 or int(p[-1]) != rows:
-            raise ValueError(f"simtopk_segmented: {side}ptr must start at 0 and end at {rows}")
+            raise ValueError(f"{what}: {side}ptr must start at 0 and end at {rows}")
         if p.numel() > 1 and bool((p[1:] < p[:-1]).any()):
-            raise ValueError(f"simtopk_segmented: {side}ptr must be non-decreasing")
+            raise ValueError(f"{what}: {side}ptr must be non-decreasing")
         return p.contiguous()
     b = torch.as_tensor(batch)
     if b.dim() != 1 or b.numel() != rows:
-        raise ValueError(f"simtopk_segmented: {side}batch must hold one segment id per row ({rows})")
+        raise ValueError(f"{what}: {side}batch must hold one segment id per row ({rows})")
     b = b.detach().to("cpu", torch.int64)           # the one device -> host copy of a batch vector
     if rows == 0:
         return torch.zeros(1, dtype=torch.int64)
     if bool((b < 0).any()) or bool((b[1:] < b[:-1]).any()):
-        raise ValueError(f"simtopk_segmented: {side}batch must be sorted and non-negative")
+        raise ValueError(f"{what}: {side}batch must be sorted and non-negative")
     counts = torch.bincount(b)
     return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(counts, 0)])
 
@@ -550,9 +551,52 @@ def kmeans_fit(X: torch.Tensor, n_clusters: int, first_centres, uniforms, *, max
                                    _p(centres), _p(seeds), ctypes.c_void_p(info.ctypes.data), X.device.index or 0,
                                    _stream(X.device))
     _lib.check(rc, "mmf_kmeans_fit")
-    out_info = {"best_init": int(info[0]), "inertia": float(info[1]), "n_iter": int(info[2]), "tol_abs": float(info[3]),
-                "ambiguous_draws": int(info[4]), "ambiguous_trials": int(info[5]), "lockstep_iterations": int(info[6]),
-                "inertia_per_init": info[7::2].tolist(), "n_iter_per_init": [int(v) for v in info[8::2]]}
+    out_info = _kmeans_info(info)
+    if return_seeds:
+        return labels, centres, out_info, seeds
+    return labels, centres, out_info
+
+
+def _kmeans_info(info) -> dict:
+    return {"best_init": int(info[0]), "inertia": float(info[1]), "n_iter": int(info[2]), "tol_abs": float(info[3]),
+            "ambiguous_draws": int(info[4]), "ambiguous_trials": int(info[5]), "lockstep_iterations": int(info[6]),
+            "inertia_per_init": info[7::2].tolist(), "n_iter_per_init": [int(v) for v in info[8::2]]}
+
+
+def kmeans_fit_segmented(X: torch.Tensor, ptr, n_clusters: int, first_centres, uniforms, *, max_iter: int = 300, tol: float = 1e-4,
+                         return_seeds: bool = False):
+    """kmeans_fit for every segment X[ptr[s]:ptr[s+1]] of a ragged batch in one call (mmf_kmeans_fit_segmented), bit for bit
+    what kmeans_fit returns on each slice.  ptr: [n_seg + 1] offsets (host); first_centres: int64 [n_seg, n_init] rows local to
+    each segment; uniforms: float64 [n_init, n_clusters - 1, trials], shared by all segments (HOST numpy arrays: kmeans.py
+    draws them).  Returns (labels int64 [n] (0 .. k-1 within each segment), centres f32 [n_seg, k, d], info: one dict per
+    segment with kmeans_fit's keys ('lockstep_iterations' is that of the segment's group)[, seeds int64 [n_seg, n_init, k],
+    global row ids])."""
+    import numpy as np
+    X = _feat(X, "kmeans_fit_segmented X").float()
+    n, d = X.shape
+    p = np.ascontiguousarray(torch.as_tensor(ptr).detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+    n_seg = int(p.shape[0]) - 1
+    k = int(n_clusters)
+    first = np.ascontiguousarray(first_centres, dtype=np.int64)
+    if first.ndim != 2 or first.shape[0] != n_seg:
+        raise ValueError("kmeans_fit_segmented: first_centres must be [n_seg, n_init]")
+    n_init = int(first.shape[1])
+    u = np.ascontiguousarray(uniforms, dtype=np.float64)
+    if k > 1 and (u.ndim != 3 or u.shape[0] != n_init or u.shape[1] != k - 1):
+        raise ValueError("kmeans_fit_segmented: uniforms must be [n_init, n_clusters - 1, trials]")
+    trials = int(u.shape[2]) if k > 1 else 1
+    _need_gpu(X, "kmeans_fit_segmented")
+    labels = torch.empty(n, dtype=torch.int64, device=X.device)
+    centres = torch.empty((max(n_seg, 0), k, d), dtype=torch.float32, device=X.device)
+    seeds = torch.empty((max(n_seg, 0), n_init, k), dtype=torch.int64, device=X.device) if return_seeds else None
+    info = np.zeros((max(n_seg, 0), 7 + 2 * n_init), dtype=np.float64)
+    rc = _lib.lib().mmf_kmeans_fit_segmented(_p(X), n, d, ctypes.c_void_p(p.ctypes.data), n_seg, k, n_init, trials,
+                                             ctypes.c_void_p(first.ctypes.data), ctypes.c_void_p(u.ctypes.data) if k > 1 else None,
+                                             int(max_iter), float(tol), _p(labels), _p(centres), _p(seeds),
+                                             ctypes.c_void_p(info.ctypes.data), X.device.index or 0,
+                                             _stream(X.device))
+    _lib.check(rc, "mmf_kmeans_fit_segmented")
+    out_info = [_kmeans_info(row) for row in info]
     if return_seeds:
         return labels, centres, out_info, seeds
     return labels, centres, out_info
