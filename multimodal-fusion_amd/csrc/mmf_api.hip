@@ -1094,6 +1094,21 @@ int mmf_knn_pairs(const int64_t* nbr, int64_t n, int k, const int64_t* labels, i
   return launch_knn_pairs(nbr, n, k, labels, pair_lo, pair_hi, out_count, static_cast<hipStream_t>(hip_stream));
 }
 
+// both KMeans entries after their own argument checks: the plain fit is the one segment ptr = {0, n}
+static int kmeans_fit_run(const float* X, int64_t d, const int64_t* ptr, int64_t n_seg, int64_t k, int64_t n_init, int trials,
+                          const int64_t* first_centres, const double* uniforms, int max_iter, double tol, int64_t* labels, float* centres,
+                          int64_t* seeds, double* info, bool segmented, int device_id, void* hip_stream) {
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  size_t need = 0;
+  const std::vector<int64_t> groups = kmeans_segment_groups(ptr, n_seg, d, k, n_init, trials, &need);
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
+  return launch_kmeans_fit(X, d, ptr, groups, k, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds, info,
+                           ws.take<char>(need), s, segmented);
+}
+
 int mmf_kmeans_fit(const float* X, int64_t n, int64_t d, int64_t n_clusters, int64_t n_init, int trials, const int64_t* first_centres,
                    const double* uniforms, int max_iter, double tol, int64_t* labels, float* centres, int64_t* seeds, double* info,
                    int device_id, void* hip_stream) {
@@ -1111,14 +1126,9 @@ int mmf_kmeans_fit(const float* X, int64_t n, int64_t d, int64_t n_clusters, int
   if (!X || !first_centres || (n_clusters > 1 && !uniforms) || !labels) { set_error("kmeans_fit: NULL pointer"); return MMF_E_INVALID; }
   for (int64_t i = 0; i < n_init; ++i)
     if (first_centres[i] < 0 || first_centres[i] >= n) { set_error("kmeans_fit: first_centres[%lld] outside [0, n)", (long long)i); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  const size_t need = kmeans_scratch_bytes(n, d, n_clusters, n_init, trials);
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
-  return launch_kmeans_fit(X, n, d, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds, info,
-                           ws.take<char>(need), s);
+  const int64_t ptr[2] = {0, n};
+  return kmeans_fit_run(X, d, ptr, 1, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds, info, false,
+                        device_id, hip_stream);
 }
 
 int mmf_kmeans_fit_segmented(const float* X, int64_t n, int64_t d, const int64_t* ptr, int64_t n_seg, int64_t n_clusters, int64_t n_init,
@@ -1163,15 +1173,8 @@ int mmf_kmeans_fit_segmented(const float* X, int64_t n, int64_t d, const int64_t
         return MMF_E_INVALID;
       }
     }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  size_t need = 0;
-  const std::vector<int64_t> groups = kmeans_segment_groups(ptr, n_seg, d, n_clusters, n_init, trials, &need);
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
-  return launch_kmeans_fit_segmented(X, d, ptr, groups, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds,
-                                     info, ws.take<char>(need), s);
+  return kmeans_fit_run(X, d, ptr, n_seg, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds, info, true,
+                        device_id, hip_stream);
 }
 
 int mmf_lower_median(const float* v, int64_t count, float* out_median, int device_id, void* hip_stream) {

@@ -243,17 +243,15 @@ int launch_segment_offdiag_mean(const float* K, int64_t n, const int64_t* order,
 size_t clique_scratch_bytes(int64_t n, int64_t S);
 int launch_clique_pairs(const int64_t* order, const int64_t* offsets, int64_t n, int64_t S, int64_t* lo, int64_t* hi,
                         int64_t capacity, int64_t* out_count, void* scratch, hipStream_t s);
-// mmf_kmeans.hip: scikit-learn's KMeans fit, decision for decision, all restarts in lockstep (host-synchronous)
-size_t kmeans_scratch_bytes(int64_t n, int64_t d, int64_t k, int64_t n_init, int trials);
-int launch_kmeans_fit(const float* X, int64_t n, int64_t d, int64_t k, int64_t n_init, int trials, const int64_t* first_h,
-                      const double* u_h, int max_iter, double tol, int64_t* out_labels, float* out_centres, int64_t* out_seeds,
-                      double* info_h, void* scratch, hipStream_t s);
-// the segmented fit (mmf_kmeans_fit_segmented): groups of consecutive segments [bounds[i], bounds[i + 1]) that fit one lockstep
-// (n_seg n_init k <= segment_max_segments(), n_init rows < 2^31, bounded scratch); *max_bytes = the largest group's scratch
+// mmf_kmeans.hip: scikit-learn's KMeans fit, decision for decision, all restarts in lockstep (host-synchronous).
+// Groups of consecutive segments [bounds[i], bounds[i + 1]) that fit one lockstep (n_seg n_init k <= segment_max_segments(),
+// n_init rows < 2^31, bounded scratch); *max_bytes = the largest group's scratch.  The plain fit is ptr = {0, n}, one segment.
 std::vector<int64_t> kmeans_segment_groups(const int64_t* ptr, int64_t n_seg, int64_t d, int64_t k, int64_t n_init, int trials, size_t* max_bytes);
-int launch_kmeans_fit_segmented(const float* X, int64_t d, const int64_t* ptr, const std::vector<int64_t>& groups, int64_t k, int64_t n_init,
-                                int trials, const int64_t* first_h, const double* u_h, int max_iter, double tol, int64_t* out_labels,
-                                float* out_centres, int64_t* out_seeds, double* info_h, void* scratch, hipStream_t s);
+// segmented: mmf_kmeans_fit_segmented (first_h [n_seg][n_init], info per segment, seeds as row ids of the batch); otherwise
+// mmf_kmeans_fit on its one group
+int launch_kmeans_fit(const float* X, int64_t d, const int64_t* ptr, const std::vector<int64_t>& groups, int64_t k, int64_t n_init, int trials,
+                      const int64_t* first_h, const double* u_h, int max_iter, double tol, int64_t* out_labels, float* out_centres,
+                      int64_t* out_seeds, double* info_h, void* scratch, hipStream_t s, bool segmented);
 int launch_knn_pairs(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t* lo, int64_t* hi, int64_t* out_count,
                      hipStream_t s);
 

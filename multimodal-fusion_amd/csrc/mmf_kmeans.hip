@@ -1067,217 +1067,20 @@ __global__ void km_init_state_kernel(KmState* st, int n_init) {
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-static inline size_t al(size_t b) { return (b + 255) & ~size_t(255); }
-static int64_t km_ds(int64_t d) { return (d + KM_KC - 1) / KM_KC * KM_KC; }
-
-size_t kmeans_scratch_bytes(int64_t n, int64_t d, int64_t k, int64_t n_init, int trials) {
-  const int64_t ds = km_ds(d), R = n_init * trials, ntile = (n + KM_T - 1) / KM_T, nblk = (n + 255) / 256, S = n_init * k;
-  const int64_t strips = (ds + 63) / 64;
-  size_t b = 0;
-  b += al((size_t)n * ds * 4);                 // Xc
-  b += al((size_t)n * 8);                      // xx
-  b += al((size_t)nblk * d * 8);               // column partials
-  b += 3 * al((size_t)d * 8) + al((size_t)d * 4);   // mean64, var64, (spare), mean32
-  b += al(256);                                // tol_abs, best, amb
-  b += 2 * al((size_t)R * n * 4);              // trial rows, two steps
-  b += 2 * al((size_t)R * 2 * ntile * 8);      // their tile partials (32-point tiles at most)
-  b += 2 * al((size_t)R * 8) + al((size_t)n_init * 8) + al((size_t)n_init * 4) + al((size_t)n_init * 4);   // cand x 2, first, pot32, sel
-  b += al((size_t)n_init * (k > 1 ? k - 1 : 1) * trials * 8);                 // uniforms
-  b += al((size_t)S * 8);                      // seeds
-  b += 2 * al((size_t)S * ds * 4);             // centres x 2
-  b += al((size_t)S * ds * 4);                 // sums32
-  b += al((size_t)S * 8);                      // cc
-  b += al((size_t)n_init * n * 8) * 2;         // labels, order
-  b += al((size_t)S * 8) + al((size_t)(S + 1) * 8);   // counts, offsets
-  b += al(segment_sort_scratch_bytes(n_init * n, S)) + al(4);
-  b += al((size_t)S * strips * 8);             // shift partials
-  b += al((size_t)n_init * sizeof(KmState)) + al((size_t)n_init * 4);
-  b += al((size_t)n * 8) + al((size_t)k * 4);  // relocation scratch
-  b += al((size_t)n_init * ntile * 8);         // inertia partials
-  b += al((size_t)k * 4);                      // map
-  return b + 4096;
-}
-
-int launch_kmeans_fit(const float* X, int64_t n, int64_t d, int64_t k, int64_t n_init, int trials, const int64_t* first_h,
-                      const double* u_h, int max_iter, double tol, int64_t* out_labels, float* out_centres, int64_t* out_seeds,
-                      double* info_h, void* scratch, hipStream_t s) {
-  const int64_t ds = km_ds(d), R = n_init * trials, ntile = (n + KM_T - 1) / KM_T, nblk = (n + 255) / 256, S = n_init * k;
-  const int64_t strips = (ds + 63) / 64;
-  char* p = static_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* q = p; p += al(bytes); return q; };
-  float* Xc = (float*)take((size_t)n * ds * 4);
-  double* xx = (double*)take((size_t)n * 8);
-  double* colpart = (double*)take((size_t)nblk * d * 8);
-  double* mean64 = (double*)take((size_t)d * 8);
-  double* var64 = (double*)take((size_t)d * 8);
-  (void)take((size_t)d * 8);
-  float* mean32 = (float*)take((size_t)d * 4);
-  char* misc = take(256);
-  double* tol_abs = (double*)misc;
-  int* best = (int*)(misc + 8);
-  unsigned int* amb = (unsigned int*)(misc + 16);
-  float* rows[2];
-  double* rpart[2];
-  int64_t* cand[2];
-  for (int u = 0; u < 2; ++u) rows[u] = (float*)take((size_t)R * n * 4);
-  for (int u = 0; u < 2; ++u) rpart[u] = (double*)take((size_t)R * 2 * ntile * 8);
-  for (int u = 0; u < 2; ++u) cand[u] = (int64_t*)take((size_t)R * 8);
-  int64_t* first = (int64_t*)take((size_t)n_init * 8);
-  float* pot32 = (float*)take((size_t)n_init * 4);
-  int* sel = (int*)take((size_t)n_init * 4);
-  const size_t u_count = (size_t)n_init * (k > 1 ? k - 1 : 1) * trials;
-  double* U = (double*)take(u_count * 8);
-  int64_t* seeds = (int64_t*)take((size_t)S * 8);
-  float* C0 = (float*)take((size_t)S * ds * 4);
-  float* C1 = (float*)take((size_t)S * ds * 4);
-  float* sums32 = (float*)take((size_t)S * ds * 4);
-  double* cc = (double*)take((size_t)S * 8);
-  int64_t* labels = (int64_t*)take((size_t)n_init * n * 8);
-  int64_t* order = (int64_t*)take((size_t)n_init * n * 8);
-  int64_t* counts = (int64_t*)take((size_t)S * 8);
-  int64_t* offsets = (int64_t*)take((size_t)(S + 1) * 8);
-  void* sort_scratch = take(segment_sort_scratch_bytes(n_init * n, S));
-  uint32_t* bad = (uint32_t*)take(4);
-  double* shift_part = (double*)take((size_t)S * strips * 8);
-  KmState* st = (KmState*)take((size_t)n_init * sizeof(KmState));
-  int* status = (int*)take((size_t)n_init * 4);
-  double* dist = (double*)take((size_t)n * 8);
-  float* cntf = (float*)take((size_t)k * 4);
-  double* ipart = (double*)take((size_t)n_init * ntile * 8);
-  int* map = (int*)take((size_t)k * 4);
-
-  const size_t lds = (size_t)4 * KM_T * KM_LD * 8;
-  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(km_seed_dots_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(km_seed_dots_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-
-  // the caller's stream of random numbers
-  MMF_HIP(hipMemcpyAsync(first, first_h, (size_t)n_init * 8, hipMemcpyHostToDevice, s));
-  if (k > 1) MMF_HIP(hipMemcpyAsync(U, u_h, u_count * 8, hipMemcpyHostToDevice, s));
-  MMF_HIP(hipMemsetAsync(misc, 0, 256, s));
-
-  // centring, tolerance, norms
-  const dim3 cgrid((unsigned)nblk, (unsigned)((d + 63) / 64));
-  hipLaunchKernelGGL(km_colsum_kernel, cgrid, dim3(256), 0, s, X, n, d, (const double*)nullptr, colpart);
-  MMF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(km_colfin_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, colpart, nblk, n, d, mean64, (float*)nullptr);
-  MMF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(km_colmean_seq_kernel, dim3((unsigned)((d + CM_COLS - 1) / CM_COLS)), dim3(256), 0, s, X, n, d, mean32);
-  MMF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(km_colsum_kernel, cgrid, dim3(256), 0, s, X, n, d, (const double*)mean64, colpart);
-  MMF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(km_colfin_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, colpart, nblk, n, d, var64, (float*)nullptr);
-  MMF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(km_tol_kernel, dim3(1), dim3(1024), 0, s, var64, d, tol, tol_abs);
-  MMF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(km_centre_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, X, n, d, ds, mean32, Xc, xx);
-  MMF_LAUNCH_CHECK();
-
-  // k-means++ for all restarts in lockstep: per step one small launch (choice of the previous step's trials + draw of the next
-  // candidates) and one launch of the distance kernel; the running closest-centre distances are a row of the previous step's output
-  hipLaunchKernelGGL(km_seed_first_kernel, dim3((unsigned)((n_init + 63) / 64)), dim3(64), 0, s, first, n_init, k, seeds, cand[0]);
-  MMF_LAUNCH_CHECK();
-  const bool small_tiles = ntile < 512;          // 64-point tiles would not give every SIMD two waves: 32-point tiles
-  const int pt = small_tiles ? 32 : 64;
-  const int64_t stile = (n + pt - 1) / pt;
-  auto dots = [&](const int64_t* cd, int64_t Rn, int64_t group, const float* prev, float* out, double* part) {
-    const dim3 grid((unsigned)stile, (unsigned)((Rn + KM_T - 1) / KM_T));
-    if (small_tiles) hipLaunchKernelGGL(km_seed_dots_kernel<2>, grid, dim3(256), lds, s, Xc, n, ds, xx, cd, Rn, group, prev, sel, out, part);
-    else hipLaunchKernelGGL(km_seed_dots_kernel<4>, grid, dim3(256), lds, s, Xc, n, ds, xx, cd, Rn, group, prev, sel, out, part);
-  };
-  dots(cand[0], n_init, 1, nullptr, rows[0], rpart[0]);
-  MMF_LAUNCH_CHECK();
-  int cur = 0, tprev = 1;
-  for (int64_t step = 1; step <= k; ++step) {
-    const bool last = step == k;
-    hipLaunchKernelGGL(km_seed_step_kernel, dim3((unsigned)n_init), dim3(256), 0, s, rows[cur], rpart[cur], stile, pt, n, tprev, cand[cur], k, step - 1,
-                       last ? (const double*)nullptr : U + (step - 1) * trials, (k - 1) * trials, trials, pot32, seeds, sel, cand[cur ^ 1], amb);
-    MMF_LAUNCH_CHECK();
-    if (last) break;
-    dots(cand[cur ^ 1], R, trials, rows[cur], rows[cur ^ 1], rpart[cur ^ 1]);
-    MMF_LAUNCH_CHECK();
-    cur ^= 1;
-    tprev = trials;
-  }
-  if (out_seeds) MMF_HIP(hipMemcpyAsync(out_seeds, seeds, (size_t)S * 8, hipMemcpyDeviceToDevice, s));
-
-  // Lloyd iterations, all restarts in lockstep
-  hipLaunchKernelGGL(km_gather_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, Xc, ds, seeds, S, C0);
-  MMF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(km_init_state_kernel, dim3((unsigned)((n_init + 63) / 64)), dim3(64), 0, s, st, (int)n_init);
-  MMF_LAUNCH_CHECK();
-  MMF_HIP(hipMemsetAsync(labels, 0xff, (size_t)n_init * n * 8, s));      // -1: every label "changes" in the first iteration
-  std::vector<int> h_status((size_t)n_init, KM_RUN);
-  int it = 0;
-  for (;; ++it) {
-    bool any_run = false, any_live = false;
-    for (int64_t g = 0; g < n_init; ++g) { any_run |= h_status[g] == KM_RUN; any_live |= h_status[g] != KM_DONE; }
-    if (!any_live) break;
-    hipLaunchKernelGGL(km_rownorm_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, C0, C1, st, k, S, ds, cc);
-    MMF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_assign_kernel, dim3((unsigned)ntile, (unsigned)n_init), dim3(256), lds, s, Xc, n, ds, C0, C1, cc, k, st, 0, labels);
-    MMF_LAUNCH_CHECK();
-    if (any_run) {
-      MMF_TRY(launch_segment_sort(labels, n_init * n, S, counts, offsets, order, sort_scratch, bad, s));
-      hipLaunchKernelGGL(km_update_kernel, dim3((unsigned)S, (unsigned)strips), dim3(256), 0, s, Xc, n, ds, order, offsets, k, C0, C1, sums32, st, 0,
-                         shift_part);
-      MMF_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(km_state_kernel, dim3((unsigned)n_init), dim3(64), 0, s, st, (int)n_init, k, strips, shift_part, tol_abs, it, max_iter,
-                       -1, status);
-    MMF_LAUNCH_CHECK();
-    MMF_HIP(hipMemcpyAsync(h_status.data(), status, (size_t)n_init * 4, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipStreamSynchronize(s));
-    for (int64_t g = 0; g < n_init; ++g) {
-      if (h_status[g] != KM_RELOC) continue;
-      hipLaunchKernelGGL(km_relocate_kernel, dim3(1), dim3(1024), 0, s, Xc, n, ds, k, (int)g, labels, offsets, C0, C1, sums32, st, dist, cntf, shift_part,
-                         strips);
-      MMF_LAUNCH_CHECK();
-      hipLaunchKernelGGL(km_state_kernel, dim3((unsigned)n_init), dim3(64), 0, s, st, (int)n_init, k, strips, shift_part, tol_abs, it, max_iter,
-                         (int)g, status);
-      MMF_LAUNCH_CHECK();
-      MMF_HIP(hipMemcpyAsync(h_status.data(), status, (size_t)n_init * 4, hipMemcpyDeviceToHost, s));
-      MMF_HIP(hipStreamSynchronize(s));
-    }
-    if (it > max_iter + 2) { set_error("kmeans_fit: the convergence state machine did not terminate (internal invariant)"); return MMF_E_INTERNAL; }
-  }
-
-  hipLaunchKernelGGL(km_inertia_kernel, dim3((unsigned)ntile, (unsigned)n_init), dim3(256), 0, s, Xc, n, ds, C0, C1, st, labels, ipart);
-  MMF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(km_pick_kernel, dim3(1), dim3(1024), 0, s, st, (int)n_init, n, k, ipart, ntile, labels, map, best);
-  MMF_LAUNCH_CHECK();
-  const int64_t fin = n > k * d ? n : k * d;
-  hipLaunchKernelGGL(km_finish_kernel, dim3((unsigned)((fin + 255) / 256)), dim3(256), 0, s, st, best, n, k, d, ds, labels, C0, C1, mean32, out_labels,
-                     out_centres);
-  MMF_LAUNCH_CHECK();
-  if (info_h) {
-    // [0] best restart, [1] its inertia, [2] its iterations, [3] tol_abs, [4] ambiguous draws, [5] ambiguous trial choices,
-    // [6] Lloyd lockstep iterations, then per restart: inertia, iterations
-    std::vector<KmState> hs((size_t)n_init);
-    int h_best = 0;
-    unsigned int h_amb[2] = {0, 0};
-    double h_tol = 0.0;
-    MMF_HIP(hipMemcpyAsync(hs.data(), st, (size_t)n_init * sizeof(KmState), hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipMemcpyAsync(&h_best, best, 4, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipMemcpyAsync(h_amb, amb, 8, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipMemcpyAsync(&h_tol, tol_abs, 8, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipStreamSynchronize(s));
-    info_h[0] = (double)h_best; info_h[1] = hs[h_best].inertia; info_h[2] = (double)hs[h_best].n_iter; info_h[3] = h_tol;
-    info_h[4] = (double)h_amb[0]; info_h[5] = (double)h_amb[1]; info_h[6] = (double)it;
-    for (int64_t g = 0; g < n_init; ++g) { info_h[7 + 2 * g] = hs[g].inertia; info_h[8 + 2 * g] = (double)hs[g].n_iter; }
-  }
-  return MMF_OK;
-}
-
-// ---- segmented fit ----------------------------------------------------------------------------------------------------
+// One driver serves both fits.  A group of consecutive segments runs as one lockstep fit (km_fit_group); the plain fit is the
+// group of its one segment, run with an empty pack: the plain instantiations, without the segment and work tables.
 // out[i] = seeds[i] + base: group-local seed rows -> row ids of the whole batch
 __global__ void km_seeds_out_kernel(const int64_t* __restrict__ seeds, int64_t count, int64_t base, int64_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) out[i] = seeds[i] + base;
 }
 
+static inline size_t al(size_t b) { return (b + 255) & ~size_t(255); }
+static int64_t km_ds(int64_t d) { return (d + KM_KC - 1) / KM_KC * KM_KC; }
+
 namespace {
-int64_t km_seed_pt(int64_t n) { return (n + KM_T - 1) / KM_T < 512 ? 32 : 64; }     // the plain fit's seeding tile width (small_tiles)
+// seeding tile width for n rows: 32 points while 64-point tiles would not give every SIMD two waves
+int64_t km_seed_pt(int64_t n) { return (n + KM_T - 1) / KM_T < 512 ? 32 : 64; }
 
 struct KmCounts {                // sizes of a group of consecutive segments
   int64_t nseg = 0, nrows = 0, max_n = 0, nblk = 0, ntile = 0, nst32 = 0, nst64 = 0;
@@ -1368,6 +1171,179 @@ KmSegBufs km_seg_carve(char* base, const KmCounts& g, int64_t d, int64_t k, int6
   return b;
 }
 
+KmSegCtx km_with(KmSegCtx c, const KmWork* work, int64_t tprev) { c.work = work; c.tprev = tprev; return c; }
+
+// One group, carved in `b`.  Ctx: empty (the plain fit: one segment, the plain instantiations) or the group's KmSegCtx, whose
+// work table and tprev every launch sets with km_with.
+template <class... Ctx>
+int km_fit_group(const float* X, int64_t d, const KmGroup& gp, const KmSegBufs& b, int64_t k, int64_t n_init, int trials,
+                 const int64_t* first_h, const double* u_h, int max_iter, double tol, int64_t* out_labels, float* out_centres,
+                 int64_t* out_seeds, double* info_h, hipStream_t s, Ctx... proto) {
+  const int64_t ds = km_ds(d), strips = (ds + 63) / 64;
+  const int64_t nseg = gp.nseg, nr = gp.nrows, G = nseg * n_init, S = G * k, R = n_init * trials;
+  const size_t lds = (size_t)4 * KM_T * KM_LD * 8;
+  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((km_seed_dots_kernel<2, Ctx...>)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((km_seed_dots_kernel<4, Ctx...>)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_kernel<Ctx...>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  KmWork* w_blk = b.work;
+  KmWork* w_tile = w_blk + gp.nblk;
+  KmWork* w_st32 = w_tile + gp.ntile;
+  KmWork* w_st64 = w_st32 + gp.nst32;
+  // (the host vectors copied below live until the first status read of the Lloyd loop has synchronised the stream)
+  const float* Xg = X + gp.row0 * d;
+  // the caller's random stream: first centres as group-local rows, the shared uniforms; the segmented fit's tables
+  std::vector<int64_t> first((size_t)G);
+  for (int64_t q = 0; q < nseg; ++q)
+    for (int64_t r = 0; r < n_init; ++r) first[q * n_init + r] = gp.segs[q].row0 + first_h[(gp.s0 + q) * n_init + r];
+  MMF_HIP(hipMemcpyAsync(b.first, first.data(), (size_t)G * 8, hipMemcpyHostToDevice, s));
+  if (k > 1) MMF_HIP(hipMemcpyAsync(b.U, u_h, (size_t)n_init * (k - 1) * trials * 8, hipMemcpyHostToDevice, s));
+  if constexpr (sizeof...(Ctx) > 0) {
+    MMF_HIP(hipMemcpyAsync(b.segs, gp.segs.data(), (size_t)nseg * sizeof(KmSeg), hipMemcpyHostToDevice, s));
+    MMF_HIP(hipMemcpyAsync(b.work, gp.work.data(), gp.work.size() * sizeof(KmWork), hipMemcpyHostToDevice, s));
+  }
+  MMF_HIP(hipMemsetAsync(b.amb, 0, (size_t)nseg * 8, s));
+
+  // centring, tolerance, norms: per segment
+  const dim3 cgrid((unsigned)gp.nblk, (unsigned)((d + 63) / 64)), fgrid((unsigned)((d + 255) / 256), (unsigned)nseg);
+  hipLaunchKernelGGL(km_colsum_kernel<Ctx...>, cgrid, dim3(256), 0, s, Xg, nr, d, (const double*)nullptr, b.colpart, km_with(proto, w_blk, 0)...);
+  MMF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(km_colfin_kernel<Ctx...>, fgrid, dim3(256), 0, s, b.colpart, gp.nblk, nr, d, b.mean64, (float*)nullptr, km_with(proto, nullptr, 0)...);
+  MMF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(km_colmean_seq_kernel<Ctx...>, dim3((unsigned)((d + CM_COLS - 1) / CM_COLS), (unsigned)nseg), dim3(256), 0, s, Xg, nr, d, b.mean32,
+                     km_with(proto, nullptr, 0)...);
+  MMF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(km_colsum_kernel<Ctx...>, cgrid, dim3(256), 0, s, Xg, nr, d, (const double*)b.mean64, b.colpart, km_with(proto, w_blk, 0)...);
+  MMF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(km_colfin_kernel<Ctx...>, fgrid, dim3(256), 0, s, b.colpart, gp.nblk, nr, d, b.var64, (float*)nullptr, km_with(proto, nullptr, 0)...);
+  MMF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(km_tol_kernel<Ctx...>, dim3((unsigned)nseg), dim3(1024), 0, s, b.var64, d, tol, b.tol_abs, km_with(proto, nullptr, 0)...);
+  MMF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(km_centre_kernel<Ctx...>, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, s, Xg, nr, d, ds, b.mean32, b.Xc, b.xx,
+                     km_with(proto, nullptr, 0)...);
+  MMF_LAUNCH_CHECK();
+
+  // k-means++: every restart of every segment in lockstep; per step one choice/draw launch and one distance launch per tile
+  // width present (one in the plain fit); the running closest-centre distances are a row of the previous step's output
+  hipLaunchKernelGGL(km_seed_first_kernel, dim3((unsigned)((G + 63) / 64)), dim3(64), 0, s, b.first, G, k, b.seeds, b.cand[0]);
+  MMF_LAUNCH_CHECK();
+  auto dots = [&](const int64_t* cd, int64_t Rn, int64_t group, const float* prev, int64_t tprev, float* out, double* part) -> int {
+    const unsigned ry = (unsigned)((Rn + KM_T - 1) / KM_T);
+    if (gp.nst32) {
+      hipLaunchKernelGGL((km_seed_dots_kernel<2, Ctx...>), dim3((unsigned)gp.nst32, ry), dim3(256), lds, s, b.Xc, nr, ds, b.xx, cd, Rn, group, prev,
+                         b.sel, out, part, km_with(proto, w_st32, tprev)...);
+      MMF_LAUNCH_CHECK();
+    }
+    if (gp.nst64) {
+      hipLaunchKernelGGL((km_seed_dots_kernel<4, Ctx...>), dim3((unsigned)gp.nst64, ry), dim3(256), lds, s, b.Xc, nr, ds, b.xx, cd, Rn, group, prev,
+                         b.sel, out, part, km_with(proto, w_st64, tprev)...);
+      MMF_LAUNCH_CHECK();
+    }
+    return MMF_OK;
+  };
+  MMF_TRY(dots(b.cand[0], n_init, 1, nullptr, 1, b.rows[0], b.rpart[0]));
+  int cur = 0, tprev = 1;
+  for (int64_t step = 1; step <= k; ++step) {
+    const bool last = step == k;
+    // (the tile count and width are the plain fit's; the segmented kernels take each segment's from its KmSeg)
+    hipLaunchKernelGGL(km_seed_step_kernel<Ctx...>, dim3((unsigned)G), dim3(256), 0, s, b.rows[cur], b.rpart[cur], gp.nstile(), (int)gp.segs[0].pt, nr,
+                       tprev, b.cand[cur], k, step - 1, last ? (const double*)nullptr : b.U + (step - 1) * trials, (k - 1) * trials, trials, b.pot32,
+                       b.seeds, b.sel, b.cand[cur ^ 1], b.amb, km_with(proto, nullptr, tprev)...);
+    MMF_LAUNCH_CHECK();
+    if (last) break;
+    MMF_TRY(dots(b.cand[cur ^ 1], R, trials, b.rows[cur], tprev, b.rows[cur ^ 1], b.rpart[cur ^ 1]));
+    cur ^= 1;
+    tprev = trials;
+  }
+  if (out_seeds) {
+    int64_t* o = out_seeds + gp.s0 * n_init * k;
+    if (gp.row0 == 0) {      // group-local rows are the batch's
+      MMF_HIP(hipMemcpyAsync(o, b.seeds, (size_t)S * 8, hipMemcpyDeviceToDevice, s));
+    } else {
+      hipLaunchKernelGGL(km_seeds_out_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, b.seeds, S, gp.row0, o);
+      MMF_LAUNCH_CHECK();
+    }
+  }
+
+  // Lloyd iterations: every restart of the group in lockstep, one status read per iteration
+  hipLaunchKernelGGL(km_gather_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, b.Xc, ds, b.seeds, S, b.C0);
+  MMF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(km_init_state_kernel, dim3((unsigned)((G + 63) / 64)), dim3(64), 0, s, b.st, (int)G);
+  MMF_LAUNCH_CHECK();
+  MMF_HIP(hipMemsetAsync(b.labels, 0xff, (size_t)n_init * nr * 8, s));      // -1: every label "changes" in the first iteration
+  std::vector<int> h_status((size_t)G, KM_RUN);
+  int it = 0;
+  for (;; ++it) {
+    bool any_run = false, any_live = false;
+    for (int64_t g = 0; g < G; ++g) { any_run |= h_status[g] == KM_RUN; any_live |= h_status[g] != KM_DONE; }
+    if (!any_live) break;
+    hipLaunchKernelGGL(km_rownorm_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, b.C0, b.C1, b.st, k, S, ds, b.cc);
+    MMF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_assign_kernel<Ctx...>, dim3((unsigned)gp.ntile, (unsigned)n_init), dim3(256), lds, s, b.Xc, nr, ds, b.C0, b.C1, b.cc, k, b.st,
+                       0, b.labels, km_with(proto, w_tile, 0)...);
+    MMF_LAUNCH_CHECK();
+    if (any_run) {
+      MMF_TRY(launch_segment_sort(b.labels, n_init * nr, S, b.counts, b.offsets, b.order, b.sort_scratch, b.bad, s));
+      hipLaunchKernelGGL(km_update_kernel<Ctx...>, dim3((unsigned)S, (unsigned)strips), dim3(256), 0, s, b.Xc, nr, ds, b.order, b.offsets, k, b.C0, b.C1,
+                         b.sums32, b.st, 0, b.shift_part, km_with(proto, nullptr, 0)...);
+      MMF_LAUNCH_CHECK();
+    }
+    // g < 0: the state step after the iteration; g >= 0: after restart g's relocation
+    auto state = [&](int g) -> int {
+      hipLaunchKernelGGL(km_state_kernel<Ctx...>, dim3((unsigned)G), dim3(64), 0, s, b.st, (int)n_init, k, strips, b.shift_part, b.tol_abs, it, max_iter,
+                         g, b.status, km_with(proto, nullptr, 0)...);
+      MMF_LAUNCH_CHECK();
+      MMF_HIP(hipMemcpyAsync(h_status.data(), b.status, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipStreamSynchronize(s));
+      return MMF_OK;
+    };
+    MMF_TRY(state(-1));
+    for (int64_t g = 0; g < G; ++g) {
+      if (h_status[g] != KM_RELOC) continue;
+      hipLaunchKernelGGL(km_relocate_kernel<Ctx...>, dim3(1), dim3(1024), 0, s, b.Xc, nr, ds, k, (int)g, b.labels, b.offsets, b.C0, b.C1, b.sums32, b.st,
+                         b.dist, b.cntf, b.shift_part, strips, km_with(proto, nullptr, 0)...);
+      MMF_LAUNCH_CHECK();
+      MMF_TRY(state((int)g));
+    }
+    if (it > max_iter + 2) {
+      set_error("%s: the convergence state machine did not terminate (internal invariant)", sizeof...(Ctx) ? "kmeans_fit_segmented" : "kmeans_fit");
+      return MMF_E_INTERNAL;
+    }
+  }
+
+  hipLaunchKernelGGL(km_inertia_kernel<Ctx...>, dim3((unsigned)gp.ntile, (unsigned)n_init), dim3(256), 0, s, b.Xc, nr, ds, b.C0, b.C1, b.st, b.labels,
+                     b.ipart, km_with(proto, w_tile, 0)...);
+  MMF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(km_pick_kernel<Ctx...>, dim3((unsigned)nseg), dim3(1024), 0, s, b.st, (int)n_init, nr, k, b.ipart, gp.ntile, b.labels, b.map, b.best,
+                     km_with(proto, nullptr, 0)...);
+  MMF_LAUNCH_CHECK();
+  const int64_t fin = gp.max_n > k * d ? gp.max_n : k * d;
+  hipLaunchKernelGGL(km_finish_kernel<Ctx...>, dim3((unsigned)((fin + 255) / 256), (unsigned)nseg), dim3(256), 0, s, b.st, b.best, nr, k, d, ds, b.labels,
+                     b.C0, b.C1, b.mean32, out_labels + gp.row0, out_centres ? out_centres + gp.s0 * k * d : nullptr, km_with(proto, nullptr, 0)...);
+  MMF_LAUNCH_CHECK();
+  if (info_h) {
+    // per segment: [0] best restart, [1] its inertia, [2] its iterations, [3] tol_abs, [4] ambiguous draws, [5] ambiguous trial
+    // choices, [6] the group's Lloyd lockstep iterations, then per restart: inertia, iterations
+    std::vector<KmState> hs((size_t)G);
+    std::vector<int> h_best((size_t)nseg);
+    std::vector<unsigned int> h_amb((size_t)nseg * 2);
+    std::vector<double> h_tol((size_t)nseg);
+    MMF_HIP(hipMemcpyAsync(hs.data(), b.st, (size_t)G * sizeof(KmState), hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipMemcpyAsync(h_best.data(), b.best, (size_t)nseg * 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipMemcpyAsync(h_amb.data(), b.amb, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipMemcpyAsync(h_tol.data(), b.tol_abs, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    for (int64_t q = 0; q < nseg; ++q) {
+      double* o = info_h + (gp.s0 + q) * (7 + 2 * n_init);
+      const KmState* sq = hs.data() + q * n_init;
+      const int bq = h_best[q];
+      o[0] = (double)bq; o[1] = sq[bq].inertia; o[2] = (double)sq[bq].n_iter; o[3] = h_tol[q];
+      o[4] = (double)h_amb[2 * q]; o[5] = (double)h_amb[2 * q + 1]; o[6] = (double)it;
+      for (int64_t r = 0; r < n_init; ++r) { o[7 + 2 * r] = sq[r].inertia; o[8 + 2 * r] = (double)sq[r].n_iter; }
+    }
+  }
+  return MMF_OK;
+}
+
 constexpr size_t KM_GROUP_BYTES = (size_t)2 << 30;      // a group grows while its scratch stays under this (or holds one segment)
 }  // namespace
 
@@ -1396,162 +1372,17 @@ std::vector<int64_t> kmeans_segment_groups(const int64_t* ptr, int64_t n_seg, in
   return bounds;
 }
 
-int launch_kmeans_fit_segmented(const float* X, int64_t d, const int64_t* ptr, const std::vector<int64_t>& groups, int64_t k, int64_t n_init,
-                                int trials, const int64_t* first_h, const double* u_h, int max_iter, double tol, int64_t* out_labels,
-                                float* out_centres, int64_t* out_seeds, double* info_h, void* scratch, hipStream_t s) {
-  const int64_t ds = km_ds(d), strips = (ds + 63) / 64;
-  const size_t lds = (size_t)4 * KM_T * KM_LD * 8;
-  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((km_seed_dots_kernel<2, KmSegCtx>)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>((km_seed_dots_kernel<4, KmSegCtx>)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_kernel<KmSegCtx>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const size_t u_count = (size_t)n_init * (k > 1 ? k - 1 : 1) * trials;
+int launch_kmeans_fit(const float* X, int64_t d, const int64_t* ptr, const std::vector<int64_t>& groups, int64_t k, int64_t n_init, int trials,
+                      const int64_t* first_h, const double* u_h, int max_iter, double tol, int64_t* out_labels, float* out_centres,
+                      int64_t* out_seeds, double* info_h, void* scratch, hipStream_t s, bool segmented) {
   for (size_t gi = 0; gi + 1 < groups.size(); ++gi) {
     const KmGroup gp = km_plan(ptr, groups[gi], groups[gi + 1]);
     const KmSegBufs b = km_seg_carve(static_cast<char*>(scratch), gp, d, k, n_init, trials);
-    const int64_t nseg = gp.nseg, nr = gp.nrows, G = nseg * n_init, S = G * k, R = n_init * trials;
-    KmWork* w_blk = b.work;
-    KmWork* w_tile = w_blk + gp.nblk;
-    KmWork* w_st32 = w_tile + gp.ntile;
-    KmWork* w_st64 = w_st32 + gp.nst32;
-    // (the host vectors copied below live until the first status read of the Lloyd loop has synchronised the stream)
-    const float* Xg = X + gp.row0 * d;
-    // the caller's random stream: first centres as group-local rows, the shared uniforms; the group's tables
-    std::vector<int64_t> first((size_t)G);
-    for (int64_t q = 0; q < nseg; ++q)
-      for (int64_t r = 0; r < n_init; ++r) first[q * n_init + r] = gp.segs[q].row0 + first_h[(gp.s0 + q) * n_init + r];
-    MMF_HIP(hipMemcpyAsync(b.first, first.data(), (size_t)G * 8, hipMemcpyHostToDevice, s));
-    if (k > 1) MMF_HIP(hipMemcpyAsync(b.U, u_h, u_count * 8, hipMemcpyHostToDevice, s));
-    MMF_HIP(hipMemcpyAsync(b.segs, gp.segs.data(), (size_t)nseg * sizeof(KmSeg), hipMemcpyHostToDevice, s));
-    MMF_HIP(hipMemcpyAsync(b.work, gp.work.data(), gp.work.size() * sizeof(KmWork), hipMemcpyHostToDevice, s));
-    MMF_HIP(hipMemsetAsync(b.amb, 0, (size_t)nseg * 8, s));
-    auto ctx = [&](const KmWork* w, int64_t tprev) { return KmSegCtx{b.segs, w, nseg, n_init, tprev}; };
-
-    // centring, tolerance, norms: per segment
-    const dim3 cgrid((unsigned)gp.nblk, (unsigned)((d + 63) / 64)), fgrid((unsigned)((d + 255) / 256), (unsigned)nseg);
-    hipLaunchKernelGGL(km_colsum_kernel<KmSegCtx>, cgrid, dim3(256), 0, s, Xg, nr, d, (const double*)nullptr, b.colpart, ctx(w_blk, 0));
-    MMF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_colfin_kernel<KmSegCtx>, fgrid, dim3(256), 0, s, b.colpart, gp.nblk, nr, d, b.mean64, (float*)nullptr, ctx(nullptr, 0));
-    MMF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_colmean_seq_kernel<KmSegCtx>, dim3((unsigned)((d + CM_COLS - 1) / CM_COLS), (unsigned)nseg), dim3(256), 0, s, Xg, nr, d,
-                       b.mean32, ctx(nullptr, 0));
-    MMF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_colsum_kernel<KmSegCtx>, cgrid, dim3(256), 0, s, Xg, nr, d, (const double*)b.mean64, b.colpart, ctx(w_blk, 0));
-    MMF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_colfin_kernel<KmSegCtx>, fgrid, dim3(256), 0, s, b.colpart, gp.nblk, nr, d, b.var64, (float*)nullptr, ctx(nullptr, 0));
-    MMF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_tol_kernel<KmSegCtx>, dim3((unsigned)nseg), dim3(1024), 0, s, b.var64, d, tol, b.tol_abs, ctx(nullptr, 0));
-    MMF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_centre_kernel<KmSegCtx>, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, s, Xg, nr, d, ds, b.mean32, b.Xc, b.xx,
-                       ctx(nullptr, 0));
-    MMF_LAUNCH_CHECK();
-
-    // k-means++: every restart of every segment in lockstep; per step one choice/draw launch and one distance launch per tile width
-    hipLaunchKernelGGL(km_seed_first_kernel, dim3((unsigned)((G + 63) / 64)), dim3(64), 0, s, b.first, G, k, b.seeds, b.cand[0]);
-    MMF_LAUNCH_CHECK();
-    auto dots = [&](const int64_t* cd, int64_t Rn, int64_t group, const float* prev, int64_t tprev, float* out, double* part) -> int {
-      const unsigned ry = (unsigned)((Rn + KM_T - 1) / KM_T);
-      if (gp.nst32) {
-        hipLaunchKernelGGL((km_seed_dots_kernel<2, KmSegCtx>), dim3((unsigned)gp.nst32, ry), dim3(256), lds, s, b.Xc, nr, ds, b.xx, cd, Rn, group, prev,
-                           b.sel, out, part, ctx(w_st32, tprev));
-        MMF_LAUNCH_CHECK();
-      }
-      if (gp.nst64) {
-        hipLaunchKernelGGL((km_seed_dots_kernel<4, KmSegCtx>), dim3((unsigned)gp.nst64, ry), dim3(256), lds, s, b.Xc, nr, ds, b.xx, cd, Rn, group, prev,
-                           b.sel, out, part, ctx(w_st64, tprev));
-        MMF_LAUNCH_CHECK();
-      }
-      return MMF_OK;
-    };
-    MMF_TRY(dots(b.cand[0], n_init, 1, nullptr, 1, b.rows[0], b.rpart[0]));
-    int cur = 0, tprev = 1;
-    for (int64_t step = 1; step <= k; ++step) {
-      const bool last = step == k;
-      hipLaunchKernelGGL(km_seed_step_kernel<KmSegCtx>, dim3((unsigned)G), dim3(256), 0, s, b.rows[cur], b.rpart[cur], (int64_t)0, 0, nr, tprev,
-                         b.cand[cur], k, step - 1, last ? (const double*)nullptr : b.U + (step - 1) * trials, (k - 1) * trials, trials, b.pot32,
-                         b.seeds, b.sel, b.cand[cur ^ 1], b.amb, ctx(nullptr, tprev));
-      MMF_LAUNCH_CHECK();
-      if (last) break;
-      MMF_TRY(dots(b.cand[cur ^ 1], R, trials, b.rows[cur], tprev, b.rows[cur ^ 1], b.rpart[cur ^ 1]));
-      cur ^= 1;
-      tprev = trials;
-    }
-    if (out_seeds) {
-      hipLaunchKernelGGL(km_seeds_out_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, b.seeds, S, gp.row0, out_seeds + gp.s0 * n_init * k);
-      MMF_LAUNCH_CHECK();
-    }
-
-    // Lloyd iterations: every restart of the group in lockstep, one status read per iteration
-    hipLaunchKernelGGL(km_gather_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, b.Xc, ds, b.seeds, S, b.C0);
-    MMF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_init_state_kernel, dim3((unsigned)((G + 63) / 64)), dim3(64), 0, s, b.st, (int)G);
-    MMF_LAUNCH_CHECK();
-    MMF_HIP(hipMemsetAsync(b.labels, 0xff, (size_t)n_init * nr * 8, s));
-    std::vector<int> h_status((size_t)G, KM_RUN);
-    int it = 0;
-    for (;; ++it) {
-      bool any_run = false, any_live = false;
-      for (int64_t g = 0; g < G; ++g) { any_run |= h_status[g] == KM_RUN; any_live |= h_status[g] != KM_DONE; }
-      if (!any_live) break;
-      hipLaunchKernelGGL(km_rownorm_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, b.C0, b.C1, b.st, k, S, ds, b.cc);
-      MMF_LAUNCH_CHECK();
-      hipLaunchKernelGGL(km_assign_kernel<KmSegCtx>, dim3((unsigned)gp.ntile, (unsigned)n_init), dim3(256), lds, s, b.Xc, nr, ds, b.C0, b.C1, b.cc, k,
-                         b.st, 0, b.labels, ctx(w_tile, 0));
-      MMF_LAUNCH_CHECK();
-      if (any_run) {
-        MMF_TRY(launch_segment_sort(b.labels, n_init * nr, S, b.counts, b.offsets, b.order, b.sort_scratch, b.bad, s));
-        hipLaunchKernelGGL(km_update_kernel<KmSegCtx>, dim3((unsigned)S, (unsigned)strips), dim3(256), 0, s, b.Xc, nr, ds, b.order, b.offsets, k, b.C0,
-                           b.C1, b.sums32, b.st, 0, b.shift_part, ctx(nullptr, 0));
-        MMF_LAUNCH_CHECK();
-      }
-      hipLaunchKernelGGL(km_state_kernel<KmSegCtx>, dim3((unsigned)G), dim3(64), 0, s, b.st, (int)n_init, k, strips, b.shift_part, b.tol_abs, it,
-                         max_iter, -1, b.status, ctx(nullptr, 0));
-      MMF_LAUNCH_CHECK();
-      MMF_HIP(hipMemcpyAsync(h_status.data(), b.status, (size_t)G * 4, hipMemcpyDeviceToHost, s));
-      MMF_HIP(hipStreamSynchronize(s));
-      for (int64_t g = 0; g < G; ++g) {
-        if (h_status[g] != KM_RELOC) continue;
-        hipLaunchKernelGGL(km_relocate_kernel<KmSegCtx>, dim3(1), dim3(1024), 0, s, b.Xc, nr, ds, k, (int)g, b.labels, b.offsets, b.C0, b.C1, b.sums32,
-                           b.st, b.dist, b.cntf, b.shift_part, strips, ctx(nullptr, 0));
-        MMF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(km_state_kernel<KmSegCtx>, dim3((unsigned)G), dim3(64), 0, s, b.st, (int)n_init, k, strips, b.shift_part, b.tol_abs, it,
-                           max_iter, (int)g, b.status, ctx(nullptr, 0));
-        MMF_LAUNCH_CHECK();
-        MMF_HIP(hipMemcpyAsync(h_status.data(), b.status, (size_t)G * 4, hipMemcpyDeviceToHost, s));
-        MMF_HIP(hipStreamSynchronize(s));
-      }
-      if (it > max_iter + 2) { set_error("kmeans_fit_segmented: the convergence state machine did not terminate (internal invariant)"); return MMF_E_INTERNAL; }
-    }
-
-    hipLaunchKernelGGL(km_inertia_kernel<KmSegCtx>, dim3((unsigned)gp.ntile, (unsigned)n_init), dim3(256), 0, s, b.Xc, nr, ds, b.C0, b.C1, b.st,
-                       b.labels, b.ipart, ctx(w_tile, 0));
-    MMF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_pick_kernel<KmSegCtx>, dim3((unsigned)nseg), dim3(1024), 0, s, b.st, (int)n_init, nr, k, b.ipart, gp.ntile, b.labels, b.map,
-                       b.best, ctx(nullptr, 0));
-    MMF_LAUNCH_CHECK();
-    const int64_t fin = gp.max_n > k * d ? gp.max_n : k * d;
-    hipLaunchKernelGGL(km_finish_kernel<KmSegCtx>, dim3((unsigned)((fin + 255) / 256), (unsigned)nseg), dim3(256), 0, s, b.st, b.best, nr, k, d, ds,
-                       b.labels, b.C0, b.C1, b.mean32, out_labels + gp.row0, out_centres ? out_centres + gp.s0 * k * d : nullptr, ctx(nullptr, 0));
-    MMF_LAUNCH_CHECK();
-    if (info_h) {
-      // per segment as the plain fit's info; [6] is the group's lockstep iteration count
-      std::vector<KmState> hs((size_t)G);
-      std::vector<int> h_best((size_t)nseg);
-      std::vector<unsigned int> h_amb((size_t)nseg * 2);
-      std::vector<double> h_tol((size_t)nseg);
-      MMF_HIP(hipMemcpyAsync(hs.data(), b.st, (size_t)G * sizeof(KmState), hipMemcpyDeviceToHost, s));
-      MMF_HIP(hipMemcpyAsync(h_best.data(), b.best, (size_t)nseg * 4, hipMemcpyDeviceToHost, s));
-      MMF_HIP(hipMemcpyAsync(h_amb.data(), b.amb, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
-      MMF_HIP(hipMemcpyAsync(h_tol.data(), b.tol_abs, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
-      MMF_HIP(hipStreamSynchronize(s));
-      for (int64_t q = 0; q < nseg; ++q) {
-        double* o = info_h + (gp.s0 + q) * (7 + 2 * n_init);
-        const KmState* sq = hs.data() + q * n_init;
-        const int bq = h_best[q];
-        o[0] = (double)bq; o[1] = sq[bq].inertia; o[2] = (double)sq[bq].n_iter; o[3] = h_tol[q];
-        o[4] = (double)h_amb[2 * q]; o[5] = (double)h_amb[2 * q + 1]; o[6] = (double)it;
-        for (int64_t r = 0; r < n_init; ++r) { o[7 + 2 * r] = sq[r].inertia; o[8 + 2 * r] = (double)sq[r].n_iter; }
-      }
-    }
+    if (!segmented)
+      MMF_TRY(km_fit_group(X, d, gp, b, k, n_init, trials, first_h, u_h, max_iter, tol, out_labels, out_centres, out_seeds, info_h, s));
+    else
+      MMF_TRY(km_fit_group(X, d, gp, b, k, n_init, trials, first_h, u_h, max_iter, tol, out_labels, out_centres, out_seeds, info_h, s,
+                           KmSegCtx{b.segs, nullptr, gp.nseg, n_init, 0}));
   }
   return MMF_OK;
 }

@@ -39,22 +39,10 @@ def _uniform_cdf(n_samples: int) -> np.ndarray:
 
 def sklearn_stream(seed: int, n_init: int, n_clusters: int, n_samples: int) -> Tuple[np.ndarray, np.ndarray]:
     """scikit-learn's draws for KMeans(n_clusters, random_state=seed, n_init=n_init) on n_samples points:
-    (first centre of every restart, int64 [n_init]; uniforms float64 [n_init, n_clusters - 1, trials]).
-
-    The first centre is ``RandomState.choice(n, p=ones(n, float32) / float32(n))``: one ``random_sample()`` looked up
-    (side='right') in the normalised float64 cumulative sum of p (numpy/random/mtrand.pyx)."""
-    trials = 2 + int(math.log(n_clusters))
-    rs = np.random.RandomState(seed)
-    cdf = _uniform_cdf(n_samples)
-    # per restart the stream gives one double for the first centre, then `trials` doubles per seeding step (uniform(size=trials) is
-    # 0.0 + 1.0 * the next doubles, bit for bit): ONE random_sample call yields the same doubles as scikit-learn's n_init * k calls
-    # (oracle/kmeans_restate.py keeps the call-by-call form; the GPU tests compare the seeds of both)
-    steps = max(n_clusters - 1, 0)
-    r = rs.random_sample(n_init * (1 + steps * trials)).reshape(n_init, 1 + steps * trials)
-    first = cdf.searchsorted(r[:, 0], side="right").astype(np.int64)
-    u = np.ascontiguousarray(r[:, 1:]).reshape(n_init, steps, trials)
-    np.clip(first, 0, n_samples - 1, out=first)
-    return first, u
+    (first centre of every restart, int64 [n_init]; uniforms float64 [n_init, n_clusters - 1, trials]), segment_streams for
+    one segment."""
+    first, u = segment_streams(seed, n_init, n_clusters, [n_samples])
+    return first[0], u
 
 
 def kmeans_fit_predict(X: torch.Tensor, n_clusters: int, *, n_init: int = 10, max_iter: int = 300,
@@ -102,9 +90,15 @@ def kmeans_fit_predict_segmented(X: torch.Tensor, n_clusters: int, *, ptr=None, 
 def segment_streams(seed: int, n_init: int, n_clusters: int, sizes) -> Tuple[np.ndarray, np.ndarray]:
     """scikit-learn's draws for every segment: (first centres int64 [n_seg, n_init], row ids local to each segment;
     uniforms float64 [n_init, n_clusters - 1, trials], the same for every segment).  Only the first centre depends on the
-    number of rows (through the uniform cdf), so the stream is drawn once."""
+    number of rows (through the uniform cdf), so the stream is drawn once.
+
+    The first centre is ``RandomState.choice(n, p=ones(n, float32) / float32(n))``: one ``random_sample()`` looked up
+    (side='right') in the normalised float64 cumulative sum of p (numpy/random/mtrand.pyx)."""
     rs = np.random.RandomState(seed)
     trials = 2 + int(math.log(n_clusters))
+    # per restart the stream gives one double for the first centre, then `trials` doubles per seeding step (uniform(size=trials) is
+    # 0.0 + 1.0 * the next doubles, bit for bit): ONE random_sample call yields the same doubles as scikit-learn's n_init * k calls
+    # (oracle/kmeans_restate.py keeps the call-by-call form; the GPU tests compare the seeds of both)
     steps = max(n_clusters - 1, 0)
     r = rs.random_sample(n_init * (1 + steps * trials)).reshape(n_init, 1 + steps * trials)
     u = np.ascontiguousarray(r[:, 1:]).reshape(n_init, steps, trials)

@@ -535,13 +535,8 @@ def kmeans_fit(X: torch.Tensor, n_clusters: int, first_centres, uniforms, *, max
     X = _feat(X, "kmeans_fit X").float()
     _need_gpu(X, "kmeans_fit")
     n, d = X.shape
-    first = np.ascontiguousarray(first_centres, dtype=np.int64)
-    n_init = int(first.shape[0])
     k = int(n_clusters)
-    u = np.ascontiguousarray(uniforms, dtype=np.float64)
-    if k > 1 and (u.ndim != 3 or u.shape[0] != n_init or u.shape[1] != k - 1):
-        raise ValueError("kmeans_fit: uniforms must be [n_init, n_clusters - 1, trials]")
-    trials = int(u.shape[2]) if k > 1 else 1
+    first, u, n_init, trials = _kmeans_stream("kmeans_fit", k, first_centres, uniforms)
     labels = torch.empty(n, dtype=torch.int64, device=X.device)
     centres = torch.empty((k, d), dtype=torch.float32, device=X.device)
     seeds = torch.empty((n_init, k), dtype=torch.int64, device=X.device) if return_seeds else None
@@ -555,6 +550,21 @@ def kmeans_fit(X: torch.Tensor, n_clusters: int, first_centres, uniforms, *, max
     if return_seeds:
         return labels, centres, out_info, seeds
     return labels, centres, out_info
+
+
+def _kmeans_stream(what: str, k: int, first_centres, uniforms, n_seg=None):
+    """The random stream as the C entries take it: (first int64, uniforms float64, both C-contiguous host arrays, n_init, trials).
+    first_centres is [n_init], or [n_seg, n_init] when n_seg is given."""
+    import numpy as np
+    first = np.ascontiguousarray(first_centres, dtype=np.int64)
+    if n_seg is not None and (first.ndim != 2 or first.shape[0] != n_seg):
+        raise ValueError(f"{what}: first_centres must be [n_seg, n_init]")
+    n_init = int(first.shape[0 if n_seg is None else 1])
+    u = np.ascontiguousarray(uniforms, dtype=np.float64)
+    if k > 1 and (u.ndim != 3 or u.shape[0] != n_init or u.shape[1] != k - 1):
+        raise ValueError(f"{what}: uniforms must be [n_init, n_clusters - 1, trials]")
+    trials = int(u.shape[2]) if k > 1 else 1
+    return first, u, n_init, trials
 
 
 def _kmeans_info(info) -> dict:
@@ -577,14 +587,7 @@ def kmeans_fit_segmented(X: torch.Tensor, ptr, n_clusters: int, first_centres, u
     p = np.ascontiguousarray(torch.as_tensor(ptr).detach().cpu().numpy(), dtype=np.int64).reshape(-1)
     n_seg = int(p.shape[0]) - 1
     k = int(n_clusters)
-    first = np.ascontiguousarray(first_centres, dtype=np.int64)
-    if first.ndim != 2 or first.shape[0] != n_seg:
-        raise ValueError("kmeans_fit_segmented: first_centres must be [n_seg, n_init]")
-    n_init = int(first.shape[1])
-    u = np.ascontiguousarray(uniforms, dtype=np.float64)
-    if k > 1 and (u.ndim != 3 or u.shape[0] != n_init or u.shape[1] != k - 1):
-        raise ValueError("kmeans_fit_segmented: uniforms must be [n_init, n_clusters - 1, trials]")
-    trials = int(u.shape[2]) if k > 1 else 1
+    first, u, n_init, trials = _kmeans_stream("kmeans_fit_segmented", k, first_centres, uniforms, n_seg)
     _need_gpu(X, "kmeans_fit_segmented")
     labels = torch.empty(n, dtype=torch.int64, device=X.device)
     centres = torch.empty((max(n_seg, 0), k, d), dtype=torch.float32, device=X.device)
