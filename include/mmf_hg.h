@@ -368,6 +368,33 @@ int mmf_combined_threshold_edges(const float* F, const float* P, int64_t n, int6
                                  int device_id, void* hip_stream);
 
 /*
+ * The weighted hypergraph of every graph of a ragged batch: segment s is rows ptr[s] .. ptr[s+1]-1 of F / P
+ * (ptr_host: HOST int64 offsets [n_seg + 1], 0 .. n, non-decreasing), n_s = ptr[s+1] - ptr[s].  Its block K_s ([n_s, n_s] f32,
+ * row-major) sits at kptr[s] = sum_{t<s} n_t^2 of one flat buffer.  Each entry returns, segment by segment, the bits of its
+ * plain counterpart on the segment's slice; offsets and sizes are checked on the host before any device work
+ * (MMF_E_INVALID names the segment), device_id < 0 -> MMF_E_UNSUPPORTED, n < 2^31.
+ *   mmf_sim_dense_combined_segmented:   out [sum n_s^2] = the blocks mmf_sim_dense_combined(F_s, P_s) — compute_combined_similarity
+ *                                       per slide, build_hypergraph/similarity_kernel.py:88-124, 171.  One scan launch.
+ *   mmf_offdiag_lower_median_segmented: out_median (device f32 [n_seg]) = mmf_offdiag_lower_median of every block K (the
+ *                                       layout above) — similarity_kernel.py:183-186 per slide.  Every n_s >= 2.  Four-pass
+ *                                       radix select: a fixed number of launches for any n_seg, no host synchronisation.
+ *   mmf_threshold_edges_segmented_count / _fill: mmf_threshold_edges_count / _fill of every block against its own threshold
+ *                                       (thresholds: device f32 [n_seg]) — similarity_kernel.py:193-202 per slide.  Edges carry
+ *                                       global row ids (ptr[s] + i, ptr[s] + j), segment-major, row-major within a segment;
+ *                                       row_offsets (device uint64 [n + 1]) are the exclusive offsets of the n rows, so the
+ *                                       edges of segment s start at row_offsets[ptr[s]]; row_offsets[n] = *out_count.
+ */
+int mmf_sim_dense_combined_segmented(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, const int64_t* ptr_host,
+                                     int64_t n_seg, float lambda_h, float lambda_g, float* out, int device_id, void* hip_stream);
+int mmf_offdiag_lower_median_segmented(const float* K, const int64_t* ptr_host, int64_t n_seg, float* out_median, int device_id,
+                                       void* hip_stream);
+int mmf_threshold_edges_segmented_count(const float* K, const int64_t* ptr_host, int64_t n_seg, const float* thresholds,
+                                        uint64_t* row_offsets, int64_t* out_count, int device_id, void* hip_stream);
+int mmf_threshold_edges_segmented_fill(const float* K, const int64_t* ptr_host, int64_t n_seg, const float* thresholds,
+                                       const uint64_t* row_offsets, int64_t* edge_index, float* edge_w, int64_t capacity,
+                                       int device_id, void* hip_stream);
+
+/*
  * Cluster-shaped steps around the similarity kernels: what the reference does with a vector
  * of KMeans labels in Python loops.  labels / order / offsets / counts / pairs are int64 device arrays (torch.long);
  * at most 16384 segments.

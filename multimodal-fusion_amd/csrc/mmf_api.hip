@@ -1548,4 +1548,125 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
 }
 
 
+// ---- segmented weighted hypergraph (the blocks K_s of a ragged batch) -------------------------------------------
+// DESIGN.md §4.9.  Segment s is rows ptr[s] .. ptr[s+1]-1 (host int64 offsets); its block K_s (n_s x n_s, row-major) sits at
+// kptr[s] = sum_{t<s} n_t^2 of one flat f32 buffer.  Every argument is checked here, before any device work.
+static int check_blocks(const char* what, const int64_t* ptr, int64_t n_seg, int64_t min_rows, int device_id, int64_t* n_out) {
+  if (device_id < 0) { set_error("%s: no CPU path", what); return MMF_E_UNSUPPORTED; }
+  if (n_seg < 1 || !ptr) { set_error("%s: need n_seg >= 1 and host offsets ptr[n_seg + 1]", what); return MMF_E_INVALID; }
+  if (ptr[0] != 0) { set_error("%s: ptr must start at 0 (got %lld)", what, (long long)ptr[0]); return MMF_E_INVALID; }
+  for (int64_t g = 0; g < n_seg; ++g) {
+    const int64_t ns = ptr[g + 1] - ptr[g];
+    if (ns < 0) { set_error("%s: ptr decreases at segment %lld", what, (long long)g); return MMF_E_INVALID; }
+    if (ns < min_rows) {
+      set_error("%s: segment %lld has %lld rows, need at least %lld", what, (long long)g, (long long)ns, (long long)min_rows);
+      return MMF_E_INVALID;
+    }
+  }
+  // n < 2^31 keeps sum n_s^2 <= n^2 below 2^62: every block offset fits int64
+  if (ptr[n_seg] >= ((int64_t)1 << 31)) { set_error("%s: %lld rows, must be < 2^31", what, (long long)ptr[n_seg]); return MMF_E_UNSUPPORTED; }
+  *n_out = ptr[n_seg];
+  return MMF_OK;
+}
+
+static std::vector<int64_t> block_offsets(const int64_t* ptr, int64_t n_seg) {
+  std::vector<int64_t> kptr((size_t)n_seg + 1, 0);
+  for (int64_t g = 0; g < n_seg; ++g) kptr[g + 1] = kptr[g] + (ptr[g + 1] - ptr[g]) * (ptr[g + 1] - ptr[g]);
+  return kptr;
+}
+
+// compute_combined_similarity of every segment (build_hypergraph/similarity_kernel.py:88-124; :171 inside
+// build_weighted_hypergraph, and the K_wsi of every slide, preprocess_hypergraph.py:136-138): row scalars and the f32 image of all n rows, then ONE scan launch over a host-built work
+// table (mmf_scan_f32.hip, SEG).  Block s is bit for bit mmf_sim_dense_combined(F_s, P_s).
+int mmf_sim_dense_combined_segmented(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, const int64_t* ptr_host,
+                                     int64_t n_seg, float lambda_h, float lambda_g, float* out, int device_id, void* hip_stream) {
+  MMF_TRY(check_common(F, n, n, d, MMF_F32, device_id));
+  if (dp < 1) { set_error("sim_dense_combined_segmented: dp < 1"); return MMF_E_INVALID; }
+  int64_t rows = 0;
+  MMF_TRY(check_blocks("sim_dense_combined_segmented", ptr_host, n_seg, 0, device_id, &rows));
+  if (rows != n) { set_error("sim_dense_combined_segmented: ptr must end at n = %lld (got %lld)", (long long)n, (long long)rows); return MMF_E_INVALID; }
+  if (n == 0) return MMF_OK;
+  if (!P || !out) { set_error("sim_dense_combined_segmented: NULL pointer"); return MMF_E_INVALID; }
+  const std::vector<int64_t> tab = sim_dense_combined_seg_table(ptr_host, n_seg);
+  const int64_t grid = (int64_t)tab.size() / 8;
+  if (grid >= ((int64_t)1 << 31)) { set_error("sim_dense_combined_segmented: %lld workgroups", (long long)grid); return MMF_E_UNSUPPORTED; }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, ws_bytes(n, 4) + ws_bytes(prep_f32_bytes(n, d), 1) + ws_bytes(tab.size(), 8), &ws));
+  float* nf = ws.take<float>(n);
+  float* Fp = reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(n, d)));
+  int64_t* d_tab = ws.take<int64_t>(tab.size());
+  MMF_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+  MMF_TRY(launch_row_scalars(F, n, d, MMF_F32, MMF_RBF, nf, nullptr, s));
+  MMF_TRY(launch_prep_f32(F, n, d, MMF_F32, nullptr, Fp, s));
+  return launch_sim_dense_combined_seg(Fp, P, d, dp, lambda_h, lambda_g, nf, d_tab, grid, out, s);
+}
+
+// The off-diagonal lower median of every block: K[~eye] + torch.median per slide, build_hypergraph/similarity_kernel.py:183-186.
+// The four-pass radix select of mmf_offdiag_lower_median with a select state per segment (mmf_edges.hip): a fixed number of
+// launches for any n_seg, no host synchronisation.
+int mmf_offdiag_lower_median_segmented(const float* K, const int64_t* ptr_host, int64_t n_seg, float* out_median, int device_id,
+                                       void* hip_stream) {
+  int64_t n = 0;
+  MMF_TRY(check_blocks("offdiag_lower_median_segmented", ptr_host, n_seg, 2, device_id, &n));
+  if (!K || !out_median) { set_error("offdiag_lower_median_segmented: NULL pointer"); return MMF_E_INVALID; }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  const size_t need = offdiag_lower_median_seg_scratch_bytes(ptr_host, n_seg);
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
+  return launch_offdiag_lower_median_seg(K, ptr_host, n_seg, out_median, ws.take<char>(need), s);
+}
+
+// The threshold edges of every block against its own threshold (thresholds: device f32 [n_seg]): the per-slide double loop
+// of build_hypergraph/similarity_kernel.py:193-202, in the two calls of mmf_threshold_edges_count / _fill.  Edges are global
+// row ids (ptr[s] + i, ptr[s] + j), segment-major and row-major inside a segment; segment s's start at row_offsets[ptr[s]].
+int mmf_threshold_edges_segmented_count(const float* K, const int64_t* ptr_host, int64_t n_seg, const float* thresholds,
+                                        uint64_t* row_offsets, int64_t* out_count, int device_id, void* hip_stream) {
+  int64_t n = 0;
+  MMF_TRY(check_blocks("threshold_edges_segmented_count", ptr_host, n_seg, 0, device_id, &n));
+  if (!out_count || !row_offsets || (n > 0 && (!K || !thresholds))) { set_error("threshold_edges_segmented_count: NULL pointer"); return MMF_E_INVALID; }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  MMF_HIP(hipMemsetAsync(out_count, 0, 8, s));
+  if (n == 0) { MMF_HIP(hipMemsetAsync(row_offsets, 0, 8, s)); return MMF_OK; }
+  const std::vector<int64_t> kptr = block_offsets(ptr_host, n_seg);
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, 2 * ws_bytes((size_t)n_seg + 1, 8) + ws_bytes((size_t)n, 4), &ws));
+  int64_t* d_ptr = ws.take<int64_t>((size_t)n_seg + 1);
+  int64_t* d_kptr = ws.take<int64_t>((size_t)n_seg + 1);
+  uint32_t* row_cnt = ws.take<uint32_t>((size_t)n);
+  MMF_HIP(hipMemcpyAsync(d_ptr, ptr_host, (size_t)(n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+  MMF_HIP(hipMemcpyAsync(d_kptr, kptr.data(), (size_t)(n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+  return launch_threshold_count_seg(K, d_ptr, d_kptr, n_seg, n, thresholds, reinterpret_cast<unsigned long long*>(row_offsets), out_count,
+                                    row_cnt, s);
+}
+
+int mmf_threshold_edges_segmented_fill(const float* K, const int64_t* ptr_host, int64_t n_seg, const float* thresholds,
+                                       const uint64_t* row_offsets, int64_t* edge_index, float* edge_w, int64_t capacity, int device_id,
+                                       void* hip_stream) {
+  int64_t n = 0;
+  MMF_TRY(check_blocks("threshold_edges_segmented_fill", ptr_host, n_seg, 0, device_id, &n));
+  if (capacity < 0) { set_error("threshold_edges_segmented_fill: bad capacity"); return MMF_E_INVALID; }
+  if (n == 0 || capacity == 0) return MMF_OK;
+  if (!K || !thresholds || !row_offsets || !edge_index || !edge_w) { set_error("threshold_edges_segmented_fill: NULL pointer"); return MMF_E_INVALID; }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  const std::vector<int64_t> kptr = block_offsets(ptr_host, n_seg);
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, 2 * ws_bytes((size_t)n_seg + 1, 8), &ws));
+  int64_t* d_ptr = ws.take<int64_t>((size_t)n_seg + 1);
+  int64_t* d_kptr = ws.take<int64_t>((size_t)n_seg + 1);
+  MMF_HIP(hipMemcpyAsync(d_ptr, ptr_host, (size_t)(n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+  MMF_HIP(hipMemcpyAsync(d_kptr, kptr.data(), (size_t)(n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+  return launch_threshold_fill_seg(K, d_ptr, d_kptr, n_seg, n, thresholds, reinterpret_cast<const unsigned long long*>(row_offsets),
+                                   edge_index, edge_w, capacity, s);
+}
+
+
 }  // extern "C"

@@ -640,15 +640,11 @@ size_t stat_partial_bytes() { return sizeof(StatPartial); }
 // ------------------------------------------------------------------------------------------------
 // threshold edges
 // ------------------------------------------------------------------------------------------------
-// K: `rows` rows of n entries each (a panel of the square matrix, or all of it)
-__global__ __launch_bounds__(256) void thr_count_kernel(const float* __restrict__ K, int64_t n, int64_t rows, float thr,
-                                                        uint32_t* __restrict__ row_cnt) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* kr = K + row * n;
+// One wave counts the entries of row kr[0 .. n) that are not below thr (every lane returns the row's count).
+// vec: n % 4 == 0 and kr 16-byte aligned.
+__device__ __forceinline__ uint32_t thr_count_row(const float* __restrict__ kr, int64_t n, float thr, bool vec, int lane) {
   uint32_t c = 0;
-  if (((n & 3) == 0) && ((reinterpret_cast<uintptr_t>(K) & 15) == 0)) {       // 16 bytes per lane, 1 KiB per wave instruction
+  if (vec) {                                                                    // 16 bytes per lane, 1 KiB per wave instruction
     for (int64_t j = (int64_t)lane * 4; j < n; j += 256) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(kr + j);
       c += (v[0] < thr ? 0u : 1u) + (v[1] < thr ? 0u : 1u) + (v[2] < thr ? 0u : 1u) + (v[3] < thr ? 0u : 1u);   // skipped iff K < thr (:198)
@@ -658,6 +654,16 @@ __global__ __launch_bounds__(256) void thr_count_kernel(const float* __restrict_
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor((int)c, o);
+  return c;
+}
+
+// K: `rows` rows of n entries each (a panel of the square matrix, or all of it)
+__global__ __launch_bounds__(256) void thr_count_kernel(const float* __restrict__ K, int64_t n, int64_t rows, float thr,
+                                                        uint32_t* __restrict__ row_cnt) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const uint32_t c = thr_count_row(K + row * n, n, thr, ((n & 3) == 0) && ((reinterpret_cast<uintptr_t>(K) & 15) == 0), lane);
   if (lane == 0) row_cnt[row] = c;
 }
 
@@ -689,15 +695,10 @@ __global__ __launch_bounds__(1024) void thr_scan_kernel(const uint32_t* __restri
   if (t == 1023) { *out_count = (int64_t)(base + part[1023]); row_off[n] = base + part[1023]; }
 }
 
-__global__ __launch_bounds__(256) void thr_fill_kernel(const float* __restrict__ K, int64_t n, int64_t row0, int64_t rows,
-                                                       float thr, const unsigned long long* __restrict__ row_off,
-                                                       int64_t* __restrict__ ei_row, int64_t* __restrict__ ei_col,
-                                                       float* __restrict__ ew, int64_t capacity) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* kr = K + row * n;
-  unsigned long long pos = row_off[row];
+// One wave writes the kept entries of row kr[0 .. n) from edge position pos on: (id_row, col0 + j, kr[j]), j ascending.
+__device__ __forceinline__ void thr_fill_row(const float* __restrict__ kr, int64_t n, float thr, unsigned long long pos, int64_t id_row,
+                                             int64_t col0, int64_t* __restrict__ ei_row, int64_t* __restrict__ ei_col,
+                                             float* __restrict__ ew, int64_t capacity, int lane) {
   // Four 64-column groups per trip: the four loads are in flight together, and every store instruction writes the
   // kept entries of one group to CONSECUTIVE positions (a lane-owns-4-columns layout would make the stores strided).
   int64_t j0 = 0;
@@ -711,7 +712,7 @@ __global__ __launch_bounds__(256) void thr_fill_kernel(const float* __restrict__
       const unsigned long long mask = __ballot(keep);
       if (keep) {
         const unsigned long long p = pos + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
-        if ((int64_t)p < capacity) { ei_row[p] = row0 + row; ei_col[p] = j0 + 64 * u + lane; ew[p] = v[u]; }
+        if ((int64_t)p < capacity) { ei_row[p] = id_row; ei_col[p] = col0 + j0 + 64 * u + lane; ew[p] = v[u]; }
       }
       pos += (unsigned long long)__popcll(mask);
     }
@@ -723,10 +724,20 @@ __global__ __launch_bounds__(256) void thr_fill_kernel(const float* __restrict__
     const unsigned long long mask = __ballot(keep);
     if (keep) {
       const unsigned long long p = pos + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
-      if ((int64_t)p < capacity) { ei_row[p] = row0 + row; ei_col[p] = j; ew[p] = v; }
+      if ((int64_t)p < capacity) { ei_row[p] = id_row; ei_col[p] = col0 + j; ew[p] = v; }
     }
     pos += (unsigned long long)__popcll(mask);
   }
+}
+
+__global__ __launch_bounds__(256) void thr_fill_kernel(const float* __restrict__ K, int64_t n, int64_t row0, int64_t rows,
+                                                       float thr, const unsigned long long* __restrict__ row_off,
+                                                       int64_t* __restrict__ ei_row, int64_t* __restrict__ ei_col,
+                                                       float* __restrict__ ew, int64_t capacity) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  thr_fill_row(K + row * n, n, thr, row_off[row], row0 + row, 0, ei_row, ei_col, ew, capacity, lane);
 }
 
 // K: rows [row0, row0 + rows) of the n x n matrix.  Edges are written to (ei_row, ei_col, ew)[0 .. count), row-major.
@@ -769,6 +780,220 @@ int launch_threshold_fill(const float* K, int64_t n, float thr, const unsigned l
                           int64_t capacity, hipStream_t s) {
   const unsigned grid = (unsigned)((n + 3) / 4);
   hipLaunchKernelGGL(thr_fill_kernel, dim3(grid), dim3(256), 0, s, K, n, (int64_t)0, n, thr, row_off, ei, ei + capacity, ew, capacity);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// segmented: the diagonal blocks K_s (n_s x n_s, row-major) of a ragged batch, stored one after the other from
+// kptr[s] = sum_{t<s} n_t^2 (mmf_offdiag_lower_median_segmented, mmf_threshold_edges_segmented_*)
+// ------------------------------------------------------------------------------------------------
+// The lower median of every block's off-diagonal entries: the four-pass radix select above, one select state per segment.
+// A segment's histogram lives in as many copies as the segment has histogram workgroups, at most kHistCopies (a small
+// segment is one workgroup and one copy: the copies are what the pick reads and clears, S times over).
+struct SegMedianHead {
+  unsigned long long prefix, rank;   // as in MedianState
+  unsigned long long hoff, copies;   // its copies: hist[hoff + 256 c + bin], c < copies
+};
+// work table of the histogram passes, one entry per workgroup: segment, first row, rows, histogram copy
+enum { SMED_SEG = 0, SMED_ROW0 = 1, SMED_ROWS = 2, SMED_COPY = 3, SMED_ENTRY = 4 };
+constexpr int64_t kSegMedianChunk = 65536;     // entries of a block per histogram workgroup (whole rows, at least one)
+
+struct SegMedianPlan {
+  std::vector<int64_t> tab;                    // [entries][SMED_ENTRY]
+  std::vector<SegMedianHead> heads;            // [S]
+  std::vector<int64_t> kptr;                   // [S + 1]
+  size_t hist_words = 0;
+  SegMedianPlan(const int64_t* ptr, int64_t S) : heads((size_t)S), kptr((size_t)S + 1) {
+    kptr[0] = 0;
+    for (int64_t s = 0; s < S; ++s) {
+      const int64_t ns = ptr[s + 1] - ptr[s];
+      kptr[s + 1] = kptr[s] + ns * ns;
+      int64_t rpe = kSegMedianChunk / ns;
+      if (rpe < 1) rpe = 1;
+      int64_t e = 0;
+      for (int64_t r0 = 0; r0 < ns; r0 += rpe, ++e) {
+        const int64_t ent[SMED_ENTRY] = {s, r0, ns - r0 < rpe ? ns - r0 : rpe, e % kHistCopies};
+        tab.insert(tab.end(), ent, ent + SMED_ENTRY);
+      }
+      const unsigned long long cnt = (unsigned long long)ns * (unsigned long long)(ns - 1);
+      heads[s] = SegMedianHead{0ull, (cnt - 1ull) / 2ull, hist_words, (unsigned long long)(e < kHistCopies ? e : kHistCopies)};
+      hist_words += 256 * heads[s].copies;
+    }
+  }
+  int64_t entries() const { return (int64_t)tab.size() / SMED_ENTRY; }
+  size_t bytes(int64_t S) const {
+    return ws_bytes((size_t)S, sizeof(SegMedianHead)) + 2 * ws_bytes((size_t)S + 1, 8) + ws_bytes(tab.size(), 8) + ws_bytes(hist_words, 8);
+  }
+};
+
+// One radix pass over the entries of ONE block (the workgroup's table entry: rows [r0, r0 + rows) of K_s) whose higher bytes
+// equal the segment's prefix; the diagonal is skipped.  The rows are walked flat, one entry per thread and step, so short rows
+// keep every lane busy: (i, j) of the thread's entry advance by 256 entries per step without a division.
+__global__ __launch_bounds__(256) void seg_median_hist_kernel(const float* __restrict__ K, const int64_t* __restrict__ ptr,
+                                                              const int64_t* __restrict__ kptr, const int64_t* __restrict__ tab,
+                                                              SegMedianHead* __restrict__ head, unsigned long long* __restrict__ hist,
+                                                              int shift) {
+  __shared__ unsigned int lh[256];
+  lh[threadIdx.x] = 0u;
+  __syncthreads();
+  const int64_t* e = tab + (size_t)blockIdx.x * SMED_ENTRY;
+  const int64_t sg = e[SMED_SEG], r0 = e[SMED_ROW0], rows = e[SMED_ROWS];
+  const int64_t ns = ptr[sg + 1] - ptr[sg];
+  const float* B = K + kptr[sg];
+  const uint32_t prefix = (uint32_t)head[sg].prefix;
+  const uint32_t himask = (shift == 24) ? 0u : (0xffffffffu << (shift + 8));
+  const uint32_t want = prefix & himask;
+  uint32_t cur = 0xffffffffu, run = 0;
+  auto feed = [&](float v) {
+    const uint32_t o = f2ord(v);
+    if ((o & himask) != want) return;
+    const uint32_t bin = (o >> shift) & 255u;
+    if (bin == cur) { ++run; return; }
+    if (run) atomicAdd(&lh[cur], run);
+    cur = bin; run = 1;
+  };
+  const int64_t f1 = (r0 + rows) * ns;
+  int64_t f = r0 * ns + threadIdx.x;
+  int64_t i = f / ns, j = f - i * ns;
+  const int64_t qs = 256 / ns, rs = 256 - qs * ns;
+  auto step = [&]() {
+    j += rs; i += qs;
+    if (j >= ns) { j -= ns; ++i; }
+  };
+  for (; f + 768 < f1; f += 1024) {                  // four loads in flight
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = B[f + 256 * u];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (i != j) feed(v[u]);
+      step();
+    }
+  }
+  for (; f < f1; f += 256) {
+    if (i != j) feed(B[f]);
+    step();
+  }
+  if (run) atomicAdd(&lh[cur], run);
+  __syncthreads();
+  if (lh[threadIdx.x]) atomicAdd(&hist[head[sg].hoff + 256 * e[SMED_COPY] + threadIdx.x], (unsigned long long)lh[threadIdx.x]);
+}
+
+// median_pick_kernel for segment blockIdx.x: sums (and clears) its copies, picks the bin of its rank
+__global__ __launch_bounds__(256) void seg_median_pick_kernel(SegMedianHead* __restrict__ head, unsigned long long* __restrict__ hist,
+                                                              int shift, float* __restrict__ out) {
+  __shared__ unsigned long long cum[256];
+  SegMedianHead* st = head + blockIdx.x;
+  const int t = threadIdx.x;
+  unsigned long long* h = hist + st->hoff;
+  const int copies = (int)st->copies;
+  unsigned long long mine = 0ull;
+  for (int c = 0; c < copies; ++c) { mine += h[256 * c + t]; h[256 * c + t] = 0ull; }
+  cum[t] = mine;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const unsigned long long v = (t >= o) ? cum[t - o] : 0ull;
+    __syncthreads();
+    cum[t] += v;
+    __syncthreads();
+  }
+  const unsigned long long r = st->rank;
+  const unsigned long long before = cum[t] - mine;
+  const bool here = (r >= before && r < cum[t]) || (t == 255 && r >= cum[255]);
+  __syncthreads();
+  if (here) {
+    st->rank = r - before;
+    st->prefix = st->prefix | ((unsigned long long)t << shift);
+    if (shift == 0) out[blockIdx.x] = ord2f((uint32_t)st->prefix);
+  }
+}
+
+size_t offdiag_lower_median_seg_scratch_bytes(const int64_t* ptr, int64_t S) { return SegMedianPlan(ptr, S).bytes(S); }
+
+// out[s] (device f32 [S]): the lower median of the n_s (n_s - 1) off-diagonal entries of block s (every n_s >= 2, checked by
+// the caller).  Launches: the state's upload and clear, then 4 x (histogram over all blocks, pick per segment), for any S.
+int launch_offdiag_lower_median_seg(const float* K, const int64_t* ptr, int64_t S, float* out, void* scratch, hipStream_t s) {
+  const SegMedianPlan plan(ptr, S);
+  char* p = static_cast<char*>(scratch);
+  SegMedianHead* head = reinterpret_cast<SegMedianHead*>(p);
+  p += ws_bytes((size_t)S, sizeof(SegMedianHead));
+  int64_t* d_ptr = reinterpret_cast<int64_t*>(p);
+  p += ws_bytes((size_t)S + 1, 8);
+  int64_t* d_kptr = reinterpret_cast<int64_t*>(p);
+  p += ws_bytes((size_t)S + 1, 8);
+  int64_t* d_tab = reinterpret_cast<int64_t*>(p);
+  p += ws_bytes(plan.tab.size(), 8);
+  unsigned long long* hist = reinterpret_cast<unsigned long long*>(p);
+  MMF_HIP(hipMemcpyAsync(head, plan.heads.data(), (size_t)S * sizeof(SegMedianHead), hipMemcpyHostToDevice, s));
+  MMF_HIP(hipMemcpyAsync(d_ptr, ptr, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, s));
+  MMF_HIP(hipMemcpyAsync(d_kptr, plan.kptr.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, s));
+  MMF_HIP(hipMemcpyAsync(d_tab, plan.tab.data(), plan.tab.size() * 8, hipMemcpyHostToDevice, s));
+  MMF_HIP(hipMemsetAsync(hist, 0, plan.hist_words * 8, s));
+  const int64_t grid = plan.entries();
+  for (int pass = 0; pass < 4; ++pass) {
+    hipLaunchKernelGGL(seg_median_hist_kernel, dim3((unsigned)grid), dim3(256), 0, s, K, d_ptr, d_kptr, d_tab, head, hist, 24 - 8 * pass);
+    MMF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(seg_median_pick_kernel, dim3((unsigned)S), dim3(256), 0, s, head, hist, 24 - 8 * pass, out);
+    MMF_LAUNCH_CHECK();
+  }
+  return MMF_OK;
+}
+
+// Threshold edges of every block: row r of the batch (segment s, local row i = r - ptr[s]) is row i of K_s against
+// thr[s]; its edges are (r, ptr[s] + j).  thr_scan_kernel's offsets over all n rows are then segment-major, row-major
+// within a segment, and segment s's edges start at row_off[ptr[s]].
+__device__ __forceinline__ int64_t seg_of_row(const int64_t* __restrict__ ptr, int64_t S, int64_t row) {
+  int64_t lo = 0, hi = S - 1;                        // the last s with ptr[s] <= row: a non-empty segment
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (ptr[mid] <= row) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void thr_count_seg_kernel(const float* __restrict__ K, const int64_t* __restrict__ ptr,
+                                                            const int64_t* __restrict__ kptr, int64_t S, int64_t n,
+                                                            const float* __restrict__ thr, uint32_t* __restrict__ row_cnt) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const int64_t sg = seg_of_row(ptr, S, row);
+  const int64_t ns = ptr[sg + 1] - ptr[sg];
+  const float* kr = K + kptr[sg] + (row - ptr[sg]) * ns;
+  const uint32_t c = thr_count_row(kr, ns, thr[sg], ((ns & 3) == 0) && ((reinterpret_cast<uintptr_t>(kr) & 15) == 0), lane);
+  if (lane == 0) row_cnt[row] = c;
+}
+
+__global__ __launch_bounds__(256) void thr_fill_seg_kernel(const float* __restrict__ K, const int64_t* __restrict__ ptr,
+                                                           const int64_t* __restrict__ kptr, int64_t S, int64_t n,
+                                                           const float* __restrict__ thr, const unsigned long long* __restrict__ row_off,
+                                                           int64_t* __restrict__ ei_row, int64_t* __restrict__ ei_col,
+                                                           float* __restrict__ ew, int64_t capacity) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const int64_t sg = seg_of_row(ptr, S, row);
+  const int64_t ns = ptr[sg + 1] - ptr[sg];
+  thr_fill_row(K + kptr[sg] + (row - ptr[sg]) * ns, ns, thr[sg], row_off[row], row, ptr[sg], ei_row, ei_col, ew, capacity, lane);
+}
+
+// d_ptr / d_kptr: device copies of the offsets (S + 1 each); n = ptr[S] >= 1.  *out_count must be zero on entry.
+int launch_threshold_count_seg(const float* K, const int64_t* d_ptr, const int64_t* d_kptr, int64_t S, int64_t n, const float* thr,
+                               unsigned long long* row_off, int64_t* out_count, uint32_t* row_cnt, hipStream_t s) {
+  const unsigned grid = (unsigned)((n + 3) / 4);
+  hipLaunchKernelGGL(thr_count_seg_kernel, dim3(grid), dim3(256), 0, s, K, d_ptr, d_kptr, S, n, thr, row_cnt);
+  MMF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(thr_scan_kernel, dim3(1), dim3(1024), 0, s, row_cnt, n, row_off, out_count);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+int launch_threshold_fill_seg(const float* K, const int64_t* d_ptr, const int64_t* d_kptr, int64_t S, int64_t n, const float* thr,
+                              const unsigned long long* row_off, int64_t* ei, float* ew, int64_t capacity, hipStream_t s) {
+  const unsigned grid = (unsigned)((n + 3) / 4);
+  hipLaunchKernelGGL(thr_fill_seg_kernel, dim3(grid), dim3(256), 0, s, K, d_ptr, d_kptr, S, n, thr, row_off, ei, ei + capacity, ew,
+                     capacity);
   MMF_LAUNCH_CHECK();
   return MMF_OK;
 }

@@ -186,6 +186,11 @@ int launch_sim_dense(const void* X, int64_t n, const void* Y, int64_t m, int64_t
 int launch_sim_dense_combined(const float* Fp, const float* P, int64_t n, int64_t d, int64_t dp,
                               float lambda_h, float lambda_g, const float* nf, int64_t row0, int64_t rows, float* out,
                               hipStream_t s);
+// segmented (mmf_sim_dense_combined_segmented): the host-built work table over the segments ptr[0..S] ([entries][8] int64,
+// block s of the output at sum_{t<s} n_t^2), and the launch over its device copy; Fp / nf / P cover all rows of the batch
+std::vector<int64_t> sim_dense_combined_seg_table(const int64_t* ptr, int64_t S);
+int launch_sim_dense_combined_seg(const float* Fp, const float* P, int64_t d, int64_t dp, float lambda_h, float lambda_g,
+                                  const float* nf, const int64_t* sched, int64_t grid, float* out, hipStream_t s);
 
 // mmf_edges.hip
 // Lower medians (torch.median: element (count - 1) / 2).  A population of 4 M values or more is first tried in ONE sweep
@@ -230,6 +235,14 @@ int launch_threshold_count(const float* K, int64_t n, float thr, unsigned long l
                            hipStream_t s);
 int launch_threshold_fill(const float* K, int64_t n, float thr, const unsigned long long* row_off, int64_t* ei, float* ew,
                           int64_t capacity, hipStream_t s);
+// segmented: the blocks K_s (n_s x n_s) stored one after the other from kptr[s] = sum_{t<s} n_t^2.  ptr: HOST offsets (every
+// n_s >= 2) for the median, which uploads its own tables into `scratch`; device copies d_ptr / d_kptr for the edges.
+size_t offdiag_lower_median_seg_scratch_bytes(const int64_t* ptr, int64_t S);
+int launch_offdiag_lower_median_seg(const float* K, const int64_t* ptr, int64_t S, float* out, void* scratch, hipStream_t s);
+int launch_threshold_count_seg(const float* K, const int64_t* d_ptr, const int64_t* d_kptr, int64_t S, int64_t n, const float* thr,
+                               unsigned long long* row_off, int64_t* out_count, uint32_t* row_cnt, hipStream_t s);
+int launch_threshold_fill_seg(const float* K, const int64_t* d_ptr, const int64_t* d_kptr, int64_t S, int64_t n, const float* thr,
+                              const unsigned long long* row_off, int64_t* ei, float* ew, int64_t capacity, hipStream_t s);
 
 // mmf_segments.hip: cluster-shaped steps (labels -> members, per-cluster means, cliques, k-NN pair dedup)
 int segment_max_segments();

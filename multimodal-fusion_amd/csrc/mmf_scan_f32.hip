@@ -64,10 +64,20 @@ struct ScanF32Args {
   const float* P; int dp; float neg_lambda_g;
   int64_t prow0;   // dense combined, panel form: query q of this launch is row prow0 + q of P
   int debug;   // MMF_F32_DEBUG (timing-only ablations): 1 skip epilogue, 2 skip staging
+  const int64_t* sched;   // SEG kernels only: [grid][SEGF_ENTRY] work table (launch_sim_dense_combined_seg)
 };
 
-template <int MODE, int CAP, int F_KC>
+// Work table entry of the segmented dense combined similarity (one per workgroup): the segment, the image row of the row
+// block's first query and how many of its F_QT queries are real, the segment's first row (candidate base for the image,
+// the norms and P), the candidate tile range inside the segment, the output base kptr[s] and the row stride n_s.
+enum { SEGF_SEG = 0, SEGF_ROW0 = 1, SEGF_NQ = 2, SEGF_CBASE = 3, SEGF_T0 = 4, SEGF_T1 = 5, SEGF_OUT = 6, SEGF_NS = 7, SEGF_ENTRY = 8 };
+
+// SEG (MODE_DENSE only, segmented calls): the row block, tile range, candidate base, output base and row stride come from the
+// work table a.sched instead of blockIdx / col_splits.  Tiles start at unaligned segment rows and read up to 127 rows past
+// them (the next segment, or the image's unwritten last block): those rows only reach masked outputs.
+template <int MODE, int CAP, int F_KC, bool SEG = false>
 __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) void scan_f32_kernel(ScanF32Args a) {
+  static_assert(!SEG || MODE == MODE_DENSE, "the segmented form has the dense epilogue only");
   constexpr int UPR = F_KC / 4;            // 16-byte units per image row
   constexpr int RPP = 64 / UPR;            // image rows per 1 KiB DMA piece
   constexpr int HP = F_QT / RPP;           // pieces per operand tile (8 / 16)
@@ -87,15 +97,24 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
   const int half = lane >> 5;
   const int c = lane & 31;
 
-  const int split = blockIdx.x % a.col_splits;
-  const int64_t rb = blockIdx.x / a.col_splits;
-  const int64_t q0 = rb * F_QT;
-
-  const int64_t total_tiles = (a.m + F_CT - 1) / F_CT;
-  int64_t t_begin = (int64_t)split * a.tiles_per_split;
-  int64_t t_end = t_begin + a.tiles_per_split;
-  if (t_end > total_tiles) t_end = total_tiles;
-  if (t_begin > t_end) t_begin = t_end;
+  int split = 0;
+  int64_t q0, t_begin, t_end;
+  int64_t m = a.m, qend = a.n_rows;        // columns of the output row; queries q < qend are real
+  int64_t cbase = 0, obase = 0;            // SEG: the segment's first row, its block's first output element
+  if constexpr (SEG) {
+    const int64_t* e = a.sched + (size_t)blockIdx.x * SEGF_ENTRY;
+    q0 = e[SEGF_ROW0]; qend = q0 + e[SEGF_NQ]; cbase = e[SEGF_CBASE];
+    t_begin = e[SEGF_T0]; t_end = e[SEGF_T1]; obase = e[SEGF_OUT]; m = e[SEGF_NS];
+  } else {
+    split = blockIdx.x % a.col_splits;
+    const int64_t rb = blockIdx.x / a.col_splits;
+    q0 = rb * F_QT;
+    const int64_t total_tiles = (a.m + F_CT - 1) / F_CT;
+    t_begin = (int64_t)split * a.tiles_per_split;
+    t_end = t_begin + a.tiles_per_split;
+    if (t_end > total_tiles) t_end = total_tiles;
+    if (t_begin > t_end) t_begin = t_end;
+  }
   const int nkc = (int)(a.dpad / F_KC);
   const int64_t steps = (t_end - t_begin) * nkc;
 
@@ -115,7 +134,7 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int64_t q = q0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * half;
-      rq16[r] = (q < a.n_rows) ? a.rx[q] : 1.0f;
+      rq16[r] = (q < qend) ? a.rx[q] : 1.0f;
     }
   }
 
@@ -142,12 +161,12 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
   auto stage = [&](int64_t ct, int kc, int buf) {
     if (kc == 0 && tid < F_CT) {
       int64_t j = ct * F_CT + tid;
-      if (j > a.m - 1) j = a.m - 1;
-      rcy = a.cy[j];
+      if (j > m - 1) j = m - 1;
+      rcy = a.cy[cbase + j];
     }
     if (a.debug & 2) return;
     const __amdgpu_buffer_rsrc_t crsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Yp + ct * F_CT * a.dpad), 0, -1, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Yp + (cbase + ct * F_CT) * a.dpad), 0, -1, 0x00020000);
     const int koff = kc * F_KC * 4;
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
@@ -226,7 +245,7 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int64_t j = ct * F_CT + 32 * t + c;            // this lane's output column
-          const bool jv = j < a.m;
+          const bool jv = j < m;
           const float cj = cys[tpar * F_CT + 32 * t + c];
           const float nl = (metric == MMF_RBF) ? a.neg_lambda : -1.0f;  // (-1)*sq == -sq exactly
 #pragma unroll
@@ -234,7 +253,7 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
             const int64_t q = q0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * half;
             const float dot = acc[t][r];
             acc[t][r] = 0.0f;
-            if (jv && q < a.n_rows) {
+            if (jv && q < qend) {
               float key;
               if (metric == MMF_DOT) key = dot;
               else if (metric == MMF_COSINE) key = key_from_dot<MMF_COSINE>(dot, rq16[r], cj, 0.0f);
@@ -244,14 +263,14 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
                 // K_g from the positions, canonical chains over dp (similarity_kernel.py:79-84, 122)
                 float ni = 0.f, nj = 0.f, dp_ = 0.f;
                 for (int e = 0; e < a.dp; ++e) {
-                  const float pi = a.P[(a.prow0 + q) * a.dp + e], pj = a.P[j * a.dp + e];
+                  const float pi = a.P[(a.prow0 + q) * a.dp + e], pj = a.P[(cbase + j) * a.dp + e];
                   ni = __builtin_fmaf(pi, pi, ni);
                   nj = __builtin_fmaf(pj, pj, nj);
                   dp_ = __builtin_fmaf(pi, pj, dp_);
                 }
                 v = v * expf(a.neg_lambda_g * sq_from(ni, nj, dp_));
               }
-              a.out[q * a.m + j] = v;
+              a.out[obase + (q - cbase) * m + j] = v;
             }
           }
         }
@@ -329,7 +348,7 @@ static size_t scan_f32_lds(int cap, int kc) {
   return sizeof(float) * (2 * F_QT * kc + 2 * F_CT * kc + 2 * F_CT) + (size_t)cap * F_NT * 8;
 }
 
-template <int MODE, int CAP>
+template <int MODE, int CAP, bool SEG = false>
 static int launch_f32_t(const ScanF32Args& a, int64_t grid, hipStream_t s) {
   if (a.metric < MMF_DOT || a.metric > MMF_RBF) {
     set_error("scan_f32: unsupported metric %d", a.metric);
@@ -341,7 +360,7 @@ static int launch_f32_t(const ScanF32Args& a, int64_t grid, hipStream_t s) {
   }
   constexpr int KC = (MODE == MODE_SCAN) ? 16 : 32;
   const size_t lds = scan_f32_lds(MODE == MODE_SCAN ? CAP : 0, KC);
-  auto kern = scan_f32_kernel<MODE, CAP, KC>;
+  auto kern = scan_f32_kernel<MODE, CAP, KC, SEG>;
   MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(F_NT), lds, s, a);
   MMF_LAUNCH_CHECK();
@@ -466,6 +485,53 @@ int launch_sim_dense_combined(const float* Fp, const float* P, int64_t n, int64_
   a.out = out; a.P = P; a.dp = (int)dp; a.neg_lambda_g = -lambda_g; a.prow0 = row0;
   a.metric = MMF_RBF;
   return launch_f32_t<MODE_DENSE, 16>(a, rbs * splits, s);
+}
+
+
+// Segmented dense combined similarity (mmf_sim_dense_combined_segmented): the work table over the segments ptr[0..S] of a
+// batch, [entries][SEGF_ENTRY] int64.  Each row block of F_QT rows of a segment takes its segment's column tiles in runs of
+// at most `per` tiles, `per` chosen so that the batch makes about as many workgroups as one plain call (1024 row block x
+// column split pairs): a few large segments split their columns and still fill the chip, thousands of small ones are one
+// entry each.  Every tile starts at a row below ptr[S] = n (the invariant that keeps the unbounded tile loads inside the
+// image, prep_f32_bytes).
+std::vector<int64_t> sim_dense_combined_seg_table(const int64_t* ptr, int64_t S) {
+  int64_t pairs = 0;
+  for (int64_t sg = 0; sg < S; ++sg) {
+    const int64_t b = (ptr[sg + 1] - ptr[sg] + F_QT - 1) / F_QT;
+    pairs += b * b;
+  }
+  int64_t per = (pairs + 1023) / 1024;
+  if (per < 1) per = 1;
+  std::vector<int64_t> tab;
+  int64_t kbase = 0;
+  for (int64_t sg = 0; sg < S; ++sg) {
+    const int64_t ns = ptr[sg + 1] - ptr[sg], tiles = (ns + F_CT - 1) / F_CT;
+    for (int64_t r = 0; r < ns; r += F_QT)
+      for (int64_t t0 = 0; t0 < tiles; t0 += per) {
+        const int64_t e[SEGF_ENTRY] = {sg, ptr[sg] + r, ns - r < F_QT ? ns - r : F_QT, ptr[sg], t0, t0 + per < tiles ? t0 + per : tiles, kbase, ns};
+        tab.insert(tab.end(), e, e + SEGF_ENTRY);
+      }
+    kbase += ns * ns;
+  }
+  return tab;
+}
+
+// One workgroup per entry of the device copy `sched` of that table (grid entries).  Fp / nf / P: f32 image, norms and
+// positions of all rows of the batch; out: the blocks K_s, block s at sched's output base.  The kernel of
+// launch_sim_dense_combined with its schedule read from the table (template flag SEG: the other instantiations are untouched).
+int launch_sim_dense_combined_seg(const float* Fp, const float* P, int64_t d, int64_t dp, float lambda_h, float lambda_g,
+                                  const float* nf, const int64_t* sched, int64_t grid, float* out, hipStream_t s) {
+  if (grid <= 0) return MMF_OK;
+  ScanF32Args a{};
+  a.dpad = prep_f32_dim(d);
+  a.Xp = Fp; a.Yp = Fp; a.n = 0; a.m = 0;
+  a.rx = nf; a.cy = nf; a.row_ids = nullptr; a.n_rows = 0;
+  a.neg_lambda = -lambda_h; a.kk = 0;
+  a.col_splits = 1; a.tiles_per_split = 0;
+  a.out = out; a.P = P; a.dp = (int)dp; a.neg_lambda_g = -lambda_g; a.prow0 = 0;
+  a.metric = MMF_RBF;
+  a.sched = sched;
+  return launch_f32_t<MODE_DENSE, 16, true>(a, grid, s);
 }
 
 }  // namespace mmf

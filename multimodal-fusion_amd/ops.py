@@ -341,6 +341,86 @@ def combined_threshold_edges(F: torch.Tensor, P: torch.Tensor, threshold: float,
     return ei, ew
 
 
+def _block_ptr(ptr, batch, what: str) -> torch.Tensor:
+    """Host offsets of the blocks K_s of a flat segmented K: like _segment_ptr, with the row count taken from ptr / batch."""
+    if ptr is not None and batch is None:
+        p = torch.as_tensor(ptr).reshape(-1)
+        rows = int(p[-1]) if p.numel() else 0
+    else:
+        rows = torch.as_tensor(batch).numel() if batch is not None else 0
+    return _segment_ptr(ptr, batch, rows, "", what)
+
+
+def _check_blocks(K: torch.Tensor, p: torch.Tensor, what: str) -> torch.Tensor:
+    sizes = p[1:] - p[:-1]
+    total = int((sizes * sizes).sum())
+    if K.numel() != total:
+        raise ValueError(f"{what}: K holds {K.numel()} values, the blocks of the segments {total}")
+    return K.contiguous().float().reshape(-1)
+
+
+def sim_dense_combined_segmented(F: torch.Tensor, P: torch.Tensor, lambda_h: float = 1.0, lambda_g: float = 1.0, *, ptr=None,
+                                 batch=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """sim_dense_combined of every segment F[ptr[s]:ptr[s+1]] in one launch (mmf_sim_dense_combined_segmented).  Returns
+    (K flat f32 [sum n_s^2] on F's device, kptr host int64 [S + 1]): block s is K[kptr[s]:kptr[s+1]].view(n_s, n_s), bit for
+    bit sim_dense_combined(F_s, P_s).  Segments: exactly one of ptr ([S + 1] offsets) / batch ([n] sorted ids, PyG)."""
+    F = _feat(F, "sim_dense_combined_segmented features").float()
+    P = _feat(P, "sim_dense_combined_segmented positions").float()
+    n, d = F.shape
+    p = _segment_ptr(ptr, batch, n, "", "sim_dense_combined_segmented")
+    sizes = p[1:] - p[:-1]
+    kptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(sizes * sizes, 0)])
+    _need_gpu(F, "sim_dense_combined_segmented")
+    if P.device != F.device or P.shape[0] != n:
+        raise ValueError("sim_dense_combined_segmented: features and positions must share device and N")
+    out = torch.empty((int(kptr[-1]),), dtype=torch.float32, device=F.device)
+    rc = _lib.lib().mmf_sim_dense_combined_segmented(_p(F), _p(P), n, d, P.shape[1], ctypes.c_void_p(p.data_ptr()), p.numel() - 1,
+                                                     float(lambda_h), float(lambda_g), _p(out), F.device.index or 0, _stream(F.device))
+    _lib.check(rc, "mmf_sim_dense_combined_segmented")
+    return out, kptr
+
+
+def offdiag_lower_median_segmented(K: torch.Tensor, *, ptr=None, batch=None) -> torch.Tensor:
+    """offdiag_lower_median of every block of a flat segmented K (the layout of sim_dense_combined_segmented): device f32 [S],
+    without a host synchronisation (mmf_offdiag_lower_median_segmented).  Every segment needs at least two rows."""
+    p = _block_ptr(ptr, batch, "offdiag_lower_median_segmented")
+    _need_gpu(K, "offdiag_lower_median_segmented")
+    K = _check_blocks(K, p, "offdiag_lower_median_segmented")
+    out = torch.empty((p.numel() - 1,), dtype=torch.float32, device=K.device)
+    rc = _lib.lib().mmf_offdiag_lower_median_segmented(_p(K), ctypes.c_void_p(p.data_ptr()), p.numel() - 1, _p(out),
+                                                       K.device.index or 0, _stream(K.device))
+    _lib.check(rc, "mmf_offdiag_lower_median_segmented")
+    return out
+
+
+def threshold_edges_segmented(K: torch.Tensor, thresholds, *, ptr=None, batch=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """threshold_edges of every block of a flat segmented K against its own threshold (thresholds: [S] floats).  Returns
+    (edge_index [2, E] int64 GLOBAL row ids, weights [E] f32, edge_ptr [S + 1] int64): the edges of segment s are
+    edge_ptr[s]:edge_ptr[s+1], those of threshold_edges(K_s, thresholds[s]) shifted by ptr[s].  One synchronisation (E)."""
+    p = _block_ptr(ptr, batch, "threshold_edges_segmented")
+    _need_gpu(K, "threshold_edges_segmented")
+    K = _check_blocks(K, p, "threshold_edges_segmented")
+    S, n = p.numel() - 1, int(p[-1])
+    thr = torch.as_tensor(thresholds, dtype=torch.float32).to(K.device).contiguous().reshape(-1)
+    if thr.numel() != S:
+        raise ValueError(f"threshold_edges_segmented: {thr.numel()} thresholds for {S} segments")
+    cnt = torch.zeros((), dtype=torch.int64, device=K.device)
+    L = _lib.lib()
+    dev, st = K.device.index or 0, _stream(K.device)
+    pp = ctypes.c_void_p(p.data_ptr())
+    row_off = torch.empty((n + 1,), dtype=torch.int64, device=K.device)
+    _lib.check(L.mmf_threshold_edges_segmented_count(_p(K), pp, S, _p(thr), _p(row_off), _p(cnt), dev, st),
+               "mmf_threshold_edges_segmented_count")
+    edge_ptr = row_off[p.to(K.device)]
+    E = int(cnt.item())
+    ei = torch.empty((2, E), dtype=torch.int64, device=K.device)
+    ew = torch.empty((E,), dtype=torch.float32, device=K.device)
+    if E:
+        _lib.check(L.mmf_threshold_edges_segmented_fill(_p(K), pp, S, _p(thr), _p(row_off), _p(ei), _p(ew), E, dev, st),
+                   "mmf_threshold_edges_segmented_fill")
+    return ei, ew, edge_ptr
+
+
 # ---------------------------------------------------------------------------------------------------
 # phase API of the fast path (row-sharded multi-GPU driver, distributed.py)
 # ---------------------------------------------------------------------------------------------------
