@@ -473,6 +473,30 @@ int mmf_clique_pairs(const int64_t* order, const int64_t* offsets, int64_t n, in
 int mmf_knn_pairs(const int64_t* nbr, int64_t n, int k, const int64_t* labels,
                   int64_t* pair_lo, int64_t* pair_hi, int64_t* out_count, int device_id, void* hip_stream);
 
+/*
+ * The edge list of the k-NN + KMeans hypergraph (build_hypergraph_knn_kmeans, preprocess_hypergraph.py:386-404) of every graph of
+ * a ragged batch, in its documented order, in two calls.  Segments as above (ptr_host: HOST offsets, ending
+ * at n; n_seg = 1 with ptr = {0, n} is the plain case).
+ *   nbr [n, k] int64   neighbour table with GLOBAL row ids, self already excluded; an entry that is negative, >= n or its own
+ *                      row is ignored, as in mmf_knn_pairs.
+ *   labels [n] int64   cluster of every row, LOCAL to its segment, in [0, n_clusters); NULL = no cliques.
+ * Edge set: every pair a < b of one segment and label, plus every undirected k-NN pair whose ends differ in (segment, label),
+ * once — what mmf_segment_sort + mmf_clique_pairs + mmf_knn_pairs give with labels made global.  Order: lexicographic in
+ * (lo, hi) over global ids, i.e. the per-graph order, graph after graph; the bits do not change from call to call.
+ *   _count  row_offsets (device uint64 [n + 1]): edges whose lo is below row i; edge_ptr (DEVICE int64 [n_seg + 1]) =
+ *           row_offsets[ptr[s]]; *out_count (device) = the number of edges, or -1 when a label lies outside its range.
+ *   _fill   edge_index [2, capacity]: lo in row 0, hi in row 1.  capacity = the count read back by the caller (the one host
+ *           read of the pair); capacity < 0 returns MMF_E_INVALID (the out-of-range label), so the flag needs no read of its own.
+ * No limit on the clusters beyond n_seg * n_clusters < 2^31; n < 2^31.  Neither entry allocates (beyond the cached workspace) or
+ * synchronises.
+ */
+int mmf_knn_clique_edges_count(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t n_clusters,
+                               const int64_t* ptr_host, int64_t n_seg, uint64_t* row_offsets, int64_t* edge_ptr,
+                               int64_t* out_count, int device_id, void* hip_stream);
+int mmf_knn_clique_edges_fill(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t n_clusters,
+                              const int64_t* ptr_host, int64_t n_seg, const uint64_t* row_offsets, int64_t* edge_index,
+                              int64_t capacity, int device_id, void* hip_stream);
+
 /* Release the library's cached per-device workspaces (they are grow-only otherwise). */
 int mmf_release_workspaces(void);
 

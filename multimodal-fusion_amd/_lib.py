@@ -51,7 +51,7 @@ EXPORTS = ["mmf_version", "mmf_last_error", "mmf_simtopk", "mmf_simtopk_ex", "mm
            "mmf_sim_dense", "mmf_sim_dense_stats", "mmf_sim_dense_combined", "mmf_offdiag_lower_median", "mmf_threshold_edges", "mmf_threshold_edges_count", "mmf_threshold_edges_fill", "mmf_lower_median", "mmf_array_stats",
            "mmf_segment_sort", "mmf_segment_mean", "mmf_segment_offdiag_mean", "mmf_clique_pairs", "mmf_knn_pairs", "mmf_kmeans_fit", "mmf_kmeans_fit_segmented", "mmf_combined_offdiag_median", "mmf_combined_threshold_edges",
            "mmf_sim_dense_combined_segmented", "mmf_offdiag_lower_median_segmented", "mmf_threshold_edges_segmented_count",
-           "mmf_threshold_edges_segmented_fill", "mmf_release_workspaces", "mmf_debug_query_order"]
+           "mmf_threshold_edges_segmented_fill", "mmf_knn_clique_edges_count", "mmf_knn_clique_edges_fill", "mmf_release_workspaces", "mmf_debug_query_order"]
 
 
 def lib() -> ctypes.CDLL:
@@ -105,6 +105,8 @@ def lib() -> ctypes.CDLL:
     L.mmf_offdiag_lower_median_segmented.argtypes = [vp, vp, i64, vp, ci, vp]
     L.mmf_threshold_edges_segmented_count.argtypes = [vp, vp, i64, vp, vp, vp, ci, vp]
     L.mmf_threshold_edges_segmented_fill.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, ci, vp]
+    L.mmf_knn_clique_edges_count.argtypes = [vp, i64, ci, vp, i64, vp, i64, vp, vp, vp, ci, vp]
+    L.mmf_knn_clique_edges_fill.argtypes = [vp, i64, ci, vp, i64, vp, i64, vp, vp, i64, ci, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("mmf_last_error", "mmf_padded_dim"):

@@ -1668,5 +1668,66 @@ int mmf_threshold_edges_segmented_fill(const float* K, const int64_t* ptr_host, 
                                    edge_index, edge_w, capacity, s);
 }
 
+// ---- ordered k-NN + clique edges of a ragged batch (mmf_knn_clique.hip) -----------------------------
+// The edge list that build_hypergraph_knn_kmeans assembles per slide (preprocess_hypergraph.py:386-404), for every segment at
+// once and already in its documented order.  Count, one host read of *out_count by the caller, fill.
+static int knn_clique_check(const char* what, const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t n_clusters,
+                            const int64_t* ptr_host, int64_t n_seg, int device_id) {
+  int64_t rows = 0;
+  MMF_TRY(check_blocks(what, ptr_host, n_seg, 0, device_id, &rows));
+  if (rows != n) { set_error("%s: ptr must end at n = %lld (got %lld)", what, (long long)n, (long long)rows); return MMF_E_INVALID; }
+  if (k < 1) { set_error("%s: k must be >= 1 (got %d)", what, k); return MMF_E_INVALID; }
+  if (n > 0 && !nbr) { set_error("%s: NULL pointer", what); return MMF_E_INVALID; }
+  if (labels) {
+    if (n_clusters < 1) { set_error("%s: n_clusters must be >= 1 (got %lld)", what, (long long)n_clusters); return MMF_E_INVALID; }
+    if (n_clusters >= ((int64_t)1 << 31) || n_seg * n_clusters >= ((int64_t)1 << 31)) {
+      set_error("%s: n_seg * n_clusters = %lld x %lld, must be < 2^31", what, (long long)n_seg, (long long)n_clusters);
+      return MMF_E_UNSUPPORTED;
+    }
+  }
+  return MMF_OK;
+}
+
+int mmf_knn_clique_edges_count(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t n_clusters, const int64_t* ptr_host,
+                               int64_t n_seg, uint64_t* row_offsets, int64_t* edge_ptr, int64_t* out_count, int device_id,
+                               void* hip_stream) {
+  MMF_TRY(knn_clique_check("knn_clique_edges_count", nbr, n, k, labels, n_clusters, ptr_host, n_seg, device_id));
+  if (!row_offsets || !edge_ptr || !out_count) { set_error("knn_clique_edges_count: NULL pointer"); return MMF_E_INVALID; }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  if (n == 0) {
+    MMF_HIP(hipMemsetAsync(out_count, 0, 8, s));
+    MMF_HIP(hipMemsetAsync(row_offsets, 0, 8, s));
+    MMF_HIP(hipMemsetAsync(edge_ptr, 0, (size_t)(n_seg + 1) * 8, s));
+    return MMF_OK;
+  }
+  const size_t need = knn_clique_scratch_bytes(n, n_seg, n_clusters, labels != nullptr);
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, need, &ws));
+  return launch_knn_clique_count(nbr, n, k, labels, n_clusters, ptr_host, n_seg, reinterpret_cast<unsigned long long*>(row_offsets),
+                                 edge_ptr, out_count, ws.take<char>(need), s);
+}
+
+int mmf_knn_clique_edges_fill(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t n_clusters, const int64_t* ptr_host,
+                              int64_t n_seg, const uint64_t* row_offsets, int64_t* edge_index, int64_t capacity, int device_id,
+                              void* hip_stream) {
+  MMF_TRY(knn_clique_check("knn_clique_edges_fill", nbr, n, k, labels, n_clusters, ptr_host, n_seg, device_id));
+  if (capacity < 0) {      // what the count entry reports instead of a count when a label is out of range
+    set_error("knn_clique_edges_fill: capacity %lld: a label lies outside [0, %lld)", (long long)capacity, (long long)n_clusters);
+    return MMF_E_INVALID;
+  }
+  if (n == 0 || capacity == 0) return MMF_OK;
+  if (!row_offsets || !edge_index) { set_error("knn_clique_edges_fill: NULL pointer"); return MMF_E_INVALID; }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  const size_t need = knn_clique_scratch_bytes(n, n_seg, n_clusters, labels != nullptr);
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, need, &ws));
+  return launch_knn_clique_fill(nbr, n, k, labels, n_clusters, ptr_host, n_seg, reinterpret_cast<const unsigned long long*>(row_offsets),
+                                edge_index, capacity, ws.take<char>(need), s);
+}
+
 
 }  // extern "C"

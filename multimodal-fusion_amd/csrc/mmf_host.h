@@ -256,6 +256,13 @@ int launch_segment_offdiag_mean(const float* K, int64_t n, const int64_t* order,
 size_t clique_scratch_bytes(int64_t n, int64_t S);
 int launch_clique_pairs(const int64_t* order, const int64_t* offsets, int64_t n, int64_t S, int64_t* lo, int64_t* hi,
                         int64_t capacity, int64_t* out_count, void* scratch, hipStream_t s);
+// mmf_knn_clique.hip: the ordered k-NN + clique edge list of every segment (mmf_knn_clique_edges_count / _fill).  ptr: HOST
+// offsets, uploaded into `scratch` (knn_clique_scratch_bytes) by both; labels local to the segment, nullptr = no cliques.
+size_t knn_clique_scratch_bytes(int64_t n, int64_t n_seg, int64_t H, bool with_labels);
+int launch_knn_clique_count(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t H, const int64_t* ptr, int64_t n_seg,
+                            unsigned long long* row_off, int64_t* edge_ptr, int64_t* out_count, void* scratch, hipStream_t s);
+int launch_knn_clique_fill(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t H, const int64_t* ptr, int64_t n_seg,
+                           const unsigned long long* row_off, int64_t* edge_index, int64_t capacity, void* scratch, hipStream_t s);
 // mmf_kmeans.hip: scikit-learn's KMeans fit, decision for decision, all restarts in lockstep (host-synchronous).
 // Groups of consecutive segments [bounds[i], bounds[i + 1]) that fit one lockstep (n_seg n_init k <= segment_max_segments(),
 // n_init rows < 2^31, bounded scratch); *max_bytes = the largest group's scratch.  The plain fit is ptr = {0, n}, one segment.

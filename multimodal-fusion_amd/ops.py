@@ -605,6 +605,40 @@ def knn_pairs(nbr: torch.Tensor, labels: Optional[torch.Tensor] = None) -> Tuple
     return lo[:E], hi[:E]
 
 
+def knn_clique_edges(nbr: torch.Tensor, labels: Optional[torch.Tensor], n_clusters: int, *, ptr=None,
+                     batch=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The ordered edge list of the k-NN + KMeans hypergraph of every segment (mmf_knn_clique_edges_count / _fill): every
+    pair a < b of one segment and label, plus every undirected pair of `nbr` ([n, k] GLOBAL row ids, self excluded, negative
+    entries ignored) whose ends differ in (segment, label), once.  `labels` ([n], LOCAL to the segment, in [0, n_clusters))
+    may be None: no cliques.  Returns (edge_index [2, E] int64, lexicographic in (lo, hi), edge_ptr [S + 1] int64 on the
+    device); neither ptr nor batch = one segment.  One synchronisation (E); a label out of range raises ValueError."""
+    if nbr.dim() != 2 or nbr.shape[1] < 1:
+        raise ValueError(f"knn_clique_edges: nbr must be [n, k] with k >= 1, got shape {tuple(nbr.shape)}")
+    n, k = nbr.shape
+    p = torch.tensor([0, n], dtype=torch.int64) if ptr is None and batch is None else _segment_ptr(ptr, batch, n, "", "knn_clique_edges")
+    S = p.numel() - 1
+    if S < 1:
+        raise ValueError("knn_clique_edges: no segments")
+    if labels is not None and labels.numel() != n:
+        raise ValueError(f"knn_clique_edges: {labels.numel()} labels for {n} rows")
+    _need_gpu(nbr, "knn_clique_edges")
+    dev = nbr.device
+    nbr = nbr.to(torch.int64).contiguous()
+    lab = None if labels is None else labels.to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
+    row_off = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    edge_ptr = torch.empty((S + 1,), dtype=torch.int64, device=dev)
+    cnt = torch.zeros((), dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    args = (_p(nbr), n, k, _p(lab), int(n_clusters), ctypes.c_void_p(p.data_ptr()), S)
+    _lib.check(L.mmf_knn_clique_edges_count(*args, _p(row_off), _p(edge_ptr), _p(cnt), dev.index or 0, _stream(dev)),
+               "mmf_knn_clique_edges_count")
+    E = int(cnt.item())                 # -1: a label out of range, which the fill entry turns into the error
+    ei = torch.empty((2, max(E, 0)), dtype=torch.int64, device=dev)
+    _lib.check(L.mmf_knn_clique_edges_fill(*args, _p(row_off), _p(ei), E, dev.index or 0, _stream(dev)),
+               "mmf_knn_clique_edges_fill")
+    return ei, edge_ptr
+
+
 def kmeans_fit(X: torch.Tensor, n_clusters: int, first_centres, uniforms, *, max_iter: int = 300, tol: float = 1e-4,
                return_seeds: bool = False):
     """scikit-learn's KMeans fit on the device, decision for decision (mmf_kmeans_fit).  X f32 [n, d] on the GPU;

@@ -1,0 +1,161 @@
+"""Segmented k-NN + KMeans hypergraph without a GPU: the header declares the two edge entries, the library and the binding
+export them, the mirror package is unchanged, every argument error is raised on the host before the device check, and the
+two-sided segment description gives the node offsets the builder numbers its nodes with."""
+import ctypes
+import os
+from importlib import import_module
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ["mmf_knn_clique_edges_count", "mmf_knn_clique_edges_fill"]
+FNS = ["build_hypergraph_knn_kmeans_segmented", "knn_kmeans_edges_segmented"]
+
+
+def _kk():
+    import multimodal_fusion_amd  # noqa: F401
+    return import_module("multimodal_fusion_amd.knn_kmeans_hypergraph")
+
+
+def test_header_declares_the_entries():
+    with open(os.path.join(ROOT, "include", "mmf_hg.h")) as f:
+        h = f.read()
+    for name in ENTRIES:
+        assert f"int {name}(" in h, name
+    assert "#define MMF_ABI_VERSION 3" in h
+
+
+def test_library_and_package_export_the_entries():
+    import multimodal_fusion_amd as mmf
+    L = ctypes.CDLL(mmf._lib.SO_PATH)
+    for name in ENTRIES:
+        assert name in mmf._lib.EXPORTS, name
+        assert hasattr(L, name), name
+    assert mmf._lib.ABI_VERSION == 3 and mmf._lib.lib().mmf_version() == 3
+    assert callable(mmf.ops.knn_clique_edges)
+    for fn in FNS:
+        assert fn in mmf.__all__ and getattr(mmf, fn) is getattr(_kk(), fn)
+
+
+def test_mirror_package_is_unchanged():
+    import multimodal_fusion_amd  # noqa: F401
+    bh = import_module("multimodal_fusion_amd.build_hypergraph")
+    for fn in FNS:
+        assert fn not in bh.__all__
+    assert len(bh.__all__) == 17
+
+
+def test_new_kernels_are_a_build_source():
+    with open(os.path.join(ROOT, "multimodal-fusion_amd", "csrc", "build.py")) as f:
+        assert '"mmf_knn_clique.hip"' in f.read()
+
+
+# 10 wsi rows and 6 tma rows on the CPU: every check comes before the device check
+BAD = [
+    (dict(wsi_ptr=[0, 5, 9], tma_ptr=[0, 3, 6]), "wsi_ptr must start at 0 and end at 10"),
+    (dict(wsi_ptr=[1, 5, 10], tma_ptr=[0, 3, 6]), "wsi_ptr must start at 0"),
+    (dict(wsi_ptr=[0, 6, 4, 10], tma_ptr=[0, 2, 4, 6]), "wsi_ptr must be non-decreasing"),
+    (dict(wsi_ptr=[0, 5, 10], tma_ptr=[0, 3, 5]), "tma_ptr must start at 0 and end at 6"),
+    (dict(wsi_ptr=[0, 5, 10], tma_ptr=[0, 4, 3, 6]), "tma_ptr must be non-decreasing"),
+    (dict(wsi_batch=torch.tensor([0, 0, 0, 1, 1, 1, 0, 1, 1, 1]), tma_ptr=[0, 3, 6]), "wsi_batch must be sorted"),
+    (dict(wsi_ptr=[0, 5, 10], tma_batch=torch.tensor([-1, 0, 0, 0, 1, 1])), "tma_batch must be sorted and non-negative"),
+    (dict(wsi_batch=torch.zeros(9, dtype=torch.long), tma_ptr=[0, 6]), r"wsi_batch must hold one segment id per row \(10\)"),
+    (dict(wsi_ptr=[0, 5, 10], wsi_batch=torch.zeros(10, dtype=torch.long), tma_ptr=[0, 3, 6]), "exactly one of wsi_ptr / wsi_batch"),
+    (dict(wsi_ptr=[0, 5, 10]), "exactly one of tma_ptr / tma_batch"),
+    (dict(tma_ptr=[0, 3, 6]), "exactly one of wsi_ptr / wsi_batch"),
+    (dict(wsi_ptr=[0, 5, 10], tma_ptr=[0, 2, 4, 6]), "wsi has 2 segments, tma has 3"),
+    (dict(wsi_ptr=[0, 5, 10], tma_batch=torch.zeros(6, dtype=torch.long)), "wsi has 2 segments, tma has 1"),
+    # slide 1 has 2 + 1 = 3 nodes: too few for k + 1 = 4 neighbours (sklearn's kneighbors text)
+    (dict(wsi_ptr=[0, 8, 10], tma_ptr=[0, 5, 6], k=3, num_hyperedges=2),
+     r"segment 1: Expected n_neighbors <= n_samples_fit, but n_neighbors = 4, n_samples_fit = 3, n_samples = 3"),
+    # slide 0 has 2 + 1 = 3 nodes: enough for k = 2, fewer than the 4 clusters (the text of kmeans_fit_predict_segmented)
+    (dict(wsi_ptr=[0, 2, 10], tma_ptr=[0, 1, 6], k=2, num_hyperedges=4), r"segment 0: n_samples=3 should be >= n_clusters=4\."),
+    # both: the neighbours are asked for first, as in the plain mirror
+    (dict(wsi_ptr=[0, 2, 10], tma_ptr=[0, 1, 6], k=5, num_hyperedges=4), r"segment 0: Expected n_neighbors <= n_samples_fit"),
+    (dict(wsi_ptr=[0, 5, 10], tma_ptr=[0, 3, 6], num_hyperedges=0), r"segment 0: n_samples=8 should be >= n_clusters=0\."),
+]
+
+
+@pytest.mark.parametrize("kw,match", BAD)
+def test_builder_rejects_bad_input_on_the_host(kw, match):
+    kw = dict(kw)
+    k, H = kw.pop("k", 2), kw.pop("num_hyperedges", 2)
+    with pytest.raises(ValueError, match=match):
+        _kk().build_hypergraph_knn_kmeans_segmented(torch.randn(10, 8), torch.randn(6, 8), None, k, H, **kw)
+
+
+def test_builder_rejects_different_feature_widths():
+    with pytest.raises(ValueError, match="D=8, tma_features D=7"):
+        _kk().build_hypergraph_knn_kmeans_segmented(torch.randn(10, 8), torch.randn(6, 7), None, 2, 2, wsi_ptr=[0, 5, 10],
+                                                    tma_ptr=[0, 3, 6])
+    with pytest.raises(ValueError, match="2-D"):
+        _kk().build_hypergraph_knn_kmeans_segmented(torch.randn(10), torch.randn(6, 7), None, 2, 2, wsi_ptr=[0, 5, 10],
+                                                    tma_ptr=[0, 3, 6])
+
+
+@pytest.mark.parametrize("kw,match", [
+    (dict(ptr=[0, 5, 9]), "end at 10"),
+    (dict(ptr=[1, 5, 10]), "start at 0"),
+    (dict(ptr=[0, 6, 4, 10]), "non-decreasing"),
+    (dict(batch=torch.tensor([0, 0, 0, 1, 1, 1, 0, 1, 1, 1])), "sorted"),
+    (dict(batch=torch.zeros(9, dtype=torch.long)), "one segment id per row"),
+    (dict(ptr=[0, 10], batch=torch.zeros(10, dtype=torch.long)), "exactly one"),
+    (dict(), "exactly one"),
+    (dict(ptr=[0, 7, 10], k=3), r"segment 1: Expected n_neighbors <= n_samples_fit, but n_neighbors = 4, n_samples_fit = 3"),
+    (dict(ptr=[0, 7, 7, 10], k=1), r"segment 1: Expected n_neighbors <= n_samples_fit, but n_neighbors = 2, n_samples_fit = 0"),
+    (dict(ptr=[0, 7, 10], k=2, num_hyperedges=5), r"segment 1: n_samples=3 should be >= n_clusters=5\."),
+])
+def test_edges_call_rejects_bad_input_on_the_host(kw, match):
+    kw = dict(kw)
+    k, H = kw.pop("k", 2), kw.pop("num_hyperedges", 2)
+    with pytest.raises(ValueError, match=match):
+        _kk().knn_kmeans_edges_segmented(torch.randn(10, 8), k, H, **kw)
+
+
+def test_valid_input_reaches_the_device_check(monkeypatch):
+    """With nothing to object to, CPU tensors fail at the device, not at an argument: no host path computes edges."""
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    with pytest.raises(RuntimeError, match="ROCm"):
+        _kk().knn_kmeans_edges_segmented(torch.randn(10, 8), 2, 2, ptr=[0, 5, 10])
+    with pytest.raises(RuntimeError, match="ROCm"):
+        _kk().build_hypergraph_knn_kmeans_segmented(torch.randn(10, 8), torch.randn(6, 8), None, 2, 2, wsi_ptr=[0, 5, 10],
+                                                    tma_ptr=[0, 3, 6])
+
+
+def test_node_offsets_from_ptr_and_from_batch():
+    kk = _kk()
+    # four slides; slide 2 has no tma rows
+    wp, tp, node = kk.node_offsets(12, 7, wsi_ptr=[0, 3, 7, 9, 12], tma_ptr=[0, 2, 5, 5, 7])
+    assert wp.tolist() == [0, 3, 7, 9, 12] and tp.tolist() == [0, 2, 5, 5, 7]
+    assert node.tolist() == [0, 5, 12, 14, 19]
+    wb = torch.tensor([0, 0, 0, 1, 1, 1, 1, 2, 2, 3, 3, 3])
+    tb = torch.tensor([0, 0, 1, 1, 1, 3, 3])                       # id 2 has no rows
+    for kw in (dict(wsi_batch=wb, tma_batch=tb), dict(wsi_ptr=[0, 3, 7, 9, 12], tma_batch=tb),
+               dict(wsi_batch=wb, tma_ptr=torch.tensor([0, 2, 5, 5, 7]))):
+        w2, t2, n2 = kk.node_offsets(12, 7, **kw)
+        assert w2.tolist() == wp.tolist() and t2.tolist() == tp.tolist() and n2.tolist() == node.tolist()
+    # slide s: wsi rows first, then its tma rows, numbered from node[s]
+    sizes = (node[1:] - node[:-1]).tolist()
+    assert sizes == [(wp[s + 1] - wp[s] + tp[s + 1] - tp[s]).item() for s in range(4)] == [5, 7, 2, 5]
+    with pytest.raises(ValueError, match="wsi has 4 segments, tma has 3"):
+        kk.node_offsets(12, 5, wsi_batch=wb, tma_batch=torch.tensor([0, 0, 1, 1, 2]))     # a batch vector ends at its last id
+
+
+def test_ops_entry_checks_its_arguments_on_the_host():
+    import multimodal_fusion_amd as mmf
+    nbr = torch.zeros((10, 3), dtype=torch.int64)
+    with pytest.raises(ValueError, match="end at 10"):
+        mmf.ops.knn_clique_edges(nbr, None, 1, ptr=[0, 4, 9])
+    with pytest.raises(ValueError, match="exactly one"):
+        mmf.ops.knn_clique_edges(nbr, None, 1, ptr=[0, 10], batch=torch.zeros(10, dtype=torch.long))
+    with pytest.raises(ValueError, match="9 labels for 10 rows"):
+        mmf.ops.knn_clique_edges(nbr, torch.zeros(9, dtype=torch.int64), 1)
+    with pytest.raises(ValueError, match=r"\[n, k\]"):
+        mmf.ops.knn_clique_edges(torch.zeros(10, dtype=torch.int64), None, 1)
+    # the C entries themselves: host checks before any device work (device_id < 0 has no path)
+    L = mmf._lib.lib()
+    ptr = (ctypes.c_int64 * 2)(0, 10)
+    assert L.mmf_knn_clique_edges_count(None, 10, 3, None, 1, ptr, 1, None, None, None, -1, None) == mmf._lib.MMF_E_UNSUPPORTED
+    bad = (ctypes.c_int64 * 3)(0, 6, 4)
+    assert L.mmf_knn_clique_edges_fill(None, 4, 3, None, 1, bad, 2, None, None, 0, 0, None) == mmf._lib.MMF_E_INVALID
