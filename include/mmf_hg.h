@@ -89,6 +89,12 @@ const char* mmf_last_error(void);
 /* diagnostics: the scan position -> row permutation of the most recent call that reordered its n queries (host buffer, n entries);
  * valid until the next fast-path call or mmf_release_workspaces.  MMF_E_INVALID when there is none. */
 int         mmf_debug_query_order(int32_t* perm_host, int64_t n);
+/* diagnostics, host only: the work table of the symmetric 16-bit scan (X against itself, cosine / dot, padded dim 512; environment
+ * MMF_SYMMETRIC = 0 / 1 forces it off / on, MMF_SYMMETRIC_G sets `group`) for `row_blocks` blocks of 256 rows in super-blocks of
+ * `group` blocks (row_blocks / group of them; the last one also takes the row_blocks % group left-over blocks).  launch 0: plain pairs, launch 1: pairs scanned once for both directions.  Returns the number of workgroups
+ * (negative: error) and, when table_host is not NULL (capacity >= that number of entries), fills entries of 8 ints:
+ * { row block or -1 (idle), first tile, tile count, first tile, tile count of a second range, 0, 0, 0 }, tiles of 32 columns. */
+int64_t     mmf_debug_symmetric_schedule(int64_t row_blocks, int group, int launch, int32_t* table_host, int64_t capacity);
 
 /*
  * Fused similarity + per-row top-k; the N x M matrix never reaches HBM.
@@ -129,7 +135,7 @@ typedef struct mmf_simtopk_stats {
   int64_t  fallback_rows;  /* rows whose candidate list overflowed and were rescanned exactly    */
   int      precision_used; /* MMF_PREC_EXACT or MMF_PREC_FAST                                    */
   int      col_splits;     /* column ranges per row block actually used                         */
-  int      scan_grid;      /* workgroups launched by the scan kernel                             */
+  int      scan_grid;      /* workgroups launched by the scan kernel (symmetric scan: the sum over its two launches) */
   float    scan_wait_ms;   /* paneled scan, profile = 1: part of scan_ms the stream spent waiting for panels'
                               ready_events (exposed exchange time), 0 otherwise                   */
   int64_t  overflow_rows;  /* fallback rows whose candidate list overflowed (near-ties beyond capacity) */

@@ -51,7 +51,8 @@ EXPORTS = ["mmf_version", "mmf_last_error", "mmf_simtopk", "mmf_simtopk_ex", "mm
            "mmf_sim_dense", "mmf_sim_dense_stats", "mmf_sim_dense_combined", "mmf_offdiag_lower_median", "mmf_threshold_edges", "mmf_threshold_edges_count", "mmf_threshold_edges_fill", "mmf_lower_median", "mmf_array_stats",
            "mmf_segment_sort", "mmf_segment_mean", "mmf_segment_offdiag_mean", "mmf_clique_pairs", "mmf_knn_pairs", "mmf_kmeans_fit", "mmf_kmeans_fit_segmented", "mmf_combined_offdiag_median", "mmf_combined_threshold_edges",
            "mmf_sim_dense_combined_segmented", "mmf_offdiag_lower_median_segmented", "mmf_threshold_edges_segmented_count",
-           "mmf_threshold_edges_segmented_fill", "mmf_knn_clique_edges_count", "mmf_knn_clique_edges_fill", "mmf_release_workspaces", "mmf_debug_query_order"]
+           "mmf_threshold_edges_segmented_fill", "mmf_knn_clique_edges_count", "mmf_knn_clique_edges_fill", "mmf_release_workspaces", "mmf_debug_query_order",
+           "mmf_debug_symmetric_schedule"]
 
 
 def lib() -> ctypes.CDLL:
@@ -112,6 +113,8 @@ def lib() -> ctypes.CDLL:
         if name not in ("mmf_last_error", "mmf_padded_dim"):
             fn.restype = ci
     L.mmf_padded_dim.restype = i64
+    L.mmf_debug_symmetric_schedule.argtypes = [i64, ci, ci, vp, i64]
+    L.mmf_debug_symmetric_schedule.restype = i64
     L.mmf_last_error.restype = ctypes.c_char_p
     if L.mmf_version() != ABI_VERSION:
         raise RuntimeError(f"{SO_PATH}: ABI version {L.mmf_version()}, this package binds version {ABI_VERSION} "

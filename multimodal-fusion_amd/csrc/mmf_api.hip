@@ -72,6 +72,10 @@ int launch_scan_b16(const void* ZQ, const void* ZC, const float* cb, const float
                     int64_t d, bool f16, int metric, int kk, int col_splits, const CandLists& L, void* scratch,
                     const ScanB16Panel& pn, hipStream_t s, int* grid_out);
 int launch_scan_b16_audit(const ScanB16Panel& pn, uint32_t* overflow, int64_t n_rows, hipStream_t s);
+size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G);
+int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const float* rn, const float* un, const uint32_t* maxima,
+                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, const CandLists& L, void* scratch,
+                        const SymBuffers& sb, std::vector<int32_t>& tab, const ScanB16Panel& pn, hipStream_t s, int* grid_out);
 size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap);
 int scan_bf16_slot_ulp(int cap);
 int scan_b16_queries_per_block(int dp);
@@ -239,6 +243,26 @@ static CandLists carve_b16_lists(Workspace& ws, int64_t n, int lists, int bcap) 
   L.overflow = ws.take<uint32_t>(n); L.spill_cnt = ws.take<uint32_t>(n); L.spill_ids = ws.take<uint32_t>((size_t)n * kSpillCap);
   L.spill_stacks = (lists == 2 && !getenv("MMF_SPILL_COUNTER")) ? 1 : 0;   // one pair: its two lanes fill the slots from both ends
   return L;
+}
+
+// The symmetric 16-bit scan (launch_scan_b16_sym) applies to X against itself with equal id offsets, cosine or dot (no
+// per-candidate bias), padded dim 512, 15-entry lists, no forced column splits, and an operand image inside the 32-bit tile
+// offsets.  MMF_SYMMETRIC (read per call): 0 = never, 1 = whenever it applies, unset = from kSymMinRows rows on — below that
+// its first launch (own + antipodal super-block only) leaves compute units idle (profiles/r04_symmetric_ab.txt).
+// MMF_SYMMETRIC_G: row blocks per super-block (default: 32, more when that would make more than 32 super-blocks).
+static constexpr int64_t kSymMinRows = 131072;
+static bool symmetric_scan_wanted(int64_t n, int dp, int bcap, int metric, int forced_splits, bool same_ids, int* G) {
+  if (!same_ids || dp != 512 || bcap != scan_bf16_cap(1, 512) || forced_splits != 0) return false;
+  if (metric != MMF_DOT && metric != MMF_COSINE) return false;
+  const int64_t nb = (n + 255) / 256;
+  if (nb * 256 * 1024 >= (int64_t(1) << 32)) return false;
+  const char* e = getenv("MMF_SYMMETRIC");
+  const int mode = e ? atoi(e) : -1;
+  if (mode == 0 || (mode < 0 && n < kSymMinRows)) return false;
+  int g = sym_default_group(nb);
+  if (const char* ge = getenv("MMF_SYMMETRIC_G")) { const int v = atoi(ge); if (v >= 1 && v <= 65536) g = v; }
+  *G = g;
+  return true;
 }
 
 // ---- the exact f32 pass -----------------------------------------------------------------------------------------------
@@ -417,6 +441,27 @@ struct FastTail {
     return MMF_OK;
   }
 
+  // Symmetric scan (launch_scan_b16_sym): tried when the call qualifies (set_symmetric), taken unless the query
+  // order is applied (scan positions are then not rows, and near-duplicate bands would flood the rows' received lists).  The
+  // buffers hold whichever path runs: the lists are carved for the larger list count and used through view().
+  bool sym_try = false; int sym_G = 32; int lists_alloc = 0;
+  SymBuffers sym;
+  std::vector<int32_t> sym_tab;   // host copy of the work tables: alive until run() has synchronised the stream
+  uint32_t* sym_cnt = nullptr; uint32_t* sym_ids = nullptr; float* sym_keys = nullptr;
+  int64_t sym_grid() const { return sym_schedule_grid((n + 255) / 256, sym_G); }
+  void set_symmetric(int G) {   // before bytes() / carve()
+    sym_try = true; sym_G = G;
+    if (lists_alloc < 4) lists_alloc = 4;
+  }
+  CandLists view(bool symmetric) const {
+    CandLists v = L;
+    v.lists = symmetric ? 4 : lists;
+    if (v.lists <= 2) { v.keys = nullptr; v.margin = nullptr; }
+    v.spill_stacks = (v.lists == 2 && !getenv("MMF_SPILL_COUNTER")) ? 1 : 0;
+    if (symmetric) { v.sym_cnt = sym_cnt; v.sym_ids = sym_ids; v.sym_keys = sym_keys; v.sym_cap = kSymCap; }
+    return v;
+  }
+
   int dp, panels;
   int panel_splits[16]; int max_splits = 1;
   int64_t n_seed;
@@ -465,25 +510,35 @@ struct FastTail {
     max_splits = 1;
     for (int p = 0; p < panels && p < 16; ++p) if (panel_splits[p] > max_splits) max_splits = panel_splits[p];
     lists = 2 * total_splits;
+    lists_alloc = lists;
     rows_exact_cap = (int64_t(64) << 20) / (4 * (m > 0 ? m : 1));
     if (rows_exact_cap > kRowsExactMax) rows_exact_cap = kRowsExactMax;
     if (rows_exact_cap < 1) rows_exact_cap = 1;
     FB = n < ExactPass::kBatch ? n : ExactPass::kBatch;   // exact rescans are done in batches of at most FB rows
     fb_splits = pick_splits((FB + 127) / 128, (m + 127) / 128, cap, 0);
   }
+  size_t scan_scratch_bytes() const {
+    const size_t a = scan_b16_scratch_bytes(n, max_splits, dp, bcap), b = sym_try ? scan_b16_sym_scratch_bytes(n, sym_G) : 0;
+    return a > b ? a : b;
+  }
   size_t bytes() const {
-    return b16_lists_bytes(n, lists, bcap) + ws_bytes(n, 4) + ws_bytes(4, 4) + ws_bytes(256, 4) +
-           ExactLists::bytes(FB, (size_t)FB * 2 * fb_splits, cap, false) + ws_bytes(scan_b16_scratch_bytes(n, max_splits, dp, bcap), 1) +
+    return b16_lists_bytes(n, lists_alloc, bcap) + ws_bytes(n, 4) + ws_bytes(4, 4) + ws_bytes(256, 4) +
+           ExactLists::bytes(FB, (size_t)FB * 2 * fb_splits, cap, false) + ws_bytes(scan_scratch_bytes(), 1) +
+           (sym_try ? ws_bytes(n, 4) + 2 * ws_bytes((size_t)n * kSymCap, 4) + SymBuffers::bytes(n_pad_q(), sym_grid()) : 0) +
            ws_bytes(2 * n_seed, 4) + ws_bytes((size_t)rows_exact_cap * m, 4) + ws_bytes(select_order_bytes(n), 1) +
            (order_try ? ws_bytes(query_order_bytes(n), 1) + ws_bytes((size_t)n_pad_q() * dp, 2) + 3 * ws_bytes(n_pad_q(), 4) : 0);
   }
   void carve(Workspace& ws) {
-    L = carve_b16_lists(ws, n, lists, bcap);
+    L = carve_b16_lists(ws, n, lists_alloc, bcap);
+    if (sym_try) {
+      sym_cnt = ws.take<uint32_t>(n); sym_ids = ws.take<uint32_t>((size_t)n * kSymCap); sym_keys = ws.take<float>((size_t)n * kSymCap);
+      sym.carve(ws, n_pad_q(), sym_grid());
+    }
     fail_rows = ws.take<int32_t>(n);
     fail_count = ws.take<uint32_t>(4);
     cand_total = ws.take<uint32_t>(256);
     XL.carve(ws, FB, (size_t)FB * 2 * fb_splits, cap, false);
-    scan_scratch = ws.take<char>(scan_b16_scratch_bytes(n, max_splits, dp, bcap));
+    scan_scratch = ws.take<char>(scan_scratch_bytes());
     seed = ws.take<int32_t>(2 * n_seed);
     row_keys = ws.take<float>((size_t)rows_exact_cap * m);
     order_scratch = ws.take<char>(select_order_bytes(n));
@@ -509,6 +564,8 @@ struct FastTail {
       }
       MMF_TRY(t_order.stop(s));
     }
+    const bool symmetric = sym_try && !fo.perm && fo.n_panels == 0;
+    const CandLists L = view(symmetric);   // (shadows the member: the lists as this call's path uses them)
     MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
     MMF_HIP(hipMemsetAsync(fail_count, 0, 16, s));
     MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
@@ -521,7 +578,10 @@ struct FastTail {
     ScanB16Panel pn;
     pn.seed = seed; pn.seed_stride = n_seed;
     pn.share = (splits > 1 || fo.n_panels > 1) ? 1 : 0;
-    if (fo.n_panels == 0) {
+    if (symmetric) {
+      MMF_TRY(launch_scan_b16_sym(fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, r.d, fo.f16, r.metric, kk, sym_G, L, scan_scratch,
+                                  sym, sym_tab, pn, s, &grid));
+    } else if (fo.n_panels == 0) {
       MMF_TRY(launch_scan_b16(fo.ZQ, fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, m, fo.m_pad_tiles, fo.dp, r.d, fo.f16,
                               r.metric, kk, splits, L, scan_scratch, pn, s, &grid));
     } else {
@@ -546,6 +606,19 @@ struct FastTail {
       if (f > 0) MMF_HIP(hipMemsetAsync(L.overflow, 1, (size_t)(f < n ? f : n) * 4, s));
     }
     MMF_TRY(t_scan.stop(s));
+    if (symmetric && getenv("MMF_SYMMETRIC_DEBUG")) {   // diagnosis: what the candidate direction carried
+      MMF_HIP(hipStreamSynchronize(s));
+      std::vector<uint32_t> hc((size_t)n), hl((size_t)sym_grid() * 8);
+      uint32_t none = 0;
+      MMF_HIP(hipMemcpy(hc.data(), sym_cnt, hc.size() * 4, hipMemcpyDeviceToHost));
+      MMF_HIP(hipMemcpy(hl.data(), sym.log_cnt, hl.size() * 4, hipMemcpyDeviceToHost));
+      MMF_HIP(hipMemcpy(&none, sym.none_cnt, 4, hipMemcpyDeviceToHost));
+      unsigned long long tot = 0; uint32_t mx = 0, lmx = 0;
+      for (uint32_t v : hc) { tot += v; if (v > mx) mx = v; }
+      for (uint32_t v : hl) if (v > lmx) lmx = v;
+      fprintf(stderr, "[mmf symmetric] G %d grid %lld: rows without a threshold %u, received entries %llu (%.1f per row, largest %u of %d), fullest wave log %u of %d\n",
+              sym_G, (long long)sym_grid(), none, tot, (double)tot / (double)n, mx, kSymCap, lmx, kSymLogPerWave);
+    }
     // the f32 rows are first touched here: a caller that is still receiving them (overlapped
     // all-gather) hands in the event that marks their arrival
     if (select_wait_event) MMF_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(select_wait_event), 0));
@@ -602,7 +675,7 @@ struct FastTail {
       MMF_TRY(ex.run(aux, XL));
     }
     MMF_TRY(t_fb.stop(s));
-    fill_stats(r.stats, r.precision, splits, grid, 0.f, t_scan.ms(), t_sel.ms(), t_fb.ms(), h_fail, h_fail4[1], h_fail4[2], h_tot,
+    fill_stats(r.stats, r.precision, symmetric ? 1 : splits, grid, 0.f, t_scan.ms(), t_sel.ms(), t_fb.ms(), h_fail, h_fail4[1], h_fail4[2], h_tot,
                near_rows);
     if (r.stats) {
       if (profile && fo.n_panels > 0) {     // what the scan stream spent waiting for panels to arrive
@@ -626,6 +699,15 @@ extern "C" {
 
 int mmf_version(void) { return MMF_ABI_VERSION; }
 int mmf_debug_query_order(int32_t* perm_host, int64_t n) { return query_order_last(perm_host, n); }
+int64_t mmf_debug_symmetric_schedule(int64_t row_blocks, int group, int launch, int32_t* table_host, int64_t capacity) {
+  if (row_blocks < 1 || group < 1 || launch < 0 || launch > 1) { set_error("debug_symmetric_schedule: bad argument"); return MMF_E_INVALID; }
+  const int64_t grid = sym_schedule_grid(row_blocks, group);
+  if (table_host) {
+    if (capacity < grid) { set_error("debug_symmetric_schedule: table of %lld entries needed", (long long)grid); return MMF_E_INVALID; }
+    sym_schedule_table(row_blocks, group, launch, table_host);
+  }
+  return grid;
+}
 const char* mmf_last_error(void) { return g_err; }
 
 int mmf_release_workspaces(void) {
@@ -678,6 +760,10 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
     const int64_t n_pad = (n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256 + (slice0 >= 0 ? 256 : 0);
     FastTail ft(n, m, r.kk, forced_splits, dp);
     MMF_TRY(ft.set_query_order(opts ? opts->query_order : MMF_QUERY_ORDER_AUTO));
+    {
+      int G = 0;
+      if (symmetric_scan_wanted(n, dp, ft.bcap, metric, forced_splits, same && row_offset == col_offset, &G)) ft.set_symmetric(G);
+    }
     size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + ws_bytes((size_t)n_pad * dp, 2) + ws_bytes((size_t)m_pad * dp, 2) +
                   4 * ws_bytes(n_pad, 4) + 4 * ws_bytes(m_pad, 4) + 3 * ws_bytes(4, 4) + ft.bytes();
     Workspace ws;

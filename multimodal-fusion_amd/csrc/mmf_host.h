@@ -100,6 +100,37 @@ struct CandLists {
   uint32_t* spill_ids = nullptr;   // [n][spill_cap], GLOBAL-mapped local column ids like `ids`
   int spill_cap = 0;
   int spill_stacks = 0;            // lists == 2: the row's two lanes fill its slots from both ends; spill_cnt[row] = front | back << 16
+  // symmetric 16-bit scan only (else nullptr): the columns a row received from the scans of OTHER rows (launch_scan_b16_sym),
+  // with their approximate keys (no slot bits) — select treats them as one more list
+  uint32_t* sym_cnt = nullptr;     // [n] entries offered (may pass sym_cap: the row is then flagged for the exact rescan)
+  uint32_t* sym_ids = nullptr;     // [n][sym_cap]
+  float* sym_keys = nullptr;       // [n][sym_cap]
+  int sym_cap = 0;
+};
+
+// mmf_scan_bf16.hip: the symmetric schedule of a scan of X against itself.  nb row blocks of 256 rows in
+// nb / G super-blocks of G (the last one also takes the nb % G left-over row blocks); launch 0 does the plain pairs (own and, for an even count, antipodal super-block), launch 1 the
+// symmetric ones.  The table has sym_schedule_grid() entries of 8 ints: row block (-1: idle), first tile and tile count of
+// two column ranges.
+int64_t sym_schedule_grid(int64_t nb, int G);
+void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out);
+int sym_default_group(int64_t nb);
+constexpr int kSymCap = 512;            // entries per row of CandLists::sym_ids (1.66 x the largest count on the bench rows, bf16 leg)
+constexpr int kSymLogPerWave = 4096;    // entries of a wave's append log (32 rows: 128 per row; 1.73 x the fullest on the bench rows, bf16 leg)
+struct SymBuffers {
+  float* thr = nullptr;            // [n_pad]
+  uint32_t* log = nullptr;         // [grid * 8][kSymLogPerWave][4]
+  uint32_t* log_cnt = nullptr;     // [grid * 8]
+  int32_t* sched = nullptr;        // [2][grid][8]
+  uint32_t* none_cnt = nullptr;    // [4] real rows that reached the symmetric launch without a threshold
+  static size_t bytes(int64_t n_pad, int64_t grid) {
+    return ws_bytes(n_pad, 4) + ws_bytes((size_t)grid * 8 * kSymLogPerWave * 4, 4) + ws_bytes((size_t)grid * 8, 4) +
+           ws_bytes((size_t)grid * 16, 4) + ws_bytes(4, 4);
+  }
+  void carve(Workspace& ws, int64_t n_pad, int64_t grid) {
+    thr = ws.take<float>(n_pad); log = ws.take<uint32_t>((size_t)grid * 8 * kSymLogPerWave * 4);
+    log_cnt = ws.take<uint32_t>((size_t)grid * 8); sched = ws.take<int32_t>((size_t)grid * 16); none_cnt = ws.take<uint32_t>(4);
+  }
 };
 
 // Where a launch of the 16-bit scan sits inside a paneled scan (all zero: the whole problem in one launch).

@@ -18,6 +18,8 @@
 //     instead of zero, which costs nothing;
 //   * epilogue per tile: 14 v_max + 2 compares, reduced before the barrier, tested behind it; only a hit enters
 //     the lane-private list code (SlotList, mmf_dev.h).
+// X against itself (cosine / dot, d <= 512 padded to 512): launch_scan_b16_sym multiplies every pair of rows of different
+// super-blocks ONCE and serves both rows with the value (template flag SYM, DESIGN.md §4.1 "Symmetric scan").
 // Where the time goes (profiles/README.md, r02 ablations): the bare ds_read + MFMA chain alone runs at 0.60 of the
 // 2.5 PFLOP/s peak (matrix pipe 73 % busy at the 1.94 GHz the chip holds under this load); the tile DMA adds 6 %
 // (instruction issue, not traffic), the list code 10 %.
@@ -217,13 +219,24 @@ struct ScanB16Args {
   float* margin_out;         // [n_rows] the queries' error margins, written with cand_keys
   uint32_t* spill_cnt; uint32_t* spill_ids; int spill_cap;   // per-row overflow lists (SpillSink), or nullptr / 0
   int spill_stacks;          // one list pair per row: the two lanes fill the row's slots from both ends, no counter (SpillSink)
-  const int32_t* sched;      // SEG kernels only: [grid][SEG_ENTRY] work table (segmented calls, see launch_scan_b16_seg)
+  const int32_t* sched;      // SEG / SYM kernels only: [grid][SEG_ENTRY] work table (launch_scan_b16_seg, launch_scan_b16_sym)
+  // SYM == 2 (the symmetric launch of a scan of X against itself, launch_scan_b16_sym): a value G_ij that reaches the
+  // threshold of its CANDIDATE row j is appended to the wave's private log as (j, i, G); sym_scatter_kernel files the logs
+  // into the rows' lists afterwards
+  const float* sym_thr;      // [m_pad] threshold of every candidate row (sym_thr_kernel: seed[] decoded; +inf for padding rows)
+  uint32_t* sym_log;         // [grid * NW][sym_log_cap][4]
+  uint32_t* sym_log_cnt;     // [grid * NW] entries written (zeroed by the host; an idle workgroup writes nothing)
+  int sym_log_cap;
 };
 
 // Work table entry of a segmented scan (one per workgroup): the row block's first position in the segment-padded query
 // image, the list row (= row of X) of its first query, how many of its QT queries are real, its candidate tile range
 // in the segment-padded candidate image, and the id offset that turns an image column into a global row id of Y.
 enum { SEG_QPOS = 0, SEG_ROW0 = 1, SEG_NQ = 2, SEG_T0 = 3, SEG_T1 = 4, SEG_IDOFF = 5, SEG_ENTRY = 8 };
+// Work table entry of the symmetric schedule (sym_schedule_table; same entry size): the workgroup's row block (-1: idle) and
+// its columns — tiles [B1, B1 + N1) followed by [B2, B2 + N2) (a cyclic range that wraps, or own + antipodal super-block).
+// N1 and N2 are multiples of 8 tiles; N1 == 0 only when N2 == 0.
+enum { SYM_RB = 0, SYM_B1 = 1, SYM_N1 = 2, SYM_B2 = 3, SYM_N2 = 4 };
 
 // Order-preserving float <-> int32 map (an involution) so that thresholds can be merged with atomicMax.
 __device__ __forceinline__ int32_t seed_enc(float f) {
@@ -258,9 +271,17 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 // SEG (segmented calls): the workgroup's row block, column range and id offset come from the work table a.sched instead
 // of blockIdx / col_splits; one workgroup per row block (split 0), queries past the block's count are idle.  List rows
 // (lists, thresholds, margins, overflow lists) are rows of X, operand rows are positions of the padded query image.
-template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false>
+//
+// SYM (a scan of X against itself split into two launches, launch_scan_b16_sym; DESIGN.md §4.1 "Symmetric scan"): the row
+// block and its columns — two tile ranges walked as one — come from the work table a.sched.  SYM == 1 is otherwise the plain
+// kernel.  SYM == 2 serves both directions of every pair it multiplies: beside the query-side filter, each value is tested
+// against the threshold of its CANDIDATE row (32 floats per tile, DMAed into LDS with the tile's biases), and a value that
+// passes is appended to a log private to the wave — a ballot and a popcount place it: one store, no atomic, no returned value to
+// wait for (the store itself retires with the iteration's vmcnt(0), like the tile DMA).
+template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0>
 __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(ScanB16Args a) {
   static_assert(!SPLITK || (TPB == 1 && NW == 8 && (KS % 8) == 0), "split-k pairs");
+  static_assert(SYM == 0 || (!SPLITK && !SEG && !DBG && TPB == 2), "symmetric schedule: the d = 512 kernel only");
   constexpr int NQW = SPLITK ? NW / 2 : NW;     // waves that own queries and lists
   constexpr int NTL = 64 * NQW;                 // threads that own lists
   constexpr int QT = 32 * NQW;
@@ -279,6 +300,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   uint32_t* lids = a.lids + (size_t)blockIdx.x * (SlotList<CAP, NTL>::SLOTS * NTL);
   f32x4* xch = reinterpret_cast<f32x4*>(lkeys + CAP * NTL);          // SPLITK: [NQW][4][64] partial accumulators
   volatile int* ack = reinterpret_cast<volatile int*>(xch + NQW * 4 * 64);   // SPLITK: [NQW] last tile the lower wave took
+  // SYM == 2: behind the lists, [STAGES][32] thresholds of a tile's candidate rows (sym_thr_stage below)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -301,7 +323,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   int64_t t_begin, t_end, row0 = 0;
   int nq = 0;
   uint32_t id_off = a.id_off;
-  if constexpr (SEG) {
+  int sym_n1 = 0, sym_skip = 0;   // SYM: tiles of the first range, and how many tiles lie between its end and the second range's start
+  if constexpr (SYM != 0) {
+    const int32_t* e = a.sched + (size_t)blockIdx.x * SEG_ENTRY;
+    if (e[SYM_RB] < 0) return;
+    rb = e[SYM_RB]; split = 0;
+    t_begin = e[SYM_B1]; t_end = t_begin + e[SYM_N1] + e[SYM_N2];      // walked as one range of N1 + N2 tiles
+    sym_n1 = e[SYM_N1]; sym_skip = e[SYM_B2] - (e[SYM_B1] + e[SYM_N1]);
+  } else if constexpr (SEG) {
     const int32_t* e = a.sched + (size_t)blockIdx.x * SEG_ENTRY;
     rb = e[SEG_QPOS] / QT; row0 = e[SEG_ROW0]; nq = e[SEG_NQ];
     t_begin = e[SEG_T0]; t_end = e[SEG_T1]; id_off = (uint32_t)e[SEG_IDOFF];
@@ -411,8 +440,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
     const int src_chunk = (chunk & ~15) | ((chunk ^ r) & 15);
     src_off[i] = (uint32_t)(r * ROWB + src_chunk * 16);
   }
-  const char* zc0 = reinterpret_cast<const char*>(a.ZC) + t_begin * (int64_t)TILEB;          // tile 0 of my range
-  const char* cb0 = reinterpret_cast<const char*>(a.cb + t_begin * B_CT);
+  // (SYM: the second range may lie BELOW the first, so the buffers start at the image's first tile and zt0 / ct0 point at the
+  //  range's; the host has checked that the whole image stays inside the 32-bit offsets)
+  const char* zc0 = reinterpret_cast<const char*>(a.ZC) + (SYM != 0 ? 0 : t_begin * (int64_t)TILEB);          // tile 0 of my range
+  const char* cb0 = reinterpret_cast<const char*>(a.cb + (SYM != 0 ? 0 : t_begin * B_CT));
+  const char* zt0 = SYM != 0 ? zc0 + t_begin * (int64_t)TILEB : zc0;
+  const char* ct0 = SYM != 0 ? cb0 + t_begin * B_CT * 4 : cb0;
   // Tile pieces go through the buffer form of the LDS-DMA: the workgroup's column range is one raw buffer
   // (base = its first tile), the running tile position is the scalar offset and the lane's swizzled position
   // the vector offset — no per-piece 64-bit address arithmetic in the MFMA chain, and (unlike the FLAT-encoded
@@ -434,6 +467,15 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       __builtin_amdgcn_raw_ptr_buffer_load_lds(brsrc, (__attribute__((address_space(3))) void*)(cbs + stage * 64), 4, (int)(l * 4u),
                                                (int)(uint32_t)(bsrc - cb0), 0, 0);
   };
+  // SYM == 2: the thresholds of the same 32 rows, same form, same place in the iteration, issued by another wave
+  auto sym_thr_stage = [&](int stage) -> float* { return lkeys + CAP * NTL + stage * 32; };
+  auto issue_thr = [&](const char* bsrc, int stage) {
+    const __amdgpu_buffer_rsrc_t trsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sym_thr), 0, -1, 0x00020000);
+    const uint32_t l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    if (l < 32)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(trsrc, (__attribute__((address_space(3))) void*)sym_thr_stage(stage), 4, (int)(l * 4u),
+                                               (int)(uint32_t)(bsrc - cb0), 0, 0);
+  };
 
   if (SPLITK && tid < NQW) ack[tid] = -1;
   const int Ti = (int)T;
@@ -442,8 +484,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
     for (int u = 0; u < TPB; ++u) {
       const bool real = u < Ti;
 #pragma unroll
-      for (int i = 0; i < PPW; ++i) issue_piece(real ? zc0 + u * (int64_t)TILEB : zc0, u, i);
-      if (wave == (u & (NW - 1))) issue_bias(real ? cb0 + u * B_CT * 4 : cb0, u);
+      for (int i = 0; i < PPW; ++i) issue_piece(real ? zt0 + u * (int64_t)TILEB : zc0, u, i);
+      if (wave == (u & (NW - 1))) issue_bias(real ? ct0 + u * B_CT * 4 : cb0, u);
+      if constexpr (SYM == 2) { if (wave == ((u + 4) & (NW - 1))) issue_thr(real ? ct0 + u * B_CT * 4 : cb0, u); }
     }
   }
   // The DMA pieces of tile t+TPB are issued inside the MFMA chain of tile t, one per group of GRP MFMAs.  The
@@ -454,8 +497,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   constexpr int GRP = KS2 / PPW;                     // k-steps (4 MFMAs each) between two DMA pieces (issuing the SPLITK
                                                      // kernel's pieces in its first k-steps instead measured the same)
   static_assert(KS2 % PPW == 0 && GRP >= 1, "DMA piece placement");
-  const char* tsrc = zc0 + TPB * (int64_t)TILEB;     // source of the first tile of the NEXT group
-  const char* bsrc = cb0 + TPB * B_CT * 4;
+  const char* tsrc = zt0 + TPB * (int64_t)TILEB;     // source of the first tile of the NEXT group
+  const char* bsrc = ct0 + TPB * B_CT * 4;
   const uint32_t id_base = (uint32_t)(t_begin * B_CT);
 
   struct Acc { f32x4 t[2][2]; };                     // [candidate block][query block]
@@ -524,7 +567,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   // placed before the barrier it would hold all eight waves, and their matrix pipes, at the barrier.
   auto filter = [&](const Acc& acc, int tt, float m0, float m1) {
     if (__builtin_expect(!(DBG && (a.debug & 1)) && __any((m0 >= thr_q0) || (m1 >= thr_q1)), 0)) {
-      const uint32_t id0 = id_base + (uint32_t)tt * B_CT;
+      uint32_t id0 = id_base + (uint32_t)tt * B_CT;
+      if constexpr (SYM != 0) id0 += (tt >= sym_n1) ? (uint32_t)(sym_skip * B_CT) : 0u;   // behind the first range: sym_skip tiles further on
       // this lane's query gets its 16 candidates together: its own 8 plus the 8 the partner lane holds
       f32x16 v;
 #pragma unroll
@@ -570,6 +614,56 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
     }
     if (DBG && (a.debug & 8) && lane == 0) atomicAdd(a.dbg + 5, 1ull);   // tiles
     if (__builtin_expect(a.share && (tt & 63) == 63, 0)) { sync_seed(); refresh_thr(); }
+  };
+
+  // SYM == 2, the candidate direction: right behind a tile's chain (its stage of thresholds is not refilled before the next
+  // barrier), the lane's 16 values against the thresholds of their candidate rows — 8 v_max + 8 compares, two LDS reads.
+  // On a hit (one in three wave-tiles at N = 262144) every passing value goes to the wave's log: position = the wave's
+  // running count + the lane's rank in the ballot; a full log flags the candidate row for the exact rescan (audit_kernel).
+  uint32_t sym_wcnt = 0;
+  auto sym_offer = [&](const Acc& x, int tt, const float* th) {
+    const f32x4 th0 = *reinterpret_cast<const f32x4*>(th + 4 * g);
+    const f32x4 th1 = *reinterpret_cast<const f32x4*>(th + 16 + 4 * g);
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      any |= fmaxf(x.t[0][0][j], x.t[0][1][j]) >= th0[j];
+      any |= fmaxf(x.t[1][0][j], x.t[1][1][j]) >= th1[j];
+    }
+    if (__builtin_expect(__any(any), 0)) {
+      const uint32_t cj0 = id_base + (uint32_t)tt * B_CT + ((tt >= sym_n1) ? (uint32_t)(sym_skip * B_CT) : 0u) + 4u * (uint32_t)g;
+      const uint32_t qi0 = (uint32_t)(q0 + 32 * qw + c16);
+      const bool sym_qv0 = q0 + 32 * qw + c16 < a.n_rows, sym_qv1 = q0 + 32 * qw + c16 + 16 < a.n_rows;
+      uint32_t* lg = a.sym_log + ((size_t)blockIdx.x * NW + wave) * (size_t)a.sym_log_cap * 4;
+      const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t cj = cj0 + 16u * cb + j;
+          const float tj = cb ? th1[j] : th0[j];
+#pragma unroll
+          for (int qb = 0; qb < 2; ++qb) {
+            const float v = x.t[cb][qb][j];
+            const bool h = (v >= tj) && (qb ? sym_qv1 : sym_qv0) && ((int64_t)cj < a.n_rows);
+            const unsigned long long mask = __ballot(h);
+            if (mask) {
+              const uint32_t at = sym_wcnt + (uint32_t)__popcll(mask & below);
+              if (h) {
+                if (at < (uint32_t)a.sym_log_cap) {
+                  u32x4 ent;
+                  ent[0] = cj; ent[1] = qi0 + 16u * qb; ent[2] = __float_as_uint(v); ent[3] = 0u;
+                  *reinterpret_cast<u32x4*>(lg + (size_t)at * 4) = ent;
+                } else {
+                  atomicMax(a.lost + cj, 0x7fffffff);
+                }
+              }
+              sym_wcnt += (uint32_t)__popcll(mask);
+            }
+          }
+        }
+      }
+    }
   };
 
   // Main loop: TPB tiles per barrier.  Iteration j reads the group of stages holding tiles j*TPB ..
@@ -628,6 +722,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       acc = tile_body(tiles + (sg + u) * TILEB + kbyte, cbs + (sg + u) * 64, src, ng + u);
       // (behind the chain: issued in front of it, the same DMA costs +8 %; mid-chain needs a branch inside the chain)
       if (wave == ((t + TPB) & (NW - 1))) issue_bias(more ? bsrc + u * B_CT * 4 : cb0, ng + u);
+      if constexpr (SYM == 2) {
+        if (wave == ((t + TPB + 4) & (NW - 1))) issue_thr(more ? bsrc + u * B_CT * 4 : cb0, ng + u);
+        if (t < Ti) sym_offer(acc, t, sym_thr_stage(sg + u));
+      }
       if (u < TPB - 1) {
         if (TPB == 2 || __builtin_expect(t < Ti, 1))      // (TPB > 2: the ragged last group can hold several dummy tiles)
         filter(acc, t, max_qb(acc, 0), max_qb(acc, 1));   // mid-iteration, no barrier nearby
@@ -655,6 +753,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
     }
     tsrc += TPB * (int64_t)TILEB;
     bsrc += TPB * B_CT * 4;
+    if constexpr (SYM != 0) {   // the next group to fetch (tiles (j + 2) TPB ..) is the first of the second range: jump there
+      if ((j + 2) * TPB == sym_n1) { tsrc += sym_skip * (int64_t)TILEB; bsrc += sym_skip * (B_CT * 4); }
+    }
     if (stamps) {
       asm volatile("" :: "v"(acc_prev.t[0][0][0]));  // the chain's result must exist before the stamp
       t3s = __builtin_amdgcn_s_memtime();
@@ -685,6 +786,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
     if (qvalid && half == 0 && (mine | theirs)) a.spill_cnt[qpos] = mine | (theirs << 16);
   }
   sync_seed();
+  if constexpr (SYM == 2) {
+    if (lane == 0) a.sym_log_cnt[(size_t)blockIdx.x * NW + wave] = sym_wcnt < (uint32_t)a.sym_log_cap ? sym_wcnt : (uint32_t)a.sym_log_cap;
+  }
   if (qvalid) {
     const int64_t lbase = qpos * a.lists_total + a.list_base + 2 * split + half;
     a.cand_cnt[lbase] = (uint32_t)list.cnt;
@@ -762,10 +866,10 @@ int launch_prep_half_gather(const void* X, int64_t n, int64_t d, int dtype, int 
   return MMF_OK;
 }
 
-static size_t scan_b16_lds(int ks, int nw, int tpb, int cap, bool splitk) {
+static size_t scan_b16_lds(int ks, int nw, int tpb, int cap, bool splitk, bool sym_thr = false) {
   const int nqw = splitk ? nw / 2 : nw;
   return (size_t)(2 * tpb) * (B_CT * ks * 32) + (size_t)(2 * tpb) * 64 * 4 + (size_t)cap * (64 * nqw) * 4 +
-         (splitk ? (size_t)nqw * 4 * 64 * 16 + 64 : 0);
+         (splitk ? (size_t)nqw * 4 * 64 * 16 + 64 : 0) + (sym_thr ? (size_t)(2 * tpb) * 32 * 4 : 0);
 }
 
 int scan_b16_queries_per_block(int dp) { return 32 * waves_for_dp(dp); }
@@ -946,6 +1050,143 @@ int launch_scan_b16_seg(const void* ZQ, const void* ZC, const float* cb, const f
     default: set_error("scan_b16_seg: unsupported padded dim %d", dp);
   }
   return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Symmetric scan of X against itself (cosine / dot, padded dim 512, 15-entry lists): DESIGN.md §4.1
+// ------------------------------------------------------------------------------------------------
+// Super-blocks of G row blocks (the last one takes the left-over row blocks too); ns of them.  Launch 0: every row block scans its own super-block and, when ns is even, the
+// antipodal one (plain: query direction only).  Launch 1: the super-blocks a + 1 .. a + (ns - 1) / 2 (cyclic), each pair of
+// rows multiplied once and served in both directions.  Every ordered (row, column) pair is covered exactly once.
+// Block ids: like the plain launch, blocks that share blockIdx % 8 share an XCD; the G row blocks of a super-block take one
+// XCD's block ids of one stretch of 8 G ids, so they run together and stream the same columns through that XCD's L2.
+int sym_default_group(int64_t nb) {
+  int64_t g = (nb + 31) / 32;                   // at most 32 super-blocks: launch 0 samples at least 1/16 of the columns
+  return (int)(g < 32 ? 32 : g);                // at least one XCD's worth of workgroups (32 CUs)
+}
+// ns = nb / G super-blocks; the row blocks left over join the LAST one (G .. 2 G - 1 row blocks), so no super-block is
+// short: a short one would give its rows thresholds from a handful of columns in launch 0 and flood their received lists.
+static int64_t sym_super_blocks(int64_t nb, int G) { const int64_t ns = nb / G; return ns < 1 ? 1 : ns; }
+int64_t sym_schedule_grid(int64_t nb, int G) {
+  const int64_t ns = sym_super_blocks(nb, G);
+  return ((ns + 7) / 8 + (nb > ns * G ? 1 : 0)) * 8 * G;      // the left-over row blocks take a stretch of block ids of their own
+}
+void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out) {
+  const int64_t ns = sym_super_blocks(nb, G), grid = sym_schedule_grid(nb, G), tiles = nb * 8;
+  const int64_t per = 8 * (int64_t)G, stretches = (ns + 7) / 8;
+  auto first_tile = [&](int64_t sb) { return sb * G * 8; };
+  auto end_tile = [&](int64_t sb) { return sb == ns - 1 ? tiles : (sb + 1) * G * 8; };
+  for (int64_t b = 0; b < grid; ++b) {
+    int32_t* e = out + b * SEG_ENTRY;
+    for (int i = 0; i < SEG_ENTRY; ++i) e[i] = 0;
+    e[SYM_RB] = -1;
+    int64_t sb = (b / per) * 8 + (b % 8), rbi = sb * G + (b % per) / 8;
+    if (b / per >= stretches) {                  // the extra stretch: left-over row blocks, on the XCD of the last super-block
+      if (b % 8 != (ns - 1) % 8) continue;
+      sb = ns - 1; rbi = ns * G + (b % per) / 8;
+    } else if (sb >= ns) continue;
+    if (rbi >= nb) continue;
+    int64_t b1 = 0, n1 = 0, b2 = 0, n2 = 0;
+    if (launch == 0) {
+      b1 = first_tile(sb); n1 = end_tile(sb) - b1;
+      if (ns >= 2 && (ns % 2) == 0) { const int64_t o = (sb + ns / 2) % ns; b2 = first_tile(o); n2 = end_tile(o) - b2; }
+    } else {
+      const int64_t h = (ns - 1) / 2;
+      if (h == 0) continue;
+      int64_t lo = sb + 1, hi = sb + h;           // super-blocks lo .. hi, cyclic
+      if (lo >= ns) { lo -= ns; hi -= ns; }
+      if (hi < ns) { b1 = first_tile(lo); n1 = end_tile(hi) - b1; }
+      else { b1 = first_tile(lo); n1 = end_tile(ns - 1) - b1; b2 = 0; n2 = end_tile(hi - ns); }
+    }
+    if (n2 == 0) b2 = b1 + n1;
+    e[SYM_RB] = (int32_t)rbi; e[SYM_B1] = (int32_t)b1; e[SYM_N1] = (int32_t)n1; e[SYM_B2] = (int32_t)b2; e[SYM_N2] = (int32_t)n2;
+  }
+}
+
+// thresholds of the candidate rows for the symmetric launch: seed[] (launch 0's proven thresholds) decoded once.  A real row
+// without one accepts everything (and is counted: it does not happen once launch 0 has seen k + self columns of the row);
+// padding rows accept nothing.
+__global__ void sym_thr_kernel(const int32_t* seed, float* thr, int64_t n, int64_t n_pad, uint32_t* none_cnt) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_pad) return;
+  if (i >= n) { thr[i] = __builtin_huge_valf(); return; }
+  const int32_t o = seed[i];
+  if (o > kSeedNone) { thr[i] = __int_as_float(o >= 0 ? o : (o ^ 0x7fffffff)); return; }
+  thr[i] = -kFltMax;
+  atomicAdd(none_cnt, 1u);
+}
+
+// files the waves' logs into the rows' lists: one workgroup per log.  An entry that finds its row's list full flags the row.
+__global__ __launch_bounds__(256) void sym_scatter_kernel(const uint32_t* log, const uint32_t* log_cnt, int log_cap, uint32_t* sym_cnt,
+                                                          uint32_t* sym_ids, float* sym_keys, int cap, int32_t* lost) {
+  const uint32_t c = log_cnt[blockIdx.x];
+  const u32x4* lg = reinterpret_cast<const u32x4*>(log) + (size_t)blockIdx.x * log_cap;
+  for (uint32_t e = threadIdx.x; e < c; e += 256) {
+    const u32x4 v = lg[e];
+    const uint32_t slot = atomicAdd(sym_cnt + v[0], 1u);
+    if (slot < (uint32_t)cap) {
+      sym_ids[(size_t)v[0] * cap + slot] = v[1];
+      sym_keys[(size_t)v[0] * cap + slot] = __uint_as_float(v[2]);
+    } else {
+      atomicMax(lost + v[0], 0x7fffffff);
+    }
+  }
+}
+
+size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G) {
+  const int64_t nb = (n_rows + 255) / 256;
+  return (size_t)sym_schedule_grid(nb, G) * 16 * 512 * 4 + 256;
+}
+
+// Both launches, the threshold image between them and the filing of the logs behind them, on stream s.  ZC is the operand
+// image of all rows (queries and candidates), n_pad / 32 tiles.  L has four lists per row (a pair per launch), keys, margins
+// and the sym_* lists; pn.seed as for launch_scan_b16.  tab: host storage of the work tables, which must outlive the upload
+// (until the caller's next synchronisation of s).  *grid_out: the sum of the two grids.
+int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const float* rn, const float* un, const uint32_t* maxima,
+                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, const CandLists& L, void* scratch,
+                        const SymBuffers& sb, std::vector<int32_t>& tab, const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
+  const int64_t nb = (n + 255) / 256, n_pad = nb * 256, grid = sym_schedule_grid(nb, G);
+  if (L.lists != 4 || L.cap != B_CAP || !L.keys || !L.margin || !L.sym_cnt || !pn.seed) { set_error("scan_b16_sym: lists missing"); return MMF_E_INTERNAL; }
+  if (n_pad * 1024 >= (int64_t(1) << 32)) { set_error("scan_b16_sym: operand image beyond the 32-bit tile offsets"); return MMF_E_INTERNAL; }
+  tab.resize((size_t)grid * 2 * SEG_ENTRY);   // the caller keeps it until the call's stream synchronisation
+  sym_schedule_table(nb, G, 0, tab.data());
+  sym_schedule_table(nb, G, 1, tab.data() + (size_t)grid * SEG_ENTRY);
+  MMF_HIP(hipMemcpyAsync(sb.sched, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+  MMF_HIP(hipMemsetAsync(L.sym_cnt, 0, (size_t)n * 4, s));
+  MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * L.lists * 4, s));   // with one or two super-blocks the second launch has no work and writes no list
+  MMF_HIP(hipMemsetAsync(sb.log_cnt, 0, (size_t)grid * 8 * 4, s));
+  MMF_HIP(hipMemsetAsync(sb.none_cnt, 0, 16, s));
+  ScanB16Args a{};
+  a.ZQ = ZC; a.ZC = ZC; a.cb = cb; a.q_zn = zn; a.q_rn = rn; a.q_un = un; a.maxima = maxima;
+  a.n_rows = n; a.m = n; a.tiles_total = n_pad / B_CT; a.tiles_per_split = 0;
+  a.row_blocks = nb; a.col_splits = 1; a.conc_splits = 1; a.blocks_per_round = 0;
+  a.kk = kk; a.metric = metric; a.d = (int)d;
+  a.lists_total = L.lists; a.list_base = 0;
+  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride; a.share = 0;
+  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow; a.cand_keys = L.keys; a.margin_out = L.margin;
+  a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap; a.spill_stacks = 0;
+  a.lids = reinterpret_cast<uint32_t*>(scratch);
+  a.sched = sb.sched;
+  a.sym_thr = sb.thr; a.sym_log = sb.log; a.sym_log_cnt = sb.log_cnt; a.sym_log_cap = kSymLogPerWave;
+  auto go = [&](auto kern, size_t lds) -> int {
+    MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, a);
+    MMF_LAUNCH_CHECK();
+    return MMF_OK;
+  };
+  const size_t lds_a = scan_b16_lds(32, 8, 2, B_CAP, false), lds_b = scan_b16_lds(32, 8, 2, B_CAP, false, true);
+  if (f16) MMF_TRY(go(scan_b16x_kernel<32, true, false, 8, 2, B_CAP, false, false, 1>, lds_a));
+  else MMF_TRY(go(scan_b16x_kernel<32, false, false, 8, 2, B_CAP, false, false, 1>, lds_a));
+  hipLaunchKernelGGL(sym_thr_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, pn.seed, sb.thr, n, n_pad, sb.none_cnt);
+  MMF_LAUNCH_CHECK();
+  a.sched = sb.sched + (size_t)grid * SEG_ENTRY; a.list_base = 2; a.share = 1;
+  if (f16) MMF_TRY(go(scan_b16x_kernel<32, true, false, 8, 2, B_CAP, false, false, 2>, lds_b));
+  else MMF_TRY(go(scan_b16x_kernel<32, false, false, 8, 2, B_CAP, false, false, 2>, lds_b));
+  hipLaunchKernelGGL(sym_scatter_kernel, dim3((unsigned)(grid * 8)), dim3(256), 0, s, sb.log, sb.log_cnt, kSymLogPerWave, L.sym_cnt,
+                     L.sym_ids, L.sym_keys, L.sym_cap, pn.seed + pn.seed_stride);
+  MMF_LAUNCH_CHECK();
+  if (grid_out) *grid_out = (int)(2 * grid);
+  return MMF_OK;
 }
 
 }  // namespace mmf

@@ -29,6 +29,8 @@ struct SelectArgs {
   int slot_ulp;                                     // ... which carry this many ulps of id-slot bits
   const uint32_t* spill_cnt; const uint32_t* spill_ids; int spill_cap;   // optional: the row's overflow list
   int spill_stacks;                                 // its two-stack form: spill_cnt[row] = front | back << 16 (SpillSink)
+  const uint32_t* sym_cnt; const uint32_t* sym_ids; const float* sym_keys; int sym_cap;   // optional (symmetric scan): one more list per row,
+                                                    // with keys — the columns the row received from the scans of other rows
   // staged kernel, two passes when overflow lists exist: pass 0 handles the rows without overflow entries in a lean
   // LDS footprint and queues the others; pass 1 (room for the overflow entries) takes the queue
   int pass; int two_pass;
@@ -145,6 +147,16 @@ __device__ __forceinline__ int gather_candidates(const SelectArgs& a, int64_t po
       if (prune) key[total + e] = a.cand_keys[base + e];
     }
     total += (int)cn;
+  }
+  if (a.sym_cnt) {   // symmetric scan: the entries other rows' scans sent to this row, ids and keys — pruned with the lists
+    const uint32_t c = a.sym_cnt[pos];
+    const int cn = (int)(c < (uint32_t)a.sym_cap ? c : (uint32_t)a.sym_cap);   // (beyond the capacity: the row is flagged, not read)
+    if (total + cn > maxc) return -1;
+    for (int e = lane; e < cn; e += 64) {
+      id[total + e] = a.sym_ids[pos * a.sym_cap + e];
+      if (prune) key[total + e] = a.sym_keys[pos * a.sym_cap + e];
+    }
+    total += cn;
   }
   // the row's overflow list (columns the lane lists had no room for): appended after the pruning below, which
   // works on approximate keys these entries do not carry
@@ -668,7 +680,7 @@ __global__ __launch_bounds__(64 * GR_W) void rerank_group_kernel(SelectArgs a) {
     if (pos < 0) continue;
     int total = -1;
     if (a.overflow[pos] == 0) {
-      if (a.lists * a.cap + a.spill_cap <= GR_MAXC) {
+      if (a.lists * a.cap + a.sym_cap + a.spill_cap <= GR_MAXC) {
         total = gather_candidates(a, pos, lane, L.cid[q], &L.dots[0][0] + q * GR_MAXC, GR_MAXC);
       } else {
         // many lists per row (paneled scans: one list pair per panel): the RAW entries can exceed what a row keeps here although the
@@ -897,7 +909,7 @@ static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* 
       b.pass = pass;
       if (!two) b.two_pass = 0;
       const int extra = (two && pass == 0) ? 0 : a.spill_cap;
-      b.maxc = ((a.lists * a.cap + extra + 63) / 64) * 64;
+      b.maxc = ((a.lists * a.cap + a.sym_cap + extra + 63) / 64) * 64;
       int sg = (extra == 0) ? 8 : 32;       // rows with overflow entries carry many candidates
       if (extra != 0) if (const char* e = getenv("MMF_SELECT_SG")) { const int v = atoi(e); if (v == 16 || v == 32) sg = v; }
       auto kern = a.dtype == MMF_F32 ? select_staged_kernel<METRIC, MMF_F32, 8>
@@ -980,7 +992,8 @@ size_t select_order_bytes(int64_t n) {
 
 int launch_select(const SelectProblem& p, const CandLists& L, hipStream_t s) {
   if (p.n_rows <= 0) return MMF_OK;
-  if ((int64_t)L.lists * L.cap + L.spill_cap > SEL_MAXC) {
+  const int sym_cap = L.sym_cnt ? L.sym_cap : 0;
+  if ((int64_t)L.lists * L.cap + sym_cap + L.spill_cap > SEL_MAXC) {
     set_error("select: %d lists x %d entries (+ %d overflow slots) exceed the per-row capacity %d", L.lists, L.cap, L.spill_cap, SEL_MAXC);
     return MMF_E_INTERNAL;
   }
@@ -996,6 +1009,7 @@ int launch_select(const SelectProblem& p, const CandLists& L, hipStream_t s) {
   a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow; a.lists = L.lists; a.cap = L.cap;
   a.cand_keys = L.keys; a.margin = L.margin; a.slot_ulp = L.slot_ulp;
   a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap; a.spill_stacks = L.spill_stacks;
+  a.sym_cnt = L.sym_cnt; a.sym_ids = L.sym_ids; a.sym_keys = L.sym_keys; a.sym_cap = sym_cap;
   a.pass = 0; a.two_pass = p.two_pass ? 1 : 0;
   void* order_temp = nullptr;
   size_t order_temp_bytes = 0;
