@@ -13,7 +13,9 @@
  *   - All pointers are raw DEVICE addresses (tensor.data_ptr()) unless a parameter says host.
  *   - Matrices are row-major and contiguous.  Indices are int64, scores are f32.
  *   - Every call enqueues on `hip_stream` (a hipStream_t, NULL = default stream) of device
- *     `device_id`.  Calls are asynchronous w.r.t. the host except where noted.
+ *     `device_id`.  Calls are asynchronous w.r.t. the host except where noted: INTEGRATION.md §6,
+ *     "Host synchronisations and host arguments", lists for every entry how often it waits for
+ *     the stream and how long its host arguments must stay valid (until the call returns).
  *   - Return value: MMF_OK (0) or a negative MMF_E_* code.  Never throws, never aborts;
  *     mmf_last_error() gives the message of the calling thread's last failure.
  *   - There is NO CPU implementation behind this ABI.  device_id < 0 is rejected with
@@ -378,7 +380,9 @@ int mmf_combined_threshold_edges(const float* F, const float* P, int64_t n, int6
  * (ptr_host: HOST int64 offsets [n_seg + 1], 0 .. n, non-decreasing), n_s = ptr[s+1] - ptr[s].  Its block K_s ([n_s, n_s] f32,
  * row-major) sits at kptr[s] = sum_{t<s} n_t^2 of one flat buffer.  Each entry returns, segment by segment, the bits of its
  * plain counterpart on the segment's slice; offsets and sizes are checked on the host before any device work
- * (MMF_E_INVALID names the segment), device_id < 0 -> MMF_E_UNSUPPORTED, n < 2^31.
+ * (MMF_E_INVALID names the segment), device_id < 0 -> MMF_E_UNSUPPORTED, n < 2^31.  None of the four synchronises, whatever
+ * n_seg: ptr_host and the tables built from it are staged in pinned memory of the library's at call time, so ptr_host may be
+ * freed as soon as the call returns.
  *   mmf_sim_dense_combined_segmented:   out [sum n_s^2] = the blocks mmf_sim_dense_combined(F_s, P_s) — compute_combined_similarity
  *                                       per slide, build_hypergraph/similarity_kernel.py:88-124, 171.  One scan launch.
  *   mmf_offdiag_lower_median_segmented: out_median (device f32 [n_seg]) = mmf_offdiag_lower_median of every block K (the
@@ -493,8 +497,8 @@ int mmf_knn_pairs(const int64_t* nbr, int64_t n, int k, const int64_t* labels,
  *           row_offsets[ptr[s]]; *out_count (device) = the number of edges, or -1 when a label lies outside its range.
  *   _fill   edge_index [2, capacity]: lo in row 0, hi in row 1.  capacity = the count read back by the caller (the one host
  *           read of the pair); capacity < 0 returns MMF_E_INVALID (the out-of-range label), so the flag needs no read of its own.
- * No limit on the clusters beyond n_seg * n_clusters < 2^31; n < 2^31.  Neither entry allocates (beyond the cached workspace) or
- * synchronises.
+ * No limit on the clusters beyond n_seg * n_clusters < 2^31; n < 2^31.  Neither entry allocates (beyond the cached workspace and
+ * the pinned block ptr_host is staged in) or synchronises; ptr_host may be freed as soon as the call returns.
  */
 int mmf_knn_clique_edges_count(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t n_clusters,
                                const int64_t* ptr_host, int64_t n_seg, uint64_t* row_offsets, int64_t* edge_ptr,

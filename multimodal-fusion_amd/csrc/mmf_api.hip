@@ -56,6 +56,45 @@ static int get_workspace_slot(int device, hipStream_t stream, int slot, size_t b
 }
 int get_workspace(int device, hipStream_t stream, size_t bytes, Workspace* out) { return get_workspace_slot(device, stream, 0, bytes, out); }
 
+struct StageBlock { char* host = nullptr; size_t cap = 0; hipEvent_t passed = nullptr; bool in_flight = false; };
+static std::map<std::pair<int, hipStream_t>, std::vector<StageBlock>> g_stage;
+
+int upload_table(hipStream_t s, void* dst, const void* src_host, size_t bytes) {
+  if (bytes == 0) return MMF_OK;
+  int device = 0;
+  MMF_HIP(hipGetDevice(&device));
+  std::lock_guard<std::mutex> lk(g_ws_mu);
+  std::vector<StageBlock>& blocks = g_stage[std::make_pair(device, s)];
+  StageBlock* b = nullptr;
+  for (StageBlock& c : blocks) {
+    if (c.cap < bytes) continue;
+    if (c.in_flight) {
+      const hipError_t q = hipEventQuery(c.passed);
+      if (q != hipSuccess) { (void)hipGetLastError(); continue; }      // hipErrorNotReady is not a failure of a later launch
+      c.in_flight = false;
+    }
+    b = &c;
+    break;
+  }
+  if (!b) {                                                              // nothing free: the stream is busy, take a new block, never wait
+    StageBlock nb;
+    nb.cap = (std::max(bytes, (size_t)1 << 16) + 4095) & ~size_t(4095);
+    void* h = nullptr;
+    hipError_t rc = hipHostMalloc(&h, nb.cap, hipHostMallocDefault);
+    if (rc != hipSuccess) { set_error("pinned staging of %zu bytes failed: %s", nb.cap, hipGetErrorString(rc)); return MMF_E_NOMEM; }
+    nb.host = static_cast<char*>(h);
+    rc = hipEventCreateWithFlags(&nb.passed, hipEventDisableTiming);
+    if (rc != hipSuccess) { (void)hipHostFree(h); set_error("hipEventCreate failed: %s", hipGetErrorString(rc)); return MMF_E_HIP; }
+    blocks.push_back(nb);
+    b = &blocks.back();
+  }
+  memcpy(b->host, src_host, bytes);
+  MMF_HIP(hipMemcpyAsync(dst, b->host, bytes, hipMemcpyHostToDevice, s));
+  MMF_HIP(hipEventRecord(b->passed, s));
+  b->in_flight = true;
+  return MMF_OK;
+}
+
 int launch_edge_cosine_impl(const void* X, int64_t d, int dtype, const float* nrm, const int64_t* ei, int64_t E,
                             float* out, hipStream_t s);
 
@@ -726,6 +765,18 @@ int mmf_release_workspaces(void) {
     }
     slot.clear();
   }
+  for (auto& kv : g_stage) {                      // the pinned staging blocks of upload_table, once their device is idle
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(kv.first.first);
+    (void)hipDeviceSynchronize();
+    for (StageBlock& b : kv.second) {
+      (void)hipEventDestroy(b.passed);
+      (void)hipHostFree(b.host);
+    }
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+  g_stage.clear();
   return MMF_OK;
 }
 
@@ -1684,7 +1735,7 @@ int mmf_sim_dense_combined_segmented(const float* F, const float* P, int64_t n, 
   float* nf = ws.take<float>(n);
   float* Fp = reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(n, d)));
   int64_t* d_tab = ws.take<int64_t>(tab.size());
-  MMF_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+  MMF_TRY(upload_table(s, d_tab, tab.data(), tab.size() * 8));
   MMF_TRY(launch_row_scalars(F, n, d, MMF_F32, MMF_RBF, nf, nullptr, s));
   MMF_TRY(launch_prep_f32(F, n, d, MMF_F32, nullptr, Fp, s));
   return launch_sim_dense_combined_seg(Fp, P, d, dp, lambda_h, lambda_g, nf, d_tab, grid, out, s);
@@ -1726,8 +1777,8 @@ int mmf_threshold_edges_segmented_count(const float* K, const int64_t* ptr_host,
   int64_t* d_ptr = ws.take<int64_t>((size_t)n_seg + 1);
   int64_t* d_kptr = ws.take<int64_t>((size_t)n_seg + 1);
   uint32_t* row_cnt = ws.take<uint32_t>((size_t)n);
-  MMF_HIP(hipMemcpyAsync(d_ptr, ptr_host, (size_t)(n_seg + 1) * 8, hipMemcpyHostToDevice, s));
-  MMF_HIP(hipMemcpyAsync(d_kptr, kptr.data(), (size_t)(n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+  MMF_TRY(upload_table(s, d_ptr, ptr_host, (size_t)(n_seg + 1) * 8));
+  MMF_TRY(upload_table(s, d_kptr, kptr.data(), (size_t)(n_seg + 1) * 8));
   return launch_threshold_count_seg(K, d_ptr, d_kptr, n_seg, n, thresholds, reinterpret_cast<unsigned long long*>(row_offsets), out_count,
                                     row_cnt, s);
 }
@@ -1748,8 +1799,8 @@ int mmf_threshold_edges_segmented_fill(const float* K, const int64_t* ptr_host, 
   MMF_TRY(get_workspace(device_id, s, 2 * ws_bytes((size_t)n_seg + 1, 8), &ws));
   int64_t* d_ptr = ws.take<int64_t>((size_t)n_seg + 1);
   int64_t* d_kptr = ws.take<int64_t>((size_t)n_seg + 1);
-  MMF_HIP(hipMemcpyAsync(d_ptr, ptr_host, (size_t)(n_seg + 1) * 8, hipMemcpyHostToDevice, s));
-  MMF_HIP(hipMemcpyAsync(d_kptr, kptr.data(), (size_t)(n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+  MMF_TRY(upload_table(s, d_ptr, ptr_host, (size_t)(n_seg + 1) * 8));
+  MMF_TRY(upload_table(s, d_kptr, kptr.data(), (size_t)(n_seg + 1) * 8));
   return launch_threshold_fill_seg(K, d_ptr, d_kptr, n_seg, n, thresholds, reinterpret_cast<const unsigned long long*>(row_offsets),
                                    edge_index, edge_w, capacity, s);
 }

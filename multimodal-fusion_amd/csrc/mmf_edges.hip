@@ -926,10 +926,10 @@ int launch_offdiag_lower_median_seg(const float* K, const int64_t* ptr, int64_t 
   int64_t* d_tab = reinterpret_cast<int64_t*>(p);
   p += ws_bytes(plan.tab.size(), 8);
   unsigned long long* hist = reinterpret_cast<unsigned long long*>(p);
-  MMF_HIP(hipMemcpyAsync(head, plan.heads.data(), (size_t)S * sizeof(SegMedianHead), hipMemcpyHostToDevice, s));
-  MMF_HIP(hipMemcpyAsync(d_ptr, ptr, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, s));
-  MMF_HIP(hipMemcpyAsync(d_kptr, plan.kptr.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, s));
-  MMF_HIP(hipMemcpyAsync(d_tab, plan.tab.data(), plan.tab.size() * 8, hipMemcpyHostToDevice, s));
+  MMF_TRY(upload_table(s, head, plan.heads.data(), (size_t)S * sizeof(SegMedianHead)));      // the plan dies with this call
+  MMF_TRY(upload_table(s, d_ptr, ptr, (size_t)(S + 1) * 8));
+  MMF_TRY(upload_table(s, d_kptr, plan.kptr.data(), (size_t)(S + 1) * 8));
+  MMF_TRY(upload_table(s, d_tab, plan.tab.data(), plan.tab.size() * 8));
   MMF_HIP(hipMemsetAsync(hist, 0, plan.hist_words * 8, s));
   const int64_t grid = plan.entries();
   for (int pass = 0; pass < 4; ++pass) {

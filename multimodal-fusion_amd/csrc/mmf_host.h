@@ -59,6 +59,14 @@ inline size_t ws_bytes(size_t count, size_t elem) { return (count * elem + 255) 
 // when it has to grow.
 int get_workspace(int device, hipStream_t stream, size_t bytes, Workspace* out);
 
+// A host table (the caller's ptr_host, a local std::vector) on its way to the device, for entries that return without
+// synchronising: the bytes are copied AT CALL TIME into pinned memory that the library owns, and the copy to `dst` is
+// enqueued on `s` from there.  The caller's memory may die as soon as the call returns, and the call never waits for the
+// stream (hipMemcpyAsync out of pageable memory does, from tables of about 1 MiB on: tests/test_gpu_stream_contract.py).
+// The pinned blocks are kept per (current device, stream), each guarded by an event recorded behind its copy, and are
+// handed out again once the stream has passed that event; mmf_release_workspaces frees them.
+int upload_table(hipStream_t s, void* dst, const void* src_host, size_t bytes);
+
 struct DeviceGuard {
   int prev = -1;
   bool ok = false;

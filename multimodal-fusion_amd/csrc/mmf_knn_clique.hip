@@ -289,7 +289,7 @@ int kc_prepare(const int64_t* labels, int64_t n, int64_t H, const int64_t* ptr_h
   st->bsum = ws.take<unsigned long long>((size_t)((n + KC_SCAN - 1) / KC_SCAN) + 1);
   st->bad = ws.take<uint32_t>(1);
   st->gid = st->members = st->pos = st->ccur = nullptr;
-  MMF_HIP(hipMemcpyAsync(st->d_ptr, ptr_host, (size_t)(n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+  MMF_TRY(upload_table(s, st->d_ptr, ptr_host, (size_t)(n_seg + 1) * 8));
   MMF_HIP(hipMemsetAsync(st->cnt, 0, (size_t)n * 4, s));
   MMF_HIP(hipMemsetAsync(st->bad, 0, 4, s));
   if (!labels) return MMF_OK;
