@@ -405,6 +405,32 @@ int mmf_threshold_edges_segmented_fill(const float* K, const int64_t* ptr_host, 
                                        int device_id, void* hip_stream);
 
 /*
+ * The WSI x TMA similarity of every slide of a cohort, and the lower median of every block of a flat ragged array
+ * (DESIGN.md §4.11).  Additions to ABI version 3; neither entry synchronises, whatever n_seg: the *_host offsets and the tables
+ * built from them are staged in pinned memory of the library's at call time and may be freed as soon as the call returns
+ * ("Cohort entries").
+ *   mmf_sim_dense_stats_segmented: mmf_sim_dense_stats(MMF_RBF_DIRECT) per segment — compute_wsi_tma_similarity slide by slide,
+ *       build_hypergraph/preprocess_hypergraph.py:248-265.  Segment s pairs X[x_ptr[s]:x_ptr[s+1]] (n_s rows) with
+ *       Y[y_ptr[s]:y_ptr[s+1]] (m_s rows); x_ptr_host / y_ptr_host: HOST int64 [n_seg + 1], starting at 0, non-decreasing,
+ *       ending at n / m, every n_s >= 1 and m_s >= 1 (else MMF_E_INVALID naming the first bad segment, before any device work).
+ *       out: block s is [n_s, m_s] row-major at optr[s] = sum_{t<s} n_t m_t of one flat f32 buffer; out_stats: device double
+ *       [n_seg][5] = mean, unbiased std (NaN for a 1 x 1 block), min, max, lower median.  Block s and out_stats[s] are bit for bit
+ *       what mmf_sim_dense_stats(X_s, n_s, Y_s, m_s, ..., MMF_RBF_DIRECT, ..., out_s, ...) returns.  Any d, f32 / bf16 / f16.
+ *       Another metric, or out == NULL -> MMF_E_UNSUPPORTED; device_id < 0 -> MMF_E_UNSUPPORTED.
+ *   mmf_lower_median_segmented: out_median[s] (device f32 [n_seg]) = the element of rank (c_s - 1) / 2 of v[ptr[s]:ptr[s+1]],
+ *       c_s = ptr[s+1] - ptr[s] >= 1, in the total order of mmf_lower_median (torch.median's lower median) — the similarity
+ *       statistics above, and the edge-weight median filter of rebuild_hypergraph_from_similarity,
+ *       build_hypergraph/preprocess_hypergraph.py:885-897, for every slide of a cohort's edge list.  Four-pass radix select
+ *       with a select state per segment: a fixed number of launches for any n_seg.
+ */
+int mmf_sim_dense_stats_segmented(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype,
+                                  int metric, float lambda,
+                                  const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_seg,
+                                  float* out, double* out_stats, int device_id, void* hip_stream);
+int mmf_lower_median_segmented(const float* v, const int64_t* ptr_host, int64_t n_seg, float* out_median,
+                               int device_id, void* hip_stream);
+
+/*
  * Cluster-shaped steps around the similarity kernels: what the reference does with a vector
  * of KMeans labels in Python loops.  labels / order / offsets / counts / pairs are int64 device arrays (torch.long);
  * at most 16384 segments.

@@ -7,6 +7,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.ops.simtopk_segmented(..., ptr=/batch=)   the same per segment of a ragged batch (one graph per slide)
     mmf.weighted_hypergraph.*                     the median-threshold weighted hypergraph of every graph of a batch
     mmf.knn_kmeans_hypergraph.*                   the k-NN + KMeans hypergraph of every slide of a cohort (ordered edges, one host read)
+    mmf.wsi_tma_similarity.*                      WSI x TMA similarity + statistics, grouping and the median edge filter of every slide of a cohort
     mmf.build_hypergraph.*                        the reference's function names and signatures
     mmf.distributed.sharded_simtopk(...)          row-sharded multi-GPU driver (RCCL all-gather)
 """
@@ -14,6 +15,10 @@ from . import _lib, ops  # noqa: F401
 from .ops import (edge_cosine, offdiag_lower_median, sim_dense, sim_dense_combined, sim_dense_combined_segmented,  # noqa: F401
                   simtopk, simtopk_segmented, threshold_edges, topk_merge)
 from .knn_kmeans_hypergraph import build_hypergraph_knn_kmeans_segmented, knn_kmeans_edges_segmented  # noqa: F401
+from .wsi_tma_similarity import (compute_wsi_tma_similarity_segmented, filter_edges_by_median_segmented,  # noqa: F401
+                                 group_by_similarity_segmented, lower_median_segmented, sim_dense_stats_segmented, similarity_block)
 
 __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combined", "sim_dense_combined_segmented", "edge_cosine",
-           "topk_merge", "offdiag_lower_median", "threshold_edges", "knn_kmeans_edges_segmented", "build_hypergraph_knn_kmeans_segmented"]
+           "topk_merge", "offdiag_lower_median", "threshold_edges", "knn_kmeans_edges_segmented", "build_hypergraph_knn_kmeans_segmented",
+           "sim_dense_stats_segmented", "lower_median_segmented", "compute_wsi_tma_similarity_segmented", "similarity_block",
+           "group_by_similarity_segmented", "filter_edges_by_median_segmented"]

@@ -54,6 +54,10 @@ EXPORTS = ["mmf_version", "mmf_last_error", "mmf_simtopk", "mmf_simtopk_ex", "mm
            "mmf_threshold_edges_segmented_fill", "mmf_knn_clique_edges_count", "mmf_knn_clique_edges_fill", "mmf_release_workspaces", "mmf_debug_query_order",
            "mmf_debug_symmetric_schedule"]
 
+# The cohort entries (include/mmf_hg.h): additions to ABI version 3, bound like EXPORTS.  Their synchronisation
+# behaviour is INTEGRATION.md's table "Cohort entries", pinned by tests/test_wsi_tma_segmented_cpu.py.
+EXPORTS_COHORT = ["mmf_sim_dense_stats_segmented", "mmf_lower_median_segmented"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -108,7 +112,9 @@ def lib() -> ctypes.CDLL:
     L.mmf_threshold_edges_segmented_fill.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, ci, vp]
     L.mmf_knn_clique_edges_count.argtypes = [vp, i64, ci, vp, i64, vp, i64, vp, vp, vp, ci, vp]
     L.mmf_knn_clique_edges_fill.argtypes = [vp, i64, ci, vp, i64, vp, i64, vp, vp, i64, ci, vp]
-    for name in EXPORTS:
+    L.mmf_sim_dense_stats_segmented.argtypes = [vp, i64, vp, i64, i64, ci, ci, f32, vp, vp, i64, vp, vp, ci, vp]
+    L.mmf_lower_median_segmented.argtypes = [vp, vp, i64, vp, ci, vp]
+    for name in EXPORTS + EXPORTS_COHORT:
         fn = getattr(L, name)
         if name not in ("mmf_last_error", "mmf_padded_dim"):
             fn.restype = ci

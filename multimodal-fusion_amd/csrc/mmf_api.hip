@@ -1805,6 +1805,91 @@ int mmf_threshold_edges_segmented_fill(const float* K, const int64_t* ptr_host, 
                                    edge_index, edge_w, capacity, s);
 }
 
+// ---- segmented WSI x TMA similarity and the flat ragged median ----------------------------------
+// One side's offsets of a two-sided segment description: start at 0, non-decreasing, at least min_rows per segment, end at rows.
+static int check_side(const char* what, const char* side, const int64_t* ptr, int64_t n_seg, int64_t min_rows, int64_t rows) {
+  if (ptr[0] != 0) { set_error("%s: %s must start at 0 (got %lld)", what, side, (long long)ptr[0]); return MMF_E_INVALID; }
+  for (int64_t g = 0; g < n_seg; ++g) {
+    const int64_t ns = ptr[g + 1] - ptr[g];
+    if (ns < 0) { set_error("%s: %s decreases at segment %lld", what, side, (long long)g); return MMF_E_INVALID; }
+    if (ns < min_rows) {
+      set_error("%s: segment %lld has %lld rows in %s, need at least %lld", what, (long long)g, (long long)ns, side, (long long)min_rows);
+      return MMF_E_INVALID;
+    }
+  }
+  if (ptr[n_seg] != rows) {
+    set_error("%s: %s must end at %lld (got %lld)", what, side, (long long)rows, (long long)ptr[n_seg]);
+    return MMF_E_INVALID;
+  }
+  return MMF_OK;
+}
+
+// compute_wsi_tma_similarity of every slide of a cohort (build_hypergraph/preprocess_hypergraph.py:248-265): the pivots, ONE tiled
+// launch over a host-built work table, the per-segment merge of the partials, the flat ragged median over the stored blocks.
+// Block s and its five statistics are bit for bit mmf_sim_dense_stats(X_s, Y_s, MMF_RBF_DIRECT).
+int mmf_sim_dense_stats_segmented(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric, float lambda,
+                                  const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_seg, float* out, double* out_stats,
+                                  int device_id, void* hip_stream) {
+  const char* what = "sim_dense_stats_segmented";
+  MMF_TRY(check_common(X, n, m, d, in_dtype, device_id));
+  if (metric < MMF_DOT || metric > MMF_RBF_DIRECT) { set_error("%s: bad metric %d", what, metric); return MMF_E_INVALID; }
+  if (metric != MMF_RBF_DIRECT) { set_error("%s: only MMF_RBF_DIRECT is supported (got metric %d)", what, metric); return MMF_E_UNSUPPORTED; }
+  if (n_seg < 1 || !x_ptr_host || !y_ptr_host) { set_error("%s: need n_seg >= 1 and host offsets x_ptr / y_ptr [n_seg + 1]", what); return MMF_E_INVALID; }
+  MMF_TRY(check_side(what, "x_ptr", x_ptr_host, n_seg, 1, n));
+  MMF_TRY(check_side(what, "y_ptr", y_ptr_host, n_seg, 1, m));
+  if (!Y || !out_stats) { set_error("%s: NULL pointer", what); return MMF_E_INVALID; }
+  if (!out) { set_error("%s: out == NULL is not supported (the median reads the stored blocks)", what); return MMF_E_UNSUPPORTED; }
+  std::vector<int64_t> optr((size_t)n_seg + 1, 0), pbase;
+  for (int64_t g = 0; g < n_seg; ++g)      // n, m < 2^31: sum n_s m_s <= n m < 2^62
+    optr[g + 1] = optr[g] + (x_ptr_host[g + 1] - x_ptr_host[g]) * (y_ptr_host[g + 1] - y_ptr_host[g]);
+  const std::vector<int64_t> tab = rbf_direct_seg_table(x_ptr_host, y_ptr_host, n_seg, &pbase);
+  const int64_t grid = pbase[n_seg];
+  if (grid >= ((int64_t)1 << 31)) { set_error("%s: %lld workgroups", what, (long long)grid); return MMF_E_UNSUPPORTED; }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  const size_t S1 = (size_t)n_seg + 1, mneed = lower_median_seg_scratch_bytes(optr.data(), n_seg);
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, ws_bytes((size_t)grid * stat_partial_bytes(), 1) + 2 * ws_bytes((size_t)n_seg, 4) + 4 * ws_bytes(S1, 8) +
+                                      ws_bytes(tab.size(), 8) + ws_bytes(mneed, 1), &ws));
+  char* part = ws.take<char>((size_t)grid * stat_partial_bytes());
+  float* pivot = ws.take<float>((size_t)n_seg);
+  float* med = ws.take<float>((size_t)n_seg);
+  int64_t* d_xptr = ws.take<int64_t>(S1);
+  int64_t* d_yptr = ws.take<int64_t>(S1);
+  int64_t* d_optr = ws.take<int64_t>(S1);
+  int64_t* d_pbase = ws.take<int64_t>(S1);
+  int64_t* d_tab = ws.take<int64_t>(tab.size());
+  void* mscratch = ws.take<char>(mneed);
+  MMF_TRY(upload_table(s, d_xptr, x_ptr_host, S1 * 8));
+  MMF_TRY(upload_table(s, d_yptr, y_ptr_host, S1 * 8));
+  MMF_TRY(upload_table(s, d_optr, optr.data(), S1 * 8));
+  MMF_TRY(upload_table(s, d_pbase, pbase.data(), S1 * 8));
+  MMF_TRY(upload_table(s, d_tab, tab.data(), tab.size() * 8));
+  MMF_TRY(launch_rbf_direct_pivot_seg(X, Y, d, in_dtype, lambda, d_xptr, d_yptr, n_seg, pivot, s));
+  MMF_TRY(launch_rbf_direct_seg(X, Y, d, in_dtype, lambda, out, part, pivot, d_tab, grid, d_xptr, d_yptr, d_optr, d_pbase, s));
+  MMF_TRY(launch_stats_finish_seg(part, d_pbase, pivot, d_xptr, d_yptr, n_seg, out_stats, s));
+  MMF_TRY(launch_lower_median_seg(out, optr.data(), n_seg, med, mscratch, s));
+  return launch_stats_set_median_seg(med, n_seg, out_stats, s);
+}
+
+// torch.median of every block v[ptr[s]:ptr[s+1]] of a flat ragged array: the similarity blocks above, and the edge-weight median
+// filter of the rebuild (preprocess_hypergraph.py:885-897) for every slide of a cohort's edge list.
+int mmf_lower_median_segmented(const float* v, const int64_t* ptr_host, int64_t n_seg, float* out_median, int device_id, void* hip_stream) {
+  const char* what = "lower_median_segmented";
+  if (device_id < 0) { set_error("%s: no CPU path", what); return MMF_E_UNSUPPORTED; }
+  if (n_seg < 1 || !ptr_host) { set_error("%s: need n_seg >= 1 and host offsets ptr[n_seg + 1]", what); return MMF_E_INVALID; }
+  MMF_TRY(check_side(what, "ptr", ptr_host, n_seg, 1, ptr_host[n_seg]));
+  if (!v || !out_median) { set_error("%s: NULL pointer", what); return MMF_E_INVALID; }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceGuard guard(device_id);
+  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  const size_t need = lower_median_seg_scratch_bytes(ptr_host, n_seg);
+  Workspace ws;
+  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
+  return launch_lower_median_seg(v, ptr_host, n_seg, out_median, ws.take<char>(need), s);
+}
+
 // ---- ordered k-NN + clique edges of a ragged batch (mmf_knn_clique.hip) -----------------------------
 // The edge list that build_hypergraph_knn_kmeans assembles per slide (preprocess_hypergraph.py:386-404), for every segment at
 // once and already in its documented order.  Count, one host read of *out_count by the caller, fill.

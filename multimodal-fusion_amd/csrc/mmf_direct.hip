@@ -39,18 +39,47 @@ __device__ __forceinline__ f32x4 dload4(const void* base, int64_t row, int64_t k
 
 constexpr int EPI_EXP = 0, EPI_EXP_STATS = 1;
 
+// SEG (the segmented call, mmf_sim_dense_stats_segmented): a 1-D grid, workgroup w takes entry w of the work table — segment,
+// tile row, tile column, ordered segment-major, tile-row-major, then tile column.  Segment s pairs rows xptr[s] .. xptr[s+1]-1
+// of X with rows yptr[s] .. yptr[s+1]-1 of Y: bounds n_s and m_s (the staging loads clamp to the segment's last row, so no
+// load leaves the segment), output block at out + optr[s] with leading dimension m_s (so the 16-byte-store test is taken per
+// segment), pivot[s], and the partial at pbase[s] + tile_row * ceil(m_s / 128) + tile_col — where the plain launch on the
+// segment's slice puts it.  The flag is the presence of a trailing DirectSegTables argument: the plain instantiations keep their
+// argument list, and with it every instruction they had before the flag existed (an extra argument, even an empty one, moves
+// the hidden gridDim slot).
+enum { DSEG_SEG = 0, DSEG_TROW = 1, DSEG_TCOL = 2, DSEG_ENTRY = 3 };
+struct DirectSegTables { const int64_t *tab, *xptr, *yptr, *optr, *pbase; };
+__device__ __forceinline__ const DirectSegTables& direct_seg_tables(const DirectSegTables& t) { return t; }
+
 // X: rows [xrow0, xrow0 + n) of the query matrix are this launch's rows; out (may be null) has leading dimension m.
-template <bool VEC4, int EPI>
+template <bool VEC4, int EPI, typename... SEGT>
 __global__ __launch_bounds__(256, 3) void rbf_direct_tiled_kernel(const void* __restrict__ X, int64_t n, const void* __restrict__ Y,
                                                                int64_t m, int64_t d, int dtype, float neg_lambda,
                                                                float* __restrict__ out, StatPartial* __restrict__ part,
-                                                               const float* __restrict__ pivot) {
+                                                               const float* __restrict__ pivot, SEGT... seg_tables) {
+  constexpr bool SEG = sizeof...(SEGT) != 0;
+  static_assert(!SEG || EPI == EPI_EXP_STATS, "the segmented form always takes the statistics");
+  int64_t seg_i0 = 0, seg_j0 = 0;
+  size_t seg_slot = 0;
+  if constexpr (SEG) {
+    const DirectSegTables& sa = direct_seg_tables(seg_tables...);
+    const int64_t* e = sa.tab + (size_t)blockIdx.x * DSEG_ENTRY;
+    const int64_t sg = e[DSEG_SEG], trow = e[DSEG_TROW], tcol = e[DSEG_TCOL];
+    const int64_t x0 = sa.xptr[sg], y0 = sa.yptr[sg];
+    const int64_t esz = (dtype == MMF_F32) ? 4 : 2;
+    n = sa.xptr[sg + 1] - x0; m = sa.yptr[sg + 1] - y0;
+    X = reinterpret_cast<const char*>(X) + x0 * d * esz;
+    Y = reinterpret_cast<const char*>(Y) + y0 * d * esz;
+    out += sa.optr[sg]; pivot += sg;
+    seg_i0 = trow * D_BM; seg_j0 = tcol * D_BN;
+    seg_slot = (size_t)(sa.pbase[sg] + trow * ((m + D_BN - 1) / D_BN) + tcol);
+  }
   constexpr bool STATS = (EPI == EPI_EXP_STATS);
   __shared__ __attribute__((aligned(16))) float As[2][D_KC][D_LD];
   __shared__ __attribute__((aligned(16))) float Bs[2][D_KC][D_LD];
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;
-  const int64_t i0 = (int64_t)blockIdx.y * D_BM, j0 = (int64_t)blockIdx.x * D_BN;
+  const int64_t i0 = SEG ? seg_i0 : (int64_t)blockIdx.y * D_BM, j0 = SEG ? seg_j0 : (int64_t)blockIdx.x * D_BN;
 
   const int srow = tid >> 2, sk = (tid & 3) * 4;
   int64_t xr[2], yr[2];
@@ -158,7 +187,7 @@ __global__ __launch_bounds__(256, 3) void rbf_direct_tiled_kernel(const void* __
     if (tid == 0) {
       StatPartial r = w[0];
       for (int q = 1; q < 4; ++q) { r.s1 += w[q].s1; r.s2 += w[q].s2; r.mn = fminf(r.mn, w[q].mn); r.mx = fmaxf(r.mx, w[q].mx); }
-      part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = r;
+      part[SEG ? seg_slot : (size_t)blockIdx.y * gridDim.x + blockIdx.x] = r;
     }
   }
 }
@@ -174,6 +203,21 @@ __global__ __launch_bounds__(64) void rbf_direct_pivot_kernel(const void* X, con
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
   if (threadIdx.x == 0) pivot[0] = expf(neg_lambda * acc);
+}
+
+// rbf_direct_pivot_kernel for segment blockIdx.x: the first pair of the segment, the same lane-strided chain and butterfly
+__global__ __launch_bounds__(64) void rbf_direct_pivot_seg_kernel(const void* X, const void* Y, int64_t d, int dtype, float neg_lambda,
+                                                                  const int64_t* __restrict__ xptr, const int64_t* __restrict__ yptr,
+                                                                  float* pivot) {
+  const int64_t xb = xptr[blockIdx.x] * d, yb = yptr[blockIdx.x] * d;
+  float acc = 0.f;
+  for (int64_t k = threadIdx.x; k < d; k += 64) {
+    const float t = ld_elem(X, xb + k, dtype) - ld_elem(Y, yb + k, dtype);
+    acc = __builtin_fmaf(t, t, acc);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if (threadIdx.x == 0) pivot[blockIdx.x] = expf(neg_lambda * acc);
 }
 
 static bool direct_vec4(const void* X, const void* Y, int64_t d, int dtype) {
@@ -203,6 +247,48 @@ int launch_rbf_direct(const void* X, int64_t n, const void* Y, int64_t m, int64_
     if (v4) hipLaunchKernelGGL((rbf_direct_tiled_kernel<true, EPI_EXP>), grid, dim3(256), 0, s, X, n, Y, m, d, dtype, -lambda, out, sp, pivot);
     else hipLaunchKernelGGL((rbf_direct_tiled_kernel<false, EPI_EXP>), grid, dim3(256), 0, s, X, n, Y, m, d, dtype, -lambda, out, sp, pivot);
   }
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
+// ---- segmented (mmf_sim_dense_stats_segmented) ---------------------------------------------------
+// The work table of the segmented launch, [entries][DSEG_ENTRY] int64, and pbase[S + 1]: the first partial of every segment.
+std::vector<int64_t> rbf_direct_seg_table(const int64_t* xptr, const int64_t* yptr, int64_t S, std::vector<int64_t>* pbase) {
+  std::vector<int64_t> tab;
+  pbase->assign((size_t)S + 1, 0);
+  for (int64_t sg = 0; sg < S; ++sg) {
+    const int64_t tr = (xptr[sg + 1] - xptr[sg] + D_BM - 1) / D_BM, tc = (yptr[sg + 1] - yptr[sg] + D_BN - 1) / D_BN;
+    for (int64_t r = 0; r < tr; ++r)
+      for (int64_t c = 0; c < tc; ++c) {
+        const int64_t e[DSEG_ENTRY] = {sg, r, c};
+        tab.insert(tab.end(), e, e + DSEG_ENTRY);
+      }
+    (*pbase)[sg + 1] = (*pbase)[sg] + tr * tc;
+  }
+  return tab;
+}
+
+// pivot[s] of every segment, one wave each.  d_xptr / d_yptr: device copies of the offsets.
+int launch_rbf_direct_pivot_seg(const void* X, const void* Y, int64_t d, int dtype, float lambda, const int64_t* d_xptr,
+                                const int64_t* d_yptr, int64_t S, float* pivot, hipStream_t s) {
+  hipLaunchKernelGGL(rbf_direct_pivot_seg_kernel, dim3((unsigned)S), dim3(64), 0, s, X, Y, d, dtype, -lambda, d_xptr, d_yptr, pivot);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
+// One launch over the device copy of the work table (grid = its entries): every block of out, every partial of part.
+int launch_rbf_direct_seg(const void* X, const void* Y, int64_t d, int dtype, float lambda, float* out, void* part, const float* pivot,
+                          const int64_t* d_tab, int64_t grid, const int64_t* d_xptr, const int64_t* d_yptr, const int64_t* d_optr,
+                          const int64_t* d_pbase, hipStream_t s) {
+  StatPartial* sp = reinterpret_cast<StatPartial*>(part);
+  const DirectSegTables sa{d_tab, d_xptr, d_yptr, d_optr, d_pbase};
+  const int64_t z = 0;
+  if (direct_vec4(X, Y, d, dtype))
+    hipLaunchKernelGGL((rbf_direct_tiled_kernel<true, EPI_EXP_STATS, DirectSegTables>), dim3((unsigned)grid), dim3(256), 0, s, X, z, Y, z, d, dtype, -lambda,
+                       out, sp, pivot, sa);
+  else
+    hipLaunchKernelGGL((rbf_direct_tiled_kernel<false, EPI_EXP_STATS, DirectSegTables>), dim3((unsigned)grid), dim3(256), 0, s, X, z, Y, z, d, dtype, -lambda,
+                       out, sp, pivot, sa);
   MMF_LAUNCH_CHECK();
   return MMF_OK;
 }

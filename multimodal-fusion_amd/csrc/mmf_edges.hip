@@ -573,8 +573,8 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(const float* __restr
 
 // out[0..3] = mean, std (unbiased, as torch.std), min, max; out[4] is the median's slot.  pivot[0]: the value the
 // partial sums were taken around.
-__global__ __launch_bounds__(256) void stats_final_kernel(const float* __restrict__ pivot, int64_t count, const StatPartial* __restrict__ part,
-                                                          int64_t nparts, double* __restrict__ out) {
+__device__ __forceinline__ void stats_final_body(const float* __restrict__ pivot, int64_t count, const StatPartial* __restrict__ part,
+                                                 int64_t nparts, double* __restrict__ out) {
   __shared__ StatPartial w[256];
   StatPartial r{0.0, 0.0, __builtin_huge_valf(), -__builtin_huge_valf()};
   for (int64_t i = threadIdx.x; i < nparts; i += 256) {   // fixed assignment, fixed order: bit-reproducible
@@ -598,7 +598,26 @@ __global__ __launch_bounds__(256) void stats_final_kernel(const float* __restric
   }
 }
 
+__global__ __launch_bounds__(256) void stats_final_kernel(const float* __restrict__ pivot, int64_t count, const StatPartial* __restrict__ part,
+                                                          int64_t nparts, double* __restrict__ out) {
+  stats_final_body(pivot, count, part, nparts, out);
+}
+
 __global__ void stats_median_kernel(const float* med, double* out) { out[4] = (double)*med; }
+
+// segmented (mmf_sim_dense_stats_segmented): workgroup s merges the partials pbase[s] .. pbase[s+1]-1 of segment s — the same
+// assignment of partials to threads, the same tree — around pivot[s] with count = n_s m_s, into out[s][0..3]
+__global__ __launch_bounds__(256) void stats_final_seg_kernel(const float* __restrict__ pivot, const int64_t* __restrict__ xptr,
+                                                              const int64_t* __restrict__ yptr, const StatPartial* __restrict__ part,
+                                                              const int64_t* __restrict__ pbase, double* __restrict__ out) {
+  const int64_t sg = blockIdx.x;
+  const int64_t count = (xptr[sg + 1] - xptr[sg]) * (yptr[sg + 1] - yptr[sg]);
+  stats_final_body(pivot + sg, count, part + pbase[sg], pbase[sg + 1] - pbase[sg], out + 5 * sg);
+}
+__global__ __launch_bounds__(256) void stats_median_seg_kernel(const float* __restrict__ med, int64_t S, double* __restrict__ out) {
+  const int64_t sg = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (sg < S) out[5 * sg + 4] = (double)med[sg];
+}
 
 size_t array_stats_scratch_bytes(int64_t count) { return 2048 * sizeof(StatPartial) + 256 + median_scratch_bytes((unsigned long long)count); }
 
@@ -632,6 +651,18 @@ int launch_stats_finish(const void* part, int64_t nparts, const float* pivot, in
 }
 int launch_stats_set_median(const float* med, double* out, hipStream_t s) {
   hipLaunchKernelGGL(stats_median_kernel, dim3(1), dim3(1), 0, s, med, out);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+int launch_stats_finish_seg(const void* part, const int64_t* d_pbase, const float* pivot, const int64_t* d_xptr, const int64_t* d_yptr,
+                            int64_t S, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(stats_final_seg_kernel, dim3((unsigned)S), dim3(256), 0, s, pivot, d_xptr, d_yptr,
+                     reinterpret_cast<const StatPartial*>(part), d_pbase, out);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+int launch_stats_set_median_seg(const float* med, int64_t S, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(stats_median_seg_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, med, S, out);
   MMF_LAUNCH_CHECK();
   return MMF_OK;
 }
@@ -796,7 +827,8 @@ struct SegMedianHead {
   unsigned long long prefix, rank;   // as in MedianState
   unsigned long long hoff, copies;   // its copies: hist[hoff + 256 c + bin], c < copies
 };
-// work table of the histogram passes, one entry per workgroup: segment, first row, rows, histogram copy
+// work table of the histogram passes, one entry per workgroup: segment, first row, rows, histogram copy (flat blocks: segment,
+// first element, elements, histogram copy)
 enum { SMED_SEG = 0, SMED_ROW0 = 1, SMED_ROWS = 2, SMED_COPY = 3, SMED_ENTRY = 4 };
 constexpr int64_t kSegMedianChunk = 65536;     // entries of a block per histogram workgroup (whole rows, at least one)
 
@@ -822,6 +854,20 @@ struct SegMedianPlan {
       hist_words += 256 * heads[s].copies;
     }
   }
+  // flat blocks (mmf_lower_median_segmented): block s is the bptr[s+1] - bptr[s] >= 1 values from bptr[s], no diagonal
+  struct Flat {};
+  SegMedianPlan(const int64_t* bptr, int64_t S, Flat) : heads((size_t)S), kptr(bptr, bptr + S + 1) {
+    for (int64_t s = 0; s < S; ++s) {
+      const int64_t cs = bptr[s + 1] - bptr[s];
+      int64_t e = 0;
+      for (int64_t f0 = 0; f0 < cs; f0 += kSegMedianChunk, ++e) {
+        const int64_t ent[SMED_ENTRY] = {s, f0, cs - f0 < kSegMedianChunk ? cs - f0 : kSegMedianChunk, e % kHistCopies};
+        tab.insert(tab.end(), ent, ent + SMED_ENTRY);
+      }
+      heads[s] = SegMedianHead{0ull, ((unsigned long long)cs - 1ull) / 2ull, hist_words, (unsigned long long)(e < kHistCopies ? e : kHistCopies)};
+      hist_words += 256 * heads[s].copies;
+    }
+  }
   int64_t entries() const { return (int64_t)tab.size() / SMED_ENTRY; }
   size_t bytes(int64_t S) const {
     return ws_bytes((size_t)S, sizeof(SegMedianHead)) + 2 * ws_bytes((size_t)S + 1, 8) + ws_bytes(tab.size(), 8) + ws_bytes(hist_words, 8);
@@ -831,6 +877,9 @@ struct SegMedianPlan {
 // One radix pass over the entries of ONE block (the workgroup's table entry: rows [r0, r0 + rows) of K_s) whose higher bytes
 // equal the segment's prefix; the diagonal is skipped.  The rows are walked flat, one entry per thread and step, so short rows
 // keep every lane busy: (i, j) of the thread's entry advance by 256 entries per step without a division.
+// FLAT: the block is kptr[sg+1] - kptr[sg] values without a diagonal (ptr is not read) and the entry is elements [r0, r0 + rows):
+// the same walk without the (i, j) bookkeeping.
+template <bool FLAT>
 __global__ __launch_bounds__(256) void seg_median_hist_kernel(const float* __restrict__ K, const int64_t* __restrict__ ptr,
                                                               const int64_t* __restrict__ kptr, const int64_t* __restrict__ tab,
                                                               SegMedianHead* __restrict__ head, unsigned long long* __restrict__ hist,
@@ -840,7 +889,7 @@ __global__ __launch_bounds__(256) void seg_median_hist_kernel(const float* __res
   __syncthreads();
   const int64_t* e = tab + (size_t)blockIdx.x * SMED_ENTRY;
   const int64_t sg = e[SMED_SEG], r0 = e[SMED_ROW0], rows = e[SMED_ROWS];
-  const int64_t ns = ptr[sg + 1] - ptr[sg];
+  const int64_t ns = FLAT ? 1 : ptr[sg + 1] - ptr[sg];
   const float* B = K + kptr[sg];
   const uint32_t prefix = (uint32_t)head[sg].prefix;
   const uint32_t himask = (shift == 24) ? 0u : (0xffffffffu << (shift + 8));
@@ -868,13 +917,13 @@ __global__ __launch_bounds__(256) void seg_median_hist_kernel(const float* __res
     for (int u = 0; u < 4; ++u) v[u] = B[f + 256 * u];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      if (i != j) feed(v[u]);
-      step();
+      if (FLAT || i != j) feed(v[u]);
+      if constexpr (!FLAT) step();
     }
   }
   for (; f < f1; f += 256) {
-    if (i != j) feed(B[f]);
-    step();
+    if (FLAT || i != j) feed(B[f]);
+    if constexpr (!FLAT) step();
   }
   if (run) atomicAdd(&lh[cur], run);
   __syncthreads();
@@ -914,8 +963,8 @@ size_t offdiag_lower_median_seg_scratch_bytes(const int64_t* ptr, int64_t S) { r
 
 // out[s] (device f32 [S]): the lower median of the n_s (n_s - 1) off-diagonal entries of block s (every n_s >= 2, checked by
 // the caller).  Launches: the state's upload and clear, then 4 x (histogram over all blocks, pick per segment), for any S.
-int launch_offdiag_lower_median_seg(const float* K, const int64_t* ptr, int64_t S, float* out, void* scratch, hipStream_t s) {
-  const SegMedianPlan plan(ptr, S);
+template <bool FLAT>
+static int run_seg_median(const float* K, const SegMedianPlan& plan, const int64_t* ptr, int64_t S, float* out, void* scratch, hipStream_t s) {
   char* p = static_cast<char*>(scratch);
   SegMedianHead* head = reinterpret_cast<SegMedianHead*>(p);
   p += ws_bytes((size_t)S, sizeof(SegMedianHead));
@@ -927,18 +976,29 @@ int launch_offdiag_lower_median_seg(const float* K, const int64_t* ptr, int64_t 
   p += ws_bytes(plan.tab.size(), 8);
   unsigned long long* hist = reinterpret_cast<unsigned long long*>(p);
   MMF_TRY(upload_table(s, head, plan.heads.data(), (size_t)S * sizeof(SegMedianHead)));      // the plan dies with this call
-  MMF_TRY(upload_table(s, d_ptr, ptr, (size_t)(S + 1) * 8));
+  if (!FLAT) MMF_TRY(upload_table(s, d_ptr, ptr, (size_t)(S + 1) * 8));
   MMF_TRY(upload_table(s, d_kptr, plan.kptr.data(), (size_t)(S + 1) * 8));
   MMF_TRY(upload_table(s, d_tab, plan.tab.data(), plan.tab.size() * 8));
   MMF_HIP(hipMemsetAsync(hist, 0, plan.hist_words * 8, s));
   const int64_t grid = plan.entries();
   for (int pass = 0; pass < 4; ++pass) {
-    hipLaunchKernelGGL(seg_median_hist_kernel, dim3((unsigned)grid), dim3(256), 0, s, K, d_ptr, d_kptr, d_tab, head, hist, 24 - 8 * pass);
+    hipLaunchKernelGGL(seg_median_hist_kernel<FLAT>, dim3((unsigned)grid), dim3(256), 0, s, K, d_ptr, d_kptr, d_tab, head, hist, 24 - 8 * pass);
     MMF_LAUNCH_CHECK();
     hipLaunchKernelGGL(seg_median_pick_kernel, dim3((unsigned)S), dim3(256), 0, s, head, hist, 24 - 8 * pass, out);
     MMF_LAUNCH_CHECK();
   }
   return MMF_OK;
+}
+
+int launch_offdiag_lower_median_seg(const float* K, const int64_t* ptr, int64_t S, float* out, void* scratch, hipStream_t s) {
+  return run_seg_median<false>(K, SegMedianPlan(ptr, S), ptr, S, out, scratch, s);
+}
+
+// The lower median of every flat block v[bptr[s] .. bptr[s+1]) (every block with at least one value, checked by the caller):
+// the same select without a diagonal.  out[s] = the element of rank (c_s - 1) / 2, what mmf_lower_median returns on the block.
+size_t lower_median_seg_scratch_bytes(const int64_t* bptr, int64_t S) { return SegMedianPlan(bptr, S, SegMedianPlan::Flat{}).bytes(S); }
+int launch_lower_median_seg(const float* v, const int64_t* bptr, int64_t S, float* out, void* scratch, hipStream_t s) {
+  return run_seg_median<true>(v, SegMedianPlan(bptr, S, SegMedianPlan::Flat{}), nullptr, S, out, scratch, s);
 }
 
 // Threshold edges of every block: row r of the batch (segment s, local row i = r - ptr[s]) is row i of K_s against

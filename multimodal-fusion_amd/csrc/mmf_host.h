@@ -278,6 +278,21 @@ int launch_threshold_fill(const float* K, int64_t n, float thr, const unsigned l
 // n_s >= 2) for the median, which uploads its own tables into `scratch`; device copies d_ptr / d_kptr for the edges.
 size_t offdiag_lower_median_seg_scratch_bytes(const int64_t* ptr, int64_t S);
 int launch_offdiag_lower_median_seg(const float* K, const int64_t* ptr, int64_t S, float* out, void* scratch, hipStream_t s);
+// flat blocks v[bptr[s] .. bptr[s+1]) (HOST offsets, every block >= 1 value): mmf_lower_median of every block, no synchronisation
+size_t lower_median_seg_scratch_bytes(const int64_t* bptr, int64_t S);
+int launch_lower_median_seg(const float* v, const int64_t* bptr, int64_t S, float* out, void* scratch, hipStream_t s);
+// per-segment merge of statistic partials (part[pbase[s] .. pbase[s+1]), pivot[s], count = n_s m_s -> out[s][0..3]) and out[s][4] = med[s]
+int launch_stats_finish_seg(const void* part, const int64_t* d_pbase, const float* pivot, const int64_t* d_xptr, const int64_t* d_yptr,
+                            int64_t S, double* out, hipStream_t s);
+int launch_stats_set_median_seg(const float* med, int64_t S, double* out, hipStream_t s);
+// mmf_direct.hip, segmented: work table ([entries][3]: segment, tile row, tile column) + first partial of every segment; pivots;
+// the launch over the device copies of the tables
+std::vector<int64_t> rbf_direct_seg_table(const int64_t* xptr, const int64_t* yptr, int64_t S, std::vector<int64_t>* pbase);
+int launch_rbf_direct_pivot_seg(const void* X, const void* Y, int64_t d, int dtype, float lambda, const int64_t* d_xptr,
+                                const int64_t* d_yptr, int64_t S, float* pivot, hipStream_t s);
+int launch_rbf_direct_seg(const void* X, const void* Y, int64_t d, int dtype, float lambda, float* out, void* part, const float* pivot,
+                          const int64_t* d_tab, int64_t grid, const int64_t* d_xptr, const int64_t* d_yptr, const int64_t* d_optr,
+                          const int64_t* d_pbase, hipStream_t s);
 int launch_threshold_count_seg(const float* K, const int64_t* d_ptr, const int64_t* d_kptr, int64_t S, int64_t n, const float* thr,
                                unsigned long long* row_off, int64_t* out_count, uint32_t* row_cnt, hipStream_t s);
 int launch_threshold_fill_seg(const float* K, const int64_t* d_ptr, const int64_t* d_kptr, int64_t S, int64_t n, const float* thr,

@@ -1,0 +1,295 @@
+"""Steps 2 and 3 of process_single_file for every slide of a ragged cohort in one call: the WSI x TMA similarity with its five
+statistics (build_hypergraph/preprocess_hypergraph.py:248-265) and the grouping of its rows (:297-306); and the edge-weight
+median filter of the rebuild (:885-897) for every slide of a cohort's edge list.
+
+Slide s pairs wsi[wsi_ptr[s]:wsi_ptr[s+1]] (n_s super patches) with tma[tma_ptr[s]:tma_ptr[s+1]] (m_s TMA patches).  Its
+similarity block is [n_s, m_s] row-major at s_ptr[s] = sum_{t<s} n_t m_t of one flat f32 buffer, and block and statistics are bit
+for bit those of ``compute_wsi_tma_similarity`` on that slide.  The chain over a cohort:
+
+    S_flat, s_ptr, sim_stats = compute_wsi_tma_similarity_segmented(wsi, pos, tma, wsi_ptr=wp, tma_ptr=tp)
+    labels, group_stats, info = group_by_similarity_segmented(S_flat, G, wsi_ptr=wp, tma_ptr=tp)
+    ei, ew, eptr, hg = build_hypergraph_knn_kmeans_segmented(wsi, tma, labels, wsi_ptr=wp, tma_ptr=tp)
+    ei, ew, eptr, flt = filter_edges_by_median_segmented(ei, ew, eptr, ratio)
+
+Every argument error is raised on the host before the device is touched (and before the "needs a ROCm device" RuntimeError),
+and names the first bad slide.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from .build_hypergraph import preprocess_hypergraph
+from .build_hypergraph._common import compute_device, result_device_like_preprocess, to_gpu
+
+
+# ---------------------------------------------------------------------------------------------------
+# host-side argument checks
+# ---------------------------------------------------------------------------------------------------
+def _slide_ptr(ptr, batch, rows: Optional[int], side: str, what: str, min_rows: int = 1) -> torch.Tensor:
+    """Host int64 offsets [S + 1] of one side from exactly one of ptr / batch (sorted slide id per row), every slide with at least
+    min_rows rows.  rows None: the row count is what ptr / batch say.  The message names the first bad slide."""
+    if (ptr is None) == (batch is None):
+        raise ValueError(f"{what}: give exactly one of {side}ptr / {side}batch")
+    if ptr is not None:
+        p = torch.as_tensor(ptr).detach().to("cpu", torch.int64).reshape(-1).contiguous()
+        if p.numel() < 2:
+            raise ValueError(f"{what}: {side}ptr describes no slide (it needs S + 1 >= 2 offsets)")
+        if int(p[0]) != 0:
+            raise ValueError(f"{what}: slide 0: {side}ptr must start at 0 (got {int(p[0])})")
+        sizes = p[1:] - p[:-1]
+        bad = torch.nonzero(sizes < min_rows).reshape(-1)
+        if bad.numel():
+            s = int(bad[0])
+            if int(sizes[s]) < 0:
+                raise ValueError(f"{what}: slide {s}: {side}ptr decreases ({int(p[s])} -> {int(p[s + 1])})")
+            raise ValueError(f"{what}: slide {s} has {int(sizes[s])} rows in {side}ptr, need at least {min_rows}")
+        if rows is not None and int(p[-1]) != rows:
+            raise ValueError(f"{what}: slide {p.numel() - 2}: {side}ptr must end at {rows} (got {int(p[-1])})")
+        return p
+    b = torch.as_tensor(batch)
+    if b.dim() != 1 or (rows is not None and b.numel() != rows):
+        raise ValueError(f"{what}: slide 0: {side}batch must hold one slide id per row ({rows})")
+    b = b.detach().to("cpu", torch.int64)           # the one device -> host copy of a batch vector
+    if b.numel() == 0:
+        raise ValueError(f"{what}: slide 0 has 0 rows in {side}batch, need at least {min_rows}")
+    if int(b[0]) < 0:
+        raise ValueError(f"{what}: slide {int(b[0])}: {side}batch must be non-negative")
+    down = torch.nonzero(b[1:] < b[:-1]).reshape(-1)
+    if down.numel():
+        r = int(down[0]) + 1
+        raise ValueError(f"{what}: slide {int(b[r])}: {side}batch must be sorted (row {r} follows slide {int(b[r - 1])})")
+    counts = torch.bincount(b)
+    bad = torch.nonzero(counts < min_rows).reshape(-1)
+    if bad.numel():
+        s = int(bad[0])
+        raise ValueError(f"{what}: slide {s} has {int(counts[s])} rows in {side}batch, need at least {min_rows}")
+    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(counts, 0)]).contiguous()
+
+
+def _two_sides(n_x: Optional[int], n_y: Optional[int], x_ptr, x_batch, y_ptr, y_batch, xs: str, ys: str,
+               what: str) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(x offsets, y offsets, block offsets s_ptr) of a two-sided slide description, all host int64 [S + 1]."""
+    xp = _slide_ptr(x_ptr, x_batch, n_x, xs, what)
+    yp = _slide_ptr(y_ptr, y_batch, n_y, ys, what)
+    if xp.numel() != yp.numel():
+        sx, sy = xp.numel() - 1, yp.numel() - 1
+        raise ValueError(f"{what}: slide {min(sx, sy)}: {xs.rstrip('_') or 'x'} describes {sx} slides, {ys.rstrip('_') or 'y'} {sy}")
+    blocks = (xp[1:] - xp[:-1]) * (yp[1:] - yp[:-1])
+    return xp, yp, torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(blocks, 0)]).contiguous()
+
+
+def _hp(t: torch.Tensor) -> ctypes.c_void_p:
+    return ctypes.c_void_p(t.data_ptr())
+
+
+# ---------------------------------------------------------------------------------------------------
+# the two C entries
+# ---------------------------------------------------------------------------------------------------
+def sim_dense_stats_segmented(X: torch.Tensor, Y: torch.Tensor, *, x_ptr=None, x_batch=None, y_ptr=None, y_batch=None,
+                              metric="rbf_direct", lam: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ops.sim_dense_stats(X_s, Y_s, metric="rbf_direct") of every segment in one call (mmf_sim_dense_stats_segmented).  Returns
+    (S_flat f32 [sum n_s m_s] on X's device, s_ptr int64 [S + 1] on the HOST, stats f64 [S, 5] on the device: mean, unbiased std,
+    min, max, lower median).  Block s is S_flat[s_ptr[s]:s_ptr[s+1]].view(n_s, m_s); block and stats[s] carry the bits of the plain
+    call on the segment's rows.  Nothing is read back: the call returns without waiting for the stream."""
+    what = "sim_dense_stats_segmented"
+    X = ops._feat(X, what + " X")
+    Y = ops._feat(Y, what + " Y")
+    if X.shape[1] != Y.shape[1]:
+        raise ValueError(f"{what}: slide 0: X has D={X.shape[1]}, Y has D={Y.shape[1]}")
+    if ops._metric(metric) != _lib.RBF_DIRECT:
+        raise ValueError(f"{what}: only metric='rbf_direct' is supported (got {metric!r})")
+    xp, yp, s_ptr = _two_sides(X.shape[0], Y.shape[0], x_ptr, x_batch, y_ptr, y_batch, "x_", "y_", what)
+    ops._need_gpu(X, what)
+    if Y.device != X.device:
+        raise ValueError(f"{what}: X and Y must share a device")
+    Y = Y.to(X.dtype)
+    S = xp.numel() - 1
+    out = torch.empty((int(s_ptr[-1]),), dtype=torch.float32, device=X.device)
+    stats = torch.empty((S, 5), dtype=torch.float64, device=X.device)
+    rc = _lib.lib().mmf_sim_dense_stats_segmented(ops._p(X), X.shape[0], ops._p(Y), Y.shape[0], X.shape[1], ops._DT[X.dtype],
+                                                  _lib.RBF_DIRECT, float(lam), _hp(xp), _hp(yp), S, ops._p(out), ops._p(stats),
+                                                  X.device.index or 0, ops._stream(X.device))
+    _lib.check(rc, "mmf_sim_dense_stats_segmented")
+    return out, s_ptr, stats
+
+
+def lower_median_segmented(v: torch.Tensor, *, ptr=None, batch=None) -> torch.Tensor:
+    """ops.lower_median (torch.median) of every block v[ptr[s]:ptr[s+1]] of a flat f32 tensor: device f32 [S], without a host
+    synchronisation (mmf_lower_median_segmented).  Every block needs at least one value."""
+    what = "lower_median_segmented"
+    if v.dim() != 1:
+        raise ValueError(f"{what}: expected a flat 1-D tensor, got shape {tuple(v.shape)}")
+    p = _slide_ptr(ptr, batch, v.numel(), "", what)
+    ops._need_gpu(v, what)
+    v = v.contiguous().float()
+    out = torch.empty((p.numel() - 1,), dtype=torch.float32, device=v.device)
+    rc = _lib.lib().mmf_lower_median_segmented(ops._p(v), _hp(p), p.numel() - 1, ops._p(out), v.device.index or 0, ops._stream(v.device))
+    _lib.check(rc, "mmf_lower_median_segmented")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# compute_wsi_tma_similarity over a cohort
+# ---------------------------------------------------------------------------------------------------
+_STAT_KEYS = ("mean", "std", "min", "max", "median")
+
+
+def compute_wsi_tma_similarity_segmented(wsi_features: torch.Tensor, wsi_positions: torch.Tensor, tma_features: torch.Tensor,
+                                         lambda_h: float = 1.0, lambda_g: float = 1.0, device: Optional[torch.device] = None, *,
+                                         wsi_ptr=None, wsi_batch=None, tma_ptr=None,
+                                         tma_batch=None) -> Tuple[torch.Tensor, torch.Tensor, List[Dict]]:
+    """compute_wsi_tma_similarity of every slide of a cohort: (S_flat f32 [sum n_s m_s] on `device` (None: the features' device
+    if it is a GPU, else the CPU, as the plain mirror), s_ptr host int64 [S + 1], one statistics dict per slide).  The dicts hold
+    Python scalars as the plain mirror's do (the f32-rounded `.item()` values), out of ONE device -> host copy of the [S, 5]
+    array.  `wsi_positions` and `lambda_g` are accepted and ignored, as in the mirror."""
+    what = "compute_wsi_tma_similarity_segmented"
+    if wsi_features.dim() != 2 or tma_features.dim() != 2:
+        raise ValueError(f"{what}: wsi_features and tma_features must be 2-D [N, D]")
+    if wsi_features.shape[1] != tma_features.shape[1]:
+        raise ValueError(f"{what}: slide 0: wsi_features have D={wsi_features.shape[1]}, tma_features D={tma_features.shape[1]}")
+    wp, tp, _ = _two_sides(wsi_features.shape[0], tma_features.shape[0], wsi_ptr, wsi_batch, tma_ptr, tma_batch, "wsi_", "tma_", what)
+    out_dev = result_device_like_preprocess(wsi_features, device)
+    dev = out_dev if out_dev.type == "cuda" else compute_device(wsi_features, tma_features)
+    S_flat, s_ptr, stats = sim_dense_stats_segmented(to_gpu(wsi_features, dev), to_gpu(tma_features, dev), x_ptr=wp, y_ptr=tp,
+                                                     metric="rbf_direct", lam=float(lambda_h))
+    host = stats.to(torch.float32).cpu().tolist()        # the reference's values are `.item()`s of f32 tensors
+    return S_flat.to(out_dev), s_ptr, [dict(zip(_STAT_KEYS, row)) for row in host]
+
+
+def similarity_block(S_flat: torch.Tensor, s_ptr, sizes: Sequence[Tuple[int, int]], s: int) -> torch.Tensor:
+    """The [n_s, m_s] view of slide s; sizes[s] = (n_s, m_s)."""
+    n_s, m_s = int(sizes[s][0]), int(sizes[s][1])
+    return S_flat[int(s_ptr[s]):int(s_ptr[s + 1])].view(n_s, m_s)
+
+
+# ---------------------------------------------------------------------------------------------------
+# group_by_similarity over a cohort
+# ---------------------------------------------------------------------------------------------------
+def width_plan(n_sizes: Sequence[int], m_sizes: Sequence[int]) -> List[Dict]:
+    """Which slide lands in which KMeans fit.  Slide s clusters the n_s rows of an [n_s, m_s] matrix, and one segmented fit takes
+    one feature dimension, so the slides are grouped by m_s: one fit per distinct width, in order of first appearance, each
+    holding its slides in slide order.  Per fit: 'width', 'slides', 'fit_ptr' (offsets of the slides' rows in the fit's
+    concatenated input: the labels fit_ptr[i]:fit_ptr[i+1] return to slide slides[i]) and 'adjacent' (the slides are
+    consecutive, so their blocks are one contiguous piece of S_flat and need no copy)."""
+    fits: Dict[int, Dict] = {}
+    for s, (n_s, m_s) in enumerate(zip(n_sizes, m_sizes)):
+        f = fits.setdefault(int(m_s), {"width": int(m_s), "slides": [], "fit_ptr": [0]})
+        f["slides"].append(s)
+        f["fit_ptr"].append(f["fit_ptr"][-1] + int(n_s))
+    for f in fits.values():
+        f["adjacent"] = f["slides"] == list(range(f["slides"][0], f["slides"][0] + len(f["slides"])))
+    return list(fits.values())
+
+
+def group_by_similarity_segmented(S_flat: torch.Tensor, num_groups: int, *, wsi_ptr=None, wsi_batch=None, tma_ptr=None,
+                                  tma_batch=None, method: str = "kmeans"):
+    """group_by_similarity of every slide's block of S_flat (the layout of compute_wsi_tma_similarity_segmented): (labels int32
+    numpy [n_wsi], 0 .. num_groups - 1 within each slide; one stats dict per slide: method, num_groups, group_sizes; info:
+    kmeans_backend and per slide ambiguous_draws / ambiguous_trials, None with the 'sklearn' backend).
+
+    Slide s clusters the rows of an n_s x m_s matrix, so the feature dimension differs between slides, while the segmented KMeans
+    fit takes one.  The slides are therefore grouped by m_s (width_plan): ONE kmeans_fit_predict_segmented call per distinct
+    width, on the concatenation of those slides' blocks (no copy when they are adjacent), and the labels are scattered back to
+    slide order.  A cohort with S distinct widths degrades to S fits.  Columns are never zero-padded to a common width:
+    scikit-learn's tolerance is tol * mean(var) over the columns, so padding would change the decisions."""
+    what = "group_by_similarity_segmented"
+    if method != "kmeans":
+        raise ValueError(f"Unknown grouping method: {method}")
+    if S_flat.dim() != 1:
+        raise ValueError(f"{what}: S_flat must be the flat 1-D buffer of the blocks, got shape {tuple(S_flat.shape)}")
+    num_groups = int(num_groups)
+    wp, tp, s_ptr = _two_sides(None, None, wsi_ptr, wsi_batch, tma_ptr, tma_batch, "wsi_", "tma_", what)
+    if S_flat.numel() != int(s_ptr[-1]):
+        raise ValueError(f"{what}: slide {wp.numel() - 2}: S_flat holds {S_flat.numel()} values, the blocks of the slides {int(s_ptr[-1])}")
+    n_sizes, m_sizes = (wp[1:] - wp[:-1]).tolist(), (tp[1:] - tp[:-1]).tolist()
+    for s, n_s in enumerate(n_sizes):
+        if not (1 <= num_groups <= n_s):
+            raise ValueError(f"{what}: slide {s}: n_samples={n_s} should be >= n_clusters={num_groups}.")
+    S, n_wsi = len(n_sizes), int(wp[-1])
+    dev = compute_device(S_flat)
+    F = to_gpu(S_flat, dev)
+    sp = s_ptr.tolist()
+    backend = preprocess_hypergraph.KMEANS_BACKEND
+    labels = torch.empty((n_wsi,), dtype=torch.int64, device=dev)
+    draws: Optional[List[int]] = [0] * S if backend == "device" else None
+    trials: Optional[List[int]] = [0] * S if backend == "device" else None
+    if backend == "device":
+        from .kmeans import kmeans_fit_predict_segmented
+        for fit in width_plan(n_sizes, m_sizes):
+            sl, m = fit["slides"], fit["width"]
+            if fit["adjacent"]:
+                X = F[sp[sl[0]]:sp[sl[-1] + 1]].view(-1, m)
+            else:
+                X = torch.cat([F[sp[s]:sp[s + 1]].view(-1, m) for s in sl], dim=0)
+            lab, _, _, info = kmeans_fit_predict_segmented(X, num_groups, ptr=fit["fit_ptr"], n_init=10, seed=42, return_info=True)
+            if fit["adjacent"]:
+                labels[int(wp[sl[0]]):int(wp[sl[-1] + 1])] = lab
+            else:
+                dest = torch.cat([torch.arange(int(wp[s]), int(wp[s + 1])) for s in sl])
+                labels[dest.to(dev)] = lab
+            for s, i in zip(sl, info):
+                draws[s], trials[s] = int(i["ambiguous_draws"]), int(i["ambiguous_trials"])
+    else:        # 'sklearn': the reference's own call, slide by slide, on the host
+        for s in range(S):
+            block = F[sp[s]:sp[s + 1]].view(n_sizes[s], m_sizes[s])
+            labels[int(wp[s]):int(wp[s + 1])] = preprocess_hypergraph._kmeans_labels(block, num_groups)
+    slide_of_row = torch.repeat_interleave(torch.arange(S), wp[1:] - wp[:-1]).to(dev)
+    sizes = torch.bincount(slide_of_row * num_groups + labels, minlength=S * num_groups).cpu().view(S, num_groups).tolist()
+    stats = [{"method": "kmeans", "num_groups": num_groups, "group_sizes": [int(v) for v in row]} for row in sizes]
+    info = {"kmeans_backend": backend, "ambiguous_draws": draws, "ambiguous_trials": trials}
+    return labels.cpu().numpy().astype(np.int32), stats, info
+
+
+# ---------------------------------------------------------------------------------------------------
+# the rebuild's edge-weight median filter over a cohort
+# ---------------------------------------------------------------------------------------------------
+def median_thresholds(medians: torch.Tensor, ratio: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(threshold f64, threshold f32) per slide from the f32 medians: `median.item() * ratio` is a float64 product
+    (preprocess_hypergraph.py:887-888), and `weights >= threshold` compares an f32 tensor with a Python scalar, which torch
+    rounds to the tensor's dtype first — the f32 threshold is that rounding."""
+    thr64 = medians.to(torch.float64) * float(ratio)
+    return thr64, thr64.to(torch.float32)
+
+
+def filter_edges_by_median_segmented(edge_index: torch.Tensor, edge_weights: torch.Tensor, edge_ptr, ratio: float):
+    """The edge-weight median filter of rebuild_hypergraph_from_similarity (:885-897) for every slide of the output of
+    build_hypergraph_knn_kmeans_segmented: slide s keeps its edges with weight >= median(weights of slide s) * ratio.  Returns
+    (edge_index [2, E'], edge_weights [E'], edge_ptr [S + 1] int64, one dict per slide: threshold (float64, the mirror's value),
+    num_edges_after_threshold, threshold_ratio), tensors on the inputs' device.  One host read: the thresholds and the kept
+    counts in one copy (edge_ptr is read on the host as every offset array is; pass host offsets to keep it at one).  A slide
+    without edges raises ValueError, as torch.median of an empty tensor does."""
+    what = "filter_edges_by_median_segmented"
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_weights.dim() != 1 or edge_index.shape[1] != edge_weights.shape[0]:
+        raise ValueError(f"{what}: expected edge_index [2, E] and edge_weights [E], got {tuple(edge_index.shape)} and {tuple(edge_weights.shape)}")
+    E = edge_weights.shape[0]
+    p = _slide_ptr(edge_ptr, None, E, "edge_", what, min_rows=0)
+    empty = torch.nonzero(p[1:] == p[:-1]).reshape(-1)
+    if empty.numel():
+        raise ValueError(f"{what}: slide {int(empty[0])} has no edges: the median of an empty tensor is undefined")
+    S = p.numel() - 1
+    out_dev = edge_weights.device
+    dev = compute_device(edge_weights)
+    w = to_gpu(edge_weights, dev)
+    ei = edge_index.detach().to(device=dev, dtype=torch.int64).contiguous()
+    med = lower_median_segmented(w, ptr=p)
+    thr64, thr32 = median_thresholds(med, ratio)
+    slide_of_edge = torch.repeat_interleave(torch.arange(S), p[1:] - p[:-1]).to(dev)
+    mask = w >= thr32[slide_of_edge]
+    kept = torch.zeros(S, dtype=torch.int64, device=dev).index_add_(0, slide_of_edge, mask.to(torch.int64))
+    host = torch.stack([thr64, kept.to(torch.float64)], dim=1).cpu()          # the one host read
+    kept_h = host[:, 1].to(torch.int64)
+    E2 = int(kept_h.sum())
+    # ordered compaction without a second read: kept edge e goes to position (number of kept edges before e); the others to a
+    # spare slot at the end that is cut off
+    pos = torch.where(mask, torch.cumsum(mask.to(torch.int64), 0) - 1, torch.full_like(slide_of_edge, E2))
+    ew2 = torch.empty((E2 + 1,), dtype=torch.float32, device=dev).scatter_(0, pos, w)[:E2]
+    ei2 = torch.empty((2, E2 + 1), dtype=torch.int64, device=dev).scatter_(1, pos.unsqueeze(0).expand(2, -1), ei)[:, :E2].contiguous()
+    new_ptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(kept_h, 0)])
+    stats = [{"threshold": float(t), "num_edges_after_threshold": int(k), "threshold_ratio": ratio}
+             for t, k in zip(host[:, 0].tolist(), kept_h.tolist())]
+    return ei2.to(out_dev), ew2.contiguous().to(out_dev), new_ptr.to(out_dev), stats
