@@ -27,6 +27,7 @@ struct WsEntry { char* base = nullptr; size_t cap = 0; };
 static std::mutex g_ws_mu;
 static std::map<std::pair<int, hipStream_t>, WsEntry> g_ws[2];
 
+// A workspace of at least `bytes` for (device, stream); reallocates (after a stream sync) when it has to grow.
 // slot 0: the call's working set.  slot 1: what only a rare branch of a call needs on top of it (the f32 operand
 // images of an exact rescan inside the 16-bit path), so that every call does not carry it.
 static int get_workspace_slot(int device, hipStream_t stream, int slot, size_t bytes, Workspace* out) {
@@ -54,7 +55,42 @@ static int get_workspace_slot(int device, hipStream_t stream, int slot, size_t b
   out->off = 0;
   return MMF_OK;
 }
-int get_workspace(int device, hipStream_t stream, size_t bytes, Workspace* out) { return get_workspace_slot(device, stream, 0, bytes, out); }
+
+// The prologue of every entry that takes (device_id, hip_stream), in the order it has to run.  on_device() is the entry's first
+// check.  Then come its checks of the host arguments: with device_id = 0 on a machine without a GPU they still answer
+// MMF_E_INVALID, not MMF_E_HIP.  Then begin(): it sets the device (restored when the Call goes) and only then gives out the
+// caller's stream and a workspace, so neither can be had past a refused device or ahead of the host checks.
+struct Call {
+  const char* who;           // the entry, for error messages
+  hipStream_t s = nullptr;   // the caller's stream, from begin()
+  Workspace ws;              // the call's slot-0 workspace, from begin(bytes)
+  Call(const char* who_, int device_id, void* hip_stream) : who(who_), device(device_id), stream(static_cast<hipStream_t>(hip_stream)) {}
+  int on_device() const {
+    if (device >= 0) return MMF_OK;
+    set_error("%s: device_id %d: no CPU path (the CPU restatement is oracle/, tests only)", who, device);
+    return MMF_E_UNSUPPORTED;
+  }
+  int begin() {
+    MMF_TRY(on_device());
+    guard.emplace(device);
+    if (!guard->ok) { set_error("hipSetDevice(%d) failed", device); return MMF_E_HIP; }
+    s = stream;
+    return MMF_OK;
+  }
+  int begin(size_t bytes) {
+    MMF_TRY(begin());
+    return workspace(bytes, &ws);
+  }
+  // after begin(): a workspace whose size only work behind begin() settles, or (slot 1) what a rare branch needs on top
+  int workspace(size_t bytes, Workspace* out, int slot = 0) const {
+    if (!guard) { set_error("%s: workspace before begin() (internal invariant)", who); return MMF_E_INTERNAL; }
+    return get_workspace_slot(device, stream, slot, bytes, out);
+  }
+
+ private:
+  int device; hipStream_t stream;
+  std::optional<DeviceGuard> guard;
+};
 
 struct StageBlock { char* host = nullptr; size_t cap = 0; hipEvent_t passed = nullptr; bool in_flight = false; };
 static std::map<std::pair<int, hipStream_t>, std::vector<StageBlock>> g_stage;
@@ -95,47 +131,38 @@ int upload_table(hipStream_t s, void* dst, const void* src_host, size_t bytes) {
   return MMF_OK;
 }
 
-int launch_edge_cosine_impl(const void* X, int64_t d, int dtype, const float* nrm, const int64_t* ei, int64_t E,
-                            float* out, hipStream_t s);
-
-// mmf_scan_bf16.hip (fast path)
-int scan_bf16_supported(int64_t d, int kk, int dtype);
-int scan_bf16_cap(int kk, int dp);
-int scan_bf16_dp(int64_t d);
-int launch_prep_half(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
-                     const uint32_t* max_n, void* Z,
-                     int64_t n_pad, int dp, int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima,
-                     hipStream_t s);
-int launch_scan_b16(const void* ZQ, const void* ZC, const float* cb, const float* q_zn, const float* q_rn,
-                    const float* q_un, const uint32_t* maxima, int64_t n_rows, int64_t m, int64_t m_pad, int dp,
-                    int64_t d, bool f16, int metric, int kk, int col_splits, const CandLists& L, void* scratch,
-                    const ScanB16Panel& pn, hipStream_t s, int* grid_out);
-int launch_scan_b16_audit(const ScanB16Panel& pn, uint32_t* overflow, int64_t n_rows, hipStream_t s);
-size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G);
-int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const float* rn, const float* un, const uint32_t* maxima,
-                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, const CandLists& L, void* scratch,
-                        const SymBuffers& sb, std::vector<int32_t>& tab, const ScanB16Panel& pn, hipStream_t s, int* grid_out);
-size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap);
-int scan_bf16_slot_ulp(int cap);
-int scan_b16_queries_per_block(int dp);
-int launch_prep_half_gather(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
-                            const uint32_t* max_n, const int32_t* gather, void* Z, int64_t n_pos, int64_t n_pad, int dp,
-                            int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima, hipStream_t s);
-size_t scan_b16_seg_scratch_bytes(int64_t grid, int dp, int cap);
-int launch_scan_b16_seg(const void* ZQ, const void* ZC, const float* cb, const float* q_zn, const float* q_rn,
-                        const float* q_un, const uint32_t* maxima, const int32_t* sched, int64_t grid, int64_t n_rows,
-                        int64_t m, int dp, int64_t d, bool f16, int metric, int kk, const CandLists& L, void* scratch,
-                        const ScanB16Panel& pn, hipStream_t s);
-
-static int check_common(const void* X, int64_t n, int64_t m, int64_t d, int in_dtype, int device_id) {
-  if (device_id < 0) {
-    set_error("device_id %d: this library has no CPU path (the CPU restatement is oracle/, tests only)", device_id);
-    return MMF_E_UNSUPPORTED;
-  }
+// The first checks of an entry that takes rows of features: the device, then shapes and dtype.
+static int check_common(const Call& c, const void* X, int64_t n, int64_t m, int64_t d, int in_dtype) {
+  MMF_TRY(c.on_device());
   if (n < 0 || m < 0 || d < 1) { set_error("bad shape n=%lld m=%lld d=%lld", (long long)n, (long long)m, (long long)d); return MMF_E_INVALID; }
   if (in_dtype != MMF_F32 && in_dtype != MMF_BF16 && in_dtype != MMF_F16) { set_error("bad in_dtype %d", in_dtype); return MMF_E_INVALID; }
   if (n > 0 && !X) { set_error("X is NULL"); return MMF_E_INVALID; }
   if (n >= (int64_t)1 << 31 || m >= (int64_t)1 << 31) { set_error("n and m must be < 2^31"); return MMF_E_UNSUPPORTED; }
+  return MMF_OK;
+}
+
+// The host offsets ptr[n_seg + 1] of a segmented entry (`name`: the array as the caller knows it): n_seg >= min_seg segments,
+// start at 0, never decrease, at least min_rows per segment, end at `rows` (kAnyRows: wherever they end).
+static constexpr int64_t kAnyRows = -1;
+static int check_offsets(const char* who, const char* name, const int64_t* ptr, int64_t n_seg, int64_t min_seg, int64_t min_rows,
+                         int64_t rows) {
+  if (n_seg < min_seg || !ptr) {
+    set_error("%s: need n_seg >= %lld and host offsets %s[n_seg + 1]", who, (long long)min_seg, name);
+    return MMF_E_INVALID;
+  }
+  if (ptr[0] != 0) { set_error("%s: %s must start at 0 (got %lld)", who, name, (long long)ptr[0]); return MMF_E_INVALID; }
+  for (int64_t g = 0; g < n_seg; ++g) {
+    const int64_t ns = ptr[g + 1] - ptr[g];
+    if (ns < 0) { set_error("%s: %s decreases at segment %lld", who, name, (long long)g); return MMF_E_INVALID; }
+    if (ns < min_rows) {
+      set_error("%s: segment %lld has %lld rows in %s, need at least %lld", who, (long long)g, (long long)ns, name, (long long)min_rows);
+      return MMF_E_INVALID;
+    }
+  }
+  if (rows != kAnyRows && ptr[n_seg] != rows) {
+    set_error("%s: %s must end at %lld (got %lld)", who, name, (long long)rows, (long long)ptr[n_seg]);
+    return MMF_E_INVALID;
+  }
   return MMF_OK;
 }
 
@@ -209,22 +236,22 @@ static int64_t admissible_columns(int64_t r0, int64_t n, int64_t c0, int64_t m, 
   return m - (o ? 1 : 0);
 }
 
-// One simtopk call (`who`: the entry, for error messages): its arguments, and what check() derives from them.
+// One simtopk call: its prologue (`call`), its arguments, and what check() derives from them.
 struct Request {
-  const char* who;
+  Call call;
   const void* X; int64_t n; const void* Y; int64_t m; int64_t d; int dtype, metric; float lambda;
   int k, exclude_self; int64_t row_offset, col_offset;   // ids reported: row_offset + row of X, col_offset + row of Y
-  int64_t* out_idx; float* out_val; mmf_simtopk_stats* stats; bool profile; hipStream_t s;
+  int64_t* out_idx; float* out_val; mmf_simtopk_stats* stats; bool profile;
   int kk = 0;                       // entries a row's lists keep: k, + 1 when self is excluded
   int precision = MMF_PREC_AUTO;    // resolved: MMF_PREC_EXACT, _FAST or _FAST_BF16
-  std::optional<DeviceGuard> guard;
 
-  // The checks every simtopk entry makes, in this order: shapes / dtype / device, metric, lambda, k, the entry's own
+  // The checks every simtopk entry makes, in this order: device / shapes / dtype, metric, lambda, k, the entry's own
   // (`entry_checks`); stats zeroed; then, when there are rows: outputs, admissible columns (of the whole block unless
   // `per_segment`), device, precision (`prec`: requested, or fixed by the operands; AUTO: the 16-bit scan if it applies).
   template <class F>
-  int check(int prec, bool per_segment, int device_id, F&& entry_checks) {
-    MMF_TRY(check_common(X, n, m, d, dtype, device_id));
+  int check(int prec, bool per_segment, F&& entry_checks) {
+    const char* who = call.who;
+    MMF_TRY(check_common(call, X, n, m, d, dtype));
     if (metric < MMF_DOT || metric > MMF_RBF) { set_error("%s: bad metric %d", who, metric); return MMF_E_INVALID; }
     if (metric == MMF_RBF && !(lambda > 0.0f)) { set_error("%s: MMF_RBF needs lambda > 0 (got %g)", who, lambda); return MMF_E_INVALID; }
     if (k < 1) { set_error("%s: k must be >= 1 (got %d)", who, k); return MMF_E_INVALID; }
@@ -239,8 +266,7 @@ struct Request {
       set_error("%s: k = %d exceeds the %lld admissible columns (m = %lld%s)", who, k, (long long)adm, (long long)m, overlap ? ", self excluded" : "");
       return MMF_E_INVALID;
     }
-    guard.emplace(device_id);
-    if (!guard->ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+    MMF_TRY(call.begin());
     const bool b16 = scan_bf16_supported(d, kk, dtype);
     precision = prec == MMF_PREC_AUTO ? (b16 ? MMF_PREC_FAST : MMF_PREC_EXACT) : prec;
     if (precision != MMF_PREC_EXACT && precision != MMF_PREC_FAST && precision != MMF_PREC_FAST_BF16) { set_error("%s: bad precision %d", who, precision); return MMF_E_INVALID; }
@@ -249,6 +275,16 @@ struct Request {
       return MMF_E_UNSUPPORTED;
     }
     return MMF_OK;
+  }
+
+  // The re-rank of the whole call: operands, metric, k, id offsets, outputs.  The caller adds the row scalars, the flag block
+  // and what its lists need.
+  SelectProblem select() const {
+    SelectProblem q{};
+    q.X = X; q.n = n; q.Y = Y; q.m = m; q.d = d; q.dtype = dtype; q.metric = metric; q.lambda = lambda;
+    q.k = k; q.exclude_self = exclude_self; q.row_offset = row_offset; q.col_offset = col_offset;
+    q.n_rows = n; q.out_idx = out_idx; q.out_val = out_val;
+    return q;
   }
 };
 
@@ -283,6 +319,27 @@ static CandLists carve_b16_lists(Workspace& ws, int64_t n, int lists, int bcap) 
   L.spill_stacks = (lists == 2 && !getenv("MMF_SPILL_COUNTER")) ? 1 : 0;   // one pair: its two lanes fill the slots from both ends
   return L;
 }
+
+// What the re-rank of a 16-bit scan leaves for the host: the rows it could not certify (fail_rows; their count in word 0 of
+// fail_count, word 1: of them, those whose lists overflowed, word 2: those that came up short) and its candidate counters.
+struct FlagBlock {
+  int32_t* fail_rows = nullptr; uint32_t *fail_count = nullptr, *cand_total = nullptr;
+  uint32_t h_fail4[4] = {0, 0, 0, 0};
+  std::vector<uint32_t> h_tot;   // read() with totals: the 256 counters, else empty
+  static size_t bytes(int64_t n) { return ws_bytes(n, 4) + ws_bytes(4, 4) + ws_bytes(256, 4); }
+  void carve(Workspace& ws, int64_t n) { fail_rows = ws.take<int32_t>(n); fail_count = ws.take<uint32_t>(4); cand_total = ws.take<uint32_t>(256); }
+  int zero(hipStream_t s) const {
+    MMF_HIP(hipMemsetAsync(fail_count, 0, 16, s)); MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
+    return MMF_OK;
+  }
+  int read(bool totals, hipStream_t s) {   // synchronises the stream
+    MMF_HIP(hipMemcpyAsync(h_fail4, fail_count, 16, hipMemcpyDeviceToHost, s));
+    h_tot.assign(totals ? 256 : 0, 0);
+    if (totals) MMF_HIP(hipMemcpyAsync(h_tot.data(), cand_total, 1024, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    return MMF_OK;
+  }
+};
 
 // The symmetric 16-bit scan (launch_scan_b16_sym) applies to X against itself with equal id offsets, cosine or dot (no
 // per-candidate bias), padded dim 512, 15-entry lists, no forced column splits, and an operand image inside the 32-bit tile
@@ -373,10 +430,10 @@ struct ExactPass {
 
   int read_fails(const ExactLists& B, std::vector<uint32_t>* h_tot) const {
     uint32_t h_fail = 0;
-    MMF_HIP(hipMemcpyAsync(&h_fail, B.fail_count, 4, hipMemcpyDeviceToHost, r.s));
-    if (h_tot) MMF_HIP(hipMemcpyAsync(h_tot->data(), cand_total, 1024, hipMemcpyDeviceToHost, r.s));
-    MMF_HIP(hipStreamSynchronize(r.s));
-    if (h_fail != 0) { set_error("%s: %u rows failed in the exact scan (internal invariant)", r.who, h_fail); return MMF_E_INTERNAL; }
+    MMF_HIP(hipMemcpyAsync(&h_fail, B.fail_count, 4, hipMemcpyDeviceToHost, r.call.s));
+    if (h_tot) MMF_HIP(hipMemcpyAsync(h_tot->data(), cand_total, 1024, hipMemcpyDeviceToHost, r.call.s));
+    MMF_HIP(hipStreamSynchronize(r.call.s));
+    if (h_fail != 0) { set_error("%s: %u rows failed in the exact scan (internal invariant)", r.call.who, h_fail); return MMF_E_INTERNAL; }
     return MMF_OK;
   }
 
@@ -384,7 +441,7 @@ struct ExactPass {
   // fail count is read back and B starts over.  t: the plain exact call's timers (prep, started by the caller; scan; re-rank), else null.
   // h_tot: the candidate counters (cand_total), read back with the fail count.
   int run(Workspace& ws, const ExactLists& B, EventTimer* t = nullptr, std::vector<uint32_t>* h_tot = nullptr) {
-    const hipStream_t s = r.s;
+    const hipStream_t s = r.call.s;
     const int64_t dpad = prep_f32_dim(r.d);
     const size_t row_bytes = (size_t)r.d * dtype_size(r.dtype);
     auto image = [&](int64_t rows) { return reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(rows, r.d))); };
@@ -413,13 +470,11 @@ struct ExactPass {
       sp.Xp = G.gathered ? Xe + (G.row0 - batch0) * dpad : Xp + r0 * dpad; sp.Yp = Yp + G.col0 * dpad;
       sp.rx = rx + r0; sp.cy = cy + G.col0; sp.row_ids = G.gathered ? row_ids + G.row0 : nullptr; sp.n_rows = G.rows;
       sp.col_splits = L.lists / 2;
-      SelectProblem q{};   // (exact lists have no overflow lists: nothing for a second select launch)
-      q.X = sp.X; q.n = sp.n; q.Y = sp.Y; q.m = sp.m; q.d = r.d; q.dtype = r.dtype; q.metric = r.metric; q.lambda = r.lambda;
-      q.exclude_self = r.exclude_self; q.row_offset = r.row_offset + r0; q.col_offset = r.col_offset + G.col0;
+      SelectProblem q = r.select();   // this piece of it (exact lists have no overflow lists: nothing for a second select launch)
+      q.X = sp.X; q.n = sp.n; q.Y = sp.Y; q.m = sp.m; q.row_offset += r0; q.col_offset += G.col0;
       q.rx = sp.rx; q.cy = sp.cy; q.row_ids = sp.row_ids; q.n_rows = G.rows;
-      q.out_idx = r.out_idx + r0 * r.k; q.out_val = r.out_val + r0 * r.k; q.out_stride = r.k;
+      q.out_idx += r0 * r.k; q.out_val += r0 * r.k; q.out_stride = r.k;
       q.fail_rows = B.fail_rows; q.fail_count = B.fail_count; q.cand_total = cand_total;
-      q.two_pass = false; q.order_scratch = nullptr; q.perm = nullptr;
       // k + self beyond 44: several passes, each offering only what ranks after the previous pass's last entry
       // (scikit-learn's n_neighbors is uncapped, preprocess_hypergraph.py:379)
       int g = 0;
@@ -464,8 +519,7 @@ struct FastTail {
   int64_t n, m; int kk, cap, bcap, splits, lists, fb_splits; int64_t FB;
   CandLists L;
   ExactLists XL;   // the exact rescan of flagged rows, FB rows at a time
-  int32_t* fail_rows = nullptr;
-  uint32_t *fail_count = nullptr, *cand_total = nullptr;
+  FlagBlock flags;
   char* scan_scratch = nullptr;
   char* order_scratch = nullptr;
   // query order of the scan (mmf_order.hip): near-duplicate rows next to each other.  Tried when forced, or (auto) at sizes where
@@ -561,7 +615,7 @@ struct FastTail {
     return a > b ? a : b;
   }
   size_t bytes() const {
-    return b16_lists_bytes(n, lists_alloc, bcap) + ws_bytes(n, 4) + ws_bytes(4, 4) + ws_bytes(256, 4) +
+    return b16_lists_bytes(n, lists_alloc, bcap) + FlagBlock::bytes(n) +
            ExactLists::bytes(FB, (size_t)FB * 2 * fb_splits, cap, false) + ws_bytes(scan_scratch_bytes(), 1) +
            (sym_try ? ws_bytes(n, 4) + 2 * ws_bytes((size_t)n * kSymCap, 4) + SymBuffers::bytes(n_pad_q(), sym_grid()) : 0) +
            ws_bytes(2 * n_seed, 4) + ws_bytes((size_t)rows_exact_cap * m, 4) + ws_bytes(select_order_bytes(n), 1) +
@@ -573,9 +627,7 @@ struct FastTail {
       sym_cnt = ws.take<uint32_t>(n); sym_ids = ws.take<uint32_t>((size_t)n * kSymCap); sym_keys = ws.take<float>((size_t)n * kSymCap);
       sym.carve(ws, n_pad_q(), sym_grid());
     }
-    fail_rows = ws.take<int32_t>(n);
-    fail_count = ws.take<uint32_t>(4);
-    cand_total = ws.take<uint32_t>(256);
+    flags.carve(ws, n);
     XL.carve(ws, FB, (size_t)FB * 2 * fb_splits, cap, false);
     scan_scratch = ws.take<char>(scan_scratch_bytes());
     seed = ws.take<int32_t>(2 * n_seed);
@@ -588,7 +640,7 @@ struct FastTail {
     }
   }
   int run(const Request& r, const FastOperands& fo_in, void* select_wait_event) {
-    const hipStream_t s = r.s;
+    const hipStream_t s = r.call.s;
     const bool profile = r.profile;
     FastOperands fo = fo_in;
     query_order_forget();
@@ -606,8 +658,7 @@ struct FastTail {
     const bool symmetric = sym_try && !fo.perm && fo.n_panels == 0;
     const CandLists L = view(symmetric);   // (shadows the member: the lists as this call's path uses them)
     MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
-    MMF_HIP(hipMemsetAsync(fail_count, 0, 16, s));
-    MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
+    MMF_TRY(flags.zero(s));
     EventTimer t_scan, t_sel, t_fb;
     EventTimer t_panel[16];
     int grid = 0;
@@ -662,27 +713,22 @@ struct FastTail {
     // all-gather) hands in the event that marks their arrival
     if (select_wait_event) MMF_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(select_wait_event), 0));
 
-    SelectProblem q{};
-    q.X = r.X; q.n = n; q.Y = r.Y; q.m = m; q.d = r.d; q.dtype = r.dtype; q.metric = r.metric; q.lambda = r.lambda;
-    q.k = r.k; q.exclude_self = r.exclude_self; q.row_offset = r.row_offset; q.col_offset = r.col_offset;
-    q.rx = fo.rx; q.cy = fo.cy; q.row_ids = nullptr; q.perm = fo.perm; q.n_rows = n; q.out_idx = r.out_idx; q.out_val = r.out_val;
-    q.fail_rows = fail_rows; q.fail_count = fail_count; q.cand_total = r.stats ? cand_total : nullptr;
+    SelectProblem q = r.select();
+    q.rx = fo.rx; q.cy = fo.cy; q.perm = fo.perm;
+    q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = r.stats ? flags.cand_total : nullptr;
     q.two_pass = true;
     q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
     MMF_TRY(t_sel.start(profile, s));
     MMF_TRY(launch_select(q, L, s));
     MMF_TRY(t_sel.stop(s));
 
-    uint32_t h_fail4[4] = {0, 0, 0, 0};
-    MMF_HIP(hipMemcpyAsync(h_fail4, fail_count, 16, hipMemcpyDeviceToHost, s));
-    std::vector<uint32_t> h_tot(r.stats ? 256 : 0);
-    if (r.stats) MMF_HIP(hipMemcpyAsync(h_tot.data(), cand_total, 1024, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipStreamSynchronize(s));
+    MMF_TRY(flags.read(r.stats != nullptr, s));
+    const uint32_t* h_fail4 = flags.h_fail4;
     const uint32_t h_fail = h_fail4[0];
     if (h_fail > 0 && getenv("MMF_DEBUG_PRINT_FLAGGED")) {   // diagnosis: which rows, and the threshold / dropped key that flagged them
       const uint32_t nshow = h_fail < 8 ? h_fail : 8;
       int32_t rows[8];
-      MMF_HIP(hipMemcpy(rows, fail_rows, nshow * sizeof(int32_t), hipMemcpyDeviceToHost));
+      MMF_HIP(hipMemcpy(rows, flags.fail_rows, nshow * sizeof(int32_t), hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < nshow; ++i) {
         int32_t enc[2] = {0, 0};
         MMF_HIP(hipMemcpy(&enc[0], seed + rows[i], 4, hipMemcpyDeviceToHost));
@@ -698,23 +744,21 @@ struct FastTail {
       for (int64_t off = 0; off < (int64_t)h_fail; off += rows_exact_cap) {
         SelectProblem fq = q;
         fq.perm = nullptr;
-        fq.row_ids = fail_rows + off;
+        fq.row_ids = flags.fail_rows + off;
         fq.n_rows = ((int64_t)h_fail - off < rows_exact_cap) ? ((int64_t)h_fail - off) : rows_exact_cap;
         MMF_TRY(launch_rows_exact(fq, row_keys, s));
       }
     } else if (h_fail > 0) {   // the exact pass over the flagged rows; its f32 images in the second workspace slot
       ExactPass ex(r, fo.rx, fo.cy);
-      ex.row_ids = fail_rows; ex.n_ids = h_fail; ex.forced_splits = fb_splits;
+      ex.row_ids = flags.fail_rows; ex.n_ids = h_fail; ex.forced_splits = fb_splits;
       ex.add(ExactGroup{0, (int64_t)h_fail, true, 0, m, r.k});
-      int dev_now = 0;
-      MMF_HIP(hipGetDevice(&dev_now));
       Workspace aux;
-      MMF_TRY(get_workspace_slot(dev_now, s, 1, ex.image_bytes(), &aux));
+      MMF_TRY(r.call.workspace(ex.image_bytes(), &aux, 1));
       MMF_TRY(XL.zero(s));
       MMF_TRY(ex.run(aux, XL));
     }
     MMF_TRY(t_fb.stop(s));
-    fill_stats(r.stats, r.precision, symmetric ? 1 : splits, grid, 0.f, t_scan.ms(), t_sel.ms(), t_fb.ms(), h_fail, h_fail4[1], h_fail4[2], h_tot,
+    fill_stats(r.stats, r.precision, symmetric ? 1 : splits, grid, 0.f, t_scan.ms(), t_sel.ms(), t_fb.ms(), h_fail, h_fail4[1], h_fail4[2], flags.h_tot,
                near_rows);
     if (r.stats) {
       if (profile && fo.n_panels > 0) {     // what the scan stream spent waiting for panels to arrive
@@ -785,11 +829,11 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
                    float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id,
                    void* hip_stream) {
   if (!Y) { Y = X; m = n; }
-  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  Request r{"simtopk", X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset, out_idx, out_val, stats,
-            opts && opts->profile, s};
-  MMF_TRY(r.check(opts ? opts->precision : MMF_PREC_AUTO, false, device_id, [] { return MMF_OK; }));
+  Request r{Call("simtopk", device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset,
+            out_idx, out_val, stats, opts && opts->profile};
+  MMF_TRY(r.check(opts ? opts->precision : MMF_PREC_AUTO, false, [] { return MMF_OK; }));
   if (n == 0) return MMF_OK;
+  const hipStream_t s = r.call.s;
   const int forced_splits = opts ? opts->col_splits : 0;
   const bool same = (Y == X) && (m == n);
 
@@ -818,7 +862,7 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
     size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + ws_bytes((size_t)n_pad * dp, 2) + ws_bytes((size_t)m_pad * dp, 2) +
                   4 * ws_bytes(n_pad, 4) + 4 * ws_bytes(m_pad, 4) + 3 * ws_bytes(4, 4) + ft.bytes();
     Workspace ws;
-    MMF_TRY(get_workspace(device_id, s, need, &ws));
+    MMF_TRY(r.call.workspace(need, &ws));
     float *rx, *cy, *q_zn, *q_rn, *q_un, *q_cb, *c_zn, *c_rn, *c_un, *c_cb;
     uint16_t *ZQ, *ZC;
     uint32_t *max_q, *max_c;
@@ -863,7 +907,7 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
   ex.add(ExactGroup{0, n, false, 0, m, k});
   const size_t need = ws_bytes(n, 4) + (same ? 0 : ws_bytes(m, 4)) + ws_bytes(256, 4) + ex.image_bytes() + ex.list_bytes();
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, need, &ws));
+  MMF_TRY(r.call.workspace(need, &ws));
   float* rx = ws.take<float>(n);
   float* cy = same ? rx : ws.take<float>(m);
   uint32_t* cand_total = ws.take<uint32_t>(256);
@@ -900,20 +944,20 @@ int mmf_fast_scan_supported(int64_t d, int k, int exclude_self) {
 
 int mmf_row_scalars(const void* X, int64_t n, int64_t d, int in_dtype, int metric, float* scal, float* max_sq_norm,
                     int device_id, void* hip_stream) {
-  MMF_TRY(check_common(X, n, n, d, in_dtype, device_id));
+  Call c("row_scalars", device_id, hip_stream);
+  MMF_TRY(check_common(c, X, n, n, d, in_dtype));
   if (metric < MMF_DOT || metric > MMF_RBF) { set_error("row_scalars: bad metric %d", metric); return MMF_E_INVALID; }
   if (n == 0) return MMF_OK;
   if (!scal) { set_error("row_scalars: NULL output"); return MMF_E_INVALID; }
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  return launch_row_scalars(X, n, d, in_dtype, metric, scal, reinterpret_cast<uint32_t*>(max_sq_norm),
-                            static_cast<hipStream_t>(hip_stream));
+  MMF_TRY(c.begin());
+  return launch_row_scalars(X, n, d, in_dtype, metric, scal, reinterpret_cast<uint32_t*>(max_sq_norm), c.s);
 }
 
 int mmf_prep_rows(const void* X, int64_t n, int64_t d, int in_dtype, int metric, int operand, const float* scal,
                   const float* max_sq_norm, void* Z, int64_t n_pad, float* zn, float* rn, float* un, float* cb,
                   float* maxima, int device_id, void* hip_stream) {
-  MMF_TRY(check_common(X, n, n, d, in_dtype, device_id));
+  Call c("prep_rows", device_id, hip_stream);
+  MMF_TRY(check_common(c, X, n, n, d, in_dtype));
   if (metric < MMF_DOT || metric > MMF_RBF) { set_error("prep_rows: bad metric %d", metric); return MMF_E_INVALID; }
   if (operand != MMF_F16 && operand != MMF_BF16) { set_error("prep_rows: operand must be MMF_F16 or MMF_BF16"); return MMF_E_INVALID; }
   const int dp = scan_bf16_dp(d);
@@ -923,11 +967,9 @@ int mmf_prep_rows(const void* X, int64_t n, int64_t d, int in_dtype, int metric,
   if (!scal || !Z || !zn || !rn || !un || !cb || !maxima || (metric != MMF_COSINE && !max_sq_norm)) {
     set_error("prep_rows: NULL pointer"); return MMF_E_INVALID;
   }
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  MMF_TRY(c.begin());
   return launch_prep_half(X, n, d, in_dtype, metric, scal, reinterpret_cast<const uint32_t*>(max_sq_norm), Z, n_pad, dp,
-                          operand == MMF_F16 ? 1 : 0, zn, rn, un, cb, reinterpret_cast<uint32_t*>(maxima),
-                          static_cast<hipStream_t>(hip_stream));
+                          operand == MMF_F16 ? 1 : 0, zn, rn, un, cb, reinterpret_cast<uint32_t*>(maxima), c.s);
 }
 
 int mmf_simtopk_prepared(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
@@ -935,9 +977,9 @@ int mmf_simtopk_prepared(const void* X, int64_t n, const void* Y, int64_t m, int
                          const mmf_prepared_side* q, const mmf_prepared_side* c, int64_t m_pad, const float* maxima,
                          int operand, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
                          mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
-  Request r{"simtopk_prepared", X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset, out_idx, out_val,
-            stats, opts && opts->profile, static_cast<hipStream_t>(hip_stream)};
-  MMF_TRY(r.check(operand == MMF_F16 ? MMF_PREC_FAST : MMF_PREC_FAST_BF16, false, device_id, [&] {
+  Request r{Call("simtopk_prepared", device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset,
+            col_offset, out_idx, out_val, stats, opts && opts->profile};
+  MMF_TRY(r.check(operand == MMF_F16 ? MMF_PREC_FAST : MMF_PREC_FAST_BF16, false, [&] {
     if (!Y || !q || !c || !maxima) { set_error("simtopk_prepared: NULL pointer"); return MMF_E_INVALID; }
     if (operand != MMF_F16 && operand != MMF_BF16) { set_error("simtopk_prepared: bad operand"); return MMF_E_INVALID; }
     if (m_pad < m || (m_pad % 256) != 0) { set_error("simtopk_prepared: m_pad must be a multiple of 256 and >= m"); return MMF_E_INVALID; }
@@ -947,7 +989,7 @@ int mmf_simtopk_prepared(const void* X, int64_t n, const void* Y, int64_t m, int
   FastTail ft(n, m, r.kk, opts ? opts->col_splits : 0, scan_bf16_dp(d));
   MMF_TRY(ft.set_query_order(opts ? opts->query_order : MMF_QUERY_ORDER_AUTO));
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, r.s, ft.bytes(), &ws));
+  MMF_TRY(r.call.workspace(ft.bytes(), &ws));
   ft.carve(ws);
   FastOperands fo{static_cast<const uint16_t*>(q->Z), static_cast<const uint16_t*>(c->Z), q->scal, c->scal, q->zn, q->rn, q->un,
                   c->cb, reinterpret_cast<const uint32_t*>(maxima), m_pad, scan_bf16_dp(d), operand == MMF_F16};
@@ -959,10 +1001,10 @@ int mmf_simtopk_panels(const void* X, int64_t n, const void* Y, int64_t m, int64
                        const mmf_prepared_side* q, const float* c_scal, const mmf_panel* panels, int n_panels,
                        const float* maxima, int operand, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
                        mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
-  Request r{"simtopk_panels", X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset, out_idx, out_val,
-            stats, opts && opts->profile, static_cast<hipStream_t>(hip_stream)};
+  Request r{Call("simtopk_panels", device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset,
+            col_offset, out_idx, out_val, stats, opts && opts->profile};
   int64_t m_min = m, m_max = 0;
-  MMF_TRY(r.check(operand == MMF_F16 ? MMF_PREC_FAST : MMF_PREC_FAST_BF16, false, device_id, [&] {
+  MMF_TRY(r.check(operand == MMF_F16 ? MMF_PREC_FAST : MMF_PREC_FAST_BF16, false, [&] {
     if (!Y || !q || !c_scal || !panels || !maxima) { set_error("simtopk_panels: NULL pointer"); return MMF_E_INVALID; }
     if (operand != MMF_F16 && operand != MMF_BF16) { set_error("simtopk_panels: bad operand"); return MMF_E_INVALID; }
     if (n_panels < 1 || n_panels > 16) { set_error("simtopk_panels: n_panels must be in 1..16"); return MMF_E_INVALID; }
@@ -990,7 +1032,7 @@ int mmf_simtopk_panels(const void* X, int64_t n, const void* Y, int64_t m, int64
     return MMF_E_UNSUPPORTED;
   }
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, r.s, ft.bytes(), &ws));
+  MMF_TRY(r.call.workspace(ft.bytes(), &ws));
   ft.carve(ws);
   FastOperands fo{static_cast<const uint16_t*>(q->Z), nullptr, q->scal, c_scal, q->zn, q->rn, q->un,
                   nullptr, reinterpret_cast<const uint32_t*>(maxima), 0, scan_bf16_dp(d), operand == MMF_F16};
@@ -1000,48 +1042,45 @@ int mmf_simtopk_panels(const void* X, int64_t n, const void* Y, int64_t m, int64
 
 int mmf_topk_merge(const int64_t* ia, const float* va, const int64_t* ib, const float* vb, int64_t n, int k,
                    int64_t* io, float* vo, int device_id, void* hip_stream) {
-  if (device_id < 0) { set_error("topk_merge: no CPU path"); return MMF_E_UNSUPPORTED; }
+  Call c("topk_merge", device_id, hip_stream);
+  MMF_TRY(c.on_device());
   if (n < 0 || k < 1) { set_error("topk_merge: bad n/k"); return MMF_E_INVALID; }
   if (n == 0) return MMF_OK;
   if (!ia || !va || !ib || !vb || !io || !vo) { set_error("topk_merge: NULL pointer"); return MMF_E_INVALID; }
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  return launch_topk_merge(ia, va, ib, vb, n, k, io, vo, static_cast<hipStream_t>(hip_stream));
+  MMF_TRY(c.begin());
+  return launch_topk_merge(ia, va, ib, vb, n, k, io, vo, c.s);
 }
 
 int mmf_edge_cosine(const void* X, int64_t n, int64_t d, int in_dtype, const int64_t* edge_index, int64_t E,
                     float* out_w, int device_id, void* hip_stream) {
-  MMF_TRY(check_common(X, n, n, d, in_dtype, device_id));
+  Call c("edge_cosine", device_id, hip_stream);
+  MMF_TRY(check_common(c, X, n, n, d, in_dtype));
   if (E < 0) { set_error("edge_cosine: E < 0"); return MMF_E_INVALID; }
   if (E == 0) return MMF_OK;
   if (!edge_index || !out_w) { set_error("edge_cosine: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(n, 4), &ws));
-  float* nrm = ws.take<float>(n);
-  MMF_TRY(launch_row_scalars(X, n, d, in_dtype, MMF_COSINE, nrm, nullptr, s));
-  return launch_edge_cosine_impl(X, d, in_dtype, nrm, edge_index, E, out_w, s);
+  MMF_TRY(c.begin(ws_bytes(n, 4)));
+  float* nrm = c.ws.take<float>(n);
+  MMF_TRY(launch_row_scalars(X, n, d, in_dtype, MMF_COSINE, nrm, nullptr, c.s));
+  return launch_edge_cosine_impl(X, d, in_dtype, nrm, edge_index, E, out_w, c.s);
 }
 
 int mmf_sim_dense(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
                   float lambda, float* out, int device_id, void* hip_stream) {
   if (!Y) { Y = X; m = n; }
-  MMF_TRY(check_common(X, n, m, d, in_dtype, device_id));
+  Call c("sim_dense", device_id, hip_stream);
+  MMF_TRY(check_common(c, X, n, m, d, in_dtype));
   if (metric < MMF_DOT || metric > MMF_RBF_DIRECT) { set_error("sim_dense: bad metric %d", metric); return MMF_E_INVALID; }
   if (n == 0 || m == 0) return MMF_OK;
   if (!out) { set_error("sim_dense: NULL output"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  MMF_TRY(c.begin());
+  const hipStream_t s = c.s;
   const bool same = (Y == X) && (m == n);
   float *rx = nullptr, *cy = nullptr, *Xp = nullptr, *Yp = nullptr;
   if (metric != MMF_RBF_DIRECT) {
     const bool img = sim_dense_needs_images(d, metric);
     Workspace ws;
-    MMF_TRY(get_workspace(device_id, s, ws_bytes(n, 4) + ws_bytes(m, 4) +
-                          (img ? ws_bytes(prep_f32_bytes(m, d), 1) + (same ? 0 : ws_bytes(prep_f32_bytes(n, d), 1)) : 0), &ws));
+    MMF_TRY(c.workspace(ws_bytes(n, 4) + ws_bytes(m, 4) +
+                        (img ? ws_bytes(prep_f32_bytes(m, d), 1) + (same ? 0 : ws_bytes(prep_f32_bytes(n, d), 1)) : 0), &ws));
     rx = ws.take<float>(n);
     cy = same ? rx : ws.take<float>(m);
     MMF_TRY(launch_row_scalars(X, n, d, in_dtype, metric, rx, nullptr, s));
@@ -1059,19 +1098,17 @@ int mmf_sim_dense(const void* X, int64_t n, const void* Y, int64_t m, int64_t d,
 int mmf_sim_dense_stats(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric, float lambda,
                         float* out, double* out_stats, int64_t panel_rows, int device_id, void* hip_stream) {
   if (!Y) { Y = X; m = n; }
-  MMF_TRY(check_common(X, n, m, d, in_dtype, device_id));
+  Call c("sim_dense_stats", device_id, hip_stream);
+  MMF_TRY(check_common(c, X, n, m, d, in_dtype));
   if (metric < MMF_DOT || metric > MMF_RBF_DIRECT) { set_error("sim_dense_stats: bad metric %d", metric); return MMF_E_INVALID; }
   if (n < 1 || m < 1) { set_error("sim_dense_stats: empty matrix"); return MMF_E_INVALID; }
   if (!out_stats) { set_error("sim_dense_stats: NULL out_stats"); return MMF_E_INVALID; }
   if (!out && metric != MMF_RBF_DIRECT) { set_error("sim_dense_stats: out == NULL is supported for MMF_RBF_DIRECT only"); return MMF_E_UNSUPPORTED; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const int64_t count = n * m;
   if (metric != MMF_RBF_DIRECT) {        // matrix-core dense kernels, then one reduction pass + the radix select
     MMF_TRY(mmf_sim_dense(X, n, Y, m, d, in_dtype, metric, lambda, out, device_id, hip_stream));
     return mmf_array_stats(out, count, out_stats, device_id, hip_stream);
   }
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
   int64_t R = n;
   if (!out) {                            // nothing stored: rows recomputed in panels for each radix pass
     R = panel_rows > 0 ? panel_rows : (int64_t(1) << 30) / (4 * m);
@@ -1082,13 +1119,13 @@ int mmf_sim_dense_stats(const void* X, int64_t n, const void* Y, int64_t m, int6
   int64_t blocks = 0;
   for (int64_t r0 = 0; r0 < n; r0 += R) blocks += rbf_direct_blocks((n - r0 < R) ? (n - r0) : R, m);
   const size_t mneed = median_scratch_bytes((unsigned long long)count);
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes((size_t)blocks * stat_partial_bytes(), 1) + ws_bytes(64, 4) + ws_bytes(mneed, 1) +
-                                      (out ? 0 : ws_bytes((size_t)R * m, 4)), &ws));
-  char* part = ws.take<char>((size_t)blocks * stat_partial_bytes());
-  float* pivot = ws.take<float>(64);
+  MMF_TRY(c.begin(ws_bytes((size_t)blocks * stat_partial_bytes(), 1) + ws_bytes(64, 4) + ws_bytes(mneed, 1) +
+                          (out ? 0 : ws_bytes((size_t)R * m, 4))));
+  const hipStream_t s = c.s;
+  char* part = c.ws.take<char>((size_t)blocks * stat_partial_bytes());
+  float* pivot = c.ws.take<float>(64);
   float* med = pivot + 8;
-  void* mscratch = ws.take<char>(mneed);
+  void* mscratch = c.ws.take<char>(mneed);
   MMF_TRY(launch_rbf_direct_pivot(X, Y, d, in_dtype, lambda, pivot, s));
   if (out) {
     MMF_TRY(launch_rbf_direct(X, n, Y, m, d, in_dtype, lambda, out, part, pivot, s));
@@ -1096,7 +1133,7 @@ int mmf_sim_dense_stats(const void* X, int64_t n, const void* Y, int64_t m, int6
   } else {
     // the matrix is never stored: every sweep of the median recomputes it panel by panel (one sweep when the sampled
     // bracket holds, four radix passes otherwise); the first sweep also leaves the statistic partials
-    float* panel = ws.take<float>((size_t)R * m);
+    float* panel = c.ws.take<float>((size_t)R * m);
     bool partials_done = false;
     const MedianSweep sweep = [&](const MedianConsume& consume) -> int {
       int64_t b0 = 0;
@@ -1123,57 +1160,52 @@ int mmf_sim_dense_stats(const void* X, int64_t n, const void* Y, int64_t m, int6
 
 int mmf_sim_dense_combined(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
                            float lambda_g, float* out, int device_id, void* hip_stream) {
-  MMF_TRY(check_common(F, n, n, d, MMF_F32, device_id));
+  Call c("sim_dense_combined", device_id, hip_stream);
+  MMF_TRY(check_common(c, F, n, n, d, MMF_F32));
   if (dp < 1) { set_error("sim_dense_combined: dp < 1"); return MMF_E_INVALID; }
   if (n == 0) return MMF_OK;
   if (!P || !out) { set_error("sim_dense_combined: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(n, 4) + ws_bytes(prep_f32_bytes(n, d), 1), &ws));
-  float* nf = ws.take<float>(n);
-  float* Fp = reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(n, d)));
+  MMF_TRY(c.begin(ws_bytes(n, 4) + ws_bytes(prep_f32_bytes(n, d), 1)));
+  const hipStream_t s = c.s;
+  float* nf = c.ws.take<float>(n);
+  float* Fp = reinterpret_cast<float*>(c.ws.take<char>(prep_f32_bytes(n, d)));
   MMF_TRY(launch_row_scalars(F, n, d, MMF_F32, MMF_RBF, nf, nullptr, s));
   MMF_TRY(launch_prep_f32(F, n, d, MMF_F32, nullptr, Fp, s));
   return launch_sim_dense_combined(Fp, P, n, d, dp, lambda_h, lambda_g, nf, 0, n, out, s);
 }
 
 int mmf_offdiag_lower_median(const float* K, int64_t n, float* out_median, int device_id, void* hip_stream) {
-  if (device_id < 0) { set_error("offdiag_lower_median: no CPU path"); return MMF_E_UNSUPPORTED; }
+  Call c("offdiag_lower_median", device_id, hip_stream);
+  MMF_TRY(c.on_device());
   if (n < 2) { set_error("offdiag_lower_median: need n >= 2 (got %lld)", (long long)n); return MMF_E_INVALID; }
   if (!K || !out_median) { set_error("offdiag_lower_median: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
   const size_t need = median_scratch_bytes((unsigned long long)n * (unsigned long long)(n - 1));
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
-  return launch_offdiag_lower_median(K, n, out_median, ws.take<char>(need), s);
+  MMF_TRY(c.begin(ws_bytes(need, 1)));
+  return launch_offdiag_lower_median(K, n, out_median, c.ws.take<char>(need), c.s);
 }
 
 // ---- cluster-shaped steps (mmf_segments.hip) ----------------------------------------------------------------------
-static int seg_common(const char* what, int64_t n, int64_t S, int device_id) {
-  if (device_id < 0) { set_error("%s: no CPU path", what); return MMF_E_UNSUPPORTED; }
-  if (n < 0 || S < 1) { set_error("%s: bad n / n_segments", what); return MMF_E_INVALID; }
-  if (S > segment_max_segments()) { set_error("%s: at most %d segments are supported (got %lld)", what, segment_max_segments(), (long long)S); return MMF_E_UNSUPPORTED; }
+static int check_cluster_counts(const Call& c, int64_t n, int64_t S) {
+  MMF_TRY(c.on_device());
+  if (n < 0 || S < 1) { set_error("%s: bad n / n_segments", c.who); return MMF_E_INVALID; }
+  if (S > segment_max_segments()) { set_error("%s: at most %d segments are supported (got %lld)", c.who, segment_max_segments(), (long long)S); return MMF_E_UNSUPPORTED; }
   return MMF_OK;
 }
 
 int mmf_segment_sort(const int64_t* labels, int64_t n, int64_t n_segments, int64_t* counts, int64_t* offsets, int64_t* order,
                      int device_id, void* hip_stream) {
-  MMF_TRY(seg_common("segment_sort", n, n_segments, device_id));
+  Call c("segment_sort", device_id, hip_stream);
+  MMF_TRY(check_cluster_counts(c, n, n_segments));
   if (!counts || !offsets || (n > 0 && (!labels || !order))) { set_error("segment_sort: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  MMF_TRY(c.begin());
+  const hipStream_t s = c.s;
   if (n == 0) {
     MMF_HIP(hipMemsetAsync(counts, 0, (size_t)n_segments * 8, s));
     MMF_HIP(hipMemsetAsync(offsets, 0, (size_t)(n_segments + 1) * 8, s));
     return MMF_OK;
   }
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(segment_sort_scratch_bytes(n, n_segments), 1) + ws_bytes(4, 4), &ws));
+  MMF_TRY(c.workspace(ws_bytes(segment_sort_scratch_bytes(n, n_segments), 1) + ws_bytes(4, 4), &ws));
   char* scratch = ws.take<char>(segment_sort_scratch_bytes(n, n_segments));
   uint32_t* bad = ws.take<uint32_t>(4);
   MMF_TRY(launch_segment_sort(labels, n, n_segments, counts, offsets, order, scratch, bad, s));
@@ -1186,70 +1218,61 @@ int mmf_segment_sort(const int64_t* labels, int64_t n, int64_t n_segments, int64
 
 int mmf_segment_mean(const float* X, int64_t n, int64_t d, const int64_t* order, const int64_t* offsets, int64_t n_segments,
                      float* out, int device_id, void* hip_stream) {
-  MMF_TRY(seg_common("segment_mean", n, n_segments, device_id));
+  Call c("segment_mean", device_id, hip_stream);
+  MMF_TRY(check_cluster_counts(c, n, n_segments));
   if (d < 1) { set_error("segment_mean: d < 1"); return MMF_E_INVALID; }
   if (!X || !order || !offsets || !out) { set_error("segment_mean: NULL pointer"); return MMF_E_INVALID; }
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  return launch_segment_mean(X, d, order, offsets, n_segments, out, static_cast<hipStream_t>(hip_stream));
+  MMF_TRY(c.begin());
+  return launch_segment_mean(X, d, order, offsets, n_segments, out, c.s);
 }
 
 int mmf_segment_offdiag_mean(const float* K, int64_t n, const int64_t* order, const int64_t* offsets, int64_t n_segments,
                              double* out_mean, int device_id, void* hip_stream) {
-  MMF_TRY(seg_common("segment_offdiag_mean", n, n_segments, device_id));
+  Call c("segment_offdiag_mean", device_id, hip_stream);
+  MMF_TRY(check_cluster_counts(c, n, n_segments));
   if (n < 1 || !K || !order || !offsets || !out_mean) { set_error("segment_offdiag_mean: NULL pointer / empty matrix"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, segment_offdiag_scratch_bytes(n), &ws));
-  return launch_segment_offdiag_mean(K, n, order, offsets, n_segments, out_mean, ws.take<char>(segment_offdiag_scratch_bytes(n)), s);
+  MMF_TRY(c.begin(segment_offdiag_scratch_bytes(n)));
+  return launch_segment_offdiag_mean(K, n, order, offsets, n_segments, out_mean, c.ws.take<char>(segment_offdiag_scratch_bytes(n)), c.s);
 }
 
 int mmf_clique_pairs(const int64_t* order, const int64_t* offsets, int64_t n, int64_t n_segments, int64_t* pair_lo,
                      int64_t* pair_hi, int64_t capacity, int64_t* out_count, int device_id, void* hip_stream) {
-  MMF_TRY(seg_common("clique_pairs", n, n_segments, device_id));
+  Call c("clique_pairs", device_id, hip_stream);
+  MMF_TRY(check_cluster_counts(c, n, n_segments));
   if (capacity < 0 || !offsets || !out_count || (n > 0 && !order) || (capacity > 0 && (!pair_lo || !pair_hi))) {
     set_error("clique_pairs: NULL pointer / bad capacity"); return MMF_E_INVALID;
   }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, clique_scratch_bytes(n, n_segments), &ws));
+  MMF_TRY(c.begin(clique_scratch_bytes(n, n_segments)));
   return launch_clique_pairs(order, offsets, n, n_segments, pair_lo, pair_hi, capacity, out_count,
-                             ws.take<char>(clique_scratch_bytes(n, n_segments)), s);
+                             c.ws.take<char>(clique_scratch_bytes(n, n_segments)), c.s);
 }
 
 int mmf_knn_pairs(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t* pair_lo, int64_t* pair_hi,
                   int64_t* out_count, int device_id, void* hip_stream) {
-  if (device_id < 0) { set_error("knn_pairs: no CPU path"); return MMF_E_UNSUPPORTED; }
+  Call c("knn_pairs", device_id, hip_stream);
+  MMF_TRY(c.on_device());
   if (n < 0 || k < 1) { set_error("knn_pairs: bad n / k"); return MMF_E_INVALID; }
   if (!out_count || (n > 0 && (!nbr || !pair_lo || !pair_hi))) { set_error("knn_pairs: NULL pointer"); return MMF_E_INVALID; }
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  return launch_knn_pairs(nbr, n, k, labels, pair_lo, pair_hi, out_count, static_cast<hipStream_t>(hip_stream));
+  MMF_TRY(c.begin());
+  return launch_knn_pairs(nbr, n, k, labels, pair_lo, pair_hi, out_count, c.s);
 }
 
 // both KMeans entries after their own argument checks: the plain fit is the one segment ptr = {0, n}
 static int kmeans_fit_run(const float* X, int64_t d, const int64_t* ptr, int64_t n_seg, int64_t k, int64_t n_init, int trials,
                           const int64_t* first_centres, const double* uniforms, int max_iter, double tol, int64_t* labels, float* centres,
-                          int64_t* seeds, double* info, bool segmented, int device_id, void* hip_stream) {
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+                          int64_t* seeds, double* info, bool segmented, Call& c) {
   size_t need = 0;
   const std::vector<int64_t> groups = kmeans_segment_groups(ptr, n_seg, d, k, n_init, trials, &need);
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
+  MMF_TRY(c.begin(ws_bytes(need, 1)));
   return launch_kmeans_fit(X, d, ptr, groups, k, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds, info,
-                           ws.take<char>(need), s, segmented);
+                           c.ws.take<char>(need), c.s, segmented);
 }
 
 int mmf_kmeans_fit(const float* X, int64_t n, int64_t d, int64_t n_clusters, int64_t n_init, int trials, const int64_t* first_centres,
                    const double* uniforms, int max_iter, double tol, int64_t* labels, float* centres, int64_t* seeds, double* info,
                    int device_id, void* hip_stream) {
-  if (device_id < 0) { set_error("kmeans_fit: no CPU path"); return MMF_E_UNSUPPORTED; }
+  Call c("kmeans_fit", device_id, hip_stream);
+  MMF_TRY(c.on_device());
   if (n < 1 || d < 1 || n_clusters < 1 || n_clusters > n || n_init < 1 || trials < 1 || trials > 64 || max_iter < 1 || !(tol >= 0.0)) {
     set_error("kmeans_fit: need 1 <= n_clusters <= n, n_init >= 1, 1 <= trials <= 64, max_iter >= 1, tol >= 0 (n = %lld, n_clusters = %lld, "
               "n_init = %lld, trials = %d, max_iter = %d)", (long long)n, (long long)n_clusters, (long long)n_init, trials, max_iter);
@@ -1264,14 +1287,14 @@ int mmf_kmeans_fit(const float* X, int64_t n, int64_t d, int64_t n_clusters, int
   for (int64_t i = 0; i < n_init; ++i)
     if (first_centres[i] < 0 || first_centres[i] >= n) { set_error("kmeans_fit: first_centres[%lld] outside [0, n)", (long long)i); return MMF_E_INVALID; }
   const int64_t ptr[2] = {0, n};
-  return kmeans_fit_run(X, d, ptr, 1, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds, info, false,
-                        device_id, hip_stream);
+  return kmeans_fit_run(X, d, ptr, 1, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds, info, false, c);
 }
 
 int mmf_kmeans_fit_segmented(const float* X, int64_t n, int64_t d, const int64_t* ptr, int64_t n_seg, int64_t n_clusters, int64_t n_init,
                              int trials, const int64_t* first_centres, const double* uniforms, int max_iter, double tol, int64_t* labels,
                              float* centres, int64_t* seeds, double* info, int device_id, void* hip_stream) {
-  if (device_id < 0) { set_error("kmeans_fit_segmented: no CPU path"); return MMF_E_UNSUPPORTED; }
+  Call c("kmeans_fit_segmented", device_id, hip_stream);
+  MMF_TRY(c.on_device());
   if (n < 1 || d < 1 || n_seg < 1 || n_clusters < 1 || n_init < 1 || trials < 1 || max_iter < 1 || !(tol >= 0.0)) {
     set_error("kmeans_fit_segmented: need n >= 1, d >= 1, n_seg >= 1, n_clusters >= 1, n_init >= 1, trials >= 1, max_iter >= 1, tol >= 0 "
               "(n = %lld, d = %lld, n_seg = %lld, n_clusters = %lld, n_init = %lld, trials = %d, max_iter = %d)", (long long)n, (long long)d,
@@ -1279,13 +1302,9 @@ int mmf_kmeans_fit_segmented(const float* X, int64_t n, int64_t d, const int64_t
     return MMF_E_INVALID;
   }
   if (!X || !ptr || !first_centres || (n_clusters > 1 && !uniforms) || !labels) { set_error("kmeans_fit_segmented: NULL pointer"); return MMF_E_INVALID; }
-  if (ptr[0] != 0 || ptr[n_seg] != n) {
-    set_error("kmeans_fit_segmented: ptr must start at 0 and end at n = %lld (got %lld, %lld)", (long long)n, (long long)ptr[0], (long long)ptr[n_seg]);
-    return MMF_E_INVALID;
-  }
-  for (int64_t s = 0; s < n_seg; ++s) {
+  MMF_TRY(check_offsets(c.who, "ptr", ptr, n_seg, 1, 0, n));
+  for (int64_t s = 0; s < n_seg; ++s) {   // scikit-learn's sentence, not the shared one
     const int64_t ns = ptr[s + 1] - ptr[s];
-    if (ns < 0) { set_error("kmeans_fit_segmented: ptr decreases at segment %lld", (long long)s); return MMF_E_INVALID; }
     if (ns < n_clusters) {
       set_error("kmeans_fit_segmented: segment %lld: n_samples=%lld should be >= n_clusters=%lld.", (long long)s, (long long)ns, (long long)n_clusters);
       return MMF_E_INVALID;
@@ -1310,79 +1329,70 @@ int mmf_kmeans_fit_segmented(const float* X, int64_t n, int64_t d, const int64_t
         return MMF_E_INVALID;
       }
     }
-  return kmeans_fit_run(X, d, ptr, n_seg, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds, info, true,
-                        device_id, hip_stream);
+  return kmeans_fit_run(X, d, ptr, n_seg, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds, info, true, c);
 }
 
 int mmf_lower_median(const float* v, int64_t count, float* out_median, int device_id, void* hip_stream) {
-  if (device_id < 0) { set_error("lower_median: no CPU path"); return MMF_E_UNSUPPORTED; }
+  Call c("lower_median", device_id, hip_stream);
+  MMF_TRY(c.on_device());
   if (count < 1) { set_error("lower_median: need count >= 1 (got %lld)", (long long)count); return MMF_E_INVALID; }
   if (!v || !out_median) { set_error("lower_median: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
   const size_t need = median_scratch_bytes((unsigned long long)count);
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
-  return launch_lower_median(v, count, out_median, ws.take<char>(need), s);
+  MMF_TRY(c.begin(ws_bytes(need, 1)));
+  return launch_lower_median(v, count, out_median, c.ws.take<char>(need), c.s);
 }
 
 int mmf_array_stats(const float* v, int64_t count, double* out_stats, int device_id, void* hip_stream) {
-  if (device_id < 0) { set_error("array_stats: no CPU path"); return MMF_E_UNSUPPORTED; }
+  Call c("array_stats", device_id, hip_stream);
+  MMF_TRY(c.on_device());
   if (count < 1) { set_error("array_stats: need count >= 1 (got %lld)", (long long)count); return MMF_E_INVALID; }
   if (!v || !out_stats) { set_error("array_stats: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(array_stats_scratch_bytes(count), 1), &ws));
-  return launch_array_stats(v, count, out_stats, ws.take<char>(array_stats_scratch_bytes(count)), s);
+  MMF_TRY(c.begin(ws_bytes(array_stats_scratch_bytes(count), 1)));
+  return launch_array_stats(v, count, out_stats, c.ws.take<char>(array_stats_scratch_bytes(count)), c.s);
 }
 
 int mmf_threshold_edges(const float* K, int64_t n, float threshold, int64_t* edge_index, float* edge_w,
                         int64_t capacity, int64_t* out_count, int device_id, void* hip_stream) {
-  if (device_id < 0) { set_error("threshold_edges: no CPU path"); return MMF_E_UNSUPPORTED; }
+  Call c("threshold_edges", device_id, hip_stream);
+  MMF_TRY(c.on_device());
   if (n < 0 || capacity < 0) { set_error("threshold_edges: bad n/capacity"); return MMF_E_INVALID; }
   if (!out_count) { set_error("threshold_edges: NULL out_count"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  MMF_HIP(hipMemsetAsync(out_count, 0, 8, s));
+  MMF_TRY(c.begin());
+  MMF_HIP(hipMemsetAsync(out_count, 0, 8, c.s));
   if (n == 0) return MMF_OK;
   if (!K || (capacity > 0 && (!edge_index || !edge_w))) { set_error("threshold_edges: NULL pointer"); return MMF_E_INVALID; }
   const size_t rows_u32 = (size_t)n * 2 + 64;
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(rows_u32, 8), &ws));
+  MMF_TRY(c.workspace(ws_bytes(rows_u32, 8), &ws));
   return launch_threshold_edges(K, n, threshold, edge_index, edge_w, capacity, out_count,
-                                reinterpret_cast<uint32_t*>(ws.take<uint64_t>(rows_u32)), rows_u32 * 2, s);
+                                reinterpret_cast<uint32_t*>(ws.take<uint64_t>(rows_u32)), rows_u32 * 2, c.s);
 }
 
 int mmf_threshold_edges_count(const float* K, int64_t n, float threshold, uint64_t* row_offsets, int64_t* out_count, int device_id,
                               void* hip_stream) {
-  if (device_id < 0) { set_error("threshold_edges_count: no CPU path"); return MMF_E_UNSUPPORTED; }
+  Call c("threshold_edges_count", device_id, hip_stream);
+  MMF_TRY(c.on_device());
   if (n < 0) { set_error("threshold_edges_count: bad n"); return MMF_E_INVALID; }
   if (!out_count || !row_offsets) { set_error("threshold_edges_count: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  MMF_TRY(c.begin());
+  const hipStream_t s = c.s;
   MMF_HIP(hipMemsetAsync(out_count, 0, 8, s));
   if (n == 0) { MMF_HIP(hipMemsetAsync(row_offsets, 0, 8, s)); return MMF_OK; }
   if (!K) { set_error("threshold_edges_count: NULL pointer"); return MMF_E_INVALID; }
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes((size_t)n, 4), &ws));
+  MMF_TRY(c.workspace(ws_bytes((size_t)n, 4), &ws));
   return launch_threshold_count(K, n, threshold, reinterpret_cast<unsigned long long*>(row_offsets), out_count, ws.take<uint32_t>((size_t)n), s);
 }
 
 int mmf_threshold_edges_fill(const float* K, int64_t n, float threshold, const uint64_t* row_offsets, int64_t* edge_index, float* edge_w,
                              int64_t capacity, int device_id, void* hip_stream) {
-  if (device_id < 0) { set_error("threshold_edges_fill: no CPU path"); return MMF_E_UNSUPPORTED; }
+  Call c("threshold_edges_fill", device_id, hip_stream);
+  MMF_TRY(c.on_device());
   if (n < 0 || capacity < 0) { set_error("threshold_edges_fill: bad n/capacity"); return MMF_E_INVALID; }
   if (n == 0 || capacity == 0) return MMF_OK;
   if (!K || !row_offsets || !edge_index || !edge_w) { set_error("threshold_edges_fill: NULL pointer"); return MMF_E_INVALID; }
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  return launch_threshold_fill(K, n, threshold, reinterpret_cast<const unsigned long long*>(row_offsets), edge_index, edge_w, capacity,
-                               static_cast<hipStream_t>(hip_stream));
+  MMF_TRY(c.begin());
+  return launch_threshold_fill(K, n, threshold, reinterpret_cast<const unsigned long long*>(row_offsets), edge_index, edge_w, capacity, c.s);
 }
 
 // ---- the same two steps for an N whose K = K_h * K_g does not fit: K is recomputed in row panels -----------------
@@ -1395,22 +1405,19 @@ static int64_t pick_panel_rows(int64_t n, int64_t panel_rows) {
 
 int mmf_combined_offdiag_median(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
                                 float lambda_g, int64_t panel_rows, float* out_median, int device_id, void* hip_stream) {
-  MMF_TRY(check_common(F, n, n, d, MMF_F32, device_id));
+  Call c("combined_offdiag_median", device_id, hip_stream);
+  MMF_TRY(check_common(c, F, n, n, d, MMF_F32));
   if (dp < 1 || n < 2) { set_error("combined_offdiag_median: need dp >= 1 and n >= 2"); return MMF_E_INVALID; }
   if (!P || !out_median) { set_error("combined_offdiag_median: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
   const int64_t R = pick_panel_rows(n, panel_rows);
-  Workspace ws;
   const unsigned long long count = (unsigned long long)n * (unsigned long long)(n - 1);
   const size_t mneed = median_scratch_bytes(count);
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(n, 4) + ws_bytes((size_t)R * n, 4) + ws_bytes(mneed, 1) +
-                        ws_bytes(prep_f32_bytes(n, d), 1), &ws));
-  float* nf = ws.take<float>(n);
-  float* Kp = ws.take<float>((size_t)R * n);
-  void* mscratch = ws.take<char>(mneed);
-  float* Fp = reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(n, d)));
+  MMF_TRY(c.begin(ws_bytes(n, 4) + ws_bytes((size_t)R * n, 4) + ws_bytes(mneed, 1) + ws_bytes(prep_f32_bytes(n, d), 1)));
+  const hipStream_t s = c.s;
+  float* nf = c.ws.take<float>(n);
+  float* Kp = c.ws.take<float>((size_t)R * n);
+  void* mscratch = c.ws.take<char>(mneed);
+  float* Fp = reinterpret_cast<float*>(c.ws.take<char>(prep_f32_bytes(n, d)));
   MMF_TRY(launch_row_scalars(F, n, d, MMF_F32, MMF_RBF, nf, nullptr, s));
   MMF_TRY(launch_prep_f32(F, n, d, MMF_F32, nullptr, Fp, s));
   // one sweep over the recomputed matrix when the sampled bracket holds (four otherwise)
@@ -1431,20 +1438,19 @@ int mmf_combined_offdiag_median(const float* F, const float* P, int64_t n, int64
 int mmf_combined_threshold_edges(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
                                  float lambda_g, float threshold, int64_t panel_rows, int64_t* edge_index, float* edge_w,
                                  int64_t capacity, int64_t* out_count, int device_id, void* hip_stream) {
-  MMF_TRY(check_common(F, n, n, d, MMF_F32, device_id));
+  Call c("combined_threshold_edges", device_id, hip_stream);
+  MMF_TRY(check_common(c, F, n, n, d, MMF_F32));
   if (dp < 1 || capacity < 0) { set_error("combined_threshold_edges: bad dp / capacity"); return MMF_E_INVALID; }
   if (!out_count) { set_error("combined_threshold_edges: NULL out_count"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  MMF_TRY(c.begin());
+  const hipStream_t s = c.s;
   MMF_HIP(hipMemsetAsync(out_count, 0, 8, s));
   if (n == 0) return MMF_OK;
   if (!P || (capacity > 0 && (!edge_index || !edge_w))) { set_error("combined_threshold_edges: NULL pointer"); return MMF_E_INVALID; }
   const int64_t R = pick_panel_rows(n, panel_rows);
   const size_t rows_u32 = (size_t)R * 2 + 64;
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(n, 4) + ws_bytes((size_t)R * n, 4) + ws_bytes(rows_u32, 8) +
-                        ws_bytes(prep_f32_bytes(n, d), 1), &ws));
+  MMF_TRY(c.workspace(ws_bytes(n, 4) + ws_bytes((size_t)R * n, 4) + ws_bytes(rows_u32, 8) + ws_bytes(prep_f32_bytes(n, d), 1), &ws));
   float* nf = ws.take<float>(n);
   float* Kp = ws.take<float>((size_t)R * n);
   uint32_t* scratch = reinterpret_cast<uint32_t*>(ws.take<uint64_t>(rows_u32));
@@ -1472,20 +1478,11 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
                           mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
   const bool self = (Y == nullptr);
   if (self) { Y = X; m = n; y_ptr_host = x_ptr_host; }
-  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  Request r{"simtopk_segmented", X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, 0, 0, out_idx, out_val, stats,
-            opts && opts->profile, s};
-  MMF_TRY(r.check(opts ? opts->precision : MMF_PREC_AUTO, true, device_id, [&] {
-    if (n_segments < 0 || !x_ptr_host || !y_ptr_host) { set_error("simtopk_segmented: bad segment offsets"); return MMF_E_INVALID; }
-    if (x_ptr_host[0] != 0 || x_ptr_host[n_segments] != n || y_ptr_host[0] != 0 || y_ptr_host[n_segments] != m) {
-      set_error("simtopk_segmented: offsets must start at 0 and end at n = %lld / m = %lld", (long long)n, (long long)m);
-      return MMF_E_INVALID;
-    }
-    for (int64_t g = 0; g < n_segments; ++g)
-      if (x_ptr_host[g + 1] < x_ptr_host[g] || y_ptr_host[g + 1] < y_ptr_host[g]) {
-        set_error("simtopk_segmented: offsets must be non-decreasing (segment %lld)", (long long)g);
-        return MMF_E_INVALID;
-      }
+  Request r{Call("simtopk_segmented", device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, 0, 0,
+            out_idx, out_val, stats, opts && opts->profile};
+  MMF_TRY(r.check(opts ? opts->precision : MMF_PREC_AUTO, true, [&] {
+    MMF_TRY(check_offsets(r.call.who, "x_ptr", x_ptr_host, n_segments, 0, 0, n));
+    MMF_TRY(check_offsets(r.call.who, "y_ptr", y_ptr_host, n_segments, 0, 0, m));
     if (m > 0 && !Y) { set_error("simtopk_segmented: Y is NULL"); return MMF_E_INVALID; }
     // (lifting this is a matter of letting the exact pass take such segments: it runs the passes k + self > 44 needs)
     if (r.kk > 44) { set_error("simtopk_segmented: k + self = %d > 44 is not supported", r.kk); return MMF_E_UNSUPPORTED; }
@@ -1497,6 +1494,7 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
   }));
   if (stats) stats->near_rows = -1;   // the query order is never probed here
   if (n == 0) return MMF_OK;
+  const hipStream_t s = r.call.s;
   const int precision = r.precision;
   const bool profile = r.profile;
   const int64_t S = n_segments;
@@ -1551,20 +1549,18 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
   const int64_t nq_pad = (nq_pos + 255) / 256 * 256, mc_pad = (mc_pos + 255) / 256 * 256;
   const int bcap = fast ? scan_bf16_cap(r.kk, dp) : 0;
   const int64_t n_seed = n;
-  size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + ws_bytes(n, 4) + ws_bytes(4, 4) + ws_bytes(256, 4);
+  size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + FlagBlock::bytes(n);
   if (grid > 0)
     need += ws_bytes((size_t)nq_pad * dp, 2) + 4 * ws_bytes(nq_pad, 4) + ws_bytes((size_t)mc_pad * dp, 2) + 4 * ws_bytes(mc_pad, 4) +
             3 * ws_bytes(4, 4) + ws_bytes(sched.size(), 4) + ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + b16_lists_bytes(n, 2, bcap) +
             ws_bytes(scan_b16_seg_scratch_bytes(grid, dp, bcap), 1) + ws_bytes(2 * (size_t)n_seed, 4) + ws_bytes(select_order_bytes(n), 1);
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, need, &ws));
+  MMF_TRY(r.call.workspace(need, &ws));
   float* rx = ws.take<float>(n);
   float* cy = self ? rx : ws.take<float>(m);
-  int32_t* fail_rows = ws.take<int32_t>(n);
-  uint32_t* fail_count = ws.take<uint32_t>(4);
-  uint32_t* cand_total = ws.take<uint32_t>(256);
-  MMF_HIP(hipMemsetAsync(fail_count, 0, 16, s));
-  MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
+  FlagBlock flags;
+  flags.carve(ws, n);
+  MMF_TRY(flags.zero(s));
 
   EventTimer t_prep, t_scan, t_sel, t_fb;
   MMF_TRY(t_prep.start(profile, s));
@@ -1573,9 +1569,8 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
   MMF_TRY(launch_row_scalars(X, n, d, in_dtype, metric, rx, max_n, s));
   if (!self && m > 0) MMF_TRY(launch_row_scalars(Y, m, d, in_dtype, metric, cy, max_n, s));
 
-  uint32_t h_fail4[4] = {0, 0, 0, 0};
+  const uint32_t* h_fail4 = flags.h_fail4;
   std::vector<int32_t> h_fail_rows;
-  std::vector<uint32_t> h_tot(stats ? 256 : 0);
   if (grid > 0) {
     const bool f16 = (precision == MMF_PREC_FAST);
     uint16_t* ZQ = ws.take<uint16_t>((size_t)nq_pad * dp);
@@ -1614,21 +1609,17 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
     MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
     MMF_TRY(t_scan.stop(s));
 
-    SelectProblem q{};
-    q.X = X; q.n = n; q.Y = Y; q.m = m; q.d = d; q.dtype = in_dtype; q.metric = metric; q.lambda = lambda;
-    q.k = k; q.exclude_self = exclude_self; q.row_offset = 0; q.col_offset = 0;
-    q.rx = rx; q.cy = cy; q.row_ids = nullptr; q.n_rows = n; q.out_idx = out_idx; q.out_val = out_val;
-    q.fail_rows = fail_rows; q.fail_count = fail_count; q.cand_total = stats ? cand_total : nullptr;
+    SelectProblem q = r.select();
+    q.rx = rx; q.cy = cy;
+    q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = stats ? flags.cand_total : nullptr;
     q.two_pass = true;
     q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
     MMF_TRY(t_sel.start(profile, s));
     MMF_TRY(launch_select(q, L, s));
     MMF_TRY(t_sel.stop(s));
-    MMF_HIP(hipMemcpyAsync(h_fail4, fail_count, 16, hipMemcpyDeviceToHost, s));
-    if (stats) MMF_HIP(hipMemcpyAsync(h_tot.data(), cand_total, 1024, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipStreamSynchronize(s));
+    MMF_TRY(flags.read(stats != nullptr, s));
     h_fail_rows.resize(h_fail4[0]);
-    if (h_fail4[0] > 0) MMF_HIP(hipMemcpy(h_fail_rows.data(), fail_rows, (size_t)h_fail4[0] * 4, hipMemcpyDeviceToHost));
+    if (h_fail4[0] > 0) MMF_HIP(hipMemcpy(h_fail_rows.data(), flags.fail_rows, (size_t)h_fail4[0] * 4, hipMemcpyDeviceToHost));
   } else {
     MMF_TRY(t_prep.stop(s));
   }
@@ -1663,10 +1654,8 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
   MMF_TRY(t_fb.start(profile && !ex.pieces.empty(), s));
   if (!ex.pieces.empty()) {   // lists and f32 images in the second workspace slot
     ex.n_ids = fallback_rows;
-    int dev_now = 0;
-    MMF_HIP(hipGetDevice(&dev_now));
     Workspace aux;
-    MMF_TRY(get_workspace_slot(dev_now, s, 1, ex.image_bytes() + ex.list_bytes() + ws_bytes(ex.n_ids, 4), &aux));
+    MMF_TRY(r.call.workspace(ex.image_bytes() + ex.list_bytes() + ws_bytes(ex.n_ids, 4), &aux, 1));
     int32_t* d_rows = aux.take<int32_t>(ex.n_ids);
     ExactLists B;
     B.carve(aux, ex.rows_total, ex.list_words, ex.cap(), false);
@@ -1680,7 +1669,7 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
   const int64_t overflow_rows = h_fail4[1] < (uint32_t)fallback_rows ? h_fail4[1] : fallback_rows;
   fill_stats(stats, grid > 0 ? precision : MMF_PREC_EXACT, 1, grid > 0 ? (int)grid : ex.grid, t_prep.ms(),
              grid > 0 ? t_scan.ms() : t_fb.ms(), t_sel.ms(), grid > 0 ? t_fb.ms() : 0.f, fallback_rows, overflow_rows,
-             fallback_rows - overflow_rows, h_tot);
+             fallback_rows - overflow_rows, flags.h_tot);
   return MMF_OK;
 }
 
@@ -1688,21 +1677,9 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
 // ---- segmented weighted hypergraph (the blocks K_s of a ragged batch) -------------------------------------------
 // DESIGN.md §4.9.  Segment s is rows ptr[s] .. ptr[s+1]-1 (host int64 offsets); its block K_s (n_s x n_s, row-major) sits at
 // kptr[s] = sum_{t<s} n_t^2 of one flat f32 buffer.  Every argument is checked here, before any device work.
-static int check_blocks(const char* what, const int64_t* ptr, int64_t n_seg, int64_t min_rows, int device_id, int64_t* n_out) {
-  if (device_id < 0) { set_error("%s: no CPU path", what); return MMF_E_UNSUPPORTED; }
-  if (n_seg < 1 || !ptr) { set_error("%s: need n_seg >= 1 and host offsets ptr[n_seg + 1]", what); return MMF_E_INVALID; }
-  if (ptr[0] != 0) { set_error("%s: ptr must start at 0 (got %lld)", what, (long long)ptr[0]); return MMF_E_INVALID; }
-  for (int64_t g = 0; g < n_seg; ++g) {
-    const int64_t ns = ptr[g + 1] - ptr[g];
-    if (ns < 0) { set_error("%s: ptr decreases at segment %lld", what, (long long)g); return MMF_E_INVALID; }
-    if (ns < min_rows) {
-      set_error("%s: segment %lld has %lld rows, need at least %lld", what, (long long)g, (long long)ns, (long long)min_rows);
-      return MMF_E_INVALID;
-    }
-  }
-  // n < 2^31 keeps sum n_s^2 <= n^2 below 2^62: every block offset fits int64
-  if (ptr[n_seg] >= ((int64_t)1 << 31)) { set_error("%s: %lld rows, must be < 2^31", what, (long long)ptr[n_seg]); return MMF_E_UNSUPPORTED; }
-  *n_out = ptr[n_seg];
+// n < 2^31 keeps sum n_s^2 <= n^2 below 2^62: every block offset fits int64
+static int check_block_rows(const char* who, int64_t n) {
+  if (n >= ((int64_t)1 << 31)) { set_error("%s: %lld rows, must be < 2^31", who, (long long)n); return MMF_E_UNSUPPORTED; }
   return MMF_OK;
 }
 
@@ -1717,24 +1694,20 @@ static std::vector<int64_t> block_offsets(const int64_t* ptr, int64_t n_seg) {
 // table (mmf_scan_f32.hip, SEG).  Block s is bit for bit mmf_sim_dense_combined(F_s, P_s).
 int mmf_sim_dense_combined_segmented(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, const int64_t* ptr_host,
                                      int64_t n_seg, float lambda_h, float lambda_g, float* out, int device_id, void* hip_stream) {
-  MMF_TRY(check_common(F, n, n, d, MMF_F32, device_id));
+  Call c("sim_dense_combined_segmented", device_id, hip_stream);
+  MMF_TRY(check_common(c, F, n, n, d, MMF_F32));   // (n < 2^31: the limit of check_block_rows)
   if (dp < 1) { set_error("sim_dense_combined_segmented: dp < 1"); return MMF_E_INVALID; }
-  int64_t rows = 0;
-  MMF_TRY(check_blocks("sim_dense_combined_segmented", ptr_host, n_seg, 0, device_id, &rows));
-  if (rows != n) { set_error("sim_dense_combined_segmented: ptr must end at n = %lld (got %lld)", (long long)n, (long long)rows); return MMF_E_INVALID; }
+  MMF_TRY(check_offsets(c.who, "ptr", ptr_host, n_seg, 1, 0, n));
   if (n == 0) return MMF_OK;
   if (!P || !out) { set_error("sim_dense_combined_segmented: NULL pointer"); return MMF_E_INVALID; }
   const std::vector<int64_t> tab = sim_dense_combined_seg_table(ptr_host, n_seg);
   const int64_t grid = (int64_t)tab.size() / 8;
   if (grid >= ((int64_t)1 << 31)) { set_error("sim_dense_combined_segmented: %lld workgroups", (long long)grid); return MMF_E_UNSUPPORTED; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(n, 4) + ws_bytes(prep_f32_bytes(n, d), 1) + ws_bytes(tab.size(), 8), &ws));
-  float* nf = ws.take<float>(n);
-  float* Fp = reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(n, d)));
-  int64_t* d_tab = ws.take<int64_t>(tab.size());
+  MMF_TRY(c.begin(ws_bytes(n, 4) + ws_bytes(prep_f32_bytes(n, d), 1) + ws_bytes(tab.size(), 8)));
+  const hipStream_t s = c.s;
+  float* nf = c.ws.take<float>(n);
+  float* Fp = reinterpret_cast<float*>(c.ws.take<char>(prep_f32_bytes(n, d)));
+  int64_t* d_tab = c.ws.take<int64_t>(tab.size());
   MMF_TRY(upload_table(s, d_tab, tab.data(), tab.size() * 8));
   MMF_TRY(launch_row_scalars(F, n, d, MMF_F32, MMF_RBF, nf, nullptr, s));
   MMF_TRY(launch_prep_f32(F, n, d, MMF_F32, nullptr, Fp, s));
@@ -1746,16 +1719,14 @@ int mmf_sim_dense_combined_segmented(const float* F, const float* P, int64_t n, 
 // launches for any n_seg, no host synchronisation.
 int mmf_offdiag_lower_median_segmented(const float* K, const int64_t* ptr_host, int64_t n_seg, float* out_median, int device_id,
                                        void* hip_stream) {
-  int64_t n = 0;
-  MMF_TRY(check_blocks("offdiag_lower_median_segmented", ptr_host, n_seg, 2, device_id, &n));
+  Call c("offdiag_lower_median_segmented", device_id, hip_stream);
+  MMF_TRY(c.on_device());
+  MMF_TRY(check_offsets(c.who, "ptr", ptr_host, n_seg, 1, 2, kAnyRows));
+  MMF_TRY(check_block_rows(c.who, ptr_host[n_seg]));
   if (!K || !out_median) { set_error("offdiag_lower_median_segmented: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
   const size_t need = offdiag_lower_median_seg_scratch_bytes(ptr_host, n_seg);
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
-  return launch_offdiag_lower_median_seg(K, ptr_host, n_seg, out_median, ws.take<char>(need), s);
+  MMF_TRY(c.begin(ws_bytes(need, 1)));
+  return launch_offdiag_lower_median_seg(K, ptr_host, n_seg, out_median, c.ws.take<char>(need), c.s);
 }
 
 // The threshold edges of every block against its own threshold (thresholds: device f32 [n_seg]): the per-slide double loop
@@ -1763,17 +1734,19 @@ int mmf_offdiag_lower_median_segmented(const float* K, const int64_t* ptr_host, 
 // row ids (ptr[s] + i, ptr[s] + j), segment-major and row-major inside a segment; segment s's start at row_offsets[ptr[s]].
 int mmf_threshold_edges_segmented_count(const float* K, const int64_t* ptr_host, int64_t n_seg, const float* thresholds,
                                         uint64_t* row_offsets, int64_t* out_count, int device_id, void* hip_stream) {
-  int64_t n = 0;
-  MMF_TRY(check_blocks("threshold_edges_segmented_count", ptr_host, n_seg, 0, device_id, &n));
+  Call c("threshold_edges_segmented_count", device_id, hip_stream);
+  MMF_TRY(c.on_device());
+  MMF_TRY(check_offsets(c.who, "ptr", ptr_host, n_seg, 1, 0, kAnyRows));
+  const int64_t n = ptr_host[n_seg];
+  MMF_TRY(check_block_rows(c.who, n));
   if (!out_count || !row_offsets || (n > 0 && (!K || !thresholds))) { set_error("threshold_edges_segmented_count: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  MMF_TRY(c.begin());
+  const hipStream_t s = c.s;
   MMF_HIP(hipMemsetAsync(out_count, 0, 8, s));
   if (n == 0) { MMF_HIP(hipMemsetAsync(row_offsets, 0, 8, s)); return MMF_OK; }
   const std::vector<int64_t> kptr = block_offsets(ptr_host, n_seg);
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, 2 * ws_bytes((size_t)n_seg + 1, 8) + ws_bytes((size_t)n, 4), &ws));
+  MMF_TRY(c.workspace(2 * ws_bytes((size_t)n_seg + 1, 8) + ws_bytes((size_t)n, 4), &ws));
   int64_t* d_ptr = ws.take<int64_t>((size_t)n_seg + 1);
   int64_t* d_kptr = ws.take<int64_t>((size_t)n_seg + 1);
   uint32_t* row_cnt = ws.take<uint32_t>((size_t)n);
@@ -1786,19 +1759,19 @@ int mmf_threshold_edges_segmented_count(const float* K, const int64_t* ptr_host,
 int mmf_threshold_edges_segmented_fill(const float* K, const int64_t* ptr_host, int64_t n_seg, const float* thresholds,
                                        const uint64_t* row_offsets, int64_t* edge_index, float* edge_w, int64_t capacity, int device_id,
                                        void* hip_stream) {
-  int64_t n = 0;
-  MMF_TRY(check_blocks("threshold_edges_segmented_fill", ptr_host, n_seg, 0, device_id, &n));
+  Call c("threshold_edges_segmented_fill", device_id, hip_stream);
+  MMF_TRY(c.on_device());
+  MMF_TRY(check_offsets(c.who, "ptr", ptr_host, n_seg, 1, 0, kAnyRows));
+  const int64_t n = ptr_host[n_seg];
+  MMF_TRY(check_block_rows(c.who, n));
   if (capacity < 0) { set_error("threshold_edges_segmented_fill: bad capacity"); return MMF_E_INVALID; }
   if (n == 0 || capacity == 0) return MMF_OK;
   if (!K || !thresholds || !row_offsets || !edge_index || !edge_w) { set_error("threshold_edges_segmented_fill: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
   const std::vector<int64_t> kptr = block_offsets(ptr_host, n_seg);
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, 2 * ws_bytes((size_t)n_seg + 1, 8), &ws));
-  int64_t* d_ptr = ws.take<int64_t>((size_t)n_seg + 1);
-  int64_t* d_kptr = ws.take<int64_t>((size_t)n_seg + 1);
+  MMF_TRY(c.begin(2 * ws_bytes((size_t)n_seg + 1, 8)));
+  const hipStream_t s = c.s;
+  int64_t* d_ptr = c.ws.take<int64_t>((size_t)n_seg + 1);
+  int64_t* d_kptr = c.ws.take<int64_t>((size_t)n_seg + 1);
   MMF_TRY(upload_table(s, d_ptr, ptr_host, (size_t)(n_seg + 1) * 8));
   MMF_TRY(upload_table(s, d_kptr, kptr.data(), (size_t)(n_seg + 1) * 8));
   return launch_threshold_fill_seg(K, d_ptr, d_kptr, n_seg, n, thresholds, reinterpret_cast<const unsigned long long*>(row_offsets),
@@ -1806,37 +1779,19 @@ int mmf_threshold_edges_segmented_fill(const float* K, const int64_t* ptr_host, 
 }
 
 // ---- segmented WSI x TMA similarity and the flat ragged median ----------------------------------
-// One side's offsets of a two-sided segment description: start at 0, non-decreasing, at least min_rows per segment, end at rows.
-static int check_side(const char* what, const char* side, const int64_t* ptr, int64_t n_seg, int64_t min_rows, int64_t rows) {
-  if (ptr[0] != 0) { set_error("%s: %s must start at 0 (got %lld)", what, side, (long long)ptr[0]); return MMF_E_INVALID; }
-  for (int64_t g = 0; g < n_seg; ++g) {
-    const int64_t ns = ptr[g + 1] - ptr[g];
-    if (ns < 0) { set_error("%s: %s decreases at segment %lld", what, side, (long long)g); return MMF_E_INVALID; }
-    if (ns < min_rows) {
-      set_error("%s: segment %lld has %lld rows in %s, need at least %lld", what, (long long)g, (long long)ns, side, (long long)min_rows);
-      return MMF_E_INVALID;
-    }
-  }
-  if (ptr[n_seg] != rows) {
-    set_error("%s: %s must end at %lld (got %lld)", what, side, (long long)rows, (long long)ptr[n_seg]);
-    return MMF_E_INVALID;
-  }
-  return MMF_OK;
-}
-
 // compute_wsi_tma_similarity of every slide of a cohort (build_hypergraph/preprocess_hypergraph.py:248-265): the pivots, ONE tiled
 // launch over a host-built work table, the per-segment merge of the partials, the flat ragged median over the stored blocks.
 // Block s and its five statistics are bit for bit mmf_sim_dense_stats(X_s, Y_s, MMF_RBF_DIRECT).
 int mmf_sim_dense_stats_segmented(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric, float lambda,
                                   const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_seg, float* out, double* out_stats,
                                   int device_id, void* hip_stream) {
-  const char* what = "sim_dense_stats_segmented";
-  MMF_TRY(check_common(X, n, m, d, in_dtype, device_id));
+  Call c("sim_dense_stats_segmented", device_id, hip_stream);
+  const char* what = c.who;
+  MMF_TRY(check_common(c, X, n, m, d, in_dtype));
   if (metric < MMF_DOT || metric > MMF_RBF_DIRECT) { set_error("%s: bad metric %d", what, metric); return MMF_E_INVALID; }
   if (metric != MMF_RBF_DIRECT) { set_error("%s: only MMF_RBF_DIRECT is supported (got metric %d)", what, metric); return MMF_E_UNSUPPORTED; }
-  if (n_seg < 1 || !x_ptr_host || !y_ptr_host) { set_error("%s: need n_seg >= 1 and host offsets x_ptr / y_ptr [n_seg + 1]", what); return MMF_E_INVALID; }
-  MMF_TRY(check_side(what, "x_ptr", x_ptr_host, n_seg, 1, n));
-  MMF_TRY(check_side(what, "y_ptr", y_ptr_host, n_seg, 1, m));
+  MMF_TRY(check_offsets(what, "x_ptr", x_ptr_host, n_seg, 1, 1, n));
+  MMF_TRY(check_offsets(what, "y_ptr", y_ptr_host, n_seg, 1, 1, m));
   if (!Y || !out_stats) { set_error("%s: NULL pointer", what); return MMF_E_INVALID; }
   if (!out) { set_error("%s: out == NULL is not supported (the median reads the stored blocks)", what); return MMF_E_UNSUPPORTED; }
   std::vector<int64_t> optr((size_t)n_seg + 1, 0), pbase;
@@ -1845,22 +1800,19 @@ int mmf_sim_dense_stats_segmented(const void* X, int64_t n, const void* Y, int64
   const std::vector<int64_t> tab = rbf_direct_seg_table(x_ptr_host, y_ptr_host, n_seg, &pbase);
   const int64_t grid = pbase[n_seg];
   if (grid >= ((int64_t)1 << 31)) { set_error("%s: %lld workgroups", what, (long long)grid); return MMF_E_UNSUPPORTED; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
   const size_t S1 = (size_t)n_seg + 1, mneed = lower_median_seg_scratch_bytes(optr.data(), n_seg);
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes((size_t)grid * stat_partial_bytes(), 1) + 2 * ws_bytes((size_t)n_seg, 4) + 4 * ws_bytes(S1, 8) +
-                                      ws_bytes(tab.size(), 8) + ws_bytes(mneed, 1), &ws));
-  char* part = ws.take<char>((size_t)grid * stat_partial_bytes());
-  float* pivot = ws.take<float>((size_t)n_seg);
-  float* med = ws.take<float>((size_t)n_seg);
-  int64_t* d_xptr = ws.take<int64_t>(S1);
-  int64_t* d_yptr = ws.take<int64_t>(S1);
-  int64_t* d_optr = ws.take<int64_t>(S1);
-  int64_t* d_pbase = ws.take<int64_t>(S1);
-  int64_t* d_tab = ws.take<int64_t>(tab.size());
-  void* mscratch = ws.take<char>(mneed);
+  MMF_TRY(c.begin(ws_bytes((size_t)grid * stat_partial_bytes(), 1) + 2 * ws_bytes((size_t)n_seg, 4) + 4 * ws_bytes(S1, 8) +
+                          ws_bytes(tab.size(), 8) + ws_bytes(mneed, 1)));
+  const hipStream_t s = c.s;
+  char* part = c.ws.take<char>((size_t)grid * stat_partial_bytes());
+  float* pivot = c.ws.take<float>((size_t)n_seg);
+  float* med = c.ws.take<float>((size_t)n_seg);
+  int64_t* d_xptr = c.ws.take<int64_t>(S1);
+  int64_t* d_yptr = c.ws.take<int64_t>(S1);
+  int64_t* d_optr = c.ws.take<int64_t>(S1);
+  int64_t* d_pbase = c.ws.take<int64_t>(S1);
+  int64_t* d_tab = c.ws.take<int64_t>(tab.size());
+  void* mscratch = c.ws.take<char>(mneed);
   MMF_TRY(upload_table(s, d_xptr, x_ptr_host, S1 * 8));
   MMF_TRY(upload_table(s, d_yptr, y_ptr_host, S1 * 8));
   MMF_TRY(upload_table(s, d_optr, optr.data(), S1 * 8));
@@ -1876,28 +1828,24 @@ int mmf_sim_dense_stats_segmented(const void* X, int64_t n, const void* Y, int64
 // torch.median of every block v[ptr[s]:ptr[s+1]] of a flat ragged array: the similarity blocks above, and the edge-weight median
 // filter of the rebuild (preprocess_hypergraph.py:885-897) for every slide of a cohort's edge list.
 int mmf_lower_median_segmented(const float* v, const int64_t* ptr_host, int64_t n_seg, float* out_median, int device_id, void* hip_stream) {
-  const char* what = "lower_median_segmented";
-  if (device_id < 0) { set_error("%s: no CPU path", what); return MMF_E_UNSUPPORTED; }
-  if (n_seg < 1 || !ptr_host) { set_error("%s: need n_seg >= 1 and host offsets ptr[n_seg + 1]", what); return MMF_E_INVALID; }
-  MMF_TRY(check_side(what, "ptr", ptr_host, n_seg, 1, ptr_host[n_seg]));
-  if (!v || !out_median) { set_error("%s: NULL pointer", what); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  Call c("lower_median_segmented", device_id, hip_stream);
+  MMF_TRY(c.on_device());
+  MMF_TRY(check_offsets(c.who, "ptr", ptr_host, n_seg, 1, 1, kAnyRows));
+  if (!v || !out_median) { set_error("%s: NULL pointer", c.who); return MMF_E_INVALID; }
   const size_t need = lower_median_seg_scratch_bytes(ptr_host, n_seg);
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, ws_bytes(need, 1), &ws));
-  return launch_lower_median_seg(v, ptr_host, n_seg, out_median, ws.take<char>(need), s);
+  MMF_TRY(c.begin(ws_bytes(need, 1)));
+  return launch_lower_median_seg(v, ptr_host, n_seg, out_median, c.ws.take<char>(need), c.s);
 }
 
 // ---- ordered k-NN + clique edges of a ragged batch (mmf_knn_clique.hip) -----------------------------
 // The edge list that build_hypergraph_knn_kmeans assembles per slide (preprocess_hypergraph.py:386-404), for every segment at
 // once and already in its documented order.  Count, one host read of *out_count by the caller, fill.
-static int knn_clique_check(const char* what, const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t n_clusters,
-                            const int64_t* ptr_host, int64_t n_seg, int device_id) {
-  int64_t rows = 0;
-  MMF_TRY(check_blocks(what, ptr_host, n_seg, 0, device_id, &rows));
-  if (rows != n) { set_error("%s: ptr must end at n = %lld (got %lld)", what, (long long)n, (long long)rows); return MMF_E_INVALID; }
+static int knn_clique_check(const Call& c, const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t n_clusters,
+                            const int64_t* ptr_host, int64_t n_seg) {
+  const char* what = c.who;
+  MMF_TRY(c.on_device());
+  MMF_TRY(check_offsets(what, "ptr", ptr_host, n_seg, 1, 0, n));
+  MMF_TRY(check_block_rows(what, n));
   if (k < 1) { set_error("%s: k must be >= 1 (got %d)", what, k); return MMF_E_INVALID; }
   if (n > 0 && !nbr) { set_error("%s: NULL pointer", what); return MMF_E_INVALID; }
   if (labels) {
@@ -1913,11 +1861,11 @@ static int knn_clique_check(const char* what, const int64_t* nbr, int64_t n, int
 int mmf_knn_clique_edges_count(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t n_clusters, const int64_t* ptr_host,
                                int64_t n_seg, uint64_t* row_offsets, int64_t* edge_ptr, int64_t* out_count, int device_id,
                                void* hip_stream) {
-  MMF_TRY(knn_clique_check("knn_clique_edges_count", nbr, n, k, labels, n_clusters, ptr_host, n_seg, device_id));
+  Call c("knn_clique_edges_count", device_id, hip_stream);
+  MMF_TRY(knn_clique_check(c, nbr, n, k, labels, n_clusters, ptr_host, n_seg));
   if (!row_offsets || !edge_ptr || !out_count) { set_error("knn_clique_edges_count: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
+  MMF_TRY(c.begin());
+  const hipStream_t s = c.s;
   if (n == 0) {
     MMF_HIP(hipMemsetAsync(out_count, 0, 8, s));
     MMF_HIP(hipMemsetAsync(row_offsets, 0, 8, s));
@@ -1926,7 +1874,7 @@ int mmf_knn_clique_edges_count(const int64_t* nbr, int64_t n, int k, const int64
   }
   const size_t need = knn_clique_scratch_bytes(n, n_seg, n_clusters, labels != nullptr);
   Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, need, &ws));
+  MMF_TRY(c.workspace(need, &ws));
   return launch_knn_clique_count(nbr, n, k, labels, n_clusters, ptr_host, n_seg, reinterpret_cast<unsigned long long*>(row_offsets),
                                  edge_ptr, out_count, ws.take<char>(need), s);
 }
@@ -1934,21 +1882,18 @@ int mmf_knn_clique_edges_count(const int64_t* nbr, int64_t n, int k, const int64
 int mmf_knn_clique_edges_fill(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t n_clusters, const int64_t* ptr_host,
                               int64_t n_seg, const uint64_t* row_offsets, int64_t* edge_index, int64_t capacity, int device_id,
                               void* hip_stream) {
-  MMF_TRY(knn_clique_check("knn_clique_edges_fill", nbr, n, k, labels, n_clusters, ptr_host, n_seg, device_id));
+  Call c("knn_clique_edges_fill", device_id, hip_stream);
+  MMF_TRY(knn_clique_check(c, nbr, n, k, labels, n_clusters, ptr_host, n_seg));
   if (capacity < 0) {      // what the count entry reports instead of a count when a label is out of range
     set_error("knn_clique_edges_fill: capacity %lld: a label lies outside [0, %lld)", (long long)capacity, (long long)n_clusters);
     return MMF_E_INVALID;
   }
   if (n == 0 || capacity == 0) return MMF_OK;
   if (!row_offsets || !edge_index) { set_error("knn_clique_edges_fill: NULL pointer"); return MMF_E_INVALID; }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  DeviceGuard guard(device_id);
-  if (!guard.ok) { set_error("hipSetDevice(%d) failed", device_id); return MMF_E_HIP; }
   const size_t need = knn_clique_scratch_bytes(n, n_seg, n_clusters, labels != nullptr);
-  Workspace ws;
-  MMF_TRY(get_workspace(device_id, s, need, &ws));
+  MMF_TRY(c.begin(need));
   return launch_knn_clique_fill(nbr, n, k, labels, n_clusters, ptr_host, n_seg, reinterpret_cast<const unsigned long long*>(row_offsets),
-                                edge_index, capacity, ws.take<char>(need), s);
+                                edge_index, capacity, c.ws.take<char>(need), c.s);
 }
 
 

@@ -55,10 +55,6 @@ struct Workspace {
 };
 inline size_t ws_bytes(size_t count, size_t elem) { return (count * elem + 255) & ~size_t(255); }
 
-// Returns a workspace of at least `bytes` for (device, stream); reallocates (after a stream sync)
-// when it has to grow.
-int get_workspace(int device, hipStream_t stream, size_t bytes, Workspace* out);
-
 // A host table (the caller's ptr_host, a local std::vector) on its way to the device, for entries that return without
 // synchronising: the bytes are copied AT CALL TIME into pinned memory that the library owns, and the copy to `dst` is
 // enqueued on `s` from there.  The caller's memory may die as soon as the call returns, and the call never waits for the
@@ -212,8 +208,38 @@ int launch_select(const SelectProblem& p, const CandLists& L, hipStream_t s);
 int launch_rows_exact(const SelectProblem& p, float* keys, hipStream_t s);
 int launch_topk_merge(const int64_t* ia, const float* va, const int64_t* ib, const float* vb,
                       int64_t n, int k, int64_t* io, float* vo, hipStream_t s);
-int launch_edge_cosine(const void* X, int64_t n, int64_t d, int dtype, const int64_t* ei, int64_t E,
-                       float* out, hipStream_t s);
+// w_e = max(0, cos(x_i, x_j)) of every edge; nrm: the rows' clamped norms (launch_row_scalars, MMF_COSINE)
+int launch_edge_cosine_impl(const void* X, int64_t d, int dtype, const float* nrm, const int64_t* ei, int64_t E,
+                            float* out, hipStream_t s);
+
+// mmf_scan_bf16.hip: the 16-bit scan (fast path) — what it supports, its operand images, its launches and their scratch
+int scan_bf16_supported(int64_t d, int kk, int dtype);
+int scan_bf16_cap(int kk, int dp);
+int scan_bf16_dp(int64_t d);
+int launch_prep_half(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
+                     const uint32_t* max_n, void* Z,
+                     int64_t n_pad, int dp, int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima,
+                     hipStream_t s);
+int launch_scan_b16(const void* ZQ, const void* ZC, const float* cb, const float* q_zn, const float* q_rn,
+                    const float* q_un, const uint32_t* maxima, int64_t n_rows, int64_t m, int64_t m_pad, int dp,
+                    int64_t d, bool f16, int metric, int kk, int col_splits, const CandLists& L, void* scratch,
+                    const ScanB16Panel& pn, hipStream_t s, int* grid_out);
+int launch_scan_b16_audit(const ScanB16Panel& pn, uint32_t* overflow, int64_t n_rows, hipStream_t s);
+size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G);
+int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const float* rn, const float* un, const uint32_t* maxima,
+                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, const CandLists& L, void* scratch,
+                        const SymBuffers& sb, std::vector<int32_t>& tab, const ScanB16Panel& pn, hipStream_t s, int* grid_out);
+size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap);
+int scan_bf16_slot_ulp(int cap);
+int scan_b16_queries_per_block(int dp);
+int launch_prep_half_gather(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
+                            const uint32_t* max_n, const int32_t* gather, void* Z, int64_t n_pos, int64_t n_pad, int dp,
+                            int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima, hipStream_t s);
+size_t scan_b16_seg_scratch_bytes(int64_t grid, int dp, int cap);
+int launch_scan_b16_seg(const void* ZQ, const void* ZC, const float* cb, const float* q_zn, const float* q_rn,
+                        const float* q_un, const uint32_t* maxima, const int32_t* sched, int64_t grid, int64_t n_rows,
+                        int64_t m, int dp, int64_t d, bool f16, int metric, int kk, const CandLists& L, void* scratch,
+                        const ScanB16Panel& pn, hipStream_t s);
 
 // mmf_dense.hip
 // Xp / Yp: f32 images of X and Y (launch_prep_f32; unused — may be null — for d <= 8 and MMF_RBF_DIRECT)
