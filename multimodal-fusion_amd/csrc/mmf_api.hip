@@ -23,7 +23,7 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-struct WsEntry { char* base = nullptr; size_t cap = 0; };
+struct WsEntry { char* base = nullptr; size_t cap = 0; WsKept kept; };
 static std::mutex g_ws_mu;
 static std::map<std::pair<int, hipStream_t>, WsEntry> g_ws[2];
 
@@ -39,6 +39,7 @@ static int get_workspace_slot(int device, hipStream_t stream, int slot, size_t b
       MMF_HIP(hipFree(e.base));
       e.base = nullptr;
       e.cap = 0;
+      e.kept = WsKept{};
     }
     size_t want = bytes + (bytes >> 3) + (1u << 20);
     void* p = nullptr;
@@ -53,6 +54,9 @@ static int get_workspace_slot(int device, hipStream_t stream, int slot, size_t b
   out->base = e.base;
   out->cap = e.cap;
   out->off = 0;
+  out->kept = e.kept;       // (a buffer that was just reallocated kept nothing: `where` cannot match)
+  e.kept = WsKept{};
+  out->keep = &e.kept;      // map nodes do not move
   return MMF_OK;
 }
 
@@ -346,6 +350,15 @@ struct FlagBlock {
 // offsets.  MMF_SYMMETRIC (read per call): 0 = never, 1 = whenever it applies, unset = from kSymMinRows rows on — below that
 // its first launch (own + antipodal super-block only) leaves compute units idle (profiles/r04_symmetric_ab.txt).
 // MMF_SYMMETRIC_G: row blocks per super-block (default: 32, more when that would make more than 32 super-blocks).
+// MMF_SYMMETRIC_LIVE (read per call): unset / 1 = the candidate rows' thresholds keep rising while the symmetric launch runs
+// and its schedule looks back, 0 = the image frozen after the first launch and the schedule looking ahead;
+// for measurements, 2 = live image with the schedule looking ahead, 3 = frozen image with the schedule looking back.
+static void symmetric_live_mode(bool* live, bool* forward) {
+  const char* e = getenv("MMF_SYMMETRIC_LIVE");
+  const int v = e ? atoi(e) : 1;
+  *live = (v == 1 || v == 2);
+  *forward = (v == 0 || v == 2);
+}
 static constexpr int64_t kSymMinRows = 131072;
 static bool symmetric_scan_wanted(int64_t n, int dp, int bcap, int metric, int forced_splits, bool same_ids, int* G) {
   if (!same_ids || dp != 512 || bcap != scan_bf16_cap(1, 512) || forced_splits != 0) return false;
@@ -539,7 +552,7 @@ struct FastTail {
   // buffers hold whichever path runs: the lists are carved for the larger list count and used through view().
   bool sym_try = false; int sym_G = 32; int lists_alloc = 0;
   SymBuffers sym;
-  std::vector<int32_t> sym_tab;   // host copy of the work tables: alive until run() has synchronised the stream
+  WsKept sym_kept; WsKept* sym_keep = nullptr;   // the work tables the workspace came with, and where to file the ones it leaves with
   uint32_t* sym_cnt = nullptr; uint32_t* sym_ids = nullptr; float* sym_keys = nullptr;
   int64_t sym_grid() const { return sym_schedule_grid((n + 255) / 256, sym_G); }
   void set_symmetric(int G) {   // before bytes() / carve()
@@ -626,6 +639,7 @@ struct FastTail {
     if (sym_try) {
       sym_cnt = ws.take<uint32_t>(n); sym_ids = ws.take<uint32_t>((size_t)n * kSymCap); sym_keys = ws.take<float>((size_t)n * kSymCap);
       sym.carve(ws, n_pad_q(), sym_grid());
+      sym_kept = ws.kept; sym_keep = ws.keep;
     }
     flags.carve(ws, n);
     XL.carve(ws, FB, (size_t)FB * 2 * fb_splits, cap, false);
@@ -669,8 +683,12 @@ struct FastTail {
     pn.seed = seed; pn.seed_stride = n_seed;
     pn.share = (splits > 1 || fo.n_panels > 1) ? 1 : 0;
     if (symmetric) {
-      MMF_TRY(launch_scan_b16_sym(fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, r.d, fo.f16, r.metric, kk, sym_G, L, scan_scratch,
-                                  sym, sym_tab, pn, s, &grid));
+      bool live, forward;
+      symmetric_live_mode(&live, &forward);
+      const WsKept tables{sym.sched, (n + 255) / 256, sym_G, forward ? 1 : 0};
+      MMF_TRY(launch_scan_b16_sym(fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, r.d, fo.f16, r.metric, kk, sym_G, live, forward,
+                                  !(sym_kept == tables), L, scan_scratch, sym, pn, s, &grid));
+      if (sym_keep) *sym_keep = tables;
     } else if (fo.n_panels == 0) {
       MMF_TRY(launch_scan_b16(fo.ZQ, fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, m, fo.m_pad_tiles, fo.dp, r.d, fo.f16,
                               r.metric, kk, splits, L, scan_scratch, pn, s, &grid));
@@ -706,8 +724,11 @@ struct FastTail {
       unsigned long long tot = 0; uint32_t mx = 0, lmx = 0;
       for (uint32_t v : hc) { tot += v; if (v > mx) mx = v; }
       for (uint32_t v : hl) if (v > lmx) lmx = v;
-      fprintf(stderr, "[mmf symmetric] G %d grid %lld: rows without a threshold %u, received entries %llu (%.1f per row, largest %u of %d), fullest wave log %u of %d\n",
-              sym_G, (long long)sym_grid(), none, tot, (double)tot / (double)n, mx, kSymCap, lmx, kSymLogPerWave);
+      bool live, forward;
+      symmetric_live_mode(&live, &forward);
+      fprintf(stderr, "[mmf symmetric] G %d grid %lld %s %s: rows without a threshold %u, received entries %llu (%.1f per row, largest %u of %d), fullest wave log %u of %d\n",
+              sym_G, (long long)sym_grid(), live ? "live" : "frozen", forward ? "ahead" : "back", none, tot, (double)tot / (double)n, mx,
+              kSymCap, lmx, kSymLogPerWave);
     }
     // the f32 rows are first touched here: a caller that is still receiving them (overlapped
     // all-gather) hands in the event that marks their arrival
@@ -787,7 +808,9 @@ int64_t mmf_debug_symmetric_schedule(int64_t row_blocks, int group, int launch, 
   const int64_t grid = sym_schedule_grid(row_blocks, group);
   if (table_host) {
     if (capacity < grid) { set_error("debug_symmetric_schedule: table of %lld entries needed", (long long)grid); return MMF_E_INVALID; }
-    sym_schedule_table(row_blocks, group, launch, table_host);
+    bool live, forward;
+    symmetric_live_mode(&live, &forward);
+    sym_schedule_table(row_blocks, group, launch, table_host, forward);
   }
   return grid;
 }

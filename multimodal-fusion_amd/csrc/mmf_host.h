@@ -39,11 +39,24 @@ void set_error(const char* fmt, ...);
     if (_rc != MMF_OK) return _rc; \
   } while (0)
 
+// What a cached workspace still holds from the previous call on its stream and a later call may use as it is (one thing:
+// the work tables of the symmetric scan, which depend on the row-block count, G and the direction alone).  Handing the
+// workspace out forgets it — whoever takes the buffer may overwrite every byte — and gives the taker what was kept until
+// then (Workspace::kept); a call that finds or writes the same content at the same place files it again (*Workspace::keep).
+struct WsKept {
+  const void* where = nullptr;
+  int64_t row_blocks = 0;
+  int group = 0, forward = 0;
+  bool operator==(const WsKept& o) const { return where == o.where && row_blocks == o.row_blocks && group == o.group && forward == o.forward; }
+};
+
 // Bump allocator over one cached device buffer per (device, stream).
 struct Workspace {
   char* base = nullptr;
   size_t cap = 0;
   size_t off = 0;
+  WsKept kept;              // what the buffer held when it was handed out
+  WsKept* keep = nullptr;   // where to file what it holds now (nullptr: nowhere)
   void reset() { off = 0; }
   template <typename T>
   T* take(size_t count) {
@@ -117,7 +130,7 @@ struct CandLists {
 // symmetric ones.  The table has sym_schedule_grid() entries of 8 ints: row block (-1: idle), first tile and tile count of
 // two column ranges.
 int64_t sym_schedule_grid(int64_t nb, int G);
-void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out);
+void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out, bool forward = false);
 int sym_default_group(int64_t nb);
 constexpr int kSymCap = 512;            // entries per row of CandLists::sym_ids (1.66 x the largest count on the bench rows, bf16 leg)
 constexpr int kSymLogPerWave = 4096;    // entries of a wave's append log (32 rows: 128 per row; 1.73 x the fullest on the bench rows, bf16 leg)
@@ -227,8 +240,8 @@ int launch_scan_b16(const void* ZQ, const void* ZC, const float* cb, const float
 int launch_scan_b16_audit(const ScanB16Panel& pn, uint32_t* overflow, int64_t n_rows, hipStream_t s);
 size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G);
 int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const float* rn, const float* un, const uint32_t* maxima,
-                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, const CandLists& L, void* scratch,
-                        const SymBuffers& sb, std::vector<int32_t>& tab, const ScanB16Panel& pn, hipStream_t s, int* grid_out);
+                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, bool live, bool forward, bool tables,
+                        const CandLists& L, void* scratch, const SymBuffers& sb, const ScanB16Panel& pn, hipStream_t s, int* grid_out);
 size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap);
 int scan_bf16_slot_ulp(int cap);
 int scan_b16_queries_per_block(int dp);

@@ -223,7 +223,8 @@ struct ScanB16Args {
   // SYM == 2 (the symmetric launch of a scan of X against itself, launch_scan_b16_sym): a value G_ij that reaches the
   // threshold of its CANDIDATE row j is appended to the wave's private log as (j, i, G); sym_scatter_kernel files the logs
   // into the rows' lists afterwards
-  const float* sym_thr;      // [m_pad] threshold of every candidate row (sym_thr_kernel: seed[] decoded; +inf for padding rows)
+  float* sym_thr;            // [m_pad] threshold of every candidate row (sym_thr_kernel: seed[] decoded; +inf for padding rows)
+  int sym_live;              // the rows' workgroups keep raising sym_thr[] while the symmetric launch runs (sync_seed)
   uint32_t* sym_log;         // [grid * NW][sym_log_cap][4]
   uint32_t* sym_log_cnt;     // [grid * NW] entries written (zeroed by the host; an idle workgroup writes nothing)
   int sym_log_cap;
@@ -278,6 +279,9 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 // against the threshold of its CANDIDATE row (32 floats per tile, DMAed into LDS with the tile's biases), and a value that
 // passes is appended to a log private to the wave — a ballot and a popcount place it: one store, no atomic, no returned value to
 // wait for (the store itself retires with the iteration's vmcnt(0), like the tile DMA).
+#ifndef MMF_SYM_ABLATE
+#define MMF_SYM_ABLATE 0   // timing-only variants of the SYM == 2 kernel's candidate direction (sym_offer below)
+#endif
 template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0>
 __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(ScanB16Args a) {
   static_assert(!SPLITK || (TPB == 1 && NW == 8 && (KS % 8) == 0), "split-k pairs");
@@ -390,15 +394,23 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   float pub = -kFltMax;
   auto sync_seed = [&]() {
     if (!qvalid) return;
+    bool rose = false;
     if (list.thr > pub && list.thr > list.lost) {
       pub = list.thr;
       atomicMax(a.seed + qpos, seed_enc(pub));
+      rose = true;
     }
     if (!a.share) return;
     const int32_t o = __hip_atomic_load(a.seed + qpos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (o > kSeedNone) {
       const float t = __int_as_float(o >= 0 ? o : (o ^ 0x7fffffff));
       if (t > list.thr) { list.thr = t; pub = t; }
+    }
+    // SYM == 2, live image: the risen threshold also goes to the image the OTHER rows' candidate-side tests read (issue_thr).
+    // Any value ever published for a row is a valid threshold for it, so neither the order in which the row's two lanes
+    // store nor how late a reader sees the store matters; agent scope makes it leave this XCD's L2 while the kernel runs.
+    if constexpr (SYM == 2) {
+      if (rose && a.sym_live) __hip_atomic_store(a.sym_thr + qpos, list.thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   };
   if (a.share) sync_seed();
@@ -469,12 +481,15 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   };
   // SYM == 2: the thresholds of the same 32 rows, same form, same place in the iteration, issued by another wave
   auto sym_thr_stage = [&](int stage) -> float* { return lkeys + CAP * NTL + stage * 32; };
+  // (cache policy 16 = sc1, what the compiler emits for an agent-scope load: the image is rewritten by other XCDs' workgroups
+  //  while this kernel runs (sync_seed), and a plain load could be served from a stale line of this XCD's L2 for as long as
+  //  it stays there)
   auto issue_thr = [&](const char* bsrc, int stage) {
-    const __amdgpu_buffer_rsrc_t trsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sym_thr), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t trsrc = __builtin_amdgcn_make_buffer_rsrc(a.sym_thr, 0, -1, 0x00020000);
     const uint32_t l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     if (l < 32)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(trsrc, (__attribute__((address_space(3))) void*)sym_thr_stage(stage), 4, (int)(l * 4u),
-                                               (int)(uint32_t)(bsrc - cb0), 0, 0);
+                                               (int)(uint32_t)(bsrc - cb0), 0, 16);
   };
 
   if (SPLITK && tid < NQW) ack[tid] = -1;
@@ -618,8 +633,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
 
   // SYM == 2, the candidate direction: right behind a tile's chain (its stage of thresholds is not refilled before the next
   // barrier), the lane's 16 values against the thresholds of their candidate rows — 8 v_max + 8 compares, two LDS reads.
-  // On a hit (one in three wave-tiles at N = 262144) every passing value goes to the wave's log: position = the wave's
-  // running count + the lane's rank in the ballot; a full log flags the candidate row for the exact rescan (audit_kernel).
+  // On a hit every passing value goes to the wave's log: position = the wave's running count + the lane's rank in the ballot;
+  // a full log flags the candidate row for the exact rescan (audit_kernel).  Almost every hit is ONE value in ONE lane, so
+  // the path costs one round: each lane folds its passing values (validity included) into a 16-bit mask, and a round takes
+  // the lowest set bit of every lane that has one — one ballot and one store per round, as many rounds as the busiest lane
+  // has values.
+  // MMF_SYM_ABLATE (scripts/ab_build.sh, timing only, the results are WRONG): 1 = the test without the hit path, 2 = neither
+  // the test nor the threshold DMA, 3 = the hit path without its log stores (the logs then read as empty).
   uint32_t sym_wcnt = 0;
   auto sym_offer = [&](const Acc& x, int tt, const float* th) {
     const f32x4 th0 = *reinterpret_cast<const f32x4*>(th + 4 * g);
@@ -630,38 +650,48 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       any |= fmaxf(x.t[0][0][j], x.t[0][1][j]) >= th0[j];
       any |= fmaxf(x.t[1][0][j], x.t[1][1][j]) >= th1[j];
     }
-    if (__builtin_expect(__any(any), 0)) {
+    if (__builtin_expect(__any(any) && (MMF_SYM_ABLATE != 1 || a.sym_log_cap < 0), 0)) {
       const uint32_t cj0 = id_base + (uint32_t)tt * B_CT + ((tt >= sym_n1) ? (uint32_t)(sym_skip * B_CT) : 0u) + 4u * (uint32_t)g;
       const uint32_t qi0 = (uint32_t)(q0 + 32 * qw + c16);
       const bool sym_qv0 = q0 + 32 * qw + c16 < a.n_rows, sym_qv1 = q0 + 32 * qw + c16 + 16 < a.n_rows;
       uint32_t* lg = a.sym_log + ((size_t)blockIdx.x * NW + wave) * (size_t)a.sym_log_cap * 4;
-      const unsigned long long below = (1ull << lane) - 1ull;
+      uint32_t m = 0;                                    // bit 8 cb + 2 j + qb: value x.t[cb][qb][j] passes and both rows are real
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const uint32_t cj = cj0 + 16u * cb + j;
           const float tj = cb ? th1[j] : th0[j];
-#pragma unroll
-          for (int qb = 0; qb < 2; ++qb) {
-            const float v = x.t[cb][qb][j];
-            const bool h = (v >= tj) && (qb ? sym_qv1 : sym_qv0) && ((int64_t)cj < a.n_rows);
-            const unsigned long long mask = __ballot(h);
-            if (mask) {
-              const uint32_t at = sym_wcnt + (uint32_t)__popcll(mask & below);
-              if (h) {
-                if (at < (uint32_t)a.sym_log_cap) {
-                  u32x4 ent;
-                  ent[0] = cj; ent[1] = qi0 + 16u * qb; ent[2] = __float_as_uint(v); ent[3] = 0u;
-                  *reinterpret_cast<u32x4*>(lg + (size_t)at * 4) = ent;
-                } else {
-                  atomicMax(a.lost + cj, 0x7fffffff);
-                }
-              }
-              sym_wcnt += (uint32_t)__popcll(mask);
-            }
+          const bool cv = (int64_t)(cj0 + 16u * cb + j) < a.n_rows;
+          m |= (x.t[cb][0][j] >= tj && sym_qv0 && cv) ? (1u << (8 * cb + 2 * j)) : 0u;
+          m |= (x.t[cb][1][j] >= tj && sym_qv1 && cv) ? (2u << (8 * cb + 2 * j)) : 0u;
+        }
+      }
+      unsigned long long busy = __ballot(m != 0u);
+      while (busy) {
+        if (m != 0u) {
+          const uint32_t b = (uint32_t)__builtin_ctz(m);
+          m &= m - 1u;
+          // value number b out of the registers: a tree of selects, one level per bit of b
+          const bool b0 = (b & 1u) != 0u, b1 = (b & 2u) != 0u, b2 = (b & 4u) != 0u, b3 = (b & 8u) != 0u;
+          const float p0 = b0 ? x.t[0][1][0] : x.t[0][0][0], p1 = b0 ? x.t[0][1][1] : x.t[0][0][1];
+          const float p2 = b0 ? x.t[0][1][2] : x.t[0][0][2], p3 = b0 ? x.t[0][1][3] : x.t[0][0][3];
+          const float p4 = b0 ? x.t[1][1][0] : x.t[1][0][0], p5 = b0 ? x.t[1][1][1] : x.t[1][0][1];
+          const float p6 = b0 ? x.t[1][1][2] : x.t[1][0][2], p7 = b0 ? x.t[1][1][3] : x.t[1][0][3];
+          const float r0 = b1 ? p1 : p0, r1 = b1 ? p3 : p2, r2 = b1 ? p5 : p4, r3 = b1 ? p7 : p6;
+          const float s0 = b2 ? r1 : r0, s1 = b2 ? r3 : r2;
+          const float v = b3 ? s1 : s0;
+          const uint32_t cj = cj0 + 16u * (b >> 3) + ((b >> 1) & 3u);
+          const uint32_t at = sym_wcnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(busy >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)busy, 0u));
+          if (at < (uint32_t)a.sym_log_cap) {
+            u32x4 ent;
+            ent[0] = cj; ent[1] = qi0 + 16u * (b & 1u); ent[2] = __float_as_uint(v); ent[3] = 0u;
+            if (MMF_SYM_ABLATE != 3) *reinterpret_cast<u32x4*>(lg + (size_t)at * 4) = ent;
+          } else {
+            atomicMax(a.lost + cj, 0x7fffffff);
           }
         }
+        sym_wcnt += (uint32_t)__popcll(busy);
+        busy = __ballot(m != 0u);
       }
     }
   };
@@ -722,7 +752,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       acc = tile_body(tiles + (sg + u) * TILEB + kbyte, cbs + (sg + u) * 64, src, ng + u);
       // (behind the chain: issued in front of it, the same DMA costs +8 %; mid-chain needs a branch inside the chain)
       if (wave == ((t + TPB) & (NW - 1))) issue_bias(more ? bsrc + u * B_CT * 4 : cb0, ng + u);
-      if constexpr (SYM == 2) {
+      if constexpr (SYM == 2 && MMF_SYM_ABLATE != 2) {
         if (wave == ((t + TPB + 4) & (NW - 1))) issue_thr(more ? bsrc + u * B_CT * 4 : cb0, ng + u);
         if (t < Ti) sym_offer(acc, t, sym_thr_stage(sg + u));
       }
@@ -787,6 +817,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   }
   sync_seed();
   if constexpr (SYM == 2) {
+    if (MMF_SYM_ABLATE == 3) sym_wcnt = 0;   // nothing was stored: nothing for sym_scatter_kernel to read
     if (lane == 0) a.sym_log_cnt[(size_t)blockIdx.x * NW + wave] = sym_wcnt < (uint32_t)a.sym_log_cap ? sym_wcnt : (uint32_t)a.sym_log_cap;
   }
   if (qvalid) {
@@ -1056,8 +1087,11 @@ int launch_scan_b16_seg(const void* ZQ, const void* ZC, const float* cb, const f
 // Symmetric scan of X against itself (cosine / dot, padded dim 512, 15-entry lists): DESIGN.md §4.1
 // ------------------------------------------------------------------------------------------------
 // Super-blocks of G row blocks (the last one takes the left-over row blocks too); ns of them.  Launch 0: every row block scans its own super-block and, when ns is even, the
-// antipodal one (plain: query direction only).  Launch 1: the super-blocks a + 1 .. a + (ns - 1) / 2 (cyclic), each pair of
-// rows multiplied once and served in both directions.  Every ordered (row, column) pair is covered exactly once.
+// antipodal one (plain: query direction only).  Launch 1: the super-blocks a - (ns - 1) / 2 .. a - 1 (cyclic; `forward`:
+// a + 1 .. a + (ns - 1) / 2), each pair of rows multiplied once and served in both directions.  Every ordered (row, column)
+// pair is covered exactly once.  Looking BACK is what the live threshold image (sync_seed) wants: workgroups are dispatched in
+// block-id order, so the rows a workgroup tests as candidates mostly belong to workgroups that run or have finished and have
+// raised their thresholds; only the pairs of the wrap-around meet rows whose workgroup has not started.
 // Block ids: like the plain launch, blocks that share blockIdx % 8 share an XCD; the G row blocks of a super-block take one
 // XCD's block ids of one stretch of 8 G ids, so they run together and stream the same columns through that XCD's L2.
 int sym_default_group(int64_t nb) {
@@ -1071,7 +1105,7 @@ int64_t sym_schedule_grid(int64_t nb, int G) {
   const int64_t ns = sym_super_blocks(nb, G);
   return ((ns + 7) / 8 + (nb > ns * G ? 1 : 0)) * 8 * G;      // the left-over row blocks take a stretch of block ids of their own
 }
-void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out) {
+void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out, bool forward) {
   const int64_t ns = sym_super_blocks(nb, G), grid = sym_schedule_grid(nb, G), tiles = nb * 8;
   const int64_t per = 8 * (int64_t)G, stretches = (ns + 7) / 8;
   auto first_tile = [&](int64_t sb) { return sb * G * 8; };
@@ -1093,8 +1127,9 @@ void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out) {
     } else {
       const int64_t h = (ns - 1) / 2;
       if (h == 0) continue;
-      int64_t lo = sb + 1, hi = sb + h;           // super-blocks lo .. hi, cyclic
+      int64_t lo = forward ? sb + 1 : sb - h, hi = lo + h - 1;   // super-blocks lo .. hi, cyclic
       if (lo >= ns) { lo -= ns; hi -= ns; }
+      if (lo < 0) { lo += ns; hi += ns; }
       if (hi < ns) { b1 = first_tile(lo); n1 = end_tile(hi) - b1; }
       else { b1 = first_tile(lo); n1 = end_tile(ns - 1) - b1; b2 = 0; n2 = end_tile(hi - ns); }
     }
@@ -1140,18 +1175,22 @@ size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G) {
 
 // Both launches, the threshold image between them and the filing of the logs behind them, on stream s.  ZC is the operand
 // image of all rows (queries and candidates), n_pad / 32 tiles.  L has four lists per row (a pair per launch), keys, margins
-// and the sym_* lists; pn.seed as for launch_scan_b16.  tab: host storage of the work tables, which must outlive the upload
-// (until the caller's next synchronisation of s).  *grid_out: the sum of the two grids.
+// and the sym_* lists; pn.seed as for launch_scan_b16.  live: the rows' workgroups keep raising the threshold image while the
+// symmetric launch runs; forward: its schedule looks ahead (sym_schedule_table).  tables: build the two work tables and
+// upload them to sb.sched — they depend on (row blocks, G, forward) alone, so a caller whose sb.sched still holds them from
+// an earlier call on this stream passes false.  *grid_out: the sum of the two grids.
 int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const float* rn, const float* un, const uint32_t* maxima,
-                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, const CandLists& L, void* scratch,
-                        const SymBuffers& sb, std::vector<int32_t>& tab, const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
+                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, bool live, bool forward, bool tables,
+                        const CandLists& L, void* scratch, const SymBuffers& sb, const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
   const int64_t nb = (n + 255) / 256, n_pad = nb * 256, grid = sym_schedule_grid(nb, G);
   if (L.lists != 4 || L.cap != B_CAP || !L.keys || !L.margin || !L.sym_cnt || !pn.seed) { set_error("scan_b16_sym: lists missing"); return MMF_E_INTERNAL; }
   if (n_pad * 1024 >= (int64_t(1) << 32)) { set_error("scan_b16_sym: operand image beyond the 32-bit tile offsets"); return MMF_E_INTERNAL; }
-  tab.resize((size_t)grid * 2 * SEG_ENTRY);   // the caller keeps it until the call's stream synchronisation
-  sym_schedule_table(nb, G, 0, tab.data());
-  sym_schedule_table(nb, G, 1, tab.data() + (size_t)grid * SEG_ENTRY);
-  MMF_HIP(hipMemcpyAsync(sb.sched, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+  if (tables) {
+    std::vector<int32_t> tab((size_t)grid * 2 * SEG_ENTRY);
+    sym_schedule_table(nb, G, 0, tab.data(), forward);
+    sym_schedule_table(nb, G, 1, tab.data() + (size_t)grid * SEG_ENTRY, forward);
+    MMF_TRY(upload_table(s, sb.sched, tab.data(), tab.size() * 4));
+  }
   MMF_HIP(hipMemsetAsync(L.sym_cnt, 0, (size_t)n * 4, s));
   MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * L.lists * 4, s));   // with one or two super-blocks the second launch has no work and writes no list
   MMF_HIP(hipMemsetAsync(sb.log_cnt, 0, (size_t)grid * 8 * 4, s));
@@ -1167,7 +1206,7 @@ int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const 
   a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap; a.spill_stacks = 0;
   a.lids = reinterpret_cast<uint32_t*>(scratch);
   a.sched = sb.sched;
-  a.sym_thr = sb.thr; a.sym_log = sb.log; a.sym_log_cnt = sb.log_cnt; a.sym_log_cap = kSymLogPerWave;
+  a.sym_thr = sb.thr; a.sym_live = live ? 1 : 0; a.sym_log = sb.log; a.sym_log_cnt = sb.log_cnt; a.sym_log_cap = kSymLogPerWave;
   auto go = [&](auto kern, size_t lds) -> int {
     MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, a);
