@@ -58,6 +58,11 @@ EXPORTS = ["mmf_version", "mmf_last_error", "mmf_simtopk", "mmf_simtopk_ex", "mm
 # behaviour is INTEGRATION.md's table "Cohort entries", pinned by tests/test_wsi_tma_segmented_cpu.py.
 EXPORTS_COHORT = ["mmf_sim_dense_stats_segmented", "mmf_lower_median_segmented"]
 
+# The pooling entries (include/mmf_hg_pool.h): additions to ABI version 3 declared in a header of their own, so
+# that the two lists above stay exactly what include/mmf_hg.h declares.  Their synchronisation behaviour is INTEGRATION.md's table
+# "Pooling entries", pinned by tests/test_super_patches_segmented_cpu.py.
+EXPORTS_POOL = ["mmf_segment_sort_segmented", "mmf_super_patches_segmented"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -114,7 +119,9 @@ def lib() -> ctypes.CDLL:
     L.mmf_knn_clique_edges_fill.argtypes = [vp, i64, ci, vp, i64, vp, i64, vp, vp, i64, ci, vp]
     L.mmf_sim_dense_stats_segmented.argtypes = [vp, i64, vp, i64, i64, ci, ci, f32, vp, vp, i64, vp, vp, ci, vp]
     L.mmf_lower_median_segmented.argtypes = [vp, vp, i64, vp, ci, vp]
-    for name in EXPORTS + EXPORTS_COHORT:
+    L.mmf_segment_sort_segmented.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, ci, vp]
+    L.mmf_super_patches_segmented.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL:
         fn = getattr(L, name)
         if name not in ("mmf_last_error", "mmf_padded_dim"):
             fn.restype = ci

@@ -30,7 +30,7 @@ static std::map<std::pair<int, hipStream_t>, WsEntry> g_ws[2];
 // A workspace of at least `bytes` for (device, stream); reallocates (after a stream sync) when it has to grow.
 // slot 0: the call's working set.  slot 1: what only a rare branch of a call needs on top of it (the f32 operand
 // images of an exact rescan inside the 16-bit path), so that every call does not carry it.
-static int get_workspace_slot(int device, hipStream_t stream, int slot, size_t bytes, Workspace* out) {
+int get_workspace_slot(int device, hipStream_t stream, int slot, size_t bytes, Workspace* out) {
   std::lock_guard<std::mutex> lk(g_ws_mu);
   WsEntry& e = g_ws[slot][std::make_pair(device, stream)];
   if (e.cap < bytes) {
@@ -59,42 +59,6 @@ static int get_workspace_slot(int device, hipStream_t stream, int slot, size_t b
   out->keep = &e.kept;      // map nodes do not move
   return MMF_OK;
 }
-
-// The prologue of every entry that takes (device_id, hip_stream), in the order it has to run.  on_device() is the entry's first
-// check.  Then come its checks of the host arguments: with device_id = 0 on a machine without a GPU they still answer
-// MMF_E_INVALID, not MMF_E_HIP.  Then begin(): it sets the device (restored when the Call goes) and only then gives out the
-// caller's stream and a workspace, so neither can be had past a refused device or ahead of the host checks.
-struct Call {
-  const char* who;           // the entry, for error messages
-  hipStream_t s = nullptr;   // the caller's stream, from begin()
-  Workspace ws;              // the call's slot-0 workspace, from begin(bytes)
-  Call(const char* who_, int device_id, void* hip_stream) : who(who_), device(device_id), stream(static_cast<hipStream_t>(hip_stream)) {}
-  int on_device() const {
-    if (device >= 0) return MMF_OK;
-    set_error("%s: device_id %d: no CPU path (the CPU restatement is oracle/, tests only)", who, device);
-    return MMF_E_UNSUPPORTED;
-  }
-  int begin() {
-    MMF_TRY(on_device());
-    guard.emplace(device);
-    if (!guard->ok) { set_error("hipSetDevice(%d) failed", device); return MMF_E_HIP; }
-    s = stream;
-    return MMF_OK;
-  }
-  int begin(size_t bytes) {
-    MMF_TRY(begin());
-    return workspace(bytes, &ws);
-  }
-  // after begin(): a workspace whose size only work behind begin() settles, or (slot 1) what a rare branch needs on top
-  int workspace(size_t bytes, Workspace* out, int slot = 0) const {
-    if (!guard) { set_error("%s: workspace before begin() (internal invariant)", who); return MMF_E_INTERNAL; }
-    return get_workspace_slot(device, stream, slot, bytes, out);
-  }
-
- private:
-  int device; hipStream_t stream;
-  std::optional<DeviceGuard> guard;
-};
 
 struct StageBlock { char* host = nullptr; size_t cap = 0; hipEvent_t passed = nullptr; bool in_flight = false; };
 static std::map<std::pair<int, hipStream_t>, std::vector<StageBlock>> g_stage;
@@ -147,8 +111,7 @@ static int check_common(const Call& c, const void* X, int64_t n, int64_t m, int6
 
 // The host offsets ptr[n_seg + 1] of a segmented entry (`name`: the array as the caller knows it): n_seg >= min_seg segments,
 // start at 0, never decrease, at least min_rows per segment, end at `rows` (kAnyRows: wherever they end).
-static constexpr int64_t kAnyRows = -1;
-static int check_offsets(const char* who, const char* name, const int64_t* ptr, int64_t n_seg, int64_t min_seg, int64_t min_rows,
+int check_offsets(const char* who, const char* name, const int64_t* ptr, int64_t n_seg, int64_t min_seg, int64_t min_rows,
                          int64_t rows) {
   if (n_seg < min_seg || !ptr) {
     set_error("%s: need n_seg >= %lld and host offsets %s[n_seg + 1]", who, (long long)min_seg, name);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <functional>
+#include <optional>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -86,6 +87,51 @@ struct DeviceGuard {
     if (prev >= 0) (void)hipSetDevice(prev);
   }
 };
+
+// mmf_api.hip: a workspace of at least `bytes` for (device, stream), slot 0 or 1 (Call::workspace)
+int get_workspace_slot(int device, hipStream_t stream, int slot, size_t bytes, Workspace* out);
+
+// The prologue of every entry that takes (device_id, hip_stream), in the order it has to run.  on_device() is the entry's first
+// check.  Then come its checks of the host arguments: with device_id = 0 on a machine without a GPU they still answer
+// MMF_E_INVALID, not MMF_E_HIP.  Then begin(): it sets the device (restored when the Call goes) and only then gives out the
+// caller's stream and a workspace, so neither can be had past a refused device or ahead of the host checks.
+struct Call {
+  const char* who;           // the entry, for error messages
+  hipStream_t s = nullptr;   // the caller's stream, from begin()
+  Workspace ws;              // the call's slot-0 workspace, from begin(bytes)
+  Call(const char* who_, int device_id, void* hip_stream) : who(who_), device(device_id), stream(static_cast<hipStream_t>(hip_stream)) {}
+  int on_device() const {
+    if (device >= 0) return MMF_OK;
+    set_error("%s: device_id %d: no CPU path (the CPU restatement is oracle/, tests only)", who, device);
+    return MMF_E_UNSUPPORTED;
+  }
+  int begin() {
+    MMF_TRY(on_device());
+    guard.emplace(device);
+    if (!guard->ok) { set_error("hipSetDevice(%d) failed", device); return MMF_E_HIP; }
+    s = stream;
+    return MMF_OK;
+  }
+  int begin(size_t bytes) {
+    MMF_TRY(begin());
+    return workspace(bytes, &ws);
+  }
+  // after begin(): a workspace whose size only work behind begin() settles, or (slot 1) what a rare branch needs on top
+  int workspace(size_t bytes, Workspace* out, int slot = 0) const {
+    if (!guard) { set_error("%s: workspace before begin() (internal invariant)", who); return MMF_E_INTERNAL; }
+    return get_workspace_slot(device, stream, slot, bytes, out);
+  }
+
+ private:
+  int device; hipStream_t stream;
+  std::optional<DeviceGuard> guard;
+};
+
+
+// The host offsets ptr[n_seg + 1] of a segmented entry (mmf_api.hip): n_seg >= min_seg segments, start at 0, never decrease, at
+// least min_rows per segment, end at `rows` (kAnyRows: wherever they end).  MMF_E_INVALID names the first bad segment.
+constexpr int64_t kAnyRows = -1;
+int check_offsets(const char* who, const char* name, const int64_t* ptr, int64_t n_seg, int64_t min_seg, int64_t min_rows, int64_t rows);
 
 inline size_t dtype_size(int dt) { return dt == MMF_F32 ? 4 : 2; }
 
