@@ -9,6 +9,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.knn_kmeans_hypergraph.*                   the k-NN + KMeans hypergraph of every slide of a cohort (ordered edges, one host read)
     mmf.wsi_tma_similarity.*                      WSI x TMA similarity + statistics, grouping and the median edge filter of every slide of a cohort
     mmf.super_patches.*                           super-patch aggregation of every slide of a cohort (sort, pooling, statistics; one host read per group)
+    mmf.super_patch_stats.*                       the statistics of that step for a slide whose similarity matrix does not fit: K recomputed in row panels
     mmf.cohort.build_cohort_hypergraphs(...)      the four steps of process_single_file for every slide of a cohort, in memory
     mmf.build_hypergraph.*                        the reference's function names and signatures
     mmf.distributed.sharded_simtopk(...)          row-sharded multi-GPU driver (RCCL all-gather)
@@ -19,7 +20,7 @@ from .ops import (edge_cosine, offdiag_lower_median, sim_dense, sim_dense_combin
 from .knn_kmeans_hypergraph import build_hypergraph_knn_kmeans_segmented, knn_kmeans_edges_segmented  # noqa: F401
 from .wsi_tma_similarity import (compute_wsi_tma_similarity_segmented, filter_edges_by_median_segmented,  # noqa: F401
                                  group_by_similarity_segmented, lower_median_segmented, sim_dense_stats_segmented, similarity_block)
-from . import cohort, super_patches  # noqa: F401,E402
+from . import cohort, super_patch_stats, super_patches  # noqa: F401,E402
 from .cohort import build_cohort_hypergraphs  # noqa: F401,E402
 from .super_patches import (aggregate_wsi_super_patches_segmented, pool_super_patches_segmented,  # noqa: F401,E402
                             segment_sort_segmented)
@@ -27,5 +28,5 @@ from .super_patches import (aggregate_wsi_super_patches_segmented, pool_super_pa
 __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combined", "sim_dense_combined_segmented", "edge_cosine",
            "topk_merge", "offdiag_lower_median", "threshold_edges", "knn_kmeans_edges_segmented", "build_hypergraph_knn_kmeans_segmented",
            "sim_dense_stats_segmented", "lower_median_segmented", "compute_wsi_tma_similarity_segmented", "similarity_block",
-           "group_by_similarity_segmented", "filter_edges_by_median_segmented", "super_patches", "cohort", "segment_sort_segmented",
+           "group_by_similarity_segmented", "filter_edges_by_median_segmented", "super_patches", "super_patch_stats", "cohort", "segment_sort_segmented",
            "pool_super_patches_segmented", "aggregate_wsi_super_patches_segmented", "build_cohort_hypergraphs"]

@@ -63,6 +63,11 @@ EXPORTS_COHORT = ["mmf_sim_dense_stats_segmented", "mmf_lower_median_segmented"]
 # "Pooling entries", pinned by tests/test_super_patches_segmented_cpu.py.
 EXPORTS_POOL = ["mmf_segment_sort_segmented", "mmf_super_patches_segmented"]
 
+# The streaming entries (include/mmf_hg_stream.h): additions to ABI version 3 in a header of their own, like the
+# pooling entries.  Their synchronisation behaviour is INTEGRATION.md's table "Streaming entries", pinned by
+# tests/test_super_patch_stats_streamed_cpu.py.
+EXPORTS_STREAM = ["mmf_super_patch_stats_streamed", "mmf_super_patch_stats_streamed_bytes"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -121,11 +126,14 @@ def lib() -> ctypes.CDLL:
     L.mmf_lower_median_segmented.argtypes = [vp, vp, i64, vp, ci, vp]
     L.mmf_segment_sort_segmented.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, ci, vp]
     L.mmf_super_patches_segmented.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, ci, vp]
-    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL:
+    L.mmf_super_patch_stats_streamed.argtypes = [vp, vp, i64, i64, i64, f32, f32, vp, vp, i64, i64, vp, vp, ci, vp]
+    L.mmf_super_patch_stats_streamed_bytes.argtypes = [i64, i64, i64, i64, i64]
+    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM:
         fn = getattr(L, name)
-        if name not in ("mmf_last_error", "mmf_padded_dim"):
+        if name not in ("mmf_last_error", "mmf_padded_dim", "mmf_super_patch_stats_streamed_bytes"):
             fn.restype = ci
     L.mmf_padded_dim.restype = i64
+    L.mmf_super_patch_stats_streamed_bytes.restype = i64
     L.mmf_debug_symmetric_schedule.argtypes = [i64, ci, ci, vp, i64]
     L.mmf_debug_symmetric_schedule.restype = i64
     L.mmf_last_error.restype = ctypes.c_char_p

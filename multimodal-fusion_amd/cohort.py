@@ -16,7 +16,8 @@ from .wsi_tma_similarity import _slide_ptr, compute_wsi_tma_similarity_segmented
 def build_cohort_hypergraphs(wsi_features: torch.Tensor, wsi_positions: torch.Tensor, tma_features: torch.Tensor, *, wsi_ptr=None,
                              wsi_batch=None, tma_ptr=None, tma_batch=None, num_wsi_super_patches: int = 100, num_groups: int = 10,
                              hypergraph_k: int = 5, num_hyperedges: int = 10, lambda_h: float = 1.0, lambda_g: float = 1.0,
-                             device: Optional[torch.device] = None, keep_similarity: bool = False) -> Dict:
+                             device: Optional[torch.device] = None, keep_similarity: bool = False,
+                             budget_bytes: Optional[int] = None) -> Dict:
     """The hypergraph of every slide of a cohort.  Slide s is wsi rows wsi_ptr[s]:wsi_ptr[s+1] (patches) with tma rows
     tma_ptr[s]:tma_ptr[s+1]; each side's slides come as ptr or batch.  Every slide needs TMA rows (process_single_file skips a
     file without them; here that is a ValueError naming the slide).  Returns a dict:
@@ -29,7 +30,9 @@ def build_cohort_hypergraphs(wsi_features: torch.Tensor, wsi_positions: torch.Te
         stats                                                  per slide {"wsi_aggregation", "similarity", "grouping",
                                                                "hypergraph"}: process_single_file's dict, JSON-serialisable
 
-    Per slide everything equals the chain of the four plain mirrors on that slide."""
+    Per slide everything equals the chain of the four plain mirrors on that slide.  budget_bytes: the memory the similarity
+    blocks of one group of slides may take in the first step (aggregate_wsi_super_patches_segmented; None: its default); with
+    keep_similarity=False a slide whose block alone is larger has its statistics streamed and its block never stored."""
     what = "build_cohort_hypergraphs"
     if wsi_features.dim() != 2 or wsi_positions.dim() != 2 or tma_features.dim() != 2:
         raise ValueError(f"{what}: slide 0: wsi_features, wsi_positions and tma_features must be 2-D")
@@ -56,7 +59,8 @@ def build_cohort_hypergraphs(wsi_features: torch.Tensor, wsi_positions: torch.Te
         if not (1 <= H <= n_s):
             raise ValueError(f"{what}: slide {s}: n_samples={n_s} should be >= n_clusters={H}.")
     sf, sp, agg_stats, K_flat, k_ptr = aggregate_wsi_super_patches_segmented(
-        wsi_features, wsi_positions, C, lambda_h, lambda_g, device, ptr=wp, keep_similarity=keep_similarity)
+        wsi_features, wsi_positions, C, lambda_h, lambda_g, device, ptr=wp, keep_similarity=keep_similarity,
+        budget_bytes=budget_bytes)
     sw = torch.arange(S + 1, dtype=torch.int64) * C
     S_flat, s_ptr, sim_stats = compute_wsi_tma_similarity_segmented(sf, sp, tma_features, lambda_h, lambda_g, device, wsi_ptr=sw,
                                                                     tma_ptr=tp)

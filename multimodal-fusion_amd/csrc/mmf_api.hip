@@ -1382,12 +1382,6 @@ int mmf_threshold_edges_fill(const float* K, int64_t n, float threshold, const u
 }
 
 // ---- the same two steps for an N whose K = K_h * K_g does not fit: K is recomputed in row panels -----------------
-static int64_t pick_panel_rows(int64_t n, int64_t panel_rows) {
-  if (panel_rows <= 0) panel_rows = (int64_t(1) << 30) / (4 * n);     // about 1 GiB of f32 per panel
-  if (panel_rows < 128) panel_rows = 128;
-  if (panel_rows > n) panel_rows = n;
-  return panel_rows;
-}
 
 int mmf_combined_offdiag_median(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
                                 float lambda_g, int64_t panel_rows, float* out_median, int device_id, void* hip_stream) {

@@ -292,16 +292,42 @@ __device__ __forceinline__ double wave_sum(double x) {
 // kNoDiagonal as row0 for data without a diagonal).  One wave per row, 16 bytes per lane when n % 4 == 0.
 // part != NULL: the sweep also leaves the workgroup's statistic partial (sums around pivot[0], minimum, maximum) over the entries
 // it visits — mmf_array_stats then reads its array once instead of twice.
+//
+// CARRY (mmf_stream_stats.hip): K is a run of rows out of a longer array that one launch of `ln.grid` workgroups
+// would sweep — row li here is row ln.row0 + li there — and this launch stands in for that one on these rows.  Workgroup
+// blockIdx.x acts as workgroup (ln.block0 + blockIdx.x) % ln.grid of it and takes the rows that one would take; every lane
+// starts from the running (s1, s2, min, max) its counterpart left in `ln` and puts it back, so over all the runs a lane adds the
+// same values in the same order as in the one launch.  No partial is written: stat_lanes_finish_kernel reduces the lanes once.
+struct StatLanes {
+  double* s1; double* s2; float* mn; float* mx;      // [grid * 256]
+  int64_t grid, row0, block0;
+};
+
+static StatLanes stat_lanes_of(void* lanes, int64_t grid, int64_t row0, int64_t block0);
+
+template <bool CARRY>
 __global__ __launch_bounds__(256) void bracket_sweep_kernel(const float* __restrict__ K, int64_t n, int64_t row0, int64_t rows,
                                                             BracketState* st, float* __restrict__ buf, StatPartial* __restrict__ part,
-                                                            const float* __restrict__ pivot) {
+                                                            const float* __restrict__ pivot, StatLanes ln) {
   __shared__ float stage[4][1024];
   __shared__ unsigned long long wbelow[4];
   __shared__ StatPartial wstat[4];
-  const double pv = part ? (double)pivot[0] : 0.0;
+  const bool stats = CARRY || part;
+  const double pv = stats ? (double)pivot[0] : 0.0;
   double s1 = 0.0, s2 = 0.0;
   float smn = __builtin_huge_valf(), smx = -__builtin_huge_valf();
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int64_t li = (int64_t)blockIdx.x * 4 + w, step = (int64_t)gridDim.x * 4;
+  int64_t slot = 0;
+  if constexpr (CARRY) {
+    const int64_t lb = (ln.block0 + (int64_t)blockIdx.x) % ln.grid;
+    slot = lb * 256 + threadIdx.x;
+    s1 = ln.s1[slot]; s2 = ln.s2[slot]; smn = ln.mn[slot]; smx = ln.mx[slot];
+    step = ln.grid * 4;
+    const int64_t first = lb * 4 + w;                 // the wave's rows of the long array: first, first + step, ...
+    const int64_t skip = ln.row0 > first ? (ln.row0 - first + step - 1) / step : 0;
+    li = first + skip * step - ln.row0;
+  }
   const float lo = st->lo, hi = st->hi;
   const unsigned long long seg_cap = st->seg_cap;
   const int seg = (int)((blockIdx.x * 4u + (unsigned)w) % (unsigned)kBracketSegs);
@@ -320,7 +346,7 @@ __global__ __launch_bounds__(256) void bracket_sweep_kernel(const float* __restr
   auto offer = [&](float x, bool valid) {
     const bool in = valid && x >= lo && x <= hi;
     below += (valid && x < lo) ? 1ull : 0ull;
-    if (part && valid) {
+    if (stats && valid) {
       const double dx = (double)x - pv;
       s1 += dx; s2 = __builtin_fma(dx, dx, s2);
       smn = fminf(smn, x); smx = fmaxf(smx, x);
@@ -330,7 +356,7 @@ __global__ __launch_bounds__(256) void bracket_sweep_kernel(const float* __restr
     cnt += __popcll(mask);
   };
   const bool vec = ((n & 3) == 0) && ((reinterpret_cast<uintptr_t>(K) & 15) == 0);
-  for (int64_t li = (int64_t)blockIdx.x * 4 + w; li < rows; li += (int64_t)gridDim.x * 4) {
+  for (; li < rows; li += step) {
     const float* row = K + li * n;
     const int64_t i = row0 + li;
     if (vec) {
@@ -357,7 +383,9 @@ __global__ __launch_bounds__(256) void bracket_sweep_kernel(const float* __restr
     const unsigned long long lo32 = (unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)below, o);
     below += (hi32 << 32) | lo32;
   }
-  if (part) {
+  if constexpr (CARRY) {
+    ln.s1[slot] = s1; ln.s2[slot] = s2; ln.mn[slot] = smn; ln.mx[slot] = smx;
+  } else if (part) {
     s1 = wave_sum(s1); s2 = wave_sum(s2);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { smn = fminf(smn, __shfl_xor(smn, o)); smx = fmaxf(smx, __shfl_xor(smx, o)); }
@@ -368,7 +396,7 @@ __global__ __launch_bounds__(256) void bracket_sweep_kernel(const float* __restr
   if (threadIdx.x == 0) {
     const unsigned long long t = wbelow[0] + wbelow[1] + wbelow[2] + wbelow[3];
     if (t) atomicAdd(&st->below[(blockIdx.x % (unsigned)kBracketSegs) * kBracketPad], t);
-    if (part) {
+    if (!CARRY && part) {
       StatPartial r = wstat[0];
       for (int i = 1; i < 4; ++i) { r.s1 += wstat[i].s1; r.s2 += wstat[i].s2; r.mn = fminf(r.mn, wstat[i].mn); r.mx = fmaxf(r.mx, wstat[i].mx); }
       part[blockIdx.x] = r;
@@ -450,8 +478,10 @@ size_t median_scratch_bytes(unsigned long long count) {
 // One host synchronisation (the bracket's verdict) when the one-sweep path is taken.
 // stat_part / stat_pivot / stat_nparts (optional): the one-sweep path leaves statistic partials of the population there (one per
 // workgroup of every sweep launch, *stat_nparts of them); *stat_nparts stays 0 when the sweep did not run.
+// carry (optional, with stat_part): the sweep hands over a long array of rows in runs (SweepCarry, mmf_host.h) and the partials
+// are those of ONE launch over all of it.
 int lower_median_of(unsigned long long count, const MedianSampler& sampler, const MedianSweep& sweep, float* out, void* scratch,
-                    hipStream_t s, void* stat_part, const float* stat_pivot, int64_t* stat_nparts) {
+                    hipStream_t s, void* stat_part, const float* stat_pivot, int64_t* stat_nparts, SweepCarry* carry) {
   if (stat_nparts) *stat_nparts = 0;
   int64_t parts_used = 0;
   char* base = static_cast<char*>(scratch);
@@ -468,17 +498,43 @@ int lower_median_of(unsigned long long count, const MedianSampler& sampler, cons
     hipLaunchKernelGGL(bracket_bounds_kernel, dim3(1), dim3(1024), kBracketSample * 4, s, sample, kBracketSample,
                        kBracketSample / 2 - kBracketHalfWidth, kBracketSample / 2 + kBracketHalfWidth, rank, cap / kBracketSegs, st);
     MMF_LAUNCH_CHECK();
+    bool carry_tail = false;
+    if (carry && stat_part) MMF_TRY(launch_stat_lanes_init(carry->lanes, carry->grid, s));
     MMF_TRY(sweep([&](const float* data, int64_t cols, int64_t row0, int64_t rows) -> int {
       if (rows <= 0) return MMF_OK;
+      if (carry && stat_part) {
+        if (carry->row0 >= 0) {                        // a run of whole rows: the workgroups of the one launch that own some of them
+          const int64_t w0 = carry->row0 % (carry->grid * 4);
+          int64_t nb = (w0 % 4 + rows + 3) / 4;
+          if (nb > carry->grid) nb = carry->grid;
+          const StatLanes ln = stat_lanes_of(carry->lanes, carry->grid, carry->row0, w0 / 4);
+          hipLaunchKernelGGL(bracket_sweep_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, data, cols, row0, rows, st, buf,
+                             (StatPartial*)nullptr, stat_pivot, ln);
+          MMF_LAUNCH_CHECK();
+          return MMF_OK;
+        }
+        // the ragged last row: the launch of one workgroup it has in the plain sweep, its partial behind the others
+        if (rows != 1 || carry_tail) { set_error("median sweep: a carried sweep has one ragged last row"); return MMF_E_INTERNAL; }
+        hipLaunchKernelGGL(bracket_sweep_kernel<false>, dim3(1), dim3(256), 0, s, data, cols, row0, rows, st, buf,
+                           reinterpret_cast<StatPartial*>(stat_part) + carry->grid, stat_pivot, StatLanes{});
+        MMF_LAUNCH_CHECK();
+        carry_tail = true;
+        return MMF_OK;
+      }
       int64_t grid = (rows + 3) / 4;
       if (grid > (stat_part ? 2040 : 2048)) grid = stat_part ? 2040 : 2048;     // a ragged last row adds one launch of one workgroup
       StatPartial* sp = stat_part ? reinterpret_cast<StatPartial*>(stat_part) + parts_used : nullptr;
       if (sp && parts_used + grid > 2048) { set_error("median sweep: more than 2048 statistic partials"); return MMF_E_INTERNAL; }
-      hipLaunchKernelGGL(bracket_sweep_kernel, dim3((unsigned)grid), dim3(256), 0, s, data, cols, row0, rows, st, buf, sp, stat_pivot);
+      hipLaunchKernelGGL(bracket_sweep_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, data, cols, row0, rows, st, buf, sp, stat_pivot,
+                         StatLanes{});
       MMF_LAUNCH_CHECK();
       if (sp) parts_used += grid;
       return MMF_OK;
     }));
+    if (carry && stat_part) {
+      MMF_TRY(launch_stat_lanes_finish(carry->lanes, carry->grid, stat_part, s));
+      parts_used = carry->grid + (carry_tail ? 1 : 0);
+    }
     if (stat_nparts) *stat_nparts = parts_used;
     hipLaunchKernelGGL(bracket_begin_kernel, dim3(1), dim3(64), 0, s, st);
     MMF_LAUNCH_CHECK();
@@ -541,8 +597,16 @@ int launch_lower_median(const float* v, int64_t count, float* out, void* scratch
 // every workgroup writes its partial, one workgroup merges them in index order.
 // Replaces: K.mean(), K.std(), K.min(), K.max() — four passes — at preprocess_hypergraph.py:190-195, 260-263.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void stats_partial_kernel(const float* __restrict__ v, int64_t count, StatPartial* __restrict__ part) {
-  const double p = (double)v[0];                       // pivot: sums of (x - p) stay small when the values cluster
+//
+// CARRY (mmf_stream_stats.hip): v is a run out of a longer 16-byte aligned array that one launch of `ln.grid`
+// workgroups would reduce: ln.row0 is the index there of this run's first group of four values, `count` the run's length, and
+// the run ends either on a group boundary or at the end of the array (then its last count % 4 values are the array's scalar
+// tail).  Thread t here acts as thread (ln.block0 * 256 + t) % (ln.grid * 256) of that launch, takes the groups it would take,
+// starts from the lane's running sums in `ln` and puts them back; pivot[0] is the array's first value.
+template <bool CARRY>
+__global__ __launch_bounds__(256) void stats_partial_kernel(const float* __restrict__ v, int64_t count, StatPartial* __restrict__ part,
+                                                            const float* __restrict__ pivot, StatLanes ln) {
+  const double p = CARRY ? (double)pivot[0] : (double)v[0];   // pivot: sums of (x - p) stay small when the values cluster
   double s1 = 0.0, s2 = 0.0;
   float mn = __builtin_huge_valf(), mx = -__builtin_huge_valf();
   auto feed = [&](float x) {
@@ -550,6 +614,26 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(const float* __restr
     s1 += dx; s2 = __builtin_fma(dx, dx, s2);
     mn = fminf(mn, x); mx = fmaxf(mx, x);
   };
+  if constexpr (CARRY) {
+    const int64_t nth = ln.grid * 256;
+    const int64_t tid = ((ln.block0 + (int64_t)blockIdx.x) % ln.grid) * 256 + threadIdx.x;
+    s1 = ln.s1[tid]; s2 = ln.s2[tid]; mn = ln.mn[tid]; mx = ln.mx[tid];
+    const int64_t n4 = count >> 2;
+    const int64_t skip = ln.row0 > tid ? (ln.row0 - tid + nth - 1) / nth : 0;
+    const bool vec = (reinterpret_cast<uintptr_t>(v) & 15) == 0;
+    for (int64_t i = tid + skip * nth - ln.row0; i < n4; i += nth) {
+      if (vec) {
+        const f32x4 x = reinterpret_cast<const f32x4*>(v)[i];
+        feed(x[0]); feed(x[1]); feed(x[2]); feed(x[3]);
+      } else {
+        const float x0 = v[4 * i], x1 = v[4 * i + 1], x2 = v[4 * i + 2], x3 = v[4 * i + 3];
+        feed(x0); feed(x1); feed(x2); feed(x3);
+      }
+    }
+    if (n4 * 4 + tid < count) feed(v[n4 * 4 + tid]);     // the array's scalar tail: threads 0 .. 2 of the one launch
+    ln.s1[tid] = s1; ln.s2[tid] = s2; ln.mn[tid] = mn; ln.mx[tid] = mx;
+    return;
+  }
   const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
   const int64_t n4 = ((reinterpret_cast<uintptr_t>(v) & 15) == 0) ? (count >> 2) : 0;
   for (int64_t i = tid; i < n4; i += nth) {
@@ -567,6 +651,31 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(const float* __restr
   if (threadIdx.x == 0) {
     StatPartial r = w[0];
     for (int i = 1; i < 4; ++i) { r.s1 += w[i].s1; r.s2 += w[i].s2; r.mn = fminf(r.mn, w[i].mn); r.mx = fmaxf(r.mx, w[i].mx); }
+    part[blockIdx.x] = r;
+  }
+}
+
+// The lanes of a carried launch (StatLanes): every lane at the state it has before it adds its first value, and the end both
+// producers share — wave butterflies, then the workgroup's four waves in order — once the last run has been added.
+__global__ __launch_bounds__(256) void stat_lanes_init_kernel(StatLanes ln) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  ln.s1[i] = 0.0; ln.s2[i] = 0.0; ln.mn[i] = __builtin_huge_valf(); ln.mx[i] = -__builtin_huge_valf();
+}
+
+__global__ __launch_bounds__(256) void stat_lanes_finish_kernel(StatLanes ln, StatPartial* __restrict__ part) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  double s1 = ln.s1[i], s2 = ln.s2[i];
+  float mn = ln.mn[i], mx = ln.mx[i];
+  s1 = wave_sum(s1); s2 = wave_sum(s2);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+  __shared__ StatPartial w[4];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) w[wave] = StatPartial{s1, s2, mn, mx};
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    StatPartial r = w[0];
+    for (int k = 1; k < 4; ++k) { r.s1 += w[k].s1; r.s2 += w[k].s2; r.mn = fminf(r.mn, w[k].mn); r.mx = fmaxf(r.mx, w[k].mx); }
     part[blockIdx.x] = r;
   }
 }
@@ -635,12 +744,50 @@ int launch_array_stats(const float* v, int64_t count, double* out, void* scratch
     int64_t grid = (count + 256 * 16 - 1) / (256 * 16);
     if (grid > 2048) grid = 2048;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(stats_partial_kernel, dim3((unsigned)grid), dim3(256), 0, s, v, count, part);
+    hipLaunchKernelGGL(stats_partial_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, v, count, part, (const float*)nullptr, StatLanes{});
     MMF_LAUNCH_CHECK();
     nparts = grid;
   }
   MMF_TRY(launch_stats_finish(part, nparts, v, count, out, s));
   return launch_stats_set_median(med, out, s);
+}
+
+// ---- statistics carried across the runs of an array that is never whole in memory (mmf_stream_stats.hip) ----
+size_t stat_lanes_bytes(int64_t grid) { return 2 * ws_bytes((size_t)grid * 256, 8) + 2 * ws_bytes((size_t)grid * 256, 4); }
+static StatLanes stat_lanes_of(void* lanes, int64_t grid, int64_t row0, int64_t block0) {
+  char* b = static_cast<char*>(lanes);
+  const size_t d8 = ws_bytes((size_t)grid * 256, 8), d4 = ws_bytes((size_t)grid * 256, 4);
+  return StatLanes{reinterpret_cast<double*>(b), reinterpret_cast<double*>(b + d8), reinterpret_cast<float*>(b + 2 * d8),
+                   reinterpret_cast<float*>(b + 2 * d8 + d4), grid, row0, block0};
+}
+int launch_stat_lanes_init(void* lanes, int64_t grid, hipStream_t s) {
+  hipLaunchKernelGGL(stat_lanes_init_kernel, dim3((unsigned)grid), dim3(256), 0, s, stat_lanes_of(lanes, grid, 0, 0));
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+int launch_stat_lanes_finish(void* lanes, int64_t grid, void* part, hipStream_t s) {
+  hipLaunchKernelGGL(stat_lanes_finish_kernel, dim3((unsigned)grid), dim3(256), 0, s, stat_lanes_of(lanes, grid, 0, 0),
+                     reinterpret_cast<StatPartial*>(part));
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+bool median_one_sweep(unsigned long long count) { return bracket_capacity(count) != 0ull; }
+int64_t stats_partial_grid(int64_t count) {
+  int64_t grid = (count + 256 * 16 - 1) / (256 * 16);
+  if (grid > 2048) grid = 2048;
+  return grid < 1 ? 1 : grid;
+}
+// values v[0 .. count) = values [group0 * 4, group0 * 4 + count) of the array that stats_partial_kernel would reduce with `grid`
+// workgroups; count % 4 != 0 only for the run that ends the array
+int launch_stats_partial_carry(const float* v, int64_t count, int64_t group0, const float* pivot, void* lanes, int64_t grid, hipStream_t s) {
+  if (count <= 0) return MMF_OK;
+  const int64_t nth = grid * 256, t0 = group0 % nth;
+  int64_t nb = (t0 % 256 + (count >> 2) + 255) / 256, b0 = t0 / 256;
+  if (nb > grid || (count & 3)) { nb = grid; b0 = 0; }          // the scalar tail belongs to threads 0 .. 2
+  hipLaunchKernelGGL(stats_partial_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, v, count, (StatPartial*)nullptr, pivot,
+                     stat_lanes_of(lanes, grid, group0, b0));
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
 }
 
 // the merge of per-workgroup partials (StatPartial: {double s1, s2; float mn, mx}) written by ANY producer kernel

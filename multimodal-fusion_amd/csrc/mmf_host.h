@@ -325,8 +325,25 @@ using MedianSweep = std::function<int(const MedianConsume&)>;      // streams th
 using MedianSampler = std::function<int(float* sample, int s)>;   // s values at hashed positions (device)
 size_t median_scratch_bytes(unsigned long long count);
 int64_t median_no_diagonal_row();                                  // row0 for data without a diagonal to skip
+// A sweep whose rows are never all in memory (mmf_stream_stats.hip): the statistic partials of lower_median_of's one sweep are
+// those of ONE launch of `grid` workgroups over all the whole rows, the lanes' running sums kept in `lanes` between the runs.
+// The sweep sets row0 before every consume(): the index of the run's first row among all rows, or -1 for the ragged last row.
+struct SweepCarry {
+  void* lanes;          // stat_lanes_bytes(grid)
+  int64_t grid;         // workgroups of that one launch: min((rows + 3) / 4, 2040)
+  int64_t row0;
+};
 int lower_median_of(unsigned long long count, const MedianSampler& sampler, const MedianSweep& sweep, float* out, void* scratch,
-                    hipStream_t s, void* stat_part = nullptr, const float* stat_pivot = nullptr, int64_t* stat_nparts = nullptr);
+                    hipStream_t s, void* stat_part = nullptr, const float* stat_pivot = nullptr, int64_t* stat_nparts = nullptr,
+                    SweepCarry* carry = nullptr);
+bool median_one_sweep(unsigned long long count);                   // does lower_median_of try its one sweep for this population?
+size_t stat_lanes_bytes(int64_t grid);
+int launch_stat_lanes_init(void* lanes, int64_t grid, hipStream_t s);
+int launch_stat_lanes_finish(void* lanes, int64_t grid, void* part /* [grid] partials */, hipStream_t s);
+// stats_partial_kernel's assignment, run by run: its grid for `count` values, and one run of the array (v = values
+// [4 group0, 4 group0 + count) of it; only the array's last run may have count % 4 != 0; pivot[0] = the array's first value)
+int64_t stats_partial_grid(int64_t count);
+int launch_stats_partial_carry(const float* v, int64_t count, int64_t group0, const float* pivot, void* lanes, int64_t grid, hipStream_t s);
 int launch_sample_gather(const float* data, int64_t n_sq, unsigned long long count, float* sample, int s_count, hipStream_t s);
 int launch_sample_pairs(const void* A, const void* B, int64_t nb, int64_t d, int dtype, float lambda, const float* P, int dp,
                         float lambda_g, int offdiag, unsigned long long count, float* sample, int s_count, hipStream_t s);
@@ -383,6 +400,14 @@ int launch_threshold_count_seg(const float* K, const int64_t* d_ptr, const int64
 int launch_threshold_fill_seg(const float* K, const int64_t* d_ptr, const int64_t* d_kptr, int64_t S, int64_t n, const float* thr,
                               const unsigned long long* row_off, int64_t* ei, float* ew, int64_t capacity, hipStream_t s);
 
+// rows of a panel of a recomputed n x n matrix: the caller's panel_rows, or about 1 GiB of f32 (at least 128 rows, at most n)
+inline int64_t pick_panel_rows(int64_t n, int64_t panel_rows) {
+  if (panel_rows <= 0) panel_rows = (int64_t(1) << 30) / (4 * n);
+  if (panel_rows < 128) panel_rows = 128;
+  if (panel_rows > n) panel_rows = n;
+  return panel_rows;
+}
+
 // mmf_segments.hip: cluster-shaped steps (labels -> members, per-cluster means, cliques, k-NN pair dedup)
 int segment_max_segments();
 size_t segment_sort_scratch_bytes(int64_t n, int64_t S);
@@ -392,6 +417,8 @@ int launch_segment_mean(const float* X, int64_t d, const int64_t* order, const i
 size_t segment_offdiag_scratch_bytes(int64_t n);
 int launch_segment_offdiag_mean(const float* K, int64_t n, const int64_t* order, const int64_t* offsets, int64_t S,
                                 double* out_mean, void* scratch, hipStream_t s);
+int launch_segment_member_clusters(const int64_t* offsets, int64_t S, int32_t* seg_of /* [n] */, hipStream_t s);
+int launch_segment_offdiag_final(const double* row_sum, const int64_t* offsets, int64_t S, double* out_mean, hipStream_t s);
 size_t clique_scratch_bytes(int64_t n, int64_t S);
 int launch_clique_pairs(const int64_t* order, const int64_t* offsets, int64_t n, int64_t S, int64_t* lo, int64_t* hi,
                         int64_t capacity, int64_t* out_count, void* scratch, hipStream_t s);

@@ -244,10 +244,20 @@ int launch_segment_offdiag_mean(const float* K, int64_t n, const int64_t* order,
                                 double* out_mean, void* scratch, hipStream_t s) {
   double* row_sum = reinterpret_cast<double*>(scratch);
   int32_t* seg_of = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(scratch) + ws_bytes((size_t)n, 8));
-  hipLaunchKernelGGL(seg_of_kernel, dim3((unsigned)S), dim3(256), 0, s, offsets, (int)S, seg_of);
-  MMF_LAUNCH_CHECK();
+  MMF_TRY(launch_segment_member_clusters(offsets, S, seg_of, s));
   hipLaunchKernelGGL(seg_row_sums_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, K, n, order, offsets, seg_of, n, row_sum);
   MMF_LAUNCH_CHECK();
+  return launch_segment_offdiag_final(row_sum, offsets, S, out_mean, s);
+}
+
+// its two ends, also for a K that is recomputed in panels (mmf_stream_stats.hip): the cluster of every member before the row
+// sums, the clusters' means after the last of them
+int launch_segment_member_clusters(const int64_t* offsets, int64_t S, int32_t* seg_of, hipStream_t s) {
+  hipLaunchKernelGGL(seg_of_kernel, dim3((unsigned)S), dim3(256), 0, s, offsets, (int)S, seg_of);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+int launch_segment_offdiag_final(const double* row_sum, const int64_t* offsets, int64_t S, double* out_mean, hipStream_t s) {
   hipLaunchKernelGGL(seg_offdiag_final_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, row_sum, offsets, (int)S, out_mean);
   MMF_LAUNCH_CHECK();
   return MMF_OK;

@@ -21,11 +21,13 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .super_patch_stats import super_patch_stats_streamed
 from .build_hypergraph import preprocess_hypergraph, similarity_kernel
 from .build_hypergraph._common import compute_device, result_device_like_preprocess, to_gpu
 from .weighted_hypergraph import _groups
 from .wsi_tma_similarity import _STAT_KEYS, _slide_ptr
 
+STREAM_MIN_VALUES = 1 << 22   # a block of fewer values (16 MiB) is stored even when it alone exceeds the budget
 MAX_CLUSTERS = 16384          # clusters per slide (the LDS histogram of one slide's chunk, csrc/mmf_pool.hip)
 
 
@@ -156,9 +158,11 @@ def aggregate_wsi_super_patches_segmented(wsi_features: torch.Tensor, wsi_positi
     The labels come from one kmeans_fit_predict_segmented call.  `wsi_similarity_flat`, if given, is used as K (the blocks in the
     layout of ops.sim_dense_combined_segmented) and returned; otherwise K is computed.  With keep_similarity=False no K is
     returned and the slides are processed in groups of consecutive slides whose blocks fit `budget_bytes` together (default:
-    similarity_kernel.STREAM_BYTES).  A slide whose block alone exceeds the budget runs alone and still needs its n_s^2 floats, as
-    the plain mirror does: the budget bounds the memory of a group, not of one slide.  One host read per group (status, intra
-    means, statistics) besides the KMeans call's own.  An empty cluster raises ValueError(f"slide {s}: Cluster {c} is empty")."""
+    similarity_kernel.STREAM_BYTES).  A slide whose block alone exceeds the budget runs alone, and if that block holds 2^22 values
+    or more it is never stored: its statistics come from super_patch_stats_streamed, which recomputes K in row panels
+    (similarity_kernel.PANEL_ROWS) and returns the same bits (a smaller block over the budget, 16 MiB at most, is still stored).
+    info["streamed"] says per group whether that happened.  One host read per group (status, intra means, statistics) besides
+    the KMeans call's own.  An empty cluster raises ValueError(f"slide {s}: Cluster {c} is empty")."""
     what = "aggregate_wsi_super_patches_segmented"
     if wsi_features.dim() != 2 or wsi_positions.dim() != 2:
         raise ValueError(f"{what}: slide 0: wsi_features [N, D] and wsi_positions [N, dp] must be 2-D")
@@ -175,7 +179,10 @@ def aggregate_wsi_super_patches_segmented(wsi_features: torch.Tensor, wsi_positi
                          f"{wsi_similarity_flat.numel()} values, the blocks of the slides {int(k_ptr[-1])}")
     budget = int(similarity_kernel.STREAM_BYTES if budget_bytes is None else budget_bytes)
     whole = keep_similarity or wsi_similarity_flat is not None
-    groups = [(0, S)] if whole else group_plan(sizes, budget)
+    plan = [(0, S, False)] if whole else _groups([int(v) for v in sizes], budget)
+    groups = [(a, b) for a, b, _ in plan]
+    # a slide that _groups set apart is streamed unless its block is small enough to go through the plain routines anyway
+    streamed = [bool(alone) and not whole and int(sizes[a]) ** 2 >= STREAM_MIN_VALUES for a, _, alone in plan]
     out_dev = result_device_like_preprocess(wsi_features, device)
     dev = out_dev if out_dev.type == "cuda" else compute_device(wsi_features, wsi_positions)
     F, P = to_gpu(wsi_features, dev), to_gpu(wsi_positions, dev)
@@ -185,11 +192,13 @@ def aggregate_wsi_super_patches_segmented(wsi_features: torch.Tensor, wsi_positi
     super_f = torch.empty((S * C, F.shape[1]), dtype=torch.float32, device=dev)
     super_p = torch.empty((S * C, P.shape[1]), dtype=torch.float32, device=dev)
     stats: List[Dict] = []
-    for a, b in groups:
+    for (a, b), stream in zip(groups, streamed):
         r0, r1 = int(p[a]), int(p[b])
         local = (p[a:b + 1] - r0).contiguous()
         Fg, Pg = F[r0:r1], P[r0:r1]
-        if K_all is not None:
+        if stream:
+            K = None
+        elif K_all is not None:
             K = K_all[int(k_ptr[a]):int(k_ptr[b])]
         else:
             K, _ = ops.sim_dense_combined_segmented(Fg, Pg, lh, lg, ptr=local)
@@ -197,6 +206,8 @@ def aggregate_wsi_super_patches_segmented(wsi_features: torch.Tensor, wsi_positi
                 K_all = K
         _, offsets, order, status = segment_sort_segmented(labels[r0:r1], C, ptr=local)
         sf, sp, intra, k_stats = pool_super_patches_segmented(Fg, Pg, order, offsets, C, ptr=local, K_flat=K)
+        if stream:                                     # one slide: its local rows are the rows mmf_segment_sort would give
+            intra, k_stats = super_patch_stats_streamed(Fg, Pg, order, offsets, C, lh, lg, panel_rows=similarity_kernel.PANEL_ROWS)
         super_f[a * C:b * C], super_p[a * C:b * C] = sf, sp
         host = torch.cat([status.to(torch.float64), intra, k_stats.reshape(-1)]).cpu().numpy()      # the group's one host read
         del K
@@ -219,6 +230,6 @@ def aggregate_wsi_super_patches_segmented(wsi_features: torch.Tensor, wsi_positi
     res = (super_f.to(out_dev), super_p.to(out_dev), stats, K_out, k_ptr)
     if return_info:
         info = {"kmeans_backend": preprocess_hypergraph.KMEANS_BACKEND, "ambiguous_draws": draws, "ambiguous_trials": trials,
-                "groups": [list(g) for g in groups]}
+                "groups": [list(g) for g in groups], "streamed": streamed}
         return res + (info,)
     return res
