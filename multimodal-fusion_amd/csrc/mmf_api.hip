@@ -322,6 +322,12 @@ static void symmetric_live_mode(bool* live, bool* forward) {
   *live = (v == 1 || v == 2);
   *forward = (v == 0 || v == 2);
 }
+// MMF_SYMMETRIC_PRUNE (read per call): unset / 1 = the logs' entries are filed into the rows' received lists only if select could
+// still keep them (sym_scatter_kernel), 0 = every entry is filed.  Results are the same; for measurements and tests.
+static bool symmetric_prune_mode() {
+  const char* e = getenv("MMF_SYMMETRIC_PRUNE");
+  return !e || atoi(e) != 0;
+}
 static constexpr int64_t kSymMinRows = 131072;
 static bool symmetric_scan_wanted(int64_t n, int dp, int bcap, int metric, int forced_splits, bool same_ids, int* G) {
   if (!same_ids || dp != 512 || bcap != scan_bf16_cap(1, 512) || forced_splits != 0) return false;
@@ -650,7 +656,7 @@ struct FastTail {
       symmetric_live_mode(&live, &forward);
       const WsKept tables{sym.sched, (n + 255) / 256, sym_G, forward ? 1 : 0};
       MMF_TRY(launch_scan_b16_sym(fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, r.d, fo.f16, r.metric, kk, sym_G, live, forward,
-                                  !(sym_kept == tables), L, scan_scratch, sym, pn, s, &grid));
+                                  symmetric_prune_mode(), !(sym_kept == tables), L, scan_scratch, sym, pn, s, &grid));
       if (sym_keep) *sym_keep = tables;
     } else if (fo.n_panels == 0) {
       MMF_TRY(launch_scan_b16(fo.ZQ, fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, m, fo.m_pad_tiles, fo.dp, r.d, fo.f16,
@@ -684,14 +690,14 @@ struct FastTail {
       MMF_HIP(hipMemcpy(hc.data(), sym_cnt, hc.size() * 4, hipMemcpyDeviceToHost));
       MMF_HIP(hipMemcpy(hl.data(), sym.log_cnt, hl.size() * 4, hipMemcpyDeviceToHost));
       MMF_HIP(hipMemcpy(&none, sym.none_cnt, 4, hipMemcpyDeviceToHost));
-      unsigned long long tot = 0; uint32_t mx = 0, lmx = 0;
+      unsigned long long tot = 0, logged = 0; uint32_t mx = 0, lmx = 0;
       for (uint32_t v : hc) { tot += v; if (v > mx) mx = v; }
-      for (uint32_t v : hl) if (v > lmx) lmx = v;
+      for (uint32_t v : hl) { logged += v; if (v > lmx) lmx = v; }
       bool live, forward;
       symmetric_live_mode(&live, &forward);
-      fprintf(stderr, "[mmf symmetric] G %d grid %lld %s %s: rows without a threshold %u, received entries %llu (%.1f per row, largest %u of %d), fullest wave log %u of %d\n",
+      fprintf(stderr, "[mmf symmetric] G %d grid %lld %s %s: rows without a threshold %u, received entries %llu (%.1f per row, largest %u of %d), fullest wave log %u of %d, logged entries %llu (%.1f per row, filing %s)\n",
               sym_G, (long long)sym_grid(), live ? "live" : "frozen", forward ? "ahead" : "back", none, tot, (double)tot / (double)n, mx,
-              kSymCap, lmx, kSymLogPerWave);
+              kSymCap, lmx, kSymLogPerWave, logged, (double)logged / (double)n, symmetric_prune_mode() ? "pruned" : "complete");
     }
     // the f32 rows are first touched here: a caller that is still receiving them (overlapped
     // all-gather) hands in the event that marks their arrival

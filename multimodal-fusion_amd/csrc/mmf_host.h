@@ -286,7 +286,7 @@ int launch_scan_b16(const void* ZQ, const void* ZC, const float* cb, const float
 int launch_scan_b16_audit(const ScanB16Panel& pn, uint32_t* overflow, int64_t n_rows, hipStream_t s);
 size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G);
 int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const float* rn, const float* un, const uint32_t* maxima,
-                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, bool live, bool forward, bool tables,
+                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, bool live, bool forward, bool prune, bool tables,
                         const CandLists& L, void* scratch, const SymBuffers& sb, const ScanB16Panel& pn, hipStream_t s, int* grid_out);
 size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap);
 int scan_bf16_slot_ulp(int cap);

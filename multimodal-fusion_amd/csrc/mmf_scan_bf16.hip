@@ -282,6 +282,9 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 #ifndef MMF_SYM_ABLATE
 #define MMF_SYM_ABLATE 0   // timing-only variants of the SYM == 2 kernel's candidate direction (sym_offer below)
 #endif
+#ifndef MMF_SYM_EARLY_THR
+#define MMF_SYM_EARLY_THR 1   // SYM == 2: 1 = ONE 64-lane threshold DMA per iteration for both tiles of the next group, issued between
+#endif                        // the iteration's two chains; 0 = one 32-lane DMA behind each chain (the placement before; scripts/ab_build.sh)
 template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0>
 __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(ScanB16Args a) {
   static_assert(!SPLITK || (TPB == 1 && NW == 8 && (KS % 8) == 0), "split-k pairs");
@@ -492,6 +495,15 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
                                                (int)(uint32_t)(bsrc - cb0), 0, 16);
   };
 
+  // ... and of the 64 rows of BOTH tiles of a group in one DMA by all 64 lanes: a group's two tiles are consecutive rows (ranges
+  // are multiples of 8 tiles and the jump to the second range sits on a group boundary) and its two stages are adjacent
+  auto issue_thr_pair = [&](const char* bsrc, int stage) {
+    const __amdgpu_buffer_rsrc_t trsrc = __builtin_amdgcn_make_buffer_rsrc(a.sym_thr, 0, -1, 0x00020000);
+    const uint32_t l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(trsrc, (__attribute__((address_space(3))) void*)sym_thr_stage(stage), 4, (int)(l * 4u),
+                                             (int)(uint32_t)(bsrc - cb0), 0, 16);
+  };
+
   if (SPLITK && tid < NQW) ack[tid] = -1;
   const int Ti = (int)T;
   if (Ti > 0) {   // first group of TPB tiles -> stages 0 .. TPB-1
@@ -500,9 +512,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       const bool real = u < Ti;
 #pragma unroll
       for (int i = 0; i < PPW; ++i) issue_piece(real ? zt0 + u * (int64_t)TILEB : zc0, u, i);
-      if (wave == (u & (NW - 1))) issue_bias(real ? ct0 + u * B_CT * 4 : cb0, u);
-      if constexpr (SYM == 2) { if (wave == ((u + 4) & (NW - 1))) issue_thr(real ? ct0 + u * B_CT * 4 : cb0, u); }
+      if constexpr (SYM == 0) { if (wave == (u & (NW - 1))) issue_bias(real ? ct0 + u * B_CT * 4 : cb0, u); }
+      if constexpr (SYM == 2 && !MMF_SYM_EARLY_THR) { if (wave == ((u + 4) & (NW - 1))) issue_thr(real ? ct0 + u * B_CT * 4 : cb0, u); }
     }
+    if constexpr (SYM == 2 && MMF_SYM_EARLY_THR) { if (wave == 4) issue_thr_pair(Ti >= TPB ? ct0 : cb0, 0); }
   }
   // The DMA pieces of tile t+TPB are issued inside the MFMA chain of tile t, one per group of GRP MFMAs.  The
   // chain is straight-line code and the DMA is unconditional — past the end of the range it re-fetches tile 0
@@ -519,11 +532,17 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   struct Acc { f32x4 t[2][2]; };                     // [candidate block][query block]
   auto tile_body = [&](const char* tb, const float* cbt, const char* src, int s2) -> Acc {
     Acc acc;
+    if constexpr (SYM != 0) {   // cosine / dot only (launch_scan_b16_sym): the bias of every real row is zero — no stage, no read;
+                                // padding rows are masked behind the chain (mask_padding)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) { acc.t[cb][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc.t[cb][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    } else {
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
       f32x4 b4 = *reinterpret_cast<const f32x4*>(cbt + 16 * cb + 4 * g);
       if (SPLITK && !owner) b4 = f32x4{0.f, 0.f, 0.f, 0.f};      // the bias is added once, by the lower-half wave
       acc.t[cb][0] = b4; acc.t[cb][1] = b4;
+    }
     }
     // A fragments are read PD k-steps ahead of the MFMAs that consume them (explicit register ring)
     constexpr int PD = 2;
@@ -565,6 +584,21 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
     const f32x4& p = x.t[0][qb];
     const f32x4& q = x.t[1][qb];
     return fmaxf(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])), fmaxf(fmaxf(q[0], q[1]), fmaxf(q[2], q[3])));
+  };
+  // SYM: without a bias nothing rejects the padding rows of the image's last row block (zero operands: G = 0, which beats the real
+  // candidates of a row whose best cosines are negative).  A wave-uniform test per tile — does it reach past the real rows — sends
+  // exactly those tiles through a cold branch that sets the padding rows' values to -inf, what their bias used to make them.
+  auto mask_padding = [&](Acc& x, int tt) {
+    const int64_t r0 = (int64_t)id_base + (int64_t)tt * B_CT + ((tt >= sym_n1) ? (int64_t)sym_skip * B_CT : 0);   // first row of the tile
+    if (__builtin_expect(r0 + B_CT > a.m, 0)) {
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          if (r0 + 16 * cb + 4 * g + jj >= a.m) { x.t[cb][0][jj] = kNegInf; x.t[cb][1][jj] = kNegInf; }
+        }
+      }
+    }
   };
   // thresholds of the two queries this lane holds values for: its own list's and its partner's (lane ^ 16);
   // they change only inside the list code and in sync_seed, and are re-read from the partner there
@@ -751,9 +785,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       Acc acc;
       acc = tile_body(tiles + (sg + u) * TILEB + kbyte, cbs + (sg + u) * 64, src, ng + u);
       // (behind the chain: issued in front of it, the same DMA costs +8 %; mid-chain needs a branch inside the chain)
-      if (wave == ((t + TPB) & (NW - 1))) issue_bias(more ? bsrc + u * B_CT * 4 : cb0, ng + u);
+      if constexpr (SYM == 0) { if (wave == ((t + TPB) & (NW - 1))) issue_bias(more ? bsrc + u * B_CT * 4 : cb0, ng + u); }
+      else mask_padding(acc, t);
       if constexpr (SYM == 2 && MMF_SYM_ABLATE != 2) {
-        if (wave == ((t + TPB + 4) & (NW - 1))) issue_thr(more ? bsrc + u * B_CT * 4 : cb0, ng + u);
+        // the next group's thresholds: between the iteration's two chains, far from either barrier (issued behind the LAST chain, a
+        // fetch that has not landed holds all eight waves at the next barrier); the issuing wave rotates with the iteration
+        if constexpr (MMF_SYM_EARLY_THR) { if (u == 0 && wave == (j & (NW - 1))) issue_thr_pair(more ? bsrc : cb0, ng); }
+        else if (wave == ((t + TPB + 4) & (NW - 1))) issue_thr(more ? bsrc + u * B_CT * 4 : cb0, ng + u);
         if (t < Ti) sym_offer(acc, t, sym_thr_stage(sg + u));
       }
       if (u < TPB - 1) {
@@ -1152,12 +1190,21 @@ __global__ void sym_thr_kernel(const int32_t* seed, float* thr, int64_t n, int64
 }
 
 // files the waves' logs into the rows' lists: one workgroup per log.  An entry that finds its row's list full flags the row.
+// An entry was logged against the threshold its row had at the time; by now seed[] holds every row's FINAL proven threshold (all scan
+// launches have finished), and select's pruning threshold is never below it (DESIGN.md §4.1 "Pruned filing"): an entry that fails
+// select's own test — enc(key) + slot_ulp >= threshold — against seed[] would be dropped there, so it is not filed (seed: nullptr =
+// file everything, MMF_SYMMETRIC_PRUNE=0).
 __global__ __launch_bounds__(256) void sym_scatter_kernel(const uint32_t* log, const uint32_t* log_cnt, int log_cap, uint32_t* sym_cnt,
-                                                          uint32_t* sym_ids, float* sym_keys, int cap, int32_t* lost) {
+                                                          uint32_t* sym_ids, float* sym_keys, int cap, int32_t* lost,
+                                                          const int32_t* seed, int slot_ulp) {
   const uint32_t c = log_cnt[blockIdx.x];
   const u32x4* lg = reinterpret_cast<const u32x4*>(log) + (size_t)blockIdx.x * log_cap;
   for (uint32_t e = threadIdx.x; e < c; e += 256) {
     const u32x4 v = lg[e];
+    if (seed) {
+      const int32_t sd = seed[v[0]], b = (int32_t)v[2];
+      if (sd > kSeedNone && (b >= 0 ? b : (b ^ 0x7fffffff)) + slot_ulp < sd) continue;   // (no proven threshold: keep)
+    }
     const uint32_t slot = atomicAdd(sym_cnt + v[0], 1u);
     if (slot < (uint32_t)cap) {
       sym_ids[(size_t)v[0] * cap + slot] = v[1];
@@ -1180,9 +1227,14 @@ size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G) {
 // upload them to sb.sched — they depend on (row blocks, G, forward) alone, so a caller whose sb.sched still holds them from
 // an earlier call on this stream passes false.  *grid_out: the sum of the two grids.
 int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const float* rn, const float* un, const uint32_t* maxima,
-                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, bool live, bool forward, bool tables,
+                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, bool live, bool forward, bool prune, bool tables,
                         const CandLists& L, void* scratch, const SymBuffers& sb, const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
   const int64_t nb = (n + 255) / 256, n_pad = nb * 256, grid = sym_schedule_grid(nb, G);
+  // the SYM kernels neither fetch nor add the per-candidate bias: only metrics whose bias is zero for every real row may come here
+  if (metric != MMF_DOT && metric != MMF_COSINE) {
+    set_error("scan_b16_sym: metric %d has a per-candidate bias, which the symmetric kernels do not apply", metric);
+    return MMF_E_INTERNAL;
+  }
   if (L.lists != 4 || L.cap != B_CAP || !L.keys || !L.margin || !L.sym_cnt || !pn.seed) { set_error("scan_b16_sym: lists missing"); return MMF_E_INTERNAL; }
   if (n_pad * 1024 >= (int64_t(1) << 32)) { set_error("scan_b16_sym: operand image beyond the 32-bit tile offsets"); return MMF_E_INTERNAL; }
   if (tables) {
@@ -1222,7 +1274,7 @@ int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const 
   if (f16) MMF_TRY(go(scan_b16x_kernel<32, true, false, 8, 2, B_CAP, false, false, 2>, lds_b));
   else MMF_TRY(go(scan_b16x_kernel<32, false, false, 8, 2, B_CAP, false, false, 2>, lds_b));
   hipLaunchKernelGGL(sym_scatter_kernel, dim3((unsigned)(grid * 8)), dim3(256), 0, s, sb.log, sb.log_cnt, kSymLogPerWave, L.sym_cnt,
-                     L.sym_ids, L.sym_keys, L.sym_cap, pn.seed + pn.seed_stride);
+                     L.sym_ids, L.sym_keys, L.sym_cap, pn.seed + pn.seed_stride, prune ? pn.seed : nullptr, L.slot_ulp);
   MMF_LAUNCH_CHECK();
   if (grid_out) *grid_out = (int)(2 * grid);
   return MMF_OK;
