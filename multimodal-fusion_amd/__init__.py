@@ -5,6 +5,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
 
     mmf.ops.simtopk(...)                          fused similarity + top-k on gfx950
     mmf.ops.simtopk_segmented(..., ptr=/batch=)   the same per segment of a ragged batch (one graph per slide)
+    mmf.ragged.*                                  host-side offsets, plans and size checks of a ragged batch, shared by every module below
     mmf.weighted_hypergraph.*                     the median-threshold weighted hypergraph of every graph of a batch
     mmf.knn_kmeans_hypergraph.*                   the k-NN + KMeans hypergraph of every slide of a cohort (ordered edges, one host read)
     mmf.wsi_tma_similarity.*                      WSI x TMA similarity + statistics, grouping and the median edge filter of every slide of a cohort

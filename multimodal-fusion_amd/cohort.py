@@ -8,9 +8,10 @@ from typing import Dict, Optional
 
 import torch
 
+from . import ragged
 from .knn_kmeans_hypergraph import build_hypergraph_knn_kmeans_segmented
-from .super_patches import _check_clusters, aggregate_wsi_super_patches_segmented
-from .wsi_tma_similarity import _slide_ptr, compute_wsi_tma_similarity_segmented, group_by_similarity_segmented
+from .super_patches import aggregate_wsi_super_patches_segmented
+from .wsi_tma_similarity import compute_wsi_tma_similarity_segmented, group_by_similarity_segmented
 
 
 def build_cohort_hypergraphs(wsi_features: torch.Tensor, wsi_positions: torch.Tensor, tma_features: torch.Tensor, *, wsi_ptr=None,
@@ -38,26 +39,19 @@ def build_cohort_hypergraphs(wsi_features: torch.Tensor, wsi_positions: torch.Te
         raise ValueError(f"{what}: slide 0: wsi_features, wsi_positions and tma_features must be 2-D")
     if wsi_features.shape[1] != tma_features.shape[1]:
         raise ValueError(f"{what}: slide 0: wsi_features have D={wsi_features.shape[1]}, tma_features D={tma_features.shape[1]}")
-    wp = _slide_ptr(wsi_ptr, wsi_batch, wsi_features.shape[0], "wsi_", what)
-    tp = _slide_ptr(tma_ptr, tma_batch, tma_features.shape[0], "tma_", what, min_rows=0)
+    wp, tp = ragged.two_sided(wsi_features.shape[0], tma_features.shape[0], wsi_ptr, wsi_batch, tma_ptr, tma_batch, xs="wsi_",
+                              ys="tma_", what=what, unit="slide", min_rows=(1, 0))
     S = wp.numel() - 1
-    if tp.numel() - 1 != S:
-        raise ValueError(f"{what}: slide {min(S, tp.numel() - 1)}: wsi describes {S} slides, tma {tp.numel() - 1}")
     empty = torch.nonzero(tp[1:] == tp[:-1]).reshape(-1)
     if empty.numel():
         raise ValueError(f"{what}: slide {int(empty[0])} has no TMA rows (the per-file pipeline skips such a file)")
     C, G = int(num_wsi_super_patches), int(num_groups)
-    # what the later steps would object to, before the first step touches the device
-    _check_clusters((wp[1:] - wp[:-1]).tolist(), C, what)
-    if not (1 <= G <= C):
-        raise ValueError(f"{what}: slide 0: n_samples={C} should be >= n_clusters={G}.")
+    # what the four steps' KMeans and k-NN calls would object to, before the first step touches the device (the first step's
+    # own limits on C are its to report: it checks them on the host too)
+    ragged.check_kmeans_sizes((wp[1:] - wp[:-1]).tolist(), C, what, "slide")
+    ragged.check_kmeans_sizes([C], G, what, "slide")
     k, H = int(hypergraph_k), int(num_hyperedges)
-    for s, n_s in enumerate((C + (tp[1:] - tp[:-1])).tolist()):          # the mirror's two failures per slide: kneighbors, then KMeans
-        if k + 1 > n_s:
-            raise ValueError(f"{what}: slide {s}: Expected n_neighbors <= n_samples_fit, but n_neighbors = {k + 1}, "
-                             f"n_samples_fit = {n_s}, n_samples = {n_s}")
-        if not (1 <= H <= n_s):
-            raise ValueError(f"{what}: slide {s}: n_samples={n_s} should be >= n_clusters={H}.")
+    ragged.check_knn_sizes((C + (tp[1:] - tp[:-1])).tolist(), k, what, "slide", n_clusters=H)
     sf, sp, agg_stats, K_flat, k_ptr = aggregate_wsi_super_patches_segmented(
         wsi_features, wsi_positions, C, lambda_h, lambda_g, device, ptr=wp, keep_similarity=keep_similarity,
         budget_bytes=budget_bytes)

@@ -24,7 +24,7 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, ragged
 
 
 @functools.lru_cache(maxsize=4)
@@ -70,13 +70,9 @@ def kmeans_fit_predict_segmented(X: torch.Tensor, n_clusters: int, *, ptr=None, 
     0 .. k-1 within each segment, centres f32 [n_seg, k, D], inertia f64 numpy [n_seg]), bit for bit the per-segment calls.
     Bad segments raise ValueError on the host, before the device is touched."""
     X = ops._feat(X, "kmeans_fit_predict_segmented X")
-    p = ops._segment_ptr(ptr, batch, X.shape[0], "", "kmeans_fit_predict_segmented")
+    p = ragged.offsets(ptr, batch, X.shape[0], what="kmeans_fit_predict_segmented")
     sizes = (p[1:] - p[:-1]).tolist()
-    if not sizes:
-        raise ValueError("kmeans_fit_predict_segmented: no segments")
-    for s, n_s in enumerate(sizes):
-        if not (1 <= n_clusters <= n_s):
-            raise ValueError(f"kmeans_fit_predict_segmented: segment {s}: n_samples={n_s} should be >= n_clusters={n_clusters}.")
+    ragged.check_kmeans_sizes(sizes, n_clusters, "kmeans_fit_predict_segmented")
     if not X.is_cuda:
         raise RuntimeError("kmeans_fit_predict_segmented: X must be on a ROCm device (no CPU path)")
     first, u = segment_streams(int(seed), int(n_init), int(n_clusters), sizes)
@@ -85,6 +81,19 @@ def kmeans_fit_predict_segmented(X: torch.Tensor, n_clusters: int, *, ptr=None, 
     if return_info:
         return labels, centres, inertia, info
     return labels, centres, inertia
+
+
+def segmented_labels(X: torch.Tensor, p, n_clusters: int):
+    """The labels every cohort step clusters with, from the mirror's KMeans backend: (int64 labels [N] on X's device, local to each
+    segment of the host offsets p (tensor or list); ambiguous_draws, ambiguous_trials per segment, or None twice with the 'sklearn' backend).
+    'device': ONE kmeans_fit_predict_segmented call; 'sklearn': the reference's own call, segment by segment, on the host."""
+    from .build_hypergraph import preprocess_hypergraph        # the mirror and this module use each other: both import lazily
+    if preprocess_hypergraph.KMEANS_BACKEND == "device":
+        labels, _, _, info = kmeans_fit_predict_segmented(X, n_clusters, ptr=p, n_init=10, seed=42, return_info=True)
+        return labels, [int(i["ambiguous_draws"]) for i in info], [int(i["ambiguous_trials"]) for i in info]
+    bounds = torch.as_tensor(p).tolist()
+    parts = [preprocess_hypergraph._kmeans_labels(X[a:b], n_clusters) for a, b in zip(bounds[:-1], bounds[1:])]
+    return torch.cat(parts), None, None
 
 
 def segment_streams(seed: int, n_init: int, n_clusters: int, sizes) -> Tuple[np.ndarray, np.ndarray]:

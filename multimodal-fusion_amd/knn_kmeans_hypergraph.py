@@ -14,32 +14,10 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import ops, ragged
+from .kmeans import segmented_labels
 from .build_hypergraph import preprocess_hypergraph
 from .build_hypergraph._common import compute_device, result_device_like_preprocess, to_gpu
-
-
-def _check_sizes(sizes, k: int, num_hyperedges: int, what: str) -> None:
-    """The two per-slide failures of the plain mirror, for the first segment that has one: sklearn's kneighbors (:382), then
-    KMeans (:391)."""
-    for s, n_s in enumerate(sizes):
-        if k + 1 > n_s:
-            raise ValueError(f"{what}: segment {s}: Expected n_neighbors <= n_samples_fit, but n_neighbors = {k + 1}, "
-                             f"n_samples_fit = {n_s}, n_samples = {n_s}")
-        if not (1 <= num_hyperedges <= n_s):
-            raise ValueError(f"{what}: segment {s}: n_samples={n_s} should be >= n_clusters={num_hyperedges}.")
-
-
-def _labels(X: torch.Tensor, p: torch.Tensor, num_hyperedges: int):
-    """(labels int64 [N] local to each segment, ambiguous_draws, ambiguous_trials per segment or None) with the mirror's backend."""
-    if preprocess_hypergraph.KMEANS_BACKEND == "device":
-        from .kmeans import kmeans_fit_predict_segmented
-        labels, _, _, info = kmeans_fit_predict_segmented(X, num_hyperedges, ptr=p, n_init=10, seed=42, return_info=True)
-        return labels, [int(i["ambiguous_draws"]) for i in info], [int(i["ambiguous_trials"]) for i in info]
-    # 'sklearn': the reference's own call, slide by slide, on the host
-    bounds = p.tolist()
-    parts = [preprocess_hypergraph._kmeans_labels(X[a:b], num_hyperedges) for a, b in zip(bounds[:-1], bounds[1:])]
-    return torch.cat(parts), None, None
 
 
 def knn_kmeans_edges_segmented(X: torch.Tensor, k: int = 5, num_hyperedges: int = 10, *, ptr=None, batch=None,
@@ -50,15 +28,13 @@ def knn_kmeans_edges_segmented(X: torch.Tensor, k: int = 5, num_hyperedges: int 
     segment's ambiguous_draws / ambiguous_trials (None for 'sklearn')."""
     what = "knn_kmeans_edges_segmented"
     X = ops._feat(X, what + " X")
-    p = ops._segment_ptr(ptr, batch, X.shape[0], "", what)
-    if p.numel() < 2:
-        raise ValueError(f"{what}: no segments")
+    p = ragged.offsets(ptr, batch, X.shape[0], what=what)
     k, num_hyperedges = int(k), int(num_hyperedges)
-    _check_sizes((p[1:] - p[:-1]).tolist(), k, num_hyperedges, what)
+    ragged.check_knn_sizes((p[1:] - p[:-1]).tolist(), k, what, n_clusters=num_hyperedges)
     ops._need_gpu(X, what)
     X = X.detach().float().contiguous()
     nbr, _ = ops.simtopk_segmented(X, ptr=p, metric="neg_sq_l2", k=k, exclude_self=True)
-    labels, draws, trials = _labels(X, p, num_hyperedges)
+    labels, draws, trials = segmented_labels(X, p, num_hyperedges)
     edge_index, edge_ptr = ops.knn_clique_edges(nbr, labels, num_hyperedges, ptr=p)
     if edge_index.shape[1] == 0:
         edge_weights = torch.empty((0,), dtype=torch.float32, device=X.device)
@@ -75,12 +51,7 @@ def node_offsets(n_wsi: int, n_tma: int, *, wsi_ptr=None, wsi_batch=None, tma_pt
     """Host offsets (wsi_ptr, tma_ptr, node_ptr = wsi_ptr + tma_ptr) of the two-sided segment description: segment s has the
     nodes wsi[wsi_ptr[s]:wsi_ptr[s+1]] then tma[tma_ptr[s]:tma_ptr[s+1]], numbered from node_ptr[s].  Both sides must describe the same
     number of segments (a batch vector ends at its last id: trailing segments without rows need ptr)."""
-    wp = ops._segment_ptr(wsi_ptr, wsi_batch, n_wsi, "wsi_", what)
-    tp = ops._segment_ptr(tma_ptr, tma_batch, n_tma, "tma_", what)
-    if wp.numel() != tp.numel():
-        raise ValueError(f"{what}: wsi has {wp.numel() - 1} segments, tma has {tp.numel() - 1}")
-    if wp.numel() < 2:
-        raise ValueError(f"{what}: no segments")
+    wp, tp = ragged.two_sided(n_wsi, n_tma, wsi_ptr, wsi_batch, tma_ptr, tma_batch, xs="wsi_", ys="tma_", what=what)
     return wp, tp, wp + tp
 
 
@@ -105,7 +76,7 @@ def build_hypergraph_knn_kmeans_segmented(wsi_features: torch.Tensor, tma_featur
                                     what=what)
     k, num_hyperedges = int(k), int(num_hyperedges)
     sizes = (node_ptr[1:] - node_ptr[:-1]).tolist()
-    _check_sizes(sizes, k, num_hyperedges, what)
+    ragged.check_knn_sizes(sizes, k, what, n_clusters=num_hyperedges)
     out_dev = result_device_like_preprocess(wsi_features, device)
     dev = out_dev if out_dev.type == "cuda" else compute_device(wsi_features, tma_features)
     # the mirror's torch.cat per slide, as two scatters: wsi row r of slide s -> r + tma_ptr[s], tma row r -> r + wsi_ptr[s+1]

@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, ragged
 
 _DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 
@@ -37,12 +37,35 @@ def _p(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+_hp = _p      # a host tensor gives its pointer the same way; the name marks the arguments a C entry reads on the host
+
+
 def _metric(m) -> int:
     if isinstance(m, str):
         if m not in _lib.METRICS:
             raise ValueError(f"unknown metric {m!r}")
         return _lib.METRICS[m]
     return int(m)
+
+
+def _call(name: str, dev: torch.device, *args, what: Optional[str] = None) -> None:
+    """The C entry `name` on args + (device index, the current stream of dev); a return code other than MMF_OK raises under the
+    name `what` (default: the entry's)."""
+    _lib.check(getattr(_lib.lib(), name)(*args, dev.index or 0, _stream(dev)), what or name)
+
+
+def _simtopk_entry(name: str, X: torch.Tensor, Y: Optional[torch.Tensor], metric, lam: float, k: int, exclude_self, middle: tuple,
+                   opts, return_stats: bool, what: Optional[str] = None):
+    """What the four simtopk entries share: the leading arguments, the [n, k] outputs, options and statistics after the entry's
+    own `middle` arguments, and the (idx, val[, stats dict]) result."""
+    n, d = X.shape
+    m = n if Y is None else Y.shape[0]
+    idx = torch.empty((n, k), dtype=torch.int64, device=X.device)
+    val = torch.empty((n, k), dtype=torch.float32, device=X.device)
+    stats = _lib.SimtopkStats()
+    _call(name, X.device, _p(X), n, _p(Y), m, d, _DT[X.dtype], _metric(metric), float(lam), int(k), int(bool(exclude_self)), *middle,
+          _p(idx), _p(val), ctypes.byref(opts), ctypes.byref(stats), what=what)
+    return (idx, val, stats.as_dict()) if return_stats else (idx, val)
 
 
 def simtopk(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, metric="cosine", lam: float = 1.0, k: int = 5,
@@ -59,43 +82,9 @@ def simtopk(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, metric="cosine
             raise ValueError("simtopk: X and Y must share device, dtype and feature dim")
     if exclude_self is None:
         exclude_self = Y is None
-    n, d = X.shape
-    m = n if Y is None else Y.shape[0]
-    idx = torch.empty((n, k), dtype=torch.int64, device=X.device)
-    val = torch.empty((n, k), dtype=torch.float32, device=X.device)
     opts = _lib.SimtopkOpts(_lib.PRECISIONS[precision], int(profile), int(col_splits), _lib.QUERY_ORDERS[query_order], None)
-    stats = _lib.SimtopkStats()
-    rc = _lib.lib().mmf_simtopk_ex(_p(X), n, _p(Y), m, d, _DT[X.dtype], _metric(metric), float(lam), int(k),
-                                   int(bool(exclude_self)), int(row_offset), int(col_offset), _p(idx), _p(val),
-                                   ctypes.byref(opts), ctypes.byref(stats), X.device.index or 0, _stream(X.device))
-    _lib.check(rc, "mmf_simtopk")
-    if return_stats:
-        return idx, val, stats.as_dict()
-    return idx, val
-
-
-def _segment_ptr(ptr, batch, rows: int, side: str, what: str = "simtopk_segmented") -> torch.Tensor:
-    """Host int64 offsets [S + 1] from exactly one of ptr (offsets) / batch (sorted segment id per row, PyG convention).
-    `what` names the caller in the messages."""
-    if (ptr is None) == (batch is None):
-        raise ValueError(f"{what}: give exactly one of {side}ptr / {side}batch")
-    if ptr is not None:
-        p = torch.as_tensor(ptr).detach().to("cpu", torch.int64).reshape(-1)
-        if p.numel() < 1 or int(p[0]) != 0 or int(p[-1]) != rows:
-            raise ValueError(f"{what}: {side}ptr must start at 0 and end at {rows}")
-        if p.numel() > 1 and bool((p[1:] < p[:-1]).any()):
-            raise ValueError(f"{what}: {side}ptr must be non-decreasing")
-        return p.contiguous()
-    b = torch.as_tensor(batch)
-    if b.dim() != 1 or b.numel() != rows:
-        raise ValueError(f"{what}: {side}batch must hold one segment id per row ({rows})")
-    b = b.detach().to("cpu", torch.int64)           # the one device -> host copy of a batch vector
-    if rows == 0:
-        return torch.zeros(1, dtype=torch.int64)
-    if bool((b < 0).any()) or bool((b[1:] < b[:-1]).any()):
-        raise ValueError(f"{what}: {side}batch must be sorted and non-negative")
-    counts = torch.bincount(b)
-    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(counts, 0)])
+    return _simtopk_entry("mmf_simtopk_ex", X, Y, metric, lam, k, exclude_self, (int(row_offset), int(col_offset)), opts, return_stats,
+                          what="mmf_simtopk")
 
 
 def simtopk_segmented(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, ptr=None, batch=None, y_ptr=None, y_batch=None,
@@ -118,39 +107,25 @@ def simtopk_segmented(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, ptr=
         raise ValueError(f"simtopk_segmented: k must be >= 1 (got {k})")
     if precision not in _lib.PRECISIONS:
         raise ValueError(f"simtopk_segmented: unknown precision {precision!r}")
-    n, d = X.shape
-    xp = _segment_ptr(ptr, batch, n, "")
     if Y is None:
         if y_ptr is not None or y_batch is not None:
             raise ValueError("simtopk_segmented: y_ptr / y_batch need Y")
-        m, yp = n, xp
+        xp = yp = ragged.offsets(ptr, batch, X.shape[0], what="simtopk_segmented", allow_no_segments=True)
     else:
-        m = Y.shape[0]
-        yp = _segment_ptr(y_ptr, y_batch, m, "y_")
-        if xp.numel() != yp.numel():
-            raise ValueError(f"simtopk_segmented: X has {xp.numel() - 1} segments, Y has {yp.numel() - 1}")
+        xp, yp = ragged.two_sided(X.shape[0], Y.shape[0], ptr, batch, y_ptr, y_batch, xs="", ys="y_", what="simtopk_segmented",
+                                  allow_no_segments=True)
     if exclude_self is None:
         exclude_self = Y is None
     _need_gpu(X, "simtopk_segmented")
-    S = xp.numel() - 1
-    idx = torch.empty((n, k), dtype=torch.int64, device=X.device)
-    val = torch.empty((n, k), dtype=torch.float32, device=X.device)
     opts = _lib.SimtopkOpts(_lib.PRECISIONS[precision], int(profile), 0, _lib.QUERY_ORDERS["off"], None)
-    stats = _lib.SimtopkStats()
-    rc = _lib.lib().mmf_simtopk_segmented(_p(X), n, _p(Y), m, d, _DT[X.dtype], _metric(metric), float(lam), int(k),
-                                          int(bool(exclude_self)), ctypes.c_void_p(xp.data_ptr()), ctypes.c_void_p(yp.data_ptr()),
-                                          S, _p(idx), _p(val), ctypes.byref(opts), ctypes.byref(stats),
-                                          X.device.index or 0, _stream(X.device))
-    _lib.check(rc, "mmf_simtopk_segmented")
-    if return_stats:
-        return idx, val, stats.as_dict()
-    return idx, val
+    return _simtopk_entry("mmf_simtopk_segmented", X, Y, metric, lam, k, exclude_self, (_hp(xp), _hp(yp), xp.numel() - 1), opts,
+                          return_stats)
 
 
 def last_query_order(n: int) -> torch.Tensor:
     """Diagnostics: scan position -> row of the most recent simtopk call that reordered its n queries (mmf_debug_query_order)."""
     out = torch.empty((n,), dtype=torch.int32)
-    _lib.check(_lib.lib().mmf_debug_query_order(ctypes.c_void_p(out.data_ptr()), ctypes.c_int64(n)), "mmf_debug_query_order")
+    _lib.check(_lib.lib().mmf_debug_query_order(_hp(out), ctypes.c_int64(n)), "mmf_debug_query_order")
     return out
 
 
@@ -164,15 +139,17 @@ def sim_dense(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, metric="rbf"
     n, d = X.shape
     m = n if Y is None else Y.shape[0]
     out = torch.empty((n, m), dtype=torch.float32, device=X.device)
-    rc = _lib.lib().mmf_sim_dense(_p(X), n, _p(Y), m, d, _DT[X.dtype], _metric(metric), float(lam), _p(out),
-                                  X.device.index or 0, _stream(X.device))
-    _lib.check(rc, "mmf_sim_dense")
+    _call("mmf_sim_dense", X.device, _p(X), n, _p(Y), m, d, _DT[X.dtype], _metric(metric), float(lam), _p(out))
     return out
 
 
-def _stats_dict(out: torch.Tensor) -> dict:
+STAT_KEYS = ("mean", "std", "min", "max", "median")
+
+
+def _stats_dict(out: torch.Tensor):
+    """The statistics dict of a [5] device array, one dict per row of an [S, 5] one: Python floats out of ONE device -> host copy."""
     h = out.to(torch.float32).cpu().tolist()        # the reference's values are `.item()`s of f32 tensors
-    return {"mean": h[0], "std": h[1], "min": h[2], "max": h[3], "median": h[4]}
+    return [dict(zip(STAT_KEYS, row)) for row in h] if out.dim() == 2 else dict(zip(STAT_KEYS, h))
 
 
 def sim_dense_stats(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, metric="rbf_direct", lam: float = 1.0,
@@ -191,23 +168,28 @@ def sim_dense_stats(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, metric
         raise ValueError("sim_dense_stats: empty matrix")
     out = torch.empty((n, m), dtype=torch.float32, device=X.device) if store else None
     st = torch.empty((5,), dtype=torch.float64, device=X.device)
-    rc = _lib.lib().mmf_sim_dense_stats(_p(X), n, _p(Y), m, d, _DT[X.dtype], _metric(metric), float(lam), _p(out), _p(st),
-                                        int(panel_rows), X.device.index or 0, _stream(X.device))
-    _lib.check(rc, "mmf_sim_dense_stats")
+    _call("mmf_sim_dense_stats", X.device, _p(X), n, _p(Y), m, d, _DT[X.dtype], _metric(metric), float(lam), _p(out), _p(st),
+          int(panel_rows))
     return out, _stats_dict(st)
 
 
-def sim_dense_combined(F: torch.Tensor, P: torch.Tensor, lambda_h: float = 1.0, lambda_g: float = 1.0) -> torch.Tensor:
-    F = _feat(F, "sim_dense_combined features").float()
-    P = _feat(P, "sim_dense_combined positions").float()
-    _need_gpu(F, "sim_dense_combined")
+def _feat_pair(F: torch.Tensor, P: torch.Tensor, what: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Features and positions of a `combined` function as contiguous f32 [N, D] / [N, dp]."""
+    return _feat(F, what + " features").float(), _feat(P, what + " positions").float()
+
+
+def _need_gpu_pair(F: torch.Tensor, P: torch.Tensor, what: str) -> None:
+    _need_gpu(F, what)
     if P.device != F.device or P.shape[0] != F.shape[0]:
-        raise ValueError("sim_dense_combined: features and positions must share device and N")
+        raise ValueError(f"{what}: features and positions must share device and N")
+
+
+def sim_dense_combined(F: torch.Tensor, P: torch.Tensor, lambda_h: float = 1.0, lambda_g: float = 1.0) -> torch.Tensor:
+    F, P = _feat_pair(F, P, "sim_dense_combined")
+    _need_gpu_pair(F, P, "sim_dense_combined")
     n, d = F.shape
     out = torch.empty((n, n), dtype=torch.float32, device=F.device)
-    rc = _lib.lib().mmf_sim_dense_combined(_p(F), _p(P), n, d, P.shape[1], float(lambda_h), float(lambda_g), _p(out),
-                                           F.device.index or 0, _stream(F.device))
-    _lib.check(rc, "mmf_sim_dense_combined")
+    _call("mmf_sim_dense_combined", F.device, _p(F), _p(P), n, d, P.shape[1], float(lambda_h), float(lambda_g), _p(out))
     return out
 
 
@@ -221,9 +203,7 @@ def edge_cosine(X: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
     if E and (int(ei.min()) < 0 or int(ei.max()) >= X.shape[0]):
         raise ValueError("edge_cosine: edge_index out of range")
     out = torch.empty((E,), dtype=torch.float32, device=X.device)
-    rc = _lib.lib().mmf_edge_cosine(_p(X), X.shape[0], X.shape[1], _DT[X.dtype], _p(ei), E, _p(out),
-                                    X.device.index or 0, _stream(X.device))
-    _lib.check(rc, "mmf_edge_cosine")
+    _call("mmf_edge_cosine", X.device, _p(X), X.shape[0], X.shape[1], _DT[X.dtype], _p(ei), E, _p(out))
     return out
 
 
@@ -236,9 +216,7 @@ def topk_merge(ia: torch.Tensor, va: torch.Tensor, ib: torch.Tensor, vb: torch.T
     n, k = ia.shape
     io = torch.empty_like(ia)
     vo = torch.empty_like(va)
-    rc = _lib.lib().mmf_topk_merge(_p(ia), _p(va), _p(ib), _p(vb), n, k, _p(io), _p(vo), ia.device.index or 0,
-                                   _stream(ia.device))
-    _lib.check(rc, "mmf_topk_merge")
+    _call("mmf_topk_merge", ia.device, _p(ia), _p(va), _p(ib), _p(vb), n, k, _p(io), _p(vo))
     return io, vo
 
 
@@ -250,8 +228,7 @@ def offdiag_lower_median(K: torch.Tensor) -> torch.Tensor:
     if K.dim() != 2 or K.shape[0] != K.shape[1]:
         raise ValueError("offdiag_lower_median: K must be square")
     out = torch.empty((), dtype=torch.float32, device=K.device)
-    rc = _lib.lib().mmf_offdiag_lower_median(_p(K), K.shape[0], _p(out), K.device.index or 0, _stream(K.device))
-    _lib.check(rc, "mmf_offdiag_lower_median")
+    _call("mmf_offdiag_lower_median", K.device, _p(K), K.shape[0], _p(out))
     return out
 
 
@@ -263,8 +240,7 @@ def lower_median(v: torch.Tensor) -> torch.Tensor:
     if v.numel() < 1:
         raise ValueError("lower_median: empty input")
     out = torch.empty((), dtype=torch.float32, device=v.device)
-    rc = _lib.lib().mmf_lower_median(_p(v), v.numel(), _p(out), v.device.index or 0, _stream(v.device))
-    _lib.check(rc, "mmf_lower_median")
+    _call("mmf_lower_median", v.device, _p(v), v.numel(), _p(out))
     return out
 
 
@@ -276,8 +252,7 @@ def array_stats(v: torch.Tensor) -> dict:
     if v.numel() < 1:
         raise ValueError("array_stats: empty input")
     out = torch.empty((5,), dtype=torch.float64, device=v.device)
-    rc = _lib.lib().mmf_array_stats(_p(v), v.numel(), _p(out), v.device.index or 0, _stream(v.device))
-    _lib.check(rc, "mmf_array_stats")
+    _call("mmf_array_stats", v.device, _p(v), v.numel(), _p(out))
     return _stats_dict(out)
 
 
@@ -289,71 +264,47 @@ def threshold_edges(K: torch.Tensor, threshold: float) -> Tuple[torch.Tensor, to
         raise ValueError("threshold_edges: K must be square")
     n = K.shape[0]
     cnt = torch.zeros((), dtype=torch.int64, device=K.device)
-    L = _lib.lib()
-    dev, st = K.device.index or 0, _stream(K.device)
     # pass 1: count + row offsets; pass 2: fill from the offsets (K is read twice in all)
     row_off = torch.empty((n + 1,), dtype=torch.int64, device=K.device)
-    _lib.check(L.mmf_threshold_edges_count(_p(K), n, float(threshold), _p(row_off), _p(cnt), dev, st), "mmf_threshold_edges_count")
+    _call("mmf_threshold_edges_count", K.device, _p(K), n, float(threshold), _p(row_off), _p(cnt))
     E = int(cnt.item())
     ei = torch.empty((2, E), dtype=torch.int64, device=K.device)
     ew = torch.empty((E,), dtype=torch.float32, device=K.device)
     if E:
-        _lib.check(L.mmf_threshold_edges_fill(_p(K), n, float(threshold), _p(row_off), _p(ei), _p(ew), E, dev, st),
-                   "mmf_threshold_edges_fill")
+        _call("mmf_threshold_edges_fill", K.device, _p(K), n, float(threshold), _p(row_off), _p(ei), _p(ew), E)
     return ei, ew
 
 
 def combined_offdiag_median(F: torch.Tensor, P: torch.Tensor, lambda_h: float = 1.0, lambda_g: float = 1.0,
                             panel_rows: int = 0) -> torch.Tensor:
     """Lower median of the off-diagonal entries of K = K_h * K_g without materialising K (recomputed in row panels)."""
-    F = _feat(F, "combined_offdiag_median features").float()
-    P = _feat(P, "combined_offdiag_median positions").float()
-    _need_gpu(F, "combined_offdiag_median")
-    if P.device != F.device or P.shape[0] != F.shape[0]:
-        raise ValueError("combined_offdiag_median: features and positions must share device and N")
+    F, P = _feat_pair(F, P, "combined_offdiag_median")
+    _need_gpu_pair(F, P, "combined_offdiag_median")
     out = torch.empty((), dtype=torch.float32, device=F.device)
-    rc = _lib.lib().mmf_combined_offdiag_median(_p(F), _p(P), F.shape[0], F.shape[1], P.shape[1], float(lambda_h),
-                                                float(lambda_g), int(panel_rows), _p(out), F.device.index or 0,
-                                                _stream(F.device))
-    _lib.check(rc, "mmf_combined_offdiag_median")
+    _call("mmf_combined_offdiag_median", F.device, _p(F), _p(P), F.shape[0], F.shape[1], P.shape[1], float(lambda_h), float(lambda_g),
+          int(panel_rows), _p(out))
     return out
 
 
 def combined_threshold_edges(F: torch.Tensor, P: torch.Tensor, threshold: float, lambda_h: float = 1.0,
                              lambda_g: float = 1.0, panel_rows: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """threshold_edges of K = K_h * K_g without materialising K: one sweep to count, one to fill."""
-    F = _feat(F, "combined_threshold_edges features").float()
-    P = _feat(P, "combined_threshold_edges positions").float()
-    _need_gpu(F, "combined_threshold_edges")
-    if P.device != F.device or P.shape[0] != F.shape[0]:
-        raise ValueError("combined_threshold_edges: features and positions must share device and N")
+    F, P = _feat_pair(F, P, "combined_threshold_edges")
+    _need_gpu_pair(F, P, "combined_threshold_edges")
     n, d = F.shape
     cnt = torch.zeros((), dtype=torch.int64, device=F.device)
-    L = _lib.lib()
     args = (_p(F), _p(P), n, d, P.shape[1], float(lambda_h), float(lambda_g), float(threshold), int(panel_rows))
-    dev, st = F.device.index or 0, _stream(F.device)
-    _lib.check(L.mmf_combined_threshold_edges(*args, None, None, 0, _p(cnt), dev, st), "mmf_combined_threshold_edges")
+    _call("mmf_combined_threshold_edges", F.device, *args, None, None, 0, _p(cnt))
     E = int(cnt.item())
     ei = torch.empty((2, E), dtype=torch.int64, device=F.device)
     ew = torch.empty((E,), dtype=torch.float32, device=F.device)
     if E:
-        _lib.check(L.mmf_combined_threshold_edges(*args, _p(ei), _p(ew), E, _p(cnt), dev, st), "mmf_combined_threshold_edges")
+        _call("mmf_combined_threshold_edges", F.device, *args, _p(ei), _p(ew), E, _p(cnt))
     return ei, ew
 
 
-def _block_ptr(ptr, batch, what: str) -> torch.Tensor:
-    """Host offsets of the blocks K_s of a flat segmented K: like _segment_ptr, with the row count taken from ptr / batch."""
-    if ptr is not None and batch is None:
-        p = torch.as_tensor(ptr).reshape(-1)
-        rows = int(p[-1]) if p.numel() else 0
-    else:
-        rows = torch.as_tensor(batch).numel() if batch is not None else 0
-    return _segment_ptr(ptr, batch, rows, "", what)
-
-
 def _check_blocks(K: torch.Tensor, p: torch.Tensor, what: str) -> torch.Tensor:
-    sizes = p[1:] - p[:-1]
-    total = int((sizes * sizes).sum())
+    total = int(ragged.block_offsets(p)[-1])
     if K.numel() != total:
         raise ValueError(f"{what}: K holds {K.numel()} values, the blocks of the segments {total}")
     return K.contiguous().float().reshape(-1)
@@ -364,32 +315,25 @@ def sim_dense_combined_segmented(F: torch.Tensor, P: torch.Tensor, lambda_h: flo
     """sim_dense_combined of every segment F[ptr[s]:ptr[s+1]] in one launch (mmf_sim_dense_combined_segmented).  Returns
     (K flat f32 [sum n_s^2] on F's device, kptr host int64 [S + 1]): block s is K[kptr[s]:kptr[s+1]].view(n_s, n_s), bit for
     bit sim_dense_combined(F_s, P_s).  Segments: exactly one of ptr ([S + 1] offsets) / batch ([n] sorted ids, PyG)."""
-    F = _feat(F, "sim_dense_combined_segmented features").float()
-    P = _feat(P, "sim_dense_combined_segmented positions").float()
+    F, P = _feat_pair(F, P, "sim_dense_combined_segmented")
     n, d = F.shape
-    p = _segment_ptr(ptr, batch, n, "", "sim_dense_combined_segmented")
-    sizes = p[1:] - p[:-1]
-    kptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(sizes * sizes, 0)])
-    _need_gpu(F, "sim_dense_combined_segmented")
-    if P.device != F.device or P.shape[0] != n:
-        raise ValueError("sim_dense_combined_segmented: features and positions must share device and N")
+    p = ragged.offsets(ptr, batch, n, what="sim_dense_combined_segmented", allow_no_segments=True)
+    kptr = ragged.block_offsets(p)
+    _need_gpu_pair(F, P, "sim_dense_combined_segmented")
     out = torch.empty((int(kptr[-1]),), dtype=torch.float32, device=F.device)
-    rc = _lib.lib().mmf_sim_dense_combined_segmented(_p(F), _p(P), n, d, P.shape[1], ctypes.c_void_p(p.data_ptr()), p.numel() - 1,
-                                                     float(lambda_h), float(lambda_g), _p(out), F.device.index or 0, _stream(F.device))
-    _lib.check(rc, "mmf_sim_dense_combined_segmented")
+    _call("mmf_sim_dense_combined_segmented", F.device, _p(F), _p(P), n, d, P.shape[1], _hp(p), p.numel() - 1, float(lambda_h),
+          float(lambda_g), _p(out))
     return out, kptr
 
 
 def offdiag_lower_median_segmented(K: torch.Tensor, *, ptr=None, batch=None) -> torch.Tensor:
     """offdiag_lower_median of every block of a flat segmented K (the layout of sim_dense_combined_segmented): device f32 [S],
     without a host synchronisation (mmf_offdiag_lower_median_segmented).  Every segment needs at least two rows."""
-    p = _block_ptr(ptr, batch, "offdiag_lower_median_segmented")
+    p = ragged.offsets(ptr, batch, None, what="offdiag_lower_median_segmented", allow_no_segments=True)
     _need_gpu(K, "offdiag_lower_median_segmented")
     K = _check_blocks(K, p, "offdiag_lower_median_segmented")
     out = torch.empty((p.numel() - 1,), dtype=torch.float32, device=K.device)
-    rc = _lib.lib().mmf_offdiag_lower_median_segmented(_p(K), ctypes.c_void_p(p.data_ptr()), p.numel() - 1, _p(out),
-                                                       K.device.index or 0, _stream(K.device))
-    _lib.check(rc, "mmf_offdiag_lower_median_segmented")
+    _call("mmf_offdiag_lower_median_segmented", K.device, _p(K), _hp(p), p.numel() - 1, _p(out))
     return out
 
 
@@ -397,7 +341,7 @@ def threshold_edges_segmented(K: torch.Tensor, thresholds, *, ptr=None, batch=No
     """threshold_edges of every block of a flat segmented K against its own threshold (thresholds: [S] floats).  Returns
     (edge_index [2, E] int64 GLOBAL row ids, weights [E] f32, edge_ptr [S + 1] int64): the edges of segment s are
     edge_ptr[s]:edge_ptr[s+1], those of threshold_edges(K_s, thresholds[s]) shifted by ptr[s].  One synchronisation (E)."""
-    p = _block_ptr(ptr, batch, "threshold_edges_segmented")
+    p = ragged.offsets(ptr, batch, None, what="threshold_edges_segmented", allow_no_segments=True)
     _need_gpu(K, "threshold_edges_segmented")
     K = _check_blocks(K, p, "threshold_edges_segmented")
     S, n = p.numel() - 1, int(p[-1])
@@ -405,19 +349,15 @@ def threshold_edges_segmented(K: torch.Tensor, thresholds, *, ptr=None, batch=No
     if thr.numel() != S:
         raise ValueError(f"threshold_edges_segmented: {thr.numel()} thresholds for {S} segments")
     cnt = torch.zeros((), dtype=torch.int64, device=K.device)
-    L = _lib.lib()
-    dev, st = K.device.index or 0, _stream(K.device)
-    pp = ctypes.c_void_p(p.data_ptr())
     row_off = torch.empty((n + 1,), dtype=torch.int64, device=K.device)
-    _lib.check(L.mmf_threshold_edges_segmented_count(_p(K), pp, S, _p(thr), _p(row_off), _p(cnt), dev, st),
-               "mmf_threshold_edges_segmented_count")
+    args = (_p(K), _hp(p), S, _p(thr), _p(row_off))
+    _call("mmf_threshold_edges_segmented_count", K.device, *args, _p(cnt))
     edge_ptr = row_off[p.to(K.device)]
     E = int(cnt.item())
     ei = torch.empty((2, E), dtype=torch.int64, device=K.device)
     ew = torch.empty((E,), dtype=torch.float32, device=K.device)
     if E:
-        _lib.check(L.mmf_threshold_edges_segmented_fill(_p(K), pp, S, _p(thr), _p(row_off), _p(ei), _p(ew), E, dev, st),
-                   "mmf_threshold_edges_segmented_fill")
+        _call("mmf_threshold_edges_segmented_fill", K.device, *args, _p(ei), _p(ew), E)
     return ei, ew, edge_ptr
 
 
@@ -441,9 +381,7 @@ def row_scalars(X: torch.Tensor, metric, scal: torch.Tensor, max_sq_norm: Option
     """scal[i] = canonical n_i (clamped norm for cosine); max_sq_norm[0] is raised to max n_i."""
     X = _feat(X, "row_scalars X")
     _need_gpu(X, "row_scalars")
-    rc = _lib.lib().mmf_row_scalars(_p(X), X.shape[0], X.shape[1], _DT[X.dtype], _metric(metric), _p(scal),
-                                    _p(max_sq_norm), X.device.index or 0, _stream(X.device))
-    _lib.check(rc, "mmf_row_scalars")
+    _call("mmf_row_scalars", X.device, _p(X), X.shape[0], X.shape[1], _DT[X.dtype], _metric(metric), _p(scal), _p(max_sq_norm))
 
 
 def prep_rows(X: torch.Tensor, metric, operand: str, scal: torch.Tensor, max_sq_norm: Optional[torch.Tensor],
@@ -456,10 +394,12 @@ def prep_rows(X: torch.Tensor, metric, operand: str, scal: torch.Tensor, max_sq_
     for t in (Z, zn, rn, un, cb):
         if not t.is_contiguous():
             raise ValueError("prep_rows: output buffers must be contiguous")
-    rc = _lib.lib().mmf_prep_rows(_p(X), X.shape[0], X.shape[1], _DT[X.dtype], _metric(metric), _OPERAND[operand],
-                                  _p(scal), _p(max_sq_norm), _p(Z), n_pad, _p(zn), _p(rn), _p(un), _p(cb), _p(maxima),
-                                  X.device.index or 0, _stream(X.device))
-    _lib.check(rc, "mmf_prep_rows")
+    _call("mmf_prep_rows", X.device, _p(X), X.shape[0], X.shape[1], _DT[X.dtype], _metric(metric), _OPERAND[operand], _p(scal),
+          _p(max_sq_norm), _p(Z), n_pad, _p(zn), _p(rn), _p(un), _p(cb), _p(maxima))
+
+
+def _prepared_side(side: dict) -> "_lib.PreparedSide":
+    return _lib.PreparedSide(*(_p(side[key]) for key in ("Z", "scal", "zn", "rn", "un", "cb")))
 
 
 def simtopk_prepared(X: torch.Tensor, Y: torch.Tensor, q: dict, c: dict, m_pad: int, maxima: torch.Tensor, *,
@@ -470,25 +410,11 @@ def simtopk_prepared(X: torch.Tensor, Y: torch.Tensor, q: dict, c: dict, m_pad: 
     Z, scal, zn, rn, un, cb of the query / candidate side.  wait_event: recorded when the f32 rows of
     X / Y are complete; the stream waits for it only after the scan."""
     _need_gpu(X, "simtopk_prepared")
-    n, d = X.shape
-    m = Y.shape[0]
-    idx = torch.empty((n, k), dtype=torch.int64, device=X.device)
-    val = torch.empty((n, k), dtype=torch.float32, device=X.device)
-
-    def side(dd):
-        return _lib.PreparedSide(*(ctypes.c_void_p(dd[key].data_ptr()) for key in ("Z", "scal", "zn", "rn", "un", "cb")))
-    qs, cs = side(q), side(c)
+    qs, cs = _prepared_side(q), _prepared_side(c)
     ev = ctypes.c_void_p(wait_event.cuda_event) if wait_event is not None else None
     opts = _lib.SimtopkOpts(_lib.PRECISIONS["fast"], int(profile), int(col_splits), _lib.QUERY_ORDERS[query_order], ev)
-    stats = _lib.SimtopkStats()
-    rc = _lib.lib().mmf_simtopk_prepared(_p(X), n, _p(Y), m, d, _DT[X.dtype], _metric(metric), float(lam), int(k),
-                                         int(bool(exclude_self)), int(row_offset), int(col_offset), ctypes.byref(qs),
-                                         ctypes.byref(cs), int(m_pad), _p(maxima), _OPERAND[operand], _p(idx), _p(val),
-                                         ctypes.byref(opts), ctypes.byref(stats), X.device.index or 0, _stream(X.device))
-    _lib.check(rc, "mmf_simtopk_prepared")
-    if return_stats:
-        return idx, val, stats.as_dict()
-    return idx, val
+    middle = (int(row_offset), int(col_offset), ctypes.byref(qs), ctypes.byref(cs), int(m_pad), _p(maxima), _OPERAND[operand])
+    return _simtopk_entry("mmf_simtopk_prepared", X, Y, metric, lam, k, exclude_self, middle, opts, return_stats)
 
 
 def simtopk_panels(X: torch.Tensor, Y: torch.Tensor, q: dict, c_scal: torch.Tensor, panels: list, maxima: torch.Tensor, *,
@@ -499,28 +425,17 @@ def simtopk_panels(X: torch.Tensor, Y: torch.Tensor, q: dict, c_scal: torch.Tens
     m_pad, and optionally seg_len / seg_stride / id_base (panel column -> column of Y) and `event` (a
     torch.cuda.Event the scan of that panel waits for).  q: query-side dict as for simtopk_prepared."""
     _need_gpu(X, "simtopk_panels")
-    n, d = X.shape
-    m = Y.shape[0]
-    idx = torch.empty((n, k), dtype=torch.int64, device=X.device)
-    val = torch.empty((n, k), dtype=torch.float32, device=X.device)
-    qs = _lib.PreparedSide(*(ctypes.c_void_p(q[key].data_ptr()) for key in ("Z", "scal", "zn", "rn", "un", "cb")))
+    qs = _prepared_side(q)
     arr = (_lib.Panel * len(panels))()
     for i, pn in enumerate(panels):
         ev = pn.get("event")
-        arr[i] = _lib.Panel(ctypes.c_void_p(pn["Z"].data_ptr()), ctypes.c_void_p(pn["cb"].data_ptr()), int(pn["m"]),
+        arr[i] = _lib.Panel(_p(pn["Z"]), _p(pn["cb"]), int(pn["m"]),
                             int(pn["m_pad"]), int(pn.get("seg_len", 0)), int(pn.get("seg_stride", 0)),
                             int(pn.get("id_base", 0)), ctypes.c_void_p(ev.cuda_event) if ev is not None else None)
     ev = ctypes.c_void_p(wait_event.cuda_event) if wait_event is not None else None
     opts = _lib.SimtopkOpts(_lib.PRECISIONS["fast"], int(profile), int(col_splits), _lib.QUERY_ORDERS[query_order], ev)
-    stats = _lib.SimtopkStats()
-    rc = _lib.lib().mmf_simtopk_panels(_p(X), n, _p(Y), m, d, _DT[X.dtype], _metric(metric), float(lam), int(k),
-                                       int(bool(exclude_self)), int(row_offset), int(col_offset), ctypes.byref(qs),
-                                       _p(c_scal), arr, len(panels), _p(maxima), _OPERAND[operand], _p(idx), _p(val),
-                                       ctypes.byref(opts), ctypes.byref(stats), X.device.index or 0, _stream(X.device))
-    _lib.check(rc, "mmf_simtopk_panels")
-    if return_stats:
-        return idx, val, stats.as_dict()
-    return idx, val
+    middle = (int(row_offset), int(col_offset), ctypes.byref(qs), _p(c_scal), arr, len(panels), _p(maxima), _OPERAND[operand])
+    return _simtopk_entry("mmf_simtopk_panels", X, Y, metric, lam, k, exclude_self, middle, opts, return_stats)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -542,9 +457,7 @@ def segment_sort(labels: torch.Tensor, n_segments: int) -> Segments:
     counts = torch.empty((S,), dtype=torch.int64, device=lab.device)
     offsets = torch.empty((S + 1,), dtype=torch.int64, device=lab.device)
     order = torch.empty((n,), dtype=torch.int64, device=lab.device)
-    rc = _lib.lib().mmf_segment_sort(_p(lab), n, S, _p(counts), _p(offsets), _p(order), lab.device.index or 0,
-                                     _stream(lab.device))
-    _lib.check(rc, "mmf_segment_sort")
+    _call("mmf_segment_sort", lab.device, _p(lab), n, S, _p(counts), _p(offsets), _p(order))
     return Segments(counts, offsets, order, n, S)
 
 
@@ -555,9 +468,7 @@ def segment_mean(X: torch.Tensor, seg: Segments) -> torch.Tensor:
     if X.shape[0] != seg.n:
         raise ValueError("segment_mean: X has a different number of rows than the labels")
     out = torch.empty((seg.n_segments, X.shape[1]), dtype=torch.float32, device=X.device)
-    rc = _lib.lib().mmf_segment_mean(_p(X), X.shape[0], X.shape[1], _p(seg.order), _p(seg.offsets), seg.n_segments,
-                                     _p(out), X.device.index or 0, _stream(X.device))
-    _lib.check(rc, "mmf_segment_mean")
+    _call("mmf_segment_mean", X.device, _p(X), X.shape[0], X.shape[1], _p(seg.order), _p(seg.offsets), seg.n_segments, _p(out))
     return out
 
 
@@ -568,9 +479,7 @@ def segment_offdiag_mean(K: torch.Tensor, seg: Segments) -> torch.Tensor:
     if K.dim() != 2 or K.shape[0] != K.shape[1] or K.shape[0] != seg.n:
         raise ValueError("segment_offdiag_mean: K must be [n, n] with n = number of labels")
     out = torch.empty((seg.n_segments,), dtype=torch.float64, device=K.device)
-    rc = _lib.lib().mmf_segment_offdiag_mean(_p(K), K.shape[0], _p(seg.order), _p(seg.offsets), seg.n_segments, _p(out),
-                                             K.device.index or 0, _stream(K.device))
-    _lib.check(rc, "mmf_segment_offdiag_mean")
+    _call("mmf_segment_offdiag_mean", K.device, _p(K), K.shape[0], _p(seg.order), _p(seg.offsets), seg.n_segments, _p(out))
     return out
 
 
@@ -578,14 +487,13 @@ def clique_pairs(seg: Segments) -> Tuple[torch.Tensor, torch.Tensor]:
     """(lo, hi) int64: every pair a < b inside every segment (mmf_clique_pairs: count, then fill)."""
     dev = seg.order.device
     cnt = torch.zeros((), dtype=torch.int64, device=dev)
-    L = _lib.lib()
     args = (_p(seg.order), _p(seg.offsets), seg.n, seg.n_segments)
-    _lib.check(L.mmf_clique_pairs(*args, None, None, 0, _p(cnt), dev.index or 0, _stream(dev)), "mmf_clique_pairs")
+    _call("mmf_clique_pairs", dev, *args, None, None, 0, _p(cnt))
     E = int(cnt.item())
     lo = torch.empty((E,), dtype=torch.int64, device=dev)
     hi = torch.empty((E,), dtype=torch.int64, device=dev)
     if E:
-        _lib.check(L.mmf_clique_pairs(*args, _p(lo), _p(hi), E, _p(cnt), dev.index or 0, _stream(dev)), "mmf_clique_pairs")
+        _call("mmf_clique_pairs", dev, *args, _p(lo), _p(hi), E, _p(cnt))
     return lo, hi
 
 
@@ -599,8 +507,7 @@ def knn_pairs(nbr: torch.Tensor, labels: Optional[torch.Tensor] = None) -> Tuple
     lo = torch.empty((n * k,), dtype=torch.int64, device=nbr.device)
     hi = torch.empty((n * k,), dtype=torch.int64, device=nbr.device)
     cnt = torch.zeros((), dtype=torch.int64, device=nbr.device)
-    rc = _lib.lib().mmf_knn_pairs(_p(nbr), n, k, _p(lab), _p(lo), _p(hi), _p(cnt), nbr.device.index or 0, _stream(nbr.device))
-    _lib.check(rc, "mmf_knn_pairs")
+    _call("mmf_knn_pairs", nbr.device, _p(nbr), n, k, _p(lab), _p(lo), _p(hi), _p(cnt))
     E = int(cnt.item())
     return lo[:E], hi[:E]
 
@@ -615,10 +522,9 @@ def knn_clique_edges(nbr: torch.Tensor, labels: Optional[torch.Tensor], n_cluste
     if nbr.dim() != 2 or nbr.shape[1] < 1:
         raise ValueError(f"knn_clique_edges: nbr must be [n, k] with k >= 1, got shape {tuple(nbr.shape)}")
     n, k = nbr.shape
-    p = torch.tensor([0, n], dtype=torch.int64) if ptr is None and batch is None else _segment_ptr(ptr, batch, n, "", "knn_clique_edges")
+    one = ptr is None and batch is None
+    p = torch.tensor([0, n], dtype=torch.int64) if one else ragged.offsets(ptr, batch, n, what="knn_clique_edges")
     S = p.numel() - 1
-    if S < 1:
-        raise ValueError("knn_clique_edges: no segments")
     if labels is not None and labels.numel() != n:
         raise ValueError(f"knn_clique_edges: {labels.numel()} labels for {n} rows")
     _need_gpu(nbr, "knn_clique_edges")
@@ -628,14 +534,11 @@ def knn_clique_edges(nbr: torch.Tensor, labels: Optional[torch.Tensor], n_cluste
     row_off = torch.empty((n + 1,), dtype=torch.int64, device=dev)
     edge_ptr = torch.empty((S + 1,), dtype=torch.int64, device=dev)
     cnt = torch.zeros((), dtype=torch.int64, device=dev)
-    L = _lib.lib()
-    args = (_p(nbr), n, k, _p(lab), int(n_clusters), ctypes.c_void_p(p.data_ptr()), S)
-    _lib.check(L.mmf_knn_clique_edges_count(*args, _p(row_off), _p(edge_ptr), _p(cnt), dev.index or 0, _stream(dev)),
-               "mmf_knn_clique_edges_count")
+    args = (_p(nbr), n, k, _p(lab), int(n_clusters), _hp(p), S)
+    _call("mmf_knn_clique_edges_count", dev, *args, _p(row_off), _p(edge_ptr), _p(cnt))
     E = int(cnt.item())                 # -1: a label out of range, which the fill entry turns into the error
     ei = torch.empty((2, max(E, 0)), dtype=torch.int64, device=dev)
-    _lib.check(L.mmf_knn_clique_edges_fill(*args, _p(row_off), _p(ei), E, dev.index or 0, _stream(dev)),
-               "mmf_knn_clique_edges_fill")
+    _call("mmf_knn_clique_edges_fill", dev, *args, _p(row_off), _p(ei), E)
     return ei, edge_ptr
 
 
@@ -655,11 +558,9 @@ def kmeans_fit(X: torch.Tensor, n_clusters: int, first_centres, uniforms, *, max
     centres = torch.empty((k, d), dtype=torch.float32, device=X.device)
     seeds = torch.empty((n_init, k), dtype=torch.int64, device=X.device) if return_seeds else None
     info = np.zeros(7 + 2 * n_init, dtype=np.float64)
-    rc = _lib.lib().mmf_kmeans_fit(_p(X), n, d, k, n_init, trials, ctypes.c_void_p(first.ctypes.data),
-                                   ctypes.c_void_p(u.ctypes.data) if k > 1 else None, int(max_iter), float(tol), _p(labels),
-                                   _p(centres), _p(seeds), ctypes.c_void_p(info.ctypes.data), X.device.index or 0,
-                                   _stream(X.device))
-    _lib.check(rc, "mmf_kmeans_fit")
+    _call("mmf_kmeans_fit", X.device, _p(X), n, d, k, n_init, trials, ctypes.c_void_p(first.ctypes.data),
+          ctypes.c_void_p(u.ctypes.data) if k > 1 else None, int(max_iter), float(tol), _p(labels), _p(centres), _p(seeds),
+          ctypes.c_void_p(info.ctypes.data))
     out_info = _kmeans_info(info)
     if return_seeds:
         return labels, centres, out_info, seeds
@@ -698,21 +599,18 @@ def kmeans_fit_segmented(X: torch.Tensor, ptr, n_clusters: int, first_centres, u
     import numpy as np
     X = _feat(X, "kmeans_fit_segmented X").float()
     n, d = X.shape
-    p = np.ascontiguousarray(torch.as_tensor(ptr).detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-    n_seg = int(p.shape[0]) - 1
+    p = ragged.offsets(ptr, None, n, what="kmeans_fit_segmented", allow_no_segments=True)
+    n_seg = p.numel() - 1
     k = int(n_clusters)
     first, u, n_init, trials = _kmeans_stream("kmeans_fit_segmented", k, first_centres, uniforms, n_seg)
     _need_gpu(X, "kmeans_fit_segmented")
     labels = torch.empty(n, dtype=torch.int64, device=X.device)
-    centres = torch.empty((max(n_seg, 0), k, d), dtype=torch.float32, device=X.device)
-    seeds = torch.empty((max(n_seg, 0), n_init, k), dtype=torch.int64, device=X.device) if return_seeds else None
-    info = np.zeros((max(n_seg, 0), 7 + 2 * n_init), dtype=np.float64)
-    rc = _lib.lib().mmf_kmeans_fit_segmented(_p(X), n, d, ctypes.c_void_p(p.ctypes.data), n_seg, k, n_init, trials,
-                                             ctypes.c_void_p(first.ctypes.data), ctypes.c_void_p(u.ctypes.data) if k > 1 else None,
-                                             int(max_iter), float(tol), _p(labels), _p(centres), _p(seeds),
-                                             ctypes.c_void_p(info.ctypes.data), X.device.index or 0,
-                                             _stream(X.device))
-    _lib.check(rc, "mmf_kmeans_fit_segmented")
+    centres = torch.empty((n_seg, k, d), dtype=torch.float32, device=X.device)
+    seeds = torch.empty((n_seg, n_init, k), dtype=torch.int64, device=X.device) if return_seeds else None
+    info = np.zeros((n_seg, 7 + 2 * n_init), dtype=np.float64)
+    _call("mmf_kmeans_fit_segmented", X.device, _p(X), n, d, _hp(p), n_seg, k, n_init, trials, ctypes.c_void_p(first.ctypes.data),
+          ctypes.c_void_p(u.ctypes.data) if k > 1 else None, int(max_iter), float(tol), _p(labels), _p(centres), _p(seeds),
+          ctypes.c_void_p(info.ctypes.data))
     out_info = [_kmeans_info(row) for row in info]
     if return_seeds:
         return labels, centres, out_info, seeds

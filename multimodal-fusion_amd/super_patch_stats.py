@@ -70,8 +70,6 @@ def super_patch_stats_streamed(F: torch.Tensor, P: torch.Tensor, order: Optional
         order, offsets = order.to(torch.int64).contiguous(), offsets.to(torch.int64).contiguous()
         intra = torch.empty((C,), dtype=torch.float64, device=dev)
     k_stats = torch.empty((5,), dtype=torch.float64, device=dev)
-    rc = _lib.lib().mmf_super_patch_stats_streamed(ops._p(F), ops._p(P), n, F.shape[1], P.shape[1], float(lambda_h), float(lambda_g),
-                                                   ops._p(order), ops._p(offsets if order is not None else None), C, int(panel_rows),
-                                                   ops._p(intra), ops._p(k_stats), dev.index or 0, ops._stream(dev))
-    _lib.check(rc, "mmf_super_patch_stats_streamed")
+    ops._call("mmf_super_patch_stats_streamed", dev, ops._p(F), ops._p(P), n, F.shape[1], P.shape[1], float(lambda_h), float(lambda_g),
+              ops._p(order), ops._p(offsets if order is not None else None), C, int(panel_rows), ops._p(intra), ops._p(k_stats))
     return intra, k_stats

@@ -14,32 +14,27 @@ Every argument error is raised on the host before the device is touched, and nam
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import ops, ragged
+from .kmeans import segmented_labels
 from .super_patch_stats import super_patch_stats_streamed
 from .build_hypergraph import preprocess_hypergraph, similarity_kernel
 from .build_hypergraph._common import compute_device, result_device_like_preprocess, to_gpu
-from .weighted_hypergraph import _groups
-from .wsi_tma_similarity import _STAT_KEYS, _slide_ptr
 
 STREAM_MIN_VALUES = 1 << 22   # a block of fewer values (16 MiB) is stored even when it alone exceeds the budget
 MAX_CLUSTERS = 16384          # clusters per slide (the LDS histogram of one slide's chunk, csrc/mmf_pool.hip)
 
 
-def _hp(t: torch.Tensor) -> ctypes.c_void_p:
-    return ctypes.c_void_p(t.data_ptr())
+_cohort_labels = segmented_labels      # looked up at call time: a test puts labels of its own in its place
 
 
 def _check_clusters(sizes, n_clusters: int, what: str) -> None:
     """What scikit-learn raises for a slide with fewer rows than clusters, with the slide named; the per-slide limit; G < 2^31."""
-    for s, n_s in enumerate(sizes):
-        if not (1 <= n_clusters <= n_s):
-            raise ValueError(f"{what}: slide {s}: n_samples={n_s} should be >= n_clusters={n_clusters}.")
+    ragged.check_kmeans_sizes(sizes, n_clusters, what, "slide")
     if n_clusters > MAX_CLUSTERS:
         raise ValueError(f"{what}: slide 0: at most {MAX_CLUSTERS} clusters per slide are supported (got {n_clusters})")
     if len(sizes) * n_clusters >= 2 ** 31:
@@ -47,9 +42,9 @@ def _check_clusters(sizes, n_clusters: int, what: str) -> None:
 
 
 def group_plan(sizes, budget_bytes: int) -> List[Tuple[int, int]]:
-    """Consecutive slides [a, b) whose blocks K_s (n_s^2 f32 each) fit `budget_bytes` together (weighted_hypergraph._groups); a
+    """Consecutive slides [a, b) whose blocks K_s (n_s^2 f32 each) fit `budget_bytes` together (ragged.budget_groups); a
     slide whose block alone is larger is a group of its own."""
-    return [(a, b) for a, b, _ in _groups([int(v) for v in sizes], int(budget_bytes))]
+    return [(a, b) for a, b, _ in ragged.budget_groups([int(v) for v in sizes], int(budget_bytes))]
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -65,7 +60,7 @@ def segment_sort_segmented(labels: torch.Tensor, n_clusters: int, *, ptr=None, b
     if labels.dim() != 1:
         raise ValueError(f"{what}: expected a flat 1-D label vector, got shape {tuple(labels.shape)}")
     n, C = labels.numel(), int(n_clusters)
-    p = _slide_ptr(ptr, batch, n, "", what, min_rows=0)
+    p = ragged.offsets(ptr, batch, n, what=what, unit="slide")
     S = p.numel() - 1
     if C < 1 or C > MAX_CLUSTERS:
         raise ValueError(f"{what}: slide 0: n_clusters must lie in [1, {MAX_CLUSTERS}] (got {C})")
@@ -78,9 +73,8 @@ def segment_sort_segmented(labels: torch.Tensor, n_clusters: int, *, ptr=None, b
     offsets = torch.empty((S * C + 1,), dtype=torch.int64, device=dev)
     order = torch.empty((n,), dtype=torch.int64, device=dev)
     status = torch.empty((2,), dtype=torch.int64, device=dev)
-    rc = _lib.lib().mmf_segment_sort_segmented(ops._p(lab), n, _hp(p), S, C, ops._p(counts), ops._p(offsets), ops._p(order),
-                                               ops._p(status), dev.index or 0, ops._stream(dev))
-    _lib.check(rc, "mmf_segment_sort_segmented")
+    ops._call("mmf_segment_sort_segmented", dev, ops._p(lab), n, ops._hp(p), S, C, ops._p(counts), ops._p(offsets), ops._p(order),
+              ops._p(status))
     return counts, offsets, order, status
 
 
@@ -96,7 +90,7 @@ def pool_super_patches_segmented(F: torch.Tensor, P: torch.Tensor, order: torch.
     if F.dim() != 2 or P.dim() != 2 or P.shape[0] != F.shape[0]:
         raise ValueError(f"{what}: slide 0: features [N, D] and positions [N, dp] must share N")
     n, C = F.shape[0], int(n_clusters)
-    p = _slide_ptr(ptr, None, n, "", what, min_rows=0 if K_flat is None else 1)
+    p = ragged.offsets(ptr, None, n, what=what, unit="slide", min_rows=0 if K_flat is None else 1)
     S = p.numel() - 1
     if C < 1 or S * C >= 2 ** 31:
         raise ValueError(f"{what}: slide 0: bad n_clusters {C}")
@@ -104,7 +98,7 @@ def pool_super_patches_segmented(F: torch.Tensor, P: torch.Tensor, order: torch.
         raise ValueError(f"{what}: slide 0: order must hold {n} rows and offsets {S * C + 1} entries "
                          f"(got {order.numel()} and {offsets.numel()})")
     if K_flat is not None:
-        total = int(((p[1:] - p[:-1]) ** 2).sum())
+        total = int(ragged.block_offsets(p)[-1])
         if K_flat.dim() != 1 or K_flat.numel() != total:
             raise ValueError(f"{what}: slide {S - 1}: K_flat holds {K_flat.numel()} values, the blocks of the slides {total}")
     ops._need_gpu(F, what)
@@ -120,31 +114,14 @@ def pool_super_patches_segmented(F: torch.Tensor, P: torch.Tensor, order: torch.
         K_flat = K_flat.float().contiguous()
         intra = torch.empty((S * C,), dtype=torch.float64, device=dev)
         k_stats = torch.empty((S, 5), dtype=torch.float64, device=dev)
-    rc = _lib.lib().mmf_super_patches_segmented(ops._p(F), ops._p(P), n, F.shape[1], P.shape[1], _hp(p), S, C, ops._p(order),
-                                                ops._p(offsets), ops._p(K_flat), ops._p(super_f), ops._p(super_p), ops._p(intra),
-                                                ops._p(k_stats), dev.index or 0, ops._stream(dev))
-    _lib.check(rc, "mmf_super_patches_segmented")
+    ops._call("mmf_super_patches_segmented", dev, ops._p(F), ops._p(P), n, F.shape[1], P.shape[1], ops._hp(p), S, C, ops._p(order),
+              ops._p(offsets), ops._p(K_flat), ops._p(super_f), ops._p(super_p), ops._p(intra), ops._p(k_stats))
     return super_f, super_p, intra, k_stats
 
 
 # ---------------------------------------------------------------------------------------------------
 # aggregate_wsi_super_patches over a cohort
 # ---------------------------------------------------------------------------------------------------
-def _cohort_labels(F: torch.Tensor, p: torch.Tensor, n_clusters: int):
-    """(int64 labels [N] on F's device, local to each slide; ambiguous draws, ambiguous trials per slide or None): ONE segmented
-    KMeans fit for the cohort, or with the 'sklearn' backend the reference's own call slide by slide on the host."""
-    backend = preprocess_hypergraph.KMEANS_BACKEND
-    S = p.numel() - 1
-    if backend == "device":
-        from .kmeans import kmeans_fit_predict_segmented
-        lab, _, _, info = kmeans_fit_predict_segmented(F, n_clusters, ptr=p, n_init=10, seed=42, return_info=True)
-        return lab, [int(i["ambiguous_draws"]) for i in info], [int(i["ambiguous_trials"]) for i in info]
-    labels = torch.empty((F.shape[0],), dtype=torch.int64, device=F.device)
-    for s in range(S):
-        labels[int(p[s]):int(p[s + 1])] = preprocess_hypergraph._kmeans_labels(F[int(p[s]):int(p[s + 1])], n_clusters)
-    return labels, None, None
-
-
 def aggregate_wsi_super_patches_segmented(wsi_features: torch.Tensor, wsi_positions: torch.Tensor, num_super_patches: int,
                                           lambda_h: float = 1.0, lambda_g: float = 1.0, device: Optional[torch.device] = None,
                                           wsi_similarity_flat: Optional[torch.Tensor] = None, *, ptr=None, batch=None,
@@ -169,19 +146,19 @@ def aggregate_wsi_super_patches_segmented(wsi_features: torch.Tensor, wsi_positi
     if wsi_positions.shape[0] != wsi_features.shape[0]:
         raise ValueError(f"{what}: slide 0: wsi_features have {wsi_features.shape[0]} rows, wsi_positions {wsi_positions.shape[0]}")
     N, C = wsi_features.shape[0], int(num_super_patches)
-    p = _slide_ptr(ptr, batch, N, "", what)
+    p = ragged.offsets(ptr, batch, N, what=what, unit="slide", min_rows=1)
     sizes = (p[1:] - p[:-1]).tolist()
     S = len(sizes)
     _check_clusters(sizes, C, what)
-    k_ptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum((p[1:] - p[:-1]) ** 2, 0)]).contiguous()
+    k_ptr = ragged.block_offsets(p)
     if wsi_similarity_flat is not None and (wsi_similarity_flat.dim() != 1 or wsi_similarity_flat.numel() != int(k_ptr[-1])):
         raise ValueError(f"{what}: slide {S - 1}: wsi_similarity_flat must be the flat 1-D buffer of the blocks: it holds "
                          f"{wsi_similarity_flat.numel()} values, the blocks of the slides {int(k_ptr[-1])}")
     budget = int(similarity_kernel.STREAM_BYTES if budget_bytes is None else budget_bytes)
     whole = keep_similarity or wsi_similarity_flat is not None
-    plan = [(0, S, False)] if whole else _groups([int(v) for v in sizes], budget)
+    plan = [(0, S, False)] if whole else ragged.budget_groups([int(v) for v in sizes], budget)
     groups = [(a, b) for a, b, _ in plan]
-    # a slide that _groups set apart is streamed unless its block is small enough to go through the plain routines anyway
+    # a slide that budget_groups set apart is streamed unless its block is small enough to go through the plain routines anyway
     streamed = [bool(alone) and not whole and int(sizes[a]) ** 2 >= STREAM_MIN_VALUES for a, _, alone in plan]
     out_dev = result_device_like_preprocess(wsi_features, device)
     dev = out_dev if out_dev.type == "cuda" else compute_device(wsi_features, wsi_positions)
@@ -225,7 +202,7 @@ def aggregate_wsi_super_patches_segmented(wsi_features: torch.Tensor, wsi_positi
             v = intra32[i][~np.isnan(intra32[i])]
             stats.append({"num_original_patches": int(sizes[a + i]), "num_super_patches": C,
                           "avg_intra_cluster_similarity": float(np.mean(v.astype(np.float64))) if v.size else 0.0,
-                          "wsi_similarity_matrix_stats": dict(zip(_STAT_KEYS, st32[i]))})
+                          "wsi_similarity_matrix_stats": dict(zip(ops.STAT_KEYS, st32[i]))})
     K_out = K_all.to(out_dev) if (keep_similarity and K_all is not None) else None
     res = (super_f.to(out_dev), super_p.to(out_dev), stats, K_out, k_ptr)
     if return_info:

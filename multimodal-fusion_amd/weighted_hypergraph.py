@@ -16,7 +16,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, ragged
 from .build_hypergraph import similarity_kernel
 from .build_hypergraph._common import compute_device, f32_ceil, result_device_like_kernel, to_gpu
 
@@ -37,9 +37,7 @@ def _segments(features: torch.Tensor, positions: torch.Tensor, ptr, batch, what:
     """Host offsets, checked before any device work: shapes, ptr / batch, and at least two rows per segment."""
     if features.dim() != 2 or positions.dim() != 2 or positions.shape[0] != features.shape[0]:
         raise ValueError(f"{what}: features [N, D] and positions [N, dp] must share N")
-    p = ops._segment_ptr(ptr, batch, features.shape[0], "", what)
-    if p.numel() < 2:
-        raise ValueError(f"{what}: no segments")
+    p = ragged.offsets(ptr, batch, features.shape[0], what=what)
     sizes = p[1:] - p[:-1]
     small = torch.nonzero(sizes <= 1)
     if small.numel():
@@ -49,24 +47,7 @@ def _segments(features: torch.Tensor, positions: torch.Tensor, ptr, batch, what:
     return p
 
 
-def _groups(sizes, budget: int):
-    """Consecutive segments [a, b) whose blocks fit `budget` bytes together; (s, s + 1, True) for a segment streamed alone."""
-    out, a, acc = [], 0, 0
-    for s, n_s in enumerate(sizes):
-        b = n_s * n_s * 4
-        if b > budget:
-            if s > a:
-                out.append((a, s, False))
-            out.append((s, s + 1, True))
-            a, acc = s + 1, 0
-            continue
-        if acc + b > budget and s > a:
-            out.append((a, s, False))
-            a, acc = s, 0
-        acc += b
-    if len(sizes) > a:
-        out.append((a, len(sizes), False))
-    return out
+_groups = ragged.budget_groups      # the name tests and DESIGN.md know it by
 
 
 def _need_ratio(ratio, what: str) -> None:
@@ -149,10 +130,8 @@ def build_hypergraph_data_segmented(features: torch.Tensor, positions: torch.Ten
     positions = positions.to(device)
     edge_index, edge_weights, _ = build_weighted_hypergraph_segmented(features, positions, lambda_h, lambda_g,
                                                                       threshold_median_ratio, device, ptr=p)
-    sizes = p[1:] - p[:-1]
-    seg_ids = torch.repeat_interleave(torch.arange(sizes.numel(), dtype=torch.int64), sizes)
     result = {"x": features, "edge_index": edge_index, "edge_attr": edge_weights, "pos": positions,
-              "batch": seg_ids.to(device), "ptr": p.to(device)}
+              "batch": ragged.segment_ids(p).to(device), "ptr": p.to(device)}
     if use_pooling:
         result["pooled_feature"] = segment_mean_pool(features, p)
     return result

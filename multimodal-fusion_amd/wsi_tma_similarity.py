@@ -16,75 +16,15 @@ and names the first bad slide.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, ragged
+from .kmeans import segmented_labels
 from .build_hypergraph import preprocess_hypergraph
 from .build_hypergraph._common import compute_device, result_device_like_preprocess, to_gpu
-
-
-# ---------------------------------------------------------------------------------------------------
-# host-side argument checks
-# ---------------------------------------------------------------------------------------------------
-def _slide_ptr(ptr, batch, rows: Optional[int], side: str, what: str, min_rows: int = 1) -> torch.Tensor:
-    """Host int64 offsets [S + 1] of one side from exactly one of ptr / batch (sorted slide id per row), every slide with at least
-    min_rows rows.  rows None: the row count is what ptr / batch say.  The message names the first bad slide."""
-    if (ptr is None) == (batch is None):
-        raise ValueError(f"{what}: give exactly one of {side}ptr / {side}batch")
-    if ptr is not None:
-        p = torch.as_tensor(ptr).detach().to("cpu", torch.int64).reshape(-1).contiguous()
-        if p.numel() < 2:
-            raise ValueError(f"{what}: {side}ptr describes no slide (it needs S + 1 >= 2 offsets)")
-        if int(p[0]) != 0:
-            raise ValueError(f"{what}: slide 0: {side}ptr must start at 0 (got {int(p[0])})")
-        sizes = p[1:] - p[:-1]
-        bad = torch.nonzero(sizes < min_rows).reshape(-1)
-        if bad.numel():
-            s = int(bad[0])
-            if int(sizes[s]) < 0:
-                raise ValueError(f"{what}: slide {s}: {side}ptr decreases ({int(p[s])} -> {int(p[s + 1])})")
-            raise ValueError(f"{what}: slide {s} has {int(sizes[s])} rows in {side}ptr, need at least {min_rows}")
-        if rows is not None and int(p[-1]) != rows:
-            raise ValueError(f"{what}: slide {p.numel() - 2}: {side}ptr must end at {rows} (got {int(p[-1])})")
-        return p
-    b = torch.as_tensor(batch)
-    if b.dim() != 1 or (rows is not None and b.numel() != rows):
-        raise ValueError(f"{what}: slide 0: {side}batch must hold one slide id per row ({rows})")
-    b = b.detach().to("cpu", torch.int64)           # the one device -> host copy of a batch vector
-    if b.numel() == 0:
-        raise ValueError(f"{what}: slide 0 has 0 rows in {side}batch, need at least {min_rows}")
-    if int(b[0]) < 0:
-        raise ValueError(f"{what}: slide {int(b[0])}: {side}batch must be non-negative")
-    down = torch.nonzero(b[1:] < b[:-1]).reshape(-1)
-    if down.numel():
-        r = int(down[0]) + 1
-        raise ValueError(f"{what}: slide {int(b[r])}: {side}batch must be sorted (row {r} follows slide {int(b[r - 1])})")
-    counts = torch.bincount(b)
-    bad = torch.nonzero(counts < min_rows).reshape(-1)
-    if bad.numel():
-        s = int(bad[0])
-        raise ValueError(f"{what}: slide {s} has {int(counts[s])} rows in {side}batch, need at least {min_rows}")
-    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(counts, 0)]).contiguous()
-
-
-def _two_sides(n_x: Optional[int], n_y: Optional[int], x_ptr, x_batch, y_ptr, y_batch, xs: str, ys: str,
-               what: str) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """(x offsets, y offsets, block offsets s_ptr) of a two-sided slide description, all host int64 [S + 1]."""
-    xp = _slide_ptr(x_ptr, x_batch, n_x, xs, what)
-    yp = _slide_ptr(y_ptr, y_batch, n_y, ys, what)
-    if xp.numel() != yp.numel():
-        sx, sy = xp.numel() - 1, yp.numel() - 1
-        raise ValueError(f"{what}: slide {min(sx, sy)}: {xs.rstrip('_') or 'x'} describes {sx} slides, {ys.rstrip('_') or 'y'} {sy}")
-    blocks = (xp[1:] - xp[:-1]) * (yp[1:] - yp[:-1])
-    return xp, yp, torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(blocks, 0)]).contiguous()
-
-
-def _hp(t: torch.Tensor) -> ctypes.c_void_p:
-    return ctypes.c_void_p(t.data_ptr())
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -103,7 +43,9 @@ def sim_dense_stats_segmented(X: torch.Tensor, Y: torch.Tensor, *, x_ptr=None, x
         raise ValueError(f"{what}: slide 0: X has D={X.shape[1]}, Y has D={Y.shape[1]}")
     if ops._metric(metric) != _lib.RBF_DIRECT:
         raise ValueError(f"{what}: only metric='rbf_direct' is supported (got {metric!r})")
-    xp, yp, s_ptr = _two_sides(X.shape[0], Y.shape[0], x_ptr, x_batch, y_ptr, y_batch, "x_", "y_", what)
+    xp, yp = ragged.two_sided(X.shape[0], Y.shape[0], x_ptr, x_batch, y_ptr, y_batch, xs="x_", ys="y_", what=what, unit="slide",
+                              min_rows=(1, 1))
+    s_ptr = ragged.block_offsets(xp, yp)
     ops._need_gpu(X, what)
     if Y.device != X.device:
         raise ValueError(f"{what}: X and Y must share a device")
@@ -111,10 +53,8 @@ def sim_dense_stats_segmented(X: torch.Tensor, Y: torch.Tensor, *, x_ptr=None, x
     S = xp.numel() - 1
     out = torch.empty((int(s_ptr[-1]),), dtype=torch.float32, device=X.device)
     stats = torch.empty((S, 5), dtype=torch.float64, device=X.device)
-    rc = _lib.lib().mmf_sim_dense_stats_segmented(ops._p(X), X.shape[0], ops._p(Y), Y.shape[0], X.shape[1], ops._DT[X.dtype],
-                                                  _lib.RBF_DIRECT, float(lam), _hp(xp), _hp(yp), S, ops._p(out), ops._p(stats),
-                                                  X.device.index or 0, ops._stream(X.device))
-    _lib.check(rc, "mmf_sim_dense_stats_segmented")
+    ops._call("mmf_sim_dense_stats_segmented", X.device, ops._p(X), X.shape[0], ops._p(Y), Y.shape[0], X.shape[1], ops._DT[X.dtype],
+              _lib.RBF_DIRECT, float(lam), ops._hp(xp), ops._hp(yp), S, ops._p(out), ops._p(stats))
     return out, s_ptr, stats
 
 
@@ -124,21 +64,17 @@ def lower_median_segmented(v: torch.Tensor, *, ptr=None, batch=None) -> torch.Te
     what = "lower_median_segmented"
     if v.dim() != 1:
         raise ValueError(f"{what}: expected a flat 1-D tensor, got shape {tuple(v.shape)}")
-    p = _slide_ptr(ptr, batch, v.numel(), "", what)
+    p = ragged.offsets(ptr, batch, v.numel(), what=what, unit="slide", min_rows=1)
     ops._need_gpu(v, what)
     v = v.contiguous().float()
     out = torch.empty((p.numel() - 1,), dtype=torch.float32, device=v.device)
-    rc = _lib.lib().mmf_lower_median_segmented(ops._p(v), _hp(p), p.numel() - 1, ops._p(out), v.device.index or 0, ops._stream(v.device))
-    _lib.check(rc, "mmf_lower_median_segmented")
+    ops._call("mmf_lower_median_segmented", v.device, ops._p(v), ops._hp(p), p.numel() - 1, ops._p(out))
     return out
 
 
 # ---------------------------------------------------------------------------------------------------
 # compute_wsi_tma_similarity over a cohort
 # ---------------------------------------------------------------------------------------------------
-_STAT_KEYS = ("mean", "std", "min", "max", "median")
-
-
 def compute_wsi_tma_similarity_segmented(wsi_features: torch.Tensor, wsi_positions: torch.Tensor, tma_features: torch.Tensor,
                                          lambda_h: float = 1.0, lambda_g: float = 1.0, device: Optional[torch.device] = None, *,
                                          wsi_ptr=None, wsi_batch=None, tma_ptr=None,
@@ -152,13 +88,13 @@ def compute_wsi_tma_similarity_segmented(wsi_features: torch.Tensor, wsi_positio
         raise ValueError(f"{what}: wsi_features and tma_features must be 2-D [N, D]")
     if wsi_features.shape[1] != tma_features.shape[1]:
         raise ValueError(f"{what}: slide 0: wsi_features have D={wsi_features.shape[1]}, tma_features D={tma_features.shape[1]}")
-    wp, tp, _ = _two_sides(wsi_features.shape[0], tma_features.shape[0], wsi_ptr, wsi_batch, tma_ptr, tma_batch, "wsi_", "tma_", what)
+    wp, tp = ragged.two_sided(wsi_features.shape[0], tma_features.shape[0], wsi_ptr, wsi_batch, tma_ptr, tma_batch, xs="wsi_",
+                              ys="tma_", what=what, unit="slide", min_rows=(1, 1))
     out_dev = result_device_like_preprocess(wsi_features, device)
     dev = out_dev if out_dev.type == "cuda" else compute_device(wsi_features, tma_features)
     S_flat, s_ptr, stats = sim_dense_stats_segmented(to_gpu(wsi_features, dev), to_gpu(tma_features, dev), x_ptr=wp, y_ptr=tp,
                                                      metric="rbf_direct", lam=float(lambda_h))
-    host = stats.to(torch.float32).cpu().tolist()        # the reference's values are `.item()`s of f32 tensors
-    return S_flat.to(out_dev), s_ptr, [dict(zip(_STAT_KEYS, row)) for row in host]
+    return S_flat.to(out_dev), s_ptr, ops._stats_dict(stats)
 
 
 def similarity_block(S_flat: torch.Tensor, s_ptr, sizes: Sequence[Tuple[int, int]], s: int) -> torch.Tensor:
@@ -203,13 +139,13 @@ def group_by_similarity_segmented(S_flat: torch.Tensor, num_groups: int, *, wsi_
     if S_flat.dim() != 1:
         raise ValueError(f"{what}: S_flat must be the flat 1-D buffer of the blocks, got shape {tuple(S_flat.shape)}")
     num_groups = int(num_groups)
-    wp, tp, s_ptr = _two_sides(None, None, wsi_ptr, wsi_batch, tma_ptr, tma_batch, "wsi_", "tma_", what)
+    wp, tp = ragged.two_sided(None, None, wsi_ptr, wsi_batch, tma_ptr, tma_batch, xs="wsi_", ys="tma_", what=what, unit="slide",
+                              min_rows=(1, 1))
+    s_ptr = ragged.block_offsets(wp, tp)
     if S_flat.numel() != int(s_ptr[-1]):
         raise ValueError(f"{what}: slide {wp.numel() - 2}: S_flat holds {S_flat.numel()} values, the blocks of the slides {int(s_ptr[-1])}")
     n_sizes, m_sizes = (wp[1:] - wp[:-1]).tolist(), (tp[1:] - tp[:-1]).tolist()
-    for s, n_s in enumerate(n_sizes):
-        if not (1 <= num_groups <= n_s):
-            raise ValueError(f"{what}: slide {s}: n_samples={n_s} should be >= n_clusters={num_groups}.")
+    ragged.check_kmeans_sizes(n_sizes, num_groups, what, "slide")
     S, n_wsi = len(n_sizes), int(wp[-1])
     dev = compute_device(S_flat)
     F = to_gpu(S_flat, dev)
@@ -218,27 +154,22 @@ def group_by_similarity_segmented(S_flat: torch.Tensor, num_groups: int, *, wsi_
     labels = torch.empty((n_wsi,), dtype=torch.int64, device=dev)
     draws: Optional[List[int]] = [0] * S if backend == "device" else None
     trials: Optional[List[int]] = [0] * S if backend == "device" else None
-    if backend == "device":
-        from .kmeans import kmeans_fit_predict_segmented
-        for fit in width_plan(n_sizes, m_sizes):
-            sl, m = fit["slides"], fit["width"]
-            if fit["adjacent"]:
-                X = F[sp[sl[0]]:sp[sl[-1] + 1]].view(-1, m)
-            else:
-                X = torch.cat([F[sp[s]:sp[s + 1]].view(-1, m) for s in sl], dim=0)
-            lab, _, _, info = kmeans_fit_predict_segmented(X, num_groups, ptr=fit["fit_ptr"], n_init=10, seed=42, return_info=True)
-            if fit["adjacent"]:
-                labels[int(wp[sl[0]]):int(wp[sl[-1] + 1])] = lab
-            else:
-                dest = torch.cat([torch.arange(int(wp[s]), int(wp[s + 1])) for s in sl])
-                labels[dest.to(dev)] = lab
-            for s, i in zip(sl, info):
-                draws[s], trials[s] = int(i["ambiguous_draws"]), int(i["ambiguous_trials"])
-    else:        # 'sklearn': the reference's own call, slide by slide, on the host
-        for s in range(S):
-            block = F[sp[s]:sp[s + 1]].view(n_sizes[s], m_sizes[s])
-            labels[int(wp[s]):int(wp[s + 1])] = preprocess_hypergraph._kmeans_labels(block, num_groups)
-    slide_of_row = torch.repeat_interleave(torch.arange(S), wp[1:] - wp[:-1]).to(dev)
+    for fit in width_plan(n_sizes, m_sizes):
+        sl, m = fit["slides"], fit["width"]
+        if fit["adjacent"]:
+            X = F[sp[sl[0]]:sp[sl[-1] + 1]].view(-1, m)
+        else:
+            X = torch.cat([F[sp[s]:sp[s + 1]].view(-1, m) for s in sl], dim=0)
+        lab, fit_draws, fit_trials = segmented_labels(X, fit["fit_ptr"], num_groups)
+        if fit["adjacent"]:
+            labels[int(wp[sl[0]]):int(wp[sl[-1] + 1])] = lab
+        else:
+            dest = torch.cat([torch.arange(int(wp[s]), int(wp[s + 1])) for s in sl])
+            labels[dest.to(dev)] = lab
+        if draws is not None:
+            for i, s in enumerate(sl):
+                draws[s], trials[s] = fit_draws[i], fit_trials[i]
+    slide_of_row = ragged.segment_ids(wp).to(dev)
     sizes = torch.bincount(slide_of_row * num_groups + labels, minlength=S * num_groups).cpu().view(S, num_groups).tolist()
     stats = [{"method": "kmeans", "num_groups": num_groups, "group_sizes": [int(v) for v in row]} for row in sizes]
     info = {"kmeans_backend": backend, "ambiguous_draws": draws, "ambiguous_trials": trials}
@@ -267,7 +198,7 @@ def filter_edges_by_median_segmented(edge_index: torch.Tensor, edge_weights: tor
     if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_weights.dim() != 1 or edge_index.shape[1] != edge_weights.shape[0]:
         raise ValueError(f"{what}: expected edge_index [2, E] and edge_weights [E], got {tuple(edge_index.shape)} and {tuple(edge_weights.shape)}")
     E = edge_weights.shape[0]
-    p = _slide_ptr(edge_ptr, None, E, "edge_", what, min_rows=0)
+    p = ragged.offsets(edge_ptr, None, E, side="edge_", what=what, unit="slide")
     empty = torch.nonzero(p[1:] == p[:-1]).reshape(-1)
     if empty.numel():
         raise ValueError(f"{what}: slide {int(empty[0])} has no edges: the median of an empty tensor is undefined")
@@ -278,7 +209,7 @@ def filter_edges_by_median_segmented(edge_index: torch.Tensor, edge_weights: tor
     ei = edge_index.detach().to(device=dev, dtype=torch.int64).contiguous()
     med = lower_median_segmented(w, ptr=p)
     thr64, thr32 = median_thresholds(med, ratio)
-    slide_of_edge = torch.repeat_interleave(torch.arange(S), p[1:] - p[:-1]).to(dev)
+    slide_of_edge = ragged.segment_ids(p).to(dev)
     mask = w >= thr32[slide_of_edge]
     kept = torch.zeros(S, dtype=torch.int64, device=dev).index_add_(0, slide_of_edge, mask.to(torch.int64))
     host = torch.stack([thr64, kept.to(torch.float64)], dim=1).cpu()          # the one host read

@@ -36,7 +36,7 @@ def test_library_exports_the_entry():
     (dict(batch=torch.tensor([-1, -1, -1, 0, 0, 0, 0, 0, 0, 0])), "non-negative"),         # negative
     (dict(batch=torch.zeros(9, dtype=torch.long)), "one segment id per row"),             # wrong length
     (dict(ptr=[0, 5, 9]), "end at 10"),                                                   # not ending at n
-    (dict(ptr=[0, 6, 4, 10]), "non-decreasing"),                                          # decreasing
+    (dict(ptr=[0, 6, 4, 10]), "segment 1: ptr decreases"),                                # decreasing
     (dict(ptr=[0, 10], batch=torch.zeros(10, dtype=torch.long)), "exactly one"),          # both
     (dict(), "exactly one"),                                                              # neither
     (dict(ptr=[0, 5, 5, 10]), r"segment 1: n_samples=0 should be >= n_clusters=3"),        # empty segment
@@ -52,6 +52,20 @@ def test_bad_segments_are_rejected_on_the_host(kw, match):
 def test_valid_segments_on_a_cpu_tensor_need_the_device():
     with pytest.raises(RuntimeError):
         _km().kmeans_fit_predict_segmented(torch.randn(10, 8), 3, ptr=[0, 4, 10])
+
+
+def test_segmented_labels_check_the_sizes_before_the_device(monkeypatch):
+    """The one backend dispatch of the cohort steps: with the default 'device' backend and no GPU, a short segment is the
+    ValueError scikit-learn would raise, and only sizes that pass reach the device check."""
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    km, X = _km(), torch.randn(10, 8)
+    with pytest.raises(ValueError, match=r"segment 1: n_samples=2 should be >= n_clusters=3\."):
+        km.segmented_labels(X, torch.tensor([0, 8, 10]), 3)
+    with pytest.raises(ValueError, match=r"segment 0: n_samples=4 should be >= n_clusters=0\."):
+        km.segmented_labels(X, [0, 4, 10], 0)
+    for p in (torch.tensor([0, 4, 10]), [0, 4, 10]):
+        with pytest.raises(RuntimeError, match="ROCm"):
+            km.segmented_labels(X, p, 3)
 
 
 @pytest.mark.parametrize("k", [1, 3, 10, 100])

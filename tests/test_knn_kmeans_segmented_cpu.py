@@ -55,17 +55,17 @@ def test_new_kernels_are_a_build_source():
 BAD = [
     (dict(wsi_ptr=[0, 5, 9], tma_ptr=[0, 3, 6]), "wsi_ptr must start at 0 and end at 10"),
     (dict(wsi_ptr=[1, 5, 10], tma_ptr=[0, 3, 6]), "wsi_ptr must start at 0"),
-    (dict(wsi_ptr=[0, 6, 4, 10], tma_ptr=[0, 2, 4, 6]), "wsi_ptr must be non-decreasing"),
+    (dict(wsi_ptr=[0, 6, 4, 10], tma_ptr=[0, 2, 4, 6]), "segment 1: wsi_ptr decreases"),
     (dict(wsi_ptr=[0, 5, 10], tma_ptr=[0, 3, 5]), "tma_ptr must start at 0 and end at 6"),
-    (dict(wsi_ptr=[0, 5, 10], tma_ptr=[0, 4, 3, 6]), "tma_ptr must be non-decreasing"),
+    (dict(wsi_ptr=[0, 5, 10], tma_ptr=[0, 4, 3, 6]), "segment 1: tma_ptr decreases"),
     (dict(wsi_batch=torch.tensor([0, 0, 0, 1, 1, 1, 0, 1, 1, 1]), tma_ptr=[0, 3, 6]), "wsi_batch must be sorted"),
-    (dict(wsi_ptr=[0, 5, 10], tma_batch=torch.tensor([-1, 0, 0, 0, 1, 1])), "tma_batch must be sorted and non-negative"),
+    (dict(wsi_ptr=[0, 5, 10], tma_batch=torch.tensor([-1, 0, 0, 0, 1, 1])), "segment -1: tma_batch must be non-negative"),
     (dict(wsi_batch=torch.zeros(9, dtype=torch.long), tma_ptr=[0, 6]), r"wsi_batch must hold one segment id per row \(10\)"),
     (dict(wsi_ptr=[0, 5, 10], wsi_batch=torch.zeros(10, dtype=torch.long), tma_ptr=[0, 3, 6]), "exactly one of wsi_ptr / wsi_batch"),
     (dict(wsi_ptr=[0, 5, 10]), "exactly one of tma_ptr / tma_batch"),
     (dict(tma_ptr=[0, 3, 6]), "exactly one of wsi_ptr / wsi_batch"),
-    (dict(wsi_ptr=[0, 5, 10], tma_ptr=[0, 2, 4, 6]), "wsi has 2 segments, tma has 3"),
-    (dict(wsi_ptr=[0, 5, 10], tma_batch=torch.zeros(6, dtype=torch.long)), "wsi has 2 segments, tma has 1"),
+    (dict(wsi_ptr=[0, 5, 10], tma_ptr=[0, 2, 4, 6]), "segment 2: wsi describes 2 segments, tma 3"),
+    (dict(wsi_ptr=[0, 5, 10], tma_batch=torch.zeros(6, dtype=torch.long)), "segment 1: wsi describes 2 segments, tma 1"),
     # slide 1 has 2 + 1 = 3 nodes: too few for k + 1 = 4 neighbours (sklearn's kneighbors text)
     (dict(wsi_ptr=[0, 8, 10], tma_ptr=[0, 5, 6], k=3, num_hyperedges=2),
      r"segment 1: Expected n_neighbors <= n_samples_fit, but n_neighbors = 4, n_samples_fit = 3, n_samples = 3"),
@@ -97,7 +97,7 @@ def test_builder_rejects_different_feature_widths():
 @pytest.mark.parametrize("kw,match", [
     (dict(ptr=[0, 5, 9]), "end at 10"),
     (dict(ptr=[1, 5, 10]), "start at 0"),
-    (dict(ptr=[0, 6, 4, 10]), "non-decreasing"),
+    (dict(ptr=[0, 6, 4, 10]), "segment 1: ptr decreases"),
     (dict(batch=torch.tensor([0, 0, 0, 1, 1, 1, 0, 1, 1, 1])), "sorted"),
     (dict(batch=torch.zeros(9, dtype=torch.long)), "one segment id per row"),
     (dict(ptr=[0, 10], batch=torch.zeros(10, dtype=torch.long)), "exactly one"),
@@ -138,7 +138,7 @@ def test_node_offsets_from_ptr_and_from_batch():
     # slide s: wsi rows first, then its tma rows, numbered from node[s]
     sizes = (node[1:] - node[:-1]).tolist()
     assert sizes == [(wp[s + 1] - wp[s] + tp[s + 1] - tp[s]).item() for s in range(4)] == [5, 7, 2, 5]
-    with pytest.raises(ValueError, match="wsi has 4 segments, tma has 3"):
+    with pytest.raises(ValueError, match="segment 3: wsi describes 4 segments, tma 3"):
         kk.node_offsets(12, 5, wsi_batch=wb, tma_batch=torch.tensor([0, 0, 1, 1, 2]))     # a batch vector ends at its last id
 
 

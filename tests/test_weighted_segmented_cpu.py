@@ -47,7 +47,7 @@ def test_mirror_package_is_unchanged():
 @pytest.mark.parametrize("kw,match", [
     (dict(ptr=[0, 5, 9]), "end at 10"),                                                    # not ending at N
     (dict(ptr=[1, 5, 10]), "start at 0"),                                                  # not starting at 0
-    (dict(ptr=[0, 6, 4, 10]), "non-decreasing"),                                           # decreasing
+    (dict(ptr=[0, 6, 4, 10]), "segment 1: ptr decreases"),                                 # decreasing
     (dict(batch=torch.tensor([0, 0, 0, 1, 1, 1, 0, 1, 1, 1])), "sorted"),                  # unsorted
     (dict(batch=torch.tensor([-1, -1, 0, 0, 0, 0, 0, 0, 0, 0])), "non-negative"),          # negative
     (dict(batch=torch.zeros(9, dtype=torch.long)), "one segment id per row"),             # wrong length
