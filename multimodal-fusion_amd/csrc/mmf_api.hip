@@ -271,6 +271,9 @@ static void fill_stats(mmf_simtopk_stats* st, int precision, int splits, int gri
 // that fills them as well is redone exactly
 static constexpr int kSpillCap = 192;
 
+// one list pair per row: its two lanes fill the row's overflow slots from both ends (MMF_SPILL_COUNTER: one counter instead)
+static int spill_stacks_for(int lists) { return (lists == 2 && !getenv("MMF_SPILL_COUNTER")) ? 1 : 0; }
+
 // The 16-bit scan's candidate lists of n rows: `lists` lists of bcap entries per row, and the overflow lists.
 static size_t b16_lists_bytes(int64_t n, int lists, int bcap) {
   const size_t e = (size_t)n * lists;
@@ -283,7 +286,7 @@ static CandLists carve_b16_lists(Workspace& ws, int64_t n, int lists, int bcap) 
   L.cnt = ws.take<uint32_t>((size_t)n * lists); L.ids = ws.take<uint32_t>((size_t)n * lists * bcap);
   if (lists > 2) { L.keys = ws.take<float>((size_t)n * lists * bcap); L.margin = ws.take<float>(n); }   // one pair: nothing to prune against
   L.overflow = ws.take<uint32_t>(n); L.spill_cnt = ws.take<uint32_t>(n); L.spill_ids = ws.take<uint32_t>((size_t)n * kSpillCap);
-  L.spill_stacks = (lists == 2 && !getenv("MMF_SPILL_COUNTER")) ? 1 : 0;   // one pair: its two lanes fill the slots from both ends
+  L.spill_stacks = spill_stacks_for(lists);
   return L;
 }
 
@@ -484,16 +487,14 @@ struct ExactPass {
 // wait), exact re-rank, exact rescan of flagged rows, stats.  Shared by mmf_simtopk_ex,
 // mmf_simtopk_prepared and mmf_simtopk_panels.
 struct FastOperands {
-  const uint16_t* ZQ; const uint16_t* ZC;
+  HalfImage q, c;        // the 16-bit images of the queries and of the candidates (c: Z / cb / maxima are read)
   const float* rx; const float* cy;
-  const float* q_zn; const float* q_rn; const float* q_un;
-  const float* c_cb; const uint32_t* max_c;
   int64_t m_pad_tiles;   // candidate rows covered by tiles (multiple of 256)
   int dp; bool f16;
   // paneled scan (mmf_simtopk_panels): the candidate operands come as n_panels separate blocks, each scanned by
-  // its own launch once its event has fired; ZC / c_cb / m_pad_tiles above are then unused
+  // its own launch once its event has fired; c.Z / c.cb / m_pad_tiles above are then unused
   const mmf_panel* panels = nullptr; int n_panels = 0;
-  // ZQ / q_zn / q_rn / q_un hold the queries in scan order: position p is row perm[p] (mmf_order.hip); null: row order
+  // q holds the queries in scan order: position p is row perm[p] (mmf_order.hip); null: row order
   const int32_t* perm = nullptr;
 };
 
@@ -532,7 +533,7 @@ struct FastTail {
     CandLists v = L;
     v.lists = symmetric ? 4 : lists;
     if (v.lists <= 2) { v.keys = nullptr; v.margin = nullptr; }
-    v.spill_stacks = (v.lists == 2 && !getenv("MMF_SPILL_COUNTER")) ? 1 : 0;
+    v.spill_stacks = spill_stacks_for(v.lists);
     if (symmetric) { v.sym_cnt = sym_cnt; v.sym_ids = sym_ids; v.sym_keys = sym_keys; v.sym_cap = kSymCap; }
     return v;
   }
@@ -631,10 +632,10 @@ struct FastTail {
     int64_t near_rows = -1;
     if (order_try) {
       MMF_TRY(t_order.start(profile, s));
-      MMF_TRY(launch_query_order_probe(fo.ZQ, fo.q_zn, n, fo.dp, fo.f16, qo_scratch, &near_rows, s));
+      MMF_TRY(launch_query_order_probe(fo.q.Z, fo.q.zn, n, fo.dp, fo.f16, qo_scratch, &near_rows, s));
       if (order_mode == MMF_QUERY_ORDER_ON || near_rows >= 8 * (int64_t)query_order_pivots()) {
-        MMF_TRY(launch_query_order_apply(fo.ZQ, fo.q_zn, fo.q_rn, fo.q_un, n, n_pad_q(), fo.dp, fo.f16, qo_scratch, qo_Z, qo_zn, qo_rn, qo_un, &fo.perm, s));
-        fo.ZQ = qo_Z; fo.q_zn = qo_zn; fo.q_rn = qo_rn; fo.q_un = qo_un;
+        MMF_TRY(launch_query_order_apply(fo.q.Z, fo.q.zn, fo.q.rn, fo.q.un, n, n_pad_q(), fo.dp, fo.f16, qo_scratch, qo_Z, qo_zn, qo_rn, qo_un, &fo.perm, s));
+        fo.q.Z = qo_Z; fo.q.zn = qo_zn; fo.q.rn = qo_rn; fo.q.un = qo_un;
       }
       MMF_TRY(t_order.stop(s));
     }
@@ -651,16 +652,16 @@ struct FastTail {
     ScanB16Panel pn;
     pn.seed = seed; pn.seed_stride = n_seed;
     pn.share = (splits > 1 || fo.n_panels > 1) ? 1 : 0;
+    ScanB16Problem sp(fo.q, fo.c, n, m, fo.m_pad_tiles, fo.dp, r.d, fo.f16, r.metric, kk);
     if (symmetric) {
       bool live, forward;
       symmetric_live_mode(&live, &forward);
       const WsKept tables{sym.sched, (n + 255) / 256, sym_G, forward ? 1 : 0};
-      MMF_TRY(launch_scan_b16_sym(fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, r.d, fo.f16, r.metric, kk, sym_G, live, forward,
-                                  symmetric_prune_mode(), !(sym_kept == tables), L, scan_scratch, sym, pn, s, &grid));
+      MMF_TRY(launch_scan_b16_sym(sp, SymLaunch{sym_G, live, forward, symmetric_prune_mode(), !(sym_kept == tables)}, L, scan_scratch, sym,
+                                  pn, s, &grid));
       if (sym_keep) *sym_keep = tables;
     } else if (fo.n_panels == 0) {
-      MMF_TRY(launch_scan_b16(fo.ZQ, fo.ZC, fo.c_cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, m, fo.m_pad_tiles, fo.dp, r.d, fo.f16,
-                              r.metric, kk, splits, L, scan_scratch, pn, s, &grid));
+      MMF_TRY(launch_scan_b16(sp, splits, L, scan_scratch, pn, s, &grid));
     } else {
       // one launch per panel, each behind its own arrival event; the launches share the lists (disjoint
       // slots), the id scratch (they run one after the other) and the per-query thresholds
@@ -672,8 +673,8 @@ struct FastTail {
         pn.list_base = list_base;
         list_base += 2 * panel_splits[p];
         pn.seg_len = (uint32_t)P.seg_len; pn.seg_stride = (uint32_t)P.seg_stride; pn.id_off = (uint32_t)P.id_base;
-        MMF_TRY(launch_scan_b16(fo.ZQ, P.Z, P.cb, fo.q_zn, fo.q_rn, fo.q_un, fo.max_c, n, P.m, P.m_pad, fo.dp, r.d, fo.f16,
-                                r.metric, kk, panel_splits[p], L, scan_scratch, pn, s, &grid));
+        sp.ZC = P.Z; sp.cb = P.cb; sp.m = P.m; sp.m_pad = P.m_pad;
+        MMF_TRY(launch_scan_b16(sp, panel_splits[p], L, scan_scratch, pn, s, &grid));
         MMF_TRY(t_panel[p].stop(s));
       }
     }
@@ -851,42 +852,34 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
       int G = 0;
       if (symmetric_scan_wanted(n, dp, ft.bcap, metric, forced_splits, same && row_offset == col_offset, &G)) ft.set_symmetric(G);
     }
-    size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + ws_bytes((size_t)n_pad * dp, 2) + ws_bytes((size_t)m_pad * dp, 2) +
-                  4 * ws_bytes(n_pad, 4) + 4 * ws_bytes(m_pad, 4) + 3 * ws_bytes(4, 4) + ft.bytes();
+    // both images and both scalar vectors, shared or not, and max_n
+    const size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + HalfImage::bytes(n_pad, dp) + HalfImage::bytes(m_pad, dp) + ws_bytes(4, 4) +
+                        ft.bytes();
     Workspace ws;
     MMF_TRY(r.call.workspace(need, &ws));
-    float *rx, *cy, *q_zn, *q_rn, *q_un, *q_cb, *c_zn, *c_rn, *c_un, *c_cb;
-    uint16_t *ZQ, *ZC;
-    uint32_t *max_q, *max_c;
-    if (shared) {
-      const int64_t r0 = same ? 0 : slice0;
-      cy = ws.take<float>(m); rx = cy + r0;
-      ZC = ws.take<uint16_t>((size_t)m_pad * dp); ZQ = ZC + (size_t)r0 * dp;
-      c_zn = ws.take<float>(m_pad); c_rn = ws.take<float>(m_pad); c_un = ws.take<float>(m_pad); c_cb = ws.take<float>(m_pad);
-      q_zn = c_zn + r0; q_rn = c_rn + r0; q_un = c_un + r0; q_cb = c_cb + r0;
-      max_c = ws.take<uint32_t>(4); max_q = max_c;
-    } else {
-      rx = ws.take<float>(n); cy = ws.take<float>(m);
-      ZQ = ws.take<uint16_t>((size_t)n_pad * dp); ZC = ws.take<uint16_t>((size_t)m_pad * dp);
-      q_zn = ws.take<float>(n_pad); q_rn = ws.take<float>(n_pad); q_un = ws.take<float>(n_pad); q_cb = ws.take<float>(n_pad);
-      c_zn = ws.take<float>(m_pad); c_rn = ws.take<float>(m_pad); c_un = ws.take<float>(m_pad); c_cb = ws.take<float>(m_pad);
-      max_q = ws.take<uint32_t>(4); max_c = ws.take<uint32_t>(4);
-    }
+    // the candidate side is always carved; the query side is rows r0 .. of it (shared) or a carve of its own
+    const int64_t r0 = same ? 0 : slice0;
+    float* rx = shared ? nullptr : ws.take<float>(n);
+    float* cy = ws.take<float>(m);
+    HalfImage Q, C;
+    if (!shared) Q.carve(ws, n_pad, dp);
+    C.carve(ws, m_pad, dp);
+    if (shared) { rx = cy + r0; Q = C.from_row(r0, dp); }
     uint32_t* max_n = ws.take<uint32_t>(4);   // largest squared row norm over X and Y -> common scale
     ft.carve(ws);
-    MMF_HIP(hipMemsetAsync(max_c, 0, 16, s));
+    MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
     MMF_HIP(hipMemsetAsync(max_n, 0, 16, s));
-    if (!shared) MMF_HIP(hipMemsetAsync(max_q, 0, 16, s));
+    if (!shared) MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
 
     EventTimer t_prep;
     MMF_TRY(t_prep.start(r.profile, s));
     MMF_TRY(launch_row_scalars(Y, m, d, in_dtype, metric, cy, max_n, s));
     if (!shared) MMF_TRY(launch_row_scalars(X, n, d, in_dtype, metric, rx, max_n, s));
-    MMF_TRY(launch_prep_half(Y, m, d, in_dtype, metric, cy, max_n, ZC, m_pad, dp, f16 ? 1 : 0, c_zn, c_rn, c_un, c_cb, max_c, s));
-    if (!shared) MMF_TRY(launch_prep_half(X, n, d, in_dtype, metric, rx, max_n, ZQ, n_pad, dp, f16 ? 1 : 0, q_zn, q_rn, q_un, q_cb, max_q, s));
+    MMF_TRY(launch_prep_half({Y, m, d, in_dtype, metric, cy, max_n}, C, dp, f16, s));
+    if (!shared) MMF_TRY(launch_prep_half({X, n, d, in_dtype, metric, rx, max_n}, Q, dp, f16, s));
     MMF_TRY(t_prep.stop(s));
 
-    FastOperands fo{ZQ, ZC, rx, cy, q_zn, q_rn, q_un, c_cb, max_c, (m + 255) / 256 * 256, dp, f16};
+    FastOperands fo{Q, C, rx, cy, (m + 255) / 256 * 256, dp, f16};
     MMF_TRY(ft.run(r, fo, opts ? opts->select_wait_event : nullptr));
     if (stats) stats->prep_ms = t_prep.ms();
     return MMF_OK;
@@ -960,8 +953,8 @@ int mmf_prep_rows(const void* X, int64_t n, int64_t d, int in_dtype, int metric,
     set_error("prep_rows: NULL pointer"); return MMF_E_INVALID;
   }
   MMF_TRY(c.begin());
-  return launch_prep_half(X, n, d, in_dtype, metric, scal, reinterpret_cast<const uint32_t*>(max_sq_norm), Z, n_pad, dp,
-                          operand == MMF_F16 ? 1 : 0, zn, rn, un, cb, reinterpret_cast<uint32_t*>(maxima), c.s);
+  const HalfImage out{static_cast<uint16_t*>(Z), zn, rn, un, cb, reinterpret_cast<uint32_t*>(maxima), n_pad};
+  return launch_prep_half({X, n, d, in_dtype, metric, scal, reinterpret_cast<const uint32_t*>(max_sq_norm)}, out, dp, operand == MMF_F16, c.s);
 }
 
 int mmf_simtopk_prepared(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
@@ -983,8 +976,8 @@ int mmf_simtopk_prepared(const void* X, int64_t n, const void* Y, int64_t m, int
   Workspace ws;
   MMF_TRY(r.call.workspace(ft.bytes(), &ws));
   ft.carve(ws);
-  FastOperands fo{static_cast<const uint16_t*>(q->Z), static_cast<const uint16_t*>(c->Z), q->scal, c->scal, q->zn, q->rn, q->un,
-                  c->cb, reinterpret_cast<const uint32_t*>(maxima), m_pad, scan_bf16_dp(d), operand == MMF_F16};
+  FastOperands fo{HalfImage::of(*q, nullptr, ft.n_pad_q()), HalfImage::of(*c, maxima, m_pad), q->scal, c->scal, m_pad, scan_bf16_dp(d),
+                  operand == MMF_F16};
   return ft.run(r, fo, opts ? opts->select_wait_event : nullptr);
 }
 
@@ -1026,8 +1019,8 @@ int mmf_simtopk_panels(const void* X, int64_t n, const void* Y, int64_t m, int64
   Workspace ws;
   MMF_TRY(r.call.workspace(ft.bytes(), &ws));
   ft.carve(ws);
-  FastOperands fo{static_cast<const uint16_t*>(q->Z), nullptr, q->scal, c_scal, q->zn, q->rn, q->un,
-                  nullptr, reinterpret_cast<const uint32_t*>(maxima), 0, scan_bf16_dp(d), operand == MMF_F16};
+  const HalfImage none = HalfImage::of(mmf_prepared_side{}, maxima, 0);   // the candidate operands are the panels'; the maxima are those of all of them
+  FastOperands fo{HalfImage::of(*q, nullptr, ft.n_pad_q()), none, q->scal, c_scal, 0, scan_bf16_dp(d), operand == MMF_F16};
   fo.panels = panels; fo.n_panels = n_panels;
   return ft.run(r, fo, opts ? opts->select_wait_event : nullptr);
 }
@@ -1537,8 +1530,8 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
   const int64_t n_seed = n;
   size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + FlagBlock::bytes(n);
   if (grid > 0)
-    need += ws_bytes((size_t)nq_pad * dp, 2) + 4 * ws_bytes(nq_pad, 4) + ws_bytes((size_t)mc_pad * dp, 2) + 4 * ws_bytes(mc_pad, 4) +
-            3 * ws_bytes(4, 4) + ws_bytes(sched.size(), 4) + ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + b16_lists_bytes(n, 2, bcap) +
+    need += HalfImage::bytes(nq_pad, dp) + HalfImage::bytes(mc_pad, dp) + ws_bytes(4, 4) + ws_bytes(sched.size(), 4) +
+            ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + b16_lists_bytes(n, 2, bcap) +
             ws_bytes(scan_b16_seg_scratch_bytes(grid, dp, bcap), 1) + ws_bytes(2 * (size_t)n_seed, 4) + ws_bytes(select_order_bytes(n), 1);
   Workspace ws;
   MMF_TRY(r.call.workspace(need, &ws));
@@ -1559,11 +1552,9 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
   std::vector<int32_t> h_fail_rows;
   if (grid > 0) {
     const bool f16 = (precision == MMF_PREC_FAST);
-    uint16_t* ZQ = ws.take<uint16_t>((size_t)nq_pad * dp);
-    float *q_zn = ws.take<float>(nq_pad), *q_rn = ws.take<float>(nq_pad), *q_un = ws.take<float>(nq_pad), *q_cb = ws.take<float>(nq_pad);
-    uint16_t* ZC = ws.take<uint16_t>((size_t)mc_pad * dp);
-    float *c_zn = ws.take<float>(mc_pad), *c_rn = ws.take<float>(mc_pad), *c_un = ws.take<float>(mc_pad), *c_cb = ws.take<float>(mc_pad);
-    uint32_t *max_q = ws.take<uint32_t>(4), *max_c = ws.take<uint32_t>(4);
+    HalfImage Q, C;
+    Q.carve(ws, nq_pad, dp);
+    C.carve(ws, mc_pad, dp);
     int32_t* d_sched = ws.take<int32_t>(sched.size());
     int32_t* d_qg = ws.take<int32_t>(nq_pos);
     int32_t* d_cg = ws.take<int32_t>(mc_pos);
@@ -1574,12 +1565,10 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
     MMF_HIP(hipMemcpyAsync(d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice, s));
     MMF_HIP(hipMemcpyAsync(d_qg, qgather.data(), (size_t)nq_pos * 4, hipMemcpyHostToDevice, s));
     MMF_HIP(hipMemcpyAsync(d_cg, cgather.data(), (size_t)mc_pos * 4, hipMemcpyHostToDevice, s));
-    MMF_HIP(hipMemsetAsync(max_q, 0, 16, s));
-    MMF_HIP(hipMemsetAsync(max_c, 0, 16, s));
-    MMF_TRY(launch_prep_half_gather(Y, m, d, in_dtype, metric, cy, max_n, d_cg, ZC, mc_pos, mc_pad, dp, f16 ? 1 : 0, c_zn, c_rn,
-                                    c_un, c_cb, max_c, s));
-    MMF_TRY(launch_prep_half_gather(X, n, d, in_dtype, metric, rx, max_n, d_qg, ZQ, nq_pos, nq_pad, dp, f16 ? 1 : 0, q_zn, q_rn,
-                                    q_un, q_cb, max_q, s));
+    MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
+    MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
+    MMF_TRY(launch_prep_half_gather({Y, m, d, in_dtype, metric, cy, max_n}, d_cg, mc_pos, C, dp, f16, s));
+    MMF_TRY(launch_prep_half_gather({X, n, d, in_dtype, metric, rx, max_n}, d_qg, nq_pos, Q, dp, f16, s));
     MMF_TRY(t_prep.stop(s));
 
     // rows of segments the scan does not serve keep empty lists: the re-rank reports them, the exact pass below redoes them
@@ -1590,8 +1579,7 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
     ScanB16Panel pn;
     pn.seed = seed; pn.seed_stride = n_seed; pn.share = 0;
     MMF_TRY(t_scan.start(profile, s));
-    MMF_TRY(launch_scan_b16_seg(ZQ, ZC, c_cb, q_zn, q_rn, q_un, max_c, d_sched, grid, n, m, dp, d, f16, metric, r.kk, L,
-                                scan_scratch, pn, s));
+    MMF_TRY(launch_scan_b16_seg(ScanB16Problem(Q, C, n, m, mc_pad, dp, d, f16, metric, r.kk), d_sched, grid, L, scan_scratch, pn, s));
     MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
     MMF_TRY(t_scan.stop(s));
 

@@ -275,29 +275,63 @@ int launch_edge_cosine_impl(const void* X, int64_t d, int dtype, const float* nr
 int scan_bf16_supported(int64_t d, int kk, int dtype);
 int scan_bf16_cap(int kk, int dp);
 int scan_bf16_dp(int64_t d);
-int launch_prep_half(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
-                     const uint32_t* max_n, void* Z,
-                     int64_t n_pad, int dp, int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima,
-                     hipStream_t s);
-int launch_scan_b16(const void* ZQ, const void* ZC, const float* cb, const float* q_zn, const float* q_rn,
-                    const float* q_un, const uint32_t* maxima, int64_t n_rows, int64_t m, int64_t m_pad, int dp,
-                    int64_t d, bool f16, int metric, int kk, int col_splits, const CandLists& L, void* scratch,
-                    const ScanB16Panel& pn, hipStream_t s, int* grid_out);
+// The 16-bit operand image of one side: what launch_prep_half writes and the scan reads.  Z [n_pad][dp] operands, zn / rn / un
+// [n_pad] norms of the rounded row, of the rounding residual and of the row, cb [n_pad] per-candidate bias (-inf: padding),
+// maxima [4] float bits (max zn, max rn, max un, max |cb|; zeroed by the caller before the prep).
+struct HalfImage {
+  uint16_t* Z = nullptr;
+  float *zn = nullptr, *rn = nullptr, *un = nullptr, *cb = nullptr;
+  uint32_t* maxima = nullptr;
+  int64_t n_pad = 0;
+  static size_t bytes(int64_t n_pad, int dp) { return ws_bytes((size_t)n_pad * dp, 2) + 4 * ws_bytes(n_pad, 4) + ws_bytes(4, 4); }
+  void carve(Workspace& ws, int64_t n_pad_, int dp) {
+    n_pad = n_pad_;
+    Z = ws.take<uint16_t>((size_t)n_pad * dp);
+    zn = ws.take<float>(n_pad); rn = ws.take<float>(n_pad); un = ws.take<float>(n_pad); cb = ws.take<float>(n_pad);
+    maxima = ws.take<uint32_t>(4);
+  }
+  // rows r0 .. of this image as an image of their own (the queries of a row slice; they share the maxima)
+  HalfImage from_row(int64_t r0, int dp) const { return {Z + (size_t)r0 * dp, zn + r0, rn + r0, un + r0, cb + r0, maxima, n_pad - r0}; }
+  // a side the caller prepared (mmf_prep_rows): only ever read through the image
+  static HalfImage of(const mmf_prepared_side& p, const float* maxima, int64_t n_pad) {
+    return {static_cast<uint16_t*>(const_cast<void*>(p.Z)), const_cast<float*>(p.zn), const_cast<float*>(p.rn), const_cast<float*>(p.un),
+            const_cast<float*>(p.cb), reinterpret_cast<uint32_t*>(const_cast<float*>(maxima)), n_pad};
+  }
+};
+// the rows an image is made of: scal their canonical row scalars (launch_row_scalars), max_n the float bits of the largest
+// squared norm over both sides (unused for cosine)
+struct PrepRows { const void* X; int64_t n, d; int dtype, metric; const float* scal; const uint32_t* max_n; };
+int launch_prep_half(const PrepRows& r, const HalfImage& out, int dp, bool f16, hipStream_t s);
+// positions [0, n_pos) of the image are rows gather[pos] of X (-1: padding), positions [n_pos, n_pad) padding
+int launch_prep_half_gather(const PrepRows& r, const int32_t* gather, int64_t n_pos, const HalfImage& out, int dp, bool f16, hipStream_t s);
+
+// What every launch of the 16-bit scan needs: the query image (the scan reads Z / zn / rn / un of it), Z / cb / maxima of the
+// candidate side, and the shape.  m_pad: candidate rows covered by tiles (multiple of 256).
+struct ScanB16Problem {
+  const void* ZQ; const float *q_zn, *q_rn, *q_un;
+  const void* ZC; const float* cb; const uint32_t* maxima;
+  int64_t n_rows, m, m_pad;
+  int dp; int64_t d; bool f16; int metric, kk;
+  ScanB16Problem(const HalfImage& q, const HalfImage& c, int64_t n_rows_, int64_t m_, int64_t m_pad_, int dp_, int64_t d_, bool f16_,
+                 int metric_, int kk_)
+      : ZQ(q.Z), q_zn(q.zn), q_rn(q.rn), q_un(q.un), ZC(c.Z), cb(c.cb), maxima(c.maxima), n_rows(n_rows_), m(m_), m_pad(m_pad_),
+        dp(dp_), d(d_), f16(f16_), metric(metric_), kk(kk_) {}
+};
+// col_splits must be a power of two.  Lists are indexed by query position.
+int launch_scan_b16(const ScanB16Problem& p, int col_splits, const CandLists& L, void* scratch, const ScanB16Panel& pn, hipStream_t s,
+                    int* grid_out);
 int launch_scan_b16_audit(const ScanB16Panel& pn, uint32_t* overflow, int64_t n_rows, hipStream_t s);
 size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G);
-int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const float* rn, const float* un, const uint32_t* maxima,
-                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, bool live, bool forward, bool prune, bool tables,
-                        const CandLists& L, void* scratch, const SymBuffers& sb, const ScanB16Panel& pn, hipStream_t s, int* grid_out);
+// G: row blocks per super-block; live / forward / prune: MMF_SYMMETRIC_LIVE and MMF_SYMMETRIC_PRUNE as read by the caller;
+// tables: build and upload the two work tables (false: SymBuffers::sched still holds them)
+struct SymLaunch { int G; bool live, forward, prune, tables; };
+int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandLists& L, void* scratch, const SymBuffers& sb,
+                        const ScanB16Panel& pn, hipStream_t s, int* grid_out);
 size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap);
 int scan_bf16_slot_ulp(int cap);
 int scan_b16_queries_per_block(int dp);
-int launch_prep_half_gather(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
-                            const uint32_t* max_n, const int32_t* gather, void* Z, int64_t n_pos, int64_t n_pad, int dp,
-                            int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima, hipStream_t s);
 size_t scan_b16_seg_scratch_bytes(int64_t grid, int dp, int cap);
-int launch_scan_b16_seg(const void* ZQ, const void* ZC, const float* cb, const float* q_zn, const float* q_rn,
-                        const float* q_un, const uint32_t* maxima, const int32_t* sched, int64_t grid, int64_t n_rows,
-                        int64_t m, int dp, int64_t d, bool f16, int metric, int kk, const CandLists& L, void* scratch,
+int launch_scan_b16_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const CandLists& L, void* scratch,
                         const ScanB16Panel& pn, hipStream_t s);
 
 // mmf_dense.hip

@@ -912,23 +912,14 @@ int scan_bf16_cap(int kk, int dp) {
 int scan_bf16_slot_ulp(int cap) { return cap <= 16 ? 16 : 32; }
 int scan_bf16_dp(int64_t d) { return pad_dp(d); }
 
-int launch_prep_half_gather(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
-                            const uint32_t* max_n, const int32_t* gather, void* Z, int64_t n_pos, int64_t n_pad, int dp,
-                            int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima, hipStream_t s);
-
-int launch_prep_half(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
-                     const uint32_t* max_n, void* Z, int64_t n_pad, int dp, int z_f16, float* zn, float* rn,
-                     float* un, float* cb, uint32_t* maxima, hipStream_t s) {
-  return launch_prep_half_gather(X, n, d, dtype, metric, scal, max_n, nullptr, Z, n, n_pad, dp, z_f16, zn, rn, un, cb, maxima, s);
+int launch_prep_half(const PrepRows& r, const HalfImage& out, int dp, bool f16, hipStream_t s) {
+  return launch_prep_half_gather(r, nullptr, r.n, out, dp, f16, s);
 }
 
-// positions [0, n_pos) of Z are rows gather[pos] of X (-1: padding), positions [n_pos, n_pad) padding
-int launch_prep_half_gather(const void* X, int64_t n, int64_t d, int dtype, int metric, const float* scal,
-                            const uint32_t* max_n, const int32_t* gather, void* Z, int64_t n_pos, int64_t n_pad, int dp,
-                            int z_f16, float* zn, float* rn, float* un, float* cb, uint32_t* maxima, hipStream_t s) {
-  (void)n;
-  PrepArgs a{X, n_pos, d, dtype, metric, scal, max_n, Z, n_pad, dp, z_f16, zn, rn, un, cb, maxima, gather};
-  int64_t grid = (n_pad + 3) / 4;
+int launch_prep_half_gather(const PrepRows& r, const int32_t* gather, int64_t n_pos, const HalfImage& out, int dp, bool f16, hipStream_t s) {
+  PrepArgs a{r.X, n_pos, r.d, r.dtype, r.metric, r.scal, r.max_n, out.Z, out.n_pad, dp, f16 ? 1 : 0, out.zn, out.rn, out.un, out.cb,
+             out.maxima, gather};
+  int64_t grid = (out.n_pad + 3) / 4;
   if (grid > 1024) grid = 1024;          // 16 waves per CU; fewer, longer workgroups keep the final atomics few
   hipLaunchKernelGGL(prep_half_kernel, dim3((unsigned)grid), dim3(256), 0, s, a);
   MMF_LAUNCH_CHECK();
@@ -965,18 +956,19 @@ size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap) {
   return (size_t)scan_b16_grid(n_rows, col_splits, dp) * (cap <= 16 ? 16 : 32) * (64 * waves_for_dp(dp)) * 4 + 256;
 }
 
-template <int KS, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false>
+// SEG and SYM kernels have no instrumented build
+template <int KS, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0>
 static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_t s) {
-  const size_t lds = scan_b16_lds(KS, NW, TPB, CAP, SPLITK);
+  const size_t lds = scan_b16_lds(KS, NW, TPB, CAP, SPLITK, SYM == 2);
   auto go = [&](auto kern) -> int {
     MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * NW), lds, s, a);
     MMF_LAUNCH_CHECK();
     return MMF_OK;
   };
-  if constexpr (SEG) {
-    if (f16) return go(scan_b16x_kernel<KS, true, false, NW, TPB, CAP, SPLITK, true>);
-    return go(scan_b16x_kernel<KS, false, false, NW, TPB, CAP, SPLITK, true>);
+  if constexpr (SEG || SYM != 0) {
+    if (f16) return go(scan_b16x_kernel<KS, true, false, NW, TPB, CAP, SPLITK, SEG, SYM>);
+    return go(scan_b16x_kernel<KS, false, false, NW, TPB, CAP, SPLITK, SEG, SYM>);
   }
   if (a.debug != 0) {   // instrumented build of the same kernel (MMF_SCAN_DEBUG)
     if (f16) return go(scan_b16x_kernel<KS, true, true, NW, TPB, CAP, SPLITK>);
@@ -984,6 +976,30 @@ static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_
   }
   if (f16) return go(scan_b16x_kernel<KS, true, false, NW, TPB, CAP, SPLITK>);
   return go(scan_b16x_kernel<KS, false, false, NW, TPB, CAP, SPLITK>);
+}
+
+// (padded dim, list capacity) -> <KS, NW, TPB, CAP, SPLITK>, for the plain launch and (SEG) the table-driven one
+template <bool SEG>
+static int launch_b16_for(const char* who, int dp, int cap, const ScanB16Args& a, bool f16, int64_t grid, hipStream_t s) {
+  const bool big = (cap == B_CAP_BIG);   // k + self in 12..20: 16-entry lists, one tile per barrier
+  if (cap == B_CAP_WIDE) {               // k + self in 21..44: 32-entry lists, one tile per barrier, d <= 512
+    switch (dp) {
+      case 128: return launch_b16_t<8, 8, 1, B_CAP_WIDE, false, SEG>(a, f16, grid, s);
+      case 256: return launch_b16_t<16, 8, 1, B_CAP_WIDE, false, SEG>(a, f16, grid, s);
+      case 512: return launch_b16_t<32, 8, 1, B_CAP_WIDE, false, SEG>(a, f16, grid, s);
+    }
+    set_error("%s: 32-entry lists need a padded dim <= 512 (got %d)", who, dp);
+    return MMF_E_INTERNAL;
+  }
+  switch (dp) {
+    // d <= 256: the smaller tiles leave room for eight stages — four tiles per barrier (-1.5 % against two at d = 256)
+    case 128: return big ? launch_b16_t<8, 8, 2, B_CAP_BIG, false, SEG>(a, f16, grid, s) : launch_b16_t<8, 8, 4, B_CAP, false, SEG>(a, f16, grid, s);
+    case 256: return big ? launch_b16_t<16, 8, 2, B_CAP_BIG, false, SEG>(a, f16, grid, s) : launch_b16_t<16, 8, 4, B_CAP, false, SEG>(a, f16, grid, s);
+    case 512: return big ? launch_b16_t<32, 8, 1, B_CAP_BIG, false, SEG>(a, f16, grid, s) : launch_b16_t<32, 8, 2, B_CAP, false, SEG>(a, f16, grid, s);
+    case 1024: return launch_b16_t<64, 8, 1, B_CAP, true, SEG>(a, f16, grid, s);
+  }
+  set_error("%s: unsupported padded dim %d", who, dp);
+  return MMF_E_INTERNAL;
 }
 
 // Settles the audited losses of all scan launches of a problem (call once, after the last one).
@@ -994,33 +1010,43 @@ int launch_scan_b16_audit(const ScanB16Panel& pn, uint32_t* overflow, int64_t n_
   return MMF_OK;
 }
 
-// col_splits must be a power of two.  Lists are indexed by query position, cap = B_CAP.
-int launch_scan_b16(const void* ZQ, const void* ZC, const float* cb, const float* q_zn, const float* q_rn,
-                    const float* q_un, const uint32_t* maxima, int64_t n_rows, int64_t m, int64_t m_pad, int dp,
-                    int64_t d, bool f16, int metric, int kk, int col_splits, const CandLists& L, void* scratch,
-                    const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
+// What every launch shares: operands, shape, lists and threshold buffers.  One column range, the first list slots, no threshold
+// sharing, no work table; each launcher sets what is its own.
+static ScanB16Args scan_args(const ScanB16Problem& p, const CandLists& L, const ScanB16Panel& pn, void* scratch) {
   ScanB16Args a{};
-  a.ZQ = ZQ; a.ZC = ZC; a.cb = cb; a.q_zn = q_zn; a.q_rn = q_rn; a.q_un = q_un; a.maxima = maxima;
-  a.n_rows = n_rows; a.m = m; a.tiles_total = m_pad / B_CT;
+  a.ZQ = p.ZQ; a.ZC = p.ZC; a.cb = p.cb; a.q_zn = p.q_zn; a.q_rn = p.q_rn; a.q_un = p.q_un; a.maxima = p.maxima;
+  a.n_rows = p.n_rows; a.m = p.m; a.kk = p.kk; a.metric = p.metric; a.d = (int)p.d;
+  a.col_splits = 1; a.conc_splits = 1;
+  a.lists_total = L.lists;
+  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride;
+  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow; a.cand_keys = L.keys; a.margin_out = L.margin;
+  a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap; a.spill_stacks = L.spill_stacks;
+  a.lids = reinterpret_cast<uint32_t*>(scratch);
+  return a;
+}
+
+// col_splits must be a power of two.  Lists are indexed by query position.
+int launch_scan_b16(const ScanB16Problem& p, int col_splits, const CandLists& L, void* scratch, const ScanB16Panel& pn, hipStream_t s,
+                    int* grid_out) {
+  ScanB16Args a = scan_args(p, L, pn, scratch);
+  a.tiles_total = p.m_pad / B_CT;
   a.tiles_per_split = (a.tiles_total + col_splits - 1) / col_splits;
-  if (a.tiles_per_split * (int64_t)B_CT * dp * 2 >= (int64_t(1) << 32)) {   // 32-bit scalar offsets of the tile DMA
+  if (a.tiles_per_split * (int64_t)B_CT * p.dp * 2 >= (int64_t(1) << 32)) {   // 32-bit scalar offsets of the tile DMA
     set_error("scan_b16: a column range of %lld tiles x %d exceeds 4 GiB of operands; use more col_splits",
-              (long long)a.tiles_per_split, dp);
+              (long long)a.tiles_per_split, p.dp);
     return MMF_E_UNSUPPORTED;
   }
-  a.row_blocks = (n_rows + scan_b16_queries_per_block(dp) - 1) / scan_b16_queries_per_block(dp);
-  a.col_splits = col_splits; a.kk = kk; a.metric = metric; a.d = (int)d;
+  a.row_blocks = (p.n_rows + scan_b16_queries_per_block(p.dp) - 1) / scan_b16_queries_per_block(p.dp);
+  a.col_splits = col_splits;
   a.conc_splits = conc_splits_for(a.row_blocks, col_splits);
   a.blocks_per_round = scan_b16_round_blocks(a.row_blocks, a.conc_splits);
-  a.lists_total = L.lists; a.list_base = pn.list_base;
+  a.list_base = pn.list_base; a.share = pn.share;
   a.seg_len = pn.seg_len; a.seg_stride = pn.seg_stride; a.id_off = pn.id_off;
-  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride; a.share = pn.share;
   if (!pn.seed) { set_error("scan_b16: threshold buffers missing"); return MMF_E_INTERNAL; }
   if (pn.list_base + 2 * col_splits > L.lists) { set_error("scan_b16: list slots out of range"); return MMF_E_INTERNAL; }
   {
     const char* dbg = getenv("MMF_SCAN_DEBUG");
     a.debug = dbg ? atoi(dbg) : 0;
-    a.dbg = nullptr;
     if (a.debug & (8 | 16)) {
       static unsigned long long* dbuf = nullptr;
       if (!dbuf) MMF_HIP(hipMalloc(&dbuf, 128));
@@ -1028,30 +1054,9 @@ int launch_scan_b16(const void* ZQ, const void* ZC, const float* cb, const float
       a.dbg = dbuf;
     }
   }
-  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow; a.cand_keys = L.keys; a.margin_out = L.margin;
-  a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap;
-  a.spill_stacks = L.spill_stacks;
-  const int64_t grid = scan_b16_grid(n_rows, col_splits, dp);
-  a.lids = reinterpret_cast<uint32_t*>(scratch);
+  const int64_t grid = scan_b16_grid(p.n_rows, col_splits, p.dp);
   if (grid_out) *grid_out = (int)grid;
-  int rc = MMF_E_INTERNAL;
-  const bool big = (L.cap == B_CAP_BIG);   // k + self in 12..20: 16-entry lists, one tile per barrier
-  if (L.cap == B_CAP_WIDE) {               // k + self in 21..44: 32-entry lists, one tile per barrier, d <= 512
-    switch (dp) {
-      case 128: rc = launch_b16_t<8, 8, 1, B_CAP_WIDE>(a, f16, grid, s); break;
-      case 256: rc = launch_b16_t<16, 8, 1, B_CAP_WIDE>(a, f16, grid, s); break;
-      case 512: rc = launch_b16_t<32, 8, 1, B_CAP_WIDE>(a, f16, grid, s); break;
-      default: set_error("scan_b16: 32-entry lists need a padded dim <= 512 (got %d)", dp);
-    }
-  } else
-  switch (dp) {
-    // d <= 256: the smaller tiles leave room for eight stages — four tiles per barrier (-1.5 % against two at d = 256)
-    case 128: rc = big ? launch_b16_t<8, 8, 2, B_CAP_BIG>(a, f16, grid, s) : launch_b16_t<8, 8, 4, B_CAP>(a, f16, grid, s); break;
-    case 256: rc = big ? launch_b16_t<16, 8, 2, B_CAP_BIG>(a, f16, grid, s) : launch_b16_t<16, 8, 4, B_CAP>(a, f16, grid, s); break;
-    case 512: rc = big ? launch_b16_t<32, 8, 1, B_CAP_BIG>(a, f16, grid, s) : launch_b16_t<32, 8, 2, B_CAP>(a, f16, grid, s); break;
-    case 1024: rc = launch_b16_t<64, 8, 1, B_CAP, true>(a, f16, grid, s); break;
-    default: set_error("scan_b16: unsupported padded dim %d", dp);
-  }
+  const int rc = launch_b16_for<false>("scan_b16", p.dp, L.cap, a, p.f16, grid, s);
   if (rc == MMF_OK && (a.debug & 16)) {
     unsigned long long h[16];
     MMF_HIP(hipMemcpyAsync(h, a.dbg, 128, hipMemcpyDeviceToHost, s));
@@ -1074,51 +1079,20 @@ int launch_scan_b16(const void* ZQ, const void* ZC, const float* cb, const float
 
 // Segmented scan (mmf_simtopk_segmented): one workgroup per entry of the work table `sched` ([grid][SEG_ENTRY] int32,
 // device), one list pair per row (L.lists == 2), no threshold sharing.  The tables' tile ranges index the segment-padded
-// candidate image ZC / cb; ZQ / q_zn / q_rn / q_un are the segment-padded query image.  Same kernel as launch_scan_b16
-// with its schedule read from the table (template flag SEG: the production instantiations are untouched).
+// candidate image; the query image is segment-padded too.  Same kernel as launch_scan_b16 with its schedule read from the
+// table (template flag SEG: the production instantiations are untouched).
 size_t scan_b16_seg_scratch_bytes(int64_t grid, int dp, int cap) {
   return (size_t)grid * (cap <= 16 ? 16 : 32) * (64 * waves_for_dp(dp)) * 4 + 256;
 }
 
-int launch_scan_b16_seg(const void* ZQ, const void* ZC, const float* cb, const float* q_zn, const float* q_rn,
-                        const float* q_un, const uint32_t* maxima, const int32_t* sched, int64_t grid, int64_t n_rows,
-                        int64_t m, int dp, int64_t d, bool f16, int metric, int kk, const CandLists& L, void* scratch,
+int launch_scan_b16_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const CandLists& L, void* scratch,
                         const ScanB16Panel& pn, hipStream_t s) {
   if (grid <= 0) return MMF_OK;
   if (L.lists != 2) { set_error("scan_b16_seg: one list pair per row expected"); return MMF_E_INTERNAL; }
   if (!pn.seed) { set_error("scan_b16_seg: threshold buffers missing"); return MMF_E_INTERNAL; }
-  ScanB16Args a{};
-  a.ZQ = ZQ; a.ZC = ZC; a.cb = cb; a.q_zn = q_zn; a.q_rn = q_rn; a.q_un = q_un; a.maxima = maxima;
-  a.n_rows = n_rows; a.m = m; a.tiles_total = 0; a.tiles_per_split = 0;
-  a.row_blocks = 0; a.col_splits = 1; a.conc_splits = 1; a.blocks_per_round = 0;
-  a.kk = kk; a.metric = metric; a.d = (int)d;
-  a.lists_total = L.lists; a.list_base = 0;
-  a.seg_len = 0; a.seg_stride = 0; a.id_off = 0;
-  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride; a.share = 0;
-  a.debug = 0; a.dbg = nullptr;
-  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow; a.cand_keys = L.keys; a.margin_out = L.margin;
-  a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap;
-  a.spill_stacks = L.spill_stacks;
-  a.lids = reinterpret_cast<uint32_t*>(scratch);
+  ScanB16Args a = scan_args(p, L, pn, scratch);
   a.sched = sched;
-  int rc = MMF_E_INTERNAL;
-  const bool big = (L.cap == B_CAP_BIG);
-  if (L.cap == B_CAP_WIDE) {
-    switch (dp) {
-      case 128: rc = launch_b16_t<8, 8, 1, B_CAP_WIDE, false, true>(a, f16, grid, s); break;
-      case 256: rc = launch_b16_t<16, 8, 1, B_CAP_WIDE, false, true>(a, f16, grid, s); break;
-      case 512: rc = launch_b16_t<32, 8, 1, B_CAP_WIDE, false, true>(a, f16, grid, s); break;
-      default: set_error("scan_b16_seg: 32-entry lists need a padded dim <= 512 (got %d)", dp);
-    }
-  } else
-  switch (dp) {
-    case 128: rc = big ? launch_b16_t<8, 8, 2, B_CAP_BIG, false, true>(a, f16, grid, s) : launch_b16_t<8, 8, 4, B_CAP, false, true>(a, f16, grid, s); break;
-    case 256: rc = big ? launch_b16_t<16, 8, 2, B_CAP_BIG, false, true>(a, f16, grid, s) : launch_b16_t<16, 8, 4, B_CAP, false, true>(a, f16, grid, s); break;
-    case 512: rc = big ? launch_b16_t<32, 8, 1, B_CAP_BIG, false, true>(a, f16, grid, s) : launch_b16_t<32, 8, 2, B_CAP, false, true>(a, f16, grid, s); break;
-    case 1024: rc = launch_b16_t<64, 8, 1, B_CAP, true, true>(a, f16, grid, s); break;
-    default: set_error("scan_b16_seg: unsupported padded dim %d", dp);
-  }
-  return rc;
+  return launch_b16_for<true>("scan_b16_seg", p.dp, L.cap, a, p.f16, grid, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1220,61 +1194,45 @@ size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G) {
   return (size_t)sym_schedule_grid(nb, G) * 16 * 512 * 4 + 256;
 }
 
-// Both launches, the threshold image between them and the filing of the logs behind them, on stream s.  ZC is the operand
+// Both launches, the threshold image between them and the filing of the logs behind them, on stream s.  p.ZC is the operand
 // image of all rows (queries and candidates), n_pad / 32 tiles.  L has four lists per row (a pair per launch), keys, margins
-// and the sym_* lists; pn.seed as for launch_scan_b16.  live: the rows' workgroups keep raising the threshold image while the
-// symmetric launch runs; forward: its schedule looks ahead (sym_schedule_table).  tables: build the two work tables and
+// and the sym_* lists; pn.seed as for launch_scan_b16.  y.live: the rows' workgroups keep raising the threshold image while the
+// symmetric launch runs; y.forward: its schedule looks ahead (sym_schedule_table).  y.tables: build the two work tables and
 // upload them to sb.sched — they depend on (row blocks, G, forward) alone, so a caller whose sb.sched still holds them from
 // an earlier call on this stream passes false.  *grid_out: the sum of the two grids.
-int launch_scan_b16_sym(const void* ZC, const float* cb, const float* zn, const float* rn, const float* un, const uint32_t* maxima,
-                        int64_t n, int64_t d, bool f16, int metric, int kk, int G, bool live, bool forward, bool prune, bool tables,
-                        const CandLists& L, void* scratch, const SymBuffers& sb, const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
-  const int64_t nb = (n + 255) / 256, n_pad = nb * 256, grid = sym_schedule_grid(nb, G);
+int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandLists& L, void* scratch, const SymBuffers& sb,
+                        const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
+  const int64_t n = p.n_rows, nb = (n + 255) / 256, n_pad = nb * 256, grid = sym_schedule_grid(nb, y.G);
   // the SYM kernels neither fetch nor add the per-candidate bias: only metrics whose bias is zero for every real row may come here
-  if (metric != MMF_DOT && metric != MMF_COSINE) {
-    set_error("scan_b16_sym: metric %d has a per-candidate bias, which the symmetric kernels do not apply", metric);
+  if (p.metric != MMF_DOT && p.metric != MMF_COSINE) {
+    set_error("scan_b16_sym: metric %d has a per-candidate bias, which the symmetric kernels do not apply", p.metric);
     return MMF_E_INTERNAL;
   }
   if (L.lists != 4 || L.cap != B_CAP || !L.keys || !L.margin || !L.sym_cnt || !pn.seed) { set_error("scan_b16_sym: lists missing"); return MMF_E_INTERNAL; }
   if (n_pad * 1024 >= (int64_t(1) << 32)) { set_error("scan_b16_sym: operand image beyond the 32-bit tile offsets"); return MMF_E_INTERNAL; }
-  if (tables) {
+  if (y.tables) {
     std::vector<int32_t> tab((size_t)grid * 2 * SEG_ENTRY);
-    sym_schedule_table(nb, G, 0, tab.data(), forward);
-    sym_schedule_table(nb, G, 1, tab.data() + (size_t)grid * SEG_ENTRY, forward);
+    sym_schedule_table(nb, y.G, 0, tab.data(), y.forward);
+    sym_schedule_table(nb, y.G, 1, tab.data() + (size_t)grid * SEG_ENTRY, y.forward);
     MMF_TRY(upload_table(s, sb.sched, tab.data(), tab.size() * 4));
   }
   MMF_HIP(hipMemsetAsync(L.sym_cnt, 0, (size_t)n * 4, s));
   MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * L.lists * 4, s));   // with one or two super-blocks the second launch has no work and writes no list
   MMF_HIP(hipMemsetAsync(sb.log_cnt, 0, (size_t)grid * 8 * 4, s));
   MMF_HIP(hipMemsetAsync(sb.none_cnt, 0, 16, s));
-  ScanB16Args a{};
-  a.ZQ = ZC; a.ZC = ZC; a.cb = cb; a.q_zn = zn; a.q_rn = rn; a.q_un = un; a.maxima = maxima;
-  a.n_rows = n; a.m = n; a.tiles_total = n_pad / B_CT; a.tiles_per_split = 0;
-  a.row_blocks = nb; a.col_splits = 1; a.conc_splits = 1; a.blocks_per_round = 0;
-  a.kk = kk; a.metric = metric; a.d = (int)d;
-  a.lists_total = L.lists; a.list_base = 0;
-  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride; a.share = 0;
-  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow; a.cand_keys = L.keys; a.margin_out = L.margin;
-  a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap; a.spill_stacks = 0;
-  a.lids = reinterpret_cast<uint32_t*>(scratch);
+  ScanB16Args a = scan_args(p, L, pn, scratch);
+  a.ZQ = p.ZC;                                          // one image: the rows are queries and candidates
+  a.tiles_total = n_pad / B_CT; a.row_blocks = nb;
+  a.spill_stacks = 0;
   a.sched = sb.sched;
-  a.sym_thr = sb.thr; a.sym_live = live ? 1 : 0; a.sym_log = sb.log; a.sym_log_cnt = sb.log_cnt; a.sym_log_cap = kSymLogPerWave;
-  auto go = [&](auto kern, size_t lds) -> int {
-    MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, a);
-    MMF_LAUNCH_CHECK();
-    return MMF_OK;
-  };
-  const size_t lds_a = scan_b16_lds(32, 8, 2, B_CAP, false), lds_b = scan_b16_lds(32, 8, 2, B_CAP, false, true);
-  if (f16) MMF_TRY(go(scan_b16x_kernel<32, true, false, 8, 2, B_CAP, false, false, 1>, lds_a));
-  else MMF_TRY(go(scan_b16x_kernel<32, false, false, 8, 2, B_CAP, false, false, 1>, lds_a));
+  a.sym_thr = sb.thr; a.sym_live = y.live ? 1 : 0; a.sym_log = sb.log; a.sym_log_cnt = sb.log_cnt; a.sym_log_cap = kSymLogPerWave;
+  MMF_TRY((launch_b16_t<32, 8, 2, B_CAP, false, false, 1>(a, p.f16, grid, s)));
   hipLaunchKernelGGL(sym_thr_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, pn.seed, sb.thr, n, n_pad, sb.none_cnt);
   MMF_LAUNCH_CHECK();
   a.sched = sb.sched + (size_t)grid * SEG_ENTRY; a.list_base = 2; a.share = 1;
-  if (f16) MMF_TRY(go(scan_b16x_kernel<32, true, false, 8, 2, B_CAP, false, false, 2>, lds_b));
-  else MMF_TRY(go(scan_b16x_kernel<32, false, false, 8, 2, B_CAP, false, false, 2>, lds_b));
+  MMF_TRY((launch_b16_t<32, 8, 2, B_CAP, false, false, 2>(a, p.f16, grid, s)));
   hipLaunchKernelGGL(sym_scatter_kernel, dim3((unsigned)(grid * 8)), dim3(256), 0, s, sb.log, sb.log_cnt, kSymLogPerWave, L.sym_cnt,
-                     L.sym_ids, L.sym_keys, L.sym_cap, pn.seed + pn.seed_stride, prune ? pn.seed : nullptr, L.slot_ulp);
+                     L.sym_ids, L.sym_keys, L.sym_cap, pn.seed + pn.seed_stride, y.prune ? pn.seed : nullptr, L.slot_ulp);
   MMF_LAUNCH_CHECK();
   if (grid_out) *grid_out = (int)(2 * grid);
   return MMF_OK;

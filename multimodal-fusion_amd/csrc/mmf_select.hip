@@ -899,6 +899,26 @@ __global__ __launch_bounds__(64 * GR_W) void rerank_group_kernel(SelectArgs a) {
   }   // parts
 }
 
+// The staged re-rank kernel for (dtype, sg candidates per group) with its dynamic LDS bytes for maxc candidates per row, and the
+// same for the grouped re-rank: the one place the dtype picks an instantiation.
+struct StagedPick { void (*kern)(SelectArgs); size_t lds; };
+template <int METRIC, int SG>
+static StagedPick pick_staged_sg(int dtype, int maxc) {
+  return {dtype == MMF_F32 ? select_staged_kernel<METRIC, MMF_F32, SG>
+                           : (dtype == MMF_BF16 ? select_staged_kernel<METRIC, MMF_BF16, SG> : select_staged_kernel<METRIC, MMF_F16, SG>),
+          sizeof(float) * SEL_WAVES * (SG * SLD + SC) + (size_t)SEL_WAVES * maxc * 8};
+}
+template <int METRIC>
+static StagedPick pick_staged(int dtype, int sg, int maxc) {
+  return sg == 8 ? pick_staged_sg<METRIC, 8>(dtype, maxc) : (sg == 16 ? pick_staged_sg<METRIC, 16>(dtype, maxc) : pick_staged_sg<METRIC, 32>(dtype, maxc));
+}
+template <int METRIC>
+static StagedPick pick_group(int dtype) {
+  return {dtype == MMF_F32 ? rerank_group_kernel<METRIC, MMF_F32>
+                           : (dtype == MMF_BF16 ? rerank_group_kernel<METRIC, MMF_BF16> : rerank_group_kernel<METRIC, MMF_F16>),
+          sizeof(GroupLds)};
+}
+
 template <int METRIC>
 static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* order_temp, size_t order_temp_bytes, hipStream_t s) {
   const int64_t grid = (a.n_rows + SEL_WAVES - 1) / SEL_WAVES;
@@ -912,14 +932,8 @@ static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* 
       b.maxc = ((a.lists * a.cap + a.sym_cap + extra + 63) / 64) * 64;
       int sg = (extra == 0) ? 8 : 32;       // rows with overflow entries carry many candidates
       if (extra != 0) if (const char* e = getenv("MMF_SELECT_SG")) { const int v = atoi(e); if (v == 16 || v == 32) sg = v; }
-      auto kern = a.dtype == MMF_F32 ? select_staged_kernel<METRIC, MMF_F32, 8>
-                  : (a.dtype == MMF_BF16 ? select_staged_kernel<METRIC, MMF_BF16, 8> : select_staged_kernel<METRIC, MMF_F16, 8>);
-      if (sg == 16) kern = a.dtype == MMF_F32 ? select_staged_kernel<METRIC, MMF_F32, 16>
-                           : (a.dtype == MMF_BF16 ? select_staged_kernel<METRIC, MMF_BF16, 16> : select_staged_kernel<METRIC, MMF_F16, 16>);
-      if (sg == 32) kern = a.dtype == MMF_F32 ? select_staged_kernel<METRIC, MMF_F32, 32>
-                           : (a.dtype == MMF_BF16 ? select_staged_kernel<METRIC, MMF_BF16, 32> : select_staged_kernel<METRIC, MMF_F16, 32>);
-      const size_t lds = sizeof(float) * SEL_WAVES * (sg * SLD + SC) + (size_t)SEL_WAVES * b.maxc * 8;
-      MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      const StagedPick sp = pick_staged<METRIC>(a.dtype, sg, b.maxc);
+      MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sp.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.lds));
       int64_t g = grid;
       b.order_blocks = grid;
       if (pass == 1 && a.key_in) {
@@ -944,11 +958,10 @@ static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* 
         // grouped re-rank of 32 consecutive rows of that order on the matrix cores; what it leaves is done by the launch below
         if (a.done && (vec4 || staged16) && !getenv("MMF_SELECT_NO_GROUPS")) {
           MMF_HIP(hipMemsetAsync(a.done, 0, (size_t)a.n_rows, s));
-          auto gk = a.dtype == MMF_F32 ? rerank_group_kernel<METRIC, MMF_F32>
-                    : (a.dtype == MMF_BF16 ? rerank_group_kernel<METRIC, MMF_BF16> : rerank_group_kernel<METRIC, MMF_F16>);
-          MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(GroupLds)));
+          const StagedPick gp = pick_group<METRIC>(a.dtype);
+          MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gp.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gp.lds));
           const int64_t groups = ((a.n_rows + GR_Q - 1) / GR_Q + 7) / 8 * 8;
-          hipLaunchKernelGGL(gk, dim3((unsigned)groups), dim3(64 * GR_W), sizeof(GroupLds), s, b);
+          hipLaunchKernelGGL(gp.kern, dim3((unsigned)groups), dim3(64 * GR_W), gp.lds, s, b);
           MMF_LAUNCH_CHECK();
           if (g > 16384) g = 16384;                   // what is left, walked by a grid-stride loop
           // Few waiting rows (the group kernel left them all: scattered rows with a few dozen candidates each) are best served by
@@ -957,11 +970,9 @@ static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* 
           if (sg == 32) {
             SelectArgs c = b;
             c.only_if = 1;
-            auto k16 = a.dtype == MMF_F32 ? select_staged_kernel<METRIC, MMF_F32, 16>
-                       : (a.dtype == MMF_BF16 ? select_staged_kernel<METRIC, MMF_BF16, 16> : select_staged_kernel<METRIC, MMF_F16, 16>);
-            const size_t lds16 = sizeof(float) * SEL_WAVES * (16 * SLD + SC) + (size_t)SEL_WAVES * c.maxc * 8;
-            MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-            hipLaunchKernelGGL(k16, dim3((unsigned)g), dim3(64 * SEL_WAVES), lds16, s, c);
+            const StagedPick p16 = pick_staged<METRIC>(a.dtype, 16, c.maxc);
+            MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(p16.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p16.lds));
+            hipLaunchKernelGGL(p16.kern, dim3((unsigned)g), dim3(64 * SEL_WAVES), p16.lds, s, c);
             MMF_LAUNCH_CHECK();
             b.only_if = 2;
           }
@@ -972,7 +983,7 @@ static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* 
         b.key_sorted = nullptr;
         b.done = nullptr;
       }
-      hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(64 * SEL_WAVES), lds, s, b);
+      hipLaunchKernelGGL(sp.kern, dim3((unsigned)g), dim3(64 * SEL_WAVES), sp.lds, s, b);
       MMF_LAUNCH_CHECK();
     }
   } else if (vec4) hipLaunchKernelGGL((select_kernel<METRIC, true>), dim3((unsigned)grid), dim3(64 * SEL_WAVES), 0, s, a);
