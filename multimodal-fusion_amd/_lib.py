@@ -68,6 +68,10 @@ EXPORTS_POOL = ["mmf_segment_sort_segmented", "mmf_super_patches_segmented"]
 # tests/test_super_patch_stats_streamed_cpu.py.
 EXPORTS_STREAM = ["mmf_super_patch_stats_streamed", "mmf_super_patch_stats_streamed_bytes"]
 
+# The top-k entries (include/mmf_hg_topk.h): an addition to ABI version 3 in a header of its own, like the pooling
+# entries.  Its synchronisation behaviour is INTEGRATION.md's table "Top-k entries", pinned by tests/test_simtopk_combined_cpu.py.
+EXPORTS_TOPK = ["mmf_simtopk_combined"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -128,7 +132,9 @@ def lib() -> ctypes.CDLL:
     L.mmf_super_patches_segmented.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, ci, vp]
     L.mmf_super_patch_stats_streamed.argtypes = [vp, vp, i64, i64, i64, f32, f32, vp, vp, i64, i64, vp, vp, ci, vp]
     L.mmf_super_patch_stats_streamed_bytes.argtypes = [i64, i64, i64, i64, i64]
-    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM:
+    L.mmf_simtopk_combined.argtypes = [vp, vp, i64, i64, i64, f32, f32, ci, ci, vp, i64, vp, vp,
+                                       ctypes.POINTER(SimtopkOpts), ctypes.POINTER(SimtopkStats), ci, vp]
+    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK:
         fn = getattr(L, name)
         if name not in ("mmf_last_error", "mmf_padded_dim", "mmf_super_patch_stats_streamed_bytes"):
             fn.restype = ci

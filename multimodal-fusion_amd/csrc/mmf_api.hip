@@ -389,6 +389,8 @@ struct ExactPass {
   const int32_t* row_ids = nullptr;         // device: the rows of X that gathered groups name
   int64_t n_ids = 0;
   uint32_t* cand_total = nullptr;           // optional: the re-rank counts its candidates here
+  const float *P = nullptr, *pn = nullptr;  // optional (slices of X against itself only): rank by the exponent of K_h * K_g — positions
+  int dp = 0; float lambda_g = 0.0f;        //   [n][dp] and their chains; r.metric MMF_RBF, r.lambda = lambda_h (mmf_simtopk_combined)
   std::vector<ExactGroup> pieces;           // the groups, gathered ones in pieces of at most kBatch rows
   int64_t rows_total = 0; size_t list_words = 0; bool slices = false;
   int grid = 0;                             // out: scan workgroups (of each piece's last pass)
@@ -460,6 +462,10 @@ struct ExactPass {
       q.rx = sp.rx; q.cy = sp.cy; q.row_ids = sp.row_ids; q.n_rows = G.rows;
       q.out_idx += r0 * r.k; q.out_val += r0 * r.k; q.out_stride = r.k;
       q.fail_rows = B.fail_rows; q.fail_count = B.fail_count; q.cand_total = cand_total;
+      if (P) {
+        sp.Pq = q.Pq = P + r0 * dp; sp.Pc = q.Pc = P + G.col0 * dp; sp.pnq = q.pnq = pn + r0; sp.pnc = q.pnc = pn + G.col0;
+        sp.dp = q.dp = dp; sp.lambda_g = q.lambda_g = lambda_g;
+      }
       // k + self beyond 44: several passes, each offering only what ranks after the previous pass's last entry
       // (scikit-learn's n_neighbors is uncapped, preprocess_hypergraph.py:379)
       int g = 0;
@@ -472,7 +478,7 @@ struct ExactPass {
         if (t && one_pass) { MMF_TRY(t[1].stop(s)); MMF_TRY(t[2].start(r.profile, s)); }
         q.k = kp; q.out_off = done;
         q.floor_key_out = more ? B.floor_key : nullptr; q.floor_id_out = more ? B.floor_id : nullptr;
-        MMF_TRY(launch_select(q, L, s));
+        MMF_TRY(P ? launch_rerank_combined(q, L, s) : launch_select(q, L, s));
       }
       grid += g;
       used += G.rows;
@@ -764,6 +770,66 @@ struct FastTail {
     return MMF_OK;
   }
 };
+
+// mmf_simtopk_combined (include/mmf_hg_topk.h; entry and host checks in mmf_topk.hip): every segment is a slice of F against
+// itself through the exact pass, two launches per segment on the stream (DESIGN.md §4.7 "Exact rows", §4.14), one fail-count
+// readback at the end.  A segment with fewer than k admissible columns is ranked for what it has; the re-rank pads its rows.
+int run_simtopk_combined(const char* who, const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
+                         float lambda_g, int k, int exclude_self, const int64_t* ptr, int64_t n_seg, int64_t* out_idx, float* out_val,
+                         const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  Request r{Call(who, device_id, hip_stream), F, n, F, n, d, MMF_F32, MMF_RBF, lambda_h, k, exclude_self, 0, 0,
+            out_idx, out_val, stats, opts && opts->profile};
+  const int self1 = exclude_self ? 1 : 0;
+  r.kk = k + self1;
+  r.precision = MMF_PREC_EXACT;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  MMF_TRY(r.call.begin());
+  const hipStream_t s = r.call.s;
+  ExactPass ex(r, nullptr, nullptr);
+  ex.same = true;
+  ex.forced_splits = opts ? opts->col_splits : 0;
+  ex.P = P; ex.dp = (int)dp; ex.lambda_g = lambda_g;
+  std::vector<int64_t> bare;   // segments without an admissible column (one row, self excluded): -1 / -inf
+  for (int64_t g = 0; g < n_seg; ++g) {
+    const int64_t ng = ptr[g + 1] - ptr[g];
+    if (ng == 0) continue;
+    const int64_t ks = std::min<int64_t>(k, ng - self1);
+    if (ks > 0) ex.add(ExactGroup{ptr[g], ng, false, ptr[g], ng, (int)ks});
+    else bare.push_back(g);
+  }
+  const size_t need = 2 * ws_bytes(n, 4) + ws_bytes(256, 4) + (ex.pieces.empty() ? 0 : ex.image_bytes() + ex.list_bytes());
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* nf = ws.take<float>(n);
+  float* pn = ws.take<float>(n);
+  uint32_t* cand_total = ws.take<uint32_t>(256);
+  ex.rx = nf; ex.cy = nf; ex.pn = pn;
+  ex.cand_total = stats ? cand_total : nullptr;
+  for (int64_t g : bare) {
+    const int64_t ng = ptr[g + 1] - ptr[g];
+    MMF_HIP(hipMemsetAsync(out_idx + ptr[g] * k, 0xff, (size_t)ng * k * 8, s));
+    MMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out_val + ptr[g] * k), (int)0xff800000u, (size_t)ng * k, s));
+  }
+  if (ex.pieces.empty()) return MMF_OK;
+  ExactLists B;
+  B.carve(ws, ex.rows_total, ex.list_words, ex.cap(), false);
+  MMF_TRY(B.zero(s));
+  MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
+
+  // timers: prep (row scalars, f32 image), scan, re-rank for one graph; with several segments the launches alternate, and
+  // "scan" is the image and every segment's two launches
+  const bool one = ex.pieces.size() == 1;
+  EventTimer t[3];
+  MMF_TRY(t[0].start(r.profile, s));
+  MMF_TRY(launch_row_scalars(F, n, d, MMF_F32, MMF_RBF, nf, nullptr, s));
+  MMF_TRY(launch_row_scalars(P, n, dp, MMF_F32, MMF_RBF, pn, nullptr, s));
+  if (!one) { MMF_TRY(t[0].stop(s)); MMF_TRY(t[1].start(r.profile, s)); }
+  std::vector<uint32_t> h_tot(stats ? 256 : 0);
+  MMF_TRY(ex.run(ws, B, one ? t : nullptr, stats ? &h_tot : nullptr));
+  if (!one) MMF_TRY(t[1].stop(s));
+  fill_stats(stats, MMF_PREC_EXACT, ex.splits(ex.pieces[0]), ex.grid, t[0].ms(), t[1].ms(), t[2].ms(), 0.f, 0, 0, 0, h_tot);
+  return MMF_OK;
+}
 
 }  // namespace mmf
 

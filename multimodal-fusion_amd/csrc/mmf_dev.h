@@ -57,6 +57,25 @@ __device__ __forceinline__ float val_from_key(float key) {
   return key;
 }
 
+// The position term of the combined similarity K_h * K_g (similarity_kernel.py:79-84, 122) as an exponent:
+//   eg = neg_lambda_g * sq_from(chain(p_i,p_i), chain(p_j,p_j), chain(p_i,p_j)).
+// T >= dp terms of the chain, the terms beyond dp ZERO in both rows: fmaf(0, 0, acc) = acc, so every T gives the bits of the
+// dp-term chain (the f32 operand image pads its rows the same way).  ni / nj: the rows' chains from launch_row_scalars.
+// The one place the top-k of K_h * K_g forms this term: the scan's epilogue (mmf_scan_f32.hip) and the re-rank (mmf_topk.hip)
+// must agree bit for bit, because the scan's lists are truncated by the final order.
+template <int T>
+__device__ __forceinline__ float pos_exponent(const float* pi, const float* pj, float ni, float nj, float neg_lambda_g) {
+  float dot = 0.0f;
+#pragma unroll
+  for (int e = 0; e < T; ++e) dot = __builtin_fmaf(pi[e], pj[e], dot);
+  return neg_lambda_g * sq_from(ni, nj, dot);
+}
+// key and value of a pair of the combined similarity from its two exponents eh = (-lambda_h) sq_h, eg = (-lambda_g) sq_g:
+// ranked by the SUM of the exponents (one f32 add; the product underflows to 0 for most far pairs), reported as the entry
+// mmf_sim_dense_combined writes.
+__device__ __forceinline__ float combined_key(float eh, float eg) { return eh + eg; }
+__device__ __forceinline__ float combined_val(float eh, float eg) { return expf(eh) * expf(eg); }
+
 // element loads with exact upcast to f32
 __device__ __forceinline__ float ld_f32(const float* p, int64_t i) { return p[i]; }
 __device__ __forceinline__ float bf16_bits_to_f32(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }

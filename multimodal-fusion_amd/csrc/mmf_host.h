@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mmf_hg.h"
+#include "../../include/mmf_hg_topk.h"
 
 namespace mmf {
 
@@ -229,6 +230,11 @@ struct ScanProblem {
   int col_splits;
   const float* floor_key = nullptr;     // exact scan only: per query, offer only what ranks strictly after (floor_key, floor_id)
   const uint32_t* floor_id = nullptr;   //   in the total order — the later passes of a call with k + self > 44
+  // exact scan only, optional (Pc set): rank by the exponent of K_h * K_g (mmf_simtopk_combined) — positions [rows][dp] f32 of
+  // the query and candidate rows, chain(p, p) of each (launch_row_scalars), and lambda_g; metric MMF_RBF, lambda = lambda_h
+  const float *Pq = nullptr, *Pc = nullptr, *pnq = nullptr, *pnc = nullptr;
+  int dp = 0;
+  float lambda_g = 0.0f;
 };
 
 // mmf_scan_f32.hip: exact scan on v_mfma_f32_32x32x2_f32 (any d, f32/bf16/f16 inputs).
@@ -251,6 +257,10 @@ struct SelectProblem {
   void* order_scratch = nullptr;   // select_order_bytes(n_rows): that second launch walks its rows ordered by their smallest candidate id
   const int32_t* perm = nullptr;   // optional (row_ids must be null): list position -> row of X, a permutation of 0 .. n_rows - 1 — the scan
                                    // took its queries in that order (mmf_order.hip); X, rx, the outputs and fail_rows stay in row order
+  // launch_rerank_combined only: the position fields of ScanProblem
+  const float *Pq = nullptr, *Pc = nullptr, *pnq = nullptr, *pnc = nullptr;
+  int dp = 0;
+  float lambda_g = 0.0f;
 };
 size_t select_order_bytes(int64_t n);
 // mmf_order.hip: the order in which the 16-bit scan takes its query rows (near-duplicate rows next to each other)
@@ -263,6 +273,13 @@ int launch_query_order_apply(const uint16_t* ZQ, const float* q_zn, const float*
                              int dp, bool f16, void* scratch, uint16_t* Zo, float* zno, float* rno, float* uno, const int32_t** perm,
                              hipStream_t s);
 int launch_select(const SelectProblem& p, const CandLists& L, hipStream_t s);
+// mmf_topk.hip: the re-rank of the combined key over the exact scan's lists (f32 rows, no row_ids / perm / floors): key and value
+// recomputed with fmaf chains over F and P, ranked by counting under better(); k entries per row, then -1 / -inf up to out_stride
+int launch_rerank_combined(const SelectProblem& p, const CandLists& L, hipStream_t s);
+// mmf_api.hip: mmf_simtopk_combined behind its host checks (ptr: host offsets of n_seg >= 1 segments) — ExactPass over the segments
+int run_simtopk_combined(const char* who, const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h, float lambda_g,
+                         int k, int exclude_self, const int64_t* ptr, int64_t n_seg, int64_t* out_idx, float* out_val,
+                         const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream);
 // exact top-k of a few rows (p.row_ids) against every column, no candidate lists; keys: p.n_rows * p.m floats
 int launch_rows_exact(const SelectProblem& p, float* keys, hipStream_t s);
 int launch_topk_merge(const int64_t* ia, const float* va, const int64_t* ib, const float* vb,

@@ -30,6 +30,8 @@
 //           sklearn brute-force kneighbors, build_hypergraph/preprocess_hypergraph.py:379-382.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "mmf_dev.h"
 #include "mmf_host.h"
 
@@ -65,6 +67,9 @@ struct ScanF32Args {
   int64_t prow0;   // dense combined, panel form: query q of this launch is row prow0 + q of P
   int debug;   // MMF_F32_DEBUG (timing-only ablations): 1 skip epilogue, 2 skip staging
   const int64_t* sched;   // SEG kernels only: [grid][SEGF_ENTRY] work table (launch_sim_dense_combined_seg)
+  // COMB kernels only (the scan of K_h * K_g): P / dp / neg_lambda_g above are the CANDIDATES' positions; the queries' positions
+  // (row q of Pq is query row q) and chain(p, p) of the query and candidate rows
+  const float* Pq; const float* pnq; const float* pnc;
 };
 
 // Work table entry of the segmented dense combined similarity (one per workgroup): the segment, the image row of the row
@@ -75,9 +80,17 @@ enum { SEGF_SEG = 0, SEGF_ROW0 = 1, SEGF_NQ = 2, SEGF_CBASE = 3, SEGF_T0 = 4, SE
 // SEG (MODE_DENSE only, segmented calls): the row block, tile range, candidate base, output base and row stride come from the
 // work table a.sched instead of blockIdx / col_splits.  Tiles start at unaligned segment rows and read up to 127 rows past
 // them (the next segment, or the image's unwritten last block): those rows only reach masked outputs.
-template <int MODE, int CAP, int F_KC, bool SEG = false>
-__global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) void scan_f32_kernel(ScanF32Args a) {
+//
+// COMB (MODE_SCAN only, mmf_simtopk_combined): the key is the exponent of K_h * K_g, eh + eg (mmf_dev.h: pos_exponent,
+// combined_key).  A lane keeps its query's position (at most 8 floats, zero padded) and chain(p_i, p_i) in registers; the candidate
+// tile's positions and their chains ride into LDS beside cys with the tile's first chunk, clamped at m - 1 as cy is.  In the
+// epilogue the 32 lanes of a half read the same candidate's position (an LDS broadcast).  The chain, the DMA, the floor test and
+// LaneList are those of the plain scan; the other instantiations are untouched.  COMB asks for two workgroups per CU at every
+// capacity: that bounds the allocator at 256 registers (204 VGPRs, no AGPRs, nothing spilled); LDS decides how many run.
+template <int MODE, int CAP, int F_KC, bool SEG = false, bool COMB = false>
+__global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16 || COMB) ? 2 : 1) void scan_f32_kernel(ScanF32Args a) {
   static_assert(!SEG || MODE == MODE_DENSE, "the segmented form has the dense epilogue only");
+  static_assert(!COMB || MODE == MODE_SCAN, "the combined key is a scan epilogue");
   constexpr int UPR = F_KC / 4;            // 16-byte units per image row
   constexpr int RPP = 64 / UPR;            // image rows per 1 KiB DMA piece
   constexpr int HP = F_QT / RPP;           // pieces per operand tile (8 / 16)
@@ -90,6 +103,8 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
   float* cys = Cs + 2 * F_CT * F_KC;            // [2][F_CT] per-candidate scalars of the tile being accumulated
   float* lkeys = cys + 2 * F_CT;                // [CAP][F_NT]
   uint32_t* lids = reinterpret_cast<uint32_t*>(lkeys + CAP * F_NT);
+  float* pss = reinterpret_cast<float*>(lids + CAP * F_NT);   // COMB: [2][F_CT][8] candidate positions (zero beyond dp), as cys
+  float* pns = pss + 2 * F_CT * 8;                            // COMB: [2][F_CT] their chains
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -127,6 +142,18 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
   const bool floored = (MODE == MODE_SCAN) && a.floor_key != nullptr;
   const float fk = (floored && qvalid) ? a.floor_key[qpos] : 0.0f;
   const uint32_t fid = (floored && qvalid) ? a.floor_id[qpos] : 0u;
+  // COMB: this lane's position and its chain
+  float pq[8], pnq = 0.0f;
+  const float* Pc = nullptr; const float* pnc = nullptr; float nlg = 0.0f;
+  if constexpr (COMB) {
+    // uniform, but kept in vector registers: the list code under the epilogue has no scalar register to spare (in scalar
+    // registers these five words cost ten scalar spills inside LaneList::compact)
+    Pc = a.P; pnc = a.pnc; nlg = a.neg_lambda_g;
+    asm volatile("" : "+v"(Pc), "+v"(pnc), "+v"(nlg));
+#pragma unroll
+    for (int e = 0; e < 8; ++e) pq[e] = (qvalid && e < a.dp) ? a.Pq[qrow * a.dp + e] : 0.0f;
+    if (qvalid) pnq = a.pnq[qrow];
+  }
 
   // DENSE: the 16 query rows this lane's accumulator elements belong to (fixed for the workgroup's lifetime)
   float rq16[16];
@@ -157,12 +184,24 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
   const __amdgpu_buffer_rsrc_t qrsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Xp + q0 * a.dpad), 0, -1, 0x00020000);
   float rcy = 0.0f;
+  f32x4 rpp = {0.0f, 0.0f, 0.0f, 0.0f};   // COMB: floats 4 (tid & 1) .. + 3 of candidate tid >> 1's position
+  float rpn = 0.0f;                       // COMB: chain(p, p) of candidate tid
   // chunk kc of candidate tile ct -> stage `buf`; the tile's 128 per-candidate scalars ride along with its first chunk
   auto stage = [&](int64_t ct, int kc, int buf) {
     if (kc == 0 && tid < F_CT) {
       int64_t j = ct * F_CT + tid;
       if (j > m - 1) j = m - 1;
       rcy = a.cy[cbase + j];
+      if constexpr (COMB) rpn = pnc[cbase + j];
+    }
+    if constexpr (COMB) {
+      if (kc == 0) {
+        int64_t j = ct * F_CT + (tid >> 1);
+        if (j > m - 1) j = m - 1;
+        const int e0 = 4 * (tid & 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rpp[i] = (e0 + i < a.dp) ? Pc[(cbase + j) * a.dp + e0 + i] : 0.0f;
+      }
     }
     if (a.debug & 2) return;
     const __amdgpu_buffer_rsrc_t crsrc =
@@ -193,6 +232,10 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
   if (steps > 0) {
     stage(t_begin, 0, 0);
     if (tid < F_CT) cys[tid] = rcy;
+    if constexpr (COMB) {
+      *reinterpret_cast<f32x4*>(pss + 4 * tid) = rpp;
+      if (tid < F_CT) pns[tid] = rpn;
+    }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -281,7 +324,38 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
         const float* cyt = cys + tpar * F_CT + 32 * t + 4 * half;
         f32x16 key;
         // keys in three wave-uniform flavours (no per-element switch): dot | dot/(r*c) | nl*((r+c)-2dot)
-        if (metric == MMF_DOT) {
+        if constexpr (COMB) {
+          // nl_h*((r+c)-2dot) + nl_g*((pr+pc)-2pdot); the chain over the positions in 2, 4 or 8 terms (wave-uniform)
+          const float* pst = pss + (tpar * F_CT + 32 * t + 4 * half) * 8;
+          const float* pnt = pns + tpar * F_CT + 32 * t + 4 * half;
+          auto keys = [&](auto terms) {
+            constexpr int T = decltype(terms)::value;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              const f32x4 c4 = *reinterpret_cast<const f32x4*>(cyt + 8 * g);
+              const f32x4 n4 = *reinterpret_cast<const f32x4*>(pnt + 8 * g);
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                float pj[T];
+                if constexpr (T == 2) {
+                  const f32x2 v = *reinterpret_cast<const f32x2*>(pst + (8 * g + i) * 8);
+                  pj[0] = v[0]; pj[1] = v[1];
+                } else {
+#pragma unroll
+                  for (int u = 0; u < T; u += 4) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(pst + (8 * g + i) * 8 + u);
+                    pj[u] = v[0]; pj[u + 1] = v[1]; pj[u + 2] = v[2]; pj[u + 3] = v[3];
+                  }
+                }
+                const float eh = key_from_dot<MMF_RBF>(acc[t][4 * g + i], ri, c4[i], a.neg_lambda);
+                key[4 * g + i] = combined_key(eh, pos_exponent<T>(pq, pj, pnq, n4[i], nlg));
+              }
+            }
+          };
+          if (a.dp <= 2) keys(std::integral_constant<int, 2>{});
+          else if (a.dp <= 4) keys(std::integral_constant<int, 4>{});
+          else keys(std::integral_constant<int, 8>{});
+        } else if (metric == MMF_DOT) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) key[r] = acc[t][r];
         } else if (metric == MMF_COSINE) {
@@ -320,6 +394,13 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16) ? 2 : 1) vo
 
       }
     if (s + 1 < steps && nkcn == 0 && tid < F_CT) cys[(int)((nct - t_begin) & 1) * F_CT + tid] = rcy;
+    if constexpr (COMB) {
+      if (s + 1 < steps && nkcn == 0) {
+        const int par = (int)((nct - t_begin) & 1);
+        *reinterpret_cast<f32x4*>(pss + par * F_CT * 8 + 4 * tid) = rpp;
+        if (tid < F_CT) pns[par * F_CT + tid] = rpn;
+      }
+    }
     ct = nct; kc = nkcn;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of the next chunk have landed
     __syncthreads();
@@ -347,8 +428,9 @@ int scan_f32_cap(int kk) {
 static size_t scan_f32_lds(int cap, int kc) {
   return sizeof(float) * (2 * F_QT * kc + 2 * F_CT * kc + 2 * F_CT) + (size_t)cap * F_NT * 8;
 }
+constexpr size_t kScanPosLds = sizeof(float) * 2 * F_CT * 9;   // COMB: the tiles' positions and their chains
 
-template <int MODE, int CAP, bool SEG = false>
+template <int MODE, int CAP, bool SEG = false, bool COMB = false>
 static int launch_f32_t(const ScanF32Args& a, int64_t grid, hipStream_t s) {
   if (a.metric < MMF_DOT || a.metric > MMF_RBF) {
     set_error("scan_f32: unsupported metric %d", a.metric);
@@ -359,8 +441,8 @@ static int launch_f32_t(const ScanF32Args& a, int64_t grid, hipStream_t s) {
     return MMF_E_INTERNAL;
   }
   constexpr int KC = (MODE == MODE_SCAN) ? 16 : 32;
-  const size_t lds = scan_f32_lds(MODE == MODE_SCAN ? CAP : 0, KC);
-  auto kern = scan_f32_kernel<MODE, CAP, KC, SEG>;
+  const size_t lds = scan_f32_lds(MODE == MODE_SCAN ? CAP : 0, KC) + (COMB ? kScanPosLds : 0);
+  auto kern = scan_f32_kernel<MODE, CAP, KC, SEG, COMB>;
   MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(F_NT), lds, s, a);
   MMF_LAUNCH_CHECK();
@@ -381,6 +463,18 @@ int launch_scan_f32(const ScanProblem& p, const CandLists& L, hipStream_t s, int
   if (grid_out) *grid_out = (int)grid;
   a.metric = p.metric;
   { const char* e = getenv("MMF_F32_DEBUG"); a.debug = e ? atoi(e) : 0; }
+  if (p.Pc) {   // the combined key (mmf_simtopk_combined)
+    if (!p.Pq || !p.pnq || !p.pnc || p.dp < 1 || p.dp > 8 || p.metric != MMF_RBF || p.row_ids) {
+      set_error("scan_f32: combined key needs both sides' positions and chains, 1 <= dp <= 8 (got %d), MMF_RBF and no gathered rows", p.dp);
+      return MMF_E_INTERNAL;
+    }
+    a.P = p.Pc; a.Pq = p.Pq; a.pnq = p.pnq; a.pnc = p.pnc; a.dp = p.dp; a.neg_lambda_g = -p.lambda_g;
+    if (L.cap == 16) return launch_f32_t<MODE_SCAN, 16, false, true>(a, grid, s);
+    if (L.cap == 32) return launch_f32_t<MODE_SCAN, 32, false, true>(a, grid, s);
+    if (L.cap == 48) return launch_f32_t<MODE_SCAN, 48, false, true>(a, grid, s);
+    set_error("scan_f32: unsupported list capacity %d", L.cap);
+    return MMF_E_INTERNAL;
+  }
   if (L.cap == 16) return launch_f32_t<MODE_SCAN, 16>(a, grid, s);
   if (L.cap == 32) return launch_f32_t<MODE_SCAN, 32>(a, grid, s);
   if (L.cap == 48) return launch_f32_t<MODE_SCAN, 48>(a, grid, s);

@@ -1,0 +1,194 @@
+// mmf_topk.hip — mmf_simtopk_combined (include/mmf_hg_topk.h): the k best columns per row of the combined
+// similarity K = K_h * K_g (build_hypergraph/similarity_kernel.py:88-124) without the N x N matrix.
+//
+// The scan is the exact f32 scan with the combined key in its epilogue (mmf_scan_f32.hip, COMB); this file holds the re-rank
+// of its lists and the entry with its host checks.  The driver is the exact pass of mmf_api.hip (run_simtopk_combined).
+//
+// Re-rank: one wave per row.  The row's 2 x col_splits exact lists hold every column of its final top-(k + self) (they are
+// truncated by the final order, never by an approximation), so the wave recomputes key and value of each listed column with
+// the canonical fmaf chains over F and P — the same pos_exponent / combined_key as the scan, so the same bits — drops the
+// row itself by identity, and ranks by COUNTING: an entry's rank is the number of entries that beat it under better(), ranks
+// are distinct because a column sits in one list only, and every entry of rank < k writes itself.  No sort, no rounds of k.
+#include <math.h>
+#include <string.h>
+
+#include "mmf_dev.h"
+#include "mmf_host.h"
+
+namespace mmf {
+
+constexpr int RR_WAVES = 4;
+constexpr int RR_MAXC = 1024;   // candidates per row: 2 x col_splits x cap <= 1024 (pick_splits, mmf_api.hip)
+
+struct RerankCombinedArgs {
+  const float* X; const float* Y; int64_t d; int64_t m;   // query rows / candidate rows of F ([.][d] f32)
+  const float* rx; const float* cy;                       // their chains chain(f, f)
+  const float* Pq; const float* Pc; int dp;               // positions ([.][dp] f32)
+  const float* pnq; const float* pnc;                     // chain(p, p)
+  float neg_lambda_h, neg_lambda_g;
+  int k, out_stride, exclude_self;
+  int64_t row_offset, col_offset, n_rows;
+  const uint32_t* cand_cnt; const uint32_t* cand_ids; const uint32_t* overflow; int lists, cap;
+  int64_t* out_idx; float* out_val;
+  int32_t* fail_rows; uint32_t* fail_count; uint32_t* cand_total;
+};
+
+template <bool VEC4>
+__global__ __launch_bounds__(64 * RR_WAVES) void rerank_combined_kernel(RerankCombinedArgs a) {
+  __shared__ float skey[RR_WAVES][RR_MAXC];
+  __shared__ float sval[RR_WAVES][RR_MAXC];
+  __shared__ uint32_t sid[RR_WAVES][RR_MAXC];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * RR_WAVES + wave;
+  if (row >= a.n_rows) return;
+  float* key = skey[wave];
+  float* val = sval[wave];
+  uint32_t* id = sid[wave];
+
+  bool failed = a.overflow[row] != 0;
+  const bool was_overflow = failed;
+  int total = 0;
+  for (int l = 0; l < a.lists && !failed; ++l) {
+    const uint32_t cn = a.cand_cnt[row * a.lists + l];
+    if (cn > (uint32_t)a.cap || total + (int)cn > RR_MAXC) { failed = true; break; }
+    const int64_t base = (row * a.lists + l) * a.cap;
+    for (uint32_t e = lane; e < cn; e += 64) id[total + e] = a.cand_ids[base + e];
+    total += (int)cn;
+  }
+  const int64_t grow = a.row_offset + row;
+  int valid = 0;
+  if (!failed) {
+    __builtin_amdgcn_wave_barrier();
+    const float ri = a.rx[row], pni = a.pnq[row];
+    float pi[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) pi[e] = (e < a.dp) ? a.Pq[row * a.dp + e] : 0.0f;
+    for (int e = lane; e < total; e += 64) {
+      const uint32_t j = id[e];
+      const bool self = a.exclude_self && (a.col_offset + (int64_t)j == grow);
+      float kx = kNegInf, vx = kNegInf;
+      if (!self && (int64_t)j < a.m) {
+        float dot = 0.0f;
+        if constexpr (VEC4) {
+          const f32x4* xp = reinterpret_cast<const f32x4*>(a.X + row * a.d);
+          const f32x4* yp = reinterpret_cast<const f32x4*>(a.Y + (int64_t)j * a.d);
+          for (int64_t q = 0; q < (a.d >> 2); ++q) {
+            const f32x4 xv = xp[q], yv = yp[q];
+            dot = __builtin_fmaf(xv[0], yv[0], dot);
+            dot = __builtin_fmaf(xv[1], yv[1], dot);
+            dot = __builtin_fmaf(xv[2], yv[2], dot);
+            dot = __builtin_fmaf(xv[3], yv[3], dot);
+          }
+        } else {
+          for (int64_t q = 0; q < a.d; ++q) dot = __builtin_fmaf(a.X[row * a.d + q], a.Y[(int64_t)j * a.d + q], dot);
+        }
+        float pj[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) pj[u] = (u < a.dp) ? a.Pc[(int64_t)j * a.dp + u] : 0.0f;
+        const float eh = key_from_dot<MMF_RBF>(dot, ri, a.cy[j], a.neg_lambda_h);
+        const float eg = pos_exponent<8>(pi, pj, pni, a.pnc[j], a.neg_lambda_g);
+        kx = combined_key(eh, eg);
+        vx = combined_val(eh, eg);
+        if (kx != kx) kx = kNegInf;   // NaN keys rank last (undefined for non-finite inputs, as everywhere)
+        ++valid;
+      } else {
+        id[e] = kNoIdx;
+      }
+      key[e] = kx;
+      val[e] = vx;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) valid += __shfl_xor(valid, o);
+    if (valid < a.k) failed = true;
+  }
+  if (failed) {
+    if (lane == 0) {
+      const uint32_t slot = atomicAdd(a.fail_count, 1u);
+      a.fail_rows[slot] = (int32_t)row;
+      atomicAdd(a.fail_count + (was_overflow ? 1 : 2), 1u);   // reason counters, as select
+    }
+    return;
+  }
+  if (a.cand_total && lane == 0) atomicAdd(a.cand_total + (blockIdx.x & 255), (uint32_t)total);
+  __builtin_amdgcn_wave_barrier();
+  int64_t* oi = a.out_idx + row * a.out_stride;
+  float* ov = a.out_val + row * a.out_stride;
+  for (int e = lane; e < total; e += 64) {
+    const uint32_t ie = id[e];
+    if (ie == kNoIdx) continue;
+    const float ke = key[e];
+    int rank = 0;
+    for (int f = 0; f < total; ++f) {
+      const uint32_t jf = id[f];
+      rank += (jf != kNoIdx && better(key[f], jf, ke, ie)) ? 1 : 0;
+    }
+    if (rank < a.k) { oi[rank] = a.col_offset + (int64_t)ie; ov[rank] = val[e]; }
+  }
+  for (int t = a.k + lane; t < a.out_stride; t += 64) { oi[t] = -1; ov[t] = kNegInf; }
+}
+
+int launch_rerank_combined(const SelectProblem& p, const CandLists& L, hipStream_t s) {
+  if (p.n_rows <= 0) return MMF_OK;
+  if (p.dtype != MMF_F32 || p.row_ids || p.perm || p.floor_key_out || !p.Pq || !p.Pc || !p.pnq || !p.pnc || p.dp < 1 || p.dp > 8 ||
+      p.out_off != 0 || p.k < 1 || p.k > (p.out_stride ? p.out_stride : p.k) || L.lists * L.cap > RR_MAXC) {
+    set_error("rerank_combined: f32 rows in order, both sides' positions (1 <= dp <= 8), one pass, at most %d candidates per row", RR_MAXC);
+    return MMF_E_INTERNAL;
+  }
+  RerankCombinedArgs a{};
+  a.X = static_cast<const float*>(p.X); a.Y = static_cast<const float*>(p.Y); a.d = p.d; a.m = p.m;
+  a.rx = p.rx; a.cy = p.cy; a.Pq = p.Pq; a.Pc = p.Pc; a.dp = p.dp; a.pnq = p.pnq; a.pnc = p.pnc;
+  a.neg_lambda_h = -p.lambda; a.neg_lambda_g = -p.lambda_g;
+  a.k = p.k; a.out_stride = p.out_stride ? p.out_stride : p.k; a.exclude_self = p.exclude_self;
+  a.row_offset = p.row_offset; a.col_offset = p.col_offset; a.n_rows = p.n_rows;
+  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow; a.lists = L.lists; a.cap = L.cap;
+  a.out_idx = p.out_idx; a.out_val = p.out_val;
+  a.fail_rows = p.fail_rows; a.fail_count = p.fail_count; a.cand_total = p.cand_total;
+  const dim3 grid((unsigned)((p.n_rows + RR_WAVES - 1) / RR_WAVES));
+  const bool vec4 = (p.d % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.X) & 15) == 0) && ((reinterpret_cast<uintptr_t>(p.Y) & 15) == 0);
+  if (vec4) hipLaunchKernelGGL(rerank_combined_kernel<true>, grid, dim3(64 * RR_WAVES), 0, s, a);
+  else hipLaunchKernelGGL(rerank_combined_kernel<false>, grid, dim3(64 * RR_WAVES), 0, s, a);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
+}  // namespace mmf
+
+using namespace mmf;
+
+extern "C" {
+
+int mmf_simtopk_combined(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h, float lambda_g, int k,
+                         int exclude_self, const int64_t* ptr_host, int64_t n_segments, int64_t* out_idx, float* out_val,
+                         const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  const char* who = "simtopk_combined";
+  MMF_TRY(Call(who, device_id, hip_stream).on_device());
+  if (n < 0) { set_error("%s: n must be >= 0 (got %lld)", who, (long long)n); return MMF_E_INVALID; }
+  if (d < 1) { set_error("%s: d must be at least 1 (got %lld)", who, (long long)d); return MMF_E_INVALID; }
+  if (dp < 1) { set_error("%s: dp must be at least 1 (got %lld)", who, (long long)dp); return MMF_E_INVALID; }
+  if (k < 1) { set_error("%s: k must be at least 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (!(lambda_h >= 0.0f) || !isfinite(lambda_h)) { set_error("%s: lambda_h must be finite and >= 0 (got %g)", who, lambda_h); return MMF_E_INVALID; }
+  if (!(lambda_g >= 0.0f) || !isfinite(lambda_g)) { set_error("%s: lambda_g must be finite and >= 0 (got %g)", who, lambda_g); return MMF_E_INVALID; }
+  if (n > 0 && !F) { set_error("%s: F is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !P) { set_error("%s: P is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !out_idx) { set_error("%s: out_idx is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !out_val) { set_error("%s: out_val is NULL", who); return MMF_E_INVALID; }
+  const int64_t one_graph[2] = {0, n};
+  const bool segmented = ptr_host != nullptr || n_segments != 0;
+  if (segmented) MMF_TRY(check_offsets(who, "ptr_host", ptr_host, n_segments, 0, 0, n));
+  if (dp > 8) { set_error("%s: dp = %lld > 8 is not supported", who, (long long)dp); return MMF_E_UNSUPPORTED; }
+  const int kk = k + (exclude_self ? 1 : 0);
+  if (kk > 44) { set_error("%s: k + self = %d > 44 is not supported (the multi-pass floors are a follow-up)", who, kk); return MMF_E_UNSUPPORTED; }
+  if (n >= (int64_t)1 << 31) { set_error("%s: n must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  const int prec = opts ? opts->precision : MMF_PREC_AUTO;
+  if (prec != MMF_PREC_AUTO && prec != MMF_PREC_EXACT) {
+    set_error("%s: precision %d: only MMF_PREC_AUTO and MMF_PREC_EXACT (the 16-bit scan does not form this key)", who, prec);
+    return MMF_E_UNSUPPORTED;
+  }
+  if (opts && opts->col_splits < 0) { set_error("%s: col_splits must be >= 0 (got %d)", who, opts->col_splits); return MMF_E_INVALID; }
+  if (n == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return MMF_OK; }
+  return run_simtopk_combined(who, F, P, n, d, dp, lambda_h, lambda_g, k, exclude_self, segmented ? ptr_host : one_graph,
+                              segmented ? n_segments : 1, out_idx, out_val, opts, stats, device_id, hip_stream);
+}
+
+}  // extern "C"
