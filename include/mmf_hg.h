@@ -69,12 +69,14 @@ extern "C" {
  * (final keys are always the canonical f32 chain); the mode only picks which MFMA pipe scans
  * the N x M pairs. */
 #define MMF_PREC_AUTO  0  /* FAST when the 16-bit scan supports the shape (d <= 1024 and k + self <= 20, or
-                             d <= 512 and k + self <= 44), else EXACT (any d, any k: k + self > 44
+                             d <= 512 and k + self <= 44; in mmf_simtopk / mmf_simtopk_ex also 1024 < d <= 4096
+                             and k + self <= 20, the wide scan of mmf_hg_wide.h), else EXACT (any d, any k: k + self > 44
                              takes ceil(k / (44 - self)) passes, each ranked after the one before)  */
 #define MMF_PREC_EXACT 1  /* v_mfma_f32_32x32x2_f32 scan, canonical keys in-kernel           */
 #define MMF_PREC_FAST  2  /* f16 MFMA scan (rows scaled by an exact power of two) with a proven error
                              margin + exact f32 re-rank; columns inside a row's margin that do not fit its
-                             lists go to a per-row overflow list, rows that exhaust it are rescanned exactly */
+                             lists go to a per-row overflow list, rows that exhaust it are rescanned exactly
+                             (the wide scan for d > 1024 has no overflow list: such a row is rescanned exactly) */
 #define MMF_PREC_FAST_BF16 3 /* same with bf16 operands: 8x larger rounding residual, wider margin    */
 
 /* order in which the 16-bit scan takes its query rows (mmf_simtopk_opts.query_order).  A scan wave serves 32 consecutive
@@ -135,7 +137,7 @@ typedef struct mmf_simtopk_stats {
   float    fallback_ms;    /* exact rescans of overflowed rows (0 when none)                     */
   int64_t  candidates;     /* total candidates handed to the re-rank                            */
   int64_t  fallback_rows;  /* rows whose candidate list overflowed and were rescanned exactly    */
-  int      precision_used; /* MMF_PREC_EXACT or MMF_PREC_FAST                                    */
+  int      precision_used; /* MMF_PREC_EXACT, MMF_PREC_FAST or MMF_PREC_FAST_BF16: what scanned   */
   int      col_splits;     /* column ranges per row block actually used                         */
   int      scan_grid;      /* workgroups launched by the scan kernel (symmetric scan: the sum over its two launches) */
   float    scan_wait_ms;   /* paneled scan, profile = 1: part of scan_ms the stream spent waiting for panels'
@@ -147,6 +149,10 @@ typedef struct mmf_simtopk_stats {
   int      query_order;    /* 1: the scan took the queries with near-duplicate rows next to each other           */
 } mmf_simtopk_stats;
 
+/* opts->precision: MMF_PREC_FAST / _FAST_BF16 are served for d <= 1024 (k + self <= 20; <= 44 at d <= 512) and, through the
+ * wide scan (mmf_hg_wide.h), for 1024 < d <= 4096 with k + self <= 20; elsewhere they are refused with MMF_E_UNSUPPORTED
+ * ("does not support").  On the wide scan opts->query_order is ignored and col_splits is honoured up to one range per
+ * 128 columns. */
 int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d,
                    int in_dtype, int metric, float lambda, int k, int exclude_self,
                    int64_t row_offset, int64_t col_offset,

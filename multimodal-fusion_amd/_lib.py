@@ -72,6 +72,10 @@ EXPORTS_STREAM = ["mmf_super_patch_stats_streamed", "mmf_super_patch_stats_strea
 # entries.  Its synchronisation behaviour is INTEGRATION.md's table "Top-k entries", pinned by tests/test_simtopk_combined_cpu.py.
 EXPORTS_TOPK = ["mmf_simtopk_combined"]
 
+# The wide-scan queries (include/mmf_hg_wide.h): an addition to ABI version 3 in a header of its own.  Host-only:
+# they take neither a device nor a stream.
+EXPORTS_WIDE = ["mmf_wide_scan_supported", "mmf_wide_scan_list_capacity"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -134,7 +138,9 @@ def lib() -> ctypes.CDLL:
     L.mmf_super_patch_stats_streamed_bytes.argtypes = [i64, i64, i64, i64, i64]
     L.mmf_simtopk_combined.argtypes = [vp, vp, i64, i64, i64, f32, f32, ci, ci, vp, i64, vp, vp,
                                        ctypes.POINTER(SimtopkOpts), ctypes.POINTER(SimtopkStats), ci, vp]
-    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK:
+    L.mmf_wide_scan_supported.argtypes = [i64, ci, ci]
+    L.mmf_wide_scan_list_capacity.argtypes = [ci, ci]
+    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE:
         fn = getattr(L, name)
         if name not in ("mmf_last_error", "mmf_padded_dim", "mmf_super_patch_stats_streamed_bytes"):
             fn.restype = ci

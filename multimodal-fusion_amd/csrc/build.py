@@ -18,9 +18,10 @@ PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 OUT = os.path.join(PKG, "libmmf_hg.so")
 OBJ = os.path.join(HERE, "_obj")
-SOURCES = ["mmf_api.hip", "mmf_prep.hip", "mmf_scan_f32.hip", "mmf_scan_bf16.hip", "mmf_select.hip", "mmf_edges.hip", "mmf_segments.hip", "mmf_knn_clique.hip", "mmf_direct.hip", "mmf_kmeans.hip", "mmf_order.hip", "mmf_pool.hip", "mmf_stream_stats.hip", "mmf_topk.hip"]
+SOURCES = ["mmf_api.hip", "mmf_prep.hip", "mmf_scan_f32.hip", "mmf_scan_bf16.hip", "mmf_scan_b16w.hip", "mmf_select.hip", "mmf_edges.hip", "mmf_segments.hip", "mmf_knn_clique.hip", "mmf_direct.hip", "mmf_kmeans.hip", "mmf_order.hip", "mmf_pool.hip", "mmf_stream_stats.hip", "mmf_topk.hip"]
 HEADERS = ["mmf_dev.h", "mmf_host.h", os.path.join(ROOT, "include", "mmf_hg.h"), os.path.join(ROOT, "include", "mmf_hg_pool.h"),
-           os.path.join(ROOT, "include", "mmf_hg_stream.h"), os.path.join(ROOT, "include", "mmf_hg_topk.h")]
+           os.path.join(ROOT, "include", "mmf_hg_stream.h"), os.path.join(ROOT, "include", "mmf_hg_topk.h"),
+           os.path.join(ROOT, "include", "mmf_hg_wide.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]
@@ -29,7 +30,8 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++
 # kernel); together with the out-of-line list path the exact f32 scan went from 54.0 to 49.3 ms at N = 65536 (same-
 # process A/B).  Non-finite inputs are outside the numerics contract; infinities are still honoured
 # (-inf is the padding bias and the "no key" marker).
-EXTRA_FLAGS = {"mmf_scan_bf16.hip": ["-fno-honor-nans"], "mmf_scan_f32.hip": ["-fno-honor-nans"]}
+EXTRA_FLAGS = {"mmf_scan_bf16.hip": ["-fno-honor-nans"], "mmf_scan_f32.hip": ["-fno-honor-nans"],
+               "mmf_scan_b16w.hip": ["-fno-honor-nans"]}
 
 
 def _newer(target: str, deps) -> bool:

@@ -203,6 +203,11 @@ static int64_t admissible_columns(int64_t r0, int64_t n, int64_t c0, int64_t m, 
   return m - (o ? 1 : 0);
 }
 
+// What MMF_PREC_AUTO does where only the wide 16-bit scan applies (1024 < d <= 4096, k + self <= 20): it takes it.  Measured
+// (profiles/wide_scan_timing.txt): the whole call is 4.6x / 4.3x faster than the exact scan at N = 16384 /
+// 65536, d = 1536 — 125 and 431 times the exact arm's spread, where the rule asks for three.
+static bool wide_scan_auto() { return true; }
+
 // One simtopk call: its prologue (`call`), its arguments, and what check() derives from them.
 struct Request {
   Call call;
@@ -211,6 +216,8 @@ struct Request {
   int64_t* out_idx; float* out_val; mmf_simtopk_stats* stats; bool profile;
   int kk = 0;                       // entries a row's lists keep: k, + 1 when self is excluded
   int precision = MMF_PREC_AUTO;    // resolved: MMF_PREC_EXACT, _FAST or _FAST_BF16
+  bool wide_ok = false;             // the entry has the wide 16-bit scan (mmf_scan_b16w.hip) behind it: mmf_simtopk / _ex only
+  bool wide = false;                // resolved: the 16-bit scan of this call is the wide one (1024 < d <= 4096)
 
   // The checks every simtopk entry makes, in this order: device / shapes / dtype, metric, lambda, k, the entry's own
   // (`entry_checks`); stats zeroed; then, when there are rows: outputs, admissible columns (of the whole block unless
@@ -234,9 +241,12 @@ struct Request {
       return MMF_E_INVALID;
     }
     MMF_TRY(call.begin());
-    const bool b16 = scan_bf16_supported(d, kk, dtype);
-    precision = prec == MMF_PREC_AUTO ? (b16 ? MMF_PREC_FAST : MMF_PREC_EXACT) : prec;
+    const bool narrow = scan_bf16_supported(d, kk, dtype);
+    const bool b16 = narrow || (wide_ok && scan_b16w_supported(d, kk));
+    // AUTO: the register-resident 16-bit scan where it applies; the wide one only where wide_scan_auto() says it pays
+    precision = prec == MMF_PREC_AUTO ? ((narrow || (b16 && wide_scan_auto())) ? MMF_PREC_FAST : MMF_PREC_EXACT) : prec;
     if (precision != MMF_PREC_EXACT && precision != MMF_PREC_FAST && precision != MMF_PREC_FAST_BF16) { set_error("%s: bad precision %d", who, precision); return MMF_E_INVALID; }
+    wide = precision != MMF_PREC_EXACT && !narrow && b16;
     if (precision != MMF_PREC_EXACT && !b16) {
       set_error("%s: MMF_PREC_FAST does not support d = %lld, k = %d (AUTO takes the exact scan there)", who, (long long)d, k);
       return MMF_E_UNSUPPORTED;
@@ -519,7 +529,7 @@ struct FastTail {
   int set_query_order(int mode) {   // before bytes() / carve()
     if (mode < MMF_QUERY_ORDER_AUTO || mode > MMF_QUERY_ORDER_ON) { set_error("simtopk: bad query_order %d", mode); return MMF_E_INVALID; }
     order_mode = mode;
-    order_try = mode == MMF_QUERY_ORDER_ON || (mode == MMF_QUERY_ORDER_AUTO && n >= 32768 && m >= 32768);
+    order_try = !wide && (mode == MMF_QUERY_ORDER_ON || (mode == MMF_QUERY_ORDER_AUTO && n >= 32768 && m >= 32768));
     return MMF_OK;
   }
 
@@ -545,6 +555,7 @@ struct FastTail {
   }
 
   int dp, panels;
+  bool wide = false;   // dp > 1024: launch_scan_b16w takes the slot of launch_scan_b16 (no query order, symmetric scan or panels)
   int panel_splits[16]; int max_splits = 1;
   int64_t n_seed;
   int32_t* seed = nullptr;
@@ -556,10 +567,12 @@ struct FastTail {
   FastTail(int64_t n_, int64_t m_, int kk_, int forced_splits, int dp_, int panels_ = 1, int64_t m_panel_min = -1,
            int64_t m_panel_max = -1)
       : n(n_), m(m_), kk(kk_), cap(scan_f32_cap(kk_)), dp(dp_), panels(panels_) {
-    bcap = scan_bf16_cap(kk, dp);
-    const int qt = scan_b16_queries_per_block(dp);
+    wide = dp > 1024;   // the wide kernel's sizes: its list capacity, 128 queries per workgroup, column tiles of 128, no id scratch
+    bcap = wide ? scan_b16w_cap(kk) : scan_bf16_cap(kk, dp);
+    const int qt = wide ? scan_b16w_queries_per_block() : scan_b16_queries_per_block(dp);
     if (m_panel_min < 0) m_panel_min = m;
-    const int64_t row_blocks = (n + qt - 1) / qt, col_tiles = ((m_panel_min + 255) / 256 * 256) / 32;
+    const int64_t row_blocks = (n + qt - 1) / qt;
+    const int64_t col_tiles = wide ? (m_panel_min + scan_b16w_col_tile() - 1) / scan_b16w_col_tile() : ((m_panel_min + 255) / 256 * 256) / 32;
     n_seed = row_blocks * qt;
     splits = 1;
     if (forced_splits > 0) { while (splits < forced_splits) splits <<= 1; }
@@ -600,6 +613,7 @@ struct FastTail {
     fb_splits = pick_splits((FB + 127) / 128, (m + 127) / 128, cap, 0);
   }
   size_t scan_scratch_bytes() const {
+    if (wide) return 256;
     const size_t a = scan_b16_scratch_bytes(n, max_splits, dp, bcap), b = sym_try ? scan_b16_sym_scratch_bytes(n, sym_G) : 0;
     return a > b ? a : b;
   }
@@ -667,7 +681,8 @@ struct FastTail {
                                   pn, s, &grid));
       if (sym_keep) *sym_keep = tables;
     } else if (fo.n_panels == 0) {
-      MMF_TRY(launch_scan_b16(sp, splits, L, scan_scratch, pn, s, &grid));
+      if (wide) MMF_TRY(launch_scan_b16w(sp, splits, L, pn, s, &grid));
+      else MMF_TRY(launch_scan_b16(sp, splits, L, scan_scratch, pn, s, &grid));
     } else {
       // one launch per panel, each behind its own arrival event; the launches share the lists (disjoint
       // slots), the id scratch (they run one after the other) and the per-query thresholds
@@ -890,6 +905,7 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
   if (!Y) { Y = X; m = n; }
   Request r{Call("simtopk", device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset,
             out_idx, out_val, stats, opts && opts->profile};
+  r.wide_ok = true;
   MMF_TRY(r.check(opts ? opts->precision : MMF_PREC_AUTO, false, [] { return MMF_OK; }));
   if (n == 0) return MMF_OK;
   const hipStream_t s = r.call.s;
@@ -898,7 +914,7 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
 
   if (r.precision != MMF_PREC_EXACT) {
     // ---- fast path: f16/bf16 MFMA scan -> exact re-rank -> exact rescan of overflowed rows -------
-    const int dp = scan_bf16_dp(d);
+    const int dp = r.wide ? scan_b16w_dp(d) : scan_bf16_dp(d);
     const bool f16 = (r.precision == MMF_PREC_FAST);   // operand type of the scan, not of the input
     // X a row-slice of Y (the row-sharded multi-GPU case passes full[lo:hi] and full): every query-side
     // buffer is then a view into the candidate-side one and only Y is prepared.
@@ -987,6 +1003,16 @@ int mmf_simtopk(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, i
 }
 
 int64_t mmf_padded_dim(int64_t d) { return (int64_t)scan_bf16_dp(d); }
+
+int mmf_wide_scan_supported(int64_t d, int k, int exclude_self) {
+  if (d < 1 || k < 1) return 0;
+  return scan_b16w_supported(d, k + (exclude_self ? 1 : 0));
+}
+
+int mmf_wide_scan_list_capacity(int k, int exclude_self) {
+  const int kk = k + (exclude_self ? 1 : 0);
+  return (k >= 1 && kk <= 20) ? scan_b16w_cap(kk) : 0;
+}
 
 int mmf_fast_scan_supported(int64_t d, int k, int exclude_self) {
   if (d < 1 || k < 1) return 0;

@@ -12,6 +12,7 @@
 
 #include "../../include/mmf_hg.h"
 #include "../../include/mmf_hg_topk.h"
+#include "../../include/mmf_hg_wide.h"
 
 namespace mmf {
 
@@ -350,6 +351,16 @@ int scan_b16_queries_per_block(int dp);
 size_t scan_b16_seg_scratch_bytes(int64_t grid, int dp, int cap);
 int launch_scan_b16_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const CandLists& L, void* scratch,
                         const ScanB16Panel& pn, hipStream_t s);
+
+// mmf_scan_b16w.hip: the wide 16-bit scan (1024 < d <= 4096, k + self <= 20) — both operands streamed through
+// LDS in k-chunks.  Same operand images (dp = d rounded up to 128), lists, threshold buffers and audit as launch_scan_b16; no
+// id scratch, no overflow lists, no panels, no shared thresholds.  col_splits must be a power of two, L.lists == 2 * col_splits.
+int scan_b16w_supported(int64_t d, int kk);
+int scan_b16w_cap(int kk);
+int scan_b16w_dp(int64_t d);
+int scan_b16w_queries_per_block();
+int scan_b16w_col_tile();
+int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L, const ScanB16Panel& pn, hipStream_t s, int* grid_out);
 
 // mmf_dense.hip
 // Xp / Yp: f32 images of X and Y (launch_prep_f32; unused — may be null — for d <= 8 and MMF_RBF_DIRECT)

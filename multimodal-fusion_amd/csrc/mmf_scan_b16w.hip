@@ -1,0 +1,502 @@
+// mmf_scan_b16w.hip — the WIDE 16-bit scan: f16 / bf16 MFMA candidate generation for feature dims above 1024
+// (1024 < d <= 4096, k + self <= 20), where the register-resident scan of mmf_scan_bf16.hip stops.  DESIGN.md §4.15.
+//
+// scan_b16x_kernel keeps a wave's 32 queries in registers (128 VGPRs at d = 512, split-k wave pairs up to 1024); here
+// nothing is resident.  The structure is scan_f32_kernel's: a workgroup = 4 waves owns a macro tile of 128 queries x 128
+// candidates, BOTH operands stream through LDS in k-chunks of 64 halves (128 bytes per row, 32 KiB per stage), double
+// buffered, one barrier per chunk, and the epilogue runs once per macro tile after the whole d — the larger d is, the less
+// it weighs.
+//   * Operands are the 16-bit images of launch_prep_half, unchanged, with dp = d rounded up to 128 (pad rows: zeros, bias
+//     -inf, so a padding column never reaches a list and no column needs a bounds test).
+//   * Staging is buffer-form LDS-DMA, 1 KiB (8 rows x 128 B) per wave instruction, 8 per wave and chunk; LDS stays
+//     lane-linear and the 16-byte unit u of tile row r is fetched to unit u ^ ((r >> 1) & 7) — the XOR on the SOURCE
+//     address — so the 16 lanes of a ds_read_b128 group (16 rows, one unit) hit 16 distinct bank quads.
+//   * v_mfma_f32_16x16x32_{f16,bf16}: wave w owns queries 32 w .. 32 w + 31 (B operand, two 16-query blocks) and sweeps the
+//     tile's 128 candidates (A operand, eight 16-row blocks): 16 accumulator tiles, 64 VGPRs, initialised with the
+//     candidates' bias cb_j (-n_j / 2 for the L2 metrics, -inf for padding).  C layout as in mmf_scan_bf16.hip: lane l holds
+//     column l & 15, rows 4 (l >> 4) + {0..3}, i.e. TWO queries x 4 candidates per tile; the list code keeps "one lane = one
+//     query, 16 of every 32 candidates": lane l owns query (l & 15) + 16 ((l >> 4) & 1) and, on the rare slow path, swaps
+//     with lane l ^ 16 the values they hold for each other's query.  Lanes l and l ^ 32 own the two halves of one query.
+//   * Lists (WideList below): approximate key AND column id in LDS, 8 bytes per entry, CAP = 16 (k + self <= 11) or 32
+//     (k + self in 12..20) entries per lane.  No overflow lists: a crowded row is flagged and the exact rescan answers it.
+//
+// Error margin (the formula of mmf_scan_bf16.hip with KS * 16 read as dp; stored keys carry no slot bits here): with u the
+// f32 rows (normalised for cosine, scaled by the common power of two), z = round_16(u), the scanned value G = bias_j + z_i.z_j
+// differs from the real-number target Q = bias_j + u_i.u_j by at most
+//   E1_i = |dz_i| max|z_j| + |u_i| max|dz_j| + (dp + 8) 2^-24 (|z_i| max|z_j| + max|bias|)
+// (products of 16-bit values are exact in f32; the last term bounds the f32 accumulation of dp products and the bias in any
+// order), and the canonical f32 key (mapped to Q units) differs from Q by at most E2_i (rounding of the chain and of the
+// metric's few f32 ops).  margin_i = 2 (E1_i + E2_i): every column that can be in the canonical top-k has
+// G >= (k-th best G) - margin_i.
+//
+// What a list guarantees: it holds its best CAP keys under (G desc, id asc) among the columns that passed its threshold, and
+// a key is DROPPED only from a list that then holds CAP entries ranking before it (the best dropped key is remembered).  The
+// threshold is max(proven, lost): proven = (kk-th best key the two lists of the query hold) - margin, a lower bound of the
+// final one; lost = the best dropped key — anything below it matters only if the row is not flagged, i.e. if the final
+// threshold is above it.  After the scan the row is flagged (launch_scan_b16_audit) iff its best dropped key reaches the best
+// threshold proven for it.  A row whose margin band — the columns with G >= (kk-th best G over ALL columns) - margin — holds
+// at most CAP columns is therefore never flagged: a dropped key has CAP + 1 columns at or above it, so it lies below the
+// band, and every column of the band is still in a list when the thresholds are settled (wide_seed_union_kernel settles them
+// across column splits).
+#include "mmf_dev.h"
+#include "mmf_host.h"
+
+namespace mmf {
+
+namespace {
+
+constexpr int W_NT = 256;                        // threads per workgroup
+constexpr int W_QT = 128;                        // queries per macro tile
+constexpr int W_CT = 128;                        // candidates per macro tile
+constexpr int W_KC = 64;                         // halves per staged chunk
+constexpr int W_ROWB = W_KC * 2;                 // bytes per LDS row (128)
+constexpr int W_OPB = W_QT * W_ROWB;             // bytes per operand tile of a stage (16 KiB)
+constexpr int W_STAGEB = 2 * W_OPB;              // queries, then candidates
+constexpr int W_UPR = W_ROWB / 16;               // 16-byte units per row (8)
+constexpr int W_RPP = 64 / W_UPR;                // rows per 1 KiB DMA piece (8)
+constexpr int W_HP = W_QT / W_RPP;               // pieces per operand tile (16)
+constexpr int W_PPW = 2 * W_HP / 4;              // pieces per wave and chunk (8): the first half query pieces
+constexpr int W_FSH = 1;                         // unit u of tile row r sits at unit u ^ ((r >> W_FSH) & (W_UPR - 1))
+// (chunks of 32 halves — 64-byte rows, two workgroups per CU beside 16-entry lists — measured 27 % slower at N = 16384 and
+//  5 % faster at N = 65536, d = 1536; 8 % slower at d = 2560: one chunk size)
+constexpr int W_CAP_SMALL = 16;                  // list entries per lane, k + self <= 11
+constexpr int W_CAP_BIG = 32;                    // ... k + self in 12..20
+
+typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 wf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t wu32x4 __attribute__((ext_vector_type(4)));
+
+// order-preserving float -> int32 map of the threshold buffers (ScanB16Panel::seed; memset 0x80 = none)
+__device__ __forceinline__ int32_t wide_enc(float f) {
+  const int32_t b = __float_as_int(f);
+  return b >= 0 ? b : (b ^ 0x7fffffff);
+}
+
+struct ScanB16WArgs {
+  const void* ZQ;            // [nq_pad][dp] query side
+  const void* ZC;            // [m_pad][dp]  candidate side
+  const float* cb;           // [m_pad]
+  const float* q_zn; const float* q_rn; const float* q_un;
+  const uint32_t* maxima;    // candidate-side maxima
+  int64_t n_rows;            // queries
+  int64_t tiles_total;       // ceil(m / 128) <= m_pad / 128
+  int64_t tiles_per_split;
+  int col_splits;
+  int dp;                    // multiple of 128
+  int d;
+  int metric;
+  int kk;
+  int lists_total;           // lists per query row in cand_cnt / cand_ids
+  int list_base;
+  int32_t* seed;             // [>= n_rows] best proven threshold per query (wide_enc; atomicMax)
+  int32_t* lost;             // [>= n_rows] best dropped key per query
+  uint32_t* cand_cnt; uint32_t* cand_ids;
+  float* cand_keys;          // approximate keys of the entries, or nullptr
+  float* margin_out;         // [n_rows], written with cand_keys
+};
+
+// The lane-private list: entry e of thread t at keys[e * NT + t] / ids[e * NT + t] (LaneList's layout), approximate keys.
+template <int CAP, int NT>
+struct WideList {
+  float* keys; uint32_t* ids;
+  int cnt;
+  float thr;       // max(proven, lost): what a column has to reach
+  float proven;    // best (kk-th best key of the pair's lists) - margin seen so far; -FLT_MAX: none
+  float lost;      // best dropped key; -inf: none
+  bool crowded;    // the last compaction left the list full: hits replace its worst entry, no compaction until a partner asks
+
+  __device__ __forceinline__ void init(float* k, uint32_t* i) {
+    keys = k; ids = i; cnt = 0; thr = -kFltMax; proven = -kFltMax; lost = kNegInf; crowded = false;
+  }
+  __device__ __forceinline__ void push(float key, uint32_t id) {
+    keys[cnt * NT] = key; ids[cnt * NT] = id; ++cnt;
+  }
+  static __device__ __forceinline__ long long order64(float key, uint32_t id) {   // (key desc, id asc) as one signed compare
+    const int b = __float_as_int(key + 0.0f);
+    const int e = b >= 0 ? b : (b ^ 0x7fffffff);
+    return (long long)(((unsigned long long)(uint32_t)e << 32) | (unsigned long long)(~id));
+  }
+
+  // Wave-wide (EXEC full).  Ranks every entry by counting the entries of its own and of the partner lane's list (lane ^ 32,
+  // same wave: its LDS writes are ordered before these reads) that beat it, eight entries per sweep (LaneList::compact).
+  // The entry of union rank kk - 1 gives the proven threshold; what lies below the threshold leaves the list — that is no
+  // drop: a column below (kk-th best of a subset) - margin cannot be in the final top-kk.
+  __device__ __forceinline__ void compact(int kk, float margin) {
+    constexpr int BLK = 8;
+    const int pofs = (int)((threadIdx.x ^ 32u) - threadIdx.x);
+    const int pcnt = __shfl_xor(cnt, 32);
+    float t_own = kNegInf;
+#pragma nounroll
+    for (int e0 = 0; e0 < cnt; e0 += BLK) {
+      float kf32[BLK]; long long ke[BLK]; int rk[BLK];
+#pragma unroll
+      for (int i = 0; i < BLK; ++i) {                   // rows beyond cnt: stale but inside the lane's column; masked below
+        const int e = (e0 + i < CAP) ? e0 + i : CAP - 1;
+        kf32[i] = keys[e * NT]; ke[i] = order64(kf32[i], ids[e * NT]); rk[i] = 0;
+      }
+#pragma nounroll
+      for (int f = 0; f < cnt; ++f) {
+        const long long kf = order64(keys[f * NT], ids[f * NT]);
+#pragma unroll
+        for (int i = 0; i < BLK; ++i) rk[i] += (kf > ke[i]) ? 1 : 0;
+      }
+#pragma nounroll
+      for (int f = 0; f < pcnt; ++f) {
+        const long long kf = order64(keys[f * NT + pofs], ids[f * NT + pofs]);
+#pragma unroll
+        for (int i = 0; i < BLK; ++i) rk[i] += (kf > ke[i]) ? 1 : 0;
+      }
+#pragma unroll
+      for (int i = 0; i < BLK; ++i)
+        if (e0 + i < cnt && rk[i] == kk - 1) t_own = kf32[i];
+    }
+    const float t = fmaxf(t_own, __shfl_xor(t_own, 32));
+    if (t != kNegInf) {                                 // fewer than kk entries in the union: keep collecting everything
+      const float p = t - margin;
+      if (p > proven) proven = p;
+      if (proven > thr) thr = proven;
+    }
+    int w = 0;
+#pragma nounroll
+    for (int e = 0; e < cnt; ++e) {
+      const float ke = keys[e * NT];
+      const uint32_t ie = ids[e * NT];
+      if (ke >= thr) { keys[w * NT] = ke; ids[w * NT] = ie; ++w; }
+    }
+    cnt = w;
+    crowded = cnt >= CAP;
+  }
+
+  // A hit on a full list (lane-private): the worst of the CAP + 1 under (key desc, id asc) is dropped — CAP entries rank
+  // before it — and remembered; nothing below it can matter unless the row is flagged.
+  __device__ __forceinline__ void replace_worst(float x, uint32_t id) {
+    int wpos = 0;
+    float wk = keys[0]; uint32_t wi = ids[0];
+#pragma nounroll
+    for (int e = 1; e < CAP; ++e) {
+      const float ke = keys[e * NT]; const uint32_t ie = ids[e * NT];
+      if (better(wk, wi, ke, ie)) { wk = ke; wi = ie; wpos = e; }
+    }
+    float dropped = x;
+    if (better(x, id, wk, wi)) { keys[wpos * NT] = x; ids[wpos * NT] = id; dropped = wk; }
+    lost = fmaxf(lost, dropped);
+    thr = fmaxf(thr, lost);
+  }
+
+  // One 32-candidate sub-tile's 16 values of this lane's query; rowof(r): sub-tile row of element r.  Called by the whole
+  // wave when any lane has a hit; only the elements that hold a hit in SOME lane run the push code.
+  template <class RowOf>
+  __device__ __forceinline__ void offer_tile(const f32x16& v, uint32_t id0, RowOf rowof, int kk, float margin) {
+    uint32_t rmask = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rmask |= (__any(v[r] >= thr) ? 1u : 0u) << r;
+    while (rmask) {
+      const int r = __builtin_ctz(rmask);
+      rmask &= rmask - 1;
+      const float x = v[r];
+      bool hit = x >= thr;
+      if (__any(hit && cnt >= CAP && !crowded)) {
+        compact(kk, margin);
+        hit = x >= thr;
+      }
+      if (hit) {
+        const uint32_t id = id0 + rowof(r);
+        if (cnt < CAP) push(x, id);
+        else replace_worst(x, id);
+      }
+    }
+  }
+};
+
+// 64 KiB of stages + 1 KiB of biases + 32 / 64 KiB of lists: one workgroup per CU
+constexpr size_t scan_b16w_lds(int cap) { return (size_t)2 * W_STAGEB + (size_t)2 * W_CT * 4 + (size_t)cap * W_NT * 8; }
+
+template <bool F16, int CAP>
+__global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
+  extern __shared__ __attribute__((aligned(1024))) char smem[];
+  char* stages = smem;                                                   // [2][W_STAGEB]
+  float* cbs = reinterpret_cast<float*>(smem + 2 * W_STAGEB);            // [2][W_CT] bias of the tile being accumulated / the next
+  float* lkeys = cbs + 2 * W_CT;                                         // [CAP][W_NT]
+  uint32_t* lids = reinterpret_cast<uint32_t*>(lkeys + CAP * W_NT);      // [CAP][W_NT]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane >> 5;
+  const int g = lane >> 4;                      // row group of the C layout: rows 4 g .. 4 g + 3 of each 16-row block
+  const int c16 = lane & 15;
+  const int ownb = g & 1;                       // the query block (0 / 1) whose list this lane owns
+  const int c = c16 + 16 * ownb;                // own query within the wave
+
+  const int split = blockIdx.x % a.col_splits;
+  const int64_t rb = blockIdx.x / a.col_splits;
+  const int64_t q0 = rb * W_QT;
+  int64_t t_begin = (int64_t)split * a.tiles_per_split;
+  int64_t t_end = t_begin + a.tiles_per_split;
+  if (t_end > a.tiles_total) t_end = a.tiles_total;
+  if (t_begin > t_end) t_begin = t_end;
+  const int nkc = a.dp / W_KC;
+  const int64_t steps = (t_end - t_begin) * nkc;
+
+  const int64_t qpos = q0 + 32 * wave + c;
+  const bool qvalid = qpos < a.n_rows;
+
+  // margin of this lane's query (see the header): 2 (E1 + E2)
+  float margin;
+  {
+    const float ZB = __uint_as_float(a.maxima[0]), RB = __uint_as_float(a.maxima[1]);
+    const float UB = __uint_as_float(a.maxima[2]), CB = __uint_as_float(a.maxima[3]);
+    const float zn = a.q_zn[qpos], rn = a.q_rn[qpos], un = a.q_un[qpos];   // arrays are padded to whole row blocks
+    const float g_acc = (float)(a.dp + 8) * 5.9604645e-8f;
+    const float g_chain = (float)(a.d + 2) * 5.9604645e-8f;
+    const float e1 = rn * ZB + un * RB + g_acc * (zn * ZB + CB);
+    float e2;
+    if (a.metric == MMF_DOT) e2 = g_chain * un * UB;
+    else if (a.metric == MMF_COSINE) e2 = (g_chain + 4.7683716e-7f) * un * UB * 1.01f;
+    else e2 = g_chain * un * UB + 2.3841858e-7f * (un * un + UB * UB);
+    margin = 2.0f * (e1 + e2) * 1.001f + 1e-30f;
+  }
+
+  WideList<CAP, W_NT> list;
+  list.init(lkeys + tid, lids + tid);
+  if (!qvalid) list.thr = __builtin_huge_valf();
+
+  // DMA roles (scan_f32_kernel's): piece p = wave + 4 i covers tile rows [(p % W_HP) * 8, + 8) of the query (i < 4) or
+  // candidate tile; lane l lands at row l / 8, unit l % 8 of the piece and fetches the unit the swizzle puts there.  The
+  // lane's byte offset inside a tile image is loop invariant; the chunk moves through the scalar offset, the tile through
+  // the buffer's base.
+  uint32_t voff[W_PPW];
+#pragma unroll
+  for (int i = 0; i < W_PPW; ++i) {
+    const int row = ((wave + 4 * i) % W_HP) * W_RPP + lane / W_UPR;
+    const int lu = (lane % W_UPR) ^ ((row >> W_FSH) & (W_UPR - 1));
+    voff[i] = (uint32_t)(row * a.dp * 2 + 16 * lu);
+  }
+  const char* zq0 = reinterpret_cast<const char*>(a.ZQ) + q0 * (int64_t)a.dp * 2;
+  const __amdgpu_buffer_rsrc_t qrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(zq0), 0, -1, 0x00020000);
+  float rcb = 0.0f;
+  // chunk kc of candidate tile ct -> stage `buf`; the tile's 128 biases ride along with its first chunk
+  auto stage = [&](int64_t ct, int kc, int buf) {
+    if (kc == 0 && tid < W_CT) rcb = a.cb[ct * W_CT + tid];
+    const char* zc = reinterpret_cast<const char*>(a.ZC) + ct * W_CT * (int64_t)a.dp * 2;
+    const __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(zc), 0, -1, 0x00020000);
+    const int koff = kc * W_ROWB;
+    char* sb = stages + buf * W_STAGEB;
+#pragma unroll
+    for (int i = 0; i < W_PPW; ++i) {
+      const int pr = (wave + 4 * i) % W_HP;
+      if (i < W_PPW / 2)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(qrsrc, (__attribute__((address_space(3))) void*)(sb + pr * 1024), 16, (int)voff[i], koff, 0, 0);
+      else
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(crsrc, (__attribute__((address_space(3))) void*)(sb + W_OPB + pr * 1024), 16, (int)voff[i], koff, 0, 0);
+    }
+  };
+
+  f32x4 acc[8][2];                              // [candidate block][query block]
+#pragma unroll
+  for (int cb = 0; cb < 8; ++cb) { acc[cb][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[cb][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+
+  // thresholds of the two queries this lane holds values for: its own list's and its partner's (lane ^ 16)
+  float thr_q0, thr_q1;
+  auto refresh_thr = [&]() {
+    const float mine = list.thr;
+    const float theirs = __shfl_xor(mine, 16);
+    thr_q0 = ownb ? theirs : mine;
+    thr_q1 = ownb ? mine : theirs;
+  };
+  refresh_thr();
+
+  // operand reads inside a stage: query row 32 wave + c16 (+ 16 qb), candidate row c16 (+ 16 cb); all of them share
+  // the swizzle term of row c16 (the other rows differ by multiples of 16), so one term serves every read of the lane
+  const int sw = (c16 >> W_FSH) & (W_UPR - 1);
+  const int qoff = (32 * wave + c16) * W_ROWB;
+  const int coff = W_OPB + c16 * W_ROWB;
+
+  if (steps > 0) {
+    stage(t_begin, 0, 0);
+    if (tid < W_CT) cbs[tid] = rcb;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  int64_t ct = t_begin;        // tile and chunk being multiplied
+  int kc = 0;
+  for (int64_t s = 0; s < steps; ++s) {
+    const int buf = (int)(s & 1);
+    int nkcn = kc + 1;
+    int64_t nct = ct;
+    if (nkcn == nkc) { nkcn = 0; nct = ct + 1; }
+    if (s + 1 < steps) stage(nct, nkcn, buf ^ 1);
+    const int tpar = (int)((ct - t_begin) & 1);
+
+    if (kc == 0) {             // a new tile: accumulators start from the candidates' bias
+#pragma unroll
+      for (int cb = 0; cb < 8; ++cb) {
+        const f32x4 b4 = *reinterpret_cast<const f32x4*>(cbs + tpar * W_CT + 16 * cb + 4 * g);
+        acc[cb][0] = b4; acc[cb][1] = b4;
+      }
+    }
+
+    const char* sb = stages + buf * W_STAGEB;
+#pragma unroll
+    for (int ks = 0; ks < W_KC / 32; ++ks) {
+      const int uo = ((4 * ks + g) ^ sw) * 16;
+      const wu32x4 b0 = *reinterpret_cast<const wu32x4*>(sb + qoff + uo);
+      const wu32x4 b1 = *reinterpret_cast<const wu32x4*>(sb + qoff + 16 * W_ROWB + uo);
+#pragma unroll
+      for (int cb = 0; cb < 8; ++cb) {
+        const wu32x4 av = *reinterpret_cast<const wu32x4*>(sb + coff + cb * 16 * W_ROWB + uo);
+        if constexpr (F16) {
+          acc[cb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wf16x8, av), __builtin_bit_cast(wf16x8, b0), acc[cb][0], 0, 0, 0);
+          acc[cb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wf16x8, av), __builtin_bit_cast(wf16x8, b1), acc[cb][1], 0, 0, 0);
+        } else {
+          acc[cb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wbf16x8, av), __builtin_bit_cast(wbf16x8, b0), acc[cb][0], 0, 0, 0);
+          acc[cb][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wbf16x8, av), __builtin_bit_cast(wbf16x8, b1), acc[cb][1], 0, 0, 0);
+        }
+      }
+    }
+
+    if (kc == nkc - 1) {       // the whole d is in: one epilogue per macro tile, a 32-candidate sub-tile at a time
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const f32x4& p0 = acc[2 * t][0]; const f32x4& r0 = acc[2 * t + 1][0];
+        const f32x4& p1 = acc[2 * t][1]; const f32x4& r1 = acc[2 * t + 1][1];
+        const float m0 = fmaxf(fmaxf(fmaxf(p0[0], p0[1]), fmaxf(p0[2], p0[3])), fmaxf(fmaxf(r0[0], r0[1]), fmaxf(r0[2], r0[3])));
+        const float m1 = fmaxf(fmaxf(fmaxf(p1[0], p1[1]), fmaxf(p1[2], p1[3])), fmaxf(fmaxf(r1[0], r1[1]), fmaxf(r1[2], r1[3])));
+        if (__builtin_expect(__any((m0 >= thr_q0) || (m1 >= thr_q1)), 0)) {
+          // this lane's query gets its 16 candidates together: its own 8 plus the 8 the partner lane holds
+          f32x16 v;
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float mine = ownb ? acc[2 * t + cb][1][j] : acc[2 * t + cb][0][j];
+              const float give = ownb ? acc[2 * t + cb][0][j] : acc[2 * t + cb][1][j];
+              v[4 * cb + j] = mine;
+              v[8 + 4 * cb + j] = __shfl_xor(give, 16);
+            }
+          }
+          // v[0..7]: rows of this lane's group g, v[8..15]: rows of the partner's group g ^ 1
+          const int g4 = 4 * g;
+          auto rowof = [g4](int r) -> uint32_t { return (uint32_t)((g4 ^ ((r & 8) >> 1)) + (r & 3) + 16 * ((r >> 2) & 1)); };
+          list.offer_tile(v, (uint32_t)(ct * W_CT + 32 * t), rowof, a.kk, margin);
+          refresh_thr();
+        }
+      }
+    }
+
+    if (s + 1 < steps && nkcn == 0 && tid < W_CT) cbs[(int)((nct - t_begin) & 1) * W_CT + tid] = rcb;
+    ct = nct; kc = nkcn;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of the next chunk have landed
+    __syncthreads();
+  }
+
+  // Settle: the pair's proven threshold from what the two lists hold, entries below the threshold dropped before they are
+  // written (the re-rank gathers about kk rows per list, not CAP).
+  list.compact(a.kk, margin);
+  if (qvalid) {
+    const int64_t lbase = qpos * a.lists_total + a.list_base + 2 * split + half;
+    a.cand_cnt[lbase] = (uint32_t)list.cnt;
+    for (int e = 0; e < list.cnt; ++e) {
+      a.cand_ids[lbase * CAP + e] = list.ids[e * W_NT];
+      if (a.cand_keys) a.cand_keys[lbase * CAP + e] = list.keys[e * W_NT];
+    }
+    if (a.cand_keys && half == 0) a.margin_out[qpos] = margin;
+    if (list.proven > -kFltMax) atomicMax(a.seed + qpos, wide_enc(list.proven));
+    if (list.lost > kNegInf) atomicMax(a.lost + qpos, wide_enc(list.lost));
+  }
+}
+
+// Column splits: every pair of lists proves a threshold from ITS columns only, (kk-th best of the split) - margin, which can
+// lie far below the row's.  One wave per row takes the kk-th best key of everything the row's lists hold — a subset of the
+// row's columns, so a valid lower bound — and raises the row's threshold to it minus the margin.  With that, "band <= CAP
+// columns => never flagged" holds for any number of splits (header).  kk rounds of "best entry ranked after the previous
+// pick" under (key desc, position asc), as select's pruning does.
+__global__ __launch_bounds__(256) void wide_seed_union_kernel(const uint32_t* cand_cnt, const float* cand_keys, const float* margin,
+                                                              int lists, int cap, int kk, int32_t* seed, int64_t n_rows) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n_rows) return;
+  const int slots = lists * cap;
+  float pk = 0.0f;
+  uint32_t pe = 0;
+  for (int t = 0; t < kk; ++t) {
+    float bk = kNegInf;
+    uint32_t be = kNoIdx;
+    for (int e = lane; e < slots; e += 64) {
+      const int l = e / cap;
+      if ((uint32_t)(e - l * cap) >= cand_cnt[row * lists + l]) continue;
+      const float ke = cand_keys[row * slots + e];
+      if (t > 0 && !better(pk, pe, ke, (uint32_t)e)) continue;
+      if (be == kNoIdx || better(ke, (uint32_t)e, bk, be)) { bk = ke; be = (uint32_t)e; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ok = __shfl_xor(bk, o);
+      const uint32_t oe = (uint32_t)__shfl_xor((int)be, o);
+      if (oe != kNoIdx && (be == kNoIdx || better(ok, oe, bk, be))) { bk = ok; be = oe; }
+    }
+    if (be == kNoIdx) return;          // fewer than kk entries: nothing to prove
+    pk = bk; pe = be;
+  }
+  if (lane == 0) atomicMax(seed + row, wide_enc(pk - margin[row]));
+}
+
+template <int CAP>
+int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) {
+  const size_t lds = scan_b16w_lds(CAP);
+  auto go = [&](auto kern) -> int {
+    MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(W_NT), lds, s, a);
+    MMF_LAUNCH_CHECK();
+    return MMF_OK;
+  };
+  if (f16) return go(scan_b16w_kernel<true, CAP>);
+  return go(scan_b16w_kernel<false, CAP>);
+}
+
+}  // namespace
+
+int scan_b16w_supported(int64_t d, int kk) { return (d > 1024 && d <= 4096 && kk >= 1 && kk <= 20) ? 1 : 0; }
+int scan_b16w_cap(int kk) { return kk <= 11 ? W_CAP_SMALL : W_CAP_BIG; }
+int scan_b16w_dp(int64_t d) { return (int)((d + 127) / 128 * 128); }
+int scan_b16w_queries_per_block() { return W_QT; }
+int scan_b16w_col_tile() { return W_CT; }
+
+// col_splits must be a power of two.  Lists are indexed by query position; pn: the threshold buffers (no panels, no shared
+// thresholds on this path).  With more than one split L.keys / L.margin must be set: wide_seed_union_kernel reads them.
+int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L, const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
+  if (p.n_rows <= 0 || p.m <= 0) return MMF_OK;
+  if (!scan_b16w_supported(p.d, p.kk) || p.dp != scan_b16w_dp(p.d)) {
+    set_error("scan_b16w: d = %lld (padded %d), k + self = %d outside 1024 < d <= 4096, k + self <= 20", (long long)p.d, p.dp, p.kk);
+    return MMF_E_INTERNAL;
+  }
+  if (col_splits < 1 || (col_splits & (col_splits - 1)) != 0) { set_error("scan_b16w: col_splits %d is no power of two", col_splits); return MMF_E_INTERNAL; }
+  if (!pn.seed) { set_error("scan_b16w: threshold buffers missing"); return MMF_E_INTERNAL; }
+  if (pn.list_base != 0 || pn.seg_len != 0 || pn.id_off != 0) { set_error("scan_b16w: no paneled form"); return MMF_E_INTERNAL; }
+  if (2 * col_splits != L.lists) { set_error("scan_b16w: %d lists per row for %d column splits", L.lists, col_splits); return MMF_E_INTERNAL; }
+  if (L.cap != scan_b16w_cap(p.kk)) { set_error("scan_b16w: list capacity %d, expected %d", L.cap, scan_b16w_cap(p.kk)); return MMF_E_INTERNAL; }
+  if (col_splits > 1 && (!L.keys || !L.margin)) { set_error("scan_b16w: column splits need the lists' keys and margins"); return MMF_E_INTERNAL; }
+  ScanB16WArgs a{};
+  a.ZQ = p.ZQ; a.ZC = p.ZC; a.cb = p.cb; a.q_zn = p.q_zn; a.q_rn = p.q_rn; a.q_un = p.q_un; a.maxima = p.maxima;
+  a.n_rows = p.n_rows; a.kk = p.kk; a.metric = p.metric; a.d = (int)p.d; a.dp = p.dp;
+  a.tiles_total = (p.m + W_CT - 1) / W_CT;
+  if (a.tiles_total * W_CT > p.m_pad) { set_error("scan_b16w: candidate image of %lld rows is shorter than its tiles", (long long)p.m_pad); return MMF_E_INTERNAL; }
+  a.col_splits = col_splits;
+  a.tiles_per_split = (a.tiles_total + col_splits - 1) / col_splits;
+  a.lists_total = L.lists; a.list_base = 0;
+  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride;
+  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.cand_keys = L.keys; a.margin_out = L.margin;
+  const int64_t row_blocks = (p.n_rows + W_QT - 1) / W_QT;
+  const int64_t grid = row_blocks * col_splits;
+  if (grid_out) *grid_out = (int)grid;
+  MMF_TRY(L.cap == W_CAP_SMALL ? launch_b16w_t<W_CAP_SMALL>(a, p.f16, grid, s) : launch_b16w_t<W_CAP_BIG>(a, p.f16, grid, s));
+  if (col_splits > 1) {
+    hipLaunchKernelGGL(wide_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
+                       p.kk, pn.seed, p.n_rows);
+    MMF_LAUNCH_CHECK();
+  }
+  return MMF_OK;
+}
+
+}  // namespace mmf
