@@ -76,6 +76,10 @@ EXPORTS_TOPK = ["mmf_simtopk_combined"]
 # they take neither a device nor a stream.
 EXPORTS_WIDE = ["mmf_wide_scan_supported", "mmf_wide_scan_list_capacity"]
 
+# The segmented wide scan (include/mmf_hg_wide_seg.h): an addition to ABI version 3 in a header of its own.  Its
+# synchronisation behaviour is INTEGRATION.md's table "Wide segmented entries", pinned by tests/test_wide_segmented_cpu.py.
+EXPORTS_WIDE_SEG = ["mmf_simtopk_segmented_wide"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -140,7 +144,8 @@ def lib() -> ctypes.CDLL:
                                        ctypes.POINTER(SimtopkOpts), ctypes.POINTER(SimtopkStats), ci, vp]
     L.mmf_wide_scan_supported.argtypes = [i64, ci, ci]
     L.mmf_wide_scan_list_capacity.argtypes = [ci, ci]
-    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE:
+    L.mmf_simtopk_segmented_wide.argtypes = list(L.mmf_simtopk_segmented.argtypes)
+    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG:
         fn = getattr(L, name)
         if name not in ("mmf_last_error", "mmf_padded_dim", "mmf_super_patch_stats_streamed_bytes"):
             fn.restype = ci

@@ -208,6 +208,12 @@ static int64_t admissible_columns(int64_t r0, int64_t n, int64_t c0, int64_t m, 
 // 65536, d = 1536 — 125 and 431 times the exact arm's spread, where the rule asks for three.
 static bool wide_scan_auto() { return true; }
 
+// Whether the segmented wide scan splits its segments' columns on its own (FastTail's rule applied to the call).  It does not:
+// measured at 4 segments of 4096 rows, d = 1536 (profiles/wide_segmented_timing.txt) the rule's two ranges took
+// 1.090 ms against 1.411 ms for one — 2.9 times the spread of the one-range arm, where the project's rule asks for more than
+// three.  opts->col_splits forces a count either way.
+static bool wide_seg_auto_splits() { return false; }
+
 // One simtopk call: its prologue (`call`), its arguments, and what check() derives from them.
 struct Request {
   Call call;
@@ -1543,22 +1549,46 @@ int mmf_combined_threshold_edges(const float* F, const float* P, int64_t n, int6
 // audit and the exact re-rank over all rows, then one host synchronisation.  Rows the 16-bit path cannot certify, and
 // every row of a segment with fewer than k admissible columns (or of every segment under MMF_PREC_EXACT), go through the
 // exact pass (ExactPass) segment by segment: two launches per segment, not a work table ("Exact rows").
-int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
-                          float lambda, int k, int exclude_self, const int64_t* x_ptr_host, const int64_t* y_ptr_host,
-                          int64_t n_segments, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
-                          mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+//
+// One body for mmf_simtopk_segmented (`who` "simtopk_segmented", wide_allowed false) and mmf_simtopk_segmented_wide
+// (include/mmf_hg_wide_seg.h).  wide_allowed: for 1024 < d <= 4096, k + self <= 20 the 16-bit candidates come
+// from the wide scan (launch_scan_b16w_seg) — 128-row tiles on both sides, its list capacity, no id scratch, column splits per
+// segment — and MMF_PREC_AUTO takes it; everything around the scan launch is the narrow path's.  The body keeps the name of
+// the entry it was written for: mmf::mmf_simtopk_segmented(who, wide_allowed, ...) is the overload the two C entries call.
+}  // extern "C"
+
+namespace mmf {
+
+int mmf_simtopk_segmented(const char* who, bool wide_allowed, const void* X, int64_t n, const void* Y, int64_t m, int64_t d,
+                          int in_dtype, int metric, float lambda, int k, int exclude_self, const int64_t* x_ptr_host,
+                          const int64_t* y_ptr_host, int64_t n_segments, int64_t* out_idx, float* out_val,
+                          const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
   const bool self = (Y == nullptr);
   if (self) { Y = X; m = n; y_ptr_host = x_ptr_host; }
-  Request r{Call("simtopk_segmented", device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, 0, 0,
+  Request r{Call(who, device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, 0, 0,
             out_idx, out_val, stats, opts && opts->profile};
-  MMF_TRY(r.check(opts ? opts->precision : MMF_PREC_AUTO, true, [&] {
+  r.wide_ok = wide_allowed;
+  const int prec_asked = opts ? opts->precision : MMF_PREC_AUTO;
+  MMF_TRY(r.check(prec_asked, true, [&] {
     MMF_TRY(check_offsets(r.call.who, "x_ptr", x_ptr_host, n_segments, 0, 0, n));
     MMF_TRY(check_offsets(r.call.who, "y_ptr", y_ptr_host, n_segments, 0, 0, m));
-    if (m > 0 && !Y) { set_error("simtopk_segmented: Y is NULL"); return MMF_E_INVALID; }
+    if (m > 0 && !Y) { set_error("%s: Y is NULL", who); return MMF_E_INVALID; }
     // (lifting this is a matter of letting the exact pass take such segments: it runs the passes k + self > 44 needs)
-    if (r.kk > 44) { set_error("simtopk_segmented: k + self = %d > 44 is not supported", r.kk); return MMF_E_UNSUPPORTED; }
-    if (opts && (opts->col_splits != 0 || opts->select_wait_event)) {
-      set_error("simtopk_segmented: col_splits and select_wait_event are not supported");
+    if (r.kk > 44) { set_error("%s: k + self = %d > 44 is not supported", who, r.kk); return MMF_E_UNSUPPORTED; }
+    // the shapes the wide scan serves take col_splits (0 or a power of two); everywhere else the options are the narrow entry's
+    const bool wide_shape = wide_allowed && prec_asked != MMF_PREC_EXACT && scan_b16w_supported(d, r.kk);
+    if (wide_shape) {
+      if (opts && opts->select_wait_event) { set_error("%s: select_wait_event is not supported", who); return MMF_E_UNSUPPORTED; }
+      const int cs = opts ? opts->col_splits : 0;
+      if (cs < 0 || (cs & (cs - 1)) != 0) { set_error("%s: col_splits must be 0 or a power of two (got %d)", who, cs); return MMF_E_INVALID; }
+    } else if (opts && (opts->col_splits != 0 || opts->select_wait_event)) {
+      set_error("%s: col_splits and select_wait_event are not supported", who);
+      return MMF_E_UNSUPPORTED;
+    }
+    // the wide entry settles the precision before any device call (Request::check repeats this behind Call::begin)
+    if (wide_allowed && (prec_asked == MMF_PREC_FAST || prec_asked == MMF_PREC_FAST_BF16) && !scan_bf16_supported(d, r.kk, in_dtype) &&
+        !scan_b16w_supported(d, r.kk)) {
+      set_error("%s: MMF_PREC_FAST does not support d = %lld, k = %d (AUTO takes the exact scan there)", who, (long long)d, k);
       return MMF_E_UNSUPPORTED;
     }
     return MMF_OK;
@@ -1574,9 +1604,24 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
   std::vector<int64_t> adm(S);
   for (int64_t g = 0; g < S; ++g) adm[g] = admissible_columns(xp[g], xp[g + 1] - xp[g], yp[g], yp[g + 1] - yp[g], exclude_self);
   const bool fast = precision != MMF_PREC_EXACT;
-  const int dp = fast ? scan_bf16_dp(d) : 0;
-  const int qt = fast ? scan_b16_queries_per_block(dp) : 1;
-  constexpr int kTile = 32;                       // candidate rows per tile of the 16-bit scan (B_CT)
+  const bool wide = r.wide;                       // the 16-bit scan of this call is the wide one (wide_allowed entries only)
+  const int dp = !fast ? 0 : wide ? scan_b16w_dp(d) : scan_bf16_dp(d);
+  const int qt = !fast ? 1 : wide ? scan_b16w_queries_per_block() : scan_b16_queries_per_block(dp);
+  const int kTile = wide ? scan_b16w_col_tile() : 32;   // candidate rows per tile of the 16-bit scan (W_CT / B_CT)
+  const int bcap = !fast ? 0 : wide ? scan_b16w_cap(r.kk) : scan_bf16_cap(r.kk, dp);
+  // Column ranges per segment (wide only): FastTail's rule applied to the call — with R row blocks over the
+  // served segments, double while R x splits < 256 and select's capacity per row holds 2 x splits lists; a forced value takes
+  // the same bound; each segment caps its count at its own tile count, rounded down to a power of two.
+  int call_splits = 1, max_splits = 1;
+  if (wide) {
+    int64_t R = 0;
+    for (int64_t g = 0; g < S; ++g)
+      if (xp[g + 1] > xp[g] && adm[g] >= k) R += (xp[g + 1] - xp[g] + qt - 1) / qt;
+    const int forced = opts ? opts->col_splits : 0;
+    const auto fits = [&](int sp) { return 2 * sp * bcap <= 1024 - kSpillCap; };
+    if (forced > 0) { while (call_splits < forced && fits(2 * call_splits)) call_splits <<= 1; }
+    else if (wide_seg_auto_splits()) { while (R > 0 && R * call_splits < 256 && fits(2 * call_splits)) call_splits <<= 1; }
+  }
   // segments the 16-bit scan serves: rows present and at least k admissible columns (the others are done exactly)
   std::vector<char> on_fast(S, 0);
   int64_t nq_pos = 0, mc_pos = 0;
@@ -1586,21 +1631,29 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
       const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g];
       if (ng == 0 || adm[g] < k) continue;
       const int64_t tiles = (mg + kTile - 1) / kTile;
-      if (tiles * kTile * (int64_t)dp * 2 >= (int64_t(1) << 32)) {   // 32-bit offsets of the tile DMA
-        set_error("simtopk_segmented: segment %lld has %lld candidate rows, over 4 GiB of 16-bit operands", (long long)g, (long long)mg);
+      // 32-bit offsets of the tile DMA (the wide kernel moves a tile through the buffer base: no such limit)
+      if (!wide && tiles * kTile * (int64_t)dp * 2 >= (int64_t(1) << 32)) {
+        set_error("%s: segment %lld has %lld candidate rows, over 4 GiB of 16-bit operands", who, (long long)g, (long long)mg);
         return MMF_E_UNSUPPORTED;
       }
       on_fast[g] = 1;
       const int64_t t0 = mc_pos / kTile;
+      int sp = 1;                                   // column ranges of this segment: one table entry and one list pair each
+      while (2 * sp <= call_splits && 2 * sp <= tiles) sp <<= 1;
+      if (sp > max_splits) max_splits = sp;
+      const int64_t tps = (tiles + sp - 1) / sp;
       for (int64_t b = 0; b < ng; b += qt) {
-        const int32_t e[8] = {(int32_t)(nq_pos + b), (int32_t)(xp[g] + b), (int32_t)(ng - b < qt ? ng - b : qt), (int32_t)t0,
-                              (int32_t)(t0 + tiles), (int32_t)(uint32_t)(yp[g] - t0 * kTile), 0, 0};
-        sched.insert(sched.end(), e, e + 8);
+        for (int c = 0; c < sp; ++c) {
+          const int64_t tb = std::min(t0 + c * tps, t0 + tiles), te = std::min(tb + tps, t0 + tiles);
+          const int32_t e[8] = {(int32_t)(nq_pos + b), (int32_t)(xp[g] + b), (int32_t)(ng - b < qt ? ng - b : qt), (int32_t)tb,
+                                (int32_t)te, (int32_t)(uint32_t)(yp[g] - t0 * kTile), 2 * c, 0};
+          sched.insert(sched.end(), e, e + 8);
+        }
       }
       nq_pos += (ng + qt - 1) / qt * qt;
       mc_pos += tiles * kTile;
     }
-    if (nq_pos >= (int64_t(1) << 31) || mc_pos >= (int64_t(1) << 31)) { set_error("simtopk_segmented: padded images too large"); return MMF_E_UNSUPPORTED; }
+    if (nq_pos >= (int64_t(1) << 31) || mc_pos >= (int64_t(1) << 31)) { set_error("%s: padded images too large", who); return MMF_E_UNSUPPORTED; }
   }
   const int64_t grid = (int64_t)sched.size() / 8;
   std::vector<int32_t> qgather(nq_pos, -1), cgather(mc_pos, -1);
@@ -1618,13 +1671,14 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
 
   // ---- workspace (slot 0): row scalars, the 16-bit images, tables, lists -------------------------------------------
   const int64_t nq_pad = (nq_pos + 255) / 256 * 256, mc_pad = (mc_pos + 255) / 256 * 256;
-  const int bcap = fast ? scan_bf16_cap(r.kk, dp) : 0;
+  const int lists = 2 * max_splits;               // per row; narrow scan: one pair
+  const size_t scratch_bytes = wide ? 256 : scan_b16_seg_scratch_bytes(grid, dp, bcap);   // the wide kernel keeps no id scratch
   const int64_t n_seed = n;
   size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + FlagBlock::bytes(n);
   if (grid > 0)
     need += HalfImage::bytes(nq_pad, dp) + HalfImage::bytes(mc_pad, dp) + ws_bytes(4, 4) + ws_bytes(sched.size(), 4) +
-            ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + b16_lists_bytes(n, 2, bcap) +
-            ws_bytes(scan_b16_seg_scratch_bytes(grid, dp, bcap), 1) + ws_bytes(2 * (size_t)n_seed, 4) + ws_bytes(select_order_bytes(n), 1);
+            ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + b16_lists_bytes(n, lists, bcap) +
+            ws_bytes(scratch_bytes, 1) + ws_bytes(2 * (size_t)n_seed, 4) + ws_bytes(select_order_bytes(n), 1);
   Workspace ws;
   MMF_TRY(r.call.workspace(need, &ws));
   float* rx = ws.take<float>(n);
@@ -1650,8 +1704,8 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
     int32_t* d_sched = ws.take<int32_t>(sched.size());
     int32_t* d_qg = ws.take<int32_t>(nq_pos);
     int32_t* d_cg = ws.take<int32_t>(mc_pos);
-    const CandLists L = carve_b16_lists(ws, n, 2, bcap);
-    char* scan_scratch = ws.take<char>(scan_b16_seg_scratch_bytes(grid, dp, bcap));
+    const CandLists L = carve_b16_lists(ws, n, lists, bcap);
+    char* scan_scratch = ws.take<char>(scratch_bytes);
     int32_t* seed = ws.take<int32_t>(2 * (size_t)n_seed);
     char* order_scratch = ws.take<char>(select_order_bytes(n));
     MMF_HIP(hipMemcpyAsync(d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice, s));
@@ -1664,14 +1718,16 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
     MMF_TRY(t_prep.stop(s));
 
     // rows of segments the scan does not serve keep empty lists: the re-rank reports them, the exact pass below redoes them
-    MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * 2 * 4, s));
+    MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));
     MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
     MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
     MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n_seed * 8, s));
     ScanB16Panel pn;
     pn.seed = seed; pn.seed_stride = n_seed; pn.share = 0;
     MMF_TRY(t_scan.start(profile, s));
-    MMF_TRY(launch_scan_b16_seg(ScanB16Problem(Q, C, n, m, mc_pad, dp, d, f16, metric, r.kk), d_sched, grid, L, scan_scratch, pn, s));
+    const ScanB16Problem sp(Q, C, n, m, mc_pad, dp, d, f16, metric, r.kk);
+    if (wide) MMF_TRY(launch_scan_b16w_seg(sp, d_sched, grid, lists, L, pn, s));
+    else MMF_TRY(launch_scan_b16_seg(sp, d_sched, grid, L, scan_scratch, pn, s));
     MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
     MMF_TRY(t_scan.stop(s));
 
@@ -1733,10 +1789,31 @@ int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, in
   MMF_TRY(t_fb.stop(s));
   MMF_HIP(hipStreamSynchronize(s));
   const int64_t overflow_rows = h_fail4[1] < (uint32_t)fallback_rows ? h_fail4[1] : fallback_rows;
-  fill_stats(stats, grid > 0 ? precision : MMF_PREC_EXACT, 1, grid > 0 ? (int)grid : ex.grid, t_prep.ms(),
+  fill_stats(stats, grid > 0 ? precision : MMF_PREC_EXACT, max_splits, grid > 0 ? (int)grid : ex.grid, t_prep.ms(),
              grid > 0 ? t_scan.ms() : t_fb.ms(), t_sel.ms(), grid > 0 ? t_fb.ms() : 0.f, fallback_rows, overflow_rows,
              fallback_rows - overflow_rows, flags.h_tot);
   return MMF_OK;
+}
+
+}  // namespace mmf
+
+extern "C" {
+
+int mmf_simtopk_segmented(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
+                          float lambda, int k, int exclude_self, const int64_t* x_ptr_host, const int64_t* y_ptr_host,
+                          int64_t n_segments, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
+                          mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  return mmf::mmf_simtopk_segmented("simtopk_segmented", false, X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, x_ptr_host,
+                                    y_ptr_host, n_segments, out_idx, out_val, opts, stats, device_id, hip_stream);
+}
+
+// include/mmf_hg_wide_seg.h, DESIGN.md §4.16
+int mmf_simtopk_segmented_wide(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
+                               float lambda, int k, int exclude_self, const int64_t* x_ptr_host, const int64_t* y_ptr_host,
+                               int64_t n_segments, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
+                               mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  return mmf::mmf_simtopk_segmented("simtopk_segmented_wide", true, X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, x_ptr_host,
+                                    y_ptr_host, n_segments, out_idx, out_val, opts, stats, device_id, hip_stream);
 }
 
 

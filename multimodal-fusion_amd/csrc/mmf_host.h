@@ -13,6 +13,7 @@
 #include "../../include/mmf_hg.h"
 #include "../../include/mmf_hg_topk.h"
 #include "../../include/mmf_hg_wide.h"
+#include "../../include/mmf_hg_wide_seg.h"
 
 namespace mmf {
 
@@ -361,6 +362,12 @@ int scan_b16w_dp(int64_t d);
 int scan_b16w_queries_per_block();
 int scan_b16w_col_tile();
 int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L, const ScanB16Panel& pn, hipStream_t s, int* grid_out);
+// Segmented form: one workgroup per entry of the device work table `sched` ([grid][8] int32: query position in the
+// query image, row of X, real queries, first / end tile in the candidate image, id offset, list slot).  p.n_rows: rows of X (lists,
+// thresholds and margins are indexed by them); both images are padded per segment to 128 rows.  lists == L.lists == 2 x the
+// largest number of column ranges of a segment (a power of two).
+int launch_scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, int lists, const CandLists& L, const ScanB16Panel& pn,
+                         hipStream_t s);
 
 // mmf_dense.hip
 // Xp / Yp: f32 images of X and Y (launch_prep_f32; unused — may be null — for d <= 8 and MMF_RBF_DIRECT)

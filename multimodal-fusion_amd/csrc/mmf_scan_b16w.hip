@@ -93,6 +93,21 @@ struct ScanB16WArgs {
   uint32_t* cand_cnt; uint32_t* cand_ids;
   float* cand_keys;          // approximate keys of the entries, or nullptr
   float* margin_out;         // [n_rows], written with cand_keys
+  const int32_t* sched;      // SEG kernels only: [grid][WSEG_ENTRY] work table (launch_scan_b16w_seg)
+};
+
+// One entry of the segmented work table: a workgroup = one row block of one segment against one column range of that segment.
+// Operands, zn / rn / un and the biases are addressed by image position (both images are padded per segment to whole tiles);
+// lists, seed, lost and margin_out by the row of X.
+enum {
+  WSEG_QPOS = 0,    // position of the row block's first query in the query image (a multiple of 128)
+  WSEG_ROW0 = 1,    // row of X of that query
+  WSEG_NQ = 2,      // real queries of the block (<= 128)
+  WSEG_T0 = 3,      // first and end tile of the column range, in the candidate image (tiles of 128)
+  WSEG_T1 = 4,
+  WSEG_IDOFF = 5,   // y_ptr[s] - first column of the segment's tiles (mod 2^32): lists hold global rows of Y
+  WSEG_SLOT = 6,    // first list slot of this range (2 x split)
+  WSEG_ENTRY = 8
 };
 
 // The lane-private list: entry e of thread t at keys[e * NT + t] / ids[e * NT + t] (LaneList's layout), approximate keys.
@@ -211,7 +226,9 @@ struct WideList {
 // 64 KiB of stages + 1 KiB of biases + 32 / 64 KiB of lists: one workgroup per CU
 constexpr size_t scan_b16w_lds(int cap) { return (size_t)2 * W_STAGEB + (size_t)2 * W_CT * 4 + (size_t)cap * W_NT * 8; }
 
-template <bool F16, int CAP>
+// SEG (segmented calls, launch_scan_b16w_seg): the workgroup's row block, column range, id offset and list slot come from the
+// work table a.sched instead of blockIdx / col_splits; everything else is shared.
+template <bool F16, int CAP, bool SEG = false>
 __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   char* stages = smem;                                                   // [2][W_STAGEB]
@@ -228,18 +245,32 @@ __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
   const int ownb = g & 1;                       // the query block (0 / 1) whose list this lane owns
   const int c = c16 + 16 * ownb;                // own query within the wave
 
-  const int split = blockIdx.x % a.col_splits;
-  const int64_t rb = blockIdx.x / a.col_splits;
-  const int64_t q0 = rb * W_QT;
-  int64_t t_begin = (int64_t)split * a.tiles_per_split;
-  int64_t t_end = t_begin + a.tiles_per_split;
-  if (t_end > a.tiles_total) t_end = a.tiles_total;
-  if (t_begin > t_end) t_begin = t_end;
+  int slot;                                     // first list slot of this workgroup's column range
+  int64_t q0, t_begin, t_end;
+  int64_t row0 = 0;                             // SEG: row of X of the block's first query
+  int nq = W_QT;                                // SEG: real queries of the block
+  uint32_t id_off = 0;                          // SEG: column of the candidate image -> row of Y
+  if constexpr (SEG) {
+    const int32_t* e = a.sched + (size_t)blockIdx.x * WSEG_ENTRY;
+    q0 = e[WSEG_QPOS]; row0 = e[WSEG_ROW0]; nq = e[WSEG_NQ];
+    t_begin = e[WSEG_T0]; t_end = e[WSEG_T1]; id_off = (uint32_t)e[WSEG_IDOFF]; slot = e[WSEG_SLOT];
+    if (t_begin > t_end) t_begin = t_end;
+  } else {
+    const int split = blockIdx.x % a.col_splits;
+    const int64_t rb = blockIdx.x / a.col_splits;
+    q0 = rb * W_QT;
+    t_begin = (int64_t)split * a.tiles_per_split;
+    t_end = t_begin + a.tiles_per_split;
+    if (t_end > a.tiles_total) t_end = a.tiles_total;
+    if (t_begin > t_end) t_begin = t_end;
+    slot = 2 * split;
+  }
   const int nkc = a.dp / W_KC;
   const int64_t steps = (t_end - t_begin) * nkc;
 
-  const int64_t qpos = q0 + 32 * wave + c;
-  const bool qvalid = qpos < a.n_rows;
+  const int64_t qpos = q0 + 32 * wave + c;      // position in the query image
+  const int64_t lrow = SEG ? row0 + 32 * wave + c : qpos;   // row of the lists and of the threshold buffers
+  const bool qvalid = SEG ? (32 * wave + c < nq) : (qpos < a.n_rows);
 
   // margin of this lane's query (see the header): 2 (E1 + E2)
   float margin;
@@ -379,7 +410,7 @@ __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
           // v[0..7]: rows of this lane's group g, v[8..15]: rows of the partner's group g ^ 1
           const int g4 = 4 * g;
           auto rowof = [g4](int r) -> uint32_t { return (uint32_t)((g4 ^ ((r & 8) >> 1)) + (r & 3) + 16 * ((r >> 2) & 1)); };
-          list.offer_tile(v, (uint32_t)(ct * W_CT + 32 * t), rowof, a.kk, margin);
+          list.offer_tile(v, (uint32_t)(ct * W_CT + 32 * t) + id_off, rowof, a.kk, margin);
           refresh_thr();
         }
       }
@@ -395,15 +426,15 @@ __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
   // written (the re-rank gathers about kk rows per list, not CAP).
   list.compact(a.kk, margin);
   if (qvalid) {
-    const int64_t lbase = qpos * a.lists_total + a.list_base + 2 * split + half;
+    const int64_t lbase = lrow * a.lists_total + a.list_base + slot + half;
     a.cand_cnt[lbase] = (uint32_t)list.cnt;
     for (int e = 0; e < list.cnt; ++e) {
       a.cand_ids[lbase * CAP + e] = list.ids[e * W_NT];
       if (a.cand_keys) a.cand_keys[lbase * CAP + e] = list.keys[e * W_NT];
     }
-    if (a.cand_keys && half == 0) a.margin_out[qpos] = margin;
-    if (list.proven > -kFltMax) atomicMax(a.seed + qpos, wide_enc(list.proven));
-    if (list.lost > kNegInf) atomicMax(a.lost + qpos, wide_enc(list.lost));
+    if (a.cand_keys && half == 0) a.margin_out[lrow] = margin;
+    if (list.proven > -kFltMax) atomicMax(a.seed + lrow, wide_enc(list.proven));
+    if (list.lost > kNegInf) atomicMax(a.lost + lrow, wide_enc(list.lost));
   }
 }
 
@@ -442,7 +473,7 @@ __global__ __launch_bounds__(256) void wide_seed_union_kernel(const uint32_t* ca
   if (lane == 0) atomicMax(seed + row, wide_enc(pk - margin[row]));
 }
 
-template <int CAP>
+template <int CAP, bool SEG = false>
 int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) {
   const size_t lds = scan_b16w_lds(CAP);
   auto go = [&](auto kern) -> int {
@@ -451,8 +482,8 @@ int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) 
     MMF_LAUNCH_CHECK();
     return MMF_OK;
   };
-  if (f16) return go(scan_b16w_kernel<true, CAP>);
-  return go(scan_b16w_kernel<false, CAP>);
+  if (f16) return go(scan_b16w_kernel<true, CAP, SEG>);
+  return go(scan_b16w_kernel<false, CAP, SEG>);
 }
 
 }  // namespace
@@ -491,6 +522,48 @@ int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L
   const int64_t grid = row_blocks * col_splits;
   if (grid_out) *grid_out = (int)grid;
   MMF_TRY(L.cap == W_CAP_SMALL ? launch_b16w_t<W_CAP_SMALL>(a, p.f16, grid, s) : launch_b16w_t<W_CAP_BIG>(a, p.f16, grid, s));
+  if (col_splits > 1) {
+    hipLaunchKernelGGL(wide_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
+                       p.kk, pn.seed, p.n_rows);
+    MMF_LAUNCH_CHECK();
+  }
+  return MMF_OK;
+}
+
+// Segmented scan (mmf_simtopk_segmented_wide): one workgroup per entry of the work table `sched` ([grid][8] int32,
+// device; the WSEG_* fields above).  p.n_rows: rows of X — lists, thresholds and margins are indexed by them, the operand images
+// by the table's positions.  `lists` = 2 x the largest split count of a segment; a segment with fewer ranges leaves the rest of its
+// rows' lists empty (the caller zeroes the counts).  With more than one range per segment the lists carry keys and margins and
+// wide_seed_union_kernel settles every row's threshold, as in launch_scan_b16w.
+int launch_scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, int lists, const CandLists& L, const ScanB16Panel& pn,
+                         hipStream_t s) {
+  if (grid <= 0 || p.n_rows <= 0) return MMF_OK;
+  if (!scan_b16w_supported(p.d, p.kk) || p.dp != scan_b16w_dp(p.d)) {
+    set_error("scan_b16w_seg: d = %lld (padded %d), k + self = %d outside 1024 < d <= 4096, k + self <= 20", (long long)p.d, p.dp, p.kk);
+    return MMF_E_INTERNAL;
+  }
+  const int col_splits = lists / 2;
+  if (lists < 2 || lists != 2 * col_splits || (col_splits & (col_splits - 1)) != 0) {
+    set_error("scan_b16w_seg: %d lists per row are no power-of-two number of pairs", lists);
+    return MMF_E_INTERNAL;
+  }
+  if (!sched) { set_error("scan_b16w_seg: work table missing"); return MMF_E_INTERNAL; }
+  if (!pn.seed) { set_error("scan_b16w_seg: threshold buffers missing"); return MMF_E_INTERNAL; }
+  if (pn.seed_stride < p.n_rows) { set_error("scan_b16w_seg: threshold buffers shorter than the rows"); return MMF_E_INTERNAL; }
+  if (pn.list_base != 0 || pn.seg_len != 0 || pn.id_off != 0) { set_error("scan_b16w_seg: no paneled form"); return MMF_E_INTERNAL; }
+  if (lists != L.lists) { set_error("scan_b16w_seg: %d lists per row for %d column splits", L.lists, col_splits); return MMF_E_INTERNAL; }
+  if (L.cap != scan_b16w_cap(p.kk)) { set_error("scan_b16w_seg: list capacity %d, expected %d", L.cap, scan_b16w_cap(p.kk)); return MMF_E_INTERNAL; }
+  if (col_splits > 1 && (!L.keys || !L.margin)) { set_error("scan_b16w_seg: column splits need the lists' keys and margins"); return MMF_E_INTERNAL; }
+  if (p.m_pad % W_CT != 0) { set_error("scan_b16w_seg: candidate image of %lld rows is no whole number of tiles", (long long)p.m_pad); return MMF_E_INTERNAL; }
+  ScanB16WArgs a{};
+  a.ZQ = p.ZQ; a.ZC = p.ZC; a.cb = p.cb; a.q_zn = p.q_zn; a.q_rn = p.q_rn; a.q_un = p.q_un; a.maxima = p.maxima;
+  a.n_rows = p.n_rows; a.kk = p.kk; a.metric = p.metric; a.d = (int)p.d; a.dp = p.dp;
+  a.tiles_total = p.m_pad / W_CT; a.tiles_per_split = a.tiles_total; a.col_splits = 1;   // unused: the table carries the ranges
+  a.lists_total = L.lists; a.list_base = 0;
+  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride;
+  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.cand_keys = L.keys; a.margin_out = L.margin;
+  a.sched = sched;
+  MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, true>(a, p.f16, grid, s)) : (launch_b16w_t<W_CAP_BIG, true>(a, p.f16, grid, s)));
   if (col_splits > 1) {
     hipLaunchKernelGGL(wide_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
                        p.kk, pn.seed, p.n_rows);

@@ -4,7 +4,7 @@ undirected dedup, max(0, cosine) weights.
 
 Segment s's edges are bit for bit those of ``build_hypergraph_knn_kmeans`` on that slide with both ids shifted by the
 segment's first node.  The three batched steps run once for the whole batch: ``simtopk_segmented`` for the
-neighbours, ``kmeans_fit_predict_segmented`` for the labels, ``ops.knn_clique_edges`` for the edge list, which comes out in
+neighbours (``wide_scan.simtopk_segmented`` where the feature dim is above 1024 and the wide 16-bit scan applies), ``kmeans_fit_predict_segmented`` for the labels, ``ops.knn_clique_edges`` for the edge list, which comes out in
 its documented order without a sort and costs one host read (the edge count).  The labels are scikit-learn's unless a seeding
 decision came within float32 noise of going the other way: ``ambiguous_draws`` / ``ambiguous_trials`` say for which segments.
 """
@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import ops, ragged
+from . import ops, ragged, wide_scan
 from .kmeans import segmented_labels
 from .build_hypergraph import preprocess_hypergraph
 from .build_hypergraph._common import compute_device, result_device_like_preprocess, to_gpu
@@ -33,7 +33,12 @@ def knn_kmeans_edges_segmented(X: torch.Tensor, k: int = 5, num_hyperedges: int 
     ragged.check_knn_sizes((p[1:] - p[:-1]).tolist(), k, what, n_clusters=num_hyperedges)
     ops._need_gpu(X, what)
     X = X.detach().float().contiguous()
-    nbr, _ = ops.simtopk_segmented(X, ptr=p, metric="neg_sq_l2", k=k, exclude_self=True)
+    # feature dims above 1024: the entry with the wide 16-bit scan behind it (one launch, not the exact pass per segment; the same
+    # bits — DESIGN.md §4.16)
+    if wide_scan.wide_scan_supported(X.shape[1], k, True):
+        nbr, _ = wide_scan.simtopk_segmented(X, ptr=p, metric="neg_sq_l2", k=k, exclude_self=True)
+    else:
+        nbr, _ = ops.simtopk_segmented(X, ptr=p, metric="neg_sq_l2", k=k, exclude_self=True)
     labels, draws, trials = segmented_labels(X, p, num_hyperedges)
     edge_index, edge_ptr = ops.knn_clique_edges(nbr, labels, num_hyperedges, ptr=p)
     if edge_index.shape[1] == 0:
