@@ -80,6 +80,11 @@ EXPORTS_WIDE = ["mmf_wide_scan_supported", "mmf_wide_scan_list_capacity"]
 # synchronisation behaviour is INTEGRATION.md's table "Wide segmented entries", pinned by tests/test_wide_segmented_cpu.py.
 EXPORTS_WIDE_SEG = ["mmf_simtopk_segmented_wide"]
 
+# The 16-bit top-k of the combined similarity (include/mmf_hg_topk16.h): an addition to ABI version 3 in a header
+# of its own.  Its synchronisation behaviour is INTEGRATION.md's table "16-bit top-k entries", pinned by
+# tests/test_simtopk_combined_fast_cpu.py.
+EXPORTS_TOPK16 = ["mmf_simtopk_combined_fast"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -145,7 +150,8 @@ def lib() -> ctypes.CDLL:
     L.mmf_wide_scan_supported.argtypes = [i64, ci, ci]
     L.mmf_wide_scan_list_capacity.argtypes = [ci, ci]
     L.mmf_simtopk_segmented_wide.argtypes = list(L.mmf_simtopk_segmented.argtypes)
-    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG:
+    L.mmf_simtopk_combined_fast.argtypes = list(L.mmf_simtopk_combined.argtypes)
+    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16:
         fn = getattr(L, name)
         if name not in ("mmf_last_error", "mmf_padded_dim", "mmf_super_patch_stats_streamed_bytes"):
             fn.restype = ci

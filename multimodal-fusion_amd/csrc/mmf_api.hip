@@ -852,6 +852,144 @@ int run_simtopk_combined(const char* who, const float* F, const float* P, int64_
   return MMF_OK;
 }
 
+// What MMF_PREC_AUTO does in mmf_simtopk_combined_fast: the 16-bit scan only for the (d, k) range where the whole call beat the
+// exact one by more than three times the exact arm's spread at every measured N (DESIGN.md §4.17,
+// profiles/simtopk_combined_fast_timing.txt): k = 5 (16-entry lists), d = 512 at N = 16384 / 65536 / 262144 — 2.87x / 3.36x /
+// 3.83x, the difference 23 / 92 / 542 times that spread — and d = 1536 at N = 65536 — 3.84x, 117 times.  Between the two measured
+// dims the epilogue's share only falls; outside 512 <= d <= 1536, or with the 32-entry lists of k + self > 11, nothing is
+// measured and AUTO stays exact (precision = MMF_PREC_FAST is served everywhere).
+static bool combined_fast_auto(int64_t d, int kk) { return d >= 512 && d <= 1536 && kk <= 11; }
+
+// mmf_simtopk_combined_fast (include/mmf_hg_topk16.h; entry and host checks in mmf_scan_b16c.hip), one graph, DESIGN.md §4.17:
+// row scalars of F and P, the 16-bit image of F, the scan of the combined key (launch_scan_b16c), the audit, the re-rank of the
+// combined key over the 16-bit lists, one readback.  The rows the audit or the re-rank flagged are answered by the exact pass
+// over slices of F against itself: their 128-row blocks, adjacent blocks merged into runs — all of F when more than a quarter
+// of the blocks hold a flagged row.  The values are the same bits by contract, so overwriting a block's clean rows changes nothing.
+int run_simtopk_combined_fast(const char* who, const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
+                              float lambda_g, int k, int exclude_self, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
+                              mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  const int self1 = exclude_self ? 1 : 0;
+  int prec = opts ? opts->precision : MMF_PREC_AUTO;
+  if (prec == MMF_PREC_AUTO) prec = combined_fast_auto(d, k + self1) ? MMF_PREC_FAST : MMF_PREC_EXACT;
+  const int ks = (int)std::min<int64_t>(k, n - self1);   // entries a row can have; the re-rank pads the rest with -1 / -inf
+  if (prec == MMF_PREC_EXACT || ks <= 0) {                // (one row, self excluded: nothing to scan)
+    const int64_t one_graph[2] = {0, n};
+    return run_simtopk_combined(who, F, P, n, d, dp, lambda_h, lambda_g, k, exclude_self, one_graph, 1, out_idx, out_val, opts, stats,
+                                device_id, hip_stream);
+  }
+  Request r{Call(who, device_id, hip_stream), F, n, F, n, d, MMF_F32, MMF_RBF, lambda_h, k, exclude_self, 0, 0,
+            out_idx, out_val, stats, opts && opts->profile};
+  r.kk = ks + self1;
+  r.precision = prec;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  MMF_TRY(r.call.begin());
+  const hipStream_t s = r.call.s;
+  const bool f16 = prec == MMF_PREC_FAST;
+  const int dpf = scan_b16c_dp(d), bcap = scan_b16c_cap(r.kk);
+  const int64_t n_pad = (n + 255) / 256 * 256, row_blocks = (n + 127) / 128, n_seed = row_blocks * 128;
+  // column splits: a power of two; enough workgroups for the device, no more ranges than column tiles, and no more lists than
+  // the re-rank gathers (launch_rerank_combined: lists x cap <= 1024)
+  int splits = 1;
+  const int forced = opts ? opts->col_splits : 0;
+  if (forced > 0) { while (splits < forced && splits < 32) splits <<= 1; }
+  else { while (row_blocks * splits < 256 && splits < 32) splits <<= 1; }
+  while (splits > 1 && (splits > row_blocks || 2 * splits * bcap > 1024)) splits >>= 1;
+  const int lists = 2 * splits;
+  constexpr int64_t kFailPeek = 1024;   // flagged row ids that come back with the fail count
+  const int64_t peek = std::min(n, kFailPeek);
+
+  const size_t need = 2 * ws_bytes(n, 4) + ws_bytes(8, 4) + HalfImage::bytes(n_pad, dpf) + b16_lists_bytes(n, lists, bcap) +
+                      FlagBlock::bytes(n) + ws_bytes(2 * n_seed, 4);
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* nf = ws.take<float>(n);
+  float* pn = ws.take<float>(n);
+  uint32_t* maxw = ws.take<uint32_t>(8);   // word 0: largest chain(f, f), word 4: largest chain(p, p)
+  HalfImage C;
+  C.carve(ws, n_pad, dpf);
+  const CandLists L = carve_b16_lists(ws, n, lists, bcap);
+  FlagBlock flags;
+  flags.carve(ws, n);
+  int32_t* seed = ws.take<int32_t>(2 * n_seed);
+  MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
+  MMF_HIP(hipMemsetAsync(maxw, 0, 32, s));
+  MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
+  MMF_TRY(flags.zero(s));
+  MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n_seed * 8, s));   // kSeedNone, thresholds and dropped keys
+
+  EventTimer t_prep, t_scan, t_sel, t_fb;
+  MMF_TRY(t_prep.start(r.profile, s));
+  MMF_TRY(launch_row_scalars(F, n, d, MMF_F32, MMF_RBF, nf, maxw, s));
+  MMF_TRY(launch_row_scalars(P, n, dp, MMF_F32, MMF_RBF, pn, maxw + 4, s));
+  MMF_TRY(launch_prep_half({F, n, d, MMF_F32, MMF_RBF, nf, maxw}, C, dpf, f16, s));
+  MMF_TRY(t_prep.stop(s));
+
+  int grid = 0;
+  MMF_TRY(t_scan.start(r.profile, s));
+  ScanB16Panel pnl;
+  pnl.seed = seed; pnl.seed_stride = n_seed;
+  const ScanB16Problem sp(C, C, n, n, n_pad, dpf, d, f16, MMF_RBF, r.kk);
+  const ScanB16Comb sc{P, pn, nf, maxw, maxw + 4, (int)dp, lambda_h, lambda_g};
+  MMF_TRY(launch_scan_b16c(sp, sc, splits, L, pnl, s, &grid));
+  MMF_TRY(launch_scan_b16_audit(pnl, L.overflow, n, s));
+  if (const char* e = getenv("MMF_DEBUG_FLAG_ROWS")) {   // test hook: send the first rows down the exact pass (FastTail::run's)
+    const int64_t f = atoll(e);
+    if (f > 0) MMF_HIP(hipMemsetAsync(L.overflow, 1, (size_t)(f < n ? f : n) * 4, s));
+  }
+  MMF_TRY(t_scan.stop(s));
+
+  SelectProblem q = r.select();
+  q.k = ks; q.out_stride = k;
+  q.rx = nf; q.cy = nf; q.Pq = P; q.Pc = P; q.pnq = pn; q.pnc = pn; q.dp = (int)dp; q.lambda_g = lambda_g;
+  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = stats ? flags.cand_total : nullptr;
+  MMF_TRY(t_sel.start(r.profile, s));
+  MMF_TRY(launch_rerank_combined(q, L, s));
+  MMF_TRY(t_sel.stop(s));
+
+  std::vector<int32_t> h_rows((size_t)peek);
+  MMF_HIP(hipMemcpyAsync(h_rows.data(), flags.fail_rows, (size_t)peek * 4, hipMemcpyDeviceToHost, s));
+  MMF_TRY(flags.read(stats != nullptr, s));   // the call's synchronisation
+  const int64_t h_fail = flags.h_fail4[0];
+  MMF_TRY(t_fb.start(r.profile && h_fail > 0, s));
+  if (h_fail > 0) {
+    h_rows.resize((size_t)h_fail);
+    if (h_fail > peek) {
+      MMF_HIP(hipMemcpyAsync(h_rows.data(), flags.fail_rows, (size_t)h_fail * 4, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipStreamSynchronize(s));
+    }
+    std::vector<char> hit((size_t)row_blocks, 0);
+    int64_t n_hit = 0;
+    for (int32_t row : h_rows) {
+      if (row < 0 || row >= n) { set_error("%s: flagged row %d outside the %lld rows (internal invariant)", who, row, (long long)n); return MMF_E_INTERNAL; }
+      if (!hit[(size_t)(row / 128)]) { hit[(size_t)(row / 128)] = 1; ++n_hit; }
+    }
+    ExactPass ex(r, nf, nf);
+    ex.same = true;
+    ex.P = P; ex.pn = pn; ex.dp = (int)dp; ex.lambda_g = lambda_g;
+    if (4 * n_hit > row_blocks) {
+      ex.add(ExactGroup{0, n, false, 0, n, ks});
+    } else {
+      for (int64_t b = 0; b < row_blocks; ++b) {
+        if (!hit[(size_t)b]) continue;
+        int64_t e = b;
+        while (e + 1 < row_blocks && hit[(size_t)(e + 1)]) ++e;
+        const int64_t row0 = b * 128, end = std::min(n, (e + 1) * 128);
+        ex.add(ExactGroup{row0, end - row0, false, 0, n, ks});
+        b = e;
+      }
+    }
+    Workspace aux;   // the f32 image and the exact lists, in the second workspace slot
+    MMF_TRY(r.call.workspace(ex.image_bytes() + ex.list_bytes(), &aux, 1));
+    ExactLists B;
+    B.carve(aux, ex.rows_total, ex.list_words, ex.cap(), false);
+    MMF_TRY(B.zero(s));
+    MMF_TRY(ex.run(aux, B));
+  }
+  MMF_TRY(t_fb.stop(s));
+  fill_stats(stats, prec, splits, grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), h_fail, flags.h_fail4[1], flags.h_fail4[2], flags.h_tot);
+  return MMF_OK;
+}
+
 }  // namespace mmf
 
 using namespace mmf;

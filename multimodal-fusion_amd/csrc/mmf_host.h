@@ -12,6 +12,7 @@
 
 #include "../../include/mmf_hg.h"
 #include "../../include/mmf_hg_topk.h"
+#include "../../include/mmf_hg_topk16.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -368,6 +369,28 @@ int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L
 // largest number of column ranges of a segment (a power of two).
 int launch_scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, int lists, const CandLists& L, const ScanB16Panel& pn,
                          hipStream_t s);
+
+// mmf_scan_b16c.hip: the 16-bit scan of the combined key eh + eg (mmf_simtopk_combined_fast), 1 <= d <= 4096,
+// k + self <= 20: the wide scan's structure with the position term formed in the epilogue.  One MMF_RBF operand image scanned
+// against itself (p.ZQ == p.ZC, p.n_rows == p.m, dp = d rounded up to 128); lists, threshold buffers and audit as launch_scan_b16w,
+// L.margin receives m0_i of margin_i(t) = m0_i + m1 |t|.
+struct ScanB16Comb {
+  const float* P; const float* pn;    // positions [n][dp] and chain(p, p) of every row (launch_row_scalars)
+  const float* nf;                    // chain(f, f) of every row
+  const uint32_t* max_nf;             // float bits of the largest nf: the word the prep took its scale from
+  const uint32_t* max_pn;             // float bits of the largest pn
+  int dp; float lambda_h, lambda_g;
+};
+int scan_b16c_supported(int64_t d, int kk);
+int scan_b16c_cap(int kk);
+int scan_b16c_dp(int64_t d);
+int launch_scan_b16c(const ScanB16Problem& p, const ScanB16Comb& c, int col_splits, const CandLists& L, const ScanB16Panel& pn, hipStream_t s,
+                     int* grid_out);
+// mmf_api.hip: mmf_simtopk_combined_fast behind its host checks (one graph) — 16-bit scan, audit, re-rank of the combined key,
+// exact pass over the row blocks of flagged rows; MMF_PREC_EXACT (and AUTO where the fast path does not pay): run_simtopk_combined
+int run_simtopk_combined_fast(const char* who, const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
+                              float lambda_g, int k, int exclude_self, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
+                              mmf_simtopk_stats* stats, int device_id, void* hip_stream);
 
 // mmf_dense.hip
 // Xp / Yp: f32 images of X and Y (launch_prep_f32; unused — may be null — for d <= 8 and MMF_RBF_DIRECT)
