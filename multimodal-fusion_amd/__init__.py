@@ -13,6 +13,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.super_patch_stats.*                       the statistics of that step for a slide whose similarity matrix does not fit: K recomputed in row panels
     mmf.combined_topk.*                           the k best columns per row of K_h * K_g (features x positions) of one graph or a batch, K never stored
     mmf.combined_topk16.*                         the same top-k of K_h * K_g of one graph from the 16-bit matrix cores, bit for bit (f16 / bf16 scan, exact re-rank)
+    mmf.combined_topk16_segmented.*               that 16-bit top-k for every graph of a ragged batch from one launch of the scan, bit for bit
     mmf.wide_scan.*                               what the wide 16-bit scan (feature dims 1025..4096) covers: host-only queries
     mmf.cohort.build_cohort_hypergraphs(...)      the four steps of process_single_file for every slide of a cohort, in memory
     mmf.build_hypergraph.*                        the reference's function names and signatures
@@ -35,6 +36,10 @@ from .combined_topk import build_topk_hypergraph_data, build_topk_weighted_hyper
 from . import combined_topk16  # noqa: F401,E402
 from .combined_topk16 import build_topk_weighted_hypergraph_fast, simtopk_combined_fast  # noqa: F401,E402
 
+from . import combined_topk16_segmented  # noqa: F401,E402
+from .combined_topk16_segmented import (build_topk_hypergraph_data_fast, build_topk_weighted_hypergraph_fast_segmented,  # noqa: F401,E402
+                                        simtopk_combined_fast_segmented)
+
 from . import wide_scan  # noqa: F401,E402
 from .wide_scan import list_capacity, wide_scan_supported  # noqa: F401,E402
 
@@ -44,4 +49,6 @@ __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combin
            "group_by_similarity_segmented", "filter_edges_by_median_segmented", "super_patches", "super_patch_stats", "cohort", "segment_sort_segmented",
            "pool_super_patches_segmented", "aggregate_wsi_super_patches_segmented", "build_cohort_hypergraphs", "combined_topk",
            "simtopk_combined", "build_topk_weighted_hypergraph", "build_topk_hypergraph_data", "wide_scan", "wide_scan_supported",
-           "list_capacity", "combined_topk16", "simtopk_combined_fast", "build_topk_weighted_hypergraph_fast"]
+           "list_capacity", "combined_topk16", "simtopk_combined_fast", "build_topk_weighted_hypergraph_fast",
+           "combined_topk16_segmented", "simtopk_combined_fast_segmented", "build_topk_weighted_hypergraph_fast_segmented",
+           "build_topk_hypergraph_data_fast"]

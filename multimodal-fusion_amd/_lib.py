@@ -85,6 +85,11 @@ EXPORTS_WIDE_SEG = ["mmf_simtopk_segmented_wide"]
 # tests/test_simtopk_combined_fast_cpu.py.
 EXPORTS_TOPK16 = ["mmf_simtopk_combined_fast"]
 
+# The segmented 16-bit top-k of the combined similarity (include/ext/mmf_hg_topk16_seg.h): an addition to ABI
+# version 3 in a header of its own.  Its synchronisation behaviour is INTEGRATION.md's table "Segmented 16-bit top-k entries",
+# pinned by tests/test_simtopk_combined_fast_segmented_cpu.py.
+EXPORTS_TOPK16_SEG = ["mmf_simtopk_combined_fast_segmented"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -151,7 +156,9 @@ def lib() -> ctypes.CDLL:
     L.mmf_wide_scan_list_capacity.argtypes = [ci, ci]
     L.mmf_simtopk_segmented_wide.argtypes = list(L.mmf_simtopk_segmented.argtypes)
     L.mmf_simtopk_combined_fast.argtypes = list(L.mmf_simtopk_combined.argtypes)
-    for name in EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16:
+    L.mmf_simtopk_combined_fast_segmented.argtypes = list(L.mmf_simtopk_combined.argtypes)
+    for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
+                 EXPORTS_TOPK16_SEG):
         fn = getattr(L, name)
         if name not in ("mmf_last_error", "mmf_padded_dim", "mmf_super_patch_stats_streamed_bytes"):
             fn.restype = ci

@@ -990,6 +990,218 @@ int run_simtopk_combined_fast(const char* who, const float* F, const float* P, i
   return MMF_OK;
 }
 
+// What MMF_PREC_AUTO does in mmf_simtopk_combined_fast_segmented: the 16-bit scan only for the (d, k) range where the whole call
+// beat combined_topk.simtopk_combined(ptr=...) by more than three times that arm's spread at EVERY measured batch of the range
+// (profiles/simtopk_combined_fast_segmented_timing.txt): k = 5 (16-entry lists), d = 512 at 2048 x 128, 1000
+// ragged 100..300, 64 x 4096 and 16 x 16384 rows — 46.5x / 26.0x / 5.0x / 3.6x, the difference 605 / 489 / 167 / 381 times that
+// spread — and d = 1536 at 64 x 4096 — 5.8x, 168 times.  Outside 512 <= d <= 1536, or with the 32-entry lists of k + self > 11,
+// nothing is measured and AUTO stays exact, as in the one-graph entry (precision = MMF_PREC_FAST is served everywhere).
+static bool combined_fast_seg_auto(int64_t d, int kk) { return d >= 512 && d <= 1536 && kk <= 11; }
+
+// The column ranges the segmented combined scan takes on its own: FastTail's rule applied to the call (double while the served
+// segments' row blocks x ranges stay below 256), capped at the one count that was measured — two.  At 4 segments of 4096 rows,
+// d = 512 (128 row blocks) two ranges took 0.801 ms against 0.956 ms for one, 11.4 times the spread of the
+// one-range arm, where the project's rule asks for more than three; four ranges (0.923 ms) already give some of it back, and no
+// smaller batch was measured.  opts->col_splits forces a count either way.
+static int combined_fast_seg_auto_splits() { return 2; }
+
+// mmf_simtopk_combined_fast_segmented (include/ext/mmf_hg_topk16_seg.h; entry and host checks in mmf_scan_b16c.hip), DESIGN.md
+// §4.18.  Every segment with at least k admissible columns is copied into ONE 16-bit image, padded to whole tiles of 128, and
+// scanned by one table-driven launch (launch_scan_b16c_seg); audit, re-rank of the combined key over all rows, one readback.  The
+// other segments — and every segment under MMF_PREC_EXACT — are slices of the exact pass, as run_simtopk_combined ranks them; the
+// rows the audit or the re-rank flagged are answered per segment by the same pass over their 128-row blocks (counted from the
+// segment's first row, adjacent blocks merged into runs; the whole segment when more than a quarter of its blocks hold one).
+int run_simtopk_combined_fast_segmented(const char* who, const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
+                                        float lambda_g, int k, int exclude_self, const int64_t* ptr, int64_t n_seg, int64_t* out_idx,
+                                        float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  const int self1 = exclude_self ? 1 : 0;
+  const int64_t S = n_seg;
+  int prec = opts ? opts->precision : MMF_PREC_AUTO;
+  if (prec == MMF_PREC_AUTO) prec = combined_fast_seg_auto(d, k + self1) ? MMF_PREC_FAST : MMF_PREC_EXACT;
+  // segments the 16-bit scan serves: at least k admissible columns (the others are ranked exactly for what they have)
+  std::vector<char> served((size_t)S, 0);
+  int64_t R = 0, n_pos = 0;   // row blocks and image positions of the served segments
+  for (int64_t g = 0; g < S && prec != MMF_PREC_EXACT; ++g) {
+    const int64_t ng = ptr[g + 1] - ptr[g];
+    if (ng - self1 < k || ng == 0) continue;
+    served[(size_t)g] = 1;
+    R += (ng + 127) / 128;
+    n_pos += (ng + 127) / 128 * 128;
+  }
+  if (R == 0)   // MMF_PREC_EXACT, or nothing to scan
+    return run_simtopk_combined(who, F, P, n, d, dp, lambda_h, lambda_g, k, exclude_self, ptr, S, out_idx, out_val, opts, stats, device_id,
+                                hip_stream);
+  if (n_pos >= (int64_t(1) << 31)) { set_error("%s: the padded image of %lld positions is too large", who, (long long)n_pos); return MMF_E_UNSUPPORTED; }
+  Request r{Call(who, device_id, hip_stream), F, n, F, n, d, MMF_F32, MMF_RBF, lambda_h, k, exclude_self, 0, 0,
+            out_idx, out_val, stats, opts && opts->profile};
+  r.kk = k + self1;
+  r.precision = prec;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  MMF_TRY(r.call.begin());
+  const hipStream_t s = r.call.s;
+  const bool f16 = prec == MMF_PREC_FAST;
+  const int dpf = scan_b16c_dp(d), bcap = scan_b16c_cap(r.kk);
+  // Column ranges (DESIGN.md §4.16's rule): the call's count is a power of two bounded by the re-rank's gather (2 x ranges x cap
+  // <= 1024); every segment takes at most that many, and at most one per tile of its own, rounded down to a power of two
+  int call_splits = 1, max_splits = 1;
+  {
+    const int forced = opts ? opts->col_splits : 0;
+    const auto fits = [&](int sp) { return 2 * sp * bcap <= 1024; };
+    if (forced > 0) { while (call_splits < forced && fits(2 * call_splits)) call_splits <<= 1; }
+    else { while (R * call_splits < 256 && 2 * call_splits <= combined_fast_seg_auto_splits() && fits(2 * call_splits)) call_splits <<= 1; }
+  }
+  // the work table (one entry per row block and column range) and the gather table (image position -> row of F, -1: padding)
+  std::vector<int32_t> sched, gather((size_t)n_pos, -1);
+  {
+    int64_t pos = 0;
+    for (int64_t g = 0; g < S; ++g) {
+      if (!served[(size_t)g]) continue;
+      const int64_t ng = ptr[g + 1] - ptr[g], tiles = (ng + 127) / 128, t0 = pos / 128;
+      int sp = 1;
+      while (2 * sp <= call_splits && 2 * sp <= tiles) sp <<= 1;
+      if (sp > max_splits) max_splits = sp;
+      const int64_t tps = (tiles + sp - 1) / sp;
+      for (int64_t b = 0; b < ng; b += 128) {
+        for (int c = 0; c < sp; ++c) {
+          const int64_t tb = std::min(t0 + c * tps, t0 + tiles), te = std::min(tb + tps, t0 + tiles);
+          const int32_t e[8] = {(int32_t)(pos + b), (int32_t)(ptr[g] + b), (int32_t)std::min<int64_t>(ng - b, 128), (int32_t)tb, (int32_t)te,
+                                (int32_t)(uint32_t)(ptr[g] - pos), 2 * c, (int32_t)(ptr[g + 1] - 1)};
+          sched.insert(sched.end(), e, e + 8);
+        }
+      }
+      for (int64_t i = 0; i < ng; ++i) gather[(size_t)(pos + i)] = (int32_t)(ptr[g] + i);
+      pos += tiles * 128;
+    }
+  }
+  const int64_t grid = (int64_t)sched.size() / 8;
+  const int lists = 2 * max_splits;
+  const int64_t n_img = (n_pos + 255) / 256 * 256;
+  constexpr int64_t kFailPeek = 1024;   // flagged row ids that come back with the fail count
+  const int64_t peek = std::min(n, kFailPeek);
+
+  const size_t need = 2 * ws_bytes(n, 4) + ws_bytes(8, 4) + HalfImage::bytes(n_img, dpf) + ws_bytes(sched.size(), 4) + ws_bytes(n_pos, 4) +
+                      b16_lists_bytes(n, lists, bcap) + FlagBlock::bytes(n) + ws_bytes(2 * (size_t)n, 4);
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* nf = ws.take<float>(n);
+  float* pn = ws.take<float>(n);
+  uint32_t* maxw = ws.take<uint32_t>(8);   // word 0: largest chain(f, f) of the batch, word 4: largest chain(p, p)
+  HalfImage C;
+  C.carve(ws, n_img, dpf);
+  int32_t* d_sched = ws.take<int32_t>(sched.size());
+  int32_t* d_gather = ws.take<int32_t>(n_pos);
+  const CandLists L = carve_b16_lists(ws, n, lists, bcap);
+  FlagBlock flags;
+  flags.carve(ws, n);
+  int32_t* seed = ws.take<int32_t>(2 * (size_t)n);
+  MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
+  MMF_HIP(hipMemsetAsync(maxw, 0, 32, s));
+  // rows of segments the scan does not serve, and the unused ranges of a segment with fewer than max_splits, keep empty lists
+  MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));
+  MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
+  MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
+  MMF_TRY(flags.zero(s));
+  MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n * 8, s));   // kSeedNone, thresholds and dropped keys
+
+  EventTimer t_prep, t_scan, t_sel, t_fb;
+  MMF_TRY(t_prep.start(r.profile, s));
+  MMF_TRY(launch_row_scalars(F, n, d, MMF_F32, MMF_RBF, nf, maxw, s));
+  MMF_TRY(launch_row_scalars(P, n, dp, MMF_F32, MMF_RBF, pn, maxw + 4, s));
+  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
+  MMF_TRY(upload_table(s, d_gather, gather.data(), (size_t)n_pos * 4));
+  MMF_TRY(launch_prep_half_gather({F, n, d, MMF_F32, MMF_RBF, nf, maxw}, d_gather, n_pos, C, dpf, f16, s));
+  MMF_TRY(t_prep.stop(s));
+
+  MMF_TRY(t_scan.start(r.profile, s));
+  ScanB16Panel pnl;
+  pnl.seed = seed; pnl.seed_stride = n;
+  const ScanB16Problem sp(C, C, n, n, n_img, dpf, d, f16, MMF_RBF, r.kk);
+  const ScanB16Comb sc{P, pn, nf, maxw, maxw + 4, (int)dp, lambda_h, lambda_g};
+  MMF_TRY(launch_scan_b16c_seg(sp, sc, d_sched, grid, lists, L, pnl, s));
+  MMF_TRY(launch_scan_b16_audit(pnl, L.overflow, n, s));
+  if (const char* e = getenv("MMF_DEBUG_FLAG_ROWS")) {   // test hook: send the first rows down the exact pass (FastTail::run's)
+    const int64_t f = atoll(e);
+    if (f > 0) MMF_HIP(hipMemsetAsync(L.overflow, 1, (size_t)(f < n ? f : n) * 4, s));
+  }
+  MMF_TRY(t_scan.stop(s));
+
+  SelectProblem q = r.select();
+  q.out_stride = k;
+  q.rx = nf; q.cy = nf; q.Pq = P; q.Pc = P; q.pnq = pn; q.pnc = pn; q.dp = (int)dp; q.lambda_g = lambda_g;
+  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = stats ? flags.cand_total : nullptr;
+  MMF_TRY(t_sel.start(r.profile, s));
+  MMF_TRY(launch_rerank_combined(q, L, s));   // all rows: those of unserved segments come back flagged and are redone below
+  MMF_TRY(t_sel.stop(s));
+
+  std::vector<int32_t> h_rows((size_t)peek);
+  MMF_HIP(hipMemcpyAsync(h_rows.data(), flags.fail_rows, (size_t)peek * 4, hipMemcpyDeviceToHost, s));
+  MMF_TRY(flags.read(stats != nullptr, s));   // the call's synchronisation
+  const int64_t h_fail = flags.h_fail4[0];
+  h_rows.resize((size_t)h_fail);
+  if (h_fail > peek) {
+    MMF_HIP(hipMemcpyAsync(h_rows.data(), flags.fail_rows, (size_t)h_fail * 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+  }
+  std::sort(h_rows.begin(), h_rows.end());
+  if (h_fail > 0 && (h_rows.front() < 0 || h_rows.back() >= n)) {
+    set_error("%s: flagged row outside the %lld rows (internal invariant)", who, (long long)n);
+    return MMF_E_INTERNAL;
+  }
+
+  // ---- exact pass: the segments the scan did not serve, and per served segment the blocks of its flagged rows ---------------
+  ExactPass ex(r, nf, nf);
+  ex.same = true;
+  ex.P = P; ex.pn = pn; ex.dp = (int)dp; ex.lambda_g = lambda_g;
+  int64_t fallback_rows = 0;
+  size_t e = 0;
+  for (int64_t g = 0; g < S; ++g) {
+    const int64_t ng = ptr[g + 1] - ptr[g];
+    const size_t e0 = e;
+    while (e < h_rows.size() && h_rows[e] < ptr[g + 1]) ++e;
+    if (ng == 0) continue;
+    if (!served[(size_t)g]) {
+      const int64_t ks = std::min<int64_t>(k, ng - self1);
+      if (ks > 0) { ex.add(ExactGroup{ptr[g], ng, false, ptr[g], ng, (int)ks}); continue; }
+      // one row, self excluded: -1 / -inf
+      MMF_HIP(hipMemsetAsync(out_idx + ptr[g] * k, 0xff, (size_t)ng * k * 8, s));
+      MMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out_val + ptr[g] * k), (int)0xff800000u, (size_t)ng * k, s));
+      continue;
+    }
+    if (e == e0) continue;
+    fallback_rows += (int64_t)(e - e0);
+    const int64_t nb = (ng + 127) / 128;
+    std::vector<char> hit((size_t)nb, 0);
+    int64_t n_hit = 0;
+    for (size_t i = e0; i < e; ++i) {
+      const int64_t b = (h_rows[i] - ptr[g]) / 128;
+      if (!hit[(size_t)b]) { hit[(size_t)b] = 1; ++n_hit; }
+    }
+    if (4 * n_hit > nb) { ex.add(ExactGroup{ptr[g], ng, false, ptr[g], ng, k}); continue; }
+    for (int64_t b = 0; b < nb; ++b) {
+      if (!hit[(size_t)b]) continue;
+      int64_t l = b;
+      while (l + 1 < nb && hit[(size_t)(l + 1)]) ++l;
+      const int64_t row0 = ptr[g] + b * 128, end = std::min(ptr[g + 1], ptr[g] + (l + 1) * 128);
+      ex.add(ExactGroup{row0, end - row0, false, ptr[g], ng, k});
+      b = l;
+    }
+  }
+  MMF_TRY(t_fb.start(r.profile && !ex.pieces.empty(), s));
+  if (!ex.pieces.empty()) {
+    Workspace aux;   // the f32 image and the exact lists, in the second workspace slot
+    MMF_TRY(r.call.workspace(ex.image_bytes() + ex.list_bytes(), &aux, 1));
+    ExactLists B;
+    B.carve(aux, ex.rows_total, ex.list_words, ex.cap(), false);
+    MMF_TRY(B.zero(s));
+    MMF_TRY(ex.run(aux, B));
+  }
+  MMF_TRY(t_fb.stop(s));
+  const int64_t overflow_rows = std::min<int64_t>(flags.h_fail4[1], fallback_rows);
+  fill_stats(stats, prec, max_splits, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback_rows, overflow_rows,
+             fallback_rows - overflow_rows, flags.h_tot);
+  return MMF_OK;
+}
+
 }  // namespace mmf
 
 using namespace mmf;

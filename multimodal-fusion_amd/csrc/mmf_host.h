@@ -13,6 +13,7 @@
 #include "../../include/mmf_hg.h"
 #include "../../include/mmf_hg_topk.h"
 #include "../../include/mmf_hg_topk16.h"
+#include "../../include/ext/mmf_hg_topk16_seg.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -386,11 +387,20 @@ int scan_b16c_cap(int kk);
 int scan_b16c_dp(int64_t d);
 int launch_scan_b16c(const ScanB16Problem& p, const ScanB16Comb& c, int col_splits, const CandLists& L, const ScanB16Panel& pn, hipStream_t s,
                      int* grid_out);
+// the same scan over a ragged batch: one workgroup per entry of the device work table `sched` ([grid][8] int32);
+// p.m_pad: positions of the one image, every segment padded to whole tiles of 128; `lists` = 2 x the largest range count
+int launch_scan_b16c_seg(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, const CandLists& L,
+                         const ScanB16Panel& pn, hipStream_t s);
 // mmf_api.hip: mmf_simtopk_combined_fast behind its host checks (one graph) — 16-bit scan, audit, re-rank of the combined key,
 // exact pass over the row blocks of flagged rows; MMF_PREC_EXACT (and AUTO where the fast path does not pay): run_simtopk_combined
 int run_simtopk_combined_fast(const char* who, const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
                               float lambda_g, int k, int exclude_self, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
                               mmf_simtopk_stats* stats, int device_id, void* hip_stream);
+// mmf_api.hip: mmf_simtopk_combined_fast_segmented behind its host checks (ptr: host offsets of n_seg >= 0 segments) — one table-driven
+// launch of the 16-bit scan for every segment with at least k admissible columns, the exact pass for the others and for flagged rows
+int run_simtopk_combined_fast_segmented(const char* who, const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
+                                        float lambda_g, int k, int exclude_self, const int64_t* ptr, int64_t n_seg, int64_t* out_idx,
+                                        float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream);
 
 // mmf_dense.hip
 // Xp / Yp: f32 images of X and Y (launch_prep_f32; unused — may be null — for d <= 8 and MMF_RBF_DIRECT)

@@ -46,6 +46,11 @@
 // the columns with A >= T - margin_i(T), T the kk-th best A over ALL columns — holds at most CAP columns is never flagged.
 // A flagged row is answered by the exact pass.  A scale outside f32's reach (|e| > 60: a would overflow or vanish) flags
 // every row.
+//
+// Segmented form (mmf_simtopk_combined_fast_segmented, include/ext/mmf_hg_topk16_seg.h): the same kernel with
+// SEG = true takes its row block, column range, id offset, list slot and clamp rows from a host-built work table, one entry per
+// workgroup, over ONE image in which every segment is padded to whole tiles of 128.  Scale and maxima are the batch's — a superset
+// of any one segment's rows, so m0_i is at least a per-segment call's — and a row's band is taken inside its own segment.
 #include <math.h>
 #include <string.h>
 
@@ -110,6 +115,22 @@ struct ScanB16CArgs {
   uint32_t* cand_cnt; uint32_t* cand_ids;
   float* cand_keys;          // approximate keys of the entries, or nullptr
   float* margin_out;         // [n_rows] m0_i, written with cand_keys
+  const int32_t* sched;      // SEG kernels only: [grid][CSEG_ENTRY] work table (launch_scan_b16c_seg)
+};
+
+// One entry of the segmented work table (the layout of mmf_scan_b16w.hip's, plus the clamp row): a workgroup = one row block of
+// one segment against one column range of that segment.  There is ONE operand image (X is Y), padded per segment to whole tiles
+// of 128: Z, cb and zn / rn / un are addressed by image position; nf, P, pn, the lists and the threshold buffers by row of F.
+enum : int {
+  CSEG_QPOS = 0,    // position of the row block's first query in the image (a multiple of 128)
+  CSEG_ROW0 = 1,    // row of F of that query
+  CSEG_NQ = 2,      // real queries of the block (<= 128)
+  CSEG_T0 = 3,      // first and end tile of the column range, in the image (tiles of 128)
+  CSEG_T1 = 4,
+  CSEG_IDOFF = 5,   // ptr[s] - image position of the segment's first column (mod 2^32): lists hold global rows of F
+  CSEG_SLOT = 6,    // first list slot of this range (2 x split)
+  CSEG_LAST = 7,    // global row of the segment's last row: the clamp of the candidates' position / chain reads
+  CSEG_ENTRY = 8
 };
 
 __device__ __forceinline__ float comb_margin(float m0, float t) { return m0 + C_M1 * __builtin_fabsf(t); }
@@ -229,7 +250,9 @@ constexpr size_t scan_b16c_lds(int cap) {
   return (size_t)2 * C_STAGEB + (size_t)2 * C_CT * 4 + (size_t)2 * C_CT * 9 * 4 + (size_t)cap * C_NT * 8;
 }
 
-template <bool F16, int CAP>
+// SEG (segmented calls, launch_scan_b16c_seg): the workgroup's row block, column range, id offset, list slot and clamp rows come
+// from the work table a.sched instead of blockIdx / col_splits; everything else is shared.
+template <bool F16, int CAP, bool SEG = false>
 __global__ __launch_bounds__(C_NT, 1) void scan_b16c_kernel(ScanB16CArgs a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   char* stages = smem;                                                   // [2][C_STAGEB]
@@ -248,20 +271,35 @@ __global__ __launch_bounds__(C_NT, 1) void scan_b16c_kernel(ScanB16CArgs a) {
   const int ownb = g & 1;                       // the query block (0 / 1) whose list this lane owns
   const int c = c16 + 16 * ownb;                // own query within the wave
 
-  const int split = blockIdx.x % a.col_splits;
-  const int64_t rb = blockIdx.x / a.col_splits;
-  const int64_t q0 = rb * C_QT;
-  int64_t t_begin = (int64_t)split * a.tiles_per_split;
-  int64_t t_end = t_begin + a.tiles_per_split;
-  if (t_end > a.tiles_total) t_end = a.tiles_total;
-  if (t_begin > t_end) t_begin = t_end;
-  const int slot = 2 * split;
+  int slot;                                     // first list slot of this workgroup's column range
+  int64_t q0, t_begin, t_end;
+  int64_t m;                                    // candidate rows are clamped at m - 1 (SEG: the segment's last row)
+  int64_t row0 = 0;                             // SEG: row of F of the block's first query
+  int nq = C_QT;                                // SEG: real queries of the block
+  uint32_t id_off = 0;                          // SEG: column of the image -> row of F
+  if constexpr (SEG) {
+    const int32_t* e = a.sched + (size_t)blockIdx.x * CSEG_ENTRY;
+    q0 = e[CSEG_QPOS]; row0 = e[CSEG_ROW0]; nq = e[CSEG_NQ];
+    t_begin = e[CSEG_T0]; t_end = e[CSEG_T1]; id_off = (uint32_t)e[CSEG_IDOFF]; slot = e[CSEG_SLOT];
+    m = (int64_t)e[CSEG_LAST] + 1;
+    if (t_begin > t_end) t_begin = t_end;
+  } else {
+    const int split = blockIdx.x % a.col_splits;
+    const int64_t rb = blockIdx.x / a.col_splits;
+    q0 = rb * C_QT;
+    t_begin = (int64_t)split * a.tiles_per_split;
+    t_end = t_begin + a.tiles_per_split;
+    if (t_end > a.tiles_total) t_end = a.tiles_total;
+    if (t_begin > t_end) t_begin = t_end;
+    slot = 2 * split;
+    m = a.n_rows;
+  }
   const int nkc = a.dp / C_KC;
   const int64_t steps = (t_end - t_begin) * nkc;
-  const int64_t m = a.n_rows;
 
-  const int64_t qpos = q0 + 32 * wave + c;      // own query: row of the image, of the lists and of the threshold buffers
-  const bool qvalid = qpos < a.n_rows;
+  const int64_t qpos = q0 + 32 * wave + c;      // own query: row of the image; without SEG also of the lists and threshold buffers
+  const int64_t lrow = SEG ? row0 + 32 * wave + c : qpos;   // row of F: lists, threshold buffers, margins
+  const bool qvalid = SEG ? (32 * wave + c < nq) : (qpos < a.n_rows);
 
   // a = 2 lambda_h / s^2 from the prep's scale (prep_half_kernel's formula on the same word)
   float av;
@@ -288,9 +326,10 @@ __global__ __launch_bounds__(C_NT, 1) void scan_b16c_kernel(ScanB16CArgs a) {
   {
     const float PNB = __uint_as_float(a.max_pn[0]);
     const float ge = a.lambda_g * (float)(2 * a.dpp + 4) * C_U * 1.01f;
-    int64_t qa = q0 + 32 * wave + c16, qb = qa + 16;
-    if (qa > m - 1) qa = m - 1;
-    if (qb > m - 1) qb = m - 1;
+    int64_t qa = (SEG ? row0 : q0) + 32 * wave + c16, qb = qa + 16;
+    const int64_t qlast = SEG ? row0 + nq - 1 : m - 1;   // SEG: the block's last real query
+    if (qa > qlast) qa = qlast;
+    if (qb > qlast) qb = qlast;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       pq0[e] = (e < a.dpp) ? a.P[qa * a.dpp + e] : 0.0f;
@@ -340,11 +379,11 @@ __global__ __launch_bounds__(C_NT, 1) void scan_b16c_kernel(ScanB16CArgs a) {
     if (kc == 0) {
       if (tid < C_CT) {
         rcb = a.cb[ct * C_CT + tid];
-        int64_t j = ct * C_CT + tid;
+        int64_t j = SEG ? (int64_t)((uint32_t)(ct * C_CT + tid) + id_off) : ct * C_CT + tid;
         if (j > m - 1) j = m - 1;
         rpn = pnc[j];
       }
-      int64_t j = ct * C_CT + (tid >> 1);
+      int64_t j = SEG ? (int64_t)((uint32_t)(ct * C_CT + (tid >> 1)) + id_off) : ct * C_CT + (tid >> 1);
       if (j > m - 1) j = m - 1;
       const int e0 = 4 * (tid & 1);
 #pragma unroll
@@ -490,7 +529,7 @@ __global__ __launch_bounds__(C_NT, 1) void scan_b16c_kernel(ScanB16CArgs a) {
             // v[0..7]: rows of this lane's group g, v[8..15]: rows of the partner's group g ^ 1
             const int g4 = 4 * g;
             auto rowof = [g4](int r) -> uint32_t { return (uint32_t)((g4 ^ ((r & 8) >> 1)) + (r & 3) + 16 * ((r >> 2) & 1)); };
-            list.offer_tile(v, (uint32_t)(ct * C_CT + 32 * t), rowof, a.kk, m0);
+            list.offer_tile(v, (uint32_t)(ct * C_CT + 32 * t) + id_off, rowof, a.kk, m0);
             refresh_thr();
           }
         }
@@ -507,16 +546,16 @@ __global__ __launch_bounds__(C_NT, 1) void scan_b16c_kernel(ScanB16CArgs a) {
   // written (the re-rank gathers about kk rows per list, not CAP).
   list.compact(a.kk, m0);
   if (qvalid) {
-    const int64_t lbase = qpos * a.lists_total + slot + half;
+    const int64_t lbase = lrow * a.lists_total + slot + half;
     a.cand_cnt[lbase] = (uint32_t)list.cnt;
     for (int e = 0; e < list.cnt; ++e) {
       a.cand_ids[lbase * CAP + e] = list.ids[e * C_NT];
       if (a.cand_keys) a.cand_keys[lbase * CAP + e] = list.keys[e * C_NT];
     }
-    if (a.cand_keys && half == 0) a.margin_out[qpos] = m0;
-    if (list.proven > -kFltMax) atomicMax(a.seed + qpos, comb_enc(list.proven));
-    if (list.lost > kNegInf) atomicMax(a.lost + qpos, comb_enc(list.lost));
-    if (bad_scale && half == 0) atomicMax(a.lost + qpos, comb_enc(kFltMax));   // no usable key: the exact pass answers the row
+    if (a.cand_keys && half == 0) a.margin_out[lrow] = m0;
+    if (list.proven > -kFltMax) atomicMax(a.seed + lrow, comb_enc(list.proven));
+    if (list.lost > kNegInf) atomicMax(a.lost + lrow, comb_enc(list.lost));
+    if (bad_scale && half == 0) atomicMax(a.lost + lrow, comb_enc(kFltMax));   // no usable key: the exact pass answers the row
   }
 }
 
@@ -553,7 +592,7 @@ __global__ __launch_bounds__(256) void comb_seed_union_kernel(const uint32_t* ca
   if (lane == 0) atomicMax(seed + row, comb_enc(pk - comb_margin(m0[row], pk)));
 }
 
-template <int CAP>
+template <int CAP, bool SEG = false>
 int launch_b16c_t(const ScanB16CArgs& a, bool f16, int64_t grid, hipStream_t s) {
   const size_t lds = scan_b16c_lds(CAP);
   auto go = [&](auto kern) -> int {
@@ -562,6 +601,10 @@ int launch_b16c_t(const ScanB16CArgs& a, bool f16, int64_t grid, hipStream_t s) 
     MMF_LAUNCH_CHECK();
     return MMF_OK;
   };
+  if constexpr (SEG) {
+    if (f16) return go(scan_b16c_kernel<true, CAP, true>);
+    return go(scan_b16c_kernel<false, CAP, true>);
+  }
   if (f16) return go(scan_b16c_kernel<true, CAP>);
   return go(scan_b16c_kernel<false, CAP>);
 }
@@ -614,6 +657,50 @@ int launch_scan_b16c(const ScanB16Problem& p, const ScanB16Comb& c, int col_spli
   return MMF_OK;
 }
 
+// Segmented scan (mmf_simtopk_combined_fast_segmented): one workgroup per entry of the work table `sched`
+// ([grid][8] int32, device; the CSEG_* fields above).  p.n_rows = p.m: rows of F — lists, thresholds and margins are indexed by
+// them; p.m_pad: positions of the one operand image, every segment padded to whole tiles of 128.  `lists` = 2 x the largest range
+// count of a segment; a segment with fewer ranges leaves the rest of its rows' lists empty (the caller zeroes the counts).  With
+// more than one range per segment the lists carry keys and margins and comb_seed_union_kernel settles every row's threshold.
+int launch_scan_b16c_seg(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, const CandLists& L,
+                         const ScanB16Panel& pn, hipStream_t s) {
+  if (grid <= 0 || p.n_rows <= 0) return MMF_OK;
+  if (!scan_b16c_supported(p.d, p.kk) || p.dp != scan_b16c_dp(p.d) || p.metric != MMF_RBF) {
+    set_error("scan_b16c_seg: d = %lld (padded %d), k + self = %d, metric %d outside 1 <= d <= 4096, k + self <= 20, MMF_RBF", (long long)p.d,
+              p.dp, p.kk, p.metric);
+    return MMF_E_INTERNAL;
+  }
+  if (p.ZQ != p.ZC || p.n_rows != p.m) { set_error("scan_b16c_seg: one image against itself only"); return MMF_E_INTERNAL; }
+  if (!c.P || !c.pn || !c.nf || !c.max_nf || !c.max_pn || c.dp < 1 || c.dp > 8) { set_error("scan_b16c_seg: positions, chains and maxima (1 <= dp <= 8) missing"); return MMF_E_INTERNAL; }
+  const int col_splits = lists / 2;
+  if (lists < 2 || lists != 2 * col_splits || (col_splits & (col_splits - 1)) != 0) {
+    set_error("scan_b16c_seg: %d lists per row are no power-of-two number of pairs", lists);
+    return MMF_E_INTERNAL;
+  }
+  if (!sched) { set_error("scan_b16c_seg: work table missing"); return MMF_E_INTERNAL; }
+  if (!pn.seed || pn.seed_stride < p.n_rows) { set_error("scan_b16c_seg: threshold buffers missing"); return MMF_E_INTERNAL; }
+  if (lists != L.lists) { set_error("scan_b16c_seg: %d lists per row for %d column splits", L.lists, col_splits); return MMF_E_INTERNAL; }
+  if (L.cap != scan_b16c_cap(p.kk)) { set_error("scan_b16c_seg: list capacity %d, expected %d", L.cap, scan_b16c_cap(p.kk)); return MMF_E_INTERNAL; }
+  if (col_splits > 1 && (!L.keys || !L.margin)) { set_error("scan_b16c_seg: column splits need the lists' keys and margins"); return MMF_E_INTERNAL; }
+  if (p.m_pad % C_CT != 0) { set_error("scan_b16c_seg: image of %lld positions is no whole number of tiles", (long long)p.m_pad); return MMF_E_INTERNAL; }
+  ScanB16CArgs a{};
+  a.Z = p.ZC; a.cb = p.cb; a.q_zn = p.q_zn; a.q_rn = p.q_rn; a.q_un = p.q_un; a.maxima = p.maxima;
+  a.nf = c.nf; a.P = c.P; a.pn = c.pn; a.max_nf = c.max_nf; a.max_pn = c.max_pn; a.lambda_h = c.lambda_h; a.lambda_g = c.lambda_g; a.dpp = c.dp;
+  a.n_rows = p.n_rows; a.kk = p.kk; a.d = (int)p.d; a.dp = p.dp;
+  a.tiles_total = p.m_pad / C_CT; a.tiles_per_split = a.tiles_total; a.col_splits = 1;   // unused: the table carries the ranges
+  a.lists_total = L.lists;
+  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride;
+  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.cand_keys = L.keys; a.margin_out = L.margin;
+  a.sched = sched;
+  MMF_TRY(L.cap == C_CAP_SMALL ? (launch_b16c_t<C_CAP_SMALL, true>(a, p.f16, grid, s)) : (launch_b16c_t<C_CAP_BIG, true>(a, p.f16, grid, s)));
+  if (col_splits > 1) {
+    hipLaunchKernelGGL(comb_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
+                       p.kk, pn.seed, p.n_rows);
+    MMF_LAUNCH_CHECK();
+  }
+  return MMF_OK;
+}
+
 }  // namespace mmf
 
 using namespace mmf;
@@ -653,6 +740,42 @@ int mmf_simtopk_combined_fast(const float* F, const float* P, int64_t n, int64_t
   if (n == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return MMF_OK; }
   return run_simtopk_combined_fast(who, F, P, n, d, dp, lambda_h, lambda_g, k, exclude_self, out_idx, out_val, opts, stats, device_id,
                                    hip_stream);
+}
+
+// include/ext/mmf_hg_topk16_seg.h, DESIGN.md §4.18: a ragged batch in one launch of the combined-key 16-bit scan.  The checks are
+// mmf_simtopk_combined_fast's, in its order and wording; the offsets are required and checked as mmf_simtopk_combined checks them.
+int mmf_simtopk_combined_fast_segmented(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h, float lambda_g,
+                                        int k, int exclude_self, const int64_t* ptr_host, int64_t n_segments, int64_t* out_idx,
+                                        float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id,
+                                        void* hip_stream) {
+  const char* who = "simtopk_combined_fast_segmented";
+  MMF_TRY(Call(who, device_id, hip_stream).on_device());
+  if (n < 0) { set_error("%s: n must be >= 0 (got %lld)", who, (long long)n); return MMF_E_INVALID; }
+  if (d < 1) { set_error("%s: d must be at least 1 (got %lld)", who, (long long)d); return MMF_E_INVALID; }
+  if (dp < 1) { set_error("%s: dp must be at least 1 (got %lld)", who, (long long)dp); return MMF_E_INVALID; }
+  if (k < 1) { set_error("%s: k must be at least 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (!(lambda_h >= 0.0f) || !isfinite(lambda_h)) { set_error("%s: lambda_h must be finite and >= 0 (got %g)", who, lambda_h); return MMF_E_INVALID; }
+  if (!(lambda_g >= 0.0f) || !isfinite(lambda_g)) { set_error("%s: lambda_g must be finite and >= 0 (got %g)", who, lambda_g); return MMF_E_INVALID; }
+  if (n > 0 && !F) { set_error("%s: F is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !P) { set_error("%s: P is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !out_idx) { set_error("%s: out_idx is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !out_val) { set_error("%s: out_val is NULL", who); return MMF_E_INVALID; }
+  MMF_TRY(check_offsets(who, "ptr_host", ptr_host, n_segments, 0, 0, n));
+  if (dp > 8) { set_error("%s: dp = %lld > 8 is not supported", who, (long long)dp); return MMF_E_UNSUPPORTED; }
+  const int kk = k + (exclude_self ? 1 : 0);
+  if (kk > 20) { set_error("%s: k + self = %d > 20 is not supported (mmf_simtopk_combined takes up to 44)", who, kk); return MMF_E_UNSUPPORTED; }
+  if (d > 4096) { set_error("%s: d = %lld > 4096 is not supported (mmf_simtopk_combined takes any d)", who, (long long)d); return MMF_E_UNSUPPORTED; }
+  if (n >= (int64_t)1 << 31) { set_error("%s: n must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  const int prec = opts ? opts->precision : MMF_PREC_AUTO;
+  if (prec != MMF_PREC_AUTO && prec != MMF_PREC_EXACT && prec != MMF_PREC_FAST && prec != MMF_PREC_FAST_BF16) {
+    set_error("%s: precision %d: MMF_PREC_AUTO, _EXACT, _FAST (f16 operands) or _FAST_BF16", who, prec);
+    return MMF_E_INVALID;
+  }
+  const int cs = opts ? opts->col_splits : 0;
+  if (cs < 0 || (cs & (cs - 1)) != 0) { set_error("%s: col_splits must be 0 or a power of two (got %d)", who, cs); return MMF_E_INVALID; }
+  if (n == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return MMF_OK; }
+  return run_simtopk_combined_fast_segmented(who, F, P, n, d, dp, lambda_h, lambda_g, k, exclude_self, ptr_host, n_segments, out_idx, out_val,
+                                             opts, stats, device_id, hip_stream);
 }
 
 }  // extern "C"
