@@ -90,6 +90,11 @@ EXPORTS_TOPK16 = ["mmf_simtopk_combined_fast"]
 # pinned by tests/test_simtopk_combined_fast_segmented_cpu.py.
 EXPORTS_TOPK16_SEG = ["mmf_simtopk_combined_fast_segmented"]
 
+# The two-set top-k of the combined similarity (include/ext/mmf_hg_topk_xy.h): an addition to ABI version 3 in a
+# header of its own.  Its synchronisation behaviour is INTEGRATION.md's table "Two-set top-k entries", pinned by
+# tests/test_simtopk_combined_xy_cpu.py.
+EXPORTS_TOPK_XY = ["mmf_simtopk_combined_xy"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -157,8 +162,10 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_segmented_wide.argtypes = list(L.mmf_simtopk_segmented.argtypes)
     L.mmf_simtopk_combined_fast.argtypes = list(L.mmf_simtopk_combined.argtypes)
     L.mmf_simtopk_combined_fast_segmented.argtypes = list(L.mmf_simtopk_combined.argtypes)
+    L.mmf_simtopk_combined_xy.argtypes = [vp, vp, i64, vp, vp, i64, i64, i64, f32, f32, ci, ci, i64, i64, vp, vp,
+                                          ctypes.POINTER(SimtopkOpts), ctypes.POINTER(SimtopkStats), ci, vp]
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
-                 EXPORTS_TOPK16_SEG):
+                 EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)
         if name not in ("mmf_last_error", "mmf_padded_dim", "mmf_super_patch_stats_streamed_bytes"):
             fn.restype = ci

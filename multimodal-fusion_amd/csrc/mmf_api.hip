@@ -405,8 +405,10 @@ struct ExactPass {
   const int32_t* row_ids = nullptr;         // device: the rows of X that gathered groups name
   int64_t n_ids = 0;
   uint32_t* cand_total = nullptr;           // optional: the re-rank counts its candidates here
-  const float *P = nullptr, *pn = nullptr;  // optional (slices of X against itself only): rank by the exponent of K_h * K_g — positions
-  int dp = 0; float lambda_g = 0.0f;        //   [n][dp] and their chains; r.metric MMF_RBF, r.lambda = lambda_h (mmf_simtopk_combined)
+  const float *P = nullptr, *pn = nullptr;  // optional (slices only): rank by the exponent of K_h * K_g — positions [n][dp] of the rows of
+  int dp = 0; float lambda_g = 0.0f;        //   X and their chains; r.metric MMF_RBF, r.lambda = lambda_h (mmf_simtopk_combined)
+  const float *Pc = nullptr, *pnc = nullptr;   // ... and of the rows of Y (mmf_simtopk_combined_xy); null: P / pn, X against itself
+  int64_t out_row0 = 0;                     // the outputs' first row is row out_row0 of X (the caller holds a row slice of X's rows)
   std::vector<ExactGroup> pieces;           // the groups, gathered ones in pieces of at most kBatch rows
   int64_t rows_total = 0; size_t list_words = 0; bool slices = false;
   int grid = 0;                             // out: scan workgroups (of each piece's last pass)
@@ -476,10 +478,11 @@ struct ExactPass {
       SelectProblem q = r.select();   // this piece of it (exact lists have no overflow lists: nothing for a second select launch)
       q.X = sp.X; q.n = sp.n; q.Y = sp.Y; q.m = sp.m; q.row_offset += r0; q.col_offset += G.col0;
       q.rx = sp.rx; q.cy = sp.cy; q.row_ids = sp.row_ids; q.n_rows = G.rows;
-      q.out_idx += r0 * r.k; q.out_val += r0 * r.k; q.out_stride = r.k;
+      q.out_idx += (r0 - out_row0) * r.k; q.out_val += (r0 - out_row0) * r.k; q.out_stride = r.k;
       q.fail_rows = B.fail_rows; q.fail_count = B.fail_count; q.cand_total = cand_total;
       if (P) {
-        sp.Pq = q.Pq = P + r0 * dp; sp.Pc = q.Pc = P + G.col0 * dp; sp.pnq = q.pnq = pn + r0; sp.pnc = q.pnc = pn + G.col0;
+        sp.Pq = q.Pq = P + r0 * dp; sp.Pc = q.Pc = (Pc ? Pc : P) + G.col0 * dp;
+        sp.pnq = q.pnq = pn + r0; sp.pnc = q.pnc = (pnc ? pnc : pn) + G.col0;
         sp.dp = q.dp = dp; sp.lambda_g = q.lambda_g = lambda_g;
       }
       // k + self beyond 44: several passes, each offering only what ranks after the previous pass's last entry
@@ -1199,6 +1202,275 @@ int run_simtopk_combined_fast_segmented(const char* who, const float* F, const f
   const int64_t overflow_rows = std::min<int64_t>(flags.h_fail4[1], fallback_rows);
   fill_stats(stats, prec, max_splits, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback_rows, overflow_rows,
              fallback_rows - overflow_rows, flags.h_tot);
+  return MMF_OK;
+}
+
+// ---- mmf_simtopk_combined_xy (include/ext/mmf_hg_topk_xy.h; entry and host checks in mmf_scan_b16c.hip) --------
+
+// What MMF_PREC_AUTO does in mmf_simtopk_combined_xy: the 16-bit scan only for the (d, k) range where the whole call beat this
+// entry's own exact arm by more than three times that arm's spread at every measured shape (the rule of DESIGN.md §4.17; §4.19,
+// profiles/simtopk_combined_xy_timing.txt): k = 5 (16-entry lists) at d = 512 and d = 1536, for a row panel of one eighth of
+// N = 65536 and, at d = 512, of N = 262144, and for 16384 queries against 65536 distinct candidates — 3.05x / 3.83x / 3.22x at
+// d = 512 and 3.48x / 3.41x at d = 1536, the difference 79 / 312 / 39 and 44 / 121 times that spread.  Outside
+// 512 <= d <= 1536, or with the 32-entry lists of k + self > 11, nothing is measured and AUTO stays exact, as in the self
+// entries (precision = MMF_PREC_FAST is served wherever the scan applies).
+static bool combined_xy_auto(int64_t d, int kk) { return d >= 512 && d <= 1536 && kk <= 11; }
+
+// Queries [a, b) and the entries each of them can have: all nc candidates, minus one where self is excluded and the query's own
+// id lies among the candidates' ids.  Adjacent ranges with the same count are one.
+struct XYRange { int64_t a, b; int ks; };
+static std::vector<XYRange> xy_ranges(int64_t nq, int64_t nc, int k, int exclude_self, int64_t row_offset, int64_t col_offset) {
+  int64_t o0 = 0, o1 = 0;   // the queries whose id is a candidate's
+  if (exclude_self) {
+    o0 = std::min(std::max<int64_t>(col_offset - row_offset, 0), nq);
+    o1 = std::min(std::max<int64_t>(col_offset + nc - row_offset, o0), nq);
+  }
+  const XYRange three[3] = {{0, o0, (int)std::min<int64_t>(k, nc)}, {o0, o1, (int)std::min<int64_t>(k, nc - 1)}, {o1, nq, (int)std::min<int64_t>(k, nc)}};
+  std::vector<XYRange> out;
+  for (const XYRange& g : three) {
+    if (g.a >= g.b) continue;
+    if (!out.empty() && out.back().ks == g.ks) out.back().b = g.b;
+    else out.push_back(g);
+  }
+  return out;
+}
+
+// rows without an admissible candidate: -1 / -inf
+static int xy_fill_none(int64_t* out_idx, float* out_val, int64_t row0, int64_t rows, int k, hipStream_t s) {
+  MMF_HIP(hipMemsetAsync(out_idx + row0 * k, 0xff, (size_t)rows * k * 8, s));
+  MMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out_val + row0 * k), (int)0xff800000u, (size_t)rows * k, s));
+  return MMF_OK;
+}
+
+// The 16-bit path of run_simtopk_combined_xy, behind r.call.begin(): nc >= k + self candidates, so every query has k entries.
+// r is the call as the exact pass wants it (X = the candidates for a slice, whose row slice0 is query 0; else the queries).
+// One image (candidates, then — unless the queries are rows of them — the queries), chains and positions in the joint numbering
+// of mmf_scan_b16c.hip's "Two-set form", a work table of one entry per query block and column range, launch_scan_b16c_xy, audit,
+// the two-sided re-rank, one readback; flagged rows as in run_simtopk_combined_fast.
+static int xy_fast(Request& r, const float* Fq, const float* Pq, int64_t nq, const float* Fc, const float* Pc, int64_t nc, int64_t slice0,
+                   int64_t dp, float lambda_g, int64_t row_offset, const mmf_simtopk_opts* opts) {
+  const char* who = r.call.who;
+  const hipStream_t s = r.call.s;
+  const bool slice = slice0 >= 0, f16 = r.precision == MMF_PREC_FAST;
+  const int64_t d = r.d, x0 = slice ? slice0 : 0;
+  const int k = r.k;
+  const float lambda_h = r.lambda;
+  const int dpf = scan_b16c_dp(d), bcap = scan_b16c_cap(r.kk);
+  const int64_t ncp = (nc + 127) / 128 * 128, tiles = ncp / 128, row_blocks = (nq + 127) / 128;
+  const int64_t J = slice ? nc : nc + nq;           // rows of the joint numbering: candidates, then the queries unless they are among them
+  const int64_t q_row0 = slice ? slice0 : nc;       // the first query's row in it
+  const int64_t q_pos0 = slice ? slice0 : ncp;      // ... and its image position
+  // a slice's last query block reads up to 127 rows behind its last query: one spare block of padding keeps them inside the image
+  const int64_t n_img = ncp + (slice ? 128 : row_blocks * 128);
+  if (n_img >= (int64_t(1) << 31) || J >= (int64_t(1) << 31)) { set_error("%s: the padded image of %lld positions is too large", who, (long long)n_img); return MMF_E_UNSUPPORTED; }
+  // column splits: run_simtopk_combined_fast's rule, bounded by the candidate tiles
+  int splits = 1;
+  const int forced = opts ? opts->col_splits : 0;
+  if (forced > 0) { while (splits < forced && splits < 32) splits <<= 1; }
+  else { while (row_blocks * splits < 256 && splits < 32) splits <<= 1; }
+  while (splits > 1 && (splits > tiles || 2 * splits * bcap > 1024)) splits >>= 1;
+  const int lists = 2 * splits;
+  const int64_t tps = (tiles + splits - 1) / splits;
+  std::vector<int32_t> sched;
+  sched.reserve((size_t)row_blocks * splits * 8);
+  for (int64_t b = 0; b < nq; b += 128) {
+    for (int c = 0; c < splits; ++c) {
+      const int64_t tb = std::min(c * tps, tiles), te = std::min(tb + tps, tiles);
+      const int32_t e[8] = {(int32_t)(q_pos0 + b), (int32_t)(q_row0 + b), (int32_t)std::min<int64_t>(nq - b, 128), (int32_t)tb, (int32_t)te, 0,
+                            2 * c, (int32_t)(nc - 1)};
+      sched.insert(sched.end(), e, e + 8);
+    }
+  }
+  const int64_t grid = row_blocks * splits;
+  constexpr int64_t kFailPeek = 1024;   // flagged row ids that come back with the fail count
+  const int64_t peek = std::min(nq, kFailPeek);
+
+  const size_t need = 2 * ws_bytes(J, 4) + ws_bytes(8, 4) + (slice ? 0 : ws_bytes((size_t)J * dp, 4)) + HalfImage::bytes(n_img, dpf) +
+                      ws_bytes(sched.size(), 4) + b16_lists_bytes(nq, lists, bcap) + FlagBlock::bytes(nq) + ws_bytes(2 * (size_t)nq, 4);
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* nf = ws.take<float>(J);
+  float* pn = ws.take<float>(J);
+  uint32_t* maxw = ws.take<uint32_t>(8);   // word 0: largest chain(f, f) of both sides, word 4: largest chain(p, p)
+  float* Pj = slice ? nullptr : ws.take<float>((size_t)J * dp);   // both sides' positions in the joint numbering
+  HalfImage C;
+  C.carve(ws, n_img, dpf);
+  int32_t* d_sched = ws.take<int32_t>(sched.size());
+  const CandLists L = carve_b16_lists(ws, nq, lists, bcap);
+  FlagBlock flags;
+  flags.carve(ws, nq);
+  int32_t* seed = ws.take<int32_t>(2 * (size_t)nq);
+  MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
+  MMF_HIP(hipMemsetAsync(maxw, 0, 32, s));
+  MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)nq * 4, s));
+  MMF_TRY(flags.zero(s));
+  MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)nq * 8, s));   // kSeedNone, thresholds and dropped keys
+
+  EventTimer t_prep, t_scan, t_sel, t_fb;
+  MMF_TRY(t_prep.start(r.profile, s));
+  MMF_TRY(launch_row_scalars(Fc, nc, d, MMF_F32, MMF_RBF, nf, maxw, s));
+  MMF_TRY(launch_row_scalars(Pc, nc, dp, MMF_F32, MMF_RBF, pn, maxw + 4, s));
+  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
+  if (slice) {
+    MMF_TRY(launch_prep_half({Fc, nc, d, MMF_F32, MMF_RBF, nf, maxw}, C, dpf, f16, s));
+  } else {
+    // scale and maxima over both sides: the queries' scalars join the same words before either image is written
+    MMF_TRY(launch_row_scalars(Fq, nq, d, MMF_F32, MMF_RBF, nf + nc, maxw, s));
+    MMF_TRY(launch_row_scalars(Pq, nq, dp, MMF_F32, MMF_RBF, pn + nc, maxw + 4, s));
+    MMF_HIP(hipMemcpyAsync(Pj, Pc, (size_t)nc * dp * 4, hipMemcpyDeviceToDevice, s));
+    MMF_HIP(hipMemcpyAsync(Pj + nc * dp, Pq, (size_t)nq * dp * 4, hipMemcpyDeviceToDevice, s));
+    HalfImage Cc = C;
+    Cc.n_pad = ncp;
+    MMF_TRY(launch_prep_half({Fc, nc, d, MMF_F32, MMF_RBF, nf, maxw}, Cc, dpf, f16, s));
+    MMF_TRY(launch_prep_half({Fq, nq, d, MMF_F32, MMF_RBF, nf + nc, maxw}, C.from_row(ncp, dpf), dpf, f16, s));
+  }
+  MMF_TRY(t_prep.stop(s));
+
+  MMF_TRY(t_scan.start(r.profile, s));
+  ScanB16Panel pnl;
+  pnl.seed = seed; pnl.seed_stride = nq;
+  const ScanB16Problem sp(C, C, nq, nc, n_img, dpf, d, f16, MMF_RBF, r.kk);
+  const ScanB16Comb sc{slice ? Pc : Pj, pn, nf, maxw, maxw + 4, (int)dp, lambda_h, lambda_g};
+  MMF_TRY(launch_scan_b16c_xy(sp, sc, d_sched, grid, lists, q_row0, L, pnl, s));
+  MMF_TRY(launch_scan_b16_audit(pnl, L.overflow, nq, s));
+  if (const char* e = getenv("MMF_DEBUG_FLAG_ROWS")) {   // test hook: send the first queries down the exact pass (FastTail::run's)
+    const int64_t f = atoll(e);
+    if (f > 0) MMF_HIP(hipMemsetAsync(L.overflow, 1, (size_t)(f < nq ? f : nq) * 4, s));
+  }
+  MMF_TRY(t_scan.stop(s));
+
+  SelectProblem q = r.select();
+  q.X = Fq; q.n = nq; q.n_rows = nq; q.row_offset = row_offset; q.out_stride = k;
+  q.rx = nf + q_row0; q.cy = nf; q.Pq = Pq; q.Pc = Pc; q.pnq = pn + q_row0; q.pnc = pn; q.dp = (int)dp; q.lambda_g = lambda_g;
+  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = r.stats ? flags.cand_total : nullptr;
+  MMF_TRY(t_sel.start(r.profile, s));
+  MMF_TRY(launch_rerank_combined(q, L, s));
+  MMF_TRY(t_sel.stop(s));
+
+  std::vector<int32_t> h_rows((size_t)peek);
+  MMF_HIP(hipMemcpyAsync(h_rows.data(), flags.fail_rows, (size_t)peek * 4, hipMemcpyDeviceToHost, s));
+  MMF_TRY(flags.read(r.stats != nullptr, s));   // the call's synchronisation
+  const int64_t h_fail = flags.h_fail4[0];
+  MMF_TRY(t_fb.start(r.profile && h_fail > 0, s));
+  if (h_fail > 0) {
+    h_rows.resize((size_t)h_fail);
+    if (h_fail > peek) {
+      MMF_HIP(hipMemcpyAsync(h_rows.data(), flags.fail_rows, (size_t)h_fail * 4, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipStreamSynchronize(s));
+    }
+    std::vector<char> hit((size_t)row_blocks, 0);
+    int64_t n_hit = 0;
+    for (int32_t row : h_rows) {
+      if (row < 0 || row >= nq) { set_error("%s: flagged row %d outside the %lld queries (internal invariant)", who, row, (long long)nq); return MMF_E_INTERNAL; }
+      if (!hit[(size_t)(row / 128)]) { hit[(size_t)(row / 128)] = 1; ++n_hit; }
+    }
+    // the exact pass over the flagged queries' 128-row blocks against all candidates: rows x0 + ... of r.X
+    ExactPass ex(r, nf + (slice ? 0 : nc), nf);
+    ex.same = slice;
+    ex.P = slice ? Pc : Pq; ex.pn = pn + (slice ? 0 : nc); ex.dp = (int)dp; ex.lambda_g = lambda_g; ex.out_row0 = x0;
+    if (!slice) { ex.Pc = Pc; ex.pnc = pn; }
+    if (4 * n_hit > row_blocks) {
+      ex.add(ExactGroup{x0, nq, false, 0, nc, k});
+    } else {
+      for (int64_t b = 0; b < row_blocks; ++b) {
+        if (!hit[(size_t)b]) continue;
+        int64_t e = b;
+        while (e + 1 < row_blocks && hit[(size_t)(e + 1)]) ++e;
+        const int64_t row0 = b * 128, end = std::min(nq, (e + 1) * 128);
+        ex.add(ExactGroup{x0 + row0, end - row0, false, 0, nc, k});
+        b = e;
+      }
+    }
+    Workspace aux;   // the f32 images and the exact lists, in the second workspace slot
+    MMF_TRY(r.call.workspace(ex.image_bytes() + ex.list_bytes(), &aux, 1));
+    ExactLists B;
+    B.carve(aux, ex.rows_total, ex.list_words, ex.cap(), false);
+    MMF_TRY(B.zero(s));
+    MMF_TRY(ex.run(aux, B));
+  }
+  MMF_TRY(t_fb.stop(s));
+  fill_stats(r.stats, r.precision, splits, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), h_fail, flags.h_fail4[1], flags.h_fail4[2],
+             flags.h_tot);
+  return MMF_OK;
+}
+
+// Queries against candidates.  A row slice (Fq / Pq point at the same row of Fc / Pc, nq rows inside nc) is a slice of the
+// candidates against themselves: one image, one set of chains, and the groups the self entries run for those rows — so their bits.
+// Exact: one ExactGroup of all queries against all candidates (up to three when self is excluded, some queries' ids lie among the
+// candidates' and there are fewer than k + 1 candidates: the queries then differ in how many entries they can have).
+int run_simtopk_combined_xy(const char* who, const float* Fq, const float* Pq, int64_t nq, const float* Fc, const float* Pc, int64_t nc,
+                            int64_t d, int64_t dp, float lambda_h, float lambda_g, int k, int exclude_self, int64_t row_offset,
+                            int64_t col_offset, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats,
+                            int device_id, void* hip_stream) {
+  const int self1 = exclude_self ? 1 : 0, kk = k + self1;
+  int prec = opts ? opts->precision : MMF_PREC_AUTO;
+  if (prec == MMF_PREC_AUTO) prec = (scan_b16c_supported(d, kk) && combined_xy_auto(d, kk)) ? MMF_PREC_FAST : MMF_PREC_EXACT;
+  if (nc < kk) prec = MMF_PREC_EXACT;   // fewer candidates than a row's lists keep: nothing for a candidate scan to narrow down
+  int64_t slice0 = -1;
+  if (nc > 0) {
+    const uintptr_t fq = reinterpret_cast<uintptr_t>(Fq), fc = reinterpret_cast<uintptr_t>(Fc);
+    const size_t row_bytes = (size_t)d * 4;
+    if (fq >= fc && (fq - fc) % row_bytes == 0) {
+      const int64_t r0 = (int64_t)((fq - fc) / row_bytes);
+      if (r0 <= nc - nq && Pq == Pc + r0 * dp) slice0 = r0;
+    }
+  }
+  const bool slice = slice0 >= 0;
+  const int64_t x0 = slice ? slice0 : 0;   // query 0 is row x0 of r.X
+  Request r{Call(who, device_id, hip_stream), slice ? Fc : Fq, slice ? nc : nq, Fc, nc, d, MMF_F32, MMF_RBF, lambda_h, k, exclude_self,
+            row_offset - x0, col_offset, out_idx, out_val, stats, opts && opts->profile};
+  r.kk = kk;
+  r.precision = prec;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  MMF_TRY(r.call.begin());
+  const hipStream_t s = r.call.s;
+  if (stats) stats->precision_used = prec;
+  if (nc == 0) return xy_fill_none(out_idx, out_val, 0, nq, k, s);
+  if (prec != MMF_PREC_EXACT) return xy_fast(r, Fq, Pq, nq, Fc, Pc, nc, slice0, dp, lambda_g, row_offset, opts);
+
+  ExactPass ex(r, nullptr, nullptr);
+  ex.same = slice;
+  ex.forced_splits = opts ? opts->col_splits : 0;
+  ex.dp = (int)dp; ex.lambda_g = lambda_g; ex.out_row0 = x0;
+  std::vector<XYRange> bare;   // queries without an admissible candidate (one candidate, and it is the query itself)
+  for (const XYRange& g : xy_ranges(nq, nc, k, exclude_self, row_offset, col_offset)) {
+    if (g.ks > 0) ex.add(ExactGroup{x0 + g.a, g.b - g.a, false, 0, nc, g.ks});
+    else bare.push_back(g);
+  }
+  const size_t need = 2 * ws_bytes(nc, 4) + (slice ? 0 : 2 * ws_bytes(nq, 4)) + ws_bytes(256, 4) +
+                      (ex.pieces.empty() ? 0 : ex.image_bytes() + ex.list_bytes());
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* nfc = ws.take<float>(nc);
+  float* pnc = ws.take<float>(nc);
+  float* nfq = slice ? nfc : ws.take<float>(nq);
+  float* pnq = slice ? pnc : ws.take<float>(nq);
+  uint32_t* cand_total = ws.take<uint32_t>(256);
+  ex.rx = nfq; ex.cy = nfc; ex.P = slice ? Pc : Pq; ex.pn = pnq;
+  if (!slice) { ex.Pc = Pc; ex.pnc = pnc; }
+  ex.cand_total = stats ? cand_total : nullptr;
+  for (const XYRange& g : bare) MMF_TRY(xy_fill_none(out_idx, out_val, g.a, g.b - g.a, k, s));
+  if (ex.pieces.empty()) return MMF_OK;
+  ExactLists B;
+  B.carve(ws, ex.rows_total, ex.list_words, ex.cap(), false);
+  MMF_TRY(B.zero(s));
+  MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
+
+  // timers as run_simtopk_combined: prep (row scalars, f32 images), scan, re-rank for one group; with several, "scan" is all of it
+  const bool one = ex.pieces.size() == 1;
+  EventTimer t[3];
+  MMF_TRY(t[0].start(r.profile, s));
+  MMF_TRY(launch_row_scalars(Fc, nc, d, MMF_F32, MMF_RBF, nfc, nullptr, s));
+  MMF_TRY(launch_row_scalars(Pc, nc, dp, MMF_F32, MMF_RBF, pnc, nullptr, s));
+  if (!slice) {
+    MMF_TRY(launch_row_scalars(Fq, nq, d, MMF_F32, MMF_RBF, nfq, nullptr, s));
+    MMF_TRY(launch_row_scalars(Pq, nq, dp, MMF_F32, MMF_RBF, pnq, nullptr, s));
+  }
+  if (!one) { MMF_TRY(t[0].stop(s)); MMF_TRY(t[1].start(r.profile, s)); }
+  std::vector<uint32_t> h_tot(stats ? 256 : 0);
+  MMF_TRY(ex.run(ws, B, one ? t : nullptr, stats ? &h_tot : nullptr));
+  if (!one) MMF_TRY(t[1].stop(s));
+  fill_stats(stats, MMF_PREC_EXACT, ex.splits(ex.pieces[0]), ex.grid, t[0].ms(), t[1].ms(), t[2].ms(), 0.f, 0, 0, 0, h_tot);
   return MMF_OK;
 }
 

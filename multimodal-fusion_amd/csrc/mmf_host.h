@@ -14,6 +14,7 @@
 #include "../../include/mmf_hg_topk.h"
 #include "../../include/mmf_hg_topk16.h"
 #include "../../include/ext/mmf_hg_topk16_seg.h"
+#include "../../include/ext/mmf_hg_topk_xy.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -391,6 +392,18 @@ int launch_scan_b16c(const ScanB16Problem& p, const ScanB16Comb& c, int col_spli
 // p.m_pad: positions of the one image, every segment padded to whole tiles of 128; `lists` = 2 x the largest range count
 int launch_scan_b16c_seg(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, const CandLists& L,
                          const ScanB16Panel& pn, hipStream_t s);
+// the same scan for queries that are not the candidates, or only some of them (mmf_simtopk_combined_xy): the table
+// names, per workgroup, a block of 128 queries anywhere in the one image and a range of CANDIDATE tiles.  c.P / c.pn / c.nf are in
+// the joint numbering of the table (candidates first); the lists, threshold buffers and margins hold only the p.n_rows queries,
+// whose first one is row `list_row0` of that numbering; p.m: candidate rows, p.m_pad: positions of the image
+int launch_scan_b16c_xy(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, int64_t list_row0,
+                        const CandLists& L, const ScanB16Panel& pn, hipStream_t s);
+// mmf_api.hip: mmf_simtopk_combined_xy behind its host checks — the exact pass over the queries against the candidates, or the
+// table-driven 16-bit scan, audit, re-rank and the exact pass over the row blocks of flagged rows
+int run_simtopk_combined_xy(const char* who, const float* Fq, const float* Pq, int64_t nq, const float* Fc, const float* Pc, int64_t nc,
+                            int64_t d, int64_t dp, float lambda_h, float lambda_g, int k, int exclude_self, int64_t row_offset,
+                            int64_t col_offset, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats,
+                            int device_id, void* hip_stream);
 // mmf_api.hip: mmf_simtopk_combined_fast behind its host checks (one graph) — 16-bit scan, audit, re-rank of the combined key,
 // exact pass over the row blocks of flagged rows; MMF_PREC_EXACT (and AUTO where the fast path does not pay): run_simtopk_combined
 int run_simtopk_combined_fast(const char* who, const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,

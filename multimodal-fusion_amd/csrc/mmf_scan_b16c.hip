@@ -51,6 +51,23 @@
 // SEG = true takes its row block, column range, id offset, list slot and clamp rows from a host-built work table, one entry per
 // workgroup, over ONE image in which every segment is padded to whole tiles of 128.  Scale and maxima are the batch's — a superset
 // of any one segment's rows, so m0_i is at least a per-segment call's — and a row's band is taken inside its own segment.
+//
+// Two-set form (mmf_simtopk_combined_xy, include/ext/mmf_hg_topk_xy.h): the SEG = true kernel again, unchanged,
+// for queries that are not the candidates (or only rows r0 .. of them).  ONE image: the candidates from position 0, padded to
+// whole tiles of 128; queries that are no slice of the candidates appended from the next multiple of 128.  nf / P / pn are in the
+// joint numbering candidates-then-queries (for a slice: the candidates' own), so CSEG_ROW0 is a query block's row in it,
+// CSEG_QPOS its image position (for a slice r0 + 128 b: any position — the query DMA and zn / rn / un only need 128 mapped rows
+// behind it, which one spare block of padding behind the image gives), the tile range covers candidate tiles only, CSEG_IDOFF = 0
+// and CSEG_LAST = nc - 1: the lists hold candidate rows and the candidate-side reads stay on the candidates.  Lists, threshold
+// buffers and margins exist for the queries alone: the launcher hands the kernel their bases moved back by the first query's
+// joint row (launch_scan_b16c_xy).
+// Why the margin proof carries over.  The proof above uses, for a pair (i, j): one scale s for z_i and z_j; E1_i / E2_i, which
+// bound the rounding of row i against ANY row whose zn / rn / un / |cb| lie below the four maxima; egb_i, which needs max pn over
+// every row j that i meets; and nothing else that ties i to the set j comes from.  Scale, maxima and the largest pn are taken
+// over the UNION of both sides here (both prep launches and both row-scalar launches write the same words), a superset of the
+// candidates — all a query's bound needs — so every inequality holds pair by pair with m0_i at least the value a self call over
+// the union would use, and a query's band is taken among the candidate columns only.  For a slice the union is the candidates,
+// so m0_i, the approximate keys and therefore the flagged rows are those of the self call on the candidates.
 #include <math.h>
 #include <string.h>
 
@@ -701,6 +718,55 @@ int launch_scan_b16c_seg(const ScanB16Problem& p, const ScanB16Comb& c, const in
   return MMF_OK;
 }
 
+// Two-set scan (mmf_simtopk_combined_xy; the header's "Two-set form"): launch_scan_b16c_seg's launch with the
+// queries' buffers apart.  The kernel indexes lists, threshold buffers and margins by a query's row in the table's joint
+// numbering, CSEG_ROW0 + its place in the block; the p.n_rows queries are rows list_row0 .. of that numbering, so the kernel gets
+// the bases moved back by list_row0 rows and only ever forms addresses inside the buffers (it writes for real queries only).  The
+// seed union and the caller's audit and re-rank see the buffers as they are: row 0 = the first query.
+int launch_scan_b16c_xy(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, int64_t list_row0,
+                        const CandLists& L, const ScanB16Panel& pn, hipStream_t s) {
+  if (grid <= 0 || p.n_rows <= 0) return MMF_OK;
+  if (!scan_b16c_supported(p.d, p.kk) || p.dp != scan_b16c_dp(p.d) || p.metric != MMF_RBF) {
+    set_error("scan_b16c_xy: d = %lld (padded %d), k + self = %d, metric %d outside 1 <= d <= 4096, k + self <= 20, MMF_RBF", (long long)p.d,
+              p.dp, p.kk, p.metric);
+    return MMF_E_INTERNAL;
+  }
+  if (p.ZQ != p.ZC || p.m < 1 || list_row0 < 0) { set_error("scan_b16c_xy: one image holding both sides, candidates first"); return MMF_E_INTERNAL; }
+  if (!c.P || !c.pn || !c.nf || !c.max_nf || !c.max_pn || c.dp < 1 || c.dp > 8) { set_error("scan_b16c_xy: positions, chains and maxima (1 <= dp <= 8) missing"); return MMF_E_INTERNAL; }
+  const int col_splits = lists / 2;
+  if (lists < 2 || lists != 2 * col_splits || (col_splits & (col_splits - 1)) != 0) {
+    set_error("scan_b16c_xy: %d lists per row are no power-of-two number of pairs", lists);
+    return MMF_E_INTERNAL;
+  }
+  if (!sched) { set_error("scan_b16c_xy: work table missing"); return MMF_E_INTERNAL; }
+  if (!pn.seed || pn.seed_stride < p.n_rows) { set_error("scan_b16c_xy: threshold buffers missing"); return MMF_E_INTERNAL; }
+  if (lists != L.lists) { set_error("scan_b16c_xy: %d lists per row for %d column splits", L.lists, col_splits); return MMF_E_INTERNAL; }
+  if (L.cap != scan_b16c_cap(p.kk)) { set_error("scan_b16c_xy: list capacity %d, expected %d", L.cap, scan_b16c_cap(p.kk)); return MMF_E_INTERNAL; }
+  if (col_splits > 1 && (!L.keys || !L.margin)) { set_error("scan_b16c_xy: column splits need the lists' keys and margins"); return MMF_E_INTERNAL; }
+  if (p.m_pad % C_CT != 0 || (p.m + C_CT - 1) / C_CT * C_CT > p.m_pad) {
+    set_error("scan_b16c_xy: image of %lld positions for %lld candidates", (long long)p.m_pad, (long long)p.m);
+    return MMF_E_INTERNAL;
+  }
+  ScanB16CArgs a{};
+  a.Z = p.ZC; a.cb = p.cb; a.q_zn = p.q_zn; a.q_rn = p.q_rn; a.q_un = p.q_un; a.maxima = p.maxima;
+  a.nf = c.nf; a.P = c.P; a.pn = c.pn; a.max_nf = c.max_nf; a.max_pn = c.max_pn; a.lambda_h = c.lambda_h; a.lambda_g = c.lambda_g; a.dpp = c.dp;
+  a.n_rows = p.n_rows; a.kk = p.kk; a.d = (int)p.d; a.dp = p.dp;
+  a.tiles_total = p.m_pad / C_CT; a.tiles_per_split = a.tiles_total; a.col_splits = 1;   // unused: the table carries the ranges
+  a.lists_total = L.lists;
+  const int64_t lw = list_row0 * L.lists;   // list words ahead of the first query's
+  a.seed = pn.seed - list_row0; a.lost = pn.seed + pn.seed_stride - list_row0;
+  a.cand_cnt = L.cnt - lw; a.cand_ids = L.ids - lw * L.cap;
+  a.cand_keys = L.keys ? L.keys - lw * L.cap : nullptr; a.margin_out = L.margin ? L.margin - list_row0 : nullptr;
+  a.sched = sched;
+  MMF_TRY(L.cap == C_CAP_SMALL ? (launch_b16c_t<C_CAP_SMALL, true>(a, p.f16, grid, s)) : (launch_b16c_t<C_CAP_BIG, true>(a, p.f16, grid, s)));
+  if (col_splits > 1) {
+    hipLaunchKernelGGL(comb_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
+                       p.kk, pn.seed, p.n_rows);
+    MMF_LAUNCH_CHECK();
+  }
+  return MMF_OK;
+}
+
 }  // namespace mmf
 
 using namespace mmf;
@@ -776,6 +842,49 @@ int mmf_simtopk_combined_fast_segmented(const float* F, const float* P, int64_t 
   if (n == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return MMF_OK; }
   return run_simtopk_combined_fast_segmented(who, F, P, n, d, dp, lambda_h, lambda_g, k, exclude_self, ptr_host, n_segments, out_idx, out_val,
                                              opts, stats, device_id, hip_stream);
+}
+
+// include/ext/mmf_hg_topk_xy.h, DESIGN.md §4.19: queries against candidates.  The checks are the siblings', in their order and
+// wording, with two sides and the id offsets of mmf_simtopk.
+int mmf_simtopk_combined_xy(const float* Fq, const float* Pq, int64_t nq, const float* Fc, const float* Pc, int64_t nc, int64_t d, int64_t dp,
+                            float lambda_h, float lambda_g, int k, int exclude_self, int64_t row_offset, int64_t col_offset,
+                            int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id,
+                            void* hip_stream) {
+  const char* who = "simtopk_combined_xy";
+  MMF_TRY(Call(who, device_id, hip_stream).on_device());
+  if (nq < 0) { set_error("%s: nq must be >= 0 (got %lld)", who, (long long)nq); return MMF_E_INVALID; }
+  if (nc < 0) { set_error("%s: nc must be >= 0 (got %lld)", who, (long long)nc); return MMF_E_INVALID; }
+  if (d < 1) { set_error("%s: d must be at least 1 (got %lld)", who, (long long)d); return MMF_E_INVALID; }
+  if (dp < 1) { set_error("%s: dp must be at least 1 (got %lld)", who, (long long)dp); return MMF_E_INVALID; }
+  if (k < 1) { set_error("%s: k must be at least 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (row_offset < 0) { set_error("%s: row_offset must be >= 0 (got %lld)", who, (long long)row_offset); return MMF_E_INVALID; }
+  if (col_offset < 0) { set_error("%s: col_offset must be >= 0 (got %lld)", who, (long long)col_offset); return MMF_E_INVALID; }
+  if (!(lambda_h >= 0.0f) || !isfinite(lambda_h)) { set_error("%s: lambda_h must be finite and >= 0 (got %g)", who, lambda_h); return MMF_E_INVALID; }
+  if (!(lambda_g >= 0.0f) || !isfinite(lambda_g)) { set_error("%s: lambda_g must be finite and >= 0 (got %g)", who, lambda_g); return MMF_E_INVALID; }
+  if (nq > 0 && !Fq) { set_error("%s: Fq is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && !Pq) { set_error("%s: Pq is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && nc > 0 && !Fc) { set_error("%s: Fc is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && nc > 0 && !Pc) { set_error("%s: Pc is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && !out_idx) { set_error("%s: out_idx is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && !out_val) { set_error("%s: out_val is NULL", who); return MMF_E_INVALID; }
+  const int prec = opts ? opts->precision : MMF_PREC_AUTO;
+  if (prec != MMF_PREC_AUTO && prec != MMF_PREC_EXACT && prec != MMF_PREC_FAST && prec != MMF_PREC_FAST_BF16) {
+    set_error("%s: precision %d: MMF_PREC_AUTO, _EXACT, _FAST (f16 operands) or _FAST_BF16", who, prec);
+    return MMF_E_INVALID;
+  }
+  if (opts && opts->col_splits < 0) { set_error("%s: col_splits must be >= 0 (got %d)", who, opts->col_splits); return MMF_E_INVALID; }
+  if (dp > 8) { set_error("%s: dp = %lld > 8 is not supported", who, (long long)dp); return MMF_E_UNSUPPORTED; }
+  const int kk = k + (exclude_self ? 1 : 0);
+  if (kk > 44) { set_error("%s: k + self = %d > 44 is not supported (the multi-pass floors are a follow-up)", who, kk); return MMF_E_UNSUPPORTED; }
+  if (prec == MMF_PREC_FAST || prec == MMF_PREC_FAST_BF16) {
+    if (kk > 20) { set_error("%s: k + self = %d > 20 is not supported (MMF_PREC_EXACT takes up to 44)", who, kk); return MMF_E_UNSUPPORTED; }
+    if (d > 4096) { set_error("%s: d = %lld > 4096 is not supported (MMF_PREC_EXACT takes any d)", who, (long long)d); return MMF_E_UNSUPPORTED; }
+  }
+  if (nq >= ((int64_t)1 << 31) - row_offset) { set_error("%s: row_offset + nq must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  if (nc >= ((int64_t)1 << 31) - col_offset) { set_error("%s: col_offset + nc must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  if (nq == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return MMF_OK; }
+  return run_simtopk_combined_xy(who, Fq, Pq, nq, Fc, Pc, nc, d, dp, lambda_h, lambda_g, k, exclude_self, row_offset, col_offset, out_idx,
+                                 out_val, opts, stats, device_id, hip_stream);
 }
 
 }  // extern "C"

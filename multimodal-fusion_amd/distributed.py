@@ -319,3 +319,46 @@ def sharded_simtopk(x_local: torch.Tensor, n_total: int, *, metric="cosine", lam
             stats["driver"] = "simple"
         return idx, val, stats
     return idx, val
+
+
+def sharded_simtopk_combined(f_local: torch.Tensor, p_local: torch.Tensor, n_total: int, *, lambda_h: float = 1.0, lambda_g: float = 1.0,
+                             k: int = 5, exclude_self: bool = True, precision: str = "auto", group=None, gather_output: bool = False,
+                             op: Optional[Callable] = None, return_stats: bool = False):
+    """Top-k of the combined similarity K_h * K_g of every local row against ALL n_total rows: the simple
+    driver's shape — one all-gather of the feature shards and one of the position shards, then mmf_simtopk_combined_xy on the
+    view [lo:hi) of the gathered arrays with row_offset = lo, which the library recognises as a row slice (one operand image, the
+    bits of the unsharded call).
+
+    f_local [N_r, D], p_local [N_r, dp]: this rank's rows shard_bounds(n_total, world, rank).  Returns (idx int64 [N_r, k] GLOBAL
+    row ids, val f32 [N_r, k][, stats dict]); with gather_output the full [n_total, k] result is replicated on every rank.
+    `op(q_features, q_positions, c_features, c_positions, lambda_h, lambda_g, k, exclude_self=, row_offset=, col_offset=)` lets
+    the CPU tests substitute the oracle for the device op; the default is combined_topk_xy.simtopk_combined_xy."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    lo, hi = shard_bounds(n_total, world, rank)
+    if f_local.shape[0] != hi - lo or p_local.shape[0] != hi - lo:
+        raise ValueError(f"rank {rank}: shards have {f_local.shape[0]} / {p_local.shape[0]} rows, expected {hi - lo}")
+    f_full = all_gather_rows(f_local, n_total, group) if world > 1 else f_local
+    p_full = all_gather_rows(p_local, n_total, group) if world > 1 else p_local
+    kw = dict(exclude_self=exclude_self, row_offset=lo, col_offset=0)
+    stats = None
+    if op is None:
+        from . import combined_topk_xy
+        if not f_full.is_cuda:      # CPU shards: one copy to the device, so that the op still sees views of one array
+            from .build_hypergraph._common import compute_device, to_gpu
+            dev = compute_device(f_full, p_full)
+            f_full, p_full = to_gpu(f_full, dev), to_gpu(p_full, dev)
+        out = combined_topk_xy.simtopk_combined_xy(f_full[lo:hi], p_full[lo:hi], f_full, p_full, lambda_h, lambda_g, k, precision=precision,
+                                                   return_stats=return_stats, profile=return_stats, **kw)
+        idx, val = out[0].to(f_local.device), out[1].to(f_local.device)
+        if return_stats:
+            stats = out[2]
+            stats["driver"] = "simple"
+    else:
+        idx, val = op(f_full[lo:hi], p_full[lo:hi], f_full, p_full, lambda_h, lambda_g, k, **kw)
+    if gather_output and world > 1:
+        idx = all_gather_rows(idx, n_total, group)
+        val = all_gather_rows(val, n_total, group)
+    if return_stats:
+        return idx, val, stats
+    return idx, val
