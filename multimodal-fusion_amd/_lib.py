@@ -95,6 +95,11 @@ EXPORTS_TOPK16_SEG = ["mmf_simtopk_combined_fast_segmented"]
 # tests/test_simtopk_combined_xy_cpu.py.
 EXPORTS_TOPK_XY = ["mmf_simtopk_combined_xy"]
 
+# The segmented exact scan (include/ext/mmf_hg_seg_exact.h): an addition to ABI version 3 in a header of its own.
+# Both entries synchronise once per call (the re-rank's fail counts; once more when a segment is short of k admissible columns);
+# mmf_segmented_exact_table is host-only.  Pinned by tests/test_segmented_exact_cpu.py.
+EXPORTS_SEG_EXACT = ["mmf_simtopk_segmented_exact", "mmf_simtopk_combined_segmented_exact", "mmf_segmented_exact_table"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -164,6 +169,11 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_combined_fast_segmented.argtypes = list(L.mmf_simtopk_combined.argtypes)
     L.mmf_simtopk_combined_xy.argtypes = [vp, vp, i64, vp, vp, i64, i64, i64, f32, f32, ci, ci, i64, i64, vp, vp,
                                           ctypes.POINTER(SimtopkOpts), ctypes.POINTER(SimtopkStats), ci, vp]
+    L.mmf_simtopk_segmented_exact.argtypes = list(L.mmf_simtopk_segmented.argtypes)
+    L.mmf_simtopk_combined_segmented_exact.argtypes = list(L.mmf_simtopk_combined.argtypes)
+    L.mmf_simtopk_segmented_exact.restype = L.mmf_simtopk_combined_segmented_exact.restype = ci
+    L.mmf_segmented_exact_table.argtypes = [vp, vp, i64, ci, ci, ci, vp, i64, ctypes.POINTER(ci)]
+    L.mmf_segmented_exact_table.restype = i64
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

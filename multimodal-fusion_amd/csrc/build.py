@@ -22,7 +22,8 @@ SOURCES = ["mmf_api.hip", "mmf_prep.hip", "mmf_scan_f32.hip", "mmf_scan_bf16.hip
 HEADERS = ["mmf_dev.h", "mmf_host.h", os.path.join(ROOT, "include", "mmf_hg.h"), os.path.join(ROOT, "include", "mmf_hg_pool.h"),
            os.path.join(ROOT, "include", "mmf_hg_stream.h"), os.path.join(ROOT, "include", "mmf_hg_topk.h"), os.path.join(ROOT, "include", "mmf_hg_topk16.h"),
            os.path.join(ROOT, "include", "mmf_hg_wide.h"), os.path.join(ROOT, "include", "mmf_hg_wide_seg.h"),
-           os.path.join(ROOT, "include", "ext", "mmf_hg_topk16_seg.h"), os.path.join(ROOT, "include", "ext", "mmf_hg_topk_xy.h")]
+           os.path.join(ROOT, "include", "ext", "mmf_hg_topk16_seg.h"), os.path.join(ROOT, "include", "ext", "mmf_hg_topk_xy.h"),
+           os.path.join(ROOT, "include", "ext", "mmf_hg_seg_exact.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]

@@ -2663,3 +2663,230 @@ int mmf_knn_clique_edges_fill(const int64_t* nbr, int64_t n, int k, const int64_
 
 
 }  // extern "C"
+
+// ---- segmented exact scan (include/ext/mmf_hg_seg_exact.h) -----------------------------------------------
+// One table-driven launch of the exact scan for every segment with rows and at least k admissible columns, one re-rank over all
+// rows with ids that are rows of Y, one fail-count readback.  The segments short of columns keep the launch loop (ExactPass
+// slices).  P set: the combined key of mmf_simtopk_combined (r.X == r.Y == F, MMF_RBF, r.lambda = lambda_h).
+namespace mmf {
+
+static int check_pow2_splits(const char* who, const mmf_simtopk_opts* opts) {
+  const int cs = opts ? opts->col_splits : 0;
+  if (cs < 0 || (cs & (cs - 1)) != 0) { set_error("%s: col_splits must be 0 or a power of two (got %d)", who, cs); return MMF_E_INVALID; }
+  return MMF_OK;
+}
+
+// r: checked, begun, n > 0.  xp / yp: host offsets of the S segments on the two sides (the same array for a self call).
+static int run_segmented_exact(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts,
+                               const float* P, int dp, float lambda_g) {
+  const char* who = r.call.who;
+  const hipStream_t s = r.call.s;
+  const int k = r.k, self1 = r.exclude_self ? 1 : 0;
+  const int cap = scan_f32_cap(std::min(r.kk, 44));
+  int ranges = 1;
+  std::vector<char> served;
+  const std::vector<int64_t> tab = seg_exact_table(xp, yp, S, k, r.exclude_self, opts ? opts->col_splits : 0, &ranges, &served);
+  const int64_t grid = (int64_t)tab.size() / 8;
+  if (grid >= ((int64_t)1 << 31)) { set_error("%s: %lld workgroups", who, (long long)grid); return MMF_E_UNSUPPORTED; }
+  const int lists = 2 * ranges;
+  const int k_pass_max = 44 - self1;
+  const int passes = (k + k_pass_max - 1) / k_pass_max;
+  const bool floors = passes > 1;
+
+  // the segments the table does not serve: the launch loop, for what they have
+  ExactPass ex(r, nullptr, nullptr);
+  ex.same = self;
+  ex.P = P; ex.dp = dp; ex.lambda_g = lambda_g;
+  int64_t unserved_rows = 0;
+  for (int64_t g = 0; g < S; ++g) {
+    const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g];
+    if (ng == 0 || served[g]) continue;
+    unserved_rows += ng;
+    MMF_HIP(hipMemsetAsync(r.out_idx + xp[g] * k, 0xff, (size_t)ng * k * 8, s));
+    MMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.out_val + xp[g] * k), (int)0xff800000u, (size_t)ng * k, s));
+    const int64_t adm = admissible_columns(xp[g], ng, yp[g], mg, r.exclude_self);
+    if (adm > 0) ex.add(ExactGroup{xp[g], ng, false, yp[g], mg, (int)adm});
+  }
+
+  const int64_t n = r.n, m = r.m;
+  const size_t list_words = (size_t)n * lists;
+  size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + 2 * ws_bytes(n, 4) + ws_bytes(256, 4) + ws_bytes(4 * (size_t)passes, 4);
+  if (grid > 0)
+    need += ws_bytes(prep_f32_bytes(m, r.d), 1) + (self ? 0 : ws_bytes(prep_f32_bytes(n, r.d), 1)) + ws_bytes(tab.size(), 8) +
+            ExactLists::bytes(n, list_words, cap, floors);
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* rx = ws.take<float>(n);
+  float* cy = self ? rx : ws.take<float>(m);
+  float* pn = P ? ws.take<float>(n) : nullptr;
+  uint32_t* cand_total = ws.take<uint32_t>(256);
+  uint32_t* fail_counts = ws.take<uint32_t>(4 * (size_t)passes);   // one block per pass: the rows outside the table fail in each
+  ex.rx = rx; ex.cy = cy; ex.pn = pn;
+
+  EventTimer t[3];   // prep (row scalars, f32 images, table), scan, re-rank; several passes: the whole loop is "scan"
+  MMF_TRY(t[0].start(r.profile, s));
+  MMF_TRY(launch_row_scalars(r.X, n, r.d, r.dtype, r.metric, rx, nullptr, s));
+  if (!self && m > 0) MMF_TRY(launch_row_scalars(r.Y, m, r.d, r.dtype, r.metric, cy, nullptr, s));
+  if (P) MMF_TRY(launch_row_scalars(P, n, dp, MMF_F32, MMF_RBF, pn, nullptr, s));
+  std::vector<uint32_t> h_fail(4 * (size_t)passes, 0), h_tot(r.stats && grid > 0 ? 256 : 0);
+  if (grid > 0) {
+    float* Yp = reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(m, r.d)));
+    float* Xp = self ? Yp : reinterpret_cast<float*>(ws.take<char>(prep_f32_bytes(n, r.d)));
+    int64_t* d_tab = ws.take<int64_t>(tab.size());
+    ExactLists B;
+    B.carve(ws, n, list_words, cap, floors);
+    MMF_TRY(launch_prep_f32(r.Y, m, r.d, r.dtype, nullptr, Yp, s));
+    if (!self) MMF_TRY(launch_prep_f32(r.X, n, r.d, r.dtype, nullptr, Xp, s));
+    MMF_TRY(upload_table(s, d_tab, tab.data(), tab.size() * 8));
+    // the slots of ranges a segment does not use, and every slot of a row outside the table, stay empty
+    MMF_HIP(hipMemsetAsync(B.L.cnt, 0, list_words * 4, s));
+    MMF_HIP(hipMemsetAsync(B.L.overflow, 0, (size_t)n * 4, s));
+    MMF_HIP(hipMemsetAsync(fail_counts, 0, 16 * (size_t)passes, s));
+    MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
+    MMF_TRY(t[0].stop(s));
+
+    CandLists L = B.L;
+    L.lists = lists; L.cap = cap;
+    ScanProblem sp{};
+    sp.X = r.X; sp.n = n; sp.Y = r.Y; sp.m = m; sp.Xp = Xp; sp.Yp = Yp; sp.d = r.d; sp.dtype = r.dtype; sp.metric = r.metric;
+    sp.lambda = r.lambda; sp.rx = rx; sp.cy = cy; sp.row_ids = nullptr; sp.n_rows = n; sp.col_splits = ranges;
+    SelectProblem q = r.select();   // all rows, ids are rows of Y: no offsets
+    q.rx = rx; q.cy = cy; q.out_stride = k;
+    q.fail_rows = B.fail_rows; q.cand_total = r.stats ? cand_total : nullptr;
+    if (P) {
+      sp.Pq = sp.Pc = q.Pq = q.Pc = P; sp.pnq = sp.pnc = q.pnq = q.pnc = pn;
+      sp.dp = q.dp = dp; sp.lambda_g = q.lambda_g = lambda_g;
+    }
+    MMF_TRY(t[1].start(r.profile, s));
+    int pass = 0;
+    for (int done = 0; done < k; done += k_pass_max, ++pass) {
+      const int kp = std::min(k - done, k_pass_max);
+      const bool more = done + kp < k;
+      sp.kk = kp + self1;
+      if (done > 0) { sp.floor_key = B.floor_key; sp.floor_id = B.floor_id; }
+      MMF_TRY(launch_scan_f32_seg(sp, L, d_tab, grid, s));
+      if (passes == 1) { MMF_TRY(t[1].stop(s)); MMF_TRY(t[2].start(r.profile, s)); }
+      q.k = kp; q.out_off = done;
+      q.fail_count = fail_counts + 4 * pass;
+      q.floor_key_out = more ? B.floor_key : nullptr; q.floor_id_out = more ? B.floor_id : nullptr;
+      MMF_TRY(P ? launch_rerank_combined(q, L, s) : launch_select(q, L, s));
+    }
+    MMF_TRY(t[passes == 1 ? 2 : 1].stop(s));
+    MMF_HIP(hipMemcpyAsync(h_fail.data(), fail_counts, 16 * (size_t)passes, hipMemcpyDeviceToHost, s));
+    if (!h_tot.empty()) MMF_HIP(hipMemcpyAsync(h_tot.data(), cand_total, 1024, hipMemcpyDeviceToHost, s));
+  } else {
+    MMF_TRY(t[0].stop(s));
+  }
+  if (!ex.pieces.empty()) {   // images and lists of the launch loop in the second workspace slot
+    Workspace aux;
+    MMF_TRY(r.call.workspace(ex.image_bytes() + ex.list_bytes(), &aux, 1));
+    ExactLists B;
+    B.carve(aux, ex.rows_total, ex.list_words, ex.cap(), ex.floors());
+    MMF_TRY(B.zero(s));
+    MMF_TRY(ex.run(aux, B));
+  }
+  MMF_HIP(hipStreamSynchronize(s));
+  for (int p = 0; p < passes && grid > 0; ++p)
+    if (h_fail[4 * p] != (uint32_t)unserved_rows) {
+      set_error("%s: %lld rows failed in the exact scan (internal invariant)", who, (long long)h_fail[4 * p] - (long long)unserved_rows);
+      return MMF_E_INTERNAL;
+    }
+  fill_stats(r.stats, MMF_PREC_EXACT, grid > 0 ? ranges : (ex.pieces.empty() ? 1 : ex.splits(ex.pieces[0])), grid > 0 ? (int)grid : ex.grid,
+             t[0].ms(), t[1].ms(), t[2].ms(), 0.f, 0, 0, 0, h_tot);
+  return MMF_OK;
+}
+
+}  // namespace mmf
+
+extern "C" {
+
+int mmf_simtopk_segmented_exact(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
+                                float lambda, int k, int exclude_self, const int64_t* x_ptr_host, const int64_t* y_ptr_host,
+                                int64_t n_segments, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
+                                mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  const char* who = "simtopk_segmented_exact";
+  const bool self = (Y == nullptr);
+  if (self) { Y = X; m = n; y_ptr_host = x_ptr_host; }
+  Request r{Call(who, device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, 0, 0,
+            out_idx, out_val, stats, opts && opts->profile};
+  // check_common's refusals, under this entry's name
+  MMF_TRY(r.call.on_device());
+  if (n < 0 || m < 0 || d < 1) { set_error("%s: bad shape n=%lld m=%lld d=%lld", who, (long long)n, (long long)m, (long long)d); return MMF_E_INVALID; }
+  if (in_dtype != MMF_F32 && in_dtype != MMF_BF16 && in_dtype != MMF_F16) { set_error("%s: bad in_dtype %d", who, in_dtype); return MMF_E_INVALID; }
+  if (n > 0 && !X) { set_error("%s: X is NULL", who); return MMF_E_INVALID; }
+  if (n >= (int64_t)1 << 31 || m >= (int64_t)1 << 31) { set_error("%s: n and m must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  MMF_TRY(r.check(MMF_PREC_EXACT, true, [&] {
+    MMF_TRY(check_offsets(who, "x_ptr", x_ptr_host, n_segments, 0, 0, n));
+    MMF_TRY(check_offsets(who, "y_ptr", y_ptr_host, n_segments, 0, 0, m));
+    if (m > 0 && !Y) { set_error("%s: Y is NULL", who); return MMF_E_INVALID; }
+    MMF_TRY(check_pow2_splits(who, opts));
+    const int prec = opts ? opts->precision : MMF_PREC_AUTO;
+    if (prec != MMF_PREC_AUTO && prec != MMF_PREC_EXACT) {
+      set_error("%s: precision %d: only MMF_PREC_AUTO and MMF_PREC_EXACT (the 16-bit scans are mmf_simtopk_segmented_wide's)", who, prec);
+      return prec == MMF_PREC_FAST || prec == MMF_PREC_FAST_BF16 ? MMF_E_UNSUPPORTED : MMF_E_INVALID;
+    }
+    if (n > 0 && (!out_idx || !out_val)) { set_error("%s: NULL output", who); return MMF_E_INVALID; }
+    return MMF_OK;
+  }));
+  if (stats) stats->near_rows = -1;
+  if (n == 0) return MMF_OK;
+  return run_segmented_exact(r, self, x_ptr_host, y_ptr_host, n_segments, opts, nullptr, 0, 0.0f);
+}
+
+int mmf_simtopk_combined_segmented_exact(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
+                                         float lambda_g, int k, int exclude_self, const int64_t* ptr_host, int64_t n_segments,
+                                         int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats,
+                                         int device_id, void* hip_stream) {
+  const char* who = "simtopk_combined_segmented_exact";
+  MMF_TRY(Call(who, device_id, hip_stream).on_device());
+  if (n < 0) { set_error("%s: n must be >= 0 (got %lld)", who, (long long)n); return MMF_E_INVALID; }
+  if (d < 1) { set_error("%s: d must be at least 1 (got %lld)", who, (long long)d); return MMF_E_INVALID; }
+  if (dp < 1) { set_error("%s: dp must be at least 1 (got %lld)", who, (long long)dp); return MMF_E_INVALID; }
+  if (k < 1) { set_error("%s: k must be at least 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (!(lambda_h >= 0.0f) || !std::isfinite(lambda_h)) { set_error("%s: lambda_h must be finite and >= 0 (got %g)", who, lambda_h); return MMF_E_INVALID; }
+  if (!(lambda_g >= 0.0f) || !std::isfinite(lambda_g)) { set_error("%s: lambda_g must be finite and >= 0 (got %g)", who, lambda_g); return MMF_E_INVALID; }
+  if (n > 0 && !F) { set_error("%s: F is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !P) { set_error("%s: P is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !out_idx) { set_error("%s: out_idx is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !out_val) { set_error("%s: out_val is NULL", who); return MMF_E_INVALID; }
+  MMF_TRY(check_offsets(who, "ptr_host", ptr_host, n_segments, 0, 0, n));
+  MMF_TRY(check_pow2_splits(who, opts));
+  if (dp > 8) { set_error("%s: dp = %lld > 8 is not supported", who, (long long)dp); return MMF_E_UNSUPPORTED; }
+  const int kk = k + (exclude_self ? 1 : 0);
+  if (kk > 44) { set_error("%s: k + self = %d > 44 is not supported (the combined re-rank has no floors)", who, kk); return MMF_E_UNSUPPORTED; }
+  if (n >= (int64_t)1 << 31) { set_error("%s: n must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  const int prec = opts ? opts->precision : MMF_PREC_AUTO;
+  if (prec != MMF_PREC_AUTO && prec != MMF_PREC_EXACT) {
+    set_error("%s: precision %d: only MMF_PREC_AUTO and MMF_PREC_EXACT (the 16-bit scan is mmf_simtopk_combined_fast_segmented)", who, prec);
+    return MMF_E_UNSUPPORTED;
+  }
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n == 0) return MMF_OK;
+  Request r{Call(who, device_id, hip_stream), F, n, F, n, d, MMF_F32, MMF_RBF, lambda_h, k, exclude_self, 0, 0,
+            out_idx, out_val, stats, opts && opts->profile};
+  r.kk = kk;
+  r.precision = MMF_PREC_EXACT;
+  MMF_TRY(r.call.begin());
+  return run_segmented_exact(r, true, ptr_host, ptr_host, n_segments, opts, P, (int)dp, lambda_g);
+}
+
+int64_t mmf_segmented_exact_table(const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_segments, int k, int exclude_self,
+                                  int col_splits, int64_t* table_host, int64_t capacity, int* lists_out) {
+  const char* who = "segmented_exact_table";
+  if (!y_ptr_host) y_ptr_host = x_ptr_host;
+  MMF_TRY(check_offsets(who, "x_ptr", x_ptr_host, n_segments, 0, 0, kAnyRows));
+  MMF_TRY(check_offsets(who, "y_ptr", y_ptr_host, n_segments, 0, 0, kAnyRows));
+  if (k < 1) { set_error("%s: k must be >= 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (col_splits < 0 || (col_splits & (col_splits - 1)) != 0) { set_error("%s: col_splits must be 0 or a power of two (got %d)", who, col_splits); return MMF_E_INVALID; }
+  int ranges = 1;
+  const std::vector<int64_t> tab = seg_exact_table(x_ptr_host, y_ptr_host, n_segments, k, exclude_self, col_splits, &ranges, nullptr);
+  const int64_t grid = (int64_t)tab.size() / 8;
+  if (table_host) {
+    if (capacity < grid) { set_error("%s: table of %lld entries needed", who, (long long)grid); return MMF_E_INVALID; }
+    if (grid > 0) memcpy(table_host, tab.data(), tab.size() * 8);
+  }
+  if (lists_out) *lists_out = 2 * ranges;
+  return grid;
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@
 #include "../../include/mmf_hg_topk16.h"
 #include "../../include/ext/mmf_hg_topk16_seg.h"
 #include "../../include/ext/mmf_hg_topk_xy.h"
+#include "../../include/ext/mmf_hg_seg_exact.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -245,6 +246,14 @@ struct ScanProblem {
 // mmf_scan_f32.hip: exact scan on v_mfma_f32_32x32x2_f32 (any d, f32/bf16/f16 inputs).
 int scan_f32_cap(int kk);  // list capacity the kernel will use for kk (0 = unsupported)
 int launch_scan_f32(const ScanProblem& p, const CandLists& L, hipStream_t s, int* grid_out);
+
+// the segmented exact scan: the host work table ([entries][8] int64) over the segments x_ptr / y_ptr [S + 1] with
+// at least k admissible columns (*served_out), `col_splits` forced column ranges per segment (0: the runs of
+// sim_dense_combined_seg_table), *ranges_out the largest range count; and ONE launch over its device copy, images / scalars /
+// floors / lists covering all rows, ids = rows of Y, L.lists = 2 * ranges, counts zeroed by the caller
+std::vector<int64_t> seg_exact_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int k, int exclude_self, int col_splits,
+                                     int* ranges_out, std::vector<char>* served_out);
+int launch_scan_f32_seg(const ScanProblem& p, const CandLists& L, const int64_t* sched, int64_t grid, hipStream_t s);
 
 // mmf_select.hip: canonical keys of the candidates, self dropped, top-k by (key desc, id asc).
 struct SelectProblem {

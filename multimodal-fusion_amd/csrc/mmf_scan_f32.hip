@@ -30,6 +30,7 @@
 //           sklearn brute-force kneighbors, build_hypergraph/preprocess_hypergraph.py:379-382.
 #include <stdlib.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "mmf_dev.h"
@@ -77,9 +78,16 @@ struct ScanF32Args {
 // the norms and P), the candidate tile range inside the segment, the output base kptr[s] and the row stride n_s.
 enum { SEGF_SEG = 0, SEGF_ROW0 = 1, SEGF_NQ = 2, SEGF_CBASE = 3, SEGF_T0 = 4, SEGF_T1 = 5, SEGF_OUT = 6, SEGF_NS = 7, SEGF_ENTRY = 8 };
 
-// SEG (MODE_DENSE only, segmented calls): the row block, tile range, candidate base, output base and row stride come from the
+// SEG (segmented calls): the row block, tile range, candidate base, output base and row stride come from the
 // work table a.sched instead of blockIdx / col_splits.  Tiles start at unaligned segment rows and read up to 127 rows past
 // them (the next segment, or the image's unwritten last block): those rows only reach masked outputs.
+//
+// SEG with MODE_SCAN (mmf_simtopk_segmented_exact): the same table, with the segment's column count in SEGF_NS
+// and the number of the workgroup's column range in SEGF_OUT.  q0 is a row of X and rx, the floors, the positions and the
+// lists are addressed by it; a lane past the block's SEGF_NQ queries is a !qvalid lane (threshold +inf, nothing written).  The
+// candidates are rows cbase + j of Y, j < SEGF_NS, and cbase + j is the id the lists, the floor test and the re-rank see: one
+// id space, the rows of all of Y.  The range's list slot is row * 2 col_splits + 2 range + half, a.col_splits being the largest
+// range count of any segment.
 //
 // COMB (MODE_SCAN only, mmf_simtopk_combined): the key is the exponent of K_h * K_g, eh + eg (mmf_dev.h: pos_exponent,
 // combined_key).  A lane keeps its query's position (at most 8 floats, zero padded) and chain(p_i, p_i) in registers; the candidate
@@ -89,7 +97,7 @@ enum { SEGF_SEG = 0, SEGF_ROW0 = 1, SEGF_NQ = 2, SEGF_CBASE = 3, SEGF_T0 = 4, SE
 // capacity: that bounds the allocator at 256 registers (204 VGPRs, no AGPRs, nothing spilled); LDS decides how many run.
 template <int MODE, int CAP, int F_KC, bool SEG = false, bool COMB = false>
 __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16 || COMB) ? 2 : 1) void scan_f32_kernel(ScanF32Args a) {
-  static_assert(!SEG || MODE == MODE_DENSE, "the segmented form has the dense epilogue only");
+  constexpr bool SSEG = SEG && MODE == MODE_SCAN;   // the table-driven scan epilogue (launch_scan_f32_seg)
   static_assert(!COMB || MODE == MODE_SCAN, "the combined key is a scan epilogue");
   constexpr int UPR = F_KC / 4;            // 16-byte units per image row
   constexpr int RPP = 64 / UPR;            // image rows per 1 KiB DMA piece
@@ -120,6 +128,7 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16 || COMB) ? 2
     const int64_t* e = a.sched + (size_t)blockIdx.x * SEGF_ENTRY;
     q0 = e[SEGF_ROW0]; qend = q0 + e[SEGF_NQ]; cbase = e[SEGF_CBASE];
     t_begin = e[SEGF_T0]; t_end = e[SEGF_T1]; obase = e[SEGF_OUT]; m = e[SEGF_NS];
+    if constexpr (SSEG) split = (int)e[SEGF_OUT];   // the scan form keeps its column range's number there: the list slot
   } else {
     split = blockIdx.x % a.col_splits;
     const int64_t rb = blockIdx.x / a.col_splits;
@@ -135,7 +144,7 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16 || COMB) ? 2
 
   // this lane's query
   const int64_t qpos = q0 + 32 * wave + c;
-  const bool qvalid = qpos < a.n_rows;
+  const bool qvalid = SSEG ? (qpos < qend) : (qpos < a.n_rows);
   const int64_t qrow = qvalid ? (a.row_ids ? (int64_t)a.row_ids[qpos] : qpos) : 0;
   const float ri = qvalid ? a.rx[qrow] : 1.0f;
   const int metric = a.metric;
@@ -376,19 +385,19 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16 || COMB) ? 2
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const bool jv = (cand0 + (r & 3) + 8 * (r >> 2) + 4 * half) < a.m;
+          const bool jv = (cand0 + (r & 3) + 8 * (r >> 2) + 4 * half) < (SSEG ? m : a.m);
           key[r] = jv ? key[r] : kNegInf;
           acc[t][r] = 0.0f;
         }
         if (floored) {                             // wave-uniform: a later pass of a large-k call
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const uint32_t j = (uint32_t)(cand0 + (r & 3) + 8 * (r >> 2) + 4 * half);
+            const uint32_t j = (uint32_t)((SSEG ? cbase : 0) + cand0 + (r & 3) + 8 * (r >> 2) + 4 * half);
             const bool after = (key[r] < fk) || (key[r] == fk && j > fid);
             key[r] = after ? key[r] : kNegInf;
           }
         }
-        if (__builtin_expect(__any(max16(key) >= list.thr), 0)) list.offer_tile(key, (uint32_t)cand0, half, a.kk);
+        if (__builtin_expect(__any(max16(key) >= list.thr), 0)) list.offer_tile(key, (uint32_t)((SSEG ? cbase : 0) + cand0), half, a.kk);
       }
     }
 
@@ -479,6 +488,82 @@ int launch_scan_f32(const ScanProblem& p, const CandLists& L, hipStream_t s, int
   if (L.cap == 32) return launch_f32_t<MODE_SCAN, 32>(a, grid, s);
   if (L.cap == 48) return launch_f32_t<MODE_SCAN, 48>(a, grid, s);
   set_error("scan_f32: unsupported list capacity %d", L.cap);
+  return MMF_E_INTERNAL;
+}
+
+// The work table of the segmented exact scan ([entries][SEGF_ENTRY] int64, one entry per workgroup): every segment with rows
+// and at least k admissible columns ("served") gets, per block of F_QT of its rows, one entry per column range.  A segment of T
+// column tiles has R ranges of ceil(T / R) tiles (the empty ones at the end make no entry); R is a power of two, at most T, at
+// most `col_splits` when that is forced (> 0), and 2 R cap <= 1024 candidates per row of the re-rank.  col_splits == 0 is the
+// automatic rule, sim_dense_combined_seg_table's: runs of `per` tiles, `per` sized so that the call makes about 1024 workgroups —
+// a few large segments split their columns and fill the chip, many segments are one range each (measured: DESIGN.md §4.20).
+// y_ptr == x_ptr for a self call.  *ranges_out: the largest R.
+std::vector<int64_t> seg_exact_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int k, int exclude_self, int col_splits,
+                                     int* ranges_out, std::vector<char>* served_out) {
+  const int kk = k + (exclude_self ? 1 : 0);
+  const int cap = scan_f32_cap(kk < 44 ? kk : 44);
+  int max_r = 1;
+  while (2 * (2 * max_r) * cap <= 1024) max_r <<= 1;
+  std::vector<char> served((size_t)S, 0);
+  int64_t pairs = 0;
+  for (int64_t g = 0; g < S; ++g) {
+    const int64_t ng = x_ptr[g + 1] - x_ptr[g], mg = y_ptr[g + 1] - y_ptr[g];
+    const bool overlap = exclude_self && x_ptr[g] < y_ptr[g] + mg && x_ptr[g] + ng > y_ptr[g];
+    served[g] = ng > 0 && mg - (overlap ? 1 : 0) >= k;
+    if (served[g]) pairs += ((ng + F_QT - 1) / F_QT) * ((mg + F_CT - 1) / F_CT);
+  }
+  const int64_t per = std::max<int64_t>(1, (pairs + 1023) / 1024);
+  std::vector<int64_t> tab;
+  int ranges = 1;
+  for (int64_t g = 0; g < S; ++g) {
+    if (!served[g]) continue;
+    const int64_t ng = x_ptr[g + 1] - x_ptr[g], mg = y_ptr[g + 1] - y_ptr[g], tiles = (mg + F_CT - 1) / F_CT;
+    const int64_t want = col_splits > 0 ? col_splits : (tiles + per - 1) / per;
+    int R = 1;
+    while (2 * R <= want && 2 * R <= tiles && 2 * R <= max_r) R <<= 1;
+    if (R > ranges) ranges = R;
+    const int64_t tps = (tiles + R - 1) / R;
+    for (int64_t r = 0; r < ng; r += F_QT)
+      for (int c = 0; c < R && c * tps < tiles; ++c) {
+        const int64_t e[SEGF_ENTRY] = {g, x_ptr[g] + r, ng - r < F_QT ? ng - r : F_QT, y_ptr[g], c * tps,
+                                       std::min<int64_t>((c + 1) * tps, tiles), c, mg};
+        tab.insert(tab.end(), e, e + SEGF_ENTRY);
+      }
+  }
+  if (ranges_out) *ranges_out = ranges;
+  if (served_out) served_out->swap(served);
+  return tab;
+}
+
+// One workgroup per entry of the device copy `sched` of that table.  p.Xp / p.Yp: the f32 images of ALL rows of X and Y; p.rx /
+// p.cy, the floors, the positions and the lists L (L.lists = 2 x the table's largest range count) cover all rows; p.kk, the
+// metric and the floors are those of launch_scan_f32.  Counts of the slots a segment does not use must be zero already.
+int launch_scan_f32_seg(const ScanProblem& p, const CandLists& L, const int64_t* sched, int64_t grid, hipStream_t s) {
+  if (grid <= 0) return MMF_OK;
+  if (p.row_ids || !sched || L.lists < 2 || (L.lists & 1)) { set_error("scan_f32_seg: needs a work table, list pairs and no gathered rows"); return MMF_E_INTERNAL; }
+  ScanF32Args a{};
+  a.Xp = p.Xp; a.Yp = p.Yp; a.n = p.n; a.m = p.m; a.dpad = prep_f32_dim(p.d);
+  a.rx = p.rx; a.cy = p.cy; a.row_ids = nullptr; a.n_rows = p.n;
+  a.neg_lambda = -p.lambda; a.kk = p.kk; a.col_splits = L.lists / 2; a.tiles_per_split = 0;
+  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow;
+  a.floor_key = p.floor_key; a.floor_id = p.floor_id;
+  a.metric = p.metric;
+  a.sched = sched;
+  if (p.Pc) {
+    if (!p.Pq || !p.pnq || !p.pnc || p.dp < 1 || p.dp > 8 || p.metric != MMF_RBF) {
+      set_error("scan_f32_seg: combined key needs both sides' positions and chains, 1 <= dp <= 8 (got %d) and MMF_RBF", p.dp);
+      return MMF_E_INTERNAL;
+    }
+    a.P = p.Pc; a.Pq = p.Pq; a.pnq = p.pnq; a.pnc = p.pnc; a.dp = p.dp; a.neg_lambda_g = -p.lambda_g;
+    if (L.cap == 16) return launch_f32_t<MODE_SCAN, 16, true, true>(a, grid, s);
+    if (L.cap == 32) return launch_f32_t<MODE_SCAN, 32, true, true>(a, grid, s);
+    if (L.cap == 48) return launch_f32_t<MODE_SCAN, 48, true, true>(a, grid, s);
+  } else {
+    if (L.cap == 16) return launch_f32_t<MODE_SCAN, 16, true>(a, grid, s);
+    if (L.cap == 32) return launch_f32_t<MODE_SCAN, 32, true>(a, grid, s);
+    if (L.cap == 48) return launch_f32_t<MODE_SCAN, 48, true>(a, grid, s);
+  }
+  set_error("scan_f32_seg: unsupported list capacity %d", L.cap);
   return MMF_E_INTERNAL;
 }
 

@@ -4,7 +4,8 @@ undirected dedup, max(0, cosine) weights.
 
 Segment s's edges are bit for bit those of ``build_hypergraph_knn_kmeans`` on that slide with both ids shifted by the
 segment's first node.  The three batched steps run once for the whole batch: ``simtopk_segmented`` for the
-neighbours (``wide_scan.simtopk_segmented`` where the feature dim is above 1024 and the wide 16-bit scan applies), ``kmeans_fit_predict_segmented`` for the labels, ``ops.knn_clique_edges`` for the edge list, which comes out in
+neighbours (``wide_scan.simtopk_segmented`` where the feature dim is above 1024 and the wide 16-bit scan applies,
+``segmented_exact.simtopk_segmented_exact`` where no 16-bit scan applies), ``kmeans_fit_predict_segmented`` for the labels, ``ops.knn_clique_edges`` for the edge list, which comes out in
 its documented order without a sort and costs one host read (the edge count).  The labels are scikit-learn's unless a seeding
 decision came within float32 noise of going the other way: ``ambiguous_draws`` / ``ambiguous_trials`` say for which segments.
 """
@@ -37,6 +38,11 @@ def knn_kmeans_edges_segmented(X: torch.Tensor, k: int = 5, num_hyperedges: int 
     # bits — DESIGN.md §4.16)
     if wide_scan.wide_scan_supported(X.shape[1], k, True):
         nbr, _ = wide_scan.simtopk_segmented(X, ptr=p, metric="neg_sq_l2", k=k, exclude_self=True)
+    elif not ops.fast_scan_supported(X.shape[1], k, True):
+        # no 16-bit scan applies (k + self > 20 above d = 512, d > 4096): one table-driven launch of the exact scan instead of the
+        # exact pass per segment; the same bits — DESIGN.md §4.20
+        from . import segmented_exact
+        nbr, _ = segmented_exact.simtopk_segmented_exact(X, ptr=p, metric="neg_sq_l2", k=k, exclude_self=True)
     else:
         nbr, _ = ops.simtopk_segmented(X, ptr=p, metric="neg_sq_l2", k=k, exclude_self=True)
     labels, draws, trials = segmented_labels(X, p, num_hyperedges)
