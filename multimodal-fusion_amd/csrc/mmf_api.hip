@@ -548,7 +548,7 @@ struct FastTail {
   bool sym_try = false; int sym_G = 32; int lists_alloc = 0;
   SymBuffers sym;
   WsKept sym_kept; WsKept* sym_keep = nullptr;   // the work tables the workspace came with, and where to file the ones it leaves with
-  uint32_t* sym_cnt = nullptr; uint32_t* sym_ids = nullptr; float* sym_keys = nullptr;
+  uint32_t* sym_cnt = nullptr; uint2* sym_ent = nullptr;
   int64_t sym_grid() const { return sym_schedule_grid((n + 255) / 256, sym_G); }
   void set_symmetric(int G) {   // before bytes() / carve()
     sym_try = true; sym_G = G;
@@ -559,7 +559,7 @@ struct FastTail {
     v.lists = symmetric ? 4 : lists;
     if (v.lists <= 2) { v.keys = nullptr; v.margin = nullptr; }
     v.spill_stacks = spill_stacks_for(v.lists);
-    if (symmetric) { v.sym_cnt = sym_cnt; v.sym_ids = sym_ids; v.sym_keys = sym_keys; v.sym_cap = kSymCap; }
+    if (symmetric) { v.sym_cnt = sym_cnt; v.sym_ent = sym_ent; v.sym_cap = kSymCap; }
     return v;
   }
 
@@ -629,14 +629,14 @@ struct FastTail {
   size_t bytes() const {
     return b16_lists_bytes(n, lists_alloc, bcap) + FlagBlock::bytes(n) +
            ExactLists::bytes(FB, (size_t)FB * 2 * fb_splits, cap, false) + ws_bytes(scan_scratch_bytes(), 1) +
-           (sym_try ? ws_bytes(n, 4) + 2 * ws_bytes((size_t)n * kSymCap, 4) + SymBuffers::bytes(n_pad_q(), sym_grid()) : 0) +
+           (sym_try ? ws_bytes(n, 4) + ws_bytes((size_t)n * kSymCap, 8) + SymBuffers::bytes(n_pad_q(), sym_grid()) : 0) +
            ws_bytes(2 * n_seed, 4) + ws_bytes((size_t)rows_exact_cap * m, 4) + ws_bytes(select_order_bytes(n), 1) +
            (order_try ? ws_bytes(query_order_bytes(n), 1) + ws_bytes((size_t)n_pad_q() * dp, 2) + 3 * ws_bytes(n_pad_q(), 4) : 0);
   }
   void carve(Workspace& ws) {
     L = carve_b16_lists(ws, n, lists_alloc, bcap);
     if (sym_try) {
-      sym_cnt = ws.take<uint32_t>(n); sym_ids = ws.take<uint32_t>((size_t)n * kSymCap); sym_keys = ws.take<float>((size_t)n * kSymCap);
+      sym_cnt = ws.take<uint32_t>(n); sym_ent = ws.take<uint2>((size_t)n * kSymCap);
       sym.carve(ws, n_pad_q(), sym_grid());
       sym_kept = ws.kept; sym_keep = ws.keep;
     }

@@ -173,8 +173,7 @@ struct CandLists {
   // symmetric 16-bit scan only (else nullptr): the columns a row received from the scans of OTHER rows (launch_scan_b16_sym),
   // with their approximate keys (no slot bits) — select treats them as one more list
   uint32_t* sym_cnt = nullptr;     // [n] entries offered (may pass sym_cap: the row is then flagged for the exact rescan)
-  uint32_t* sym_ids = nullptr;     // [n][sym_cap]
-  float* sym_keys = nullptr;       // [n][sym_cap]
+  uint2* sym_ent = nullptr;        // [n][sym_cap] (id, key bits): one 8-byte store files an entry, one 8-byte load reads it
   int sym_cap = 0;
 };
 
@@ -185,7 +184,7 @@ struct CandLists {
 int64_t sym_schedule_grid(int64_t nb, int G);
 void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out, bool forward = false);
 int sym_default_group(int64_t nb);
-constexpr int kSymCap = 512;            // entries per row of CandLists::sym_ids (1.66 x the largest count on the bench rows, bf16 leg)
+constexpr int kSymCap = 512;            // entries per row of CandLists::sym_ent (1.66 x the largest count on the bench rows, bf16 leg)
 constexpr int kSymLogPerWave = 4096;    // entries of a wave's append log (32 rows: 128 per row; 1.73 x the fullest on the bench rows, bf16 leg)
 struct SymBuffers {
   float* thr = nullptr;            // [n_pad]

@@ -1169,7 +1169,7 @@ __global__ void sym_thr_kernel(const int32_t* seed, float* thr, int64_t n, int64
 // select's own test — enc(key) + slot_ulp >= threshold — against seed[] would be dropped there, so it is not filed (seed: nullptr =
 // file everything, MMF_SYMMETRIC_PRUNE=0).
 __global__ __launch_bounds__(256) void sym_scatter_kernel(const uint32_t* log, const uint32_t* log_cnt, int log_cap, uint32_t* sym_cnt,
-                                                          uint32_t* sym_ids, float* sym_keys, int cap, int32_t* lost,
+                                                          uint2* sym_ent, int cap, int32_t* lost,
                                                           const int32_t* seed, int slot_ulp) {
   const uint32_t c = log_cnt[blockIdx.x];
   const u32x4* lg = reinterpret_cast<const u32x4*>(log) + (size_t)blockIdx.x * log_cap;
@@ -1181,8 +1181,7 @@ __global__ __launch_bounds__(256) void sym_scatter_kernel(const uint32_t* log, c
     }
     const uint32_t slot = atomicAdd(sym_cnt + v[0], 1u);
     if (slot < (uint32_t)cap) {
-      sym_ids[(size_t)v[0] * cap + slot] = v[1];
-      sym_keys[(size_t)v[0] * cap + slot] = __uint_as_float(v[2]);
+      sym_ent[(size_t)v[0] * cap + slot] = make_uint2(v[1], v[2]);      // (id, key bits): one 8-byte store
     } else {
       atomicMax(lost + v[0], 0x7fffffff);
     }
@@ -1232,7 +1231,7 @@ int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandL
   a.sched = sb.sched + (size_t)grid * SEG_ENTRY; a.list_base = 2; a.share = 1;
   MMF_TRY((launch_b16_t<32, 8, 2, B_CAP, false, false, 2>(a, p.f16, grid, s)));
   hipLaunchKernelGGL(sym_scatter_kernel, dim3((unsigned)(grid * 8)), dim3(256), 0, s, sb.log, sb.log_cnt, kSymLogPerWave, L.sym_cnt,
-                     L.sym_ids, L.sym_keys, L.sym_cap, pn.seed + pn.seed_stride, y.prune ? pn.seed : nullptr, L.slot_ulp);
+                     L.sym_ent, L.sym_cap, pn.seed + pn.seed_stride, y.prune ? pn.seed : nullptr, L.slot_ulp);
   MMF_LAUNCH_CHECK();
   if (grid_out) *grid_out = (int)(2 * grid);
   return MMF_OK;

@@ -29,8 +29,10 @@ struct SelectArgs {
   int slot_ulp;                                     // ... which carry this many ulps of id-slot bits
   const uint32_t* spill_cnt; const uint32_t* spill_ids; int spill_cap;   // optional: the row's overflow list
   int spill_stacks;                                 // its two-stack form: spill_cnt[row] = front | back << 16 (SpillSink)
-  const uint32_t* sym_cnt; const uint32_t* sym_ids; const float* sym_keys; int sym_cap;   // optional (symmetric scan): one more list per row,
-                                                    // with keys — the columns the row received from the scans of other rows
+  const uint32_t* sym_cnt; const uint2* sym_ent; int sym_cap;   // optional (symmetric scan): one more list per row, (id, key bits)
+                                                    // pairs — the columns the row received from the scans of other rows
+  int lean;                                         // MMF_SELECT_LEAN: every count of a row in one memory round trip and every entry in a second,
+                                                    // the pruning threshold by rank counting (0: list after list, and the round loop)
   // staged kernel, two passes when overflow lists exist: pass 0 handles the rows without overflow entries in a lean
   // LDS footprint and queues the others; pass 1 (room for the overflow entries) takes the queue
   int pass; int two_pass;
@@ -100,15 +102,33 @@ __device__ __forceinline__ bool row_waits(const SelectArgs& a, int64_t pos) {
   return a.spill_cnt[pos] != 0 || (a.late != nullptr && a.late[pos] != 0);
 }
 
+// The counts a row's gather starts from, in the many-short-lists layout: a lane's list count and the count of received entries.  A
+// caller that looks at the row's flags first fetches them together with those (one memory round trip for all of them).
+struct GatherHead { uint32_t mycn, symc; };
+__device__ __forceinline__ bool gather_lean(const SelectArgs& a) { return a.lean && a.lists > 2 && a.lists <= 64 && a.cap <= 16; }
+__device__ __forceinline__ GatherHead gather_head(const SelectArgs& a, int64_t pos, int lane) {
+  GatherHead h;
+  h.mycn = lane < a.lists ? a.cand_cnt[pos * a.lists + lane] : 0u;
+  h.symc = a.sym_cnt ? a.sym_cnt[pos] : 0u;
+  return h;
+}
+
 __device__ __forceinline__ int gather_candidates(const SelectArgs& a, int64_t pos, int lane, uint32_t* id, float* key,
-                                                 int maxc) {
+                                                 int maxc, bool have_head = false, GatherHead head = GatherHead{0u, 0u}) {
   int total = 0;
   const bool prune = a.cand_keys != nullptr && a.margin != nullptr;
+  bool sym_placed = false;
   if (a.lists > 2 && a.lists <= 64 && a.cap <= 16) {
     // many short lists (paneled scans, column splits): one lane per list reads the counts, a wave scan places the lists, and four lists
     // are copied at a time (16 lanes each) — list after list, every count and every copy was a memory round trip of its own (18 lists:
     // 27 us per row).  Same layout as below: list 0's entries, then list 1's, ...
-    const uint32_t mycn = lane < a.lists ? a.cand_cnt[pos * a.lists + lane] : 0u;
+    // Lean (MMF_SELECT_LEAN): the count of the received entries comes with the list counts, and the first 64 of those entries — (id, key)
+    // pairs — are loaded in the same batch as the lists' entries and placed behind them as before: two dependent round trips per row
+    // where there were four.
+    const bool lean = gather_lean(a);
+    GatherHead h = head;
+    if (!(lean && have_head)) { h = GatherHead{lane < a.lists ? a.cand_cnt[pos * a.lists + lane] : 0u, 0u}; if (lean) h.symc = a.sym_cnt ? a.sym_cnt[pos] : 0u; }
+    const uint32_t mycn = h.mycn;
     uint32_t incl = mycn;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -117,6 +137,12 @@ __device__ __forceinline__ int gather_candidates(const SelectArgs& a, int64_t po
     }
     const int raw = __shfl((int)incl, 63);
     if (raw > maxc) return -1;
+    const int scn = (int)(h.symc < (uint32_t)a.sym_cap ? h.symc : (uint32_t)a.sym_cap);   // (beyond the capacity: the row is flagged, not read)
+    uint2 sv = make_uint2(0u, 0u);
+    if (lean && a.sym_cnt) {
+      if (raw + scn > maxc) return -1;
+      sv = a.sym_ent[pos * a.sym_cap + (lane < scn ? lane : 0)];
+    }
     const uint32_t excl = incl - mycn;
     const int g = lane >> 4, e = lane & 15;
     // (loads unconditional — a clamped address where the lane has no entry — and four steps unrolled: the loads of a step do not wait
@@ -137,6 +163,19 @@ __device__ __forceinline__ int gather_candidates(const SelectArgs& a, int64_t po
       }
     }
     total = raw;
+    if (lean && a.sym_cnt) {
+      if (lane < scn) {
+        id[total + lane] = sv.x;
+        if (prune) key[total + lane] = __uint_as_float(sv.y);
+      }
+      for (int e2 = 64 + lane; e2 < scn; e2 += 64) {
+        const uint2 v = a.sym_ent[pos * a.sym_cap + e2];
+        id[total + e2] = v.x;
+        if (prune) key[total + e2] = __uint_as_float(v.y);
+      }
+      total += scn;
+      sym_placed = true;
+    }
   } else
   for (int l = 0; l < a.lists; ++l) {
     const uint32_t cn = a.cand_cnt[pos * a.lists + l];
@@ -148,13 +187,14 @@ __device__ __forceinline__ int gather_candidates(const SelectArgs& a, int64_t po
     }
     total += (int)cn;
   }
-  if (a.sym_cnt) {   // symmetric scan: the entries other rows' scans sent to this row, ids and keys — pruned with the lists
+  if (a.sym_cnt && !sym_placed) {   // symmetric scan: the entries other rows' scans sent to this row, ids and keys — pruned with the lists
     const uint32_t c = a.sym_cnt[pos];
     const int cn = (int)(c < (uint32_t)a.sym_cap ? c : (uint32_t)a.sym_cap);   // (beyond the capacity: the row is flagged, not read)
     if (total + cn > maxc) return -1;
     for (int e = lane; e < cn; e += 64) {
-      id[total + e] = a.sym_ids[pos * a.sym_cap + e];
-      if (prune) key[total + e] = a.sym_keys[pos * a.sym_cap + e];
+      const uint2 v = a.sym_ent[pos * a.sym_cap + e];
+      id[total + e] = v.x;
+      if (prune) key[total + e] = __uint_as_float(v.y);
     }
     total += cn;
   }
@@ -186,10 +226,27 @@ __device__ __forceinline__ int gather_candidates(const SelectArgs& a, int64_t po
   if (!prune || total <= kk) return append_spill(total);
   __builtin_amdgcn_s_waitcnt(0xC07F);
   __builtin_amdgcn_wave_barrier();
-  // t = kk-th largest approximate key: kk rounds of "best entry ranked after the previous pick" under
-  // (key desc, position asc), so equal keys are counted once each
+  // t = kk-th largest approximate key under (key desc, position asc), so equal keys are counted once each.
+  // Lean, a union of at most 64 entries (the usual row): one key per lane, every lane COUNTS the entries that rank before its own —
+  // each one broadcast out of its lane's register by v_readlane, no LDS trip, no butterfly — and the lane of rank kk - 1 holds t.
+  // (key, position) is a strict total order, so exactly one lane has that rank; should keys outside the numerics contract (NaN)
+  // break the order, the rounds below decide as they always did.
   float pk = 0.0f;
   uint32_t pe = 0;
+  bool ranked = false;
+  if (a.lean && total <= 64) {
+    const int nt = __builtin_amdgcn_readfirstlane(total);
+    const float mk = lane < nt ? key[lane] : kNegInf;
+    int rank = 0;
+    for (int e = 0; e < nt; ++e) {
+      const float ke = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(mk), e));
+      rank += better(ke, (uint32_t)e, mk, (uint32_t)lane) ? 1 : 0;
+    }
+    const unsigned long long hit = __ballot(lane < nt && rank == kk - 1);
+    if (__popcll(hit) == 1) { pk = __shfl(mk, __builtin_ctzll(hit)); ranked = true; }
+  }
+  // otherwise kk rounds of "best entry ranked after the previous pick"
+  if (!ranked)
   for (int t = 0; t < kk; ++t) {
     float bk = kNegInf;
     uint32_t be = kNoIdx;
@@ -420,11 +477,15 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void select_staged_kernel(SelectArg
     for (int i = lane; i < 256; i += 64) { c += a.defer_cnt[i]; dn += a.defer_cnt[256 + i]; }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { c += (uint32_t)__shfl_xor((int)c, o); dn += (uint32_t)__shfl_xor((int)dn, o); }
+    if (c == 0) return;                                       // no row waits (the usual call on Gaussian rows): nothing to walk, in either shape
     const bool scattered = (int64_t)dn * 2 < (int64_t)c;     // the grouped kernel finished less than half of the waiting rows
     if ((a.only_if == 1) != scattered) return;
   }
+  const bool lean_head = gather_lean(a);
   for (int64_t vb = blockIdx.x; vb < (SECOND ? a.order_blocks : (int64_t)gridDim.x); vb += gridDim.x) {
   int64_t pos = vb * SEL_WAVES + wave;
+  GatherHead head{0u, 0u};
+  bool have_head = false;
   if (SECOND && a.pass == 1 && a.key_sorted && a.only_if != 1) {   // (the launch for scattered rows walks them in row order: their
                                                                      //  candidate sets share nothing, and row order keeps the list reads streaming)
     // virtual block b -> chunk (b % 8) * (blocks / 8) + b / 8 of the sorted order (order_blocks is a multiple of 8)
@@ -435,6 +496,7 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void select_staged_kernel(SelectArg
     if (a.done && a.done[pos]) continue;
   } else {
     if (pos >= a.n_rows) continue;
+    if (lean_head) { head = gather_head(a, pos, lane); have_head = true; }      // issued with the flag loads below: one round trip for all of them
     if (a.two_pass) {
       // two passes: rows with overflow entries wait for the second launch, which has LDS room for them.  Both launches
       // cover every row and a row decides by its own counters which one it belongs to (a queue filled through one
@@ -454,7 +516,7 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void select_staged_kernel(SelectArg
   const bool was_overflow = failed;
   int total = 0;
   if (!failed) {
-    total = gather_candidates(a, pos, lane, id, key, maxc);
+    total = gather_candidates(a, pos, lane, id, key, maxc, have_head, head);
     if (total < 0) { failed = true; total = 0; }
   }
   if (!SECOND && a.two_pass && a.late && !failed && total > 2 * (a.k + a.exclude_self) + 32) {    // heavy after pruning: the second pass (grouped re-rank) takes it
@@ -633,6 +695,8 @@ __global__ __launch_bounds__(64 * GR_W) void rerank_group_kernel(SelectArgs a) {
   const int64_t grp = ((int64_t)blockIdx.x & 7) * per + ((int64_t)blockIdx.x >> 3);
   const int64_t slot0 = grp * GR_Q;
   if (slot0 >= a.n_rows) return;
+  // key order: the waiting rows come first, so a group whose first row carries the marker holds none — leave before touching LDS
+  if (!a.group_by_pos && a.key_sorted[slot0] == 0xffffffffu) return;
   if (tid < GR_Q) {
     const int64_t slot = slot0 + tid;
     int p = -1;
@@ -1001,6 +1065,14 @@ size_t select_order_bytes(int64_t n) {
   return (5 * nn + 512) * 4 + ((tb + 255) & ~size_t(255)) + 256;
 }
 
+// MMF_SELECT_LEAN (read per call): unset / 1 = a row's counts in one memory round trip, its entries in a second, and the pruning
+// threshold by rank counting (gather_candidates); 0 = list after list and the round loop.  Results are the same; for measurements
+// and tests.
+static bool select_lean_mode() {
+  const char* e = getenv("MMF_SELECT_LEAN");
+  return !e || atoi(e) != 0;
+}
+
 int launch_select(const SelectProblem& p, const CandLists& L, hipStream_t s) {
   if (p.n_rows <= 0) return MMF_OK;
   const int sym_cap = L.sym_cnt ? L.sym_cap : 0;
@@ -1020,7 +1092,8 @@ int launch_select(const SelectProblem& p, const CandLists& L, hipStream_t s) {
   a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow; a.lists = L.lists; a.cap = L.cap;
   a.cand_keys = L.keys; a.margin = L.margin; a.slot_ulp = L.slot_ulp;
   a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap; a.spill_stacks = L.spill_stacks;
-  a.sym_cnt = L.sym_cnt; a.sym_ids = L.sym_ids; a.sym_keys = L.sym_keys; a.sym_cap = sym_cap;
+  a.sym_cnt = L.sym_cnt; a.sym_ent = L.sym_ent; a.sym_cap = sym_cap;
+  a.lean = select_lean_mode() ? 1 : 0;
   a.pass = 0; a.two_pass = p.two_pass ? 1 : 0;
   void* order_temp = nullptr;
   size_t order_temp_bytes = 0;
