@@ -347,6 +347,13 @@ static bool symmetric_prune_mode() {
   const char* e = getenv("MMF_SYMMETRIC_PRUNE");
   return !e || atoi(e) != 0;
 }
+// MMF_WIDE_SINK (read per call): unset / 1 = the wide scan's crowded lists write to the rows' overflow lists (mmf_scan_b16w.hip,
+// DESIGN.md §4.21), 0 = the kernels without them: a crowded row is flagged and rescanned exactly.  Results are the same; for
+// measurements and tests.
+static bool wide_sink_mode() {
+  const char* e = getenv("MMF_WIDE_SINK");
+  return !e || atoi(e) != 0;
+}
 static constexpr int64_t kSymMinRows = 131072;
 static bool symmetric_scan_wanted(int64_t n, int dp, int bcap, int metric, int forced_splits, bool same_ids, int* G) {
   if (!same_ids || dp != 512 || bcap != scan_bf16_cap(1, 512) || forced_splits != 0) return false;
@@ -564,10 +571,12 @@ struct FastTail {
   }
 
   int dp, panels;
-  bool wide = false;   // dp > 1024: launch_scan_b16w takes the slot of launch_scan_b16 (no query order, symmetric scan or panels)
+  bool wide = false;   // dp > 1024: launch_scan_b16w takes the slot of launch_scan_b16 (no query order, symmetric scan or panels);
+                       // it writes the same overflow lists (L.spill_*) unless MMF_WIDE_SINK=0
   int panel_splits[16]; int max_splits = 1;
   int64_t n_seed;
   int32_t* seed = nullptr;
+  int64_t seed_stripes() const { return wide ? 3 : 2; }   // thresholds, dropped keys; wide: the overflow lists' best keys (ScanB16Panel::sunk)
   // a handful of flagged rows skips the matrix-core rescan: all their keys, then a block-wide top-k
   static constexpr int64_t kRowsExactMax = 48;
   int64_t rows_exact_cap = 0;
@@ -630,7 +639,7 @@ struct FastTail {
     return b16_lists_bytes(n, lists_alloc, bcap) + FlagBlock::bytes(n) +
            ExactLists::bytes(FB, (size_t)FB * 2 * fb_splits, cap, false) + ws_bytes(scan_scratch_bytes(), 1) +
            (sym_try ? ws_bytes(n, 4) + ws_bytes((size_t)n * kSymCap, 8) + SymBuffers::bytes(n_pad_q(), sym_grid()) : 0) +
-           ws_bytes(2 * n_seed, 4) + ws_bytes((size_t)rows_exact_cap * m, 4) + ws_bytes(select_order_bytes(n), 1) +
+           ws_bytes(seed_stripes() * n_seed, 4) + ws_bytes((size_t)rows_exact_cap * m, 4) + ws_bytes(select_order_bytes(n), 1) +
            (order_try ? ws_bytes(query_order_bytes(n), 1) + ws_bytes((size_t)n_pad_q() * dp, 2) + 3 * ws_bytes(n_pad_q(), 4) : 0);
   }
   void carve(Workspace& ws) {
@@ -643,7 +652,7 @@ struct FastTail {
     flags.carve(ws, n);
     XL.carve(ws, FB, (size_t)FB * 2 * fb_splits, cap, false);
     scan_scratch = ws.take<char>(scan_scratch_bytes());
-    seed = ws.take<int32_t>(2 * n_seed);
+    seed = ws.take<int32_t>(seed_stripes() * n_seed);
     row_keys = ws.take<float>((size_t)rows_exact_cap * m);
     order_scratch = ws.take<char>(select_order_bytes(n));
     if (order_try) {
@@ -675,7 +684,7 @@ struct FastTail {
     EventTimer t_scan, t_sel, t_fb;
     EventTimer t_panel[16];
     int grid = 0;
-    MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n_seed * 8, s));   // kSeedNone, thresholds and dropped keys
+    MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n_seed * 4 * seed_stripes(), s));   // kSeedNone, thresholds and dropped keys
     MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
     MMF_TRY(t_scan.start(profile, s));
     ScanB16Panel pn;
@@ -690,7 +699,12 @@ struct FastTail {
                                   pn, s, &grid));
       if (sym_keep) *sym_keep = tables;
     } else if (fo.n_panels == 0) {
-      if (wide) MMF_TRY(launch_scan_b16w(sp, splits, L, pn, s, &grid));
+      if (wide) {
+        CandLists Lw = L;   // without the sink the overflow lists stay zeroed: select reads them as empty
+        if (!wide_sink_mode()) { Lw.spill_cnt = nullptr; Lw.spill_ids = nullptr; Lw.spill_cap = 0; Lw.spill_stacks = 0; }
+        pn.sunk = seed + 2 * n_seed;
+        MMF_TRY(launch_scan_b16w(sp, splits, Lw, pn, s, &grid));
+      }
       else MMF_TRY(launch_scan_b16(sp, splits, L, scan_scratch, pn, s, &grid));
     } else {
       // one launch per panel, each behind its own arrival event; the launches share the lists (disjoint

@@ -209,6 +209,8 @@ struct ScanB16Panel {
   int32_t* seed = nullptr;                             // [2][seed_stride]: best proven threshold / best dropped key per query
   int64_t seed_stride = 0;                             //   (ordered-int encoding), memset to 0x80 before the first launch
   int share = 0;                                       // more than one workgroup / launch scans each query
+  int32_t* sunk = nullptr;                             // wide scan with overflow lists in the counter form: [seed_stride] best key
+                                                       //   written to the row's overflow list (same encoding and memset), or nullptr
 };
 
 // mmf_prep.hip: the f32 operand image of mmf_scan_f32.hip — [prep_f32_rows(n)][prep_f32_dim(d)] floats, zero padded,

@@ -18,7 +18,9 @@
 //     query, 16 of every 32 candidates": lane l owns query (l & 15) + 16 ((l >> 4) & 1) and, on the rare slow path, swaps
 //     with lane l ^ 16 the values they hold for each other's query.  Lanes l and l ^ 32 own the two halves of one query.
 //   * Lists (WideList below): approximate key AND column id in LDS, 8 bytes per entry, CAP = 16 (k + self <= 11) or 32
-//     (k + self in 12..20) entries per lane.  No overflow lists: a crowded row is flagged and the exact rescan answers it.
+//     (k + self in 12..20) entries per lane.  The plain launches (launch_scan_b16w) give every row an overflow list in global
+//     memory (SpillSink, mmf_dev.h; "Overflow lists" below); the segmented launches have none: there a crowded row is flagged
+//     and the exact rescan answers it.
 //
 // Error margin (the formula of mmf_scan_bf16.hip with KS * 16 read as dp; stored keys carry no slot bits here): with u the
 // f32 rows (normalised for cosine, scaled by the common power of two), z = round_16(u), the scanned value G = bias_j + z_i.z_j
@@ -37,7 +39,35 @@
 // threshold proven for it.  A row whose margin band — the columns with G >= (kk-th best G over ALL columns) - margin — holds
 // at most CAP columns is therefore never flagged: a dropped key has CAP + 1 columns at or above it, so it lies below the
 // band, and every column of the band is still in a list when the thresholds are settled (wide_seed_union_kernel settles them
-// across column splits).
+// across column splits).  A band column that is in neither a list nor the row's overflow list at the end has raised `lost` to
+// at least its key, so the audit flags the row.
+//
+// Overflow lists (the SINK instantiations).  A column is offered to one list pair once and ends in a list, in
+// the row's overflow list, or below the threshold; select re-ranks the overflow entries exactly, so ANY hit may be written down
+// instead of pushed.  A threshold is only ever proven from keys the lists hold (a subset of the row's columns: a lower bound).
+// The policy, for a list whose last compaction left it full (`crowded`, so cnt == CAP) with tband = the pair's kk-th best key
+// at that compaction:
+//   1. a hit below tband + MMF_BAND_SLACK * margin goes straight to the overflow list and does not touch the list (it could
+//      raise the threshold by less than the slack);
+//   2. any other hit replaces the list's worst entry and the worst of the CAP + 1 goes to the overflow list;
+//   3. after kk such replacements the list asks for a compaction.  Each of them left the list with one more key at or above
+//      tband + slack (the key itself, or CAP entries that beat it), CAP >= kk, so the pair's kk-th best is then at least
+//      tband + slack: every compaction a crowded list asks for raises its proven threshold by at least the slack, and a list
+//      costs at most kk overflow slots per slack of threshold it climbs.
+// Without rule 3 a crowded list would never compact of its own accord: drops no longer raise `lost`, the threshold would stay
+// where a transient crowd early in the scan left it, and every later hit would pour into the overflow list.
+// When the overflow list refuses a key (full, or the two stacks met) the old rule applies to that key: lost, thr = max(thr,
+// lost), audited.  One column range per row: the two-stack form (the pair's lower lane fills the row's slots from the front,
+// the upper one from the back, no counter; the pair writes front | back << 16 when the scan ends, stacks that met flag the
+// row).  Column splits: the counter form, slots reserved in chunks of SpillSink::kChunk (at most 7 wasted slots per lane),
+// closed with the empty marker.
+// What was written down and has since been proven irrelevant is taken back when the thresholds are settled, so that a transient
+// crowd early in a scan costs the re-rank nothing: every lane remembers the best key it wrote (`sunk`).  One column range: at
+// every compaction a lane whose best written key lies below the pair's proven threshold empties its stack, so a transient
+// crowd does not use the slots up either; stacks are taken to have met if their high-water marks add up to more than the
+// slots.  Column splits: the lanes leave the row's best written key in ScanB16WArgs::sunk and wide_seed_union_kernel empties
+// the row's overflow list if that key lies below the row's settled threshold (the slots stay used while the scan runs).
+// Either way every discarded key lies below a proven threshold: outside the band.
 #include "mmf_dev.h"
 #include "mmf_host.h"
 
@@ -94,6 +124,9 @@ struct ScanB16WArgs {
   float* cand_keys;          // approximate keys of the entries, or nullptr
   float* margin_out;         // [n_rows], written with cand_keys
   const int32_t* sched;      // SEG kernels only: [grid][WSEG_ENTRY] work table (launch_scan_b16w_seg)
+  // SINK kernels only: the rows' overflow lists (CandLists; SpillSink)
+  uint32_t* spill_cnt; uint32_t* spill_ids; int spill_cap; int spill_stacks;
+  int32_t* sunk;             // counter form: [>= n_rows] best key written to the row's overflow list (wide_enc; atomicMax), or nullptr
 };
 
 // One entry of the segmented work table: a workgroup = one row block of one segment against one column range of that segment.
@@ -111,8 +144,13 @@ enum {
 };
 
 // The lane-private list: entry e of thread t at keys[e * NT + t] / ids[e * NT + t] (LaneList's layout), approximate keys.
-template <int CAP, int NT>
+template <int CAP, int NT, bool SINK = false>
 struct WideList {
+  SpillSink sink;  // SINK only: the row's overflow list
+  float tband;     // SINK only: the pair's kk-th best key at the last compaction that left this list crowded
+  int repl;        // SINK only: hits that went through replace_worst since the last compaction
+  float sunk;      // SINK only: best key this lane wrote to the overflow list and has not taken back; -inf: none
+  uint32_t high;   // SINK only, two stacks: the most entries this lane's stack held before it was emptied
   float* keys; uint32_t* ids;
   int cnt;
   float thr;       // max(proven, lost): what a column has to reach
@@ -122,6 +160,7 @@ struct WideList {
 
   __device__ __forceinline__ void init(float* k, uint32_t* i) {
     keys = k; ids = i; cnt = 0; thr = -kFltMax; proven = -kFltMax; lost = kNegInf; crowded = false;
+    if constexpr (SINK) { tband = kNegInf; repl = 0; sunk = kNegInf; high = 0; }
   }
   __device__ __forceinline__ void push(float key, uint32_t id) {
     keys[cnt * NT] = key; ids[cnt * NT] = id; ++cnt;
@@ -180,10 +219,19 @@ struct WideList {
     }
     cnt = w;
     crowded = cnt >= CAP;
+    if constexpr (SINK) {
+      repl = 0;
+      if (crowded && t > tband) tband = t;
+      if (sink.stacks && sunk < proven) {              // nothing this lane wrote can matter any more: its stack starts over
+        high = sink.cpos > high ? sink.cpos : high;
+        sink.cpos = 0; sunk = kNegInf;
+      }
+    }
   }
 
   // A hit on a full list (lane-private): the worst of the CAP + 1 under (key desc, id asc) is dropped — CAP entries rank
-  // before it — and remembered; nothing below it can matter unless the row is flagged.
+  // before it — and remembered; nothing below it can matter unless the row is flagged.  SINK: it goes to the row's overflow
+  // list instead and is lost only if that refuses it.
   __device__ __forceinline__ void replace_worst(float x, uint32_t id) {
     int wpos = 0;
     float wk = keys[0]; uint32_t wi = ids[0];
@@ -193,7 +241,12 @@ struct WideList {
       if (better(wk, wi, ke, ie)) { wk = ke; wi = ie; wpos = e; }
     }
     float dropped = x;
-    if (better(x, id, wk, wi)) { keys[wpos * NT] = x; ids[wpos * NT] = id; dropped = wk; }
+    uint32_t dropped_id = id;
+    if (better(x, id, wk, wi)) { keys[wpos * NT] = x; ids[wpos * NT] = id; dropped = wk; dropped_id = wi; }
+    if constexpr (SINK) {
+      ++repl;
+      if (sink.put(dropped_id, true)) { sunk = fmaxf(sunk, dropped); return; }
+    }
     lost = fmaxf(lost, dropped);
     thr = fmaxf(thr, lost);
   }
@@ -210,6 +263,24 @@ struct WideList {
       rmask &= rmask - 1;
       const float x = v[r];
       bool hit = x >= thr;
+      if constexpr (SINK) {
+        // rules 1 - 3 of the header; crowded implies cnt == CAP
+        bool band = crowded && x < tband + MMF_BAND_SLACK * margin;
+        if (__any(hit && !band && cnt >= CAP && (!crowded || repl >= kk))) {
+          compact(kk, margin);
+          hit = x >= thr;
+          band = crowded && x < tband + MMF_BAND_SLACK * margin;
+        }
+        if (hit) {
+          const uint32_t id = id0 + rowof(r);
+          if (band) {
+            if (sink.put(id, true)) sunk = fmaxf(sunk, x);
+            else { lost = fmaxf(lost, x); thr = fmaxf(thr, lost); }
+          } else if (cnt < CAP) push(x, id);
+          else replace_worst(x, id);
+        }
+        continue;
+      }
       if (__any(hit && cnt >= CAP && !crowded)) {
         compact(kk, margin);
         hit = x >= thr;
@@ -227,8 +298,9 @@ struct WideList {
 constexpr size_t scan_b16w_lds(int cap) { return (size_t)2 * W_STAGEB + (size_t)2 * W_CT * 4 + (size_t)cap * W_NT * 8; }
 
 // SEG (segmented calls, launch_scan_b16w_seg): the workgroup's row block, column range, id offset and list slot come from the
-// work table a.sched instead of blockIdx / col_splits; everything else is shared.
-template <bool F16, int CAP, bool SEG = false>
+// work table a.sched instead of blockIdx / col_splits; everything else is shared.  SINK (plain launches only): crowded lists
+// write to the rows' overflow lists (header, "Overflow lists").
+template <bool F16, int CAP, bool SEG = false, bool SINK = false>
 __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   char* stages = smem;                                                   // [2][W_STAGEB]
@@ -288,9 +360,16 @@ __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
     margin = 2.0f * (e1 + e2) * 1.001f + 1e-30f;
   }
 
-  WideList<CAP, W_NT> list;
+  static_assert(!(SEG && SINK), "overflow ids are local columns: no segmented form");
+  WideList<CAP, W_NT, SINK> list;
   list.init(lkeys + tid, lids + tid);
   if (!qvalid) list.thr = __builtin_huge_valf();
+  if constexpr (SINK) {
+    if (qvalid) {   // (a lane without a query keeps cap == 0: its sink refuses everything, and it never has a hit)
+      list.sink.cnt = a.spill_cnt; list.sink.ids = a.spill_ids; list.sink.cap = (uint32_t)a.spill_cap; list.sink.row = lrow;
+      if (a.spill_stacks) list.sink.stacks = 1 + half;
+    }
+  }
 
   // DMA roles (scan_f32_kernel's): piece p = wave + 4 i covers tile rows [(p % W_HP) * 8, + 8) of the query (i < 4) or
   // candidate tile; lane l lands at row l / 8, unit l % 8 of the piece and fetches the unit the swizzle puts there.  The
@@ -425,6 +504,19 @@ __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
   // Settle: the pair's proven threshold from what the two lists hold, entries below the threshold dropped before they are
   // written (the re-rank gathers about kk rows per list, not CAP).
   list.compact(a.kk, margin);
+  if constexpr (SINK) {
+    list.sink.close();                    // reserved overflow slots this lane did not use
+    if (a.spill_stacks) {                 // two stacks: both counts in one word; stacks that met cost the row its fast path
+      const uint32_t mine = qvalid ? list.sink.cpos : 0u;   // (the compaction above has emptied a stack that no longer matters)
+      const uint32_t theirs = (uint32_t)__shfl_xor((int)mine, 32);
+      const uint32_t mine_high = mine > list.high ? mine : list.high;
+      const uint32_t theirs_high = (uint32_t)__shfl_xor((int)mine_high, 32);
+      if (qvalid && mine_high + theirs_high > (uint32_t)a.spill_cap) list.lost = kFltMax;
+      if (qvalid && half == 0 && (mine | theirs)) a.spill_cnt[lrow] = mine | (theirs << 16);
+    } else if (qvalid && a.sunk && list.sunk > kNegInf) {
+      atomicMax(a.sunk + lrow, wide_enc(list.sunk));
+    }
+  }
   if (qvalid) {
     const int64_t lbase = lrow * a.lists_total + a.list_base + slot + half;
     a.cand_cnt[lbase] = (uint32_t)list.cnt;
@@ -443,14 +535,18 @@ __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
 // row's columns, so a valid lower bound — and raises the row's threshold to it minus the margin.  With that, "band <= CAP
 // columns => never flagged" holds for any number of splits (header).  kk rounds of "best entry ranked after the previous
 // pick" under (key desc, position asc), as select's pruning does.
+// sunk / spill_cnt (plain launches with overflow lists in the counter form, else nullptr): a row whose best written key lies below
+// its settled threshold gets its overflow list emptied (header of this file, "Overflow lists").
 __global__ __launch_bounds__(256) void wide_seed_union_kernel(const uint32_t* cand_cnt, const float* cand_keys, const float* margin,
-                                                              int lists, int cap, int kk, int32_t* seed, int64_t n_rows) {
+                                                              int lists, int cap, int kk, int32_t* seed, int64_t n_rows,
+                                                              const int32_t* sunk, uint32_t* spill_cnt) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n_rows) return;
   const int slots = lists * cap;
   float pk = 0.0f;
   uint32_t pe = 0;
+  bool proved = true;
   for (int t = 0; t < kk; ++t) {
     float bk = kNegInf;
     uint32_t be = kNoIdx;
@@ -467,13 +563,20 @@ __global__ __launch_bounds__(256) void wide_seed_union_kernel(const uint32_t* ca
       const uint32_t oe = (uint32_t)__shfl_xor((int)be, o);
       if (oe != kNoIdx && (be == kNoIdx || better(ok, oe, bk, be))) { bk = ok; be = oe; }
     }
-    if (be == kNoIdx) return;          // fewer than kk entries: nothing to prove
+    if (be == kNoIdx) { proved = false; break; }   // fewer than kk entries: nothing to prove
     pk = bk; pe = be;
   }
-  if (lane == 0) atomicMax(seed + row, wide_enc(pk - margin[row]));
+  if (lane != 0) return;
+  int32_t settled = seed[row];         // what the scan's lists proved (the scan has finished: same stream)
+  if (proved) {
+    const int32_t p = wide_enc(pk - margin[row]);
+    atomicMax(seed + row, p);
+    if (p > settled) settled = p;
+  }
+  if (sunk && sunk[row] < settled) spill_cnt[row] = 0u;   // (no key written: the count is 0 already)
 }
 
-template <int CAP, bool SEG = false>
+template <int CAP, bool SEG = false, bool SINK = false>
 int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) {
   const size_t lds = scan_b16w_lds(CAP);
   auto go = [&](auto kern) -> int {
@@ -482,6 +585,10 @@ int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) 
     MMF_LAUNCH_CHECK();
     return MMF_OK;
   };
+  if constexpr (SINK) {
+    if (f16) return go(scan_b16w_kernel<true, CAP, SEG, true>);
+    return go(scan_b16w_kernel<false, CAP, SEG, true>);
+  }
   if (f16) return go(scan_b16w_kernel<true, CAP, SEG>);
   return go(scan_b16w_kernel<false, CAP, SEG>);
 }
@@ -496,6 +603,10 @@ int scan_b16w_col_tile() { return W_CT; }
 
 // col_splits must be a power of two.  Lists are indexed by query position; pn: the threshold buffers (no panels, no shared
 // thresholds on this path).  With more than one split L.keys / L.margin must be set: wide_seed_union_kernel reads them.
+// L.spill_cnt (zeroed by the caller) with L.spill_cap > 0: the rows' overflow lists, written by the SINK instantiations in the
+// form L.spill_stacks names (two stacks need the one list pair); without them the kernels that lose what a list cannot hold.
+// pn.sunk (optional, counter form): the rows' best written keys, memset like pn.seed; with it a row whose overflow entries all
+// lie below its settled threshold gets its overflow list emptied.
 int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L, const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
   if (p.n_rows <= 0 || p.m <= 0) return MMF_OK;
   if (!scan_b16w_supported(p.d, p.kk) || p.dp != scan_b16w_dp(p.d)) {
@@ -505,6 +616,11 @@ int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L
   if (col_splits < 1 || (col_splits & (col_splits - 1)) != 0) { set_error("scan_b16w: col_splits %d is no power of two", col_splits); return MMF_E_INTERNAL; }
   if (!pn.seed) { set_error("scan_b16w: threshold buffers missing"); return MMF_E_INTERNAL; }
   if (pn.list_base != 0 || pn.seg_len != 0 || pn.id_off != 0) { set_error("scan_b16w: no paneled form"); return MMF_E_INTERNAL; }
+  const bool sink = L.spill_cnt != nullptr && L.spill_cap > 0;
+  if (sink && (!L.spill_ids || L.spill_cap > 0xffff || (L.spill_stacks && col_splits != 1))) {
+    set_error("scan_b16w: overflow lists of %d slots (two stacks: %d) for %d column splits", L.spill_cap, L.spill_stacks, col_splits);
+    return MMF_E_INTERNAL;
+  }
   if (2 * col_splits != L.lists) { set_error("scan_b16w: %d lists per row for %d column splits", L.lists, col_splits); return MMF_E_INTERNAL; }
   if (L.cap != scan_b16w_cap(p.kk)) { set_error("scan_b16w: list capacity %d, expected %d", L.cap, scan_b16w_cap(p.kk)); return MMF_E_INTERNAL; }
   if (col_splits > 1 && (!L.keys || !L.margin)) { set_error("scan_b16w: column splits need the lists' keys and margins"); return MMF_E_INTERNAL; }
@@ -518,13 +634,18 @@ int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L
   a.lists_total = L.lists; a.list_base = 0;
   a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride;
   a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.cand_keys = L.keys; a.margin_out = L.margin;
+  if (sink) {
+    a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap; a.spill_stacks = L.spill_stacks;
+    a.sunk = L.spill_stacks ? nullptr : pn.sunk;
+  }
   const int64_t row_blocks = (p.n_rows + W_QT - 1) / W_QT;
   const int64_t grid = row_blocks * col_splits;
   if (grid_out) *grid_out = (int)grid;
-  MMF_TRY(L.cap == W_CAP_SMALL ? launch_b16w_t<W_CAP_SMALL>(a, p.f16, grid, s) : launch_b16w_t<W_CAP_BIG>(a, p.f16, grid, s));
+  if (sink) MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, false, true>(a, p.f16, grid, s)) : (launch_b16w_t<W_CAP_BIG, false, true>(a, p.f16, grid, s)));
+  else MMF_TRY(L.cap == W_CAP_SMALL ? launch_b16w_t<W_CAP_SMALL>(a, p.f16, grid, s) : launch_b16w_t<W_CAP_BIG>(a, p.f16, grid, s));
   if (col_splits > 1) {
     hipLaunchKernelGGL(wide_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
-                       p.kk, pn.seed, p.n_rows);
+                       p.kk, pn.seed, p.n_rows, a.sunk, a.sunk ? a.spill_cnt : nullptr);
     MMF_LAUNCH_CHECK();
   }
   return MMF_OK;
@@ -566,7 +687,7 @@ int launch_scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t 
   MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, true>(a, p.f16, grid, s)) : (launch_b16w_t<W_CAP_BIG, true>(a, p.f16, grid, s)));
   if (col_splits > 1) {
     hipLaunchKernelGGL(wide_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
-                       p.kk, pn.seed, p.n_rows);
+                       p.kk, pn.seed, p.n_rows, nullptr, nullptr);
     MMF_LAUNCH_CHECK();
   }
   return MMF_OK;

@@ -3,6 +3,13 @@ for feature dims above 1024, where the register-resident scan stops.  Host-only 
 
 ``simtopk_segmented`` is the segmented form (include/mmf_hg_wide_seg.h): the k-NN of every segment of a ragged
 batch in one call, with the wide scan behind it where it applies.
+
+Flagged rows (``fallback_rows`` of the call's stats).  A row's candidate lists hold ``list_capacity`` entries each; what a crowded
+list of ``ops.simtopk``'s wide scan cannot hold goes to the row's ``OVERFLOW_SLOTS`` overflow slots and is re-ranked exactly with
+the lists.  A row is flagged, and answered by the exact f32 rescan, only when a column of its error-margin
+band found neither a list nor a free overflow slot: near-duplicate clusters of up to about ``OVERFLOW_SLOTS`` rows stay on the
+fast path.  ``MMF_WIDE_SINK=0`` in the environment (read per call) switches the overflow lists off: every row whose band
+exceeds a list is then flagged, as in the segmented form, which has no overflow lists.  The results are the same bits either way.
 """
 from __future__ import annotations
 
@@ -12,6 +19,9 @@ import torch
 
 from . import _lib, ragged
 from .ops import _feat, _hp, _need_gpu, _simtopk_entry
+
+
+OVERFLOW_SLOTS = 192   # overflow slots per row of the wide scan (kSpillCap, csrc/mmf_api.hip)
 
 
 def wide_scan_supported(d: int, k: int, exclude_self: bool = True) -> bool:
