@@ -248,6 +248,26 @@ struct LaneList {
 #ifndef MMF_BAND_DIRECT
 #define MMF_BAND_DIRECT 1
 #endif
+// How SlotList::offer_tile files a visit's hits: 1 = per-lane rounds (every lane folds its passing values into a 16-bit mask and a
+// round takes the lowest set bit of every lane that has one: as many rounds as the busiest lane has hits), 0 = the loop over the
+// accumulator rows that hold a hit in some lane (16 ballots to find them, one iteration per row; scripts/ab_build.sh).
+#ifndef MMF_VISIT_ROUNDS
+#define MMF_VISIT_ROUNDS 1
+#endif
+
+// Value number b (0 .. 15; higher bits ignored) of sixteen values that live in registers: a four-level tree of selects, one level
+// per bit of b — 15 v_cndmask, no scratch and no indexed register access.  The values are passed one by one (by value): handed over
+// as an indexable object they end up on the stack.
+__device__ __forceinline__ float select16(uint32_t b, float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7,
+                                          float a8, float a9, float a10, float a11, float a12, float a13, float a14, float a15) {
+  const bool b0 = (b & 1u) != 0u, b1 = (b & 2u) != 0u, b2 = (b & 4u) != 0u, b3 = (b & 8u) != 0u;
+  const float p0 = b0 ? a1 : a0, p1 = b0 ? a3 : a2, p2 = b0 ? a5 : a4, p3 = b0 ? a7 : a6;
+  const float p4 = b0 ? a9 : a8, p5 = b0 ? a11 : a10, p6 = b0 ? a13 : a12, p7 = b0 ? a15 : a14;
+  const float r0 = b1 ? p1 : p0, r1 = b1 ? p3 : p2, r2 = b1 ? p5 : p4, r3 = b1 ? p7 : p6;
+  const float s0 = b2 ? r1 : r0, s1 = b2 ? r3 : r2;
+  return b3 ? s1 : s0;
+}
+
 struct SpillSink {
   uint32_t* cnt = nullptr;    // [rows]
   uint32_t* ids = nullptr;    // [rows][cap]
@@ -491,13 +511,45 @@ struct SlotList {
   }
 
   // One tile's 16 values of this lane's query.  rowof(r): tile row (0..31) of element r — the MFMA shape's C layout.
-  // A pre-emptive compaction when some list is nearly full, then only the accumulator rows that hold a hit in
-  // ANY lane run the push code (16 branch-free compares find them; thr only rises meanwhile, so the mask is a
-  // superset).  A hit that finds its list full compacts first (wave-wide; the loop is wave-uniform) and is
-  // dropped — under the audited-loss rule — only if that frees nothing.
-  template <class RowOf>
+  // A pre-emptive compaction when some list is nearly full, then the hits are filed in ROUNDS: every lane folds its passing
+  // values into a 16-bit mask (thr only rises meanwhile, so the mask is a superset), and a round takes the lowest set bit of
+  // every lane that has one — the value comes out of the registers by a tree of selects (select16) — so a visit runs as many
+  // rounds as its busiest lane has hits, mostly one.  A lane files its own hits in ascending r, as the row loop below did; only
+  // the moment of a compaction relative to the other lanes' pushes differs, and with it the slot numbers in the stored keys
+  // (inside the margin).  A hit that finds its list full compacts first (wave-wide: the condition is evaluated once per round,
+  // before the round's pushes) and is dropped — under the audited-loss rule — only if that frees nothing.
+  // MMF_VISIT_ROUNDS == 0, or ROUNDS == false (a kernel instantiation that has no registers left for the rounds): the loop over
+  // the accumulator rows that hold a hit in ANY lane (16 ballots find them), one iteration per row.
+  template <bool ROUNDS = true, class RowOf>
   __device__ __forceinline__ void offer_tile(const f32x16& v, uint32_t id0, RowOf rowof, int kk, float margin) {
     if (__any(cnt >= CAP - 1)) { compact(kk, margin); MMF_DRAIN_AFTER_COMPACT; }
+    if constexpr (ROUNDS && MMF_VISIT_ROUNDS != 0) {
+      uint32_t m = 0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) m |= (v[r] >= thr) ? (1u << r) : 0u;
+      while (__any(m != 0u)) {
+        const bool mine = m != 0u;
+        const uint32_t r = (uint32_t)__builtin_ctz(m | 0x10000u);      // (a lane without a hit left: 16, which selects v[0]; `mine` masks it)
+        m &= m - 1u;
+        const float x = select16(r, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], v[12], v[13], v[14], v[15]);
+        bool hit = mine && x >= thr;                                   // thr: a compaction earlier in the visit may have raised it
+        const bool band = MMF_BAND_DIRECT && x < tband + MMF_BAND_SLACK * margin;
+        if (__any(hit && !band && cnt >= CAP)) {
+          compact(kk, margin);
+          MMF_DRAIN_AFTER_COMPACT;
+          hit = mine && x >= thr;
+        }
+        if (hit) {
+          if (__builtin_expect(!band && cnt < CAP, 1)) {
+            push(x, id0 + rowof((int)r));
+          } else if (!sink.put(id0 + rowof((int)r), tband != kNegInf)) {     // a band entry of a crowded list, or a hit that found the list full
+            lost = fmaxf(lost, x);
+            thr = fmaxf(thr, lost);
+          }
+        }
+      }
+      return;
+    }
     uint32_t rmask = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) rmask |= (__any(v[r] >= thr) ? 1u : 0u) << r;

@@ -285,6 +285,13 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 #ifndef MMF_SYM_EARLY_THR
 #define MMF_SYM_EARLY_THR 1   // SYM == 2: 1 = ONE 64-lane threshold DMA per iteration for both tiles of the next group, issued between
 #endif                        // the iteration's two chains; 0 = one 32-lane DMA behind each chain (the placement before; scripts/ab_build.sh)
+// The SYM kernels have no instrumented (DBG) build; their query-side list code is measured with two build switches (scripts/ab_build.sh):
+#ifndef MMF_SYM_ABLATE_Q
+#define MMF_SYM_ABLATE_Q 0    // timing only, the results are WRONG: bit 0 / bit 1 = the SYM == 1 / SYM == 2 kernel never enters the query-side list code
+#endif
+#ifndef MMF_SYM_COUNT
+#define MMF_SYM_COUNT 0       // 1 = both SYM launches count wave-tiles, visits, hits and compactions (MMF_SCAN_DEBUG bit 8's counters)
+#endif                        //     and launch_scan_b16_sym prints them per launch (it synchronises the stream: not for timing)
 template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0>
 __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(ScanB16Args a) {
   static_assert(!SPLITK || (TPB == 1 && NW == 8 && (KS % 8) == 0), "split-k pairs");
@@ -614,8 +621,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   // The filter of tile t-1 runs AFTER barrier t, ahead of this wave's own MFMA chain: a wave that
   // falls into the (rare) list code then delays only itself while its SIMD partner issues MFMAs;
   // placed before the barrier it would hold all eight waves, and their matrix pipes, at the barrier.
+  constexpr bool SYMCNT = SYM != 0 && MMF_SYM_COUNT != 0;
   auto filter = [&](const Acc& acc, int tt, float m0, float m1) {
-    if (__builtin_expect(!(DBG && (a.debug & 1)) && __any((m0 >= thr_q0) || (m1 >= thr_q1)), 0)) {
+    if (__builtin_expect(!(DBG && (a.debug & 1)) && !(SYM != 0 && (MMF_SYM_ABLATE_Q & SYM) != 0) && __any((m0 >= thr_q0) || (m1 >= thr_q1)), 0)) {
       uint32_t id0 = id_base + (uint32_t)tt * B_CT;
       if constexpr (SYM != 0) id0 += (tt >= sym_n1) ? (uint32_t)(sym_skip * B_CT) : 0u;   // behind the first range: sym_skip tiles further on
       // this lane's query gets its 16 candidates together: its own 8 plus the 8 the partner lane holds
@@ -635,7 +643,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       auto rowof = [g4](int r) -> uint32_t { return (uint32_t)((g4 ^ ((r & 8) >> 1)) + (r & 3) + 16 * ((r >> 2) & 1)); };
       // robust (never dropping) path while thresholds are still forming: first 32 tiles of the range
       const bool cold = (!seeded && tt < 32) || __any(list.thr == -kFltMax);
-      if (DBG && (a.debug & 8)) {
+      if ((DBG && (a.debug & 8)) || SYMCNT) {
         const bool willc = __any(list.cnt >= CAP - 1);
         int nh = 0;
 #pragma unroll
@@ -653,7 +661,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       }
       unsigned long long ts0 = 0;
       if (DBG && (a.debug & 16)) ts0 = __builtin_amdgcn_s_memtime();
-      list.offer_tile(v, id0, rowof, a.kk, margin);
+      // (the instrumented build of the split-k kernel keeps the row loop: with the rounds it spills a VGPR — profiles/r08_scan_variants.txt)
+      list.template offer_tile<!(DBG && SPLITK)>(v, id0, rowof, a.kk, margin);
       if (DBG && (a.debug & 16) && lane == 0) {
         const unsigned long long dt = __builtin_amdgcn_s_memtime() - ts0;
         atomicAdd(a.dbg + (cold ? 4 : 5), dt);
@@ -661,7 +670,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       }
       refresh_thr();
     }
-    if (DBG && (a.debug & 8) && lane == 0) atomicAdd(a.dbg + 5, 1ull);   // tiles
+    if (((DBG && (a.debug & 8)) || SYMCNT) && lane == 0) atomicAdd(a.dbg + 5, 1ull);   // tiles
     if (__builtin_expect(a.share && (tt & 63) == 63, 0)) { sync_seed(); refresh_thr(); }
   };
 
@@ -705,15 +714,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
         if (m != 0u) {
           const uint32_t b = (uint32_t)__builtin_ctz(m);
           m &= m - 1u;
-          // value number b out of the registers: a tree of selects, one level per bit of b
-          const bool b0 = (b & 1u) != 0u, b1 = (b & 2u) != 0u, b2 = (b & 4u) != 0u, b3 = (b & 8u) != 0u;
-          const float p0 = b0 ? x.t[0][1][0] : x.t[0][0][0], p1 = b0 ? x.t[0][1][1] : x.t[0][0][1];
-          const float p2 = b0 ? x.t[0][1][2] : x.t[0][0][2], p3 = b0 ? x.t[0][1][3] : x.t[0][0][3];
-          const float p4 = b0 ? x.t[1][1][0] : x.t[1][0][0], p5 = b0 ? x.t[1][1][1] : x.t[1][0][1];
-          const float p6 = b0 ? x.t[1][1][2] : x.t[1][0][2], p7 = b0 ? x.t[1][1][3] : x.t[1][0][3];
-          const float r0 = b1 ? p1 : p0, r1 = b1 ? p3 : p2, r2 = b1 ? p5 : p4, r3 = b1 ? p7 : p6;
-          const float s0 = b2 ? r1 : r0, s1 = b2 ? r3 : r2;
-          const float v = b3 ? s1 : s0;
+          // value number b = 8 cb + 2 j + qb out of the registers: a tree of selects, one level per bit of b (select16, mmf_dev.h)
+          const float v = select16(b, x.t[0][0][0], x.t[0][1][0], x.t[0][0][1], x.t[0][1][1], x.t[0][0][2], x.t[0][1][2], x.t[0][0][3], x.t[0][1][3],
+                                   x.t[1][0][0], x.t[1][1][0], x.t[1][0][1], x.t[1][1][1], x.t[1][0][2], x.t[1][1][2], x.t[1][0][3], x.t[1][1][3]);
           const uint32_t cj = cj0 + 16u * (b >> 3) + ((b >> 1) & 3u);
           const uint32_t at = sym_wcnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(busy >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)busy, 0u));
           if (at < (uint32_t)a.sym_log_cap) {
@@ -1225,11 +1228,32 @@ int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandL
   a.spill_stacks = 0;
   a.sched = sb.sched;
   a.sym_thr = sb.thr; a.sym_live = y.live ? 1 : 0; a.sym_log = sb.log; a.sym_log_cnt = sb.log_cnt; a.sym_log_cap = kSymLogPerWave;
+#if MMF_SYM_COUNT
+  static unsigned long long* dbuf = nullptr;
+  if (!dbuf) MMF_HIP(hipMalloc(&dbuf, 128));
+  a.dbg = dbuf;
+  auto report = [&](int launch) -> int {
+    unsigned long long h[8];
+    MMF_HIP(hipMemcpyAsync(h, dbuf, 64, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    fprintf(stderr, "[mmf sym count] launch %d: wave-tiles=%llu visits=%llu (cold %llu) hits=%llu entry-compactions=%llu lanes-with-hit=%llu\n",
+            launch, h[5], h[0], h[1], h[2], h[3], h[4]);
+    return MMF_OK;
+  };
+  MMF_HIP(hipMemsetAsync(dbuf, 0, 128, s));
+#endif
   MMF_TRY((launch_b16_t<32, 8, 2, B_CAP, false, false, 1>(a, p.f16, grid, s)));
+#if MMF_SYM_COUNT
+  MMF_TRY(report(0));
+  MMF_HIP(hipMemsetAsync(dbuf, 0, 128, s));
+#endif
   hipLaunchKernelGGL(sym_thr_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, pn.seed, sb.thr, n, n_pad, sb.none_cnt);
   MMF_LAUNCH_CHECK();
   a.sched = sb.sched + (size_t)grid * SEG_ENTRY; a.list_base = 2; a.share = 1;
   MMF_TRY((launch_b16_t<32, 8, 2, B_CAP, false, false, 2>(a, p.f16, grid, s)));
+#if MMF_SYM_COUNT
+  MMF_TRY(report(1));
+#endif
   hipLaunchKernelGGL(sym_scatter_kernel, dim3((unsigned)(grid * 8)), dim3(256), 0, s, sb.log, sb.log_cnt, kSymLogPerWave, L.sym_cnt,
                      L.sym_ent, L.sym_cap, pn.seed + pn.seed_stride, y.prune ? pn.seed : nullptr, L.slot_ulp);
   MMF_LAUNCH_CHECK();
