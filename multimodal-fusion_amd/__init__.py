@@ -16,6 +16,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.combined_topk16_segmented.*               that 16-bit top-k for every graph of a ragged batch from one launch of the scan, bit for bit
     mmf.combined_topk_xy.*                        the top-k of K_h * K_g for two node sets (queries x candidates, id offsets), or rows [lo, hi) of one graph against all of it
     mmf.segmented_exact.*                         the exact f32 top-k of every segment of a batch from one table-driven scan launch (any k), and the router
+    mmf.kmeans_ragged.*                           scikit-learn's KMeans fit for every block of a flat buffer in one call, each block with a width of its own
     mmf.wide_scan.*                               what the wide 16-bit scan (feature dims 1025..4096) covers: host-only queries
     mmf.cohort.build_cohort_hypergraphs(...)      the four steps of process_single_file for every slide of a cohort, in memory
     mmf.build_hypergraph.*                        the reference's function names and signatures
@@ -49,6 +50,9 @@ from .combined_topk_xy import simtopk_combined_rows, simtopk_combined_xy  # noqa
 from . import segmented_exact  # noqa: F401,E402
 from .segmented_exact import segmented_exact_table, simtopk_combined_exact, simtopk_segmented_exact  # noqa: F401,E402
 
+from . import kmeans_ragged  # noqa: F401,E402
+from .kmeans_ragged import kmeans_fit_predict_ragged, kmeans_fit_ragged, ragged_groups  # noqa: F401,E402
+
 from . import wide_scan  # noqa: F401,E402
 from .wide_scan import list_capacity, wide_scan_supported  # noqa: F401,E402
 
@@ -61,4 +65,5 @@ __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combin
            "list_capacity", "combined_topk16", "simtopk_combined_fast", "build_topk_weighted_hypergraph_fast",
            "combined_topk16_segmented", "simtopk_combined_fast_segmented", "build_topk_weighted_hypergraph_fast_segmented",
            "build_topk_hypergraph_data_fast", "combined_topk_xy", "simtopk_combined_xy", "simtopk_combined_rows",
-           "segmented_exact", "simtopk_segmented_exact", "simtopk_combined_exact", "segmented_exact_table"]
+           "segmented_exact", "simtopk_segmented_exact", "simtopk_combined_exact", "segmented_exact_table",
+           "kmeans_ragged", "kmeans_fit_ragged", "kmeans_fit_predict_ragged", "ragged_groups"]

@@ -100,6 +100,11 @@ EXPORTS_TOPK_XY = ["mmf_simtopk_combined_xy"]
 # mmf_segmented_exact_table is host-only.  Pinned by tests/test_segmented_exact_cpu.py.
 EXPORTS_SEG_EXACT = ["mmf_simtopk_segmented_exact", "mmf_simtopk_combined_segmented_exact", "mmf_segmented_exact_table"]
 
+# The ragged-width segmented KMeans (include/ext/mmf_hg_kmeans_ragged.h): an addition to ABI version 3 in a header
+# of its own.  mmf_kmeans_fit_ragged synchronises once per Lloyd iteration, like mmf_kmeans_fit_segmented (INTEGRATION.md's table
+# "Ragged KMeans entries"); mmf_kmeans_ragged_groups is host-only.  Pinned by tests/test_kmeans_ragged_cpu.py.
+EXPORTS_KMEANS_RAGGED = ["mmf_kmeans_fit_ragged", "mmf_kmeans_ragged_groups"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -174,6 +179,10 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_segmented_exact.restype = L.mmf_simtopk_combined_segmented_exact.restype = ci
     L.mmf_segmented_exact_table.argtypes = [vp, vp, i64, ci, ci, ci, vp, i64, ctypes.POINTER(ci)]
     L.mmf_segmented_exact_table.restype = i64
+    L.mmf_kmeans_fit_ragged.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, ci, vp, vp, ci, ctypes.c_double, vp, vp, vp, vp, ci, vp]
+    L.mmf_kmeans_fit_ragged.restype = ci
+    L.mmf_kmeans_ragged_groups.argtypes = [vp, vp, i64, i64, i64, ci, vp, vp]
+    L.mmf_kmeans_ragged_groups.restype = i64
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

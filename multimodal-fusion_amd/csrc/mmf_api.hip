@@ -2051,6 +2051,76 @@ int mmf_kmeans_fit_segmented(const float* X, int64_t n, int64_t d, const int64_t
   return kmeans_fit_run(X, d, ptr, n_seg, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres, seeds, info, true, c);
 }
 
+// ---- ragged-width segmented KMeans (include/ext/mmf_hg_kmeans_ragged.h) --------------------------------
+// the checks both entries share: the shapes of the table and the limits one segment alone can break
+static int kmeans_ragged_check(const char* who, const int64_t* rows, const int64_t* width, int64_t n_seg, int64_t n_clusters, int64_t n_init,
+                               int trials) {
+  if (n_seg < 1 || n_clusters < 1 || n_init < 1 || trials < 1) {
+    set_error("%s: need n_seg >= 1, n_clusters >= 1, n_init >= 1, trials >= 1 (n_seg = %lld, n_clusters = %lld, n_init = %lld, trials = %d)", who,
+              (long long)n_seg, (long long)n_clusters, (long long)n_init, trials);
+    return MMF_E_INVALID;
+  }
+  if (!rows || !width) { set_error("%s: NULL pointer", who); return MMF_E_INVALID; }
+  for (int64_t s = 0; s < n_seg; ++s) {
+    if (rows[s] < n_clusters) {      // scikit-learn's sentence
+      set_error("%s: segment %lld: n_samples=%lld should be >= n_clusters=%lld.", who, (long long)s, (long long)rows[s], (long long)n_clusters);
+      return MMF_E_INVALID;
+    }
+    if (width[s] < 1) { set_error("%s: segment %lld: width %lld must be >= 1", who, (long long)s, (long long)width[s]); return MMF_E_INVALID; }
+  }
+  if (n_init * n_clusters > segment_max_segments()) {
+    set_error("%s: n_init * n_clusters = %lld above the supported %d", who, (long long)(n_init * n_clusters), segment_max_segments());
+    return MMF_E_UNSUPPORTED;
+  }
+  if (trials > 64) { set_error("%s: trials = %d above the supported 64", who, trials); return MMF_E_UNSUPPORTED; }
+  for (int64_t s = 0; s < n_seg; ++s)
+    if (n_init * rows[s] >= ((int64_t)1 << 31)) {
+      set_error("%s: segment %lld: n_init * n_samples must be < 2^31", who, (long long)s);
+      return MMF_E_UNSUPPORTED;
+    }
+  return MMF_OK;
+}
+
+int mmf_kmeans_fit_ragged(const float* V, int64_t n_values, const int64_t* xoff, const int64_t* rows, const int64_t* width, int64_t n_seg,
+                          int64_t n_clusters, int64_t n_init, int trials, const int64_t* first_centres, const double* uniforms, int max_iter,
+                          double tol, int64_t* labels, float* centres, int64_t* seeds, double* info, int device_id, void* hip_stream) {
+  Call c("kmeans_fit_ragged", device_id, hip_stream);
+  MMF_TRY(c.on_device());
+  if (max_iter < 1 || !(tol >= 0.0)) { set_error("kmeans_fit_ragged: need max_iter >= 1, tol >= 0 (max_iter = %d)", max_iter); return MMF_E_INVALID; }
+  if (!V || !xoff || !first_centres || (n_clusters > 1 && !uniforms) || !labels) { set_error("kmeans_fit_ragged: NULL pointer"); return MMF_E_INVALID; }
+  MMF_TRY(kmeans_ragged_check(c.who, rows, width, n_seg, n_clusters, n_init, trials));
+  for (int64_t s = 0; s < n_seg; ++s) {
+    // (rows < 2^31 / n_init was checked; the product is taken in 128 bits against a width near 2^63)
+    if (xoff[s] < 0 || (__int128)xoff[s] + (__int128)rows[s] * width[s] > (__int128)n_values) {
+      set_error("kmeans_fit_ragged: segment %lld: block [%lld, %lld + %lld x %lld) outside the %lld values of V", (long long)s, (long long)xoff[s],
+                (long long)xoff[s], (long long)rows[s], (long long)width[s], (long long)n_values);
+      return MMF_E_INVALID;
+    }
+    for (int64_t i = 0; i < n_init; ++i) {
+      const int64_t f = first_centres[s * n_init + i];
+      if (f < 0 || f >= rows[s]) {
+        set_error("kmeans_fit_ragged: segment %lld: first_centres[%lld] outside [0, n_samples)", (long long)s, (long long)i);
+        return MMF_E_INVALID;
+      }
+    }
+  }
+  size_t need = 0;
+  const std::vector<int64_t> groups = kmeans_ragged_groups(rows, width, n_seg, n_clusters, n_init, trials, &need, nullptr);
+  MMF_TRY(c.begin(ws_bytes(need, 1)));
+  return launch_kmeans_fit_ragged(V, xoff, rows, width, groups, n_clusters, n_init, trials, first_centres, uniforms, max_iter, tol, labels, centres,
+                                  seeds, info, c.ws.take<char>(need), c.s);
+}
+
+int64_t mmf_kmeans_ragged_groups(const int64_t* rows, const int64_t* width, int64_t n_seg, int64_t n_clusters, int64_t n_init, int trials,
+                                 int64_t* bounds, int64_t* ds) {
+  const int rc = kmeans_ragged_check("kmeans_ragged_groups", rows, width, n_seg, n_clusters, n_init, trials);
+  if (rc != MMF_OK) return rc;
+  if (!bounds) { set_error("kmeans_ragged_groups: NULL pointer"); return MMF_E_INVALID; }
+  const std::vector<int64_t> b = kmeans_ragged_groups(rows, width, n_seg, n_clusters, n_init, trials, nullptr, ds);
+  for (size_t i = 0; i < b.size(); ++i) bounds[i] = b[i];
+  return (int64_t)b.size() - 1;
+}
+
 int mmf_lower_median(const float* v, int64_t count, float* out_median, int device_id, void* hip_stream) {
   Call c("lower_median", device_id, hip_stream);
   MMF_TRY(c.on_device());

@@ -16,6 +16,7 @@
 #include "../../include/ext/mmf_hg_topk16_seg.h"
 #include "../../include/ext/mmf_hg_topk_xy.h"
 #include "../../include/ext/mmf_hg_seg_exact.h"
+#include "../../include/ext/mmf_hg_kmeans_ragged.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -563,6 +564,14 @@ std::vector<int64_t> kmeans_segment_groups(const int64_t* ptr, int64_t n_seg, in
 int launch_kmeans_fit(const float* X, int64_t d, const int64_t* ptr, const std::vector<int64_t>& groups, int64_t k, int64_t n_init, int trials,
                       const int64_t* first_h, const double* u_h, int max_iter, double tol, int64_t* out_labels, float* out_centres,
                       int64_t* out_seeds, double* info_h, void* scratch, hipStream_t s, bool segmented);
+// The ragged fit (mmf_kmeans_fit_ragged): segment q is rows[q] x width[q] at element xoff[q] of the flat buffer V.  Groups as above,
+// plus the padding rule: sum rows * km_ds(widest) <= 2 sum rows * km_ds(width) per group; ds_out (optional, [n_seg]) receives the
+// internal width of each segment's group.  Labels in call order, centres [k][width] per segment back to back, seeds local rows.
+std::vector<int64_t> kmeans_ragged_groups(const int64_t* rows, const int64_t* width, int64_t n_seg, int64_t k, int64_t n_init, int trials,
+                                          size_t* max_bytes, int64_t* ds_out);
+int launch_kmeans_fit_ragged(const float* V, const int64_t* xoff, const int64_t* rows, const int64_t* width, const std::vector<int64_t>& groups,
+                             int64_t k, int64_t n_init, int trials, const int64_t* first_h, const double* u_h, int max_iter, double tol,
+                             int64_t* out_labels, float* out_centres, int64_t* out_seeds, double* info_h, void* scratch, hipStream_t s);
 int launch_knn_pairs(const int64_t* nbr, int64_t n, int k, const int64_t* labels, int64_t* lo, int64_t* hi, int64_t* out_count,
                      hipStream_t s);
 

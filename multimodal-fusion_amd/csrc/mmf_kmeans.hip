@@ -77,6 +77,30 @@ struct KmSegCtx {
 template <class... Seg>
 __device__ __forceinline__ KmSegCtx km_ctx(Seg... sx) { return KmSegCtx{sx...}; }
 
+// ---- ragged-width segmented fit (mmf_kmeans_fit_ragged) -----------------------------------------------------------------
+// The segments of a group have feature widths of their own.  Everything behind the centring runs on Xc, whose rows have the
+// group's common width ds_g = km_ds(widest segment) with zeros from the segment's own width on: a trailing zero column adds an
+// exact +0.0 to the sums that run over the columns of Xc (see each kernel), so those kernels are the segmented fit's.  The kernels
+// that read the raw block or are sized by d take the segment's own width and base from the KmRag table, and the state step the
+// segment's own strip count.  Per-segment arrays over the columns (mean32 / mean64 / var64, the rows of colpart) have the common
+// stride `ld`.  The third trailing context type: the plain and the segmented instantiations compile without any of it.
+struct KmRag {
+  int64_t xoff;                 // first element of the segment's [n][d] block in the flat buffer
+  int64_t d;                    // its feature width
+  int64_t strips;               // ceil(km_ds(d) / 64): the shift partials the plain fit sums for a centre
+  int64_t coff;                 // first element of its [k][d] centres in the output
+};
+struct KmRagCtx {
+  KmSegCtx seg;
+  const KmRag* rag;
+  int64_t ld;
+};
+__device__ __forceinline__ KmSegCtx km_ctx(KmRagCtx r) { return r.seg; }
+template <class... Seg> struct KmIsRag : std::false_type {};
+template <> struct KmIsRag<KmRagCtx> : std::true_type {};
+template <class... Seg>
+__device__ __forceinline__ KmRagCtx km_rag(Seg... sx) { return KmRagCtx{sx...}; }
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -94,14 +118,23 @@ __global__ __launch_bounds__(256) void km_colsum_kernel(const float* __restrict_
   const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
   const int64_t col = (int64_t)blockIdx.y * 64 + c;
   int64_t r0 = (int64_t)blockIdx.x * 256;
+  int64_t ld = d;                          // row stride of partial and mean (ragged: the group's; d becomes the segment's width)
   if constexpr (sizeof...(Seg) > 0) {
     const KmSegCtx cx = km_ctx(sx...);
     const KmWork wk = cx.work[blockIdx.x];
     const KmSeg sg = cx.segs[wk.seg];
-    X += sg.row0 * d;
+    if constexpr (KmIsRag<Seg...>::value) {
+      const KmRagCtx rc = km_rag(sx...);
+      const KmRag rg = rc.rag[wk.seg];
+      X += rg.xoff;
+      d = rg.d;
+      ld = rc.ld;
+    } else {
+      X += sg.row0 * d;
+    }
     n = sg.n;
     r0 = (int64_t)wk.tile * 256;
-    if (mean) mean += (int64_t)wk.seg * d;
+    if (mean) mean += (int64_t)wk.seg * ld;
   }
   double acc = 0.0;
   if (col < d) {
@@ -116,7 +149,7 @@ __global__ __launch_bounds__(256) void km_colsum_kernel(const float* __restrict_
   }
   sh[q][c] = acc;
   __syncthreads();
-  if (q == 0 && col < d) partial[(int64_t)blockIdx.x * d + col] = ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
+  if (q == 0 && col < d) partial[(int64_t)blockIdx.x * ld + col] = ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
 }
 
 // one thread per column: mean (f64 and the float32 scikit-learn subtracts), or the variance; thread 0 of the last launch
@@ -126,12 +159,18 @@ template <class... Seg>
 __global__ void km_colfin_kernel(const double* __restrict__ partial, int64_t nblk, int64_t n, int64_t d, double* __restrict__ out64,
                                  float* __restrict__ out32, Seg... sx) {
   const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t ld = d;                          // row stride of partial and out64 (ragged: the group's)
   if constexpr (sizeof...(Seg) > 0) {
     const KmSeg sg = km_ctx(sx...).segs[blockIdx.y];
-    partial += sg.blk0 * d;
+    if constexpr (KmIsRag<Seg...>::value) {
+      const KmRagCtx rc = km_rag(sx...);
+      d = rc.rag[blockIdx.y].d;
+      ld = rc.ld;
+    }
+    partial += sg.blk0 * ld;
     nblk = (sg.n + 255) / 256;
     n = sg.n;
-    out64 += (int64_t)blockIdx.y * d;
+    out64 += (int64_t)blockIdx.y * ld;
   }
   if (col >= d) return;
   double s = 0.0;
@@ -139,11 +178,11 @@ __global__ void km_colfin_kernel(const double* __restrict__ partial, int64_t nbl
   for (; b + 8 <= nblk; b += 8) {                     // eight partials in flight, added in order
     double v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = partial[(b + u) * d + col];
+    for (int u = 0; u < 8; ++u) v[u] = partial[(b + u) * ld + col];
 #pragma unroll
     for (int u = 0; u < 8; ++u) s += v[u];
   }
-  for (; b < nblk; ++b) s += partial[b * d + col];
+  for (; b < nblk; ++b) s += partial[b * ld + col];
   s /= (double)n;
   out64[col] = s;
   if (out32) out32[col] = (float)s;
@@ -162,9 +201,17 @@ __global__ __launch_bounds__(256) void km_colmean_seq_kernel(const float* __rest
   __shared__ float tile[CM_ROWS][CM_COLS];
   if constexpr (sizeof...(Seg) > 0) {
     const KmSeg sg = km_ctx(sx...).segs[blockIdx.y];
-    X += sg.row0 * d;
+    if constexpr (KmIsRag<Seg...>::value) {
+      const KmRagCtx rc = km_rag(sx...);
+      const KmRag rg = rc.rag[blockIdx.y];
+      X += rg.xoff;
+      mean32 += (int64_t)blockIdx.y * rc.ld;
+      d = rg.d;
+    } else {
+      X += sg.row0 * d;
+      mean32 += (int64_t)blockIdx.y * d;
+    }
     n = sg.n;
-    mean32 += (int64_t)blockIdx.y * d;
   }
   const int c = threadIdx.x & (CM_COLS - 1), q = threadIdx.x / CM_COLS;      // q in [0, 32)
   const int64_t col = (int64_t)blockIdx.x * CM_COLS + c;
@@ -209,7 +256,13 @@ template <class... Seg>
 __global__ __launch_bounds__(1024) void km_tol_kernel(const double* __restrict__ var, int64_t d, double tol, double* __restrict__ tol_abs, Seg... sx) {
   __shared__ double sh[1024];
   if constexpr (sizeof...(Seg) > 0) {
-    var += (int64_t)blockIdx.x * d;
+    if constexpr (KmIsRag<Seg...>::value) {      // the divisor and the column count are the segment's own
+      const KmRagCtx rc = km_rag(sx...);
+      var += (int64_t)blockIdx.x * rc.ld;
+      d = rc.rag[blockIdx.x].d;
+    } else {
+      var += (int64_t)blockIdx.x * d;
+    }
     tol_abs += blockIdx.x;
   }
   double s = 0.0;
@@ -232,6 +285,7 @@ __global__ __launch_bounds__(256) void km_centre_kernel(const float* __restrict_
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n) return;
+  int64_t xrow = row;                      // the row inside X (ragged: inside the segment's block)
   if constexpr (sizeof...(Seg) > 0) {      // the row's segment: the last one that starts at or before it
     const KmSegCtx cx = km_ctx(sx...);
     int64_t lo = 0, hi = cx.n_seg - 1;
@@ -239,12 +293,21 @@ __global__ __launch_bounds__(256) void km_centre_kernel(const float* __restrict_
       const int64_t mid = (lo + hi + 1) >> 1;
       if (cx.segs[mid].row0 <= row) lo = mid; else hi = mid - 1;
     }
-    mean32 += lo * d;
+    if constexpr (KmIsRag<Seg...>::value) {
+      const KmRagCtx rc = km_rag(sx...);
+      const KmRag rg = rc.rag[lo];
+      X += rg.xoff;
+      xrow = row - cx.segs[lo].row0;
+      mean32 += lo * rc.ld;
+      d = rg.d;
+    } else {
+      mean32 += lo * d;
+    }
   }
   double acc = 0.0;
   for (int64_t j = lane; j < ds; j += 64) {
     float v = 0.f;
-    if (j < d) v = X[row * d + j] - mean32[j];
+    if (j < d) v = X[xrow * d + j] - mean32[j];
     Xc[row * ds + j] = v;
     acc += (double)v * (double)v;
   }
@@ -809,7 +872,14 @@ __global__ __launch_bounds__(64) void km_state_kernel(KmState* __restrict__ st, 
         s.state = KM_RELOC;
       } else {
         double sh = 0.0;
-        for (int64_t q = lane; q < k * strips; q += 64) sh += shift_part[(int64_t)g * k * strips + q];
+        if constexpr (KmIsRag<Seg...>::value) {
+          // which lane a (centre, strip) partial lands on depends on the strip count: the segment's own, as in its plain fit
+          // (the strips behind it hold zeros)
+          const int64_t own = km_rag(sx...).rag[g / n_init].strips;
+          for (int64_t q = lane; q < k * own; q += 64) sh += shift_part[((int64_t)g * k + q / own) * strips + q % own];
+        } else {
+          for (int64_t q = lane; q < k * strips; q += 64) sh += shift_part[(int64_t)g * k * strips + q];
+        }
         sh = wave_sum(sh);
         s.shift = sh;
         s.cur ^= 1;
@@ -1043,9 +1113,17 @@ __global__ __launch_bounds__(256) void km_finish_kernel(const KmState* __restric
     labels += cx.n_init * sg.row0;
     C0 += sid * cx.n_init * k * ds;
     C1 += sid * cx.n_init * k * ds;
-    mean32 += sid * d;
+    if constexpr (KmIsRag<Seg...>::value) {
+      const KmRagCtx rc = km_rag(sx...);
+      const KmRag rg = rc.rag[sid];
+      mean32 += sid * rc.ld;
+      if (out_centres) out_centres += rg.coff;
+      d = rg.d;
+    } else {
+      mean32 += sid * d;
+      if (out_centres) out_centres += sid * k * d;
+    }
     out_labels += sg.row0;
-    if (out_centres) out_centres += sid * k * d;
     koff = sid * cx.n_init * k;
   }
   const int best = *best_p;
@@ -1074,6 +1152,12 @@ __global__ void km_seeds_out_kernel(const int64_t* __restrict__ seeds, int64_t c
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) out[i] = seeds[i] + base;
 }
+// ragged fit: out[i] = seeds[i] - first row of i's segment: group-local seed rows -> rows of the segment's own block
+__global__ void km_seeds_local_kernel(const int64_t* __restrict__ seeds, int64_t count, int64_t per_seg, const KmSeg* __restrict__ segs,
+                                      int64_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) out[i] = seeds[i] - segs[i / per_seg].row0;
+}
 
 static inline size_t al(size_t b) { return (b + 255) & ~size_t(255); }
 static int64_t km_ds(int64_t d) { return (d + KM_KC - 1) / KM_KC * KM_KC; }
@@ -1098,6 +1182,7 @@ struct KmGroup : KmCounts {      // host plan of one group
   int64_t s0 = 0, row0 = 0;
   std::vector<KmSeg> segs;
   std::vector<KmWork> work;      // column-sum blocks, then 64-point tiles, then 32- and 64-point seeding tiles
+  std::vector<KmRag> rag;        // ragged fit only: one per segment
 };
 
 KmGroup km_plan(const int64_t* ptr, int64_t s0, int64_t s1) {
@@ -1122,11 +1207,13 @@ struct KmSegBufs {
   float* rows[2]; double* rpart[2]; int64_t* cand[2]; int64_t* first; float* pot32; int* sel; double* U; int64_t* seeds;
   float* C0; float* C1; float* sums32; double* cc; int64_t* labels; int64_t* order; int64_t* counts; int64_t* offsets; void* sort_scratch;
   uint32_t* bad; double* shift_part; KmState* st; int* status; double* dist; float* cntf; double* ipart; int* map; KmSeg* segs; KmWork* work;
+  KmRag* rag;                    // ragged fit only
   size_t bytes;
 };
 
-// The group's scratch, carved from `base` (NULL: only the size).
-KmSegBufs km_seg_carve(char* base, const KmCounts& g, int64_t d, int64_t k, int64_t n_init, int trials) {
+// The group's scratch, carved from `base` (NULL: only the size).  ragged: d is the widest segment's width (the common stride of the
+// per-segment column arrays, ds the group's width of Xc), and the KmRag table follows everything else.
+KmSegBufs km_seg_carve(char* base, const KmCounts& g, int64_t d, int64_t k, int64_t n_init, int trials, bool ragged = false) {
   const int64_t ds = km_ds(d), Rs = n_init * trials, G = g.nseg * n_init, S = G * k, nr = g.nrows, strips = (ds + 63) / 64;
   size_t off = 0;
   auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off += al(bytes); return q; };
@@ -1167,18 +1254,23 @@ KmSegBufs km_seg_carve(char* base, const KmCounts& g, int64_t d, int64_t k, int6
   b.map = (int*)take((size_t)g.nseg * k * 4);
   b.segs = (KmSeg*)take((size_t)g.nseg * sizeof(KmSeg));
   b.work = (KmWork*)take((size_t)g.nwork() * sizeof(KmWork));
+  b.rag = ragged ? (KmRag*)take((size_t)g.nseg * sizeof(KmRag)) : nullptr;
   b.bytes = off + 4096;
   return b;
 }
 
 KmSegCtx km_with(KmSegCtx c, const KmWork* work, int64_t tprev) { c.work = work; c.tprev = tprev; return c; }
+KmRagCtx km_with(KmRagCtx c, const KmWork* work, int64_t tprev) { c.seg = km_with(c.seg, work, tprev); return c; }
 
 // One group, carved in `b`.  Ctx: empty (the plain fit: one segment, the plain instantiations) or the group's KmSegCtx, whose
-// work table and tprev every launch sets with km_with.
+// work table and tprev every launch sets with km_with; or the group's KmRagCtx (the ragged fit): X is then the flat buffer, d the
+// widest segment's width, out_centres the whole output and out_seeds rows of each segment's own block.
 template <class... Ctx>
 int km_fit_group(const float* X, int64_t d, const KmGroup& gp, const KmSegBufs& b, int64_t k, int64_t n_init, int trials,
                  const int64_t* first_h, const double* u_h, int max_iter, double tol, int64_t* out_labels, float* out_centres,
                  int64_t* out_seeds, double* info_h, hipStream_t s, Ctx... proto) {
+  constexpr bool RAG = KmIsRag<Ctx...>::value;
+  const char* who = RAG ? "kmeans_fit_ragged" : sizeof...(Ctx) ? "kmeans_fit_segmented" : "kmeans_fit";
   const int64_t ds = km_ds(d), strips = (ds + 63) / 64;
   const int64_t nseg = gp.nseg, nr = gp.nrows, G = nseg * n_init, S = G * k, R = n_init * trials;
   const size_t lds = (size_t)4 * KM_T * KM_LD * 8;
@@ -1190,7 +1282,7 @@ int km_fit_group(const float* X, int64_t d, const KmGroup& gp, const KmSegBufs& 
   KmWork* w_st32 = w_tile + gp.ntile;
   KmWork* w_st64 = w_st32 + gp.nst32;
   // (the host vectors copied below live until the first status read of the Lloyd loop has synchronised the stream)
-  const float* Xg = X + gp.row0 * d;
+  const float* Xg = RAG ? X : X + gp.row0 * d;
   // the caller's random stream: first centres as group-local rows, the shared uniforms; the segmented fit's tables
   std::vector<int64_t> first((size_t)G);
   for (int64_t q = 0; q < nseg; ++q)
@@ -1201,6 +1293,7 @@ int km_fit_group(const float* X, int64_t d, const KmGroup& gp, const KmSegBufs& 
     MMF_HIP(hipMemcpyAsync(b.segs, gp.segs.data(), (size_t)nseg * sizeof(KmSeg), hipMemcpyHostToDevice, s));
     MMF_HIP(hipMemcpyAsync(b.work, gp.work.data(), gp.work.size() * sizeof(KmWork), hipMemcpyHostToDevice, s));
   }
+  if constexpr (RAG) MMF_HIP(hipMemcpyAsync(b.rag, gp.rag.data(), (size_t)nseg * sizeof(KmRag), hipMemcpyHostToDevice, s));
   MMF_HIP(hipMemsetAsync(b.amb, 0, (size_t)nseg * 8, s));
 
   // centring, tolerance, norms: per segment
@@ -1256,7 +1349,10 @@ int km_fit_group(const float* X, int64_t d, const KmGroup& gp, const KmSegBufs& 
   }
   if (out_seeds) {
     int64_t* o = out_seeds + gp.s0 * n_init * k;
-    if (gp.row0 == 0) {      // group-local rows are the batch's
+    if constexpr (RAG) {
+      hipLaunchKernelGGL(km_seeds_local_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, b.seeds, S, n_init * k, b.segs, o);
+      MMF_LAUNCH_CHECK();
+    } else if (gp.row0 == 0) {      // group-local rows are the batch's
       MMF_HIP(hipMemcpyAsync(o, b.seeds, (size_t)S * 8, hipMemcpyDeviceToDevice, s));
     } else {
       hipLaunchKernelGGL(km_seeds_out_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, b.seeds, S, gp.row0, o);
@@ -1305,7 +1401,7 @@ int km_fit_group(const float* X, int64_t d, const KmGroup& gp, const KmSegBufs& 
       MMF_TRY(state((int)g));
     }
     if (it > max_iter + 2) {
-      set_error("%s: the convergence state machine did not terminate (internal invariant)", sizeof...(Ctx) ? "kmeans_fit_segmented" : "kmeans_fit");
+      set_error("%s: the convergence state machine did not terminate (internal invariant)", who);
       return MMF_E_INTERNAL;
     }
   }
@@ -1318,7 +1414,7 @@ int km_fit_group(const float* X, int64_t d, const KmGroup& gp, const KmSegBufs& 
   MMF_LAUNCH_CHECK();
   const int64_t fin = gp.max_n > k * d ? gp.max_n : k * d;
   hipLaunchKernelGGL(km_finish_kernel<Ctx...>, dim3((unsigned)((fin + 255) / 256), (unsigned)nseg), dim3(256), 0, s, b.st, b.best, nr, k, d, ds, b.labels,
-                     b.C0, b.C1, b.mean32, out_labels + gp.row0, out_centres ? out_centres + gp.s0 * k * d : nullptr, km_with(proto, nullptr, 0)...);
+                     b.C0, b.C1, b.mean32, out_labels + gp.row0, out_centres && !RAG ? out_centres + gp.s0 * k * d : out_centres, km_with(proto, nullptr, 0)...);
   MMF_LAUNCH_CHECK();
   if (info_h) {
     // per segment: [0] best restart, [1] its inertia, [2] its iterations, [3] tol_abs, [4] ambiguous draws, [5] ambiguous trial
@@ -1383,6 +1479,60 @@ int launch_kmeans_fit(const float* X, int64_t d, const int64_t* ptr, const std::
     else
       MMF_TRY(km_fit_group(X, d, gp, b, k, n_init, trials, first_h, u_h, max_iter, tol, out_labels, out_centres, out_seeds, info_h, s,
                            KmSegCtx{b.segs, nullptr, gp.nseg, n_init, 0}));
+  }
+  return MMF_OK;
+}
+
+// ---- the ragged fit's planner and driver ---------------------------------------------------------------------------------------
+// Groups of consecutive segments, in call order.  The limits of kmeans_segment_groups, with the scratch sized for the widest
+// segment; and a group closes before a segment that would make its padded volume sum rows * ds_g exceed twice the sum of
+// rows * km_ds(width): one very wide block does not inflate Xc, the centres and the E step of all the others.
+std::vector<int64_t> kmeans_ragged_groups(const int64_t* rows, const int64_t* width, int64_t n_seg, int64_t k, int64_t n_init, int trials,
+                                          size_t* max_bytes, int64_t* ds_out) {
+  std::vector<int64_t> bounds{0};
+  size_t mx = 0;
+  int64_t s0 = 0;
+  while (s0 < n_seg) {
+    KmCounts c;
+    c.add(rows[s0]);
+    int64_t s1 = s0 + 1, dmax = width[s0], own = rows[s0] * km_ds(width[s0]);
+    size_t bytes = km_seg_carve(nullptr, c, dmax, k, n_init, trials, true).bytes;
+    while (s1 < n_seg) {
+      KmCounts c2 = c;
+      c2.add(rows[s1]);
+      const int64_t d2 = width[s1] > dmax ? width[s1] : dmax, own2 = own + rows[s1] * km_ds(width[s1]);
+      if (c2.nseg * n_init * k > segment_max_segments() || c2.nrows * n_init >= ((int64_t)1 << 31)) break;
+      if (c2.nrows * km_ds(d2) > 2 * own2) break;
+      const size_t b2 = km_seg_carve(nullptr, c2, d2, k, n_init, trials, true).bytes;
+      if (b2 > KM_GROUP_BYTES) break;
+      c = c2; bytes = b2; dmax = d2; own = own2; ++s1;
+    }
+    if (ds_out)
+      for (int64_t s = s0; s < s1; ++s) ds_out[s] = km_ds(dmax);
+    mx = bytes > mx ? bytes : mx;
+    bounds.push_back(s1);
+    s0 = s1;
+  }
+  if (max_bytes) *max_bytes = mx;
+  return bounds;
+}
+
+int launch_kmeans_fit_ragged(const float* V, const int64_t* xoff, const int64_t* rows, const int64_t* width, const std::vector<int64_t>& groups,
+                             int64_t k, int64_t n_init, int trials, const int64_t* first_h, const double* u_h, int max_iter, double tol,
+                             int64_t* out_labels, float* out_centres, int64_t* out_seeds, double* info_h, void* scratch, hipStream_t s) {
+  const int64_t n_seg = groups.back();
+  std::vector<int64_t> ptr((size_t)n_seg + 1, 0), coff((size_t)n_seg + 1, 0);      // label rows and centre elements, call order
+  for (int64_t q = 0; q < n_seg; ++q) { ptr[q + 1] = ptr[q] + rows[q]; coff[q + 1] = coff[q] + k * width[q]; }
+  for (size_t gi = 0; gi + 1 < groups.size(); ++gi) {
+    KmGroup gp = km_plan(ptr.data(), groups[gi], groups[gi + 1]);
+    int64_t dmax = 0;
+    for (int64_t q = groups[gi]; q < groups[gi + 1]; ++q) {
+      dmax = width[q] > dmax ? width[q] : dmax;
+      gp.rag.push_back(KmRag{xoff[q], width[q], (km_ds(width[q]) + 63) / 64, coff[q]});
+    }
+    const KmSegBufs b = km_seg_carve(static_cast<char*>(scratch), gp, dmax, k, n_init, trials, true);
+    MMF_TRY(km_fit_group(V, dmax, gp, b, k, n_init, trials, first_h, u_h, max_iter, tol, out_labels, out_centres, out_seeds, info_h, s,
+                         KmRagCtx{KmSegCtx{b.segs, nullptr, gp.nseg, n_init, 0}, b.rag, dmax}));
   }
   return MMF_OK;
 }

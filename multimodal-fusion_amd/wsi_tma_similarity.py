@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, ops, ragged
+from . import _lib, kmeans_ragged, ops, ragged
 from .kmeans import segmented_labels
 from .build_hypergraph import preprocess_hypergraph
 from .build_hypergraph._common import compute_device, result_device_like_preprocess, to_gpu
@@ -107,9 +107,11 @@ def similarity_block(S_flat: torch.Tensor, s_ptr, sizes: Sequence[Tuple[int, int
 # group_by_similarity over a cohort
 # ---------------------------------------------------------------------------------------------------
 def width_plan(n_sizes: Sequence[int], m_sizes: Sequence[int]) -> List[Dict]:
-    """Which slide lands in which KMeans fit.  Slide s clusters the n_s rows of an [n_s, m_s] matrix, and one segmented fit takes
-    one feature dimension, so the slides are grouped by m_s: one fit per distinct width, in order of first appearance, each
-    holding its slides in slide order.  Per fit: 'width', 'slides', 'fit_ptr' (offsets of the slides' rows in the fit's
+    """The slides of a cohort by TMA width.  Slide s clusters the n_s rows of an [n_s, m_s] matrix, and one segmented fit
+    (kmeans_fit_predict_segmented) takes one feature dimension: the slides grouped by m_s, one fit per distinct width, in order of
+    first appearance, each holding its slides in slide order.  group_by_similarity_segmented runs this plan when it has one
+    entry, and with the 'sklearn' backend; a plan of several widths on the 'device' backend is ONE ragged fit instead
+    (kmeans_ragged.kmeans_fit_predict_ragged).  Per fit: 'width', 'slides', 'fit_ptr' (offsets of the slides' rows in the fit's
     concatenated input: the labels fit_ptr[i]:fit_ptr[i+1] return to slide slides[i]) and 'adjacent' (the slides are
     consecutive, so their blocks are one contiguous piece of S_flat and need no copy)."""
     fits: Dict[int, Dict] = {}
@@ -128,11 +130,13 @@ def group_by_similarity_segmented(S_flat: torch.Tensor, num_groups: int, *, wsi_
     numpy [n_wsi], 0 .. num_groups - 1 within each slide; one stats dict per slide: method, num_groups, group_sizes; info:
     kmeans_backend and per slide ambiguous_draws / ambiguous_trials, None with the 'sklearn' backend).
 
-    Slide s clusters the rows of an n_s x m_s matrix, so the feature dimension differs between slides, while the segmented KMeans
-    fit takes one.  The slides are therefore grouped by m_s (width_plan): ONE kmeans_fit_predict_segmented call per distinct
-    width, on the concatenation of those slides' blocks (no copy when they are adjacent), and the labels are scattered back to
-    slide order.  A cohort with S distinct widths degrades to S fits.  Columns are never zero-padded to a common width:
-    scikit-learn's tolerance is tol * mean(var) over the columns, so padding would change the decisions."""
+    Slide s clusters the rows of an n_s x m_s matrix, so the feature dimension differs between slides.  With the 'device' backend
+    and more than one distinct m_s the whole cohort is ONE kmeans_fit_predict_ragged call on S_flat itself (kmeans_ragged.py,
+    DESIGN.md §4.22): every block keeps its own width for the means, the variances, scikit-learn's tolerance tol * mean(var) and
+    the centring, and nothing is copied.  The input is never zero-padded to a common width, which would change that tolerance;
+    only the fit's internal mean-centred copy is, where a zero column adds an exact 0.0.  One distinct width is one
+    kmeans_fit_predict_segmented call, as before.  The 'sklearn' backend runs the reference's own call on the host, one fit per
+    distinct width (width_plan), slide by slide."""
     what = "group_by_similarity_segmented"
     if method != "kmeans":
         raise ValueError(f"Unknown grouping method: {method}")
@@ -154,7 +158,14 @@ def group_by_similarity_segmented(S_flat: torch.Tensor, num_groups: int, *, wsi_
     labels = torch.empty((n_wsi,), dtype=torch.int64, device=dev)
     draws: Optional[List[int]] = [0] * S if backend == "device" else None
     trials: Optional[List[int]] = [0] * S if backend == "device" else None
-    for fit in width_plan(n_sizes, m_sizes):
+    plan = width_plan(n_sizes, m_sizes)
+    if backend == "device" and len(plan) > 1:      # one ragged fit on S_flat itself: every slide's block with its own width
+        labels, _, _, fit_info = kmeans_ragged.kmeans_fit_predict_ragged(F, num_groups, rows=n_sizes, widths=m_sizes, xoff=sp[:-1], n_init=10,
+                                                                         seed=42, return_info=True)
+        draws = [int(i["ambiguous_draws"]) for i in fit_info]
+        trials = [int(i["ambiguous_trials"]) for i in fit_info]
+        plan = []
+    for fit in plan:
         sl, m = fit["slides"], fit["width"]
         if fit["adjacent"]:
             X = F[sp[sl[0]]:sp[sl[-1] + 1]].view(-1, m)
