@@ -16,12 +16,14 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.combined_topk16_segmented.*               that 16-bit top-k for every graph of a ragged batch from one launch of the scan, bit for bit
     mmf.combined_topk_xy.*                        the top-k of K_h * K_g for two node sets (queries x candidates, id offsets), or rows [lo, hi) of one graph against all of it
     mmf.segmented_exact.*                         the exact f32 top-k of every segment of a batch from one table-driven scan launch (any k), and the router
+    mmf.combined_topk_anyk.*                      the top-k of K_h * K_g for any k (one graph, a batch, two node sets, row panels): exact passes behind per-row floors
     mmf.kmeans_ragged.*                           scikit-learn's KMeans fit for every block of a flat buffer in one call, each block with a width of its own
     mmf.wide_scan.*                               what the wide 16-bit scan (feature dims 1025..4096) covers: host-only queries
     mmf.cohort.build_cohort_hypergraphs(...)      the four steps of process_single_file for every slide of a cohort, in memory
     mmf.build_hypergraph.*                        the reference's function names and signatures
     mmf.distributed.sharded_simtopk(...)          row-sharded multi-GPU driver (RCCL all-gather)
     mmf.distributed.sharded_simtopk_combined(...) the same driver for the top-k of K_h * K_g
+    mmf.distributed.sharded_simtopk_combined_any_k(...) that driver for any k
 """
 from . import _lib, ops  # noqa: F401
 from .ops import (edge_cosine, offdiag_lower_median, sim_dense, sim_dense_combined, sim_dense_combined_segmented,  # noqa: F401
@@ -53,6 +55,10 @@ from .segmented_exact import segmented_exact_table, simtopk_combined_exact, simt
 from . import kmeans_ragged  # noqa: F401,E402
 from .kmeans_ragged import kmeans_fit_predict_ragged, kmeans_fit_ragged, ragged_groups  # noqa: F401,E402
 
+from . import combined_topk_anyk  # noqa: F401,E402
+from .combined_topk_anyk import (anyk_route, build_topk_hypergraph_data_any_k, build_topk_weighted_hypergraph_any_k,  # noqa: F401,E402
+                                 simtopk_combined_any_k, simtopk_combined_rows_any_k, simtopk_combined_xy_any_k)
+
 from . import wide_scan  # noqa: F401,E402
 from .wide_scan import list_capacity, wide_scan_supported  # noqa: F401,E402
 
@@ -66,4 +72,6 @@ __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combin
            "combined_topk16_segmented", "simtopk_combined_fast_segmented", "build_topk_weighted_hypergraph_fast_segmented",
            "build_topk_hypergraph_data_fast", "combined_topk_xy", "simtopk_combined_xy", "simtopk_combined_rows",
            "segmented_exact", "simtopk_segmented_exact", "simtopk_combined_exact", "segmented_exact_table",
-           "kmeans_ragged", "kmeans_fit_ragged", "kmeans_fit_predict_ragged", "ragged_groups"]
+           "kmeans_ragged", "kmeans_fit_ragged", "kmeans_fit_predict_ragged", "ragged_groups",
+           "combined_topk_anyk", "anyk_route", "simtopk_combined_any_k", "simtopk_combined_xy_any_k", "simtopk_combined_rows_any_k",
+           "build_topk_weighted_hypergraph_any_k", "build_topk_hypergraph_data_any_k"]

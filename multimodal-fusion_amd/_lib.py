@@ -105,6 +105,11 @@ EXPORTS_SEG_EXACT = ["mmf_simtopk_segmented_exact", "mmf_simtopk_combined_segmen
 # "Ragged KMeans entries"); mmf_kmeans_ragged_groups is host-only.  Pinned by tests/test_kmeans_ragged_cpu.py.
 EXPORTS_KMEANS_RAGGED = ["mmf_kmeans_fit_ragged", "mmf_kmeans_ragged_groups"]
 
+# The combined top-k for any k (include/ext/mmf_hg_topk_anyk.h): an addition to ABI version 3 in a header of its
+# own.  Its synchronisation behaviour is INTEGRATION.md's table "Any-k top-k entries", pinned by
+# tests/test_simtopk_combined_anyk_cpu.py.
+EXPORTS_TOPK_ANYK = ["mmf_simtopk_combined_anyk", "mmf_simtopk_combined_xy_anyk"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -183,6 +188,9 @@ def lib() -> ctypes.CDLL:
     L.mmf_kmeans_fit_ragged.restype = ci
     L.mmf_kmeans_ragged_groups.argtypes = [vp, vp, i64, i64, i64, ci, vp, vp]
     L.mmf_kmeans_ragged_groups.restype = i64
+    L.mmf_simtopk_combined_anyk.argtypes = list(L.mmf_simtopk_combined.argtypes)
+    L.mmf_simtopk_combined_xy_anyk.argtypes = list(L.mmf_simtopk_combined_xy.argtypes)
+    L.mmf_simtopk_combined_anyk.restype = L.mmf_simtopk_combined_xy_anyk.restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

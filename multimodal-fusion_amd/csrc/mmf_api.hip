@@ -850,7 +850,7 @@ int run_simtopk_combined(const char* who, const float* F, const float* P, int64_
   }
   if (ex.pieces.empty()) return MMF_OK;
   ExactLists B;
-  B.carve(ws, ex.rows_total, ex.list_words, ex.cap(), false);
+  B.carve(ws, ex.rows_total, ex.list_words, ex.cap(), ex.floors());   // floors: the passes of the any-k entries (k + self > 44)
   MMF_TRY(B.zero(s));
   MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
 
@@ -1466,7 +1466,7 @@ int run_simtopk_combined_xy(const char* who, const float* Fq, const float* Pq, i
   for (const XYRange& g : bare) MMF_TRY(xy_fill_none(out_idx, out_val, g.a, g.b - g.a, k, s));
   if (ex.pieces.empty()) return MMF_OK;
   ExactLists B;
-  B.carve(ws, ex.rows_total, ex.list_words, ex.cap(), false);
+  B.carve(ws, ex.rows_total, ex.list_words, ex.cap(), ex.floors());   // floors: the passes of the any-k entries (k + self > 44)
   MMF_TRY(B.zero(s));
   MMF_HIP(hipMemsetAsync(cand_total, 0, 1024, s));
 
@@ -2952,6 +2952,95 @@ int mmf_simtopk_combined_segmented_exact(const float* F, const float* P, int64_t
   r.precision = MMF_PREC_EXACT;
   MMF_TRY(r.call.begin());
   return run_segmented_exact(r, true, ptr_host, ptr_host, n_segments, opts, P, (int)dp, lambda_g);
+}
+
+// ---- the combined top-k for any k (include/ext/mmf_hg_topk_anyk.h) ---------------------------------------
+// The drivers of the entries above without their k + self > 44 refusal: ExactPass::run and run_segmented_exact loop over passes of
+// at most 44 - self entries, and launch_rerank_combined (mmf_topk.hip) now writes a pass's columns and the next pass's floors.
+
+int mmf_simtopk_combined_anyk(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h, float lambda_g, int k,
+                              int exclude_self, const int64_t* ptr_host, int64_t n_segments, int64_t* out_idx, float* out_val,
+                              const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  const char* who = "simtopk_combined_anyk";
+  MMF_TRY(Call(who, device_id, hip_stream).on_device());
+  if (n < 0) { set_error("%s: n must be >= 0 (got %lld)", who, (long long)n); return MMF_E_INVALID; }
+  if (d < 1) { set_error("%s: d must be at least 1 (got %lld)", who, (long long)d); return MMF_E_INVALID; }
+  if (dp < 1) { set_error("%s: dp must be at least 1 (got %lld)", who, (long long)dp); return MMF_E_INVALID; }
+  if (k < 1) { set_error("%s: k must be at least 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (!(lambda_h >= 0.0f) || !std::isfinite(lambda_h)) { set_error("%s: lambda_h must be finite and >= 0 (got %g)", who, lambda_h); return MMF_E_INVALID; }
+  if (!(lambda_g >= 0.0f) || !std::isfinite(lambda_g)) { set_error("%s: lambda_g must be finite and >= 0 (got %g)", who, lambda_g); return MMF_E_INVALID; }
+  if (n > 0 && !F) { set_error("%s: F is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !P) { set_error("%s: P is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !out_idx) { set_error("%s: out_idx is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !out_val) { set_error("%s: out_val is NULL", who); return MMF_E_INVALID; }
+  const bool segmented = ptr_host != nullptr || n_segments != 0;
+  if (segmented) {
+    MMF_TRY(check_offsets(who, "ptr_host", ptr_host, n_segments, 0, 0, n));
+    MMF_TRY(check_pow2_splits(who, opts));
+  }
+  if (dp > 8) { set_error("%s: dp = %lld > 8 is not supported", who, (long long)dp); return MMF_E_UNSUPPORTED; }
+  if (n >= (int64_t)1 << 31) { set_error("%s: n must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  const int prec = opts ? opts->precision : MMF_PREC_AUTO;
+  if (prec != MMF_PREC_AUTO && prec != MMF_PREC_EXACT) {
+    set_error("%s: precision %d: only MMF_PREC_AUTO and MMF_PREC_EXACT (the 16-bit combined scans stop at k + self = 20)", who, prec);
+    return MMF_E_UNSUPPORTED;
+  }
+  if (opts && opts->col_splits < 0) { set_error("%s: col_splits must be >= 0 (got %d)", who, opts->col_splits); return MMF_E_INVALID; }
+  if (n == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return MMF_OK; }
+  if (!segmented) {
+    const int64_t one_graph[2] = {0, n};
+    return run_simtopk_combined(who, F, P, n, d, dp, lambda_h, lambda_g, k, exclude_self, one_graph, 1, out_idx, out_val, opts, stats,
+                                device_id, hip_stream);
+  }
+  if (stats) memset(stats, 0, sizeof(*stats));
+  Request r{Call(who, device_id, hip_stream), F, n, F, n, d, MMF_F32, MMF_RBF, lambda_h, k, exclude_self, 0, 0,
+            out_idx, out_val, stats, opts && opts->profile};
+  r.kk = k + (exclude_self ? 1 : 0);
+  r.precision = MMF_PREC_EXACT;
+  MMF_TRY(r.call.begin());
+  return run_segmented_exact(r, true, ptr_host, ptr_host, n_segments, opts, P, (int)dp, lambda_g);
+}
+
+int mmf_simtopk_combined_xy_anyk(const float* Fq, const float* Pq, int64_t nq, const float* Fc, const float* Pc, int64_t nc,
+                                 int64_t d, int64_t dp, float lambda_h, float lambda_g, int k, int exclude_self,
+                                 int64_t row_offset, int64_t col_offset, int64_t* out_idx, float* out_val,
+                                 const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  const char* who = "simtopk_combined_xy_anyk";
+  MMF_TRY(Call(who, device_id, hip_stream).on_device());
+  if (nq < 0) { set_error("%s: nq must be >= 0 (got %lld)", who, (long long)nq); return MMF_E_INVALID; }
+  if (nc < 0) { set_error("%s: nc must be >= 0 (got %lld)", who, (long long)nc); return MMF_E_INVALID; }
+  if (d < 1) { set_error("%s: d must be at least 1 (got %lld)", who, (long long)d); return MMF_E_INVALID; }
+  if (dp < 1) { set_error("%s: dp must be at least 1 (got %lld)", who, (long long)dp); return MMF_E_INVALID; }
+  if (k < 1) { set_error("%s: k must be at least 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (row_offset < 0) { set_error("%s: row_offset must be >= 0 (got %lld)", who, (long long)row_offset); return MMF_E_INVALID; }
+  if (col_offset < 0) { set_error("%s: col_offset must be >= 0 (got %lld)", who, (long long)col_offset); return MMF_E_INVALID; }
+  if (!(lambda_h >= 0.0f) || !std::isfinite(lambda_h)) { set_error("%s: lambda_h must be finite and >= 0 (got %g)", who, lambda_h); return MMF_E_INVALID; }
+  if (!(lambda_g >= 0.0f) || !std::isfinite(lambda_g)) { set_error("%s: lambda_g must be finite and >= 0 (got %g)", who, lambda_g); return MMF_E_INVALID; }
+  if (nq > 0 && !Fq) { set_error("%s: Fq is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && !Pq) { set_error("%s: Pq is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && nc > 0 && !Fc) { set_error("%s: Fc is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && nc > 0 && !Pc) { set_error("%s: Pc is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && !out_idx) { set_error("%s: out_idx is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && !out_val) { set_error("%s: out_val is NULL", who); return MMF_E_INVALID; }
+  const int prec = opts ? opts->precision : MMF_PREC_AUTO;
+  if (prec != MMF_PREC_AUTO && prec != MMF_PREC_EXACT && prec != MMF_PREC_FAST && prec != MMF_PREC_FAST_BF16) {
+    set_error("%s: precision %d: MMF_PREC_AUTO or MMF_PREC_EXACT", who, prec);
+    return MMF_E_INVALID;
+  }
+  if (opts && opts->col_splits < 0) { set_error("%s: col_splits must be >= 0 (got %d)", who, opts->col_splits); return MMF_E_INVALID; }
+  if (dp > 8) { set_error("%s: dp = %lld > 8 is not supported", who, (long long)dp); return MMF_E_UNSUPPORTED; }
+  if (prec == MMF_PREC_FAST || prec == MMF_PREC_FAST_BF16) {
+    set_error("%s: precision %d: only MMF_PREC_AUTO and MMF_PREC_EXACT (the 16-bit combined scans stop at k + self = 20)", who, prec);
+    return MMF_E_UNSUPPORTED;
+  }
+  if (nq >= ((int64_t)1 << 31) - row_offset) { set_error("%s: row_offset + nq must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  if (nc >= ((int64_t)1 << 31) - col_offset) { set_error("%s: col_offset + nc must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  if (nq == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return MMF_OK; }
+  mmf_simtopk_opts exact{};   // AUTO means the exact scan here, whatever the (d, k) range
+  if (opts) exact = *opts;
+  exact.precision = MMF_PREC_EXACT;
+  return run_simtopk_combined_xy(who, Fq, Pq, nq, Fc, Pc, nc, d, dp, lambda_h, lambda_g, k, exclude_self, row_offset, col_offset, out_idx,
+                                 out_val, &exact, stats, device_id, hip_stream);
 }
 
 int64_t mmf_segmented_exact_table(const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_segments, int k, int exclude_self,

@@ -16,6 +16,7 @@
 #include "../../include/ext/mmf_hg_topk16_seg.h"
 #include "../../include/ext/mmf_hg_topk_xy.h"
 #include "../../include/ext/mmf_hg_seg_exact.h"
+#include "../../include/ext/mmf_hg_topk_anyk.h"
 #include "../../include/ext/mmf_hg_kmeans_ragged.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
@@ -289,8 +290,11 @@ int launch_query_order_apply(const uint16_t* ZQ, const float* q_zn, const float*
                              int dp, bool f16, void* scratch, uint16_t* Zo, float* zno, float* rno, float* uno, const int32_t** perm,
                              hipStream_t s);
 int launch_select(const SelectProblem& p, const CandLists& L, hipStream_t s);
-// mmf_topk.hip: the re-rank of the combined key over the exact scan's lists (f32 rows, no row_ids / perm / floors): key and value
-// recomputed with fmaf chains over F and P, ranked by counting under better(); k entries per row, then -1 / -inf up to out_stride
+// mmf_topk.hip: the re-rank of the combined key over the exact scan's lists (f32 rows, no row_ids / perm): key and value
+// recomputed with fmaf chains over F and P, ranked by counting under better(); k entries per row from column out_off on, then
+// -1 / -inf up to out_stride.  One pass of several (out_off != 0 or floor_key_out set): the columns before
+// out_off are left alone, the entry of rank k - 1 leaves its key and LOCAL id in floor_key_out / floor_id_out, and only the
+// last pass (no floor_key_out) pads
 int launch_rerank_combined(const SelectProblem& p, const CandLists& L, hipStream_t s);
 // mmf_api.hip: mmf_simtopk_combined behind its host checks (ptr: host offsets of n_seg >= 1 segments) — ExactPass over the segments
 int run_simtopk_combined(const char* who, const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h, float lambda_g,

@@ -9,8 +9,14 @@
 // the canonical fmaf chains over F and P — the same pos_exponent / combined_key as the scan, so the same bits — drops the
 // row itself by identity, and ranks by COUNTING: an entry's rank is the number of entries that beat it under better(), ranks
 // are distinct because a column sits in one list only, and every entry of rank < k writes itself.  No sort, no rounds of k.
+//
+// k + self > 44 (mmf_simtopk_combined_anyk, include/ext/mmf_hg_topk_anyk.h) runs several passes of scan and
+// re-rank: the PASS instantiations write a pass's entries behind the previous pass's columns and leave the per-row floor (key,
+// local id) of the last entry for the next scan, as launch_select does for the plain key.
 #include <math.h>
 #include <string.h>
+
+#include <type_traits>
 
 #include "mmf_dev.h"
 #include "mmf_host.h"
@@ -33,8 +39,17 @@ struct RerankCombinedArgs {
   int32_t* fail_rows; uint32_t* fail_count; uint32_t* cand_total;
 };
 
-template <bool VEC4>
-__global__ __launch_bounds__(64 * RR_WAVES) void rerank_combined_kernel(RerankCombinedArgs a) {
+// One pass of several: the k entries go to columns out_off .. out_off + k - 1 of the row, the entry of rank
+// k - 1 leaves (key, local id) in the row's floor slot for the next pass's scan, and only the last pass (no floor slot) pads.
+struct RerankCombinedPassArgs : RerankCombinedArgs {
+  int out_off;
+  float* floor_key_out; uint32_t* floor_id_out;
+};
+
+// PASS = false is the single-pass re-rank as it was (the same instructions); PASS = true adds only what sits under
+// `if constexpr (PASS)`.
+template <bool VEC4, bool PASS = false>
+__global__ __launch_bounds__(64 * RR_WAVES) void rerank_combined_kernel(std::conditional_t<PASS, RerankCombinedPassArgs, RerankCombinedArgs> a) {
   __shared__ float skey[RR_WAVES][RR_MAXC];
   __shared__ float sval[RR_WAVES][RR_MAXC];
   __shared__ uint32_t sid[RR_WAVES][RR_MAXC];
@@ -114,6 +129,7 @@ __global__ __launch_bounds__(64 * RR_WAVES) void rerank_combined_kernel(RerankCo
   __builtin_amdgcn_wave_barrier();
   int64_t* oi = a.out_idx + row * a.out_stride;
   float* ov = a.out_val + row * a.out_stride;
+  if constexpr (PASS) { oi += a.out_off; ov += a.out_off; }
   for (int e = lane; e < total; e += 64) {
     const uint32_t ie = id[e];
     if (ie == kNoIdx) continue;
@@ -124,30 +140,48 @@ __global__ __launch_bounds__(64 * RR_WAVES) void rerank_combined_kernel(RerankCo
       rank += (jf != kNoIdx && better(key[f], jf, ke, ie)) ? 1 : 0;
     }
     if (rank < a.k) { oi[rank] = a.col_offset + (int64_t)ie; ov[rank] = val[e]; }
+    if constexpr (PASS) {
+      // the next pass's floor: the key the scan compares (NaN already -inf) and the list's id, before col_offset — as select
+      if (a.floor_key_out && rank == a.k - 1) { a.floor_key_out[row] = ke; a.floor_id_out[row] = ie; }
+    }
   }
-  for (int t = a.k + lane; t < a.out_stride; t += 64) { oi[t] = -1; ov[t] = kNegInf; }
+  if constexpr (PASS) {
+    if (!a.floor_key_out)
+      for (int t = a.k + lane; t < a.out_stride - a.out_off; t += 64) { oi[t] = -1; ov[t] = kNegInf; }
+  } else {
+    for (int t = a.k + lane; t < a.out_stride; t += 64) { oi[t] = -1; ov[t] = kNegInf; }
+  }
 }
 
 int launch_rerank_combined(const SelectProblem& p, const CandLists& L, hipStream_t s) {
   if (p.n_rows <= 0) return MMF_OK;
-  if (p.dtype != MMF_F32 || p.row_ids || p.perm || p.floor_key_out || !p.Pq || !p.Pc || !p.pnq || !p.pnc || p.dp < 1 || p.dp > 8 ||
-      p.out_off != 0 || p.k < 1 || p.k > (p.out_stride ? p.out_stride : p.k) || L.lists * L.cap > RR_MAXC) {
-    set_error("rerank_combined: f32 rows in order, both sides' positions (1 <= dp <= 8), one pass, at most %d candidates per row", RR_MAXC);
+  const int stride = p.out_stride ? p.out_stride : p.k;
+  if (p.dtype != MMF_F32 || p.row_ids || p.perm || !p.Pq || !p.Pc || !p.pnq || !p.pnc || p.dp < 1 || p.dp > 8 || p.out_off < 0 ||
+      p.k < 1 || p.out_off + p.k > stride || (p.floor_key_out && !p.floor_id_out) || L.lists * L.cap > RR_MAXC) {
+    set_error("rerank_combined: f32 rows in order, both sides' positions (1 <= dp <= 8), columns inside the row, at most %d candidates per row", RR_MAXC);
     return MMF_E_INTERNAL;
   }
-  RerankCombinedArgs a{};
+  const bool pass = p.out_off != 0 || p.floor_key_out != nullptr;   // one pass of several: the kernel with out_off and floors
+  RerankCombinedPassArgs a{};
   a.X = static_cast<const float*>(p.X); a.Y = static_cast<const float*>(p.Y); a.d = p.d; a.m = p.m;
   a.rx = p.rx; a.cy = p.cy; a.Pq = p.Pq; a.Pc = p.Pc; a.dp = p.dp; a.pnq = p.pnq; a.pnc = p.pnc;
   a.neg_lambda_h = -p.lambda; a.neg_lambda_g = -p.lambda_g;
-  a.k = p.k; a.out_stride = p.out_stride ? p.out_stride : p.k; a.exclude_self = p.exclude_self;
+  a.k = p.k; a.out_stride = stride; a.exclude_self = p.exclude_self;
   a.row_offset = p.row_offset; a.col_offset = p.col_offset; a.n_rows = p.n_rows;
   a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow; a.lists = L.lists; a.cap = L.cap;
   a.out_idx = p.out_idx; a.out_val = p.out_val;
   a.fail_rows = p.fail_rows; a.fail_count = p.fail_count; a.cand_total = p.cand_total;
   const dim3 grid((unsigned)((p.n_rows + RR_WAVES - 1) / RR_WAVES));
   const bool vec4 = (p.d % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.X) & 15) == 0) && ((reinterpret_cast<uintptr_t>(p.Y) & 15) == 0);
-  if (vec4) hipLaunchKernelGGL(rerank_combined_kernel<true>, grid, dim3(64 * RR_WAVES), 0, s, a);
-  else hipLaunchKernelGGL(rerank_combined_kernel<false>, grid, dim3(64 * RR_WAVES), 0, s, a);
+  if (pass) {
+    a.out_off = p.out_off; a.floor_key_out = p.floor_key_out; a.floor_id_out = p.floor_id_out;
+    if (vec4) hipLaunchKernelGGL((rerank_combined_kernel<true, true>), grid, dim3(64 * RR_WAVES), 0, s, a);
+    else hipLaunchKernelGGL((rerank_combined_kernel<false, true>), grid, dim3(64 * RR_WAVES), 0, s, a);
+  } else {
+    const RerankCombinedArgs& a1 = a;
+    if (vec4) hipLaunchKernelGGL(rerank_combined_kernel<true>, grid, dim3(64 * RR_WAVES), 0, s, a1);
+    else hipLaunchKernelGGL(rerank_combined_kernel<false>, grid, dim3(64 * RR_WAVES), 0, s, a1);
+  }
   MMF_LAUNCH_CHECK();
   return MMF_OK;
 }
