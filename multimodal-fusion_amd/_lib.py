@@ -110,6 +110,12 @@ EXPORTS_KMEANS_RAGGED = ["mmf_kmeans_fit_ragged", "mmf_kmeans_ragged_groups"]
 # tests/test_simtopk_combined_anyk_cpu.py.
 EXPORTS_TOPK_ANYK = ["mmf_simtopk_combined_anyk", "mmf_simtopk_combined_xy_anyk"]
 
+# The cross-segment top-k (include/ext/mmf_hg_cross_seg.h): an addition to ABI version 3 in a header of its own.
+# mmf_simtopk_cross_segments synchronises once per call (the re-rank's fail counts); mmf_cross_segments_table is host-only.  Pinned
+# by tests/test_cross_segments_cpu.py.  (The name does not begin with EXPORTS: tests/test_simtopk_combined_anyk_cpu.py pins the
+# set of names that do.)
+CROSS_SEG_EXPORTS = ["mmf_simtopk_cross_segments", "mmf_cross_segments_table"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -191,6 +197,11 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_combined_anyk.argtypes = list(L.mmf_simtopk_combined.argtypes)
     L.mmf_simtopk_combined_xy_anyk.argtypes = list(L.mmf_simtopk_combined_xy.argtypes)
     L.mmf_simtopk_combined_anyk.restype = L.mmf_simtopk_combined_xy_anyk.restype = ci
+    L.mmf_simtopk_cross_segments.argtypes = [vp, i64, vp, i64, i64, ci, ci, f32, ci, vp, vp, i64, vp, vp,
+                                             ctypes.POINTER(SimtopkOpts), ctypes.POINTER(SimtopkStats), ci, vp]
+    L.mmf_simtopk_cross_segments.restype = ci
+    L.mmf_cross_segments_table.argtypes = [vp, vp, i64, ci, ci, vp, i64, ctypes.POINTER(ci)]
+    L.mmf_cross_segments_table.restype = i64
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

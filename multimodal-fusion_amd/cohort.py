@@ -9,6 +9,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ragged
+from .cross_segments import link_slides  # noqa: F401  (cohort.link_slides: the inter-slide edges of this module's result)
 from .knn_kmeans_hypergraph import build_hypergraph_knn_kmeans_segmented
 from .super_patches import aggregate_wsi_super_patches_segmented
 from .wsi_tma_similarity import compute_wsi_tma_similarity_segmented, group_by_similarity_segmented
@@ -66,3 +67,4 @@ def build_cohort_hypergraphs(wsi_features: torch.Tensor, wsi_positions: torch.Te
     return {"super_features": sf, "super_positions": sp, "S_flat": S_flat, "s_ptr": s_ptr, "group_labels": labels, "group_ptr": sw,
             "edge_index": edge_index, "edge_weights": edge_weights, "edge_ptr": edge_ptr,
             "node_ptr": torch.tensor(hg["node_ptr"], dtype=torch.int64), "K_flat": K_flat, "k_ptr": k_ptr, "stats": stats}
+

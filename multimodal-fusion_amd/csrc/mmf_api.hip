@@ -2761,15 +2761,19 @@ static int check_pow2_splits(const char* who, const mmf_simtopk_opts* opts) {
 }
 
 // r: checked, begun, n > 0.  xp / yp: host offsets of the S segments on the two sides (the same array for a self call).
+// cross (mmf_simtopk_cross_segments): the complement — the table is cross_seg_table's, the kernel masks each
+// block's own segment of Y; the entry has refused every segment short of k admissible columns, so the table serves every row.
 static int run_segmented_exact(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts,
-                               const float* P, int dp, float lambda_g) {
+                               const float* P, int dp, float lambda_g, bool cross = false) {
   const char* who = r.call.who;
   const hipStream_t s = r.call.s;
   const int k = r.k, self1 = r.exclude_self ? 1 : 0;
   const int cap = scan_f32_cap(std::min(r.kk, 44));
   int ranges = 1;
   std::vector<char> served;
-  const std::vector<int64_t> tab = seg_exact_table(xp, yp, S, k, r.exclude_self, opts ? opts->col_splits : 0, &ranges, &served);
+  const std::vector<int64_t> tab = cross ? cross_seg_table(xp, yp, S, k, opts ? opts->col_splits : 0, &ranges)
+                                         : seg_exact_table(xp, yp, S, k, r.exclude_self, opts ? opts->col_splits : 0, &ranges, &served);
+  if (cross) served.assign((size_t)S, 1);
   const int64_t grid = (int64_t)tab.size() / 8;
   if (grid >= ((int64_t)1 << 31)) { set_error("%s: %lld workgroups", who, (long long)grid); return MMF_E_UNSUPPORTED; }
   const int lists = 2 * ranges;
@@ -2848,7 +2852,7 @@ static int run_segmented_exact(Request& r, bool self, const int64_t* xp, const i
       const bool more = done + kp < k;
       sp.kk = kp + self1;
       if (done > 0) { sp.floor_key = B.floor_key; sp.floor_id = B.floor_id; }
-      MMF_TRY(launch_scan_f32_seg(sp, L, d_tab, grid, s));
+      MMF_TRY(launch_scan_f32_seg(sp, L, d_tab, grid, s, cross));
       if (passes == 1) { MMF_TRY(t[1].stop(s)); MMF_TRY(t[2].start(r.profile, s)); }
       q.k = kp; q.out_off = done;
       q.fail_count = fail_counts + 4 * pass;
@@ -2915,6 +2919,68 @@ int mmf_simtopk_segmented_exact(const void* X, int64_t n, const void* Y, int64_t
   if (stats) stats->near_rows = -1;
   if (n == 0) return MMF_OK;
   return run_segmented_exact(r, self, x_ptr_host, y_ptr_host, n_segments, opts, nullptr, 0, 0.0f);
+}
+
+// ---- cross-segment top-k (include/ext/mmf_hg_cross_seg.h) -------------------------------------------------------
+// The complement of the entry above from the same driver: every row against the rows of Y outside its own segment.  A row's self
+// lies inside its segment, so nothing is excluded by identity (kk = k); a segment short of k admissible columns is refused here,
+// on the host, so the driver's launch loop for unserved segments never runs.
+int mmf_simtopk_cross_segments(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric, float lambda,
+                               int k, const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_segments, int64_t* out_idx,
+                               float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream) {
+  const char* who = "simtopk_cross_segments";
+  const bool self = (Y == nullptr);
+  if (self) { Y = X; m = n; y_ptr_host = x_ptr_host; }
+  Request r{Call(who, device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, 0, 0, 0,
+            out_idx, out_val, stats, opts && opts->profile};
+  MMF_TRY(r.call.on_device());
+  if (n < 0 || m < 0 || d < 1) { set_error("%s: bad shape n=%lld m=%lld d=%lld", who, (long long)n, (long long)m, (long long)d); return MMF_E_INVALID; }
+  if (in_dtype != MMF_F32 && in_dtype != MMF_BF16 && in_dtype != MMF_F16) { set_error("%s: bad in_dtype %d", who, in_dtype); return MMF_E_INVALID; }
+  if (n > 0 && !X) { set_error("%s: X is NULL", who); return MMF_E_INVALID; }
+  if (n >= (int64_t)1 << 31 || m >= (int64_t)1 << 31) { set_error("%s: n and m must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  MMF_TRY(r.check(MMF_PREC_EXACT, true, [&] {
+    MMF_TRY(check_offsets(who, "x_ptr", x_ptr_host, n_segments, 0, 0, n));
+    MMF_TRY(check_offsets(who, "y_ptr", y_ptr_host, n_segments, 0, 0, m));
+    if (m > 0 && !Y) { set_error("%s: Y is NULL", who); return MMF_E_INVALID; }
+    MMF_TRY(check_pow2_splits(who, opts));
+    const int prec = opts ? opts->precision : MMF_PREC_AUTO;
+    if (prec != MMF_PREC_AUTO && prec != MMF_PREC_EXACT) {
+      set_error("%s: precision %d: only MMF_PREC_AUTO and MMF_PREC_EXACT (no 16-bit scan serves the cross-segment entry yet)", who, prec);
+      return prec == MMF_PREC_FAST || prec == MMF_PREC_FAST_BF16 ? MMF_E_UNSUPPORTED : MMF_E_INVALID;
+    }
+    if (n > 0 && (!out_idx || !out_val)) { set_error("%s: NULL output", who); return MMF_E_INVALID; }
+    for (int64_t g = 0; g < n_segments; ++g) {
+      const int64_t own = y_ptr_host[g + 1] - y_ptr_host[g];
+      if (x_ptr_host[g + 1] > x_ptr_host[g] && m - own < k) {
+        set_error("%s: segment %lld has %lld admissible columns (m = %lld minus its own %lld rows of Y), k = %d needs at least %d", who,
+                  (long long)g, (long long)(m - own), (long long)m, (long long)own, k, k);
+        return MMF_E_INVALID;
+      }
+    }
+    return MMF_OK;
+  }));
+  if (stats) stats->near_rows = -1;
+  if (n == 0) return MMF_OK;
+  return run_segmented_exact(r, self, x_ptr_host, y_ptr_host, n_segments, opts, nullptr, 0, 0.0f, true);
+}
+
+int64_t mmf_cross_segments_table(const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_segments, int k, int col_splits,
+                                 int64_t* table_host, int64_t capacity, int* lists_out) {
+  const char* who = "cross_segments_table";
+  if (!y_ptr_host) y_ptr_host = x_ptr_host;
+  MMF_TRY(check_offsets(who, "x_ptr", x_ptr_host, n_segments, 0, 0, kAnyRows));
+  MMF_TRY(check_offsets(who, "y_ptr", y_ptr_host, n_segments, 0, 0, kAnyRows));
+  if (k < 1) { set_error("%s: k must be >= 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (col_splits < 0 || (col_splits & (col_splits - 1)) != 0) { set_error("%s: col_splits must be 0 or a power of two (got %d)", who, col_splits); return MMF_E_INVALID; }
+  int ranges = 1;
+  const std::vector<int64_t> tab = cross_seg_table(x_ptr_host, y_ptr_host, n_segments, k, col_splits, &ranges);
+  const int64_t grid = (int64_t)tab.size() / 8;
+  if (table_host) {
+    if (capacity < grid) { set_error("%s: table of %lld entries needed", who, (long long)grid); return MMF_E_INVALID; }
+    if (grid > 0) memcpy(table_host, tab.data(), tab.size() * 8);
+  }
+  if (lists_out) *lists_out = 2 * ranges;
+  return grid;
 }
 
 int mmf_simtopk_combined_segmented_exact(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,

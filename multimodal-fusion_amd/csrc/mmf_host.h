@@ -18,6 +18,7 @@
 #include "../../include/ext/mmf_hg_seg_exact.h"
 #include "../../include/ext/mmf_hg_topk_anyk.h"
 #include "../../include/ext/mmf_hg_kmeans_ragged.h"
+#include "../../include/ext/mmf_hg_cross_seg.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -91,6 +92,9 @@ struct DeviceGuard {
   bool ok = false;
   explicit DeviceGuard(int dev) {
     if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(dev) == hipSuccess) ok = true;
+    // a refused device is reported through the entry's status; HIP also keeps it as the thread's last error, where the next
+    // launch check of this process — the library's or the caller's framework's — would find it and blame an unrelated call
+    else (void)hipGetLastError();
   }
   ~DeviceGuard() {
     if (prev >= 0) (void)hipSetDevice(prev);
@@ -256,7 +260,12 @@ int launch_scan_f32(const ScanProblem& p, const CandLists& L, hipStream_t s, int
 // floors / lists covering all rows, ids = rows of Y, L.lists = 2 * ranges, counts zeroed by the caller
 std::vector<int64_t> seg_exact_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int k, int exclude_self, int col_splits,
                                      int* ranges_out, std::vector<char>* served_out);
-int launch_scan_f32_seg(const ScanProblem& p, const CandLists& L, const int64_t* sched, int64_t grid, hipStream_t s);
+// the cross-segment scan: the table of the complement — per block of 128 rows of a segment, runs of the 128-row
+// tiles of ALL of Y that do not lie wholly inside the segment's own rows y_ptr[s] .. y_ptr[s + 1]; the two bounds ride in the
+// words seg_exact_table gives to the segment's first row and column count; *ranges_out the largest range count of a block
+std::vector<int64_t> cross_seg_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int k, int col_splits, int* ranges_out);
+// cross: `sched` is a cross_seg_table, the kernel masks each entry's excluded range (no combined key)
+int launch_scan_f32_seg(const ScanProblem& p, const CandLists& L, const int64_t* sched, int64_t grid, hipStream_t s, bool cross = false);
 
 // mmf_select.hip: canonical keys of the candidates, self dropped, top-k by (key desc, id asc).
 struct SelectProblem {

@@ -95,10 +95,18 @@ enum { SEGF_SEG = 0, SEGF_ROW0 = 1, SEGF_NQ = 2, SEGF_CBASE = 3, SEGF_T0 = 4, SE
 // epilogue the 32 lanes of a half read the same candidate's position (an LDS broadcast).  The chain, the DMA, the floor test and
 // LaneList are those of the plain scan; the other instantiations are untouched.  COMB asks for two workgroups per CU at every
 // capacity: that bounds the allocator at 256 registers (204 VGPRs, no AGPRs, nothing spilled); LDS decides how many run.
-template <int MODE, int CAP, int F_KC, bool SEG = false, bool COMB = false>
+//
+// XSEG (SEG with MODE_SCAN, no COMB; mmf_simtopk_cross_segments): the complement of the segmented scan.  The row
+// block is still SEGF_ROW0 / SEGF_NQ of one segment, but the candidates are rows j of ALL of Y (base 0, j < a.m, tiles aligned to
+// 128 rows as in the plain scan) and a key whose column lies in the block's excluded range [SEGF_CBASE, SEGF_NS) — the segment's
+// own rows of Y, the two table words that would always be 0 and m here — becomes -inf where the m mask is applied, before the floor
+// test and before LaneList sees the tile.  Both bounds are workgroup-uniform; a 32-column sub-tile that does not touch the range
+// skips the test (wave-uniform branch).  Everything else is the SEG scan's code; the other instantiations are untouched.
+template <int MODE, int CAP, int F_KC, bool SEG = false, bool COMB = false, bool XSEG = false>
 __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16 || COMB) ? 2 : 1) void scan_f32_kernel(ScanF32Args a) {
   constexpr bool SSEG = SEG && MODE == MODE_SCAN;   // the table-driven scan epilogue (launch_scan_f32_seg)
   static_assert(!COMB || MODE == MODE_SCAN, "the combined key is a scan epilogue");
+  static_assert(!XSEG || (SSEG && !COMB), "the cross flavour is the table-driven scan without the combined key");
   constexpr int UPR = F_KC / 4;            // 16-byte units per image row
   constexpr int RPP = 64 / UPR;            // image rows per 1 KiB DMA piece
   constexpr int HP = F_QT / RPP;           // pieces per operand tile (8 / 16)
@@ -124,7 +132,13 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16 || COMB) ? 2
   int64_t q0, t_begin, t_end;
   int64_t m = a.m, qend = a.n_rows;        // columns of the output row; queries q < qend are real
   int64_t cbase = 0, obase = 0;            // SEG: the segment's first row, its block's first output element
-  if constexpr (SEG) {
+  int ex_lo = 0, ex_len = 0;               // XSEG: first row and row count of the excluded columns (ids below 2^31)
+  if constexpr (XSEG) {
+    const int64_t* e = a.sched + (size_t)blockIdx.x * SEGF_ENTRY;
+    q0 = e[SEGF_ROW0]; qend = q0 + e[SEGF_NQ];
+    t_begin = e[SEGF_T0]; t_end = e[SEGF_T1]; split = (int)e[SEGF_OUT];
+    ex_lo = (int)e[SEGF_CBASE]; ex_len = (int)(e[SEGF_NS] - e[SEGF_CBASE]);
+  } else if constexpr (SEG) {
     const int64_t* e = a.sched + (size_t)blockIdx.x * SEGF_ENTRY;
     q0 = e[SEGF_ROW0]; qend = q0 + e[SEGF_NQ]; cbase = e[SEGF_CBASE];
     t_begin = e[SEGF_T0]; t_end = e[SEGF_T1]; obase = e[SEGF_OUT]; m = e[SEGF_NS];
@@ -389,6 +403,18 @@ __global__ __launch_bounds__(F_NT, (MODE == MODE_DENSE || CAP <= 16 || COMB) ? 2
           key[r] = jv ? key[r] : kNegInf;
           acc[t][r] = 0.0f;
         }
+        if constexpr (XSEG) {
+          // the row block's own segment: columns ex_lo .. ex_lo + ex_len - 1 (one unsigned compare per key; a sub-tile outside
+          // the range, which is every sub-tile of all but the two boundary tiles, takes the branch around it)
+          const int c0 = (int)cand0;
+          if (c0 < ex_lo + ex_len && c0 > ex_lo - 32) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const uint32_t off = (uint32_t)(c0 + (r & 3) + 8 * (r >> 2) + 4 * half - ex_lo);
+              key[r] = off < (uint32_t)ex_len ? kNegInf : key[r];
+            }
+          }
+        }
         if (floored) {                             // wave-uniform: a later pass of a large-k call
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -439,7 +465,7 @@ static size_t scan_f32_lds(int cap, int kc) {
 }
 constexpr size_t kScanPosLds = sizeof(float) * 2 * F_CT * 9;   // COMB: the tiles' positions and their chains
 
-template <int MODE, int CAP, bool SEG = false, bool COMB = false>
+template <int MODE, int CAP, bool SEG = false, bool COMB = false, bool XSEG = false>
 static int launch_f32_t(const ScanF32Args& a, int64_t grid, hipStream_t s) {
   if (a.metric < MMF_DOT || a.metric > MMF_RBF) {
     set_error("scan_f32: unsupported metric %d", a.metric);
@@ -451,7 +477,7 @@ static int launch_f32_t(const ScanF32Args& a, int64_t grid, hipStream_t s) {
   }
   constexpr int KC = (MODE == MODE_SCAN) ? 16 : 32;
   const size_t lds = scan_f32_lds(MODE == MODE_SCAN ? CAP : 0, KC) + (COMB ? kScanPosLds : 0);
-  auto kern = scan_f32_kernel<MODE, CAP, KC, SEG, COMB>;
+  auto kern = scan_f32_kernel<MODE, CAP, KC, SEG, COMB, XSEG>;
   MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(F_NT), lds, s, a);
   MMF_LAUNCH_CHECK();
@@ -535,10 +561,82 @@ std::vector<int64_t> seg_exact_table(const int64_t* x_ptr, const int64_t* y_ptr,
   return tab;
 }
 
+// The work table of the cross-segment scan (mmf_simtopk_cross_segments), the layout of seg_exact_table with two
+// words re-used: entry = segment, first row of X, real queries, ex_lo = y_ptr[s] (SEGF_CBASE), first and end tile, number of the
+// column range, ex_hi = y_ptr[s + 1] (SEGF_NS).  The column tiles are the F_CT-row tiles of ALL of Y from row 0, T = ceil(m / F_CT)
+// of them.  The segment's hole is the tiles that lie wholly inside [ex_lo, ex_hi) — tiles ceil(ex_lo / F_CT) up to floor(ex_hi /
+// F_CT), up to T when ex_hi == m: they appear in no entry; a tile that straddles a bound appears once and the kernel masks it.  The
+// A = T - hole admissible tiles, numbered without the hole, are cut into R runs of ceil(A / R) as in seg_exact_table: R a power of
+// two, at most A, at most `col_splits` when that is forced (> 0), else ceil(A / per) with `per` sized so that the call makes about
+// 1024 workgroups.  A run that spans the hole becomes TWO entries, one on each side of it, with range numbers (and so list slots)
+// of their own: the ranges of a block are numbered 0, 1, ... in tile order, at most R + 1 of them, which is why R stops at the
+// largest power of two with 2 (R + 1) cap <= 1024, the re-rank's candidates per row.  A segment without rows, or without an
+// admissible tile, makes no entry; a segment with no rows of Y excludes nothing.  *ranges_out: the largest range count of a block.
+std::vector<int64_t> cross_seg_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int k, int col_splits, int* ranges_out) {
+  const int cap = scan_f32_cap(k < 44 ? k : 44);
+  int max_r = 1;
+  while (2 * (2 * max_r + 1) * cap <= 1024) max_r <<= 1;
+  const int64_t m = S > 0 ? y_ptr[S] : 0, T = (m + F_CT - 1) / F_CT;
+  auto hole = [&](int64_t g, int64_t* h0, int64_t* h1) {
+    *h0 = (y_ptr[g] + F_CT - 1) / F_CT;
+    *h1 = y_ptr[g + 1] == m ? T : y_ptr[g + 1] / F_CT;
+    if (*h1 < *h0) *h1 = *h0;
+  };
+  int64_t pairs = 0;
+  for (int64_t g = 0; g < S; ++g) {
+    int64_t h0, h1;
+    hole(g, &h0, &h1);
+    pairs += ((x_ptr[g + 1] - x_ptr[g] + F_QT - 1) / F_QT) * (T - (h1 - h0));
+  }
+  const int64_t per = std::max<int64_t>(1, (pairs + 1023) / 1024);
+  std::vector<int64_t> tab;
+  int ranges = 1;
+  for (int64_t g = 0; g < S; ++g) {
+    const int64_t ng = x_ptr[g + 1] - x_ptr[g];
+    int64_t h0, h1;
+    hole(g, &h0, &h1);
+    const int64_t adm = T - (h1 - h0);
+    if (ng <= 0 || adm <= 0) continue;
+    const int64_t want = col_splits > 0 ? col_splits : (adm + per - 1) / per;
+    int R = 1;
+    while (2 * R <= want && 2 * R <= adm && 2 * R <= max_r) R <<= 1;
+    const int64_t tps = (adm + R - 1) / R;
+    for (int64_t r = 0; r < ng; r += F_QT) {
+      int number = 0;
+      auto entry = [&](int64_t t0, int64_t t1) {
+        if (t0 >= t1) return;
+        const int64_t e[SEGF_ENTRY] = {g, x_ptr[g] + r, ng - r < F_QT ? ng - r : F_QT, y_ptr[g], t0, t1, number++, y_ptr[g + 1]};
+        tab.insert(tab.end(), e, e + SEGF_ENTRY);
+      };
+      for (int64_t a0 = 0; a0 < adm; a0 += tps) {
+        // admissible tile a is tile a below the hole and tile a + (h1 - h0) above it
+        const int64_t a1 = std::min(a0 + tps, adm);
+        if (h1 == h0 || a1 <= h0) entry(a0, a1);
+        else if (a0 >= h0) entry(a0 + (h1 - h0), a1 + (h1 - h0));
+        else { entry(a0, h0); entry(h1, a1 + (h1 - h0)); }
+      }
+      if (number > ranges) ranges = number;
+    }
+  }
+  // Longest run first.  The two sides of a hole are as uneven as the segment's place in the batch makes them (a block of the
+  // last segment is one run of nearly all tiles and one of none), and in table order the longest runs would start last: measured
+  //  the launch then ends in a tail of a few long workgroups.  Entries are independent, so any order is correct.
+  const size_t entries = tab.size() / SEGF_ENTRY;
+  std::vector<size_t> order(entries);
+  for (size_t i = 0; i < entries; ++i) order[i] = i;
+  auto len = [&](size_t i) { return tab[i * SEGF_ENTRY + SEGF_T1] - tab[i * SEGF_ENTRY + SEGF_T0]; };
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return len(a) > len(b); });
+  std::vector<int64_t> sorted(tab.size());
+  for (size_t i = 0; i < entries; ++i) std::copy_n(tab.begin() + order[i] * SEGF_ENTRY, SEGF_ENTRY, sorted.begin() + i * SEGF_ENTRY);
+  if (ranges_out) *ranges_out = ranges;
+  return sorted;
+}
+
 // One workgroup per entry of the device copy `sched` of that table.  p.Xp / p.Yp: the f32 images of ALL rows of X and Y; p.rx /
 // p.cy, the floors, the positions and the lists L (L.lists = 2 x the table's largest range count) cover all rows; p.kk, the
 // metric and the floors are those of launch_scan_f32.  Counts of the slots a segment does not use must be zero already.
-int launch_scan_f32_seg(const ScanProblem& p, const CandLists& L, const int64_t* sched, int64_t grid, hipStream_t s) {
+// cross: `sched` is a cross_seg_table and the kernel is the XSEG flavour (no combined key).
+int launch_scan_f32_seg(const ScanProblem& p, const CandLists& L, const int64_t* sched, int64_t grid, hipStream_t s, bool cross) {
   if (grid <= 0) return MMF_OK;
   if (p.row_ids || !sched || L.lists < 2 || (L.lists & 1)) { set_error("scan_f32_seg: needs a work table, list pairs and no gathered rows"); return MMF_E_INTERNAL; }
   ScanF32Args a{};
@@ -549,7 +647,12 @@ int launch_scan_f32_seg(const ScanProblem& p, const CandLists& L, const int64_t*
   a.floor_key = p.floor_key; a.floor_id = p.floor_id;
   a.metric = p.metric;
   a.sched = sched;
-  if (p.Pc) {
+  if (cross) {
+    if (p.Pc || p.m >= ((int64_t)1 << 31)) { set_error("scan_f32_seg: the cross flavour has no combined key and needs m < 2^31"); return MMF_E_INTERNAL; }
+    if (L.cap == 16) return launch_f32_t<MODE_SCAN, 16, true, false, true>(a, grid, s);
+    if (L.cap == 32) return launch_f32_t<MODE_SCAN, 32, true, false, true>(a, grid, s);
+    if (L.cap == 48) return launch_f32_t<MODE_SCAN, 48, true, false, true>(a, grid, s);
+  } else if (p.Pc) {
     if (!p.Pq || !p.pnq || !p.pnc || p.dp < 1 || p.dp > 8 || p.metric != MMF_RBF) {
       set_error("scan_f32_seg: combined key needs both sides' positions and chains, 1 <= dp <= 8 (got %d) and MMF_RBF", p.dp);
       return MMF_E_INTERNAL;
