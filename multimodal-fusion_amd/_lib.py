@@ -116,6 +116,11 @@ EXPORTS_TOPK_ANYK = ["mmf_simtopk_combined_anyk", "mmf_simtopk_combined_xy_anyk"
 # set of names that do.)
 CROSS_SEG_EXPORTS = ["mmf_simtopk_cross_segments", "mmf_cross_segments_table"]
 
+# The cross-segment top-k on the 16-bit scan (include/ext/mmf_hg_cross_seg16.h): an addition to ABI version 3 in a
+# header of its own.  mmf_simtopk_cross_segments_fast synchronises once per call (the re-rank's fail counts; once more when rows
+# were flagged for the exact rescan); mmf_cross_segments_fast_table is host-only.  Pinned by tests/test_cross_segments_fast_cpu.py.
+CROSS_SEG16_EXPORTS = ["mmf_simtopk_cross_segments_fast", "mmf_cross_segments_fast_table"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -202,6 +207,10 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_cross_segments.restype = ci
     L.mmf_cross_segments_table.argtypes = [vp, vp, i64, ci, ci, vp, i64, ctypes.POINTER(ci)]
     L.mmf_cross_segments_table.restype = i64
+    L.mmf_simtopk_cross_segments_fast.argtypes = list(L.mmf_simtopk_cross_segments.argtypes)
+    L.mmf_simtopk_cross_segments_fast.restype = ci
+    L.mmf_cross_segments_fast_table.argtypes = [vp, vp, i64, i64, ci, ci, vp, i64, ctypes.POINTER(ci)]
+    L.mmf_cross_segments_fast_table.restype = i64
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

@@ -8,7 +8,7 @@ neighbours, the inter-slide edges of a cohort hypergraph, a bank that already ho
     cohort.link_slides(out, k=5)                   those edges among the super patches of build_cohort_hypergraphs' result
 
 The bits are those of one exact ``ops.simtopk`` per segment against the rest of Y, ids mapped back.  One scan launch and one re-rank
-per pass of 44 entries; ``precision="fast"`` does not exist here yet.
+per pass of 44 entries; the 16-bit scan of the same answer, and the router between the two, are cross_segments16.
 """
 from __future__ import annotations
 
@@ -22,7 +22,7 @@ from .build_hypergraph._common import compute_device
 from .ops import _DT, _call, _feat, _hp, _metric, _need_gpu, _p
 
 
-def _col_splits(col_splits, what: str) -> int:
+def checked_col_splits(col_splits, what: str) -> int:
     col_splits = int(col_splits)
     if col_splits < 0 or col_splits & (col_splits - 1):
         raise ValueError(f"{what}: col_splits must be 0 or a power of two (got {col_splits})")
@@ -66,7 +66,7 @@ def simtopk_cross_segments(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *,
         if Y.device != X.device or Y.dtype != X.dtype or Y.shape[1] != X.shape[1]:
             raise ValueError(f"{what}: X and Y must share device, dtype and feature dim")
     xp, yp = checked_offsets(X.shape[0], None if Y is None else Y.shape[0], ptr, batch, y_ptr, y_batch, k, what)
-    col_splits = _col_splits(col_splits, what)
+    col_splits = checked_col_splits(col_splits, what)
     mt = _metric(metric)
     _need_gpu(X, what)
     n, d = X.shape
@@ -107,6 +107,11 @@ def cross_segment_knn_edges(X: torch.Tensor, *, ptr=None, batch=None, k: int = 5
     (build_hypergraph_knn_kmeans, rows a8 / a9).  Every row's k Euclidean nearest rows OUTSIDE its own segment (``neg_sq_l2``
     through ``simtopk_cross_segments``), the undirected dedup of ``ops.knn_pairs`` (a pair both rows emit appears once, lower id
     first), sorted by (lower, higher) id, and the max(0, cosine) weights of ``ops.edge_cosine``.  Every edge joins two segments."""
+    return knn_edges_over(X, ptr, batch, k, simtopk_cross_segments)
+
+
+def knn_edges_over(X, ptr, batch, k, topk):
+    """cross_segment_knn_edges over the neighbours of ``topk`` (this module's exact call, or cross_segments16's router)."""
     what = "cross_segment_knn_edges"
     if ptr is None and batch is None:
         raise ValueError(f"{what}: needs ptr or batch (without segments every row is admissible: ops.simtopk)")
@@ -116,7 +121,7 @@ def cross_segment_knn_edges(X: torch.Tensor, *, ptr=None, batch=None, k: int = 5
     n = X.shape[0]
     if n == 0:
         return torch.empty((2, 0), dtype=torch.int64, device=X.device), torch.empty((0,), dtype=torch.float32, device=X.device)
-    nbr, _ = simtopk_cross_segments(X, ptr=ptr, batch=batch, metric="neg_sq_l2", k=k)
+    nbr, _ = topk(X, ptr=ptr, batch=batch, metric="neg_sq_l2", k=k)
     lo, hi = ops.knn_pairs(nbr)
     code = torch.sort(lo * n + hi).values
     edge_index = torch.stack([code // n, code % n], dim=0).contiguous()
@@ -131,6 +136,11 @@ def link_slides(out: dict, k: int = 5):
     max(0, cosine) weights) and the edges are returned in the cohort's node numbering: super patch c of slide s is node
     node_ptr[s] + c, so they can be concatenated with out["edge_index"].  The result lives where out["super_features"] does; the
     arithmetic runs on the GPU."""
+    return link_slides_over(out, k, cross_segment_knn_edges)
+
+
+def link_slides_over(out, k, knn_edges):
+    """link_slides over the edges of ``knn_edges`` (cross_segment_knn_edges of this module or of cross_segments16)."""
     what = "link_slides"
     if not isinstance(out, dict) or any(key not in out for key in ("super_features", "group_ptr", "node_ptr")):
         raise ValueError(f"{what}: needs the dict of build_cohort_hypergraphs (super_features, group_ptr, node_ptr)")
@@ -147,7 +157,7 @@ def link_slides(out: dict, k: int = 5):
     checked_offsets(sf.shape[0], None, gp, None, None, None, k, what)      # k >= 1 and k admissible super patches for every slide
     home = sf.device
     dev = compute_device(sf)
-    ei, ew = cross_segment_knn_edges(sf.detach().to(dev), ptr=gp, k=k)
+    ei, ew = knn_edges(sf.detach().to(dev), ptr=gp, k=k)
     shift = (node_ptr[:-1] - gp[:-1]).to(dev)                       # row -> node: slide s's rows move by node_ptr[s] - group_ptr[s]
     seg = ragged.segment_ids(gp).to(dev)
     ei = ei + shift[seg][ei]

@@ -19,6 +19,7 @@
 #include "../../include/ext/mmf_hg_topk_anyk.h"
 #include "../../include/ext/mmf_hg_kmeans_ragged.h"
 #include "../../include/ext/mmf_hg_cross_seg.h"
+#include "../../include/ext/mmf_hg_cross_seg16.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -264,7 +265,13 @@ std::vector<int64_t> seg_exact_table(const int64_t* x_ptr, const int64_t* y_ptr,
 // tiles of ALL of Y that do not lie wholly inside the segment's own rows y_ptr[s] .. y_ptr[s + 1]; the two bounds ride in the
 // words seg_exact_table gives to the segment's first row and column count; *ranges_out the largest range count of a block
 std::vector<int64_t> cross_seg_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int k, int col_splits, int* ranges_out);
-// cross: `sched` is a cross_seg_table, the kernel masks each entry's excluded range (no combined key)
+// the 16-bit cross-segment scan: its [entries][8] int32 work table over row blocks of qt rows of X and the 32-row
+// tiles of the plain image of Y (mmf_scan_f32.hip, beside cross_seg_table); *lists_out 2 x the largest entry count of a block, -1
+// when a run cannot be kept inside the tile DMA's 32-bit offsets
+std::vector<int32_t> cross_seg16_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int qt, int dp, int cap, int cand_budget,
+                                       int col_splits, int* lists_out);
+// cross: `sched` is a cross_seg_table, the kernel masks each entry's excluded range (no combined key); p.row_ids may then name
+// gathered rows (the table's rows are positions of p.Xp and of the lists)
 int launch_scan_f32_seg(const ScanProblem& p, const CandLists& L, const int64_t* sched, int64_t grid, hipStream_t s, bool cross = false);
 
 // mmf_select.hip: canonical keys of the candidates, self dropped, top-k by (key desc, id asc).
@@ -379,6 +386,10 @@ int scan_b16_queries_per_block(int dp);
 size_t scan_b16_seg_scratch_bytes(int64_t grid, int dp, int cap);
 int launch_scan_b16_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const CandLists& L, void* scratch,
                         const ScanB16Panel& pn, hipStream_t s);
+// the cross-segment flavour: plain images on both sides, `sched` a device copy of cross_seg16_table, `bounds`
+// [n_pad][2] the excluded column range (first, count) of every query row, L.lists = the table's list count, pn.share as the table says
+int launch_scan_b16_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, const CandLists& L,
+                         void* scratch, const ScanB16Panel& pn, hipStream_t s);
 
 // mmf_scan_b16w.hip: the wide 16-bit scan (1024 < d <= 4096, k + self <= 20) — both operands streamed through
 // LDS in k-chunks.  Same operand images (dp = d rounded up to 128), lists, threshold buffers and audit as launch_scan_b16; no

@@ -228,6 +228,9 @@ struct ScanB16Args {
   uint32_t* sym_log;         // [grid * NW][sym_log_cap][4]
   uint32_t* sym_log_cnt;     // [grid * NW] entries written (zeroed by the host; an idle workgroup writes nothing)
   int sym_log_cap;
+  // XSEG kernels only (launch_scan_b16_xseg): [n_pad][2] per query row, first row and row count of the columns the row may not
+  // take (its own segment's rows of Y; padding rows: 0, 0)
+  const uint32_t* xbounds;
 };
 
 // Work table entry of a segmented scan (one per workgroup): the row block's first position in the segment-padded query
@@ -238,6 +241,10 @@ enum { SEG_QPOS = 0, SEG_ROW0 = 1, SEG_NQ = 2, SEG_T0 = 3, SEG_T1 = 4, SEG_IDOFF
 // its columns — tiles [B1, B1 + N1) followed by [B2, B2 + N2) (a cyclic range that wraps, or own + antipodal super-block).
 // N1 and N2 are multiples of 8 tiles; N1 == 0 only when N2 == 0.
 enum { SYM_RB = 0, SYM_B1 = 1, SYM_N1 = 2, SYM_B2 = 3, SYM_N2 = 4 };
+// Work table entry of the cross-segment scan (cross_seg16_table; same entry size, SEG's words 0 .. 4): both images are the plain
+// ones, so the id offset is zero and its word carries the entry's list-slot number; words 6 and 7 are the entry's mask window,
+// the tiles [W0, W1) of its range that hold a column some query of the block may not take (W0 == W1: none).
+enum { XSEG_SLOT = 5, XSEG_W0 = 6, XSEG_W1 = 7 };
 
 // Order-preserving float <-> int32 map (an involution) so that thresholds can be merged with atomicMax.
 __device__ __forceinline__ int32_t seed_enc(float f) {
@@ -292,10 +299,18 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 #ifndef MMF_SYM_COUNT
 #define MMF_SYM_COUNT 0       // 1 = both SYM launches count wave-tiles, visits, hits and compactions (MMF_SCAN_DEBUG bit 8's counters)
 #endif                        //     and launch_scan_b16_sym prints them per launch (it synchronises the stream: not for timing)
-template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0>
+//
+// XSEG (implies SEG; mmf_simtopk_cross_segments_fast): every row against the columns OUTSIDE its own segment, on the
+// plain images of both sides (column = row of Y, no id offset).  The schedule is SEG's plus the entry's list slot (a row block has
+// several entries, which share thresholds through a.share) and its mask window.  A tile inside the window goes through a cold,
+// wave-uniform branch behind its chain: the lane fetches the excluded column range (first, count) of its two queries from
+// a.xbounds and sets each of its 16 values whose column lies inside to -inf — before max_qb, acc_prev and filter, so a masked value
+// reaches no list, overflow list, threshold, seed or lost.  SPLITK: only the owner wave masks; -inf survives the partner's partial sums.
+template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0, bool XSEG = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(ScanB16Args a) {
   static_assert(!SPLITK || (TPB == 1 && NW == 8 && (KS % 8) == 0), "split-k pairs");
   static_assert(SYM == 0 || (!SPLITK && !SEG && !DBG && TPB == 2), "symmetric schedule: the d = 512 kernel only");
+  static_assert(!XSEG || (SEG && SYM == 0 && !DBG), "the cross-segment mask rides on the table-driven schedule");
   constexpr int NQW = SPLITK ? NW / 2 : NW;     // waves that own queries and lists
   constexpr int NTL = 64 * NQW;                 // threads that own lists
   constexpr int QT = 32 * NQW;
@@ -338,6 +353,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   int nq = 0;
   uint32_t id_off = a.id_off;
   int sym_n1 = 0, sym_skip = 0;   // SYM: tiles of the first range, and how many tiles lie between its end and the second range's start
+  int xw0 = 0, xw1 = 0;           // XSEG: the mask window, as tile numbers inside this entry's range
   if constexpr (SYM != 0) {
     const int32_t* e = a.sched + (size_t)blockIdx.x * SEG_ENTRY;
     if (e[SYM_RB] < 0) return;
@@ -347,8 +363,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   } else if constexpr (SEG) {
     const int32_t* e = a.sched + (size_t)blockIdx.x * SEG_ENTRY;
     rb = e[SEG_QPOS] / QT; row0 = e[SEG_ROW0]; nq = e[SEG_NQ];
-    t_begin = e[SEG_T0]; t_end = e[SEG_T1]; id_off = (uint32_t)e[SEG_IDOFF];
-    split = 0;
+    t_begin = e[SEG_T0]; t_end = e[SEG_T1];
+    if constexpr (XSEG) {
+      id_off = 0u; split = e[XSEG_SLOT];
+      xw0 = e[XSEG_W0] - e[SEG_T0]; xw1 = e[XSEG_W1] - e[SEG_T0];
+    } else {
+      id_off = (uint32_t)e[SEG_IDOFF];
+      split = 0;
+    }
   } else {
     const int CS = a.conc_splits;
     const int64_t round = blockIdx.x / a.blocks_per_round;
@@ -607,6 +629,27 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       }
     }
   };
+  // XSEG: the columns a query may not take.  The window test is wave-uniform and almost always false (a block inside one segment
+  // has at most two such tiles); the four bound words are loaded inside the branch, so the tile loop carries no register for them.
+  auto mask_excluded = [&](Acc& x, int tt) {
+    if (__builtin_expect(tt >= xw0 && tt < xw1, 0)) {
+      if (owner) {
+        const uint32_t* bq = a.xbounds + 2 * (q0 + 32 * qw + c16);       // query block 0; block 1 is 16 rows on
+        const uint2 b0 = *reinterpret_cast<const uint2*>(bq);
+        const uint2 b1 = *reinterpret_cast<const uint2*>(bq + 32);
+        const uint32_t j0 = id_base + (uint32_t)tt * B_CT + 4u * (uint32_t)g;
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            const uint32_t j = j0 + 16u * cb + jj;
+            if ((uint32_t)(j - b0.x) < b0.y) x.t[cb][0][jj] = kNegInf;
+            if ((uint32_t)(j - b1.x) < b1.y) x.t[cb][1][jj] = kNegInf;
+          }
+        }
+      }
+    }
+  };
   // thresholds of the two queries this lane holds values for: its own list's and its partner's (lane ^ 16);
   // they change only inside the list code and in sync_seed, and are re-read from the partner there
   float thr_q0, thr_q1;
@@ -790,6 +833,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       // (behind the chain: issued in front of it, the same DMA costs +8 %; mid-chain needs a branch inside the chain)
       if constexpr (SYM == 0) { if (wave == ((t + TPB) & (NW - 1))) issue_bias(more ? bsrc + u * B_CT * 4 : cb0, ng + u); }
       else mask_padding(acc, t);
+      if constexpr (XSEG) mask_excluded(acc, t);
       if constexpr (SYM == 2 && MMF_SYM_ABLATE != 2) {
         // the next group's thresholds: between the iteration's two chains, far from either barrier (issued behind the LAST chain, a
         // fetch that has not landed holds all eight waves at the next barrier); the issuing wave rotates with the iteration
@@ -960,7 +1004,7 @@ size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap) {
 }
 
 // SEG and SYM kernels have no instrumented build
-template <int KS, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0>
+template <int KS, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0, bool XSEG = false>
 static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_t s) {
   const size_t lds = scan_b16_lds(KS, NW, TPB, CAP, SPLITK, SYM == 2);
   auto go = [&](auto kern) -> int {
@@ -970,8 +1014,8 @@ static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_
     return MMF_OK;
   };
   if constexpr (SEG || SYM != 0) {
-    if (f16) return go(scan_b16x_kernel<KS, true, false, NW, TPB, CAP, SPLITK, SEG, SYM>);
-    return go(scan_b16x_kernel<KS, false, false, NW, TPB, CAP, SPLITK, SEG, SYM>);
+    if (f16) return go(scan_b16x_kernel<KS, true, false, NW, TPB, CAP, SPLITK, SEG, SYM, XSEG>);
+    return go(scan_b16x_kernel<KS, false, false, NW, TPB, CAP, SPLITK, SEG, SYM, XSEG>);
   }
   if (a.debug != 0) {   // instrumented build of the same kernel (MMF_SCAN_DEBUG)
     if (f16) return go(scan_b16x_kernel<KS, true, true, NW, TPB, CAP, SPLITK>);
@@ -981,25 +1025,26 @@ static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_
   return go(scan_b16x_kernel<KS, false, false, NW, TPB, CAP, SPLITK>);
 }
 
-// (padded dim, list capacity) -> <KS, NW, TPB, CAP, SPLITK>, for the plain launch and (SEG) the table-driven one
-template <bool SEG>
+// (padded dim, list capacity) -> <KS, NW, TPB, CAP, SPLITK>, for the plain launch, (SEG) the table-driven one and (XSEG) the
+// table-driven one with the cross-segment mask
+template <bool SEG, bool XSEG = false>
 static int launch_b16_for(const char* who, int dp, int cap, const ScanB16Args& a, bool f16, int64_t grid, hipStream_t s) {
   const bool big = (cap == B_CAP_BIG);   // k + self in 12..20: 16-entry lists, one tile per barrier
   if (cap == B_CAP_WIDE) {               // k + self in 21..44: 32-entry lists, one tile per barrier, d <= 512
     switch (dp) {
-      case 128: return launch_b16_t<8, 8, 1, B_CAP_WIDE, false, SEG>(a, f16, grid, s);
-      case 256: return launch_b16_t<16, 8, 1, B_CAP_WIDE, false, SEG>(a, f16, grid, s);
-      case 512: return launch_b16_t<32, 8, 1, B_CAP_WIDE, false, SEG>(a, f16, grid, s);
+      case 128: return launch_b16_t<8, 8, 1, B_CAP_WIDE, false, SEG, 0, XSEG>(a, f16, grid, s);
+      case 256: return launch_b16_t<16, 8, 1, B_CAP_WIDE, false, SEG, 0, XSEG>(a, f16, grid, s);
+      case 512: return launch_b16_t<32, 8, 1, B_CAP_WIDE, false, SEG, 0, XSEG>(a, f16, grid, s);
     }
     set_error("%s: 32-entry lists need a padded dim <= 512 (got %d)", who, dp);
     return MMF_E_INTERNAL;
   }
   switch (dp) {
     // d <= 256: the smaller tiles leave room for eight stages — four tiles per barrier (-1.5 % against two at d = 256)
-    case 128: return big ? launch_b16_t<8, 8, 2, B_CAP_BIG, false, SEG>(a, f16, grid, s) : launch_b16_t<8, 8, 4, B_CAP, false, SEG>(a, f16, grid, s);
-    case 256: return big ? launch_b16_t<16, 8, 2, B_CAP_BIG, false, SEG>(a, f16, grid, s) : launch_b16_t<16, 8, 4, B_CAP, false, SEG>(a, f16, grid, s);
-    case 512: return big ? launch_b16_t<32, 8, 1, B_CAP_BIG, false, SEG>(a, f16, grid, s) : launch_b16_t<32, 8, 2, B_CAP, false, SEG>(a, f16, grid, s);
-    case 1024: return launch_b16_t<64, 8, 1, B_CAP, true, SEG>(a, f16, grid, s);
+    case 128: return big ? launch_b16_t<8, 8, 2, B_CAP_BIG, false, SEG, 0, XSEG>(a, f16, grid, s) : launch_b16_t<8, 8, 4, B_CAP, false, SEG, 0, XSEG>(a, f16, grid, s);
+    case 256: return big ? launch_b16_t<16, 8, 2, B_CAP_BIG, false, SEG, 0, XSEG>(a, f16, grid, s) : launch_b16_t<16, 8, 4, B_CAP, false, SEG, 0, XSEG>(a, f16, grid, s);
+    case 512: return big ? launch_b16_t<32, 8, 1, B_CAP_BIG, false, SEG, 0, XSEG>(a, f16, grid, s) : launch_b16_t<32, 8, 2, B_CAP, false, SEG, 0, XSEG>(a, f16, grid, s);
+    case 1024: return launch_b16_t<64, 8, 1, B_CAP, true, SEG, 0, XSEG>(a, f16, grid, s);
   }
   set_error("%s: unsupported padded dim %d", who, dp);
   return MMF_E_INTERNAL;
@@ -1096,6 +1141,21 @@ int launch_scan_b16_seg(const ScanB16Problem& p, const int32_t* sched, int64_t g
   ScanB16Args a = scan_args(p, L, pn, scratch);
   a.sched = sched;
   return launch_b16_for<true>("scan_b16_seg", p.dp, L.cap, a, p.f16, grid, s);
+}
+
+// Cross-segment scan (mmf_simtopk_cross_segments_fast): one workgroup per entry of `sched` (cross_seg16_table,
+// device copy), both operand images the plain ones (column = row of Y), `bounds` the [n_pad][2] excluded ranges of the query rows.
+// L.lists = 2 x the largest entry count of a row block (every entry's XSEG_SLOT is below that count); pn.share: the entries of a
+// block share thresholds.  Same kernel as launch_scan_b16_seg with the template flag XSEG: the other instantiations are untouched.
+int launch_scan_b16_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, const CandLists& L,
+                         void* scratch, const ScanB16Panel& pn, hipStream_t s) {
+  if (grid <= 0) return MMF_OK;
+  if (L.lists < 2 || (L.lists & 1) || !bounds || !sched) { set_error("scan_b16_xseg: list pairs, a work table and the rows' bounds expected"); return MMF_E_INTERNAL; }
+  if (L.lists > 2 && (!L.keys || !L.margin)) { set_error("scan_b16_xseg: several list pairs need keys and margins"); return MMF_E_INTERNAL; }
+  if (!pn.seed) { set_error("scan_b16_xseg: threshold buffers missing"); return MMF_E_INTERNAL; }
+  ScanB16Args a = scan_args(p, L, pn, scratch);
+  a.sched = sched; a.xbounds = bounds; a.share = pn.share;
+  return launch_b16_for<true, true>("scan_b16_xseg", p.dp, L.cap, a, p.f16, grid, s);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -632,16 +632,104 @@ std::vector<int64_t> cross_seg_table(const int64_t* x_ptr, const int64_t* y_ptr,
   return sorted;
 }
 
+// The work table of the 16-bit cross-segment scan (mmf_simtopk_cross_segments_fast): [entries][8] int32, the
+// words of the 16-bit scan's SEG entry with the id-offset word (zero on the plain images) carrying the list slot —
+//   first row of the block (operand position = list row), the same again, real queries, first and end tile, list slot, and the
+//   mask window [w0, w1) of the entry (w0 == w1: no tile of it needs the mask).
+// Row block b is rows [b qt, min((b + 1) qt, n)) of X whatever the segments: with s_first / s_last the segments of its first and
+// last row, U = [y_ptr[s_first], y_ptr[s_last + 1]) is the union of its rows' excluded ranges and I their intersection (U for a
+// block inside one segment, empty otherwise).  The column tiles are the 32-row tiles of the plain image of Y, T = m_pad / 32 of
+// them (m_pad: m rounded up to 256).  The block's hole — in no entry — is the tiles wholly inside I: ceil(I.lo / 32) up to
+// floor(I.hi / 32), up to T when I.hi == m (the tiles behind m hold padding only).  Its mask window is the tiles that meet U
+// without the hole.  The A = T - hole admissible tiles are cut into R runs of ceil(A / R) by cross_seg_table's rule (R a power of
+// two, at most A, `col_splits` when forced, else ceil(A / per) with `per` sized for about 1024 workgroups per call but no run shorter
+// than 64 tiles, the cadence of the threshold exchange), R capped at
+// the largest power of two with 2 (R + 1) cap <= cand_budget (what the re-rank takes per row beside the overflow list) and raised
+// while a run would pass the 32-bit offsets of the tile DMA (run tiles x 32 x dp x 2 bytes < 2^32); a run that spans the hole is
+// two entries.  Slots number a block's entries in tile order.  Entries come longest run first.  *lists_out: 2 x the largest entry
+// count of a block, or -1 when a run cannot be made short enough (the table is then empty).
+std::vector<int32_t> cross_seg16_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int qt, int dp, int cap, int cand_budget,
+                                       int col_splits, int* lists_out) {
+  const int64_t n = S > 0 ? x_ptr[S] : 0, m = S > 0 ? y_ptr[S] : 0;
+  const int64_t T = (m + 255) / 256 * 8;
+  int max_r = 1;
+  while (2 * (2 * max_r + 1) * cap <= cand_budget) max_r <<= 1;
+  const int64_t max_run = (((int64_t)1 << 32) - 1) / ((int64_t)64 * dp);
+  struct Block { int64_t h0, h1, w0, w1; };
+  std::vector<Block> blocks((size_t)((n + qt - 1) / qt));
+  int64_t pairs = 0, g = 0;
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    const int64_t r0 = (int64_t)b * qt, r1 = std::min<int64_t>(r0 + qt, n);
+    while (x_ptr[g + 1] <= r0) ++g;                      // segment of the block's first row (empty segments hold no row)
+    int64_t gl = g;
+    while (x_ptr[gl + 1] <= r1 - 1) ++gl;                // ... and of its last
+    const int64_t ulo = y_ptr[g], uhi = y_ptr[gl + 1];
+    Block& B = blocks[b];
+    B.h0 = B.h1 = 0;
+    if (gl == g) {
+      B.h0 = (ulo + 31) / 32;
+      B.h1 = uhi == m ? T : uhi / 32;
+      if (B.h1 < B.h0) B.h1 = B.h0;
+    }
+    B.w0 = ulo / 32; B.w1 = uhi > ulo ? (uhi + 31) / 32 : B.w0;
+    pairs += T - (B.h1 - B.h0);
+  }
+  const int64_t per = std::max<int64_t>(1, (pairs + 1023) / 1024);
+  std::vector<int32_t> tab;
+  int most = 1;
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    const Block& B = blocks[b];
+    const int64_t r0 = (int64_t)b * qt, hole = B.h1 - B.h0, adm = T - hole;
+    if (adm <= 0) continue;
+    // automatic: no run shorter than kMinRun tiles.  The workgroups of a row block exchange thresholds every 64 tiles (sync_seed), so
+    // a shorter run never imports one on its way and proves its own from a few hundred columns only: measured at 2001 rows, d = 600,
+    // k = 20 with bf16 operands, sixteen runs of four tiles flagged 286 rows for the exact rescan, one run none.
+    constexpr int64_t kMinRun = 64;
+    const int64_t want = col_splits > 0 ? col_splits : std::min((adm + per - 1) / per, std::max<int64_t>(1, adm / kMinRun));
+    int R = 1;
+    while (2 * R <= want && 2 * R <= adm && 2 * R <= max_r) R <<= 1;
+    while ((adm + R - 1) / R > max_run && 2 * R <= adm && 2 * R <= max_r) R <<= 1;
+    const int64_t tps = (adm + R - 1) / R;
+    if (tps > max_run) { if (lists_out) *lists_out = -1; return {}; }
+    int slot = 0;
+    auto entry = [&](int64_t t0, int64_t t1) {
+      if (t0 >= t1) return;
+      int64_t w0 = std::max(B.w0, t0), w1 = std::min(B.w1, t1);
+      if (w0 >= w1) w0 = w1 = t0;
+      const int32_t e[8] = {(int32_t)r0, (int32_t)r0, (int32_t)std::min<int64_t>(qt, n - r0), (int32_t)t0, (int32_t)t1, slot++, (int32_t)w0, (int32_t)w1};
+      tab.insert(tab.end(), e, e + 8);
+    };
+    for (int64_t a0 = 0; a0 < adm; a0 += tps) {
+      const int64_t a1 = std::min(a0 + tps, adm);          // admissible tile a is tile a below the hole and a + hole above it
+      if (hole == 0 || a1 <= B.h0) entry(a0, a1);
+      else if (a0 >= B.h0) entry(a0 + hole, a1 + hole);
+      else { entry(a0, B.h0); entry(B.h1, a1 + hole); }
+    }
+    if (slot > most) most = slot;
+  }
+  const size_t entries = tab.size() / 8;
+  std::vector<size_t> order(entries);
+  for (size_t i = 0; i < entries; ++i) order[i] = i;
+  auto len = [&](size_t i) { return tab[i * 8 + 4] - tab[i * 8 + 3]; };
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return len(a) > len(b); });
+  std::vector<int32_t> sorted(tab.size());
+  for (size_t i = 0; i < entries; ++i) std::copy_n(tab.begin() + order[i] * 8, 8, sorted.begin() + i * 8);
+  if (lists_out) *lists_out = 2 * most;
+  return sorted;
+}
+
 // One workgroup per entry of the device copy `sched` of that table.  p.Xp / p.Yp: the f32 images of ALL rows of X and Y; p.rx /
 // p.cy, the floors, the positions and the lists L (L.lists = 2 x the table's largest range count) cover all rows; p.kk, the
 // metric and the floors are those of launch_scan_f32.  Counts of the slots a segment does not use must be zero already.
 // cross: `sched` is a cross_seg_table and the kernel is the XSEG flavour (no combined key).
 int launch_scan_f32_seg(const ScanProblem& p, const CandLists& L, const int64_t* sched, int64_t grid, hipStream_t s, bool cross) {
   if (grid <= 0) return MMF_OK;
-  if (p.row_ids || !sched || L.lists < 2 || (L.lists & 1)) { set_error("scan_f32_seg: needs a work table, list pairs and no gathered rows"); return MMF_E_INTERNAL; }
+  // (gathered rows — p.row_ids: the table's rows are positions of p.Xp and of the lists, position q is row row_ids[q] of X — go with
+  //  the cross flavour only: the flagged rows of mmf_simtopk_cross_segments_fast)
+  if ((p.row_ids && !cross) || !sched || L.lists < 2 || (L.lists & 1)) { set_error("scan_f32_seg: needs a work table, list pairs and no gathered rows"); return MMF_E_INTERNAL; }
   ScanF32Args a{};
   a.Xp = p.Xp; a.Yp = p.Yp; a.n = p.n; a.m = p.m; a.dpad = prep_f32_dim(p.d);
-  a.rx = p.rx; a.cy = p.cy; a.row_ids = nullptr; a.n_rows = p.n;
+  a.rx = p.rx; a.cy = p.cy; a.row_ids = cross ? p.row_ids : nullptr; a.n_rows = p.n;
   a.neg_lambda = -p.lambda; a.kk = p.kk; a.col_splits = L.lists / 2; a.tiles_per_split = 0;
   a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.overflow = L.overflow;
   a.floor_key = p.floor_key; a.floor_id = p.floor_id;
