@@ -121,6 +121,11 @@ CROSS_SEG_EXPORTS = ["mmf_simtopk_cross_segments", "mmf_cross_segments_table"]
 # were flagged for the exact rescan); mmf_cross_segments_fast_table is host-only.  Pinned by tests/test_cross_segments_fast_cpu.py.
 CROSS_SEG16_EXPORTS = ["mmf_simtopk_cross_segments_fast", "mmf_cross_segments_fast_table"]
 
+# The cross-segment top-k on the wide 16-bit scan (include/ext/mmf_hg_cross_segw.h): an addition to ABI version 3 in
+# a header of its own.  mmf_simtopk_cross_segments_wide synchronises as its narrow twin does (once per call; once more when rows
+# were flagged); mmf_cross_segments_wide_table is host-only.  Pinned by tests/test_cross_segments_wide_cpu.py.
+CROSS_SEGW_EXPORTS = ["mmf_simtopk_cross_segments_wide", "mmf_cross_segments_wide_table"]
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -211,6 +216,10 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_cross_segments_fast.restype = ci
     L.mmf_cross_segments_fast_table.argtypes = [vp, vp, i64, i64, ci, ci, vp, i64, ctypes.POINTER(ci)]
     L.mmf_cross_segments_fast_table.restype = i64
+    L.mmf_simtopk_cross_segments_wide.argtypes = list(L.mmf_simtopk_cross_segments_fast.argtypes)
+    L.mmf_simtopk_cross_segments_wide.restype = ci
+    L.mmf_cross_segments_wide_table.argtypes = list(L.mmf_cross_segments_fast_table.argtypes)
+    L.mmf_cross_segments_wide_table.restype = i64
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

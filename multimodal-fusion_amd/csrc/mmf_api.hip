@@ -3223,6 +3223,183 @@ int64_t mmf_cross_segments_fast_table(const int64_t* x_ptr_host, const int64_t* 
   return grid;
 }
 
+// ---- cross-segment top-k on the wide 16-bit scan (include/ext/mmf_hg_cross_segw.h) -------------------------------
+// run_cross_segments_fast for 1024 < d <= 4096: the plain 16-bit images at the wide scan's padded dim, ONE table-driven launch of the
+// wide scan whose epilogue masks, per query row, the columns of the row's own segment (launch_scan_b16w_xseg; its threshold union
+// when a block has several entries), the audit, one re-rank over all rows, one host synchronisation.  Flagged rows: cross_flagged.
+}  // extern "C"
+
+namespace mmf {
+
+// r: checked, begun, n > 0, precision MMF_PREC_FAST or _FAST_BF16, (d, k) served by the wide scan.
+static int run_cross_segments_wide(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts) {
+  const hipStream_t s = r.call.s;
+  const int64_t n = r.n, m = r.m;
+  const bool profile = r.profile, f16 = (r.precision == MMF_PREC_FAST);
+  const int dp = scan_b16w_dp(r.d), bcap = scan_b16w_cap(r.kk);
+  int lists = 2;
+  const std::vector<int32_t> sched = cross_segw_table(xp, yp, S, bcap, kCross16Budget, opts ? opts->col_splits : 0, &lists);
+  const int64_t grid = (int64_t)sched.size() / 8;
+  const int64_t n_pad = (n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256;
+  // per row of X: first row and row count of the columns it may not take; padding rows exclude nothing
+  std::vector<uint32_t> bounds((size_t)n_pad * 2, 0u);
+  for (int64_t g = 0; g < S; ++g)
+    for (int64_t i = xp[g]; i < xp[g + 1]; ++i) { bounds[2 * i] = (uint32_t)yp[g]; bounds[2 * i + 1] = (uint32_t)(yp[g + 1] - yp[g]); }
+
+  // the wide kernel's sizes: its list capacity, no id scratch; the overflow lists stay zeroed and unused (select reads them as empty)
+  const size_t need = ws_bytes(n, 4) + (self ? 0 : ws_bytes(m, 4)) + FlagBlock::bytes(n) + ws_bytes(4, 4) + HalfImage::bytes(n_pad, dp) +
+                      (self ? 0 : HalfImage::bytes(m_pad, dp)) + ws_bytes(sched.size(), 4) + ws_bytes(bounds.size(), 4) +
+                      b16_lists_bytes(n, lists, bcap) + ws_bytes(2 * (size_t)n, 4) + ws_bytes(select_order_bytes(n), 1);
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* rx = ws.take<float>(n);
+  float* cy = self ? rx : ws.take<float>(m);
+  FlagBlock flags;
+  flags.carve(ws, n);
+  MMF_TRY(flags.zero(s));
+  uint32_t* max_n = ws.take<uint32_t>(4);
+  HalfImage Q, C;
+  Q.carve(ws, n_pad, dp);
+  if (self) C = Q; else C.carve(ws, m_pad, dp);
+  int32_t* d_sched = ws.take<int32_t>(sched.size());
+  uint32_t* d_bounds = ws.take<uint32_t>(bounds.size());
+  const CandLists L = carve_b16_lists(ws, n, lists, bcap);
+  int32_t* seed = ws.take<int32_t>(2 * (size_t)n);
+  char* order_scratch = ws.take<char>(select_order_bytes(n));
+
+  EventTimer t_prep, t_scan, t_sel, t_fb;
+  MMF_TRY(t_prep.start(profile, s));
+  MMF_HIP(hipMemsetAsync(max_n, 0, 16, s));
+  MMF_TRY(launch_row_scalars(r.X, n, r.d, r.dtype, r.metric, rx, max_n, s));
+  if (!self) MMF_TRY(launch_row_scalars(r.Y, m, r.d, r.dtype, r.metric, cy, max_n, s));
+  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
+  MMF_TRY(upload_table(s, d_bounds, bounds.data(), bounds.size() * 4));
+  MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
+  if (!self) MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
+  MMF_TRY(launch_prep_half({r.Y, m, r.d, r.dtype, r.metric, cy, max_n}, C, dp, f16, s));
+  if (!self) MMF_TRY(launch_prep_half({r.X, n, r.d, r.dtype, r.metric, rx, max_n}, Q, dp, f16, s));
+  MMF_TRY(t_prep.stop(s));
+
+  MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));   // the slots a block's entries do not use stay empty
+  MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
+  MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
+  MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n * 8, s));
+  ScanB16Panel pn;
+  pn.seed = seed; pn.seed_stride = n; pn.share = 0;
+  MMF_TRY(t_scan.start(profile, s));
+  const ScanB16Problem sp(Q, C, n, m, m_pad, dp, r.d, f16, r.metric, r.kk);
+  MMF_TRY(launch_scan_b16w_xseg(sp, d_sched, grid, d_bounds, lists, L, pn, s));
+  MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
+  MMF_TRY(t_scan.stop(s));
+
+  SelectProblem q = r.select();
+  q.rx = rx; q.cy = cy;
+  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = r.stats ? flags.cand_total : nullptr;
+  q.two_pass = true;
+  q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
+  MMF_TRY(t_sel.start(profile, s));
+  MMF_TRY(launch_select(q, L, s));
+  MMF_TRY(t_sel.stop(s));
+  MMF_TRY(flags.read(r.stats != nullptr, s));   // the call's one synchronisation when no row is flagged
+  const uint32_t* h_fail4 = flags.h_fail4;
+  const int64_t fallback_rows = h_fail4[0];
+  MMF_TRY(t_fb.start(profile && fallback_rows > 0, s));
+  if (fallback_rows > 0) {
+    std::vector<int32_t> rows((size_t)fallback_rows);
+    MMF_HIP(hipMemcpyAsync(rows.data(), flags.fail_rows, (size_t)fallback_rows * 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));               // only on this branch: the fail list, now that its length is known
+    std::sort(rows.begin(), rows.end());
+    MMF_TRY(cross_flagged(r, rx, cy, rows, xp, yp, S));
+  }
+  MMF_TRY(t_fb.stop(s));
+  const int64_t overflow_rows = h_fail4[1] < (uint32_t)fallback_rows ? h_fail4[1] : fallback_rows;
+  fill_stats(r.stats, r.precision, lists / 2, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback_rows, overflow_rows,
+             fallback_rows - overflow_rows, flags.h_tot);
+  return MMF_OK;
+}
+
+}  // namespace mmf
+
+extern "C" {
+
+int mmf_simtopk_cross_segments_wide(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric, float lambda,
+                                    int k, const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_segments, int64_t* out_idx,
+                                    float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id,
+                                    void* hip_stream) {
+  const char* who = "simtopk_cross_segments_wide";
+  const bool self = (Y == nullptr);
+  if (self) { Y = X; m = n; y_ptr_host = x_ptr_host; }
+  Request r{Call(who, device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, 0, 0, 0,
+            out_idx, out_val, stats, opts && opts->profile};
+  r.wide_ok = true;
+  MMF_TRY(r.call.on_device());
+  if (n < 0 || m < 0 || d < 1) { set_error("%s: bad shape n=%lld m=%lld d=%lld", who, (long long)n, (long long)m, (long long)d); return MMF_E_INVALID; }
+  if (in_dtype != MMF_F32 && in_dtype != MMF_BF16 && in_dtype != MMF_F16) { set_error("%s: bad in_dtype %d", who, in_dtype); return MMF_E_INVALID; }
+  if (n > 0 && !X) { set_error("%s: X is NULL", who); return MMF_E_INVALID; }
+  if (n >= (int64_t)1 << 31 || m >= (int64_t)1 << 31) { set_error("%s: n and m must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  // AUTO means FAST where the WIDE scan serves (d, k) and the exact driver elsewhere — also where the narrow 16-bit scan would
+  // serve: routing between the two 16-bit entries is the caller's; settled here, before any device call
+  int prec = opts ? opts->precision : MMF_PREC_AUTO;
+  const bool served = k >= 1 && scan_b16w_supported(d, k);
+  if (prec == MMF_PREC_AUTO) prec = served ? MMF_PREC_FAST : MMF_PREC_EXACT;
+  MMF_TRY(r.check(prec, true, [&] {
+    MMF_TRY(check_offsets(who, "x_ptr", x_ptr_host, n_segments, 0, 0, n));
+    MMF_TRY(check_offsets(who, "y_ptr", y_ptr_host, n_segments, 0, 0, m));
+    if (m > 0 && !Y) { set_error("%s: Y is NULL", who); return MMF_E_INVALID; }
+    MMF_TRY(check_pow2_splits(who, opts));
+    if (prec != MMF_PREC_EXACT && prec != MMF_PREC_FAST && prec != MMF_PREC_FAST_BF16) {
+      set_error("%s: bad precision %d", who, prec);
+      return MMF_E_INVALID;
+    }
+    if (opts && opts->select_wait_event) { set_error("%s: select_wait_event is not supported", who); return MMF_E_UNSUPPORTED; }
+    if (prec != MMF_PREC_EXACT && !served) {
+      set_error("%s: MMF_PREC_FAST does not support d = %lld, k = %d (the wide scan serves 1024 < d <= 4096 with k <= 20)", who, (long long)d, k);
+      return MMF_E_UNSUPPORTED;
+    }
+    if (n > 0 && (!out_idx || !out_val)) { set_error("%s: NULL output", who); return MMF_E_INVALID; }
+    for (int64_t g = 0; g < n_segments; ++g) {
+      const int64_t own = y_ptr_host[g + 1] - y_ptr_host[g];
+      if (x_ptr_host[g + 1] > x_ptr_host[g] && m - own < k) {
+        set_error("%s: segment %lld has %lld admissible columns (m = %lld minus its own %lld rows of Y), k = %d needs at least %d", who,
+                  (long long)g, (long long)(m - own), (long long)m, (long long)own, k, k);
+        return MMF_E_INVALID;
+      }
+    }
+    return MMF_OK;
+  }));
+  if (stats) stats->near_rows = -1;
+  if (n == 0) return MMF_OK;
+  if (r.precision == MMF_PREC_EXACT) return run_segmented_exact(r, self, x_ptr_host, y_ptr_host, n_segments, opts, nullptr, 0, 0.0f, true);
+  return run_cross_segments_wide(r, self, x_ptr_host, y_ptr_host, n_segments, opts);
+}
+
+int64_t mmf_cross_segments_wide_table(const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_segments, int64_t d, int k,
+                                      int col_splits, int32_t* table_host, int64_t capacity, int* lists_out) {
+  const char* who = "cross_segments_wide_table";
+  if (!y_ptr_host) y_ptr_host = x_ptr_host;
+  MMF_TRY(check_offsets(who, "x_ptr", x_ptr_host, n_segments, 0, 0, kAnyRows));
+  MMF_TRY(check_offsets(who, "y_ptr", y_ptr_host, n_segments, 0, 0, kAnyRows));
+  if (k < 1) { set_error("%s: k must be >= 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (col_splits < 0 || (col_splits & (col_splits - 1)) != 0) { set_error("%s: col_splits must be 0 or a power of two (got %d)", who, col_splits); return MMF_E_INVALID; }
+  if (d < 1 || !scan_b16w_supported(d, k)) {
+    set_error("%s: the wide 16-bit scan does not serve d = %lld, k = %d", who, (long long)d, k);
+    return MMF_E_UNSUPPORTED;
+  }
+  if ((n_segments > 0 ? x_ptr_host[n_segments] : 0) >= (int64_t)1 << 31 || (n_segments > 0 ? y_ptr_host[n_segments] : 0) >= (int64_t)1 << 31) {
+    set_error("%s: n and m must be < 2^31", who);
+    return MMF_E_UNSUPPORTED;
+  }
+  int lists = 2;
+  const std::vector<int32_t> tab = cross_segw_table(x_ptr_host, y_ptr_host, n_segments, scan_b16w_cap(k), kCross16Budget, col_splits, &lists);
+  const int64_t grid = (int64_t)tab.size() / 8;
+  if (table_host) {
+    if (capacity < grid) { set_error("%s: table of %lld entries needed", who, (long long)grid); return MMF_E_INVALID; }
+    if (grid > 0) memcpy(table_host, tab.data(), tab.size() * 4);
+  }
+  if (lists_out) *lists_out = lists;
+  return grid;
+}
+
 int mmf_simtopk_combined_segmented_exact(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h,
                                          float lambda_g, int k, int exclude_self, const int64_t* ptr_host, int64_t n_segments,
                                          int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats,

@@ -20,6 +20,7 @@
 #include "../../include/ext/mmf_hg_kmeans_ragged.h"
 #include "../../include/ext/mmf_hg_cross_seg.h"
 #include "../../include/ext/mmf_hg_cross_seg16.h"
+#include "../../include/ext/mmf_hg_cross_segw.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -270,6 +271,10 @@ std::vector<int64_t> cross_seg_table(const int64_t* x_ptr, const int64_t* y_ptr,
 // when a run cannot be kept inside the tile DMA's 32-bit offsets
 std::vector<int32_t> cross_seg16_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int qt, int dp, int cap, int cand_budget,
                                        int col_splits, int* lists_out);
+// the wide 16-bit cross-segment scan: the same rule over row blocks of 128 rows of X and the 128-row tiles of the
+// plain image of Y, in the wide scan's entry layout; automatic runs fill 256 workgroups and are at least 8 tiles long
+std::vector<int32_t> cross_segw_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int cap, int cand_budget, int col_splits,
+                                      int* lists_out);
 // cross: `sched` is a cross_seg_table, the kernel masks each entry's excluded range (no combined key); p.row_ids may then name
 // gathered rows (the table's rows are positions of p.Xp and of the lists)
 int launch_scan_f32_seg(const ScanProblem& p, const CandLists& L, const int64_t* sched, int64_t grid, hipStream_t s, bool cross = false);
@@ -406,6 +411,10 @@ int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L
 // largest number of column ranges of a segment (a power of two).
 int launch_scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, int lists, const CandLists& L, const ScanB16Panel& pn,
                          hipStream_t s);
+// Cross-segment form: plain images on both sides, `sched` a device copy of cross_segw_table, `bounds` [n_pad][2]
+// the excluded column range (first, count) of every query row, lists == L.lists == the table's list count (any even number).
+int launch_scan_b16w_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, int lists, const CandLists& L,
+                          const ScanB16Panel& pn, hipStream_t s);
 
 // mmf_scan_b16c.hip: the 16-bit scan of the combined key eh + eg (mmf_simtopk_combined_fast), 1 <= d <= 4096,
 // k + self <= 20: the wide scan's structure with the position term formed in the epilogue.  One MMF_RBF operand image scanned

@@ -127,6 +127,9 @@ struct ScanB16WArgs {
   // SINK kernels only: the rows' overflow lists (CandLists; SpillSink)
   uint32_t* spill_cnt; uint32_t* spill_ids; int spill_cap; int spill_stacks;
   int32_t* sunk;             // counter form: [>= n_rows] best key written to the row's overflow list (wide_enc; atomicMax), or nullptr
+  // XSEG kernels only (launch_scan_b16w_xseg): [n_pad][2] per query row, first row and row count of the columns the row may not
+  // take (its own segment's rows of Y); rows of the padding exclude nothing
+  const uint32_t* bounds;
 };
 
 // One entry of the segmented work table: a workgroup = one row block of one segment against one column range of that segment.
@@ -142,6 +145,11 @@ enum {
   WSEG_SLOT = 6,    // first list slot of this range (2 x split)
   WSEG_ENTRY = 8
 };
+// Work table entry of the cross-segment scan (cross_segw_table; same entry size, words 0 .. 4 and 6 as above): both images are the
+// plain ones of launch_prep_half, so the query position IS the row of X (words 0 and 1 are equal), the id offset is zero, and its
+// word and the spare one carry the entry's mask window [w0, w1), in tiles of the candidate image: the tiles of [T0, T1) that hold a
+// column some row of the block may not take (w0 == w1: none).
+enum { WXSEG_W0 = 5, WXSEG_W1 = 7 };
 
 // The lane-private list: entry e of thread t at keys[e * NT + t] / ids[e * NT + t] (LaneList's layout), approximate keys.
 template <int CAP, int NT, bool SINK = false>
@@ -300,7 +308,12 @@ constexpr size_t scan_b16w_lds(int cap) { return (size_t)2 * W_STAGEB + (size_t)
 // SEG (segmented calls, launch_scan_b16w_seg): the workgroup's row block, column range, id offset and list slot come from the
 // work table a.sched instead of blockIdx / col_splits; everything else is shared.  SINK (plain launches only): crowded lists
 // write to the rows' overflow lists (header, "Overflow lists").
-template <bool F16, int CAP, bool SEG = false, bool SINK = false>
+// XSEG (implies SEG, excludes SINK; mmf_simtopk_cross_segments_wide): every row against the columns OUTSIDE its own
+// segment, on the plain images.  A row block is 128 consecutive rows of X whatever the segments; the table leaves out the tiles every
+// row of the block excludes, and on the tiles of the entry's mask window the epilogue sets the accumulators of a query's excluded
+// columns (a.bounds) to -inf before anything reads them: such a value is below every threshold (the first one is -FLT_MAX), so it
+// reaches neither the tile maxima's test, nor a list, nor proven / lost / seed — exactly like the -inf bias of a padding column.
+template <bool F16, int CAP, bool SEG = false, bool SINK = false, bool XSEG = false>
 __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   char* stages = smem;                                                   // [2][W_STAGEB]
@@ -322,11 +335,14 @@ __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
   int64_t row0 = 0;                             // SEG: row of X of the block's first query
   int nq = W_QT;                                // SEG: real queries of the block
   uint32_t id_off = 0;                          // SEG: column of the candidate image -> row of Y
+  int64_t xw0 = 0, xw1 = 0;                     // XSEG: the entry's mask window, in tiles of the candidate image
+  static_assert(!XSEG || (SEG && !SINK), "the cross-segment mask rides on the table-driven schedule, without overflow lists");
   if constexpr (SEG) {
     const int32_t* e = a.sched + (size_t)blockIdx.x * WSEG_ENTRY;
     q0 = e[WSEG_QPOS]; row0 = e[WSEG_ROW0]; nq = e[WSEG_NQ];
     t_begin = e[WSEG_T0]; t_end = e[WSEG_T1]; id_off = (uint32_t)e[WSEG_IDOFF]; slot = e[WSEG_SLOT];
     if (t_begin > t_end) t_begin = t_end;
+    if constexpr (XSEG) { id_off = 0u; xw0 = e[WXSEG_W0]; xw1 = e[WXSEG_W1]; }
   } else {
     const int split = blockIdx.x % a.col_splits;
     const int64_t rb = blockIdx.x / a.col_splits;
@@ -467,6 +483,26 @@ __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
     }
 
     if (kc == nkc - 1) {       // the whole d is in: one epilogue per macro tile, a 32-candidate sub-tile at a time
+      if constexpr (XSEG) {
+        // The columns a query may not take.  The window test is wave-uniform and almost always false (a block inside one segment
+        // meets its mask on the two tiles that straddle the segment's bounds); the bounds of the lane's two queries — c16 and
+        // c16 + 16 of the wave — are loaded inside the branch, so the tile loop carries nothing for them.  acc starts from the bias
+        // again at the next tile.
+        if (__builtin_expect(xw0 <= ct && ct < xw1, 0)) {
+          const uint32_t* bq = a.bounds + 2 * (q0 + 32 * wave + c16);
+          const uint32_t lo0 = bq[0], len0 = bq[1], lo1 = bq[32], len1 = bq[33];
+          const uint32_t col0 = (uint32_t)(ct * W_CT) + 4 * g;
+#pragma unroll
+          for (int cb = 0; cb < 8; ++cb) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const uint32_t col = col0 + 16 * cb + j;      // acc[cb][qb][j]: candidate 16 cb + 4 g + j of the tile
+              if (col - lo0 < len0) acc[cb][0][j] = kNegInf;
+              if (col - lo1 < len1) acc[cb][1][j] = kNegInf;
+            }
+          }
+        }
+      }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const f32x4& p0 = acc[2 * t][0]; const f32x4& r0 = acc[2 * t + 1][0];
@@ -576,7 +612,7 @@ __global__ __launch_bounds__(256) void wide_seed_union_kernel(const uint32_t* ca
   if (sunk && sunk[row] < settled) spill_cnt[row] = 0u;   // (no key written: the count is 0 already)
 }
 
-template <int CAP, bool SEG = false, bool SINK = false>
+template <int CAP, bool SEG = false, bool SINK = false, bool XSEG = false>
 int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) {
   const size_t lds = scan_b16w_lds(CAP);
   auto go = [&](auto kern) -> int {
@@ -589,6 +625,10 @@ int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) 
     if (f16) return go(scan_b16w_kernel<true, CAP, SEG, true>);
     return go(scan_b16w_kernel<false, CAP, SEG, true>);
   }
+  if constexpr (XSEG) {
+    if (f16) return go(scan_b16w_kernel<true, CAP, true, false, true>);
+    return go(scan_b16w_kernel<false, CAP, true, false, true>);
+  }
   if (f16) return go(scan_b16w_kernel<true, CAP, SEG>);
   return go(scan_b16w_kernel<false, CAP, SEG>);
 }
@@ -600,6 +640,48 @@ int scan_b16w_cap(int kk) { return kk <= 11 ? W_CAP_SMALL : W_CAP_BIG; }
 int scan_b16w_dp(int64_t d) { return (int)((d + 127) / 128 * 128); }
 int scan_b16w_queries_per_block() { return W_QT; }
 int scan_b16w_col_tile() { return W_CT; }
+
+// Cross-segment scan (mmf_simtopk_cross_segments_wide): one workgroup per entry of `sched`, a device copy of
+// cross_segw_table ([grid][8] int32: WSEG_* words 0 .. 4 and 6, WXSEG_W0 / _W1).  Both images are the plain ones of launch_prep_half
+// (p.n_rows rows of X, m_pad rows of Y in whole tiles); `bounds` is [n_pad][2], the excluded column range (first, count) of every
+// query row, n_pad covering whole 128-row blocks.  `lists` == L.lists == 2 x the largest entry count of a row block — any even
+// number: a run cut by a hole is two entries — and a block with fewer entries leaves the rest of its rows' lists empty (the caller
+// zeroes the counts).  With more than one pair the lists carry keys and margins and wide_seed_union_kernel settles every row's
+// threshold over all of its entries, as in the other launchers.  No overflow lists: a crowded row is flagged.
+int launch_scan_b16w_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, int lists, const CandLists& L,
+                          const ScanB16Panel& pn, hipStream_t s) {
+  if (grid <= 0 || p.n_rows <= 0) return MMF_OK;
+  if (!scan_b16w_supported(p.d, p.kk) || p.dp != scan_b16w_dp(p.d)) {
+    set_error("scan_b16w_xseg: d = %lld (padded %d), k = %d outside 1024 < d <= 4096, k <= 20", (long long)p.d, p.dp, p.kk);
+    return MMF_E_INTERNAL;
+  }
+  if (lists < 2 || (lists & 1)) { set_error("scan_b16w_xseg: %d lists per row are no whole number of pairs", lists); return MMF_E_INTERNAL; }
+  if (!sched || !bounds) { set_error("scan_b16w_xseg: work table or mask bounds missing"); return MMF_E_INTERNAL; }
+  if (!pn.seed) { set_error("scan_b16w_xseg: threshold buffers missing"); return MMF_E_INTERNAL; }
+  if (pn.seed_stride < p.n_rows) { set_error("scan_b16w_xseg: threshold buffers shorter than the rows"); return MMF_E_INTERNAL; }
+  if (pn.list_base != 0 || pn.seg_len != 0 || pn.id_off != 0) { set_error("scan_b16w_xseg: no paneled form"); return MMF_E_INTERNAL; }
+  if (lists != L.lists) { set_error("scan_b16w_xseg: %d lists per row for a table of %d", L.lists, lists); return MMF_E_INTERNAL; }
+  if (L.cap != scan_b16w_cap(p.kk)) { set_error("scan_b16w_xseg: list capacity %d, expected %d", L.cap, scan_b16w_cap(p.kk)); return MMF_E_INTERNAL; }
+  if (lists > 2 && (!L.keys || !L.margin)) { set_error("scan_b16w_xseg: several entries per block need the lists' keys and margins"); return MMF_E_INTERNAL; }
+  if (p.m_pad % W_CT != 0) { set_error("scan_b16w_xseg: candidate image of %lld rows is no whole number of tiles", (long long)p.m_pad); return MMF_E_INTERNAL; }
+  if (p.m >= (int64_t(1) << 31)) { set_error("scan_b16w_xseg: column ids need m < 2^31"); return MMF_E_INTERNAL; }
+  ScanB16WArgs a{};
+  a.ZQ = p.ZQ; a.ZC = p.ZC; a.cb = p.cb; a.q_zn = p.q_zn; a.q_rn = p.q_rn; a.q_un = p.q_un; a.maxima = p.maxima;
+  a.n_rows = p.n_rows; a.kk = p.kk; a.metric = p.metric; a.d = (int)p.d; a.dp = p.dp;
+  a.tiles_total = p.m_pad / W_CT; a.tiles_per_split = a.tiles_total; a.col_splits = 1;   // unused: the table carries the ranges
+  a.lists_total = L.lists; a.list_base = 0;
+  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride;
+  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.cand_keys = L.keys; a.margin_out = L.margin;
+  a.sched = sched; a.bounds = bounds;
+  MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, true, false, true>(a, p.f16, grid, s))
+                               : (launch_b16w_t<W_CAP_BIG, true, false, true>(a, p.f16, grid, s)));
+  if (lists > 2) {
+    wide_seed_union_kernel<<<dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s>>>(L.cnt, L.keys, L.margin, L.lists, L.cap, p.kk, pn.seed,
+                                                                                     p.n_rows, nullptr, nullptr);
+    MMF_LAUNCH_CHECK();
+  }
+  return MMF_OK;
+}
 
 // col_splits must be a power of two.  Lists are indexed by query position; pn: the threshold buffers (no panels, no shared
 // thresholds on this path).  With more than one split L.keys / L.margin must be set: wide_seed_union_kernel reads them.

@@ -632,6 +632,70 @@ std::vector<int64_t> cross_seg_table(const int64_t* x_ptr, const int64_t* y_ptr,
   return sorted;
 }
 
+namespace {
+
+// Row block geometry shared by the two 16-bit cross-segment tables (cross_seg16_table, cross_segw_table): hole [h0, h1) and mask
+// window [w0, w1) of every block of qt rows of X, in tiles of `tile` rows of the plain image of Y (T tiles).
+struct CrossBlock { int64_t h0, h1, w0, w1; };
+std::vector<CrossBlock> cross_blocks(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int qt, int tile, int64_t T) {
+  const int64_t n = S > 0 ? x_ptr[S] : 0, m = S > 0 ? y_ptr[S] : 0;
+  std::vector<CrossBlock> blocks((size_t)((n + qt - 1) / qt));
+  int64_t g = 0;
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    const int64_t r0 = (int64_t)b * qt, r1 = std::min<int64_t>(r0 + qt, n);
+    while (x_ptr[g + 1] <= r0) ++g;                      // segment of the block's first row (empty segments hold no row)
+    int64_t gl = g;
+    while (x_ptr[gl + 1] <= r1 - 1) ++gl;                // ... and of its last
+    const int64_t ulo = y_ptr[g], uhi = y_ptr[gl + 1];
+    CrossBlock& B = blocks[b];
+    B.h0 = B.h1 = 0;
+    if (gl == g) {
+      B.h0 = (ulo + tile - 1) / tile;
+      B.h1 = uhi == m ? T : uhi / tile;
+      if (B.h1 < B.h0) B.h1 = B.h0;
+    }
+    B.w0 = ulo / tile; B.w1 = uhi > ulo ? (uhi + tile - 1) / tile : B.w0;
+  }
+  return blocks;
+}
+
+// The T - hole admissible tiles of block B cut into R runs of ceil(A / R); a run that spans the hole is two entries.  Calls
+// entry(t0, t1, w0, w1) in tile order ([w0, w1): the entry's part of the mask window, w0 == w1 == t0 when it has none) and returns
+// the number of entries.
+template <class Entry>
+int cross_block_runs(const CrossBlock& B, int64_t T, int R, Entry entry) {
+  const int64_t hole = B.h1 - B.h0, adm = T - hole, tps = (adm + R - 1) / R;
+  int count = 0;
+  auto one = [&](int64_t t0, int64_t t1) {
+    if (t0 >= t1) return;
+    int64_t w0 = std::max(B.w0, t0), w1 = std::min(B.w1, t1);
+    if (w0 >= w1) w0 = w1 = t0;
+    entry(t0, t1, w0, w1);
+    ++count;
+  };
+  for (int64_t a0 = 0; a0 < adm; a0 += tps) {
+    const int64_t a1 = std::min(a0 + tps, adm);          // admissible tile a is tile a below the hole and a + hole above it
+    if (hole == 0 || a1 <= B.h0) one(a0, a1);
+    else if (a0 >= B.h0) one(a0 + hole, a1 + hole);
+    else { one(a0, B.h0); one(B.h1, a1 + hole); }
+  }
+  return count;
+}
+
+// entries of 8 int32 words, first / end tile in words 3 / 4: longest run first (stable)
+std::vector<int32_t> longest_run_first(const std::vector<int32_t>& tab) {
+  const size_t entries = tab.size() / 8;
+  std::vector<size_t> order(entries);
+  for (size_t i = 0; i < entries; ++i) order[i] = i;
+  auto len = [&](size_t i) { return tab[i * 8 + 4] - tab[i * 8 + 3]; };
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return len(a) > len(b); });
+  std::vector<int32_t> sorted(tab.size());
+  for (size_t i = 0; i < entries; ++i) std::copy_n(tab.begin() + order[i] * 8, 8, sorted.begin() + i * 8);
+  return sorted;
+}
+
+}  // namespace
+
 // The work table of the 16-bit cross-segment scan (mmf_simtopk_cross_segments_fast): [entries][8] int32, the
 // words of the 16-bit scan's SEG entry with the id-offset word (zero on the plain images) carrying the list slot —
 //   first row of the block (operand position = list row), the same again, real queries, first and end tile, list slot, and the
@@ -655,31 +719,15 @@ std::vector<int32_t> cross_seg16_table(const int64_t* x_ptr, const int64_t* y_pt
   int max_r = 1;
   while (2 * (2 * max_r + 1) * cap <= cand_budget) max_r <<= 1;
   const int64_t max_run = (((int64_t)1 << 32) - 1) / ((int64_t)64 * dp);
-  struct Block { int64_t h0, h1, w0, w1; };
-  std::vector<Block> blocks((size_t)((n + qt - 1) / qt));
-  int64_t pairs = 0, g = 0;
-  for (size_t b = 0; b < blocks.size(); ++b) {
-    const int64_t r0 = (int64_t)b * qt, r1 = std::min<int64_t>(r0 + qt, n);
-    while (x_ptr[g + 1] <= r0) ++g;                      // segment of the block's first row (empty segments hold no row)
-    int64_t gl = g;
-    while (x_ptr[gl + 1] <= r1 - 1) ++gl;                // ... and of its last
-    const int64_t ulo = y_ptr[g], uhi = y_ptr[gl + 1];
-    Block& B = blocks[b];
-    B.h0 = B.h1 = 0;
-    if (gl == g) {
-      B.h0 = (ulo + 31) / 32;
-      B.h1 = uhi == m ? T : uhi / 32;
-      if (B.h1 < B.h0) B.h1 = B.h0;
-    }
-    B.w0 = ulo / 32; B.w1 = uhi > ulo ? (uhi + 31) / 32 : B.w0;
-    pairs += T - (B.h1 - B.h0);
-  }
+  const std::vector<CrossBlock> blocks = cross_blocks(x_ptr, y_ptr, S, qt, 32, T);
+  int64_t pairs = 0;
+  for (const CrossBlock& B : blocks) pairs += T - (B.h1 - B.h0);
   const int64_t per = std::max<int64_t>(1, (pairs + 1023) / 1024);
   std::vector<int32_t> tab;
   int most = 1;
   for (size_t b = 0; b < blocks.size(); ++b) {
-    const Block& B = blocks[b];
-    const int64_t r0 = (int64_t)b * qt, hole = B.h1 - B.h0, adm = T - hole;
+    const CrossBlock& B = blocks[b];
+    const int64_t r0 = (int64_t)b * qt, adm = T - (B.h1 - B.h0);
     if (adm <= 0) continue;
     // automatic: no run shorter than kMinRun tiles.  The workgroups of a row block exchange thresholds every 64 tiles (sync_seed), so
     // a shorter run never imports one on its way and proves its own from a few hundred columns only: measured at 2001 rows, d = 600,
@@ -689,33 +737,58 @@ std::vector<int32_t> cross_seg16_table(const int64_t* x_ptr, const int64_t* y_pt
     int R = 1;
     while (2 * R <= want && 2 * R <= adm && 2 * R <= max_r) R <<= 1;
     while ((adm + R - 1) / R > max_run && 2 * R <= adm && 2 * R <= max_r) R <<= 1;
-    const int64_t tps = (adm + R - 1) / R;
-    if (tps > max_run) { if (lists_out) *lists_out = -1; return {}; }
+    if ((adm + R - 1) / R > max_run) { if (lists_out) *lists_out = -1; return {}; }
     int slot = 0;
-    auto entry = [&](int64_t t0, int64_t t1) {
-      if (t0 >= t1) return;
-      int64_t w0 = std::max(B.w0, t0), w1 = std::min(B.w1, t1);
-      if (w0 >= w1) w0 = w1 = t0;
+    const int count = cross_block_runs(B, T, R, [&](int64_t t0, int64_t t1, int64_t w0, int64_t w1) {
       const int32_t e[8] = {(int32_t)r0, (int32_t)r0, (int32_t)std::min<int64_t>(qt, n - r0), (int32_t)t0, (int32_t)t1, slot++, (int32_t)w0, (int32_t)w1};
       tab.insert(tab.end(), e, e + 8);
-    };
-    for (int64_t a0 = 0; a0 < adm; a0 += tps) {
-      const int64_t a1 = std::min(a0 + tps, adm);          // admissible tile a is tile a below the hole and a + hole above it
-      if (hole == 0 || a1 <= B.h0) entry(a0, a1);
-      else if (a0 >= B.h0) entry(a0 + hole, a1 + hole);
-      else { entry(a0, B.h0); entry(B.h1, a1 + hole); }
-    }
-    if (slot > most) most = slot;
+    });
+    if (count > most) most = count;
   }
-  const size_t entries = tab.size() / 8;
-  std::vector<size_t> order(entries);
-  for (size_t i = 0; i < entries; ++i) order[i] = i;
-  auto len = [&](size_t i) { return tab[i * 8 + 4] - tab[i * 8 + 3]; };
-  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return len(a) > len(b); });
-  std::vector<int32_t> sorted(tab.size());
-  for (size_t i = 0; i < entries; ++i) std::copy_n(tab.begin() + order[i] * 8, 8, sorted.begin() + i * 8);
   if (lists_out) *lists_out = 2 * most;
-  return sorted;
+  return longest_run_first(tab);
+}
+
+// The work table of the wide 16-bit cross-segment scan (mmf_simtopk_cross_segments_wide): cross_seg16_table's rule
+// with the wide kernel's numbers — row blocks of 128 rows of X, column tiles of 128 rows of the plain image of Y, T = m_pad / 128 of
+// them (m_pad: m rounded up to 256) — in the wide scan's entry layout (mmf_scan_b16w.hip, WSEG_* / WXSEG_*):
+//   first row of the block (operand position = list row), the same again, real queries, first and end tile, first tile of the mask
+//   window, first list slot (2 x the entry's number in its block, in tile order), end tile of the mask window.
+// Hole, mask window, runs and the two entries of a run that spans the hole are cross_blocks' and cross_block_runs'.  R is a power of
+// two, at most A, at most the largest one with 2 (R + 1) cap <= cand_budget (16 at cap 16, 8 at cap 32: the bounds of §4.16);
+// `col_splits` when forced (> 0), else the smallest power of two with (row blocks) x R >= 256 — the wide kernel runs one workgroup
+// per CU — but no automatic run shorter than 8 tiles.  The wide kernel moves a tile through the buffer base: no run is too long.
+// Entries come longest run first.  *lists_out: 2 x the largest entry count of a block.
+std::vector<int32_t> cross_segw_table(const int64_t* x_ptr, const int64_t* y_ptr, int64_t S, int cap, int cand_budget, int col_splits,
+                                      int* lists_out) {
+  constexpr int kQT = 128, kTile = 128;
+  constexpr int64_t kFill = 256, kMinRun = 8;
+  const int64_t n = S > 0 ? x_ptr[S] : 0, m = S > 0 ? y_ptr[S] : 0;
+  const int64_t T = (m + 255) / 256 * 2;
+  int max_r = 1;
+  while (2 * (2 * max_r + 1) * cap <= cand_budget) max_r <<= 1;
+  const std::vector<CrossBlock> blocks = cross_blocks(x_ptr, y_ptr, S, kQT, kTile, T);
+  int64_t fill = 1;
+  while ((int64_t)blocks.size() * fill < kFill && fill < max_r) fill <<= 1;
+  std::vector<int32_t> tab;
+  int most = 1;
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    const CrossBlock& B = blocks[b];
+    const int64_t r0 = (int64_t)b * kQT, adm = T - (B.h1 - B.h0);
+    if (adm <= 0) continue;
+    const int64_t want = col_splits > 0 ? col_splits : std::min(fill, std::max<int64_t>(1, adm / kMinRun));
+    int R = 1;
+    while (2 * R <= want && 2 * R <= adm && 2 * R <= max_r) R <<= 1;
+    int number = 0;
+    const int count = cross_block_runs(B, T, R, [&](int64_t t0, int64_t t1, int64_t w0, int64_t w1) {
+      const int32_t e[8] = {(int32_t)r0, (int32_t)r0, (int32_t)std::min<int64_t>(kQT, n - r0), (int32_t)t0, (int32_t)t1, (int32_t)w0,
+                            2 * number++, (int32_t)w1};
+      tab.insert(tab.end(), e, e + 8);
+    });
+    if (count > most) most = count;
+  }
+  if (lists_out) *lists_out = 2 * most;
+  return longest_run_first(tab);
 }
 
 // One workgroup per entry of the device copy `sched` of that table.  p.Xp / p.Yp: the f32 images of ALL rows of X and Y; p.rx /
