@@ -126,6 +126,22 @@ CROSS_SEG16_EXPORTS = ["mmf_simtopk_cross_segments_fast", "mmf_cross_segments_fa
 # were flagged); mmf_cross_segments_wide_table is host-only.  Pinned by tests/test_cross_segments_wide_cpu.py.
 CROSS_SEGW_EXPORTS = ["mmf_simtopk_cross_segments_wide", "mmf_cross_segments_wide_table"]
 
+# The 16-bit top-k for any k (include/ext/mmf_hg_fast_anyk.h): an addition to ABI version 3 in a header of its own.
+# mmf_simtopk_fast_anyk synchronises once per pass (fail counts and yield histogram together; once more in a pass that sends rows to
+# the exact rescan); mmf_fast_anyk_plan is host-only.  Pinned by tests/test_fast_anyk_cpu.py.
+FAST_ANYK_EXPORTS = ["mmf_simtopk_fast_anyk", "mmf_fast_anyk_plan"]
+FAST_ANYK_MAX_PASSES = 16
+
+
+class FastAnykInfo(ctypes.Structure):
+    _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
+                ("ghost_max", ctypes.c_int32 * FAST_ANYK_MAX_PASSES), ("exact_rows", ctypes.c_int64 * FAST_ANYK_MAX_PASSES)]
+
+    def as_dict(self):
+        p = min(int(self.passes), FAST_ANYK_MAX_PASSES)
+        return {"passes": int(self.passes), "yield": list(self.yield_[:p]), "ghost_max": list(self.ghost_max[:p]),
+                "exact_rows": list(self.exact_rows[:p])}
+
 
 def lib() -> ctypes.CDLL:
     global _lib
@@ -220,6 +236,10 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_cross_segments_wide.restype = ci
     L.mmf_cross_segments_wide_table.argtypes = list(L.mmf_cross_segments_fast_table.argtypes)
     L.mmf_cross_segments_wide_table.restype = i64
+    L.mmf_simtopk_fast_anyk.argtypes = list(L.mmf_simtopk_ex.argtypes) + [ctypes.POINTER(FastAnykInfo)]
+    L.mmf_simtopk_fast_anyk.restype = ci
+    L.mmf_fast_anyk_plan.argtypes = [i64, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.mmf_fast_anyk_plan.restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

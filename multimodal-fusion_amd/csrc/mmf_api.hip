@@ -416,13 +416,19 @@ struct ExactPass {
   int dp = 0; float lambda_g = 0.0f;        //   X and their chains; r.metric MMF_RBF, r.lambda = lambda_h (mmf_simtopk_combined)
   const float *Pc = nullptr, *pnc = nullptr;   // ... and of the rows of Y (mmf_simtopk_combined_xy); null: P / pn, X against itself
   int64_t out_row0 = 0;                     // the outputs' first row is row out_row0 of X (the caller holds a row slice of X's rows)
+  // One pass of several for gathered rows (mmf_simtopk_fast_anyk): the output rows are out_stride wide (0: r.k) and
+  // already hold out_off0 entries; the rows' floors live in row_floor_key / row_floor_id, indexed by row of X — read before a piece's
+  // first scan (floors_in) and left behind its last re-rank (floors_out)
+  int out_stride = 0, out_off0 = 0;
+  bool floors_in = false, floors_out = false;
+  float* row_floor_key = nullptr; uint32_t* row_floor_id = nullptr;
   std::vector<ExactGroup> pieces;           // the groups, gathered ones in pieces of at most kBatch rows
   int64_t rows_total = 0; size_t list_words = 0; bool slices = false;
   int grid = 0;                             // out: scan workgroups (of each piece's last pass)
 
   ExactPass(const Request& r_, const float* rx_, const float* cy_) : r(r_), rx(rx_), cy(cy_) {}
   int cap() const { return scan_f32_cap(std::min(r.kk, 44)); }
-  bool floors() const { return r.kk > 44; }
+  bool floors() const { return r.kk > 44 || floors_in || floors_out; }
   int splits(const ExactGroup& G) const { return pick_splits((G.rows + 127) / 128, (G.cols + 127) / 128, cap(), forced_splits); }
   void add(ExactGroup G) {
     const int64_t end = G.row0 + G.rows;
@@ -485,7 +491,8 @@ struct ExactPass {
       SelectProblem q = r.select();   // this piece of it (exact lists have no overflow lists: nothing for a second select launch)
       q.X = sp.X; q.n = sp.n; q.Y = sp.Y; q.m = sp.m; q.row_offset += r0; q.col_offset += G.col0;
       q.rx = sp.rx; q.cy = sp.cy; q.row_ids = sp.row_ids; q.n_rows = G.rows;
-      q.out_idx += (r0 - out_row0) * r.k; q.out_val += (r0 - out_row0) * r.k; q.out_stride = r.k;
+      q.out_stride = out_stride > 0 ? out_stride : r.k;
+      q.out_idx += (r0 - out_row0) * q.out_stride; q.out_val += (r0 - out_row0) * q.out_stride;
       q.fail_rows = B.fail_rows; q.fail_count = B.fail_count; q.cand_total = cand_total;
       if (P) {
         sp.Pq = q.Pq = P + r0 * dp; sp.Pc = q.Pc = (Pc ? Pc : P) + G.col0 * dp;
@@ -495,17 +502,20 @@ struct ExactPass {
       // k + self beyond 44: several passes, each offering only what ranks after the previous pass's last entry
       // (scikit-learn's n_neighbors is uncapped, preprocess_hypergraph.py:379)
       int g = 0;
+      const bool row_floors = G.gathered && (floors_in || floors_out);
+      if (row_floors && floors_in) MMF_TRY(launch_floor_move(row_ids + G.row0, G.rows, row_floor_key, row_floor_id, B.floor_key, B.floor_id, false, s));
       for (int done = 0; done < G.k; done += k_pass_max) {
         const int kp = std::min(G.k - done, k_pass_max);
-        const bool more = done + kp < G.k;
+        const bool more = done + kp < G.k || (row_floors && floors_out);
         sp.kk = kp + self1;
-        if (done > 0) { sp.floor_key = B.floor_key; sp.floor_id = B.floor_id; }
+        if (done > 0 || (row_floors && floors_in)) { sp.floor_key = B.floor_key; sp.floor_id = B.floor_id; }
         MMF_TRY(launch_scan_f32(sp, L, s, &g));
         if (t && one_pass) { MMF_TRY(t[1].stop(s)); MMF_TRY(t[2].start(r.profile, s)); }
-        q.k = kp; q.out_off = done;
+        q.k = kp; q.out_off = out_off0 + done;
         q.floor_key_out = more ? B.floor_key : nullptr; q.floor_id_out = more ? B.floor_id : nullptr;
         MMF_TRY(P ? launch_rerank_combined(q, L, s) : launch_select(q, L, s));
       }
+      if (row_floors && floors_out) MMF_TRY(launch_floor_move(row_ids + G.row0, G.rows, row_floor_key, row_floor_id, B.floor_key, B.floor_id, true, s));
       grid += g;
       used += G.rows;
     }
@@ -581,6 +591,12 @@ struct FastTail {
   static constexpr int64_t kRowsExactMax = 48;
   int64_t rows_exact_cap = 0;
   float* row_keys = nullptr;
+  // The first pass of mmf_simtopk_fast_anyk (set before bytes() / carve()): the output rows are out_stride wide
+  // (0: r.k) and every row — the flagged ones too, which then all take the matrix-core rescan — leaves the key and local id of its
+  // last entry in floor_key_out / floor_id_out [n]
+  bool leave_floors = false; int out_stride = 0;
+  float* floor_key_out = nullptr; uint32_t* floor_id_out = nullptr;
+  int64_t failed_rows = 0;   // out: rows the last run() sent to the exact rescan
   // m_panel_min: columns of the smallest panel (== m_ when the scan is one launch); `splits` is per launch
   FastTail(int64_t n_, int64_t m_, int kk_, int forced_splits, int dp_, int panels_ = 1, int64_t m_panel_min = -1,
            int64_t m_panel_max = -1)
@@ -637,7 +653,7 @@ struct FastTail {
   }
   size_t bytes() const {
     return b16_lists_bytes(n, lists_alloc, bcap) + FlagBlock::bytes(n) +
-           ExactLists::bytes(FB, (size_t)FB * 2 * fb_splits, cap, false) + ws_bytes(scan_scratch_bytes(), 1) +
+           ExactLists::bytes(FB, (size_t)FB * 2 * fb_splits, cap, leave_floors) + ws_bytes(scan_scratch_bytes(), 1) +
            (sym_try ? ws_bytes(n, 4) + ws_bytes((size_t)n * kSymCap, 8) + SymBuffers::bytes(n_pad_q(), sym_grid()) : 0) +
            ws_bytes(seed_stripes() * n_seed, 4) + ws_bytes((size_t)rows_exact_cap * m, 4) + ws_bytes(select_order_bytes(n), 1) +
            (order_try ? ws_bytes(query_order_bytes(n), 1) + ws_bytes((size_t)n_pad_q() * dp, 2) + 3 * ws_bytes(n_pad_q(), 4) : 0);
@@ -650,7 +666,7 @@ struct FastTail {
       sym_kept = ws.kept; sym_keep = ws.keep;
     }
     flags.carve(ws, n);
-    XL.carve(ws, FB, (size_t)FB * 2 * fb_splits, cap, false);
+    XL.carve(ws, FB, (size_t)FB * 2 * fb_splits, cap, leave_floors);
     scan_scratch = ws.take<char>(scan_scratch_bytes());
     seed = ws.take<int32_t>(seed_stripes() * n_seed);
     row_keys = ws.take<float>((size_t)rows_exact_cap * m);
@@ -753,6 +769,8 @@ struct FastTail {
     q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = r.stats ? flags.cand_total : nullptr;
     q.two_pass = true;
     q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
+    q.out_stride = out_stride;
+    if (leave_floors) { q.floor_key_out = floor_key_out; q.floor_id_out = floor_id_out; }
     MMF_TRY(t_sel.start(profile, s));
     MMF_TRY(launch_select(q, L, s));
     MMF_TRY(t_sel.stop(s));
@@ -760,6 +778,7 @@ struct FastTail {
     MMF_TRY(flags.read(r.stats != nullptr, s));
     const uint32_t* h_fail4 = flags.h_fail4;
     const uint32_t h_fail = h_fail4[0];
+    failed_rows = h_fail;
     if (h_fail > 0 && getenv("MMF_DEBUG_PRINT_FLAGGED")) {   // diagnosis: which rows, and the threshold / dropped key that flagged them
       const uint32_t nshow = h_fail < 8 ? h_fail : 8;
       int32_t rows[8];
@@ -775,7 +794,7 @@ struct FastTail {
     }
 
     MMF_TRY(t_fb.start(profile && h_fail > 0, s));
-    if (h_fail > 0 && (int64_t)h_fail <= kRowsExactMax) {
+    if (h_fail > 0 && (int64_t)h_fail <= kRowsExactMax && !leave_floors) {
       for (int64_t off = 0; off < (int64_t)h_fail; off += rows_exact_cap) {
         SelectProblem fq = q;
         fq.perm = nullptr;
@@ -786,6 +805,8 @@ struct FastTail {
     } else if (h_fail > 0) {   // the exact pass over the flagged rows; its f32 images in the second workspace slot
       ExactPass ex(r, fo.rx, fo.cy);
       ex.row_ids = flags.fail_rows; ex.n_ids = h_fail; ex.forced_splits = fb_splits;
+      ex.out_stride = out_stride;
+      if (leave_floors) { ex.floors_out = true; ex.row_floor_key = floor_key_out; ex.row_floor_id = floor_id_out; }
       ex.add(ExactGroup{0, (int64_t)h_fail, true, 0, m, r.k});
       Workspace aux;
       MMF_TRY(r.call.workspace(ex.image_bytes(), &aux, 1));
@@ -1540,15 +1561,58 @@ int mmf_release_workspaces(void) {
   return MMF_OK;
 }
 
-int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
-                   float lambda, int k, int exclude_self, int64_t row_offset, int64_t col_offset, int64_t* out_idx,
-                   float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id,
-                   void* hip_stream) {
-  if (!Y) { Y = X; m = n; }
-  Request r{Call("simtopk", device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset,
-            out_idx, out_val, stats, opts && opts->profile};
-  r.wide_ok = true;
-  MMF_TRY(r.check(opts ? opts->precision : MMF_PREC_AUTO, false, [] { return MMF_OK; }));
+// The 16-bit operands of a fast call: both images and both scalar vectors, shared or not, and max_n.  X a row-slice of Y (the
+// row-sharded multi-GPU case passes full[lo:hi] and full): every query-side buffer is then a view into the candidate-side one
+// and only Y is prepared.
+struct FastPrep {
+  int64_t n, m; int dp; bool f16;
+  bool same, shared; int64_t slice0 = -1, n_pad, m_pad;
+  float *rx = nullptr, *cy = nullptr; HalfImage Q, C;
+  uint32_t* max_n = nullptr;   // largest squared row norm over X and Y -> common scale
+  FastPrep(const Request& r, int dp_, bool f16_) : n(r.n), m(r.m), dp(dp_), f16(f16_) {
+    same = (r.Y == r.X) && (m == n);
+    const size_t row_bytes = (size_t)r.d * dtype_size(r.dtype);
+    if (!same) {
+      const char* xb = static_cast<const char*>(r.X);
+      const char* yb = static_cast<const char*>(r.Y);
+      if (xb >= yb && xb + (size_t)n * row_bytes <= yb + (size_t)m * row_bytes && ((size_t)(xb - yb) % row_bytes) == 0)
+        slice0 = (int64_t)((size_t)(xb - yb) / row_bytes);
+    }
+    shared = same || slice0 >= 0;
+    n_pad = (n + 255) / 256 * 256; m_pad = (m + 255) / 256 * 256 + (slice0 >= 0 ? 256 : 0);
+  }
+  size_t bytes() const { return ws_bytes(n, 4) + ws_bytes(m, 4) + HalfImage::bytes(n_pad, dp) + HalfImage::bytes(m_pad, dp) + ws_bytes(4, 4); }
+  // the candidate side is always carved; the query side is rows r0 .. of it (shared) or a carve of its own
+  void carve(Workspace& ws) {
+    const int64_t r0 = same ? 0 : slice0;
+    rx = shared ? nullptr : ws.take<float>(n);
+    cy = ws.take<float>(m);
+    if (!shared) Q.carve(ws, n_pad, dp);
+    C.carve(ws, m_pad, dp);
+    if (shared) { rx = cy + r0; Q = C.from_row(r0, dp); }
+    max_n = ws.take<uint32_t>(4);
+  }
+  int run(const Request& r, EventTimer* t_prep) const {
+    const hipStream_t s = r.call.s;
+    MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
+    MMF_HIP(hipMemsetAsync(max_n, 0, 16, s));
+    if (!shared) MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
+    MMF_TRY(t_prep->start(r.profile, s));
+    MMF_TRY(launch_row_scalars(r.Y, m, r.d, r.dtype, r.metric, cy, max_n, s));
+    if (!shared) MMF_TRY(launch_row_scalars(r.X, n, r.d, r.dtype, r.metric, rx, max_n, s));
+    MMF_TRY(launch_prep_half({r.Y, m, r.d, r.dtype, r.metric, cy, max_n}, C, dp, f16, s));
+    if (!shared) MMF_TRY(launch_prep_half({r.X, n, r.d, r.dtype, r.metric, rx, max_n}, Q, dp, f16, s));
+    return t_prep->stop(s);
+  }
+  FastOperands operands() const { return FastOperands{Q, C, rx, cy, (m + 255) / 256 * 256, dp, f16}; }
+};
+
+// mmf_simtopk_ex behind its checks (and mmf_simtopk_fast_anyk where one pass serves): the fast path or the exact path, as r.precision says
+static int simtopk_run(Request& r, const mmf_simtopk_opts* opts) {
+  const void* X = r.X; const void* Y = r.Y;
+  const int64_t n = r.n, m = r.m, d = r.d, row_offset = r.row_offset, col_offset = r.col_offset;
+  const int in_dtype = r.dtype, metric = r.metric, k = r.k;
+  mmf_simtopk_stats* stats = r.stats;
   if (n == 0) return MMF_OK;
   const hipStream_t s = r.call.s;
   const int forced_splits = opts ? opts->col_splits : 0;
@@ -1558,53 +1622,21 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
     // ---- fast path: f16/bf16 MFMA scan -> exact re-rank -> exact rescan of overflowed rows -------
     const int dp = r.wide ? scan_b16w_dp(d) : scan_bf16_dp(d);
     const bool f16 = (r.precision == MMF_PREC_FAST);   // operand type of the scan, not of the input
-    // X a row-slice of Y (the row-sharded multi-GPU case passes full[lo:hi] and full): every query-side
-    // buffer is then a view into the candidate-side one and only Y is prepared.
-    const size_t row_bytes = (size_t)d * dtype_size(in_dtype);
-    int64_t slice0 = -1;
-    if (!same) {
-      const char* xb = static_cast<const char*>(X);
-      const char* yb = static_cast<const char*>(Y);
-      if (xb >= yb && xb + (size_t)n * row_bytes <= yb + (size_t)m * row_bytes && ((size_t)(xb - yb) % row_bytes) == 0)
-        slice0 = (int64_t)((size_t)(xb - yb) / row_bytes);
-    }
-    const bool shared = same || slice0 >= 0;
-    const int64_t n_pad = (n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256 + (slice0 >= 0 ? 256 : 0);
+    FastPrep fp(r, dp, f16);
     FastTail ft(n, m, r.kk, forced_splits, dp);
     MMF_TRY(ft.set_query_order(opts ? opts->query_order : MMF_QUERY_ORDER_AUTO));
     {
       int G = 0;
       if (symmetric_scan_wanted(n, dp, ft.bcap, metric, forced_splits, same && row_offset == col_offset, &G)) ft.set_symmetric(G);
     }
-    // both images and both scalar vectors, shared or not, and max_n
-    const size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + HalfImage::bytes(n_pad, dp) + HalfImage::bytes(m_pad, dp) + ws_bytes(4, 4) +
-                        ft.bytes();
     Workspace ws;
-    MMF_TRY(r.call.workspace(need, &ws));
-    // the candidate side is always carved; the query side is rows r0 .. of it (shared) or a carve of its own
-    const int64_t r0 = same ? 0 : slice0;
-    float* rx = shared ? nullptr : ws.take<float>(n);
-    float* cy = ws.take<float>(m);
-    HalfImage Q, C;
-    if (!shared) Q.carve(ws, n_pad, dp);
-    C.carve(ws, m_pad, dp);
-    if (shared) { rx = cy + r0; Q = C.from_row(r0, dp); }
-    uint32_t* max_n = ws.take<uint32_t>(4);   // largest squared row norm over X and Y -> common scale
+    MMF_TRY(r.call.workspace(fp.bytes() + ft.bytes(), &ws));
+    fp.carve(ws);
     ft.carve(ws);
-    MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
-    MMF_HIP(hipMemsetAsync(max_n, 0, 16, s));
-    if (!shared) MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
-
     EventTimer t_prep;
-    MMF_TRY(t_prep.start(r.profile, s));
-    MMF_TRY(launch_row_scalars(Y, m, d, in_dtype, metric, cy, max_n, s));
-    if (!shared) MMF_TRY(launch_row_scalars(X, n, d, in_dtype, metric, rx, max_n, s));
-    MMF_TRY(launch_prep_half({Y, m, d, in_dtype, metric, cy, max_n}, C, dp, f16, s));
-    if (!shared) MMF_TRY(launch_prep_half({X, n, d, in_dtype, metric, rx, max_n}, Q, dp, f16, s));
-    MMF_TRY(t_prep.stop(s));
+    MMF_TRY(fp.run(r, &t_prep));
 
-    FastOperands fo{Q, C, rx, cy, (m + 255) / 256 * 256, dp, f16};
-    MMF_TRY(ft.run(r, fo, opts ? opts->select_wait_event : nullptr));
+    MMF_TRY(ft.run(r, fp.operands(), opts ? opts->select_wait_event : nullptr));
     if (stats) stats->prep_ms = t_prep.ms();
     return MMF_OK;
   }
@@ -1635,6 +1667,200 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
   MMF_TRY(ex.run(ws, B, t, stats ? &h_tot : nullptr));
   fill_stats(stats, MMF_PREC_EXACT, ex.splits(ex.pieces[0]), ex.grid, t[0].ms(), t[1].ms(), t[2].ms(), 0.f, 0, 0, 0, h_tot);
   return MMF_OK;
+}
+
+int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
+                   float lambda, int k, int exclude_self, int64_t row_offset, int64_t col_offset, int64_t* out_idx,
+                   float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id,
+                   void* hip_stream) {
+  if (!Y) { Y = X; m = n; }
+  Request r{Call("simtopk", device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset,
+            out_idx, out_val, stats, opts && opts->profile};
+  r.wide_ok = true;
+  MMF_TRY(r.check(opts ? opts->precision : MMF_PREC_AUTO, false, [] { return MMF_OK; }));
+  return simtopk_run(r, opts);
+}
+
+// ---- mmf_simtopk_fast_anyk (include/ext/mmf_hg_fast_anyk.h) ---------------------------------------------------
+// The depth of a pass of the 16-bit scan, self's slot included: the largest k + self scan_bf16_supported serves at d.
+static int anyk_depth(int64_t d) { return d <= 512 ? 44 : 20; }
+
+int mmf_fast_anyk_plan(int64_t d, int k, int exclude_self, int* scan_kk, int* first_yield, int* min_passes) {
+  if (d < 1 || k < 1) { set_error("fast_anyk_plan: need d >= 1 and k >= 1 (got d = %lld, k = %d)", (long long)d, k); return MMF_E_INVALID; }
+  const int self1 = exclude_self ? 1 : 0, kk = k + self1;
+  const bool one = d <= 1024 ? scan_bf16_supported(d, kk, MMF_F32) != 0 : scan_b16w_supported(d, kk) != 0;
+  if (!one && d > 1024) {
+    set_error("fast_anyk_plan: d = %lld, k = %d is beyond one pass of the wide 16-bit scan, which has no ceilings (d <= 1024 is served for any k)",
+              (long long)d, k);
+    return MMF_E_UNSUPPORTED;
+  }
+  const int depth = one ? kk : anyk_depth(d), per = anyk_depth(d) - self1;
+  if (scan_kk) *scan_kk = depth;
+  if (first_yield) *first_yield = depth - self1;
+  if (min_passes) *min_passes = one ? 1 : 1 + (k - (depth - self1) + per - 1) / per;
+  return one ? 0 : 1;
+}
+
+// MMF_ANYK_SHORT_DIV (read per call): a later pass may leave n / div unflagged rows short of its yield (they take the exact rescan).
+// An operating point, not a correctness condition (profiles/fast_anyk_timing.txt).
+static int64_t anyk_short_div() {
+  const char* e = getenv("MMF_ANYK_SHORT_DIV");
+  const long v = e ? atol(e) : 0;
+  return (v >= 1 && v <= 65536) ? v : 64;
+}
+
+static void anyk_record(mmf_fast_anyk_info* info, int pass, int yield, int ghost_max, int64_t exact_rows) {
+  if (!info) return;
+  info->passes = pass + 1;
+  if (pass >= MMF_FAST_ANYK_MAX_PASSES) return;
+  info->yield[pass] = yield; info->ghost_max[pass] = ghost_max; info->exact_rows[pass] = exact_rows;
+}
+
+// The passes (r.precision MMF_PREC_FAST or _FAST_BF16, d <= 1024, k + self beyond one pass).  Pass 0 is the fast call at the full
+// depth (FastTail::run), leaving every row's floor.  A later pass: ceilings from the floors, the plain scan under them at the full
+// depth, the re-rank into the staging rows, the count of each row's certified entries (one host synchronisation: histogram and
+// flagged rows), the yield t, the emit of t entries per row, and the exact rescan with floors of the rows that could not.
+static int fast_anyk_run(Request& r, const mmf_simtopk_opts* opts, mmf_fast_anyk_info* info) {
+  const int64_t n = r.n, m = r.m;
+  const hipStream_t s = r.call.s;
+  const int k = r.k, self1 = r.exclude_self ? 1 : 0, depth = anyk_depth(r.d), K = depth - self1;
+  const int dp = scan_bf16_dp(r.d);
+  FastPrep fp(r, dp, r.precision == MMF_PREC_FAST);
+  // (the symmetric scan needs the 15-entry lists of k + self <= 11: it never applies at the full depth)
+  FastTail ft(n, m, depth, opts ? opts->col_splits : 0, dp);
+  MMF_TRY(ft.set_query_order(opts ? opts->query_order : MMF_QUERY_ORDER_AUTO));
+  ft.leave_floors = true; ft.out_stride = k;
+  // the exact rescans of the later passes, FB rows at a time: lists for the deepest exact pass, with floors
+  const int xcap = scan_f32_cap(44), xsplits = pick_splits((ft.FB + 127) / 128, (m + 127) / 128, xcap, 0);
+  const size_t xwords = (size_t)ft.FB * 2 * xsplits;
+  const size_t stage = (size_t)n * K;
+  const size_t extra = 4 * ws_bytes(n, 4) + ws_bytes(fp.n_pad, 4) + ws_bytes(64, 4) + ws_bytes(4, 4) + ws_bytes(stage, 8) + 2 * ws_bytes(stage, 4) +
+                       ExactLists::bytes(ft.FB, xwords, xcap, true);
+  Workspace ws;
+  MMF_TRY(r.call.workspace(fp.bytes() + ft.bytes() + extra, &ws));
+  fp.carve(ws);
+  ft.carve(ws);
+  float* fkey = ws.take<float>(n); uint32_t* fid = ws.take<uint32_t>(n);
+  int32_t* certified = ws.take<int32_t>(n); int32_t* rescan_rows = ws.take<int32_t>(n);
+  float* ceil = ws.take<float>(fp.n_pad);
+  uint32_t* hist = ws.take<uint32_t>(64); uint32_t* rescan_count = ws.take<uint32_t>(4);
+  int64_t* sidx = ws.take<int64_t>(stage); float* sval = ws.take<float>(stage); float* skey = ws.take<float>(stage);
+  ExactLists XB;
+  XB.carve(ws, ft.FB, xwords, xcap, true);
+  ft.floor_key_out = fkey; ft.floor_id_out = fid;
+  EventTimer t_prep;
+  MMF_TRY(fp.run(r, &t_prep));
+
+  // pass 0: K entries per row, r.k wide rows
+  r.k = K; r.kk = depth;
+  const int rc0 = ft.run(r, fp.operands(), nullptr);
+  r.k = k; r.kk = k + self1;
+  MMF_TRY(rc0);
+  if (r.stats) r.stats->prep_ms = t_prep.ms();
+  anyk_record(info, 0, K, 0, ft.failed_rows);
+
+  const int64_t budget = n / anyk_short_div();
+  const CandLists L = ft.view(false);
+  ScanB16Panel pn;
+  pn.seed = ft.seed; pn.seed_stride = ft.n_seed; pn.share = ft.splits > 1 ? 1 : 0;
+  const ScanB16Problem sp(fp.Q, fp.C, n, m, (m + 255) / 256 * 256, dp, r.d, fp.f16, r.metric, depth);
+  const AnykStage st{sidx, sval, skey, n, K, r.col_offset};
+  int done = K;
+  // kq more entries, from the floors on, for `cnt` rows by the exact scan; floors left unless these are the call's last entries
+  auto exact_rows = [&](const int32_t* rows, int64_t cnt, int kq) -> int {
+    ExactPass ex(r, fp.rx, fp.cy);
+    ex.row_ids = rows; ex.n_ids = cnt; ex.forced_splits = xsplits;
+    ex.out_off0 = done; ex.floors_in = true; ex.floors_out = done + kq < k;
+    ex.row_floor_key = fkey; ex.row_floor_id = fid;
+    ex.add(ExactGroup{0, cnt, true, 0, m, kq});
+    Workspace aux;
+    MMF_TRY(r.call.workspace(ex.image_bytes(), &aux, 1));
+    MMF_TRY(XB.zero(s));
+    MMF_TRY(ex.run(aux, XB));
+    if (r.stats) r.stats->fallback_rows += cnt;
+    return MMF_OK;
+  };
+  auto finish_exact = [&](int pass) -> int {   // every row, everything that is left
+    MMF_TRY(launch_anyk_iota(rescan_rows, n, s));
+    MMF_TRY(exact_rows(rescan_rows, n, k - done));
+    anyk_record(info, pass, k - done, 0, n);
+    return MMF_OK;
+  };
+  for (int pass = 1; done < k; ++pass) {
+    if (pass >= MMF_FAST_ANYK_MAX_PASSES - 1) return finish_exact(pass);
+    MMF_TRY(launch_scan_b16_ceilings(sp, L.cap, fkey, fp.rx, fp.max_n, r.lambda, fp.n_pad, ceil, s));
+    MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
+    MMF_TRY(ft.flags.zero(s));
+    MMF_HIP(hipMemsetAsync(ft.seed, 0x80, (size_t)ft.n_seed * 4 * ft.seed_stripes(), s));
+    MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
+    MMF_TRY(launch_scan_b16_ceil(sp, ft.splits, L, ft.scan_scratch, pn, ceil, s, nullptr));
+    MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
+    SelectProblem q = r.select();
+    q.k = K; q.out_idx = sidx; q.out_val = sval; q.key_out = skey; q.out_stride = K;
+    q.rx = fp.rx; q.cy = fp.cy;
+    q.fail_rows = ft.flags.fail_rows; q.fail_count = ft.flags.fail_count;
+    q.two_pass = true;
+    q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : ft.order_scratch;
+    MMF_TRY(launch_select(q, L, s));
+    MMF_TRY(launch_anyk_count(st, ft.flags.fail_rows, ft.flags.fail_count, fkey, fid, certified, hist, s));
+    uint32_t h[64];
+    MMF_HIP(hipMemcpyAsync(h, hist, (size_t)(K + 3) * 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    // the largest yield that leaves at most `budget` unflagged rows short of it
+    const int t_max = std::min(K, k - done);
+    int t = 0;
+    int64_t below = 0, short_rows = 0;   // unflagged rows with fewer than t' certified entries
+    for (int tq = 1; tq <= t_max; ++tq) {
+      below += h[tq - 1];
+      if (below > budget) break;
+      t = tq; short_rows = below;
+    }
+    if (t < 1) return finish_exact(pass);
+    MMF_TRY(launch_anyk_emit(st, certified, t, done, k, r.out_idx, r.out_val, fkey, fid, rescan_rows, rescan_count, s));
+    const int64_t rescan = (int64_t)h[K + 1] + short_rows;
+    if (rescan > 0) MMF_TRY(exact_rows(rescan_rows, rescan, t));
+    anyk_record(info, pass, t, (int)h[K + 2], rescan);
+    done += t;
+  }
+  return MMF_OK;
+}
+
+int mmf_simtopk_fast_anyk(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric, float lambda,
+                          int k, int exclude_self, int64_t row_offset, int64_t col_offset, int64_t* out_idx, float* out_val,
+                          const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream,
+                          mmf_fast_anyk_info* info) {
+  if (!Y) { Y = X; m = n; }
+  if (info) memset(info, 0, sizeof(*info));
+  mmf_simtopk_stats own_stats;   // info reports the first pass's flagged rows, which the call counts in its stats
+  Request r{Call("simtopk_fast_anyk", device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset,
+            out_idx, out_val, stats ? stats : (info ? &own_stats : nullptr), opts && opts->profile};
+  r.wide_ok = true;
+  const int asked = opts ? opts->precision : MMF_PREC_AUTO;
+  const int prec = asked == MMF_PREC_AUTO ? MMF_PREC_FAST : asked;
+  const bool fast = prec != MMF_PREC_EXACT;
+  // more than one pass: the 16-bit scan serves d but not k + self (the checks below refuse what makes this meaningless)
+  const bool multi = fast && d >= 1 && d <= 1024 && k >= 1 && !scan_bf16_supported(d, k + (exclude_self ? 1 : 0), in_dtype);
+  MMF_TRY(r.check(multi ? MMF_PREC_EXACT : prec, false, [&] {
+    if (asked < MMF_PREC_AUTO || asked > MMF_PREC_FAST_BF16) { set_error("%s: bad precision %d", r.call.who, asked); return MMF_E_INVALID; }
+    if (opts && opts->select_wait_event) {
+      set_error("%s: select_wait_event is not supported (every pass reads the rows; wait on the stream before the call)", r.call.who);
+      return MMF_E_UNSUPPORTED;
+    }
+    if (fast && d > 1024 && r.kk > 20) {
+      set_error("%s: d = %lld, k = %d is beyond one pass of the wide 16-bit scan, which has no ceilings (d <= 1024 is served for any k)",
+                r.call.who, (long long)d, k);
+      return MMF_E_UNSUPPORTED;
+    }
+    return MMF_OK;
+  }));
+  if (n == 0) return MMF_OK;
+  if (!multi) {
+    MMF_TRY(simtopk_run(r, opts));
+    anyk_record(info, 0, k, 0, r.stats ? r.stats->fallback_rows : 0);
+    return MMF_OK;
+  }
+  r.precision = prec;
+  return fast_anyk_run(r, opts, info);
 }
 
 int mmf_simtopk(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric, float lambda,

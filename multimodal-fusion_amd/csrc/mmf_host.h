@@ -21,6 +21,7 @@
 #include "../../include/ext/mmf_hg_cross_seg.h"
 #include "../../include/ext/mmf_hg_cross_seg16.h"
 #include "../../include/ext/mmf_hg_cross_segw.h"
+#include "../../include/ext/mmf_hg_fast_anyk.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -290,8 +291,10 @@ struct SelectProblem {
   uint32_t* cand_total;                        // optional accumulated candidate count
   bool two_pass = false;   // rows with overflow-list entries are handled by a second launch that has LDS room for them
   int out_stride = 0, out_off = 0;       // out_idx / out_val rows are out_stride wide (0: k) and this call fills columns out_off .. out_off + k
-  float* floor_key_out = nullptr;        // optional: key and LOCAL column id of the last entry emitted per row (the next pass's floor)
+  float* floor_key_out = nullptr;        // optional: key and LOCAL column id of the last entry emitted per row (the next pass's floor),
+                                         //   indexed by list position (two_pass with `perm`: by row — positions are only the scan's order)
   uint32_t* floor_id_out = nullptr;
+  float* key_out = nullptr;              // optional (launch_select): the canonical key of every entry emitted, laid out like out_val
   void* order_scratch = nullptr;   // select_order_bytes(n_rows): that second launch walks its rows ordered by their smallest candidate id
   const int32_t* perm = nullptr;   // optional (row_ids must be null): list position -> row of X, a permutation of 0 .. n_rows - 1 — the scan
                                    // took its queries in that order (mmf_order.hip); X, rx, the outputs and fail_rows stay in row order
@@ -379,6 +382,14 @@ struct ScanB16Problem {
 int launch_scan_b16(const ScanB16Problem& p, int col_splits, const CandLists& L, void* scratch, const ScanB16Panel& pn, hipStream_t s,
                     int* grid_out);
 int launch_scan_b16_audit(const ScanB16Panel& pn, uint32_t* overflow, int64_t n_rows, hipStream_t s);
+// The later passes of mmf_simtopk_fast_anyk: the plain launch with a ceiling per query row — a scanned value above
+// ceil[row] ([n_pad], the kernel's units, +inf for padding rows) reaches no list, overflow list or threshold — and the kernel that
+// turns the rows' floors (canonical keys, [p.n_rows]) into those ceilings: rx the rows' canonical scalars, max_n the word the
+// operand images took their scale from, cap the lane lists' capacity of the launch that follows
+int launch_scan_b16_ceil(const ScanB16Problem& p, int col_splits, const CandLists& L, void* scratch, const ScanB16Panel& pn, const float* ceil,
+                         hipStream_t s, int* grid_out);
+int launch_scan_b16_ceilings(const ScanB16Problem& p, int cap, const float* floor_key, const float* rx, const uint32_t* max_n, float lambda,
+                             int64_t n_pad, float* ceil, hipStream_t s);
 size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G);
 // G: row blocks per super-block; live / forward / prune: MMF_SYMMETRIC_LIVE and MMF_SYMMETRIC_PRUNE as read by the caller;
 // tables: build and upload the two work tables (false: SymBuffers::sched still holds them)
@@ -395,6 +406,22 @@ int launch_scan_b16_seg(const ScanB16Problem& p, const int32_t* sched, int64_t g
 // [n_pad][2] the excluded column range (first, count) of every query row, L.lists = the table's list count, pn.share as the table says
 int launch_scan_b16_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, const CandLists& L,
                          void* scratch, const ScanB16Panel& pn, hipStream_t s);
+
+// mmf_fast_anyk.hip: the per-row bookkeeping of mmf_simtopk_fast_anyk's later passes.  The re-rank of such a pass
+// fills a staging row per query: `depth` entries in the final order (ids with col_offset added, values, canonical keys).
+struct AnykStage { const int64_t* idx; const float* val; const float* key; int64_t n; int depth; int64_t col_offset; };
+// certified [n]: -1 for the rows of the re-rank's fail list, else the staged entries that rank strictly after the row's floor;
+// hist [depth + 3]: rows per certified count, then the flagged rows, then the largest number of entries dropped for a row
+int launch_anyk_count(const AnykStage& st, const int32_t* fail_rows, const uint32_t* fail_count, const float* floor_key, const uint32_t* floor_id,
+                      int32_t* certified, uint32_t* hist, hipStream_t s);
+// rows with certified >= t: t entries to columns done .. of the out_stride-wide outputs, and the new floor; the others: listed for the
+// exact rescan (rescan_rows [n], *rescan_count)
+int launch_anyk_emit(const AnykStage& st, const int32_t* certified, int t, int done, int out_stride, int64_t* out_idx, float* out_val,
+                     float* floor_key, uint32_t* floor_id, int32_t* rescan_rows, uint32_t* rescan_count, hipStream_t s);
+int launch_anyk_iota(int32_t* rows, int64_t n, hipStream_t s);
+// floors of the gathered rows rows[0 .. cnt): from their row-indexed home to a position-indexed block, or (back) home again
+int launch_floor_move(const int32_t* rows, int64_t cnt, float* row_key, uint32_t* row_id, float* pos_key, uint32_t* pos_id, bool back,
+                      hipStream_t s);
 
 // mmf_scan_b16w.hip: the wide 16-bit scan (1024 < d <= 4096, k + self <= 20) — both operands streamed through
 // LDS in k-chunks.  Same operand images (dp = d rounded up to 128), lists, threshold buffers and audit as launch_scan_b16; no

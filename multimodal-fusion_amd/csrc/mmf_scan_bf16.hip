@@ -76,6 +76,17 @@ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
   return (uint16_t)(u >> 16);
 }
 
+// the operands' common power-of-two scale outside prep_half_kernel (ceil_kernel's copy of the block at its top); max_n: float bits of
+// the largest squared norm (unused for cosine)
+__device__ __forceinline__ float prep_scale(int metric, const uint32_t* max_n) {
+  float mx = (metric == MMF_COSINE) ? 1.0f : __builtin_sqrtf(__uint_as_float(max_n[0]));
+  int ex = 0;
+  if (mx > 0.0f && mx < __builtin_huge_valf()) (void)frexpf(mx, &ex); else ex = 9;
+  int e = 9 - ex;
+  e = e < -100 ? -100 : (e > 100 ? 100 : e);
+  return ldexpf(1.0f, e);
+}
+
 __global__ __launch_bounds__(256) void prep_half_kernel(PrepArgs a) {
   const int lane = threadIdx.x & 63;
   // Common exact power-of-two scale: the largest row norm lands in [256, 512), so f16 keeps its full
@@ -231,6 +242,9 @@ struct ScanB16Args {
   // XSEG kernels only (launch_scan_b16_xseg): [n_pad][2] per query row, first row and row count of the columns the row may not
   // take (its own segment's rows of Y; padding rows: 0, 0)
   const uint32_t* xbounds;
+  // CEIL kernels only (launch_scan_b16_ceil): [n_pad] per query row, the largest scanned value the row may still take, in the
+  // kernel's own units (bias and 2^(2e) scale included); padding rows: +inf
+  const float* ceil;
 };
 
 // Work table entry of a segmented scan (one per workgroup): the row block's first position in the segment-padded query
@@ -252,6 +266,24 @@ __device__ __forceinline__ int32_t seed_enc(float f) {
   return b >= 0 ? b : (b ^ 0x7fffffff);
 }
 constexpr int32_t kSeedNone = (int32_t)0x80808080;   // hipMemset(0x80) pattern: "no threshold yet"
+
+// The margin 2 (E1 + E2) of a query row (see the header) outside the scan kernel — ceil_kernel's copy of the block at the top of
+// scan_b16x_kernel, term for term (the kernel keeps its own so that its instantiations stay the instruction streams they were):
+// zn / rn / un the row's norms, maxima the candidate side's, dp the padded dim, cap the lane lists' capacity.
+__device__ __forceinline__ float scan_margin(int metric, int d, int dp, int cap, float zn, float rn, float un, const uint32_t* maxima) {
+  const float ZB = __uint_as_float(maxima[0]), RB = __uint_as_float(maxima[1]);
+  const float UB = __uint_as_float(maxima[2]), CB = __uint_as_float(maxima[3]);
+  const float g_acc = (float)(dp + 8) * 5.9604645e-8f;
+  const float g_chain = (float)(d + 2) * 5.9604645e-8f;
+  // + 2^-19 |G| (2^-18 with 5 slot bits): the slot number a stored key carries in its low mantissa bits (SlotList)
+  const float slot_eps = (cap <= 16) ? 1.9073486e-6f : 3.8146973e-6f;
+  const float e1 = rn * ZB + un * RB + (g_acc + slot_eps) * (zn * ZB + CB);
+  float e2;
+  if (metric == MMF_DOT) e2 = g_chain * un * UB;
+  else if (metric == MMF_COSINE) e2 = (g_chain + 4.7683716e-7f) * un * UB * 1.01f;
+  else e2 = g_chain * un * UB + 2.3841858e-7f * (un * un + UB * UB);
+  return 2.0f * (e1 + e2) * 1.001f + 1e-30f;
+}
 
 // LDS-DMA (global -> LDS, no registers) of the 32 biases of a tile.  LDS address = wave-uniform base + lane * 4.
 __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
@@ -306,8 +338,17 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 // wave-uniform branch behind its chain: the lane fetches the excluded column range (first, count) of its two queries from
 // a.xbounds and sets each of its 16 values whose column lies inside to -inf — before max_qb, acc_prev and filter, so a masked value
 // reaches no list, overflow list, threshold, seed or lost.  SPLITK: only the owner wave masks; -inf survives the partner's partial sums.
-template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0, bool XSEG = false>
+//
+// CEIL (mmf_simtopk_fast_anyk; the plain schedule only): the later passes of a call with more neighbours than one
+// pass holds.  Every query row comes with a ceiling a.ceil[row]; a value above it belongs to a column the row has already emitted.
+// Such a value is above the row's threshold by construction, so it enters the list code as a hit anyway: the compare sits THERE, on
+// the lane's 16 gathered values before they are offered — the tile loop's v_max + two compares are untouched, and the ceiling is
+// loaded inside the branch, so the loop carries no register for it.  A value set to -inf there reaches no list, overflow list,
+// threshold, seed or lost.  SPLITK: only the owner wave runs the list code, so only it compares.
+template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0, bool XSEG = false,
+          bool CEIL = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(ScanB16Args a) {
+  static_assert(!CEIL || (!SEG && SYM == 0 && !DBG && !XSEG), "per-row ceilings: the plain schedule only");
   static_assert(!SPLITK || (TPB == 1 && NW == 8 && (KS % 8) == 0), "split-k pairs");
   static_assert(SYM == 0 || (!SPLITK && !SEG && !DBG && TPB == 2), "symmetric schedule: the d = 512 kernel only");
   static_assert(!XSEG || (SEG && SYM == 0 && !DBG), "the cross-segment mask rides on the table-driven schedule");
@@ -681,6 +722,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
           v[8 + 4 * cb + j] = __shfl_xor(give, 16);
         }
       }
+      if constexpr (CEIL) {   // columns the row has already emitted (and nothing that ranks after its floor: §4.27) lie above its ceiling
+        const float ce = a.ceil[qop];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = (v[r] > ce) ? kNegInf : v[r];
+      }
       // v[0..7]: rows of this lane's group g, v[8..15]: rows of the partner's group g ^ 1 (4 g ^ 4)
       const int g4 = 4 * g;
       auto rowof = [g4](int r) -> uint32_t { return (uint32_t)((g4 ^ ((r & 8) >> 1)) + (r & 3) + 16 * ((r >> 2) & 1)); };
@@ -929,6 +975,35 @@ __global__ void audit_kernel(const int32_t* seed, const int32_t* lost, uint32_t*
   if (l > kSeedNone && l >= seed[i]) overflow[i] = 1u;
 }
 
+// The ceilings of the CEIL kernels.  Row i has emitted everything down to its floor, the canonical key fk_i; a
+// column that ranks after the floor has a key <= fk_i, so its real-number target Q is at most map_i(fk_i) + E2_i and its scanned
+// value at most map_i(fk_i) + E1_i + E2_i.  map_i turns a canonical key into Q units (Q = bias_j + u_i . u_j, operands scaled by s):
+//   dot, cosine: s^2 key;   -|x - y|^2: s^2 (key + n_i) / 2;   rbf (key = -lambda |x - y|^2): s^2 (key / lambda + n_i) / 2.
+// E1 + E2 is half the scan's margin; `slack` covers the f32 rounding of the map itself and of the rbf key's product with lambda
+// (a few 2^-24 of the terms; 2^-21 of their magnitudes is taken).  The sum is rounded up by one more ulp.
+struct CeilArgs {
+  const float* floor_key; const float* rx;   // [n] the rows' floors and canonical row scalars
+  const float *q_zn, *q_rn, *q_un; const uint32_t* maxima; const uint32_t* max_n;
+  int64_t n, n_pad; int metric, d, dp, cap; float lambda;
+  float* ceil;                               // [n_pad]
+};
+__global__ void ceil_kernel(CeilArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n_pad) return;
+  if (i >= a.n) { a.ceil[i] = __builtin_huge_valf(); return; }
+  const float s = prep_scale(a.metric, a.max_n), s2 = s * s;
+  const float fk = a.floor_key[i];
+  float q, mag;
+  if (a.metric == MMF_DOT || a.metric == MMF_COSINE) { q = s2 * fk; mag = fabsf(q); }
+  else {
+    const float t = (a.metric == MMF_RBF) ? fk / a.lambda : fk, ni = a.rx[i];
+    q = 0.5f * s2 * (t + ni); mag = 0.5f * s2 * (fabsf(t) + ni);
+  }
+  const float half_margin = 0.5f * scan_margin(a.metric, a.d, a.dp, a.cap, a.q_zn[i], a.q_rn[i], a.q_un[i], a.maxima);
+  const float c = q + half_margin + 4.7683716e-7f * mag;
+  a.ceil[i] = (c == c) ? nextafterf(c, __builtin_huge_valf()) : __builtin_huge_valf();
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -1004,7 +1079,7 @@ size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap) {
 }
 
 // SEG and SYM kernels have no instrumented build
-template <int KS, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0, bool XSEG = false>
+template <int KS, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0, bool XSEG = false, bool CEIL = false>
 static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_t s) {
   const size_t lds = scan_b16_lds(KS, NW, TPB, CAP, SPLITK, SYM == 2);
   auto go = [&](auto kern) -> int {
@@ -1013,9 +1088,9 @@ static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_
     MMF_LAUNCH_CHECK();
     return MMF_OK;
   };
-  if constexpr (SEG || SYM != 0) {
-    if (f16) return go(scan_b16x_kernel<KS, true, false, NW, TPB, CAP, SPLITK, SEG, SYM, XSEG>);
-    return go(scan_b16x_kernel<KS, false, false, NW, TPB, CAP, SPLITK, SEG, SYM, XSEG>);
+  if constexpr (SEG || SYM != 0 || CEIL) {
+    if (f16) return go(scan_b16x_kernel<KS, true, false, NW, TPB, CAP, SPLITK, SEG, SYM, XSEG, CEIL>);
+    return go(scan_b16x_kernel<KS, false, false, NW, TPB, CAP, SPLITK, SEG, SYM, XSEG, CEIL>);
   }
   if (a.debug != 0) {   // instrumented build of the same kernel (MMF_SCAN_DEBUG)
     if (f16) return go(scan_b16x_kernel<KS, true, true, NW, TPB, CAP, SPLITK>);
@@ -1026,28 +1101,36 @@ static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_
 }
 
 // (padded dim, list capacity) -> <KS, NW, TPB, CAP, SPLITK>, for the plain launch, (SEG) the table-driven one and (XSEG) the
-// table-driven one with the cross-segment mask
-template <bool SEG, bool XSEG = false>
+// table-driven one with the cross-segment mask; (CEIL) the plain launch with per-row ceilings
+template <bool SEG, bool XSEG = false, bool CEIL = false>
 static int launch_b16_for(const char* who, int dp, int cap, const ScanB16Args& a, bool f16, int64_t grid, hipStream_t s) {
   const bool big = (cap == B_CAP_BIG);   // k + self in 12..20: 16-entry lists, one tile per barrier
   if (cap == B_CAP_WIDE) {               // k + self in 21..44: 32-entry lists, one tile per barrier, d <= 512
     switch (dp) {
-      case 128: return launch_b16_t<8, 8, 1, B_CAP_WIDE, false, SEG, 0, XSEG>(a, f16, grid, s);
-      case 256: return launch_b16_t<16, 8, 1, B_CAP_WIDE, false, SEG, 0, XSEG>(a, f16, grid, s);
-      case 512: return launch_b16_t<32, 8, 1, B_CAP_WIDE, false, SEG, 0, XSEG>(a, f16, grid, s);
+      case 128: return launch_b16_t<8, 8, 1, B_CAP_WIDE, false, SEG, 0, XSEG, CEIL>(a, f16, grid, s);
+      case 256: return launch_b16_t<16, 8, 1, B_CAP_WIDE, false, SEG, 0, XSEG, CEIL>(a, f16, grid, s);
+      case 512: return launch_b16_t<32, 8, 1, B_CAP_WIDE, false, SEG, 0, XSEG, CEIL>(a, f16, grid, s);
     }
     set_error("%s: 32-entry lists need a padded dim <= 512 (got %d)", who, dp);
     return MMF_E_INTERNAL;
   }
   switch (dp) {
     // d <= 256: the smaller tiles leave room for eight stages — four tiles per barrier (-1.5 % against two at d = 256)
-    case 128: return big ? launch_b16_t<8, 8, 2, B_CAP_BIG, false, SEG, 0, XSEG>(a, f16, grid, s) : launch_b16_t<8, 8, 4, B_CAP, false, SEG, 0, XSEG>(a, f16, grid, s);
-    case 256: return big ? launch_b16_t<16, 8, 2, B_CAP_BIG, false, SEG, 0, XSEG>(a, f16, grid, s) : launch_b16_t<16, 8, 4, B_CAP, false, SEG, 0, XSEG>(a, f16, grid, s);
-    case 512: return big ? launch_b16_t<32, 8, 1, B_CAP_BIG, false, SEG, 0, XSEG>(a, f16, grid, s) : launch_b16_t<32, 8, 2, B_CAP, false, SEG, 0, XSEG>(a, f16, grid, s);
-    case 1024: return launch_b16_t<64, 8, 1, B_CAP, true, SEG, 0, XSEG>(a, f16, grid, s);
+    case 128: return big ? launch_b16_t<8, 8, 2, B_CAP_BIG, false, SEG, 0, XSEG, CEIL>(a, f16, grid, s) : launch_b16_t<8, 8, 4, B_CAP, false, SEG, 0, XSEG, CEIL>(a, f16, grid, s);
+    case 256: return big ? launch_b16_t<16, 8, 2, B_CAP_BIG, false, SEG, 0, XSEG, CEIL>(a, f16, grid, s) : launch_b16_t<16, 8, 4, B_CAP, false, SEG, 0, XSEG, CEIL>(a, f16, grid, s);
+    case 512: return big ? launch_b16_t<32, 8, 1, B_CAP_BIG, false, SEG, 0, XSEG, CEIL>(a, f16, grid, s) : launch_b16_t<32, 8, 2, B_CAP, false, SEG, 0, XSEG, CEIL>(a, f16, grid, s);
+    case 1024: return launch_b16_t<64, 8, 1, B_CAP, true, SEG, 0, XSEG, CEIL>(a, f16, grid, s);
   }
   set_error("%s: unsupported padded dim %d", who, dp);
   return MMF_E_INTERNAL;
+}
+
+int launch_scan_b16_ceilings(const ScanB16Problem& p, int cap, const float* floor_key, const float* rx, const uint32_t* max_n, float lambda,
+                             int64_t n_pad, float* ceil, hipStream_t s) {
+  CeilArgs a{floor_key, rx, p.q_zn, p.q_rn, p.q_un, p.maxima, max_n, p.n_rows, n_pad, p.metric, (int)p.d, p.dp, cap, lambda, ceil};
+  hipLaunchKernelGGL(ceil_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, a);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
 }
 
 // Settles the audited losses of all scan launches of a problem (call once, after the last one).
@@ -1073,10 +1156,11 @@ static ScanB16Args scan_args(const ScanB16Problem& p, const CandLists& L, const 
   return a;
 }
 
-// col_splits must be a power of two.  Lists are indexed by query position.
-int launch_scan_b16(const ScanB16Problem& p, int col_splits, const CandLists& L, void* scratch, const ScanB16Panel& pn, hipStream_t s,
-                    int* grid_out) {
+// col_splits must be a power of two.  Lists are indexed by query position.  ceil: nullptr, or the rows' ceilings (CEIL kernels).
+static int scan_b16_plain(const ScanB16Problem& p, int col_splits, const CandLists& L, void* scratch, const ScanB16Panel& pn, const float* ceil,
+                          hipStream_t s, int* grid_out) {
   ScanB16Args a = scan_args(p, L, pn, scratch);
+  a.ceil = ceil;
   a.tiles_total = p.m_pad / B_CT;
   a.tiles_per_split = (a.tiles_total + col_splits - 1) / col_splits;
   if (a.tiles_per_split * (int64_t)B_CT * p.dp * 2 >= (int64_t(1) << 32)) {   // 32-bit scalar offsets of the tile DMA
@@ -1092,7 +1176,7 @@ int launch_scan_b16(const ScanB16Problem& p, int col_splits, const CandLists& L,
   a.seg_len = pn.seg_len; a.seg_stride = pn.seg_stride; a.id_off = pn.id_off;
   if (!pn.seed) { set_error("scan_b16: threshold buffers missing"); return MMF_E_INTERNAL; }
   if (pn.list_base + 2 * col_splits > L.lists) { set_error("scan_b16: list slots out of range"); return MMF_E_INTERNAL; }
-  {
+  if (!ceil) {   // (the CEIL kernels have no instrumented build)
     const char* dbg = getenv("MMF_SCAN_DEBUG");
     a.debug = dbg ? atoi(dbg) : 0;
     if (a.debug & (8 | 16)) {
@@ -1104,7 +1188,8 @@ int launch_scan_b16(const ScanB16Problem& p, int col_splits, const CandLists& L,
   }
   const int64_t grid = scan_b16_grid(p.n_rows, col_splits, p.dp);
   if (grid_out) *grid_out = (int)grid;
-  const int rc = launch_b16_for<false>("scan_b16", p.dp, L.cap, a, p.f16, grid, s);
+  const int rc = ceil ? launch_b16_for<false, false, true>("scan_b16_ceil", p.dp, L.cap, a, p.f16, grid, s)
+                      : launch_b16_for<false>("scan_b16", p.dp, L.cap, a, p.f16, grid, s);
   if (rc == MMF_OK && (a.debug & 16)) {
     unsigned long long h[16];
     MMF_HIP(hipMemcpyAsync(h, a.dbg, 128, hipMemcpyDeviceToHost, s));
@@ -1123,6 +1208,17 @@ int launch_scan_b16(const ScanB16Problem& p, int col_splits, const CandLists& L,
             h[5], h[0], h[1], h[2], h[3], h[4]);
   }
   return rc;
+}
+
+int launch_scan_b16(const ScanB16Problem& p, int col_splits, const CandLists& L, void* scratch, const ScanB16Panel& pn, hipStream_t s,
+                    int* grid_out) {
+  return scan_b16_plain(p, col_splits, L, scratch, pn, nullptr, s, grid_out);
+}
+// The same launch with a ceiling per query row (mmf_simtopk_fast_anyk): ceil [n_pad] in the kernel's units.
+int launch_scan_b16_ceil(const ScanB16Problem& p, int col_splits, const CandLists& L, void* scratch, const ScanB16Panel& pn, const float* ceil,
+                         hipStream_t s, int* grid_out) {
+  if (!ceil) { set_error("scan_b16_ceil: ceilings missing"); return MMF_E_INTERNAL; }
+  return scan_b16_plain(p, col_splits, L, scratch, pn, ceil, s, grid_out);
 }
 
 // Segmented scan (mmf_simtopk_segmented): one workgroup per entry of the work table `sched` ([grid][SEG_ENTRY] int32,

@@ -55,7 +55,20 @@ struct SelectArgs {
   float* floor_key_out; uint32_t* floor_id_out;    // optional: (key, local id) of the last entry emitted per row
   int32_t* fail_rows; uint32_t* fail_count; uint32_t* cand_total;
   int maxc;   // staged kernel: candidate slots per wave in dynamic LDS
+  // KEYS instantiations only (the passes of mmf_simtopk_fast_anyk; the others are the kernels they were): the
+  // canonical key of every entry emitted, laid out like out_val (optional); floors also from the grouped re-rank, and indexed by
+  // row when the positions are only the scan's order (is_perm)
+  float* key_out;
 };
+
+// what a KEYS instantiation leaves beside an emitted entry: `last` marks the entry of rank k - 1
+__device__ __forceinline__ void emit_keys(const SelectArgs& a, int64_t pos, int64_t row, int rank, float key, uint32_t id) {
+  if (a.floor_key_out && rank == a.k - 1) {
+    const int64_t fs = a.is_perm ? row : pos;
+    a.floor_key_out[fs] = key; a.floor_id_out[fs] = id;
+  }
+  if (a.key_out) a.key_out[row * a.out_stride + a.out_off + rank] = key;
+}
 
 template <bool VEC4>
 __device__ __forceinline__ float chain_rows(const void* X, int64_t xr, const void* Y, int64_t yr, int64_t d,
@@ -284,7 +297,7 @@ __device__ __forceinline__ int gather_candidates(const SelectArgs& a, int64_t po
   return append_spill(kept);
 }
 
-template <int METRIC, bool VEC4>
+template <int METRIC, bool VEC4, bool KEYS = false>
 __global__ __launch_bounds__(64 * SEL_WAVES) void select_kernel(SelectArgs a) {
   __shared__ float skey[SEL_WAVES][SEL_MAXC];
   __shared__ uint32_t sid[SEL_WAVES][SEL_MAXC];
@@ -357,7 +370,8 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void select_kernel(SelectArgs a) {
     if (lane == 0) {
       a.out_idx[row * a.out_stride + a.out_off + t] = a.col_offset + (int64_t)bi;
       a.out_val[row * a.out_stride + a.out_off + t] = val_from_key<METRIC>(bk);
-      if (a.floor_key_out && t == a.k - 1) { a.floor_key_out[pos] = bk; a.floor_id_out[pos] = bi; }
+      if constexpr (KEYS) emit_keys(a, pos, row, t, bk, bi);
+      else if (a.floor_key_out && t == a.k - 1) { a.floor_key_out[pos] = bk; a.floor_id_out[pos] = bi; }
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -458,7 +472,7 @@ __global__ __launch_bounds__(256) void select_keys_kernel(SelectArgs a) {
   if (lane == 0 && nwait) atomicAdd(a.defer_cnt + (blockIdx.x & 255), (uint32_t)nwait);
 }
 
-template <int METRIC, int DT, int SG>
+template <int METRIC, int DT, int SG, bool KEYS = false>
 __global__ __launch_bounds__(64 * SEL_WAVES) void select_staged_kernel(SelectArgs a) {
   // dynamic LDS: per wave [maxc] keys + [maxc] ids (maxc = lists * cap rounded up to 64), then the tiles
   extern __shared__ __attribute__((aligned(16))) char sel_smem[];
@@ -623,7 +637,8 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void select_staged_kernel(SelectArg
     if (mi != kNoIdx && rank < a.k) {
       a.out_idx[row * a.out_stride + a.out_off + rank] = a.col_offset + (int64_t)mi;
       a.out_val[row * a.out_stride + a.out_off + rank] = val_from_key<METRIC>(mk);
-      if (a.floor_key_out && rank == a.k - 1) { a.floor_key_out[pos] = mk; a.floor_id_out[pos] = mi; }
+      if constexpr (KEYS) emit_keys(a, pos, row, rank, mk, mi);
+      else if (a.floor_key_out && rank == a.k - 1) { a.floor_key_out[pos] = mk; a.floor_id_out[pos] = mi; }
     }
     continue;
   }
@@ -647,7 +662,8 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void select_staged_kernel(SelectArg
     if (lane == 0) {
       a.out_idx[row * a.out_stride + a.out_off + t] = a.col_offset + (int64_t)bi;
       a.out_val[row * a.out_stride + a.out_off + t] = val_from_key<METRIC>(bk);
-      if (a.floor_key_out && t == a.k - 1) { a.floor_key_out[pos] = bk; a.floor_id_out[pos] = bi; }
+      if constexpr (KEYS) emit_keys(a, pos, row, t, bk, bi);
+      else if (a.floor_key_out && t == a.k - 1) { a.floor_key_out[pos] = bk; a.floor_id_out[pos] = bi; }
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_wave_barrier();
@@ -685,7 +701,7 @@ struct GroupLds {
   int first;
 };
 
-template <int METRIC, int DT>
+template <int METRIC, int DT, bool KEYS = false>
 __global__ __launch_bounds__(64 * GR_W) void rerank_group_kernel(SelectArgs a) {
   extern __shared__ __attribute__((aligned(16))) char grp_smem[];
   GroupLds& L = *reinterpret_cast<GroupLds*>(grp_smem);
@@ -956,6 +972,7 @@ __global__ __launch_bounds__(64 * GR_W) void rerank_group_kernel(SelectArgs a) {
       if (lane == 0) {
         a.out_idx[row * a.out_stride + a.out_off + t] = a.col_offset + (int64_t)bi;
         a.out_val[row * a.out_stride + a.out_off + t] = val_from_key<METRIC>(bk);
+        if constexpr (KEYS) emit_keys(a, pos, row, t, bk, bi);
       }
     }
     if (lane == 0) { a.done[pos] = 1; atomicAdd(a.defer_cnt + 256 + (blockIdx.x & 255), 1u); }
@@ -966,24 +983,25 @@ __global__ __launch_bounds__(64 * GR_W) void rerank_group_kernel(SelectArgs a) {
 // The staged re-rank kernel for (dtype, sg candidates per group) with its dynamic LDS bytes for maxc candidates per row, and the
 // same for the grouped re-rank: the one place the dtype picks an instantiation.
 struct StagedPick { void (*kern)(SelectArgs); size_t lds; };
-template <int METRIC, int SG>
+template <int METRIC, int SG, bool KEYS>
 static StagedPick pick_staged_sg(int dtype, int maxc) {
-  return {dtype == MMF_F32 ? select_staged_kernel<METRIC, MMF_F32, SG>
-                           : (dtype == MMF_BF16 ? select_staged_kernel<METRIC, MMF_BF16, SG> : select_staged_kernel<METRIC, MMF_F16, SG>),
+  return {dtype == MMF_F32 ? select_staged_kernel<METRIC, MMF_F32, SG, KEYS>
+                           : (dtype == MMF_BF16 ? select_staged_kernel<METRIC, MMF_BF16, SG, KEYS> : select_staged_kernel<METRIC, MMF_F16, SG, KEYS>),
           sizeof(float) * SEL_WAVES * (SG * SLD + SC) + (size_t)SEL_WAVES * maxc * 8};
 }
-template <int METRIC>
+template <int METRIC, bool KEYS>
 static StagedPick pick_staged(int dtype, int sg, int maxc) {
-  return sg == 8 ? pick_staged_sg<METRIC, 8>(dtype, maxc) : (sg == 16 ? pick_staged_sg<METRIC, 16>(dtype, maxc) : pick_staged_sg<METRIC, 32>(dtype, maxc));
+  return sg == 8 ? pick_staged_sg<METRIC, 8, KEYS>(dtype, maxc)
+                 : (sg == 16 ? pick_staged_sg<METRIC, 16, KEYS>(dtype, maxc) : pick_staged_sg<METRIC, 32, KEYS>(dtype, maxc));
 }
-template <int METRIC>
+template <int METRIC, bool KEYS>
 static StagedPick pick_group(int dtype) {
-  return {dtype == MMF_F32 ? rerank_group_kernel<METRIC, MMF_F32>
-                           : (dtype == MMF_BF16 ? rerank_group_kernel<METRIC, MMF_BF16> : rerank_group_kernel<METRIC, MMF_F16>),
+  return {dtype == MMF_F32 ? rerank_group_kernel<METRIC, MMF_F32, KEYS>
+                           : (dtype == MMF_BF16 ? rerank_group_kernel<METRIC, MMF_BF16, KEYS> : rerank_group_kernel<METRIC, MMF_F16, KEYS>),
           sizeof(GroupLds)};
 }
 
-template <int METRIC>
+template <int METRIC, bool KEYS>
 static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* order_temp, size_t order_temp_bytes, hipStream_t s) {
   const int64_t grid = (a.n_rows + SEL_WAVES - 1) / SEL_WAVES;
   if ((vec4 || staged16) && a.d >= 64) {
@@ -996,7 +1014,7 @@ static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* 
       b.maxc = ((a.lists * a.cap + a.sym_cap + extra + 63) / 64) * 64;
       int sg = (extra == 0) ? 8 : 32;       // rows with overflow entries carry many candidates
       if (extra != 0) if (const char* e = getenv("MMF_SELECT_SG")) { const int v = atoi(e); if (v == 16 || v == 32) sg = v; }
-      const StagedPick sp = pick_staged<METRIC>(a.dtype, sg, b.maxc);
+      const StagedPick sp = pick_staged<METRIC, KEYS>(a.dtype, sg, b.maxc);
       MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sp.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.lds));
       int64_t g = grid;
       b.order_blocks = grid;
@@ -1022,7 +1040,7 @@ static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* 
         // grouped re-rank of 32 consecutive rows of that order on the matrix cores; what it leaves is done by the launch below
         if (a.done && (vec4 || staged16) && !getenv("MMF_SELECT_NO_GROUPS")) {
           MMF_HIP(hipMemsetAsync(a.done, 0, (size_t)a.n_rows, s));
-          const StagedPick gp = pick_group<METRIC>(a.dtype);
+          const StagedPick gp = pick_group<METRIC, KEYS>(a.dtype);
           MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gp.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gp.lds));
           const int64_t groups = ((a.n_rows + GR_Q - 1) / GR_Q + 7) / 8 * 8;
           hipLaunchKernelGGL(gp.kern, dim3((unsigned)groups), dim3(64 * GR_W), gp.lds, s, b);
@@ -1034,7 +1052,7 @@ static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* 
           if (sg == 32) {
             SelectArgs c = b;
             c.only_if = 1;
-            const StagedPick p16 = pick_staged<METRIC>(a.dtype, 16, c.maxc);
+            const StagedPick p16 = pick_staged<METRIC, KEYS>(a.dtype, 16, c.maxc);
             MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(p16.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p16.lds));
             hipLaunchKernelGGL(p16.kern, dim3((unsigned)g), dim3(64 * SEL_WAVES), p16.lds, s, c);
             MMF_LAUNCH_CHECK();
@@ -1050,8 +1068,8 @@ static int launch_select_m(const SelectArgs& a, bool vec4, bool staged16, void* 
       hipLaunchKernelGGL(sp.kern, dim3((unsigned)g), dim3(64 * SEL_WAVES), sp.lds, s, b);
       MMF_LAUNCH_CHECK();
     }
-  } else if (vec4) hipLaunchKernelGGL((select_kernel<METRIC, true>), dim3((unsigned)grid), dim3(64 * SEL_WAVES), 0, s, a);
-  else hipLaunchKernelGGL((select_kernel<METRIC, false>), dim3((unsigned)grid), dim3(64 * SEL_WAVES), 0, s, a);
+  } else if (vec4) hipLaunchKernelGGL((select_kernel<METRIC, true, KEYS>), dim3((unsigned)grid), dim3(64 * SEL_WAVES), 0, s, a);
+  else hipLaunchKernelGGL((select_kernel<METRIC, false, KEYS>), dim3((unsigned)grid), dim3(64 * SEL_WAVES), 0, s, a);
   MMF_LAUNCH_CHECK();
   return MMF_OK;
 }
@@ -1111,18 +1129,24 @@ int launch_select(const SelectProblem& p, const CandLists& L, hipStream_t s) {
   }
   a.out_idx = p.out_idx; a.out_val = p.out_val;
   a.out_stride = p.out_stride > 0 ? p.out_stride : p.k; a.out_off = p.out_off;
-  a.floor_key_out = p.floor_key_out; a.floor_id_out = p.floor_id_out;
+  a.floor_key_out = p.floor_key_out; a.floor_id_out = p.floor_id_out; a.key_out = p.key_out;
   a.fail_rows = p.fail_rows; a.fail_count = p.fail_count; a.cand_total = p.cand_total;
   const bool v4 = p.dtype == MMF_F32 && (p.d % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.X) & 15) == 0) &&
                   ((reinterpret_cast<uintptr_t>(p.Y) & 15) == 0);
   // 16-bit rows take the same staged kernel with 8-byte loads
   const bool s16 = p.dtype != MMF_F32 && (p.d % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.X) & 7) == 0) &&
                    ((reinterpret_cast<uintptr_t>(p.Y) & 7) == 0);
+  // the KEYS instantiations: staged keys, or floors behind the two-launch re-rank of a 16-bit scan (mmf_simtopk_fast_anyk)
+  const bool keys = p.key_out != nullptr || (p.floor_key_out != nullptr && p.two_pass);
   switch (p.metric) {
-    case MMF_DOT: return launch_select_m<MMF_DOT>(a, v4, s16, order_temp, order_temp_bytes, s);
-    case MMF_COSINE: return launch_select_m<MMF_COSINE>(a, v4, s16, order_temp, order_temp_bytes, s);
-    case MMF_NEG_SQ_L2: return launch_select_m<MMF_NEG_SQ_L2>(a, v4, s16, order_temp, order_temp_bytes, s);
-    case MMF_RBF: return launch_select_m<MMF_RBF>(a, v4, s16, order_temp, order_temp_bytes, s);
+    case MMF_DOT: return keys ? launch_select_m<MMF_DOT, true>(a, v4, s16, order_temp, order_temp_bytes, s)
+                              : launch_select_m<MMF_DOT, false>(a, v4, s16, order_temp, order_temp_bytes, s);
+    case MMF_COSINE: return keys ? launch_select_m<MMF_COSINE, true>(a, v4, s16, order_temp, order_temp_bytes, s)
+                                 : launch_select_m<MMF_COSINE, false>(a, v4, s16, order_temp, order_temp_bytes, s);
+    case MMF_NEG_SQ_L2: return keys ? launch_select_m<MMF_NEG_SQ_L2, true>(a, v4, s16, order_temp, order_temp_bytes, s)
+                                    : launch_select_m<MMF_NEG_SQ_L2, false>(a, v4, s16, order_temp, order_temp_bytes, s);
+    case MMF_RBF: return keys ? launch_select_m<MMF_RBF, true>(a, v4, s16, order_temp, order_temp_bytes, s)
+                              : launch_select_m<MMF_RBF, false>(a, v4, s16, order_temp, order_temp_bytes, s);
   }
   set_error("select: unsupported metric %d", p.metric);
   return MMF_E_INVALID;
