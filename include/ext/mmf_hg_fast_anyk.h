@@ -43,8 +43,8 @@ typedef struct mmf_fast_anyk_info {
  * operands) / MMF_PREC_FAST_BF16 run the passes, MMF_PREC_AUTO means MMF_PREC_FAST, MMF_PREC_EXACT forwards to the exact path of
  * mmf_simtopk_ex; col_splits, query_order and profile as in mmf_simtopk_ex (query_order and the symmetric scan apply to the first
  * pass only); select_wait_event is refused.  Where one pass holds k + self the call IS the fast call of mmf_simtopk_ex: same
- * launches, same bits (info: one pass).  d > 1024 with k + self > 20 is refused with MMF_E_UNSUPPORTED (the wide scan has no
- * ceilings yet); d > 1024 with k + self <= 20 is mmf_simtopk_ex's wide scan.
+ * launches, same bits (info: one pass).  d > 1024 with k + self > 20 is refused with MMF_E_UNSUPPORTED by THIS entry
+ * (mmf_simtopk_wide_anyk, mmf_hg_wide_anyk.h, serves it); d > 1024 with k + self <= 20 is mmf_simtopk_ex's wide scan.
  * MMF_ANYK_SHORT_DIV (environment, read per call, default 64, 1 .. 65536): a pass emits the largest yield that leaves at most
  * n / MMF_ANYK_SHORT_DIV unflagged rows short of it; results do not depend on it.
  * stats (may be NULL): those of the first pass, with fallback_rows summed over the passes.

@@ -75,6 +75,9 @@ from .cross_segments_wide import cross_segments_route, cross_segments_wide_table
 from . import fast_anyk  # noqa: F401,E402
 from .fast_anyk import fast_anyk_plan, simtopk_fast_any_k  # noqa: F401,E402
 
+from . import wide_anyk  # noqa: F401,E402
+from .wide_anyk import simtopk_wide_any_k, wide_anyk_plan  # noqa: F401,E402
+
 from . import wide_scan  # noqa: F401,E402
 from .wide_scan import list_capacity, wide_scan_supported  # noqa: F401,E402
 
@@ -94,4 +97,5 @@ __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combin
            "cross_segments", "simtopk_cross_segments", "cross_segments_table", "cross_segment_knn_edges",
            "cross_segments16", "simtopk_cross_segments_fast", "cross_segments_fast_table",
            "cross_segments_wide", "simtopk_cross_segments_wide", "cross_segments_wide_table", "cross_segments_route",
-           "fast_anyk", "simtopk_fast_any_k", "fast_anyk_plan"]
+           "fast_anyk", "simtopk_fast_any_k", "fast_anyk_plan",
+           "wide_anyk", "simtopk_wide_any_k", "wide_anyk_plan"]

@@ -132,6 +132,11 @@ CROSS_SEGW_EXPORTS = ["mmf_simtopk_cross_segments_wide", "mmf_cross_segments_wid
 FAST_ANYK_EXPORTS = ["mmf_simtopk_fast_anyk", "mmf_fast_anyk_plan"]
 FAST_ANYK_MAX_PASSES = 16
 
+# The wide 16-bit top-k for any k (include/ext/mmf_hg_wide_anyk.h): an addition to ABI version 3 in a header of its
+# own; the twin of the two entries above for 1024 < d <= 4096 (same info struct, same synchronisation: once per pass, once more in a
+# pass that sends rows to the exact rescan; mmf_wide_anyk_plan is host-only).  Pinned by tests/test_wide_anyk_cpu.py.
+WIDE_ANYK_EXPORTS = ["mmf_simtopk_wide_anyk", "mmf_wide_anyk_plan"]
+
 
 class FastAnykInfo(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
@@ -240,6 +245,10 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_fast_anyk.restype = ci
     L.mmf_fast_anyk_plan.argtypes = [i64, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     L.mmf_fast_anyk_plan.restype = ci
+    L.mmf_simtopk_wide_anyk.argtypes = list(L.mmf_simtopk_fast_anyk.argtypes)
+    L.mmf_simtopk_wide_anyk.restype = ci
+    L.mmf_wide_anyk_plan.argtypes = list(L.mmf_fast_anyk_plan.argtypes)
+    L.mmf_wide_anyk_plan.restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

@@ -1716,7 +1716,8 @@ static void anyk_record(mmf_fast_anyk_info* info, int pass, int yield, int ghost
   info->yield[pass] = yield; info->ghost_max[pass] = ghost_max; info->exact_rows[pass] = exact_rows;
 }
 
-// The passes (r.precision MMF_PREC_FAST or _FAST_BF16, d <= 1024, k + self beyond one pass).  Pass 0 is the fast call at the full
+// The passes (r.precision MMF_PREC_FAST or _FAST_BF16, k + self beyond one pass; d <= 1024: mmf_simtopk_fast_anyk, above it the wide
+// scan's launches take the narrow ones' slots: mmf_simtopk_wide_anyk).  Pass 0 is the fast call at the full
 // depth (FastTail::run), leaving every row's floor.  A later pass: ceilings from the floors, the plain scan under them at the full
 // depth, the re-rank into the staging rows, the count of each row's certified entries (one host synchronisation: histogram and
 // flagged rows), the yield t, the emit of t entries per row, and the exact rescan with floors of the rows that could not.
@@ -1724,7 +1725,8 @@ static int fast_anyk_run(Request& r, const mmf_simtopk_opts* opts, mmf_fast_anyk
   const int64_t n = r.n, m = r.m;
   const hipStream_t s = r.call.s;
   const int k = r.k, self1 = r.exclude_self ? 1 : 0, depth = anyk_depth(r.d), K = depth - self1;
-  const int dp = scan_bf16_dp(r.d);
+  const bool wide = r.d > 1024;   // launch_scan_b16w_ceilings / _ceil for launch_scan_b16_ceilings / _ceil; no query order (FastTail)
+  const int dp = wide ? scan_b16w_dp(r.d) : scan_bf16_dp(r.d);
   FastPrep fp(r, dp, r.precision == MMF_PREC_FAST);
   // (the symmetric scan needs the 15-entry lists of k + self <= 11: it never applies at the full depth)
   FastTail ft(n, m, depth, opts ? opts->col_splits : 0, dp);
@@ -1765,6 +1767,11 @@ static int fast_anyk_run(Request& r, const mmf_simtopk_opts* opts, mmf_fast_anyk
   pn.seed = ft.seed; pn.seed_stride = ft.n_seed; pn.share = ft.splits > 1 ? 1 : 0;
   const ScanB16Problem sp(fp.Q, fp.C, n, m, (m + 255) / 256 * 256, dp, r.d, fp.f16, r.metric, depth);
   const AnykStage st{sidx, sval, skey, n, K, r.col_offset};
+  CandLists Lw = L;   // wide: what the scan writes — without the sink the overflow lists stay zeroed and select reads them as empty
+  if (wide) {
+    if (!wide_sink_mode()) { Lw.spill_cnt = nullptr; Lw.spill_ids = nullptr; Lw.spill_cap = 0; Lw.spill_stacks = 0; }
+    pn.sunk = ft.seed + 2 * ft.n_seed;
+  }
   int done = K;
   // kq more entries, from the floors on, for `cnt` rows by the exact scan; floors left unless these are the call's last entries
   auto exact_rows = [&](const int32_t* rows, int64_t cnt, int kq) -> int {
@@ -1788,12 +1795,14 @@ static int fast_anyk_run(Request& r, const mmf_simtopk_opts* opts, mmf_fast_anyk
   };
   for (int pass = 1; done < k; ++pass) {
     if (pass >= MMF_FAST_ANYK_MAX_PASSES - 1) return finish_exact(pass);
-    MMF_TRY(launch_scan_b16_ceilings(sp, L.cap, fkey, fp.rx, fp.max_n, r.lambda, fp.n_pad, ceil, s));
+    if (wide) MMF_TRY(launch_scan_b16w_ceilings(sp, fkey, fp.rx, fp.max_n, r.lambda, fp.n_pad, ceil, s));
+    else MMF_TRY(launch_scan_b16_ceilings(sp, L.cap, fkey, fp.rx, fp.max_n, r.lambda, fp.n_pad, ceil, s));
     MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
     MMF_TRY(ft.flags.zero(s));
     MMF_HIP(hipMemsetAsync(ft.seed, 0x80, (size_t)ft.n_seed * 4 * ft.seed_stripes(), s));
     MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
-    MMF_TRY(launch_scan_b16_ceil(sp, ft.splits, L, ft.scan_scratch, pn, ceil, s, nullptr));
+    if (wide) MMF_TRY(launch_scan_b16w_ceil(sp, ft.splits, Lw, pn, ceil, s, nullptr));
+    else MMF_TRY(launch_scan_b16_ceil(sp, ft.splits, L, ft.scan_scratch, pn, ceil, s, nullptr));
     MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
     SelectProblem q = r.select();
     q.k = K; q.out_idx = sidx; q.out_val = sval; q.key_out = skey; q.out_stride = K;
@@ -1849,6 +1858,61 @@ int mmf_simtopk_fast_anyk(const void* X, int64_t n, const void* Y, int64_t m, in
     if (fast && d > 1024 && r.kk > 20) {
       set_error("%s: d = %lld, k = %d is beyond one pass of the wide 16-bit scan, which has no ceilings (d <= 1024 is served for any k)",
                 r.call.who, (long long)d, k);
+      return MMF_E_UNSUPPORTED;
+    }
+    return MMF_OK;
+  }));
+  if (n == 0) return MMF_OK;
+  if (!multi) {
+    MMF_TRY(simtopk_run(r, opts));
+    anyk_record(info, 0, k, 0, r.stats ? r.stats->fallback_rows : 0);
+    return MMF_OK;
+  }
+  r.precision = prec;
+  return fast_anyk_run(r, opts, info);
+}
+
+// ---- mmf_simtopk_wide_anyk (include/ext/mmf_hg_wide_anyk.h) ---------------------------------------------------
+int mmf_wide_anyk_plan(int64_t d, int k, int exclude_self, int* scan_kk, int* first_yield, int* min_passes) {
+  if (d < 1 || k < 1) { set_error("wide_anyk_plan: need d >= 1 and k >= 1 (got d = %lld, k = %d)", (long long)d, k); return MMF_E_INVALID; }
+  if (d <= 1024) { set_error("wide_anyk_plan: d = %lld is served by mmf_fast_anyk_plan (this one: 1024 < d <= 4096)", (long long)d); return MMF_E_UNSUPPORTED; }
+  if (d > 4096) { set_error("wide_anyk_plan: d = %lld is beyond the wide 16-bit scan (1024 < d <= 4096)", (long long)d); return MMF_E_UNSUPPORTED; }
+  const int self1 = exclude_self ? 1 : 0, kk = k + self1;
+  const bool one = scan_b16w_supported(d, kk) != 0;
+  const int depth = one ? kk : anyk_depth(d), per = anyk_depth(d) - self1;
+  if (scan_kk) *scan_kk = depth;
+  if (first_yield) *first_yield = depth - self1;
+  if (min_passes) *min_passes = one ? 1 : 1 + (k - (depth - self1) + per - 1) / per;
+  return one ? 0 : 1;
+}
+
+int mmf_simtopk_wide_anyk(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric, float lambda,
+                          int k, int exclude_self, int64_t row_offset, int64_t col_offset, int64_t* out_idx, float* out_val,
+                          const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream,
+                          mmf_fast_anyk_info* info) {
+  if (!Y) { Y = X; m = n; }
+  if (info) memset(info, 0, sizeof(*info));
+  mmf_simtopk_stats own_stats;   // info reports the first pass's flagged rows, which the call counts in its stats
+  Request r{Call("simtopk_wide_anyk", device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, row_offset, col_offset,
+            out_idx, out_val, stats ? stats : (info ? &own_stats : nullptr), opts && opts->profile};
+  r.wide_ok = true;
+  const int asked = opts ? opts->precision : MMF_PREC_AUTO;
+  const int prec = asked == MMF_PREC_AUTO ? MMF_PREC_FAST : asked;
+  const bool fast = prec != MMF_PREC_EXACT;
+  // more than one pass: the wide scan serves d but not k + self (the checks below refuse what makes this meaningless)
+  const bool multi = fast && d > 1024 && d <= 4096 && k >= 1 && !scan_b16w_supported(d, k + (exclude_self ? 1 : 0));
+  MMF_TRY(r.check(multi ? MMF_PREC_EXACT : prec, false, [&] {
+    if (asked < MMF_PREC_AUTO || asked > MMF_PREC_FAST_BF16) { set_error("%s: bad precision %d", r.call.who, asked); return MMF_E_INVALID; }
+    if (opts && opts->select_wait_event) {
+      set_error("%s: select_wait_event is not supported (every pass reads the rows; wait on the stream before the call)", r.call.who);
+      return MMF_E_UNSUPPORTED;
+    }
+    if (d <= 1024) {
+      set_error("%s: d = %lld is not above 1024: call mmf_simtopk_fast_anyk, which serves d <= 1024 for any k", r.call.who, (long long)d);
+      return MMF_E_UNSUPPORTED;
+    }
+    if (fast && d > 4096) {
+      set_error("%s: d = %lld is beyond the wide 16-bit scan (1024 < d <= 4096; MMF_PREC_EXACT serves it)", r.call.who, (long long)d);
       return MMF_E_UNSUPPORTED;
     }
     return MMF_OK;

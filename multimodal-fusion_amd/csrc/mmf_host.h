@@ -22,6 +22,7 @@
 #include "../../include/ext/mmf_hg_cross_seg16.h"
 #include "../../include/ext/mmf_hg_cross_segw.h"
 #include "../../include/ext/mmf_hg_fast_anyk.h"
+#include "../../include/ext/mmf_hg_wide_anyk.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -432,6 +433,15 @@ int scan_b16w_dp(int64_t d);
 int scan_b16w_queries_per_block();
 int scan_b16w_col_tile();
 int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L, const ScanB16Panel& pn, hipStream_t s, int* grid_out);
+// The later passes of mmf_simtopk_wide_anyk, as launch_scan_b16_ceil / launch_scan_b16_ceilings serve
+// mmf_simtopk_fast_anyk: the plain launch with a ceiling per query row — a scanned value above ceil[row] ([n_pad], the kernel's
+// units, +inf for padding rows; n_pad covers whole 128-row blocks) reaches no list, overflow list or threshold — and the kernel
+// that turns the rows' floors (canonical keys, [p.n_rows]) into those ceilings with the wide scan's margin: rx the rows' canonical
+// scalars, max_n the word the operand images took their scale from
+int launch_scan_b16w_ceil(const ScanB16Problem& p, int col_splits, const CandLists& L, const ScanB16Panel& pn, const float* ceil, hipStream_t s,
+                          int* grid_out);
+int launch_scan_b16w_ceilings(const ScanB16Problem& p, const float* floor_key, const float* rx, const uint32_t* max_n, float lambda, int64_t n_pad,
+                              float* ceil, hipStream_t s);
 // Segmented form: one workgroup per entry of the device work table `sched` ([grid][8] int32: query position in the
 // query image, row of X, real queries, first / end tile in the candidate image, id offset, list slot).  p.n_rows: rows of X (lists,
 // thresholds and margins are indexed by them); both images are padded per segment to 128 rows.  lists == L.lists == 2 x the

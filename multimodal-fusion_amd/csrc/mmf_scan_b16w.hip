@@ -68,6 +68,12 @@
 // slots.  Column splits: the lanes leave the row's best written key in ScanB16WArgs::sunk and wide_seed_union_kernel empties
 // the row's overflow list if that key lies below the row's settled threshold (the slots stay used while the scan runs).
 // Either way every discarded key lies below a proven threshold: outside the band.
+//
+// Ceilings (the CEIL instantiations).  A call with more neighbours than one pass holds (mmf_simtopk_wide_anyk) runs
+// the plain launch again with a ceiling per query row: ceil_i = map_i(floor key) + E1_i + E2_i (wide_ceil_kernel; E1, E2 as above),
+// so that no column ranking after the row's floor is scanned above it.  The epilogue's hit branch sets the gathered values above
+// the ceiling to -inf before they are offered; everything said above about lists, thresholds and overflow lists then holds for the
+// columns at or below the ceiling.
 #include "mmf_dev.h"
 #include "mmf_host.h"
 
@@ -130,6 +136,9 @@ struct ScanB16WArgs {
   // XSEG kernels only (launch_scan_b16w_xseg): [n_pad][2] per query row, first row and row count of the columns the row may not
   // take (its own segment's rows of Y); rows of the padding exclude nothing
   const uint32_t* bounds;
+  // CEIL kernels only (launch_scan_b16w_ceil): [n_pad] per query row, the largest scanned value the row may still take, in the
+  // kernel's own units (bias and 2^(2e) scale included); padding rows: +inf
+  const float* ceil;
 };
 
 // One entry of the segmented work table: a workgroup = one row block of one segment against one column range of that segment.
@@ -313,8 +322,15 @@ constexpr size_t scan_b16w_lds(int cap) { return (size_t)2 * W_STAGEB + (size_t)
 // row of the block excludes, and on the tiles of the entry's mask window the epilogue sets the accumulators of a query's excluded
 // columns (a.bounds) to -inf before anything reads them: such a value is below every threshold (the first one is -FLT_MAX), so it
 // reaches neither the tile maxima's test, nor a list, nor proven / lost / seed — exactly like the -inf bias of a padding column.
-template <bool F16, int CAP, bool SEG = false, bool SINK = false, bool XSEG = false>
+// CEIL (the plain schedule only, with or without SINK; mmf_simtopk_wide_anyk): the later passes of a call with more
+// neighbours than one pass holds.  Every query row comes with a ceiling a.ceil[row]; a value above it belongs to a column the row has
+// already emitted.  Such a value is above the row's threshold by construction, so it takes the epilogue's hit branch anyway: the
+// compare sits THERE, on the lane's 16 gathered values before they are offered — the sub-tile's 14 v_max + two compares are
+// untouched, and the ceiling is loaded inside the branch, so the k-loop carries no register for it.  A value set to -inf there
+// reaches no list, overflow list or sink slot, proven, lost, seed or threshold.
+template <bool F16, int CAP, bool SEG = false, bool SINK = false, bool XSEG = false, bool CEIL = false>
 __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
+  static_assert(!CEIL || (!SEG && !XSEG), "per-row ceilings: the plain schedule only");
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   char* stages = smem;                                                   // [2][W_STAGEB]
   float* cbs = reinterpret_cast<float*>(smem + 2 * W_STAGEB);            // [2][W_CT] bias of the tile being accumulated / the next
@@ -522,6 +538,11 @@ __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
               v[8 + 4 * cb + j] = __shfl_xor(give, 16);
             }
           }
+          if constexpr (CEIL) {   // columns the row has already emitted (and nothing that ranks after its floor: §4.28) lie above its ceiling
+            const float ce = a.ceil[qpos];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[r] = (v[r] > ce) ? kNegInf : v[r];
+          }
           // v[0..7]: rows of this lane's group g, v[8..15]: rows of the partner's group g ^ 1
           const int g4 = 4 * g;
           auto rowof = [g4](int r) -> uint32_t { return (uint32_t)((g4 ^ ((r & 8) >> 1)) + (r & 3) + 16 * ((r >> 2) & 1)); };
@@ -612,7 +633,62 @@ __global__ __launch_bounds__(256) void wide_seed_union_kernel(const uint32_t* ca
   if (sunk && sunk[row] < settled) spill_cnt[row] = 0u;   // (no key written: the count is 0 already)
 }
 
-template <int CAP, bool SEG = false, bool SINK = false, bool XSEG = false>
+// The ceilings of the CEIL kernels (ceil_kernel of mmf_scan_bf16.hip with THIS scan's margin).  Row i has emitted
+// everything down to its floor, the canonical key fk_i; a column that ranks after the floor has a key <= fk_i, so its real-number
+// target Q is at most map_i(fk_i) + E2_i and its scanned value at most map_i(fk_i) + E1_i + E2_i.  map_i turns a canonical key into
+// Q units (Q = bias_j + u_i . u_j, operands scaled by s):
+//   dot, cosine: s^2 key;   -|x - y|^2: s^2 (key + n_i) / 2;   rbf (key = -lambda |x - y|^2): s^2 (key / lambda + n_i) / 2.
+// E1 + E2 is half the scan's margin — the margin block at the top of scan_b16w_kernel copied term for term (dp = d rounded up to
+// 128, no slot-bit term; the kernel keeps its own text so that its instantiations stay the instruction streams they were), the
+// scale the block at the top of prep_half_kernel.  2^-21 of the terms' magnitudes covers the f32 rounding of the map itself and of
+// the rbf key's product with lambda; the sum is rounded up by one more ulp.
+struct WideCeilArgs {
+  const float* floor_key; const float* rx;   // [n] the rows' floors and canonical row scalars
+  const float *q_zn, *q_rn, *q_un; const uint32_t* maxima; const uint32_t* max_n;
+  int64_t n, n_pad; int metric, d, dp; float lambda;
+  float* ceil;                               // [n_pad]
+};
+__global__ void wide_ceil_kernel(WideCeilArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n_pad) return;
+  if (i >= a.n) { a.ceil[i] = __builtin_huge_valf(); return; }
+  // the operands' common power-of-two scale; max_n: float bits of the largest squared norm (unused for cosine)
+  float s;
+  {
+    float mx = (a.metric == MMF_COSINE) ? 1.0f : __builtin_sqrtf(__uint_as_float(a.max_n[0]));
+    int ex = 0;
+    if (mx > 0.0f && mx < __builtin_huge_valf()) (void)frexpf(mx, &ex); else ex = 9;
+    int e = 9 - ex;
+    e = e < -100 ? -100 : (e > 100 ? 100 : e);
+    s = ldexpf(1.0f, e);
+  }
+  const float s2 = s * s;
+  const float fk = a.floor_key[i];
+  float q, mag;
+  if (a.metric == MMF_DOT || a.metric == MMF_COSINE) { q = s2 * fk; mag = fabsf(q); }
+  else {
+    const float t = (a.metric == MMF_RBF) ? fk / a.lambda : fk, ni = a.rx[i];
+    q = 0.5f * s2 * (t + ni); mag = 0.5f * s2 * (fabsf(t) + ni);
+  }
+  float margin;
+  {
+    const float ZB = __uint_as_float(a.maxima[0]), RB = __uint_as_float(a.maxima[1]);
+    const float UB = __uint_as_float(a.maxima[2]), CB = __uint_as_float(a.maxima[3]);
+    const float zn = a.q_zn[i], rn = a.q_rn[i], un = a.q_un[i];
+    const float g_acc = (float)(a.dp + 8) * 5.9604645e-8f;
+    const float g_chain = (float)(a.d + 2) * 5.9604645e-8f;
+    const float e1 = rn * ZB + un * RB + g_acc * (zn * ZB + CB);
+    float e2;
+    if (a.metric == MMF_DOT) e2 = g_chain * un * UB;
+    else if (a.metric == MMF_COSINE) e2 = (g_chain + 4.7683716e-7f) * un * UB * 1.01f;
+    else e2 = g_chain * un * UB + 2.3841858e-7f * (un * un + UB * UB);
+    margin = 2.0f * (e1 + e2) * 1.001f + 1e-30f;
+  }
+  const float c = q + 0.5f * margin + 4.7683716e-7f * mag;
+  a.ceil[i] = (c == c) ? nextafterf(c, __builtin_huge_valf()) : __builtin_huge_valf();
+}
+
+template <int CAP, bool SEG = false, bool SINK = false, bool XSEG = false, bool CEIL = false>
 int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) {
   const size_t lds = scan_b16w_lds(CAP);
   auto go = [&](auto kern) -> int {
@@ -621,6 +697,10 @@ int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) 
     MMF_LAUNCH_CHECK();
     return MMF_OK;
   };
+  if constexpr (CEIL) {
+    if (f16) return go(scan_b16w_kernel<true, CAP, false, SINK, false, true>);
+    return go(scan_b16w_kernel<false, CAP, false, SINK, false, true>);
+  }
   if constexpr (SINK) {
     if (f16) return go(scan_b16w_kernel<true, CAP, SEG, true>);
     return go(scan_b16w_kernel<false, CAP, SEG, true>);
@@ -689,7 +769,14 @@ int launch_scan_b16w_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t
 // form L.spill_stacks names (two stacks need the one list pair); without them the kernels that lose what a list cannot hold.
 // pn.sunk (optional, counter form): the rows' best written keys, memset like pn.seed; with it a row whose overflow entries all
 // lie below its settled threshold gets its overflow list emptied.
+static int scan_b16w_plain(const ScanB16Problem& p, int col_splits, const CandLists& L, const ScanB16Panel& pn, const float* ceil, hipStream_t s,
+                           int* grid_out);
 int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L, const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
+  return scan_b16w_plain(p, col_splits, L, pn, nullptr, s, grid_out);
+}
+// The launch itself.  ceil: nullptr, or the rows' ceilings (CEIL kernels).
+static int scan_b16w_plain(const ScanB16Problem& p, int col_splits, const CandLists& L, const ScanB16Panel& pn, const float* ceil, hipStream_t s,
+                           int* grid_out) {
   if (p.n_rows <= 0 || p.m <= 0) return MMF_OK;
   if (!scan_b16w_supported(p.d, p.kk) || p.dp != scan_b16w_dp(p.d)) {
     set_error("scan_b16w: d = %lld (padded %d), k + self = %d outside 1024 < d <= 4096, k + self <= 20", (long long)p.d, p.dp, p.kk);
@@ -720,16 +807,37 @@ int launch_scan_b16w(const ScanB16Problem& p, int col_splits, const CandLists& L
     a.spill_cnt = L.spill_cnt; a.spill_ids = L.spill_ids; a.spill_cap = L.spill_cap; a.spill_stacks = L.spill_stacks;
     a.sunk = L.spill_stacks ? nullptr : pn.sunk;
   }
+  a.ceil = ceil;
   const int64_t row_blocks = (p.n_rows + W_QT - 1) / W_QT;
   const int64_t grid = row_blocks * col_splits;
   if (grid_out) *grid_out = (int)grid;
-  if (sink) MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, false, true>(a, p.f16, grid, s)) : (launch_b16w_t<W_CAP_BIG, false, true>(a, p.f16, grid, s)));
+  if (ceil && sink) MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, false, true, false, true>(a, p.f16, grid, s)) : (launch_b16w_t<W_CAP_BIG, false, true, false, true>(a, p.f16, grid, s)));
+  else if (ceil) MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, false, false, false, true>(a, p.f16, grid, s)) : (launch_b16w_t<W_CAP_BIG, false, false, false, true>(a, p.f16, grid, s)));
+  else if (sink) MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, false, true>(a, p.f16, grid, s)) : (launch_b16w_t<W_CAP_BIG, false, true>(a, p.f16, grid, s)));
   else MMF_TRY(L.cap == W_CAP_SMALL ? launch_b16w_t<W_CAP_SMALL>(a, p.f16, grid, s) : launch_b16w_t<W_CAP_BIG>(a, p.f16, grid, s));
   if (col_splits > 1) {
     hipLaunchKernelGGL(wide_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
                        p.kk, pn.seed, p.n_rows, a.sunk, a.sunk ? a.spill_cnt : nullptr);
     MMF_LAUNCH_CHECK();
   }
+  return MMF_OK;
+}
+
+// The same launch with a ceiling per query row (mmf_simtopk_wide_anyk): ceil [n_pad] in the kernel's units, n_pad
+// covering whole 128-row blocks.
+int launch_scan_b16w_ceil(const ScanB16Problem& p, int col_splits, const CandLists& L, const ScanB16Panel& pn, const float* ceil, hipStream_t s,
+                          int* grid_out) {
+  if (!ceil) { set_error("scan_b16w_ceil: ceilings missing"); return MMF_E_INTERNAL; }
+  return scan_b16w_plain(p, col_splits, L, pn, ceil, s, grid_out);
+}
+// The ceilings of that launch from the rows' floors (canonical keys, [p.n_rows]): rx the rows' canonical scalars, max_n the word the
+// operand images took their scale from; ceil [n_pad], +inf for the padding rows.
+int launch_scan_b16w_ceilings(const ScanB16Problem& p, const float* floor_key, const float* rx, const uint32_t* max_n, float lambda, int64_t n_pad,
+                              float* ceil, hipStream_t s) {
+  if (n_pad < (p.n_rows + W_QT - 1) / W_QT * W_QT) { set_error("scan_b16w_ceilings: %lld ceilings do not cover the row blocks of %lld rows", (long long)n_pad, (long long)p.n_rows); return MMF_E_INTERNAL; }
+  WideCeilArgs a{floor_key, rx, p.q_zn, p.q_rn, p.q_un, p.maxima, max_n, p.n_rows, n_pad, p.metric, (int)p.d, p.dp, lambda, ceil};
+  wide_ceil_kernel<<<dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s>>>(a);
+  MMF_LAUNCH_CHECK();
   return MMF_OK;
 }
 
