@@ -137,6 +137,12 @@ FAST_ANYK_MAX_PASSES = 16
 # pass that sends rows to the exact rescan; mmf_wide_anyk_plan is host-only).  Pinned by tests/test_wide_anyk_cpu.py.
 WIDE_ANYK_EXPORTS = ["mmf_simtopk_wide_anyk", "mmf_wide_anyk_plan"]
 
+# The segmented 16-bit top-k for any k (include/ext/mmf_hg_seg_anyk.h): an addition to ABI version 3 in a header of
+# its own; the cohort form of mmf_simtopk_fast_anyk for d <= 1024 (same info struct).  mmf_simtopk_segmented_fast_anyk synchronises
+# once per pass (fail counts and yield histogram together) and once more in a pass that sends rows to the exact rescan (the rows are
+# read and grouped per segment on the host); mmf_segmented_anyk_plan is host-only.  Pinned by tests/test_segmented_anyk_cpu.py.
+SEG_ANYK_EXPORTS = ["mmf_simtopk_segmented_fast_anyk", "mmf_segmented_anyk_plan"]
+
 
 class FastAnykInfo(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
@@ -249,6 +255,10 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_wide_anyk.restype = ci
     L.mmf_wide_anyk_plan.argtypes = list(L.mmf_fast_anyk_plan.argtypes)
     L.mmf_wide_anyk_plan.restype = ci
+    L.mmf_simtopk_segmented_fast_anyk.argtypes = list(L.mmf_simtopk_segmented.argtypes) + [ctypes.POINTER(FastAnykInfo)]
+    L.mmf_simtopk_segmented_fast_anyk.restype = ci
+    L.mmf_segmented_anyk_plan.argtypes = list(L.mmf_fast_anyk_plan.argtypes)
+    L.mmf_segmented_anyk_plan.restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

@@ -24,6 +24,23 @@ int launch_floor_move(const int32_t* rows, int64_t cnt, float* row_key, uint32_t
   return MMF_OK;
 }
 
+// the segmented call's floors between ids that are rows of Y (their home) and ids local to the row's segment (what an exact pass over
+// one segment's columns reads and leaves); uint32 arithmetic, so the two directions undo each other exactly
+__global__ void floor_rebase_kernel(const int32_t* rows, int64_t cnt, uint32_t* floor_id, const int32_t* col0, int add) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= cnt) return;
+  const int64_t r = rows[p];
+  const uint32_t c = (uint32_t)col0[r];
+  floor_id[r] = add ? floor_id[r] + c : floor_id[r] - c;
+}
+
+int launch_floor_rebase(const int32_t* rows, int64_t cnt, uint32_t* floor_id, const int32_t* col0, bool add, hipStream_t s) {
+  if (cnt <= 0) return MMF_OK;
+  hipLaunchKernelGGL(floor_rebase_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, rows, cnt, floor_id, col0, add ? 1 : 0);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
 __global__ void anyk_iota_kernel(int32_t* rows, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) rows[i] = (int32_t)i;

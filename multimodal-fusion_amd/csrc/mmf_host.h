@@ -23,6 +23,7 @@
 #include "../../include/ext/mmf_hg_cross_segw.h"
 #include "../../include/ext/mmf_hg_fast_anyk.h"
 #include "../../include/ext/mmf_hg_wide_anyk.h"
+#include "../../include/ext/mmf_hg_seg_anyk.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -403,6 +404,14 @@ int scan_b16_queries_per_block(int dp);
 size_t scan_b16_seg_scratch_bytes(int64_t grid, int dp, int cap);
 int launch_scan_b16_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const CandLists& L, void* scratch,
                         const ScanB16Panel& pn, hipStream_t s);
+// The later passes of mmf_simtopk_segmented_fast_anyk: the table-driven launch with a ceiling per OPERAND POSITION
+// (ceil [nq_pad], positions of the segment-padded query image; +inf for padding) — full-depth lists only (32 entries at d <= 512, the
+// split-k pair kernel at d <= 1024) — and the ceilings of those positions: gather [n_pos] is the row of X at each position (-1:
+// padding), floor_key and rx are indexed by row of X, the margin's maxima are those of the whole padded candidate image
+int launch_scan_b16_seg_ceil(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const CandLists& L, void* scratch,
+                             const ScanB16Panel& pn, const float* ceil, hipStream_t s);
+int launch_scan_b16_ceilings_gather(const ScanB16Problem& p, int cap, const int32_t* gather, int64_t n_pos, const float* floor_key, const float* rx,
+                                    const uint32_t* max_n, float lambda, int64_t nq_pad, float* ceil, hipStream_t s);
 // the cross-segment flavour: plain images on both sides, `sched` a device copy of cross_seg16_table, `bounds`
 // [n_pad][2] the excluded column range (first, count) of every query row, L.lists = the table's list count, pn.share as the table says
 int launch_scan_b16_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, const CandLists& L,
@@ -423,6 +432,10 @@ int launch_anyk_iota(int32_t* rows, int64_t n, hipStream_t s);
 // floors of the gathered rows rows[0 .. cnt): from their row-indexed home to a position-indexed block, or (back) home again
 int launch_floor_move(const int32_t* rows, int64_t cnt, float* row_key, uint32_t* row_id, float* pos_key, uint32_t* pos_id, bool back,
                       hipStream_t s);
+// mmf_simtopk_segmented_fast_anyk keeps the floors' ids as rows of Y; an exact pass over the gathered rows of one
+// segment reads and leaves ids local to that segment's columns.  floor_id[rows[i]] -= col0[rows[i]] (add: +=) for i < cnt, col0 [n] the
+// first row of Y of each row's segment
+int launch_floor_rebase(const int32_t* rows, int64_t cnt, uint32_t* floor_id, const int32_t* col0, bool add, hipStream_t s);
 
 // mmf_scan_b16w.hip: the wide 16-bit scan (1024 < d <= 4096, k + self <= 20) — both operands streamed through
 // LDS in k-chunks.  Same operand images (dp = d rounded up to 128), lists, threshold buffers and audit as launch_scan_b16; no

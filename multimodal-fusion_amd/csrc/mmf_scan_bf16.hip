@@ -242,8 +242,10 @@ struct ScanB16Args {
   // XSEG kernels only (launch_scan_b16_xseg): [n_pad][2] per query row, first row and row count of the columns the row may not
   // take (its own segment's rows of Y; padding rows: 0, 0)
   const uint32_t* xbounds;
-  // CEIL kernels only (launch_scan_b16_ceil): [n_pad] per query row, the largest scanned value the row may still take, in the
-  // kernel's own units (bias and 2^(2e) scale included); padding rows: +inf
+  // CEIL kernels only (launch_scan_b16_ceil, launch_scan_b16_seg_ceil): [n_pad] per query row, the largest scanned value the row may
+  // still take, in the kernel's own units (bias and 2^(2e) scale included); padding rows: +inf.  Indexed by OPERAND POSITION (qop), like
+  // q_zn / q_rn / q_un: the plain schedule's positions are its rows, the table-driven (SEG) one's are positions of the segment-padded
+  // query image ([nq_pad]; launch_scan_b16_ceilings_gather fills them through the position -> row table)
   const float* ceil;
 };
 
@@ -339,7 +341,8 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 // a.xbounds and sets each of its 16 values whose column lies inside to -inf — before max_qb, acc_prev and filter, so a masked value
 // reaches no list, overflow list, threshold, seed or lost.  SPLITK: only the owner wave masks; -inf survives the partner's partial sums.
 //
-// CEIL (mmf_simtopk_fast_anyk; the plain schedule only): the later passes of a call with more neighbours than one
+// CEIL (mmf_simtopk_fast_anyk, DESIGN.md §4.27: the plain schedule; mmf_simtopk_segmented_fast_anyk, §4.29: with SEG, four depth
+// shapes — launch_b16_seg_ceil_for): the later passes of a call with more neighbours than one
 // pass holds.  Every query row comes with a ceiling a.ceil[row]; a value above it belongs to a column the row has already emitted.
 // Such a value is above the row's threshold by construction, so it enters the list code as a hit anyway: the compare sits THERE, on
 // the lane's 16 gathered values before they are offered — the tile loop's v_max + two compares are untouched, and the ceiling is
@@ -348,7 +351,7 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0, bool XSEG = false,
           bool CEIL = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(ScanB16Args a) {
-  static_assert(!CEIL || (!SEG && SYM == 0 && !DBG && !XSEG), "per-row ceilings: the plain schedule only");
+  static_assert(!CEIL || (SYM == 0 && !DBG && !XSEG), "per-row ceilings: the plain and the table-driven schedule only");
   static_assert(!SPLITK || (TPB == 1 && NW == 8 && (KS % 8) == 0), "split-k pairs");
   static_assert(SYM == 0 || (!SPLITK && !SEG && !DBG && TPB == 2), "symmetric schedule: the d = 512 kernel only");
   static_assert(!XSEG || (SEG && SYM == 0 && !DBG), "the cross-segment mask rides on the table-driven schedule");
@@ -986,17 +989,27 @@ struct CeilArgs {
   const float *q_zn, *q_rn, *q_un; const uint32_t* maxima; const uint32_t* max_n;
   int64_t n, n_pad; int metric, d, dp, cap; float lambda;
   float* ceil;                               // [n_pad]
+  // GATHER (the segmented passes): i is a position of the segment-padded query image, n the positions in use and
+  // gather [n] the row of X at each (-1: padding inside a segment's last block, ceiling +inf); floor_key and rx are read through it,
+  // the norms by position
+  const int32_t* gather;
 };
+template <bool GATHER>
 __global__ void ceil_kernel(CeilArgs a) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n_pad) return;
   if (i >= a.n) { a.ceil[i] = __builtin_huge_valf(); return; }
+  int64_t row = i;
+  if constexpr (GATHER) {
+    row = a.gather[i];
+    if (row < 0) { a.ceil[i] = __builtin_huge_valf(); return; }
+  }
   const float s = prep_scale(a.metric, a.max_n), s2 = s * s;
-  const float fk = a.floor_key[i];
+  const float fk = a.floor_key[row];
   float q, mag;
   if (a.metric == MMF_DOT || a.metric == MMF_COSINE) { q = s2 * fk; mag = fabsf(q); }
   else {
-    const float t = (a.metric == MMF_RBF) ? fk / a.lambda : fk, ni = a.rx[i];
+    const float t = (a.metric == MMF_RBF) ? fk / a.lambda : fk, ni = a.rx[row];
     q = 0.5f * s2 * (t + ni); mag = 0.5f * s2 * (fabsf(t) + ni);
   }
   const float half_margin = 0.5f * scan_margin(a.metric, a.d, a.dp, a.cap, a.q_zn[i], a.q_rn[i], a.q_un[i], a.maxima);
@@ -1127,8 +1140,21 @@ static int launch_b16_for(const char* who, int dp, int cap, const ScanB16Args& a
 
 int launch_scan_b16_ceilings(const ScanB16Problem& p, int cap, const float* floor_key, const float* rx, const uint32_t* max_n, float lambda,
                              int64_t n_pad, float* ceil, hipStream_t s) {
-  CeilArgs a{floor_key, rx, p.q_zn, p.q_rn, p.q_un, p.maxima, max_n, p.n_rows, n_pad, p.metric, (int)p.d, p.dp, cap, lambda, ceil};
-  hipLaunchKernelGGL(ceil_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, a);
+  CeilArgs a{floor_key, rx, p.q_zn, p.q_rn, p.q_un, p.maxima, max_n, p.n_rows, n_pad, p.metric, (int)p.d, p.dp, cap, lambda, ceil, nullptr};
+  hipLaunchKernelGGL(ceil_kernel<false>, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, a);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
+// The same for a segment-padded query image (mmf_simtopk_segmented_fast_anyk): ceil [nq_pad] by operand position,
+// gather [n_pos] the row of X at each position (-1: padding); floor_key and rx stay indexed by row of X.  The margin's maxima are
+// those of the whole padded candidate image (p.maxima), as in the scan that follows.
+int launch_scan_b16_ceilings_gather(const ScanB16Problem& p, int cap, const int32_t* gather, int64_t n_pos, const float* floor_key, const float* rx,
+                                    const uint32_t* max_n, float lambda, int64_t nq_pad, float* ceil, hipStream_t s) {
+  if (!gather) { set_error("scan_b16_ceilings_gather: position table missing"); return MMF_E_INTERNAL; }
+  if (nq_pad <= 0) return MMF_OK;
+  CeilArgs a{floor_key, rx, p.q_zn, p.q_rn, p.q_un, p.maxima, max_n, n_pos, nq_pad, p.metric, (int)p.d, p.dp, cap, lambda, ceil, gather};
+  hipLaunchKernelGGL(ceil_kernel<true>, dim3((unsigned)((nq_pad + 255) / 256)), dim3(256), 0, s, a);
   MMF_LAUNCH_CHECK();
   return MMF_OK;
 }
@@ -1237,6 +1263,35 @@ int launch_scan_b16_seg(const ScanB16Problem& p, const int32_t* sched, int64_t g
   ScanB16Args a = scan_args(p, L, pn, scratch);
   a.sched = sched;
   return launch_b16_for<true>("scan_b16_seg", p.dp, L.cap, a, p.f16, grid, s);
+}
+
+// The table-driven launch with a ceiling per operand position (the later passes of mmf_simtopk_segmented_fast_anyk).
+// Such a pass runs at the full list depth only — 32-entry lists at d <= 512, the split-k pair kernel at d <= 1024 — so SEG + CEIL is
+// instantiated for those four shapes and not for the whole table of launch_b16_for.
+static int launch_b16_seg_ceil_for(int dp, int cap, const ScanB16Args& a, bool f16, int64_t grid, hipStream_t s) {
+  if (cap == B_CAP_WIDE) {
+    switch (dp) {
+      case 128: return launch_b16_t<8, 8, 1, B_CAP_WIDE, false, true, 0, false, true>(a, f16, grid, s);
+      case 256: return launch_b16_t<16, 8, 1, B_CAP_WIDE, false, true, 0, false, true>(a, f16, grid, s);
+      case 512: return launch_b16_t<32, 8, 1, B_CAP_WIDE, false, true, 0, false, true>(a, f16, grid, s);
+    }
+  } else if (cap == B_CAP && dp == 1024) {
+    return launch_b16_t<64, 8, 1, B_CAP, true, true, 0, false, true>(a, f16, grid, s);
+  }
+  set_error("scan_b16_seg_ceil: no kernel for padded dim %d with %d-entry lists (full-depth passes only)", dp, cap);
+  return MMF_E_INTERNAL;
+}
+
+// ceil: [nq_pad] by position of the segment-padded query image (launch_scan_b16_ceilings_gather)
+int launch_scan_b16_seg_ceil(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const CandLists& L, void* scratch,
+                             const ScanB16Panel& pn, const float* ceil, hipStream_t s) {
+  if (grid <= 0) return MMF_OK;
+  if (L.lists != 2) { set_error("scan_b16_seg_ceil: one list pair per row expected"); return MMF_E_INTERNAL; }
+  if (!pn.seed) { set_error("scan_b16_seg_ceil: threshold buffers missing"); return MMF_E_INTERNAL; }
+  if (!ceil) { set_error("scan_b16_seg_ceil: ceilings missing"); return MMF_E_INTERNAL; }
+  ScanB16Args a = scan_args(p, L, pn, scratch);
+  a.sched = sched; a.ceil = ceil;
+  return launch_b16_seg_ceil_for(p.dp, L.cap, a, p.f16, grid, s);
 }
 
 // Cross-segment scan (mmf_simtopk_cross_segments_fast): one workgroup per entry of `sched` (cross_seg16_table,
