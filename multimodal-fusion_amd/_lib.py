@@ -143,6 +143,13 @@ WIDE_ANYK_EXPORTS = ["mmf_simtopk_wide_anyk", "mmf_wide_anyk_plan"]
 # read and grouped per segment on the host); mmf_segmented_anyk_plan is host-only.  Pinned by tests/test_segmented_anyk_cpu.py.
 SEG_ANYK_EXPORTS = ["mmf_simtopk_segmented_fast_anyk", "mmf_segmented_anyk_plan"]
 
+# The 16-bit cross-segment top-k for any k (include/ext/mmf_hg_cross_seg_anyk.h): an addition to ABI version 3 in a
+# header of its own; the cross-segment form of mmf_simtopk_fast_anyk for d <= 1024 (same info struct).
+# mmf_simtopk_cross_segments_fast_anyk synchronises once per pass (fail counts and yield histogram together) and once more in a pass
+# that sends rows to the exact rescan (the rows are read to the host, which builds the exact table over them);
+# mmf_cross_segments_anyk_plan is host-only.  Pinned by tests/test_cross_segments_anyk_cpu.py.
+CROSS_ANYK_EXPORTS = ["mmf_simtopk_cross_segments_fast_anyk", "mmf_cross_segments_anyk_plan"]
+
 
 class FastAnykInfo(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
@@ -259,6 +266,10 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_segmented_fast_anyk.restype = ci
     L.mmf_segmented_anyk_plan.argtypes = list(L.mmf_fast_anyk_plan.argtypes)
     L.mmf_segmented_anyk_plan.restype = ci
+    L.mmf_simtopk_cross_segments_fast_anyk.argtypes = list(L.mmf_simtopk_cross_segments_fast.argtypes) + [ctypes.POINTER(FastAnykInfo)]
+    L.mmf_simtopk_cross_segments_fast_anyk.restype = ci
+    L.mmf_cross_segments_anyk_plan.argtypes = [i64, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.mmf_cross_segments_anyk_plan.restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

@@ -24,6 +24,7 @@
 #include "../../include/ext/mmf_hg_fast_anyk.h"
 #include "../../include/ext/mmf_hg_wide_anyk.h"
 #include "../../include/ext/mmf_hg_seg_anyk.h"
+#include "../../include/ext/mmf_hg_cross_seg_anyk.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -416,6 +417,10 @@ int launch_scan_b16_ceilings_gather(const ScanB16Problem& p, int cap, const int3
 // [n_pad][2] the excluded column range (first, count) of every query row, L.lists = the table's list count, pn.share as the table says
 int launch_scan_b16_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, const CandLists& L,
                          void* scratch, const ScanB16Panel& pn, hipStream_t s);
+// the later passes of mmf_simtopk_cross_segments_fast_anyk: the same launch under a ceiling per query row (ceil
+// [n_pad] by row of X, what launch_scan_b16_ceilings leaves: the plain images' positions are rows) — full-depth lists only
+int launch_scan_b16_xseg_ceil(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, const CandLists& L,
+                              void* scratch, const ScanB16Panel& pn, const float* ceil, hipStream_t s);
 
 // mmf_fast_anyk.hip: the per-row bookkeeping of mmf_simtopk_fast_anyk's later passes.  The re-rank of such a pass
 // fills a staging row per query: `depth` entries in the final order (ids with col_offset added, values, canonical keys).

@@ -242,10 +242,11 @@ struct ScanB16Args {
   // XSEG kernels only (launch_scan_b16_xseg): [n_pad][2] per query row, first row and row count of the columns the row may not
   // take (its own segment's rows of Y; padding rows: 0, 0)
   const uint32_t* xbounds;
-  // CEIL kernels only (launch_scan_b16_ceil, launch_scan_b16_seg_ceil): [n_pad] per query row, the largest scanned value the row may
-  // still take, in the kernel's own units (bias and 2^(2e) scale included); padding rows: +inf.  Indexed by OPERAND POSITION (qop), like
-  // q_zn / q_rn / q_un: the plain schedule's positions are its rows, the table-driven (SEG) one's are positions of the segment-padded
-  // query image ([nq_pad]; launch_scan_b16_ceilings_gather fills them through the position -> row table)
+  // CEIL kernels only (launch_scan_b16_ceil, launch_scan_b16_seg_ceil, launch_scan_b16_xseg_ceil): [n_pad] per query row, the largest
+  // scanned value the row may still take, in the kernel's own units (bias and 2^(2e) scale included); padding rows: +inf.  Indexed by
+  // OPERAND POSITION (qop), like q_zn / q_rn / q_un: the plain schedule's positions are its rows, and so are the cross-segment (XSEG)
+  // one's, whose images are the plain ones (launch_scan_b16_ceilings fills both); the table-driven (SEG) one's are positions of the
+  // segment-padded query image ([nq_pad]; launch_scan_b16_ceilings_gather fills them through the position -> row table)
   const float* ceil;
 };
 
@@ -342,16 +343,19 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 // reaches no list, overflow list, threshold, seed or lost.  SPLITK: only the owner wave masks; -inf survives the partner's partial sums.
 //
 // CEIL (mmf_simtopk_fast_anyk, DESIGN.md §4.27: the plain schedule; mmf_simtopk_segmented_fast_anyk, §4.29: with SEG, four depth
-// shapes — launch_b16_seg_ceil_for): the later passes of a call with more neighbours than one
+// shapes — launch_b16_seg_ceil_for; mmf_simtopk_cross_segments_fast_anyk, §4.30: with XSEG, the same four shapes —
+// launch_b16_xseg_ceil_for): the later passes of a call with more neighbours than one
 // pass holds.  Every query row comes with a ceiling a.ceil[row]; a value above it belongs to a column the row has already emitted.
 // Such a value is above the row's threshold by construction, so it enters the list code as a hit anyway: the compare sits THERE, on
 // the lane's 16 gathered values before they are offered — the tile loop's v_max + two compares are untouched, and the ceiling is
 // loaded inside the branch, so the loop carries no register for it.  A value set to -inf there reaches no list, overflow list,
 // threshold, seed or lost.  SPLITK: only the owner wave runs the list code, so only it compares.
+// With XSEG the two do not meet: the mask has made a value -inf behind its tile's chain, before the list code gathers it, and the
+// ceiling compare leaves -inf alone; a value either of them removes reaches no threshold the entries of a row block share (a.share).
 template <int KS, bool F16, bool DBG, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0, bool XSEG = false,
           bool CEIL = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(ScanB16Args a) {
-  static_assert(!CEIL || (SYM == 0 && !DBG && !XSEG), "per-row ceilings: the plain and the table-driven schedule only");
+  static_assert(!CEIL || (SYM == 0 && !DBG), "per-row ceilings: the plain and the table-driven schedules (SEG, XSEG) only");
   static_assert(!SPLITK || (TPB == 1 && NW == 8 && (KS % 8) == 0), "split-k pairs");
   static_assert(SYM == 0 || (!SPLITK && !SEG && !DBG && TPB == 2), "symmetric schedule: the d = 512 kernel only");
   static_assert(!XSEG || (SEG && SYM == 0 && !DBG), "the cross-segment mask rides on the table-driven schedule");
@@ -726,7 +730,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
         }
       }
       if constexpr (CEIL) {   // columns the row has already emitted (and nothing that ranks after its floor: §4.27) lie above its ceiling
-        const float ce = a.ceil[qop];
+        float ce;
+        if constexpr (XSEG) {   // the same word, a.ceil[qop], addressed from the wave's scalar base and a lane id read here: with qop kept
+          // live across the tile loop beside the mask's operands the d = 512 kernel spills a VGPR
+          const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+          ce = (a.ceil + (q0 + 32 * qw))[(ln & 15) + (ln & 16)];
+        } else ce = a.ceil[qop];
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = (v[r] > ce) ? kNegInf : v[r];
       }
@@ -1307,6 +1316,35 @@ int launch_scan_b16_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t 
   ScanB16Args a = scan_args(p, L, pn, scratch);
   a.sched = sched; a.xbounds = bounds; a.share = pn.share;
   return launch_b16_for<true, true>("scan_b16_xseg", p.dp, L.cap, a, p.f16, grid, s);
+}
+
+// The cross-segment launch with a ceiling per query row (the later passes of mmf_simtopk_cross_segments_fast_anyk).
+// Both images are the plain ones, so a position is a row and `ceil` [n_pad] is what launch_scan_b16_ceilings leaves.  Such a pass
+// runs at the full list depth only, so XSEG + CEIL is instantiated for the four shapes of launch_b16_seg_ceil_for.
+static int launch_b16_xseg_ceil_for(int dp, int cap, const ScanB16Args& a, bool f16, int64_t grid, hipStream_t s) {
+  if (cap == B_CAP_WIDE) {
+    switch (dp) {
+      case 128: return launch_b16_t<8, 8, 1, B_CAP_WIDE, false, true, 0, true, true>(a, f16, grid, s);
+      case 256: return launch_b16_t<16, 8, 1, B_CAP_WIDE, false, true, 0, true, true>(a, f16, grid, s);
+      case 512: return launch_b16_t<32, 8, 1, B_CAP_WIDE, false, true, 0, true, true>(a, f16, grid, s);
+    }
+  } else if (cap == B_CAP && dp == 1024) {
+    return launch_b16_t<64, 8, 1, B_CAP, true, true, 0, true, true>(a, f16, grid, s);
+  }
+  set_error("scan_b16_xseg_ceil: no kernel for padded dim %d with %d-entry lists (full-depth passes only)", dp, cap);
+  return MMF_E_INTERNAL;
+}
+
+int launch_scan_b16_xseg_ceil(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, const CandLists& L,
+                              void* scratch, const ScanB16Panel& pn, const float* ceil, hipStream_t s) {
+  if (grid <= 0) return MMF_OK;
+  if (L.lists < 2 || (L.lists & 1) || !bounds || !sched) { set_error("scan_b16_xseg_ceil: list pairs, a work table and the rows' bounds expected"); return MMF_E_INTERNAL; }
+  if (L.lists > 2 && (!L.keys || !L.margin)) { set_error("scan_b16_xseg_ceil: several list pairs need keys and margins"); return MMF_E_INTERNAL; }
+  if (!pn.seed) { set_error("scan_b16_xseg_ceil: threshold buffers missing"); return MMF_E_INTERNAL; }
+  if (!ceil) { set_error("scan_b16_xseg_ceil: ceilings missing"); return MMF_E_INTERNAL; }
+  ScanB16Args a = scan_args(p, L, pn, scratch);
+  a.sched = sched; a.xbounds = bounds; a.share = pn.share; a.ceil = ceil;
+  return launch_b16_xseg_ceil_for(p.dp, L.cap, a, p.f16, grid, s);
 }
 
 // ------------------------------------------------------------------------------------------------
