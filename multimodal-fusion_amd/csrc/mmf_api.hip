@@ -341,6 +341,25 @@ static void symmetric_live_mode(bool* live, bool* forward) {
   *live = (v == 1 || v == 2);
   *forward = (v == 0 || v == 2);
 }
+// MMF_SYMMETRIC_PHASES (read per call): unset / 2 = the symmetric launch looks back in two phases, the wrap-around pairs behind all
+// others (sym_schedule_table), 1 = the single cyclic look-back.  MMF_SYMMETRIC_ANTIPODAL (read per call): 1 = with an even number
+// of super-blocks (four or more) the antipodal pairs are multiplied once, in the symmetric launch, 0 = twice, in the first launch;
+// unset = 1 with two phases and super-blocks of at least kSymAntipodalMinGroup row blocks (every default G: launch 0 then gives a
+// row its threshold from its own super-block alone, and with the 256 columns of a forced G = 1 rows with crowded margin bands drop
+// keys they would not have dropped — tests/test_gpu_scan16_adversarial.py flags 3 rows instead of 1), else 0
+// (MMF_SYMMETRIC_PHASES=1 alone is the schedule before both; with one phase the
+// antipodal pairs fill the wave logs on the benchmark rows in bf16 — profiles/r09_symmetric_schedule.txt — so that pair is for
+// measurements only).  Neither applies to the look-ahead table (MMF_SYMMETRIC_LIVE=0 / 2).  Results are the same.
+// `schedule_default`: what an unset MMF_SYMMETRIC_PHASES means — 2 for a scan; mmf_debug_symmetric_schedule passes 1, so that
+// it shows the tables with phases or without the antipodal range only where it is asked for them.
+static constexpr int kSymAntipodalMinGroup = 32;
+static void symmetric_schedule_mode(int* phases, bool* antipodal, int G, int schedule_default = 2) {
+  const char* e = getenv("MMF_SYMMETRIC_PHASES");
+  const int v = e ? atoi(e) : schedule_default;
+  *phases = v == 1 ? 1 : (v == 2 ? 2 : schedule_default);
+  const char* a = getenv("MMF_SYMMETRIC_ANTIPODAL");
+  *antipodal = a ? atoi(a) == 1 : (*phases == 2 && G >= kSymAntipodalMinGroup);
+}
 // MMF_SYMMETRIC_PRUNE (read per call): unset / 1 = the logs' entries are filed into the rows' received lists only if select could
 // still keep them (sym_scatter_kernel), 0 = every entry is filed.  Results are the same; for measurements and tests.
 static bool symmetric_prune_mode() {
@@ -569,11 +588,11 @@ struct FastTail {
   int64_t sym_grid() const { return sym_schedule_grid((n + 255) / 256, sym_G); }
   void set_symmetric(int G) {   // before bytes() / carve()
     sym_try = true; sym_G = G;
-    if (lists_alloc < 4) lists_alloc = 4;
+    if (lists_alloc < 2 * kSymListPairs) lists_alloc = 2 * kSymListPairs;
   }
   CandLists view(bool symmetric) const {
     CandLists v = L;
-    v.lists = symmetric ? 4 : lists;
+    v.lists = symmetric ? 2 * kSymListPairs : lists;
     if (v.lists <= 2) { v.keys = nullptr; v.margin = nullptr; }
     v.spill_stacks = spill_stacks_for(v.lists);
     if (symmetric) { v.sym_cnt = sym_cnt; v.sym_ent = sym_ent; v.sym_cap = kSymCap; }
@@ -710,9 +729,11 @@ struct FastTail {
     if (symmetric) {
       bool live, forward;
       symmetric_live_mode(&live, &forward);
-      const WsKept tables{sym.sched, (n + 255) / 256, sym_G, forward ? 1 : 0};
-      MMF_TRY(launch_scan_b16_sym(sp, SymLaunch{sym_G, live, forward, symmetric_prune_mode(), !(sym_kept == tables)}, L, scan_scratch, sym,
-                                  pn, s, &grid));
+      int phases; bool antipodal;
+      symmetric_schedule_mode(&phases, &antipodal, sym_G);
+      const WsKept tables{sym.sched, (n + 255) / 256, sym_G, forward ? 1 : 0, phases, antipodal ? 1 : 0};
+      MMF_TRY(launch_scan_b16_sym(sp, SymLaunch{sym_G, live, forward, symmetric_prune_mode(), !(sym_kept == tables), phases, antipodal}, L,
+                                  scan_scratch, sym, pn, s, &grid));
       if (sym_keep) *sym_keep = tables;
     } else if (fo.n_panels == 0) {
       if (wide) {
@@ -756,9 +777,16 @@ struct FastTail {
       for (uint32_t v : hl) { logged += v; if (v > lmx) lmx = v; }
       bool live, forward;
       symmetric_live_mode(&live, &forward);
-      fprintf(stderr, "[mmf symmetric] G %d grid %lld %s %s: rows without a threshold %u, received entries %llu (%.1f per row, largest %u of %d), fullest wave log %u of %d, logged entries %llu (%.1f per row, filing %s)\n",
+      int phases; bool antipodal;
+      symmetric_schedule_mode(&phases, &antipodal, sym_G);
+      // logged entries by the phase of the workgroup that logged them (sym_schedule_grid: phase B's block ids follow phase A's)
+      const size_t first_b = (size_t)sym_schedule_phase_b_begin((n + 255) / 256, sym_G) * 8;
+      unsigned long long logged_b = 0;
+      for (size_t i = first_b; i < hl.size(); ++i) logged_b += hl[i];
+      fprintf(stderr, "[mmf symmetric] G %d grid %lld %s %s: rows without a threshold %u, received entries %llu (%.1f per row, largest %u of %d), fullest wave log %u of %d, logged entries %llu (%.1f per row, filing %s), phases %d antipodal %d, logged by phase B %llu (%.1f per row)\n",
               sym_G, (long long)sym_grid(), live ? "live" : "frozen", forward ? "ahead" : "back", none, tot, (double)tot / (double)n, mx,
-              kSymCap, lmx, kSymLogPerWave, logged, (double)logged / (double)n, symmetric_prune_mode() ? "pruned" : "complete");
+              kSymCap, lmx, kSymLogPerWave, logged, (double)logged / (double)n, symmetric_prune_mode() ? "pruned" : "complete",
+              forward ? 1 : phases, (antipodal && !forward) ? 1 : 0, logged_b, (double)logged_b / (double)n);
     }
     // the f32 rows are first touched here: a caller that is still receiving them (overlapped
     // all-gather) hands in the event that marks their arrival
@@ -1524,7 +1552,9 @@ int64_t mmf_debug_symmetric_schedule(int64_t row_blocks, int group, int launch, 
     if (capacity < grid) { set_error("debug_symmetric_schedule: table of %lld entries needed", (long long)grid); return MMF_E_INVALID; }
     bool live, forward;
     symmetric_live_mode(&live, &forward);
-    sym_schedule_table(row_blocks, group, launch, table_host, forward);
+    int phases; bool antipodal;
+    symmetric_schedule_mode(&phases, &antipodal, group, 1);
+    sym_schedule_table(row_blocks, group, launch, table_host, forward, phases, antipodal);
   }
   return grid;
 }

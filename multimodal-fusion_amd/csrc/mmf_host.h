@@ -57,14 +57,18 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 // What a cached workspace still holds from the previous call on its stream and a later call may use as it is (one thing:
-// the work tables of the symmetric scan, which depend on the row-block count, G and the direction alone).  Handing the
+// the work tables of the symmetric scan, which depend on the row-block count, G, the direction, the phase count and the
+// antipodal switch alone).  Handing the
 // workspace out forgets it — whoever takes the buffer may overwrite every byte — and gives the taker what was kept until
 // then (Workspace::kept); a call that finds or writes the same content at the same place files it again (*Workspace::keep).
 struct WsKept {
   const void* where = nullptr;
   int64_t row_blocks = 0;
-  int group = 0, forward = 0;
-  bool operator==(const WsKept& o) const { return where == o.where && row_blocks == o.row_blocks && group == o.group && forward == o.forward; }
+  int group = 0, forward = 0, phases = 0, antipodal = 0;
+  bool operator==(const WsKept& o) const {
+    return where == o.where && row_blocks == o.row_blocks && group == o.group && forward == o.forward && phases == o.phases &&
+           antipodal == o.antipodal;
+  }
 };
 
 // Bump allocator over one cached device buffer per (device, stream).
@@ -192,9 +196,13 @@ struct CandLists {
 // mmf_scan_bf16.hip: the symmetric schedule of a scan of X against itself.  nb row blocks of 256 rows in
 // nb / G super-blocks of G (the last one also takes the nb % G left-over row blocks); launch 0 does the plain pairs (own and, for an even count, antipodal super-block), launch 1 the
 // symmetric ones.  The table has sym_schedule_grid() entries of 8 ints: row block (-1: idle), first tile and tile count of
-// two column ranges.
+// two column ranges, the entry's list pair within its launch and its phase.  phases == 2: the symmetric launch's wrap-around
+// pairs run behind all others (phase B, block ids of their own); antipodal: launch 0 does the own super-block alone and the
+// antipodal pairs are symmetric ones.  The look-ahead table (forward) has neither.
+constexpr int kSymListPairs = 3;        // list pairs of a row in the symmetric scan: launch 0, phase A, phase B
 int64_t sym_schedule_grid(int64_t nb, int G);
-void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out, bool forward = false);
+int64_t sym_schedule_phase_b_begin(int64_t nb, int G);   // first block id of phase B (they run to the end of the grid)
+void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out, bool forward = false, int phases = 1, bool antipodal = false);
 int sym_default_group(int64_t nb);
 constexpr int kSymCap = 512;            // entries per row of CandLists::sym_ent (1.66 x the largest count on the bench rows, bf16 leg)
 constexpr int kSymLogPerWave = 4096;    // entries of a wave's append log (32 rows: 128 per row; 1.73 x the fullest on the bench rows, bf16 leg)
@@ -395,8 +403,9 @@ int launch_scan_b16_ceilings(const ScanB16Problem& p, int cap, const float* floo
                              int64_t n_pad, float* ceil, hipStream_t s);
 size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G);
 // G: row blocks per super-block; live / forward / prune: MMF_SYMMETRIC_LIVE and MMF_SYMMETRIC_PRUNE as read by the caller;
+// phases / antipodal: MMF_SYMMETRIC_PHASES and MMF_SYMMETRIC_ANTIPODAL (sym_schedule_table);
 // tables: build and upload the two work tables (false: SymBuffers::sched still holds them)
-struct SymLaunch { int G; bool live, forward, prune, tables; };
+struct SymLaunch { int G; bool live, forward, prune, tables; int phases = 2; bool antipodal = false; };
 int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandLists& L, void* scratch, const SymBuffers& sb,
                         const ScanB16Panel& pn, hipStream_t s, int* grid_out);
 size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap);

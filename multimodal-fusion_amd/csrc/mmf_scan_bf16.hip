@@ -256,8 +256,9 @@ struct ScanB16Args {
 enum { SEG_QPOS = 0, SEG_ROW0 = 1, SEG_NQ = 2, SEG_T0 = 3, SEG_T1 = 4, SEG_IDOFF = 5, SEG_ENTRY = 8 };
 // Work table entry of the symmetric schedule (sym_schedule_table; same entry size): the workgroup's row block (-1: idle) and
 // its columns — tiles [B1, B1 + N1) followed by [B2, B2 + N2) (a cyclic range that wraps, or own + antipodal super-block).
-// N1 and N2 are multiples of 8 tiles; N1 == 0 only when N2 == 0.
-enum { SYM_RB = 0, SYM_B1 = 1, SYM_N1 = 2, SYM_B2 = 3, SYM_N2 = 4 };
+// N1 and N2 are multiples of 8 tiles; N1 == 0 only when N2 == 0.  SLOT: the entry's list pair within its launch (a row block has
+// an entry per phase of the symmetric launch, like XSEG_SLOT); PHASE: 0 = a table without phases, 1 / 2 = phase A / B (host only).
+enum { SYM_RB = 0, SYM_B1 = 1, SYM_N1 = 2, SYM_B2 = 3, SYM_N2 = 4, SYM_SLOT = 5, SYM_PHASE = 6 };
 // Work table entry of the cross-segment scan (cross_seg16_table; same entry size, SEG's words 0 .. 4): both images are the plain
 // ones, so the id offset is zero and its word carries the entry's list-slot number; words 6 and 7 are the entry's mask window,
 // the tiles [W0, W1) of its range that hold a column some query of the block may not take (W0 == W1: none).
@@ -330,7 +331,8 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 // The SYM kernels have no instrumented (DBG) build; their query-side list code is measured with two build switches (scripts/ab_build.sh):
 #ifndef MMF_SYM_ABLATE_Q
 #define MMF_SYM_ABLATE_Q 0    // timing only, the results are WRONG: bit 0 / bit 1 = the SYM == 1 / SYM == 2 kernel never enters the query-side list code
-#endif
+#endif                        // bit 2 = ... and the tile maxima are folded into one value that is stored at the end.  WITHOUT bit 2 nothing reads the
+                              // SYM == 1 kernel's accumulators and the compiler drops its MFMA chain: such a build does not time the matrix work
 #ifndef MMF_SYM_COUNT
 #define MMF_SYM_COUNT 0       // 1 = both SYM launches count wave-tiles, visits, hits and compactions (MMF_SCAN_DEBUG bit 8's counters)
 #endif                        //     and launch_scan_b16_sym prints them per launch (it synchronises the stream: not for timing)
@@ -405,7 +407,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   if constexpr (SYM != 0) {
     const int32_t* e = a.sched + (size_t)blockIdx.x * SEG_ENTRY;
     if (e[SYM_RB] < 0) return;
-    rb = e[SYM_RB]; split = 0;
+    rb = e[SYM_RB]; split = SYM == 2 ? e[SYM_SLOT] : 0;
     t_begin = e[SYM_B1]; t_end = t_begin + e[SYM_N1] + e[SYM_N2];      // walked as one range of N1 + N2 tiles
     sym_n1 = e[SYM_N1]; sym_skip = e[SYM_B2] - (e[SYM_B1] + e[SYM_N1]);
   } else if constexpr (SEG) {
@@ -713,7 +715,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   // falls into the (rare) list code then delays only itself while its SIMD partner issues MFMAs;
   // placed before the barrier it would hold all eight waves, and their matrix pipes, at the barrier.
   constexpr bool SYMCNT = SYM != 0 && MMF_SYM_COUNT != 0;
+  float ablate_keep = -kFltMax;   // MMF_SYM_ABLATE_Q bit 2: the tile maxima folded into one value, stored once at the end
   auto filter = [&](const Acc& acc, int tt, float m0, float m1) {
+    if (SYM != 0 && (MMF_SYM_ABLATE_Q & SYM) != 0 && (MMF_SYM_ABLATE_Q & 4) != 0) ablate_keep = fmaxf(ablate_keep, fmaxf(m0, m1));
     if (__builtin_expect(!(DBG && (a.debug & 1)) && !(SYM != 0 && (MMF_SYM_ABLATE_Q & SYM) != 0) && __any((m0 >= thr_q0) || (m1 >= thr_q1)), 0)) {
       uint32_t id0 = id_base + (uint32_t)tt * B_CT;
       if constexpr (SYM != 0) id0 += (tt >= sym_n1) ? (uint32_t)(sym_skip * B_CT) : 0u;   // behind the first range: sym_skip tiles further on
@@ -977,6 +981,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
     if (a.cand_keys && half == 0) a.margin_out[qpos] = margin;
     if (list.lost > kNegInf) atomicMax(a.lost + qpos, seed_enc(list.lost) + SlotList<CAP, NTL>::SLOTS);   // stored keys carry slot bits
   }
+  // (behind the last read of the id slots: the workgroup's own scratch, one word per list thread)
+  if (SYM != 0 && (MMF_SYM_ABLATE_Q & SYM) != 0 && (MMF_SYM_ABLATE_Q & 4) != 0) lids[tid & (NTL - 1)] = __float_as_uint(ablate_keep);
 }
 
 // overflow[row] |= (a key was dropped for the row) && (no list proved a threshold above it)
@@ -1365,40 +1371,82 @@ int sym_default_group(int64_t nb) {
 // ns = nb / G super-blocks; the row blocks left over join the LAST one (G .. 2 G - 1 row blocks), so no super-block is
 // short: a short one would give its rows thresholds from a handful of columns in launch 0 and flood their received lists.
 static int64_t sym_super_blocks(int64_t nb, int G) { const int64_t ns = nb / G; return ns < 1 ? 1 : ns; }
-int64_t sym_schedule_grid(int64_t nb, int G) {
+// Two phases (`phases` == 2, looking back only; the default): the wrap-around pairs leave the cyclic look-back and run LAST.  Phase A,
+// the block ids of the single-phase table: super-block b scans max(0, b - h) .. b - 1, so every candidate row belongs to a
+// workgroup of an earlier or the same stretch of block ids.  Phase B, the block ids behind ALL of phase A: super-block b < h
+// scans what it lost, b + ns - h .. ns - 1, whose rows have all at least started phase A — longest first (b ascending: h - b
+// super-blocks), so the launch ends with its short workgroups.  A row block has an entry per phase, each with a list pair of
+// its own (SYM_SLOT).  The grid has the stretches of phase B whatever table is built (they are idle in the other tables and
+// in launch 0): one grid, one workspace layout and one block count for every switch.
+// `antipodal` (ns even and at least 4, looking back only): launch 0 scans the own super-block alone, and the pair (a, a + ns / 2) is
+// multiplied once, symmetric, by the later super-block a + ns / 2 as its LAST range (the second one, which lies below the first).
+static int64_t sym_phase_a_grid(int64_t nb, int G) {
   const int64_t ns = sym_super_blocks(nb, G);
   return ((ns + 7) / 8 + (nb > ns * G ? 1 : 0)) * 8 * G;      // the left-over row blocks take a stretch of block ids of their own
 }
-void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out, bool forward) {
-  const int64_t ns = sym_super_blocks(nb, G), grid = sym_schedule_grid(nb, G), tiles = nb * 8;
+int64_t sym_schedule_phase_b_begin(int64_t nb, int G) { return sym_phase_a_grid(nb, G); }
+int64_t sym_schedule_grid(int64_t nb, int G) {
+  const int64_t ns = sym_super_blocks(nb, G), h = (ns - 1) / 2;
+  if (h == 0) return sym_phase_a_grid(nb, G);
+  // (8 idle ids more when phase A's super-blocks fill its stretches to the last id: without them 64 row blocks in 8 super-blocks
+  //  come to 128 ids per launch, 256 in all — the plain scan's block count at that size, and stats.scan_grid is how callers and
+  //  tests tell which path ran)
+  const int64_t pad = (ns % 8 == 0 && nb == ns * G) ? 8 : 0;
+  return sym_phase_a_grid(nb, G) + (h + 7) / 8 * 8 * G + pad;
+}
+void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out, bool forward, int phases, bool antipodal) {
+  const int64_t ns = sym_super_blocks(nb, G), grid = sym_schedule_grid(nb, G), grid_a = sym_phase_a_grid(nb, G), tiles = nb * 8;
   const int64_t per = 8 * (int64_t)G, stretches = (ns + 7) / 8;
+  const int64_t h = (ns - 1) / 2;
+  if (forward) { phases = 1; antipodal = false; }   // the look-ahead arms keep the table they were measured with
+  if (ns < 4 || (ns % 2) != 0) antipodal = false;   // (two super-blocks: launch 0 keeps all the pairs and the symmetric launch stays empty)
   auto first_tile = [&](int64_t sb) { return sb * G * 8; };
   auto end_tile = [&](int64_t sb) { return sb == ns - 1 ? tiles : (sb + 1) * G * 8; };
   for (int64_t b = 0; b < grid; ++b) {
     int32_t* e = out + b * SEG_ENTRY;
     for (int i = 0; i < SEG_ENTRY; ++i) e[i] = 0;
     e[SYM_RB] = -1;
-    int64_t sb = (b / per) * 8 + (b % 8), rbi = sb * G + (b % per) / 8;
-    if (b / per >= stretches) {                  // the extra stretch: left-over row blocks, on the XCD of the last super-block
-      if (b % 8 != (ns - 1) % 8) continue;
-      sb = ns - 1; rbi = ns * G + (b % per) / 8;
+    const bool phase_b = b >= grid_a;
+    if (phase_b && (launch == 0 || phases != 2)) continue;
+    const int64_t bb = phase_b ? b - grid_a : b;
+    int64_t sb = (bb / per) * 8 + (bb % 8), rbi = sb * G + (bb % per) / 8;
+    if (phase_b) {
+      if (sb >= h) continue;
+    } else if (bb / per >= stretches) {          // the extra stretch: left-over row blocks, on the XCD of the last super-block
+      if (bb % 8 != (ns - 1) % 8) continue;
+      sb = ns - 1; rbi = ns * G + (bb % per) / 8;
     } else if (sb >= ns) continue;
     if (rbi >= nb) continue;
     int64_t b1 = 0, n1 = 0, b2 = 0, n2 = 0;
     if (launch == 0) {
       b1 = first_tile(sb); n1 = end_tile(sb) - b1;
-      if (ns >= 2 && (ns % 2) == 0) { const int64_t o = (sb + ns / 2) % ns; b2 = first_tile(o); n2 = end_tile(o) - b2; }
+      if (ns >= 2 && (ns % 2) == 0 && !antipodal) { const int64_t o = (sb + ns / 2) % ns; b2 = first_tile(o); n2 = end_tile(o) - b2; }
+    } else if (phase_b) {
+      b1 = first_tile(sb + ns - h); n1 = tiles - b1;
     } else {
-      const int64_t h = (ns - 1) / 2;
-      if (h == 0) continue;
-      int64_t lo = forward ? sb + 1 : sb - h, hi = lo + h - 1;   // super-blocks lo .. hi, cyclic
-      if (lo >= ns) { lo -= ns; hi -= ns; }
-      if (lo < 0) { lo += ns; hi += ns; }
-      if (hi < ns) { b1 = first_tile(lo); n1 = end_tile(hi) - b1; }
-      else { b1 = first_tile(lo); n1 = end_tile(ns - 1) - b1; b2 = 0; n2 = end_tile(hi - ns); }
+      const bool anti = antipodal && sb >= ns / 2;   // (its look-back sb - h .. sb - 1 starts behind the antipodal super-block: no wrap)
+      if (h == 0 && !anti) continue;
+      if (h > 0) {
+        int64_t lo = forward ? sb + 1 : sb - h, hi = lo + h - 1;   // super-blocks lo .. hi, cyclic
+        if (phases == 2) { if (lo < 0) lo = 0; }                    // (hi = sb - 1; sb == 0: nothing)
+        else {
+          if (lo >= ns) { lo -= ns; hi -= ns; }
+          if (lo < 0) { lo += ns; hi += ns; }
+        }
+        if (hi < lo) continue;
+        if (hi < ns) { b1 = first_tile(lo); n1 = end_tile(hi) - b1; }
+        else { b1 = first_tile(lo); n1 = end_tile(ns - 1) - b1; b2 = 0; n2 = end_tile(hi - ns); }
+      }
+      if (anti) {
+        const int64_t o = sb - ns / 2;
+        if (n1 == 0) { b1 = first_tile(o); n1 = end_tile(o) - b1; }
+        else { b2 = first_tile(o); n2 = end_tile(o) - b2; }
+      }
     }
     if (n2 == 0) b2 = b1 + n1;
     e[SYM_RB] = (int32_t)rbi; e[SYM_B1] = (int32_t)b1; e[SYM_N1] = (int32_t)n1; e[SYM_B2] = (int32_t)b2; e[SYM_N2] = (int32_t)n2;
+    e[SYM_SLOT] = phase_b ? 1 : 0;
+    e[SYM_PHASE] = launch == 0 || phases != 2 ? 0 : (phase_b ? 2 : 1);
   }
 }
 
@@ -1446,10 +1494,11 @@ size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G) {
 }
 
 // Both launches, the threshold image between them and the filing of the logs behind them, on stream s.  p.ZC is the operand
-// image of all rows (queries and candidates), n_pad / 32 tiles.  L has four lists per row (a pair per launch), keys, margins
+// image of all rows (queries and candidates), n_pad / 32 tiles.  L has six lists per row (a pair for launch 0 and one per phase of
+// the symmetric launch; a pair no entry writes keeps the count 0 it is given here), keys, margins
 // and the sym_* lists; pn.seed as for launch_scan_b16.  y.live: the rows' workgroups keep raising the threshold image while the
 // symmetric launch runs; y.forward: its schedule looks ahead (sym_schedule_table).  y.tables: build the two work tables and
-// upload them to sb.sched — they depend on (row blocks, G, forward) alone, so a caller whose sb.sched still holds them from
+// upload them to sb.sched — they depend on (row blocks, G, forward, phases, antipodal) alone, so a caller whose sb.sched still holds them from
 // an earlier call on this stream passes false.  *grid_out: the sum of the two grids.
 int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandLists& L, void* scratch, const SymBuffers& sb,
                         const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
@@ -1459,12 +1508,12 @@ int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandL
     set_error("scan_b16_sym: metric %d has a per-candidate bias, which the symmetric kernels do not apply", p.metric);
     return MMF_E_INTERNAL;
   }
-  if (L.lists != 4 || L.cap != B_CAP || !L.keys || !L.margin || !L.sym_cnt || !pn.seed) { set_error("scan_b16_sym: lists missing"); return MMF_E_INTERNAL; }
+  if (L.lists != 2 * kSymListPairs || L.cap != B_CAP || !L.keys || !L.margin || !L.sym_cnt || !pn.seed) { set_error("scan_b16_sym: lists missing"); return MMF_E_INTERNAL; }
   if (n_pad * 1024 >= (int64_t(1) << 32)) { set_error("scan_b16_sym: operand image beyond the 32-bit tile offsets"); return MMF_E_INTERNAL; }
   if (y.tables) {
     std::vector<int32_t> tab((size_t)grid * 2 * SEG_ENTRY);
-    sym_schedule_table(nb, y.G, 0, tab.data(), y.forward);
-    sym_schedule_table(nb, y.G, 1, tab.data() + (size_t)grid * SEG_ENTRY, y.forward);
+    sym_schedule_table(nb, y.G, 0, tab.data(), y.forward, y.phases, y.antipodal);
+    sym_schedule_table(nb, y.G, 1, tab.data() + (size_t)grid * SEG_ENTRY, y.forward, y.phases, y.antipodal);
     MMF_TRY(upload_table(s, sb.sched, tab.data(), tab.size() * 4));
   }
   MMF_HIP(hipMemsetAsync(L.sym_cnt, 0, (size_t)n * 4, s));

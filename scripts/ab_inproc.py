@@ -1,7 +1,8 @@
 """A/B of library variants in ONE process, interleaved rounds (boxes of the pool differ by a few per cent, and so do
 separate processes): scripts/ab_inproc.py [--rows N] [--rounds R] [--prec fast|fast_bf16] base nw4 early ...
-A name maps to multimodal-fusion_amd/libmmf_hg_<name>.so ("base" = the shipped library).  Every variant's result is
-compared with the first variant's, bit for bit."""
+A name maps to multimodal-fusion_amd/libmmf_hg_<name>.so ("base" = the shipped library); name@KEY=VALUE,... runs that library
+with per-call switches set (base base@MMF_SYMMETRIC_PHASES=1).  Every variant's result is compared with the first variant's,
+bit for bit."""
 import argparse
 import os
 import statistics
@@ -37,7 +38,19 @@ if a.half:
     X = X.half()
 
 
-def use(name):
+arm_env = set()
+
+
+def use(arm):
+    """arm = <library name>[@KEY=VALUE[,KEY=VALUE...]]: the switches the library reads per call, set for this arm's calls only."""
+    name, _, env = arm.partition("@")
+    for k in arm_env:
+        os.environ.pop(k, None)
+    arm_env.clear()
+    for kv in filter(None, env.split(",")):
+        k, _, v = kv.partition("=")
+        os.environ[k] = v
+        arm_env.add(k)
     path = os.path.join(ROOT, "multimodal-fusion_amd", "libmmf_hg.so" if name == "base" else f"libmmf_hg_{name}.so")
     lib = libs.get(name)
     mmf._lib._lib = lib
