@@ -23,6 +23,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.fast_anyk.*                               the 16-bit top-k for any k at feature dims <= 1024 (later passes scan under per-row ceilings), bit for bit, and the router
     mmf.segmented_anyk.*                          that any-k 16-bit top-k for every segment of a ragged batch (the cohort form), bit for bit, and the router
     mmf.cross_segments_anyk.*                     that any-k 16-bit top-k across segments (every row against all OTHER segments), bit for bit, and the router
+    mmf.cross_segments_wide_anyk.*                that any-k top-k across segments from the wide 16-bit scan (feature dims 1025..4096), bit for bit, and the router
     mmf.kmeans_ragged.*                           scikit-learn's KMeans fit for every block of a flat buffer in one call, each block with a width of its own
     mmf.wide_scan.*                               what the wide 16-bit scan (feature dims 1025..4096) covers: host-only queries
     mmf.cohort.build_cohort_hypergraphs(...)      the four steps of process_single_file for every slide of a cohort, in memory
@@ -86,6 +87,9 @@ from .segmented_anyk import segmented_anyk_plan, simtopk_segmented_fast_any_k  #
 from . import cross_segments_anyk  # noqa: F401,E402
 from .cross_segments_anyk import cross_segments_anyk_plan, simtopk_cross_segments_fast_any_k  # noqa: F401,E402
 
+from . import cross_segments_wide_anyk  # noqa: F401,E402
+from .cross_segments_wide_anyk import cross_segments_wide_anyk_plan, simtopk_cross_segments_wide_any_k  # noqa: F401,E402
+
 from . import wide_scan  # noqa: F401,E402
 from .wide_scan import list_capacity, wide_scan_supported  # noqa: F401,E402
 
@@ -108,4 +112,5 @@ __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combin
            "fast_anyk", "simtopk_fast_any_k", "fast_anyk_plan",
            "wide_anyk", "simtopk_wide_any_k", "wide_anyk_plan",
            "segmented_anyk", "simtopk_segmented_fast_any_k", "segmented_anyk_plan",
-           "cross_segments_anyk", "simtopk_cross_segments_fast_any_k", "cross_segments_anyk_plan"]
+           "cross_segments_anyk", "simtopk_cross_segments_fast_any_k", "cross_segments_anyk_plan",
+           "cross_segments_wide_anyk", "simtopk_cross_segments_wide_any_k", "cross_segments_wide_anyk_plan"]

@@ -4568,3 +4568,278 @@ int mmf_simtopk_cross_segments_fast_anyk(const void* X, int64_t n, const void* Y
 }
 
 }  // extern "C"
+
+// ---- mmf_simtopk_cross_segments_wide_anyk (include/ext/mmf_hg_cross_segw_anyk.h) -------------------------------
+// cross_anyk_run with the wide pieces, 1024 < d <= 4096: the images at the wide scan's padded dim, cross_segw_table at the full depth
+// (20 entries, 32-entry lists) and the rows' bounds, all once.  r: checked, begun, n > 0, r.precision MMF_PREC_FAST or _FAST_BF16, k
+// beyond one pass; the entry has refused every segment short of k columns outside itself.  Pass 0: the launches of
+// run_cross_segments_wide at depth 20 into the k-wide rows, every row's floor left behind (the flagged ones by the exact cross scan).
+// A later pass: ceilings by row with the wide margin (launch_scan_b16w_ceilings), the same device work table under them
+// (launch_scan_b16w_xseg_ceil: the masked scan and, with several entries per row block, its threshold union over kept values), the
+// audit, the re-rank into staging rows, count, one yield for the whole call, emit, and the exact rescan of the rows that were flagged
+// or short.  No overflow lists on this schedule: a crowded row is flagged.  Shallow rows stay in the table, as in cross_anyk_run.
+namespace mmf {
+
+static int cross_wide_anyk_run(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts,
+                               mmf_fast_anyk_info* info) {
+  const char* who = r.call.who;
+  const hipStream_t s = r.call.s;
+  const int64_t n = r.n, m = r.m;
+  const int k = r.k, depth = anyk_depth(r.d), K = depth;
+  const bool profile = r.profile, f16 = (r.precision == MMF_PREC_FAST);
+  mmf_simtopk_stats* stats = r.stats;
+  const int dp = scan_b16w_dp(r.d), bcap = scan_b16w_cap(depth);
+  int lists = 2;
+  const std::vector<int32_t> sched = cross_segw_table(xp, yp, S, bcap, kCross16Budget, opts ? opts->col_splits : 0, &lists);
+  const int64_t grid = (int64_t)sched.size() / 8;
+  const int64_t n_pad = (n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256;
+  // per row of X: first row and row count of the columns it may not take; padding rows exclude nothing
+  std::vector<uint32_t> bounds((size_t)n_pad * 2, 0u);
+  for (int64_t g = 0; g < S; ++g)
+    for (int64_t i = xp[g]; i < xp[g + 1]; ++i) { bounds[2 * i] = (uint32_t)yp[g]; bounds[2 * i + 1] = (uint32_t)(yp[g + 1] - yp[g]); }
+
+  // ---- workspace (slot 0): the wide call's at the pass depth, then floors, bookkeeping, ceilings and the staging rows -----------------
+  const size_t stage = (size_t)n * K;
+  const size_t need = ws_bytes(n, 4) + (self ? 0 : ws_bytes(m, 4)) + FlagBlock::bytes(n) + ws_bytes(4, 4) + HalfImage::bytes(n_pad, dp) +
+                      (self ? 0 : HalfImage::bytes(m_pad, dp)) + ws_bytes(sched.size(), 4) + ws_bytes(bounds.size(), 4) +
+                      b16_lists_bytes(n, lists, bcap) + ws_bytes(2 * (size_t)n, 4) + ws_bytes(select_order_bytes(n), 1) +
+                      4 * ws_bytes(n, 4) + ws_bytes(n_pad, 4) + ws_bytes(64, 4) + 2 * ws_bytes(4, 4) + ws_bytes(stage, 8) + 2 * ws_bytes(stage, 4);
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* rx = ws.take<float>(n);
+  float* cy = self ? rx : ws.take<float>(m);
+  FlagBlock flags;
+  flags.carve(ws, n);
+  MMF_TRY(flags.zero(s));
+  uint32_t* max_n = ws.take<uint32_t>(4);
+  HalfImage Q, C;
+  Q.carve(ws, n_pad, dp);
+  if (self) C = Q; else C.carve(ws, m_pad, dp);
+  int32_t* d_sched = ws.take<int32_t>(sched.size());
+  uint32_t* d_bounds = ws.take<uint32_t>(bounds.size());
+  const CandLists L = carve_b16_lists(ws, n, lists, bcap);
+  int32_t* seed = ws.take<int32_t>(2 * (size_t)n);
+  char* order_scratch = ws.take<char>(select_order_bytes(n));
+  float* fkey = ws.take<float>(n); uint32_t* fid = ws.take<uint32_t>(n);
+  int32_t* certified = ws.take<int32_t>(n); int32_t* rescan_rows = ws.take<int32_t>(n);
+  float* ceil = ws.take<float>(n_pad);
+  uint32_t* hist = ws.take<uint32_t>(64); uint32_t* rescan_count = ws.take<uint32_t>(4);
+  uint32_t* xfail = ws.take<uint32_t>(4);   // rows the exact rescans could not certify (an internal invariant: none)
+  int64_t* sidx = ws.take<int64_t>(stage); float* sval = ws.take<float>(stage); float* skey = ws.take<float>(stage);
+
+  // ---- prep, once ---------------------------------------------------------------------------------------------------------------------
+  EventTimer t_prep, t_scan, t_sel, t_fb;
+  MMF_TRY(t_prep.start(profile, s));
+  MMF_HIP(hipMemsetAsync(max_n, 0, 16, s));
+  MMF_HIP(hipMemsetAsync(xfail, 0, 16, s));
+  MMF_TRY(launch_row_scalars(r.X, n, r.d, r.dtype, r.metric, rx, max_n, s));
+  if (!self) MMF_TRY(launch_row_scalars(r.Y, m, r.d, r.dtype, r.metric, cy, max_n, s));
+  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
+  MMF_TRY(upload_table(s, d_bounds, bounds.data(), bounds.size() * 4));
+  MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
+  if (!self) MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
+  MMF_TRY(launch_prep_half({r.Y, m, r.d, r.dtype, r.metric, cy, max_n}, C, dp, f16, s));
+  if (!self) MMF_TRY(launch_prep_half({r.X, n, r.d, r.dtype, r.metric, rx, max_n}, Q, dp, f16, s));
+  MMF_TRY(t_prep.stop(s));
+
+  ScanB16Panel pn;
+  pn.seed = seed; pn.seed_stride = n; pn.share = 0;
+  const ScanB16Problem sp(Q, C, n, m, m_pad, dp, r.d, f16, r.metric, depth);
+  // what the wide call resets before its scan
+  auto reset_lists = [&]() -> int {
+    MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));   // the slots a block's entries do not use stay empty
+    MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
+    MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));    // no overflow lists here: select reads them as empty
+    MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n * 8, s));
+    return MMF_OK;
+  };
+  // `cnt` device rows on the host, ascending (one more synchronisation)
+  auto sorted_rows = [&](const int32_t* dev_rows, int64_t cnt, std::vector<int32_t>* out) -> int {
+    out->resize((size_t)cnt);
+    if (cnt > 0) {
+      MMF_HIP(hipMemcpyAsync(out->data(), dev_rows, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipStreamSynchronize(s));
+      std::sort(out->begin(), out->end());
+    }
+    return MMF_OK;
+  };
+  bool xfail_pending = false;   // an exact rescan has run since *xfail was last read
+  auto xfail_check = [&](uint32_t v) -> int {
+    xfail_pending = false;
+    if (v != 0) { set_error("%s: %u rows failed in the exact scan (internal invariant)", who, v); return MMF_E_INTERNAL; }
+    return MMF_OK;
+  };
+
+  // ---- pass 0: K entries per row, k-wide rows, floors left ----------------------------------------------------------------------
+  MMF_TRY(reset_lists());
+  MMF_TRY(t_scan.start(profile, s));
+  MMF_TRY(launch_scan_b16w_xseg(sp, d_sched, grid, d_bounds, lists, L, pn, s));
+  MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
+  MMF_TRY(t_scan.stop(s));
+  SelectProblem q = r.select();
+  q.k = K; q.out_stride = k;
+  q.rx = rx; q.cy = cy;
+  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = stats ? flags.cand_total : nullptr;
+  q.two_pass = true;
+  q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
+  q.floor_key_out = fkey; q.floor_id_out = fid;
+  MMF_TRY(t_sel.start(profile, s));
+  MMF_TRY(launch_select(q, L, s));
+  MMF_TRY(t_sel.stop(s));
+  MMF_TRY(flags.read(stats != nullptr, s));
+  std::vector<int32_t> ex_rows;
+  const int64_t fallback0 = flags.h_fail4[0];
+  MMF_TRY(t_fb.start(profile && fallback0 > 0, s));
+  if (fallback0 > 0) {
+    MMF_TRY(sorted_rows(flags.fail_rows, fallback0, &ex_rows));
+    MMF_TRY(cross_flagged_from(r, rx, cy, ex_rows, xp, yp, S, K, 0, false, true, fkey, fid, xfail));
+    xfail_pending = true;
+  }
+  MMF_TRY(t_fb.stop(s));
+  {
+    const int64_t overflow_rows = flags.h_fail4[1] < (uint32_t)fallback0 ? flags.h_fail4[1] : fallback0;
+    fill_stats(stats, r.precision, lists / 2, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback0, overflow_rows,
+               fallback0 - overflow_rows, flags.h_tot);
+  }
+  anyk_record(info, 0, K, 0, fallback0);
+
+  // ---- later passes ---------------------------------------------------------------------------------------------------------------
+  const int64_t budget = n / anyk_short_div();
+  const AnykStage st{sidx, sval, skey, n, K, 0};
+  int done = K;
+  auto finish = [&]() -> int {   // the exact rescans' fail count, when none of the call's synchronisations has read it yet
+    if (!xfail_pending) return MMF_OK;
+    uint32_t v = 0;
+    MMF_HIP(hipMemcpyAsync(&v, xfail, 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    return xfail_check(v);
+  };
+  auto finish_exact = [&](int pass) -> int {   // every row, everything that is left, from the floors
+    ex_rows.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) ex_rows[(size_t)i] = (int32_t)i;
+    MMF_TRY(cross_flagged_from(r, rx, cy, ex_rows, xp, yp, S, k - done, done, true, false, fkey, fid, xfail));
+    xfail_pending = true;
+    if (stats) stats->fallback_rows += n;
+    anyk_record(info, pass, k - done, 0, n);
+    return finish();
+  };
+  for (int pass = 1; done < k; ++pass) {
+    if (pass >= MMF_FAST_ANYK_MAX_PASSES - 1) return finish_exact(pass);
+    MMF_TRY(launch_scan_b16w_ceilings(sp, fkey, rx, max_n, r.lambda, n_pad, ceil, s));
+    MMF_TRY(reset_lists());
+    MMF_TRY(flags.zero(s));
+    MMF_TRY(launch_scan_b16w_xseg_ceil(sp, d_sched, grid, d_bounds, lists, L, pn, ceil, s));
+    MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
+    SelectProblem ql = r.select();
+    ql.k = K; ql.out_idx = sidx; ql.out_val = sval; ql.key_out = skey; ql.out_stride = K;
+    ql.rx = rx; ql.cy = cy;
+    ql.fail_rows = flags.fail_rows; ql.fail_count = flags.fail_count;
+    ql.two_pass = true;
+    ql.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
+    MMF_TRY(launch_select(ql, L, s));
+    MMF_TRY(launch_anyk_count(st, flags.fail_rows, flags.fail_count, fkey, fid, certified, hist, s));
+    uint32_t h[64], xf = 0;
+    MMF_HIP(hipMemcpyAsync(h, hist, (size_t)(K + 3) * 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipMemcpyAsync(&xf, xfail, 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    MMF_TRY(xfail_check(xf));
+    // the largest yield that leaves at most `budget` unflagged rows short of it
+    const int t_max = std::min(K, k - done);
+    int t = 0;
+    int64_t below = 0, short_rows = 0;   // unflagged rows with fewer than t' certified entries
+    for (int tq = 1; tq <= t_max; ++tq) {
+      below += h[tq - 1];
+      if (below > budget) break;
+      t = tq; short_rows = below;
+    }
+    if (t < 1) return finish_exact(pass);
+    MMF_TRY(launch_anyk_emit(st, certified, t, done, k, r.out_idx, r.out_val, fkey, fid, rescan_rows, rescan_count, s));
+    const int64_t rescan = (int64_t)h[K + 1] + short_rows;
+    if (rescan > 0) {
+      MMF_TRY(sorted_rows(rescan_rows, rescan, &ex_rows));
+      MMF_TRY(cross_flagged_from(r, rx, cy, ex_rows, xp, yp, S, t, done, true, done + t < k, fkey, fid, xfail));
+      xfail_pending = true;
+      if (stats) stats->fallback_rows += rescan;
+    }
+    anyk_record(info, pass, t, (int)h[K + 2], rescan);
+    done += t;
+  }
+  return finish();
+}
+
+}  // namespace mmf
+
+extern "C" {
+
+int mmf_cross_segments_wide_anyk_plan(int64_t d, int k, int* scan_kk, int* first_yield, int* min_passes) {
+  return mmf_wide_anyk_plan(d, k, 0, scan_kk, first_yield, min_passes);
+}
+
+int mmf_simtopk_cross_segments_wide_anyk(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
+                                         float lambda, int k, const int64_t* x_ptr_host, const int64_t* y_ptr_host,
+                                         int64_t n_segments, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
+                                         mmf_simtopk_stats* stats, int device_id, void* hip_stream, mmf_fast_anyk_info* info) {
+  const char* who = "simtopk_cross_segments_wide_anyk";
+  const bool self = (Y == nullptr);
+  if (self) { Y = X; m = n; y_ptr_host = x_ptr_host; }
+  if (info) memset(info, 0, sizeof(*info));
+  mmf_simtopk_stats own_stats;   // info reports the first pass's flagged rows, which the call counts in its stats
+  Request r{Call(who, device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, 0, 0, 0,
+            out_idx, out_val, stats ? stats : (info ? &own_stats : nullptr), opts && opts->profile};
+  r.wide_ok = true;
+  MMF_TRY(r.call.on_device());
+  if (n < 0 || m < 0 || d < 1) { set_error("%s: bad shape n=%lld m=%lld d=%lld", who, (long long)n, (long long)m, (long long)d); return MMF_E_INVALID; }
+  if (in_dtype != MMF_F32 && in_dtype != MMF_BF16 && in_dtype != MMF_F16) { set_error("%s: bad in_dtype %d", who, in_dtype); return MMF_E_INVALID; }
+  if (n > 0 && !X) { set_error("%s: X is NULL", who); return MMF_E_INVALID; }
+  if (n >= (int64_t)1 << 31 || m >= (int64_t)1 << 31) { set_error("%s: n and m must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  const int asked = opts ? opts->precision : MMF_PREC_AUTO;
+  const int prec = asked == MMF_PREC_AUTO ? MMF_PREC_FAST : asked;
+  const bool fast = prec != MMF_PREC_EXACT;
+  // more than one pass: the wide scan serves d but not k (the checks below refuse what makes this meaningless)
+  const bool multi = fast && d > 1024 && d <= 4096 && k >= 1 && !scan_b16w_supported(d, k);
+  MMF_TRY(r.check(multi ? MMF_PREC_EXACT : prec, true, [&] {
+    MMF_TRY(check_offsets(who, "x_ptr", x_ptr_host, n_segments, 0, 0, n));
+    MMF_TRY(check_offsets(who, "y_ptr", y_ptr_host, n_segments, 0, 0, m));
+    if (m > 0 && !Y) { set_error("%s: Y is NULL", who); return MMF_E_INVALID; }
+    MMF_TRY(check_pow2_splits(who, opts));
+    if (prec != MMF_PREC_EXACT && prec != MMF_PREC_FAST && prec != MMF_PREC_FAST_BF16) {
+      set_error("%s: bad precision %d", who, prec);
+      return MMF_E_INVALID;
+    }
+    if (opts && opts->select_wait_event) { set_error("%s: select_wait_event is not supported", who); return MMF_E_UNSUPPORTED; }
+    if (d <= 1024) {
+      set_error("%s: d = %lld is not above 1024: call mmf_simtopk_cross_segments_fast_anyk, which serves d <= 1024 for any k", who, (long long)d);
+      return MMF_E_UNSUPPORTED;
+    }
+    if (fast && d > 4096) {
+      set_error("%s: d = %lld is beyond the wide 16-bit scan (1024 < d <= 4096; MMF_PREC_EXACT serves it)", who, (long long)d);
+      return MMF_E_UNSUPPORTED;
+    }
+    if (n > 0 && (!out_idx || !out_val)) { set_error("%s: NULL output", who); return MMF_E_INVALID; }
+    for (int64_t g = 0; g < n_segments; ++g) {
+      const int64_t own = y_ptr_host[g + 1] - y_ptr_host[g];
+      if (x_ptr_host[g + 1] > x_ptr_host[g] && m - own < k) {
+        set_error("%s: segment %lld has %lld admissible columns (m = %lld minus its own %lld rows of Y), k = %d needs at least %d", who,
+                  (long long)g, (long long)(m - own), (long long)m, (long long)own, k, k);
+        return MMF_E_INVALID;
+      }
+    }
+    return MMF_OK;
+  }));
+  if (r.stats) r.stats->near_rows = -1;   // the query order is never probed here
+  if (n == 0) return MMF_OK;
+  if (!fast) {   // mmf_simtopk_cross_segments behind its checks
+    MMF_TRY(run_segmented_exact(r, self, x_ptr_host, y_ptr_host, n_segments, opts, nullptr, 0, 0.0f, true));
+    anyk_record(info, 0, k, 0, 0);
+    return MMF_OK;
+  }
+  if (!multi) {   // one pass serves: the call IS mmf_simtopk_cross_segments_wide
+    MMF_TRY(run_cross_segments_wide(r, self, x_ptr_host, y_ptr_host, n_segments, opts));
+    anyk_record(info, 0, k, 0, r.stats ? r.stats->fallback_rows : 0);
+    return MMF_OK;
+  }
+  r.precision = prec;
+  return cross_wide_anyk_run(r, self, x_ptr_host, y_ptr_host, n_segments, opts, info);
+}
+
+}  // extern "C"

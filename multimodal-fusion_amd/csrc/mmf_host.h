@@ -25,6 +25,7 @@
 #include "../../include/ext/mmf_hg_wide_anyk.h"
 #include "../../include/ext/mmf_hg_seg_anyk.h"
 #include "../../include/ext/mmf_hg_cross_seg_anyk.h"
+#include "../../include/ext/mmf_hg_cross_segw_anyk.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -479,6 +480,10 @@ int launch_scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t 
 // the excluded column range (first, count) of every query row, lists == L.lists == the table's list count (any even number).
 int launch_scan_b16w_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, int lists, const CandLists& L,
                           const ScanB16Panel& pn, hipStream_t s);
+// the later passes of mmf_simtopk_cross_segments_wide_anyk: the same launch under a ceiling per query row (ceil
+// [n_pad] by row of X, what launch_scan_b16w_ceilings leaves: the plain images' positions are rows) — full-depth lists only
+int launch_scan_b16w_xseg_ceil(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, int lists, const CandLists& L,
+                               const ScanB16Panel& pn, const float* ceil, hipStream_t s);
 
 // mmf_scan_b16c.hip: the 16-bit scan of the combined key eh + eg (mmf_simtopk_combined_fast), 1 <= d <= 4096,
 // k + self <= 20: the wide scan's structure with the position term formed in the epilogue.  One MMF_RBF operand image scanned

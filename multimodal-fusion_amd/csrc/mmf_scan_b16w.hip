@@ -73,7 +73,8 @@
 // the plain launch again with a ceiling per query row: ceil_i = map_i(floor key) + E1_i + E2_i (wide_ceil_kernel; E1, E2 as above),
 // so that no column ranking after the row's floor is scanned above it.  The epilogue's hit branch sets the gathered values above
 // the ceiling to -inf before they are offered; everything said above about lists, thresholds and overflow lists then holds for the
-// columns at or below the ceiling.
+// columns at or below the ceiling.  The cross-segment call's later passes (mmf_simtopk_cross_segments_wide_anyk) run
+// the masked table-driven launch under the same ceilings; there is no overflow list on that schedule, so a crowded row is flagged.
 #include "mmf_dev.h"
 #include "mmf_host.h"
 
@@ -328,9 +329,13 @@ constexpr size_t scan_b16w_lds(int cap) { return (size_t)2 * W_STAGEB + (size_t)
 // compare sits THERE, on the lane's 16 gathered values before they are offered — the sub-tile's 14 v_max + two compares are
 // untouched, and the ceiling is loaded inside the branch, so the k-loop carries no register for it.  A value set to -inf there
 // reaches no list, overflow list or sink slot, proven, lost, seed or threshold.
+// CEIL with XSEG (mmf_simtopk_cross_segments_wide_anyk; CEIL with the plain SEG stays excluded): both images of the
+// cross form are the plain ones, so the query position is the row of X and a.ceil[qpos] is the row's ceiling.  Mask and ceiling do not
+// meet: the mask writes -inf into the accumulators ahead of the tile maxima, the ceiling compare works on the gathered values inside
+// the hit branch and leaves a -inf as it is (-inf > ce is false for every ceiling).
 template <bool F16, int CAP, bool SEG = false, bool SINK = false, bool XSEG = false, bool CEIL = false>
 __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
-  static_assert(!CEIL || (!SEG && !XSEG), "per-row ceilings: the plain schedule only");
+  static_assert(!CEIL || !SEG || XSEG, "per-row ceilings: the plain schedule, or under the cross-segment mask");
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   char* stages = smem;                                                   // [2][W_STAGEB]
   float* cbs = reinterpret_cast<float*>(smem + 2 * W_STAGEB);            // [2][W_CT] bias of the tile being accumulated / the next
@@ -697,6 +702,11 @@ int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) 
     MMF_LAUNCH_CHECK();
     return MMF_OK;
   };
+  if constexpr (XSEG && CEIL) {   // full-depth lists only: the later passes of the cross-segment any-k call
+    static_assert(CAP == W_CAP_BIG && !SINK, "ceilings under the cross-segment mask: every pass is 20 deep");
+    if (f16) return go(scan_b16w_kernel<true, CAP, true, false, true, true>);
+    return go(scan_b16w_kernel<false, CAP, true, false, true, true>);
+  }
   if constexpr (CEIL) {
     if (f16) return go(scan_b16w_kernel<true, CAP, false, SINK, false, true>);
     return go(scan_b16w_kernel<false, CAP, false, SINK, false, true>);
@@ -728,8 +738,23 @@ int scan_b16w_col_tile() { return W_CT; }
 // number: a run cut by a hole is two entries — and a block with fewer entries leaves the rest of its rows' lists empty (the caller
 // zeroes the counts).  With more than one pair the lists carry keys and margins and wide_seed_union_kernel settles every row's
 // threshold over all of its entries, as in the other launchers.  No overflow lists: a crowded row is flagged.
+static int scan_b16w_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, int lists, const CandLists& L,
+                          const ScanB16Panel& pn, const float* ceil, hipStream_t s);
 int launch_scan_b16w_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, int lists, const CandLists& L,
                           const ScanB16Panel& pn, hipStream_t s) {
+  return scan_b16w_xseg(p, sched, grid, bounds, lists, L, pn, nullptr, s);
+}
+// The same launch with a ceiling per query row (mmf_simtopk_cross_segments_wide_anyk): ceil [n_pad] by row of X, what
+// launch_scan_b16w_ceilings leaves — the plain images' positions are rows.  Full-depth lists only (every pass of that call is 20 deep).
+int launch_scan_b16w_xseg_ceil(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, int lists, const CandLists& L,
+                               const ScanB16Panel& pn, const float* ceil, hipStream_t s) {
+  if (!ceil) { set_error("scan_b16w_xseg_ceil: ceilings missing"); return MMF_E_INTERNAL; }
+  if (L.cap != W_CAP_BIG) { set_error("scan_b16w_xseg_ceil: list capacity %d, the ceilings run at the full depth (%d)", L.cap, W_CAP_BIG); return MMF_E_INTERNAL; }
+  return scan_b16w_xseg(p, sched, grid, bounds, lists, L, pn, ceil, s);
+}
+// The launch itself.  ceil: nullptr, or the rows' ceilings (CEIL kernels).
+static int scan_b16w_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, int lists, const CandLists& L,
+                          const ScanB16Panel& pn, const float* ceil, hipStream_t s) {
   if (grid <= 0 || p.n_rows <= 0) return MMF_OK;
   if (!scan_b16w_supported(p.d, p.kk) || p.dp != scan_b16w_dp(p.d)) {
     set_error("scan_b16w_xseg: d = %lld (padded %d), k = %d outside 1024 < d <= 4096, k <= 20", (long long)p.d, p.dp, p.kk);
@@ -752,9 +777,10 @@ int launch_scan_b16w_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t
   a.lists_total = L.lists; a.list_base = 0;
   a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride;
   a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.cand_keys = L.keys; a.margin_out = L.margin;
-  a.sched = sched; a.bounds = bounds;
-  MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, true, false, true>(a, p.f16, grid, s))
-                               : (launch_b16w_t<W_CAP_BIG, true, false, true>(a, p.f16, grid, s)));
+  a.sched = sched; a.bounds = bounds; a.ceil = ceil;
+  if (ceil) MMF_TRY((launch_b16w_t<W_CAP_BIG, true, false, true, true>(a, p.f16, grid, s)));
+  else MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, true, false, true>(a, p.f16, grid, s))
+                                    : (launch_b16w_t<W_CAP_BIG, true, false, true>(a, p.f16, grid, s)));
   if (lists > 2) {
     wide_seed_union_kernel<<<dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s>>>(L.cnt, L.keys, L.margin, L.lists, L.cap, p.kk, pn.seed,
                                                                                      p.n_rows, nullptr, nullptr);
