@@ -156,6 +156,12 @@ CROSS_ANYK_EXPORTS = ["mmf_simtopk_cross_segments_fast_anyk", "mmf_cross_segment
 # tests/test_cross_segments_wide_anyk_cpu.py.
 CROSS_WIDE_ANYK_EXPORTS = ["mmf_simtopk_cross_segments_wide_anyk", "mmf_cross_segments_wide_anyk_plan"]
 
+# The segmented wide 16-bit top-k for any k (include/ext/mmf_hg_segw_anyk.h): an addition to ABI version 3 in a header
+# of its own; the twin of SEG_ANYK_EXPORTS for 1024 < d <= 4096 (same arguments, same info struct, same synchronisation: once per pass,
+# once more in a pass that sends rows to the exact rescan; mmf_segmented_wide_anyk_plan is host-only).  Pinned by
+# tests/test_segmented_wide_anyk_cpu.py.
+SEGW_ANYK_EXPORTS = ["mmf_simtopk_segmented_wide_anyk", "mmf_segmented_wide_anyk_plan"]
+
 
 class FastAnykInfo(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
@@ -280,6 +286,10 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_cross_segments_wide_anyk.restype = ci
     L.mmf_cross_segments_wide_anyk_plan.argtypes = list(L.mmf_cross_segments_anyk_plan.argtypes)
     L.mmf_cross_segments_wide_anyk_plan.restype = ci
+    L.mmf_simtopk_segmented_wide_anyk.argtypes = list(L.mmf_simtopk_segmented_fast_anyk.argtypes)
+    L.mmf_simtopk_segmented_wide_anyk.restype = ci
+    L.mmf_segmented_wide_anyk_plan.argtypes = list(L.mmf_segmented_anyk_plan.argtypes)
+    L.mmf_segmented_wide_anyk_plan.restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

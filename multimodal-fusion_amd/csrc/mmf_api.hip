@@ -4843,3 +4843,364 @@ int mmf_simtopk_cross_segments_wide_anyk(const void* X, int64_t n, const void* Y
 }
 
 }  // extern "C"
+
+// ---- mmf_simtopk_segmented_wide_anyk (include/ext/mmf_hg_segw_anyk.h) ------------------------------------------
+// segmented_anyk_run with the wide pieces of the segmented body (mmf::mmf_simtopk_segmented, wide_allowed), 1024 < d <= 4096: the
+// segment-padded images at the wide scan's padded dim and 128-row tiles, the work table at the full depth (20 entries, 32-entry
+// lists) with a forced opts->col_splits under the body's bounds (automatic: one range per segment), no id scratch.  r: checked,
+// begun, n > 0, r.precision MMF_PREC_FAST or _FAST_BF16, k + self beyond one pass.  A segment is SERVED when it has rows and at
+// least k admissible columns; the others go through the exact launch loop in pass 0, as in the body.  Pass 0: launch_scan_b16w_seg,
+// the audit, the re-rank of K entries into the k-wide output rows, every served row's floor left behind (the flagged ones by the
+// exact pass, gathered per segment).  A later pass: ceilings by operand position with the wide margin
+// (launch_scan_b16w_ceilings_gather), the same device work table under them (launch_scan_b16w_seg_ceil: the scan and, with several
+// ranges per segment, its threshold union), the audit, the re-rank into staging rows, count, one yield for the whole call, emit, and
+// the exact rescan — one gathered group per segment — of the served rows that were flagged or short.  Floor ids live as rows of Y
+// and are rebased around the per-segment exact passes (launch_floor_rebase).  No overflow lists on this schedule: a crowded row is
+// flagged.  A served segment that runs out of unemitted columns (adm - done < K) stays in the work table, as in segmented_anyk_run.
+namespace mmf {
+
+static int segw_anyk_run(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts,
+                         mmf_fast_anyk_info* info) {
+  const char* who = r.call.who;
+  const hipStream_t s = r.call.s;
+  const int64_t n = r.n, m = r.m, d = r.d;
+  const int k = r.k, self1 = r.exclude_self ? 1 : 0, depth = anyk_depth(d), K = depth - self1;
+  const bool f16 = r.precision == MMF_PREC_FAST, profile = r.profile;
+  mmf_simtopk_stats* stats = r.stats;
+  const int dp = scan_b16w_dp(d), qt = scan_b16w_queries_per_block(), kTile = scan_b16w_col_tile(), bcap = scan_b16w_cap(depth);
+
+  // ---- the body's tables: column ranges, work table, position -> row gathers; and per row the first row of Y of its segment -------
+  std::vector<int64_t> adm(S);
+  std::vector<char> on_fast(S, 0);
+  int64_t unserved_rows = 0, n_served = 0;
+  for (int64_t g = 0; g < S; ++g) {
+    const int64_t ng = xp[g + 1] - xp[g];
+    adm[g] = admissible_columns(xp[g], ng, yp[g], yp[g + 1] - yp[g], r.exclude_self);
+    if (ng == 0) continue;
+    if (adm[g] < k) { unserved_rows += ng; continue; }
+    on_fast[g] = 1;
+    n_served += ng;
+  }
+  // the body's rule: a forced count is taken while select's capacity per row holds 2 x splits lists; each segment
+  // caps its count at its own tile count, rounded down to a power of two
+  int call_splits = 1, max_splits = 1;
+  {
+    int64_t R = 0;
+    for (int64_t g = 0; g < S; ++g)
+      if (on_fast[g]) R += (xp[g + 1] - xp[g] + qt - 1) / qt;
+    const int forced = opts ? opts->col_splits : 0;
+    const auto fits = [&](int sp) { return 2 * sp * bcap <= 1024 - kSpillCap; };
+    if (forced > 0) { while (call_splits < forced && fits(2 * call_splits)) call_splits <<= 1; }
+    else if (wide_seg_auto_splits()) { while (R > 0 && R * call_splits < 256 && fits(2 * call_splits)) call_splits <<= 1; }
+  }
+  std::vector<int32_t> sched, col0(n, 0), served_rows;
+  served_rows.reserve((size_t)n_served);
+  int64_t nq_pos = 0, mc_pos = 0;
+  for (int64_t g = 0; g < S; ++g) {
+    if (!on_fast[g]) continue;
+    const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g];
+    const int64_t tiles = (mg + kTile - 1) / kTile;
+    const int64_t t0 = mc_pos / kTile;
+    int sp = 1;                                   // column ranges of this segment: one table entry and one list pair each
+    while (2 * sp <= call_splits && 2 * sp <= tiles) sp <<= 1;
+    if (sp > max_splits) max_splits = sp;
+    const int64_t tps = (tiles + sp - 1) / sp;
+    for (int64_t b = 0; b < ng; b += qt) {
+      for (int c = 0; c < sp; ++c) {
+        const int64_t tb = std::min(t0 + c * tps, t0 + tiles), te = std::min(tb + tps, t0 + tiles);
+        const int32_t e[8] = {(int32_t)(nq_pos + b), (int32_t)(xp[g] + b), (int32_t)(ng - b < qt ? ng - b : qt), (int32_t)tb,
+                              (int32_t)te, (int32_t)(uint32_t)(yp[g] - t0 * kTile), 2 * c, 0};
+        sched.insert(sched.end(), e, e + 8);
+      }
+    }
+    for (int64_t i = 0; i < ng; ++i) { col0[xp[g] + i] = (int32_t)yp[g]; served_rows.push_back((int32_t)(xp[g] + i)); }
+    nq_pos += (ng + qt - 1) / qt * qt;
+    mc_pos += tiles * kTile;
+    if (nq_pos >= (int64_t(1) << 31) || mc_pos >= (int64_t(1) << 31)) { set_error("%s: padded images too large", who); return MMF_E_UNSUPPORTED; }
+  }
+  const int64_t grid = (int64_t)sched.size() / 8;
+  std::vector<int32_t> qgather(nq_pos, -1), cgather(mc_pos, -1);
+  {
+    int64_t qpos = 0, cpos = 0;
+    for (int64_t g = 0; g < S; ++g) {
+      if (!on_fast[g]) continue;
+      const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g];
+      for (int64_t i = 0; i < ng; ++i) qgather[qpos + i] = (int32_t)(xp[g] + i);
+      for (int64_t j = 0; j < mg; ++j) cgather[cpos + j] = (int32_t)(yp[g] + j);
+      qpos += (ng + qt - 1) / qt * qt;
+      cpos += (mg + kTile - 1) / kTile * kTile;
+    }
+  }
+
+  // ---- workspace (slot 0): the body's, then floors, bookkeeping, ceilings and the staging rows -----------------------------------
+  const int64_t nq_pad = (nq_pos + 255) / 256 * 256, mc_pad = (mc_pos + 255) / 256 * 256;
+  const int lists = 2 * max_splits;
+  const int64_t n_seed = n;
+  const size_t stage = (size_t)n * K;
+  size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + FlagBlock::bytes(n);
+  if (grid > 0)
+    need += HalfImage::bytes(nq_pad, dp) + HalfImage::bytes(mc_pad, dp) + ws_bytes(4, 4) + ws_bytes(sched.size(), 4) +
+            ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + b16_lists_bytes(n, lists, bcap) +
+            ws_bytes(2 * (size_t)n_seed, 4) + ws_bytes(select_order_bytes(n), 1) +
+            5 * ws_bytes(n, 4) + ws_bytes(nq_pad, 4) + ws_bytes(64, 4) + ws_bytes(4, 4) + ws_bytes(stage, 8) + 2 * ws_bytes(stage, 4);
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* rx = ws.take<float>(n);
+  float* cy = self ? rx : ws.take<float>(m);
+  FlagBlock flags;
+  flags.carve(ws, n);
+  MMF_TRY(flags.zero(s));
+
+  EventTimer t_prep, t_scan, t_sel, t_fb;
+  MMF_TRY(t_prep.start(profile, s));
+  uint32_t* max_n = nullptr;
+  if (grid > 0) { max_n = ws.take<uint32_t>(4); MMF_HIP(hipMemsetAsync(max_n, 0, 16, s)); }
+  MMF_TRY(launch_row_scalars(r.X, n, d, r.dtype, r.metric, rx, max_n, s));
+  if (!self && m > 0) MMF_TRY(launch_row_scalars(r.Y, m, d, r.dtype, r.metric, cy, max_n, s));
+
+  // kq entries per row from column out_off0 on for `rows` (served rows, ascending: grouped by segment) by the exact pass, one
+  // gathered group per segment; `whole`: also the unserved segments, for what they have (pass 0 only).  Does not synchronise.
+  int32_t* d_rows = nullptr; int32_t* d_col0 = nullptr;
+  float* fkey = nullptr; uint32_t* fid = nullptr;
+  auto exact_rows = [&](const std::vector<int32_t>& rows, int kq, int out_off0, bool floors_in, bool floors_out, bool whole) -> int {
+    ExactPass ex(r, rx, cy);
+    ex.same = self;
+    ex.out_stride = k; ex.out_off0 = out_off0;
+    ex.floors_in = floors_in; ex.floors_out = floors_out;
+    ex.row_floor_key = fkey; ex.row_floor_id = fid;
+    const int64_t cnt = (int64_t)rows.size();
+    for (int64_t g = 0, e = 0; g < S; ++g) {
+      const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g], e0 = e;
+      if (on_fast[g]) {
+        while (e < cnt && rows[e] < xp[g + 1]) ++e;
+        if (e > e0) ex.add(ExactGroup{e0, e - e0, true, yp[g], mg, kq});
+      } else if (whole && ng > 0) {   // short of k admissible columns: its top-(m_g - self) first, then -1 / -inf
+        MMF_HIP(hipMemsetAsync(r.out_idx + xp[g] * k, 0xff, (size_t)ng * k * 8, s));
+        MMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.out_val + xp[g] * k), (int)0xff800000u, (size_t)ng * k, s));
+        if (adm[g] > 0) ex.add(ExactGroup{xp[g], ng, false, yp[g], mg, (int)adm[g]});
+      }
+    }
+    if (ex.pieces.empty()) return MMF_OK;
+    ex.n_ids = cnt; ex.row_ids = d_rows;
+    Workspace aux;   // lists and f32 images in the second workspace slot
+    MMF_TRY(r.call.workspace(ex.image_bytes() + ex.list_bytes(), &aux, 1));
+    ExactLists B;
+    B.carve(aux, ex.rows_total, ex.list_words, ex.cap(), ex.floors());
+    if (cnt > 0) MMF_TRY(upload_table(s, d_rows, rows.data(), (size_t)cnt * 4));
+    if (floors_in) MMF_TRY(launch_floor_rebase(d_rows, cnt, fid, d_col0, false, s));
+    MMF_TRY(B.zero(s));
+    MMF_TRY(ex.run(aux, B));
+    if (floors_out) MMF_TRY(launch_floor_rebase(d_rows, cnt, fid, d_col0, true, s));
+    return MMF_OK;
+  };
+
+  if (grid == 0) {   // no segment is served: the launch loop answers the call
+    MMF_TRY(t_prep.stop(s));
+    MMF_TRY(t_fb.start(profile, s));
+    MMF_TRY(exact_rows({}, 0, 0, false, false, true));
+    MMF_TRY(t_fb.stop(s));
+    MMF_HIP(hipStreamSynchronize(s));
+    fill_stats(stats, MMF_PREC_EXACT, 1, 0, t_prep.ms(), t_fb.ms(), 0.f, 0.f, 0, 0, 0, flags.h_tot);
+    anyk_record(info, 0, k, 0, 0);
+    return MMF_OK;
+  }
+
+  HalfImage Q, C;
+  Q.carve(ws, nq_pad, dp);
+  C.carve(ws, mc_pad, dp);
+  int32_t* d_sched = ws.take<int32_t>(sched.size());
+  int32_t* d_qg = ws.take<int32_t>(nq_pos);
+  int32_t* d_cg = ws.take<int32_t>(mc_pos);
+  const CandLists L = carve_b16_lists(ws, n, lists, bcap);
+  int32_t* seed = ws.take<int32_t>(2 * (size_t)n_seed);
+  char* order_scratch = ws.take<char>(select_order_bytes(n));
+  fkey = ws.take<float>(n); fid = ws.take<uint32_t>(n);
+  int32_t* certified = ws.take<int32_t>(n); int32_t* rescan_rows = ws.take<int32_t>(n);
+  d_col0 = ws.take<int32_t>(n); d_rows = rescan_rows;   // (a pass's rescan list is read to the host before the sorted rows take its place)
+  float* ceil = ws.take<float>(nq_pad);
+  uint32_t* hist = ws.take<uint32_t>(64); uint32_t* rescan_count = ws.take<uint32_t>(4);
+  int64_t* sidx = ws.take<int64_t>(stage); float* sval = ws.take<float>(stage); float* skey = ws.take<float>(stage);
+  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
+  MMF_TRY(upload_table(s, d_qg, qgather.data(), (size_t)nq_pos * 4));
+  MMF_TRY(upload_table(s, d_cg, cgather.data(), (size_t)mc_pos * 4));
+  MMF_TRY(upload_table(s, d_col0, col0.data(), (size_t)n * 4));
+  MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
+  MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
+  MMF_TRY(launch_prep_half_gather({r.Y, m, d, r.dtype, r.metric, cy, max_n}, d_cg, mc_pos, C, dp, f16, s));
+  MMF_TRY(launch_prep_half_gather({r.X, n, d, r.dtype, r.metric, rx, max_n}, d_qg, nq_pos, Q, dp, f16, s));
+  MMF_TRY(t_prep.stop(s));
+
+  ScanB16Panel pn;
+  pn.seed = seed; pn.seed_stride = n_seed; pn.share = 0;
+  const ScanB16Problem sp(Q, C, n, m, mc_pad, dp, d, f16, r.metric, depth);
+  // what the body resets before its scan (rows of unserved segments keep empty lists: the re-rank reports them every pass)
+  auto reset_lists = [&]() -> int {
+    MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));
+    MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
+    MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));    // no overflow lists here: select reads them as empty
+    MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n_seed * 8, s));
+    return MMF_OK;
+  };
+  // the served rows among `cnt` device rows, ascending (one more synchronisation)
+  auto served_of = [&](const int32_t* dev_rows, int64_t cnt, std::vector<int32_t>* out) -> int {
+    std::vector<int32_t> h((size_t)cnt);
+    if (cnt > 0) {
+      MMF_HIP(hipMemcpyAsync(h.data(), dev_rows, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipStreamSynchronize(s));
+    }
+    out->clear();
+    for (int32_t row : h) {
+      const int64_t g = (int64_t)(std::upper_bound(xp, xp + S + 1, (int64_t)row) - xp) - 1;
+      if (g >= 0 && g < S && on_fast[g]) out->push_back(row);
+    }
+    std::sort(out->begin(), out->end());
+    return MMF_OK;
+  };
+
+  // ---- pass 0: K entries per row, k-wide rows, floors left ----------------------------------------------------------------------
+  MMF_TRY(reset_lists());
+  MMF_TRY(t_scan.start(profile, s));
+  MMF_TRY(launch_scan_b16w_seg(sp, d_sched, grid, lists, L, pn, s));
+  MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
+  MMF_TRY(t_scan.stop(s));
+  SelectProblem q = r.select();
+  q.k = K; q.out_stride = k;
+  q.rx = rx; q.cy = cy;
+  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = stats ? flags.cand_total : nullptr;
+  q.two_pass = true;
+  q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
+  q.floor_key_out = fkey; q.floor_id_out = fid;
+  MMF_TRY(t_sel.start(profile, s));
+  MMF_TRY(launch_select(q, L, s));
+  MMF_TRY(t_sel.stop(s));
+  MMF_TRY(flags.read(stats != nullptr, s));
+  std::vector<int32_t> ex_rows;
+  MMF_TRY(served_of(flags.fail_rows, flags.h_fail4[0], &ex_rows));
+  const int64_t fallback0 = (int64_t)ex_rows.size();
+  MMF_TRY(t_fb.start(profile && (fallback0 > 0 || unserved_rows > 0), s));
+  MMF_TRY(exact_rows(ex_rows, K, 0, false, true, true));
+  MMF_TRY(t_fb.stop(s));
+  {
+    const int64_t overflow_rows = flags.h_fail4[1] < (uint32_t)fallback0 ? flags.h_fail4[1] : fallback0;
+    fill_stats(stats, r.precision, max_splits, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback0, overflow_rows,
+               fallback0 - overflow_rows, flags.h_tot);
+  }
+  anyk_record(info, 0, K, 0, fallback0);
+
+  // ---- later passes ---------------------------------------------------------------------------------------------------------------
+  const int64_t budget = n_served / anyk_short_div();
+  const AnykStage st{sidx, sval, skey, n, K, 0};
+  int done = K;
+  auto finish_exact = [&](int pass) -> int {   // every served row, everything that is left
+    MMF_TRY(exact_rows(served_rows, k - done, done, true, false, false));
+    if (stats) stats->fallback_rows += n_served;
+    anyk_record(info, pass, k - done, 0, n_served);
+    return MMF_OK;
+  };
+  for (int pass = 1; done < k; ++pass) {
+    if (pass >= MMF_FAST_ANYK_MAX_PASSES - 1) return finish_exact(pass);
+    MMF_TRY(launch_scan_b16w_ceilings_gather(sp, d_qg, nq_pos, fkey, rx, max_n, r.lambda, nq_pad, ceil, s));
+    MMF_TRY(reset_lists());
+    MMF_TRY(flags.zero(s));
+    MMF_TRY(launch_scan_b16w_seg_ceil(sp, d_sched, grid, lists, L, pn, ceil, s));
+    MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
+    SelectProblem ql = r.select();
+    ql.k = K; ql.out_idx = sidx; ql.out_val = sval; ql.key_out = skey; ql.out_stride = K;
+    ql.rx = rx; ql.cy = cy;
+    ql.fail_rows = flags.fail_rows; ql.fail_count = flags.fail_count;
+    ql.two_pass = true;
+    ql.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
+    MMF_TRY(launch_select(ql, L, s));
+    MMF_TRY(launch_anyk_count(st, flags.fail_rows, flags.fail_count, fkey, fid, certified, hist, s));
+    uint32_t h[64];
+    MMF_HIP(hipMemcpyAsync(h, hist, (size_t)(K + 3) * 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    // the largest yield that leaves at most `budget` unflagged rows short of it (unserved rows are always flagged)
+    const int t_max = std::min(K, k - done);
+    int t = 0;
+    int64_t below = 0, short_rows = 0;
+    for (int tq = 1; tq <= t_max; ++tq) {
+      below += h[tq - 1];
+      if (below > budget) break;
+      t = tq; short_rows = below;
+    }
+    if (t < 1) return finish_exact(pass);
+    MMF_TRY(launch_anyk_emit(st, certified, t, done, k, r.out_idx, r.out_val, fkey, fid, rescan_rows, rescan_count, s));
+    const int64_t listed = (int64_t)h[K + 1] + short_rows;   // the emit kernel's list: flagged rows (the unserved ones among them) and short rows
+    int64_t rescan = 0;
+    if (listed > unserved_rows) {
+      MMF_TRY(served_of(rescan_rows, listed, &ex_rows));
+      rescan = (int64_t)ex_rows.size();
+      MMF_TRY(exact_rows(ex_rows, t, done, true, done + t < k, false));
+      if (stats) stats->fallback_rows += rescan;
+    }
+    anyk_record(info, pass, t, (int)h[K + 2], rescan);
+    done += t;
+  }
+  return MMF_OK;
+}
+
+}  // namespace mmf
+
+extern "C" {
+
+int mmf_segmented_wide_anyk_plan(int64_t d, int k, int exclude_self, int* scan_kk, int* first_yield, int* min_passes) {
+  return mmf_wide_anyk_plan(d, k, exclude_self, scan_kk, first_yield, min_passes);
+}
+
+int mmf_simtopk_segmented_wide_anyk(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
+                                    float lambda, int k, int exclude_self, const int64_t* x_ptr_host, const int64_t* y_ptr_host,
+                                    int64_t n_segments, int64_t* out_idx, float* out_val, const mmf_simtopk_opts* opts,
+                                    mmf_simtopk_stats* stats, int device_id, void* hip_stream, mmf_fast_anyk_info* info) {
+  const char* who = "simtopk_segmented_wide_anyk";
+  const void* Y_in = Y; const int64_t m_in = m; const int64_t* y_ptr_in = y_ptr_host;
+  const bool self = (Y == nullptr);
+  if (self) { Y = X; m = n; y_ptr_host = x_ptr_host; }
+  if (info) memset(info, 0, sizeof(*info));
+  mmf_simtopk_stats own_stats;   // info reports the first pass's flagged rows, which the call counts in its stats
+  Request r{Call(who, device_id, hip_stream), X, n, Y, m, d, in_dtype, metric, lambda, k, exclude_self, 0, 0,
+            out_idx, out_val, stats ? stats : (info ? &own_stats : nullptr), opts && opts->profile};
+  r.wide_ok = true;
+  const int asked = opts ? opts->precision : MMF_PREC_AUTO;
+  const int prec = asked == MMF_PREC_AUTO ? MMF_PREC_FAST : asked;
+  const bool fast = prec != MMF_PREC_EXACT;
+  // more than one pass: the wide scan serves d but not k + self (the checks below refuse what makes this meaningless)
+  const bool multi = fast && d > 1024 && d <= 4096 && k >= 1 && !scan_b16w_supported(d, k + (exclude_self ? 1 : 0));
+  MMF_TRY(r.check(multi ? MMF_PREC_EXACT : prec, true, [&] {
+    MMF_TRY(check_offsets(who, "x_ptr", x_ptr_host, n_segments, 0, 0, n));
+    MMF_TRY(check_offsets(who, "y_ptr", y_ptr_host, n_segments, 0, 0, m));
+    if (m > 0 && !Y) { set_error("%s: Y is NULL", who); return MMF_E_INVALID; }
+    MMF_TRY(check_pow2_splits(who, opts));
+    if (asked < MMF_PREC_AUTO || asked > MMF_PREC_FAST_BF16) { set_error("%s: bad precision %d", who, asked); return MMF_E_INVALID; }
+    if (opts && opts->select_wait_event) { set_error("%s: select_wait_event is not supported", who); return MMF_E_UNSUPPORTED; }
+    if (d <= 1024) {
+      set_error("%s: d = %lld is not above 1024: call mmf_simtopk_segmented_fast_anyk, which serves d <= 1024 for any k", who, (long long)d);
+      return MMF_E_UNSUPPORTED;
+    }
+    if (fast && d > 4096) {
+      set_error("%s: d = %lld is beyond the wide 16-bit scan (1024 < d <= 4096; MMF_PREC_EXACT serves it)", who, (long long)d);
+      return MMF_E_UNSUPPORTED;
+    }
+    return MMF_OK;
+  }));
+  if (r.stats) r.stats->near_rows = -1;   // the query order is never probed here
+  if (n == 0) return MMF_OK;
+  if (!fast) {   // mmf_simtopk_segmented_exact behind its checks
+    MMF_TRY(run_segmented_exact(r, self, x_ptr_host, y_ptr_host, n_segments, opts, nullptr, 0, 0.0f));
+    anyk_record(info, 0, k, 0, 0);
+    return MMF_OK;
+  }
+  if (!multi) {   // one pass serves: the call IS mmf_simtopk_segmented_wide
+    mmf_simtopk_opts one{};
+    if (opts) one = *opts;
+    one.precision = prec;
+    MMF_TRY(mmf::mmf_simtopk_segmented(who, true, X, n, Y_in, m_in, d, in_dtype, metric, lambda, k, exclude_self, x_ptr_host, y_ptr_in,
+                                       n_segments, out_idx, out_val, &one, r.stats, device_id, hip_stream));
+    anyk_record(info, 0, k, 0, r.stats ? r.stats->fallback_rows : 0);
+    return MMF_OK;
+  }
+  r.precision = prec;
+  return segw_anyk_run(r, self, x_ptr_host, y_ptr_host, n_segments, opts, info);
+}
+
+}  // extern "C"

@@ -26,6 +26,7 @@
 #include "../../include/ext/mmf_hg_seg_anyk.h"
 #include "../../include/ext/mmf_hg_cross_seg_anyk.h"
 #include "../../include/ext/mmf_hg_cross_segw_anyk.h"
+#include "../../include/ext/mmf_hg_segw_anyk.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -476,6 +477,14 @@ int launch_scan_b16w_ceilings(const ScanB16Problem& p, const float* floor_key, c
 // largest number of column ranges of a segment (a power of two).
 int launch_scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, int lists, const CandLists& L, const ScanB16Panel& pn,
                          hipStream_t s);
+// The later passes of mmf_simtopk_segmented_wide_anyk: the same launch with a ceiling per OPERAND POSITION (ceil
+// [nq_pad], positions of the segment-padded query image; +inf for padding) — full-depth lists only — and the ceilings of those
+// positions: gather [n_pos] is the row of X at each position (-1: padding), floor_key and rx are indexed by row of X, the norms by
+// position, the margin's maxima are those of the whole padded candidate image
+int launch_scan_b16w_seg_ceil(const ScanB16Problem& p, const int32_t* sched, int64_t grid, int lists, const CandLists& L, const ScanB16Panel& pn,
+                              const float* ceil, hipStream_t s);
+int launch_scan_b16w_ceilings_gather(const ScanB16Problem& p, const int32_t* gather, int64_t n_pos, const float* floor_key, const float* rx,
+                                     const uint32_t* max_n, float lambda, int64_t nq_pad, float* ceil, hipStream_t s);
 // Cross-segment form: plain images on both sides, `sched` a device copy of cross_segw_table, `bounds` [n_pad][2]
 // the excluded column range (first, count) of every query row, lists == L.lists == the table's list count (any even number).
 int launch_scan_b16w_xseg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, const uint32_t* bounds, int lists, const CandLists& L,

@@ -75,6 +75,8 @@
 // the ceiling to -inf before they are offered; everything said above about lists, thresholds and overflow lists then holds for the
 // columns at or below the ceiling.  The cross-segment call's later passes (mmf_simtopk_cross_segments_wide_anyk) run
 // the masked table-driven launch under the same ceilings; there is no overflow list on that schedule, so a crowded row is flagged.
+// The segmented call's later passes (mmf_simtopk_segmented_wide_anyk) run the table-driven launch under ceilings
+// indexed by operand position (wide_ceil_kernel<true> reads the rows' floors through the position -> row table); no overflow list either.
 #include "mmf_dev.h"
 #include "mmf_host.h"
 
@@ -138,7 +140,10 @@ struct ScanB16WArgs {
   // take (its own segment's rows of Y); rows of the padding exclude nothing
   const uint32_t* bounds;
   // CEIL kernels only (launch_scan_b16w_ceil): [n_pad] per query row, the largest scanned value the row may still take, in the
-  // kernel's own units (bias and 2^(2e) scale included); padding rows: +inf
+  // kernel's own units (bias and 2^(2e) scale included); padding rows: +inf.  Indexed by OPERAND POSITION (qpos), like q_zn / q_rn /
+  // q_un: the plain schedule's positions are its rows, and so are the cross-segment (XSEG) one's, whose images are the plain ones
+  // (launch_scan_b16w_ceilings fills both); the table-driven (SEG) one's are positions of the segment-padded query image ([nq_pad];
+  // launch_scan_b16w_ceilings_gather fills them through the position -> row table)
   const float* ceil;
 };
 
@@ -329,13 +334,16 @@ constexpr size_t scan_b16w_lds(int cap) { return (size_t)2 * W_STAGEB + (size_t)
 // compare sits THERE, on the lane's 16 gathered values before they are offered — the sub-tile's 14 v_max + two compares are
 // untouched, and the ceiling is loaded inside the branch, so the k-loop carries no register for it.  A value set to -inf there
 // reaches no list, overflow list or sink slot, proven, lost, seed or threshold.
-// CEIL with XSEG (mmf_simtopk_cross_segments_wide_anyk; CEIL with the plain SEG stays excluded): both images of the
+// CEIL with XSEG (mmf_simtopk_cross_segments_wide_anyk): both images of the
 // cross form are the plain ones, so the query position is the row of X and a.ceil[qpos] is the row's ceiling.  Mask and ceiling do not
 // meet: the mask writes -inf into the accumulators ahead of the tile maxima, the ceiling compare works on the gathered values inside
 // the hit branch and leaves a -inf as it is (-inf > ce is false for every ceiling).
+// CEIL with the plain SEG (mmf_simtopk_segmented_wide_anyk): qpos is the position in the segment-padded query image
+// and lrow the row of X; the hit branch reads a.ceil[qpos], so the ceilings of a segmented pass are indexed by operand position, like
+// the norms (launch_scan_b16w_ceilings_gather).  A padding position inside a segment's last block carries +inf and is not valid anyway.
 template <bool F16, int CAP, bool SEG = false, bool SINK = false, bool XSEG = false, bool CEIL = false>
 __global__ __launch_bounds__(W_NT, 1) void scan_b16w_kernel(ScanB16WArgs a) {
-  static_assert(!CEIL || !SEG || XSEG, "per-row ceilings: the plain schedule, or under the cross-segment mask");
+  static_assert(!CEIL || !SEG || !SINK, "per-row ceilings on a table-driven schedule: no overflow lists");
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   char* stages = smem;                                                   // [2][W_STAGEB]
   float* cbs = reinterpret_cast<float*>(smem + 2 * W_STAGEB);            // [2][W_CT] bias of the tile being accumulated / the next
@@ -652,11 +660,21 @@ struct WideCeilArgs {
   const float *q_zn, *q_rn, *q_un; const uint32_t* maxima; const uint32_t* max_n;
   int64_t n, n_pad; int metric, d, dp; float lambda;
   float* ceil;                               // [n_pad]
+  // GATHER (the segmented passes): i is a position of the segment-padded query image, n the positions in use and
+  // gather [n] the row of X at each (-1: padding inside a segment's last block, ceiling +inf); floor_key and rx are read through it,
+  // the norms by position
+  const int32_t* gather;
 };
+template <bool GATHER>
 __global__ void wide_ceil_kernel(WideCeilArgs a) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n_pad) return;
   if (i >= a.n) { a.ceil[i] = __builtin_huge_valf(); return; }
+  int64_t row = i;
+  if constexpr (GATHER) {
+    row = a.gather[i];
+    if (row < 0) { a.ceil[i] = __builtin_huge_valf(); return; }
+  }
   // the operands' common power-of-two scale; max_n: float bits of the largest squared norm (unused for cosine)
   float s;
   {
@@ -668,11 +686,11 @@ __global__ void wide_ceil_kernel(WideCeilArgs a) {
     s = ldexpf(1.0f, e);
   }
   const float s2 = s * s;
-  const float fk = a.floor_key[i];
+  const float fk = a.floor_key[row];
   float q, mag;
   if (a.metric == MMF_DOT || a.metric == MMF_COSINE) { q = s2 * fk; mag = fabsf(q); }
   else {
-    const float t = (a.metric == MMF_RBF) ? fk / a.lambda : fk, ni = a.rx[i];
+    const float t = (a.metric == MMF_RBF) ? fk / a.lambda : fk, ni = a.rx[row];
     q = 0.5f * s2 * (t + ni); mag = 0.5f * s2 * (fabsf(t) + ni);
   }
   float margin;
@@ -706,6 +724,11 @@ int launch_b16w_t(const ScanB16WArgs& a, bool f16, int64_t grid, hipStream_t s) 
     static_assert(CAP == W_CAP_BIG && !SINK, "ceilings under the cross-segment mask: every pass is 20 deep");
     if (f16) return go(scan_b16w_kernel<true, CAP, true, false, true, true>);
     return go(scan_b16w_kernel<false, CAP, true, false, true, true>);
+  }
+  if constexpr (SEG && CEIL) {   // full-depth lists only: the later passes of the segmented any-k call
+    static_assert(CAP == W_CAP_BIG && !SINK, "ceilings on the table-driven schedule: every pass is 20 deep");
+    if (f16) return go(scan_b16w_kernel<true, CAP, true, false, false, true>);
+    return go(scan_b16w_kernel<false, CAP, true, false, false, true>);
   }
   if constexpr (CEIL) {
     if (f16) return go(scan_b16w_kernel<true, CAP, false, SINK, false, true>);
@@ -861,8 +884,24 @@ int launch_scan_b16w_ceil(const ScanB16Problem& p, int col_splits, const CandLis
 int launch_scan_b16w_ceilings(const ScanB16Problem& p, const float* floor_key, const float* rx, const uint32_t* max_n, float lambda, int64_t n_pad,
                               float* ceil, hipStream_t s) {
   if (n_pad < (p.n_rows + W_QT - 1) / W_QT * W_QT) { set_error("scan_b16w_ceilings: %lld ceilings do not cover the row blocks of %lld rows", (long long)n_pad, (long long)p.n_rows); return MMF_E_INTERNAL; }
-  WideCeilArgs a{floor_key, rx, p.q_zn, p.q_rn, p.q_un, p.maxima, max_n, p.n_rows, n_pad, p.metric, (int)p.d, p.dp, lambda, ceil};
-  wide_ceil_kernel<<<dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s>>>(a);
+  WideCeilArgs a{floor_key, rx, p.q_zn, p.q_rn, p.q_un, p.maxima, max_n, p.n_rows, n_pad, p.metric, (int)p.d, p.dp, lambda, ceil, nullptr};
+  wide_ceil_kernel<false><<<dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s>>>(a);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+// The same for a segment-padded query image (mmf_simtopk_segmented_wide_anyk): ceil [nq_pad] by operand position,
+// gather [n_pos] the row of X at each position (-1: padding); floor_key and rx stay indexed by row of X, the norms by position.  The
+// margin's maxima are those of the whole padded candidate image (p.maxima), as in the scan that follows.
+int launch_scan_b16w_ceilings_gather(const ScanB16Problem& p, const int32_t* gather, int64_t n_pos, const float* floor_key, const float* rx,
+                                     const uint32_t* max_n, float lambda, int64_t nq_pad, float* ceil, hipStream_t s) {
+  if (!gather) { set_error("scan_b16w_ceilings_gather: position table missing"); return MMF_E_INTERNAL; }
+  if (nq_pad <= 0) return MMF_OK;
+  if (n_pos < 0 || n_pos > nq_pad || n_pos % W_QT != 0) {
+    set_error("scan_b16w_ceilings_gather: %lld positions in an image of %lld are no whole row blocks", (long long)n_pos, (long long)nq_pad);
+    return MMF_E_INTERNAL;
+  }
+  WideCeilArgs a{floor_key, rx, p.q_zn, p.q_rn, p.q_un, p.maxima, max_n, n_pos, nq_pad, p.metric, (int)p.d, p.dp, lambda, ceil, gather};
+  wide_ceil_kernel<true><<<dim3((unsigned)((nq_pad + 255) / 256)), dim3(256), 0, s>>>(a);
   MMF_LAUNCH_CHECK();
   return MMF_OK;
 }
@@ -872,8 +911,23 @@ int launch_scan_b16w_ceilings(const ScanB16Problem& p, const float* floor_key, c
 // by the table's positions.  `lists` = 2 x the largest split count of a segment; a segment with fewer ranges leaves the rest of its
 // rows' lists empty (the caller zeroes the counts).  With more than one range per segment the lists carry keys and margins and
 // wide_seed_union_kernel settles every row's threshold, as in launch_scan_b16w.
+static int scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, int lists, const CandLists& L, const ScanB16Panel& pn,
+                         const float* ceil, hipStream_t s);
 int launch_scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, int lists, const CandLists& L, const ScanB16Panel& pn,
                          hipStream_t s) {
+  return scan_b16w_seg(p, sched, grid, lists, L, pn, nullptr, s);
+}
+// The same launch with a ceiling per OPERAND POSITION (mmf_simtopk_segmented_wide_anyk): ceil [nq_pad] by position of
+// the segment-padded query image, what launch_scan_b16w_ceilings_gather leaves.  Full-depth lists only (every pass of that call is 20 deep).
+int launch_scan_b16w_seg_ceil(const ScanB16Problem& p, const int32_t* sched, int64_t grid, int lists, const CandLists& L, const ScanB16Panel& pn,
+                              const float* ceil, hipStream_t s) {
+  if (!ceil) { set_error("scan_b16w_seg_ceil: ceilings missing"); return MMF_E_INTERNAL; }
+  if (L.cap != W_CAP_BIG) { set_error("scan_b16w_seg_ceil: list capacity %d, the ceilings run at the full depth (%d)", L.cap, W_CAP_BIG); return MMF_E_INTERNAL; }
+  return scan_b16w_seg(p, sched, grid, lists, L, pn, ceil, s);
+}
+// The launch itself.  ceil: nullptr, or the positions' ceilings (CEIL kernels).
+static int scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t grid, int lists, const CandLists& L, const ScanB16Panel& pn,
+                         const float* ceil, hipStream_t s) {
   if (grid <= 0 || p.n_rows <= 0) return MMF_OK;
   if (!scan_b16w_supported(p.d, p.kk) || p.dp != scan_b16w_dp(p.d)) {
     set_error("scan_b16w_seg: d = %lld (padded %d), k + self = %d outside 1024 < d <= 4096, k + self <= 20", (long long)p.d, p.dp, p.kk);
@@ -899,8 +953,9 @@ int launch_scan_b16w_seg(const ScanB16Problem& p, const int32_t* sched, int64_t 
   a.lists_total = L.lists; a.list_base = 0;
   a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride;
   a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.cand_keys = L.keys; a.margin_out = L.margin;
-  a.sched = sched;
-  MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, true>(a, p.f16, grid, s)) : (launch_b16w_t<W_CAP_BIG, true>(a, p.f16, grid, s)));
+  a.sched = sched; a.ceil = ceil;
+  if (ceil) MMF_TRY((launch_b16w_t<W_CAP_BIG, true, false, false, true>(a, p.f16, grid, s)));
+  else MMF_TRY(L.cap == W_CAP_SMALL ? (launch_b16w_t<W_CAP_SMALL, true>(a, p.f16, grid, s)) : (launch_b16w_t<W_CAP_BIG, true>(a, p.f16, grid, s)));
   if (col_splits > 1) {
     hipLaunchKernelGGL(wide_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
                        p.kk, pn.seed, p.n_rows, nullptr, nullptr);
