@@ -1715,6 +1715,16 @@ int mmf_simtopk_ex(const void* X, int64_t n, const void* Y, int64_t m, int64_t d
 // The depth of a pass of the 16-bit scan, self's slot included: the largest k + self scan_bf16_supported serves at d.
 static int anyk_depth(int64_t d) { return d <= 512 ? 44 : 20; }
 
+// What every *_anyk_plan reports behind its own checks.  one: a single pass at k + self serves the call; else pass 0 at the full
+// depth and later passes of at most depth - self entries each.  Returns 0 / 1 for one / several passes.
+static int anyk_plan(int64_t d, int k, int self1, bool one, int* scan_kk, int* first_yield, int* min_passes) {
+  const int depth = one ? k + self1 : anyk_depth(d), per = anyk_depth(d) - self1;
+  if (scan_kk) *scan_kk = depth;
+  if (first_yield) *first_yield = depth - self1;
+  if (min_passes) *min_passes = one ? 1 : 1 + (k - (depth - self1) + per - 1) / per;
+  return one ? 0 : 1;
+}
+
 int mmf_fast_anyk_plan(int64_t d, int k, int exclude_self, int* scan_kk, int* first_yield, int* min_passes) {
   if (d < 1 || k < 1) { set_error("fast_anyk_plan: need d >= 1 and k >= 1 (got d = %lld, k = %d)", (long long)d, k); return MMF_E_INVALID; }
   const int self1 = exclude_self ? 1 : 0, kk = k + self1;
@@ -1724,11 +1734,7 @@ int mmf_fast_anyk_plan(int64_t d, int k, int exclude_self, int* scan_kk, int* fi
               (long long)d, k);
     return MMF_E_UNSUPPORTED;
   }
-  const int depth = one ? kk : anyk_depth(d), per = anyk_depth(d) - self1;
-  if (scan_kk) *scan_kk = depth;
-  if (first_yield) *first_yield = depth - self1;
-  if (min_passes) *min_passes = one ? 1 : 1 + (k - (depth - self1) + per - 1) / per;
-  return one ? 0 : 1;
+  return anyk_plan(d, k, self1, one, scan_kk, first_yield, min_passes);
 }
 
 // MMF_ANYK_SHORT_DIV (read per call): a later pass may leave n / div unflagged rows short of its yield (they take the exact rescan).
@@ -1744,6 +1750,43 @@ static void anyk_record(mmf_fast_anyk_info* info, int pass, int yield, int ghost
   info->passes = pass + 1;
   if (pass >= MMF_FAST_ANYK_MAX_PASSES) return;
   info->yield[pass] = yield; info->ghost_max[pass] = ghost_max; info->exact_rows[pass] = exact_rows;
+}
+
+// The yield of a later pass: the largest t <= t_max that leaves at most `budget` unflagged rows short of it (0: none does).
+// h: launch_anyk_count's histogram, rows per certified count; *short_rows: the unflagged rows with fewer than t certified entries.
+static int anyk_yield(const uint32_t* h, int t_max, int64_t budget, int64_t* short_rows) {
+  int t = 0;
+  int64_t below = 0;
+  *short_rows = 0;
+  for (int tq = 1; tq <= t_max; ++tq) {
+    below += h[tq - 1];
+    if (below > budget) break;
+    t = tq; *short_rows = below;
+  }
+  return t;
+}
+
+// The re-rank of a later pass: K entries per row into the K-wide staging rows with their keys, flagged rows into `flags`.
+static SelectProblem anyk_stage_select(const Request& r, int K, int64_t* sidx, float* sval, float* skey, const float* rx, const float* cy,
+                                       const FlagBlock& flags, char* order_scratch) {
+  SelectProblem q = r.select();
+  q.k = K; q.out_idx = sidx; q.out_val = sval; q.key_out = skey; q.out_stride = K;
+  q.rx = rx; q.cy = cy;
+  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count;
+  q.two_pass = true;
+  q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
+  return q;
+}
+
+// What a table-driven 16-bit scan of the segmented and cross-segment runners needs reset before every launch: list counts (the slots
+// a block's entries do not use stay empty), overflow marks, overflow-list counts (the wide scan has no such lists: select reads them
+// as empty) and the thresholds' seeds.
+static int reset_b16_lists(const CandLists& L, int64_t n, int lists, int32_t* seed, int64_t n_seed, hipStream_t s) {
+  MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));
+  MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
+  MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
+  MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n_seed * 8, s));
+  return MMF_OK;
 }
 
 // The passes (r.precision MMF_PREC_FAST or _FAST_BF16, k + self beyond one pass; d <= 1024: mmf_simtopk_fast_anyk, above it the wide
@@ -1834,26 +1877,13 @@ static int fast_anyk_run(Request& r, const mmf_simtopk_opts* opts, mmf_fast_anyk
     if (wide) MMF_TRY(launch_scan_b16w_ceil(sp, ft.splits, Lw, pn, ceil, s, nullptr));
     else MMF_TRY(launch_scan_b16_ceil(sp, ft.splits, L, ft.scan_scratch, pn, ceil, s, nullptr));
     MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
-    SelectProblem q = r.select();
-    q.k = K; q.out_idx = sidx; q.out_val = sval; q.key_out = skey; q.out_stride = K;
-    q.rx = fp.rx; q.cy = fp.cy;
-    q.fail_rows = ft.flags.fail_rows; q.fail_count = ft.flags.fail_count;
-    q.two_pass = true;
-    q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : ft.order_scratch;
-    MMF_TRY(launch_select(q, L, s));
+    MMF_TRY(launch_select(anyk_stage_select(r, K, sidx, sval, skey, fp.rx, fp.cy, ft.flags, ft.order_scratch), L, s));
     MMF_TRY(launch_anyk_count(st, ft.flags.fail_rows, ft.flags.fail_count, fkey, fid, certified, hist, s));
     uint32_t h[64];
     MMF_HIP(hipMemcpyAsync(h, hist, (size_t)(K + 3) * 4, hipMemcpyDeviceToHost, s));
     MMF_HIP(hipStreamSynchronize(s));
-    // the largest yield that leaves at most `budget` unflagged rows short of it
-    const int t_max = std::min(K, k - done);
-    int t = 0;
-    int64_t below = 0, short_rows = 0;   // unflagged rows with fewer than t' certified entries
-    for (int tq = 1; tq <= t_max; ++tq) {
-      below += h[tq - 1];
-      if (below > budget) break;
-      t = tq; short_rows = below;
-    }
+    int64_t short_rows = 0;
+    const int t = anyk_yield(h, std::min(K, k - done), budget, &short_rows);
     if (t < 1) return finish_exact(pass);
     MMF_TRY(launch_anyk_emit(st, certified, t, done, k, r.out_idx, r.out_val, fkey, fid, rescan_rows, rescan_count, s));
     const int64_t rescan = (int64_t)h[K + 1] + short_rows;
@@ -1907,13 +1937,8 @@ int mmf_wide_anyk_plan(int64_t d, int k, int exclude_self, int* scan_kk, int* fi
   if (d < 1 || k < 1) { set_error("wide_anyk_plan: need d >= 1 and k >= 1 (got d = %lld, k = %d)", (long long)d, k); return MMF_E_INVALID; }
   if (d <= 1024) { set_error("wide_anyk_plan: d = %lld is served by mmf_fast_anyk_plan (this one: 1024 < d <= 4096)", (long long)d); return MMF_E_UNSUPPORTED; }
   if (d > 4096) { set_error("wide_anyk_plan: d = %lld is beyond the wide 16-bit scan (1024 < d <= 4096)", (long long)d); return MMF_E_UNSUPPORTED; }
-  const int self1 = exclude_self ? 1 : 0, kk = k + self1;
-  const bool one = scan_b16w_supported(d, kk) != 0;
-  const int depth = one ? kk : anyk_depth(d), per = anyk_depth(d) - self1;
-  if (scan_kk) *scan_kk = depth;
-  if (first_yield) *first_yield = depth - self1;
-  if (min_passes) *min_passes = one ? 1 : 1 + (k - (depth - self1) + per - 1) / per;
-  return one ? 0 : 1;
+  const int self1 = exclude_self ? 1 : 0;
+  return anyk_plan(d, k, self1, scan_b16w_supported(d, k + self1) != 0, scan_kk, first_yield, min_passes);
 }
 
 int mmf_simtopk_wide_anyk(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric, float lambda,
@@ -3365,18 +3390,21 @@ static int cross_flagged(const Request& r, const float* rx, const float* cy, con
   return MMF_OK;
 }
 
-// r: checked, begun, n > 0, precision MMF_PREC_FAST or _FAST_BF16, (d, k) served by the 16-bit scan.
-static int run_cross_segments_fast(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts) {
-  const char* who = r.call.who;
+// r: checked, begun, n > 0, precision MMF_PREC_FAST or _FAST_BF16, (d, k) served by the 16-bit scan — the wide one under `wide`
+// (1024 < d <= 4096): the images at its padded dim, cross_segw_table, its list capacity, no id scratch, no shared
+// thresholds, launch_scan_b16w_xseg; the overflow lists stay zeroed and unused there (select reads them as empty).
+static int run_cross_segments16(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts,
+                                bool wide) {
   const hipStream_t s = r.call.s;
   const int64_t n = r.n, m = r.m;
-  const int k = r.k;
   const bool profile = r.profile, f16 = (r.precision == MMF_PREC_FAST);
-  const int dp = scan_bf16_dp(r.d), qt = scan_b16_queries_per_block(dp), bcap = scan_bf16_cap(r.kk, dp);
+  const int dp = wide ? scan_b16w_dp(r.d) : scan_bf16_dp(r.d), bcap = wide ? scan_b16w_cap(r.kk) : scan_bf16_cap(r.kk, dp);
+  const int forced = opts ? opts->col_splits : 0;
   int lists = 2;
-  const std::vector<int32_t> sched = cross_seg16_table(xp, yp, S, qt, dp, bcap, kCross16Budget, opts ? opts->col_splits : 0, &lists);
-  if (lists < 0) {
-    set_error("%s: a column run of the %lld rows of Y exceeds 4 GiB of 16-bit operands at padded dim %d", who, (long long)m, dp);
+  const std::vector<int32_t> sched = wide ? cross_segw_table(xp, yp, S, bcap, kCross16Budget, forced, &lists)
+                                          : cross_seg16_table(xp, yp, S, scan_b16_queries_per_block(dp), dp, bcap, kCross16Budget, forced, &lists);
+  if (!wide && lists < 0) {
+    set_error("%s: a column run of the %lld rows of Y exceeds 4 GiB of 16-bit operands at padded dim %d", r.call.who, (long long)m, dp);
     return MMF_E_UNSUPPORTED;
   }
   const int64_t grid = (int64_t)sched.size() / 8;
@@ -3386,7 +3414,7 @@ static int run_cross_segments_fast(Request& r, bool self, const int64_t* xp, con
   for (int64_t g = 0; g < S; ++g)
     for (int64_t i = xp[g]; i < xp[g + 1]; ++i) { bounds[2 * i] = (uint32_t)yp[g]; bounds[2 * i + 1] = (uint32_t)(yp[g + 1] - yp[g]); }
 
-  const size_t scratch_bytes = scan_b16_seg_scratch_bytes(grid, dp, bcap);
+  const size_t scratch_bytes = wide ? 0 : scan_b16_seg_scratch_bytes(grid, dp, bcap);   // 0 bytes: nothing is carved
   const size_t need = ws_bytes(n, 4) + (self ? 0 : ws_bytes(m, 4)) + FlagBlock::bytes(n) + ws_bytes(4, 4) + HalfImage::bytes(n_pad, dp) +
                       (self ? 0 : HalfImage::bytes(m_pad, dp)) + ws_bytes(sched.size(), 4) + ws_bytes(bounds.size(), 4) +
                       b16_lists_bytes(n, lists, bcap) + ws_bytes(scratch_bytes, 1) + ws_bytes(2 * (size_t)n, 4) +
@@ -3422,15 +3450,13 @@ static int run_cross_segments_fast(Request& r, bool self, const int64_t* xp, con
   if (!self) MMF_TRY(launch_prep_half({r.X, n, r.d, r.dtype, r.metric, rx, max_n}, Q, dp, f16, s));
   MMF_TRY(t_prep.stop(s));
 
-  MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));   // the slots a block's entries do not use stay empty
-  MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
-  MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
-  MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n * 8, s));
+  MMF_TRY(reset_b16_lists(L, n, lists, seed, n, s));
   ScanB16Panel pn;
-  pn.seed = seed; pn.seed_stride = n; pn.share = lists > 2 ? 1 : 0;
+  pn.seed = seed; pn.seed_stride = n; pn.share = (!wide && lists > 2) ? 1 : 0;
   MMF_TRY(t_scan.start(profile, s));
   const ScanB16Problem sp(Q, C, n, m, m_pad, dp, r.d, f16, r.metric, r.kk);
-  MMF_TRY(launch_scan_b16_xseg(sp, d_sched, grid, d_bounds, L, scan_scratch, pn, s));
+  if (wide) MMF_TRY(launch_scan_b16w_xseg(sp, d_sched, grid, d_bounds, lists, L, pn, s));
+  else MMF_TRY(launch_scan_b16_xseg(sp, d_sched, grid, d_bounds, L, scan_scratch, pn, s));
   MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
   MMF_TRY(t_scan.stop(s));
 
@@ -3510,7 +3536,7 @@ int mmf_simtopk_cross_segments_fast(const void* X, int64_t n, const void* Y, int
   if (stats) stats->near_rows = -1;
   if (n == 0) return MMF_OK;
   if (r.precision == MMF_PREC_EXACT) return run_segmented_exact(r, self, x_ptr_host, y_ptr_host, n_segments, opts, nullptr, 0, 0.0f, true);
-  return run_cross_segments_fast(r, self, x_ptr_host, y_ptr_host, n_segments, opts);
+  return run_cross_segments16(r, self, x_ptr_host, y_ptr_host, n_segments, opts, false);
 }
 
 int64_t mmf_cross_segments_fast_table(const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_segments, int64_t d, int k,
@@ -3544,104 +3570,10 @@ int64_t mmf_cross_segments_fast_table(const int64_t* x_ptr_host, const int64_t* 
 }
 
 // ---- cross-segment top-k on the wide 16-bit scan (include/ext/mmf_hg_cross_segw.h) -------------------------------
-// run_cross_segments_fast for 1024 < d <= 4096: the plain 16-bit images at the wide scan's padded dim, ONE table-driven launch of the
-// wide scan whose epilogue masks, per query row, the columns of the row's own segment (launch_scan_b16w_xseg; its threshold union
-// when a block has several entries), the audit, one re-rank over all rows, one host synchronisation.  Flagged rows: cross_flagged.
-}  // extern "C"
-
-namespace mmf {
-
-// r: checked, begun, n > 0, precision MMF_PREC_FAST or _FAST_BF16, (d, k) served by the wide scan.
-static int run_cross_segments_wide(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts) {
-  const hipStream_t s = r.call.s;
-  const int64_t n = r.n, m = r.m;
-  const bool profile = r.profile, f16 = (r.precision == MMF_PREC_FAST);
-  const int dp = scan_b16w_dp(r.d), bcap = scan_b16w_cap(r.kk);
-  int lists = 2;
-  const std::vector<int32_t> sched = cross_segw_table(xp, yp, S, bcap, kCross16Budget, opts ? opts->col_splits : 0, &lists);
-  const int64_t grid = (int64_t)sched.size() / 8;
-  const int64_t n_pad = (n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256;
-  // per row of X: first row and row count of the columns it may not take; padding rows exclude nothing
-  std::vector<uint32_t> bounds((size_t)n_pad * 2, 0u);
-  for (int64_t g = 0; g < S; ++g)
-    for (int64_t i = xp[g]; i < xp[g + 1]; ++i) { bounds[2 * i] = (uint32_t)yp[g]; bounds[2 * i + 1] = (uint32_t)(yp[g + 1] - yp[g]); }
-
-  // the wide kernel's sizes: its list capacity, no id scratch; the overflow lists stay zeroed and unused (select reads them as empty)
-  const size_t need = ws_bytes(n, 4) + (self ? 0 : ws_bytes(m, 4)) + FlagBlock::bytes(n) + ws_bytes(4, 4) + HalfImage::bytes(n_pad, dp) +
-                      (self ? 0 : HalfImage::bytes(m_pad, dp)) + ws_bytes(sched.size(), 4) + ws_bytes(bounds.size(), 4) +
-                      b16_lists_bytes(n, lists, bcap) + ws_bytes(2 * (size_t)n, 4) + ws_bytes(select_order_bytes(n), 1);
-  Workspace ws;
-  MMF_TRY(r.call.workspace(need, &ws));
-  float* rx = ws.take<float>(n);
-  float* cy = self ? rx : ws.take<float>(m);
-  FlagBlock flags;
-  flags.carve(ws, n);
-  MMF_TRY(flags.zero(s));
-  uint32_t* max_n = ws.take<uint32_t>(4);
-  HalfImage Q, C;
-  Q.carve(ws, n_pad, dp);
-  if (self) C = Q; else C.carve(ws, m_pad, dp);
-  int32_t* d_sched = ws.take<int32_t>(sched.size());
-  uint32_t* d_bounds = ws.take<uint32_t>(bounds.size());
-  const CandLists L = carve_b16_lists(ws, n, lists, bcap);
-  int32_t* seed = ws.take<int32_t>(2 * (size_t)n);
-  char* order_scratch = ws.take<char>(select_order_bytes(n));
-
-  EventTimer t_prep, t_scan, t_sel, t_fb;
-  MMF_TRY(t_prep.start(profile, s));
-  MMF_HIP(hipMemsetAsync(max_n, 0, 16, s));
-  MMF_TRY(launch_row_scalars(r.X, n, r.d, r.dtype, r.metric, rx, max_n, s));
-  if (!self) MMF_TRY(launch_row_scalars(r.Y, m, r.d, r.dtype, r.metric, cy, max_n, s));
-  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
-  MMF_TRY(upload_table(s, d_bounds, bounds.data(), bounds.size() * 4));
-  MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
-  if (!self) MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
-  MMF_TRY(launch_prep_half({r.Y, m, r.d, r.dtype, r.metric, cy, max_n}, C, dp, f16, s));
-  if (!self) MMF_TRY(launch_prep_half({r.X, n, r.d, r.dtype, r.metric, rx, max_n}, Q, dp, f16, s));
-  MMF_TRY(t_prep.stop(s));
-
-  MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));   // the slots a block's entries do not use stay empty
-  MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
-  MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
-  MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n * 8, s));
-  ScanB16Panel pn;
-  pn.seed = seed; pn.seed_stride = n; pn.share = 0;
-  MMF_TRY(t_scan.start(profile, s));
-  const ScanB16Problem sp(Q, C, n, m, m_pad, dp, r.d, f16, r.metric, r.kk);
-  MMF_TRY(launch_scan_b16w_xseg(sp, d_sched, grid, d_bounds, lists, L, pn, s));
-  MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
-  MMF_TRY(t_scan.stop(s));
-
-  SelectProblem q = r.select();
-  q.rx = rx; q.cy = cy;
-  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = r.stats ? flags.cand_total : nullptr;
-  q.two_pass = true;
-  q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
-  MMF_TRY(t_sel.start(profile, s));
-  MMF_TRY(launch_select(q, L, s));
-  MMF_TRY(t_sel.stop(s));
-  MMF_TRY(flags.read(r.stats != nullptr, s));   // the call's one synchronisation when no row is flagged
-  const uint32_t* h_fail4 = flags.h_fail4;
-  const int64_t fallback_rows = h_fail4[0];
-  MMF_TRY(t_fb.start(profile && fallback_rows > 0, s));
-  if (fallback_rows > 0) {
-    std::vector<int32_t> rows((size_t)fallback_rows);
-    MMF_HIP(hipMemcpyAsync(rows.data(), flags.fail_rows, (size_t)fallback_rows * 4, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipStreamSynchronize(s));               // only on this branch: the fail list, now that its length is known
-    std::sort(rows.begin(), rows.end());
-    MMF_TRY(cross_flagged(r, rx, cy, rows, xp, yp, S));
-  }
-  MMF_TRY(t_fb.stop(s));
-  const int64_t overflow_rows = h_fail4[1] < (uint32_t)fallback_rows ? h_fail4[1] : fallback_rows;
-  fill_stats(r.stats, r.precision, lists / 2, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback_rows, overflow_rows,
-             fallback_rows - overflow_rows, flags.h_tot);
-  return MMF_OK;
-}
-
-}  // namespace mmf
-
-extern "C" {
-
+// run_cross_segments16 under `wide`, 1024 < d <= 4096: the plain 16-bit images at the wide scan's padded dim, ONE table-driven
+// launch of the wide scan whose epilogue masks, per query row, the columns of the row's own segment (launch_scan_b16w_xseg; its
+// threshold union when a block has several entries), the audit, one re-rank over all rows, one host synchronisation.  Flagged
+// rows: cross_flagged.
 int mmf_simtopk_cross_segments_wide(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric, float lambda,
                                     int k, const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_segments, int64_t* out_idx,
                                     float* out_val, const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id,
@@ -3690,7 +3622,7 @@ int mmf_simtopk_cross_segments_wide(const void* X, int64_t n, const void* Y, int
   if (stats) stats->near_rows = -1;
   if (n == 0) return MMF_OK;
   if (r.precision == MMF_PREC_EXACT) return run_segmented_exact(r, self, x_ptr_host, y_ptr_host, n_segments, opts, nullptr, 0, 0.0f, true);
-  return run_cross_segments_wide(r, self, x_ptr_host, y_ptr_host, n_segments, opts);
+  return run_cross_segments16(r, self, x_ptr_host, y_ptr_host, n_segments, opts, true);
 }
 
 int64_t mmf_cross_segments_wide_table(const int64_t* x_ptr_host, const int64_t* y_ptr_host, int64_t n_segments, int64_t d, int k,
@@ -3868,8 +3800,11 @@ int64_t mmf_segmented_exact_table(const int64_t* x_ptr_host, const int64_t* y_pt
 }  // extern "C"
 
 // ---- mmf_simtopk_segmented_fast_anyk (include/ext/mmf_hg_seg_anyk.h) ------------------------------------------
-// The passes of fast_anyk_run over the images and the work table of the segmented body (mmf::mmf_simtopk_segmented), narrow scan
-// only (d <= 1024).  r: checked, begun, n > 0, r.precision MMF_PREC_FAST or _FAST_BF16, k + self beyond one pass.  A segment is
+// The passes of fast_anyk_run over the images and the work table of the segmented body (mmf::mmf_simtopk_segmented); d <= 1024 the
+// narrow scan, above it (mmf_simtopk_segmented_wide_anyk) `wide`: the wide scan's padded dim, 128-row tiles and
+// 32-entry lists, a forced opts->col_splits under the body's bounds (automatic: one range per segment) with one table entry and one
+// list pair per range, no id scratch, its launches in the narrow ones' slots and no overflow lists (a crowded row is flagged).
+// r: checked, begun, n > 0, r.precision MMF_PREC_FAST or _FAST_BF16, k + self beyond one pass.  A segment is
 // SERVED when it has rows and at least k admissible columns; the others go through the exact launch loop in pass 0, as in the body.
 // Pass 0: the body's launches at the full depth, K entries into the k-wide output rows, every served row's floor left behind (the
 // flagged ones by the exact pass, gathered per segment).  A later pass: ceilings by operand position, the same device work table
@@ -3880,43 +3815,72 @@ int64_t mmf_segmented_exact_table(const int64_t* x_ptr_host, const int64_t* y_pt
 // flags its rows and they take the rescan.
 namespace mmf {
 
-static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, mmf_fast_anyk_info* info) {
+static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts,
+                              mmf_fast_anyk_info* info) {
   const char* who = r.call.who;
   const hipStream_t s = r.call.s;
   const int64_t n = r.n, m = r.m, d = r.d;
   const int k = r.k, self1 = r.exclude_self ? 1 : 0, depth = anyk_depth(d), K = depth - self1;
   const bool f16 = r.precision == MMF_PREC_FAST, profile = r.profile;
+  const bool wide = d > 1024;   // the wide scan's sizes and launches, column ranges per segment, no id scratch
   mmf_simtopk_stats* stats = r.stats;
-  const int dp = scan_bf16_dp(d), qt = scan_b16_queries_per_block(dp), kTile = 32, bcap = scan_bf16_cap(depth, dp);
+  const int dp = wide ? scan_b16w_dp(d) : scan_bf16_dp(d), qt = wide ? scan_b16w_queries_per_block() : scan_b16_queries_per_block(dp);
+  const int kTile = wide ? scan_b16w_col_tile() : 32, bcap = wide ? scan_b16w_cap(depth) : scan_bf16_cap(depth, dp);
 
-  // ---- the body's tables: work table, position -> row gathers; and per row the first row of Y of its segment --------------------
+  // ---- the body's tables: column ranges, work table, position -> row gathers; and per row the first row of Y of its segment -------
   std::vector<int64_t> adm(S);
   std::vector<char> on_fast(S, 0);
-  std::vector<int32_t> sched, col0(n, 0), served_rows;
-  int64_t nq_pos = 0, mc_pos = 0, unserved_rows = 0;
+  int64_t unserved_rows = 0, n_served = 0;
   for (int64_t g = 0; g < S; ++g) {
     const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g];
     adm[g] = admissible_columns(xp[g], ng, yp[g], mg, r.exclude_self);
     if (ng == 0) continue;
     if (adm[g] < k) { unserved_rows += ng; continue; }
-    const int64_t tiles = (mg + kTile - 1) / kTile;
-    if (tiles * kTile * (int64_t)dp * 2 >= (int64_t(1) << 32)) {
+    if (!wide && (mg + kTile - 1) / kTile * kTile * (int64_t)dp * 2 >= (int64_t(1) << 32)) {   // the narrow tile DMA's 32-bit offsets
       set_error("%s: segment %lld has %lld candidate rows, over 4 GiB of 16-bit operands", who, (long long)g, (long long)mg);
       return MMF_E_UNSUPPORTED;
     }
     on_fast[g] = 1;
+    n_served += ng;
+  }
+  // wide, the body's rule: a forced count is taken while select's capacity per row holds 2 x splits lists; each
+  // segment caps its count at its own tile count, rounded down to a power of two.  Narrow: one range per segment.
+  int call_splits = 1, max_splits = 1;
+  if (wide) {
+    int64_t R = 0;
+    for (int64_t g = 0; g < S; ++g)
+      if (on_fast[g]) R += (xp[g + 1] - xp[g] + qt - 1) / qt;
+    const int forced = opts ? opts->col_splits : 0;
+    const auto fits = [&](int sp) { return 2 * sp * bcap <= 1024 - kSpillCap; };
+    if (forced > 0) { while (call_splits < forced && fits(2 * call_splits)) call_splits <<= 1; }
+    else if (wide_seg_auto_splits()) { while (R > 0 && R * call_splits < 256 && fits(2 * call_splits)) call_splits <<= 1; }
+  }
+  std::vector<int32_t> sched, col0(n, 0), served_rows;
+  served_rows.reserve((size_t)n_served);
+  int64_t nq_pos = 0, mc_pos = 0;
+  for (int64_t g = 0; g < S; ++g) {
+    if (!on_fast[g]) continue;
+    const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g];
+    const int64_t tiles = (mg + kTile - 1) / kTile;
     const int64_t t0 = mc_pos / kTile;
+    int sp = 1;                                   // column ranges of this segment: one table entry and one list pair each
+    while (2 * sp <= call_splits && 2 * sp <= tiles) sp <<= 1;
+    if (sp > max_splits) max_splits = sp;
+    const int64_t tps = (tiles + sp - 1) / sp;
     for (int64_t b = 0; b < ng; b += qt) {
-      const int32_t e[8] = {(int32_t)(nq_pos + b), (int32_t)(xp[g] + b), (int32_t)(ng - b < qt ? ng - b : qt), (int32_t)t0,
-                            (int32_t)(t0 + tiles), (int32_t)(uint32_t)(yp[g] - t0 * kTile), 0, 0};
-      sched.insert(sched.end(), e, e + 8);
+      for (int c = 0; c < sp; ++c) {
+        const int64_t tb = std::min(t0 + c * tps, t0 + tiles), te = std::min(tb + tps, t0 + tiles);
+        const int32_t e[8] = {(int32_t)(nq_pos + b), (int32_t)(xp[g] + b), (int32_t)(ng - b < qt ? ng - b : qt), (int32_t)tb,
+                              (int32_t)te, (int32_t)(uint32_t)(yp[g] - t0 * kTile), 2 * c, 0};
+        sched.insert(sched.end(), e, e + 8);
+      }
     }
     for (int64_t i = 0; i < ng; ++i) { col0[xp[g] + i] = (int32_t)yp[g]; served_rows.push_back((int32_t)(xp[g] + i)); }
     nq_pos += (ng + qt - 1) / qt * qt;
     mc_pos += tiles * kTile;
+    if (nq_pos >= (int64_t(1) << 31) || mc_pos >= (int64_t(1) << 31)) { set_error("%s: padded images too large", who); return MMF_E_UNSUPPORTED; }
   }
-  if (nq_pos >= (int64_t(1) << 31) || mc_pos >= (int64_t(1) << 31)) { set_error("%s: padded images too large", who); return MMF_E_UNSUPPORTED; }
-  const int64_t grid = (int64_t)sched.size() / 8, n_served = (int64_t)served_rows.size();
+  const int64_t grid = (int64_t)sched.size() / 8;
   std::vector<int32_t> qgather(nq_pos, -1), cgather(mc_pos, -1);
   {
     int64_t qpos = 0, cpos = 0;
@@ -3932,8 +3896,8 @@ static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const in
 
   // ---- workspace (slot 0): the body's, then floors, bookkeeping, ceilings and the staging rows -----------------------------------
   const int64_t nq_pad = (nq_pos + 255) / 256 * 256, mc_pad = (mc_pos + 255) / 256 * 256;
-  const int lists = 2;
-  const size_t scratch_bytes = scan_b16_seg_scratch_bytes(grid, dp, bcap);
+  const int lists = 2 * max_splits;   // (narrow: 2)
+  const size_t scratch_bytes = wide ? 0 : scan_b16_seg_scratch_bytes(grid, dp, bcap);   // 0 bytes: nothing is carved
   const int64_t n_seed = n;
   const size_t stage = (size_t)n * K;
   size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + FlagBlock::bytes(n);
@@ -3941,7 +3905,7 @@ static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const in
     need += HalfImage::bytes(nq_pad, dp) + HalfImage::bytes(mc_pad, dp) + ws_bytes(4, 4) + ws_bytes(sched.size(), 4) +
             ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + b16_lists_bytes(n, lists, bcap) +
             ws_bytes(scratch_bytes, 1) + ws_bytes(2 * (size_t)n_seed, 4) + ws_bytes(select_order_bytes(n), 1) +
-            5 * ws_bytes(n, 4) + ws_bytes(nq_pad, 4) + ws_bytes(64, 4) + ws_bytes(stage, 8) + 2 * ws_bytes(stage, 4);
+            5 * ws_bytes(n, 4) + ws_bytes(nq_pad, 4) + ws_bytes(64, 4) + ws_bytes(4, 4) + ws_bytes(stage, 8) + 2 * ws_bytes(stage, 4);
   Workspace ws;
   MMF_TRY(r.call.workspace(need, &ws));
   float* rx = ws.take<float>(n);
@@ -3958,7 +3922,7 @@ static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const in
   if (!self && m > 0) MMF_TRY(launch_row_scalars(r.Y, m, d, r.dtype, r.metric, cy, max_n, s));
 
   // kq entries per row from column out_off0 on for `rows` (served rows, ascending: grouped by segment) by the exact pass, one
-  // gathered group per segment; `whole`: also the unserved segments, for what they have (pass 0 only).  Synchronises.
+  // gathered group per segment; `whole`: also the unserved segments, for what they have (pass 0 only).  Does not synchronise.
   int32_t* d_rows = nullptr; int32_t* d_col0 = nullptr;
   float* fkey = nullptr; uint32_t* fid = nullptr;
   auto exact_rows = [&](const std::vector<int32_t>& rows, int kq, int out_off0, bool floors_in, bool floors_out, bool whole) -> int {
@@ -3980,7 +3944,7 @@ static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const in
       }
     }
     if (ex.pieces.empty()) return MMF_OK;
-    if (getenv("MMF_SEG_ANYK_DEBUG"))   // diagnosis: what the exact pass is asked for (two launches per piece and internal pass of 44)
+    if (!wide && getenv("MMF_SEG_ANYK_DEBUG"))   // diagnosis: what the exact pass is asked for (two launches per piece and internal pass of 44)
       fprintf(stderr, "[mmf segmented anyk] exact pass behind column %d: %lld gathered rows, %zu pieces, %d entries each\n", out_off0,
               (long long)cnt, ex.pieces.size(), kq);
     ex.n_ids = cnt; ex.row_ids = d_rows;
@@ -4021,12 +3985,12 @@ static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const in
   int32_t* certified = ws.take<int32_t>(n); int32_t* rescan_rows = ws.take<int32_t>(n);
   d_col0 = ws.take<int32_t>(n); d_rows = rescan_rows;   // (a pass's rescan list is read to the host before the sorted rows take its place)
   float* ceil = ws.take<float>(nq_pad);
-  uint32_t* hist = ws.take<uint32_t>(60); uint32_t* rescan_count = hist + 60;
+  uint32_t* hist = ws.take<uint32_t>(64); uint32_t* rescan_count = ws.take<uint32_t>(4);
   int64_t* sidx = ws.take<int64_t>(stage); float* sval = ws.take<float>(stage); float* skey = ws.take<float>(stage);
-  MMF_HIP(hipMemcpyAsync(d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice, s));
-  MMF_HIP(hipMemcpyAsync(d_qg, qgather.data(), (size_t)nq_pos * 4, hipMemcpyHostToDevice, s));
-  MMF_HIP(hipMemcpyAsync(d_cg, cgather.data(), (size_t)mc_pos * 4, hipMemcpyHostToDevice, s));
-  MMF_HIP(hipMemcpyAsync(d_col0, col0.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
+  MMF_TRY(upload_table(s, d_qg, qgather.data(), (size_t)nq_pos * 4));
+  MMF_TRY(upload_table(s, d_cg, cgather.data(), (size_t)mc_pos * 4));
+  MMF_TRY(upload_table(s, d_col0, col0.data(), (size_t)n * 4));
   MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
   MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
   MMF_TRY(launch_prep_half_gather({r.Y, m, d, r.dtype, r.metric, cy, max_n}, d_cg, mc_pos, C, dp, f16, s));
@@ -4036,14 +4000,6 @@ static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const in
   ScanB16Panel pn;
   pn.seed = seed; pn.seed_stride = n_seed; pn.share = 0;
   const ScanB16Problem sp(Q, C, n, m, mc_pad, dp, d, f16, r.metric, depth);
-  // what the body resets before its scan (rows of unserved segments keep empty lists: the re-rank reports them every pass)
-  auto reset_lists = [&]() -> int {
-    MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));
-    MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
-    MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
-    MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n_seed * 8, s));
-    return MMF_OK;
-  };
   // the served rows among `cnt` device rows, ascending (one more synchronisation)
   auto served_of = [&](const int32_t* dev_rows, int64_t cnt, std::vector<int32_t>* out) -> int {
     std::vector<int32_t> h((size_t)cnt);
@@ -4061,9 +4017,11 @@ static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const in
   };
 
   // ---- pass 0: K entries per row, k-wide rows, floors left ----------------------------------------------------------------------
-  MMF_TRY(reset_lists());
+  // (every scan starts from the body's reset; rows of unserved segments keep empty lists: the re-rank reports them every pass)
+  MMF_TRY(reset_b16_lists(L, n, lists, seed, n_seed, s));
   MMF_TRY(t_scan.start(profile, s));
-  MMF_TRY(launch_scan_b16_seg(sp, d_sched, grid, L, scan_scratch, pn, s));
+  if (wide) MMF_TRY(launch_scan_b16w_seg(sp, d_sched, grid, lists, L, pn, s));
+  else MMF_TRY(launch_scan_b16_seg(sp, d_sched, grid, L, scan_scratch, pn, s));
   MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
   MMF_TRY(t_scan.stop(s));
   SelectProblem q = r.select();
@@ -4083,10 +4041,10 @@ static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const in
   MMF_TRY(t_fb.start(profile && (fallback0 > 0 || unserved_rows > 0), s));
   MMF_TRY(exact_rows(ex_rows, K, 0, false, true, true));
   MMF_TRY(t_fb.stop(s));
-  MMF_HIP(hipStreamSynchronize(s));
+  if (!wide) MMF_HIP(hipStreamSynchronize(s));   // (the narrow entry has always waited for pass 0's exact rows here)
   {
     const int64_t overflow_rows = flags.h_fail4[1] < (uint32_t)fallback0 ? flags.h_fail4[1] : fallback0;
-    fill_stats(stats, r.precision, 1, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback0, overflow_rows,
+    fill_stats(stats, r.precision, max_splits, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback0, overflow_rows,
                fallback0 - overflow_rows, flags.h_tot);
   }
   anyk_record(info, 0, K, 0, fallback0);
@@ -4103,31 +4061,20 @@ static int segmented_anyk_run(Request& r, bool self, const int64_t* xp, const in
   };
   for (int pass = 1; done < k; ++pass) {
     if (pass >= MMF_FAST_ANYK_MAX_PASSES - 1) return finish_exact(pass);
-    MMF_TRY(launch_scan_b16_ceilings_gather(sp, L.cap, d_qg, nq_pos, fkey, rx, max_n, r.lambda, nq_pad, ceil, s));
-    MMF_TRY(reset_lists());
+    if (wide) MMF_TRY(launch_scan_b16w_ceilings_gather(sp, d_qg, nq_pos, fkey, rx, max_n, r.lambda, nq_pad, ceil, s));
+    else MMF_TRY(launch_scan_b16_ceilings_gather(sp, L.cap, d_qg, nq_pos, fkey, rx, max_n, r.lambda, nq_pad, ceil, s));
+    MMF_TRY(reset_b16_lists(L, n, lists, seed, n_seed, s));
     MMF_TRY(flags.zero(s));
-    MMF_TRY(launch_scan_b16_seg_ceil(sp, d_sched, grid, L, scan_scratch, pn, ceil, s));
+    if (wide) MMF_TRY(launch_scan_b16w_seg_ceil(sp, d_sched, grid, lists, L, pn, ceil, s));
+    else MMF_TRY(launch_scan_b16_seg_ceil(sp, d_sched, grid, L, scan_scratch, pn, ceil, s));
     MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
-    SelectProblem ql = r.select();
-    ql.k = K; ql.out_idx = sidx; ql.out_val = sval; ql.key_out = skey; ql.out_stride = K;
-    ql.rx = rx; ql.cy = cy;
-    ql.fail_rows = flags.fail_rows; ql.fail_count = flags.fail_count;
-    ql.two_pass = true;
-    ql.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
-    MMF_TRY(launch_select(ql, L, s));
+    MMF_TRY(launch_select(anyk_stage_select(r, K, sidx, sval, skey, rx, cy, flags, order_scratch), L, s));
     MMF_TRY(launch_anyk_count(st, flags.fail_rows, flags.fail_count, fkey, fid, certified, hist, s));
     uint32_t h[64];
     MMF_HIP(hipMemcpyAsync(h, hist, (size_t)(K + 3) * 4, hipMemcpyDeviceToHost, s));
     MMF_HIP(hipStreamSynchronize(s));
-    // the largest yield that leaves at most `budget` unflagged rows short of it (unserved rows are always flagged)
-    const int t_max = std::min(K, k - done);
-    int t = 0;
-    int64_t below = 0, short_rows = 0;
-    for (int tq = 1; tq <= t_max; ++tq) {
-      below += h[tq - 1];
-      if (below > budget) break;
-      t = tq; short_rows = below;
-    }
+    int64_t short_rows = 0;   // (unserved rows are always flagged, never short)
+    const int t = anyk_yield(h, std::min(K, k - done), budget, &short_rows);
     if (t < 1) return finish_exact(pass);
     MMF_TRY(launch_anyk_emit(st, certified, t, done, k, r.out_idx, r.out_val, fkey, fid, rescan_rows, rescan_count, s));
     const int64_t listed = (int64_t)h[K + 1] + short_rows;   // the emit kernel's list: flagged rows (the unserved ones among them) and short rows
@@ -4157,10 +4104,7 @@ int mmf_segmented_anyk_plan(int64_t d, int k, int exclude_self, int* scan_kk, in
               (long long)d, k);
     return MMF_E_UNSUPPORTED;
   }
-  if (scan_kk) *scan_kk = kk;
-  if (first_yield) *first_yield = k;
-  if (min_passes) *min_passes = 1;
-  return 0;
+  return anyk_plan(d, k, self1, true, scan_kk, first_yield, min_passes);
 }
 
 int mmf_simtopk_segmented_fast_anyk(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
@@ -4214,21 +4158,24 @@ int mmf_simtopk_segmented_fast_anyk(const void* X, int64_t n, const void* Y, int
     return MMF_OK;
   }
   r.precision = prec;
-  return segmented_anyk_run(r, self, x_ptr_host, y_ptr_host, n_segments, info);
+  return segmented_anyk_run(r, self, x_ptr_host, y_ptr_host, n_segments, opts, info);
 }
 
 }  // extern "C"
 
 // ---- mmf_simtopk_cross_segments_fast_anyk (include/ext/mmf_hg_cross_seg_anyk.h) --------------------------------
-// The passes of fast_anyk_run over the images, the work table and the per-row mask of run_cross_segments_fast, narrow scan only
-// (d <= 1024).  r: checked, begun, n > 0, r.precision MMF_PREC_FAST or _FAST_BF16, k beyond one pass; the entry has refused every
+// The passes of fast_anyk_run over the images, the work table and the per-row mask of run_cross_segments16; d <= 1024 the narrow
+// scan, above it (mmf_simtopk_cross_segments_wide_anyk) `wide`: the wide scan's padded dim, cross_segw_table, 32-entry
+// lists, no id scratch, no shared thresholds, its launches in the narrow ones' slots and no overflow lists (a crowded row is flagged).
+// r: checked, begun, n > 0, r.precision MMF_PREC_FAST or _FAST_BF16, k beyond one pass; the entry has refused every
 // segment short of k columns outside itself, so every row is served.  Nothing is excluded by identity (a row's self lies inside its
-// masked segment), so a pass is K = 44 / 20 entries deep.  Prep happens once: row scalars, the plain 16-bit images, cross_seg16_table
-// at the full depth and the rows' bounds.  Pass 0: the fast call's launches at depth K into the k-wide rows, every row's floor left
-// behind (the flagged ones by the exact cross scan).  A later pass: ceilings by row, the same device work table under them
-// (launch_scan_b16_xseg_ceil), the audit, the re-rank into staging rows, count, one yield for the whole call, emit, and the exact
-// rescan of the rows that were flagged or short.  Floor ids are rows of all of Y on both sides: no rebase.  A row that runs out of
-// unemitted columns outside its segment stays in the table: its lists come up short, the re-rank flags it and it takes the rescan.
+// masked segment), so a pass is K = 44 / 20 entries deep.  Prep happens once: row scalars, the plain 16-bit images, the work table
+// at the full depth and the rows' bounds.  Pass 0: the one-pass call's launches at depth K into the k-wide rows, every row's floor
+// left behind (the flagged ones by the exact cross scan).  A later pass: ceilings by row, the same device work table under them
+// (launch_scan_b16_xseg_ceil / launch_scan_b16w_xseg_ceil), the audit, the re-rank into staging rows, count, one yield for the whole
+// call, emit, and the exact rescan of the rows that were flagged or short.  Floor ids are rows of all of Y on both sides: no rebase.
+// A row that runs out of unemitted columns outside its segment stays in the table: its lists come up short, the re-rank flags it
+// and it takes the rescan.
 namespace mmf {
 
 // cross_flagged with a depth, an output column offset and floors: kq entries per row from column out_off on for the gathered rows
@@ -4300,11 +4247,14 @@ static int cross_anyk_run(Request& r, bool self, const int64_t* xp, const int64_
   const int64_t n = r.n, m = r.m;
   const int k = r.k, depth = anyk_depth(r.d), K = depth;
   const bool profile = r.profile, f16 = (r.precision == MMF_PREC_FAST);
+  const bool wide = r.d > 1024;   // run_cross_segments16's wide pieces, launch_scan_b16w_ceilings / _xseg_ceil under the ceilings
   mmf_simtopk_stats* stats = r.stats;
-  const int dp = scan_bf16_dp(r.d), qt = scan_b16_queries_per_block(dp), bcap = scan_bf16_cap(depth, dp);
+  const int dp = wide ? scan_b16w_dp(r.d) : scan_bf16_dp(r.d), bcap = wide ? scan_b16w_cap(depth) : scan_bf16_cap(depth, dp);
+  const int forced = opts ? opts->col_splits : 0;
   int lists = 2;
-  const std::vector<int32_t> sched = cross_seg16_table(xp, yp, S, qt, dp, bcap, kCross16Budget, opts ? opts->col_splits : 0, &lists);
-  if (lists < 0) {
+  const std::vector<int32_t> sched = wide ? cross_segw_table(xp, yp, S, bcap, kCross16Budget, forced, &lists)
+                                          : cross_seg16_table(xp, yp, S, scan_b16_queries_per_block(dp), dp, bcap, kCross16Budget, forced, &lists);
+  if (!wide && lists < 0) {
     set_error("%s: a column run of the %lld rows of Y exceeds 4 GiB of 16-bit operands at padded dim %d", who, (long long)m, dp);
     return MMF_E_UNSUPPORTED;
   }
@@ -4315,8 +4265,8 @@ static int cross_anyk_run(Request& r, bool self, const int64_t* xp, const int64_
   for (int64_t g = 0; g < S; ++g)
     for (int64_t i = xp[g]; i < xp[g + 1]; ++i) { bounds[2 * i] = (uint32_t)yp[g]; bounds[2 * i + 1] = (uint32_t)(yp[g + 1] - yp[g]); }
 
-  // ---- workspace (slot 0): the fast call's at the pass depth, then floors, bookkeeping, ceilings and the staging rows -------------
-  const size_t scratch_bytes = scan_b16_seg_scratch_bytes(grid, dp, bcap);
+  // ---- workspace (slot 0): the one-pass call's at the pass depth, then floors, bookkeeping, ceilings and the staging rows ---------
+  const size_t scratch_bytes = wide ? 0 : scan_b16_seg_scratch_bytes(grid, dp, bcap);   // 0 bytes: nothing is carved
   const size_t stage = (size_t)n * K;
   const size_t need = ws_bytes(n, 4) + (self ? 0 : ws_bytes(m, 4)) + FlagBlock::bytes(n) + ws_bytes(4, 4) + HalfImage::bytes(n_pad, dp) +
                       (self ? 0 : HalfImage::bytes(m_pad, dp)) + ws_bytes(sched.size(), 4) + ws_bytes(bounds.size(), 4) +
@@ -4363,16 +4313,8 @@ static int cross_anyk_run(Request& r, bool self, const int64_t* xp, const int64_
   MMF_TRY(t_prep.stop(s));
 
   ScanB16Panel pn;
-  pn.seed = seed; pn.seed_stride = n; pn.share = lists > 2 ? 1 : 0;
+  pn.seed = seed; pn.seed_stride = n; pn.share = (!wide && lists > 2) ? 1 : 0;
   const ScanB16Problem sp(Q, C, n, m, m_pad, dp, r.d, f16, r.metric, depth);
-  // what the fast call resets before its scan
-  auto reset_lists = [&]() -> int {
-    MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));   // the slots a block's entries do not use stay empty
-    MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
-    MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));
-    MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n * 8, s));
-    return MMF_OK;
-  };
   // `cnt` device rows on the host, ascending (one more synchronisation)
   auto sorted_rows = [&](const int32_t* dev_rows, int64_t cnt, std::vector<int32_t>* out) -> int {
     out->resize((size_t)cnt);
@@ -4391,9 +4333,10 @@ static int cross_anyk_run(Request& r, bool self, const int64_t* xp, const int64_
   };
 
   // ---- pass 0: K entries per row, k-wide rows, floors left ----------------------------------------------------------------------
-  MMF_TRY(reset_lists());
+  MMF_TRY(reset_b16_lists(L, n, lists, seed, n, s));
   MMF_TRY(t_scan.start(profile, s));
-  MMF_TRY(launch_scan_b16_xseg(sp, d_sched, grid, d_bounds, L, scan_scratch, pn, s));
+  if (wide) MMF_TRY(launch_scan_b16w_xseg(sp, d_sched, grid, d_bounds, lists, L, pn, s));
+  else MMF_TRY(launch_scan_b16_xseg(sp, d_sched, grid, d_bounds, L, scan_scratch, pn, s));
   MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
   MMF_TRY(t_scan.stop(s));
   SelectProblem q = r.select();
@@ -4445,33 +4388,22 @@ static int cross_anyk_run(Request& r, bool self, const int64_t* xp, const int64_
   };
   for (int pass = 1; done < k; ++pass) {
     if (pass >= MMF_FAST_ANYK_MAX_PASSES - 1) return finish_exact(pass);
-    MMF_TRY(launch_scan_b16_ceilings(sp, L.cap, fkey, rx, max_n, r.lambda, n_pad, ceil, s));
-    MMF_TRY(reset_lists());
+    if (wide) MMF_TRY(launch_scan_b16w_ceilings(sp, fkey, rx, max_n, r.lambda, n_pad, ceil, s));
+    else MMF_TRY(launch_scan_b16_ceilings(sp, L.cap, fkey, rx, max_n, r.lambda, n_pad, ceil, s));
+    MMF_TRY(reset_b16_lists(L, n, lists, seed, n, s));
     MMF_TRY(flags.zero(s));
-    MMF_TRY(launch_scan_b16_xseg_ceil(sp, d_sched, grid, d_bounds, L, scan_scratch, pn, ceil, s));
+    if (wide) MMF_TRY(launch_scan_b16w_xseg_ceil(sp, d_sched, grid, d_bounds, lists, L, pn, ceil, s));
+    else MMF_TRY(launch_scan_b16_xseg_ceil(sp, d_sched, grid, d_bounds, L, scan_scratch, pn, ceil, s));
     MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
-    SelectProblem ql = r.select();
-    ql.k = K; ql.out_idx = sidx; ql.out_val = sval; ql.key_out = skey; ql.out_stride = K;
-    ql.rx = rx; ql.cy = cy;
-    ql.fail_rows = flags.fail_rows; ql.fail_count = flags.fail_count;
-    ql.two_pass = true;
-    ql.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
-    MMF_TRY(launch_select(ql, L, s));
+    MMF_TRY(launch_select(anyk_stage_select(r, K, sidx, sval, skey, rx, cy, flags, order_scratch), L, s));
     MMF_TRY(launch_anyk_count(st, flags.fail_rows, flags.fail_count, fkey, fid, certified, hist, s));
     uint32_t h[64], xf = 0;
     MMF_HIP(hipMemcpyAsync(h, hist, (size_t)(K + 3) * 4, hipMemcpyDeviceToHost, s));
     MMF_HIP(hipMemcpyAsync(&xf, xfail, 4, hipMemcpyDeviceToHost, s));
     MMF_HIP(hipStreamSynchronize(s));
     MMF_TRY(xfail_check(xf));
-    // the largest yield that leaves at most `budget` unflagged rows short of it
-    const int t_max = std::min(K, k - done);
-    int t = 0;
-    int64_t below = 0, short_rows = 0;   // unflagged rows with fewer than t' certified entries
-    for (int tq = 1; tq <= t_max; ++tq) {
-      below += h[tq - 1];
-      if (below > budget) break;
-      t = tq; short_rows = below;
-    }
+    int64_t short_rows = 0;
+    const int t = anyk_yield(h, std::min(K, k - done), budget, &short_rows);
     if (t < 1) return finish_exact(pass);
     MMF_TRY(launch_anyk_emit(st, certified, t, done, k, r.out_idx, r.out_val, fkey, fid, rescan_rows, rescan_count, s));
     const int64_t rescan = (int64_t)h[K + 1] + short_rows;
@@ -4499,10 +4431,7 @@ int mmf_cross_segments_anyk_plan(int64_t d, int k, int* scan_kk, int* first_yiel
               (long long)d, k);
     return MMF_E_UNSUPPORTED;
   }
-  if (scan_kk) *scan_kk = k;
-  if (first_yield) *first_yield = k;
-  if (min_passes) *min_passes = 1;
-  return 0;
+  return anyk_plan(d, k, 0, true, scan_kk, first_yield, min_passes);
 }
 
 int mmf_simtopk_cross_segments_fast_anyk(const void* X, int64_t n, const void* Y, int64_t m, int64_t d, int in_dtype, int metric,
@@ -4558,8 +4487,7 @@ int mmf_simtopk_cross_segments_fast_anyk(const void* X, int64_t n, const void* Y
     return MMF_OK;
   }
   if (!multi) {   // one pass serves: the call IS mmf_simtopk_cross_segments_fast (above 1024: mmf_simtopk_cross_segments_wide)
-    MMF_TRY(d <= 1024 ? run_cross_segments_fast(r, self, x_ptr_host, y_ptr_host, n_segments, opts)
-                      : run_cross_segments_wide(r, self, x_ptr_host, y_ptr_host, n_segments, opts));
+    MMF_TRY(run_cross_segments16(r, self, x_ptr_host, y_ptr_host, n_segments, opts, d > 1024));
     anyk_record(info, 0, k, 0, r.stats ? r.stats->fallback_rows : 0);
     return MMF_OK;
   }
@@ -4567,210 +4495,8 @@ int mmf_simtopk_cross_segments_fast_anyk(const void* X, int64_t n, const void* Y
   return cross_anyk_run(r, self, x_ptr_host, y_ptr_host, n_segments, opts, info);
 }
 
-}  // extern "C"
-
 // ---- mmf_simtopk_cross_segments_wide_anyk (include/ext/mmf_hg_cross_segw_anyk.h) -------------------------------
-// cross_anyk_run with the wide pieces, 1024 < d <= 4096: the images at the wide scan's padded dim, cross_segw_table at the full depth
-// (20 entries, 32-entry lists) and the rows' bounds, all once.  r: checked, begun, n > 0, r.precision MMF_PREC_FAST or _FAST_BF16, k
-// beyond one pass; the entry has refused every segment short of k columns outside itself.  Pass 0: the launches of
-// run_cross_segments_wide at depth 20 into the k-wide rows, every row's floor left behind (the flagged ones by the exact cross scan).
-// A later pass: ceilings by row with the wide margin (launch_scan_b16w_ceilings), the same device work table under them
-// (launch_scan_b16w_xseg_ceil: the masked scan and, with several entries per row block, its threshold union over kept values), the
-// audit, the re-rank into staging rows, count, one yield for the whole call, emit, and the exact rescan of the rows that were flagged
-// or short.  No overflow lists on this schedule: a crowded row is flagged.  Shallow rows stay in the table, as in cross_anyk_run.
-namespace mmf {
-
-static int cross_wide_anyk_run(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts,
-                               mmf_fast_anyk_info* info) {
-  const char* who = r.call.who;
-  const hipStream_t s = r.call.s;
-  const int64_t n = r.n, m = r.m;
-  const int k = r.k, depth = anyk_depth(r.d), K = depth;
-  const bool profile = r.profile, f16 = (r.precision == MMF_PREC_FAST);
-  mmf_simtopk_stats* stats = r.stats;
-  const int dp = scan_b16w_dp(r.d), bcap = scan_b16w_cap(depth);
-  int lists = 2;
-  const std::vector<int32_t> sched = cross_segw_table(xp, yp, S, bcap, kCross16Budget, opts ? opts->col_splits : 0, &lists);
-  const int64_t grid = (int64_t)sched.size() / 8;
-  const int64_t n_pad = (n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256;
-  // per row of X: first row and row count of the columns it may not take; padding rows exclude nothing
-  std::vector<uint32_t> bounds((size_t)n_pad * 2, 0u);
-  for (int64_t g = 0; g < S; ++g)
-    for (int64_t i = xp[g]; i < xp[g + 1]; ++i) { bounds[2 * i] = (uint32_t)yp[g]; bounds[2 * i + 1] = (uint32_t)(yp[g + 1] - yp[g]); }
-
-  // ---- workspace (slot 0): the wide call's at the pass depth, then floors, bookkeeping, ceilings and the staging rows -----------------
-  const size_t stage = (size_t)n * K;
-  const size_t need = ws_bytes(n, 4) + (self ? 0 : ws_bytes(m, 4)) + FlagBlock::bytes(n) + ws_bytes(4, 4) + HalfImage::bytes(n_pad, dp) +
-                      (self ? 0 : HalfImage::bytes(m_pad, dp)) + ws_bytes(sched.size(), 4) + ws_bytes(bounds.size(), 4) +
-                      b16_lists_bytes(n, lists, bcap) + ws_bytes(2 * (size_t)n, 4) + ws_bytes(select_order_bytes(n), 1) +
-                      4 * ws_bytes(n, 4) + ws_bytes(n_pad, 4) + ws_bytes(64, 4) + 2 * ws_bytes(4, 4) + ws_bytes(stage, 8) + 2 * ws_bytes(stage, 4);
-  Workspace ws;
-  MMF_TRY(r.call.workspace(need, &ws));
-  float* rx = ws.take<float>(n);
-  float* cy = self ? rx : ws.take<float>(m);
-  FlagBlock flags;
-  flags.carve(ws, n);
-  MMF_TRY(flags.zero(s));
-  uint32_t* max_n = ws.take<uint32_t>(4);
-  HalfImage Q, C;
-  Q.carve(ws, n_pad, dp);
-  if (self) C = Q; else C.carve(ws, m_pad, dp);
-  int32_t* d_sched = ws.take<int32_t>(sched.size());
-  uint32_t* d_bounds = ws.take<uint32_t>(bounds.size());
-  const CandLists L = carve_b16_lists(ws, n, lists, bcap);
-  int32_t* seed = ws.take<int32_t>(2 * (size_t)n);
-  char* order_scratch = ws.take<char>(select_order_bytes(n));
-  float* fkey = ws.take<float>(n); uint32_t* fid = ws.take<uint32_t>(n);
-  int32_t* certified = ws.take<int32_t>(n); int32_t* rescan_rows = ws.take<int32_t>(n);
-  float* ceil = ws.take<float>(n_pad);
-  uint32_t* hist = ws.take<uint32_t>(64); uint32_t* rescan_count = ws.take<uint32_t>(4);
-  uint32_t* xfail = ws.take<uint32_t>(4);   // rows the exact rescans could not certify (an internal invariant: none)
-  int64_t* sidx = ws.take<int64_t>(stage); float* sval = ws.take<float>(stage); float* skey = ws.take<float>(stage);
-
-  // ---- prep, once ---------------------------------------------------------------------------------------------------------------------
-  EventTimer t_prep, t_scan, t_sel, t_fb;
-  MMF_TRY(t_prep.start(profile, s));
-  MMF_HIP(hipMemsetAsync(max_n, 0, 16, s));
-  MMF_HIP(hipMemsetAsync(xfail, 0, 16, s));
-  MMF_TRY(launch_row_scalars(r.X, n, r.d, r.dtype, r.metric, rx, max_n, s));
-  if (!self) MMF_TRY(launch_row_scalars(r.Y, m, r.d, r.dtype, r.metric, cy, max_n, s));
-  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
-  MMF_TRY(upload_table(s, d_bounds, bounds.data(), bounds.size() * 4));
-  MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
-  if (!self) MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
-  MMF_TRY(launch_prep_half({r.Y, m, r.d, r.dtype, r.metric, cy, max_n}, C, dp, f16, s));
-  if (!self) MMF_TRY(launch_prep_half({r.X, n, r.d, r.dtype, r.metric, rx, max_n}, Q, dp, f16, s));
-  MMF_TRY(t_prep.stop(s));
-
-  ScanB16Panel pn;
-  pn.seed = seed; pn.seed_stride = n; pn.share = 0;
-  const ScanB16Problem sp(Q, C, n, m, m_pad, dp, r.d, f16, r.metric, depth);
-  // what the wide call resets before its scan
-  auto reset_lists = [&]() -> int {
-    MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));   // the slots a block's entries do not use stay empty
-    MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
-    MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));    // no overflow lists here: select reads them as empty
-    MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n * 8, s));
-    return MMF_OK;
-  };
-  // `cnt` device rows on the host, ascending (one more synchronisation)
-  auto sorted_rows = [&](const int32_t* dev_rows, int64_t cnt, std::vector<int32_t>* out) -> int {
-    out->resize((size_t)cnt);
-    if (cnt > 0) {
-      MMF_HIP(hipMemcpyAsync(out->data(), dev_rows, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
-      MMF_HIP(hipStreamSynchronize(s));
-      std::sort(out->begin(), out->end());
-    }
-    return MMF_OK;
-  };
-  bool xfail_pending = false;   // an exact rescan has run since *xfail was last read
-  auto xfail_check = [&](uint32_t v) -> int {
-    xfail_pending = false;
-    if (v != 0) { set_error("%s: %u rows failed in the exact scan (internal invariant)", who, v); return MMF_E_INTERNAL; }
-    return MMF_OK;
-  };
-
-  // ---- pass 0: K entries per row, k-wide rows, floors left ----------------------------------------------------------------------
-  MMF_TRY(reset_lists());
-  MMF_TRY(t_scan.start(profile, s));
-  MMF_TRY(launch_scan_b16w_xseg(sp, d_sched, grid, d_bounds, lists, L, pn, s));
-  MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
-  MMF_TRY(t_scan.stop(s));
-  SelectProblem q = r.select();
-  q.k = K; q.out_stride = k;
-  q.rx = rx; q.cy = cy;
-  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = stats ? flags.cand_total : nullptr;
-  q.two_pass = true;
-  q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
-  q.floor_key_out = fkey; q.floor_id_out = fid;
-  MMF_TRY(t_sel.start(profile, s));
-  MMF_TRY(launch_select(q, L, s));
-  MMF_TRY(t_sel.stop(s));
-  MMF_TRY(flags.read(stats != nullptr, s));
-  std::vector<int32_t> ex_rows;
-  const int64_t fallback0 = flags.h_fail4[0];
-  MMF_TRY(t_fb.start(profile && fallback0 > 0, s));
-  if (fallback0 > 0) {
-    MMF_TRY(sorted_rows(flags.fail_rows, fallback0, &ex_rows));
-    MMF_TRY(cross_flagged_from(r, rx, cy, ex_rows, xp, yp, S, K, 0, false, true, fkey, fid, xfail));
-    xfail_pending = true;
-  }
-  MMF_TRY(t_fb.stop(s));
-  {
-    const int64_t overflow_rows = flags.h_fail4[1] < (uint32_t)fallback0 ? flags.h_fail4[1] : fallback0;
-    fill_stats(stats, r.precision, lists / 2, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback0, overflow_rows,
-               fallback0 - overflow_rows, flags.h_tot);
-  }
-  anyk_record(info, 0, K, 0, fallback0);
-
-  // ---- later passes ---------------------------------------------------------------------------------------------------------------
-  const int64_t budget = n / anyk_short_div();
-  const AnykStage st{sidx, sval, skey, n, K, 0};
-  int done = K;
-  auto finish = [&]() -> int {   // the exact rescans' fail count, when none of the call's synchronisations has read it yet
-    if (!xfail_pending) return MMF_OK;
-    uint32_t v = 0;
-    MMF_HIP(hipMemcpyAsync(&v, xfail, 4, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipStreamSynchronize(s));
-    return xfail_check(v);
-  };
-  auto finish_exact = [&](int pass) -> int {   // every row, everything that is left, from the floors
-    ex_rows.resize((size_t)n);
-    for (int64_t i = 0; i < n; ++i) ex_rows[(size_t)i] = (int32_t)i;
-    MMF_TRY(cross_flagged_from(r, rx, cy, ex_rows, xp, yp, S, k - done, done, true, false, fkey, fid, xfail));
-    xfail_pending = true;
-    if (stats) stats->fallback_rows += n;
-    anyk_record(info, pass, k - done, 0, n);
-    return finish();
-  };
-  for (int pass = 1; done < k; ++pass) {
-    if (pass >= MMF_FAST_ANYK_MAX_PASSES - 1) return finish_exact(pass);
-    MMF_TRY(launch_scan_b16w_ceilings(sp, fkey, rx, max_n, r.lambda, n_pad, ceil, s));
-    MMF_TRY(reset_lists());
-    MMF_TRY(flags.zero(s));
-    MMF_TRY(launch_scan_b16w_xseg_ceil(sp, d_sched, grid, d_bounds, lists, L, pn, ceil, s));
-    MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
-    SelectProblem ql = r.select();
-    ql.k = K; ql.out_idx = sidx; ql.out_val = sval; ql.key_out = skey; ql.out_stride = K;
-    ql.rx = rx; ql.cy = cy;
-    ql.fail_rows = flags.fail_rows; ql.fail_count = flags.fail_count;
-    ql.two_pass = true;
-    ql.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
-    MMF_TRY(launch_select(ql, L, s));
-    MMF_TRY(launch_anyk_count(st, flags.fail_rows, flags.fail_count, fkey, fid, certified, hist, s));
-    uint32_t h[64], xf = 0;
-    MMF_HIP(hipMemcpyAsync(h, hist, (size_t)(K + 3) * 4, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipMemcpyAsync(&xf, xfail, 4, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipStreamSynchronize(s));
-    MMF_TRY(xfail_check(xf));
-    // the largest yield that leaves at most `budget` unflagged rows short of it
-    const int t_max = std::min(K, k - done);
-    int t = 0;
-    int64_t below = 0, short_rows = 0;   // unflagged rows with fewer than t' certified entries
-    for (int tq = 1; tq <= t_max; ++tq) {
-      below += h[tq - 1];
-      if (below > budget) break;
-      t = tq; short_rows = below;
-    }
-    if (t < 1) return finish_exact(pass);
-    MMF_TRY(launch_anyk_emit(st, certified, t, done, k, r.out_idx, r.out_val, fkey, fid, rescan_rows, rescan_count, s));
-    const int64_t rescan = (int64_t)h[K + 1] + short_rows;
-    if (rescan > 0) {
-      MMF_TRY(sorted_rows(rescan_rows, rescan, &ex_rows));
-      MMF_TRY(cross_flagged_from(r, rx, cy, ex_rows, xp, yp, S, t, done, true, done + t < k, fkey, fid, xfail));
-      xfail_pending = true;
-      if (stats) stats->fallback_rows += rescan;
-    }
-    anyk_record(info, pass, t, (int)h[K + 2], rescan);
-    done += t;
-  }
-  return finish();
-}
-
-}  // namespace mmf
-
-extern "C" {
-
+// cross_anyk_run under `wide`, 1024 < d <= 4096: passes of 20 entries over 32-entry lists.
 int mmf_cross_segments_wide_anyk_plan(int64_t d, int k, int* scan_kk, int* first_yield, int* min_passes) {
   return mmf_wide_anyk_plan(d, k, 0, scan_kk, first_yield, min_passes);
 }
@@ -4834,316 +4560,16 @@ int mmf_simtopk_cross_segments_wide_anyk(const void* X, int64_t n, const void* Y
     return MMF_OK;
   }
   if (!multi) {   // one pass serves: the call IS mmf_simtopk_cross_segments_wide
-    MMF_TRY(run_cross_segments_wide(r, self, x_ptr_host, y_ptr_host, n_segments, opts));
+    MMF_TRY(run_cross_segments16(r, self, x_ptr_host, y_ptr_host, n_segments, opts, true));
     anyk_record(info, 0, k, 0, r.stats ? r.stats->fallback_rows : 0);
     return MMF_OK;
   }
   r.precision = prec;
-  return cross_wide_anyk_run(r, self, x_ptr_host, y_ptr_host, n_segments, opts, info);
+  return cross_anyk_run(r, self, x_ptr_host, y_ptr_host, n_segments, opts, info);
 }
-
-}  // extern "C"
 
 // ---- mmf_simtopk_segmented_wide_anyk (include/ext/mmf_hg_segw_anyk.h) ------------------------------------------
-// segmented_anyk_run with the wide pieces of the segmented body (mmf::mmf_simtopk_segmented, wide_allowed), 1024 < d <= 4096: the
-// segment-padded images at the wide scan's padded dim and 128-row tiles, the work table at the full depth (20 entries, 32-entry
-// lists) with a forced opts->col_splits under the body's bounds (automatic: one range per segment), no id scratch.  r: checked,
-// begun, n > 0, r.precision MMF_PREC_FAST or _FAST_BF16, k + self beyond one pass.  A segment is SERVED when it has rows and at
-// least k admissible columns; the others go through the exact launch loop in pass 0, as in the body.  Pass 0: launch_scan_b16w_seg,
-// the audit, the re-rank of K entries into the k-wide output rows, every served row's floor left behind (the flagged ones by the
-// exact pass, gathered per segment).  A later pass: ceilings by operand position with the wide margin
-// (launch_scan_b16w_ceilings_gather), the same device work table under them (launch_scan_b16w_seg_ceil: the scan and, with several
-// ranges per segment, its threshold union), the audit, the re-rank into staging rows, count, one yield for the whole call, emit, and
-// the exact rescan — one gathered group per segment — of the served rows that were flagged or short.  Floor ids live as rows of Y
-// and are rebased around the per-segment exact passes (launch_floor_rebase).  No overflow lists on this schedule: a crowded row is
-// flagged.  A served segment that runs out of unemitted columns (adm - done < K) stays in the work table, as in segmented_anyk_run.
-namespace mmf {
-
-static int segw_anyk_run(Request& r, bool self, const int64_t* xp, const int64_t* yp, int64_t S, const mmf_simtopk_opts* opts,
-                         mmf_fast_anyk_info* info) {
-  const char* who = r.call.who;
-  const hipStream_t s = r.call.s;
-  const int64_t n = r.n, m = r.m, d = r.d;
-  const int k = r.k, self1 = r.exclude_self ? 1 : 0, depth = anyk_depth(d), K = depth - self1;
-  const bool f16 = r.precision == MMF_PREC_FAST, profile = r.profile;
-  mmf_simtopk_stats* stats = r.stats;
-  const int dp = scan_b16w_dp(d), qt = scan_b16w_queries_per_block(), kTile = scan_b16w_col_tile(), bcap = scan_b16w_cap(depth);
-
-  // ---- the body's tables: column ranges, work table, position -> row gathers; and per row the first row of Y of its segment -------
-  std::vector<int64_t> adm(S);
-  std::vector<char> on_fast(S, 0);
-  int64_t unserved_rows = 0, n_served = 0;
-  for (int64_t g = 0; g < S; ++g) {
-    const int64_t ng = xp[g + 1] - xp[g];
-    adm[g] = admissible_columns(xp[g], ng, yp[g], yp[g + 1] - yp[g], r.exclude_self);
-    if (ng == 0) continue;
-    if (adm[g] < k) { unserved_rows += ng; continue; }
-    on_fast[g] = 1;
-    n_served += ng;
-  }
-  // the body's rule: a forced count is taken while select's capacity per row holds 2 x splits lists; each segment
-  // caps its count at its own tile count, rounded down to a power of two
-  int call_splits = 1, max_splits = 1;
-  {
-    int64_t R = 0;
-    for (int64_t g = 0; g < S; ++g)
-      if (on_fast[g]) R += (xp[g + 1] - xp[g] + qt - 1) / qt;
-    const int forced = opts ? opts->col_splits : 0;
-    const auto fits = [&](int sp) { return 2 * sp * bcap <= 1024 - kSpillCap; };
-    if (forced > 0) { while (call_splits < forced && fits(2 * call_splits)) call_splits <<= 1; }
-    else if (wide_seg_auto_splits()) { while (R > 0 && R * call_splits < 256 && fits(2 * call_splits)) call_splits <<= 1; }
-  }
-  std::vector<int32_t> sched, col0(n, 0), served_rows;
-  served_rows.reserve((size_t)n_served);
-  int64_t nq_pos = 0, mc_pos = 0;
-  for (int64_t g = 0; g < S; ++g) {
-    if (!on_fast[g]) continue;
-    const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g];
-    const int64_t tiles = (mg + kTile - 1) / kTile;
-    const int64_t t0 = mc_pos / kTile;
-    int sp = 1;                                   // column ranges of this segment: one table entry and one list pair each
-    while (2 * sp <= call_splits && 2 * sp <= tiles) sp <<= 1;
-    if (sp > max_splits) max_splits = sp;
-    const int64_t tps = (tiles + sp - 1) / sp;
-    for (int64_t b = 0; b < ng; b += qt) {
-      for (int c = 0; c < sp; ++c) {
-        const int64_t tb = std::min(t0 + c * tps, t0 + tiles), te = std::min(tb + tps, t0 + tiles);
-        const int32_t e[8] = {(int32_t)(nq_pos + b), (int32_t)(xp[g] + b), (int32_t)(ng - b < qt ? ng - b : qt), (int32_t)tb,
-                              (int32_t)te, (int32_t)(uint32_t)(yp[g] - t0 * kTile), 2 * c, 0};
-        sched.insert(sched.end(), e, e + 8);
-      }
-    }
-    for (int64_t i = 0; i < ng; ++i) { col0[xp[g] + i] = (int32_t)yp[g]; served_rows.push_back((int32_t)(xp[g] + i)); }
-    nq_pos += (ng + qt - 1) / qt * qt;
-    mc_pos += tiles * kTile;
-    if (nq_pos >= (int64_t(1) << 31) || mc_pos >= (int64_t(1) << 31)) { set_error("%s: padded images too large", who); return MMF_E_UNSUPPORTED; }
-  }
-  const int64_t grid = (int64_t)sched.size() / 8;
-  std::vector<int32_t> qgather(nq_pos, -1), cgather(mc_pos, -1);
-  {
-    int64_t qpos = 0, cpos = 0;
-    for (int64_t g = 0; g < S; ++g) {
-      if (!on_fast[g]) continue;
-      const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g];
-      for (int64_t i = 0; i < ng; ++i) qgather[qpos + i] = (int32_t)(xp[g] + i);
-      for (int64_t j = 0; j < mg; ++j) cgather[cpos + j] = (int32_t)(yp[g] + j);
-      qpos += (ng + qt - 1) / qt * qt;
-      cpos += (mg + kTile - 1) / kTile * kTile;
-    }
-  }
-
-  // ---- workspace (slot 0): the body's, then floors, bookkeeping, ceilings and the staging rows -----------------------------------
-  const int64_t nq_pad = (nq_pos + 255) / 256 * 256, mc_pad = (mc_pos + 255) / 256 * 256;
-  const int lists = 2 * max_splits;
-  const int64_t n_seed = n;
-  const size_t stage = (size_t)n * K;
-  size_t need = ws_bytes(n, 4) + ws_bytes(m, 4) + FlagBlock::bytes(n);
-  if (grid > 0)
-    need += HalfImage::bytes(nq_pad, dp) + HalfImage::bytes(mc_pad, dp) + ws_bytes(4, 4) + ws_bytes(sched.size(), 4) +
-            ws_bytes(nq_pos, 4) + ws_bytes(mc_pos, 4) + b16_lists_bytes(n, lists, bcap) +
-            ws_bytes(2 * (size_t)n_seed, 4) + ws_bytes(select_order_bytes(n), 1) +
-            5 * ws_bytes(n, 4) + ws_bytes(nq_pad, 4) + ws_bytes(64, 4) + ws_bytes(4, 4) + ws_bytes(stage, 8) + 2 * ws_bytes(stage, 4);
-  Workspace ws;
-  MMF_TRY(r.call.workspace(need, &ws));
-  float* rx = ws.take<float>(n);
-  float* cy = self ? rx : ws.take<float>(m);
-  FlagBlock flags;
-  flags.carve(ws, n);
-  MMF_TRY(flags.zero(s));
-
-  EventTimer t_prep, t_scan, t_sel, t_fb;
-  MMF_TRY(t_prep.start(profile, s));
-  uint32_t* max_n = nullptr;
-  if (grid > 0) { max_n = ws.take<uint32_t>(4); MMF_HIP(hipMemsetAsync(max_n, 0, 16, s)); }
-  MMF_TRY(launch_row_scalars(r.X, n, d, r.dtype, r.metric, rx, max_n, s));
-  if (!self && m > 0) MMF_TRY(launch_row_scalars(r.Y, m, d, r.dtype, r.metric, cy, max_n, s));
-
-  // kq entries per row from column out_off0 on for `rows` (served rows, ascending: grouped by segment) by the exact pass, one
-  // gathered group per segment; `whole`: also the unserved segments, for what they have (pass 0 only).  Does not synchronise.
-  int32_t* d_rows = nullptr; int32_t* d_col0 = nullptr;
-  float* fkey = nullptr; uint32_t* fid = nullptr;
-  auto exact_rows = [&](const std::vector<int32_t>& rows, int kq, int out_off0, bool floors_in, bool floors_out, bool whole) -> int {
-    ExactPass ex(r, rx, cy);
-    ex.same = self;
-    ex.out_stride = k; ex.out_off0 = out_off0;
-    ex.floors_in = floors_in; ex.floors_out = floors_out;
-    ex.row_floor_key = fkey; ex.row_floor_id = fid;
-    const int64_t cnt = (int64_t)rows.size();
-    for (int64_t g = 0, e = 0; g < S; ++g) {
-      const int64_t ng = xp[g + 1] - xp[g], mg = yp[g + 1] - yp[g], e0 = e;
-      if (on_fast[g]) {
-        while (e < cnt && rows[e] < xp[g + 1]) ++e;
-        if (e > e0) ex.add(ExactGroup{e0, e - e0, true, yp[g], mg, kq});
-      } else if (whole && ng > 0) {   // short of k admissible columns: its top-(m_g - self) first, then -1 / -inf
-        MMF_HIP(hipMemsetAsync(r.out_idx + xp[g] * k, 0xff, (size_t)ng * k * 8, s));
-        MMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.out_val + xp[g] * k), (int)0xff800000u, (size_t)ng * k, s));
-        if (adm[g] > 0) ex.add(ExactGroup{xp[g], ng, false, yp[g], mg, (int)adm[g]});
-      }
-    }
-    if (ex.pieces.empty()) return MMF_OK;
-    ex.n_ids = cnt; ex.row_ids = d_rows;
-    Workspace aux;   // lists and f32 images in the second workspace slot
-    MMF_TRY(r.call.workspace(ex.image_bytes() + ex.list_bytes(), &aux, 1));
-    ExactLists B;
-    B.carve(aux, ex.rows_total, ex.list_words, ex.cap(), ex.floors());
-    if (cnt > 0) MMF_TRY(upload_table(s, d_rows, rows.data(), (size_t)cnt * 4));
-    if (floors_in) MMF_TRY(launch_floor_rebase(d_rows, cnt, fid, d_col0, false, s));
-    MMF_TRY(B.zero(s));
-    MMF_TRY(ex.run(aux, B));
-    if (floors_out) MMF_TRY(launch_floor_rebase(d_rows, cnt, fid, d_col0, true, s));
-    return MMF_OK;
-  };
-
-  if (grid == 0) {   // no segment is served: the launch loop answers the call
-    MMF_TRY(t_prep.stop(s));
-    MMF_TRY(t_fb.start(profile, s));
-    MMF_TRY(exact_rows({}, 0, 0, false, false, true));
-    MMF_TRY(t_fb.stop(s));
-    MMF_HIP(hipStreamSynchronize(s));
-    fill_stats(stats, MMF_PREC_EXACT, 1, 0, t_prep.ms(), t_fb.ms(), 0.f, 0.f, 0, 0, 0, flags.h_tot);
-    anyk_record(info, 0, k, 0, 0);
-    return MMF_OK;
-  }
-
-  HalfImage Q, C;
-  Q.carve(ws, nq_pad, dp);
-  C.carve(ws, mc_pad, dp);
-  int32_t* d_sched = ws.take<int32_t>(sched.size());
-  int32_t* d_qg = ws.take<int32_t>(nq_pos);
-  int32_t* d_cg = ws.take<int32_t>(mc_pos);
-  const CandLists L = carve_b16_lists(ws, n, lists, bcap);
-  int32_t* seed = ws.take<int32_t>(2 * (size_t)n_seed);
-  char* order_scratch = ws.take<char>(select_order_bytes(n));
-  fkey = ws.take<float>(n); fid = ws.take<uint32_t>(n);
-  int32_t* certified = ws.take<int32_t>(n); int32_t* rescan_rows = ws.take<int32_t>(n);
-  d_col0 = ws.take<int32_t>(n); d_rows = rescan_rows;   // (a pass's rescan list is read to the host before the sorted rows take its place)
-  float* ceil = ws.take<float>(nq_pad);
-  uint32_t* hist = ws.take<uint32_t>(64); uint32_t* rescan_count = ws.take<uint32_t>(4);
-  int64_t* sidx = ws.take<int64_t>(stage); float* sval = ws.take<float>(stage); float* skey = ws.take<float>(stage);
-  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
-  MMF_TRY(upload_table(s, d_qg, qgather.data(), (size_t)nq_pos * 4));
-  MMF_TRY(upload_table(s, d_cg, cgather.data(), (size_t)mc_pos * 4));
-  MMF_TRY(upload_table(s, d_col0, col0.data(), (size_t)n * 4));
-  MMF_HIP(hipMemsetAsync(Q.maxima, 0, 16, s));
-  MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
-  MMF_TRY(launch_prep_half_gather({r.Y, m, d, r.dtype, r.metric, cy, max_n}, d_cg, mc_pos, C, dp, f16, s));
-  MMF_TRY(launch_prep_half_gather({r.X, n, d, r.dtype, r.metric, rx, max_n}, d_qg, nq_pos, Q, dp, f16, s));
-  MMF_TRY(t_prep.stop(s));
-
-  ScanB16Panel pn;
-  pn.seed = seed; pn.seed_stride = n_seed; pn.share = 0;
-  const ScanB16Problem sp(Q, C, n, m, mc_pad, dp, d, f16, r.metric, depth);
-  // what the body resets before its scan (rows of unserved segments keep empty lists: the re-rank reports them every pass)
-  auto reset_lists = [&]() -> int {
-    MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * lists * 4, s));
-    MMF_HIP(hipMemsetAsync(L.overflow, 0, (size_t)n * 4, s));
-    MMF_HIP(hipMemsetAsync(L.spill_cnt, 0, (size_t)n * 4, s));    // no overflow lists here: select reads them as empty
-    MMF_HIP(hipMemsetAsync(seed, 0x80, (size_t)n_seed * 8, s));
-    return MMF_OK;
-  };
-  // the served rows among `cnt` device rows, ascending (one more synchronisation)
-  auto served_of = [&](const int32_t* dev_rows, int64_t cnt, std::vector<int32_t>* out) -> int {
-    std::vector<int32_t> h((size_t)cnt);
-    if (cnt > 0) {
-      MMF_HIP(hipMemcpyAsync(h.data(), dev_rows, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
-      MMF_HIP(hipStreamSynchronize(s));
-    }
-    out->clear();
-    for (int32_t row : h) {
-      const int64_t g = (int64_t)(std::upper_bound(xp, xp + S + 1, (int64_t)row) - xp) - 1;
-      if (g >= 0 && g < S && on_fast[g]) out->push_back(row);
-    }
-    std::sort(out->begin(), out->end());
-    return MMF_OK;
-  };
-
-  // ---- pass 0: K entries per row, k-wide rows, floors left ----------------------------------------------------------------------
-  MMF_TRY(reset_lists());
-  MMF_TRY(t_scan.start(profile, s));
-  MMF_TRY(launch_scan_b16w_seg(sp, d_sched, grid, lists, L, pn, s));
-  MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
-  MMF_TRY(t_scan.stop(s));
-  SelectProblem q = r.select();
-  q.k = K; q.out_stride = k;
-  q.rx = rx; q.cy = cy;
-  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count; q.cand_total = stats ? flags.cand_total : nullptr;
-  q.two_pass = true;
-  q.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
-  q.floor_key_out = fkey; q.floor_id_out = fid;
-  MMF_TRY(t_sel.start(profile, s));
-  MMF_TRY(launch_select(q, L, s));
-  MMF_TRY(t_sel.stop(s));
-  MMF_TRY(flags.read(stats != nullptr, s));
-  std::vector<int32_t> ex_rows;
-  MMF_TRY(served_of(flags.fail_rows, flags.h_fail4[0], &ex_rows));
-  const int64_t fallback0 = (int64_t)ex_rows.size();
-  MMF_TRY(t_fb.start(profile && (fallback0 > 0 || unserved_rows > 0), s));
-  MMF_TRY(exact_rows(ex_rows, K, 0, false, true, true));
-  MMF_TRY(t_fb.stop(s));
-  {
-    const int64_t overflow_rows = flags.h_fail4[1] < (uint32_t)fallback0 ? flags.h_fail4[1] : fallback0;
-    fill_stats(stats, r.precision, max_splits, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback0, overflow_rows,
-               fallback0 - overflow_rows, flags.h_tot);
-  }
-  anyk_record(info, 0, K, 0, fallback0);
-
-  // ---- later passes ---------------------------------------------------------------------------------------------------------------
-  const int64_t budget = n_served / anyk_short_div();
-  const AnykStage st{sidx, sval, skey, n, K, 0};
-  int done = K;
-  auto finish_exact = [&](int pass) -> int {   // every served row, everything that is left
-    MMF_TRY(exact_rows(served_rows, k - done, done, true, false, false));
-    if (stats) stats->fallback_rows += n_served;
-    anyk_record(info, pass, k - done, 0, n_served);
-    return MMF_OK;
-  };
-  for (int pass = 1; done < k; ++pass) {
-    if (pass >= MMF_FAST_ANYK_MAX_PASSES - 1) return finish_exact(pass);
-    MMF_TRY(launch_scan_b16w_ceilings_gather(sp, d_qg, nq_pos, fkey, rx, max_n, r.lambda, nq_pad, ceil, s));
-    MMF_TRY(reset_lists());
-    MMF_TRY(flags.zero(s));
-    MMF_TRY(launch_scan_b16w_seg_ceil(sp, d_sched, grid, lists, L, pn, ceil, s));
-    MMF_TRY(launch_scan_b16_audit(pn, L.overflow, n, s));
-    SelectProblem ql = r.select();
-    ql.k = K; ql.out_idx = sidx; ql.out_val = sval; ql.key_out = skey; ql.out_stride = K;
-    ql.rx = rx; ql.cy = cy;
-    ql.fail_rows = flags.fail_rows; ql.fail_count = flags.fail_count;
-    ql.two_pass = true;
-    ql.order_scratch = getenv("MMF_SELECT_UNORDERED") ? nullptr : order_scratch;
-    MMF_TRY(launch_select(ql, L, s));
-    MMF_TRY(launch_anyk_count(st, flags.fail_rows, flags.fail_count, fkey, fid, certified, hist, s));
-    uint32_t h[64];
-    MMF_HIP(hipMemcpyAsync(h, hist, (size_t)(K + 3) * 4, hipMemcpyDeviceToHost, s));
-    MMF_HIP(hipStreamSynchronize(s));
-    // the largest yield that leaves at most `budget` unflagged rows short of it (unserved rows are always flagged)
-    const int t_max = std::min(K, k - done);
-    int t = 0;
-    int64_t below = 0, short_rows = 0;
-    for (int tq = 1; tq <= t_max; ++tq) {
-      below += h[tq - 1];
-      if (below > budget) break;
-      t = tq; short_rows = below;
-    }
-    if (t < 1) return finish_exact(pass);
-    MMF_TRY(launch_anyk_emit(st, certified, t, done, k, r.out_idx, r.out_val, fkey, fid, rescan_rows, rescan_count, s));
-    const int64_t listed = (int64_t)h[K + 1] + short_rows;   // the emit kernel's list: flagged rows (the unserved ones among them) and short rows
-    int64_t rescan = 0;
-    if (listed > unserved_rows) {
-      MMF_TRY(served_of(rescan_rows, listed, &ex_rows));
-      rescan = (int64_t)ex_rows.size();
-      MMF_TRY(exact_rows(ex_rows, t, done, true, done + t < k, false));
-      if (stats) stats->fallback_rows += rescan;
-    }
-    anyk_record(info, pass, t, (int)h[K + 2], rescan);
-    done += t;
-  }
-  return MMF_OK;
-}
-
-}  // namespace mmf
-
-extern "C" {
-
+// segmented_anyk_run under `wide`, 1024 < d <= 4096: passes of 20 entries (self's slot included) over 32-entry lists.
 int mmf_segmented_wide_anyk_plan(int64_t d, int k, int exclude_self, int* scan_kk, int* first_yield, int* min_passes) {
   return mmf_wide_anyk_plan(d, k, exclude_self, scan_kk, first_yield, min_passes);
 }
@@ -5200,7 +4626,7 @@ int mmf_simtopk_segmented_wide_anyk(const void* X, int64_t n, const void* Y, int
     return MMF_OK;
   }
   r.precision = prec;
-  return segw_anyk_run(r, self, x_ptr_host, y_ptr_host, n_segments, opts, info);
+  return segmented_anyk_run(r, self, x_ptr_host, y_ptr_host, n_segments, opts, info);
 }
 
 }  // extern "C"

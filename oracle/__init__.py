@@ -36,9 +36,10 @@ def build(force: bool = False) -> str:
     """Compile oracle/mmf_oracle.c -> oracle/libmmf_oracle.so (gcc).  Idempotent."""
     if (not force) and os.path.exists(_SO) and os.path.getmtime(_SO) >= os.path.getmtime(_SRC):
         return _SO
-    cmd = ["gcc", *CFLAGS, _SRC, "-o", _SO + ".tmp", "-lm"]
+    tmp = f"{_SO}.{os.getpid()}.tmp"   # per process: the ranks of a spawned test may all find the library stale at once
+    cmd = ["gcc", *CFLAGS, _SRC, "-o", tmp, "-lm"]
     subprocess.run(cmd, check=True)
-    os.replace(_SO + ".tmp", _SO)
+    os.replace(tmp, _SO)
     return _SO
 
 

@@ -182,14 +182,19 @@ def test_the_entry_makes_every_refusal_before_the_first_device_call_and_keeps_th
         raw = f.read()
     body = raw.split("int mmf_simtopk_cross_segments_fast(", 1)[1].split("\n}\n", 1)[0]
     assert body.index(".on_device()") < body.index("set_error(") and body.rindex("set_error(") < body.index("run_segmented_exact(")
-    assert body.index("run_segmented_exact(") < body.index("run_cross_segments_fast(")
+    # the one driver of both one-pass 16-bit entries, on its narrow side: the literal `false`, behind this entry's own served test
+    narrow_call = "run_cross_segments16(r, self, x_ptr_host, y_ptr_host, n_segments, opts, false)"
+    assert body.count("run_cross_segments16(") == 1 and body.index("run_segmented_exact(") < body.index(narrow_call)
+    assert "scan_bf16_supported(d, k, in_dtype)" in body
     assert "hipStream" not in body and "hipMemcpy" not in body and "hipDeviceSynchronize" not in body
     assert "run_segmented_exact(r, self, x_ptr_host, y_ptr_host, n_segments, opts, nullptr, 0, 0.0f, true)" in body
     table = raw.split("int64_t mmf_cross_segments_fast_table(", 1)[1].split("\n}\n", 1)[0]
     assert "hip" not in table and "Call(" not in table                                          # host only
-    driver = raw.split("static int run_cross_segments_fast(", 1)[1].split("\n}\n", 1)[0]
-    assert driver.count("launch_scan_b16_xseg(") == 1 and driver.count("launch_select(") == 1 and driver.count("launch_scan_b16_audit(") == 1
-    assert driver.count("upload_table(") == 2 and driver.count("flags.read(") == 1
+    assert "run_cross_segments_fast" not in raw and raw.count("static int run_cross_segments16(") == 1
+    driver = raw.split("static int run_cross_segments16(", 1)[1].split("\n}\n", 1)[0]
+    assert driver.count("launch_scan_b16_xseg(") == 1 and driver.count("launch_scan_b16w_xseg(") == 1
+    assert driver.count("launch_select(") == 1 and driver.count("launch_scan_b16_audit(") == 1
+    assert driver.count("upload_table(") == 2 and driver.count("flags.read(") == 1 and driver.count("cross_flagged(") == 1
     # one synchronisation (flags.read) when no row is flagged; the second one sits inside the flagged branch
     assert driver.count("hipStreamSynchronize") == 1 and driver.index("if (fallback_rows > 0) {") < driver.index("hipStreamSynchronize")
     # the exact entry still refuses the 16-bit precisions with its own words (tests/test_cross_segments_cpu.py pins them)

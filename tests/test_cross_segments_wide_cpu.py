@@ -218,14 +218,19 @@ def test_the_entry_makes_every_refusal_before_the_first_device_call_and_keeps_th
         raw = f.read()
     body = raw.split("int mmf_simtopk_cross_segments_wide(", 1)[1].split("\n}\n", 1)[0]
     assert body.index(".on_device()") < body.index("set_error(") and body.rindex("set_error(") < body.index("run_segmented_exact(")
-    assert body.index("run_segmented_exact(") < body.index("run_cross_segments_wide(")
+    # the one driver of both one-pass 16-bit entries, on its wide side: the literal `true`
+    wide_call = "run_cross_segments16(r, self, x_ptr_host, y_ptr_host, n_segments, opts, true)"
+    narrow_call = "run_cross_segments16(r, self, x_ptr_host, y_ptr_host, n_segments, opts, false)"
+    assert body.count("run_cross_segments16(") == 1 and body.index("run_segmented_exact(") < body.index(wide_call)
     assert "hipStream" not in body and "hipMemcpy" not in body and "hipDeviceSynchronize" not in body
     assert "run_segmented_exact(r, self, x_ptr_host, y_ptr_host, n_segments, opts, nullptr, 0, 0.0f, true)" in body
-    assert "run_cross_segments_fast(" not in body and "scan_bf16_supported" not in body          # AUTO does not forward to the narrow entry
+    assert narrow_call not in body and "scan_bf16_supported" not in body                        # AUTO does not forward to the narrow entry
     table = raw.split("int64_t mmf_cross_segments_wide_table(", 1)[1].split("\n}\n", 1)[0]
     assert "hip" not in table and "Call(" not in table                                          # host only
-    driver = raw.split("static int run_cross_segments_wide(", 1)[1].split("\n}\n", 1)[0]
-    assert driver.count("launch_scan_b16w_xseg(") == 1 and driver.count("launch_select(") == 1 and driver.count("launch_scan_b16_audit(") == 1
+    assert "run_cross_segments_wide" not in raw and raw.count("static int run_cross_segments16(") == 1
+    driver = raw.split("static int run_cross_segments16(", 1)[1].split("\n}\n", 1)[0]
+    assert driver.count("launch_scan_b16w_xseg(") == 1 and driver.count("launch_scan_b16_xseg(") == 1
+    assert driver.count("launch_select(") == 1 and driver.count("launch_scan_b16_audit(") == 1
     assert driver.count("upload_table(") == 2 and driver.count("flags.read(") == 1 and driver.count("cross_flagged(") == 1
     assert driver.count("hipStreamSynchronize") == 1 and driver.index("if (fallback_rows > 0) {") < driver.index("hipStreamSynchronize")
     assert "(hipStream_t)0" not in driver and "hipMemcpy(" not in driver and "hipMemset(" not in driver
@@ -233,7 +238,7 @@ def test_the_entry_makes_every_refusal_before_the_first_device_call_and_keeps_th
     exact = raw.split("int mmf_simtopk_cross_segments(", 1)[1].split("\n}\n", 1)[0]
     assert "no 16-bit scan serves the cross-segment entry yet" in exact
     narrow = raw.split("int mmf_simtopk_cross_segments_fast(", 1)[1].split("\n}\n", 1)[0]
-    assert "scan_bf16_supported(d, k, in_dtype)" in narrow and "run_cross_segments_wide" not in narrow
+    assert "scan_bf16_supported(d, k, in_dtype)" in narrow and narrow_call in narrow and wide_call not in narrow
 
 
 # ---- 5. Python: ValueErrors on the host, and the router's route -------------------------------------------------------------------
