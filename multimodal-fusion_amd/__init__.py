@@ -25,6 +25,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.cross_segments_anyk.*                     that any-k 16-bit top-k across segments (every row against all OTHER segments), bit for bit, and the router
     mmf.cross_segments_wide_anyk.*                that any-k top-k across segments from the wide 16-bit scan (feature dims 1025..4096), bit for bit, and the router
     mmf.segmented_wide_anyk.*                     that any-k top-k for every segment of a ragged batch from the wide 16-bit scan (feature dims 1025..4096), bit for bit, and the router
+    mmf.combined_topk16_anyk.*                    the any-k top-k of K_h * K_g from the 16-bit scan of the combined key (one graph or a batch), bit for bit, and the router
     mmf.kmeans_ragged.*                           scikit-learn's KMeans fit for every block of a flat buffer in one call, each block with a width of its own
     mmf.wide_scan.*                               what the wide 16-bit scan (feature dims 1025..4096) covers: host-only queries
     mmf.cohort.build_cohort_hypergraphs(...)      the four steps of process_single_file for every slide of a cohort, in memory
@@ -94,6 +95,11 @@ from .cross_segments_wide_anyk import cross_segments_wide_anyk_plan, simtopk_cro
 from . import segmented_wide_anyk  # noqa: F401,E402
 from .segmented_wide_anyk import segmented_wide_anyk_plan, simtopk_segmented_wide_any_k  # noqa: F401,E402
 
+# (the module's router carries the name of combined_topk_anyk's call, which keeps the package-level name: reach it through the module)
+from . import combined_topk16_anyk  # noqa: F401,E402
+from .combined_topk16_anyk import (build_topk_hypergraph_data_fast_any_k, build_topk_weighted_hypergraph_fast_any_k,  # noqa: F401,E402
+                                   combined_fast_anyk_plan, simtopk_combined_fast_any_k)
+
 from . import wide_scan  # noqa: F401,E402
 from .wide_scan import list_capacity, wide_scan_supported  # noqa: F401,E402
 
@@ -118,4 +124,6 @@ __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combin
            "segmented_anyk", "simtopk_segmented_fast_any_k", "segmented_anyk_plan",
            "cross_segments_anyk", "simtopk_cross_segments_fast_any_k", "cross_segments_anyk_plan",
            "cross_segments_wide_anyk", "simtopk_cross_segments_wide_any_k", "cross_segments_wide_anyk_plan",
-           "segmented_wide_anyk", "simtopk_segmented_wide_any_k", "segmented_wide_anyk_plan"]
+           "segmented_wide_anyk", "simtopk_segmented_wide_any_k", "segmented_wide_anyk_plan",
+           "combined_topk16_anyk", "simtopk_combined_fast_any_k", "combined_fast_anyk_plan",
+           "build_topk_weighted_hypergraph_fast_any_k", "build_topk_hypergraph_data_fast_any_k"]

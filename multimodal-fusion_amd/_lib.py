@@ -162,6 +162,13 @@ CROSS_WIDE_ANYK_EXPORTS = ["mmf_simtopk_cross_segments_wide_anyk", "mmf_cross_se
 # tests/test_segmented_wide_anyk_cpu.py.
 SEGW_ANYK_EXPORTS = ["mmf_simtopk_segmented_wide_anyk", "mmf_segmented_wide_anyk_plan"]
 
+# The 16-bit combined top-k for any k (include/ext/mmf_hg_topk16_anyk.h): an addition to ABI version 3 in a header of
+# its own; the arguments of mmf_simtopk_combined plus the info struct of FAST_ANYK_EXPORTS.  mmf_simtopk_combined_fast_anyk
+# synchronises once per pass (fail counts and yield histogram together) and, in a pass that sends rows to the exact rescan, once
+# more for the rows (read and grouped per segment on the host) and once for the rescan's fail count; mmf_combined_fast_anyk_plan is
+# host-only.  Pinned by tests/test_simtopk_combined_fast_anyk_cpu.py.
+TOPK16_ANYK_EXPORTS = ["mmf_simtopk_combined_fast_anyk", "mmf_combined_fast_anyk_plan"]
+
 
 class FastAnykInfo(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
@@ -290,6 +297,10 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_segmented_wide_anyk.restype = ci
     L.mmf_segmented_wide_anyk_plan.argtypes = list(L.mmf_segmented_anyk_plan.argtypes)
     L.mmf_segmented_wide_anyk_plan.restype = ci
+    L.mmf_simtopk_combined_fast_anyk.argtypes = list(L.mmf_simtopk_combined.argtypes) + [ctypes.POINTER(FastAnykInfo)]
+    L.mmf_simtopk_combined_fast_anyk.restype = ci
+    L.mmf_combined_fast_anyk_plan.argtypes = list(L.mmf_fast_anyk_plan.argtypes)
+    L.mmf_combined_fast_anyk_plan.restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

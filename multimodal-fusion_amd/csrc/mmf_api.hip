@@ -431,7 +431,7 @@ struct ExactPass {
   const int32_t* row_ids = nullptr;         // device: the rows of X that gathered groups name
   int64_t n_ids = 0;
   uint32_t* cand_total = nullptr;           // optional: the re-rank counts its candidates here
-  const float *P = nullptr, *pn = nullptr;  // optional (slices only): rank by the exponent of K_h * K_g — positions [n][dp] of the rows of
+  const float *P = nullptr, *pn = nullptr;  // optional: rank by the exponent of K_h * K_g — positions [n][dp] of the rows of
   int dp = 0; float lambda_g = 0.0f;        //   X and their chains; r.metric MMF_RBF, r.lambda = lambda_h (mmf_simtopk_combined)
   const float *Pc = nullptr, *pnc = nullptr;   // ... and of the rows of Y (mmf_simtopk_combined_xy); null: P / pn, X against itself
   int64_t out_row0 = 0;                     // the outputs' first row is row out_row0 of X (the caller holds a row slice of X's rows)
@@ -532,7 +532,8 @@ struct ExactPass {
         if (t && one_pass) { MMF_TRY(t[1].stop(s)); MMF_TRY(t[2].start(r.profile, s)); }
         q.k = kp; q.out_off = out_off0 + done;
         q.floor_key_out = more ? B.floor_key : nullptr; q.floor_id_out = more ? B.floor_id : nullptr;
-        MMF_TRY(P ? launch_rerank_combined(q, L, s) : launch_select(q, L, s));
+        // (the combined key over gathered rows: the passes of mmf_simtopk_combined_fast_anyk)
+        MMF_TRY(P ? (q.row_ids ? launch_rerank_combined_ext(q, L, s) : launch_rerank_combined(q, L, s)) : launch_select(q, L, s));
       }
       if (row_floors && floors_out) MMF_TRY(launch_floor_move(row_ids + G.row0, G.rows, row_floor_key, row_floor_id, B.floor_key, B.floor_id, true, s));
       grid += g;
@@ -4627,6 +4628,359 @@ int mmf_simtopk_segmented_wide_anyk(const void* X, int64_t n, const void* Y, int
   }
   r.precision = prec;
   return segmented_anyk_run(r, self, x_ptr_host, y_ptr_host, n_segments, opts, info);
+}
+
+}  // extern "C"
+
+// ---- mmf_simtopk_combined_fast_anyk (include/ext/mmf_hg_topk16_anyk.h) ------------------------------------------
+// The passes of segmented_anyk_run over the image and the work table of run_simtopk_combined_fast_segmented, for the combined key;
+// one graph is a batch of one segment.  r: begun, n > 0, F against itself (MMF_F32, MMF_RBF, r.lambda = lambda_h), r.precision
+// MMF_PREC_FAST or _FAST_BF16, k + self > 20, at least one SERVED segment (rows and at least k admissible columns); the others go
+// through the exact launch loop in pass 0, as in the one-pass entry.
+// Pass 0: that entry's launches at depth 20, K = 20 - self entries into the k-wide output rows, every served row's floor left behind
+// (the PASS re-rank's floor slot; the flagged rows by the exact pass, gathered per segment).  A later pass: ceilings by row from the
+// floors (launch_scan_b16c_ceilings), the same device work table under them, the combined re-rank into staging rows with the
+// canonical key of every entry, count, one yield for the whole call, emit (the bookkeeping kernels of mmf_fast_anyk.hip, unchanged),
+// and the exact rescan — one gathered group per segment, the exact scan of the combined key over gathered rows — of the served rows
+// that were flagged or short.  The floors' ids are rows of F (what the call-wide re-rank leaves and anyk_count compares); an exact
+// pass over one segment's columns reads and leaves ids local to them: launch_floor_rebase on both sides.
+namespace mmf {
+
+static int combined_fast_anyk_run(Request& r, const float* P, int dpos, float lambda_g, const int64_t* ptr, int64_t S,
+                                  const mmf_simtopk_opts* opts, mmf_fast_anyk_info* info) {
+  const char* who = r.call.who;
+  const hipStream_t s = r.call.s;
+  const float* F = static_cast<const float*>(r.X);
+  const int64_t n = r.n, d = r.d;
+  const int k = r.k, self1 = r.exclude_self ? 1 : 0, depth = 20, K = depth - self1;
+  const bool f16 = r.precision == MMF_PREC_FAST, profile = r.profile;
+  mmf_simtopk_stats* stats = r.stats;
+  const int dpf = scan_b16c_dp(d), bcap = scan_b16c_cap(depth);
+
+  // ---- the one-pass entry's tables: served segments, column ranges, work table, position -> row gather; per row its segment's first row
+  std::vector<char> served((size_t)S, 0);
+  int64_t R = 0, n_pos = 0, unserved_rows = 0, n_served = 0;
+  for (int64_t g = 0; g < S; ++g) {
+    const int64_t ng = ptr[g + 1] - ptr[g];
+    if (ng == 0) continue;
+    if (ng - self1 < k) { unserved_rows += ng; continue; }
+    served[(size_t)g] = 1;
+    n_served += ng;
+    R += (ng + 127) / 128;
+    n_pos += (ng + 127) / 128 * 128;
+  }
+  if (R == 0) { set_error("%s: no served segment (internal invariant)", who); return MMF_E_INTERNAL; }
+  if (n_pos >= (int64_t(1) << 31)) { set_error("%s: the padded image of %lld positions is too large", who, (long long)n_pos); return MMF_E_UNSUPPORTED; }
+  int call_splits = 1, max_splits = 1;
+  {
+    const int forced = opts ? opts->col_splits : 0;
+    const auto fits = [&](int sp) { return 2 * sp * bcap <= 1024; };
+    if (forced > 0) { while (call_splits < forced && fits(2 * call_splits)) call_splits <<= 1; }
+    else { while (R * call_splits < 256 && 2 * call_splits <= combined_fast_seg_auto_splits() && fits(2 * call_splits)) call_splits <<= 1; }
+  }
+  std::vector<int32_t> sched, gather((size_t)n_pos, -1), col0((size_t)n, 0), served_rows;
+  served_rows.reserve((size_t)n_served);
+  {
+    int64_t pos = 0;
+    for (int64_t g = 0; g < S; ++g) {
+      if (!served[(size_t)g]) continue;
+      const int64_t ng = ptr[g + 1] - ptr[g], tiles = (ng + 127) / 128, t0 = pos / 128;
+      int sp = 1;
+      while (2 * sp <= call_splits && 2 * sp <= tiles) sp <<= 1;
+      if (sp > max_splits) max_splits = sp;
+      const int64_t tps = (tiles + sp - 1) / sp;
+      for (int64_t b = 0; b < ng; b += 128) {
+        for (int c = 0; c < sp; ++c) {
+          const int64_t tb = std::min(t0 + c * tps, t0 + tiles), te = std::min(tb + tps, t0 + tiles);
+          const int32_t e[8] = {(int32_t)(pos + b), (int32_t)(ptr[g] + b), (int32_t)std::min<int64_t>(ng - b, 128), (int32_t)tb, (int32_t)te,
+                                (int32_t)(uint32_t)(ptr[g] - pos), 2 * c, (int32_t)(ptr[g + 1] - 1)};
+          sched.insert(sched.end(), e, e + 8);
+        }
+      }
+      for (int64_t i = 0; i < ng; ++i) {
+        gather[(size_t)(pos + i)] = (int32_t)(ptr[g] + i);
+        col0[(size_t)(ptr[g] + i)] = (int32_t)ptr[g];
+        served_rows.push_back((int32_t)(ptr[g] + i));
+      }
+      pos += tiles * 128;
+    }
+  }
+  const int64_t grid = (int64_t)sched.size() / 8;
+  const int lists = 2 * max_splits;
+  const int64_t n_img = (n_pos + 255) / 256 * 256;
+
+  // ---- workspace (slot 0): the one-pass entry's, then floors, bookkeeping, segment offsets, ceilings and the staging rows ----------
+  const size_t stage = (size_t)n * K;
+  const size_t need = 2 * ws_bytes(n, 4) + ws_bytes(8, 4) + HalfImage::bytes(n_img, dpf) + ws_bytes(sched.size(), 4) + ws_bytes(n_pos, 4) +
+                      b16_lists_bytes(n, lists, bcap) + FlagBlock::bytes(n) + ws_bytes(2 * (size_t)n, 4) + 6 * ws_bytes(n, 4) + ws_bytes(64, 4) +
+                      ws_bytes(4, 4) + ws_bytes(stage, 8) + 2 * ws_bytes(stage, 4);
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* nf = ws.take<float>(n);
+  float* pn = ws.take<float>(n);
+  uint32_t* maxw = ws.take<uint32_t>(8);   // word 0: largest chain(f, f) of the batch, word 4: largest chain(p, p)
+  HalfImage C;
+  C.carve(ws, n_img, dpf);
+  int32_t* d_sched = ws.take<int32_t>(sched.size());
+  int32_t* d_gather = ws.take<int32_t>(n_pos);
+  const CandLists L = carve_b16_lists(ws, n, lists, bcap);
+  FlagBlock flags;
+  flags.carve(ws, n);
+  int32_t* seed = ws.take<int32_t>(2 * (size_t)n);
+  float* fkey = ws.take<float>(n); uint32_t* fid = ws.take<uint32_t>(n);
+  int32_t* certified = ws.take<int32_t>(n); int32_t* rescan_rows = ws.take<int32_t>(n);
+  int32_t* d_col0 = ws.take<int32_t>(n);
+  int32_t* d_rows = rescan_rows;   // (a pass's rescan list is read to the host before the sorted rows take its place)
+  float* ceil = ws.take<float>(n);
+  uint32_t* hist = ws.take<uint32_t>(64); uint32_t* rescan_count = ws.take<uint32_t>(4);
+  int64_t* sidx = ws.take<int64_t>(stage); float* sval = ws.take<float>(stage); float* skey = ws.take<float>(stage);
+  MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
+  MMF_HIP(hipMemsetAsync(maxw, 0, 32, s));
+  MMF_TRY(flags.zero(s));
+
+  EventTimer t_prep, t_scan, t_sel, t_fb;
+  MMF_TRY(t_prep.start(profile, s));
+  MMF_TRY(launch_row_scalars(F, n, d, MMF_F32, MMF_RBF, nf, maxw, s));
+  MMF_TRY(launch_row_scalars(P, n, dpos, MMF_F32, MMF_RBF, pn, maxw + 4, s));
+  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
+  MMF_TRY(upload_table(s, d_gather, gather.data(), (size_t)n_pos * 4));
+  MMF_TRY(upload_table(s, d_col0, col0.data(), (size_t)n * 4));
+  MMF_TRY(launch_prep_half_gather({F, n, d, MMF_F32, MMF_RBF, nf, maxw}, d_gather, n_pos, C, dpf, f16, s));
+  MMF_TRY(t_prep.stop(s));
+
+  // kq entries per row from column out_off0 on for `rows` (served rows, ascending: grouped by segment) by the exact pass, one
+  // gathered group per segment; `whole`: also the unserved segments, for what they have (pass 0 only)
+  auto exact_rows = [&](const std::vector<int32_t>& rows, int kq, int out_off0, bool floors_in, bool floors_out, bool whole) -> int {
+    ExactPass ex(r, nf, nf);
+    ex.same = true;
+    ex.P = P; ex.pn = pn; ex.dp = dpos; ex.lambda_g = lambda_g;
+    ex.out_stride = k; ex.out_off0 = out_off0;
+    ex.floors_in = floors_in; ex.floors_out = floors_out;
+    ex.row_floor_key = fkey; ex.row_floor_id = fid;
+    const int64_t cnt = (int64_t)rows.size();
+    for (int64_t g = 0, e = 0; g < S; ++g) {
+      const int64_t ng = ptr[g + 1] - ptr[g], e0 = e;
+      if (served[(size_t)g]) {
+        while (e < cnt && rows[(size_t)e] < ptr[g + 1]) ++e;
+        if (e > e0) ex.add(ExactGroup{e0, e - e0, true, ptr[g], ng, kq});
+      } else if (whole && ng > 0) {   // short of k admissible columns: its top-(n_g - self) first, then -1 / -inf
+        MMF_HIP(hipMemsetAsync(r.out_idx + ptr[g] * k, 0xff, (size_t)ng * k * 8, s));
+        MMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.out_val + ptr[g] * k), (int)0xff800000u, (size_t)ng * k, s));
+        if (ng - self1 > 0) ex.add(ExactGroup{ptr[g], ng, false, ptr[g], ng, (int)(ng - self1)});
+      }
+    }
+    if (ex.pieces.empty()) return MMF_OK;
+    ex.n_ids = cnt; ex.row_ids = d_rows;
+    Workspace aux;   // lists and f32 images in the second workspace slot
+    MMF_TRY(r.call.workspace(ex.image_bytes() + ex.list_bytes(), &aux, 1));
+    ExactLists B;
+    B.carve(aux, ex.rows_total, ex.list_words, ex.cap(), ex.floors());
+    if (cnt > 0) MMF_TRY(upload_table(s, d_rows, rows.data(), (size_t)cnt * 4));
+    if (floors_in) MMF_TRY(launch_floor_rebase(d_rows, cnt, fid, d_col0, false, s));
+    MMF_TRY(B.zero(s));
+    MMF_TRY(ex.run(aux, B));
+    if (floors_out) MMF_TRY(launch_floor_rebase(d_rows, cnt, fid, d_col0, true, s));
+    return MMF_OK;
+  };
+  // the served rows among `cnt` device rows, ascending (one more synchronisation)
+  auto served_of = [&](const int32_t* dev_rows, int64_t cnt, std::vector<int32_t>* out) -> int {
+    std::vector<int32_t> h((size_t)cnt);
+    if (cnt > 0) {
+      MMF_HIP(hipMemcpyAsync(h.data(), dev_rows, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipStreamSynchronize(s));
+    }
+    out->clear();
+    for (int32_t row : h) {
+      if (row < 0 || row >= n) { set_error("%s: flagged row %d outside the %lld rows (internal invariant)", who, row, (long long)n); return MMF_E_INTERNAL; }
+      const int64_t g = (int64_t)(std::upper_bound(ptr, ptr + S + 1, (int64_t)row) - ptr) - 1;
+      if (g >= 0 && g < S && served[(size_t)g]) out->push_back(row);
+    }
+    std::sort(out->begin(), out->end());
+    return MMF_OK;
+  };
+  // test hook, every pass: send the first rows down the exact paths (FastTail::run's)
+  auto debug_flag_rows = [&]() -> int {
+    if (const char* e = getenv("MMF_DEBUG_FLAG_ROWS")) {
+      const int64_t f = atoll(e);
+      if (f > 0) MMF_HIP(hipMemsetAsync(L.overflow, 1, (size_t)(f < n ? f : n) * 4, s));
+    }
+    return MMF_OK;
+  };
+
+  ScanB16Panel pnl;
+  pnl.seed = seed; pnl.seed_stride = n;
+  const ScanB16Problem sp(C, C, n, n, n_img, dpf, d, f16, MMF_RBF, depth);
+  const ScanB16Comb sc{P, pn, nf, maxw, maxw + 4, dpos, r.lambda, lambda_g};
+  SelectProblem q = r.select();
+  q.rx = nf; q.cy = nf; q.Pq = P; q.Pc = P; q.pnq = pn; q.pnc = pn; q.dp = dpos; q.lambda_g = lambda_g;
+  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count;
+
+  // ---- pass 0: K entries per row, k-wide rows, floors left ----------------------------------------------------------------------
+  // (every scan starts from the same reset; rows of unserved segments keep empty lists: the re-rank reports them every pass)
+  MMF_TRY(reset_b16_lists(L, n, lists, seed, n, s));
+  MMF_TRY(t_scan.start(profile, s));
+  MMF_TRY(launch_scan_b16c_seg(sp, sc, d_sched, grid, lists, L, pnl, s));
+  MMF_TRY(launch_scan_b16_audit(pnl, L.overflow, n, s));
+  MMF_TRY(debug_flag_rows());
+  MMF_TRY(t_scan.stop(s));
+  {
+    SelectProblem q0 = q;
+    q0.k = K; q0.out_stride = k; q0.cand_total = stats ? flags.cand_total : nullptr;
+    q0.floor_key_out = fkey; q0.floor_id_out = fid;
+    MMF_TRY(t_sel.start(profile, s));
+    MMF_TRY(launch_rerank_combined(q0, L, s));
+    MMF_TRY(t_sel.stop(s));
+  }
+  MMF_TRY(flags.read(stats != nullptr, s));
+  std::vector<int32_t> ex_rows;
+  MMF_TRY(served_of(flags.fail_rows, flags.h_fail4[0], &ex_rows));
+  const int64_t fallback0 = (int64_t)ex_rows.size();
+  MMF_TRY(t_fb.start(profile && (fallback0 > 0 || unserved_rows > 0), s));
+  MMF_TRY(exact_rows(ex_rows, K, 0, false, true, true));
+  MMF_TRY(t_fb.stop(s));
+  {
+    const int64_t overflow_rows = flags.h_fail4[1] < (uint32_t)fallback0 ? flags.h_fail4[1] : fallback0;
+    fill_stats(stats, r.precision, max_splits, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback0, overflow_rows,
+               fallback0 - overflow_rows, flags.h_tot);
+  }
+  anyk_record(info, 0, K, 0, fallback0);
+
+  // ---- later passes ---------------------------------------------------------------------------------------------------------------
+  const int64_t budget = n_served / anyk_short_div();
+  const AnykStage st{sidx, sval, skey, n, K, 0};
+  int done = K;
+  auto finish_exact = [&](int pass) -> int {   // every served row, everything that is left
+    MMF_TRY(exact_rows(served_rows, k - done, done, true, false, false));
+    if (stats) stats->fallback_rows += n_served;
+    anyk_record(info, pass, k - done, 0, n_served);
+    return MMF_OK;
+  };
+  for (int pass = 1; done < k; ++pass) {
+    if (pass >= MMF_FAST_ANYK_MAX_PASSES - 1) return finish_exact(pass);
+    MMF_TRY(launch_scan_b16c_ceilings(sp, sc, d_gather, n_pos, fkey, ceil, s));
+    MMF_TRY(reset_b16_lists(L, n, lists, seed, n, s));
+    MMF_TRY(flags.zero(s));
+    MMF_TRY(launch_scan_b16c_seg_ceil(sp, sc, d_sched, grid, lists, L, pnl, ceil, s));
+    MMF_TRY(launch_scan_b16_audit(pnl, L.overflow, n, s));
+    MMF_TRY(debug_flag_rows());
+    {
+      SelectProblem qs = q;   // K entries per row into the K-wide staging rows, with their keys
+      qs.k = K; qs.out_idx = sidx; qs.out_val = sval; qs.key_out = skey; qs.out_stride = K;
+      MMF_TRY(launch_rerank_combined_ext(qs, L, s));
+    }
+    MMF_TRY(launch_anyk_count(st, flags.fail_rows, flags.fail_count, fkey, fid, certified, hist, s));
+    uint32_t h[64];
+    MMF_HIP(hipMemcpyAsync(h, hist, (size_t)(K + 3) * 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    int64_t short_rows = 0;   // (unserved rows are always flagged, never short)
+    const int t = anyk_yield(h, std::min(K, k - done), budget, &short_rows);
+    if (t < 1) return finish_exact(pass);
+    MMF_TRY(launch_anyk_emit(st, certified, t, done, k, r.out_idx, r.out_val, fkey, fid, rescan_rows, rescan_count, s));
+    const int64_t listed = (int64_t)h[K + 1] + short_rows;   // the emit kernel's list: flagged rows (the unserved ones among them) and short rows
+    int64_t rescan = 0;
+    if (listed > unserved_rows) {
+      MMF_TRY(served_of(rescan_rows, listed, &ex_rows));
+      rescan = (int64_t)ex_rows.size();
+      MMF_TRY(exact_rows(ex_rows, t, done, true, done + t < k, false));
+      if (stats) stats->fallback_rows += rescan;
+    }
+    anyk_record(info, pass, t, (int)h[K + 2], rescan);
+    done += t;
+  }
+  return MMF_OK;
+}
+
+}  // namespace mmf
+
+extern "C" {
+
+int mmf_combined_fast_anyk_plan(int64_t d, int k, int exclude_self, int* scan_kk, int* first_yield, int* min_passes) {
+  if (d < 1 || k < 1) { set_error("combined_fast_anyk_plan: need d >= 1 and k >= 1 (got d = %lld, k = %d)", (long long)d, k); return MMF_E_INVALID; }
+  if (d > 4096) { set_error("combined_fast_anyk_plan: d = %lld > 4096 is beyond the 16-bit scan of the combined key", (long long)d); return MMF_E_UNSUPPORTED; }
+  const int self1 = exclude_self ? 1 : 0, kk = k + self1, per = 20 - self1;
+  const bool one = scan_b16c_supported(d, kk) != 0;
+  const int depth = one ? kk : 20;
+  if (scan_kk) *scan_kk = depth;
+  if (first_yield) *first_yield = depth - self1;
+  if (min_passes) *min_passes = one ? 1 : 1 + (k - (depth - self1) + per - 1) / per;
+  return one ? 0 : 1;
+}
+
+int mmf_simtopk_combined_fast_anyk(const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h, float lambda_g, int k,
+                                   int exclude_self, const int64_t* ptr_host, int64_t n_segments, int64_t* out_idx, float* out_val,
+                                   const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream,
+                                   mmf_fast_anyk_info* info) {
+  const char* who = "simtopk_combined_fast_anyk";
+  MMF_TRY(Call(who, device_id, hip_stream).on_device());
+  if (n < 0) { set_error("%s: n must be >= 0 (got %lld)", who, (long long)n); return MMF_E_INVALID; }
+  if (d < 1) { set_error("%s: d must be at least 1 (got %lld)", who, (long long)d); return MMF_E_INVALID; }
+  if (dp < 1) { set_error("%s: dp must be at least 1 (got %lld)", who, (long long)dp); return MMF_E_INVALID; }
+  if (k < 1) { set_error("%s: k must be at least 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (!(lambda_h >= 0.0f) || !std::isfinite(lambda_h)) { set_error("%s: lambda_h must be finite and >= 0 (got %g)", who, lambda_h); return MMF_E_INVALID; }
+  if (!(lambda_g >= 0.0f) || !std::isfinite(lambda_g)) { set_error("%s: lambda_g must be finite and >= 0 (got %g)", who, lambda_g); return MMF_E_INVALID; }
+  if (n > 0 && !F) { set_error("%s: F is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !P) { set_error("%s: P is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !out_idx) { set_error("%s: out_idx is NULL", who); return MMF_E_INVALID; }
+  if (n > 0 && !out_val) { set_error("%s: out_val is NULL", who); return MMF_E_INVALID; }
+  const bool segmented = ptr_host != nullptr || n_segments != 0;
+  if (segmented) MMF_TRY(check_offsets(who, "ptr_host", ptr_host, n_segments, 0, 0, n));
+  if (dp > 8) { set_error("%s: dp = %lld > 8 is not supported", who, (long long)dp); return MMF_E_UNSUPPORTED; }
+  if (d > 4096) { set_error("%s: d = %lld > 4096 is not supported (mmf_simtopk_combined takes any d)", who, (long long)d); return MMF_E_UNSUPPORTED; }
+  if (n >= (int64_t)1 << 31) { set_error("%s: n must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  const int asked = opts ? opts->precision : MMF_PREC_AUTO;
+  if (asked != MMF_PREC_AUTO && asked != MMF_PREC_EXACT && asked != MMF_PREC_FAST && asked != MMF_PREC_FAST_BF16) {
+    set_error("%s: precision %d: MMF_PREC_AUTO, _EXACT, _FAST (f16 operands) or _FAST_BF16", who, asked);
+    return MMF_E_INVALID;
+  }
+  MMF_TRY(check_pow2_splits(who, opts));
+  if (info) memset(info, 0, sizeof(*info));
+  if (n == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return MMF_OK; }
+
+  const int self1 = exclude_self ? 1 : 0, kk = k + self1;
+  const int prec = asked == MMF_PREC_AUTO ? MMF_PREC_FAST : asked;
+  const int64_t one_graph[2] = {0, n};
+  const int64_t* ptr = segmented ? ptr_host : one_graph;
+  const int64_t S = segmented ? n_segments : 1;
+  mmf_simtopk_stats own_stats;   // info reports the first pass's flagged rows, which the call counts in its stats
+  mmf_simtopk_stats* st = stats ? stats : (info ? &own_stats : nullptr);
+  bool any_served = false;       // a segment with rows and at least k admissible columns
+  for (int64_t g = 0; g < S; ++g) any_served |= (ptr[g + 1] - ptr[g] > 0 && ptr[g + 1] - ptr[g] - self1 >= k);
+  mmf_simtopk_opts one{};
+  if (opts) one = *opts;
+  if (prec == MMF_PREC_EXACT || (kk > 20 && !any_served)) {
+    // the drivers behind mmf_simtopk_combined_anyk (they also answer a batch in which no segment has k admissible columns: the
+    // exact launch loop would take every segment anyway)
+    one.precision = MMF_PREC_EXACT;
+    if (!segmented) {
+      MMF_TRY(run_simtopk_combined(who, F, P, n, d, dp, lambda_h, lambda_g, k, exclude_self, one_graph, 1, out_idx, out_val, &one, st, device_id,
+                                   hip_stream));
+    } else {
+      if (st) memset(st, 0, sizeof(*st));
+      Request r{Call(who, device_id, hip_stream), F, n, F, n, d, MMF_F32, MMF_RBF, lambda_h, k, exclude_self, 0, 0, out_idx, out_val, st,
+                opts && opts->profile};
+      r.kk = kk;
+      r.precision = MMF_PREC_EXACT;
+      MMF_TRY(r.call.begin());
+      MMF_TRY(run_segmented_exact(r, true, ptr_host, ptr_host, n_segments, &one, P, (int)dp, lambda_g));
+    }
+    anyk_record(info, 0, k, 0, 0);
+    return MMF_OK;
+  }
+  if (kk <= 20) {   // one pass serves: the call IS the one-pass entry
+    one.precision = prec;
+    if (!segmented) MMF_TRY(run_simtopk_combined_fast(who, F, P, n, d, dp, lambda_h, lambda_g, k, exclude_self, out_idx, out_val, &one, st, device_id, hip_stream));
+    else MMF_TRY(run_simtopk_combined_fast_segmented(who, F, P, n, d, dp, lambda_h, lambda_g, k, exclude_self, ptr_host, n_segments, out_idx, out_val, &one,
+                                                     st, device_id, hip_stream));
+    anyk_record(info, 0, k, 0, st ? st->fallback_rows : 0);
+    return MMF_OK;
+  }
+  if (st) memset(st, 0, sizeof(*st));
+  Request r{Call(who, device_id, hip_stream), F, n, F, n, d, MMF_F32, MMF_RBF, lambda_h, k, exclude_self, 0, 0, out_idx, out_val, st,
+            opts && opts->profile};
+  r.kk = kk;
+  r.precision = prec;
+  MMF_TRY(r.call.begin());
+  return combined_fast_anyk_run(r, P, (int)dp, lambda_g, ptr, S, opts, info);
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 #include "../../include/ext/mmf_hg_cross_seg_anyk.h"
 #include "../../include/ext/mmf_hg_cross_segw_anyk.h"
 #include "../../include/ext/mmf_hg_segw_anyk.h"
+#include "../../include/ext/mmf_hg_topk16_anyk.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -333,6 +334,10 @@ int launch_select(const SelectProblem& p, const CandLists& L, hipStream_t s);
 // out_off are left alone, the entry of rank k - 1 leaves its key and LOCAL id in floor_key_out / floor_id_out, and only the
 // last pass (no floor_key_out) pads
 int launch_rerank_combined(const SelectProblem& p, const CandLists& L, hipStream_t s);
+// mmf_topk_anyk.hip: the same re-rank with launch_select's `row_ids` (gathered rows: lists, overflow words and floor slots by list
+// position, F, P, chains, self, outputs and the fail list by row) and `key_out` (the canonical key of every emitted entry) — the
+// passes of mmf_simtopk_combined_fast_anyk; always the pass form: only a call without floor_key_out pads
+int launch_rerank_combined_ext(const SelectProblem& p, const CandLists& L, hipStream_t s);
 // mmf_api.hip: mmf_simtopk_combined behind its host checks (ptr: host offsets of n_seg >= 1 segments) — ExactPass over the segments
 int run_simtopk_combined(const char* who, const float* F, const float* P, int64_t n, int64_t d, int64_t dp, float lambda_h, float lambda_g,
                          int k, int exclude_self, const int64_t* ptr, int64_t n_seg, int64_t* out_idx, float* out_val,
@@ -514,6 +519,13 @@ int launch_scan_b16c(const ScanB16Problem& p, const ScanB16Comb& c, int col_spli
 // p.m_pad: positions of the one image, every segment padded to whole tiles of 128; `lists` = 2 x the largest range count
 int launch_scan_b16c_seg(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, const CandLists& L,
                          const ScanB16Panel& pn, hipStream_t s);
+// The later passes of mmf_simtopk_combined_fast_anyk: the same launch with a ceiling per row of F — an approximate
+// key above ceil[row] reaches no list, threshold or seed (32-entry lists only) — and the kernel that turns the rows' floors (canonical
+// combined keys, by row of F; -inf: no column left) into ceilings: gather [n_pos] maps an image position to its row of F (-1: padding)
+int launch_scan_b16c_seg_ceil(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, const CandLists& L,
+                              const ScanB16Panel& pn, const float* ceil, hipStream_t s);
+int launch_scan_b16c_ceilings(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* gather, int64_t n_pos, const float* floor_key,
+                              float* ceil, hipStream_t s);
 // the same scan for queries that are not the candidates, or only some of them (mmf_simtopk_combined_xy): the table
 // names, per workgroup, a block of 128 queries anywhere in the one image and a range of CANDIDATE tiles.  c.P / c.pn / c.nf are in
 // the joint numbering of the table (candidates first); the lists, threshold buffers and margins hold only the p.n_rows queries,

@@ -68,6 +68,26 @@
 // candidates — all a query's bound needs — so every inequality holds pair by pair with m0_i at least the value a self call over
 // the union would use, and a query's band is taken among the candidate columns only.  For a slice the union is the candidates,
 // so m0_i, the approximate keys and therefore the flagged rows are those of the self call on the candidates.
+//
+// Ceilings (mmf_simtopk_combined_fast_anyk, include/ext/mmf_hg_topk16_anyk.h): a later pass of a call with
+// k + self > 20 scans for the columns that rank strictly AFTER the row's floor (fk_i, fid_i) — the last entry the row has
+// emitted — in the total order (key descending, id ascending).  Call that set S_i.  The CEIL kernel turns every approximate key
+// above a per-row ceiling into -inf; the ceiling must never mask a member of S_i.  From the error margin above, with
+//   e0_i = a (E1_i + E2_i) + u' (lambda_h n_i + pb_i)   (so that |A_ij - key_ij| <= e0_i + 3 u' |A_ij|; m0_i >= 2.002 e0_i),
+// a column j of S_i has key_ij <= fk_i, hence A_ij <= h + 3 u' |A_ij| with h = fk_i + e0_i:
+//   A_ij >= 0:      A_ij (1 - 3 u') <= h, so h >= 0 and A_ij <= h / (1 - 3 u') <= h + 3.1 u' h;
+//   h < A_ij < 0:   |A_ij| < |h|, so A_ij < h + 3 u' |h|;     A_ij <= h: nothing to show.
+// Either way A_ij <= h + 3.1 u' |h| <= h + 3.2 u |h| in real numbers.  comb_ceil_kernel takes e0 = m0_i / 2 (exact halving of the
+// word the scan itself uses; m0_i / 2 >= 1.001 e0_i covers the roundings of forming it, as in the scan), hf = fl(fk_i + e0)
+// (h <= hf + u |hf|, |h| <= (1 + u) |hf|, so the bound is at most hf + 4.3 u |hf|) and returns the float above
+// fl(hf + fl(6 u |hf|)) >= hf + (6 (1 - u) - 1.01) u |hf|.  fk_i = -inf (the row has no column left) gives -inf: everything is
+// masked.  The distance from the floor to the ceiling is e0 + 6 u |h| plus two ulps — about half of margin_i(fk_i).
+// What gets through without belonging to S_i — a ghost: a column the row has already emitted, or the row itself — has
+// key_ij >= fk_i: in the exact order every ghost stands before every member of S_i, so in a re-ranked row the ghosts are a
+// prefix; and key_ij <= A_ij + e0_i + 3 u' |A_ij| <= ceiling + e0_i + 3 u' |ceiling|, within about margin_i(fk_i) of the floor.
+// The lists' guarantee (the band through margin_i) is a statement about ANY set of columns, here the unmasked ones, so the
+// re-rank certifies the best entries among them exactly as in a first pass.  The coarse test (i) still bounds the unmasked keys
+// from above (masking only lowers keys), so it stays sound; it is merely less sharp for a row whose best columns are masked.
 #include <math.h>
 #include <string.h>
 
@@ -133,6 +153,7 @@ struct ScanB16CArgs {
   float* cand_keys;          // approximate keys of the entries, or nullptr
   float* margin_out;         // [n_rows] m0_i, written with cand_keys
   const int32_t* sched;      // SEG kernels only: [grid][CSEG_ENTRY] work table (launch_scan_b16c_seg)
+  const float* ceil;         // CEIL kernels only: [n_rows] per-row ceiling of the approximate key, by row of F (comb_ceil_kernel)
 };
 
 // One entry of the segmented work table (the layout of mmf_scan_b16w.hip's, plus the clamp row): a workgroup = one row block of
@@ -269,8 +290,11 @@ constexpr size_t scan_b16c_lds(int cap) {
 
 // SEG (segmented calls, launch_scan_b16c_seg): the workgroup's row block, column range, id offset, list slot and clamp rows come
 // from the work table a.sched instead of blockIdx / col_splits; everything else is shared.
-template <bool F16, int CAP, bool SEG = false>
-__global__ __launch_bounds__(C_NT, 1) void scan_b16c_kernel(ScanB16CArgs a) {
+// The kernel's body, inlined into the kernels below.  CEIL (scan_b16c_ceil_kernel: a later pass of mmf_simtopk_combined_fast_anyk,
+// launch_scan_b16c_seg_ceil): an approximate key above its row's ceiling a.ceil becomes -inf in stage (ii) of the epilogue, before
+// anything but the coarse test (i) has seen it; CEIL = false is the kernel as it was.
+template <bool F16, int CAP, bool SEG, bool CEIL>
+__device__ __forceinline__ void scan_b16c_body(ScanB16CArgs a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   char* stages = smem;                                                   // [2][C_STAGEB]
   float* cbs = reinterpret_cast<float*>(smem + 2 * C_STAGEB);            // [2][C_CT] bias of the tile being accumulated / the next
@@ -531,6 +555,20 @@ __global__ __launch_bounds__(C_NT, 1) void scan_b16c_kernel(ScanB16CArgs a) {
           if (a.dpp <= 2) keys(std::integral_constant<int, 2>{});
           else if (a.dpp <= 4) keys(std::integral_constant<int, 4>{});
           else keys(std::integral_constant<int, 8>{});
+          if constexpr (CEIL) {
+            // the two queries' ceilings, fetched here — only a sub-tile that passed (i) pays for them — by the clamped rows of
+            // F the positions above came from
+            int64_t qa = (SEG ? row0 : q0) + 32 * wave + c16, qb = qa + 16;
+            const int64_t qlast = SEG ? row0 + nq - 1 : m - 1;
+            if (qa > qlast) qa = qlast;
+            if (qb > qlast) qb = qlast;
+            const float c0 = a.ceil[qa], c1 = a.ceil[qb];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              A0[e] = A0[e] > c0 ? kNegInf : A0[e];
+              A1[e] = A1[e] > c1 ? kNegInf : A1[e];
+            }
+          }
           const float m0k = fmaxf(fmaxf(fmaxf(A0[0], A0[1]), fmaxf(A0[2], A0[3])), fmaxf(fmaxf(A0[4], A0[5]), fmaxf(A0[6], A0[7])));
           const float m1k = fmaxf(fmaxf(fmaxf(A1[0], A1[1]), fmaxf(A1[2], A1[3])), fmaxf(fmaxf(A1[4], A1[5]), fmaxf(A1[6], A1[7])));
           if (__any((m0k >= thr_q0) || (m1k >= thr_q1))) {
@@ -574,6 +612,17 @@ __global__ __launch_bounds__(C_NT, 1) void scan_b16c_kernel(ScanB16CArgs a) {
     if (list.lost > kNegInf) atomicMax(a.lost + lrow, comb_enc(list.lost));
     if (bad_scale && half == 0) atomicMax(a.lost + lrow, comb_enc(kFltMax));   // no usable key: the exact pass answers the row
   }
+}
+
+template <bool F16, int CAP, bool SEG = false>
+__global__ __launch_bounds__(C_NT, 1) void scan_b16c_kernel(ScanB16CArgs a) {
+  scan_b16c_body<F16, CAP, SEG, false>(a);
+}
+
+// the table-driven scan with 32-entry lists under per-row ceilings (the header's "Ceilings")
+template <bool F16>
+__global__ __launch_bounds__(C_NT, 1) void scan_b16c_ceil_kernel(ScanB16CArgs a) {
+  scan_b16c_body<F16, C_CAP_BIG, true, true>(a);
 }
 
 // Column splits: wide_seed_union_kernel with margin_i(t).  One wave per row takes the kk-th best key pk of everything the
@@ -715,6 +764,111 @@ int launch_scan_b16c_seg(const ScanB16Problem& p, const ScanB16Comb& c, const in
                        p.kk, pn.seed, p.n_rows);
     MMF_LAUNCH_CHECK();
   }
+  return MMF_OK;
+}
+
+// The same launch under per-row ceilings (a later pass of mmf_simtopk_combined_fast_anyk; the header's
+// "Ceilings"): launch_scan_b16c_seg's checks and arguments, 32-entry lists only, ceil [p.n_rows] by row of F (from
+// launch_scan_b16c_ceilings).  The seed union sees masked lists only.
+int launch_scan_b16c_seg_ceil(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, const CandLists& L,
+                              const ScanB16Panel& pn, const float* ceil, hipStream_t s) {
+  if (grid <= 0 || p.n_rows <= 0) return MMF_OK;
+  if (!scan_b16c_supported(p.d, p.kk) || p.dp != scan_b16c_dp(p.d) || p.metric != MMF_RBF) {
+    set_error("scan_b16c_seg_ceil: d = %lld (padded %d), k + self = %d, metric %d outside 1 <= d <= 4096, k + self <= 20, MMF_RBF", (long long)p.d,
+              p.dp, p.kk, p.metric);
+    return MMF_E_INTERNAL;
+  }
+  if (p.ZQ != p.ZC || p.n_rows != p.m) { set_error("scan_b16c_seg_ceil: one image against itself only"); return MMF_E_INTERNAL; }
+  if (!c.P || !c.pn || !c.nf || !c.max_nf || !c.max_pn || c.dp < 1 || c.dp > 8) { set_error("scan_b16c_seg_ceil: positions, chains and maxima (1 <= dp <= 8) missing"); return MMF_E_INTERNAL; }
+  const int col_splits = lists / 2;
+  if (lists < 2 || lists != 2 * col_splits || (col_splits & (col_splits - 1)) != 0) {
+    set_error("scan_b16c_seg_ceil: %d lists per row are no power-of-two number of pairs", lists);
+    return MMF_E_INTERNAL;
+  }
+  if (!sched || !ceil) { set_error("scan_b16c_seg_ceil: work table or ceilings missing"); return MMF_E_INTERNAL; }
+  if (!pn.seed || pn.seed_stride < p.n_rows) { set_error("scan_b16c_seg_ceil: threshold buffers missing"); return MMF_E_INTERNAL; }
+  if (lists != L.lists) { set_error("scan_b16c_seg_ceil: %d lists per row for %d column splits", L.lists, col_splits); return MMF_E_INTERNAL; }
+  if (L.cap != C_CAP_BIG) { set_error("scan_b16c_seg_ceil: list capacity %d, expected %d", L.cap, C_CAP_BIG); return MMF_E_INTERNAL; }
+  if (col_splits > 1 && (!L.keys || !L.margin)) { set_error("scan_b16c_seg_ceil: column splits need the lists' keys and margins"); return MMF_E_INTERNAL; }
+  if (p.m_pad % C_CT != 0) { set_error("scan_b16c_seg_ceil: image of %lld positions is no whole number of tiles", (long long)p.m_pad); return MMF_E_INTERNAL; }
+  ScanB16CArgs a{};
+  a.Z = p.ZC; a.cb = p.cb; a.q_zn = p.q_zn; a.q_rn = p.q_rn; a.q_un = p.q_un; a.maxima = p.maxima;
+  a.nf = c.nf; a.P = c.P; a.pn = c.pn; a.max_nf = c.max_nf; a.max_pn = c.max_pn; a.lambda_h = c.lambda_h; a.lambda_g = c.lambda_g; a.dpp = c.dp;
+  a.n_rows = p.n_rows; a.kk = p.kk; a.d = (int)p.d; a.dp = p.dp;
+  a.tiles_total = p.m_pad / C_CT; a.tiles_per_split = a.tiles_total; a.col_splits = 1;   // unused: the table carries the ranges
+  a.lists_total = L.lists;
+  a.seed = pn.seed; a.lost = pn.seed + pn.seed_stride;
+  a.cand_cnt = L.cnt; a.cand_ids = L.ids; a.cand_keys = L.keys; a.margin_out = L.margin;
+  a.sched = sched; a.ceil = ceil;
+  const size_t lds = scan_b16c_lds(C_CAP_BIG);
+  const auto kern = p.f16 ? scan_b16c_ceil_kernel<true> : scan_b16c_ceil_kernel<false>;
+  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C_NT), lds, s, a);
+  MMF_LAUNCH_CHECK();
+  if (col_splits > 1) {
+    hipLaunchKernelGGL(comb_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
+                       p.kk, pn.seed, p.n_rows);
+    MMF_LAUNCH_CHECK();
+  }
+  return MMF_OK;
+}
+
+namespace {
+
+// One thread per image position (the header's "Ceilings"): position q holds row gather[q] of F (-1: padding).  m0 is the scan's
+// own word — the formula of scan_b16c_kernel on the same operands, restated here so that the scan's instantiations stay as they are.
+__global__ __launch_bounds__(256) void comb_ceil_kernel(const float* q_zn, const float* q_rn, const float* q_un, const uint32_t* maxima,
+                                                        const float* nf, const float* pn, const uint32_t* max_nf, const uint32_t* max_pn,
+                                                        float lambda_h, float lambda_g, int dpp, int dp, int d, const int32_t* gather,
+                                                        int64_t n_pos, const float* floor_key, float* ceil) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n_pos) return;
+  const int64_t row = gather[q];
+  if (row < 0) return;
+  float av;
+  {
+    const float mx = __builtin_sqrtf(__uint_as_float(max_nf[0]));
+    int ex = 0;
+    if (mx > 0.0f && mx < __builtin_huge_valf()) (void)frexpf(mx, &ex); else ex = 9;
+    int e = 9 - ex;
+    e = e < -100 ? -100 : (e > 100 ? 100 : e);
+    const bool bad_scale = e < -60 || e > 60;   // such a call's rows are all flagged by the scan: any finite ceiling will do
+    const float inv_s = ldexpf(1.0f, bad_scale ? 0 : -e);
+    av = (2.0f * lambda_h * inv_s) * inv_s;
+    if (bad_scale) av = 0.0f;
+  }
+  const float ZB = __uint_as_float(maxima[0]), RB = __uint_as_float(maxima[1]);
+  const float UB = __uint_as_float(maxima[2]), CB = __uint_as_float(maxima[3]);
+  const float zn = q_zn[q], rn = q_rn[q], un = q_un[q];
+  const float g_acc = (float)(dp + 8) * C_U;
+  const float g_chain = (float)(d + 2) * C_U;
+  const float e1 = rn * ZB + un * RB + g_acc * (zn * ZB + CB);
+  const float e2 = g_chain * un * UB + 2.3841858e-7f * (un * un + UB * UB);
+  const float ae = av * (e1 + e2);
+  const float rc = -lambda_h * nf[row];
+  const float egb = lambda_g * (float)(2 * dpp + 4) * C_U * 1.01f * (pn[row] + __uint_as_float(max_pn[0]));
+  const float pb = ae * 1.01f + egb;
+  const float m0 = 2.002f * (ae + 1.01f * C_U * (__builtin_fabsf(rc) + 2.0f * pb)) + 1e-30f;
+  const float fk = floor_key[row];
+  float cl = kNegInf;
+  if (fk > kNegInf) {
+    const float hf = fk + 0.5f * m0;
+    cl = nextafterf(hf + 6.0f * C_U * __builtin_fabsf(hf), __builtin_huge_valf());
+  }
+  ceil[row] = cl;
+}
+
+}  // namespace
+
+// ceil[row] for every row of F an image position holds (gather [n_pos]: position -> row, -1 padding; the others keep what they
+// have — the scan never reads them), from the row's floor key; p / c: what launch_scan_b16c_seg_ceil will be given.
+int launch_scan_b16c_ceilings(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* gather, int64_t n_pos, const float* floor_key,
+                              float* ceil, hipStream_t s) {
+  if (n_pos <= 0) return MMF_OK;
+  if (!gather || !floor_key || !ceil || n_pos > p.m_pad) { set_error("scan_b16c_ceilings: gather table, floors and ceilings for at most %lld positions", (long long)p.m_pad); return MMF_E_INTERNAL; }
+  hipLaunchKernelGGL(comb_ceil_kernel, dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, s, p.q_zn, p.q_rn, p.q_un, p.maxima, c.nf, c.pn,
+                     c.max_nf, c.max_pn, c.lambda_h, c.lambda_g, c.dp, p.dp, (int)p.d, gather, n_pos, floor_key, ceil);
+  MMF_LAUNCH_CHECK();
   return MMF_OK;
 }
 

@@ -499,8 +499,10 @@ int launch_scan_f32(const ScanProblem& p, const CandLists& L, hipStream_t s, int
   a.metric = p.metric;
   { const char* e = getenv("MMF_F32_DEBUG"); a.debug = e ? atoi(e) : 0; }
   if (p.Pc) {   // the combined key (mmf_simtopk_combined)
-    if (!p.Pq || !p.pnq || !p.pnc || p.dp < 1 || p.dp > 8 || p.metric != MMF_RBF || p.row_ids) {
-      set_error("scan_f32: combined key needs both sides' positions and chains, 1 <= dp <= 8 (got %d), MMF_RBF and no gathered rows", p.dp);
+    // (gathered rows — p.row_ids — are served: the kernel takes a query's scalar, position and chain by row and its image, floor
+    // and lists by position; Pq / pnq are then the whole query side's, as rx is)
+    if (!p.Pq || !p.pnq || !p.pnc || p.dp < 1 || p.dp > 8 || p.metric != MMF_RBF) {
+      set_error("scan_f32: combined key needs both sides' positions and chains, 1 <= dp <= 8 (got %d) and MMF_RBF", p.dp);
       return MMF_E_INTERNAL;
     }
     a.P = p.Pc; a.Pq = p.Pq; a.pnq = p.pnq; a.pnc = p.pnc; a.dp = p.dp; a.neg_lambda_g = -p.lambda_g;
