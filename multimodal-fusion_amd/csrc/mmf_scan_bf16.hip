@@ -232,12 +232,12 @@ struct ScanB16Args {
   int spill_stacks;          // one list pair per row: the two lanes fill the row's slots from both ends, no counter (SpillSink)
   const int32_t* sched;      // SEG / SYM kernels only: [grid][SEG_ENTRY] work table (launch_scan_b16_seg, launch_scan_b16_sym)
   // SYM == 2 (the symmetric launch of a scan of X against itself, launch_scan_b16_sym): a value G_ij that reaches the
-  // threshold of its CANDIDATE row j is appended to the wave's private log as (j, i, G); sym_scatter_kernel files the logs
-  // into the rows' lists afterwards
+  // threshold of its CANDIDATE row j sends its lane's hit record (thresholds and values of the candidate block) to the wave's private
+  // log; sym_scatter_kernel picks the passing values out of the records and files them into the rows' lists afterwards
   float* sym_thr;            // [m_pad] threshold of every candidate row (sym_thr_kernel: seed[] decoded; +inf for padding rows)
   int sym_live;              // the rows' workgroups keep raising sym_thr[] while the symmetric launch runs (sync_seed)
-  uint32_t* sym_log;         // [grid * NW][sym_log_cap][4]
-  uint32_t* sym_log_cnt;     // [grid * NW] entries written (zeroed by the host; an idle workgroup writes nothing)
+  uint32_t* sym_log;         // [grid * NW][sym_log_cap][16]: hit records (MMF_SYM_RECORDS=0: [sym_log_cap][4] entries)
+  uint32_t* sym_log_cnt;     // [grid * NW] records written (zeroed by the host; an idle workgroup writes nothing)
   int sym_log_cap;
   // XSEG kernels only (launch_scan_b16_xseg): [n_pad][2] per query row, first row and row count of the columns the row may not
   // take (its own segment's rows of Y; padding rows: 0, 0)
@@ -320,14 +320,20 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 // block and its columns — two tile ranges walked as one — come from the work table a.sched.  SYM == 1 is otherwise the plain
 // kernel.  SYM == 2 serves both directions of every pair it multiplies: beside the query-side filter, each value is tested
 // against the threshold of its CANDIDATE row (32 floats per tile, DMAed into LDS with the tile's biases), and a value that
-// passes is appended to a log private to the wave — a ballot and a popcount place it: one store, no atomic, no returned value to
-// wait for (the store itself retires with the iteration's vmcnt(0), like the tile DMA).
+// passes makes its lane append a hit record to a log private to the wave — a ballot and a popcount place it: four stores, no atomic, no
+// returned value to wait for (the stores retire with the iteration's vmcnt(0), like the tile DMA).
 #ifndef MMF_SYM_ABLATE
 #define MMF_SYM_ABLATE 0   // timing-only variants of the SYM == 2 kernel's candidate direction (sym_offer below)
 #endif
 #ifndef MMF_SYM_EARLY_THR
 #define MMF_SYM_EARLY_THR 1   // SYM == 2: 1 = ONE 64-lane threshold DMA per iteration for both tiles of the next group, issued between
 #endif                        // the iteration's two chains; 0 = one 32-lane DMA behind each chain (the placement before; scripts/ab_build.sh)
+#ifndef MMF_SYM_RECORDS
+#define MMF_SYM_RECORDS 1     // SYM == 2: 1 = a lane with a hit appends one 64-byte record per candidate block (its four thresholds and eight
+#endif                        // values; sym_scatter_kernel does the per-value test), 0 = the per-value entry path before it (scripts/ab_build.sh)
+#ifndef MMF_SYM_SCALAR_ANY
+#define MMF_SYM_SCALAR_ANY 1  // SYM != 0: 1 = the hot tests branch on the ballot's scalar pair, 0 = on __any (scripts/ab_build.sh)
+#endif
 // The SYM kernels have no instrumented (DBG) build; their query-side list code is measured with two build switches (scripts/ab_build.sh):
 #ifndef MMF_SYM_ABLATE_Q
 #define MMF_SYM_ABLATE_Q 0    // timing only, the results are WRONG: bit 0 / bit 1 = the SYM == 1 / SYM == 2 kernel never enters the query-side list code
@@ -495,6 +501,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       if (rose && a.sym_live) __hip_atomic_store(a.sym_thr + qpos, list.thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   };
+  // the wave-uniform branches of the SYM kernels' hot tests: on scalar registers.  __any of an OR of compares goes through a VGPR
+  // (v_cndmask 0, 1 + v_cmp_ne on top of the s_or_b64 that already holds the answer), and so does the ballot of such an OR; the
+  // ballot of ONE compare is the compare's own SGPR pair, so the tests OR their compares' ballots (sym_hits) and branch on that.
+  // (The empty asm keeps the pair where it is: left to itself the compiler folds `ballot != 0` back into the VGPR form.)
+  constexpr bool SCALAR_ANY = SYM != 0 && MMF_SYM_SCALAR_ANY != 0;
+  auto sym_hits = [&](unsigned long long b) -> bool { asm("" : "+s"(b)); return b != 0ull; };
   if (a.share) sync_seed();
   // a wave whose queries all start from a published threshold skips the cold-start treatment
   const bool seeded = !__any(list.thr == -kFltMax);
@@ -718,7 +730,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   float ablate_keep = -kFltMax;   // MMF_SYM_ABLATE_Q bit 2: the tile maxima folded into one value, stored once at the end
   auto filter = [&](const Acc& acc, int tt, float m0, float m1) {
     if (SYM != 0 && (MMF_SYM_ABLATE_Q & SYM) != 0 && (MMF_SYM_ABLATE_Q & 4) != 0) ablate_keep = fmaxf(ablate_keep, fmaxf(m0, m1));
-    if (__builtin_expect(!(DBG && (a.debug & 1)) && !(SYM != 0 && (MMF_SYM_ABLATE_Q & SYM) != 0) && __any((m0 >= thr_q0) || (m1 >= thr_q1)), 0)) {
+    if (__builtin_expect(!(DBG && (a.debug & 1)) && !(SYM != 0 && (MMF_SYM_ABLATE_Q & SYM) != 0) &&
+                         (SCALAR_ANY ? sym_hits(__builtin_amdgcn_ballot_w64(m0 >= thr_q0) | __builtin_amdgcn_ballot_w64(m1 >= thr_q1))
+                                     : __any((m0 >= thr_q0) || (m1 >= thr_q1)) != 0), 0)) {
       uint32_t id0 = id_base + (uint32_t)tt * B_CT;
       if constexpr (SYM != 0) id0 += (tt >= sym_n1) ? (uint32_t)(sym_skip * B_CT) : 0u;   // behind the first range: sym_skip tiles further on
       // this lane's query gets its 16 candidates together: its own 8 plus the 8 the partner lane holds
@@ -781,17 +795,67 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
 
   // SYM == 2, the candidate direction: right behind a tile's chain (its stage of thresholds is not refilled before the next
   // barrier), the lane's 16 values against the thresholds of their candidate rows — 8 v_max + 8 compares, two LDS reads.
-  // On a hit every passing value goes to the wave's log: position = the wave's running count + the lane's rank in the ballot;
+  // On a hit the wave's log gets hit records (MMF_SYM_RECORDS, below).  The entry path before them (MMF_SYM_RECORDS=0):
+  // every passing value goes to the wave's log: position = the wave's running count + the lane's rank in the ballot;
   // a full log flags the candidate row for the exact rescan (audit_kernel).  Almost every hit is ONE value in ONE lane, so
   // the path costs one round: each lane folds its passing values (validity included) into a 16-bit mask, and a round takes
   // the lowest set bit of every lane that has one — one ballot and one store per round, as many rounds as the busiest lane
   // has values.
   // MMF_SYM_ABLATE (scripts/ab_build.sh, timing only, the results are WRONG): 1 = the test without the hit path, 2 = neither
-  // the test nor the threshold DMA, 3 = the hit path without its log stores (the logs then read as empty).
+  // the test nor the threshold DMA, 3 = the hit path without its log stores (the logs then read as empty; with records: the ballots and positions without the record stores).
   uint32_t sym_wcnt = 0;
   auto sym_offer = [&](const Acc& x, int tt, const float* th) {
     const f32x4 th0 = *reinterpret_cast<const f32x4*>(th + 4 * g);
     const f32x4 th1 = *reinterpret_cast<const f32x4*>(th + 16 + 4 * g);
+    if constexpr (MMF_SYM_RECORDS != 0) {
+      // Hit records: the wave does not need to know WHICH value passed — sym_scatter_kernel tests every value of a record against the
+      // thresholds recorded with it (and against the rows' validity), where nobody waits at a barrier.  So the hit path is one ballot
+      // per candidate block with a hit and, per lane with a hit, one 64-byte record: header (first of the lane's four candidate rows,
+      // first of its two query rows, two reserved words), the block's four thresholds as tested, the lane's eight values of the block.
+      // Position = the wave's running count + the lane's rank in the ballot, the second block's records behind the first's.
+      bool any0 = false, any1 = false;
+      unsigned long long hit0 = 0ull, hit1 = 0ull;     // the ballots of any0 / any1, kept as the compares' own SGPR pairs
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool p0 = fmaxf(x.t[0][0][j], x.t[0][1][j]) >= th0[j], p1 = fmaxf(x.t[1][0][j], x.t[1][1][j]) >= th1[j];
+        any0 |= p0; any1 |= p1;
+        if constexpr (SCALAR_ANY) { hit0 |= __builtin_amdgcn_ballot_w64(p0); hit1 |= __builtin_amdgcn_ballot_w64(p1); }
+      }
+      if (__builtin_expect((SCALAR_ANY ? sym_hits(hit0 | hit1) : __any(any0 || any1) != 0) && (MMF_SYM_ABLATE != 1 || a.sym_log_cap < 0), 0)) {
+        const uint32_t cj0 = id_base + (uint32_t)tt * B_CT + ((tt >= sym_n1) ? (uint32_t)(sym_skip * B_CT) : 0u) + 4u * (uint32_t)g;
+        const uint32_t qi0 = (uint32_t)(q0 + 32 * qw + c16);
+        u32x4* lg = reinterpret_cast<u32x4*>(a.sym_log) + ((size_t)blockIdx.x * NW + wave) * (size_t)a.sym_log_cap * 4;
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+          const bool hit = cb ? any1 : any0;
+          const unsigned long long b = SCALAR_ANY ? (cb ? hit1 : hit0) : __ballot(hit);
+          if (hit) {
+            const uint32_t at = sym_wcnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+            if (at < (uint32_t)a.sym_log_cap) {
+              if (MMF_SYM_ABLATE != 3) {
+                u32x4 hd;
+                hd[0] = cj0 + 16u * cb; hd[1] = qi0; hd[2] = 0u; hd[3] = 0u;
+                u32x4* r = lg + (size_t)at * 4;
+                r[0] = hd;
+                r[1] = __builtin_bit_cast(u32x4, cb ? th1 : th0);
+                r[2] = __builtin_bit_cast(u32x4, x.t[cb][0]);
+                r[3] = __builtin_bit_cast(u32x4, x.t[cb][1]);
+              }
+            } else {
+              // full log: the record is lost, and nobody knows which of its values passed — every real row among the block's four
+              // candidate rows is flagged.  Over-flagging only sends rows to the exact rescan (audit_kernel), which is always right.
+#pragma unroll
+              for (int jj = 0; jj < 4; ++jj) {
+                const uint32_t cj = cj0 + 16u * cb + jj;
+                if ((int64_t)cj < a.n_rows) atomicMax(a.lost + cj, 0x7fffffff);
+              }
+            }
+          }
+          sym_wcnt += (uint32_t)__popcll(b);
+        }
+      }
+      return;
+    }
     bool any = false;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1468,10 +1532,45 @@ __global__ void sym_thr_kernel(const int32_t* seed, float* thr, int64_t n, int64
 // launches have finished), and select's pruning threshold is never below it (DESIGN.md §4.1 "Pruned filing"): an entry that fails
 // select's own test — enc(key) + slot_ulp >= threshold — against seed[] would be dropped there, so it is not filed (seed: nullptr =
 // file everything, MMF_SYMMETRIC_PRUNE=0).
+// The log holds hit records (scan_b16x_kernel, sym_offer): 16 words — candidate row of value 0, query row of query block 0, two reserved
+// words; the four thresholds the wave tested against; the lane's 2 x 4 values [query block][candidate row].  Eight threads walk a
+// record, one value each, and apply the per-value test the scan kernel left out: the value reaches its candidate row's recorded
+// threshold, and both rows are real (records carry the padding rows of a ragged last row block and queries past n_rows).  What
+// passes is an "entry"; val_cnt[log] counts them (MMF_SYMMETRIC_DEBUG's "logged entries").
+// (MMF_SYM_RECORDS=0: the log holds the entries themselves, (candidate row, query row, key bits, 0), tested by the scan kernel.)
 __global__ __launch_bounds__(256) void sym_scatter_kernel(const uint32_t* log, const uint32_t* log_cnt, int log_cap, uint32_t* sym_cnt,
                                                           uint2* sym_ent, int cap, int32_t* lost,
-                                                          const int32_t* seed, int slot_ulp) {
+                                                          const int32_t* seed, int slot_ulp, int64_t n_rows, uint32_t* val_cnt) {
   const uint32_t c = log_cnt[blockIdx.x];
+#if MMF_SYM_RECORDS
+  __shared__ uint32_t passed_all;
+  if (c == 0) { if (threadIdx.x == 0) val_cnt[blockIdx.x] = 0u; return; }
+  if (threadIdx.x == 0) passed_all = 0u;
+  __syncthreads();
+  const uint32_t* lg = log + (size_t)blockIdx.x * log_cap * 16;
+  uint32_t passed = 0;
+  for (uint32_t e = threadIdx.x; e < 8u * c; e += 256) {
+    const uint32_t* r = lg + (size_t)(e >> 3) * 16;
+    const uint32_t vi = e & 7u, j = vi & 3u;                        // value vi = 4 qb + j of the record
+    const uint32_t cj = r[0] + j, qi = r[1] + 16u * (vi >> 2), kb = r[8 + vi];
+    if (!(__uint_as_float(kb) >= __uint_as_float(r[4 + j])) || (int64_t)qi >= n_rows || (int64_t)cj >= n_rows) continue;
+    ++passed;
+    if (seed) {
+      const int32_t sd = seed[cj], b = (int32_t)kb;
+      if (sd > kSeedNone && (b >= 0 ? b : (b ^ 0x7fffffff)) + slot_ulp < sd) continue;   // (no proven threshold: keep)
+    }
+    const uint32_t slot = atomicAdd(sym_cnt + cj, 1u);
+    if (slot < (uint32_t)cap) {
+      sym_ent[(size_t)cj * cap + slot] = make_uint2(qi, kb);           // (id, key bits): one 8-byte store
+    } else {
+      atomicMax(lost + cj, 0x7fffffff);
+    }
+  }
+  if (passed) atomicAdd(&passed_all, passed);
+  __syncthreads();
+  if (threadIdx.x == 0) val_cnt[blockIdx.x] = passed_all;
+#else
+  if (threadIdx.x == 0) val_cnt[blockIdx.x] = c;
   const u32x4* lg = reinterpret_cast<const u32x4*>(log) + (size_t)blockIdx.x * log_cap;
   for (uint32_t e = threadIdx.x; e < c; e += 256) {
     const u32x4 v = lg[e];
@@ -1486,6 +1585,18 @@ __global__ __launch_bounds__(256) void sym_scatter_kernel(const uint32_t* log, c
       atomicMax(lost + v[0], 0x7fffffff);
     }
   }
+#endif
+}
+
+// A wave log's capacity in the units the kernels count in: hit records (64 bytes), or — MMF_SYM_RECORDS=0 — entries (16 bytes, four to
+// a record's room).  MMF_SYMMETRIC_LOG_CAP (read per call) only lowers it: a small test reaches the full-log path with it.
+int scan_b16_sym_log_cap() {
+  int cap = kSymLogPerWave * (MMF_SYM_RECORDS ? 1 : 4);
+  if (const char* e = getenv("MMF_SYMMETRIC_LOG_CAP")) {
+    const int v = atoi(e);
+    if (v >= 1 && v < cap) cap = v;
+  }
+  return cap;
 }
 
 size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G) {
@@ -1503,6 +1614,7 @@ size_t scan_b16_sym_scratch_bytes(int64_t n_rows, int G) {
 int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandLists& L, void* scratch, const SymBuffers& sb,
                         const ScanB16Panel& pn, hipStream_t s, int* grid_out) {
   const int64_t n = p.n_rows, nb = (n + 255) / 256, n_pad = nb * 256, grid = sym_schedule_grid(nb, y.G);
+  const int log_cap = scan_b16_sym_log_cap();
   // the SYM kernels neither fetch nor add the per-candidate bias: only metrics whose bias is zero for every real row may come here
   if (p.metric != MMF_DOT && p.metric != MMF_COSINE) {
     set_error("scan_b16_sym: metric %d has a per-candidate bias, which the symmetric kernels do not apply", p.metric);
@@ -1525,7 +1637,7 @@ int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandL
   a.tiles_total = n_pad / B_CT; a.row_blocks = nb;
   a.spill_stacks = 0;
   a.sched = sb.sched;
-  a.sym_thr = sb.thr; a.sym_live = y.live ? 1 : 0; a.sym_log = sb.log; a.sym_log_cnt = sb.log_cnt; a.sym_log_cap = kSymLogPerWave;
+  a.sym_thr = sb.thr; a.sym_live = y.live ? 1 : 0; a.sym_log = sb.log; a.sym_log_cnt = sb.log_cnt; a.sym_log_cap = log_cap;
 #if MMF_SYM_COUNT
   static unsigned long long* dbuf = nullptr;
   if (!dbuf) MMF_HIP(hipMalloc(&dbuf, 128));
@@ -1552,8 +1664,8 @@ int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandL
 #if MMF_SYM_COUNT
   MMF_TRY(report(1));
 #endif
-  hipLaunchKernelGGL(sym_scatter_kernel, dim3((unsigned)(grid * 8)), dim3(256), 0, s, sb.log, sb.log_cnt, kSymLogPerWave, L.sym_cnt,
-                     L.sym_ent, L.sym_cap, pn.seed + pn.seed_stride, y.prune ? pn.seed : nullptr, L.slot_ulp);
+  hipLaunchKernelGGL(sym_scatter_kernel, dim3((unsigned)(grid * 8)), dim3(256), 0, s, sb.log, sb.log_cnt, log_cap, L.sym_cnt,
+                     L.sym_ent, L.sym_cap, pn.seed + pn.seed_stride, y.prune ? pn.seed : nullptr, L.slot_ulp, n, sb.val_cnt);
   MMF_LAUNCH_CHECK();
   if (grid_out) *grid_out = (int)(2 * grid);
   return MMF_OK;
