@@ -770,16 +770,18 @@ struct FastTail {
       MMF_HIP(hipStreamSynchronize(s));
       // hr: the hit records in each wave's log; hl: the values of those records that pass the thresholds recorded with them — the
       // "logged entries", counted by sym_scatter_kernel before its pruning test
-      std::vector<uint32_t> hc((size_t)n), hl((size_t)sym_grid() * 8), hr((size_t)sym_grid() * 8);
+      // hr continues with the waves' coarse visits (wave-tiles whose group test passed) and their wave-tiles with a hit
+      std::vector<uint32_t> hc((size_t)n), hl((size_t)sym_grid() * 8), hr((size_t)sym_grid() * 24);
       uint32_t none = 0;
       MMF_HIP(hipMemcpy(hc.data(), sym_cnt, hc.size() * 4, hipMemcpyDeviceToHost));
       MMF_HIP(hipMemcpy(hl.data(), sym.val_cnt, hl.size() * 4, hipMemcpyDeviceToHost));
       MMF_HIP(hipMemcpy(hr.data(), sym.log_cnt, hr.size() * 4, hipMemcpyDeviceToHost));
       MMF_HIP(hipMemcpy(&none, sym.none_cnt, 4, hipMemcpyDeviceToHost));
-      unsigned long long tot = 0, logged = 0, records = 0; uint32_t mx = 0, lmx = 0;
+      unsigned long long tot = 0, logged = 0, records = 0, coarse = 0, hit_tiles = 0; uint32_t mx = 0, lmx = 0;
       for (uint32_t v : hc) { tot += v; if (v > mx) mx = v; }
       for (uint32_t v : hl) logged += v;
-      for (uint32_t v : hr) { records += v; if (v > lmx) lmx = v; }
+      const size_t waves = hl.size();
+      for (size_t i = 0; i < waves; ++i) { records += hr[i]; if (hr[i] > lmx) lmx = hr[i]; coarse += hr[waves + i]; hit_tiles += hr[2 * waves + i]; }
       bool live, forward;
       symmetric_live_mode(&live, &forward);
       int phases; bool antipodal;
@@ -788,10 +790,10 @@ struct FastTail {
       const size_t first_b = (size_t)sym_schedule_phase_b_begin((n + 255) / 256, sym_G) * 8;
       unsigned long long logged_b = 0;
       for (size_t i = first_b; i < hl.size(); ++i) logged_b += hl[i];
-      fprintf(stderr, "[mmf symmetric] G %d grid %lld %s %s: rows without a threshold %u, received entries %llu (%.1f per row, largest %u of %d), fullest wave log %u of %d, logged entries %llu (%.1f per row, filing %s), records %llu, phases %d antipodal %d, logged by phase B %llu (%.1f per row)\n",
+      fprintf(stderr, "[mmf symmetric] G %d grid %lld %s %s: rows without a threshold %u, received entries %llu (%.1f per row, largest %u of %d), fullest wave log %u of %d, logged entries %llu (%.1f per row, filing %s), records %llu, phases %d antipodal %d, logged by phase B %llu (%.1f per row), coarse visits %llu, hit wave-tiles %llu\n",
               sym_G, (long long)sym_grid(), live ? "live" : "frozen", forward ? "ahead" : "back", none, tot, (double)tot / (double)n, mx,
               kSymCap, lmx, scan_b16_sym_log_cap(), logged, (double)logged / (double)n, symmetric_prune_mode() ? "pruned" : "complete", records,
-              forward ? 1 : phases, (antipodal && !forward) ? 1 : 0, logged_b, (double)logged_b / (double)n);
+              forward ? 1 : phases, (antipodal && !forward) ? 1 : 0, logged_b, (double)logged_b / (double)n, coarse, hit_tiles);
     }
     // the f32 rows are first touched here: a caller that is still receiving them (overlapped
     // all-gather) hands in the event that marks their arrival

@@ -211,19 +211,19 @@ constexpr int kSymCap = 512;            // entries per row of CandLists::sym_ent
 constexpr int kSymLogPerWave = 2304;    // 64-byte hit records of a wave's append log (DESIGN.md §4.1 "Capacity and memory": the fullest on the bench rows x 1.5, up to a multiple of 256)
 int scan_b16_sym_log_cap();             // ... as this call uses it: MMF_SYMMETRIC_LOG_CAP (read per call) lowers it, for tests of the full-log path
 struct SymBuffers {
-  float* thr = nullptr;            // [n_pad]
+  float* thr = nullptr;            // [n_pad] thresholds, then [n_pad / 8] group minima (four per 32-row tile), one allocation: one buffer resource
   uint32_t* log = nullptr;         // [grid * 8][kSymLogPerWave][16]
-  uint32_t* log_cnt = nullptr;     // [grid * 8] records in each log
+  uint32_t* log_cnt = nullptr;     // [3][grid * 8] per wave: records in its log, wave-tiles that passed the group test, wave-tiles with a hit
   uint32_t* val_cnt = nullptr;     // [grid * 8] values of each log's records that passed their recorded threshold (sym_scatter_kernel)
   int32_t* sched = nullptr;        // [2][grid][8]
   uint32_t* none_cnt = nullptr;    // [4] real rows that reached the symmetric launch without a threshold
   static size_t bytes(int64_t n_pad, int64_t grid) {
-    return ws_bytes(n_pad, 4) + ws_bytes((size_t)grid * 8 * kSymLogPerWave * 16, 4) + 2 * ws_bytes((size_t)grid * 8, 4) +
-           ws_bytes((size_t)grid * 16, 4) + ws_bytes(4, 4);
+    return ws_bytes(n_pad + n_pad / 8, 4) + ws_bytes((size_t)grid * 8 * kSymLogPerWave * 16, 4) + ws_bytes((size_t)grid * 24, 4) +
+           ws_bytes((size_t)grid * 8, 4) + ws_bytes((size_t)grid * 16, 4) + ws_bytes(4, 4);
   }
   void carve(Workspace& ws, int64_t n_pad, int64_t grid) {
-    thr = ws.take<float>(n_pad); log = ws.take<uint32_t>((size_t)grid * 8 * kSymLogPerWave * 16);
-    log_cnt = ws.take<uint32_t>((size_t)grid * 8); val_cnt = ws.take<uint32_t>((size_t)grid * 8); sched = ws.take<int32_t>((size_t)grid * 16); none_cnt = ws.take<uint32_t>(4);
+    thr = ws.take<float>(n_pad + n_pad / 8); log = ws.take<uint32_t>((size_t)grid * 8 * kSymLogPerWave * 16);
+    log_cnt = ws.take<uint32_t>((size_t)grid * 24); val_cnt = ws.take<uint32_t>((size_t)grid * 8); sched = ws.take<int32_t>((size_t)grid * 16); none_cnt = ws.take<uint32_t>(4);
   }
 };
 

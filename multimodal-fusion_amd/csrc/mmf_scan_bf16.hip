@@ -234,10 +234,12 @@ struct ScanB16Args {
   // SYM == 2 (the symmetric launch of a scan of X against itself, launch_scan_b16_sym): a value G_ij that reaches the
   // threshold of its CANDIDATE row j sends its lane's hit record (thresholds and values of the candidate block) to the wave's private
   // log; sym_scatter_kernel picks the passing values out of the records and files them into the rows' lists afterwards
-  float* sym_thr;            // [m_pad] threshold of every candidate row (sym_thr_kernel: seed[] decoded; +inf for padding rows)
+  float* sym_thr;            // [m_pad] threshold of every candidate row (sym_thr_kernel: seed[] decoded; +inf for padding rows), and behind it
+                             // [m_pad / 32][4] group minima: the smallest threshold of the eight rows a lane of row group g holds of a tile
   int sym_live;              // the rows' workgroups keep raising sym_thr[] while the symmetric launch runs (sync_seed)
   uint32_t* sym_log;         // [grid * NW][sym_log_cap][16]: hit records (MMF_SYM_RECORDS=0: [sym_log_cap][4] entries)
-  uint32_t* sym_log_cnt;     // [grid * NW] records written (zeroed by the host; an idle workgroup writes nothing)
+  uint32_t* sym_log_cnt;     // [3][grid * NW] records written, wave-tiles that passed the group test, wave-tiles with a hit (zeroed by the host;
+                             // an idle workgroup writes nothing)
   int sym_log_cap;
   // XSEG kernels only (launch_scan_b16_xseg): [n_pad][2] per query row, first row and row count of the columns the row may not
   // take (its own segment's rows of Y; padding rows: 0, 0)
@@ -331,6 +333,16 @@ __device__ __forceinline__ void glds4(const void* gptr, const void* lptr) {
 #ifndef MMF_SYM_RECORDS
 #define MMF_SYM_RECORDS 1     // SYM == 2: 1 = a lane with a hit appends one 64-byte record per candidate block (its four thresholds and eight
 #endif                        // values; sym_scatter_kernel does the per-value test), 0 = the per-value entry path before it (scripts/ab_build.sh)
+#ifndef MMF_SYM_COARSE
+#define MMF_SYM_COARSE 1      // SYM == 2: 1 = behind a chain the candidate side costs ONE compare, the lane's largest value against the minimum of its
+#endif                        // eight rows' thresholds (the group minima, sym_offer); the per-row test runs in the cold block behind it.  0 = the
+                              // per-row test behind every chain, as before (scripts/ab_build.sh)
+#if MMF_SYM_COARSE && !MMF_SYM_EARLY_THR
+#error "MMF_SYM_COARSE: the group minima ride on the paired threshold DMA (MMF_SYM_EARLY_THR=1)"
+#endif
+#ifndef MMF_SYM_CHAIN_WAIT
+#define MMF_SYM_CHAIN_WAIT 1  // SYM == 2: 1 = the cold blocks of the hot tests end with lgkmcnt(0), so the chain behind them opens with a counted
+#endif                        // wait for its A fragments; 0 = as before, the chain waits for all its leading reads (scripts/ab_build.sh)
 #ifndef MMF_SYM_SCALAR_ANY
 #define MMF_SYM_SCALAR_ANY 1  // SYM != 0: 1 = the hot tests branch on the ballot's scalar pair, 0 = on __any (scripts/ab_build.sh)
 #endif
@@ -385,7 +397,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   uint32_t* lids = a.lids + (size_t)blockIdx.x * (SlotList<CAP, NTL>::SLOTS * NTL);
   f32x4* xch = reinterpret_cast<f32x4*>(lkeys + CAP * NTL);          // SPLITK: [NQW][4][64] partial accumulators
   volatile int* ack = reinterpret_cast<volatile int*>(xch + NQW * 4 * 64);   // SPLITK: [NQW] last tile the lower wave took
-  // SYM == 2: behind the lists, [STAGES][32] thresholds of a tile's candidate rows (sym_thr_stage below)
+  // SYM == 2: the thresholds of a tile's candidate rows and their group minima take the bias stages (sym_thr_stage below)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -480,6 +492,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   // columns it sits in.  sync_seed publishes this lane's threshold when it has risen (and is not the product
   // of a dropped key) and adopts the best one published so far; it runs at the start and every 64 tiles.
   float pub = -kFltMax;
+  bool seed_rose = false;   // SYM == 2: the last sync_seed published a risen threshold of this lane (sync_tmin)
   auto sync_seed = [&]() {
     if (!qvalid) return;
     bool rose = false;
@@ -498,8 +511,31 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
     // Any value ever published for a row is a valid threshold for it, so neither the order in which the row's two lanes
     // store nor how late a reader sees the store matters; agent scope makes it leave this XCD's L2 while the kernel runs.
     if constexpr (SYM == 2) {
-      if (rose && a.sym_live) __hip_atomic_store(a.sym_thr + qpos, list.thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // (the lane's byte offset is made opaque HERE: left alone the compiler forms the 64-bit address in front of the tile loop, and
+      //  that pair of registers, live across the loop, is what the kernel would spill; the image is below 4 GiB, launch_scan_b16_sym)
+      if (rose && a.sym_live) {
+        uint32_t off = (uint32_t)qpos * 4u;
+        asm volatile("" : "+v"(off));
+        __hip_atomic_store(reinterpret_cast<float*>(reinterpret_cast<char*>(a.sym_thr) + off), list.thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        seed_rose = true;
+      }
     }
+  };
+  // SYM == 2, live image: ... and the group minima follow (the hot test of sym_offer reads them); called behind sync_seed, by the
+  // whole wave.  `pub` is a value published for
+  // the lane's row (or -FLT_MAX), so the minimum over the 16 lanes that own the lists of a group's eight rows is a minimum of
+  // published values: below it a value is below a valid threshold of its own row, whichever of the two images a reader sees newer.
+  // A row past n_rows counts as +inf, as in sym_thr_kernel.  Same store as the threshold image's; any order of the stores of the
+  // workgroups that share the rows leaves a valid minimum.
+  auto sync_tmin = [&]() {
+    if (__any(seed_rose)) {
+      float v = qvalid ? pub : __builtin_huge_valf();
+      v = fminf(v, __shfl_xor(v, 1)); v = fminf(v, __shfl_xor(v, 2));      // the four queries of the group in this lane's query block
+      v = fminf(v, __shfl_xor(v, 16)); v = fminf(v, __shfl_xor(v, 32));    // both query blocks, both lists of a row
+      if ((lane & 0x33) == 0)
+        __hip_atomic_store(a.sym_thr + a.tiles_total * B_CT + ((q0 >> 5) + qw) * 4 + (c16 >> 2), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    seed_rose = false;
   };
   // the wave-uniform branches of the SYM kernels' hot tests: on scalar registers.  __any of an OR of compares goes through a VGPR
   // (v_cndmask 0, 1 + v_cmp_ne on top of the s_or_b64 that already holds the answer), and so does the ballot of such an OR; the
@@ -574,7 +610,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
                                                (int)(uint32_t)(bsrc - cb0), 0, 0);
   };
   // SYM == 2: the thresholds of the same 32 rows, same form, same place in the iteration, issued by another wave
-  auto sym_thr_stage = [&](int stage) -> float* { return lkeys + CAP * NTL + stage * 32; };
+  // They live in the bias stages, which the SYM kernels leave unused: per stage group, the 64 thresholds of its two tiles and behind
+  // them the 2 x 4 group minima — 288 contiguous bytes, what one DMA writes (issue_thr_pair)
+  constexpr int SYM_GRP = 2 * B_CT + 8;
+  static_assert(SYM != 2 || (2 * SYM_GRP <= STAGES * 64 && TPB == 2), "thresholds and group minima in the bias stages");
+  auto sym_thr_stage = [&](int stage) -> float* { return cbs + (stage >> 1) * SYM_GRP + (stage & 1) * B_CT; };
+  auto sym_min_stage = [&](int stage) -> float* { return cbs + (stage >> 1) * SYM_GRP + 2 * B_CT + (stage & 1) * 4; };
   // (cache policy 16 = sc1, what the compiler emits for an agent-scope load: the image is rewritten by other XCDs' workgroups
   //  while this kernel runs (sync_seed), and a plain load could be served from a stale line of this XCD's L2 for as long as
   //  it stays there)
@@ -591,6 +632,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   auto issue_thr_pair = [&](const char* bsrc, int stage) {
     const __amdgpu_buffer_rsrc_t trsrc = __builtin_amdgcn_make_buffer_rsrc(a.sym_thr, 0, -1, 0x00020000);
     const uint32_t l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    if constexpr (MMF_SYM_COARSE != 0) {
+      // ... 16 bytes a lane: lanes 0..15 carry the 64 thresholds, lanes 16 and 17 the two tiles' group minima, which lie behind the
+      // threshold image (4 floats per tile: an eighth of the rows' byte offset), the other lanes nothing
+      const uint32_t off = (uint32_t)(bsrc - cb0);
+      const uint32_t voff = l < 16u ? off + l * 16u : (uint32_t)a.tiles_total * (B_CT * 4u) + (off >> 3) + (l - 16u) * 16u;
+      if (l < 18u)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(trsrc, (__attribute__((address_space(3))) void*)sym_thr_stage(stage), 16, (int)voff, 0, 0, 16);
+    } else
     __builtin_amdgcn_raw_ptr_buffer_load_lds(trsrc, (__attribute__((address_space(3))) void*)sym_thr_stage(stage), 4, (int)(l * 4u),
                                              (int)(uint32_t)(bsrc - cb0), 0, 16);
   };
@@ -790,7 +839,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       refresh_thr();
     }
     if (((DBG && (a.debug & 8)) || SYMCNT) && lane == 0) atomicAdd(a.dbg + 5, 1ull);   // tiles
-    if (__builtin_expect(a.share && (tt & 63) == 63, 0)) { sync_seed(); refresh_thr(); }
+    if (__builtin_expect(a.share && (tt & 63) == 63, 0)) {
+      sync_seed();
+      if constexpr (SYM == 2 && MMF_SYM_COARSE != 0) sync_tmin();
+      refresh_thr();
+    }
   };
 
   // SYM == 2, the candidate direction: right behind a tile's chain (its stage of thresholds is not refilled before the next
@@ -803,8 +856,19 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   // has values.
   // MMF_SYM_ABLATE (scripts/ab_build.sh, timing only, the results are WRONG): 1 = the test without the hit path, 2 = neither
   // the test nor the threshold DMA, 3 = the hit path without its log stores (the logs then read as empty; with records: the ballots and positions without the record stores).
-  uint32_t sym_wcnt = 0;
-  auto sym_offer = [&](const Acc& x, int tt, const float* th) {
+  // MMF_SYM_COARSE (the default): the hot test is ONE compare.  A lane's 16 values belong to eight candidate rows, those of its row
+  // group g in the tile's two candidate blocks; tmn is the smallest of their thresholds (the group minima: written with the image
+  // by sym_thr_kernel, kept up by sync_seed, fetched with the thresholds by issue_thr_pair and read from LDS BEFORE the chain), mm the
+  // largest of the 16 values (the two per-query maxima the query-side filter takes anyway).  mm < tmn: every value is below its row's
+  // threshold.  Otherwise the wave enters the cold block, which is the test above, unchanged.  ABLATE 4 = the hot test alone.
+  uint32_t sym_wcnt = 0, sym_cvis = 0, sym_htile = 0;   // records; wave-tiles that passed the group test; ... that had a hit
+  auto sym_offer = [&](const Acc& x, int tt, const float* th, float tmn, float mm) {
+    if constexpr (MMF_SYM_COARSE != 0) {
+      if (__builtin_expect(!(SCALAR_ANY ? sym_hits(__builtin_amdgcn_ballot_w64(mm >= tmn)) : __any(mm >= tmn) != 0) ||
+                           (MMF_SYM_ABLATE == 4 && a.sym_log_cap >= 0), 1)) return;
+      ++sym_cvis;
+      if (SYMCNT && lane == 0) atomicAdd(a.dbg + 6, 1ull);   // coarse visits
+    }
     const f32x4 th0 = *reinterpret_cast<const f32x4*>(th + 4 * g);
     const f32x4 th1 = *reinterpret_cast<const f32x4*>(th + 16 + 4 * g);
     if constexpr (MMF_SYM_RECORDS != 0) {
@@ -825,6 +889,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
         const uint32_t cj0 = id_base + (uint32_t)tt * B_CT + ((tt >= sym_n1) ? (uint32_t)(sym_skip * B_CT) : 0u) + 4u * (uint32_t)g;
         const uint32_t qi0 = (uint32_t)(q0 + 32 * qw + c16);
         u32x4* lg = reinterpret_cast<u32x4*>(a.sym_log) + ((size_t)blockIdx.x * NW + wave) * (size_t)a.sym_log_cap * 4;
+        ++sym_htile;
+        if (SYMCNT && lane == 0) atomicAdd(a.dbg + 7, 1ull);   // wave-tiles with a hit
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
           const bool hit = cb ? any1 : any0;
@@ -867,7 +933,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       const uint32_t qi0 = (uint32_t)(q0 + 32 * qw + c16);
       const bool sym_qv0 = q0 + 32 * qw + c16 < a.n_rows, sym_qv1 = q0 + 32 * qw + c16 + 16 < a.n_rows;
       uint32_t* lg = a.sym_log + ((size_t)blockIdx.x * NW + wave) * (size_t)a.sym_log_cap * 4;
-      uint32_t m = 0;                                    // bit 8 cb + 2 j + qb: value x.t[cb][qb][j] passes and both rows are real
+      ++sym_htile;
+      uint32_t m = 0;                                   // bit 8 cb + 2 j + qb: value x.t[cb][qb][j] passes and both rows are real
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {
 #pragma unroll
@@ -918,6 +985,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   const int nIter = (Ti + TPB - 1) / TPB;
   for (int j = 0; j < nIter; ++j) {
     if (stamps) tvs = __builtin_amdgcn_s_memtime();
+    if constexpr (SYM == 2 && MMF_SYM_CHAIN_WAIT != 0) {
+      // ... with lgkmcnt(0) in the same instruction.  On the hot path nothing of that counter is outstanding here, but the compiler
+      // carries the cold blocks' possibly outstanding scalar loads and LDS operations across the back edge and then opens the first
+      // chain with lgkmcnt(0) behind all six of its leading reads; told here that the counter is empty, it counts (lgkmcnt(5))
+      __builtin_amdgcn_s_waitcnt(0x0070);
+    } else
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) alone (expcnt 7, lgkmcnt 15 = no wait)
     if (stamps) t0s = __builtin_amdgcn_s_memtime();
     asm volatile("" ::: "memory");
@@ -955,6 +1028,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
       // the 32 biases of tile t + TPB go out BEFORE this tile's chain: issued behind it, the wave whose turn it is would
       // reach the vmcnt(0) of the next iteration with a DMA just issued, and seven waves would wait for it at the barrier
       Acc acc;
+      // SYM == 2: the tile's group minimum of this lane's row group, read in front of the chain (it landed before the barrier), so that
+      // no LDS wait sits behind it
+      constexpr bool COARSE = SYM == 2 && MMF_SYM_COARSE != 0 && MMF_SYM_ABLATE != 2;
+      float tmn = 0.f, m0 = 0.f, m1 = 0.f;
+      if constexpr (COARSE) {
+        tmn = sym_min_stage(sg + u)[g];
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
       acc = tile_body(tiles + (sg + u) * TILEB + kbyte, cbs + (sg + u) * 64, src, ng + u);
       // (behind the chain: issued in front of it, the same DMA costs +8 %; mid-chain needs a branch inside the chain)
       if constexpr (SYM == 0) { if (wave == ((t + TPB) & (NW - 1))) issue_bias(more ? bsrc + u * B_CT * 4 : cb0, ng + u); }
@@ -965,11 +1046,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
         // fetch that has not landed holds all eight waves at the next barrier); the issuing wave rotates with the iteration
         if constexpr (MMF_SYM_EARLY_THR) { if (u == 0 && wave == (j & (NW - 1))) issue_thr_pair(more ? bsrc : cb0, ng); }
         else if (wave == ((t + TPB + 4) & (NW - 1))) issue_thr(more ? bsrc + u * B_CT * 4 : cb0, ng + u);
-        if (t < Ti) sym_offer(acc, t, sym_thr_stage(sg + u));
+        // (the two per-query maxima serve the group test here and the query-side filter below)
+        if constexpr (COARSE) { m0 = max_qb(acc, 0); m1 = max_qb(acc, 1); }
+        if (t < Ti) sym_offer(acc, t, sym_thr_stage(sg + u), tmn, fmaxf(m0, m1));
       }
       if (u < TPB - 1) {
         if (TPB == 2 || __builtin_expect(t < Ti, 1))      // (TPB > 2: the ragged last group can hold several dummy tiles)
-        filter(acc, t, max_qb(acc, 0), max_qb(acc, 1));   // mid-iteration, no barrier nearby
+        filter(acc, t, COARSE ? m0 : max_qb(acc, 0), COARSE ? m1 : max_qb(acc, 1));   // mid-iteration, no barrier nearby
       } else {
         if (__builtin_expect(t >= Ti, 0)) {              // ragged range: the last tile of the last group is a dummy
 #pragma unroll
@@ -977,9 +1060,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) { acc.t[cb][0][jj] = kNegInf; acc.t[cb][1][jj] = kNegInf; }
           }
+          m0 = kNegInf; m1 = kNegInf;
         }
         acc_prev = acc;
-        if constexpr (!SPLITK) {
+        if constexpr (COARSE) {
+          m0_prev = m0; m1_prev = m1;
+        } else if constexpr (!SPLITK) {
           m0_prev = max_qb(acc, 0);     // reduced BEFORE the barrier, in time this wave would otherwise spend waiting
           m1_prev = max_qb(acc, 1);
         } else if (!owner) {
@@ -1028,8 +1114,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 1) void scan_b16x_kernel(S
   }
   sync_seed();
   if constexpr (SYM == 2) {
+    if constexpr (MMF_SYM_COARSE != 0) sync_tmin();
     if (MMF_SYM_ABLATE == 3) sym_wcnt = 0;   // nothing was stored: nothing for sym_scatter_kernel to read
-    if (lane == 0) a.sym_log_cnt[(size_t)blockIdx.x * NW + wave] = sym_wcnt < (uint32_t)a.sym_log_cap ? sym_wcnt : (uint32_t)a.sym_log_cap;
+    if (lane == 0) {
+      uint32_t* lc = a.sym_log_cnt + (size_t)blockIdx.x * NW + wave;
+      lc[0] = sym_wcnt < (uint32_t)a.sym_log_cap ? sym_wcnt : (uint32_t)a.sym_log_cap;
+      lc[(size_t)gridDim.x * NW] = sym_cvis; lc[2 * (size_t)gridDim.x * NW] = sym_htile;   // MMF_SYMMETRIC_DEBUG's "coarse visits" and "hit wave-tiles"
+    }
   }
   if (qvalid) {
     const int64_t lbase = qpos * a.lists_total + a.list_base + 2 * split + half;
@@ -1140,10 +1231,10 @@ int launch_prep_half_gather(const PrepRows& r, const int32_t* gather, int64_t n_
   return MMF_OK;
 }
 
-static size_t scan_b16_lds(int ks, int nw, int tpb, int cap, bool splitk, bool sym_thr = false) {
+static size_t scan_b16_lds(int ks, int nw, int tpb, int cap, bool splitk) {
   const int nqw = splitk ? nw / 2 : nw;
   return (size_t)(2 * tpb) * (B_CT * ks * 32) + (size_t)(2 * tpb) * 64 * 4 + (size_t)cap * (64 * nqw) * 4 +
-         (splitk ? (size_t)nqw * 4 * 64 * 16 + 64 : 0) + (sym_thr ? (size_t)(2 * tpb) * 32 * 4 : 0);
+         (splitk ? (size_t)nqw * 4 * 64 * 16 + 64 : 0);
 }
 
 int scan_b16_queries_per_block(int dp) { return 32 * waves_for_dp(dp); }
@@ -1173,7 +1264,7 @@ size_t scan_b16_scratch_bytes(int64_t n_rows, int col_splits, int dp, int cap) {
 // SEG and SYM kernels have no instrumented build
 template <int KS, int NW, int TPB, int CAP, bool SPLITK = false, bool SEG = false, int SYM = 0, bool XSEG = false, bool CEIL = false>
 static int launch_b16_t(const ScanB16Args& a, bool f16, int64_t grid, hipStream_t s) {
-  const size_t lds = scan_b16_lds(KS, NW, TPB, CAP, SPLITK, SYM == 2);
+  const size_t lds = scan_b16_lds(KS, NW, TPB, CAP, SPLITK);
   auto go = [&](auto kern) -> int {
     MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * NW), lds, s, a);
@@ -1516,15 +1607,30 @@ void sym_schedule_table(int64_t nb, int G, int launch, int32_t* out, bool forwar
 
 // thresholds of the candidate rows for the symmetric launch: seed[] (launch 0's proven thresholds) decoded once.  A real row
 // without one accepts everything (and is counted: it does not happen once launch 0 has seen k + self columns of the row);
-// padding rows accept nothing.
-__global__ void sym_thr_kernel(const int32_t* seed, float* thr, int64_t n, int64_t n_pad, uint32_t* none_cnt) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_pad) return;
-  if (i >= n) { thr[i] = __builtin_huge_valf(); return; }
-  const int32_t o = seed[i];
-  if (o > kSeedNone) { thr[i] = __int_as_float(o >= 0 ? o : (o ^ 0x7fffffff)); return; }
-  thr[i] = -kFltMax;
-  atomicAdd(none_cnt, 1u);
+// padding rows accept nothing.  Behind the image, thr[n_pad + 4 t + g]: the group minima of tile t (32 rows) — the smallest
+// threshold of rows 4 g .. 4 g + 3 and 16 + 4 g .. + 3 of the tile, the eight rows whose values a lane of row group g holds
+// (scan_b16x_kernel, sym_offer).  Padding rows (+inf) never lower one; a real row without a threshold makes its group pass always.
+// One workgroup of 256 threads per 256 rows (n_pad is a multiple of 256): eight tiles.
+__global__ __launch_bounds__(256) void sym_thr_kernel(const int32_t* seed, float* thr, int64_t n, int64_t n_pad, uint32_t* none_cnt) {
+  __shared__ float sv[256];
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  float v = __builtin_huge_valf();
+  if (i < n) {
+    const int32_t o = seed[i];
+    if (o > kSeedNone) v = __int_as_float(o >= 0 ? o : (o ^ 0x7fffffff));
+    else { v = -kFltMax; atomicAdd(none_cnt, 1u); }
+  }
+  if (i < n_pad) thr[i] = v;
+  sv[threadIdx.x] = v;
+  __syncthreads();
+  const int64_t t = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 2);
+  if (threadIdx.x < 32 && t * B_CT < n_pad) {
+    const float* r = sv + (threadIdx.x >> 2) * B_CT + 4 * (threadIdx.x & 3);
+    float m = __builtin_huge_valf();
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) m = fminf(m, fminf(r[jj], r[16 + jj]));
+    thr[n_pad + 4 * t + (threadIdx.x & 3)] = m;
+  }
 }
 
 // files the waves' logs into the rows' lists: one workgroup per log.  An entry that finds its row's list full flags the row.
@@ -1630,7 +1736,7 @@ int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandL
   }
   MMF_HIP(hipMemsetAsync(L.sym_cnt, 0, (size_t)n * 4, s));
   MMF_HIP(hipMemsetAsync(L.cnt, 0, (size_t)n * L.lists * 4, s));   // with one or two super-blocks the second launch has no work and writes no list
-  MMF_HIP(hipMemsetAsync(sb.log_cnt, 0, (size_t)grid * 8 * 4, s));
+  MMF_HIP(hipMemsetAsync(sb.log_cnt, 0, (size_t)3 * grid * 8 * 4, s));   // records, coarse visits, hit wave-tiles
   MMF_HIP(hipMemsetAsync(sb.none_cnt, 0, 16, s));
   ScanB16Args a = scan_args(p, L, pn, scratch);
   a.ZQ = p.ZC;                                          // one image: the rows are queries and candidates
@@ -1643,11 +1749,11 @@ int launch_scan_b16_sym(const ScanB16Problem& p, const SymLaunch& y, const CandL
   if (!dbuf) MMF_HIP(hipMalloc(&dbuf, 128));
   a.dbg = dbuf;
   auto report = [&](int launch) -> int {
-    unsigned long long h[8];
-    MMF_HIP(hipMemcpyAsync(h, dbuf, 64, hipMemcpyDeviceToHost, s));
+    unsigned long long h[16];
+    MMF_HIP(hipMemcpyAsync(h, dbuf, 128, hipMemcpyDeviceToHost, s));
     MMF_HIP(hipStreamSynchronize(s));
-    fprintf(stderr, "[mmf sym count] launch %d: wave-tiles=%llu visits=%llu (cold %llu) hits=%llu entry-compactions=%llu lanes-with-hit=%llu\n",
-            launch, h[5], h[0], h[1], h[2], h[3], h[4]);
+    fprintf(stderr, "[mmf sym count] launch %d: wave-tiles=%llu visits=%llu (cold %llu) hits=%llu entry-compactions=%llu lanes-with-hit=%llu coarse-visits=%llu hit-wave-tiles=%llu\n",
+            launch, h[5], h[0], h[1], h[2], h[3], h[4], h[6], h[7]);
     return MMF_OK;
   };
   MMF_HIP(hipMemsetAsync(dbuf, 0, 128, s));
