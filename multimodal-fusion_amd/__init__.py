@@ -26,6 +26,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.cross_segments_wide_anyk.*                that any-k top-k across segments from the wide 16-bit scan (feature dims 1025..4096), bit for bit, and the router
     mmf.segmented_wide_anyk.*                     that any-k top-k for every segment of a ragged batch from the wide 16-bit scan (feature dims 1025..4096), bit for bit, and the router
     mmf.combined_topk16_anyk.*                    the any-k top-k of K_h * K_g from the 16-bit scan of the combined key (one graph or a batch), bit for bit, and the router
+    mmf.combined_topk16_xy_anyk.*                 that any-k 16-bit top-k of K_h * K_g for two node sets or rows [lo, hi) of one graph, bit for bit, and the routers
     mmf.kmeans_ragged.*                           scikit-learn's KMeans fit for every block of a flat buffer in one call, each block with a width of its own
     mmf.wide_scan.*                               what the wide 16-bit scan (feature dims 1025..4096) covers: host-only queries
     mmf.cohort.build_cohort_hypergraphs(...)      the four steps of process_single_file for every slide of a cohort, in memory
@@ -33,6 +34,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.distributed.sharded_simtopk(...)          row-sharded multi-GPU driver (RCCL all-gather)
     mmf.distributed.sharded_simtopk_combined(...) the same driver for the top-k of K_h * K_g
     mmf.distributed.sharded_simtopk_combined_any_k(...) that driver for any k
+    mmf.distributed.sharded_simtopk_combined_fast_any_k(...) that driver for any k on the 16-bit scan of the combined key
 """
 from . import _lib, ops  # noqa: F401
 from .ops import (edge_cosine, offdiag_lower_median, sim_dense, sim_dense_combined, sim_dense_combined_segmented,  # noqa: F401
@@ -100,6 +102,10 @@ from . import combined_topk16_anyk  # noqa: F401,E402
 from .combined_topk16_anyk import (build_topk_hypergraph_data_fast_any_k, build_topk_weighted_hypergraph_fast_any_k,  # noqa: F401,E402
                                    combined_fast_anyk_plan, simtopk_combined_fast_any_k)
 
+# (the module's routers carry the names of combined_topk_anyk's calls, which keep the package-level names: reach them through the module)
+from . import combined_topk16_xy_anyk  # noqa: F401,E402
+from .combined_topk16_xy_anyk import simtopk_combined_rows_fast_any_k, simtopk_combined_xy_fast_any_k  # noqa: F401,E402
+
 from . import wide_scan  # noqa: F401,E402
 from .wide_scan import list_capacity, wide_scan_supported  # noqa: F401,E402
 
@@ -126,4 +132,5 @@ __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combin
            "cross_segments_wide_anyk", "simtopk_cross_segments_wide_any_k", "cross_segments_wide_anyk_plan",
            "segmented_wide_anyk", "simtopk_segmented_wide_any_k", "segmented_wide_anyk_plan",
            "combined_topk16_anyk", "simtopk_combined_fast_any_k", "combined_fast_anyk_plan",
-           "build_topk_weighted_hypergraph_fast_any_k", "build_topk_hypergraph_data_fast_any_k"]
+           "build_topk_weighted_hypergraph_fast_any_k", "build_topk_hypergraph_data_fast_any_k",
+           "combined_topk16_xy_anyk", "simtopk_combined_xy_fast_any_k", "simtopk_combined_rows_fast_any_k"]

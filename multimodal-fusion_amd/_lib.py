@@ -169,6 +169,13 @@ SEGW_ANYK_EXPORTS = ["mmf_simtopk_segmented_wide_anyk", "mmf_segmented_wide_anyk
 # host-only.  Pinned by tests/test_simtopk_combined_fast_anyk_cpu.py.
 TOPK16_ANYK_EXPORTS = ["mmf_simtopk_combined_fast_anyk", "mmf_combined_fast_anyk_plan"]
 
+# The 16-bit combined top-k for two node sets and any k (include/ext/mmf_hg_topk16_xy_anyk.h): an addition to ABI
+# version 3 in a header of its own; the arguments of mmf_simtopk_combined_xy plus the info struct of FAST_ANYK_EXPORTS.  It
+# synchronises once per pass (fail counts and yield histogram together) and, in a pass that sends queries to the exact rescan, once
+# more for their list and once for the rescan's fail count; mmf_combined_fast_anyk_plan answers for it too.  Pinned by
+# tests/test_simtopk_combined_xy_fast_anyk_cpu.py.
+TOPK16_XY_ANYK_EXPORTS = ["mmf_simtopk_combined_xy_fast_anyk"]
+
 
 class FastAnykInfo(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
@@ -301,6 +308,8 @@ def lib() -> ctypes.CDLL:
     L.mmf_simtopk_combined_fast_anyk.restype = ci
     L.mmf_combined_fast_anyk_plan.argtypes = list(L.mmf_fast_anyk_plan.argtypes)
     L.mmf_combined_fast_anyk_plan.restype = ci
+    L.mmf_simtopk_combined_xy_fast_anyk.argtypes = list(L.mmf_simtopk_combined_xy.argtypes) + [ctypes.POINTER(FastAnykInfo)]
+    L.mmf_simtopk_combined_xy_fast_anyk.restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

@@ -29,7 +29,7 @@ HEADERS = ["mmf_dev.h", "mmf_host.h", "mmf_rerank_combined.h", os.path.join(ROOT
            os.path.join(ROOT, "include", "ext", "mmf_hg_fast_anyk.h"), os.path.join(ROOT, "include", "ext", "mmf_hg_wide_anyk.h"),
            os.path.join(ROOT, "include", "ext", "mmf_hg_seg_anyk.h"), os.path.join(ROOT, "include", "ext", "mmf_hg_cross_seg_anyk.h"),
            os.path.join(ROOT, "include", "ext", "mmf_hg_cross_segw_anyk.h"), os.path.join(ROOT, "include", "ext", "mmf_hg_segw_anyk.h"),
-           os.path.join(ROOT, "include", "ext", "mmf_hg_topk16_anyk.h")]
+           os.path.join(ROOT, "include", "ext", "mmf_hg_topk16_anyk.h"), os.path.join(ROOT, "include", "ext", "mmf_hg_topk16_xy_anyk.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]

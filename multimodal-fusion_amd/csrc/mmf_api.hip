@@ -4990,3 +4990,319 @@ int mmf_simtopk_combined_fast_anyk(const float* F, const float* P, int64_t n, in
 }
 
 }  // extern "C"
+
+// ---- mmf_simtopk_combined_xy_fast_anyk (include/ext/mmf_hg_topk16_xy_anyk.h) -----------------------------------
+// The passes of combined_fast_anyk_run over the image and the work table of xy_fast: queries against candidates, or a row slice of
+// the candidates against all of them.  r: begun, as the exact pass wants it (X = the candidates for a slice, whose row slice0 is
+// query 0; else the queries), r.precision MMF_PREC_FAST or _FAST_BF16, k + self beyond one pass and nc >= k + self, so every query
+// has k admissible candidates and none is unserved.  Pass 0: xy_fast's launches at depth 20, K = 20 - self entries into the k-wide
+// output rows, every query's floor left behind (the flagged ones by the exact pass, gathered).  A later pass: ceilings by query
+// (launch_scan_b16c_xy_ceilings), the same device work table under them (launch_scan_b16c_xy_ceil), audit, the two-sided re-rank
+// into staging rows with canonical keys, count, one yield for the whole call, emit, and the exact two-set scan — one gathered group
+// against all candidates — of the queries that were flagged or short, from their floors.
+// Numberings.  Lists, thresholds, ceilings, staging rows, floors and the count / emit kernels go by QUERY (0 .. nq - 1); the floors'
+// ids are candidate rows (what the re-rank leaves before col_offset, what anyk_count compares after taking col_offset off the staged
+// id, and what an exact pass over all candidates reads and leaves: no rebase).  An exact pass goes by row of r.X: query i is row
+// x0 + i (x0 = slice0 for a slice, else 0), so it gets the floors' bases moved back by x0 rows and the gathered row ids with x0 added.
+namespace mmf {
+
+static int combined_xy_fast_anyk_run(Request& r, const float* Fq, const float* Pq, int64_t nq, const float* Fc, const float* Pc, int64_t nc,
+                                     int64_t slice0, int64_t dp, float lambda_g, int64_t row_offset, const mmf_simtopk_opts* opts,
+                                     mmf_fast_anyk_info* info) {
+  const char* who = r.call.who;
+  const hipStream_t s = r.call.s;
+  const bool slice = slice0 >= 0, f16 = r.precision == MMF_PREC_FAST, profile = r.profile;
+  const int64_t d = r.d, x0 = slice ? slice0 : 0;
+  const int k = r.k, self1 = r.exclude_self ? 1 : 0, depth = 20, K = depth - self1;
+  const float lambda_h = r.lambda;
+  mmf_simtopk_stats* stats = r.stats;
+  const int dpf = scan_b16c_dp(d), bcap = scan_b16c_cap(depth);
+
+  // ---- xy_fast's image and work table at depth 20 ---------------------------------------------------------------------------------
+  const int64_t ncp = (nc + 127) / 128 * 128, tiles = ncp / 128, row_blocks = (nq + 127) / 128;
+  const int64_t J = slice ? nc : nc + nq;           // rows of the joint numbering: candidates, then the queries unless they are among them
+  const int64_t q_row0 = slice ? slice0 : nc;       // the first query's row in it
+  const int64_t q_pos0 = slice ? slice0 : ncp;      // ... and its image position
+  const int64_t n_img = ncp + (slice ? 128 : row_blocks * 128);
+  if (n_img >= (int64_t(1) << 31) || J >= (int64_t(1) << 31)) { set_error("%s: the padded image of %lld positions is too large", who, (long long)n_img); return MMF_E_UNSUPPORTED; }
+  int splits = 1;
+  const int forced = opts ? opts->col_splits : 0;
+  if (forced > 0) { while (splits < forced && splits < 32) splits <<= 1; }
+  else { while (row_blocks * splits < 256 && splits < 32) splits <<= 1; }
+  while (splits > 1 && (splits > tiles || 2 * splits * bcap > 1024)) splits >>= 1;
+  const int lists = 2 * splits;
+  const int64_t tps = (tiles + splits - 1) / splits;
+  std::vector<int32_t> sched;
+  sched.reserve((size_t)row_blocks * splits * 8);
+  for (int64_t b = 0; b < nq; b += 128) {
+    for (int c = 0; c < splits; ++c) {
+      const int64_t tb = std::min(c * tps, tiles), te = std::min(tb + tps, tiles);
+      const int32_t e[8] = {(int32_t)(q_pos0 + b), (int32_t)(q_row0 + b), (int32_t)std::min<int64_t>(nq - b, 128), (int32_t)tb, (int32_t)te, 0,
+                            2 * c, (int32_t)(nc - 1)};
+      sched.insert(sched.end(), e, e + 8);
+    }
+  }
+  const int64_t grid = row_blocks * splits;
+
+  // ---- workspace (slot 0): xy_fast's, then floors (by row of r.X: x0 rows ahead of the first query's), bookkeeping, the identity
+  // table, ceilings and the staging rows ---------------------------------------------------------------------------------------------
+  const size_t stage = (size_t)nq * K;
+  const size_t need = 2 * ws_bytes(J, 4) + ws_bytes(8, 4) + (slice ? 0 : ws_bytes((size_t)J * dp, 4)) + HalfImage::bytes(n_img, dpf) +
+                      ws_bytes(sched.size(), 4) + b16_lists_bytes(nq, lists, bcap) + FlagBlock::bytes(nq) + ws_bytes(2 * (size_t)nq, 4) +
+                      2 * ws_bytes(x0 + nq, 4) + 4 * ws_bytes(nq, 4) + ws_bytes(64, 4) + ws_bytes(4, 4) + ws_bytes(stage, 8) + 2 * ws_bytes(stage, 4);
+  Workspace ws;
+  MMF_TRY(r.call.workspace(need, &ws));
+  float* nf = ws.take<float>(J);
+  float* pn = ws.take<float>(J);
+  uint32_t* maxw = ws.take<uint32_t>(8);   // word 0: largest chain(f, f) of both sides, word 4: largest chain(p, p)
+  float* Pj = slice ? nullptr : ws.take<float>((size_t)J * dp);   // both sides' positions in the joint numbering
+  HalfImage C;
+  C.carve(ws, n_img, dpf);
+  int32_t* d_sched = ws.take<int32_t>(sched.size());
+  const CandLists L = carve_b16_lists(ws, nq, lists, bcap);
+  FlagBlock flags;
+  flags.carve(ws, nq);
+  int32_t* seed = ws.take<int32_t>(2 * (size_t)nq);
+  float* fkey_x = ws.take<float>(x0 + nq); uint32_t* fid_x = ws.take<uint32_t>(x0 + nq);   // by row of r.X
+  float* fkey = fkey_x + x0; uint32_t* fid = fid_x + x0;                                   // by query
+  int32_t* certified = ws.take<int32_t>(nq); int32_t* rescan_rows = ws.take<int32_t>(nq);
+  int32_t* d_rows = rescan_rows;   // (a pass's rescan list is read to the host before the sorted rows take its place)
+  int32_t* d_iota = ws.take<int32_t>(nq);
+  float* ceil = ws.take<float>(nq);
+  uint32_t* hist = ws.take<uint32_t>(64); uint32_t* rescan_count = ws.take<uint32_t>(4);
+  int64_t* sidx = ws.take<int64_t>(stage); float* sval = ws.take<float>(stage); float* skey = ws.take<float>(stage);
+  MMF_HIP(hipMemsetAsync(C.maxima, 0, 16, s));
+  MMF_HIP(hipMemsetAsync(maxw, 0, 32, s));
+  MMF_TRY(flags.zero(s));
+
+  EventTimer t_prep, t_scan, t_sel, t_fb;
+  MMF_TRY(t_prep.start(profile, s));
+  MMF_TRY(launch_row_scalars(Fc, nc, d, MMF_F32, MMF_RBF, nf, maxw, s));
+  MMF_TRY(launch_row_scalars(Pc, nc, dp, MMF_F32, MMF_RBF, pn, maxw + 4, s));
+  MMF_TRY(upload_table(s, d_sched, sched.data(), sched.size() * 4));
+  MMF_TRY(launch_anyk_iota(d_iota, nq, s));
+  if (slice) {
+    MMF_TRY(launch_prep_half({Fc, nc, d, MMF_F32, MMF_RBF, nf, maxw}, C, dpf, f16, s));
+  } else {
+    // scale and maxima over both sides: the queries' scalars join the same words before either image is written
+    MMF_TRY(launch_row_scalars(Fq, nq, d, MMF_F32, MMF_RBF, nf + nc, maxw, s));
+    MMF_TRY(launch_row_scalars(Pq, nq, dp, MMF_F32, MMF_RBF, pn + nc, maxw + 4, s));
+    MMF_HIP(hipMemcpyAsync(Pj, Pc, (size_t)nc * dp * 4, hipMemcpyDeviceToDevice, s));
+    MMF_HIP(hipMemcpyAsync(Pj + nc * dp, Pq, (size_t)nq * dp * 4, hipMemcpyDeviceToDevice, s));
+    HalfImage Cc = C;
+    Cc.n_pad = ncp;
+    MMF_TRY(launch_prep_half({Fc, nc, d, MMF_F32, MMF_RBF, nf, maxw}, Cc, dpf, f16, s));
+    MMF_TRY(launch_prep_half({Fq, nq, d, MMF_F32, MMF_RBF, nf + nc, maxw}, C.from_row(ncp, dpf), dpf, f16, s));
+  }
+  MMF_TRY(t_prep.stop(s));
+
+  // kq entries per query from column out_off0 on for `rows` (rows of r.X, ascending) by the exact two-set pass: one gathered group
+  // against all candidates
+  auto exact_rows = [&](const std::vector<int32_t>& rows, int kq, int out_off0, bool floors_in, bool floors_out) -> int {
+    const int64_t cnt = (int64_t)rows.size();
+    if (cnt == 0) return MMF_OK;
+    ExactPass ex(r, nf + (slice ? 0 : nc), nf);
+    ex.same = slice;
+    ex.P = slice ? Pc : Pq; ex.pn = pn + (slice ? 0 : nc); ex.dp = (int)dp; ex.lambda_g = lambda_g; ex.out_row0 = x0;
+    if (!slice) { ex.Pc = Pc; ex.pnc = pn; }
+    ex.out_stride = k; ex.out_off0 = out_off0;
+    ex.floors_in = floors_in; ex.floors_out = floors_out;
+    ex.row_floor_key = fkey_x; ex.row_floor_id = fid_x;
+    ex.add(ExactGroup{0, cnt, true, 0, nc, kq});
+    ex.n_ids = cnt; ex.row_ids = d_rows;
+    Workspace aux;   // lists and f32 images in the second workspace slot
+    MMF_TRY(r.call.workspace(ex.image_bytes() + ex.list_bytes(), &aux, 1));
+    ExactLists B;
+    B.carve(aux, ex.rows_total, ex.list_words, ex.cap(), ex.floors());
+    MMF_TRY(upload_table(s, d_rows, rows.data(), (size_t)cnt * 4));
+    MMF_TRY(B.zero(s));
+    return ex.run(aux, B);
+  };
+  // `cnt` device queries as rows of r.X, ascending (one more synchronisation)
+  auto rows_of = [&](const int32_t* dev_rows, int64_t cnt, std::vector<int32_t>* out) -> int {
+    out->assign((size_t)cnt, 0);
+    if (cnt > 0) {
+      MMF_HIP(hipMemcpyAsync(out->data(), dev_rows, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
+      MMF_HIP(hipStreamSynchronize(s));
+    }
+    for (int32_t& row : *out) {
+      if (row < 0 || row >= nq) { set_error("%s: flagged row %d outside the %lld queries (internal invariant)", who, row, (long long)nq); return MMF_E_INTERNAL; }
+      row += (int32_t)x0;
+    }
+    std::sort(out->begin(), out->end());
+    return MMF_OK;
+  };
+  // test hook, every pass: send the first queries down the exact paths (FastTail::run's)
+  auto debug_flag_rows = [&]() -> int {
+    if (const char* e = getenv("MMF_DEBUG_FLAG_ROWS")) {
+      const int64_t f = atoll(e);
+      if (f > 0) MMF_HIP(hipMemsetAsync(L.overflow, 1, (size_t)(f < nq ? f : nq) * 4, s));
+    }
+    return MMF_OK;
+  };
+
+  ScanB16Panel pnl;
+  pnl.seed = seed; pnl.seed_stride = nq;
+  const ScanB16Problem sp(C, C, nq, nc, n_img, dpf, d, f16, MMF_RBF, depth);
+  const ScanB16Comb sc{slice ? Pc : Pj, pn, nf, maxw, maxw + 4, (int)dp, lambda_h, lambda_g};
+  SelectProblem q = r.select();   // the call-wide re-ranks go by query, as xy_fast's
+  q.X = Fq; q.n = nq; q.n_rows = nq; q.row_offset = row_offset;
+  q.rx = nf + q_row0; q.cy = nf; q.Pq = Pq; q.Pc = Pc; q.pnq = pn + q_row0; q.pnc = pn; q.dp = (int)dp; q.lambda_g = lambda_g;
+  q.fail_rows = flags.fail_rows; q.fail_count = flags.fail_count;
+
+  // ---- pass 0: K entries per query, k-wide rows, floors left ------------------------------------------------------------------------
+  MMF_TRY(reset_b16_lists(L, nq, lists, seed, nq, s));
+  MMF_TRY(t_scan.start(profile, s));
+  MMF_TRY(launch_scan_b16c_xy(sp, sc, d_sched, grid, lists, q_row0, L, pnl, s));
+  MMF_TRY(launch_scan_b16_audit(pnl, L.overflow, nq, s));
+  MMF_TRY(debug_flag_rows());
+  MMF_TRY(t_scan.stop(s));
+  {
+    SelectProblem q0 = q;
+    q0.k = K; q0.out_stride = k; q0.cand_total = stats ? flags.cand_total : nullptr;
+    q0.floor_key_out = fkey; q0.floor_id_out = fid;
+    MMF_TRY(t_sel.start(profile, s));
+    MMF_TRY(launch_rerank_combined(q0, L, s));
+    MMF_TRY(t_sel.stop(s));
+  }
+  MMF_TRY(flags.read(stats != nullptr, s));
+  std::vector<int32_t> ex_rows;
+  MMF_TRY(rows_of(flags.fail_rows, flags.h_fail4[0], &ex_rows));
+  const int64_t fallback0 = (int64_t)ex_rows.size();
+  MMF_TRY(t_fb.start(profile && fallback0 > 0, s));
+  MMF_TRY(exact_rows(ex_rows, K, 0, false, true));
+  MMF_TRY(t_fb.stop(s));
+  fill_stats(stats, r.precision, splits, (int)grid, t_prep.ms(), t_scan.ms(), t_sel.ms(), t_fb.ms(), fallback0, flags.h_fail4[1], flags.h_fail4[2],
+             flags.h_tot);
+  anyk_record(info, 0, K, 0, fallback0);
+
+  // ---- later passes ---------------------------------------------------------------------------------------------------------------
+  const int64_t budget = nq / anyk_short_div();
+  const AnykStage st{sidx, sval, skey, nq, K, r.col_offset};
+  int done = K;
+  auto finish_exact = [&](int pass) -> int {   // every query, everything that is left
+    std::vector<int32_t> all((size_t)nq);
+    for (int64_t i = 0; i < nq; ++i) all[(size_t)i] = (int32_t)(x0 + i);
+    MMF_TRY(exact_rows(all, k - done, done, true, false));
+    if (stats) stats->fallback_rows += nq;
+    anyk_record(info, pass, k - done, 0, nq);
+    return MMF_OK;
+  };
+  for (int pass = 1; done < k; ++pass) {
+    if (pass >= MMF_FAST_ANYK_MAX_PASSES - 1) return finish_exact(pass);
+    MMF_TRY(launch_scan_b16c_xy_ceilings(sp, sc, q_pos0, q_row0, d_iota, fkey, ceil, s));
+    MMF_TRY(reset_b16_lists(L, nq, lists, seed, nq, s));
+    MMF_TRY(flags.zero(s));
+    MMF_TRY(launch_scan_b16c_xy_ceil(sp, sc, d_sched, grid, lists, q_row0, L, pnl, ceil, s));
+    MMF_TRY(launch_scan_b16_audit(pnl, L.overflow, nq, s));
+    MMF_TRY(debug_flag_rows());
+    {
+      SelectProblem qs = q;   // K entries per query into the K-wide staging rows, with their keys
+      qs.k = K; qs.out_idx = sidx; qs.out_val = sval; qs.key_out = skey; qs.out_stride = K;
+      MMF_TRY(launch_rerank_combined_ext(qs, L, s));
+    }
+    MMF_TRY(launch_anyk_count(st, flags.fail_rows, flags.fail_count, fkey, fid, certified, hist, s));
+    uint32_t h[64];
+    MMF_HIP(hipMemcpyAsync(h, hist, (size_t)(K + 3) * 4, hipMemcpyDeviceToHost, s));
+    MMF_HIP(hipStreamSynchronize(s));
+    int64_t short_rows = 0;
+    const int t = anyk_yield(h, std::min(K, k - done), budget, &short_rows);
+    if (t < 1) return finish_exact(pass);
+    MMF_TRY(launch_anyk_emit(st, certified, t, done, k, r.out_idx, r.out_val, fkey, fid, rescan_rows, rescan_count, s));
+    const int64_t listed = (int64_t)h[K + 1] + short_rows;   // the emit kernel's list: flagged queries and short ones
+    if (listed > 0) {
+      MMF_TRY(rows_of(rescan_rows, listed, &ex_rows));
+      MMF_TRY(exact_rows(ex_rows, t, done, true, done + t < k));
+      if (stats) stats->fallback_rows += listed;
+    }
+    anyk_record(info, pass, t, (int)h[K + 2], listed);
+    done += t;
+  }
+  return MMF_OK;
+}
+
+}  // namespace mmf
+
+extern "C" {
+
+// The checks of mmf_simtopk_combined_xy (mmf_scan_b16c.hip) in their order and wording under this entry's name, without its
+// k + self refusals; col_splits as the any-k 16-bit entries check it.
+int mmf_simtopk_combined_xy_fast_anyk(const float* Fq, const float* Pq, int64_t nq, const float* Fc, const float* Pc, int64_t nc,
+                                      int64_t d, int64_t dp, float lambda_h, float lambda_g, int k, int exclude_self,
+                                      int64_t row_offset, int64_t col_offset, int64_t* out_idx, float* out_val,
+                                      const mmf_simtopk_opts* opts, mmf_simtopk_stats* stats, int device_id, void* hip_stream,
+                                      mmf_fast_anyk_info* info) {
+  const char* who = "simtopk_combined_xy_fast_anyk";
+  MMF_TRY(Call(who, device_id, hip_stream).on_device());
+  if (nq < 0) { set_error("%s: nq must be >= 0 (got %lld)", who, (long long)nq); return MMF_E_INVALID; }
+  if (nc < 0) { set_error("%s: nc must be >= 0 (got %lld)", who, (long long)nc); return MMF_E_INVALID; }
+  if (d < 1) { set_error("%s: d must be at least 1 (got %lld)", who, (long long)d); return MMF_E_INVALID; }
+  if (dp < 1) { set_error("%s: dp must be at least 1 (got %lld)", who, (long long)dp); return MMF_E_INVALID; }
+  if (k < 1) { set_error("%s: k must be at least 1 (got %d)", who, k); return MMF_E_INVALID; }
+  if (row_offset < 0) { set_error("%s: row_offset must be >= 0 (got %lld)", who, (long long)row_offset); return MMF_E_INVALID; }
+  if (col_offset < 0) { set_error("%s: col_offset must be >= 0 (got %lld)", who, (long long)col_offset); return MMF_E_INVALID; }
+  if (!(lambda_h >= 0.0f) || !std::isfinite(lambda_h)) { set_error("%s: lambda_h must be finite and >= 0 (got %g)", who, lambda_h); return MMF_E_INVALID; }
+  if (!(lambda_g >= 0.0f) || !std::isfinite(lambda_g)) { set_error("%s: lambda_g must be finite and >= 0 (got %g)", who, lambda_g); return MMF_E_INVALID; }
+  if (nq > 0 && !Fq) { set_error("%s: Fq is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && !Pq) { set_error("%s: Pq is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && nc > 0 && !Fc) { set_error("%s: Fc is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && nc > 0 && !Pc) { set_error("%s: Pc is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && !out_idx) { set_error("%s: out_idx is NULL", who); return MMF_E_INVALID; }
+  if (nq > 0 && !out_val) { set_error("%s: out_val is NULL", who); return MMF_E_INVALID; }
+  const int asked = opts ? opts->precision : MMF_PREC_AUTO;
+  if (asked != MMF_PREC_AUTO && asked != MMF_PREC_EXACT && asked != MMF_PREC_FAST && asked != MMF_PREC_FAST_BF16) {
+    set_error("%s: precision %d: MMF_PREC_AUTO, _EXACT, _FAST (f16 operands) or _FAST_BF16", who, asked);
+    return MMF_E_INVALID;
+  }
+  MMF_TRY(check_pow2_splits(who, opts));
+  if (dp > 8) { set_error("%s: dp = %lld > 8 is not supported", who, (long long)dp); return MMF_E_UNSUPPORTED; }
+  const int prec = asked == MMF_PREC_AUTO ? MMF_PREC_FAST : asked;
+  if (prec != MMF_PREC_EXACT && d > 4096) { set_error("%s: d = %lld > 4096 is not supported (MMF_PREC_EXACT takes any d)", who, (long long)d); return MMF_E_UNSUPPORTED; }
+  if (nq >= ((int64_t)1 << 31) - row_offset) { set_error("%s: row_offset + nq must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  if (nc >= ((int64_t)1 << 31) - col_offset) { set_error("%s: col_offset + nc must be < 2^31", who); return MMF_E_UNSUPPORTED; }
+  if (info) memset(info, 0, sizeof(*info));
+  if (nq == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return MMF_OK; }
+
+  const int self1 = exclude_self ? 1 : 0, kk = k + self1;
+  mmf_simtopk_stats own_stats;   // info reports the first pass's flagged rows, which the call counts in its stats
+  mmf_simtopk_stats* st = stats ? stats : (info ? &own_stats : nullptr);
+  mmf_simtopk_opts one{};
+  if (opts) one = *opts;
+  if (prec == MMF_PREC_EXACT || nc < kk) {
+    // the driver behind mmf_simtopk_combined_xy_anyk; fewer candidates than a query's lists keep (none at all: the fill) are served
+    // exactly, as mmf_simtopk_combined_xy serves them
+    one.precision = MMF_PREC_EXACT;
+    MMF_TRY(run_simtopk_combined_xy(who, Fq, Pq, nq, Fc, Pc, nc, d, dp, lambda_h, lambda_g, k, exclude_self, row_offset, col_offset, out_idx,
+                                    out_val, &one, st, device_id, hip_stream));
+    anyk_record(info, 0, k, 0, 0);
+    return MMF_OK;
+  }
+  if (kk <= 20) {   // one pass serves: the call IS mmf_simtopk_combined_xy's 16-bit path
+    one.precision = prec;
+    MMF_TRY(run_simtopk_combined_xy(who, Fq, Pq, nq, Fc, Pc, nc, d, dp, lambda_h, lambda_g, k, exclude_self, row_offset, col_offset, out_idx,
+                                    out_val, &one, st, device_id, hip_stream));
+    anyk_record(info, 0, k, 0, st ? st->fallback_rows : 0);
+    return MMF_OK;
+  }
+  // a row slice (Fq / Pq point at the same row of Fc / Pc, nq rows inside nc): run_simtopk_combined_xy's recognition
+  int64_t slice0 = -1;
+  {
+    const uintptr_t fq = reinterpret_cast<uintptr_t>(Fq), fc = reinterpret_cast<uintptr_t>(Fc);
+    const size_t row_bytes = (size_t)d * 4;
+    if (fq >= fc && (fq - fc) % row_bytes == 0) {
+      const int64_t r0 = (int64_t)((fq - fc) / row_bytes);
+      if (r0 <= nc - nq && Pq == Pc + r0 * dp) slice0 = r0;
+    }
+  }
+  const bool slice = slice0 >= 0;
+  const int64_t x0 = slice ? slice0 : 0;   // query 0 is row x0 of r.X
+  if (st) memset(st, 0, sizeof(*st));
+  Request r{Call(who, device_id, hip_stream), slice ? Fc : Fq, slice ? nc : nq, Fc, nc, d, MMF_F32, MMF_RBF, lambda_h, k, exclude_self,
+            row_offset - x0, col_offset, out_idx, out_val, st, opts && opts->profile};
+  r.kk = kk;
+  r.precision = prec;
+  MMF_TRY(r.call.begin());
+  return combined_xy_fast_anyk_run(r, Fq, Pq, nq, Fc, Pc, nc, slice0, dp, lambda_g, row_offset, opts, info);
+}
+
+}  // extern "C"

@@ -28,6 +28,7 @@
 #include "../../include/ext/mmf_hg_cross_segw_anyk.h"
 #include "../../include/ext/mmf_hg_segw_anyk.h"
 #include "../../include/ext/mmf_hg_topk16_anyk.h"
+#include "../../include/ext/mmf_hg_topk16_xy_anyk.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
@@ -534,6 +535,14 @@ int launch_scan_b16c_ceilings(const ScanB16Problem& p, const ScanB16Comb& c, con
 // whose first one is row `list_row0` of that numbering; p.m: candidate rows, p.m_pad: positions of the image
 int launch_scan_b16c_xy(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, int64_t list_row0,
                         const CandLists& L, const ScanB16Panel& pn, hipStream_t s);
+// The later passes of mmf_simtopk_combined_xy_fast_anyk: launch_scan_b16c_xy under a ceiling per QUERY (ceil
+// [p.n_rows], its base moved back like the lists'; 32-entry lists only), and the ceilings of the queries of such an image from their
+// floors (floor_key / ceil [p.n_rows] by query; -inf: no column left): query i sits at image position q_pos0 + i and is row
+// q_row0 + i of the joint numbering; iota [p.n_rows] = 0, 1, ... (launch_anyk_iota) is the kernel's position -> row table
+int launch_scan_b16c_xy_ceil(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, int64_t list_row0,
+                             const CandLists& L, const ScanB16Panel& pn, const float* ceil, hipStream_t s);
+int launch_scan_b16c_xy_ceilings(const ScanB16Problem& p, const ScanB16Comb& c, int64_t q_pos0, int64_t q_row0, const int32_t* iota,
+                                 const float* floor_key, float* ceil, hipStream_t s);
 // mmf_api.hip: mmf_simtopk_combined_xy behind its host checks — the exact pass over the queries against the candidates, or the
 // table-driven 16-bit scan, audit, re-rank and the exact pass over the row blocks of flagged rows
 int run_simtopk_combined_xy(const char* who, const float* Fq, const float* Pq, int64_t nq, const float* Fc, const float* Pc, int64_t nc,

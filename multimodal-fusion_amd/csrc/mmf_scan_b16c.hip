@@ -921,6 +921,75 @@ int launch_scan_b16c_xy(const ScanB16Problem& p, const ScanB16Comb& c, const int
   return MMF_OK;
 }
 
+// The two-set scan under per-query ceilings (a later pass of mmf_simtopk_combined_xy_fast_anyk): launch_scan_b16c_xy's
+// checks, arguments and moved-back bases on scan_b16c_ceil_kernel, 32-entry lists only.  ceil [p.n_rows] is indexed by query, like
+// the lists: the kernel reads it by the joint row of a (clamped) real query of the block, so its base moves back with theirs.
+int launch_scan_b16c_xy_ceil(const ScanB16Problem& p, const ScanB16Comb& c, const int32_t* sched, int64_t grid, int lists, int64_t list_row0,
+                             const CandLists& L, const ScanB16Panel& pn, const float* ceil, hipStream_t s) {
+  if (grid <= 0 || p.n_rows <= 0) return MMF_OK;
+  if (!scan_b16c_supported(p.d, p.kk) || p.dp != scan_b16c_dp(p.d) || p.metric != MMF_RBF) {
+    set_error("scan_b16c_xy_ceil: d = %lld (padded %d), k + self = %d, metric %d outside 1 <= d <= 4096, k + self <= 20, MMF_RBF", (long long)p.d,
+              p.dp, p.kk, p.metric);
+    return MMF_E_INTERNAL;
+  }
+  if (p.ZQ != p.ZC || p.m < 1 || list_row0 < 0) { set_error("scan_b16c_xy_ceil: one image holding both sides, candidates first"); return MMF_E_INTERNAL; }
+  if (!c.P || !c.pn || !c.nf || !c.max_nf || !c.max_pn || c.dp < 1 || c.dp > 8) { set_error("scan_b16c_xy_ceil: positions, chains and maxima (1 <= dp <= 8) missing"); return MMF_E_INTERNAL; }
+  const int col_splits = lists / 2;
+  if (lists < 2 || lists != 2 * col_splits || (col_splits & (col_splits - 1)) != 0) {
+    set_error("scan_b16c_xy_ceil: %d lists per row are no power-of-two number of pairs", lists);
+    return MMF_E_INTERNAL;
+  }
+  if (!sched || !ceil) { set_error("scan_b16c_xy_ceil: work table or ceilings missing"); return MMF_E_INTERNAL; }
+  if (!pn.seed || pn.seed_stride < p.n_rows) { set_error("scan_b16c_xy_ceil: threshold buffers missing"); return MMF_E_INTERNAL; }
+  if (lists != L.lists) { set_error("scan_b16c_xy_ceil: %d lists per row for %d column splits", L.lists, col_splits); return MMF_E_INTERNAL; }
+  if (L.cap != C_CAP_BIG) { set_error("scan_b16c_xy_ceil: list capacity %d, expected %d", L.cap, C_CAP_BIG); return MMF_E_INTERNAL; }
+  if (col_splits > 1 && (!L.keys || !L.margin)) { set_error("scan_b16c_xy_ceil: column splits need the lists' keys and margins"); return MMF_E_INTERNAL; }
+  if (p.m_pad % C_CT != 0 || (p.m + C_CT - 1) / C_CT * C_CT > p.m_pad) {
+    set_error("scan_b16c_xy_ceil: image of %lld positions for %lld candidates", (long long)p.m_pad, (long long)p.m);
+    return MMF_E_INTERNAL;
+  }
+  ScanB16CArgs a{};
+  a.Z = p.ZC; a.cb = p.cb; a.q_zn = p.q_zn; a.q_rn = p.q_rn; a.q_un = p.q_un; a.maxima = p.maxima;
+  a.nf = c.nf; a.P = c.P; a.pn = c.pn; a.max_nf = c.max_nf; a.max_pn = c.max_pn; a.lambda_h = c.lambda_h; a.lambda_g = c.lambda_g; a.dpp = c.dp;
+  a.n_rows = p.n_rows; a.kk = p.kk; a.d = (int)p.d; a.dp = p.dp;
+  a.tiles_total = p.m_pad / C_CT; a.tiles_per_split = a.tiles_total; a.col_splits = 1;   // unused: the table carries the ranges
+  a.lists_total = L.lists;
+  const int64_t lw = list_row0 * L.lists;   // list words ahead of the first query's
+  a.seed = pn.seed - list_row0; a.lost = pn.seed + pn.seed_stride - list_row0;
+  a.cand_cnt = L.cnt - lw; a.cand_ids = L.ids - lw * L.cap;
+  a.cand_keys = L.keys ? L.keys - lw * L.cap : nullptr; a.margin_out = L.margin ? L.margin - list_row0 : nullptr;
+  a.sched = sched; a.ceil = ceil - list_row0;
+  const size_t lds = scan_b16c_lds(C_CAP_BIG);
+  const auto kern = p.f16 ? scan_b16c_ceil_kernel<true> : scan_b16c_ceil_kernel<false>;
+  MMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C_NT), lds, s, a);
+  MMF_LAUNCH_CHECK();
+  if (col_splits > 1) {
+    hipLaunchKernelGGL(comb_seed_union_kernel, dim3((unsigned)((p.n_rows + 3) / 4)), dim3(256), 0, s, L.cnt, L.keys, L.margin, L.lists, L.cap,
+                       p.kk, pn.seed, p.n_rows);
+    MMF_LAUNCH_CHECK();
+  }
+  return MMF_OK;
+}
+
+// The ceilings of the p.n_rows queries of a two-sided image: query i sits at image position q_pos0 + i and is row q_row0 + i of the
+// joint numbering (c.nf / c.pn), its floor and its ceiling are entry i.  comb_ceil_kernel as it is: `iota` [p.n_rows] holds
+// 0, 1, ... (launch_anyk_iota) and stands in for the gather table, over the norms, chains and scalars from the first query on;
+// the maxima stay the image's — those of both sides.
+int launch_scan_b16c_xy_ceilings(const ScanB16Problem& p, const ScanB16Comb& c, int64_t q_pos0, int64_t q_row0, const int32_t* iota,
+                                 const float* floor_key, float* ceil, hipStream_t s) {
+  if (p.n_rows <= 0) return MMF_OK;
+  if (!iota || !floor_key || !ceil || q_pos0 < 0 || q_row0 < 0 || q_pos0 + p.n_rows > p.m_pad) {
+    set_error("scan_b16c_xy_ceilings: identity table, floors and ceilings for %lld queries inside the %lld positions", (long long)p.n_rows, (long long)p.m_pad);
+    return MMF_E_INTERNAL;
+  }
+  hipLaunchKernelGGL(comb_ceil_kernel, dim3((unsigned)((p.n_rows + 255) / 256)), dim3(256), 0, s, p.q_zn + q_pos0, p.q_rn + q_pos0, p.q_un + q_pos0,
+                     p.maxima, c.nf + q_row0, c.pn + q_row0, c.max_nf, c.max_pn, c.lambda_h, c.lambda_g, c.dp, p.dp, (int)p.d, iota, p.n_rows,
+                     floor_key, ceil);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
 }  // namespace mmf
 
 using namespace mmf;

@@ -390,3 +390,37 @@ def sharded_simtopk_combined_any_k(f_local: torch.Tensor, p_local: torch.Tensor,
         stats["driver"] = "simple"
         return idx, val, stats
     return idx, val
+
+
+def sharded_simtopk_combined_fast_any_k(f_local: torch.Tensor, p_local: torch.Tensor, n_total: int, *, lambda_h: float = 1.0,
+                                        lambda_g: float = 1.0, k: int = 5, exclude_self: bool = True, precision: str = "fast", group=None,
+                                        gather_output: bool = False, return_stats: bool = False):
+    """sharded_simtopk_combined_any_k on the 16-bit scan of the combined key: the same sharding — one all-gather
+    of the feature shards and one of the position shards — and this rank's rows [lo, hi) through
+    combined_topk16_xy_anyk.simtopk_combined_rows_fast_any_k, which the library sees as a row slice (one operand image; the bits of
+    the unsharded combined_topk_anyk.simtopk_combined_any_k).  precision: "fast" (f16 operands), "fast_bf16", "auto" (= "fast") or
+    "exact".  Returns (idx int64 [N_r, k] GLOBAL row ids, val f32 [N_r, k][, stats dict]); with gather_output the full [n_total, k]
+    result is replicated on every rank.  CPU shards are copied to the current GPU once, after the gather."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    lo, hi = shard_bounds(n_total, world, rank)
+    if f_local.shape[0] != hi - lo or p_local.shape[0] != hi - lo:
+        raise ValueError(f"rank {rank}: shards have {f_local.shape[0]} / {p_local.shape[0]} rows, expected {hi - lo}")
+    f_full = all_gather_rows(f_local, n_total, group) if world > 1 else f_local
+    p_full = all_gather_rows(p_local, n_total, group) if world > 1 else p_local
+    from . import combined_topk16_xy_anyk
+    if not f_full.is_cuda:      # CPU shards: one copy to the device, so that the call still sees views of one array
+        from .build_hypergraph._common import compute_device, to_gpu
+        dev = compute_device(f_full, p_full)
+        f_full, p_full = to_gpu(f_full, dev), to_gpu(p_full, dev)
+    out = combined_topk16_xy_anyk.simtopk_combined_rows_fast_any_k(f_full, p_full, lo, hi, lambda_h, lambda_g, k, exclude_self=exclude_self,
+                                                                   precision=precision, return_stats=return_stats, profile=return_stats)
+    idx, val = out[0].to(f_local.device), out[1].to(f_local.device)
+    if gather_output and world > 1:
+        idx = all_gather_rows(idx, n_total, group)
+        val = all_gather_rows(val, n_total, group)
+    if return_stats:
+        stats = out[2]
+        stats["driver"] = "simple"
+        return idx, val, stats
+    return idx, val
