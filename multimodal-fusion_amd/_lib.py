@@ -176,6 +176,11 @@ TOPK16_ANYK_EXPORTS = ["mmf_simtopk_combined_fast_anyk", "mmf_combined_fast_anyk
 # tests/test_simtopk_combined_xy_fast_anyk_cpu.py.
 TOPK16_XY_ANYK_EXPORTS = ["mmf_simtopk_combined_xy_fast_anyk"]
 
+# Hypergraph propagation on the incidence (include/ext/mmf_hg_hgconv.h): an addition to ABI version 3 in a header of
+# its own.  mmf_incidence_plan_bytes is host-only; the other three enqueue on the caller's stream and never synchronise (the plan's
+# verdict on out-of-range ids is a device status word that the Python layer reads).  Pinned by tests/test_hgconv_cpu.py.
+HGCONV_EXPORTS = ["mmf_incidence_plan_bytes", "mmf_incidence_plan", "mmf_csr_gather_sum", "mmf_hypergraph_propagate"]
+
 
 class FastAnykInfo(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
@@ -310,6 +315,12 @@ def lib() -> ctypes.CDLL:
     L.mmf_combined_fast_anyk_plan.restype = ci
     L.mmf_simtopk_combined_xy_fast_anyk.argtypes = list(L.mmf_simtopk_combined_xy.argtypes) + [ctypes.POINTER(FastAnykInfo)]
     L.mmf_simtopk_combined_xy_fast_anyk.restype = ci
+    L.mmf_incidence_plan_bytes.argtypes = [i64, i64, i64, vp]
+    L.mmf_incidence_plan.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    L.mmf_csr_gather_sum.argtypes = [vp, vp, i64, vp, i64, i64, vp, vp, vp, i64, ci, vp]
+    L.mmf_hypergraph_propagate.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, ci, ci, vp]
+    for name in HGCONV_EXPORTS:
+        getattr(L, name).restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

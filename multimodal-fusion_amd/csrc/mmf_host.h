@@ -29,6 +29,7 @@
 #include "../../include/ext/mmf_hg_segw_anyk.h"
 #include "../../include/ext/mmf_hg_topk16_anyk.h"
 #include "../../include/ext/mmf_hg_topk16_xy_anyk.h"
+#include "../../include/ext/mmf_hg_hgconv.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 
