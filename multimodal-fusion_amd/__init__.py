@@ -28,6 +28,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.combined_topk16_anyk.*                    the any-k top-k of K_h * K_g from the 16-bit scan of the combined key (one graph or a batch), bit for bit, and the router
     mmf.combined_topk16_xy_anyk.*                 that any-k 16-bit top-k of K_h * K_g for two node sets or rows [lo, hi) of one graph, bit for bit, and the routers
     mmf.hgconv.*                                  hypergraph propagation D^-1 H W B^-1 H^T x on an incidence (the reference model's HypergraphConv), bit-stable gather-sums over a reusable plan
+    mmf.readout.*                                 the attention readout over a ragged batch (the reference model's GlobalAttention), bit-stable chains, and HypergraphNetwork on top
     mmf.kmeans_ragged.*                           scikit-learn's KMeans fit for every block of a flat buffer in one call, each block with a width of its own
     mmf.wide_scan.*                               what the wide 16-bit scan (feature dims 1025..4096) covers: host-only queries
     mmf.cohort.build_cohort_hypergraphs(...)      the four steps of process_single_file for every slide of a cohort, in memory
@@ -110,6 +111,12 @@ from .combined_topk16_xy_anyk import simtopk_combined_rows_fast_any_k, simtopk_c
 from . import hgconv  # noqa: F401,E402
 from .hgconv import HypergraphConv, hypergraph_propagate, incidence_plan, knn_incidence  # noqa: F401,E402
 
+from . import readout  # noqa: F401,E402
+from .readout import GlobalAttention, attention_readout, readout_plan  # noqa: F401,E402
+
+from . import hypergraph_network  # noqa: F401,E402
+from .hypergraph_network import HypergraphNetwork  # noqa: F401,E402
+
 from . import wide_scan  # noqa: F401,E402
 from .wide_scan import list_capacity, wide_scan_supported  # noqa: F401,E402
 
@@ -138,4 +145,5 @@ __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combin
            "combined_topk16_anyk", "simtopk_combined_fast_any_k", "combined_fast_anyk_plan",
            "build_topk_weighted_hypergraph_fast_any_k", "build_topk_hypergraph_data_fast_any_k",
            "combined_topk16_xy_anyk", "simtopk_combined_xy_fast_any_k", "simtopk_combined_rows_fast_any_k",
-           "hgconv", "incidence_plan", "hypergraph_propagate", "knn_incidence", "HypergraphConv"]
+           "hgconv", "incidence_plan", "hypergraph_propagate", "knn_incidence", "HypergraphConv",
+           "readout", "attention_readout", "readout_plan", "GlobalAttention", "hypergraph_network", "HypergraphNetwork"]

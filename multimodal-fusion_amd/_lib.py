@@ -181,6 +181,11 @@ TOPK16_XY_ANYK_EXPORTS = ["mmf_simtopk_combined_xy_fast_anyk"]
 # verdict on out-of-range ids is a device status word that the Python layer reads).  Pinned by tests/test_hgconv_cpu.py.
 HGCONV_EXPORTS = ["mmf_incidence_plan_bytes", "mmf_incidence_plan", "mmf_csr_gather_sum", "mmf_hypergraph_propagate"]
 
+# The attention readout over a ragged batch (include/ext/mmf_hg_readout.h): an addition to ABI version 3 in a header
+# of its own.  mmf_attention_readout_table is host-only; the other two enqueue on the caller's stream and never synchronise.  Pinned
+# by tests/test_readout_cpu.py.
+READOUT_EXPORTS = ["mmf_attention_readout_table", "mmf_attention_readout", "mmf_attention_readout_backward"]
+
 
 class FastAnykInfo(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
@@ -321,6 +326,12 @@ def lib() -> ctypes.CDLL:
     L.mmf_hypergraph_propagate.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, ci, ci, vp]
     for name in HGCONV_EXPORTS:
         getattr(L, name).restype = ci
+    L.mmf_attention_readout_table.argtypes = [vp, i64, vp, i64]
+    L.mmf_attention_readout_table.restype = i64
+    L.mmf_attention_readout.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, ci, vp]
+    L.mmf_attention_readout.restype = ci
+    L.mmf_attention_readout_backward.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ci, vp]
+    L.mmf_attention_readout_backward.restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)
