@@ -186,6 +186,12 @@ HGCONV_EXPORTS = ["mmf_incidence_plan_bytes", "mmf_incidence_plan", "mmf_csr_gat
 # by tests/test_readout_cpu.py.
 READOUT_EXPORTS = ["mmf_attention_readout_table", "mmf_attention_readout", "mmf_attention_readout_backward"]
 
+# Pair-weighted hypergraph propagation and the softmax over the pairs of a row (include/ext/mmf_hg_hgpair.h): an
+# addition to ABI version 3 in a header of its own.  All six enqueue on the caller's stream and never synchronise.  Pinned by
+# tests/test_hgpair_cpu.py.
+HGPAIR_EXPORTS = ["mmf_incidence_pair_plan", "mmf_pair_scales", "mmf_hypergraph_propagate_pairs", "mmf_pair_weight_grad", "mmf_pair_softmax",
+                  "mmf_pair_softmax_backward"]
+
 
 class FastAnykInfo(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
@@ -332,6 +338,14 @@ def lib() -> ctypes.CDLL:
     L.mmf_attention_readout.restype = ci
     L.mmf_attention_readout_backward.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ci, vp]
     L.mmf_attention_readout_backward.restype = ci
+    L.mmf_incidence_pair_plan.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    L.mmf_pair_scales.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, ci, vp]
+    L.mmf_hypergraph_propagate_pairs.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, vp, vp, ci, ci, vp]
+    L.mmf_pair_weight_grad.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, i64, i64, vp, ci, vp]
+    L.mmf_pair_softmax.argtypes = [vp, vp, i64, i64, vp, vp, ci, vp]
+    L.mmf_pair_softmax_backward.argtypes = [vp, vp, i64, i64, vp, vp, vp, ci, vp]
+    for name in HGPAIR_EXPORTS:
+        getattr(L, name).restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):
         fn = getattr(L, name)

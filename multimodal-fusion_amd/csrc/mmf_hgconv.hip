@@ -19,11 +19,11 @@
 
 #include "mmf_dev.h"
 #include "mmf_host.h"
+#include "mmf_hgshare.h"
 
 namespace mmf {
 
 constexpr int HG_BATCH = 8;            // members whose gathers are in flight before their adds
-constexpr int64_t HG_LIMIT = (int64_t)1 << 31;
 
 // ---- plan ---------------------------------------------------------------------------------------------------------------------------
 // status [2] (memset to all ones before): lowest column with a bad node id, lowest column with a bad hyperedge id.
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void hg_scales_kernel(const int64_t* __restric
   }
 }
 
-static int key_bits(int64_t N, int64_t M) {
+int hg_key_bits(int64_t N, int64_t M) {
   const unsigned long long last = (unsigned long long)N * (unsigned long long)M;
   int bits = 1;
   while (bits < 64 && (last >> bits) != 0) ++bits;
@@ -105,24 +105,6 @@ struct GatherSumArgs {
   const float* scale; const float* scale2;
   float* out; int64_t out_stride;
   int lg;                     // log2 of the lanes per row (FULL: 6)
-};
-
-template <int VEC> struct HgVec;
-template <> struct HgVec<4> {
-  typedef float4 T;
-  static __device__ __forceinline__ T zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-  static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4*>(p); }
-  static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<float4*>(p) = v; }
-  static __device__ __forceinline__ T add(T a, T b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-  static __device__ __forceinline__ T mul(T a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-};
-template <> struct HgVec<1> {
-  typedef float T;
-  static __device__ __forceinline__ T zero() { return 0.f; }
-  static __device__ __forceinline__ T load(const float* p) { return *p; }
-  static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
-  static __device__ __forceinline__ T add(T a, T b) { return a + b; }
-  static __device__ __forceinline__ T mul(T a, float s) { return a * s; }
 };
 
 // VEC = 4: C, both row pitches and both bases are multiples of four floats; VEC = 1: any C, any pitch.  FULL: one wave per row.
@@ -190,7 +172,7 @@ static int launch_gather_sum(const int64_t* ptr, const int32_t* col, int64_t row
   return MMF_OK;
 }
 
-static int check_sizes(const char* who, int64_t N, int64_t M, int64_t E) {
+int hg_check_sizes(const char* who, int64_t N, int64_t M, int64_t E) {
   if (N < 0 || M < 0 || E < 0) {
     set_error("%s: num_nodes, num_edges and the pair count must be >= 0 (got %lld, %lld, %lld)", who, (long long)N, (long long)M, (long long)E);
     return MMF_E_INVALID;
@@ -202,6 +184,29 @@ static int check_sizes(const char* who, int64_t N, int64_t M, int64_t E) {
   return MMF_OK;
 }
 
+// the plan's steps as launches (mmf_hgshare.h): mmf_incidence_plan below and mmf_incidence_pair_plan (mmf_hgpair.hip) enqueue the same
+int hg_launch_keys(const int64_t* edge_index, int64_t E, int64_t N, int64_t M, unsigned long long* k_edge, unsigned long long* k_node,
+                   int64_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(hg_keys_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, edge_index, E, N, M, k_edge, k_node,
+                     reinterpret_cast<unsigned long long*>(status));
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
+int hg_launch_csr(const unsigned long long* sorted, int64_t E, unsigned long long last, unsigned long long inner, int64_t R, int64_t* ptr,
+                  int32_t* mem, hipStream_t s) {
+  hipLaunchKernelGGL(hg_csr_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, s, sorted, E, last, inner, R, ptr, mem);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
+int hg_launch_scales(const int64_t* eptr, int64_t M, const int64_t* nptr, const int32_t* nmem, int64_t N, const float* w, float* edge_scale,
+                     float* node_scale, hipStream_t s) {
+  hipLaunchKernelGGL(hg_scales_kernel, dim3((unsigned)((M + N + 255) / 256)), dim3(256), 0, s, eptr, M, nptr, nmem, N, w, edge_scale, node_scale);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
 }  // namespace mmf
 
 using namespace mmf;
@@ -210,7 +215,7 @@ extern "C" {
 
 int mmf_incidence_plan_bytes(int64_t num_nodes, int64_t num_edges, int64_t num_pairs, int64_t* bytes_out) {
   const char* who = "incidence_plan_bytes";
-  MMF_TRY(check_sizes(who, num_nodes, num_edges, num_pairs));
+  MMF_TRY(hg_check_sizes(who, num_nodes, num_edges, num_pairs));
   if (!bytes_out) { set_error("%s: bytes_out is NULL", who); return MMF_E_INVALID; }
   bytes_out[0] = (num_edges + 1) * 8;      // eptr int64 [M + 1]
   bytes_out[1] = num_pairs * 4;            // emem int32 [E]
@@ -227,14 +232,14 @@ int mmf_incidence_plan(const int64_t* edge_index, int64_t num_pairs, int64_t num
   Call c("incidence_plan", device_id, hip_stream);
   MMF_TRY(c.on_device());
   const int64_t N = num_nodes, M = num_edges, E = num_pairs;
-  MMF_TRY(check_sizes(c.who, N, M, E));
+  MMF_TRY(hg_check_sizes(c.who, N, M, E));
   if (!eptr || !nptr || !status || (E > 0 && (!edge_index || !emem || !nmem)) || (M > 0 && !edge_scale) || (N > 0 && !node_scale)) {
     set_error("%s: NULL pointer", c.who);
     return MMF_E_INVALID;
   }
   MMF_TRY(c.begin());
   const hipStream_t s = c.s;
-  const int bits = key_bits(N, M);
+  const int bits = hg_key_bits(N, M);
   const size_t temp = E > 0 ? hg_sort_temp(E, bits, s) : 0;
   MMF_TRY(c.workspace(3 * ws_bytes((size_t)E + 1, 8) + temp + 256, &c.ws));
   unsigned long long* k_edge = c.ws.take<unsigned long long>((size_t)E + 1);
@@ -243,27 +248,18 @@ int mmf_incidence_plan(const int64_t* edge_index, int64_t num_pairs, int64_t num
   void* sort_tmp = c.ws.take<char>(temp + 1);
   MMF_HIP(hipMemsetAsync(status, 0xff, 16, s));
   const unsigned long long last = (unsigned long long)N * (unsigned long long)M;
-  const unsigned grid_e = (unsigned)((E + 1 + 255) / 256);
   if (E > 0) {
-    hipLaunchKernelGGL(hg_keys_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, edge_index, E, N, M, k_edge, k_node,
-                       reinterpret_cast<unsigned long long*>(status));
-    MMF_LAUNCH_CHECK();
+    MMF_TRY(hg_launch_keys(edge_index, E, N, M, k_edge, k_node, status, s));
     size_t tb = temp;
     MMF_HIP(hipcub::DeviceRadixSort::SortKeys(sort_tmp, tb, k_edge, sorted, (int)E, 0, bits, s));
   }
-  hipLaunchKernelGGL(hg_csr_kernel, dim3(grid_e), dim3(256), 0, s, sorted, E, last, (unsigned long long)N, M, eptr, emem);
-  MMF_LAUNCH_CHECK();
+  MMF_TRY(hg_launch_csr(sorted, E, last, (unsigned long long)N, M, eptr, emem, s));
   if (E > 0) {
     size_t tb = temp;
     MMF_HIP(hipcub::DeviceRadixSort::SortKeys(sort_tmp, tb, k_node, sorted, (int)E, 0, bits, s));
   }
-  hipLaunchKernelGGL(hg_csr_kernel, dim3(grid_e), dim3(256), 0, s, sorted, E, last, (unsigned long long)M, N, nptr, nmem);
-  MMF_LAUNCH_CHECK();
-  if (M + N > 0) {
-    hipLaunchKernelGGL(hg_scales_kernel, dim3((unsigned)((M + N + 255) / 256)), dim3(256), 0, s, eptr, M, nptr, nmem, N, hyperedge_weight,
-                       edge_scale, node_scale);
-    MMF_LAUNCH_CHECK();
-  }
+  MMF_TRY(hg_launch_csr(sorted, E, last, (unsigned long long)M, N, nptr, nmem, s));
+  if (M + N > 0) MMF_TRY(hg_launch_scales(eptr, M, nptr, nmem, N, hyperedge_weight, edge_scale, node_scale, s));
   return MMF_OK;
 }
 
@@ -288,7 +284,7 @@ int mmf_hypergraph_propagate(const int64_t* eptr, const int32_t* emem, const int
   Call c("hypergraph_propagate", device_id, hip_stream);
   MMF_TRY(c.on_device());
   const int64_t N = num_nodes, M = num_edges, C = channels;
-  MMF_TRY(check_sizes(c.who, N, M, 0));
+  MMF_TRY(hg_check_sizes(c.who, N, M, 0));
   if (C < 0 || C >= HG_LIMIT || x_stride < C) {
     set_error("%s: channels must lie in [0, 2^31) and the row pitch of x be at least `channels` (got %lld, %lld)", c.who, (long long)C, (long long)x_stride);
     return MMF_E_INVALID;

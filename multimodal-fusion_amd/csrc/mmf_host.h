@@ -31,6 +31,7 @@
 #include "../../include/ext/mmf_hg_topk16_xy_anyk.h"
 #include "../../include/ext/mmf_hg_hgconv.h"
 #include "../../include/ext/mmf_hg_readout.h"
+#include "../../include/ext/mmf_hg_hgpair.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 

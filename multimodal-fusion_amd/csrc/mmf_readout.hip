@@ -17,6 +17,7 @@
 // No fma (the build has -ffp-contract=off), no atomics on floats, no runtime exponential: cexp below is the header's definition.
 #include "mmf_dev.h"
 #include "mmf_host.h"
+#include "mmf_hgshare.h"
 
 namespace mmf {
 
@@ -25,34 +26,7 @@ constexpr int RO_BATCH = 8;            // rows whose loads are in flight before 
 constexpr int RO_ROWS = 4;             // backward: rows per lane group in flight
 constexpr int64_t RO_LIMIT = (int64_t)1 << 31;
 
-// ---- the header's scalar definitions --------------------------------------------------------------------------------------------
-constexpr float RO_LOG2E = 1.4426950408889634f;
-constexpr float RO_LN2_HI = 0.693145751953125f;
-constexpr float RO_LN2_LO = 1.428606765330187e-06f;
-constexpr float RO_C2 = (float)(1.0 / 2), RO_C3 = (float)(1.0 / 6), RO_C4 = (float)(1.0 / 24), RO_C5 = (float)(1.0 / 120),
-                RO_C6 = (float)(1.0 / 720), RO_C7 = (float)(1.0 / 5040);
-
-__device__ __forceinline__ float ro_cexp(float t) {
-  if (t < -87.0f) return 0.0f;
-  const float n = rintf(t * RO_LOG2E);
-  const float r = (t - n * RO_LN2_HI) - n * RO_LN2_LO;
-  float p = RO_C7;
-  p = p * r; p = p + RO_C6;
-  p = p * r; p = p + RO_C5;
-  p = p * r; p = p + RO_C4;
-  p = p * r; p = p + RO_C3;
-  p = p * r; p = p + RO_C2;
-  p = p * r; p = p + 1.0f;
-  p = p * r; p = p + 1.0f;
-  return p * __int_as_float(((int)n + 127) << 23);
-}
-
-// float -> unsigned key with the order of the floats (-0 < +0), and back
-__device__ __forceinline__ uint32_t ro_key(float g) {
-  const uint32_t u = __float_as_uint(g);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ro_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+// the header's scalar definitions (cexp, the float keys) and the dot64 tree: mmf_hgshare.h
 
 // A record of the chunk table, checked against the offsets before anything is addressed with it: a record that does not lie inside
 // its segment (a table that belongs to other offsets) is skipped, it reads and writes nothing.
@@ -225,13 +199,6 @@ __global__ __launch_bounds__(256) void ro_alpha_kernel(const int64_t* __restrict
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------------------
-// the halving tree of dot64 over a group of L lanes (L < 64 only when C <= L: the levels left out would add +0 to partials that
-// are never -0); lane 0 of the group ends with the value
-__device__ __forceinline__ float ro_tree(float p, int L) {
-  for (int h = L >> 1; h >= 1; h >>= 1) p = p + __shfl_down(p, h, L);
-  return p;
-}
-
 template <bool GATE>
 __global__ __launch_bounds__(256) void ro_backward_kernel(const float* __restrict__ x, int64_t x_stride, const float* __restrict__ alpha,
                                                           const int64_t* __restrict__ ptr, const int32_t* __restrict__ table,

@@ -22,7 +22,7 @@ from . import ops
 
 __all__ = ["IncidencePlan", "incidence_plan", "hypergraph_propagate", "knn_incidence", "HypergraphConv"]
 
-_LIMIT = 2 ** 31
+LIMIT = 2 ** 31
 
 
 class IncidencePlan:
@@ -57,7 +57,7 @@ class IncidencePlan:
         return self
 
 
-def _check_edge_index(edge_index, what: str) -> None:
+def check_edge_index(edge_index, what: str) -> None:
     if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
         raise ValueError(f"{what}: edge_index must be an int64 tensor of shape [2, E]"
                          f" (got {tuple(edge_index.shape) if isinstance(edge_index, torch.Tensor) else type(edge_index).__name__})")
@@ -65,7 +65,7 @@ def _check_edge_index(edge_index, what: str) -> None:
         raise ValueError(f"{what}: edge_index must be int64 (got {edge_index.dtype})")
     if not edge_index.is_contiguous():
         raise ValueError(f"{what}: edge_index must be contiguous (row 0 the node ids, row 1 the hyperedge ids)")
-    if edge_index.shape[1] >= _LIMIT:
+    if edge_index.shape[1] >= LIMIT:
         raise ValueError(f"{what}: {edge_index.shape[1]} pairs: the pair count must stay below 2^31")
 
 
@@ -82,6 +82,29 @@ def _check_weight(w, num_edges: Optional[int], dev: torch.device, what: str) -> 
         raise ValueError(f"{what}: hyperedge_weight is on {w.device}, edge_index on {dev}")
 
 
+def plan_arguments(edge_index, num_nodes, num_edges, hyperedge_weight, what: str):
+    """The checks of a plan build, before any device work, and its sizes: (N, M, E, contiguous hyperedge_weight or None).
+    ``num_edges=None`` costs the one host read of max + 1."""
+    check_edge_index(edge_index, what)
+    N = int(num_nodes)
+    if N < 0 or N >= LIMIT:
+        raise ValueError(f"{what}: num_nodes must lie in [0, 2^31) (got {N})")
+    if num_edges is not None and not 0 <= int(num_edges) < LIMIT:
+        raise ValueError(f"{what}: num_edges must lie in [0, 2^31) (got {num_edges})")
+    dev = edge_index.device
+    _check_weight(hyperedge_weight, None if num_edges is None else int(num_edges), dev, what)
+    E = edge_index.shape[1]
+    if num_edges is None:
+        M = int(edge_index[1].max()) + 1 if E else 0                    # the one host read
+        if not 0 <= M < LIMIT:
+            raise ValueError(f"{what}: the largest hyperedge id gives num_edges = {M}, outside [0, 2^31)")
+        _check_weight(hyperedge_weight, M, dev, what)
+    else:
+        M = int(num_edges)
+    ops._need_gpu(edge_index, what)
+    return N, M, E, None if hyperedge_weight is None else hyperedge_weight.contiguous()
+
+
 def incidence_plan(edge_index: torch.Tensor, num_nodes: int, num_edges: Optional[int] = None,
                    hyperedge_weight: Optional[torch.Tensor] = None, *, check: bool = True) -> IncidencePlan:
     """The plan of ``edge_index`` int64 [2, E] (row 0 node ids in [0, num_nodes), row 1 hyperedge ids in [0, num_edges)); a pair
@@ -91,24 +114,8 @@ def incidence_plan(edge_index: torch.Tensor, num_nodes: int, num_edges: Optional
     ``check=True`` reads the plan's status word (one host synchronisation) and raises ValueError for an id outside its range;
     ``check=False`` returns without waiting for the stream (``plan.check()`` does the read later)."""
     what = "incidence_plan"
-    _check_edge_index(edge_index, what)
-    N = int(num_nodes)
-    if N < 0 or N >= _LIMIT:
-        raise ValueError(f"{what}: num_nodes must lie in [0, 2^31) (got {N})")
-    if num_edges is not None and not 0 <= int(num_edges) < _LIMIT:
-        raise ValueError(f"{what}: num_edges must lie in [0, 2^31) (got {num_edges})")
+    N, M, E, w = plan_arguments(edge_index, num_nodes, num_edges, hyperedge_weight, what)
     dev = edge_index.device
-    _check_weight(hyperedge_weight, None if num_edges is None else int(num_edges), dev, what)
-    E = edge_index.shape[1]
-    if num_edges is None:
-        M = int(edge_index[1].max()) + 1 if E else 0                    # the one host read
-        if not 0 <= M < _LIMIT:
-            raise ValueError(f"{what}: the largest hyperedge id gives num_edges = {M}, outside [0, 2^31)")
-        _check_weight(hyperedge_weight, M, dev, what)
-    else:
-        M = int(num_edges)
-    ops._need_gpu(edge_index, what)
-    w = None if hyperedge_weight is None else hyperedge_weight.contiguous()
     eptr = torch.empty((M + 1,), dtype=torch.int64, device=dev)
     nptr = torch.empty((N + 1,), dtype=torch.int64, device=dev)
     emem = torch.empty((E,), dtype=torch.int32, device=dev)
@@ -134,7 +141,7 @@ def _run(plan: IncidencePlan, x: torch.Tensor, transpose: bool):
     return out, Y
 
 
-def _rows(x: torch.Tensor) -> torch.Tensor:
+def unit_stride_rows(x: torch.Tensor) -> torch.Tensor:
     """x as the kernel reads it: unit column stride and a row pitch of at least C (a row slice of a larger tensor stays a view)."""
     n, c = x.shape
     if n == 0 or c == 0 or (c > 1 and x.stride(1) != 1) or (n > 1 and x.stride(0) < c):
@@ -145,7 +152,7 @@ def _rows(x: torch.Tensor) -> torch.Tensor:
 class _Propagate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, plan):
-        out, Y = _run(plan, _rows(x.detach()), False)
+        out, Y = _run(plan, unit_stride_rows(x.detach()), False)
         ctx.plan = plan
         ctx.mark_non_differentiable(Y)
         return out, Y
@@ -182,13 +189,13 @@ def hypergraph_propagate(x: torch.Tensor, edge_index: Optional[torch.Tensor] = N
         if plan.device != x.device:
             raise ValueError(f"{what}: the plan is on {plan.device}, x on {x.device}")
     else:
-        _check_edge_index(edge_index, what)
+        check_edge_index(edge_index, what)
         if edge_index.device != x.device:
             raise ValueError(f"{what}: edge_index is on {edge_index.device}, x on {x.device}")
         _check_weight(hyperedge_weight, None if num_edges is None else int(num_edges), x.device, what)
         plan = incidence_plan(edge_index, x.shape[0], num_edges, hyperedge_weight)
     ops._need_gpu(x, what)
-    if x.shape[1] >= _LIMIT:
+    if x.shape[1] >= LIMIT:
         raise ValueError(f"{what}: {x.shape[1]} channels: must stay below 2^31")
     out, Y = _Propagate.apply(x, plan)
     return (out, Y) if return_edge_features else out
