@@ -30,6 +30,7 @@ shim at the repo root:  ``import multimodal_fusion_amd as mmf``.
     mmf.hgconv.*                                  hypergraph propagation D^-1 H W B^-1 H^T x on an incidence (the reference model's HypergraphConv), bit-stable gather-sums over a reusable plan
     mmf.readout.*                                 the attention readout over a ragged batch (the reference model's GlobalAttention), bit-stable chains, and HypergraphNetwork on top
     mmf.hgpair.*                                  that propagation with one weight per (node, hyperedge) pair (the builders' edge_weights), the softmax over the pairs of a hyperedge or node, and the attention convolution on top
+    mmf.hg16.*                                    those three for float16 / bfloat16 x (what torch.autocast hands a layer): 16-bit storage, float32 chains, one rounding per stored tensor
     mmf.kmeans_ragged.*                           scikit-learn's KMeans fit for every block of a flat buffer in one call, each block with a width of its own
     mmf.wide_scan.*                               what the wide 16-bit scan (feature dims 1025..4096) covers: host-only queries
     mmf.cohort.build_cohort_hypergraphs(...)      the four steps of process_single_file for every slide of a cohort, in memory
@@ -122,6 +123,9 @@ from . import hgpair  # noqa: F401,E402
 from .hgpair import (HypergraphAttentionConv, IncidencePairPlan, PairWeightedHypergraphConv, hypergraph_propagate_pairs,  # noqa: F401,E402
                      incidence_pair_plan, pair_scales, pair_softmax)
 
+from . import hg16  # noqa: F401,E402
+from .hg16 import attention_readout_16, hypergraph_propagate_16, hypergraph_propagate_pairs_16  # noqa: F401,E402
+
 from . import wide_scan  # noqa: F401,E402
 from .wide_scan import list_capacity, wide_scan_supported  # noqa: F401,E402
 
@@ -153,4 +157,5 @@ __all__ = ["ops", "simtopk", "simtopk_segmented", "sim_dense", "sim_dense_combin
            "hgconv", "incidence_plan", "hypergraph_propagate", "knn_incidence", "HypergraphConv",
            "readout", "attention_readout", "readout_plan", "GlobalAttention", "hypergraph_network", "HypergraphNetwork",
            "hgpair", "incidence_pair_plan", "IncidencePairPlan", "pair_scales", "hypergraph_propagate_pairs", "pair_softmax",
-           "PairWeightedHypergraphConv", "HypergraphAttentionConv"]
+           "PairWeightedHypergraphConv", "HypergraphAttentionConv",
+           "hg16", "hypergraph_propagate_16", "hypergraph_propagate_pairs_16", "attention_readout_16"]

@@ -192,6 +192,12 @@ READOUT_EXPORTS = ["mmf_attention_readout_table", "mmf_attention_readout", "mmf_
 HGPAIR_EXPORTS = ["mmf_incidence_pair_plan", "mmf_pair_scales", "mmf_hypergraph_propagate_pairs", "mmf_pair_weight_grad", "mmf_pair_softmax",
                   "mmf_pair_softmax_backward"]
 
+# 16-bit activations for the hypergraph branch (include/ext/mmf_hg_hg16.h): f16 / bf16 x, f32 chains, one rounding
+# per stored tensor.  An addition to ABI version 3 in a header of its own.  All five enqueue on the caller's stream and never
+# synchronise.  Pinned by tests/test_hg16_cpu.py.
+HG16_EXPORTS = ["mmf_csr_gather_sum_16", "mmf_hypergraph_propagate_16", "mmf_pair_weight_grad_16", "mmf_attention_readout_16",
+                "mmf_attention_readout_backward_16"]
+
 
 class FastAnykInfo(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("yield_", ctypes.c_int32 * FAST_ANYK_MAX_PASSES),
@@ -345,6 +351,13 @@ def lib() -> ctypes.CDLL:
     L.mmf_pair_softmax.argtypes = [vp, vp, i64, i64, vp, vp, ci, vp]
     L.mmf_pair_softmax_backward.argtypes = [vp, vp, i64, i64, vp, vp, vp, ci, vp]
     for name in HGPAIR_EXPORTS:
+        getattr(L, name).restype = ci
+    L.mmf_csr_gather_sum_16.argtypes = [vp, vp, vp, vp, i64, vp, i64, i64, ci, vp, vp, vp, vp, vp, i64, ci, vp]
+    L.mmf_hypergraph_propagate_16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, ci, vp, vp, vp, ci, ci, vp]
+    L.mmf_pair_weight_grad_16.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, i64, i64, ci, vp, ci, vp]
+    L.mmf_attention_readout_16.argtypes = [vp, i64, ci, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, ci, vp]
+    L.mmf_attention_readout_backward_16.argtypes = [vp, i64, ci, vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ci, vp]
+    for name in HG16_EXPORTS:
         getattr(L, name).restype = ci
     for name in (EXPORTS + EXPORTS_COHORT + EXPORTS_POOL + EXPORTS_STREAM + EXPORTS_TOPK + EXPORTS_WIDE + EXPORTS_WIDE_SEG + EXPORTS_TOPK16 +
                  EXPORTS_TOPK16_SEG + EXPORTS_TOPK_XY):

@@ -18,7 +18,7 @@ PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 OUT = os.path.join(PKG, "libmmf_hg.so")
 OBJ = os.path.join(HERE, "_obj")
-SOURCES = ["mmf_api.hip", "mmf_prep.hip", "mmf_scan_f32.hip", "mmf_scan_bf16.hip", "mmf_scan_b16w.hip", "mmf_scan_b16c.hip", "mmf_select.hip", "mmf_edges.hip", "mmf_segments.hip", "mmf_knn_clique.hip", "mmf_direct.hip", "mmf_kmeans.hip", "mmf_order.hip", "mmf_pool.hip", "mmf_stream_stats.hip", "mmf_topk.hip", "mmf_fast_anyk.hip", "mmf_topk_anyk.hip", "mmf_hgconv.hip", "mmf_readout.hip", "mmf_hgpair.hip"]
+SOURCES = ["mmf_api.hip", "mmf_prep.hip", "mmf_scan_f32.hip", "mmf_scan_bf16.hip", "mmf_scan_b16w.hip", "mmf_scan_b16c.hip", "mmf_select.hip", "mmf_edges.hip", "mmf_segments.hip", "mmf_knn_clique.hip", "mmf_direct.hip", "mmf_kmeans.hip", "mmf_order.hip", "mmf_pool.hip", "mmf_stream_stats.hip", "mmf_topk.hip", "mmf_fast_anyk.hip", "mmf_topk_anyk.hip", "mmf_hgconv.hip", "mmf_readout.hip", "mmf_hgpair.hip", "mmf_hg16.hip"]
 HEADERS = ["mmf_dev.h", "mmf_host.h", "mmf_rerank_combined.h", "mmf_hgshare.h", os.path.join(ROOT, "include", "mmf_hg.h"), os.path.join(ROOT, "include", "mmf_hg_pool.h"),
            os.path.join(ROOT, "include", "mmf_hg_stream.h"), os.path.join(ROOT, "include", "mmf_hg_topk.h"), os.path.join(ROOT, "include", "mmf_hg_topk16.h"),
            os.path.join(ROOT, "include", "mmf_hg_wide.h"), os.path.join(ROOT, "include", "mmf_hg_wide_seg.h"),
@@ -31,7 +31,7 @@ HEADERS = ["mmf_dev.h", "mmf_host.h", "mmf_rerank_combined.h", "mmf_hgshare.h", 
            os.path.join(ROOT, "include", "ext", "mmf_hg_cross_segw_anyk.h"), os.path.join(ROOT, "include", "ext", "mmf_hg_segw_anyk.h"),
            os.path.join(ROOT, "include", "ext", "mmf_hg_topk16_anyk.h"), os.path.join(ROOT, "include", "ext", "mmf_hg_topk16_xy_anyk.h"),
            os.path.join(ROOT, "include", "ext", "mmf_hg_hgconv.h"), os.path.join(ROOT, "include", "ext", "mmf_hg_readout.h"),
-           os.path.join(ROOT, "include", "ext", "mmf_hg_hgpair.h")]
+           os.path.join(ROOT, "include", "ext", "mmf_hg_hgpair.h"), os.path.join(ROOT, "include", "ext", "mmf_hg_hg16.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]

@@ -1,9 +1,12 @@
-// mmf_hgshare.h — what mmf_hgconv.hip, mmf_readout.hip and mmf_hgpair.hip share: the device helpers whose arithmetic is part of a
-// header's rule (the canonical exponential and the dot64 tree of include/ext/mmf_hg_readout.h, the float4 / float row vector of the
-// gather-sums), and the host helpers of the incidence plan that live in mmf_hgconv.hip.
+// mmf_hgshare.h — what mmf_hgconv.hip, mmf_readout.hip, mmf_hgpair.hip and mmf_hg16.hip share: the device helpers whose arithmetic is
+// part of a header's rule (the canonical exponential and the dot64 tree of include/ext/mmf_hg_readout.h, the float4 / float row
+// vector of the gather-sums, the widening, the rounding r16 and the 8-wide row vector of include/ext/mmf_hg_hg16.h), the chunk record
+// of the readout, and the host helpers of the incidence plan (mmf_hgconv.hip) and of the readout (mmf_readout.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../include/mmf_hg.h"
 
 namespace mmf {
 
@@ -61,6 +64,80 @@ template <> struct HgVec<1> {
   static __device__ __forceinline__ T add(T a, T b) { return a + b; }
   static __device__ __forceinline__ T mul(T a, float s) { return a * s; }
 };
+
+// ---- 16-bit storage, f32 arithmetic (include/ext/mmf_hg_hg16.h) -------------------------------------------------------------------
+// DT = MMF_F16 / MMF_BF16.  widen is exact; r16 is round-to-nearest-even of a finite f32: for bf16 on the bits (the header's formula),
+// for f16 the device's conversion, which keeps subnormals and overflows to infinity under the build's flags (the f16 denormal mode of
+// a kernel is always IEEE; tests/test_gpu_hg16.py pins both).  That conversion is written as the instruction itself: as a cast, the
+// compiler folds the f32 multiply or add in front of it into v_fma_mixlo_f16, which rounds the exact result once to f16 — not the
+// rule's rounded f32 operation followed by r16 (2 of 38016 values of a readout's grad_x differed that way).
+template <int DT> struct H16;
+template <> struct H16<MMF_BF16> {
+  static __device__ __forceinline__ float widen(uint32_t b) { return __uint_as_float(b << 16); }
+  static __device__ __forceinline__ uint32_t r16(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+  }
+};
+template <> struct H16<MMF_F16> {
+  static __device__ __forceinline__ float widen(uint32_t b) { return (float)__builtin_bit_cast(_Float16, (uint16_t)b); }
+  static __device__ __forceinline__ uint32_t r16(float f) {
+    uint32_t h;
+    asm("v_cvt_f16_f32_e32 %0, %1" : "=v"(h) : "v"(f));
+    return h & 0xffffu;
+  }
+};
+
+// a lane's share of a 16-bit row as it is loaded and stored: eight columns in one 16-byte access, or one column
+template <int VEC> struct Raw16;
+template <> struct Raw16<8> {
+  uint4 q;
+  static __device__ __forceinline__ Raw16 zero() { return {make_uint4(0u, 0u, 0u, 0u)}; }
+  static __device__ __forceinline__ Raw16 load(const uint16_t* p) { return {*reinterpret_cast<const uint4*>(p)}; }
+  __device__ __forceinline__ uint32_t get(int i) const {
+    const uint32_t w = (i >> 1) == 0 ? q.x : (i >> 1) == 1 ? q.y : (i >> 1) == 2 ? q.z : q.w;
+    return (i & 1) ? (w >> 16) : (w & 0xffffu);
+  }
+  static __device__ __forceinline__ void store(uint16_t* p, const uint32_t* h) {
+    *reinterpret_cast<uint4*>(p) = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+  }
+};
+template <> struct Raw16<1> {
+  uint16_t q;
+  static __device__ __forceinline__ Raw16 zero() { return {(uint16_t)0}; }
+  static __device__ __forceinline__ Raw16 load(const uint16_t* p) { return {*p}; }
+  __device__ __forceinline__ uint32_t get(int) const { return q; }
+  static __device__ __forceinline__ void store(uint16_t* p, const uint32_t* h) { *p = (uint16_t)h[0]; }
+};
+
+// ---- the readout's chunk record (mmf_readout.hip, mmf_hg16.hip) -------------------------------------------------------------------
+constexpr int RO_BATCH = 8;            // rows whose loads are in flight before their multiply-adds
+constexpr int RO_ROWS = 4;             // backward: rows per lane group in flight
+constexpr int64_t RO_LIMIT = (int64_t)1 << 31;
+
+// A record of the chunk table, checked against the offsets before anything is addressed with it: a record that does not lie inside
+// its segment (a table that belongs to other offsets) is skipped, it reads and writes nothing.
+struct RoChunk { int s; int64_t row; int cnt; bool first; };
+__device__ __forceinline__ bool ro_chunk(const int32_t* __restrict__ table, const int64_t* __restrict__ ptr, int64_t ch, int64_t S, int64_t N,
+                                         RoChunk& k) {
+  k.s = table[2 * ch];
+  k.row = table[2 * ch + 1];
+  if (k.s < 0 || k.s >= S) return false;
+  const int64_t beg = ptr[k.s], end = ptr[k.s + 1];
+  if (beg < 0 || end > N || k.row < beg || k.row >= end) return false;
+  k.cnt = end - k.row < 64 ? (int)(end - k.row) : 64;
+  k.first = k.row == beg;
+  return true;
+}
+
+// mmf_readout.hip: the argument check of both readout entries and the launches of the forward that do not read x
+int ro_check(const char* who, int64_t num_chunks, int64_t N, int64_t S, int64_t C, int64_t x_stride);
+int ro_launch_max(const float* gate, const int64_t* ptr, const int32_t* table, int64_t num_chunks, int64_t S, int64_t N, uint32_t* segkey,
+                  int32_t* first_chunk, hipStream_t s);
+int ro_launch_finish(const int64_t* ptr, const int32_t* first_chunk, const uint32_t* segkey, const float* part_u, const float* part_z,
+                     int64_t num_chunks, int64_t S, int64_t C, float* out, float* seg_max, float* seg_sum, hipStream_t s);
+int ro_launch_alpha(const int64_t* ptr, const int32_t* table, int64_t num_chunks, int64_t S, int64_t N, const float* seg_sum, float* alpha,
+                    hipStream_t s);
 
 // ---- mmf_hgconv.hip: the steps of the incidence plan, for the pair plan of mmf_hgpair.hip ------------------------------------------
 constexpr int64_t HG_LIMIT = (int64_t)1 << 31;

@@ -32,6 +32,7 @@
 #include "../../include/ext/mmf_hg_hgconv.h"
 #include "../../include/ext/mmf_hg_readout.h"
 #include "../../include/ext/mmf_hg_hgpair.h"
+#include "../../include/ext/mmf_hg_hg16.h"
 #include "../../include/mmf_hg_wide.h"
 #include "../../include/mmf_hg_wide_seg.h"
 

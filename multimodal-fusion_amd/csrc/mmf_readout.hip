@@ -22,26 +22,8 @@
 namespace mmf {
 
 static_assert(MMF_READOUT_CHUNK == 64, "a chunk is the rows one wave holds a gate of each: the kernels below are written for 64");
-constexpr int RO_BATCH = 8;            // rows whose loads are in flight before their multiply-adds
-constexpr int RO_ROWS = 4;             // backward: rows per lane group in flight
-constexpr int64_t RO_LIMIT = (int64_t)1 << 31;
-
-// the header's scalar definitions (cexp, the float keys) and the dot64 tree: mmf_hgshare.h
-
-// A record of the chunk table, checked against the offsets before anything is addressed with it: a record that does not lie inside
-// its segment (a table that belongs to other offsets) is skipped, it reads and writes nothing.
-struct RoChunk { int s; int64_t row; int cnt; bool first; };
-__device__ __forceinline__ bool ro_chunk(const int32_t* __restrict__ table, const int64_t* __restrict__ ptr, int64_t ch, int64_t S, int64_t N,
-                                         RoChunk& k) {
-  k.s = table[2 * ch];
-  k.row = table[2 * ch + 1];
-  if (k.s < 0 || k.s >= S) return false;
-  const int64_t beg = ptr[k.s], end = ptr[k.s + 1];
-  if (beg < 0 || end > N || k.row < beg || k.row >= end) return false;
-  k.cnt = end - k.row < 64 ? (int)(end - k.row) : 64;
-  k.first = k.row == beg;
-  return true;
-}
+// RO_BATCH, RO_ROWS, RO_LIMIT, the header's scalar definitions (cexp, the float keys), the dot64 tree and the chunk record (RoChunk,
+// ro_chunk): mmf_hgshare.h
 
 // ---- max ------------------------------------------------------------------------------------------------------------------------
 // segkey [S] and first_chunk [S] are zeroed before: key 0 lies below the key of every float
@@ -252,7 +234,7 @@ __global__ __launch_bounds__(256) void ro_backward_kernel(const float* __restric
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-static int ro_check(const char* who, int64_t num_chunks, int64_t N, int64_t S, int64_t C, int64_t x_stride) {
+int ro_check(const char* who, int64_t num_chunks, int64_t N, int64_t S, int64_t C, int64_t x_stride) {
   if (num_chunks < 0 || N < 0 || S < 0 || C < 0) {
     set_error("%s: the chunk count, N, S and C must be >= 0 (got %lld, %lld, %lld, %lld)", who, (long long)num_chunks, (long long)N, (long long)S,
               (long long)C);
@@ -272,6 +254,31 @@ static int ro_check(const char* who, int64_t num_chunks, int64_t N, int64_t S, i
 }
 
 static unsigned ro_wave_grid(int64_t waves) { return (unsigned)((waves + 3) / 4); }
+
+// the launches of the forward around the chunk kernel (mmf_hgshare.h): mmf_attention_readout below and mmf_attention_readout_16
+// (mmf_hg16.hip) enqueue the same
+int ro_launch_max(const float* gate, const int64_t* ptr, const int32_t* table, int64_t num_chunks, int64_t S, int64_t N, uint32_t* segkey,
+                  int32_t* first_chunk, hipStream_t s) {
+  hipLaunchKernelGGL(ro_max_kernel, dim3(ro_wave_grid(num_chunks)), dim3(256), 0, s, gate, ptr, table, num_chunks, S, N, segkey, first_chunk);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
+int ro_launch_finish(const int64_t* ptr, const int32_t* first_chunk, const uint32_t* segkey, const float* part_u, const float* part_z,
+                     int64_t num_chunks, int64_t S, int64_t C, float* out, float* seg_max, float* seg_sum, hipStream_t s) {
+  const int64_t threads = S * (C > 0 ? C : 1);
+  hipLaunchKernelGGL(ro_finish_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ptr, first_chunk, segkey, part_u, part_z,
+                     num_chunks, S, (int)C, out, seg_max, seg_sum);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
+
+int ro_launch_alpha(const int64_t* ptr, const int32_t* table, int64_t num_chunks, int64_t S, int64_t N, const float* seg_sum, float* alpha,
+                    hipStream_t s) {
+  hipLaunchKernelGGL(ro_alpha_kernel, dim3(ro_wave_grid(num_chunks)), dim3(256), 0, s, ptr, table, num_chunks, S, N, seg_sum, alpha);
+  MMF_LAUNCH_CHECK();
+  return MMF_OK;
+}
 
 }  // namespace mmf
 
@@ -321,9 +328,7 @@ int mmf_attention_readout(const float* x, int64_t x_stride, const float* gate, c
   int32_t* first_chunk = reinterpret_cast<int32_t*>(segkey + S);
   MMF_HIP(hipMemsetAsync(segkey, 0, 2 * (size_t)S * 4, s));
   if (num_chunks > 0) {
-    hipLaunchKernelGGL(ro_max_kernel, dim3(ro_wave_grid(num_chunks)), dim3(256), 0, s, gate, ptr_dev, table_dev, num_chunks, S, N, segkey,
-                       first_chunk);
-    MMF_LAUNCH_CHECK();
+    MMF_TRY(ro_launch_max(gate, ptr_dev, table_dev, num_chunks, S, N, segkey, first_chunk, s));
     const bool vec = C % 4 == 0 && x_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
     const int64_t units = vec ? C / 4 : C;
     int lg = 0;
@@ -340,14 +345,8 @@ int mmf_attention_readout(const float* x, int64_t x_stride, const float* gate, c
     }
     MMF_LAUNCH_CHECK();
   }
-  const int64_t threads = S * (C > 0 ? C : 1);
-  hipLaunchKernelGGL(ro_finish_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ptr_dev, first_chunk, segkey, part_u, part_z,
-                     num_chunks, S, (int)C, out, seg_max, seg_sum);
-  MMF_LAUNCH_CHECK();
-  if (num_chunks > 0) {
-    hipLaunchKernelGGL(ro_alpha_kernel, dim3(ro_wave_grid(num_chunks)), dim3(256), 0, s, ptr_dev, table_dev, num_chunks, S, N, seg_sum, alpha);
-    MMF_LAUNCH_CHECK();
-  }
+  MMF_TRY(ro_launch_finish(ptr_dev, first_chunk, segkey, part_u, part_z, num_chunks, S, C, out, seg_max, seg_sum, s));
+  if (num_chunks > 0) MMF_TRY(ro_launch_alpha(ptr_dev, table_dev, num_chunks, S, N, seg_sum, alpha, s));
   return MMF_OK;
 }
 

@@ -82,6 +82,9 @@ def _check_weight(w, num_edges: Optional[int], dev: torch.device, what: str) -> 
         raise ValueError(f"{what}: hyperedge_weight is on {w.device}, edge_index on {dev}")
 
 
+check_weight = _check_weight          # for hg16, which runs the same checks
+
+
 def plan_arguments(edge_index, num_nodes, num_edges, hyperedge_weight, what: str):
     """The checks of a plan build, before any device work, and its sizes: (N, M, E, contiguous hyperedge_weight or None).
     ``num_edges=None`` costs the one host read of max + 1."""
@@ -252,6 +255,12 @@ class HypergraphConv(torch.nn.Module):
         if hyperedge_attr is not None:
             raise NotImplementedError("HypergraphConv: hyperedge_attr belongs to the attention mode, which is not implemented")
         h = self.lin(x)
+        if h.dtype in (torch.float16, torch.bfloat16):                       # autocast: the 16-bit kernels, the bias inside
+            from . import hg16
+            bias = None if self.bias is None else self.bias.float()           # a module cast as a whole: its bias is widened
+            if plan is not None:
+                return hg16.hypergraph_propagate_16(h, plan=plan, bias=bias)
+            return hg16.hypergraph_propagate_16(h, hyperedge_index, num_edges=num_edges, hyperedge_weight=hyperedge_weight, bias=bias)
         if plan is not None:
             out = hypergraph_propagate(h, plan=plan)
         else:

@@ -83,6 +83,9 @@ def _check_pairs(t, name: str, plan: IncidencePlan, what: str) -> None:
         raise ValueError(f"{what}: {name} is on {t.device}, the plan on {plan.device}")
 
 
+check_pair_plan, check_pairs = _check_pair_plan, _check_pairs          # for hg16, which runs the same checks
+
+
 def _check_x(x, plan: IncidencePlan, what: str) -> None:
     if not isinstance(x, torch.Tensor) or x.dim() != 2:
         raise ValueError(f"{what}: x must be a float32 tensor [N, C]")
@@ -282,7 +285,12 @@ class PairWeightedHypergraphConv(torch.nn.Module):
         if pair_weight is None:
             raise ValueError(f"{what}: pair_weight is required (one value per column of hyperedge_index)")
         plan = _plan_for(plan, hyperedge_index, x.shape[0], num_edges, hyperedge_weight, what)
-        out = hypergraph_propagate_pairs(self.lin(x), pair_weight, plan=plan, normalization=self.normalization)
+        h = self.lin(x)
+        if h.dtype in (torch.float16, torch.bfloat16):                       # autocast: the 16-bit kernels, the bias inside
+            from . import hg16
+            bias = None if self.bias is None else self.bias.float()           # a module cast as a whole: its bias is widened
+            return hg16.hypergraph_propagate_pairs_16(h, pair_weight, plan=plan, normalization=self.normalization, bias=bias)
+        out = hypergraph_propagate_pairs(h, pair_weight, plan=plan, normalization=self.normalization)
         return out if self.bias is None else out + self.bias
 
     def __repr__(self) -> str:
@@ -348,6 +356,8 @@ class HypergraphAttentionConv(torch.nn.Module):
         e = hyperedge_index[1].clamp(0, max(M - 1, 0))
         score = torch.nn.functional.leaky_relu(sx[v] + se[e], self.negative_slope)        # [E, H]
         group = "edge" if self.attention_mode == "node" else "node"
+        if xh.dtype in (torch.float16, torch.bfloat16):
+            return self._forward_16(xh, score.float(), plan, group)            # the scores are widened: the softmax stays float32
         outs = []
         for h in range(H):
             alpha = pair_softmax(score[:, h].contiguous(), plan=plan, group=group)
@@ -355,6 +365,22 @@ class HypergraphAttentionConv(torch.nn.Module):
             outs.append(hypergraph_propagate_pairs(xh[:, h], alpha, plan=plan, normalization="count"))
         out = torch.cat(outs, dim=1) if self.concat else torch.stack(outs, dim=0).mean(0)
         return out if self.bias is None else out + self.bias
+
+    def _forward_16(self, xh: torch.Tensor, score: torch.Tensor, plan: IncidencePairPlan, group: str) -> torch.Tensor:
+        """The heads of a 16-bit ``xh`` [N, H, F] under float32 scores [E, H]; the result keeps xh's dtype.  Concatenated heads take
+        their slice of the bias inside the kernel; averaged heads are averaged in float32, biased, and rounded once."""
+        from . import hg16
+        H, F = self.heads, self.out_channels
+        outs = []
+        for h in range(H):
+            alpha = pair_softmax(score[:, h].contiguous(), plan=plan, group=group)
+            alpha = torch.nn.functional.dropout(alpha, p=self.dropout, training=self.training)
+            bias = self.bias[h * F:(h + 1) * F].float() if self.concat and self.bias is not None else None
+            outs.append(hg16.hypergraph_propagate_pairs_16(xh[:, h], alpha, plan=plan, normalization="count", bias=bias))
+        if self.concat:
+            return torch.cat(outs, dim=1)
+        out = torch.stack(outs, dim=0).float().mean(0)
+        return (out if self.bias is None else out + self.bias).to(xh.dtype)
 
     def __repr__(self) -> str:
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads}, attention_mode={self.attention_mode!r})"

@@ -187,6 +187,9 @@ class GlobalAttention(torch.nn.Module):
                 return_attention: bool = False):
         gate = self.gate_nn(x)
         h = self.nn(x) if self.nn is not None else x
+        if h.dtype in (torch.float16, torch.bfloat16):                       # autocast: the 16-bit kernels; the token stays float32
+            from . import hg16
+            return hg16.attention_readout_16(h, gate, ptr=ptr, batch=batch, plan=plan, size=size, return_attention=return_attention)
         return attention_readout(h, gate, ptr=ptr, batch=batch, plan=plan, size=size, return_attention=return_attention)
 
     def __repr__(self) -> str:
